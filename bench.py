@@ -41,7 +41,7 @@ def usable_cpus():
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=_positive_int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--views-per-gpu", type=int, default=64)
     ap.add_argument("--segments", type=int, default=2000)
@@ -57,7 +57,73 @@ def parse():
                          "`segments` = l3d_shard_chain_partition (source segments sharded, exact on every scene), `blocks` = l3d_match_chain_partition (views sharded, "
                          "speculated + verified).  A step is the partitioned matchViews of every rank; the chain scratch is kept between steps (L3D_PART_RELEASE=0: "
                          "a one-shot job releases it).  Works at --gpus 1 too (a communicator of one rank).")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (matchViews' products) as DIR/<name>.npy, float32 / float64, "
+                         "at most 64 MB in all: two builds run with the same arguments can be compared output for output")
     return ap.parse_args()
+
+
+def _positive_int(text):
+    v = int(text)
+    if v < 1:
+        raise argparse.ArgumentTypeError("must be at least 1")
+    return v
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def match_products(l3d):
+    """matchViews' device-resident products, copied to the host: dict(seg_base, pot_start, pot_tgt, best), or None when the run's path keeps
+    none.  Line3D.resident_products without the hypothesis table: that belongs to finish, and a finish before the timed steps (the cold
+    measurement) leaves its hypothesis count behind although matchViews has since dropped the table."""
+    import ctypes as C
+    from line3d_amd.capi import MATCH_DTYPE, _p
+    nv, nd, nh = C.c_int(0), C.c_int(0), C.c_int(0)
+    npot = C.c_int64(0)
+    l3d._chk(l3d.lib.l3d_line3d_products_sizes(l3d.h, C.byref(nv), C.byref(nd), C.byref(npot), C.byref(nh)))
+    if nv.value == 0:
+        return None
+    seg_base = np.zeros(nv.value + 1, np.int32)
+    pot_start = np.zeros(nd.value + 1, np.int64)
+    pot_tgt = np.zeros(max(1, npot.value), np.int32)
+    best = np.zeros(nd.value, MATCH_DTYPE)
+    l3d._chk(l3d.lib.l3d_line3d_products_get(l3d.h, _p(seg_base), _p(pot_start), _p(pot_tgt), _p(best), None, None))
+    return dict(seg_base=seg_base, pot_start=pot_start, pot_tgt=pot_tgt[:npot.value], best=best)
+
+
+def dump_outputs(out_dir, products, st):
+    """matchViews' products (match_products) as float .npy files: integer fields as float64 (exact below 2**53), float fields as
+    they are.  Over DUMP_LIMIT_BYTES the long arrays are cut to a fixed, seeded sample of rows (the same rows for the same lengths, so two
+    runs of the same scene pick the same rows), and `<name>.rows.npy` holds the row indices taken.  Returns a summary for the result line."""
+    if products is None:
+        raise RuntimeError("--dump-outputs: this run's matchViews path keeps no device-resident products to dump")
+    arrays = {"seg_base": products["seg_base"], "pot_start": products["pot_start"], "pot_tgt": products["pot_tgt"]}
+    best = products["best"]
+    for f in best.dtype.names:
+        arrays["best_" + f] = best[f]
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32 if v.dtype.kind == "f" and v.dtype.itemsize == 4 else np.float64) for k, v in arrays.items()}
+    arrays["counts_pairs_raw_kept"] = np.array([st["pairs"], st["raw"], st["kept"]], dtype=np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    sampled = {}
+    if total > DUMP_LIMIT_BYTES:
+        # short arrays stay whole; every long one keeps the same fraction of its rows (+ 8 B per kept row for its row index)
+        long_ = [k for k, a in arrays.items() if len(a) > 65536]
+        fixed = sum(a.nbytes for k, a in arrays.items() if k not in long_)
+        frac = 0.99 * (DUMP_LIMIT_BYTES - fixed) / sum(arrays[k].nbytes + 8 * len(arrays[k]) for k in long_)
+        for k in long_:
+            n = len(arrays[k])
+            m = max(1, int(n * frac))
+            rows = np.sort(np.random.default_rng(12345).choice(n, size=m, replace=False))
+            arrays[k] = np.ascontiguousarray(arrays[k][rows])
+            arrays[k + ".rows"] = rows.astype(np.float64)
+            sampled[k] = [m, n]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return dict(dir=out_dir, files=len(arrays), bytes=int(sum(a.nbytes for a in arrays.values())), sampled_rows=sampled or None,
+                what="matchViews' products after the last timed step: per-view segment bases, potential correspondences (start, target), "
+                     "each segment's best match; pairs / raw candidates / kept matches of the step")
 
 
 def cpu_baseline(scene, n_neighbors, sample_segments, lists=None):
@@ -369,6 +435,7 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     st = l3d.stats()
+    products = match_products(l3d) if (args.dump_outputs and rank == 0) else None     # (after the clock stopped)
     prof = {} if (args.no_profile or dominant is None) else {dominant: ctx.profile_get(dominant)}
     ctx.profile_enable(False)
     ctx.profile_only(None)
@@ -491,6 +558,8 @@ def main():
                    views_per_s=V * args.steps / dt, pairs_per_step=pairs_total, raw_candidates_per_step=raw_total,
                    kept_per_step=st["kept"], setup_s=t_setup, cold=cold,
                    host_split_s=dict(gpu_call=st["t_gpu_call"], commit=st["t_commit"], finalize=st["t_finalize"], match=st["t_match"]))
+        if args.dump_outputs:
+            out["dump_outputs"] = dump_outputs(args.dump_outputs, products, st)
         if roof:
             out["roofline"] = roof
             km = roof["kernels_ms"]
