@@ -34,7 +34,7 @@ namespace l3d {
 Options options_from_env()
 {
     Options o;
-#define X(field, env, def, doc) if (kCrossChecks || !option_is_crosscheck(env)) if (const char* e = getenv(env)) o.field = (*e == 0) ? 1 : atoi(e);
+#define X(field, env, def, doc) if ((kCrossChecks || !option_is_crosscheck(env)) && !option_is_set_only(env)) if (const char* e = getenv(env)) o.field = (*e == 0) ? 1 : atoi(e);
     L3D_OPTION_TABLE(X)
 #undef X
     return o;
@@ -57,18 +57,8 @@ int l3d_ctx_create(int device, l3d_ctx** out)
     c->opt = options_from_env();                  // the one place the environment is read
     c->ch_pin_res.flags = hipHostMallocCoherent;  // result records: written by kernels, read by the host behind unfenced events (l3d_ctx.hpp: get_local_event)
     publish_tunables(c->opt);
-    c->chain_ring = c->opt.chain_ring != 0;
     c->wedge_pretest = c->opt.pretest & 7;         // diagnostic: stage-1 filter mask
-    {   // L3D_STREAM_PRIO=1: the chain's stream (per-view critical path) at the highest priority.  Measured on config 2: no
-        // difference to plain streams (21.5 ms either way), so plain streams are the default.
-        int least = 0, greatest = 0;
-        (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-        const bool prio = c->opt.stream_prio == 1;
-        if (!prio || hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, greatest) != hipSuccess) {
-            (void)hipGetLastError();
-            if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return L3D_ERR_HIP; }
-        }
-    }
+    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return L3D_ERR_HIP; }
     if (hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking) != hipSuccess) { (void)hipStreamDestroy(c->stream); delete c; return L3D_ERR_HIP; }
     if (hipStreamCreateWithFlags(&c->stage1_stream, hipStreamNonBlocking) != hipSuccess) {
         (void)hipStreamDestroy(c->copy_stream); (void)hipStreamDestroy(c->stream); delete c; return L3D_ERR_HIP;
@@ -85,7 +75,6 @@ int l3d_set_option(l3d_ctx* c, const char* name, int value)
     if (!f) return fail(c, L3D_ERR_INVALID, std::string("l3d_set_option: unknown option ") + (name ? name : "(null)"));
     *f = value;
     publish_tunables(c->opt);
-    c->chain_ring = c->opt.chain_ring != 0;
     c->wedge_pretest = c->opt.pretest & 7;        // (l3d_set_pair_pretest writes opt.pretest too: setting another option does not reset its mask)
     return L3D_OK;
 }
@@ -94,7 +83,6 @@ int l3d_get_option(l3d_ctx* c, const char* name, int* value)
 {
     if (!c || !value) return L3D_ERR_INVALID;
     if (name && strcmp(name, "crosschecks") == 0) { *value = kCrossChecks ? 1 : 0; return L3D_OK; }     // (which build this is)
-    if (name && strcmp(name, "shard_graph_launches") == 0) { *value = (int)std::min<long long>(c->shard_graph_launches, 0x7fffffff); return L3D_OK; }   // (a counter, not a switch)
     int* f = option_field(c->opt, name);
     if (!f) return fail(c, L3D_ERR_INVALID, std::string("l3d_get_option: unknown option ") + (name ? name : "(null)"));
     *value = *f;
@@ -149,14 +137,11 @@ void l3d_ctx_destroy(l3d_ctx* c)
                        &c->ch_rays, &c->aff_hyp, &c->aff_first, &c->aff_pass_pairs, &c->aff_pass_w, &c->aff_l2g, &c->edges_keep, &c->g0, &c->g1, &c->g2, &c->g3, &c->g4, &c->g5, &c->g6, &c->g7 };
     for (auto* b : bufs) b->release();
     c->ch_bestpos.release(); c->ch_hdr.release();
-    for (auto& g : c->shard_graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
-    c->shard_graphs.clear();
     c->products.release();
     c->pin_tab.release(); c->pin_ex.release(); c->pin_scal.release(); c->pin_best.release(); c->pin_kept.release();
     c->ch_pin_tables.release(); c->ch_pin_res.release(); c->ch_pin_kept.release(); c->ch_pin_best.release(); c->pin_arena.release();
     for (auto& kv : c->resident) if (!c->resident_arena_of.count(kv.first)) (void)hipFree(kv.second.first);
     for (auto& a : c->resident_arenas) if (a.first) (void)hipFree(a.first);
-    if (c->mask_stream) (void)hipStreamDestroy(c->mask_stream);
     if (c->prod_stream) (void)hipStreamDestroy(c->prod_stream);
     (void)hipStreamDestroy(c->stage1_stream);
     (void)hipStreamDestroy(c->copy_stream);

@@ -78,9 +78,8 @@ __global__ void k_exist_count(const Match* __restrict__ arena, const unsigned* _
 // g (a power of two) lanes share a run.
 // (round 6, late) NO GLOBAL ATOMICS: 2 M scattered atomicAdds per view -- every one on its own 64-byte line, the rows being N x 4 bytes apart -- ran at
 // 14 G/s whatever fed them (144 us per view at 40 x 4000 x 24, with or without the run tables).  A source's segments are cut into kExistChunks chunks; a
-// workgroup per (chunk, source) counts its runs' targets in LDS and leaves its S counters in `part`; k_exist_combine turns every (source, target segment)'s
-// chunk counts into chunk BASES (exclusive sums, in place) and stores the row count; k_place_rt's scatter workgroups -- one per (chunk, source) again -- start
-// their LDS cursors at row start + chunk base and place their records without a global cursor.
+// workgroup per (chunk, source) counts its runs' targets in LDS and leaves its S counters in `part`; k_exist_combine sums every (source, target segment)'s
+// chunk counts into the row count (and leaves the chunk bases, exclusive sums, in `part`).
 constexpr int kExistChunks = 16;
 constexpr int kExistThreads = 1024;         // (sixteen waves per (chunk, source): a workgroup's critical path is its runs / waves dependent load pairs)
 __global__ __launch_bounds__(kExistThreads) void k_exist_count_rt(const unsigned* __restrict__ qt_arena, const RtInfo* __restrict__ info, const ChainResult* __restrict__ res,
@@ -124,26 +123,6 @@ __global__ void k_cams_of_records(const Match* __restrict__ arena, long long n, 
     if (i < n) cams[i] = arena[i].camID2;
 }
 
-__global__ void k_exist_scatter(const Match* __restrict__ arena, const ChainResult* __restrict__ res, const int* __restrict__ src_index,
-                                const int* __restrict__ src_cam, unsigned view_id, int N, int S, const int* __restrict__ row_start,
-                                int* __restrict__ cursor, uint2* __restrict__ meta, float4* __restrict__ depths, int cap)
-{
-    if (row_start[(size_t)S * N] > cap) return;
-    const ChainResult* src = res + src_index[blockIdx.y];
-    const int cam = src_cam[blockIdx.y];
-    const int n = src->n_kept;
-    const Match* kept = arena + src->kept_base;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const Match r = kept[i];
-        if (r.camID2 == view_id && (int)r.segID2 < S) {
-            const int row = r.segID2 * N + cam;
-            const int slot = row_start[row] + atomicAdd(&cursor[row], 1);
-            meta[slot] = make_uint2(r.segID1, (unsigned)cam);
-            depths[slot] = make_float4(r.depths[2], r.depths[3], r.depths[0], r.depths[1]);
-        }
-    }
-}
-
 // The scatter order inside a (segment, camera) run is arbitrary.  One wave per run restores the (segment, camera,
 // target) order of the reference's list sort: every lane holds up to four entries in registers, ranks them by
 // counting (keys are broadcast with shuffles, target ids inside a run are distinct) and writes them to their place.
@@ -166,7 +145,7 @@ __global__ __launch_bounds__(256) void k_exist_sort_runs(const int* __restrict__
 // chain's critical path.  One wave per row (the first workgroups of k_place).
 // Both writers of the combined candidate arrays in one launch (independent: stage-1 candidates go to the rows of the cameras
 // to be matched, reverse matches to the rows of the source cameras): the first `blocks_move` workgroups move the stage-1 rows, the
-// others scatter the reverse matches (as k_exist_scatter, 32 workgroups per source view).
+// others scatter the reverse matches (bps workgroups per source view).
 __global__ __launch_bounds__(256) void k_place(int blocks_move, int bps, const int* __restrict__ tbm, int n_tbm, const int* __restrict__ rowA,
                                                const uint2* __restrict__ metaA, const float4* __restrict__ depthsA,
                                                const Match* __restrict__ arena, const unsigned* __restrict__ cams, const ChainResult* __restrict__ res, const int* __restrict__ src_index,
@@ -216,7 +195,7 @@ __global__ __launch_bounds__(256) void k_place(int blocks_move, int bps, const i
 }
 // k_place with run tables (default): the stage-1 rows are moved as in k_place, the reverse matches come from the sources' runs towards this view through the
 // global row cursors -- 6000 small workgroups in one launch with the move: faster than 192 (or 768) big ones with LDS cursors in a launch of their own
-// (cand_move 12.0 against 17.1 / 13.2 ms at 40 x 4000 x 24, NOTEBOOK 12.f)
+// (cand_move 12.0 against 17.1 / 13.2 ms at 40 x 4000 x 24, NOTEBOOK 12.f; the LDS-cursor variant is retired)
 __global__ __launch_bounds__(256) void k_place_rt(int blocks_move, int bps, const int* __restrict__ tbm, int n_tbm, const int* __restrict__ rowA,
                                                   const uint2* __restrict__ metaA, const float4* __restrict__ depthsA,
                                                   const Match* __restrict__ arena, const ChainResult* __restrict__ res, const int* __restrict__ src_index,
@@ -254,60 +233,6 @@ __global__ __launch_bounds__(256) void k_place_rt(int blocks_move, int bps, cons
         }
     }
 }
-// (A/B, option rt_place_lds) k_place with run tables: the stage-1 rows are moved by k_place itself (launched without sources); the reverse matches by a launch of their own -- one workgroup
-// of kExistThreads per (chunk, source), LDS cursors from the row starts and the chunk bases of k_exist_combine: no global cursor, no global atomic
-__global__ __launch_bounds__(kExistThreads) void k_place_scatter_rt(const Match* __restrict__ arena, const ChainResult* __restrict__ res, const int* __restrict__ src_index,
-                                                                    const int* __restrict__ src_cam, int N, int S, const int* __restrict__ row_start,
-                                                                    uint2* __restrict__ meta, float4* __restrict__ depths, int cap,
-                                                                    const RtInfo* __restrict__ info, const int* __restrict__ src_slot, int g, const int* __restrict__ part)
-{
-    extern __shared__ int s_cur[];
-    if (row_start[(size_t)S * N] > cap) return;
-    const int sj = blockIdx.y, bx = blockIdx.x;
-    const int si = src_index[sj], cam = src_cam[sj], slot = src_slot[sj];
-    const RtInfo w = info[si];
-    if (!w.rt || slot < 0 || res[si].n_kept == 0) return;
-    const int* base = part + ((size_t)sj * kExistChunks + bx) * S;
-    for (int u = threadIdx.x; u < S; u += kExistThreads) s_cur[u] = row_start[u * N + cam] + base[u];
-    __syncthreads();
-    const Match* kept = arena + res[si].kept_base;
-    const int* r0 = w.rt + (size_t)slot * w.S;
-    const int* r1 = r0 + w.S;
-    const int s_lo = (int)(((long long)w.S * bx) / kExistChunks), s_hi = (int)(((long long)w.S * (bx + 1)) / kExistChunks);
-    const int grp = threadIdx.x / g, gl = threadIdx.x - grp * g, ngrp = kExistThreads / g;
-    for (int sg = s_lo + grp; sg < s_hi; sg += ngrp) {
-        const int a = r0[sg], b = r1[sg];
-        for (int i = a + gl; i < b; i += g) {
-            const Match r = kept[i];
-            if ((int)r.segID2 < S) {
-                const int sl = atomicAdd(&s_cur[r.segID2], 1);
-                meta[sl] = make_uint2(r.segID1, (unsigned)cam);
-                depths[sl] = make_float4(r.depths[2], r.depths[3], r.depths[0], r.depths[1]);
-            }
-        }
-    }
-}
-
-// raw candidate total and the largest per-segment count of one view's segment range (phase 1 statistics), by one
-// workgroup; out2 = {total, max} lives in host-mapped pinned memory: no copy, the host reads it after the stage-1 event
-__global__ __launch_bounds__(1024) void k_raw_stats(const int* __restrict__ rowcnt, int N, int seg_begin, int seg_end, int* __restrict__ out2)
-{
-    __shared__ int s_t[16], s_m[16];
-    int tot = 0, mx = 0;
-    for (int s = seg_begin + (int)threadIdx.x; s < seg_end; s += 1024) {
-        int c = 0;
-        for (int k = 0; k < N; ++k) c += rowcnt[s * N + k];
-        tot += c; mx = max(mx, c);
-    }
-    for (int o = 32; o > 0; o >>= 1) { tot += __shfl_down(tot, o); mx = max(mx, __shfl_down(mx, o)); }
-    if ((threadIdx.x & 63) == 0) { s_t[threadIdx.x >> 6] = tot; s_m[threadIdx.x >> 6] = mx; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 16; ++w) { tot += s_t[w]; mx = max(mx, s_m[w]); }
-        out2[0] = tot; out2[1] = mx;
-    }
-}
-
 // Kept records of a view into its slice of the arena, in ONE launch behind the verification: each workgroup (one segment) sums
 // the kept counts in front of its segment itself (at most a few thousand ints out of L2) instead of waiting for a scan
 // launch, and the slice starts where the previous verified view's ended (its result record) -- no cursor, no atomics.
@@ -348,11 +273,6 @@ void launch_exist_count(const Match* arena, const ChainResult* res, const int* s
 {
     if (n_src > 0) hipLaunchKernelGGL(k_exist_count, dim3(std::max(1, bps), n_src), dim3(256), 0, st, arena, cams, res, src_index, src_cam, view_id, N, S, rowcnt);
 }
-void launch_exist_scatter(const Match* arena, const ChainResult* res, const int* src_index, const int* src_cam, int n_src, unsigned view_id,
-                          int N, int S, const int* row_start, int* cursor, uint2* meta, float4* depths, int cap, hipStream_t st)
-{
-    if (n_src > 0) hipLaunchKernelGGL(k_exist_scatter, dim3(32, n_src), dim3(256), 0, st, arena, res, src_index, src_cam, view_id, N, S, row_start, cursor, meta, depths, cap);
-}
 void launch_exist_sort_runs(const int* cams, int n_cams, int N, int S, const int* row_start, uint2* meta, float4* depths, int cap, hipStream_t st,
                             int seg_begin, int seg_end, float* stage, long long stage_stride, unsigned* stage_key)
 {
@@ -363,18 +283,12 @@ void launch_exist_sort_runs(const int* cams, int n_cams, int N, int S, const int
 void launch_place(const int* tbm, int n_tbm, int N, int S, const int* rowA, const uint2* metaA, const float4* depthsA,
                   const Match* arena, const ChainResult* res, const int* src_index, const int* src_cam, int n_src, unsigned view_id,
                   const int* row_start, int* cursor, int cand_cap, uint2* meta, float4* depths, hipStream_t st, const unsigned* cams, int bps,
-                  const RtInfo* info, const int* src_slot, int g, const int* part)
+                  const RtInfo* info, const int* src_slot, int g)
 {
     bps = std::max(1, bps);
     const int blocks_move = (S * n_tbm + 3) / 4;
     const int blocks = blocks_move + bps * n_src;
-    if (info && part) {     // (option rt_place_lds, A/B) the move by k_place without sources, the scatter by kExistChunks workgroups per source with LDS cursors of S ints
-        if (blocks_move > 0) hipLaunchKernelGGL(k_place, dim3(blocks_move), dim3(256), 0, st, blocks_move, 1, tbm, n_tbm, rowA, metaA, depthsA, arena, (const unsigned*)nullptr, res, src_index, src_cam,
-                                                view_id, N, S, row_start, cursor, meta, depths, cand_cap);
-        if (n_src > 0 && S > 0) hipLaunchKernelGGL(k_place_scatter_rt, dim3(kExistChunks, n_src), dim3(kExistThreads), (size_t)S * 4, st, arena, res, src_index, src_cam, N, S, row_start, meta, depths,
-                                                   cand_cap, info, src_slot, std::max(1, g), part);
-    }
-    else if (info) { if (blocks > 0) hipLaunchKernelGGL(k_place_rt, dim3(blocks), dim3(256), 0, st, blocks_move, bps, tbm, n_tbm, rowA, metaA, depthsA, arena, res, src_index, src_cam,
+    if (info) { if (blocks > 0) hipLaunchKernelGGL(k_place_rt, dim3(blocks), dim3(256), 0, st, blocks_move, bps, tbm, n_tbm, rowA, metaA, depthsA, arena, res, src_index, src_cam,
                                                          N, S, row_start, cursor, meta, depths, cand_cap, info, src_slot, std::max(1, g)); }
     else if (blocks > 0) hipLaunchKernelGGL(k_place, dim3(blocks), dim3(256), 0, st, blocks_move, bps, tbm, n_tbm, rowA, metaA, depthsA, arena, cams, res, src_index, src_cam,
                                             view_id, N, S, row_start, cursor, meta, depths, cand_cap);
@@ -387,10 +301,6 @@ void launch_exist_count_rt(const unsigned* qt_arena, const RtInfo* info, const C
     hipLaunchKernelGGL(k_exist_combine, dim3((S + 255) / 256, n_src), dim3(256), 0, st, part, src_cam, N, S, rowcnt);
 }
 int exist_chunks() { return kExistChunks; }
-void launch_raw_stats(const int* rowcnt, int N, int seg_begin, int seg_end, int* out2_host, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_raw_stats, dim3(1), dim3(1024), 0, st, rowcnt, N, seg_begin, seg_end, out2_host);
-}
 void launch_kept_write_chain(const VerifyArgs& a, const int* kept_cnt, int nrow, const ChainResult* prev, unsigned long long arena_cap, ChainResult* res,
                              ChainResult* res_host, const unsigned* l2g, Match* arena, hipStream_t st, int* best_pos, unsigned* cams, int* rt, int rt_stride)
 {
@@ -442,26 +352,22 @@ static int run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_c
     hipStream_t s1 = c->stage1_stream;  // stage 1 runs ahead here, concurrently with the latency-bound kernels of phase 2
     const bool serial = c->opt.chain_serial != 0;   // diagnostic: one stream, kernels one at a time (isolated durations)
     if (serial) s1 = st;
-    // option mask_stream: k_pair_mask of view k+1 next to k_pair_fill of view k instead of behind it
-    hipStream_t sm = s1;
-    if (c->opt.mask_stream && !serial) {
-        if (!c->mask_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->mask_stream, hipStreamNonBlocking));
-        sm = c->mask_stream;
-    }
     (void)hipGetLastError();            // errors of earlier, already reported calls are not ours
 
     // ---- validation, table layout and upload, per-view slices of the whole-run arenas (l3d_chain_common.hip: shared with the sharded chain)
     std::vector<ViewDev> vd;
     ChainLayout L;
     if (int rc = chain_plan_views(c, views, n_views, 0, 1, vd, L, "l3d_match_chain")) return rc;
-    const bool rays_env = c->opt.tgt_rays != 0;      // (0: k_pair_fill normalises per candidate, A/B)
-    if (int rc = chain_upload_tables(c, views, n_views, vd, L, rays_env, st)) return rc;
-    // bit rows: a ring that covers every view between the one being collected and the newest stage 1 (kRing below: after a capacity
-    // overflow the candidates of all of them are re-formed from their bit rows)
+    if (int rc = chain_upload_tables(c, views, n_views, vd, L, st)) return rc;
+    // run-ahead depths, A/B measured on one box (ms per config-2 pass): (12, 24) 19.1, (6, 12) 18.7, (4, 8) 18.4, (2, 4) 18.3,
+    // (24, 40) 20.0 -- a shallow queue keeps the stage-1 candidates of a view cache-warm until its chain consumes them
+    // the ring covers every view that can be in flight between the one being collected and the newest stage 1: after an
+    // overflow ALL of them are refilled before any of their chains runs again (bit rows and stage-1 candidates alike)
+    const int kAhead = L3D_AHEAD, kStage1Ahead = L3D_S1AHEAD, kRing = kAhead + kStage1Ahead + 3;
     // run tables (round 6): the kept writer fills one per view and packs (local camera, target) into the side array; later views and the products
     // read runs instead of scanning lists.  L3D_RUN_TABLES=0 / L3D_KEPT_CAMS=0: the A/B paths (side array of global camera ids / none)
-    const bool use_rt = c->opt.run_tables != 0 && c->opt.kept_cams != 0 && c->chain_ring != 0;
-    if (int rc = chain_assign_arenas(c, views, n_views, vd, L, true, true, c->chain_ring != 0 ? L3D_AHEAD + L3D_S1AHEAD + 3 : 0, st, use_rt)) return rc;
+    const bool use_rt = c->opt.run_tables != 0 && c->opt.kept_cams != 0;
+    if (int rc = chain_assign_arenas(c, views, n_views, vd, L, true, true, kRing, st, use_rt)) return rc;
     if (use_rt) {
         std::vector<RtInfo>& info = c->rtinfo_host;     // (lives in the context: the upload is asynchronous)
         info.resize((size_t)n_views);
@@ -493,7 +399,6 @@ static int run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_c
         hipEvent_t ready = get_local_event(c);
         HIPCHK(c, hipEventRecord(ready, st));
         HIPCHK(c, hipStreamWaitEvent(s1, ready, 0));
-        if (sm != s1) HIPCHK(c, hipStreamWaitEvent(sm, ready, 0));
         put_local_event(c, ready);
     }
     // per-view results are written by the kernels straight into host-mapped pinned memory (no copy operations on the streams)
@@ -503,21 +408,15 @@ static int run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_c
     ChainResult* hres_dev = nullptr;
     HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&hres_dev), hres, 0));
     int* hstats_dev = reinterpret_cast<int*>(reinterpret_cast<unsigned char*>(hres_dev) + (size_t)n_views * sizeof(ChainResult));
-    // the four depths of a stage-1 pair are triangulated once, by k_pair_fill (ring scheme only: the fill runs ahead, its true row counts
-    // are in place before the chain counts the view's reverse matches on top); L3D_DEPTH_IN_FILL=0: A/B, k_pair_mask triangulates too
-    const bool depth_in_fill_env = c->opt.depth_in_fill != 0;
-    const bool depth_in_fill = depth_in_fill_env && c->chain_ring != 0;
-    auto pair_args = [&](int k) {
-        PairArgs pa = chain_pair_args(c, views[k], vd[(size_t)k], dtab);
-        pa.depth_in_fill = depth_in_fill ? 1 : 0;
-        return pa;
-    };
+    // (the four depths of a stage-1 pair are triangulated once, by k_pair_fill: it runs ahead on the stage-1 stream, its true row counts are in place
+    // before the chain counts the view's reverse matches on top)
+    auto pair_args = [&](int k) { return chain_pair_args(c, views[k], vd[(size_t)k], dtab); };
 
     { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return fail(c, L3D_ERR_HIP, std::string("chain setup: ") + hipGetErrorString(e_)); }
     // ---- phase 1 (stage 1 of a view: pair test -> bit rows -> row counts -> statistics) is independent of the
     // chain; it is enqueued a window ahead of phase 2 so that the GPU always has work while the host trails behind
     const double pairs = L.pairs, max_pairs = L.max_pairs;
-    std::vector<hipEvent_t> ev1((size_t)n_views, nullptr), evm((size_t)n_views, nullptr);
+    std::vector<hipEvent_t> ev1((size_t)n_views, nullptr);
     int k_p1 = 0;                       // next view whose stage 1 is enqueued
     c->stats[0] = pairs;
     double raw_sum = 0;
@@ -532,11 +431,6 @@ static int run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_c
     size_t arena_cap = (size_t)(pairs * 0.004) + 1048576;
     std::vector<hipEvent_t> ev((size_t)n_views, nullptr);
     int k_enq = 0;                      // next view whose phase 2 is enqueued
-    // run-ahead depths, A/B measured on one box (ms per config-2 pass): (12, 24) 19.1, (6, 12) 18.7, (4, 8) 18.4, (2, 4) 18.3,
-    // (24, 40) 20.0 -- a shallow queue keeps the stage-1 candidates of a view cache-warm until its chain consumes them
-    // the ring covers every view that can be in flight between the one being collected and the newest stage 1: after an
-    // overflow ALL of them are refilled before any of their chains runs again
-    const int kAhead = L3D_AHEAD, kStage1Ahead = L3D_S1AHEAD, kRing = kAhead + kStage1Ahead + 3;
     int rc_final = L3D_OK;
     // a pass over the same scene (same number of views, same pair count) starts with what the previous one ended up needing: no
     // overflow, no restart, no allocation after the first pass
@@ -623,7 +517,7 @@ static int run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_c
         }
     }
     auto reserve_caps = [&]() -> int {
-        if (int rc = chain_reserve_candidates(c, L, cand_cap, c->chain_ring ? kRing : 0)) return rc;
+        if (int rc = chain_reserve_candidates(c, L, cand_cap, kRing)) return rc;
         HIPCHK(c, c->ch_kept.reserve(arena_cap * sizeof(Match)));
         if (use_cams) HIPCHK(c, c->ch_keptcam.reserve(arena_cap * 4 + 64));
         if (early && arena_cap < 0x7ffffff0ull) { HIPCHK(c, PE.e_E.reserve(arena_cap * 4 + 64)); HIPCHK(c, PE.e_T.reserve(arena_cap * 4 + 64)); }
@@ -696,18 +590,14 @@ static int run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_c
     }
     auto ringA_meta = [&](int k) { return c->ch_ringA_meta.as<uint2>() + (size_t)(k % kRing) * cand_cap; };
     auto ringA_depths = [&](int k) { return c->ch_ringA_depths.as<float4>() + (size_t)(k % kRing) * cand_cap; };
-    // row starts + depth records of a view's stage-1 candidates alone (its reverse matches are not known yet)
-    // L3D_CHAIN_RING=0 (A/B): triangulation on the chain stream, straight into the combined order -- measured 5 % slower on
-    // config 2 than the ring scheme, which keeps the chain stream short.  (Also measured: letting the verification read the
-    // stage-1 candidates in place instead of copying them (k_place) -- 20 % SLOWER: the copy is a streaming pass that
-    // leaves the candidates cache-hot for the latency-bound kernels that follow.)
-    const bool use_ring = c->chain_ring != 0;
+    // row starts + depth records of a view's stage-1 candidates alone (its reverse matches are not known yet), into the view's ring slot; k_place
+    // later moves them into the combined order on the chain stream, which stays short.  (Measured: triangulating on the chain stream instead was 5 %
+    // slower on config 2; letting the verification read the stage-1 candidates in place instead of copying them 20 % SLOWER -- the copy is a streaming
+    // pass that leaves the candidates cache-hot for the latency-bound kernels that follow.)
     // the row starts of the stage-1 candidates are formed inside k_pair_fill from k_pair_mask's counters and their block sums: no
-    // scan launch on the stage-1 stream (the longer of the two), no statistics for the host to wait for.  L3D_FUSED_ROWS=0: A/B.
-    const bool fused_rows_env = c->opt.fused_rows != 0;
-    const bool fused_rows = fused_rows_env && use_ring && depth_in_fill && maxN <= 96;      // (k_pair_mask's LDS block sums: 64 rows N apart span <= 32 blocks)
+    // scan launch on the stage-1 stream (the longer of the two), no statistics for the host to wait for -- up to 96 neighbours
+    const bool fused_rows = maxN <= 96;      // (k_pair_mask's LDS block sums: 64 rows N apart span <= 32 blocks)
     auto enqueue_fillA = [&](int k, hipStream_t s) {
-        if (!use_ring) return;
         const ViewDev& d = vd[(size_t)k];
         PairArgs pa = pair_args(k);
         pa.cand_cap = (int)cand_cap;
@@ -724,19 +614,11 @@ static int run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_c
                 PairArgs pm = pa;
                 pm.rowcnt = fused_rows ? vd[(size_t)k].rowub : vd[(size_t)k].rowcnt;
                 if (fused_rows) pm.rowblk = vd[(size_t)k].rowblk;
-                // (own stream: the bit rows' ring slot was last used by view k - kRing, whose chain may still re-form its candidates from them)
-                if (sm != s1) for (int j = k - kRing; j >= 0; j -= kRing) if (ev[(size_t)j]) { HIPCHK(c, hipStreamWaitEvent(sm, ev[(size_t)j], 0)); break; }
-                { ProfScope p(c, "pair_mask", sm); launch_pair_mask(pm, vd[(size_t)k].maxW, sm, c->opt.pair_spb); }
-                if (sm != s1) {
-                    if (!evm[(size_t)k]) evm[(size_t)k] = get_local_event(c);
-                    HIPCHK(c, hipEventRecord(evm[(size_t)k], sm));
-                    HIPCHK(c, hipStreamWaitEvent(s1, evm[(size_t)k], 0));
-                }
+                ProfScope p(c, "pair_mask", s1);
+                launch_pair_mask(pm, vd[(size_t)k].maxW, s1, c->opt.pair_spb);
             }
-            // row starts of the stage-1 candidates + their statistics straight into host-mapped memory (one launch)
-            if (fused_rows) {}
-            else if (use_ring) { ProfScope p(c, "scan", s1); launch_scan(vd[(size_t)k].rowcnt, vd[(size_t)k].rowA, views[k].S_src * views[k].N, nullptr, s1, nullptr, views[k].N, 0, views[k].S_src, hstats_dev + 2 * k); }
-            else launch_raw_stats(vd[(size_t)k].rowcnt, views[k].N, 0, views[k].S_src, hstats_dev + 2 * k, s1);
+            // (unfused) row starts of the stage-1 candidates + their statistics straight into host-mapped memory (one launch)
+            if (!fused_rows) { ProfScope p(c, "scan", s1); launch_scan(vd[(size_t)k].rowcnt, vd[(size_t)k].rowA, views[k].S_src * views[k].N, nullptr, s1, nullptr, views[k].N, 0, views[k].S_src, hstats_dev + 2 * k); }
             // the ring slot was last used by view k - kRing: wait until its chain has consumed it
             for (int j = k - kRing; j >= 0; j -= kRing) if (ev[(size_t)j]) { HIPCHK(c, hipStreamWaitEvent(s1, ev[(size_t)j], 0)); break; }
             enqueue_fillA(k, s1);
@@ -787,26 +669,16 @@ static int run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_c
         else { ProfScope p(c, "exist"); launch_exist_count(arena, dres, d_si, d_sc, v.n_sources, v.view_id, N, S, d.rowcnt, st, scan_cams, bps); }
         // combined row starts (+ zeroed scatter cursors, + the segments ordered longest first for the verification launch)
         { ProfScope p(c, "scan"); launch_scan(d.rowcnt, c->row_start.as<int>(), (int)nrow, c->ch_cursor.as<int>(), st, c->ch_segorder.as<int>(), N, 0, S); }
-        if (use_ring) {
-            {
-                ProfScope p(c, "cand_move");
-                launch_place(pa.tbm, v.n_tbm, N, S, d.rowA, ringA_meta(k), ringA_depths(k), arena, dres, d_si, d_sc, v.n_sources, v.view_id,
-                             c->row_start.as<int>(), c->ch_cursor.as<int>(), (int)cand_cap, c->cand_meta.as<uint2>(), c->cand_depths.as<float4>(), st, scan_cams, rt_exist ? rt_bps : bps,
-                             rt_exist ? d_info : nullptr, d_ss, rt_g, c->opt.rt_place_lds ? c->ch_existpart.as<int>() : nullptr);
-            }
-            if (v.n_sources && !(c->verify_mode == 0 && verify_window_supported(N))) {     // (the window kernel orders the runs itself)
-                ProfScope p(c, "exist");
-                launch_exist_sort_runs(d_sc, v.n_sources, N, S, c->row_start.as<int>(), c->cand_meta.as<uint2>(), c->cand_depths.as<float4>(), (int)cand_cap, st, 0, -1,
-                                       c->vw_scratch.as<float>(), (long long)cand_cap + kVWSlack, c->cand_conf.as<unsigned>());
-            }
-        } else {
-            if (S > 0) { ProfScope p(c, "pair_fill"); launch_pair_fill(pa, c->row_start.as<int>(), c->cand_meta.as<uint2>(), c->cand_depths.as<float4>(), st); }
+        {
+            ProfScope p(c, "cand_move");
+            launch_place(pa.tbm, v.n_tbm, N, S, d.rowA, ringA_meta(k), ringA_depths(k), arena, dres, d_si, d_sc, v.n_sources, v.view_id,
+                         c->row_start.as<int>(), c->ch_cursor.as<int>(), (int)cand_cap, c->cand_meta.as<uint2>(), c->cand_depths.as<float4>(), st, scan_cams, rt_exist ? rt_bps : bps,
+                         rt_exist ? d_info : nullptr, d_ss, rt_g);
+        }
+        if (v.n_sources && !(c->verify_mode == 0 && verify_window_supported(N))) {     // (the window kernel orders the runs itself)
             ProfScope p(c, "exist");
-            launch_exist_scatter(arena, dres, d_si, d_sc, v.n_sources, v.view_id, N, S, c->row_start.as<int>(),
-                                 c->ch_cursor.as<int>(), c->cand_meta.as<uint2>(), c->cand_depths.as<float4>(), (int)cand_cap, st);
-            if (v.n_sources && !(c->verify_mode == 0 && verify_window_supported(N)))
-                launch_exist_sort_runs(d_sc, v.n_sources, N, S, c->row_start.as<int>(), c->cand_meta.as<uint2>(), c->cand_depths.as<float4>(), (int)cand_cap, st, 0, -1,
-                                       c->vw_scratch.as<float>(), (long long)cand_cap + kVWSlack, c->cand_conf.as<unsigned>());
+            launch_exist_sort_runs(d_sc, v.n_sources, N, S, c->row_start.as<int>(), c->cand_meta.as<uint2>(), c->cand_depths.as<float4>(), (int)cand_cap, st, 0, -1,
+                                   c->vw_scratch.as<float>(), (long long)cand_cap + kVWSlack, c->cand_conf.as<unsigned>());
         }
         VerifyArgs va = chain_verify_args(c, v, d, dtab, cand_cap);
         va.res = dres + k;
@@ -927,7 +799,7 @@ static int run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_c
         if (r.overflow) {
             // not enough room for this view's candidates / kept matches: everything before it is valid and stays
             // in the arena; wait for the queue (and the delivery of earlier views) to drain, grow, and re-enqueue from this view
-            if (!hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize") || !hip_ok(hipStreamSynchronize(sm), "hipStreamSynchronize") || !hip_ok(hipStreamSynchronize(s1), "hipStreamSynchronize")) break;
+            if (!hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize") || !hip_ok(hipStreamSynchronize(s1), "hipStreamSynchronize")) break;
             if (sp && !hip_ok(hipStreamSynchronize(sp), "hipStreamSynchronize")) break;
             const double t_restart0 = now_s();
             wait_delivered();
@@ -1043,14 +915,12 @@ static int run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_c
                 (t_loop0 - t_setup0) * 1e3, (t_prod0 - t_loop0) * 1e3, t_wait * 1e3, t_ev1 * 1e3, t_d2h * 1e3, t_cb * 1e3);
     if (c->opt.timing && map) fprintf(stderr, "[l3d match_chain] products on the device %.2f ms\n", (now_s() - t_prod0) * 1e3);
     const double t_tail0 = now_s();
-    if (sm != s1) (void)hipStreamSynchronize(sm);
     (void)hipStreamSynchronize(s1);
     if (sp) (void)hipStreamSynchronize(sp);
     (void)hipStreamSynchronize(st);
     if (c->opt.timing) fprintf(stderr, "[l3d match_chain] hipSetDevice %.3f ms, final syncs %.3f ms\n", (t_setup0 - t_enter) * 1e3, (now_s() - t_tail0) * 1e3);
     for (hipEvent_t e : ev) { if (cb) put_event(c, e); else put_local_event(c, e); }
     for (hipEvent_t e : ev1) put_local_event(c, e);
-    for (hipEvent_t e : evm) put_local_event(c, e);
     c->stats[1] = raw_sum;
     c->stats[3] = kept_total;
     if (rc_final == L3D_OK && !c->test_cand_cap && !c->test_arena_cap) {

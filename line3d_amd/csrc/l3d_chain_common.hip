@@ -121,7 +121,7 @@ void launch_rt_from_qt(const RtJob* jobs_dev, int n_jobs, int max_cells, hipStre
     if (n_jobs > 0 && max_cells > 0) hipLaunchKernelGGL(k_rt_from_qt, dim3((unsigned)std::max(1, std::min(256, (max_cells + 255) / 256)), (unsigned)n_jobs), dim3(256), 0, st, jobs_dev);
 }
 
-int chain_upload_tables(l3d_ctx* c, const l3d_chain_view* views, int n_views, std::vector<ChainViewDev>& vd, ChainLayout& L, bool with_rays, hipStream_t st)
+int chain_upload_tables(l3d_ctx* c, const l3d_chain_view* views, int n_views, std::vector<ChainViewDev>& vd, ChainLayout& L, hipStream_t st)
 {
     HIPCHK(c, c->ch_pin_tables.reserve(L.tab_bytes + 16));
     HIPCHK(c, c->ch_tables.reserve(L.tab_bytes + 16));
@@ -153,7 +153,7 @@ int chain_upload_tables(l3d_ctx* c, const l3d_chain_view* views, int n_views, st
     jobs.clear();
     for (int k = 0; k < n_views; ++k) {
         vd[(size_t)k].rays = nullptr; vd[(size_t)k].src_rays = nullptr;
-        if (with_rays && vd[(size_t)k].verified && views[k].n_tbm != 0) n_ray += (size_t)views[k].n_tgt + (size_t)views[k].S_src;
+        if (vd[(size_t)k].verified && views[k].n_tbm != 0) n_ray += (size_t)views[k].n_tgt + (size_t)views[k].S_src;
     }
     HIPCHK(c, c->ch_rays.reserve(n_ray * 32 + 2 * (size_t)n_views * sizeof(RayJob) + 512));
     float4* rbase = c->ch_rays.as<float4>();
@@ -161,7 +161,7 @@ int chain_upload_tables(l3d_ctx* c, const l3d_chain_view* views, int n_views, st
     size_t ro = 0;
     for (int k = 0; k < n_views; ++k) {
         ChainViewDev& d = vd[(size_t)k];
-        if (!with_rays || !d.verified || views[k].n_tbm == 0) continue;
+        if (!d.verified || views[k].n_tbm == 0) continue;
         d.rays = rbase + 2 * ro; ro += (size_t)views[k].n_tgt;
         jobs.push_back(RayJob{ d.tgt, reinterpret_cast<const int2*>(L.dtab + d.o_off), reinterpret_cast<const float*>(L.dtab + d.o_R), d.rays, views[k].n_tgt, views[k].N });
         // (the view's own segments under its own camera: what k_pair_fill needs once per (segment, camera) row)
@@ -262,8 +262,7 @@ PairArgs chain_pair_args(const l3d_ctx* c, const l3d_chain_view& v, const ChainV
     pa.S_src = v.S_src; pa.N = v.N; pa.n_tbm = v.n_tbm; pa.W64 = d.W64;
     pa.seg_begin = d.s0; pa.seg_end = d.s1; pa.cand_cap = 0; pa.wedge_pretest = c->wedge_pretest; pa.dbg = c->pair_dbg; pa.dbg_view = (int)v.view_id; pa.rowcnt = nullptr;
     pa.depth_in_fill = 1;               // the four depths of a stage-1 pair are triangulated once, by k_pair_fill
-    const bool src_rays_env = c->opt.src_rays != 0;   // (0: A/B, k_pair_fill normalises per row)
-    pa.tgt_rays = d.rays; pa.src_rays = src_rays_env ? d.src_rays : nullptr;
+    pa.tgt_rays = d.rays; pa.src_rays = d.src_rays;
     return pa;
 }
 

@@ -127,10 +127,6 @@ struct Products {
     }
 };
 
-// one view's launch sequence of the sharded chain as an instantiated graph (l3d_chain_sharded.hip): sig = checksum of everything the
-// launches depend on, seen = passes in a row with that checksum
-struct ShardGraph { unsigned long long sig = 0; int seen = 0; hipGraphExec_t exec = nullptr; };
-
 // a rank's part of an affinity fill sharded by source key (l3d_affinity.hip: affinity_fill_core): the sources it enumerates, where its
 // candidates stand in the whole enumeration (ranks own ascending source ranges: rank << 44 orders them without knowing the other ranks' counts)
 // and what turns its local hypothesis indices into global ones
@@ -153,7 +149,6 @@ struct l3d_ctx {
     hipStream_t stream = nullptr;
     hipStream_t copy_stream = nullptr;       // bulk D2H of the resident chain, concurrent with kernels
     hipStream_t prod_stream = nullptr;       // option prod_early: a view's pair transposes, behind its kept writer (created on first use)
-    hipStream_t mask_stream = nullptr;       // option mask_stream: k_pair_mask alone, ahead of the rest of stage 1 (created on first use)
     hipStream_t stage1_stream = nullptr;     // stage 1 of the resident chain (independent of the chain state) runs ahead here
     std::string err;                         // written under err_mu: the chains report from several host threads
     std::mutex err_mu;
@@ -164,8 +159,6 @@ struct l3d_ctx {
     // arenas of the resident chain (l3d_chain.hip)
     l3d::DevBuf ch_tables, ch_mask, ch_rowcnt, ch_cursor, ch_best, ch_kept, ch_keptcam, ch_res, ch_flags, ch_send, ch_gathered, ch_stage, ch_rowA, ch_ringA_meta, ch_ringA_depths, ch_segorder, ch_rays, ch_rt, ch_rtinfo, ch_rtjobs, ch_existpart;
     l3d::PinBuf ch_pin_tables, ch_pin_res, ch_pin_kept, ch_pin_best;
-    long long shard_graph_launches = 0;          // views enqueued as one graph launch so far (l3d_get_option "shard_graph_launches")
-    std::vector<l3d::ShardGraph> shard_graphs;   // per view of the sharded chain (repeated passes replay them)
     l3d::DevBuf ch_hdr;                      // sharded run, ring mode: per-view arena offsets, header table, flags
     l3d::DevBuf ch_bestpos;                  // per segment of every view: position of its best kept match in the view's slice (resident runs)
     l3d::Products products;
@@ -173,7 +166,6 @@ struct l3d_ctx {
     l3d::PinArena pin_arena;                 // kept lists of the running / last chain (valid until the next chain starts)
     std::vector<int> h_cnt;
     int mmax_seen = 0;
-    int chain_ring = 1;             // single-GPU chain: 1 = stage-1 candidate ring + k_place (default), 0 = triangulation on the chain stream (L3D_CHAIN_RING=0, A/B)
     l3d::DevBuf vw_bstart, vw_segstate;             // split verification (k_vw_walk): bucket starts of the built images | per-segment state + unit table
     size_t part_arena_seen = 0;                     // records a partitioned segment-sharded run kept on this rank (sizes the next pass's arena)
     size_t test_cand_cap = 0, test_arena_cap = 0;   // tests: initial capacities of the resident chain (0 = estimate)
@@ -245,10 +237,9 @@ inline hipEvent_t get_event(l3d_ctx* c)
 // nothing for a fence to write back; the event's own signal is a later posted write on the same path).  That holds for the RESIDENT chain only: with a
 // delivery callback (l3d_match_chain) the host, having seen a view's event, starts D2H copies of DEVICE memory (the kept slice, the best depth pairs) on
 // another stream -- nothing but the event orders those copies behind the kernels, so run_chain takes default (fenced) events for its per-view events
-// whenever a callback is given.  Nothing another device wrote is read behind these events.  (Option event_fence = 1: default events everywhere, A/B.)
+// whenever a callback is given.  Nothing another device wrote is read behind these events.
 inline hipEvent_t get_local_event(l3d_ctx* c)
 {
-    if (c->opt.event_fence != 0) return get_event(c);
     std::lock_guard<std::mutex> lk(c->event_mu);
     if (!c->local_event_pool.empty()) { hipEvent_t e = c->local_event_pool.back(); c->local_event_pool.pop_back(); return e; }
     hipEvent_t e;
@@ -259,7 +250,7 @@ inline void put_local_event(l3d_ctx* c, hipEvent_t e)
 {
     if (!e) return;
     std::lock_guard<std::mutex> lk(c->event_mu);
-    (c->opt.event_fence != 0 ? c->event_pool : c->local_event_pool).push_back(e);
+    c->local_event_pool.push_back(e);
 }
 inline void put_event(l3d_ctx* c, hipEvent_t e) { if (e) { std::lock_guard<std::mutex> lk(c->event_mu); c->event_pool.push_back(e); } }
 
@@ -292,7 +283,6 @@ inline void prof_resolve(l3d_ctx* c)
 {
     (void)hipStreamSynchronize(c->stream);
     if (c->stage1_stream) (void)hipStreamSynchronize(c->stage1_stream);
-    if (c->mask_stream) (void)hipStreamSynchronize(c->mask_stream);
     if (c->prod_stream) (void)hipStreamSynchronize(c->prod_stream);
     std::lock_guard<std::mutex> lk(c->event_mu);         // (the pools and the pending lists: ProfScope of another enqueue thread takes it too)
     for (auto& kv : c->prof) {

@@ -495,15 +495,15 @@ __global__ __launch_bounds__(256) void k_prodt_early(const Match* __restrict__ a
     }
 }
 
-// One wave per row (x, u).  The row is put together from the views x touches, ascending, a GROUP of consecutive ones at a time (as many as fit 512
-// words of bitmap: 8 views of 2000 segments, 4 of 4000): for view y the run (u, camera of y) of x's own list (F) and column u of the pair (y, camera of
-// x) (B) set bits in y's words of the bitmap -- sorted and unique by construction; the lanes look all views' run and column bounds up at once, 64 views at
-// a time.  2 KB of LDS per wave: every wave slot of the CU is used (the first version's bitmap over all touched views, 12.5 KB at 25 x 4000, left 12).
+// One wave per row (x, u).  The row is put together from the views x touches, ascending, one view at a time in a bitmap of 512 words (a view has at most
+// 16384 segments): for view y the run (u, camera of y) of x's own list (F) and column u of the pair (y, camera of x) (B) set bits in the bitmap -- sorted
+// and unique by construction; the lanes look all views' run and column bounds up at once, 64 views at a time.  2 KB of LDS per wave: every wave slot of
+// the CU is used (the first version's bitmap over all touched views, 12.5 KB at 25 x 4000, left 12).
 template <bool WRITE>
 __global__ __launch_bounds__(256) void k_prodv_rows(const ProdRowView* __restrict__ rv, int x0, int d0, const ProdViewQ* __restrict__ vq, const ProdTouch* __restrict__ tl,
                                                     const ProdPair* __restrict__ pairs, const int* __restrict__ poff, const int* __restrict__ boff, const unsigned* __restrict__ E,
                                                     const int* __restrict__ bstart, const unsigned* __restrict__ ent, int* __restrict__ ucnt, const int* __restrict__ ustart,
-                                                    long long base, int* __restrict__ pot_tgt, int group_words, int* __restrict__ stage,
+                                                    long long base, int* __restrict__ pot_tgt, int* __restrict__ stage,
                                                     const unsigned* __restrict__ poff_kq, int maxN)
 {
     constexpr int kWords = 512;
@@ -544,7 +544,6 @@ __global__ __launch_bounds__(256) void k_prodv_rows(const ProdRowView* __restric
             }
         }
         const int cnt = min(64, v.t1 - t0);
-        const int words = j < v.t1 ? (e.y_S + 31) >> 5 : 0;
         // SHORT ROWS (config 2: 18 + 18 entries over 12 views): at most 64 entries in all -- one per lane, as dense ids; ranked against each other by
         // shuffles, put in order, neighbours compared: sorted and unique without a bitmap, a fence or a sweep per touched view
         if (v.t1 - v.t0 <= 64) {
@@ -579,47 +578,36 @@ __global__ __launch_bounds__(256) void k_prodv_rows(const ProdRowView* __restric
                 return;
             }
         }
-        int jj = 0;
-        while (jj < cnt) {
-            // the group [jj, j1): views whose words fit the bitmap together (a single view always fits: <= 16384 segments)
-            int j1 = jj, gw = 0, any = ne;
-            while (j1 < cnt) { const int w = __shfl(words, j1); if (j1 > jj && gw + w > group_words) break; gw += w; any += __shfl(f_n, j1) + __shfl(b_n, j1); ++j1; }
-            if (any == 0) { jj = j1; continue; }
-            for (int w = lane; w < gw; w += 64) bm[w] = 0u;
+        for (int k = 0; k < cnt; ++k) {
+            const int fn = __shfl(f_n, k), bn = __shfl(b_n, k);
+            if (fn + bn + ne == 0) continue;
+            const int fa = __shfl(f_a, k), ba = __shfl(b_a, k), yS = __shfl(e.y_S, k), yb = __shfl(e.y_base, k);
+            const int nw = (yS + 31) >> 5;
+            for (int w = lane; w < nw; w += 64) bm[w] = 0u;
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
             __builtin_amdgcn_wave_barrier();
-            int wo = 0;
-            for (int k = jj; k < j1; ++k) {
-                const int fn = __shfl(f_n, k), bn = __shfl(b_n, k), fa = __shfl(f_a, k), ba = __shfl(b_a, k), yS = __shfl(e.y_S, k), yb = __shfl(e.y_base, k);
-                unsigned* bw = bm + wo;
-                for (int i = lane; i < fn; i += 64) { const unsigned t = fq[fa + i] & 0xffffu; if ((int)t < yS) atomicOr(&bw[t >> 5], 1u << (t & 31u)); }
-                for (int i = lane; i < bn; i += 64) { const unsigned t = E[ba + i]; if ((int)t < yS) atomicOr(&bw[t >> 5], 1u << (t & 31u)); }
-                for (int i = lane; i < ne; i += 64) { const unsigned t = ent[e0 + i] - (unsigned)yb; if (t < (unsigned)yS) atomicOr(&bw[t >> 5], 1u << (t & 31u)); }
-                wo += (yS + 31) >> 5;
-            }
+            for (int i = lane; i < fn; i += 64) { const unsigned t = fq[fa + i] & 0xffffu; if ((int)t < yS) atomicOr(&bm[t >> 5], 1u << (t & 31u)); }
+            for (int i = lane; i < bn; i += 64) { const unsigned t = E[ba + i]; if ((int)t < yS) atomicOr(&bm[t >> 5], 1u << (t & 31u)); }
+            for (int i = lane; i < ne; i += 64) { const unsigned t = ent[e0 + i] - (unsigned)yb; if (t < (unsigned)yS) atomicOr(&bm[t >> 5], 1u << (t & 31u)); }
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
             __builtin_amdgcn_wave_barrier();
             if (!WRITE) {
-                for (int w = lane; w < gw; w += 64) total += __popc(bm[w]);
+                for (int w = lane; w < nw; w += 64) total += __popc(bm[w]);
             } else {
-                for (int wb = 0; wb < gw; wb += 64) {
+                for (int wb = 0; wb < nw; wb += 64) {
                     const int w = wb + lane;
-                    unsigned word = w < gw ? bm[w] : 0u;
+                    unsigned word = w < nw ? bm[w] : 0u;
                     if (__ballot(word != 0u) == 0ull) continue;
-                    // the view a word belongs to: the last one of the group whose first word is <= w
-                    int dbase = 0, acc = 0;
-                    for (int k = jj; k < j1; ++k) { const int yb = __shfl(e.y_base, k), yw = __shfl(words, k); if (w >= acc) dbase = yb + ((w - acc) << 5); acc += yw; }
                     const int pc = __popc(word);
                     int incl = pc;
                     for (int d = 1; d < 64; d <<= 1) { const int x = __shfl_up(incl, d); if (lane >= d) incl += x; }
                     long long p = o + (incl - pc);
-                    while (word) { const int bit = __ffs(word) - 1; pot_tgt[p++] = dbase + bit; word &= word - 1u; }
+                    while (word) { const int bit = __ffs(word) - 1; pot_tgt[p++] = yb + (w << 5) + bit; word &= word - 1u; }
                     o += __shfl(incl, 63);
                 }
             }
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
             __builtin_amdgcn_wave_barrier();
-            jj = j1;
         }
     }
     if (!WRITE) {
@@ -656,7 +644,7 @@ void l3d::launch_early_transposes(l3d_ctx* c, const EarlyView* views_dev, int k0
     while (g < 64 && g < avg_run / 4.0) g <<= 1;
     if (c->opt.prod_pair_g >= 0) g = c->opt.prod_pair_g;
     int cap = 0;
-    if (c->opt.prod_pair_stage != 0 && T) {
+    if (T) {
         cap = 12288;
         while (cap > 1024 && ((size_t)maxSt + 2 + 2 * (size_t)cap) * 4 > 64 * 1024) cap -= 1024;
         if (((size_t)maxSt + 2 + 2 * (size_t)cap) * 4 > 64 * 1024) cap = 0;
@@ -1069,14 +1057,12 @@ int l3d::build_products(l3d_ctx* c, const l3d_chain_view* views, int n_views, co
                         int g = 1;
                         while (g < 64 && g < recs / std::max(1.0, cells) / 4.0) g <<= 1;
                         if (c->opt.prod_pair_g >= 0) g = c->opt.prod_pair_g;
-                        // two-level scatter (prod_pair_stage: 1 on, 0 the direct scatter): an LDS image of `cap` entries of E per workgroup + a cursor per u of a bucket
-                        int cap = 0;
+                        // two-level scatter: an LDS image of `cap` entries of E per workgroup + a cursor per u of a bucket (cap 0: the direct scatter, when even
+                        // 1024 entries do not fit beside the block's widest view)
+                        int cap = 12288;
                         unsigned* T = nullptr;
-                        if (c->opt.prod_pair_stage != 0) {
-                            cap = 12288;
-                            while (cap > 1024 && ((size_t)B.maxS + 2 + 2 * (size_t)cap) * 4 > 64 * 1024) cap -= 1024;
-                            if (((size_t)B.maxS + 2 + 2 * (size_t)cap) * 4 <= 64 * 1024) { HIPCHK(c, P.tstage.reserve((size_t)max_rec * 4 + 256)); T = P.tstage.as<unsigned>(); } else cap = 0;
-                        }
+                        while (cap > 1024 && ((size_t)B.maxS + 2 + 2 * (size_t)cap) * 4 > 64 * 1024) cap -= 1024;
+                        if (((size_t)B.maxS + 2 + 2 * (size_t)cap) * 4 <= 64 * 1024) { HIPCHK(c, P.tstage.reserve((size_t)max_rec * 4 + 256)); T = P.tstage.as<unsigned>(); } else cap = 0;
                         hipLaunchKernelGGL(k_prodv_pair_transpose, dim3((unsigned)n_pairs), dim3(kPairThreads), ((size_t)B.maxS + 2 + 2 * (size_t)cap) * 4, st, dpr + B.pair0, dvq, dpv, dnb,
                                            (const int*)poff, g, boff, E, T, cap);
                     }
@@ -1102,7 +1088,7 @@ int l3d::build_products(l3d_ctx* c, const l3d_chain_view* views, int n_views, co
                     ProfScope p(c, "prod_rows", st);
                     HIPCHK(c, hipMemsetAsync(ucnt + rows, 0, 4, st));
                     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_prodv_rows<false>), rg, dim3(256), 0, st, drv, B.x0, d0, dvq, dtl, dpr, (const int*)poff - B.pair0, (const int*)boff,
-                                       (const unsigned*)E, bs, (const unsigned*)ent, ucnt, (const int*)ustart, base, (int*)nullptr, c->opt.prod_row_group, stage, poff_kq, e_maxN);
+                                       (const unsigned*)E, bs, (const unsigned*)ent, ucnt, (const int*)ustart, base, (int*)nullptr, stage, poff_kq, e_maxN);
                     size_t t1 = tbs;
                     HIPCHK(c, exclusive_sum_int(P.tmp.p, t1, ucnt, ustart, rows + 1, st));
                 }
@@ -1114,7 +1100,7 @@ int l3d::build_products(l3d_ctx* c, const l3d_chain_view* views, int n_views, co
                 {
                     ProfScope p(c, "prod_rows", st);
                     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_prodv_rows<true>), rg, dim3(256), 0, st, drv, B.x0, d0, dvq, dtl, dpr, (const int*)poff - B.pair0, (const int*)boff,
-                                       (const unsigned*)E, bs, (const unsigned*)ent, ucnt, (const int*)ustart, base, P.pot_tgt.as<int>(), c->opt.prod_row_group, stage, poff_kq, e_maxN);
+                                       (const unsigned*)E, bs, (const unsigned*)ent, ucnt, (const int*)ustart, base, P.pot_tgt.as<int>(), stage, poff_kq, e_maxN);
                     hipLaunchKernelGGL(k_prodt_row_starts, dim3((unsigned)((rows + 256) / 256)), dim3(256), 0, st, (const int*)ustart, rows, base, P.pot_start.as<long long>() + d0);
                 }
             } else {
