@@ -389,7 +389,7 @@ int l3d_match_chain_blocks(l3d_ctx* ctx, const l3d_chain_view* views, int n_view
                            int rank, int world, int warmup_views, int window, l3d_exchange_fn exchange, void* exchange_user, int* verdict);
 
 /* ---- Line3D::matchViews sharded by blocks of views with NOTHING REPLICATED (the configs[4] job: 2048 views x 4000 segments x 24 neighbours keep
- * 6.4 G matches -- beyond a 32-bit record index and, with the table built from them, beyond one GPU's HBM; the reference streams a view at a time
+ * 6.4 G matches -- with the table built from them, beyond one GPU's HBM; the reference streams a view at a time
  * and spills every view's matches to a file, view.cc:150-224, line3D.cc:626-648).  Same speculation and verification as l3d_match_chain_blocks;
  * but rank r runs its chain 2 x reach views PAST its block (reach = the largest distance, in chain positions, between a view and one of its
  * neighbours) and is checked max(window, 2 x reach) views in front of it -- so it holds, computed by itself, the exact kept records of every view
@@ -576,6 +576,10 @@ int l3d_line3d_affinity(const l3d_line3d* h, const l3d_edge** A, int* nnz, int* 
  * best n_dense (segID1 == 0xffffffff: none), hyp / score n_hyp */
 int l3d_line3d_products_sizes(const l3d_line3d* h, int* n_views, int* n_dense, int64_t* n_pot, int* n_hyp);
 int l3d_line3d_products_get(l3d_line3d* h, int32_t* seg_base, int64_t* pot_start, int32_t* pot_tgt, l3d_match* best, l3d_hypothesis* hyp, float* score);
+/* per chain view (the index of l3d_chain_kept_list) of the last matchViews with resident products: what the builder reported (kept / candidate counts,
+ * median depth; a partitioned job: the views this rank holds, zero elsewhere).  The array belongs to h and stays valid until the next matchViews;
+ * *n = 0 without resident products.  Kept counts are per view: their sum -- the arena -- may exceed 2^32 */
+int l3d_line3d_chain_summary(const l3d_line3d* h, const l3d_chain_summary** summary, int* n);
 int l3d_line3d_stats(const l3d_line3d* h, double* stats12);
 
 /* =================================================================================================

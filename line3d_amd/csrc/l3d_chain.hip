@@ -260,8 +260,9 @@ __global__ __launch_bounds__(256) void k_kept_write_chain(VerifyArgs a, const in
     r.R = a.row_start[nrow];
     r.overflow = r.R > a.cand_cap ? 1 : 0;
     r.n_kept = r.overflow ? 0 : total;
-    r.kept_base = prev ? prev->kept_base + prev->n_kept : 0;
-    if ((unsigned long long)r.kept_base + (unsigned long long)r.n_kept > arena_cap) { r.overflow |= 2; r.n_kept = 0; }
+    r.n_want = 0;
+    r.kept_base = prev ? prev->kept_base + (uint64_t)prev->n_kept : 0;
+    if (r.kept_base + (uint64_t)r.n_kept > arena_cap) { r.overflow |= 2; r.n_want = r.n_kept; r.n_kept = 0; }     // (the regrow must hold this view too)
     if (blockIdx.x == 0 && tid == 0) { *res = r; *res_host = r; }
     if (yl >= nseg || r.overflow) return;
     write_kept_segment_wg(a, a.seg_begin + yl, before, local2global, arena + r.kept_base, s_cnt, best_pos ? best_pos + a.seg_begin + yl : nullptr, s_best, cams ? cams + r.kept_base : nullptr,
@@ -443,7 +444,6 @@ static int run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_c
             arena_cap = std::max(arena_cap, std::min(want, fits));
         }
         (void)hipGetLastError();
-        if (arena_cap > 0xfffffff0ull) arena_cap = 0xfffffff0ull;
     }
     if (c->test_cand_cap) cand_cap = c->test_cand_cap;      // tests: force the overflow / restart path
     if (c->test_arena_cap) arena_cap = c->test_arena_cap;
@@ -529,7 +529,7 @@ static int run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_c
         size_t so = 0;
         for (int k = pre->k0; k < pre->k1; ++k) {
             ChainResult r;
-            r.kept_base = (unsigned)base; r.n_kept = has_rec[(size_t)k] ? pre->n_kept[(size_t)(k - pre->k0)] : 0; r.R = pre->R[(size_t)(k - pre->k0)]; r.overflow = 0;
+            r.kept_base = (uint64_t)base; r.n_want = 0; r.n_kept = has_rec[(size_t)k] ? pre->n_kept[(size_t)(k - pre->k0)] : 0; r.R = pre->R[(size_t)(k - pre->k0)]; r.overflow = 0;
             hres[k] = r;
             base += r.n_kept;
             if (views[k].n_tbm > 0) {
@@ -818,11 +818,34 @@ static int run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_c
                     const size_t proj = (size_t)((double)r.kept_base / done * span * (2 * done < span ? 1.5 : 1.15)) + 1048576;
                     new_cap = 2 * done < span ? std::max(new_cap, proj) : std::max(proj, arena_cap + arena_cap / 8);
                 }
-                // (records are indexed with 32 bits: the arena ends at 2^32 records = 137 GB; doubling must not run past it)
-                const size_t kMaxRecords = 0xfffffff0u;
-                if (new_cap > kMaxRecords) {
-                    if (arena_cap >= kMaxRecords) { rc_final = fail(c, L3D_ERR_UNSUPPORTED, "match_chain: more than 2^32 kept matches in one chain (view " + std::to_string(k) + " of " + std::to_string(n_views) + ")"); break; }
-                    new_cap = kMaxRecords;
+                // (records are indexed with 64 bits: memory is the only bound.)  The new arena must hold the records in use AND the view that overflowed
+                // (n_want: its true count), so that its re-run cannot overflow again.  The old arena and side array stay allocated until the used part is
+                // copied over, so near the top of HBM the new ones must fit BESIDE them, next to what the products will take (their table: 8 B per record,
+                // their smallest transient blocks: 6.4 GB): a size above what fits is cut down to it -- and when what fits cannot hold that view or is no
+                // larger than the arena that just overflowed, the chain fails with NOMEM and the sizes.  Every regrow grows the arena and lets the view
+                // through: the restarts are bounded.
+                const size_t need = (size_t)r.kept_base + (size_t)std::max(0, r.n_want) + 65536;
+                new_cap = std::max(new_cap, need);
+                {
+                    size_t fr = 0, tot = 0;
+                    if (hipMemGetInfo(&fr, &tot) == hipSuccess) {
+                        if (c->opt.regrow_free_mb > 0) fr = std::min(fr, (size_t)c->opt.regrow_free_mb << 20);     // (tests: a card with less room)
+                        const size_t per_rec = sizeof(Match) + (use_cams ? 4 : 0) + (early && new_cap < 0x7ffffff0ull ? 4 : 0) + (map ? 8 : 0);
+                        const size_t reserve = map ? (size_t)((1ll << 28) * 24) + ((size_t)1 << 30) : (size_t)512 << 20;
+                        const size_t fits = fr > reserve ? (fr - reserve) / per_rec : 0;
+                        if (new_cap > fits) {
+                            if (fits < need || fits <= arena_cap) {
+                                rc_final = fail(c, L3D_ERR_NOMEM, "match_chain: the kept arena of " + std::to_string(arena_cap) + " records is full at view " + std::to_string(k) + " of " + std::to_string(n_views) + " (" +
+                                                                      std::to_string((size_t)r.kept_base) + " records in use, the view keeps " + std::to_string(r.n_want) + ") and an arena of " +
+                                                                      std::to_string(need) + " records does not fit beside it (room for " + std::to_string(fits) + " at " + std::to_string(per_rec) + " B per record, " +
+                                                                      std::to_string(reserve >> 20) + " MB kept back; " + std::to_string(fr >> 20) + " of " + std::to_string(tot >> 20) +
+                                                                      " MB free): l3d_set_chain_capacities sizes the arena up front");
+                                break;
+                            }
+                            new_cap = fits;
+                        }
+                    }
+                    (void)hipGetLastError();
                 }
                 void* np = nullptr;
                 const double t_m0 = now_s();
@@ -1398,13 +1421,12 @@ static int chain_blocks_impl(l3d_ctx* c, const l3d_chain_view* views, int n_view
                         if (int rc = arena_grow_keep(c, (size_t)(used + n) + 64, (size_t)used)) { note(rc); break; }
                         L3D_SOFT(hipMemcpyAsync(c->ch_kept.as<Match>() + used, G + (size_t)r * eslot + hdr + (size_t)o * sizeof(Match), (size_t)n * sizeof(Match), hipMemcpyDeviceToDevice, st));
                         ChainResult& x = hloc[(size_t)si];
-                        x.kept_base = (unsigned)used; x.n_kept = n; x.R = n; x.overflow = 0;
+                        x.kept_base = (uint64_t)used; x.n_kept = n; x.R = n; x.overflow = 0;
                         used += n;
                     }
                     o += n;
                 }
             }
-            if (used > 0xfffffff0ll) note(fail(c, L3D_ERR_UNSUPPORTED, "l3d_match_chain_partition: more than 2^32 kept matches on one rank"));
         }
         // ---- the views an early return's LOCAL camera numbers name (cudawrapper.cu:877-878 hands the list back with local numbers, line3D.cc:861-865
         // files the entries under them read as view ids): rows of an early-return view point at their segments, whoever holds them.  The affinity fill
@@ -1478,7 +1500,7 @@ static int chain_blocks_impl(l3d_ctx* c, const l3d_chain_view* views, int n_view
                     L3D_SOFT(hipMemcpyAsync(c->ch_bestpos.as<int>() + best_off[(size_t)b], pk + 16, (size_t)S * 4, hipMemcpyDeviceToDevice, st));
                     L3D_SOFT(hipMemcpyAsync(c->ch_best.as<float2>() + best_off[(size_t)b], pk + 16 + (size_t)S * 4, (size_t)S * 8, hipMemcpyDeviceToDevice, st));
                     ChainResult& x = hloc[(size_t)b];
-                    x.kept_base = (unsigned)used; x.n_kept = h[2]; x.R = h[1]; x.overflow = 0;
+                    x.kept_base = (uint64_t)used; x.n_kept = h[2]; x.R = h[1]; x.overflow = 0;
                     used += h[2];
                     alias_known[(size_t)b] = 1;
                 }
@@ -1530,12 +1552,11 @@ static int chain_blocks_impl(l3d_ctx* c, const l3d_chain_view* views, int n_view
     }
     long long max_rec = 0, max_seg = 0, total = 0;
     for (int r = 0; r < world; ++r) { max_rec = std::max(max_rec, rec_of[(size_t)r]); max_seg = std::max(max_seg, seg_of[(size_t)r]); total += rec_of[(size_t)r]; }
-    if (total > 0xfffffff0ll) return fail(c, L3D_ERR_UNSUPPORTED, "l3d_match_chain_blocks: more than 2^32 kept matches (l3d_match_chain_partition keeps every rank's records where they are)");     // (the same on every rank)
     const size_t o_best = al((size_t)max_rec * sizeof(Match)), o_bpos = o_best + al((size_t)max_seg * 8), slot = o_bpos + al((size_t)max_seg * 4);
     {
         hipError_t e = c->ch_send.reserve(slot + 256);
         if (e == hipSuccess) e = c->ch_gathered.reserve(slot * (size_t)world + 256);
-        if (e != hipSuccess) note(fail(c, L3D_ERR_NOMEM, "l3d_match_chain_blocks: the blocks' slots"));
+        if (e != hipSuccess) { (void)hipGetLastError(); note(fail(c, L3D_ERR_NOMEM, "l3d_match_chain_blocks: the blocks' slots (" + std::to_string(world) + " x " + std::to_string(slot >> 20) + " MB: " + std::to_string(max_rec) + " kept matches in the largest block)")); }
         else {
             unsigned char* send = c->ch_send.as<unsigned char>();
             long long own_start = 0;                                    // (this rank's arena: the views it holds, back to back from arena_first)
@@ -1562,12 +1583,18 @@ static int chain_blocks_impl(l3d_ctx* c, const l3d_chain_view* views, int n_view
     double t3 = 0;
     const auto assemble_and_build = [&]() -> int {
         HIPCHK(c, hipStreamSynchronize(st));            // (the arena below may be reallocated: everything that reads the old one is done)
-        HIPCHK(c, c->ch_kept.reserve(((size_t)total + 64) * sizeof(Match)));
+        if (c->ch_kept.reserve(((size_t)total + 64) * sizeof(Match)) != hipSuccess) {
+            (void)hipGetLastError();
+            size_t fr = 0, tot = 0;
+            (void)hipMemGetInfo(&fr, &tot);
+            return fail(c, L3D_ERR_NOMEM, "l3d_match_chain_blocks: the one chain's arena of " + std::to_string(total) + " kept matches (" + std::to_string(((size_t)total * sizeof(Match)) >> 20) +
+                                              " MB) does not fit (" + std::to_string(fr >> 20) + " of " + std::to_string(tot >> 20) + " MB free; l3d_match_chain_partition keeps every rank's records where they are)");
+        }
         long long base = 0;
         for (int k = 0; k < n_views; ++k) {
             const BlockDigest& e = tab[(size_t)owner(k) * n_views + k];
             ChainResult& r = hres_all[(size_t)k];
-            r.kept_base = (unsigned)base; r.n_kept = e.n_kept; r.R = e.R; r.overflow = 0;
+            r.kept_base = (uint64_t)base; r.n_kept = e.n_kept; r.R = e.R; r.overflow = 0;
             base += e.n_kept;
             const bool ver = views[k].n_tbm > 0;
             pvh[(size_t)k].verified = ver ? 1 : 0;

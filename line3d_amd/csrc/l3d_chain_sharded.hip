@@ -264,7 +264,7 @@ __global__ void k_shard_totals(const unsigned char* __restrict__ hdr, size_t hdr
 // all views' slots -> ONE kept arena (views back to back, ranks in segment order: the sorted list of the unsharded run) + the whole
 // view's best depth pairs and best positions (relative to the view's slice).  grid (x, rank, view).
 __global__ __launch_bounds__(256) void k_shard_pack_all(const unsigned char* __restrict__ G, SlotGeom g, const unsigned char* __restrict__ verified,
-                                                        const unsigned* __restrict__ kept_base, const long long* __restrict__ best_off, Match* __restrict__ arena,
+                                                        const unsigned long long* __restrict__ kept_base, const long long* __restrict__ best_off, Match* __restrict__ arena,
                                                         float2* __restrict__ best_all, int* __restrict__ bestpos_all)
 {
     const int k = blockIdx.z, r = blockIdx.y;
@@ -277,7 +277,7 @@ __global__ __launch_bounds__(256) void k_shard_pack_all(const unsigned char* __r
     const int n = hd->overflow ? 0 : hd->n_kept;
     const int tid = blockIdx.x * blockDim.x + threadIdx.x, nt = gridDim.x * blockDim.x;
     const float4* src = reinterpret_cast<const float4*>(slot + g.rec_off);
-    float4* dst = reinterpret_cast<float4*>(arena + (size_t)kept_base[k] + base);
+    float4* dst = reinterpret_cast<float4*>(arena + kept_base[k] + base);
     for (int i = tid; i < 2 * n; i += nt) dst[i] = src[i];
     const float2* sb = reinterpret_cast<const float2*>(slot + g.best_off);
     const int* sp = reinterpret_cast<const int*>(slot + g.bpos_off);
@@ -486,7 +486,8 @@ int l3d_shard_chain_open(l3d_ctx* c, const l3d_chain_view* views, int n_views, i
     { int rc = chain_upload_tables(c, views, n_views, h->vd, L, st); if (rc) return bail(rc); }
     { int rc = chain_assign_arenas(c, views, n_views, h->vd, L, false, true, l3d_shard_chain::kRingA, st); if (rc) return bail(rc); }   // (+ best positions: l3d_shard_chain_products)
     h->dtab = L.dtab;
-    OCHK(c->ch_pin_res.reserve((size_t)n_views * 8 + 64));
+    // (the run's statistics words; a partitioned run's products leave the per-view result records in the same buffer afterwards: sized for both)
+    OCHK(c->ch_pin_res.reserve((size_t)n_views * std::max<size_t>(8, sizeof(ChainResult)) + 64));
     h->hstats = c->ch_pin_res.as<int>();
     OCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->hstats_dev), h->hstats, 0));
     {   // stage 1 (own stream) starts after the tables and the zeroed row counts are in place
@@ -766,7 +767,7 @@ int l3d_shard_chain_run(l3d_shard_chain* h, l3d_exchange_fn exchange, void* exch
             size_t fr = 0, tot = 0;
             if (hipMemGetInfo(&fr, &tot) == hipSuccess) {
                 const long long want = (long long)(h->pairs * h->world * 0.001 * c->opt.arena_guess) + 1048576, fits = (long long)((double)fr * 0.35 / 40.0);
-                h->arena_cap = std::min<long long>(0xfffffff0ll, std::max(h->arena_cap, std::min(want, fits)));
+                h->arena_cap = std::max(h->arena_cap, std::min(want, fits));
             }
             (void)hipGetLastError();
         }
@@ -1136,8 +1137,8 @@ static int shard_products_local(l3d_shard_chain* h, const l3d_dense_map* map, l3
     const int nv = h->n_views;
     const size_t nvs = (size_t)nv;
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    // scratch: verified flags | totals int2 | kept_base int | best_off i64
-    const size_t o_ver = 0, o_tot = al(nvs), o_kb = o_tot + al(nvs * 8), o_bo = o_kb + al(nvs * 4), bytes = o_bo + al(nvs * 8);
+    // scratch: verified flags | totals int2 | kept_base u64 | best_off i64
+    const size_t o_ver = 0, o_tot = al(nvs), o_kb = o_tot + al(nvs * 8), o_bo = o_kb + al(nvs * 8), bytes = o_bo + al(nvs * 8);
     HIPCHK(c, c->g7.reserve(bytes + 64));
     unsigned char* sc = c->g7.as<unsigned char>();
     std::vector<unsigned char> ver(nvs);
@@ -1150,17 +1151,16 @@ static int shard_products_local(l3d_shard_chain* h, const l3d_dense_map* map, l3
     HIPCHK(c, hipStreamSynchronize(st));
     std::vector<ChainResult> hres(nvs);
     std::vector<ProdChainView> pvh(nvs);
-    std::vector<unsigned> kept_base(nvs, 0);
+    std::vector<unsigned long long> kept_base(nvs, 0);
     std::vector<long long> best_off(nvs, 0);
     long long total = 0;
     for (int k = 0; k < nv; ++k) {
         const SViewDev& d = h->vd[(size_t)k];
         ChainResult& r = hres[(size_t)k];
         const bool here = !h->partition || h->keep[(size_t)k];            // (partitioned: the views this rank retired)
-        r.kept_base = (unsigned)total; r.n_kept = d.verified && here ? tot[(size_t)k].x : 0; r.R = d.verified && here ? tot[(size_t)k].y : 0; r.overflow = 0;
-        kept_base[(size_t)k] = (unsigned)total;
+        r.kept_base = (uint64_t)total; r.n_want = 0; r.n_kept = d.verified && here ? tot[(size_t)k].x : 0; r.R = d.verified && here ? tot[(size_t)k].y : 0; r.overflow = 0;
+        kept_base[(size_t)k] = (unsigned long long)total;
         total += r.n_kept;
-        if (total > 0xfffffff0ll) return fail(c, L3D_ERR_UNSUPPORTED, "l3d_shard_chain_products: more than 2^32 kept matches on this rank (l3d_shard_chain_partition keeps a rank's share only)");
         best_off[(size_t)k] = d.verified ? (long long)(d.best - c->ch_best.as<float2>()) : 0;
         pvh[(size_t)k].verified = d.verified ? 1 : 0;
         pvh[(size_t)k].best = d.verified && here ? d.best : nullptr;
@@ -1201,10 +1201,10 @@ static int shard_products_local(l3d_shard_chain* h, const l3d_dense_map* map, l3
         return build_products(c, h->views, nv, pvh.data(), hres.data(), map, summary, n_pot, 0, -1, nullptr, qt_arena);
     }
     HIPCHK(c, c->ch_kept.reserve(((size_t)total + 64) * sizeof(Match)));
-    HIPCHK(c, hipMemcpyAsync(sc + o_kb, kept_base.data(), nvs * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(sc + o_kb, kept_base.data(), nvs * 8, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(sc + o_bo, best_off.data(), nvs * 8, hipMemcpyHostToDevice, st));
     if (nv > 0)
-        hipLaunchKernelGGL(k_shard_pack_all, dim3(8, h->world, nv), dim3(256), 0, st, h->gathered, h->geom, sc + o_ver, reinterpret_cast<const unsigned*>(sc + o_kb),
+        hipLaunchKernelGGL(k_shard_pack_all, dim3(8, h->world, nv), dim3(256), 0, st, h->gathered, h->geom, sc + o_ver, reinterpret_cast<const unsigned long long*>(sc + o_kb),
                            reinterpret_cast<const long long*>(sc + o_bo), c->ch_kept.as<Match>(), c->ch_best.as<float2>(), c->ch_bestpos.as<int>());
     HIPCHK(c, hipStreamSynchronize(st));                                 // (the upload sources above are locals)
     HIPCHK(c, hipGetLastError());

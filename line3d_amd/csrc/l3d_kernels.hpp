@@ -39,9 +39,11 @@ struct Hypothesis {                 // == l3d_hypothesis
 struct RtInfo { const int* rt; int S, N; };
 
 struct ChainResult {                // per view of the resident chain (device -> pinned host)
-    unsigned kept_base;             // first record of the view's slice of the kept arena (records of 32 bytes: 32 bits reach 137 GB)
-    int n_kept, R, overflow;
+    uint64_t kept_base;             // first record of the view's slice of the kept arena (64 bits: an arena may hold more than 2^32 records of 32 bytes)
+    int n_kept, R, overflow;        // (one view's list stays below 2^31 records)
+    int n_want;                     // overflow bit 2 (its slice did not fit the arena): the records the view keeps -- n_kept is 0 then; else 0
 };
+static_assert(sizeof(ChainResult) == 24 && alignof(ChainResult) == 8, "ChainResult: the layout the kernels, the pinned host copy and the uploads share");
 
 struct PairArgs {
     const float4* src_segs;         // S_src

@@ -412,9 +412,9 @@ __global__ __launch_bounds__(kPairThreads) void k_prode_transpose(const EarlyVie
     if (!v.rt || q >= v.N) return;
     const ChainResult r = res[v.k];
     const int St = v.St[q];
-    unsigned off = r.kept_base;
+    unsigned long long off = r.kept_base;
     for (int j = 0; j < q; ++j) off += (unsigned)pcnt_kq[(size_t)v.k * maxN + j];
-    if (threadIdx.x == 0) poff_kq[(size_t)v.k * maxN + q] = off;
+    if (threadIdx.x == 0) poff_kq[(size_t)v.k * maxN + q] = (unsigned)off;          // (the chain transposes early only while its arena is below 2^31 records)
     if (r.overflow || r.n_kept == 0 || St <= 0) return;                 // (an overflowed view is run again, and transposed again behind that run)
     pair_transpose_wg(qt_arena + r.kept_base, v.rt + (size_t)q * v.S, v.rt + (size_t)(q + 1) * v.S, v.S, St, g, boff + v.boff_off[q], E + off, T ? T + off : nullptr, cap, s_h, s_w, &s_kb);
 }
@@ -691,6 +691,8 @@ int l3d::build_products(l3d_ctx* c, const l3d_chain_view* views, int n_views, co
     std::vector<int> ps_alias_view;                         // dense view a ProdSrc's alias names (-1: none)
     long long total_kept = 0, early_slots = 0;
     for (int k = 0; k < n_views; ++k) if (pvh[k].verified) total_kept = std::max(total_kept, (long long)hres[k].kept_base + hres[k].n_kept);
+    // (best_ref packs (source rank << 40 | record index): arena positions must stay below 2^40 -- 35 TB of records)
+    if (total_kept > kBestIndexMask) return fail(c, L3D_ERR_UNSUPPORTED, "products: " + std::to_string(total_kept) + " kept matches in the arena -- best-match references hold 40-bit positions");
     int max_kept = 0, maxS = 1;
     for (int k = 0; k < n_views; ++k) {
         const l3d_chain_view& v = views[k];

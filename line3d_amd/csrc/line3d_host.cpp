@@ -610,6 +610,14 @@ int l3d_line3d_products_sizes(const l3d_line3d* h, int* n_views, int* n_dense, i
     if (n_hyp) *n_hyp = on ? (int)h->hyps.size() : 0;
     return L3D_OK;
 }
+int l3d_line3d_chain_summary(const l3d_line3d* h, const l3d_chain_summary** summary, int* n)
+{
+    if (!h || !summary || !n) return L3D_ERR_INVALID;
+    const bool on = h->resident_products;
+    *summary = on && !h->chain_summary.empty() ? h->chain_summary.data() : nullptr;
+    *n = on ? (int)h->chain_summary.size() : 0;
+    return L3D_OK;
+}
 int l3d_line3d_products_get(l3d_line3d* h, int32_t* seg_base, int64_t* pot_start, int32_t* pot_tgt, l3d_match* best, l3d_hypothesis* hyp, float* score)
 {
     if (!h) return L3D_ERR_INVALID;

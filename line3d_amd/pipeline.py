@@ -10,6 +10,9 @@ import numpy as np
 from . import capi
 from .capi import MATCH_DTYPE, EDGE_DTYPE, L3DError, _p
 
+# l3d_chain_summary (include/line3d_amd.h)
+SUMMARY_DTYPE = np.dtype([("verified", np.int32), ("n_kept", np.int32), ("n_candidates", np.int64), ("median_depth", np.float32), ("pad", np.int32)])
+
 
 class Line3D:
     def __init__(self, data_directory: str = "", matchingNeighbors: int = 10, uncertainty_t_upper_2D: float = 5.0,
@@ -331,6 +334,16 @@ class Line3D:
         self._chk(self.lib.l3d_line3d_products_get(self.h, _p(seg_base), _p(pot_start), _p(pot_tgt), _p(best), _p(hyp) if nh.value else None,
                                                    _p(score) if nh.value else None))
         return dict(seg_base=seg_base, pot_start=pot_start, pot_tgt=pot_tgt[:npot.value], best=best, hyp=hyp[:nh.value], score=score[:nh.value])
+
+    def chain_summary(self):
+        """Per chain view of the last match_views with resident products (the index of Context.chain_kept_list): structured array of
+        (verified, n_kept, n_candidates, median_depth); empty without resident products"""
+        p, n = C.c_void_p(), C.c_int(0)
+        self._chk(self.lib.l3d_line3d_chain_summary(self.h, C.byref(p), C.byref(n)))
+        out = np.zeros(n.value, dtype=SUMMARY_DTYPE)
+        if n.value:
+            C.memmove(out.ctypes.data, p, n.value * SUMMARY_DTYPE.itemsize)
+        return out
 
     def stats(self):
         s = (C.c_double * 12)()

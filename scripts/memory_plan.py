@@ -172,7 +172,7 @@ def main():
     print()
     print("| largest value a 32-bit field has to hold | " + " | ".join("kept %.1f %%" % (100 * k) for k in a.kept) + " | limit |")
     print("|---|" + "---|" * (len(a.kept) + 1))
-    limits = dict(arena_records_per_rank=(2**32, "ChainResult.kept_base, unsigned"), table_entries_per_rank=(2**63, "pot_start is 64-bit"), fill_candidates_per_rank=(2**63, "64-bit positions; blocks of sources"),
+    limits = dict(arena_records_per_rank=(2**40, "ChainResult.kept_base is 64-bit; best-match references hold 40-bit positions"), table_entries_per_rank=(2**63, "pot_start is 64-bit"), fill_candidates_per_rank=(2**63, "64-bit positions; blocks of sources"),
                   fill_block_candidates=(2**30, "int, per block of sources"), affinity_entries_job=(2**31, "l3d_edge lists: int nnz"), hypotheses_job=(2**31, "int"), kept_records_job=(2**63, "never indexed as a whole"))
     for key in plans[0][1]:
         lim, what = limits.get(key, (2**31, "int"))

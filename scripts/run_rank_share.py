@@ -38,7 +38,7 @@ def main():
     ap.add_argument("--window", type=int, default=64)
     ap.add_argument("--slot-records", type=int, default=0)
     ap.add_argument("--turn-period", type=int, default=5, help="synth.make_scene(turn_period=...): the helix repeats every that many turns (0: the default generator, whose radius grows with "
-                    "every turn -- at 2048 views the scene then keeps 10-17 M matches per view and a rank's share exceeds 2^32 records)")
+                    "every turn -- at 2048 views the scene then keeps 10-17 M matches per view: rank 3 of 8 holds 5.0e9 records, 160 GB of kept arena)")
     ap.add_argument("--cand-cap", type=int, default=0)
     ap.add_argument("--arena-records", type=int, default=0, help="records of the rank's compact arena (0: the library's first guess, grown by capacity verdicts -- each one re-runs the chain)")
     a = ap.parse_args()
