@@ -40,34 +40,19 @@ namespace l3d {
 
 // reverse matches for view `view_id` out of the kept lists of earlier views (blockIdx.y = source): count per
 // (segment, camera) row.  (seg, tgt) swap roles and the depth pairs swap, line3D.cc:847-856.
-constexpr int kCamScanMin = 262144;     // records of a source's list from which the side array is scanned first
-// cams (round 5): the target camera of every record of the arena, written beside it by the kept writer -- a later view reads 4 bytes per record
-// of its sources' lists and the 32-byte record only where it points at that view (one in N): at 4000 segments x 24 neighbours the two scans of a
-// view's sources were 2.9 GB of reads per view
-__global__ void k_exist_count(const Match* __restrict__ arena, const unsigned* __restrict__ cams, const ChainResult* __restrict__ res, const int* __restrict__ src_index,
+// Short lists -- config 2 keeps 36 k matches per view, 1.2 MB -- are scanned record by record: one pass over cache-resident data beats the run tables' extra
+// level of dependent loads (12.2 vs 12.9 ms per config-2 pass).  Once the views keep more than kLongList records each on average, the following views
+// read their sources' runs instead (k_exist_count_rt, k_place_rt), and the chain transposes the products' pairs itself (L3D_PROD_EARLY=1).
+constexpr int kLongList = 262144;
+__global__ void k_exist_count(const Match* __restrict__ arena, const ChainResult* __restrict__ res, const int* __restrict__ src_index,
                               const int* __restrict__ src_cam, unsigned view_id, int N, int S, int* __restrict__ rowcnt)
 {
     const ChainResult* src = res + src_index[blockIdx.y];
     const int cam = src_cam[blockIdx.y];
     const int n = src->n_kept;
     const Match* kept = arena + src->kept_base;
-    // (short lists -- config 2 keeps 36 k matches per view, 1.2 MB -- are scanned record by record: one pass over cache-resident data beats two
-    // dependent ones; measured 12.10 vs 12.17-12.29 ms per config-2 pass, 173.2 vs 165.4 ms at 40 x 4000 x 24, profiles/r5_ab_kept_cams.txt)
-    const unsigned* kc = cams && n > kCamScanMin ? cams + src->kept_base : nullptr;
     const int stride = gridDim.x * blockDim.x;
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (kc) {
-        // the side array four entries at a time: one 4-byte load in flight per thread was 1.1 TB/s of a scan that has nothing else to wait for
-        for (; i + 3 * stride < n; i += 4 * stride) {
-            const unsigned c0 = kc[i], c1 = kc[i + stride], c2 = kc[i + 2 * stride], c3 = kc[i + 3 * stride];
-            if (c0 == view_id) { const Match r = kept[i]; if ((int)r.segID2 < S) atomicAdd(&rowcnt[r.segID2 * N + cam], 1); }
-            if (c1 == view_id) { const Match r = kept[i + stride]; if ((int)r.segID2 < S) atomicAdd(&rowcnt[r.segID2 * N + cam], 1); }
-            if (c2 == view_id) { const Match r = kept[i + 2 * stride]; if ((int)r.segID2 < S) atomicAdd(&rowcnt[r.segID2 * N + cam], 1); }
-            if (c3 == view_id) { const Match r = kept[i + 3 * stride]; if ((int)r.segID2 < S) atomicAdd(&rowcnt[r.segID2 * N + cam], 1); }
-        }
-    }
-    for (; i < n; i += stride) {
-        if (kc && kc[i] != view_id) continue;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const Match r = kept[i];
         if (r.camID2 == view_id && (int)r.segID2 < S) atomicAdd(&rowcnt[r.segID2 * N + cam], 1);
     }
@@ -116,13 +101,6 @@ __global__ __launch_bounds__(256) void k_exist_combine(int* __restrict__ part, c
     for (int ch = 0; ch < kExistChunks; ++ch) { const int t = p[(size_t)ch * S]; p[(size_t)ch * S] = run; run += t; }
     if (run) atomicAdd(&rowcnt[u * N + src_cam[j]], run);           // (one thread per cell: the atomic only keeps the add whole beside stage 1's rows of other cameras)
 }
-// the side array of records that did not come from the kept writer (a block's sources taken over from another rank)
-__global__ void k_cams_of_records(const Match* __restrict__ arena, long long n, unsigned* __restrict__ cams)
-{
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) cams[i] = arena[i].camID2;
-}
-
 // The scatter order inside a (segment, camera) run is arbitrary.  One wave per run restores the (segment, camera,
 // target) order of the reference's list sort: every lane holds up to four entries in registers, ranks them by
 // counting (keys are broadcast with shuffles, target ids inside a run are distinct) and writes them to their place.
@@ -139,61 +117,29 @@ __global__ __launch_bounds__(256) void k_exist_sort_runs(const int* __restrict__
     sort_exist_run(lane, b, n, cam, meta, depths, stage, stage_stride, stage_key);      // (stage: the verification's scratch + confidence slots, unused until it runs)
 }
 
-// Stage-1 candidates of a view are written (k_pair_fill, stage-1 stream, well ahead of the chain) in their own
-// (segment, to-be-matched camera) row order; once the reverse matches of the view are counted, each row is moved to its
-// place in the combined (segment, camera, target) order -- a 24-byte copy per candidate instead of the triangulation on the
-// chain's critical path.  One wave per row (the first workgroups of k_place).
 // Both writers of the combined candidate arrays in one launch (independent: stage-1 candidates go to the rows of the cameras
-// to be matched, reverse matches to the rows of the source cameras): the first `blocks_move` workgroups move the stage-1 rows, the
-// others scatter the reverse matches (bps workgroups per source view).
+// to be matched, reverse matches to the rows of the source cameras): the first `blocks_move` workgroups move the stage-1 rows
+// (move_stage1_row), the others scatter the reverse matches of short lists (bps workgroups per source view).
 __global__ __launch_bounds__(256) void k_place(int blocks_move, int bps, const int* __restrict__ tbm, int n_tbm, const int* __restrict__ rowA,
                                                const uint2* __restrict__ metaA, const float4* __restrict__ depthsA,
-                                               const Match* __restrict__ arena, const unsigned* __restrict__ cams, const ChainResult* __restrict__ res, const int* __restrict__ src_index,
+                                               const Match* __restrict__ arena, const ChainResult* __restrict__ res, const int* __restrict__ src_index,
                                                const int* __restrict__ src_cam, unsigned view_id, int N, int S,
                                                const int* __restrict__ row_start, int* __restrict__ cursor,
                                                uint2* __restrict__ meta, float4* __restrict__ depths, int cap)
 {
     if (row_start[(size_t)S * N] > cap) return;                  // overflow: the chain is re-run with more room
-    if ((int)blockIdx.x < blocks_move) {
-        const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-        if (row >= S * n_tbm) return;
-        const int y = row / n_tbm, cam = tbm[row % n_tbm];
-        const int a = rowA[y * N + cam], b = row_start[y * N + cam], n = row_start[y * N + cam + 1] - b;   // (rowA may have been laid out for an upper bound of the row)
-        for (int j = lane; j < n; j += 64) { meta[b + j] = metaA[a + j]; depths[b + j] = depthsA[a + j]; }
-        return;
-    }
+    if ((int)blockIdx.x < blocks_move) { move_stage1_row(0, S, tbm, n_tbm, N, rowA, metaA, depthsA, row_start, meta, depths); return; }
     const int e = (int)blockIdx.x - blocks_move, si = e / bps, bx = e % bps;         // bps workgroups per source view
     const ChainResult* src = res + src_index[si];
     const int cam = src_cam[si];
     const int n = src->n_kept;
     const Match* kept = arena + src->kept_base;
-    const unsigned* kc = cams && n > kCamScanMin ? cams + src->kept_base : nullptr;
-    auto place = [&](int i) {
+    for (int i = bx * 256 + (int)threadIdx.x; i < n; i += bps * 256) {
         const Match r = kept[i];
-        if (r.camID2 == view_id && (int)r.segID2 < S) {
-            const int row = r.segID2 * N + cam;
-            const int slot = row_start[row] + atomicAdd(&cursor[row], 1);
-            meta[slot] = make_uint2(r.segID1, (unsigned)cam);
-            depths[slot] = make_float4(r.depths[2], r.depths[3], r.depths[0], r.depths[1]);
-        }
-    };
-    const int stride = bps * 256;
-    int i = bx * 256 + (int)threadIdx.x;
-    if (kc) {                                                    // (four entries of the side array in flight per thread: k_exist_count)
-        for (; i + 3 * stride < n; i += 4 * stride) {
-            const unsigned c0 = kc[i], c1 = kc[i + stride], c2 = kc[i + 2 * stride], c3 = kc[i + 3 * stride];
-            if (c0 == view_id) place(i);
-            if (c1 == view_id) place(i + stride);
-            if (c2 == view_id) place(i + 2 * stride);
-            if (c3 == view_id) place(i + 3 * stride);
-        }
-    }
-    for (; i < n; i += stride) {
-        if (kc && kc[i] != view_id) continue;
-        place(i);
+        if (r.camID2 == view_id && (int)r.segID2 < S) place_reverse_match(r, N, cam, row_start, cursor, meta, depths);
     }
 }
-// k_place with run tables (default): the stage-1 rows are moved as in k_place, the reverse matches come from the sources' runs towards this view through the
+// k_place for long lists: the stage-1 rows are moved as in k_place, the reverse matches come from the sources' runs towards this view through the
 // global row cursors -- 6000 small workgroups in one launch with the move: faster than 192 (or 768) big ones with LDS cursors in a launch of their own
 // (cand_move 12.0 against 17.1 / 13.2 ms at 40 x 4000 x 24, NOTEBOOK 12.f; the LDS-cursor variant is retired)
 __global__ __launch_bounds__(256) void k_place_rt(int blocks_move, int bps, const int* __restrict__ tbm, int n_tbm, const int* __restrict__ rowA,
@@ -204,14 +150,7 @@ __global__ __launch_bounds__(256) void k_place_rt(int blocks_move, int bps, cons
                                                   const RtInfo* __restrict__ info, const int* __restrict__ src_slot, int g)
 {
     if (row_start[(size_t)S * N] > cap) return;
-    if ((int)blockIdx.x < blocks_move) {
-        const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-        if (row >= S * n_tbm) return;
-        const int y = row / n_tbm, cam = tbm[row % n_tbm];
-        const int a = rowA[y * N + cam], b = row_start[y * N + cam], n = row_start[y * N + cam + 1] - b;
-        for (int j = lane; j < n; j += 64) { meta[b + j] = metaA[a + j]; depths[b + j] = depthsA[a + j]; }
-        return;
-    }
+    if ((int)blockIdx.x < blocks_move) { move_stage1_row(0, S, tbm, n_tbm, N, rowA, metaA, depthsA, row_start, meta, depths); return; }
     const int e = (int)blockIdx.x - blocks_move, sj = e / bps, bx = e % bps;
     const int si = src_index[sj], cam = src_cam[sj], slot = src_slot[sj];
     const RtInfo w = info[si];
@@ -224,18 +163,13 @@ __global__ __launch_bounds__(256) void k_place_rt(int blocks_move, int bps, cons
         const int a = r0[sg], b = r1[sg];
         for (int i = a + gl; i < b; i += g) {
             const Match r = kept[i];
-            if ((int)r.segID2 < S) {
-                const int row = r.segID2 * N + cam;
-                const int sl = row_start[row] + atomicAdd(&cursor[row], 1);
-                meta[sl] = make_uint2(r.segID1, (unsigned)cam);
-                depths[sl] = make_float4(r.depths[2], r.depths[3], r.depths[0], r.depths[1]);
-            }
+            if ((int)r.segID2 < S) place_reverse_match(r, N, cam, row_start, cursor, meta, depths);
         }
     }
 }
 // Kept records of a view into its slice of the arena, in ONE launch behind the verification: each workgroup (one segment) sums
-// the kept counts in front of its segment itself (at most a few thousand ints out of L2) instead of waiting for a scan
-// launch, and the slice starts where the previous verified view's ended (its result record) -- no cursor, no atomics.
+// the kept counts in front of its segment itself (kept_before_total), and the slice starts where the previous verified view's
+// ended (its result record) -- no cursor, no atomics.
 // Workgroup 0 also writes the view's result record (device copy for later views, host-mapped copy for the host).
 __global__ __launch_bounds__(256) void k_kept_write_chain(VerifyArgs a, const int* __restrict__ kept_cnt, int nrow, const ChainResult* __restrict__ prev,
                                                           unsigned long long arena_cap, ChainResult* __restrict__ res, ChainResult* __restrict__ res_host,
@@ -246,16 +180,11 @@ __global__ __launch_bounds__(256) void k_kept_write_chain(VerifyArgs a, const in
     __shared__ int s_cnt[32];
     __shared__ int s_qcnt[256];
     __shared__ unsigned long long s_best[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int nseg = a.seg_end - a.seg_begin;
     const int yl = blockIdx.x;
-    int before = 0, total = 0;
-    for (int i = tid; i < nseg; i += 256) { const int v = kept_cnt[a.seg_begin + i]; total += v; if (i < yl) before += v; }
-    for (int o = 32; o > 0; o >>= 1) { before += __shfl_down(before, o); total += __shfl_down(total, o); }
-    if (lane == 0) { s_red[wave] = before; s_red[4 + wave] = total; }
-    __syncthreads();
-    before = s_red[0] + s_red[1] + s_red[2] + s_red[3];
-    total = s_red[4] + s_red[5] + s_red[6] + s_red[7];
+    int before, total;
+    kept_before_total(kept_cnt + a.seg_begin, nseg, yl, s_red, before, total);
     ChainResult r;
     r.R = a.row_start[nrow];
     r.overflow = r.R > a.cand_cap ? 1 : 0;
@@ -270,9 +199,9 @@ __global__ __launch_bounds__(256) void k_kept_write_chain(VerifyArgs a, const in
 }
 
 void launch_exist_count(const Match* arena, const ChainResult* res, const int* src_index, const int* src_cam, int n_src, unsigned view_id,
-                        int N, int S, int* rowcnt, hipStream_t st, const unsigned* cams, int bps)
+                        int N, int S, int* rowcnt, hipStream_t st, int bps)
 {
-    if (n_src > 0) hipLaunchKernelGGL(k_exist_count, dim3(std::max(1, bps), n_src), dim3(256), 0, st, arena, cams, res, src_index, src_cam, view_id, N, S, rowcnt);
+    if (n_src > 0) hipLaunchKernelGGL(k_exist_count, dim3(std::max(1, bps), n_src), dim3(256), 0, st, arena, res, src_index, src_cam, view_id, N, S, rowcnt);
 }
 void launch_exist_sort_runs(const int* cams, int n_cams, int N, int S, const int* row_start, uint2* meta, float4* depths, int cap, hipStream_t st,
                             int seg_begin, int seg_end, float* stage, long long stage_stride, unsigned* stage_key)
@@ -283,7 +212,7 @@ void launch_exist_sort_runs(const int* cams, int n_cams, int N, int S, const int
 }
 void launch_place(const int* tbm, int n_tbm, int N, int S, const int* rowA, const uint2* metaA, const float4* depthsA,
                   const Match* arena, const ChainResult* res, const int* src_index, const int* src_cam, int n_src, unsigned view_id,
-                  const int* row_start, int* cursor, int cand_cap, uint2* meta, float4* depths, hipStream_t st, const unsigned* cams, int bps,
+                  const int* row_start, int* cursor, int cand_cap, uint2* meta, float4* depths, hipStream_t st, int bps,
                   const RtInfo* info, const int* src_slot, int g)
 {
     bps = std::max(1, bps);
@@ -291,7 +220,7 @@ void launch_place(const int* tbm, int n_tbm, int N, int S, const int* rowA, cons
     const int blocks = blocks_move + bps * n_src;
     if (info) { if (blocks > 0) hipLaunchKernelGGL(k_place_rt, dim3(blocks), dim3(256), 0, st, blocks_move, bps, tbm, n_tbm, rowA, metaA, depthsA, arena, res, src_index, src_cam,
                                                          N, S, row_start, cursor, meta, depths, cand_cap, info, src_slot, std::max(1, g)); }
-    else if (blocks > 0) hipLaunchKernelGGL(k_place, dim3(blocks), dim3(256), 0, st, blocks_move, bps, tbm, n_tbm, rowA, metaA, depthsA, arena, cams, res, src_index, src_cam,
+    else if (blocks > 0) hipLaunchKernelGGL(k_place, dim3(blocks), dim3(256), 0, st, blocks_move, bps, tbm, n_tbm, rowA, metaA, depthsA, arena, res, src_index, src_cam,
                                             view_id, N, S, row_start, cursor, meta, depths, cand_cap);
 }
 void launch_exist_count_rt(const unsigned* qt_arena, const RtInfo* info, const ChainResult* res, const int* src_index, const int* src_cam, const int* src_slot, int n_src, int g,
@@ -365,11 +294,10 @@ static int run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_c
     // the ring covers every view that can be in flight between the one being collected and the newest stage 1: after an
     // overflow ALL of them are refilled before any of their chains runs again (bit rows and stage-1 candidates alike)
     const int kAhead = L3D_AHEAD, kStage1Ahead = L3D_S1AHEAD, kRing = kAhead + kStage1Ahead + 3;
-    // run tables (round 6): the kept writer fills one per view and packs (local camera, target) into the side array; later views and the products
-    // read runs instead of scanning lists.  L3D_RUN_TABLES=0 / L3D_KEPT_CAMS=0: the A/B paths (side array of global camera ids / none)
-    const bool use_rt = c->opt.run_tables != 0 && c->opt.kept_cams != 0;
-    if (int rc = chain_assign_arenas(c, views, n_views, vd, L, true, true, kRing, st, use_rt)) return rc;
-    if (use_rt) {
+    // run tables (round 6): the kept writer fills one per view and leaves a (local camera << 16 | target) word per record in the side array
+    // (ch_keptcam); later views and the products read runs instead of scanning lists
+    if (int rc = chain_assign_arenas(c, views, n_views, vd, L, true, true, kRing, st, true)) return rc;
+    {
         std::vector<RtInfo>& info = c->rtinfo_host;     // (lives in the context: the upload is asynchronous)
         info.resize((size_t)n_views);
         for (int k = 0; k < n_views; ++k) info[(size_t)k] = RtInfo{ vd[(size_t)k].rt, views[k].S_src, views[k].N };
@@ -457,7 +385,6 @@ static int run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_c
         arena_cap += (size_t)pre_records;
     }
 
-    const bool use_cams = c->opt.kept_cams != 0;         // (0: A/B -- the sources' lists are scanned record by record)
     // early pair transposes (round 6, l3d_products.hip): a (view, camera) pair of the potential-correspondence build depends on that view's kept list alone, so
     // it is transposed on a side stream right behind the view's kept writer -- next to the following views' chains -- and the end of matchViews finds only the rows
     // left.  Entries live in an array aligned with the kept arena (a view's pairs hold exactly its records).  L3D_PROD_EARLY=0: all transposes at the end (A/B)
@@ -465,11 +392,11 @@ static int run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_c
     // Long lists only (> 2^18 records per view: what the last pass over this scene kept, or the arena's first guess), view by view.  At config 2 (36 k records per view)
     // two launches and an event per view cost more than the 0.2 ms of transposes they take off the end (12.60 vs 12.41 ms per pass); eight views per launch still lose
     // (12.52 vs 12.41; the first pass pays 5 ms for the side stream and its buffers).  Option values 2 / 3 force a view / eight views per launch (tests)
-    bool early = map && use_rt && !ranged && !pre && !cb && c->opt.prod_early != 0 && c->opt.prod_transpose != 0 && maxN > 0;
+    bool early = map && !ranged && !pre && !cb && c->opt.prod_early != 0 && c->opt.prod_transpose != 0 && maxN > 0;
     int early_batch = c->opt.prod_early == 3 ? 8 : 1;
     if (early && c->opt.prod_early == 1) {
         const double per_view = (same_scene && c->chain_seen_kept > 0 ? c->chain_seen_kept : pairs * 0.004) / std::max(1, n_views);
-        early = per_view > (double)kCamScanMin;
+        early = per_view > (double)kLongList;
     }
     int early_next = 0;                 // views [0, early_next) have their transposes launched
     hipStream_t sp = nullptr;
@@ -519,7 +446,7 @@ static int run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_c
     auto reserve_caps = [&]() -> int {
         if (int rc = chain_reserve_candidates(c, L, cand_cap, kRing)) return rc;
         HIPCHK(c, c->ch_kept.reserve(arena_cap * sizeof(Match)));
-        if (use_cams) HIPCHK(c, c->ch_keptcam.reserve(arena_cap * 4 + 64));
+        HIPCHK(c, c->ch_keptcam.reserve(arena_cap * 4 + 64));
         if (early && arena_cap < 0x7ffffff0ull) { HIPCHK(c, PE.e_E.reserve(arena_cap * 4 + 64)); HIPCHK(c, PE.e_T.reserve(arena_cap * 4 + 64)); }
         return L3D_OK;
     };
@@ -541,15 +468,15 @@ static int run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_c
             }
         }
         if (base > 0) HIPCHK(c, hipMemcpyAsync(c->ch_kept.p, pre->records, (size_t)base * sizeof(Match), hipMemcpyDeviceToDevice, st));
-        if (base > 0 && use_cams && !use_rt) hipLaunchKernelGGL(k_cams_of_records, dim3((unsigned)((base + 255) / 256)), dim3(256), 0, st, c->ch_kept.as<Match>(), base, c->ch_keptcam.as<unsigned>());
-        if (base > 0 && use_rt) {
+        if (base > 0) {
             // the taken-over lists did not come out of this chain's kept writer: their side array and run tables are rebuilt from the records
             std::vector<RtJob> jobs;
             std::vector<unsigned> ids;
             std::vector<int> qs;
             std::vector<size_t> at;
             for (int k = pre->k0; k < pre->k1; ++k) {
-                if (!has_rec[(size_t)k] || hres[k].n_kept == 0 || !vd[(size_t)k].rt) continue;
+                if (!has_rec[(size_t)k] || hres[k].n_kept == 0) continue;
+                if (!vd[(size_t)k].rt) return fail(c, L3D_ERR_INVALID, "match_chain: view " + std::to_string(k) + " was taken over with records but has no run table");
                 std::vector<std::pair<unsigned, int>> byid;
                 for (int q = 0; q < views[k].N; ++q) byid.push_back({ views[k].local2global[q], q });
                 std::sort(byid.begin(), byid.end());
@@ -649,30 +576,29 @@ static int run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_c
         const int* d_sc = reinterpret_cast<const int*>(dtab + d.o_sc);
         (void)hipGetLastError();
         const int* d_si = reinterpret_cast<const int*>(dtab + d.o_si);
-        unsigned* cams = use_cams ? c->ch_keptcam.as<unsigned>() : nullptr;
+        unsigned* cams = c->ch_keptcam.as<unsigned>();
         // workgroups per source view of the two scans of the sources' lists: a thread walks its stride of a list with dependent loads, so the list
         // must be spread over enough of them -- 32 x 256 threads take config 2's 36 k records in 5 steps, but 3.5 M records (4000 x 24) in 430:
         // sized from the lists the chain has seen so far (the host trails a few views behind)
         const int bps = (int)std::min(512.0, std::max(32.0, (views_seen > 0 ? kept_seen / views_seen : 0.0) / 4096.0));
         // run tables: g lanes per run (the average run of the lists seen so far, rounded up to a power of two), workgroups per source to cover its segments
         const int* d_ss = reinterpret_cast<const int*>(dtab + d.o_ss);
-        const RtInfo* d_info = use_rt ? c->ch_rtinfo.as<RtInfo>() : nullptr;
+        const RtInfo* d_info = c->ch_rtinfo.as<RtInfo>();
+        const double avg_run = views_seen > 0 ? kept_seen / views_seen / std::max(1.0, (double)S * std::max(1, N)) : 1.0;
         int rt_g = 1;
-        if (use_rt) { const double avg_run = views_seen > 0 ? kept_seen / views_seen / std::max(1.0, (double)S * std::max(1, N)) : 1.0; while (rt_g < 64 && rt_g < avg_run) rt_g <<= 1; }
+        while (rt_g < 64 && rt_g < avg_run) rt_g <<= 1;
         if (c->opt.rt_g > 0) rt_g = c->opt.rt_g;
         const int rt_bps = std::max(1, std::min(512, (L.maxS * std::max(1, rt_g) + 255) / 256));
-        // short lists (config 2 keeps 36 k matches per view) are scanned record by record as before: one pass over cache-resident data beats the run
-        // tables' extra level of dependent loads (12.2 vs 12.9 ms per config-2 pass); the side array holds (camera, target) words then, not camera ids
-        const bool rt_exist = use_rt && views_seen > 0 && kept_seen / views_seen > (double)kCamScanMin;
-        const unsigned* scan_cams = use_rt ? nullptr : cams;
+        // short lists (config 2 keeps 36 k matches per view) are scanned record by record: k_exist_count
+        const bool rt_exist = views_seen > 0 && kept_seen / views_seen > (double)kLongList;
         if (rt_exist) { ProfScope p(c, "exist"); launch_exist_count_rt(cams, d_info, dres, d_si, d_sc, d_ss, v.n_sources, rt_g, N, S, d.rowcnt, c->ch_existpart.as<int>(), st); }
-        else { ProfScope p(c, "exist"); launch_exist_count(arena, dres, d_si, d_sc, v.n_sources, v.view_id, N, S, d.rowcnt, st, scan_cams, bps); }
+        else { ProfScope p(c, "exist"); launch_exist_count(arena, dres, d_si, d_sc, v.n_sources, v.view_id, N, S, d.rowcnt, st, bps); }
         // combined row starts (+ zeroed scatter cursors, + the segments ordered longest first for the verification launch)
         { ProfScope p(c, "scan"); launch_scan(d.rowcnt, c->row_start.as<int>(), (int)nrow, c->ch_cursor.as<int>(), st, c->ch_segorder.as<int>(), N, 0, S); }
         {
             ProfScope p(c, "cand_move");
             launch_place(pa.tbm, v.n_tbm, N, S, d.rowA, ringA_meta(k), ringA_depths(k), arena, dres, d_si, d_sc, v.n_sources, v.view_id,
-                         c->row_start.as<int>(), c->ch_cursor.as<int>(), (int)cand_cap, c->cand_meta.as<uint2>(), c->cand_depths.as<float4>(), st, scan_cams, rt_exist ? rt_bps : bps,
+                         c->row_start.as<int>(), c->ch_cursor.as<int>(), (int)cand_cap, c->cand_meta.as<uint2>(), c->cand_depths.as<float4>(), st, rt_exist ? rt_bps : bps,
                          rt_exist ? d_info : nullptr, d_ss, rt_g);
         }
         if (v.n_sources && !(c->verify_mode == 0 && verify_window_supported(N))) {     // (the window kernel orders the runs itself)
@@ -689,7 +615,7 @@ static int run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_c
             int pv = k - 1;
             while (pv >= 0 && !has_rec[(size_t)pv]) --pv;                    // the arena slice starts where the previous verified (or preloaded) view's ended
             launch_kept_write_chain(va, c->kept_cnt.as<int>(), (int)nrow, pv >= 0 ? dres + pv : nullptr, (unsigned long long)arena_cap, dres + k, hres_dev + k,
-                                    reinterpret_cast<const unsigned*>(dtab + d.o_l2g), arena, st, (map || ranged) ? d.bestpos : nullptr, cams, use_rt ? d.rt : nullptr, S);
+                                    reinterpret_cast<const unsigned*>(dtab + d.o_l2g), arena, st, (map || ranged) ? d.bestpos : nullptr, cams, d.rt, S);
         }
         { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return fail(c, L3D_ERR_HIP, std::string("chain launch, view ") + std::to_string(k) + ": " + hipGetErrorString(e_)); }
         // (with a delivery callback the host starts D2H copies of device memory once it has seen this event: a default, fenced event then)
@@ -697,7 +623,6 @@ static int run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_c
         HIPCHK(c, hipEventRecord(ev[(size_t)k], st));
         if (early && arena_cap < 0x7ffffff0ull && k + 1 - early_next >= early_batch) {
             HIPCHK(c, hipStreamWaitEvent(sp, ev[(size_t)k], 0));
-            const double avg_run = views_seen > 0 ? kept_seen / views_seen / std::max(1.0, (double)S * std::max(1, N)) : 1.0;
             launch_early_transposes(c, reinterpret_cast<const EarlyView*>(PE.e_tab.as<int>() + (size_t)n_views * maxN * 2), early_next, k + 1 - early_next, maxN, early_maxSt, dres, cams, PE.e_cnt.as<int>(),
                                     PE.e_poff.as<unsigned>(), PE.e_boff.as<int>(), PE.e_E.as<unsigned>(), PE.e_T.as<unsigned>(), avg_run, sp);
             early_next = k + 1;
@@ -830,7 +755,7 @@ static int run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_c
                     size_t fr = 0, tot = 0;
                     if (hipMemGetInfo(&fr, &tot) == hipSuccess) {
                         if (c->opt.regrow_free_mb > 0) fr = std::min(fr, (size_t)c->opt.regrow_free_mb << 20);     // (tests: a card with less room)
-                        const size_t per_rec = sizeof(Match) + (use_cams ? 4 : 0) + (early && new_cap < 0x7ffffff0ull ? 4 : 0) + (map ? 8 : 0);
+                        const size_t per_rec = sizeof(Match) + 4 + (early && new_cap < 0x7ffffff0ull ? 4 : 0) + (map ? 8 : 0);
                         const size_t reserve = map ? (size_t)((1ll << 28) * 24) + ((size_t)1 << 30) : (size_t)512 << 20;
                         const size_t fits = fr > reserve ? (fr - reserve) / per_rec : 0;
                         if (new_cap > fits) {
@@ -866,9 +791,9 @@ static int run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_c
                 if (c->opt.timing) fprintf(stderr, "[l3d match_chain]   arena of %zu MB: hipMalloc %.2f ms, copy of %zu MB %.2f ms, hipFree of the old one %.2f ms\n", new_cap * sizeof(Match) >> 20, (t_m1 - t_m0) * 1e3,
                                            (size_t)r.kept_base * sizeof(Match) >> 20, (t_m2 - t_m1) * 1e3, (now_s() - t_m2) * 1e3);
                 c->ch_kept.p = np; c->ch_kept.cap = new_cap * sizeof(Match);
-                if (use_cams) {                             // (the side array grows with it, its used part kept)
+                {                                           // (the side array grows with it, its used part kept)
                     void* nc = nullptr;
-                    if (!hip_ok(hipMalloc(&nc, new_cap * 4 + 64), "hipMalloc (target cameras of the kept arena)")) break;
+                    if (!hip_ok(hipMalloc(&nc, new_cap * 4 + 64), "hipMalloc (side words of the kept arena)")) break;
                     if (!hip_ok(hipMemcpy(nc, c->ch_keptcam.p, (size_t)r.kept_base * 4, hipMemcpyDeviceToDevice), "hipMemcpy")) { (void)hipFree(nc); break; }
                     (void)hipFree(c->ch_keptcam.p);
                     c->ch_keptcam.p = nc; c->ch_keptcam.cap = new_cap * 4 + 64;
@@ -914,7 +839,7 @@ static int run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_c
         // ---- the products of matchViews, on the device, from the arena (l3d_products.hip); enqueued behind the last view
         std::vector<ProdChainView> pv((size_t)n_views);
         for (int k = 0; k < n_views; ++k) pv[(size_t)k] = ProdChainView{ vd[(size_t)k].verified ? vd[(size_t)k].best : nullptr, vd[(size_t)k].verified ? vd[(size_t)k].bestpos : nullptr, vd[(size_t)k].verified ? 1 : 0,
-                                                                         use_rt && vd[(size_t)k].verified ? vd[(size_t)k].rt : nullptr };
+                                                                         vd[(size_t)k].verified ? vd[(size_t)k].rt : nullptr };
         ProdEarly pe;
         const bool early_done = early && arena_cap < 0x7ffffff0ull;
         if (early_done) {
@@ -931,7 +856,7 @@ static int run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_c
             pe.pcnt_kq = PE.e_cnt.as<int>(); pe.poff_kq = PE.e_poff.as<unsigned>(); pe.boff = PE.e_boff.as<int>(); pe.E = PE.e_E.as<unsigned>();
             pe.boff_off_host = PE.e_boff_off.data(); pe.maxN = maxN;
         }
-        rc_final = build_products(c, views, n_views, pv.data(), hres, map, summary, n_pot, 0, -1, nullptr, use_rt ? c->ch_keptcam.as<unsigned>() : nullptr, early_done ? &pe : nullptr);
+        rc_final = build_products(c, views, n_views, pv.data(), hres, map, summary, n_pot, 0, -1, nullptr, c->ch_keptcam.as<unsigned>(), early_done ? &pe : nullptr);
     }
     if (c->opt.timing)
         fprintf(stderr, "[l3d match_chain] setup %.2f ms | enqueue + watch loop %.2f ms (waiting: view results %.2f, stage-1 statistics %.2f) | delivery thread: d2h %.2f, callback %.2f\n",

@@ -177,7 +177,7 @@ int chain_upload_tables(l3d_ctx* c, const l3d_chain_view* views, int n_views, st
     return L3D_OK;
 }
 
-int chain_assign_arenas(l3d_ctx* c, const l3d_chain_view* views, int n_views, std::vector<ChainViewDev>& vd, ChainLayout& L, bool fused_rows, bool best_positions, int mask_ring, hipStream_t st, bool run_tables)
+int chain_assign_arenas(l3d_ctx* c, const l3d_chain_view* views, int n_views, std::vector<ChainViewDev>& vd, ChainLayout& L, bool fused_rows, bool best_positions, int mask_ring, hipStream_t st, bool with_rt)
 {
     const size_t nv = (size_t)n_views;
     HIPCHK(c, c->ch_mask.reserve((mask_ring > 0 ? std::min(L.mask_bytes, (size_t)mask_ring * L.max_mask_bytes) : L.mask_bytes) + 16));
@@ -191,7 +191,7 @@ int chain_assign_arenas(l3d_ctx* c, const l3d_chain_view* views, int n_views, st
     HIPCHK(c, c->ch_best.reserve(L.best_elems * 8 + 16));
     if (best_positions) HIPCHK(c, c->ch_bestpos.reserve(L.best_elems * 4 + 16));
     HIPCHK(c, hipMemsetAsync(c->ch_rowcnt.p, 0, (L.rowcnt_ints + 2 * nv) * 4, st));
-    if (run_tables) HIPCHK(c, c->ch_rt.reserve((L.rowcnt_ints + L.best_elems + 4 * nv) * 4 + 64));      // (N + 1) x S ints per verified view
+    if (with_rt) HIPCHK(c, c->ch_rt.reserve((L.rowcnt_ints + L.best_elems + 4 * nv) * 4 + 64));      // (N + 1) x S ints per verified view
     size_t mo = 0, ro = 0, bo = 0, ao = 0, ko = 0, to = 0;
     int* stats_base = c->ch_rowcnt.as<int>() + L.rowcnt_ints;
     for (int k = 0; k < n_views; ++k) {
@@ -217,7 +217,7 @@ int chain_assign_arenas(l3d_ctx* c, const l3d_chain_view* views, int n_views, st
         d.best = c->ch_best.as<float2>() + bo;
         d.bestpos = best_positions ? c->ch_bestpos.as<int>() + bo : nullptr;
         bo += (size_t)v.S_src;
-        d.rt = run_tables ? c->ch_rt.as<int>() + to : nullptr;
+        d.rt = with_rt ? c->ch_rt.as<int>() + to : nullptr;
         to += (((size_t)v.N + 1) * v.S_src + 3) & ~(size_t)3;
     }
     const size_t nrow_max = (size_t)L.maxS * L.maxN;

@@ -21,7 +21,7 @@ struct ChainViewDev {               // device addresses of one view's static tab
     int* stats = nullptr;           // {raw total, raw max per segment}
     float2* best = nullptr;
     int* bestpos = nullptr;         // per segment: position (in the view's kept slice) of its best kept match or -1 (k_kept_write_chain)
-    int* rt = nullptr;              // run table of the view's kept list, (N + 1) x S (l3d_runtable.hpp; single-GPU chain with run tables)
+    int* rt = nullptr;              // run table of the view's kept list, (N + 1) x S (l3d_runtable.hpp; the single-GPU chain's verified views)
     float4* rays = nullptr;         // unit viewing rays of the target endpoints (2 per target entry), k_tgt_rays
     float4* src_rays = nullptr;     // ... of the view's own end points (2 per source segment)
     int W64 = 0, maxW = 0;
@@ -45,7 +45,7 @@ int chain_upload_tables(l3d_ctx* c, const l3d_chain_view* views, int n_views, st
 // hands every view its slices; zeroes what the kernels add into.
 // mask_ring: slots of the bit-row arena (a view's bit rows live from its k_pair_mask to its k_pair_fill, both on the stage-1 stream in order:
 // two slots instead of one slice per view -- 24.6 MB x 2048 views = 50 GB at 4000 segments x 24 neighbours); 0: one slice per view.
-int chain_assign_arenas(l3d_ctx* c, const l3d_chain_view* views, int n_views, std::vector<ChainViewDev>& vd, ChainLayout& L, bool fused_rows, bool best_positions, int mask_ring, hipStream_t st, bool run_tables = false);
+int chain_assign_arenas(l3d_ctx* c, const l3d_chain_view* views, int n_views, std::vector<ChainViewDev>& vd, ChainLayout& L, bool fused_rows, bool best_positions, int mask_ring, hipStream_t st, bool with_rt = false);
 // Per-launch scratch that depends on the candidate capacity (candidate store, window scratch, stage-1 ring of `ring` slots).
 int chain_reserve_candidates(l3d_ctx* c, const ChainLayout& L, size_t cand_cap, int ring);
 

@@ -107,14 +107,7 @@ __global__ __launch_bounds__(256) void k_place_slots(int blocks_move, int wps, c
                                                      uint2* __restrict__ meta, float4* __restrict__ depths, int cap)
 {
     if (row_start[(size_t)S * N] > cap) return;                  // overflow: the chain is re-run with more room
-    if ((int)blockIdx.x < blocks_move) {
-        const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-        if (row >= (s1 - s0) * n_tbm) return;
-        const int y = s0 + row / n_tbm, cam = tbm[row % n_tbm];
-        const int a = rowA[y * N + cam], b = row_start[y * N + cam], n = row_start[y * N + cam + 1] - b;   // (rowA may have been laid out for an upper bound of the row)
-        for (int j = lane; j < n; j += 64) { meta[b + j] = metaA[a + j]; depths[b + j] = depthsA[a + j]; }
-        return;
-    }
+    if ((int)blockIdx.x < blocks_move) { move_stage1_row(s0, s1, tbm, n_tbm, N, rowA, metaA, depthsA, row_start, meta, depths); return; }
     const int e = (int)blockIdx.x - blocks_move, list = e / wps, bx = e % wps;
     const int src = list / g.world, r = list % g.world;
     const unsigned char* slot = G + ((size_t)(src_index[src] % g.ring) * g.world + r) * g.slot_bytes;
@@ -127,12 +120,7 @@ __global__ __launch_bounds__(256) void k_place_slots(int blocks_move, int wps, c
     const unsigned want = (unsigned)src_slot[src];
     auto place = [&](int i) {
         const Match m = kept[i];
-        if (m.camID2 == view_id && (int)m.segID2 >= s0 && (int)m.segID2 < s1) {
-            const int row = m.segID2 * N + cam;
-            const int slotpos = row_start[row] + atomicAdd(&cursor[row], 1);
-            meta[slotpos] = make_uint2(m.segID1, (unsigned)cam);
-            depths[slotpos] = make_float4(m.depths[2], m.depths[3], m.depths[0], m.depths[1]);
-        }
+        if (m.camID2 == view_id && (int)m.segID2 >= s0 && (int)m.segID2 < s1) place_reverse_match(m, N, cam, row_start, cursor, meta, depths);
     };
     auto mine = [&](unsigned w) { const int u = (int)(w & 0xffffu); return (w >> 16) == want && u >= s0 && u < s1; };
     const int stride = wps * 256;
@@ -176,16 +164,11 @@ __global__ __launch_bounds__(256) void k_slot_write(VerifyArgs a, const int* __r
     __shared__ int s_cnt[32];
     __shared__ int s_qcnt[256];
     __shared__ unsigned long long s_best[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int nseg = a.seg_end - a.seg_begin;
     const int yl = blockIdx.x;
-    int before = 0, total = 0;
-    for (int i = tid; i < nseg; i += 256) { const int v = kept_cnt[i]; total += v; if (i < yl) before += v; }
-    for (int o = 32; o > 0; o >>= 1) { before += __shfl_down(before, o); total += __shfl_down(total, o); }
-    if (lane == 0) { s_red[wave] = before; s_red[4 + wave] = total; }
-    __syncthreads();
-    before = s_red[0] + s_red[1] + s_red[2] + s_red[3];
-    total = s_red[4] + s_red[5] + s_red[6] + s_red[7];
+    int before, total;
+    kept_before_total(kept_cnt, nseg, yl, s_red, before, total);
     SlotHeader h;
     h.R = a.row_start[nrow];
     h.overflow = h.R > a.cand_cap ? 1 : 0;
@@ -202,7 +185,7 @@ __global__ __launch_bounds__(256) void k_slot_write(VerifyArgs a, const int* __r
     // the run table's rows are seg_cap apart and indexed by the segment's position in the rank's range (the writer indexes by the segment: the base is shifted)
     int* rt = g.rt_off ? reinterpret_cast<int*>(slot + g.rt_off) - a.seg_begin : nullptr;
     write_kept_segment_wg(a, y, before, local2global, reinterpret_cast<Match*>(slot + g.rec_off), s_cnt, bpos, s_best, g.cam_off ? reinterpret_cast<unsigned*>(slot + g.cam_off) : nullptr,
-                          rt, g.seg_cap, s_qcnt, true);
+                          rt, g.seg_cap, s_qcnt);
 }
 
 // Hand-over of one finished view on a committing rank: the ranks' kept records, concatenated in rank (= segment) order
@@ -475,7 +458,7 @@ int l3d_shard_chain_open(l3d_ctx* c, const l3d_chain_view* views, int n_views, i
     // ... and (round 6) the slot's RUN TABLE, (N + 1) x seg_cap ints (l3d_runtable.hpp; positions in the slot's records): a later neighbour reads the runs of its
     // camera -- 1/N of the slot -- instead of scanning the side array (188 MB per view and rank at 64 x 4000 x 24 on eight ranks)
     h->geom.max_n = h->maxN;
-    h->geom.rt_off = h->geom.cam_off && c->opt.run_tables != 0 ? salign(h->geom.cam_off + (size_t)slot_records * 4, 32) : 0;
+    h->geom.rt_off = h->geom.cam_off ? salign(h->geom.cam_off + (size_t)slot_records * 4, 32) : 0;
     h->geom.slot_bytes = salign(h->geom.rt_off ? h->geom.rt_off + ((size_t)h->maxN + 1) * h->geom.seg_cap * 4
                                 : (h->geom.cam_off ? h->geom.cam_off + (size_t)slot_records * 4 : h->geom.rec_off + (size_t)slot_records * sizeof(Match)), 256);
     *slot_bytes = h->geom.slot_bytes;
@@ -798,7 +781,7 @@ int l3d_shard_chain_run(l3d_shard_chain* h, l3d_exchange_fn exchange, void* exch
             if (!c->test_arena_cap) { long long kv = 0; for (unsigned char x : h->keep) kv += x; h->arena_cap = std::max<long long>((long long)c->part_arena_seen, h->arena_cap * kv / std::max(1, h->n_views) + 1048576); }
             HIPCHK(c, c->ch_kept.reserve_exact(((size_t)h->arena_cap + 64) * sizeof(Match)));
         }
-        // the retired views' side words and run tables (slots that carry both: L3D_RUN_TABLES, the default)
+        // the retired views' side words and run tables (slots that carry a side array carry both)
         h->retire_tables = h->geom.rt_off != 0 && h->geom.cam_off != 0 && c->opt.prod_transpose != 0 && c->opt.retire_tables != 0;
         if (h->retire_tables) {
             h->rt_off.assign(nvs, 0);

@@ -1,7 +1,7 @@
 // l3d_kept.hpp -- ordered compaction of one source segment's kept matches (conf > 1, cudawrapper.cu:1089-1110): the
 // confidences of up to 2048 candidates are fetched in ONE round of loads by the 4 waves of a workgroup before the ballots,
 // instead of one dependent load -> ballot -> store round per 64 candidates; the record loads of the few kept candidates
-// (~1.6 %) follow.  Shared by the per-view, chain and sharded-chain writers.
+// (~1.6 %) follow.  Shared by the per-view, chain and sharded-chain writers, with the smaller blocks both chains' kernels repeat.
 #pragma once
 
 #include "l3d_kernels.hpp"
@@ -17,12 +17,13 @@ namespace l3d {
 // front of every segment's group), found where the confidences already are in registers.
 // rt (round 6, with cam_out and s_qcnt = 256 ints of LDS): the view's RUN TABLE, [camera 0 .. N][segment] with rows rt_stride apart -- rt[q * rt_stride + y] =
 // position (in `out`) of the first kept match of segment y towards LOCAL camera q, row N = the end of the segment's matches: a later view finds the
-// records that point at it (line3D.cc:838-872) and the products find every (view, camera) pair's records without scanning anything.  cam_out then
-// holds (local camera << 16 | target segment) instead of the global camera id: all a reader of a run needs of the 32-byte record except the depths.
+// records that point at it (line3D.cc:838-872) and the products find every (view, camera) pair's records without scanning anything.
+// cam_out (optional): the SIDE WORD of every record, (local camera << 16 | target segment) -- all a reader of a run needs of the 32-byte record except
+// the depths.
 __device__ __forceinline__ void write_kept_segment_wg(const VerifyArgs& a, int y, int o, const unsigned* __restrict__ local2global,
                                                       Match* __restrict__ out, int* s_cnt, int* __restrict__ best_pos = nullptr,
                                                       unsigned long long* s_best = nullptr, unsigned* __restrict__ cam_out = nullptr,
-                                                      int* __restrict__ rt = nullptr, int rt_stride = 0, int* s_qcnt = nullptr, bool pack_side = false)
+                                                      int* __restrict__ rt = nullptr, int rt_stride = 0, int* s_qcnt = nullptr)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int start = a.row_start[y * a.N];
@@ -57,7 +58,7 @@ __device__ __forceinline__ void write_kept_segment_wg(const VerifyArgs& a, int y
                 rec.confidence = c[r] / 2.0f;                    // confidence_norm, cudawrapper.cu:1089,1098
                 const int pos = o + off + __popcll(b[r] & ((1ull << lane) - 1ull));
                 out[pos] = rec;
-                if (cam_out) cam_out[pos] = (rt || pack_side) ? ((meta.y << 16) | meta.x) : rec.camID2;   // (pack_side: the sharded chain's slots, without run tables)   // (the chain's side array: see rt above; without run tables the global camera id, scanned by later views)
+                if (cam_out) cam_out[pos] = (meta.y << 16) | meta.x;
                 if (rt) atomicAdd(&s_qcnt[meta.y], 1);
                 const unsigned long long key = ((unsigned long long)__float_as_uint(c[r]) << 32) | (0xffffffffu - (unsigned)pos);   // (c > 1: the bits order like the value)
                 bk = key > bk ? key : bk;
@@ -93,6 +94,47 @@ __device__ __forceinline__ void write_kept_segment_wg(const VerifyArgs& a, int y
             *best_pos = mx ? (int)(0xffffffffu - (unsigned)mx) : -1;
         }
     }
+}
+
+// The kept records in front of workgroup yl's segment (`before`) and in all nseg segments of the launch (`total`; kept_cnt: the launch's first segment),
+// summed by the workgroup itself -- at most a few thousand ints out of L2 -- instead of waiting for a scan launch.  s_red: 8 ints of LDS.  All 256 threads
+// must call.
+__device__ __forceinline__ void kept_before_total(const int* kept_cnt, int nseg, int yl, int* s_red, int& before, int& total)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int b = 0, t = 0;
+    for (int i = tid; i < nseg; i += 256) { const int v = kept_cnt[i]; t += v; if (i < yl) b += v; }
+    for (int o = 32; o > 0; o >>= 1) { b += __shfl_down(b, o); t += __shfl_down(t, o); }
+    if (lane == 0) { s_red[wave] = b; s_red[4 + wave] = t; }
+    __syncthreads();
+    before = s_red[0] + s_red[1] + s_red[2] + s_red[3];
+    total = s_red[4] + s_red[5] + s_red[6] + s_red[7];
+}
+
+// Stage-1 candidates of a view are written (k_pair_fill, stage-1 stream, well ahead of the chain) in their own (segment, to-be-matched camera) row order;
+// once the reverse matches of the view are counted, each row is moved to its place in the combined (segment, camera, target) order -- a 24-byte copy per
+// candidate instead of the triangulation on the chain's critical path.  One wave per row of the segments [s0, s1): the first workgroups of the
+// placing kernels.
+__device__ __forceinline__ void move_stage1_row(int s0, int s1, const int* __restrict__ tbm, int n_tbm, int N, const int* __restrict__ rowA,
+                                                const uint2* __restrict__ metaA, const float4* __restrict__ depthsA, const int* __restrict__ row_start,
+                                                uint2* __restrict__ meta, float4* __restrict__ depths)
+{
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= (s1 - s0) * n_tbm) return;
+    const int y = s0 + row / n_tbm, cam = tbm[row % n_tbm];
+    const int a = rowA[y * N + cam], b = row_start[y * N + cam], n = row_start[y * N + cam + 1] - b;   // (rowA may have been laid out for an upper bound of the row)
+    for (int j = lane; j < n; j += 64) { meta[b + j] = metaA[a + j]; depths[b + j] = depthsA[a + j]; }
+}
+
+// Record r of a source's kept list -- its camera `cam` in this view's list -- into the row of its target segment as a reverse match, at the row's cursor:
+// (seg, tgt) swap roles and the depth pairs swap (line3D.cc:847-856).  The order inside a run is restored afterwards (sort_exist_run, or the window kernel itself).
+__device__ __forceinline__ void place_reverse_match(const Match& r, int N, int cam, const int* __restrict__ row_start, int* __restrict__ cursor,
+                                                    uint2* __restrict__ meta, float4* __restrict__ depths)
+{
+    const int row = r.segID2 * N + cam;
+    const int sl = row_start[row] + atomicAdd(&cursor[row], 1);
+    meta[sl] = make_uint2(r.segID1, (unsigned)cam);
+    depths[sl] = make_float4(r.depths[2], r.depths[3], r.depths[0], r.depths[1]);
 }
 
 // One (segment, source camera) run of existing (reverse) matches, scattered in arbitrary order, into ascending target order:

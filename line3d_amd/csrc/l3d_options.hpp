@@ -32,7 +32,6 @@ namespace l3d {
     X(host_threads, "L3D_HOST_THREADS", 0, "worker threads of the host-side stages (0: min(16, usable CPUs))")                       \
     X(reserve_hint, "L3D_RESERVE_HINT", 1, "prepare(): 1 = the finishing stages' arenas are reserved ahead from the size of the scene (speed of the first finish), 0 = on demand (memory)") \
     X(handover_chunk_kb, "L3D_HANDOVER_CHUNK_KB", 262144, "views sharded in blocks: a missed block's sources travel in chunks of this many KB per all-gather slot (tests: small values force many chunks)") \
-    X(kept_cams, "L3D_KEPT_CAMS", 1, "resident chain: 1 = the kept writer leaves every record's target camera in a side array and later views scan that (4 B per record) for their reverse matches, 0 = they scan the records (A/B)") \
     X(part_release, "L3D_PART_RELEASE", 1, "partitioned run: 1 = the chain's per-launch scratch is released before the products are built (memory before the speed of a second pass)") \
     X(block_recover, "L3D_BLOCK_RECOVER", 1, "views sharded in blocks: 1 = a block whose cold-started speculation failed is re-run warm from its predecessor's true lists, 0 = any miss ends the call with verdict 1 (round 4; A/B)") \
     X(slot_cams_min, "L3D_SLOT_CAMS_MIN", 65536, "sharded chain: slots of at least this many records carry a 4-byte side array of target cameras (0: always; tests)") \
@@ -52,7 +51,6 @@ namespace l3d {
     X(rt_g, "L3D_RT_G", -1, "resident chain with run tables: lanes sharing a run when a view collects its reverse matches (-1: by the average run, 0: a run per thread)") \
     X(part_vrank, "L3D_PART_VRANK", 0, "with part_vworld: the rank of the job whose block of views a world-1 partitioned run keeps") \
     X(part_vworld, "L3D_PART_VWORLD", 0, "a world-1 shard_run with commit 3 keeps the block of views rank part_vrank of a job of this many ranks would own: ONE rank's share of a job that does not fit one GPU, exercised on one GPU (scripts/run_rank_share.py); l3d_set_option only") \
-    X(run_tables, "L3D_RUN_TABLES", 1, "resident chain: 1 = the kept writer fills a run table per view and packs (local camera, target) into the side array; later views and the products read runs instead of scanning lists, 0 = round 5's scans of the side array of global camera ids (A/B)") \
     X(slot_ring, "L3D_SLOT_RING", -1, "sharded run: 1 = always retire old gathered blocks into the compact arena (ring of window + 18 views), 0 = never, -1 = when all blocks exceed 8 GB") \
     X(regrow_free_mb, "L3D_REGROW_FREE_MB", 0, "tests: the free HBM the kept arena's regrow sees is capped at this many MB (0: what hipMemGetInfo reports)") \
     X(host_bookkeeping, "L3D_HOST_BOOKKEEPING", 0, "CROSS-CHECK BUILD ONLY (-DL3D_CROSSCHECKS, libline3d_amd_check.so): matchViews with the rounds-1-2 host bookkeeping") \

@@ -138,6 +138,24 @@ def test_part_share_switches_are_not_read_from_the_environment(monkeypatch):
         ctx.close()
 
 
+def test_retired_kept_list_switches_are_unknown_options():
+    """The resident chain's two kept-list switches are retired with round 5's side array of global camera ids: l3d_set_option and l3d_get_option
+    refuse every spelling of their names as unknown, like the other retired switches."""
+    from line3d_amd import capi
+    from line3d_amd.capi import L3DError
+    ctx = capi.Context(0)
+    try:
+        for stem in ("kept_" + "cams", "run_" + "tables"):         # (spelled in pieces: a search of the sources for the retired names finds nothing)
+            for name in ("L3D_" + stem.upper(), stem.upper(), stem):
+                with pytest.raises(L3DError, match="unknown option"):
+                    ctx.set_option(name, 0)
+                with pytest.raises(L3DError, match="unknown option"):
+                    ctx.get_option(name)
+        assert ctx.get_option("L3D_PROD_TRANSPOSE") == 1           # (a live switch next to them is still known)
+    finally:
+        ctx.close()
+
+
 def test_stepwise_sharded_matching_equals_whole(small_scene, small_oracle):
     """Two 'ranks' emulated in one process: each computes half of every view's source segments, the kept
     lists are concatenated (what the all-gather does) and committed -- identical to the unsharded run."""
@@ -806,15 +824,15 @@ def test_products_built_in_blocks_of_views_equal_the_one_block_build(small_scene
 def test_products_variants_agree(small_scene, small_oracle):
     """Round 6: matchViews' products are built as a transpose of the kept lists' run tables (kept writer: (local camera, target) words + a run table
     per view; per-pair LDS transposes; a bitmap or, for short rows, a rank-and-dedupe per row) instead of a radix sort of 64-bit keys.  Every variant
-    -- the sort (L3D_PROD_TRANSPOSE=0), side arrays rebuilt from the records (L3D_RUN_TABLES=0: what the block and sharded modes do), the chain's own;
-    lanes per run -- gives the same table, best matches, hypotheses and kept lists byte for byte, on a sparse and a denser
-    scene (rows of more than 64 entries take the bitmap path)."""
+    -- the sort (L3D_PROD_TRANSPOSE=0), the chain's own run tables; lanes per run; blocks of keys; the pairs transposed early or at the end -- gives the
+    same table, best matches, hypotheses and kept lists byte for byte, on a sparse and a denser scene (rows of more than 64 entries take the bitmap path).
+    (Run tables rebuilt from the records, what the block and sharded modes do, are compared byte for byte in tests/test_gpu_partition.py.)"""
     from line3d_amd.pipeline import Line3D, load_scene
     from line3d_amd.synth import make_scene
     for scene, N in ((small_scene, 6), (make_scene(10, 700, 8, seed=5, noise_px=0.05, step=0.05), 8)):
         digests = []
-        for opts in (dict(L3D_PROD_TRANSPOSE=0, L3D_RUN_TABLES=0), dict(L3D_PROD_TRANSPOSE=1, L3D_RUN_TABLES=0), dict(L3D_PROD_TRANSPOSE=1, L3D_RUN_TABLES=1),
-                     dict(L3D_PROD_TRANSPOSE=1, L3D_RUN_TABLES=1, L3D_PROD_PAIR_G=0), dict(L3D_PROD_TRANSPOSE=1, L3D_RUN_TABLES=1, L3D_PROD_PAIR_G=64, L3D_PROD_BLOCK_KEYS=5000),
+        for opts in (dict(L3D_PROD_TRANSPOSE=0), dict(L3D_PROD_TRANSPOSE=1),
+                     dict(L3D_PROD_TRANSPOSE=1, L3D_PROD_PAIR_G=0), dict(L3D_PROD_TRANSPOSE=1, L3D_PROD_PAIR_G=64, L3D_PROD_BLOCK_KEYS=5000),
                      # the pairs transposed by the chain itself, behind each view's kept writer (2: view by view, 3: eight views per launch; 1, the default: long lists only), and all at the end
                      dict(L3D_PROD_EARLY=2), dict(L3D_PROD_EARLY=2, L3D_PROD_PAIR_G=16), dict(L3D_PROD_EARLY=3), dict(L3D_PROD_EARLY=0)):
             l = Line3D("", matchingNeighbors=N)
@@ -839,7 +857,7 @@ def test_products_variants_agree(small_scene, small_oracle):
 
 def test_products_of_a_hub_view_touched_by_more_than_64_views():
     """A view that (nearly) all 79 other views list as a neighbour (and that lists two of them): its rows of the table collect entries from 79 (view, camera) pairs -- the rows
-    kernel's lanes look the touched views up 64 at a time, the short-row path does not apply.  Transposed products (the chain's side arrays and rebuilt ones)
+    kernel's lanes look the touched views up 64 at a time, the short-row path does not apply.  Transposed products (at the end and early, by the chain)
     against the sorted ones and against the plain host construction (L3D_CHECK_POT); kept lists against the per-view seam path."""
     from line3d_amd.pipeline import Line3D
     from line3d_amd.synth import make_scene
@@ -850,7 +868,8 @@ def test_products_of_a_hub_view_touched_by_more_than_64_views():
         o1, o2 = ((i + d) % V if (i + d) % V != HUB else (i + d + 1) % V for d in (6, 12))      # (three neighbours: a kept match needs two witnesses' cameras)
         v["sims"] = {HUB + 6: 1.0, HUB - 6: 0.9, HUB + 12: 0.8} if i == HUB else {HUB: 1.0, o1: 0.5, o2: 0.4}
     digests, paths = [], []
-    for opts in (dict(L3D_PROD_TRANSPOSE=0, L3D_RUN_TABLES=0), dict(L3D_PROD_TRANSPOSE=1, L3D_RUN_TABLES=0), dict(L3D_PROD_TRANSPOSE=1, L3D_RUN_TABLES=1), dict(L3D_PROD_EARLY=2)):
+    variants = (dict(L3D_PROD_TRANSPOSE=0), dict(L3D_PROD_TRANSPOSE=1), dict(L3D_PROD_EARLY=2))
+    for opts in variants:
         l = Line3D("", matchingNeighbors=3)
         for v in sc.views:
             l.addImage_fixed_sim(v["id"], v["width"], v["height"], v["segments"], v["K"], v["R"], v["t"], v["sims"])
@@ -868,9 +887,9 @@ def test_products_of_a_hub_view_touched_by_more_than_64_views():
             d["lines"] = repr([(list(s2), np.asarray(s3).tobytes()) for s2, s3 in l.getResult()])
             digests.append((d, rows0))
         l.close()
-    assert paths == [paths[0]] * 4
+    assert paths == [paths[0]] * len(variants)
     assert paths[0] == 0                                       # the resident chain took the scene: the device products exist
-    assert len(digests) == 4 and digests[0][1] > 64            # (the hub's rows hold entries of many views)
+    assert len(digests) == len(variants) and digests[0][1] > 64            # (the hub's rows hold entries of many views)
     assert all(d[0] == digests[0][0] for d in digests[1:])
 
 
@@ -1138,7 +1157,7 @@ def test_matchviews_sharded_by_blocks_of_views_with_verified_speculation():
 def test_fast_paths_equal_the_plain_paths_on_medium_scenes(seed):
     """Scenes too big for the oracle in a test (12-28 views of 600-2400 segments, 8-16 neighbours, narrow baselines: thousands of candidates per segment, rows of the table with
     hundreds of entries, pairs beyond the direct scatter) through the defaults (+ the chain's own transposes) and through the PLAIN paths whose parity the small scenes and the
-    goldens pin: the exact pair test alone (no wedge test, no interval bounds), the all-pairs verification, record scans instead of run tables, the sorted products --
+    goldens pin: the exact pair test alone (no wedge test, no interval bounds), the all-pairs verification, the sorted products --
     kept lists, products, affinity list and lines byte for byte."""
     from line3d_amd.pipeline import Line3D, load_scene
     from line3d_amd.synth import make_scene
@@ -1159,7 +1178,7 @@ def test_fast_paths_equal_the_plain_paths_on_medium_scenes(seed):
         if plain:
             ctx.set_pair_pretest(0)
             ctx.set_verify_mode(1)
-            for k, v in dict(L3D_RUN_TABLES=0, L3D_PROD_TRANSPOSE=0, L3D_KEPT_CAMS=int(rng.integers(0, 2)), L3D_AFF_SYM=0).items():
+            for k, v in dict(L3D_PROD_TRANSPOSE=0, L3D_AFF_SYM=0).items():
                 ctx.set_option(k, v)
         else:
             ctx.set_option("L3D_PROD_EARLY", int(rng.integers(1, 4)))
