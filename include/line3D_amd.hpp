@@ -64,6 +64,19 @@ public:
                                    min_baseline, useCollinearity ? 1 : 0, verbose ? 1 : 0, &h_);
         if (rc != L3D_OK) std::cerr << prefix_ << "no usable HIP device (code " << rc << "); this build has no CPU fallback" << std::endl;
     }
+    // One object over several GPUs of this process (l3d_line3d_create_node): rank r on devices[r], a device may repeat (virtual ranks on one
+    // GPU).  compute3Dmodel runs matchViews partitioned over the ranks and every method reads the result as above.  A driver changes only its
+    // construction line, main_vsfm.cpp:116-119 e.g. to
+    //     new L3D::Line3D(data_directory, neighbors, max_uncertainty, min_uncertainty, sigma_p, sigma_a, min_baseline, collinearity, verbose, devices);
+    // The reference's parameters are all given here: C++ takes default arguments only at the end of a list, and `devices` has none.
+    Line3D(const std::string data_directory, const int matchingNeighbors, const float uncertainty_t_upper_2D, const float uncertainty_t_lower_2D,
+           const float sigma_p, const float sigma_a, const float min_baseline, bool useCollinearity, bool verbose, const std::vector<int>& devices)
+        : h_(nullptr), prefix_("[L3D] "), data_directory_(data_directory), use_collinearity_(useCollinearity)
+    {
+        int rc = l3d_line3d_create_node(devices.empty() ? nullptr : devices.data(), (int)devices.size(), matchingNeighbors, uncertainty_t_upper_2D,
+                                        uncertainty_t_lower_2D, sigma_p, sigma_a, min_baseline, useCollinearity ? 1 : 0, verbose ? 1 : 0, &h_);
+        if (rc != L3D_OK) std::cerr << prefix_ << "no usable set of HIP devices (code " << rc << "); this build has no CPU fallback" << std::endl;
+    }
     ~Line3D() { l3d_line3d_destroy(h_); }
     Line3D(const Line3D&) = delete;
     Line3D& operator=(const Line3D&) = delete;

@@ -334,6 +334,19 @@ int l3d_exchange_rccl(void* user, int view, const void* send_slot, void* recv_bl
 int l3d_exchange_local(void* user, int view, const void* send_slot, void* recv_block, size_t slot_bytes, int world, void* stream);
 int l3d_exchange_replay(void* user, int view, const void* send_slot, void* recv_block, size_t slot_bytes, int world, void* stream);
 const void* l3d_shard_chain_gathered(l3d_shard_chain* chain);   /* device address of the gathered blocks after l3d_shard_chain_run */
+/* The fourth adapter: the ranks of ONE process, one per entry of a device list (a device may repeat: virtual ranks on one GPU), each on a host
+ * thread of its own.  l3d_node_comm_create enables peer access between every pair of distinct devices (L3D_ERR_UNSUPPORTED, the pair named on
+ * stderr, when a pair is refused); l3d_node_comm_bind tells it which rank's exchanges arrive on which stream (l3d_ctx_stream of the rank's
+ * context; one stream per rank).  l3d_exchange_node (user = the communicator) gathers the ranks' slots with one kernel launch per rank that
+ * reads the peers' slots through peer-mapped pointers; two host barriers per exchange, ordering by stream events only.
+ * A broken barrier -- l3d_node_comm_abort (a rank that returns with an error calls it), a failed exchange, 600 s without the other ranks --
+ * makes every pending and later exchange of every rank return non-zero: nothing hangs.  l3d_line3d_create_node owns one of these. */
+typedef struct l3d_node_comm l3d_node_comm;
+int l3d_node_comm_create(const int* devices, int n, l3d_node_comm** out);
+void l3d_node_comm_destroy(l3d_node_comm* comm);
+int l3d_node_comm_bind(l3d_node_comm* comm, int rank, void* stream);
+void l3d_node_comm_abort(l3d_node_comm* comm);
+int l3d_exchange_node(void* user, int view, const void* send_slot, void* recv_block, size_t slot_bytes, int world, void* stream);
 /* A rank that fails inside l3d_shard_chain_run (capacity, HIP error, failing callback) keeps calling `exchange` for every
  * remaining view with a slot that says "gave up": no rank is left waiting in a collective.  Afterwards every rank reads the
  * same verdict out of the gathered slot headers: L3D_ERR_NOMEM on ALL ranks when any slot overflowed.  l3d_shard_chain_info
@@ -493,6 +506,26 @@ typedef struct l3d_line3d l3d_line3d;
 int l3d_line3d_create(int device, int matching_neighbors, float uncertainty_t_upper_2D, float uncertainty_t_lower_2D,
                       float sigma_p, float sigma_a, float min_baseline, int use_collinearity, int verbose,
                       l3d_line3d** out);
+/* ONE object over several GPUs of this process: rank r of the job on devices[r] (a device may repeat: virtual ranks on one GPU), each an
+ * ordinary pipeline object with its own context, run on a host thread of its own; n_devices == 1 is l3d_line3d_create(devices[0], ...).
+ * The images go to every rank; compute3Dmodel prepares all ranks (l3d_line3d_prepare: that step alone), then runs matchViews partitioned over them (l3d_line3d_set_node_mode) and
+ * the collective finish (l3d_line3d_finish_sharded) through l3d_exchange_node: every rank ends with the whole result, read from rank 0
+ * (result_sizes, get_result, get_segment2D, save_result, num_cameras, stats, affinity, match_path); chain_summary gives every view's entry from
+ * the rank whose block of views holds it (a rank's own summary covers the views it holds only).  last_error names the first
+ * failing rank ("rank r (device d): ...").  The calls that address one rank's machinery -- shard_*, match_begin / match_order /
+ * view_num_to_be_matched / match_view_*, match_end, block_run, partition_run, finish_sharded, match_views, finish, view_matches,
+ * products_*, set_sync_matching, l3d_line3d_context (NULL) -- are refused with L3D_ERR_INVALID.  The host-thread budget (L3D_HOST_THREADS) is
+ * split among the ranks.  L3D_ERR_INVALID for NULL, n_devices <= 0 or a negative id (before any device is touched), L3D_ERR_NODEVICE without
+ * a HIP device, L3D_ERR_UNSUPPORTED when two devices cannot map each other's memory. */
+int l3d_line3d_create_node(const int* devices, int n_devices, int matching_neighbors, float uncertainty_t_upper_2D, float uncertainty_t_lower_2D,
+                           float sigma_p, float sigma_a, float min_baseline, int use_collinearity, int verbose, l3d_line3d** out);
+/* ranks of the object (1 for l3d_line3d_create) */
+int l3d_line3d_num_ranks(const l3d_line3d* h);
+/* how compute3Dmodel shards matchViews over the ranks of a node object: 0 (default) = the source segments of every view, partitioned
+ * (l3d_line3d_shard_run, commit = 3: exact on every scene, no speculation); 1 = blocks of views, partitioned (l3d_line3d_partition_run), falling
+ * back to 0 in the same call when its verdict says the speculation cannot hold (printed under verbose).  Accepted, and without effect, on a
+ * single-device object. */
+int l3d_line3d_set_node_mode(l3d_line3d* h, int mode);
 void l3d_line3d_destroy(l3d_line3d* h);
 const char* l3d_line3d_last_error(const l3d_line3d* h);
 l3d_ctx* l3d_line3d_context(l3d_line3d* h);

@@ -368,3 +368,47 @@ class Context:
         acd = np.zeros(len(x), np.float64)
         self._chk(self.lib.l3d_test_contract_math(self.h, _p(x), C.c_int(len(x)), _p(e), _p(ac), _p(acd)))
         return e, ac, acd
+
+
+class NodeComm:
+    """The in-process all-gather of the ranks of one process (l3d_node_comm_*, the adapter l3d_exchange_node): rank r on devices[r], a device may
+    repeat.  Bind each rank's stream (the stream its exchanges arrive on), then hand `h.value` as exchange_user with exchange "node" to
+    Line3D.shard_run / partition_run, or call `exchange` directly.  A broken communicator (abort(), a failed exchange) fails every later exchange."""
+
+    def __init__(self, devices):
+        self.lib = load_library()
+        self.lib.l3d_node_comm_destroy.argtypes = [C.c_void_p]
+        self.lib.l3d_node_comm_abort.argtypes = [C.c_void_p]
+        self.lib.l3d_node_comm_bind.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        self.lib.l3d_exchange_node.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+        self.devices = [int(d) for d in devices]
+        devs = np.ascontiguousarray(self.devices, dtype=np.int32)
+        h = C.c_void_p()
+        rc = self.lib.l3d_node_comm_create(_p(devs) if len(devs) else None, C.c_int(len(devs)), C.byref(h))
+        if rc != 0:
+            raise L3DError("l3d_node_comm_create(%s) failed (code %d)" % (self.devices, rc))
+        self.h = h
+
+    def bind(self, rank: int, stream: int):
+        rc = self.lib.l3d_node_comm_bind(self.h, C.c_int(rank), C.c_void_p(stream))
+        if rc != 0:
+            raise L3DError("l3d_node_comm_bind(rank %d) failed (code %d)" % (rank, rc))
+
+    def exchange(self, view: int, send_ptr: int, recv_ptr: int, slot_bytes: int, stream: int) -> int:
+        """rank (of `stream`)'s all-gather of one slot: 0 = enqueued"""
+        return int(self.lib.l3d_exchange_node(self.h, C.c_int(view), C.c_void_p(send_ptr), C.c_void_p(recv_ptr), C.c_size_t(slot_bytes),
+                                              C.c_int(len(self.devices)), C.c_void_p(stream)))
+
+    def abort(self):
+        self.lib.l3d_node_comm_abort(self.h)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.l3d_node_comm_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

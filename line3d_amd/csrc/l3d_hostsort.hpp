@@ -43,8 +43,12 @@ inline unsigned usable_cpus()
     return n;
 }
 
+// a rank of a node object (l3d_line3d_create_node) runs on a thread of its own beside the others: its share of the budget, set on that thread
+inline int& thread_host_threads() { static thread_local int n = 0; return n; }
+
 inline unsigned host_threads()         // worker threads of the host-side stages that run alone (finish of compute3Dmodel)
 {
+    if (const int t = thread_host_threads()) return (unsigned)t;
     { const int e = tunables().host_threads.load(std::memory_order_relaxed); if (e > 0) return (unsigned)std::min(64, e); }     // L3D_HOST_THREADS
     return std::max(1u, std::min(16u, usable_cpus()));
 }

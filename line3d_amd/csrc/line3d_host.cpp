@@ -2,6 +2,119 @@
 // (addImage / addImage_fixed_sim / compute3Dmodel / getResult, line3D.h) over the host pipeline in line3d_host_views.cpp (views, seam path),
 // line3d_host_chain.cpp (resident matchViews) and line3d_host_finish.cpp (selection, affinity, diffusion, clustering, fit).
 #include "line3d_host_internal.hpp"
+#include "l3d_node.hpp"
+
+#include <hip/hip_runtime_api.h>
+
+// ---- a node object: one ordinary object per rank, each on a host thread of its own while it computes ---------------------------------------
+namespace l3dh {
+struct NodeRanks {
+    std::vector<int> devices;
+    std::vector<L*> ranks;                  // rank r: an ordinary object with its own context on devices[r]
+    l3d_node_comm* comm = nullptr;          // their all-gather (l3d_node.hip), every stream bound
+    int mode = 0;                           // l3d_line3d_set_node_mode
+    int threads_per_rank = 1;               // the host-thread budget split among the ranks
+};
+}  // namespace l3dh
+
+static std::string rank_prefix(const L* h, int r)
+{
+    return "rank " + std::to_string(r) + " (device " + std::to_string(h->node->devices[(size_t)r]) + "): ";
+}
+// the calls that address one rank's machinery: refused on a node object rather than acting on rank 0
+static int node_refuse(L* h, const char* what)
+{
+    return h->fail(L3D_ERR_INVALID, std::string(what) + ": addresses one rank's machinery -- not on a node object (l3d_line3d_create_node), whose "
+                                                        "compute3Dmodel runs every rank");
+}
+static L* rank0(const L* h) { return h->node->ranks[0]; }
+// fn(rank object) on every rank in turn (the images, reset); stops at the first failure
+template <class F>
+static int node_each(L* h, F fn)
+{
+    for (size_t r = 0; r < h->node->ranks.size(); ++r)
+        if (const int rc = fn(h->node->ranks[r])) return h->fail(rc, rank_prefix(h, (int)r) + h->node->ranks[r]->err);
+    return L3D_OK;
+}
+// fn(r) on one host thread per rank, all at once: its device current, its share of the host threads.  A rank that returns an error breaks the
+// communicator (its peers' pending and later exchanges fail instead of waiting).  The message of the rank that failed first.
+static int node_run(L* h, const std::function<int(int)>& fn)
+{
+    NodeRanks& N = *h->node;
+    const int W = (int)N.ranks.size();
+    std::vector<int> rcs((size_t)W, L3D_OK);
+    std::atomic<int> first{ -1 };
+    std::vector<std::thread> th;
+    for (int r = 0; r < W; ++r)
+        th.emplace_back([&, r]() {
+            int rc = hipSetDevice(N.devices[(size_t)r]) == hipSuccess ? L3D_OK : L3D_ERR_HIP;
+            if (rc) N.ranks[(size_t)r]->fail(rc, "hipSetDevice failed on the rank's thread");
+            l3d::thread_host_threads() = N.threads_per_rank;
+            if (!rc) rc = fn(r);
+            l3d::thread_host_threads() = 0;
+            if (rc) {
+                int none = -1;
+                first.compare_exchange_strong(none, r);
+                l3d_node_comm_abort(N.comm);
+            }
+            rcs[(size_t)r] = rc;
+        });
+    for (auto& t : th) t.join();
+    // the rank whose exchange broke the communicator, else the first to return an error
+    int r = l3d::node_comm_culprit(N.comm);
+    if (r < 0 || rcs[(size_t)r] == L3D_OK) r = first.load();
+    return r < 0 ? L3D_OK : h->fail(rcs[(size_t)r], rank_prefix(h, r) + N.ranks[(size_t)r]->err);
+}
+// Line3D::compute3Dmodel over the ranks: prepare on all of them; then matchViews partitioned (set_node_mode) and the collective finish, every
+// rank through l3d_exchange_node -- every rank ends with the whole result
+static int node_compute(L* h, int perform_diffusion)
+{
+    NodeRanks& N = *h->node;
+    const int W = (int)N.ranks.size();
+    if (rank0(h)->views.size() < 4) return h->fail(L3D_ERR_INVALID, "not enough images! can't compute 3D model...");   // line3D.cc:347-351
+    int rc = node_run(h, [&](int r) { return prepare(N.ranks[(size_t)r]); });
+    if (rc) return rc;
+    int s_max = 0;
+    for (const View* v : rank0(h)->vlist) s_max = std::max(s_max, v->S());
+    // kept records one rank may produce for one view (distributed.default_slot_records): l3d_line3d_shard_run grows them on an overflow verdict
+    const int slot_records = (int)std::min<long long>(INT32_MAX / 2, std::max<long long>(1024, (10LL * s_max * rank0(h)->matching_neighbors) / W + 1024));
+    const int mode = N.mode;
+    l3d::node_comm_rearm(N.comm);
+    h->chain_summary.clear();
+    rc = node_run(h, [&](int r) {
+        L* R = N.ranks[(size_t)r];
+        int rc2 = L3D_OK;
+        bool matched = false;
+        if (mode == 1) {
+            int verdict = 1;
+            rc2 = l3d_line3d_partition_run(R, r, W, -1, l3d_exchange_node, N.comm, &verdict);
+            matched = rc2 == L3D_OK && verdict == 0;
+            if (rc2 == L3D_OK && verdict != 0 && r == 0 && h->verbose)
+                printf("[L3D] node: the blocks of views cannot vouch for one another on this scene -- matchViews runs segment-sharded (mode 0)\n");
+        }
+        if (rc2 == L3D_OK && !matched) rc2 = l3d_line3d_shard_run(R, r, W, slot_records, l3d_exchange_node, N.comm, 3, nullptr, nullptr);
+        if (rc2 == L3D_OK) rc2 = l3d_line3d_finish_sharded(R, perform_diffusion, l3d_exchange_node, N.comm);
+        return rc2;
+    });
+    if (rc) return rc;
+    // the per-view summary of the one chain: a rank's own lists only cover the views it holds -- view k from the rank whose block holds it
+    // (both modes cut the chain's views into blocks n * r / W)
+    const size_t n = rank0(h)->chain_summary.size();
+    h->chain_summary.assign(n, l3d_chain_summary());
+    for (int r = 0; r < W; ++r) {
+        const std::vector<l3d_chain_summary>& own = N.ranks[(size_t)r]->chain_summary;
+        const size_t b0 = (size_t)(((long long)n * r) / W), b1 = (size_t)(((long long)n * (r + 1)) / W);
+        for (size_t k = b0; k < b1 && k < own.size(); ++k) h->chain_summary[k] = own[k];
+    }
+    return L3D_OK;
+}
+static void node_destroy(L* h)
+{
+    for (L* r : h->node->ranks) l3d_line3d_destroy(r);
+    l3d_node_comm_destroy(h->node->comm);
+    delete h->node;
+    delete h;
+}
 
 
 // =================================================================================================
@@ -32,9 +145,50 @@ int l3d_line3d_create(int device, int matching_neighbors, float unc_upper, float
     return L3D_OK;
 }
 
+int l3d_line3d_create_node(const int* devices, int n, int matching_neighbors, float unc_upper, float unc_lower, float sigma_p, float sigma_a,
+                           float min_baseline, int use_collinearity, int verbose, l3d_line3d** out)
+{
+    if (!out) return L3D_ERR_INVALID;
+    *out = nullptr;
+    if (!devices || n <= 0) return L3D_ERR_INVALID;
+    for (int r = 0; r < n; ++r)
+        if (devices[r] < 0) return L3D_ERR_INVALID;
+    if (n == 1) return l3d_line3d_create(devices[0], matching_neighbors, unc_upper, unc_lower, sigma_p, sigma_a, min_baseline, use_collinearity, verbose, out);
+    l3d_node_comm* comm = nullptr;
+    int rc = l3d_node_comm_create(devices, n, &comm);
+    if (rc) return rc;
+    L* h = new L();
+    h->verbose = verbose != 0;
+    h->node = new NodeRanks();
+    h->node->devices.assign(devices, devices + n);
+    h->node->comm = comm;
+    for (int r = 0; r < n && rc == L3D_OK; ++r) {
+        L* R = nullptr;
+        rc = l3d_line3d_create(devices[r], matching_neighbors, unc_upper, unc_lower, sigma_p, sigma_a, min_baseline, use_collinearity, r == 0 ? verbose : 0, &R);
+        if (rc == L3D_OK) {
+            h->node->ranks.push_back(R);
+            rc = l3d_node_comm_bind(comm, r, l3d_ctx_stream(R->ctx));
+        }
+    }
+    if (rc) { node_destroy(h); return rc; }
+    h->node->threads_per_rank = std::max(1, (int)l3d::host_threads() / n);
+    l3d::node_comm_fail_at(comm, 1, hopt(h->node->ranks[1]).node_fail_at);      // (tests)
+    *out = h;
+    return L3D_OK;
+}
+int l3d_line3d_num_ranks(const l3d_line3d* h) { return !h ? 0 : h->node ? (int)h->node->ranks.size() : 1; }
+int l3d_line3d_set_node_mode(l3d_line3d* h, int mode)
+{
+    if (!h) return L3D_ERR_INVALID;
+    if (mode != 0 && mode != 1) return h->fail(L3D_ERR_INVALID, "set_node_mode: 0 (segments of every view) or 1 (blocks of views)");
+    if (h->node) h->node->mode = mode;
+    return L3D_OK;
+}
+
 void l3d_line3d_destroy(l3d_line3d* h)
 {
     if (!h) return;
+    if (h->node) { node_destroy(h); return; }
     if (h->warm_thread.joinable()) h->warm_thread.join();
     destroy_finalizer(h);                                   // joins the worker threads
     drop_plan(h);
@@ -43,12 +197,17 @@ void l3d_line3d_destroy(l3d_line3d* h)
 }
 
 const char* l3d_line3d_last_error(const l3d_line3d* h) { return h ? h->err.c_str() : "null handle"; }
-l3d_ctx* l3d_line3d_context(l3d_line3d* h) { return h ? h->ctx : nullptr; }
+l3d_ctx* l3d_line3d_context(l3d_line3d* h)
+{
+    if (h && h->node) { node_refuse(h, "context"); return nullptr; }
+    return h ? h->ctx : nullptr;
+}
 
 // Line3D::reset, line3D.cc:62-92
 int l3d_line3d_reset(l3d_line3d* h)
 {
     if (!h) return L3D_ERR_INVALID;
+    if (h->node) { h->chain_summary.clear(); return node_each(h, [](L* r) { return l3d_line3d_reset(r); }); }
     for (auto& kv : h->views) { l3d_unregister_segments(h->ctx, kv.second.segs.data()); l3d_unregister_segments(h->ctx, kv.second.nb_segs.data()); }
     h->views.clear(); h->vlist.clear(); h->view_similarities.clear(); h->num_wps.clear(); h->common_wps.clear();
     h->worldpoints2views.clear(); h->visual_neighbors.clear(); h->fundamentals.clear(); h->matched.clear();
@@ -76,6 +235,7 @@ int l3d_line3d_add_image_fixed_sim(l3d_line3d* h, uint32_t id, unsigned width, u
                                    const double* K, const double* R, const double* t,
                                    const uint32_t* sim_ids, const float* sims, int n_sims)
 {
+    if (h && h->node) return node_each(h, [&](L* r) { return l3d_line3d_add_image_fixed_sim(r, id, width, height, segs, n, K, R, t, sim_ids, sims, n_sims); });
     int rc = add_common(h, id, width, height, segs, n, K, R, t, n_sims);
     if (rc) return rc;
     for (int i = 0; i < n_sims; ++i)                       // setViewSimilarity, :1938-1946
@@ -87,6 +247,7 @@ int l3d_line3d_add_image_fixed_sim(l3d_line3d* h, uint32_t id, unsigned width, u
 int l3d_line3d_add_image(l3d_line3d* h, uint32_t id, unsigned width, unsigned height, const float* segs, int n,
                          const double* K, const double* R, const double* t, const uint32_t* worldpoints, int n_wps)
 {
+    if (h && h->node) return node_each(h, [&](L* r) { return l3d_line3d_add_image(r, id, width, height, segs, n, K, R, t, worldpoints, n_wps); });
     int rc = add_common(h, id, width, height, segs, n, K, R, t, n_wps);
     if (rc) return rc;
     process_worldpoints(h, id, worldpoints, n_wps);
@@ -98,6 +259,7 @@ int l3d_line3d_add_image_cached(l3d_line3d* h, uint32_t id, unsigned width, unsi
                                 const double* K, const double* R, const double* t, const uint32_t* worldpoints, int n_wps)
 {
     if (!h) return L3D_ERR_INVALID;
+    if (h->node) return node_each(h, [&](L* r) { return l3d_line3d_add_image_cached(r, id, width, height, cache, K, R, t, worldpoints, n_wps); });
     if (!cache) return h->fail(L3D_ERR_INVALID, "null segment cache");
     const int n = l3d_segment_cache_num_segments(cache), nc = l3d_segment_cache_num_collinearities(cache);
     std::vector<float> segs((size_t)n * 4 + 1), cw((size_t)nc + 1);
@@ -155,6 +317,12 @@ int l3d_line3d_add_image_ex(l3d_line3d* h, uint32_t id, unsigned width, unsigned
                             const double* t, const uint32_t* worldpoints, int n_wps, const char* data_directory, int max_img_width, int load_and_store)
 {
     if (!h) return L3D_ERR_INVALID;
+    if (h->node)        // (every rank makes the cache decision of the reference; the file is written once, by rank 0)
+        return node_each(h, [&](L* r) {
+            const int rc = l3d_line3d_add_image_ex(r, id, width, height, segs, n, K, R, t, worldpoints, n_wps, data_directory, max_img_width, load_and_store);
+            if (rc == L3D_OK && r != rank0(h)) r->views[id].cache_to_write.clear();
+            return rc;
+        });
     if (h->computation) return h->fail(L3D_ERR_INVALID, "reconstruction already performed! cannot add more images (try reset first)");
     if (h->views.count(id)) return h->fail(L3D_ERR_INVALID, "imageID already in use!");
     if (n_wps == 0) return h->fail(L3D_ERR_INVALID, "unlinked images cannot be added!");
@@ -180,6 +348,13 @@ int l3d_line3d_add_image_fixed_sim_ex(l3d_line3d* h, uint32_t id, unsigned width
                                       int load_and_store)
 {
     if (!h) return L3D_ERR_INVALID;
+    if (h->node)
+        return node_each(h, [&](L* r) {
+            const int rc = l3d_line3d_add_image_fixed_sim_ex(r, id, width, height, segs, n, K, R, t, sim_ids, sims, n_sims, data_directory, max_img_width,
+                                                            load_and_store);
+            if (rc == L3D_OK && r != rank0(h)) r->views[id].cache_to_write.clear();
+            return rc;
+        });
     if (h->computation) return h->fail(L3D_ERR_INVALID, "reconstruction already performed! cannot add more images (try reset first)");
     if (h->views.count(id)) return h->fail(L3D_ERR_INVALID, "imageID already in use!");
     if (n_sims == 0) return h->fail(L3D_ERR_INVALID, "unlinked images cannot be added!");
@@ -201,7 +376,7 @@ int l3d_line3d_add_image_fixed_sim_ex(l3d_line3d* h, uint32_t id, unsigned width
     return L3D_OK;
 }
 
-int l3d_line3d_num_cameras(const l3d_line3d* h) { return h ? (int)h->views.size() : 0; }
+int l3d_line3d_num_cameras(const l3d_line3d* h) { return !h ? 0 : h->node ? l3d_line3d_num_cameras(rank0(h)) : (int)h->views.size(); }
 
 // verbose: the counters compute_pairwise_matches prints per view (cudawrapper.cu:953,1114; line3D.cc:652), as totals of the pass -- the resident
 // chain never hands a view's lists to the host
@@ -214,14 +389,20 @@ static int match_views_reported(l3d_line3d* h)
     return rc;
 }
 
-int l3d_line3d_prepare(l3d_line3d* h) { return h ? prepare(h) : L3D_ERR_INVALID; }
+int l3d_line3d_prepare(l3d_line3d* h)
+{
+    if (h && h->node) return node_run(h, [h](int r) { return prepare(h->node->ranks[(size_t)r]); });
+    return h ? prepare(h) : L3D_ERR_INVALID;
+}
 int l3d_line3d_match_views(l3d_line3d* h)
 {
+    if (h && h->node) return node_refuse(h, "match_views");
     if (!h || !h->prepared) return h ? h->fail(L3D_ERR_INVALID, "prepare first") : L3D_ERR_INVALID;
     return match_views_reported(h);
 }
 int l3d_line3d_finish(l3d_line3d* h, int perform_diffusion)
 {
+    if (h && h->node) return node_refuse(h, "finish");
     if (!h || !h->prepared) return h ? h->fail(L3D_ERR_INVALID, "prepare first") : L3D_ERR_INVALID;
     const double t0 = now_s();
     if (h->partitioned && !h->part_exchange) return h->fail(L3D_ERR_INVALID, "finish: matchViews' products are partitioned over the ranks (l3d_line3d_finish_sharded)");
@@ -239,6 +420,7 @@ int l3d_line3d_finish(l3d_line3d* h, int perform_diffusion)
 int l3d_line3d_compute3Dmodel(l3d_line3d* h, int perform_diffusion)
 {
     if (!h) return L3D_ERR_INVALID;
+    if (h->node) return node_compute(h, perform_diffusion);
     int rc = prepare(h);
     if (!rc) rc = match_views_reported(h);
     if (!rc) rc = l3d_line3d_finish(h, perform_diffusion);
@@ -249,6 +431,7 @@ int l3d_line3d_compute3Dmodel(l3d_line3d* h, int perform_diffusion)
 // kept lists are all-gathered, every rank commits the same merged list) ---------------------------
 int l3d_line3d_match_begin(l3d_line3d* h, int* n_order)
 {
+    if (h && h->node) return node_refuse(h, "match_begin");
     if (!h || !h->prepared) return h ? h->fail(L3D_ERR_INVALID, "prepare first") : L3D_ERR_INVALID;
     match_begin(h);
     if (n_order) *n_order = (int)h->order.size();
@@ -257,6 +440,7 @@ int l3d_line3d_match_begin(l3d_line3d* h, int* n_order)
 int l3d_line3d_match_order(l3d_line3d* h, uint32_t* ids, int* n_segments)
 {
     if (!h) return L3D_ERR_INVALID;
+    if (h->node) return node_refuse(h, "match_order");
     for (size_t i = 0; i < h->order.size(); ++i) { if (ids) ids[i] = h->order[i]; if (n_segments) n_segments[i] = h->views[h->order[i]].S(); }
     return L3D_OK;
 }
@@ -264,6 +448,7 @@ int l3d_line3d_match_order(l3d_line3d* h, uint32_t* ids, int* n_segments)
 int l3d_line3d_view_num_to_be_matched(l3d_line3d* h, uint32_t view_id)
 {
     if (!h) return -1;
+    if (h->node) { node_refuse(h, "view_num_to_be_matched"); return -1; }
     auto it = h->visual_neighbors.find(view_id);
     if (it == h->visual_neighbors.end()) return -1;
     int n = 0;
@@ -274,6 +459,7 @@ int l3d_line3d_match_view_compute(l3d_line3d* h, uint32_t view_id, int seg_begin
                                   l3d_match** out, int* n_out, float* median, float** best, int* n_best)
 {
     if (!h) return L3D_ERR_INVALID;
+    if (h->node) return node_refuse(h, "match_view_compute");
     View* v = h->find_view(view_id);
     if (!v) return h->fail(L3D_ERR_INVALID, "unknown view");
     return compute_view(h, *v, seg_begin, seg_end, out, n_out, median, best, n_best);
@@ -283,6 +469,7 @@ int l3d_line3d_match_view_commit(l3d_line3d* h, uint32_t view_id, const l3d_matc
                                  const float* best_depths, int n_best, float median)
 {
     if (!h) return L3D_ERR_INVALID;
+    if (h->node) return node_refuse(h, "match_view_commit");
     View* v = h->find_view(view_id);
     if (!v) return h->fail(L3D_ERR_INVALID, "unknown view");
     if (n_best >= 0) {
@@ -300,6 +487,7 @@ int l3d_line3d_match_view_commit(l3d_line3d* h, uint32_t view_id, const l3d_matc
 // ---- matchViews as the resident chain sharded over ranks (one process per GPU; see include/line3d_amd.h) -----------
 int l3d_line3d_shard_open(l3d_line3d* h, int rank, int world, int slot_records, int* n_views, size_t* slot_bytes)
 {
+    if (h && h->node) return node_refuse(h, "shard_open");
     if (!h || !h->prepared) return h ? h->fail(L3D_ERR_INVALID, "prepare first") : L3D_ERR_INVALID;
     if (h->shard_plan_) return h->fail(L3D_ERR_INVALID, "a sharded chain is already open");
     match_begin(h);
@@ -315,6 +503,7 @@ int l3d_line3d_shard_open(l3d_line3d* h, int rank, int world, int slot_records, 
 }
 int l3d_line3d_shard_view_verified(l3d_line3d* h, int k)
 {
+    if (h && h->node) { node_refuse(h, "shard_view_verified"); return -1; }
     if (!h || !h->shard_plan_) return -1;
     ChainPlan* P = static_cast<ChainPlan*>(h->shard_plan_);
     if (k < 0 || (size_t)k >= P->n) return -1;
@@ -322,18 +511,21 @@ int l3d_line3d_shard_view_verified(l3d_line3d* h, int k)
 }
 int l3d_line3d_shard_enqueue(l3d_line3d* h, int k, void* send_slot, const void* gathered_base)
 {
+    if (h && h->node) return node_refuse(h, "shard_enqueue");
     if (!h || !h->shard_plan_) return L3D_ERR_INVALID;
     int rc = l3d_shard_chain_enqueue(static_cast<ChainPlan*>(h->shard_plan_)->shard, k, send_slot, gathered_base);
     return rc ? h->fail(rc, std::string("shard_chain_enqueue: ") + l3d_last_error(h->ctx)) : L3D_OK;
 }
 int l3d_line3d_shard_mark(l3d_line3d* h, int k)
 {
+    if (h && h->node) return node_refuse(h, "shard_mark");
     if (!h || !h->shard_plan_) return L3D_ERR_INVALID;
     return l3d_shard_chain_mark(static_cast<ChainPlan*>(h->shard_plan_)->shard, k);
 }
 // host bookkeeping of view k on this rank (optional per rank; views must be fetched in order)
 int l3d_line3d_shard_fetch(l3d_line3d* h, int k)
 {
+    if (h && h->node) return node_refuse(h, "shard_fetch");
     if (!h || !h->shard_plan_) return L3D_ERR_INVALID;
     ChainPlan* P = static_cast<ChainPlan*>(h->shard_plan_);
     int rc = l3d_shard_chain_fetch(P->shard, k, chain_callback, &P->user);
@@ -342,6 +534,7 @@ int l3d_line3d_shard_fetch(l3d_line3d* h, int k)
 // committed != 0: this rank fetched every view -> its host state is finalised (finish() may follow)
 int l3d_line3d_shard_close(l3d_line3d* h, int committed)
 {
+    if (h && h->node) return node_refuse(h, "shard_close");
     if (!h || !h->shard_plan_) return L3D_ERR_INVALID;
     ChainPlan* P = static_cast<ChainPlan*>(h->shard_plan_);
     int rc = l3d_shard_chain_close(P->shard);
@@ -360,6 +553,7 @@ int l3d_line3d_shard_run(l3d_line3d* h, int rank, int world, int slot_records, l
                          const void** gathered_out, size_t* slot_bytes_out)
 {
     if (!h) return L3D_ERR_INVALID;
+    if (h->node) return node_refuse(h, "shard_run");
     // A capacity failure is a verdict all ranks share (l3d_shard_chain_info): every rank reopens with the same, larger
     // capacities and runs again -- the bookkeeping of the failed attempt is dropped by the reopen (match_begin).
     size_t cand_cap_next = 0, arena_cap_next = 0;
@@ -471,12 +665,14 @@ static int block_run_impl(l3d_line3d* h, int rank, int world, int warmup_views, 
 }
 int l3d_line3d_block_run(l3d_line3d* h, int rank, int world, int warmup_views, l3d_exchange_fn exchange, void* exchange_user, int* verdict)
 {
+    if (h && h->node) return node_refuse(h, "block_run");
     return block_run_impl(h, rank, world, warmup_views, exchange, exchange_user, verdict, false);
 }
 // matchViews sharded by blocks of views with NOTHING replicated (l3d_match_chain_partition): this rank holds its block's share of the kept records
 // and of matchViews' products; the rest of compute3Dmodel is collective -- l3d_line3d_finish_sharded on every rank
 int l3d_line3d_partition_run(l3d_line3d* h, int rank, int world, int warmup_views, l3d_exchange_fn exchange, void* exchange_user, int* verdict)
 {
+    if (h && h->node) return node_refuse(h, "partition_run");
     return block_run_impl(h, rank, world, warmup_views, exchange, exchange_user, verdict, true);
 }
 // Line3D::compute3Dmodel's tail after l3d_line3d_partition_run, on every rank of the job: greedy selection on the views this rank holds, the affinity
@@ -484,6 +680,7 @@ int l3d_line3d_partition_run(l3d_line3d* h, int rank, int world, int warmup_view
 // clustering, line fit.  Every rank ends with the whole result.
 int l3d_line3d_finish_sharded(l3d_line3d* h, int perform_diffusion, l3d_exchange_fn exchange, void* exchange_user)
 {
+    if (h && h->node) return node_refuse(h, "finish_sharded");
     if (!h || !h->prepared) return h ? h->fail(L3D_ERR_INVALID, "prepare first") : L3D_ERR_INVALID;
     if (!h->partitioned || !h->resident_products) return h->fail(L3D_ERR_INVALID, "finish_sharded: matchViews did not run partitioned (l3d_line3d_partition_run)");
     if (exchange) { h->part_exchange = exchange; h->part_user = exchange_user; }
@@ -492,8 +689,14 @@ int l3d_line3d_finish_sharded(l3d_line3d* h, int perform_diffusion, l3d_exchange
 }
 // how the last l3d_line3d_match_views ran: 0 = the resident chain with its products on the device, 1 = the chain with host bookkeeping, 2 = per-view
 // seam calls because the caller asked (l3d_line3d_set_sync_matching), 3 = per-view seam calls because the schedule is not static (-1: not yet)
-int l3d_line3d_match_path(const l3d_line3d* h) { return h ? h->last_match_path : -1; }
-int l3d_line3d_match_end(l3d_line3d* h) { if (!h) return L3D_ERR_INVALID; finalize_matching(h); return L3D_OK; }
+int l3d_line3d_match_path(const l3d_line3d* h) { return !h ? -1 : h->node ? l3d_line3d_match_path(rank0(h)) : h->last_match_path; }
+int l3d_line3d_match_end(l3d_line3d* h)
+{
+    if (!h) return L3D_ERR_INVALID;
+    if (h->node) return node_refuse(h, "match_end");
+    finalize_matching(h);
+    return L3D_OK;
+}
 
 // performClustering (clustering.h:125, clustering.cc:6-47) as a host entry point: labels[k] = find(k)
 int l3d_perform_clustering(const l3d_edge* edges, int n_edges, int num_nodes, float c, int32_t* labels)
@@ -511,6 +714,7 @@ int l3d_perform_clustering(const l3d_edge* edges, int n_edges, int num_nodes, fl
 int l3d_line3d_result_sizes(const l3d_line3d* h, int* n_lines, int* n_seg3d, int* n_seg2d)
 {
     if (!h) return L3D_ERR_INVALID;
+    if (h->node) return l3d_line3d_result_sizes(rank0(h), n_lines, n_seg3d, n_seg2d);
     int a = 0, b = 0;
     for (auto& l : h->result) { a += (int)l.segs3D.size(); b += (int)l.segs2D.size(); }
     if (n_lines) *n_lines = (int)h->result.size();
@@ -522,6 +726,7 @@ int l3d_line3d_result_sizes(const l3d_line3d* h, int* n_lines, int* n_seg3d, int
 int l3d_line3d_get_result(const l3d_line3d* h, int* line_n3d, int* line_n2d, double* seg3d, uint32_t* seg2d)
 {
     if (!h) return L3D_ERR_INVALID;
+    if (h->node) return l3d_line3d_get_result(rank0(h), line_n3d, line_n2d, seg3d, seg2d);
     size_t a = 0, b = 0, li = 0;
     for (auto& l : h->result) {
         line_n3d[li] = (int)l.segs3D.size(); line_n2d[li] = (int)l.segs2D.size(); ++li;
@@ -536,6 +741,7 @@ int l3d_line3d_get_result(const l3d_line3d* h, int* line_n3d, int* line_n2d, dou
 // digits, "%g") in the TXT file; lines without 3-D segments are skipped in the TXT file only.
 int l3d_line3d_save_result(const l3d_line3d* h, const char* filename, int format)
 {
+    if (h && h->node) return l3d_line3d_save_result(rank0(h), filename, format);
     if (!h || !filename || (format != L3D_FORMAT_STL && format != L3D_FORMAT_TXT)) return L3D_ERR_INVALID;
     FILE* f = fopen(filename, "w");
     if (!f) return L3D_ERR_INVALID;
@@ -571,6 +777,7 @@ int l3d_line3d_get_segment2D(const l3d_line3d* h, uint32_t cam, uint32_t seg, fl
 {
     if (out) out[0] = out[1] = out[2] = out[3] = 0.0f;        // zeroed before any early return
     if (!h || !out) return L3D_ERR_INVALID;
+    if (h->node) return l3d_line3d_get_segment2D(rank0(h), cam, seg, out);
     auto it = h->views.find(cam);
     if (it == h->views.end() || seg >= (uint32_t)it->second.S()) return L3D_ERR_INVALID;
     memcpy(out, &it->second.segs[(size_t)seg * 4], 16);
@@ -578,11 +785,24 @@ int l3d_line3d_get_segment2D(const l3d_line3d* h, uint32_t cam, uint32_t seg, fl
 }
 
 // ---- inspection for tests / bench ----------------------------------------------------------------
-int l3d_line3d_set_sync_matching(l3d_line3d* h, int on) { if (!h) return L3D_ERR_INVALID; h->force_sync = on != 0; return L3D_OK; }
-int l3d_line3d_keep_view_matches(l3d_line3d* h, int on) { if (!h) return L3D_ERR_INVALID; h->keep_view_matches = on != 0; return L3D_OK; }
+int l3d_line3d_set_sync_matching(l3d_line3d* h, int on)
+{
+    if (!h) return L3D_ERR_INVALID;
+    if (h->node) return node_refuse(h, "set_sync_matching");
+    h->force_sync = on != 0;
+    return L3D_OK;
+}
+int l3d_line3d_keep_view_matches(l3d_line3d* h, int on)
+{
+    if (!h) return L3D_ERR_INVALID;
+    if (h->node) return node_each(h, [on](L* r) { return l3d_line3d_keep_view_matches(r, on); });
+    h->keep_view_matches = on != 0;
+    return L3D_OK;
+}
 int l3d_line3d_view_matches(const l3d_line3d* h, uint32_t view_id, const l3d_match** m, int* n, float* median)
 {
     if (!h) return L3D_ERR_INVALID;
+    if (h->node) return node_refuse(const_cast<L*>(h), "view_matches");
     auto it = h->view_matches.find(view_id);
     if (m) *m = it == h->view_matches.end() ? nullptr : it->second.data();
     if (n) *n = it == h->view_matches.end() ? 0 : (int)it->second.size();
@@ -593,6 +813,7 @@ int l3d_line3d_view_matches(const l3d_line3d* h, uint32_t view_id, const l3d_mat
 int l3d_line3d_affinity(const l3d_line3d* h, const l3d_edge** A, int* nnz, int* n_nodes)
 {
     if (!h) return L3D_ERR_INVALID;
+    if (h->node) return l3d_line3d_affinity(rank0(h), A, nnz, n_nodes);
     if (A) { if (int rc = ensure_edges(const_cast<l3d_line3d*>(h))) return rc; *A = h->A.data(); }
     if (nnz) *nnz = (int)h->n_edges;
     if (n_nodes) *n_nodes = (int)h->local2global.size();
@@ -601,6 +822,7 @@ int l3d_line3d_affinity(const l3d_line3d* h, const l3d_edge** A, int* nnz, int* 
 int l3d_line3d_products_sizes(const l3d_line3d* h, int* n_views, int* n_dense, int64_t* n_pot, int* n_hyp)
 {
     if (!h) return L3D_ERR_INVALID;
+    if (h->node) return node_refuse(const_cast<L*>(h), "products_sizes");
     const bool on = h->resident_products;
     int nd = 0;
     for (const View* v : h->vlist) nd += v->S();
@@ -613,6 +835,11 @@ int l3d_line3d_products_sizes(const l3d_line3d* h, int* n_views, int* n_dense, i
 int l3d_line3d_chain_summary(const l3d_line3d* h, const l3d_chain_summary** summary, int* n)
 {
     if (!h || !summary || !n) return L3D_ERR_INVALID;
+    if (h->node) {          // (node_compute: the views of every rank's block)
+        *summary = h->chain_summary.empty() ? nullptr : h->chain_summary.data();
+        *n = (int)h->chain_summary.size();
+        return L3D_OK;
+    }
     const bool on = h->resident_products;
     *summary = on && !h->chain_summary.empty() ? h->chain_summary.data() : nullptr;
     *n = on ? (int)h->chain_summary.size() : 0;
@@ -621,6 +848,7 @@ int l3d_line3d_chain_summary(const l3d_line3d* h, const l3d_chain_summary** summ
 int l3d_line3d_products_get(l3d_line3d* h, int32_t* seg_base, int64_t* pot_start, int32_t* pot_tgt, l3d_match* best, l3d_hypothesis* hyp, float* score)
 {
     if (!h) return L3D_ERR_INVALID;
+    if (h->node) return node_refuse(h, "products_get");
     if (!h->resident_products) return h->fail(L3D_ERR_INVALID, "no resident products");
     if (seg_base) { int b = 0; size_t i = 0; for (const View* v : h->vlist) { seg_base[i++] = b; b += v->S(); } seg_base[i] = b; }
     int rc = l3d_chain_products_get(h->ctx, pot_start, pot_tgt, best);
@@ -631,6 +859,7 @@ int l3d_line3d_products_get(l3d_line3d* h, int32_t* seg_base, int64_t* pot_start
 int l3d_line3d_stats(const l3d_line3d* h, double* s)
 {
     if (!h || !s) return L3D_ERR_INVALID;
+    if (h->node) return l3d_line3d_stats(rank0(h), s);
     s[0] = h->stat_pairs; s[1] = h->stat_raw; s[2] = h->stat_kept; s[3] = (double)h->hyps.size();
     s[4] = h->t_match; s[5] = h->t_gpu_call; s[6] = h->t_commit; s[7] = h->t_finalize; s[8] = h->t_affinity; s[9] = h->t_cluster;
     s[10] = (double)h->n_edges; s[11] = (double)h->result.size();

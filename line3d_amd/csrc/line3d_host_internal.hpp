@@ -158,12 +158,15 @@ struct FinalLine {
     std::vector<std::pair<V3, V3>> segs3D;
 };
 
+struct NodeRanks;                                  // the ranks of a node object (line3d_host.cpp)
+
 }  // namespace l3dh
 using namespace l3dh;
 
 
 struct l3d_line3d {
-    l3d_ctx* ctx = nullptr;
+    l3d_ctx* ctx = nullptr;                                    // (none on a node object: its ranks own one each)
+    NodeRanks* node = nullptr;                                 // a node object (l3d_line3d_create_node): W ordinary objects, one per rank
     std::string err;
     bool verbose = false;
     // parameters, line3D.cc:6-31

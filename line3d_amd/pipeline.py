@@ -17,7 +17,12 @@ SUMMARY_DTYPE = np.dtype([("verified", np.int32), ("n_kept", np.int32), ("n_cand
 class Line3D:
     def __init__(self, data_directory: str = "", matchingNeighbors: int = 10, uncertainty_t_upper_2D: float = 5.0,
                  uncertainty_t_lower_2D: float = 1.0, sigma_p: float = 3.5, sigma_a: float = 10.0,
-                 min_baseline: float = 0.25, useCollinearity: bool = True, verbose: bool = False, device: int = 0, crosschecks: bool = False):
+                 min_baseline: float = 0.25, useCollinearity: bool = True, verbose: bool = False, device: int | None = None, crosschecks: bool = False,
+                 devices=None):
+        """devices: a list of HIP device ids -- one object over several GPUs of this process (l3d_line3d_create_node: rank r on devices[r], a
+        device may repeat); compute3Dmodel runs matchViews partitioned over the ranks.  device: the one GPU of an ordinary object."""
+        if device is not None and devices is not None:
+            raise ValueError("Line3D: give device or devices, not both")
         self.lib = capi.load_library(crosschecks)        # (crosschecks: the test-only build in which the L3D_HOST_* switches exist)
         self.lib.l3d_line3d_last_error.restype = C.c_char_p
         self.lib.l3d_line3d_last_error.argtypes = [C.c_void_p]
@@ -26,11 +31,18 @@ class Line3D:
         self.lib.l3d_line3d_destroy.argtypes = [C.c_void_p]
         self.data_directory = data_directory          # kept for signature parity; nothing is written to disk
         h = C.c_void_p()
-        rc = self.lib.l3d_line3d_create(C.c_int(device), C.c_int(matchingNeighbors), C.c_float(uncertainty_t_upper_2D),
-                                        C.c_float(uncertainty_t_lower_2D), C.c_float(sigma_p), C.c_float(sigma_a),
-                                        C.c_float(min_baseline), C.c_int(int(useCollinearity)), C.c_int(int(verbose)), C.byref(h))
-        if rc != 0:
-            raise L3DError("l3d_line3d_create failed (code %d): no usable MI355X / HIP device -- no CPU fallback" % rc)
+        params = (C.c_int(matchingNeighbors), C.c_float(uncertainty_t_upper_2D), C.c_float(uncertainty_t_lower_2D), C.c_float(sigma_p),
+                  C.c_float(sigma_a), C.c_float(min_baseline), C.c_int(int(useCollinearity)), C.c_int(int(verbose)), C.byref(h))
+        if devices is not None:
+            devs = np.ascontiguousarray(list(devices), dtype=np.int32)
+            rc = self.lib.l3d_line3d_create_node(_p(devs) if len(devs) else None, C.c_int(len(devs)), *params)
+            if rc != 0:
+                raise L3DError("l3d_line3d_create_node(%s) failed (code %d): no usable set of MI355X / HIP devices -- no CPU fallback"
+                               % (list(devices), rc))
+        else:
+            rc = self.lib.l3d_line3d_create(C.c_int(0 if device is None else device), *params)
+            if rc != 0:
+                raise L3DError("l3d_line3d_create failed (code %d): no usable MI355X / HIP device -- no CPU fallback" % rc)
         self.h = h
         self._keep = []
 
@@ -49,11 +61,23 @@ class Line3D:
         if rc != 0:
             raise L3DError("line3d_amd error %d: %s" % (rc, self.lib.l3d_line3d_last_error(self.h).decode()))
 
+    def num_ranks(self) -> int:
+        """ranks of the object: len(devices) of a node object, 1 otherwise"""
+        return int(self.lib.l3d_line3d_num_ranks(self.h))
+
+    def set_node_mode(self, mode: int):
+        """how compute3Dmodel shards matchViews over the ranks of a node object: 0 = segments of every view (default), 1 = blocks of views
+        (falls back to 0 where its verdict says the speculation cannot hold)"""
+        self._chk(self.lib.l3d_line3d_set_node_mode(self.h, C.c_int(int(mode))))
+
     def context(self) -> capi.Context:
-        """The pipeline's l3d_ctx as a (non-owning) Context, for profiling."""
+        """The pipeline's l3d_ctx as a (non-owning) Context, for profiling (refused on a node object: one context per rank)."""
         c = capi.Context.__new__(capi.Context)
         c.lib = self.lib
-        c.h = C.c_void_p(self.lib.l3d_line3d_context(self.h))
+        ptr = self.lib.l3d_line3d_context(self.h)
+        if not ptr:
+            raise L3DError("line3d_amd: %s" % self.lib.l3d_line3d_last_error(self.h).decode())
+        c.h = C.c_void_p(ptr)
         c._keep = []
         c.close = lambda: None
         return c
@@ -222,7 +246,8 @@ class Line3D:
 
     def shard_run(self, rank: int, world: int, slot_records: int, exchange: str = "local", exchange_user=None, commit: bool = True):
         """The whole sharded chain as one native call (l3d_shard_chain_run).  exchange: "rccl" (exchange_user = a ctypes
-        l3d_rccl_link), "local" (world 1) or "replay" (exchange_user = device address of recorded gathered blocks).
+        l3d_rccl_link), "local" (world 1), "replay" (exchange_user = device address of recorded gathered blocks) or "node" (exchange_user =
+        capi.NodeComm.h of the ranks of this process, this object's stream bound to its rank).
         commit: False / 0 = compute and exchange only, True / 1 = host bookkeeping on this rank, 2 (or "device") = matchViews' products built on
         this rank's device from the gathered slots, 3 (or "partition") = as 2, but this rank keeps the records and builds the rows of its block of
         views only (l3d_shard_chain_partition: exact without speculation; finish_sharded() follows on every rank).
@@ -235,7 +260,8 @@ class Line3D:
             proto = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
             fn = self._exchange_keepalive = proto(exchange)
         else:
-            fn = {"rccl": self.lib.l3d_exchange_rccl, "local": self.lib.l3d_exchange_local, "replay": self.lib.l3d_exchange_replay}[exchange]
+            fn = {"rccl": self.lib.l3d_exchange_rccl, "local": self.lib.l3d_exchange_local, "replay": self.lib.l3d_exchange_replay,
+                  "node": self.lib.l3d_exchange_node}[exchange]
         user = C.c_void_p(exchange_user) if isinstance(exchange_user, int) else (C.c_void_p(C.addressof(exchange_user)) if exchange_user is not None else None)
         g = C.c_void_p(0)
         sb = C.c_size_t(0)
@@ -250,7 +276,7 @@ class Line3D:
             proto = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
             fn = self._exchange_keepalive = proto(exchange)
         else:
-            fn = {"rccl": self.lib.l3d_exchange_rccl, "local": self.lib.l3d_exchange_local}[exchange]
+            fn = {"rccl": self.lib.l3d_exchange_rccl, "local": self.lib.l3d_exchange_local, "node": self.lib.l3d_exchange_node}[exchange]
         user = C.c_void_p(exchange_user) if isinstance(exchange_user, int) else (C.c_void_p(C.addressof(exchange_user)) if exchange_user is not None else None)
         verdict = C.c_int(1)
         self._chk(self.lib.l3d_line3d_block_run(self.h, C.c_int(rank), C.c_int(world), C.c_int(warmup_views), C.cast(fn, C.c_void_p), user, C.byref(verdict)))
@@ -263,7 +289,7 @@ class Line3D:
             proto = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
             fn = self._exchange_keepalive = proto(exchange)
         else:
-            fn = {"rccl": self.lib.l3d_exchange_rccl, "local": self.lib.l3d_exchange_local}[exchange]
+            fn = {"rccl": self.lib.l3d_exchange_rccl, "local": self.lib.l3d_exchange_local, "node": self.lib.l3d_exchange_node}[exchange]
         user = C.c_void_p(exchange_user) if isinstance(exchange_user, int) else (C.c_void_p(C.addressof(exchange_user)) if exchange_user is not None else None)
         verdict = C.c_int(1)
         self._chk(self.lib.l3d_line3d_partition_run(self.h, C.c_int(rank), C.c_int(world), C.c_int(warmup_views), C.cast(fn, C.c_void_p), user, C.byref(verdict)))
