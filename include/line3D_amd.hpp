@@ -81,6 +81,10 @@ public:
     Line3D(const Line3D&) = delete;
     Line3D& operator=(const Line3D&) = delete;
     bool valid() const { return h_ != nullptr; }
+    // how an object built from a device list shards matchViews (l3d_line3d_set_node_mode): 0 = the segments of every view (default), 1 = blocks of
+    // views, 2 = the ranks of a device take turns on it -- a scene whose kept records do not fit the device at once, at the cost of about one
+    // single-device matchViews per rank.  Without effect on a one-device object.  false: no such mode (message printed)
+    bool setNodeMode(const int mode) { const int rc = l3d_line3d_set_node_mode(h_, mode); report(rc); return rc == L3D_OK; }
 
     // line3D.h:69-73; errors are printed and the call returns, like the reference (line3D.cc:101-127).  `image` is replaced by its size
     // and the segments the detector would have produced; maxImgWidth / loadAndStoreSegments keep their meaning: the segment cache

@@ -275,6 +275,14 @@ int l3d_match_chain_resident(l3d_ctx* ctx, const l3d_chain_view* views, int n_vi
  * 0xffffffff where a segment has none; camera ids as in the kept lists: GLOBAL, LOCAL for early-return views) -- any
  * pointer may be NULL. */
 int l3d_chain_kept_list(l3d_ctx* ctx, int index, l3d_match** out, int* n);
+/* What only matchViews and l3d_products_hypotheses read goes back to the device: the kept arena, its side words and run tables, the early pair
+ * transposes, the chain's scratch.  The products stay (rows, hypotheses): affinity fill, clustering and fits run as before.  Afterwards
+ * l3d_chain_kept_list, l3d_chain_records_digest, l3d_products_hypotheses and the best matches of l3d_chain_products_get return L3D_ERR_INVALID
+ * with a message, until the next chain builds its products. */
+int l3d_chain_release_records(l3d_ctx* ctx);
+/* an order-sensitive 64-bit digest and the length of the kept list of every chain view of the resident products (n = their number of chain views;
+ * 0 / 0 for a view of which this context holds nothing, and for an early-return view, whose list is rebuilt from its sources' records): what two contexts that ran the same chain with different keep sets must agree on */
+int l3d_chain_records_digest(l3d_ctx* ctx, uint64_t* hash, int32_t* n_kept, int n);
 int l3d_chain_products_get(l3d_ctx* ctx, int64_t* pot_start, int32_t* pot_tgt, l3d_match* best_match);
 
 /* Line3D::greedySelection (line3D.cc:899-965) on the resident products: one 3-D hypothesis per segment that has a best
@@ -524,8 +532,19 @@ int l3d_line3d_num_ranks(const l3d_line3d* h);
 /* how compute3Dmodel shards matchViews over the ranks of a node object: 0 (default) = the source segments of every view, partitioned
  * (l3d_line3d_shard_run, commit = 3: exact on every scene, no speculation); 1 = blocks of views, partitioned (l3d_line3d_partition_run), falling
  * back to 0 in the same call when its verdict says the speculation cannot hold (printed under verbose).  Accepted, and without effect, on a
- * single-device object. */
+ * single-device object.
+ * 2 = the ranks that share a device TAKE TURNS on it, for a scene whose kept records do not fit one device's memory at once: rank r computes its share of
+ * the W-rank job alone (the whole chain at world 1 with the keep set of block r -- l3d_partition_keep_views --, the rows of its share of the products, its
+ * hypotheses), takes the digests of the views it held, releases the kept arena (l3d_chain_release_records) and hands the device's token to the next rank; ranks on
+ * different devices run at the same time; turn 0 runs first and sizes every later turn exactly.  When every turn is over the 64-bit digests of the
+ * views two ranks both held are compared (a mismatch is L3D_ERR_INVALID naming the view and both ranks) and the collective finish of mode 0 follows,
+ * the device's token held around every rank's candidate enumeration.  Every turn computes the whole chain: matchViews costs about W single passes.
+ * The result is the one-device object's, bit for bit. */
 int l3d_line3d_set_node_mode(l3d_line3d* h, int mode);
+/* after a compute3Dmodel in mode 2: the kept records rank `rank` retired in its turn -- the records its arena held when the chain ended (of whatever view), plus the lists of
+ * the early-return views it held as chain_summary counts them (rebuilt from their sources' records: no room of their own in the arena).  For a turn
+ * that kept exactly its keep set this is the sum of the one chain's chain_summary kept counts over the views l3d_partition_keep_views gives its block.  L3D_ERR_INVALID on a single-device object, a rank out of range or when the last run took no turns. */
+int l3d_line3d_node_turn_records(const l3d_line3d* h, int rank, int64_t* records);
 void l3d_line3d_destroy(l3d_line3d* h);
 const char* l3d_line3d_last_error(const l3d_line3d* h);
 l3d_ctx* l3d_line3d_context(l3d_line3d* h);

@@ -267,6 +267,17 @@ class Context:
         self.lib.l3d_free(nodes)
         return A, node_hyp, nc.value
 
+    def chain_release_records(self):
+        """l3d_chain_release_records: the kept arena, its side words and run tables, the early transposes and the chain's scratch go back to the
+        device; the products stay.  chain_kept_list raises afterwards, until the next chain."""
+        self._chk(self.lib.l3d_chain_release_records(self.h))
+
+    def chain_records_digest(self, n: int):
+        """l3d_chain_records_digest: (uint64 digests, int32 lengths) of the kept lists of the n chain views of the resident products"""
+        hsh, cnt = np.zeros(n, np.uint64), np.zeros(n, np.int32)
+        self._chk(self.lib.l3d_chain_records_digest(self.h, hsh.ctypes.data_as(C.c_void_p), cnt.ctypes.data_as(C.c_void_p), C.c_int(n)))
+        return hsh, cnt
+
     def chain_kept_list(self, index: int):
         """l3d_chain_kept_list: the kept list of chain view `index` out of the resident arena (MATCH_DTYPE array); partitioned products: the
         views this rank holds, empty for the others"""

@@ -1068,7 +1068,18 @@ int l3d_affinity_fill_sharded(l3d_ctx* c, const int64_t* coll_start, const int32
             fp.h0 = P.view_hyp_begin[(size_t)part.own_dv0]; fp.h1 = P.view_hyp_begin[(size_t)part.own_dv1];
             fp.pos_base = (unsigned long long)rank << 44; fp.loc2glob = c->aff_l2g.as<int>(); fp.assume_symmetric = 1;
             int n_e = 0, n_n = 0, n_c = 0; int32_t* nhp = nullptr;
+            // (ranks that share a device: the enumeration's candidate blocks are one rank's at a time -- the gate is the device's token, no collective lies inside it.
+            // A rank that is through waits for the others in the next exchange, whose barrier gives up after 600 s: the enumerations of one device's ranks,
+            // one after another, have to fit into that -- seconds each on the scenes measured)
+            if (c->fill_gate) c->fill_gate(c->fill_gate_user, 1);
             rc = affinity_fill_core(c, a, P.seg_base.data(), P.view_hyp_begin.data(), P.n_pot, n_coll, sigma_a, nullptr, &n_e, &nhp, &n_n, &n_c, &fp);
+            if (c->fill_gate) {
+                // what the blocks of sources were enumerated in goes back before the next rank of the device enumerates its own
+                (void)hipStreamSynchronize(st);
+                DevBuf* b[] = { &c->g0, &c->g1, &c->g2, &c->g3, &c->g4, &c->g5, &c->g6 };
+                for (DevBuf* x : b) x->release();
+                c->fill_gate(c->fill_gate_user, 0);
+            }
         }
         note(rc);
     } else { c->fill_items = 0; c->fill_passed = 0; }
@@ -1158,9 +1169,20 @@ int l3d_affinity_fill_sharded(l3d_ctx* c, const int64_t* coll_start, const int32
         hipError_t e = hipStreamSynchronize(st);
         if (e != hipSuccess) { free(hd); return fail(c, L3D_ERR_HIP, std::string("l3d_affinity_fill_sharded: ") + hipGetErrorString(e)); }
     }
+    c->fill_items = items_all; c->fill_passed = passed_all;
+    // (a rank whose result nobody reads -- the ranks of a node object took turns on one device, the model comes from rank 0: no numbering, no edge list,
+    // an empty hypothesis table; the stages behind the fill then have nothing to do)
+    if (c->fill_collective_only) {
+        free(hd);
+        int32_t* hd0 = static_cast<int32_t*>(malloc(8));
+        int32_t* nh0 = static_cast<int32_t*>(malloc(8));
+        if (!hd0 || !nh0) { free(hd0); free(nh0); return fail(c, L3D_ERR_NOMEM, "malloc"); }
+        for (int v = 0; v <= V; ++v) view_hyp_begin_global[v] = 0;
+        *hyp_dense_global = hd0; *node_hyp_out = nh0;
+        return L3D_OK;
+    }
     memcpy(view_hyp_begin_global, vhb.data(), (size_t)(V + 1) * 4);
     *hyp_dense_global = hd; *n_hyp_global = nh_all;
-    c->fill_items = items_all; c->fill_passed = passed_all;
     P.n_hyp = nh_all;                                 // (l3d_products_hypotheses_get now returns the whole table; the local index tables of the fill are spent)
     // ---- 6. numbering and edges: every rank from the same data
     int rc = affinity_number_edges(c, c->aff_first.as<unsigned long long>(), nh_all, c->aff_pass_pairs.as<int2>(), c->aff_pass_w.as<float>(), passed_all, nullptr, n_edges_out, node_hyp_out, n_nodes_out);

@@ -18,6 +18,7 @@
 
 #include "l3d_ctx.hpp"
 #include "l3d_hostsort.hpp"
+#include "l3d_turns.hpp"
 
 using namespace l3d;
 
@@ -40,6 +41,21 @@ Options options_from_env()
     return o;
 }
 const Options& ctx_options(const l3d_ctx* c) { return c->opt; }
+void ctx_turn_share(l3d_ctx* c, int on) { if (c) c->turn_share = on != 0; }
+void ctx_fill_gate(l3d_ctx* c, void (*gate)(void*, int), void* user) { if (c) { c->fill_gate = gate; c->fill_gate_user = user; } }
+void ctx_fill_collective_only(l3d_ctx* c, int on) { if (c) c->fill_collective_only = on != 0; }
+const std::vector<int>& ctx_shard_view_kept(const l3d_ctx* c) { return c->shard_view_kept; }
+void ctx_release_share(l3d_ctx* c)
+{
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    (void)hipStreamSynchronize(c->stream);
+    c->products.release();
+    DevBuf* bufs[] = { &c->aff_hyp, &c->aff_first, &c->aff_pass_pairs, &c->aff_pass_w, &c->aff_l2g, &c->edges_keep, &c->ch_send, &c->ch_gathered, &c->ch_hdr,
+                       &c->g0, &c->g1, &c->g2, &c->g3, &c->g4, &c->g5, &c->g6, &c->g7 };
+    for (DevBuf* b : bufs) b->release();
+    c->resident_hyp = 0; c->resident_edges = 0; c->kept_edges = 0; c->resident_nodes = 0; c->resident_labels = 0;
+}
 }  // namespace l3d
 
 extern "C" {
@@ -150,6 +166,30 @@ void l3d_ctx_destroy(l3d_ctx* c)
 }
 
 const char* l3d_last_error(const l3d_ctx* c) { return c ? c->err.c_str() : "null context"; }
+
+// What only matchViews and the hypotheses read goes back to the device: the kept arena with its side words and run tables, the early pair
+// transposes, the chain's scratch and the scratch the products were built in.  The products themselves (rows, best matches as hypotheses, medians'
+// host copies) stay: the affinity fill, the clustering and the fits read nothing of what is released here.
+int l3d_chain_release_records(l3d_ctx* c)
+{
+    if (!c) return L3D_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stage1_stream));
+    HIPCHK(c, hipStreamSynchronize(c->copy_stream));
+    if (c->prod_stream) HIPCHK(c, hipStreamSynchronize(c->prod_stream));
+    Products& P = c->products;
+    DevBuf* bufs[] = { &c->ch_kept, &c->ch_keptcam, &c->ch_rt, &c->ch_rtinfo, &c->ch_rtjobs, &c->ch_existpart,                                    // records, side words, run tables
+                       &P.e_cnt, &P.e_poff, &P.e_boff, &P.e_E, &P.e_T, &P.e_tab,                                                                     // early pair transposes
+                       &c->ch_tables, &c->ch_mask, &c->ch_rowcnt, &c->ch_cursor, &c->ch_best, &c->ch_bestpos, &c->ch_res, &c->ch_flags, &c->ch_send, // the chain's scratch
+                       &c->ch_gathered, &c->ch_stage, &c->ch_rowA, &c->ch_ringA_meta, &c->ch_ringA_depths, &c->ch_segorder, &c->ch_rays, &c->ch_hdr,
+                       &c->cand_meta, &c->cand_depths, &c->cand_conf, &c->vw_scratch, &c->vw_bstart, &c->vw_segstate,
+                       &P.keys, &P.keys2, &P.flag, &P.pos, &P.tmp, &P.best_ref, &P.tables, &P.ttab, &P.rowstage, &P.tstage, &c->g7 };                // the products' building blocks
+    for (DevBuf* b : bufs) b->release();
+    P.e_boff_off.clear();
+    c->records_released = true;
+    return L3D_OK;
+}
 void l3d_free(void* p) { free(p); }
 
 int l3d_register_segments(l3d_ctx* c, const float* segments, int n_segments)

@@ -930,6 +930,40 @@ __global__ __launch_bounds__(256) void k_block_digest(const Match* __restrict__ 
 
 }  // namespace l3d
 
+// k_block_digest over the kept lists of the resident products, whoever built them: hash[k] / n_kept[k] of every chain view (0 / 0: nothing of
+// the view is held here).  What two ranks that took turns on one device compare of the views both held, before the records are released.
+extern "C" int l3d_chain_records_digest(l3d_ctx* c, uint64_t* hash, int32_t* n_kept, int n)
+{
+    if (!c) return L3D_ERR_INVALID;
+    Products& P = c->products;
+    if (!hash || !n_kept || n < 0) return fail(c, L3D_ERR_INVALID, "l3d_chain_records_digest: bad argument");
+    if (!P.valid || n != P.n_chain || (int)P.res.size() != n) return fail(c, L3D_ERR_INVALID, "l3d_chain_records_digest: no resident products of that many chain views");
+    if (c->records_released) return fail(c, L3D_ERR_INVALID, "l3d_chain_records_digest: the kept records of this chain were released (l3d_chain_release_records)");
+    if (n == 0) return L3D_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    // every list must lie inside the arena: the kernel trusts the records' table
+    for (int k = 0; k < n; ++k) {
+        const ChainResult& r = P.res[(size_t)k];
+        if (r.n_kept < 0 || (r.n_kept > 0 && ((size_t)r.kept_base + (size_t)r.n_kept) * sizeof(Match) > c->ch_kept.cap))
+            return fail(c, L3D_ERR_INVALID, "l3d_chain_records_digest: a kept list lies outside the arena");
+    }
+    const size_t o_dig = ((size_t)n * sizeof(ChainResult) + 255) & ~(size_t)255;
+    HIPCHK(c, c->g7.reserve(o_dig + (size_t)n * sizeof(BlockDigest) + 64));
+    ChainResult* dres = c->g7.as<ChainResult>();
+    BlockDigest* dd = reinterpret_cast<BlockDigest*>(c->g7.as<unsigned char>() + o_dig);
+    HIPCHK(c, hipMemcpyAsync(dres, P.res.data(), (size_t)n * sizeof(ChainResult), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemsetAsync(dd, 0, (size_t)n * sizeof(BlockDigest), st));
+    for (int k0 = 0; k0 < n; k0 += 32768)        // (a launch's second grid dimension holds 65 535 blocks)
+        hipLaunchKernelGGL(k_block_digest, dim3(16, (unsigned)std::min(32768, n - k0)), dim3(256), 0, st, c->ch_kept.as<Match>(), dres, k0, dd);
+    std::vector<BlockDigest> hd((size_t)n);
+    HIPCHK(c, hipMemcpyAsync(hd.data(), dd, (size_t)n * sizeof(BlockDigest), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, hipGetLastError());
+    for (int k = 0; k < n; ++k) { hash[k] = hd[(size_t)k].hash; n_kept[k] = hd[(size_t)k].n_kept; }
+    return L3D_OK;
+}
+
 namespace l3d {
 
 // one source's records that point at an early-return view, in list order (stable): out == nullptr counts only

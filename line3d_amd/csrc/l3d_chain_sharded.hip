@@ -754,6 +754,10 @@ int l3d_shard_chain_run(l3d_shard_chain* h, l3d_exchange_fn exchange, void* exch
             }
             (void)hipGetLastError();
         }
+        // (tests, option regrow_free_mb: a card with less room -- the compact arena and its side words may take that much and no more: a first guess above it
+        // is cut to it, a run that needs more ends with the capacity verdict and l3d_line3d_shard_run's NOMEM)
+        const long long room_records = c->opt.regrow_free_mb > 0 ? (long long)(((size_t)c->opt.regrow_free_mb << 20) / (sizeof(Match) + 4)) : 0;
+        if (room_records > 0 && !h->partition) h->arena_cap = std::min(h->arena_cap, room_records);
         if (!h->partition) HIPCHK(c, c->ch_kept.reserve(((size_t)h->arena_cap + 64) * sizeof(Match)));
         auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
         const size_t nvs = (size_t)h->n_views;
@@ -779,6 +783,7 @@ int l3d_shard_chain_run(l3d_shard_chain* h, l3d_exchange_fn exchange, void* exch
             h->keep_dev = hb + o_keep;
             // (the first guess of the arena: this rank's share of the scene's)
             if (!c->test_arena_cap) { long long kv = 0; for (unsigned char x : h->keep) kv += x; h->arena_cap = std::max<long long>((long long)c->part_arena_seen, h->arena_cap * kv / std::max(1, h->n_views) + 1048576); }
+            if (room_records > 0) h->arena_cap = std::min(h->arena_cap, room_records);
             HIPCHK(c, c->ch_kept.reserve_exact(((size_t)h->arena_cap + 64) * sizeof(Match)));
         }
         // the retired views' side words and run tables (slots that carry a side array carry both)
@@ -1132,6 +1137,8 @@ static int shard_products_local(l3d_shard_chain* h, const l3d_dense_map* map, l3
     std::vector<int2> tot(nvs);
     HIPCHK(c, hipMemcpyAsync(tot.data(), sc + o_tot, nvs * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
+    c->shard_view_kept.assign(nvs, 0);
+    for (int k = 0; k < nv; ++k) c->shard_view_kept[(size_t)k] = h->vd[(size_t)k].verified ? tot[(size_t)k].x : 0;
     std::vector<ChainResult> hres(nvs);
     std::vector<ProdChainView> pvh(nvs);
     std::vector<unsigned long long> kept_base(nvs, 0);
@@ -1160,6 +1167,8 @@ static int shard_products_local(l3d_shard_chain* h, const l3d_dense_map* map, l3
             auto dense_of = [&](int k) { if (k >= nv) return map->n_views; const uint32_t* it = std::lower_bound(map->view_ids, map->view_ids + map->n_views, h->views[k].view_id); return (int)(it - map->view_ids); };
             ProductsPart part;
             part.active = true; part.rank = h->rank; part.world = h->world;
+            // (a turn of a node object whose ranks share a device: the share was computed alone -- world 1 -- and joins the collective finish as the rank it stands for)
+            if (c->turn_share && h->world == 1 && c->opt.part_vworld > 0) { part.world = c->opt.part_vworld; part.rank = std::max(0, std::min(c->opt.part_vrank, part.world - 1)); }
             part.own_dv0 = dense_of(h->part_own0); part.own_dv1 = dense_of(h->part_own1);
             part.row_dv0 = dense_of(std::max(0, h->part_own0 - h->part_reach)); part.row_dv1 = dense_of(std::min(nv, h->part_own1 + h->part_reach));
             part.held_dv0 = dense_of(std::max(0, h->part_own0 - 2 * h->part_reach)); part.held_dv1 = dense_of(std::min(nv, h->part_own1 + 2 * h->part_reach));

@@ -168,6 +168,13 @@ struct l3d_ctx {
     int mmax_seen = 0;
     l3d::DevBuf vw_bstart, vw_segstate;             // split verification (k_vw_walk): bucket starts of the built images | per-segment state + unit table
     size_t part_arena_seen = 0;                     // records a partitioned segment-sharded run kept on this rank (sizes the next pass's arena)
+    // a rank of a node object whose ranks take turns on one device (l3d_turns.hpp; line3d_host.cpp, node mode 2)
+    bool turn_share = false;                        // a world-1 share (options part_vrank / part_vworld) files its products as that rank of that world: the collective finish follows
+    bool fill_collective_only = false;              // sharded fill: past its last collective this rank forms no numbering and no edge list (the result is read from another rank)
+    void (*fill_gate)(void*, int) = nullptr;        // sharded fill: called with 1 before and 0 after this rank's candidate enumeration (the device's token)
+    void* fill_gate_user = nullptr;
+    bool records_released = false;                  // l3d_chain_release_records: the products' kept records are gone (l3d_chain_kept_list refuses)
+    std::vector<int> shard_view_kept;               // the last sharded run: every chain view's kept count from its slot headers, whatever this rank retired
     size_t test_cand_cap = 0, test_arena_cap = 0;   // tests: initial capacities of the resident chain (0 = estimate)
     int chain_seen_views = 0; double chain_seen_pairs = 0; size_t chain_seen_cand_cap = 0, chain_seen_arena_cap = 0; double chain_seen_kept = 0;   // what the last chain over this scene needed (and kept)
     unsigned long long* pair_dbg = nullptr;   // L3D_PAIR_STATS=1: device counters of k_pair_mask's levels (printed at destroy)

@@ -660,6 +660,7 @@ int l3d::build_products(l3d_ctx* c, const l3d_chain_view* views, int n_views, co
 {
     Products& P = c->products;
     P.valid = false; P.hyp_valid = false;
+    c->records_released = false;
     hipStream_t st = c->stream;
     const int nv = map->n_views;
     if (nv <= 0) return fail(c, L3D_ERR_INVALID, "products: empty dense map");
@@ -1274,6 +1275,7 @@ int l3d_products_hypotheses(l3d_ctx* c, const l3d_view_geometry* geometry, int n
     if (!geometry || !view_hyp_begin || !hyp_dense_out || !n_hyp_out) return fail(c, L3D_ERR_INVALID, "l3d_products_hypotheses: bad argument");
     *hyp_dense_out = nullptr; *n_hyp_out = 0;
     if (!P.valid) return fail(c, L3D_ERR_INVALID, "l3d_products_hypotheses: no resident products (run l3d_match_chain_resident first)");
+    if (c->records_released) return fail(c, L3D_ERR_INVALID, "l3d_products_hypotheses: the kept records of this chain were released (l3d_chain_release_records)");
     if (n_views != P.n_views_all) return fail(c, L3D_ERR_INVALID, "l3d_products_hypotheses: geometry does not match the dense map");
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
@@ -1350,6 +1352,7 @@ int l3d_chain_kept_list(l3d_ctx* c, int index, l3d_match** out, int* n)
     if (!out || !n) return fail(c, L3D_ERR_INVALID, "bad argument");
     *out = nullptr; *n = 0;
     if (!P.valid || index < 0 || index >= P.n_chain) return fail(c, L3D_ERR_INVALID, "l3d_chain_kept_list: no such view in the resident products");
+    if (c->records_released) return fail(c, L3D_ERR_INVALID, "l3d_chain_kept_list: the kept records of this chain were released (l3d_chain_release_records)");
     HIPCHK(c, hipSetDevice(c->device));
     auto fetch = [&](int k, std::vector<l3d_match>& v) -> int {
         const ChainResult& r = P.res[(size_t)k];
@@ -1387,6 +1390,7 @@ int l3d_chain_products_get(l3d_ctx* c, int64_t* pot_start, int32_t* pot_tgt, l3d
     if (!c) return L3D_ERR_INVALID;
     Products& P = c->products;
     if (!P.valid) return fail(c, L3D_ERR_INVALID, "no resident products");
+    if (best_match && c->records_released) return fail(c, L3D_ERR_INVALID, "l3d_chain_products_get: the kept records of this chain were released (l3d_chain_release_records)");
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     if (pot_start) HIPCHK(c, hipMemcpyAsync(pot_start, P.pot_start.p, ((size_t)P.n_dense + 1) * 8, hipMemcpyDeviceToHost, st));

@@ -3,6 +3,7 @@
 // line3d_host_chain.cpp (resident matchViews) and line3d_host_finish.cpp (selection, affinity, diffusion, clustering, fit).
 #include "line3d_host_internal.hpp"
 #include "l3d_node.hpp"
+#include "l3d_turns.hpp"
 
 #include <hip/hip_runtime_api.h>
 
@@ -14,7 +15,110 @@ struct NodeRanks {
     l3d_node_comm* comm = nullptr;          // their all-gather (l3d_node.hip), every stream bound
     int mode = 0;                           // l3d_line3d_set_node_mode
     int threads_per_rank = 1;               // the host-thread budget split among the ranks
+    std::vector<int64_t> turn_records;      // mode 2: the records every rank retired in its turn (l3d_line3d_node_turn_records)
 };
+
+// Mode 2 of a node object: the ranks of one device take their turns in rank order, one token per device (host condition: no device-side flag, no
+// spinning).  Turn 0 runs before every other turn -- the sizes of the later ones come from it.  The same token then guards the candidate
+// enumeration of the collective fill.  A rank that fails gives the token back and wakes everybody: nobody waits for a turn that will not come.
+struct TurnGate {
+    std::mutex mu;
+    std::condition_variable cv;
+    std::vector<int> devices;
+    std::vector<char> done;                 // per rank: its turn is over
+    std::vector<int> holder;                // per rank's device (indexed by rank, the first rank of the device keeps the word): the rank holding the token, -1: free
+    bool aborted = false;
+    int failed_rank = -1, failed_rc = L3D_OK;
+    std::string failed_msg;
+    // what the turns leave for the node layer
+    std::vector<std::vector<unsigned char>> keep;      // per rank: the views it holds (l3d_partition_keep_views of its block)
+    std::vector<std::vector<uint64_t>> hash;           // per rank: k_block_digest of every view it held
+    std::vector<std::vector<int32_t>> n_kept;
+    std::vector<size_t> arena_records;                 // per rank: its exact arena, known after turn 0
+    int slot_records = 0; size_t cand_cap = 0;         // what turn 0 ended with
+
+    explicit TurnGate(const std::vector<int>& dev) : devices(dev), done(dev.size(), 0), holder(dev.size(), -1), keep(dev.size()), hash(dev.size()), n_kept(dev.size()), arena_records(dev.size(), 0) {}
+    int word(int r) const { for (int q = 0; q < r; ++q) if (devices[(size_t)q] == devices[(size_t)r]) return q; return r; }
+    bool all_done() const { for (char d : done) if (!d) return false; return true; }
+    // false: a rank failed, no turn starts any more
+    bool begin_turn(int r)
+    {
+        std::unique_lock<std::mutex> lk(mu);
+        const int w = word(r);
+        cv.wait(lk, [&] {
+            if (aborted) return true;
+            if (r > 0 && !done[0]) return false;
+            for (int q = 0; q < r; ++q) if (devices[(size_t)q] == devices[(size_t)r] && !done[(size_t)q]) return false;
+            return holder[(size_t)w] < 0;
+        });
+        if (aborted) return false;
+        holder[(size_t)w] = r;
+        return true;
+    }
+    void fail_locked(int r, int rc, const std::string& msg)
+    {
+        if (failed_rank < 0) { failed_rank = r; failed_rc = rc; failed_msg = msg; }
+        aborted = true;
+    }
+    // the views two ranks both held must have come out of their chains alike: the digests of the last rank to finish close the turns
+    void compare_locked(const std::vector<uint32_t>& view_ids)
+    {
+        const int W = (int)devices.size();
+        for (int a = 0; a < W; ++a)
+            for (int b = a + 1; b < W; ++b) {
+                const size_t n = std::min(keep[(size_t)a].size(), keep[(size_t)b].size());
+                for (size_t k = 0; k < n; ++k) {
+                    if (!keep[(size_t)a][k] || !keep[(size_t)b][k]) continue;
+                    if (hash[(size_t)a][k] == hash[(size_t)b][k] && n_kept[(size_t)a][k] == n_kept[(size_t)b][k]) continue;
+                    fail_locked(a, L3D_ERR_INVALID, "the kept list of view " + std::to_string(k < view_ids.size() ? view_ids[k] : (uint32_t)k) + " (chain index " + std::to_string(k) + ") differs between the turns of rank " +
+                                                     std::to_string(a) + " (" + std::to_string(n_kept[(size_t)a][k]) + " records) and rank " + std::to_string(b) + " (" + std::to_string(n_kept[(size_t)b][k]) + " records)");
+                    return;
+                }
+            }
+    }
+    void end_turn(int r, int rc, const std::string& msg, const std::vector<uint32_t>& view_ids)
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        const int w = word(r);
+        if (holder[(size_t)w] == r) holder[(size_t)w] = -1;
+        done[(size_t)r] = 1;
+        if (rc) fail_locked(r, rc, msg);
+        else if (!aborted && all_done()) compare_locked(view_ids);
+        cv.notify_all();
+    }
+    // every turn is over (true) or a rank failed (false)
+    bool wait_all()
+    {
+        std::unique_lock<std::mutex> lk(mu);
+        cv.wait(lk, [&] { return aborted || all_done(); });
+        return !aborted;
+    }
+    void abort()
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        aborted = true;
+        cv.notify_all();
+    }
+    // the token of rank r's device around its candidate enumeration (l3d_affinity_fill_sharded); after a failure nobody is kept waiting
+    void fill_token(int r, bool acquire)
+    {
+        std::unique_lock<std::mutex> lk(mu);
+        const int w = word(r);
+        if (acquire) {
+            cv.wait(lk, [&] { return aborted || holder[(size_t)w] < 0; });
+            if (holder[(size_t)w] < 0) holder[(size_t)w] = r;
+        } else {
+            if (holder[(size_t)w] == r) holder[(size_t)w] = -1;
+            cv.notify_all();
+        }
+    }
+};
+struct FillGateUser { TurnGate* gate; int rank; };
+static void fill_gate_fn(void* user, int acquire)
+{
+    FillGateUser* u = static_cast<FillGateUser*>(user);
+    u->gate->fill_token(u->rank, acquire != 0);
+}
 }  // namespace l3dh
 
 static std::string rank_prefix(const L* h, int r)
@@ -65,6 +169,145 @@ static int node_run(L* h, const std::function<int(int)>& fn)
     if (r < 0 || rcs[(size_t)r] == L3D_OK) r = first.load();
     return r < 0 ? L3D_OK : h->fail(rcs[(size_t)r], rank_prefix(h, r) + N.ranks[(size_t)r]->err);
 }
+// the per-view summary of the one chain: a rank's own lists only cover the views it holds -- view k from the rank whose block holds it
+// (every mode cuts the chain's views into blocks n * r / W)
+static void node_merge_summary(L* h)
+{
+    NodeRanks& N = *h->node;
+    const int W = (int)N.ranks.size();
+    const size_t n = rank0(h)->chain_summary.size();
+    h->chain_summary.assign(n, l3d_chain_summary());
+    for (int r = 0; r < W; ++r) {
+        const std::vector<l3d_chain_summary>& own = N.ranks[(size_t)r]->chain_summary;
+        const size_t b0 = (size_t)(((long long)n * r) / W), b1 = (size_t)(((long long)n * (r + 1)) / W);
+        for (size_t k = b0; k < b1 && k < own.size(); ++k) h->chain_summary[k] = own[k];
+    }
+}
+
+// one rank's turn (mode 2): its share of the W-rank job computed ALONE on its device -- the whole chain at world 1 with the keep set of block r,
+// the rows of its share of the products, the hypotheses (the last reader of the kept records), the digests of what it held; then the records go
+static int node_turn(L* h, TurnGate& G, int r, int slot_records_1)
+{
+    NodeRanks& N = *h->node;
+    const int W = (int)N.ranks.size();
+    L* R = N.ranks[(size_t)r];
+    int rc = l3d_set_option(R->ctx, "L3D_PART_VRANK", r);
+    if (!rc) rc = l3d_set_option(R->ctx, "L3D_PART_VWORLD", W);
+    if (rc) return R->fail(rc, l3d_last_error(R->ctx));
+    l3d::ctx_turn_share(R->ctx, 1);
+    R->shard_arena_cap_hint = 0;
+    if (r > 0) {        // (only turn 0 may pay a capacity re-run: the later turns start with what it ended with and with their exact arena)
+        R->shard_world_seen = 1; R->shard_slot_records_seen = G.slot_records; R->shard_cand_cap_seen = G.cand_cap;
+        R->shard_arena_cap_hint = G.arena_records[(size_t)r];
+    }
+    rc = l3d_line3d_shard_run(R, 0, 1, slot_records_1, l3d_exchange_local, nullptr, 3, nullptr, nullptr);
+    R->shard_arena_cap_hint = 0;
+    if (rc) return rc;
+    ChainPlan* P = get_plan(R);
+    if (!P) return R->fail(L3D_ERR_INVALID, "turn: no static schedule");
+    const int n = (int)P->n;
+    if (r == 0) {
+        // every view's slot header went through turn 0's chain: every later turn's arena is known exactly
+        const std::vector<int>& kept = l3d::ctx_shard_view_kept(R->ctx);
+        if ((int)kept.size() != n) return R->fail(L3D_ERR_INVALID, "turn 0: the chain left no kept count per view");
+        std::lock_guard<std::mutex> lk(G.mu);
+        for (int q = 0; q < W; ++q) {
+            G.keep[(size_t)q].assign((size_t)n, 0);
+            if (const int rk = l3d_partition_keep_views(P->cv.data(), n, (int)(((long long)n * q) / W), (int)(((long long)n * (q + 1)) / W), G.keep[(size_t)q].data(), nullptr))
+                return R->fail(rk, "turn 0: l3d_partition_keep_views refused the schedule");
+            size_t recs = 0;
+            for (int k = 0; k < n; ++k) if (G.keep[(size_t)q][(size_t)k]) recs += (size_t)kept[(size_t)k];
+            G.arena_records[(size_t)q] = recs + 4096;
+        }
+        G.slot_records = std::max(slot_records_1, R->shard_slot_records_seen);
+        G.cand_cap = R->shard_cand_cap_seen;
+    }
+    rc = greedy_selection_resident(R);                      // (l3d_products_hypotheses: nothing behind it reads the kept arena)
+    if (rc) return rc;
+    R->hyps_done = true;
+    std::vector<uint64_t> hash((size_t)n, 0);
+    std::vector<int32_t> nk((size_t)n, 0);
+    rc = l3d_chain_records_digest(R->ctx, hash.data(), nk.data(), n);
+    if (!rc) rc = l3d_chain_release_records(R->ctx);
+    if (rc) return R->fail(rc, std::string("turn: ") + l3d_last_error(R->ctx));
+    // what the turn retired: the records its arena really holds (the digests' lengths are the products' result records, which add up to the arena's fill:
+    // l3d_shard_chain_products checks that) -- of ANY view, so a chain that kept more than its keep set shows -- plus, as the chain's summary counts them,
+    // the lists of the early-return views it held (rebuilt from their sources' records, cudawrapper.cu:877-878: no room of their own in the arena)
+    int64_t recs = 0;
+    std::lock_guard<std::mutex> lk(G.mu);
+    for (int k = 0; k < n; ++k) {
+        recs += nk[(size_t)k];
+        if (G.keep[(size_t)r][(size_t)k] && P->n_tbm[(size_t)k] == 0 && k < (int)R->chain_summary.size()) recs += R->chain_summary[(size_t)k].n_kept;
+    }
+    G.hash[(size_t)r] = std::move(hash); G.n_kept[(size_t)r] = std::move(nk);
+    N.turn_records[(size_t)r] = recs;
+    return L3D_OK;
+}
+
+// compute3Dmodel with the ranks of a device taking turns (l3d_line3d_set_node_mode 2): a scene whose kept records do not fit one device's memory at once.
+// Every turn computes the WHOLE chain and keeps one block's share of it, so matchViews costs about W single passes; the collective finish is the
+// one of the other modes, every share standing for its rank.
+static int node_compute_turns(L* h, int perform_diffusion)
+{
+    NodeRanks& N = *h->node;
+    const int W = (int)N.ranks.size();
+    if (rank0(h)->views.size() < 4) return h->fail(L3D_ERR_INVALID, "not enough images! can't compute 3D model...");   // line3D.cc:347-351
+    // (a job sized by memory: no rank reserves the finishing stages' arenas from the size of the scene)
+    std::vector<int> hint((size_t)W, 1);
+    for (int r = 0; r < W; ++r) {
+        (void)l3d_get_option(N.ranks[(size_t)r]->ctx, "L3D_RESERVE_HINT", &hint[(size_t)r]);
+        if (const int rc = l3d_set_option(N.ranks[(size_t)r]->ctx, "L3D_RESERVE_HINT", 0)) return h->fail(rc, l3d_last_error(N.ranks[(size_t)r]->ctx));
+    }
+    int rc = node_run(h, [&](int r) { return prepare(N.ranks[(size_t)r]); });
+    for (int r = 0; r < W; ++r) (void)l3d_set_option(N.ranks[(size_t)r]->ctx, "L3D_RESERVE_HINT", hint[(size_t)r]);      // (read by prepare alone: the other modes keep theirs)
+    if (rc) return rc;
+    int s_max = 0;
+    for (const View* v : rank0(h)->vlist) s_max = std::max(s_max, v->S());
+    // kept records of one view's slot at world 1 (node_compute's first guess with one rank): grown by turn 0's capacity verdicts, then handed on
+    const int slot_records_1 = (int)std::min<long long>(INT32_MAX / 2, std::max<long long>(1024, 10LL * s_max * rank0(h)->matching_neighbors + 1024));
+    l3d::node_comm_rearm(N.comm);
+    h->chain_summary.clear();
+    N.turn_records.assign((size_t)W, 0);
+    TurnGate G(N.devices);
+    std::vector<FillGateUser> gate_user((size_t)W);
+    std::vector<uint32_t> order_ids;
+    rc = node_run(h, [&](int r) {
+        L* R = N.ranks[(size_t)r];
+        int rc2 = L3D_OK;
+        if (!G.begin_turn(r)) rc2 = R->fail(L3D_ERR_INVALID, "another rank failed in its turn");
+        else {
+            rc2 = node_turn(h, G, r, slot_records_1);
+            if (r == 0 && rc2 == L3D_OK) order_ids = R->order;          // (read by the last rank to finish, under the gate's lock)
+            G.end_turn(r, rc2, R->err, order_ids);
+        }
+        // no rank enters the first collective before every turn is over: a rank waiting in an exchange gives up after its time limit, a turn may take longer
+        if (rc2 == L3D_OK && !G.wait_all()) rc2 = R->fail(L3D_ERR_INVALID, "another rank failed in its turn");
+        if (rc2 == L3D_OK) {
+            gate_user[(size_t)r] = { &G, r };
+            l3d::ctx_fill_gate(R->ctx, fill_gate_fn, &gate_user[(size_t)r]);
+            l3d::ctx_fill_collective_only(R->ctx, r != 0);
+            rc2 = l3d_line3d_finish_sharded(R, perform_diffusion, l3d_exchange_node, N.comm);
+            if (rc2) G.abort();
+        }
+        // the context is an ordinary rank's again; what a rank other than 0 still holds is nobody's result
+        l3d::ctx_fill_gate(R->ctx, nullptr, nullptr);
+        l3d::ctx_fill_collective_only(R->ctx, 0);
+        l3d::ctx_turn_share(R->ctx, 0);
+        (void)l3d_set_option(R->ctx, "L3D_PART_VWORLD", 0);
+        (void)l3d_set_option(R->ctx, "L3D_PART_VRANK", 0);
+        R->hyps_done = false;
+        if (r != 0) l3d::ctx_release_share(R->ctx);
+        return rc2;
+    });
+    if (rc) {
+        // (the rank that failed in its turn, or the pair of ranks whose digests differ -- not a rank that merely heard of it)
+        if (G.failed_rank >= 0) return h->fail(G.failed_rc, rank_prefix(h, G.failed_rank) + G.failed_msg);
+        return rc;
+    }
+    node_merge_summary(h);
+    return L3D_OK;
+}
+
 // Line3D::compute3Dmodel over the ranks: prepare on all of them; then matchViews partitioned (set_node_mode) and the collective finish, every
 // rank through l3d_exchange_node -- every rank ends with the whole result
 static int node_compute(L* h, int perform_diffusion)
@@ -72,6 +315,8 @@ static int node_compute(L* h, int perform_diffusion)
     NodeRanks& N = *h->node;
     const int W = (int)N.ranks.size();
     if (rank0(h)->views.size() < 4) return h->fail(L3D_ERR_INVALID, "not enough images! can't compute 3D model...");   // line3D.cc:347-351
+    if (N.mode == 2) return node_compute_turns(h, perform_diffusion);
+    N.turn_records.clear();
     int rc = node_run(h, [&](int r) { return prepare(N.ranks[(size_t)r]); });
     if (rc) return rc;
     int s_max = 0;
@@ -97,15 +342,7 @@ static int node_compute(L* h, int perform_diffusion)
         return rc2;
     });
     if (rc) return rc;
-    // the per-view summary of the one chain: a rank's own lists only cover the views it holds -- view k from the rank whose block holds it
-    // (both modes cut the chain's views into blocks n * r / W)
-    const size_t n = rank0(h)->chain_summary.size();
-    h->chain_summary.assign(n, l3d_chain_summary());
-    for (int r = 0; r < W; ++r) {
-        const std::vector<l3d_chain_summary>& own = N.ranks[(size_t)r]->chain_summary;
-        const size_t b0 = (size_t)(((long long)n * r) / W), b1 = (size_t)(((long long)n * (r + 1)) / W);
-        for (size_t k = b0; k < b1 && k < own.size(); ++k) h->chain_summary[k] = own[k];
-    }
+    node_merge_summary(h);
     return L3D_OK;
 }
 static void node_destroy(L* h)
@@ -180,8 +417,18 @@ int l3d_line3d_num_ranks(const l3d_line3d* h) { return !h ? 0 : h->node ? (int)h
 int l3d_line3d_set_node_mode(l3d_line3d* h, int mode)
 {
     if (!h) return L3D_ERR_INVALID;
-    if (mode != 0 && mode != 1) return h->fail(L3D_ERR_INVALID, "set_node_mode: 0 (segments of every view) or 1 (blocks of views)");
+    if (mode < 0 || mode > 2) return h->fail(L3D_ERR_INVALID, "set_node_mode: 0 (segments of every view), 1 (blocks of views) or 2 (the ranks of a device take turns)");
     if (h->node) h->node->mode = mode;
+    return L3D_OK;
+}
+
+int l3d_line3d_node_turn_records(const l3d_line3d* h, int rank, int64_t* records)
+{
+    if (!h || !records) return L3D_ERR_INVALID;
+    *records = 0;
+    if (!h->node || rank < 0 || rank >= (int)h->node->ranks.size()) return const_cast<L*>(h)->fail(L3D_ERR_INVALID, "node_turn_records: no such rank of a node object");
+    if ((int)h->node->turn_records.size() != (int)h->node->ranks.size()) return const_cast<L*>(h)->fail(L3D_ERR_INVALID, "node_turn_records: the last compute3Dmodel did not run in turns (l3d_line3d_set_node_mode 2)");
+    *records = h->node->turn_records[(size_t)rank];
     return L3D_OK;
 }
 
@@ -406,7 +653,8 @@ int l3d_line3d_finish(l3d_line3d* h, int perform_diffusion)
     if (!h || !h->prepared) return h ? h->fail(L3D_ERR_INVALID, "prepare first") : L3D_ERR_INVALID;
     const double t0 = now_s();
     if (h->partitioned && !h->part_exchange) return h->fail(L3D_ERR_INVALID, "finish: matchViews' products are partitioned over the ranks (l3d_line3d_finish_sharded)");
-    if (h->resident_products) { const int rg = greedy_selection_resident(h); if (rg) return rg; }
+    if (h->hyps_done) h->hyps_done = false;                // (a turn of a node object selected before it released its records)
+    else if (h->resident_products) { const int rg = greedy_selection_resident(h); if (rg) return rg; }
     else greedy_selection(h);                              // optimizeLocalMatches, :888-896
     if (hopt(h).timing) fprintf(stderr, "[l3d finish] %-28s %8.2f ms\n", "greedy selection", (now_s() - t0) * 1e3);
     const int rc = cluster_segments_2D(h, perform_diffusion != 0);
@@ -556,7 +804,7 @@ int l3d_line3d_shard_run(l3d_line3d* h, int rank, int world, int slot_records, l
     if (h->node) return node_refuse(h, "shard_run");
     // A capacity failure is a verdict all ranks share (l3d_shard_chain_info): every rank reopens with the same, larger
     // capacities and runs again -- the bookkeeping of the failed attempt is dropped by the reopen (match_begin).
-    size_t cand_cap_next = 0, arena_cap_next = 0;
+    size_t cand_cap_next = 0, arena_cap_next = h->shard_arena_cap_hint;
     int rc = L3D_OK;
     // sizes a capacity verdict of an earlier pass of this job taught us (identical on every rank: the verdict is shared)
     if (h->shard_world_seen == world) { slot_records = std::max(slot_records, h->shard_slot_records_seen); cand_cap_next = h->shard_cand_cap_seen; }
@@ -610,7 +858,15 @@ int l3d_line3d_shard_run(l3d_line3d* h, int rank, int world, int slot_records, l
         h->fail(rc, msg);
         if (hopt(h).timing) fprintf(stderr, "[l3d shard_run] attempt %d failed (%d): %s\n", attempt, rc, msg.c_str());
         if (rc != L3D_ERR_NOMEM || (bits & 4 && !(bits & 11)) || !(bits & 11)) return rc;    // not a capacity verdict: nothing a retry would change
-        if (bits & 8) { const long long need = P_shard_arena; arena_cap_next = (size_t)need + (size_t)need / 4 + 65536; }
+        if (bits & 8) {
+            const long long need = P_shard_arena;
+            // (tests, option regrow_free_mb: the room the compact arena may take -- a run that needs more has its answer, no re-run)
+            const long long room = hopt(h).regrow_free_mb > 0 ? (long long)(((size_t)hopt(h).regrow_free_mb << 20) / (sizeof(l3d_match) + 4)) : 0;
+            if (room > 0 && need > room)
+                return h->fail(L3D_ERR_NOMEM, "shard_run: the compact arena of this rank needs " + std::to_string(need) + " records, there is room for " + std::to_string(room) + " (" +
+                                              std::to_string(hopt(h).regrow_free_mb) + " MB at " + std::to_string(sizeof(l3d_match) + 4) + " B per record)");
+            arena_cap_next = (size_t)need + (size_t)need / 4 + 65536;
+        }
         if ((bits & 2) && exchange == l3d_exchange_replay) return rc;                        // recorded blocks have the recorded slot size: the caller records again with more room
         if (bits & 1) cand_cap_next = h->shard_cand_cap_seen = std::max(cand_cap * 2, (size_t)max_cand + (size_t)max_cand / 4 + 65536);
         if (bits & 2) slot_records = h->shard_slot_records_seen = std::max(slot_records * 2, max_kept + max_kept / 4 + 1024);

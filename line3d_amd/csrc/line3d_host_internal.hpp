@@ -216,6 +216,8 @@ struct l3d_line3d {
     int64_t resident_n_pot = 0;
     int shard_world_seen = 0, shard_slot_records_seen = 0;     // sharded native run: slot / candidate sizes a capacity verdict made necessary
     size_t shard_cand_cap_seen = 0;
+    size_t shard_arena_cap_hint = 0;                           // ... and the compact arena's records when the caller knows them (a later turn of a node object, mode 2; 0: the run's own guess)
+    bool hyps_done = false;                                    // greedy selection already ran on the resident products (a turn of a node object released the records behind it): finish goes on from there
 
     // final hypotheses
     std::vector<Hyp> hyps;                                     // best_match_ in key order

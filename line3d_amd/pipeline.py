@@ -67,8 +67,15 @@ class Line3D:
 
     def set_node_mode(self, mode: int):
         """how compute3Dmodel shards matchViews over the ranks of a node object: 0 = segments of every view (default), 1 = blocks of views
-        (falls back to 0 where its verdict says the speculation cannot hold)"""
+        (falls back to 0 where its verdict says the speculation cannot hold), 2 = the ranks of a device take turns on it (a scene whose kept records do
+        not fit the device at once; every turn computes the whole chain: matchViews costs about len(devices) single passes)"""
         self._chk(self.lib.l3d_line3d_set_node_mode(self.h, C.c_int(int(mode))))
+
+    def node_turn_records(self, rank: int) -> int:
+        """after compute3Dmodel in node mode 2: the kept records rank `rank` retired in its turn (l3d_line3d_node_turn_records)"""
+        n = C.c_int64(0)
+        self._chk(self.lib.l3d_line3d_node_turn_records(self.h, C.c_int(int(rank)), C.byref(n)))
+        return int(n.value)
 
     def context(self) -> capi.Context:
         """The pipeline's l3d_ctx as a (non-owning) Context, for profiling (refused on a node object: one context per rank)."""

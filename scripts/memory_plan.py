@@ -9,6 +9,11 @@
 --mode segpart: l3d_shard_chain_partition + l3d_shard_chain_run + l3d_affinity_fill_sharded -- the segments of every view sharded (exact without
   speculation), every rank RETIRES only its block of views + 2 x reach either side: the ring of gathered slots, then the partition's share of everything.
 
+--mode turns: a node object whose W ranks take turns on ONE device (l3d_line3d_set_node_mode 2): per turn the scene, the kept arena of the turn's keep set and
+  the chain's scratch (the segpart plan at chain world 1 -- a turn computes the WHOLE chain, matchViews costs about W single passes); the arena and the
+  scratch go back before the next turn (l3d_chain_release_records); across the turns stay W shares of rows and hypotheses, every rank's resident copy of
+  the scene, and -- under the device's token -- one rank's block of fill candidates at a time.
+
 `kept` = kept matches / candidates verified (config 2 measures 2.5 %; the synthetic box scene at 4000 x 24 keeps 30 % at 40 views and 48 % at 256:
 profiles/r5_256x4000x24_one_gpu_finish.json).  Stage-1 candidates per view: rho * S^2 * n_tbm, rho = 0.065 (SURVEY 8, measured on config 2);
 candidates verified = those + the reverse matches (about half of the neighbours' kept lists): cand = raw / (1 - kept / 2).
@@ -137,6 +142,27 @@ def plan_segpart(V, S, N, W, kept_ratio, chain_world=0):
     return rows, idx, dict(chain_views=V, held_views=held_views, kept_view=kept_view, cand_view=cand_view)
 
 
+def plan_turns(V, S, N, W, kept_ratio):
+    """the rows of one turn (segpart at chain world 1) re-phased for a device its W ranks share: "turn" = live during the turn's chain and products only
+    (released by l3d_chain_release_records), "others" = what the W - 1 other ranks keep on the device across the turns"""
+    rows, idx, info = plan_segpart(V, S, N, W, kept_ratio, 1)
+    out = []
+    for phase, name, b, where in rows:
+        released = name.startswith("kept arena") or name.startswith("side words") or name.startswith("camera tables")
+        out.append(("turn" if phase == "all" and released else phase, name, b, where))
+    share = sum(r[2] for r in rows if r[0] == "after")
+    scene = sum(r[2] for r in rows if r[0] == "all" and r[1].startswith("segments"))
+    out.append(("others", "the other %d ranks' shares of rows and hypotheses (what a turn leaves behind)" % (W - 1), (W - 1) * share, "line3d_host.cpp:node_turn (l3d_chain_release_records keeps the products)"))
+    out.append(("copies", "the other %d ranks' resident copies of the scene (every rank object prepares the scene on its device)" % (W - 1), (W - 1) * scene, "line3d_host.cpp:node_compute_turns -> prepare"))
+    info = dict(info, share_rows_bytes=share, scene_bytes=scene)
+    return out, idx, info
+
+
+def turns_phases(rows):
+    g = lambda *ph: sum(r[2] for r in rows if r[0] in ph)
+    return dict(chain=g("all", "turn", "chain", "others"), products=g("all", "turn", "products", "after", "others"), fill=g("all", "after", "fill", "others"), finish=g("all", "after", "finish", "others"))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--views", type=int, default=2048)
@@ -144,21 +170,30 @@ def main():
     ap.add_argument("--neighbors", type=int, default=24)
     ap.add_argument("--world", type=int, default=8)
     ap.add_argument("--kept", type=float, nargs="+", default=[0.025, 0.25, 0.48])
-    ap.add_argument("--mode", default="partition", choices=["partition", "segments", "segpart"])
+    ap.add_argument("--mode", default="partition", choices=["partition", "segments", "segpart", "turns"])
     ap.add_argument("--chain-world", type=int, default=0, help="segpart only: the world size the CHAIN runs at (0 = --world); 1 = one rank's share exercised on one GPU")
     ap.add_argument("--rho", type=float, default=0.065, help="stage-1 candidates per segment pair (0.065: config 2; the 2048-view scene measures 0.11)")
     ap.add_argument("--json", action="store_true", help="the plan of the FIRST --kept value as one JSON object (scripts/run_rank_share.py compares it with a measured peak)")
     a = ap.parse_args()
     RHO[0] = a.rho
-    fn = dict(partition=plan_partition, segments=plan_segments, segpart=plan_segpart)[a.mode]
+    fn = dict(partition=plan_partition, segments=plan_segments, segpart=plan_segpart, turns=plan_turns)[a.mode]
     plans = [fn(a.views, a.segments, a.neighbors, a.world, k, a.chain_world) if a.mode == "segpart" else fn(a.views, a.segments, a.neighbors, a.world, k) for k in a.kept]
     if a.json:
         import json
         p = plans[0]
         g = lambda *ph: sum(r[2] for r in p[0] if r[0] in ph)
         phases = dict(chain=g("all", "chain"), products=g("all", "products", "after"), fill=g("all", "after", "fill"), finish=g("all", "after", "finish"))
+        extra = {}
+        if a.mode == "turns":
+            # turn_peak: the last turn of the device with the W - 1 other shares beside it; peak: + the other ranks' copies of the scene
+            phases = turns_phases(p[0])
+            copies = g("copies")
+            extra = dict(turn_peak_gb=round(max(phases.values()) / GB, 2), share_rows_gb=round(p[2]["share_rows_bytes"] / GB, 3), scene_copies_gb=round(copies / GB, 3), world=a.world,
+                         per_turn_gb=dict(scene=round(p[2]["scene_bytes"] / GB, 3), arena_of_the_keep_set=round(g("turn") / GB, 3), chain_scratch=round(g("chain") / GB, 3)),
+                         across_turns_gb=dict(shares_of_rows_and_hypotheses=round(a.world * p[2]["share_rows_bytes"] / GB, 3), one_fill_block=round(g("fill") / GB, 3)))
+            phases = {k: v + copies for k, v in phases.items()}
         print(json.dumps(dict(mode=a.mode, kept=a.kept[0], peak_gb=round(max(phases.values()) / GB, 2), phases_gb={k: round(v / GB, 2) for k, v in phases.items()},
-                              rows=[dict(phase=r[0], what=r[1], gb=round(r[2] / GB, 3)) for r in p[0]], fields={k: float(v) for k, v in p[1].items()})))
+                              rows=[dict(phase=r[0], what=r[1], gb=round(r[2] / GB, 3)) for r in p[0]], fields={k: float(v) for k, v in p[1].items()}, **extra)))
         return
     print("| per rank (%s), %d views x %d segments x %d neighbours, %d ranks | " % (a.mode, a.views, a.segments, a.neighbors, a.world) + " | ".join("kept %.1f %%" % (100 * k) for k in a.kept) + " | where |")
     print("|---|" + "---|" * (len(a.kept) + 1))
@@ -167,6 +202,8 @@ def main():
     # phases: what is live together.  "all" always; "chain" during matchViews only; "products" while the table is built; "after" from then on; "fill", "finish" later
     def peak(p):
         g = lambda *ph: sum(r[2] for r in p[0] if r[0] in ph)
+        if a.mode == "turns":
+            return max(turns_phases(p[0]).values()) + g("copies")
         return max(g("all", "chain"), g("all", "products", "after"), g("all", "after", "fill"), g("all", "after", "finish"))
     print("| **peak over the phases** (chain / products / fill / finish) | " + " | ".join("**%.1f GB**" % (peak(p) / GB) for p in plans) + " | of 288 GB per rank |")
     print()
