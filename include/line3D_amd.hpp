@@ -85,6 +85,9 @@ public:
     // views, 2 = the ranks of a device take turns on it -- a scene whose kept records do not fit the device at once, at the cost of about one
     // single-device matchViews per rank.  Without effect on a one-device object.  false: no such mode (message printed)
     bool setNodeMode(const int mode) { const int rc = l3d_line3d_set_node_mode(h_, mode); report(rc); return rc == L3D_OK; }
+    // node mode 2 with a warm hand-over between the turns (l3d_line3d_set_turn_handover): a turn computes its own piece of the chain from the tail
+    // its predecessor left instead of the whole chain.  Without effect in the other modes.  false: a one-device object (message printed)
+    bool setTurnHandover(const bool on) { const int rc = l3d_line3d_set_turn_handover(h_, on ? 1 : 0); report(rc); return rc == L3D_OK; }
 
     // line3D.h:69-73; errors are printed and the call returns, like the reference (line3D.cc:101-127).  `image` is replaced by its size
     // and the segments the detector would have produced; maxImgWidth / loadAndStoreSegments keep their meaning: the segment cache

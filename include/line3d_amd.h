@@ -387,6 +387,14 @@ int l3d_shard_chain_partition(l3d_shard_chain* chain, int own_begin, int own_end
 /* the keep set of l3d_shard_chain_partition as a function of the schedule alone (host logic, no context): keep[k] = 1 for the chain views a rank that
  * owns [own_begin, own_end) retires; *reach (may be NULL) = the largest chain distance between a view and one of its neighbours */
 int l3d_partition_keep_views(const l3d_chain_view* views, int n_views, int own_begin, int own_end, unsigned char* keep, int* reach);
+/* the schedule of a node object's turns that hand the chain over (l3d_line3d_set_turn_handover) as a function of the static schedule alone (host
+ * logic, no context).  out[8 * r + 0 .. 7] of turn r of `world`, in chain positions: pre0, run0 (the views [pre0, run0) are taken over from turn
+ * r - 1), run1 (the turn's chain computes [run0, run1) and holds the one chain's records of [pre0, run1)), row0, row1 (the rows of the table its share
+ * builds), own0, own1 (its block), deferred (1: its share ingests something a LATER turn's block produces -- records that point at an early-return
+ * view, best matches of a view an early return's local camera numbers name -- so it builds nothing in its turn and gets a second visit after the
+ * last turn).  info[0 .. 3] (may be NULL) = reach, check, tail, supported (0: a scene the blocks-of-views partition refuses; its compute3Dmodel
+ * runs as plain mode 2) */
+int l3d_turn_handover_plan(const l3d_chain_view* views, int n_views, int world, int32_t* out, int32_t* info);
 
 /* ---- Line3D::matchViews sharded by BLOCKS OF VIEWS over the ranks, speculatively, with exact verification ----------------------
  * (line3D.cc:620-648 is a chain over views: the kept matches of a view become candidates of its later neighbours, :806,838-872.)
@@ -545,6 +553,21 @@ int l3d_line3d_set_node_mode(l3d_line3d* h, int mode);
  * the early-return views it held as chain_summary counts them (rebuilt from their sources' records: no room of their own in the arena).  For a turn
  * that kept exactly its keep set this is the sum of the one chain's chain_summary kept counts over the views l3d_partition_keep_views gives its block.  L3D_ERR_INVALID on a single-device object, a rank out of range or when the last run took no turns. */
 int l3d_line3d_node_turn_records(const l3d_line3d* h, int rank, int64_t* records);
+/* Mode 2 with a warm hand-over between the turns (opt-in; no effect unless the node mode is 2): turn r computes only its own piece of the chain --
+ * rank 0 the views [0, own1 + tail) cold, rank r > 0 the views [own0, own1 + tail) warm from the last `check` views of turn r - 1 (records, best depth
+ * pairs, best positions: a package owned by the node object) -- builds its share as l3d_match_chain_partition would, takes its digests and releases
+ * its records.  What leaves a rank through exchanges there (the records that point at early-return views, the best matches of the views their local
+ * camera numbers name) goes into a store of the node object.  A turn whose share needs something of a LATER turn's block (l3d_turn_handover_plan:
+ * deferred) runs its piece in order, builds nothing, and is visited a second time after the last turn: the same piece from the same package, the
+ * same digests or L3D_ERR_INVALID naming the rank, then the share.  The chains of all turns then compute between one and two times the views of
+ * the one chain instead of W times (every visit still sets the chain up for all views and every turn builds its share: DESIGN.md section 6 has what was measured).
+ * Option regrow_free_mb, where set, bounds everything a turn's arena takes: its first guess, its regrow and the slices put behind its records.  A scene the
+ * partition refuses (l3d_turn_handover_plan: supported = 0) and a node object whose ranks do not all share one device run that compute3Dmodel as
+ * plain mode 2.  L3D_ERR_INVALID on a single-device object and for values other than 0 / 1.  The result is the one-device object's, bit for bit. */
+int l3d_line3d_set_turn_handover(l3d_line3d* h, int on);
+/* after a compute3Dmodel that ran in turns: the chain views rank `rank` computed (over all its visits) and its visits.  Hand-over off, or a run that
+ * fell back to plain mode 2: n_views and 1.  With the hand-over l3d_line3d_node_turn_records reports the records the rank's arena held when its share was built. */
+int l3d_line3d_node_turn_views(const l3d_line3d* h, int rank, int64_t* views_computed, int* visits);
 void l3d_line3d_destroy(l3d_line3d* h);
 const char* l3d_line3d_last_error(const l3d_line3d* h);
 l3d_ctx* l3d_line3d_context(l3d_line3d* h);

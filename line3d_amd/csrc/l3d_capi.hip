@@ -45,6 +45,7 @@ void ctx_turn_share(l3d_ctx* c, int on) { if (c) c->turn_share = on != 0; }
 void ctx_fill_gate(l3d_ctx* c, void (*gate)(void*, int), void* user) { if (c) { c->fill_gate = gate; c->fill_gate_user = user; } }
 void ctx_fill_collective_only(l3d_ctx* c, int on) { if (c) c->fill_collective_only = on != 0; }
 const std::vector<int>& ctx_shard_view_kept(const l3d_ctx* c) { return c->shard_view_kept; }
+void ctx_part_total(l3d_ctx* c, long long n_pot_all) { if (c && c->products.part.active) c->products.part.n_pot_all = n_pot_all; }
 void ctx_release_share(l3d_ctx* c)
 {
     if (!c) return;

@@ -28,6 +28,7 @@
 #include "l3d_products.hpp"
 #include "l3d_chain_common.hpp"
 #include "l3d_runtable.hpp"
+#include "l3d_turns.hpp"
 
 #ifndef L3D_AHEAD
 #define L3D_AHEAD 4
@@ -383,6 +384,15 @@ static int run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_c
         if (pre->k1 != k_begin || pre->k0 < 0 || pre->k0 > pre->k1 || (int)pre->n_kept.size() != pre->k1 - pre->k0 || (int)pre->R.size() != pre->k1 - pre->k0) return fail(c, L3D_ERR_INVALID, "match_chain: bad preload");
         for (int k = pre->k0; k < pre->k1; ++k) { pre_records += pre->n_kept[(size_t)(k - pre->k0)]; has_rec[(size_t)k] = views[k].n_tbm > 0 ? 1 : 0; }
         arena_cap += (size_t)pre_records;
+    }
+    // a turn of a node object that hands the chain over (match_chain_turn) under option regrow_free_mb: the room binds on everything the turn's arena
+    // takes -- this first guess, the regrow below, the slices its share puts behind the records -- as it does on the compact arena of a plain turn
+    const size_t turn_room = c->turn_arena_room;
+    if (turn_room) {
+        if ((size_t)pre_records + 65536 > turn_room)
+            return fail(c, L3D_ERR_NOMEM, "match_chain: the " + std::to_string(pre_records) + " records taken over from the turn before need more than the room for " + std::to_string(turn_room) + " records (" +
+                                          std::to_string(c->opt.regrow_free_mb) + " MB at " + std::to_string(sizeof(Match) + 4) + " B per record)");
+        arena_cap = std::min(arena_cap, turn_room);
     }
 
     // early pair transposes (round 6, l3d_products.hip): a (view, camera) pair of the potential-correspondence build depends on that view's kept list alone, so
@@ -756,8 +766,9 @@ static int run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_c
                     if (hipMemGetInfo(&fr, &tot) == hipSuccess) {
                         if (c->opt.regrow_free_mb > 0) fr = std::min(fr, (size_t)c->opt.regrow_free_mb << 20);     // (tests: a card with less room)
                         const size_t per_rec = sizeof(Match) + 4 + (early && new_cap < 0x7ffffff0ull ? 4 : 0) + (map ? 8 : 0);
-                        const size_t reserve = map ? (size_t)((1ll << 28) * 24) + ((size_t)1 << 30) : (size_t)512 << 20;
-                        const size_t fits = fr > reserve ? (fr - reserve) / per_rec : 0;
+                        // (a turn under the cap: the room is the arena's, nothing is kept back from it)
+                        const size_t reserve = turn_room ? 0 : map ? (size_t)((1ll << 28) * 24) + ((size_t)1 << 30) : (size_t)512 << 20;
+                        const size_t fits = turn_room ? turn_room : fr > reserve ? (fr - reserve) / per_rec : 0;
                         if (new_cap > fits) {
                             if (fits < need || fits <= arena_cap) {
                                 rc_final = fail(c, L3D_ERR_NOMEM, "match_chain: the kept arena of " + std::to_string(arena_cap) + " records is full at view " + std::to_string(k) + " of " + std::to_string(n_views) + " (" +
@@ -1643,6 +1654,426 @@ extern "C" int l3d_partition_info(l3d_ctx* c, int info[10], int64_t* n_pot_all)
     if (info) { const int v[10] = { q.rank, q.world, q.own_dv0, q.own_dv1, q.row_dv0, q.row_dv1, q.held_dv0, q.held_dv1, q.recovery_rounds, q.blocks_rerun }; memcpy(info, v, sizeof(v)); }
     if (n_pot_all) *n_pot_all = q.active ? q.n_pot_all : c->products.n_pot;
     return L3D_OK;                      // (info[1] = world of the partition; not partitioned: the defaults, world 1)
+}
+
+// =================================================================================================================================
+// Turns that hand the chain over (l3d_turns.hpp; line3d_host.cpp: node mode 2 with l3d_line3d_set_turn_handover).  The parts of the
+// blocks-of-views partition above that involve no collective, composed SEQUENTIALLY: the ranks of one device run one after the other, so a
+// successor needs no speculation -- it is given its predecessor's tail (ChainPreload, as the recovery path gives it after a miss).
+namespace {
+
+// the early-return views of a schedule with what the quirk couples them to (cudawrapper.cu:877-878, line3D.cc:861-865)
+struct TurnEarly {
+    int view = 0;
+    std::vector<int> src;           // verified earlier views whose records point at it (ProdSrc of l3d_products.hip)
+    std::vector<int> alias_rows;    // the views those sources' LOCAL camera numbers name: their rows get entries that name this view's segments
+    std::vector<int> alias_best;    // the verified views any of its local camera numbers names: k_alias_pack packages
+};
+struct TurnNeeds { std::vector<char> in_E; std::vector<int> src, alias_req, alias_opt; };
+
+void turn_early_views(const l3d_chain_view* views, int n, std::vector<TurnEarly>& out, std::vector<int>& groups_all)
+{
+    std::vector<std::pair<unsigned, int>> idx((size_t)n);
+    for (int k = 0; k < n; ++k) idx[(size_t)k] = { views[k].view_id, k };
+    std::sort(idx.begin(), idx.end());
+    auto find = [&](unsigned id) { auto it = std::lower_bound(idx.begin(), idx.end(), std::make_pair(id, -1)); return it != idx.end() && it->first == id ? it->second : -1; };
+    for (int k = 0; k < n; ++k) {
+        if (views[k].n_tbm != 0 || views[k].n_sources == 0) continue;
+        TurnEarly e;
+        e.view = k;
+        for (int q = 0; q < views[k].n_sources; ++q) {
+            const int si = views[k].source_index[q], b = find((unsigned)views[k].source_cam[q]);
+            const bool valid = si >= 0 && si < k && views[si].n_tbm > 0;
+            if (valid) { e.src.push_back(si); groups_all.push_back(si); if (b >= 0) e.alias_rows.push_back(b); }
+            if (b >= 0 && views[b].n_tbm > 0) e.alias_best.push_back(b);
+        }
+        out.push_back(e);
+    }
+    std::sort(groups_all.begin(), groups_all.end());
+    groups_all.erase(std::unique(groups_all.begin(), groups_all.end()), groups_all.end());
+}
+
+// what the share of a turn with these ranges ingests.  in_E: the early-return views it builds hypotheses and entries of -- the ones it holds and the
+// ones whose entries land in its rows; every other one is left out of its products (a partial list of sources would give it hypotheses its owner
+// does not have)
+void turn_needs(const std::vector<TurnEarly>& early, const l3d::TurnRange& t, TurnNeeds& o)
+{
+    auto held = [&](int k) { return k >= t.pre0 && k < t.run1; };
+    auto in_rows = [&](int k) { return k >= t.row0 && k < t.row1; };
+    o.in_E.assign(early.size(), 0);
+    for (size_t i = 0; i < early.size(); ++i) {
+        const TurnEarly& e = early[i];
+        bool in = held(e.view);
+        for (int b : e.alias_rows) in = in || in_rows(b);
+        if (!in) continue;
+        o.in_E[i] = 1;
+        for (int si : e.src) if (!held(si)) o.src.push_back(si);
+        for (int b : e.alias_best) if (!held(b)) { o.alias_opt.push_back(b); if (in_rows(e.view)) o.alias_req.push_back(b); }
+    }
+    for (std::vector<int>* v : { &o.src, &o.alias_req, &o.alias_opt }) { std::sort(v->begin(), v->end()); v->erase(std::unique(v->begin(), v->end()), v->end()); }
+}
+
+int turn_owner(int k, int n, int world)
+{
+    int r = (int)(((long long)k * world) / n);
+    auto bb = [&](int q) { return (int)(((long long)n * q) / world); };
+    while (r + 1 < world && bb(r + 1) <= k) ++r;
+    while (r > 0 && bb(r) > k) --r;
+    return r;
+}
+
+}  // namespace
+
+int l3d::turn_handover_schedule(const l3d_chain_view* views, int n_views, int world, int window, TurnSchedule* out)
+{
+    if (!views || n_views <= 0 || world < 1 || !out) return L3D_ERR_INVALID;
+    for (int k = 0; k < n_views; ++k) {
+        if (views[k].N < 0 || views[k].n_sources < 0 || (views[k].N > 0 && !views[k].local2global) || (views[k].n_sources > 0 && (!views[k].source_cam || !views[k].source_index))) return L3D_ERR_INVALID;
+        for (int q = 0; q < views[k].n_sources; ++q) if (views[k].source_index[q] >= n_views) return L3D_ERR_INVALID;
+    }
+    if (window <= 0) {
+        window = 1;
+        for (int k = 0; k < n_views; ++k) for (int q = 0; q < views[k].n_sources; ++q) if (views[k].source_index[q] >= 0) window = std::max(window, k - views[k].source_index[q]);
+    }
+    // reach, check and tail as chain_blocks_impl (partition = 1) computes them
+    int reach = window;
+    {
+        std::vector<std::pair<unsigned, int>> idx((size_t)n_views);
+        for (int k = 0; k < n_views; ++k) idx[(size_t)k] = { views[k].view_id, k };
+        std::sort(idx.begin(), idx.end());
+        for (int k = 0; k < n_views; ++k)
+            for (int q = 0; q < views[k].N; ++q) {
+                auto it = std::lower_bound(idx.begin(), idx.end(), std::make_pair(views[k].local2global[q], -1));
+                if (it != idx.end() && it->first == views[k].local2global[q]) reach = std::max(reach, std::abs(it->second - k));
+            }
+    }
+    TurnSchedule& S = *out;
+    S.reach = reach; S.tail = 2 * reach; S.check = std::max(window, 2 * reach); S.supported = true;
+    S.turns.assign((size_t)world, TurnRange());
+    for (int r = 0; r < world; ++r) {
+        TurnRange& t = S.turns[(size_t)r];
+        t.own0 = (int)(((long long)n_views * r) / world); t.own1 = (int)(((long long)n_views * (r + 1)) / world);
+        t.run1 = std::min(n_views, t.own1 + S.tail);
+        t.pre0 = r == 0 ? 0 : std::max(0, t.own0 - S.check);
+        t.run0 = r == 0 ? 0 : t.own0;
+        t.row0 = std::max(t.pre0, t.own0 - reach); t.row1 = std::min(t.run1, t.own1 + reach);
+        t.deferred = 0;
+    }
+    std::vector<TurnEarly> early;
+    std::vector<int> groups_all;
+    turn_early_views(views, n_views, early, groups_all);
+    if (early.size() > 64 || groups_all.size() > 480) S.supported = false;
+    for (int r = 0; r < world && world > 1; ++r) {
+        TurnNeeds need;
+        turn_needs(early, S.turns[(size_t)r], need);
+        for (int si : need.src) if (turn_owner(si, n_views, world) > r) S.turns[(size_t)r].deferred = 1;
+        for (int b : need.alias_req) if (turn_owner(b, n_views, world) > r) S.turns[(size_t)r].deferred = 1;
+        // (chain_blocks_impl: one list cannot be both the sliver of records that point at an early-return view and the view's best matches)
+        for (int b : need.alias_opt) if (std::binary_search(need.src.begin(), need.src.end(), b)) S.supported = false;
+    }
+    return L3D_OK;
+}
+
+extern "C" int l3d_turn_handover_plan(const l3d_chain_view* views, int n_views, int world, int32_t* out, int32_t* info)
+{
+    if (!out) return L3D_ERR_INVALID;
+    l3d::TurnSchedule S;
+    if (const int rc = l3d::turn_handover_schedule(views, n_views, world, 0, &S)) return rc;
+    for (int r = 0; r < world; ++r) {
+        const l3d::TurnRange& t = S.turns[(size_t)r];
+        const int v[8] = { t.pre0, t.run0, t.run1, t.row0, t.row1, t.own0, t.own1, t.deferred };
+        memcpy(out + 8 * r, v, sizeof(v));
+    }
+    if (info) { info[0] = S.reach; info[1] = S.check; info[2] = S.tail; info[3] = S.supported ? 1 : 0; }
+    return L3D_OK;
+}
+
+void l3d::turn_handover_release(TurnHandover* p)
+{
+    if (!p) return;
+    if (p->dev) { if (p->device >= 0) (void)hipSetDevice(p->device); (void)hipFree(p->dev); }
+    *p = TurnHandover();
+}
+void l3d::turn_store_release(TurnStore* s)
+{
+    if (!s) return;
+    if (s->device >= 0) (void)hipSetDevice(s->device);
+    for (auto& x : s->early) if (x.owns && x.base) (void)hipFree(x.base);
+    for (auto& x : s->alias) if (x.owns && x.base) (void)hipFree(x.base);
+    *s = TurnStore();
+}
+
+int l3d::match_chain_turn(l3d_ctx* c, const l3d_chain_view* views, int n_views, const l3d_dense_map* map, l3d_chain_summary* summary, int rank, int world, int window,
+                          const TurnHandover* in, TurnHandover* out, TurnStore* store, bool build_share, TurnReport* report)
+{
+    if (!c) return L3D_ERR_INVALID;
+    if (!views || n_views <= 0 || !map || !summary || !store || !report || world < 1 || rank < 0 || rank >= world || window < 0) return fail(c, L3D_ERR_INVALID, "match_chain_turn: bad argument");
+    TurnSchedule S;
+    if (turn_handover_schedule(views, n_views, world, window, &S)) return fail(c, L3D_ERR_INVALID, "match_chain_turn: bad schedule");
+    if (!S.supported) return fail(c, L3D_ERR_UNSUPPORTED, "match_chain_turn: a schedule the blocks-of-views partition refuses (early returns)");
+    const TurnRange T = S.turns[(size_t)rank];
+    const int last = T.run1, exact_from = T.pre0;
+    // option regrow_free_mb (tests: a card with less room): what the turn's arena may hold, records with their side words -- run_chain's first guess
+    // and regrow and the slices of step 4 all stay within it (the compact arena of a plain turn: l3d_line3d_shard_run)
+    struct RoomGuard { l3d_ctx* c; ~RoomGuard() { c->turn_arena_room = 0; } } room_guard{ c };
+    c->turn_arena_room = c->opt.regrow_free_mb > 0 ? ((size_t)c->opt.regrow_free_mb << 20) / (sizeof(Match) + 4) : 0;
+    const size_t room = c->turn_arena_room;
+    auto grow_within_room = [&](long long records, long long used_records) -> int {
+        if (room && (size_t)records > room)
+            return fail(c, L3D_ERR_NOMEM, "match_chain_turn: the arena of rank " + std::to_string(rank) + " needs " + std::to_string(records) + " records with the slices of the views it does not hold, there is room for " +
+                                          std::to_string(room) + " (" + std::to_string(c->opt.regrow_free_mb) + " MB at " + std::to_string(sizeof(Match) + 4) + " B per record)");
+        return arena_grow_keep(c, (size_t)records + 64, (size_t)used_records);
+    };
+    c->products.valid = false;
+    c->products.part = ProductsPart();
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    if (store->device < 0) { store->device = c->device; store->early.assign((size_t)n_views, TurnStore::Piece()); store->alias.assign((size_t)n_views, TurnStore::Piece()); store->has_early.assign((size_t)n_views, 0); store->has_alias.assign((size_t)n_views, 0); }
+    if (store->device != c->device || (int)store->early.size() != n_views) return fail(c, L3D_ERR_INVALID, "match_chain_turn: the store belongs to another device or scene");
+    // offsets of the views' slices in the whole-run arrays of best pairs / positions (chain_assign_arenas: verified views back to back)
+    std::vector<long long> best_off((size_t)n_views + 1, 0);
+    for (int k = 0; k < n_views; ++k) best_off[(size_t)k + 1] = best_off[(size_t)k] + (views[k].n_tbm > 0 ? views[k].S_src : 0);
+
+    // ---- 1. the chain piece: cold from view 0 (turn 0), else warm from the predecessor's tail
+    const double t0 = now_s();
+    if (T.run0 > T.pre0) {
+        if (!in || !in->dev || in->device != c->device || in->k0 != T.pre0 || in->k1 != T.run0 || (int)in->n_kept.size() != T.run0 - T.pre0 || (int)in->R.size() != T.run0 - T.pre0)
+            return fail(c, L3D_ERR_INVALID, "match_chain_turn: rank " + std::to_string(rank) + " was not handed the views " + std::to_string(T.pre0) + ".." + std::to_string(T.run0 - 1) + " of its predecessor");
+        ChainPreload pre;
+        pre.k0 = T.pre0; pre.k1 = T.run0;
+        const unsigned char* G = static_cast<const unsigned char*>(in->dev);
+        pre.records = reinterpret_cast<const Match*>(G);
+        pre.best = reinterpret_cast<const float2*>(G + in->o_best);
+        pre.bestpos = reinterpret_cast<const int*>(G + in->o_bpos);
+        pre.n_kept = in->n_kept; pre.R = in->R;
+        if (int rc = run_chain(c, views, n_views, nullptr, nullptr, nullptr, nullptr, nullptr, T.run0, last, &pre)) return rc;
+    } else if (int rc = run_chain(c, views, n_views, nullptr, nullptr, nullptr, nullptr, nullptr, T.run0, last)) return rc;
+    report->views_computed = last - T.run0;
+    // (a job sized by memory: what only a running chain needs goes back before anything else is allocated -- as the partition does)
+    if (c->opt.part_release != 0) {
+        HIPCHK(c, hipStreamSynchronize(st)); HIPCHK(c, hipStreamSynchronize(c->stage1_stream));
+        DevBuf* b[] = { &c->ch_ringA_meta, &c->ch_ringA_depths, &c->cand_meta, &c->cand_depths, &c->cand_conf, &c->vw_scratch, &c->ch_mask, &c->ch_rays, &c->ch_rowcnt, &c->ch_rowA };
+        for (DevBuf* x : b) x->release();
+    }
+    const ChainResult* hres = c->ch_pin_res.as<ChainResult>();
+    const double t1 = now_s();
+    {
+        double p = 0;
+        for (int k = T.own0; k < T.own1; ++k)
+            for (int j = 0; j < views[k].n_tbm; ++j) p += (double)views[k].S_src * views[k].offsets[2 * views[k].to_be_matched[j] + 1];
+        c->stats[0] = p;
+    }
+    std::vector<ChainResult> hloc((size_t)n_views);
+    long long used = 0;
+    for (int k = 0; k < n_views; ++k) { hloc[(size_t)k] = ChainResult(); if (k >= exact_from && k < last) { hloc[(size_t)k] = hres[k]; used = std::max(used, (long long)hres[k].kept_base + hres[k].n_kept); } }
+    if ((size_t)used * sizeof(Match) > c->ch_kept.cap) return fail(c, L3D_ERR_INVALID, "match_chain_turn: the chain's result records point outside its arena");
+    // the final records on the device (a restart rewrites them) and the digests of every view held
+    HIPCHK(c, hipMemcpyAsync(c->ch_res.p, hloc.data(), (size_t)n_views * sizeof(ChainResult), hipMemcpyHostToDevice, st));
+    report->hash.assign((size_t)n_views, 0); report->n_kept.assign((size_t)n_views, 0); report->held.assign((size_t)n_views, 0);
+    for (int k = exact_from; k < last; ++k) report->held[(size_t)k] = 1;
+    {
+        const size_t tab_bytes = al((size_t)n_views * sizeof(BlockDigest));
+        HIPCHK(c, c->ch_hdr.reserve(tab_bytes + 256));
+        BlockDigest* dd = c->ch_hdr.as<BlockDigest>();
+        HIPCHK(c, hipMemsetAsync(dd, 0, tab_bytes, st));
+        for (int k0 = exact_from; k0 < last; k0 += 32768)
+            hipLaunchKernelGGL(k_block_digest, dim3(16, (unsigned)std::min(32768, last - k0)), dim3(256), 0, st, c->ch_kept.as<Match>(), c->ch_res.as<ChainResult>(), k0, dd);
+        std::vector<BlockDigest> hd((size_t)n_views);
+        HIPCHK(c, hipMemcpyAsync(hd.data(), dd, (size_t)n_views * sizeof(BlockDigest), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        HIPCHK(c, hipGetLastError());
+        for (int k = exact_from; k < last; ++k) { report->hash[(size_t)k] = hd[(size_t)k].hash; report->n_kept[(size_t)k] = hd[(size_t)k].n_kept; }
+    }
+    report->arena_records = used;
+
+    // ---- 2. the tail for the successor, before the records go: [records | best depth pairs | best positions] of the last `check` views of the block
+    if (out && rank + 1 < world) {
+        turn_handover_release(out);
+        const TurnRange& N = S.turns[(size_t)rank + 1];
+        const int k0 = N.pre0, k1 = N.run0;
+        if (k0 < exact_from || k1 > last || k1 < k0) return fail(c, L3D_ERR_INVALID, "match_chain_turn: the successor's preload is not covered by what this rank holds");
+        long long t_rec = 0, t_seg = 0;
+        for (int k = k0; k < k1; ++k) { t_rec += hloc[(size_t)k].n_kept; if (views[k].n_tbm > 0) t_seg += views[k].S_src; }
+        out->device = c->device; out->k0 = k0; out->k1 = k1;
+        out->o_best = al((size_t)t_rec * sizeof(Match)); out->o_bpos = out->o_best + al((size_t)t_seg * 8); out->bytes = out->o_bpos + al((size_t)t_seg * 4) + 256;
+        if (hipMalloc(&out->dev, out->bytes) != hipSuccess) { (void)hipGetLastError(); out->dev = nullptr; return fail(c, L3D_ERR_NOMEM, "match_chain_turn: the hand-over package of " + std::to_string(out->bytes >> 20) + " MB"); }
+        unsigned char* G = static_cast<unsigned char*>(out->dev);
+        long long at = 0;
+        for (int k = k0; k < k1; ++k) {
+            const ChainResult& r = hloc[(size_t)k];
+            out->n_kept.push_back(r.n_kept); out->R.push_back(r.R);
+            if (r.n_kept > 0) HIPCHK(c, hipMemcpyAsync(G + (size_t)at * sizeof(Match), c->ch_kept.as<Match>() + r.kept_base, (size_t)r.n_kept * sizeof(Match), hipMemcpyDeviceToDevice, st));
+            at += r.n_kept;
+        }
+        if (t_seg > 0) {
+            HIPCHK(c, hipMemcpyAsync(G + out->o_best, c->ch_best.as<float2>() + best_off[(size_t)k0], (size_t)t_seg * 8, hipMemcpyDeviceToDevice, st));
+            HIPCHK(c, hipMemcpyAsync(G + out->o_bpos, c->ch_bestpos.as<int>() + best_off[(size_t)k0], (size_t)t_seg * 4, hipMemcpyDeviceToDevice, st));
+        }
+        HIPCHK(c, hipStreamSynchronize(st));
+    }
+
+    // ---- 3. the quirk store: what this rank's block owes the other turns (filed once: a second visit finds its pieces there)
+    std::vector<TurnEarly> early;
+    std::vector<int> groups_all;
+    turn_early_views(views, n_views, early, groups_all);
+    std::vector<unsigned> early_ids;
+    for (const TurnEarly& e : early) early_ids.push_back(views[e.view].view_id);
+    if (world > 1 && !groups_all.empty()) {
+        std::vector<int> mine;
+        for (int si : groups_all) if (turn_owner(si, n_views, world) == rank && !store->has_early[(size_t)si]) mine.push_back(si);
+        if (!mine.empty()) {
+            // (control block as in the partition: 64 ids, 480 groups -- turn_handover_schedule refuses more)
+            const size_t o_ids = 0, o_grp = 256, o_off = o_grp + 2048, o_cnt = o_off + 4096, ctl = o_cnt + 2048;
+            HIPCHK(c, c->ch_send.reserve(ctl + 256));
+            unsigned char* S0 = c->ch_send.as<unsigned char>();
+            std::vector<int> cnt(mine.size(), 0);
+            HIPCHK(c, hipMemcpyAsync(S0 + o_ids, early_ids.data(), early_ids.size() * 4, hipMemcpyHostToDevice, st));
+            HIPCHK(c, hipMemcpyAsync(S0 + o_grp, mine.data(), mine.size() * 4, hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_early_pack, dim3((unsigned)mine.size()), dim3(256), 0, st, c->ch_kept.as<Match>(), c->ch_res.as<ChainResult>(), reinterpret_cast<const int*>(S0 + o_grp),
+                               reinterpret_cast<const unsigned*>(S0 + o_ids), (int)early_ids.size(), (const long long*)nullptr, (Match*)nullptr, reinterpret_cast<int*>(S0 + o_cnt));
+            HIPCHK(c, hipMemcpyAsync(cnt.data(), S0 + o_cnt, mine.size() * 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(c, hipStreamSynchronize(st));
+            std::vector<long long> offs(mine.size(), 0);
+            long long total = 0;
+            for (size_t g = 0; g < mine.size(); ++g) { offs[g] = total; total += cnt[g]; }
+            // one allocation for this rank's sources (the first piece owns it), a slice per source
+            void* buf = nullptr;
+            if (hipMalloc(&buf, (size_t)std::max<long long>(total, 1) * sizeof(Match)) != hipSuccess) { (void)hipGetLastError(); return fail(c, L3D_ERR_NOMEM, "match_chain_turn: the records that point at early-return views"); }
+            // (filed at once: whatever fails below, the store owns the allocation)
+            for (size_t g = 0; g < mine.size(); ++g) {
+                TurnStore::Piece& x = store->early[(size_t)mine[g]];
+                x.base = buf; x.off = (size_t)offs[g] * sizeof(Match); x.n = cnt[g]; x.owns = g == 0;
+            }
+            if (total > 0) {
+                HIPCHK(c, hipMemcpyAsync(S0 + o_off, offs.data(), offs.size() * 8, hipMemcpyHostToDevice, st));
+                hipLaunchKernelGGL(k_early_pack, dim3((unsigned)mine.size()), dim3(256), 0, st, c->ch_kept.as<Match>(), c->ch_res.as<ChainResult>(), reinterpret_cast<const int*>(S0 + o_grp),
+                                   reinterpret_cast<const unsigned*>(S0 + o_ids), (int)early_ids.size(), reinterpret_cast<const long long*>(S0 + o_off), static_cast<Match*>(buf), (int*)nullptr);
+            }
+            const hipError_t e = hipStreamSynchronize(st);
+            if (e != hipSuccess) return fail(c, L3D_ERR_HIP, std::string("match_chain_turn: packing the early-return records: ") + hipGetErrorString(e));
+            for (int si : mine) store->has_early[(size_t)si] = 1;
+        }
+    }
+    auto pk_bytes = [&](int b) { return al(16 + (size_t)views[b].S_src * (12 + sizeof(Match))); };
+    if (world > 1 && !early.empty()) {
+        std::vector<int> alias;
+        for (const TurnEarly& e : early) alias.insert(alias.end(), e.alias_best.begin(), e.alias_best.end());
+        std::sort(alias.begin(), alias.end());
+        alias.erase(std::unique(alias.begin(), alias.end()), alias.end());
+        std::vector<int> pk_view, pk_S;
+        std::vector<long long> pk_bo, pk_oo;
+        size_t o = 0;
+        for (int b : alias) if (turn_owner(b, n_views, world) == rank && !store->has_alias[(size_t)b]) { pk_view.push_back(b); pk_S.push_back(views[b].S_src); pk_bo.push_back(best_off[(size_t)b]); pk_oo.push_back((long long)o); o += pk_bytes(b); }
+        const size_t n = pk_view.size();
+        if (n > 0) {
+            const size_t o1 = al(n * 4), o2 = 2 * al(n * 4), o3 = o2 + al(n * 8), ctl = al(n * 4) * 2 + al(n * 8) * 2 + 256;
+            HIPCHK(c, c->ch_send.reserve(ctl));
+            void* buf = nullptr;
+            if (hipMalloc(&buf, o + 256) != hipSuccess) { (void)hipGetLastError(); return fail(c, L3D_ERR_NOMEM, "match_chain_turn: alias-view packages"); }
+            unsigned char* S0 = c->ch_send.as<unsigned char>();
+            hipError_t e = hipMemcpyAsync(S0, pk_view.data(), n * 4, hipMemcpyHostToDevice, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(S0 + o1, pk_S.data(), n * 4, hipMemcpyHostToDevice, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(S0 + o2, pk_bo.data(), n * 8, hipMemcpyHostToDevice, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(S0 + o3, pk_oo.data(), n * 8, hipMemcpyHostToDevice, st);
+            if (e == hipSuccess) {
+                hipLaunchKernelGGL(k_alias_pack, dim3((unsigned)n), dim3(256), 0, st, c->ch_kept.as<Match>(), c->ch_res.as<ChainResult>(), reinterpret_cast<const int*>(S0), reinterpret_cast<const int*>(S0 + o1),
+                                   reinterpret_cast<const long long*>(S0 + o2), reinterpret_cast<const long long*>(S0 + o3), c->ch_best.as<float2>(), c->ch_bestpos.as<int>(), static_cast<unsigned char*>(buf));
+                e = hipStreamSynchronize(st);
+            }
+            if (e != hipSuccess) { (void)hipFree(buf); return fail(c, L3D_ERR_HIP, std::string("match_chain_turn: packing the alias views' best matches: ") + hipGetErrorString(e)); }
+            for (size_t i = 0; i < n; ++i) {
+                TurnStore::Piece& x = store->alias[(size_t)pk_view[i]];
+                x.base = buf; x.off = (size_t)pk_oo[i]; x.n = pk_S[i]; x.owns = i == 0;
+                store->has_alias[(size_t)pk_view[i]] = 1;
+            }
+        }
+    }
+    if (!build_share) {
+        if (c->opt.timing) fprintf(stderr, "[l3d chain_turn rank %d/%d] views %d..%d warm from %d: chain %.2f ms, tail and store %.2f ms; the share is deferred\n", rank, world, T.run0, last - 1, T.pre0, (t1 - t0) * 1e3, (now_s() - t1) * 1e3);
+        return L3D_OK;
+    }
+
+    // ---- 4. the share: the slices of the views this rank does not hold come out of the store (the partition reads them from the gathered buffers)
+    TurnNeeds need;
+    turn_needs(early, T, need);
+    for (int si : need.src) {
+        if (!store->has_early[(size_t)si]) return fail(c, L3D_ERR_INVALID, "match_chain_turn: rank " + std::to_string(rank) + " builds its share before the records of view " + std::to_string(views[si].view_id) + " that point at early-return views are filed");
+        const int n = store->early[(size_t)si].n;
+        const Match* src = reinterpret_cast<const Match*>(static_cast<const unsigned char*>(store->early[(size_t)si].base) + store->early[(size_t)si].off);
+        if (n <= 0) continue;
+        if (!store->early[(size_t)si].base) return fail(c, L3D_ERR_INVALID, "match_chain_turn: a filed slice has no allocation");
+        if (int rc = grow_within_room(used + n, used)) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->ch_kept.as<Match>() + used, src, (size_t)n * sizeof(Match), hipMemcpyDeviceToDevice, st));
+        ChainResult& x = hloc[(size_t)si];
+        x.kept_base = (uint64_t)used; x.n_kept = n; x.R = n; x.overflow = 0;
+        used += n;
+    }
+    std::vector<char> alias_known((size_t)n_views, 0);
+    for (int b : need.alias_opt) {
+        if (!store->has_alias[(size_t)b]) {
+            if (std::binary_search(need.alias_req.begin(), need.alias_req.end(), b)) return fail(c, L3D_ERR_INVALID, "match_chain_turn: rank " + std::to_string(rank) + " builds its share before the best matches of view " + std::to_string(views[b].view_id) + " are filed");
+            continue;
+        }
+        const unsigned char* pk = static_cast<const unsigned char*>(store->alias[(size_t)b].base) + store->alias[(size_t)b].off;
+        if (!store->alias[(size_t)b].base) return fail(c, L3D_ERR_INVALID, "match_chain_turn: a filed package has no allocation");
+        int h[4] = { 0, 0, 0, 0 };
+        HIPCHK(c, hipMemcpyAsync(h, pk, 16, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        const int Sb = views[b].S_src;
+        if (h[0] != b || h[3] != Sb || h[2] < 0 || h[2] > Sb) return fail(c, L3D_ERR_INVALID, "match_chain_turn: a package of best matches does not name the view it should");
+        if (hloc[(size_t)b].n_kept > 0) return fail(c, L3D_ERR_UNSUPPORTED, "match_chain_turn: view " + std::to_string(views[b].view_id) + " is a source of an early-return view and named by an early return's local camera number");
+        if (int rc = grow_within_room(used + h[2], used)) return rc;
+        if (h[2] > 0) HIPCHK(c, hipMemcpyAsync(c->ch_kept.as<Match>() + used, pk + 16 + (size_t)Sb * 12, (size_t)h[2] * sizeof(Match), hipMemcpyDeviceToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(c->ch_bestpos.as<int>() + best_off[(size_t)b], pk + 16, (size_t)Sb * 4, hipMemcpyDeviceToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(c->ch_best.as<float2>() + best_off[(size_t)b], pk + 16 + (size_t)Sb * 4, (size_t)Sb * 8, hipMemcpyDeviceToDevice, st));
+        ChainResult& x = hloc[(size_t)b];
+        x.kept_base = (uint64_t)used; x.n_kept = h[2]; x.R = h[1]; x.overflow = 0;
+        used += h[2];
+        alias_known[(size_t)b] = 1;
+    }
+    report->arena_records = used;
+    // an early-return view outside the set this share is about contributes nothing here: its entries land in other ranks' rows, and a partial list of
+    // its sources would give it hypotheses its owner does not have
+    std::vector<l3d_chain_view> vloc(views, views + n_views);
+    for (size_t i = 0; i < early.size(); ++i) if (!need.in_E[i]) vloc[(size_t)early[i].view].n_sources = 0;
+    const int nvd = map->n_views;
+    auto dense_of = [&](int k) {
+        if (k >= n_views) return nvd;
+        const uint32_t* it = std::lower_bound(map->view_ids, map->view_ids + nvd, views[k].view_id);
+        return (int)(it - map->view_ids);
+    };
+    std::vector<ProdChainView> pvh((size_t)n_views);
+    for (int k = 0; k < n_views; ++k) {
+        const bool ver = views[k].n_tbm > 0, held = (k >= exact_from && k < last) || alias_known[(size_t)k];
+        pvh[(size_t)k].verified = ver ? 1 : 0;
+        pvh[(size_t)k].best = ver && held ? c->ch_best.as<float2>() + best_off[(size_t)k] : nullptr;
+        pvh[(size_t)k].bestpos = ver && held ? c->ch_bestpos.as<int>() + best_off[(size_t)k] : nullptr;
+    }
+    const int row0 = T.row0, row1 = T.row1;
+    ProductsPart part;
+    part.active = true; part.rank = rank; part.world = world;
+    part.own_dv0 = dense_of(T.own0); part.own_dv1 = dense_of(T.own1);
+    part.row_dv0 = dense_of(row0); part.row_dv1 = dense_of(row1);
+    part.held_dv0 = dense_of(exact_from); part.held_dv1 = dense_of(last);
+    int64_t n_local = 0;
+    const double t3 = now_s();
+    {
+        std::vector<char> held((size_t)n_views, 0);
+        for (int k = exact_from; k < last; ++k) held[(size_t)k] = 1;
+        if (int rc = build_products(c, vloc.data(), n_views, pvh.data(), hloc.data(), map, summary, &n_local, part.row_dv0, part.row_dv1, held.data())) return rc;
+    }
+    Products& P = c->products;
+    part.n_pot_all = n_local;           // (no collective here: the node object adds the other turns' counts when all of them are through -- ctx_part_total)
+    report->n_pot = n_local;
+    P.part = part;
+    P.n_pot = n_local;
+    P.valid = true;
+    memcpy(c->ch_pin_res.as<ChainResult>(), hloc.data(), (size_t)n_views * sizeof(ChainResult));       // (what l3d_chain_kept_list reads)
+    { double kept = 0, raw = 0; for (int k = T.own0; k < T.own1; ++k) { kept += hloc[(size_t)k].n_kept; raw += hloc[(size_t)k].R; } c->stats[3] = kept; c->stats[1] = raw; }
+    if (c->opt.timing) fprintf(stderr, "[l3d chain_turn rank %d/%d] views %d..%d warm from %d: chain %.2f ms, rows of views %d..%d, %lld potential correspondences: products %.2f ms\n",
+                               rank, world, T.run0, last - 1, T.pre0, (t1 - t0) * 1e3, row0, row1 - 1, (long long)n_local, (now_s() - t3) * 1e3);
+    return L3D_OK;
 }
 
 void l3d::warm_chain() { touch_kernel(reinterpret_cast<const void*>(&k_exist_count)); }

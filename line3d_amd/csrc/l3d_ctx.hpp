@@ -173,6 +173,7 @@ struct l3d_ctx {
     bool fill_collective_only = false;              // sharded fill: past its last collective this rank forms no numbering and no edge list (the result is read from another rank)
     void (*fill_gate)(void*, int) = nullptr;        // sharded fill: called with 1 before and 0 after this rank's candidate enumeration (the device's token)
     void* fill_gate_user = nullptr;
+    size_t turn_arena_room = 0;                     // match_chain_turn under option regrow_free_mb: the records the turn's arena may hold (0: no cap); set around its chain and share only
     bool records_released = false;                  // l3d_chain_release_records: the products' kept records are gone (l3d_chain_kept_list refuses)
     std::vector<int> shard_view_kept;               // the last sharded run: every chain view's kept count from its slot headers, whatever this rank retired
     size_t test_cand_cap = 0, test_arena_cap = 0;   // tests: initial capacities of the resident chain (0 = estimate)

@@ -16,6 +16,12 @@ struct NodeRanks {
     int mode = 0;                           // l3d_line3d_set_node_mode
     int threads_per_rank = 1;               // the host-thread budget split among the ranks
     std::vector<int64_t> turn_records;      // mode 2: the records every rank retired in its turn (l3d_line3d_node_turn_records)
+    // mode 2 with a warm hand-over between the turns (l3d_line3d_set_turn_handover; l3d_turns.hpp)
+    bool handover = false;
+    std::vector<int64_t> turn_views;        // the chain views every rank computed over its visits, and its visits (l3d_line3d_node_turn_views)
+    std::vector<int> turn_visits;
+    std::vector<l3d::TurnHandover> packages;    // packages[r]: the tail turn r left for turn r + 1 -- owned here, not by a rank's context
+    l3d::TurnStore store;                   // the early-return slices and alias packages of every block
 };
 
 // Mode 2 of a node object: the ranks of one device take their turns in rank order, one token per device (host condition: no device-side flag, no
@@ -244,22 +250,31 @@ static int node_turn(L* h, TurnGate& G, int r, int slot_records_1)
     return L3D_OK;
 }
 
-// compute3Dmodel with the ranks of a device taking turns (l3d_line3d_set_node_mode 2): a scene whose kept records do not fit one device's memory at once.
-// Every turn computes the WHOLE chain and keeps one block's share of it, so matchViews costs about W single passes; the collective finish is the
-// one of the other modes, every share standing for its rank.
-static int node_compute_turns(L* h, int perform_diffusion)
+// every rank prepares the scene without reserving the finishing stages' arenas from its size (a job sized by memory)
+static int node_prepare_turns(L* h)
 {
     NodeRanks& N = *h->node;
     const int W = (int)N.ranks.size();
-    if (rank0(h)->views.size() < 4) return h->fail(L3D_ERR_INVALID, "not enough images! can't compute 3D model...");   // line3D.cc:347-351
-    // (a job sized by memory: no rank reserves the finishing stages' arenas from the size of the scene)
     std::vector<int> hint((size_t)W, 1);
     for (int r = 0; r < W; ++r) {
         (void)l3d_get_option(N.ranks[(size_t)r]->ctx, "L3D_RESERVE_HINT", &hint[(size_t)r]);
         if (const int rc = l3d_set_option(N.ranks[(size_t)r]->ctx, "L3D_RESERVE_HINT", 0)) return h->fail(rc, l3d_last_error(N.ranks[(size_t)r]->ctx));
     }
-    int rc = node_run(h, [&](int r) { return prepare(N.ranks[(size_t)r]); });
+    const int rc = node_run(h, [&](int r) { return prepare(N.ranks[(size_t)r]); });
     for (int r = 0; r < W; ++r) (void)l3d_set_option(N.ranks[(size_t)r]->ctx, "L3D_RESERVE_HINT", hint[(size_t)r]);      // (read by prepare alone: the other modes keep theirs)
+    return rc;
+}
+// compute3Dmodel with the ranks of a device taking turns (l3d_line3d_set_node_mode 2): a scene whose kept records do not fit one device's memory at once.
+// Every turn computes the WHOLE chain and keeps one block's share of it, so matchViews costs about W single passes; the collective finish is the
+// one of the other modes, every share standing for its rank.
+// prepared: the ranks have prepared the scene already (the hand-over variant falling back to this one)
+static int node_compute_turns(L* h, int perform_diffusion, bool prepared = false)
+{
+    NodeRanks& N = *h->node;
+    const int W = (int)N.ranks.size();
+    if (rank0(h)->views.size() < 4) return h->fail(L3D_ERR_INVALID, "not enough images! can't compute 3D model...");   // line3D.cc:347-351
+    N.turn_views.clear(); N.turn_visits.clear();
+    int rc = prepared ? L3D_OK : node_prepare_turns(h);
     if (rc) return rc;
     int s_max = 0;
     for (const View* v : rank0(h)->vlist) s_max = std::max(s_max, v->S());
@@ -305,6 +320,167 @@ static int node_compute_turns(L* h, int perform_diffusion)
         return rc;
     }
     node_merge_summary(h);
+    N.turn_views.assign((size_t)W, (int64_t)h->chain_summary.size());       // (every turn computed the whole chain, once)
+    N.turn_visits.assign((size_t)W, 1);
+    return L3D_OK;
+}
+
+// ---- mode 2 with a warm hand-over between the turns (l3d_line3d_set_turn_handover) ------------------------------------------------------------
+static void node_drop_handover(NodeRanks& N)
+{
+    for (l3d::TurnHandover& p : N.packages) l3d::turn_handover_release(&p);
+    N.packages.clear();
+    l3d::turn_store_release(&N.store);
+}
+// one visit of rank r: its piece of the chain warm from packages[r - 1], the tail for rank r + 1 (first visit), its pieces of the store, and -- share -- its
+// share of the products, the hypotheses (the last reader of the kept records); then the records go
+static int node_turn_visit(L* h, int r, bool first, bool share, l3d::TurnReport& rep)
+{
+    NodeRanks& N = *h->node;
+    const int W = (int)N.ranks.size();
+    L* R = N.ranks[(size_t)r];
+    const double t0 = now_s();
+    match_begin(R);
+    ChainPlan* P = get_plan(R);
+    if (!P) return R->fail(L3D_ERR_INVALID, "turn: no static schedule");
+    std::vector<uint32_t> ids; std::vector<int32_t> base;
+    dense_map(R, ids, base);
+    l3d_dense_map map;
+    map.n_views = (int32_t)ids.size(); map.view_ids = ids.data(); map.seg_base = base.data();
+    R->chain_summary.assign(P->n, l3d_chain_summary());
+    R->resident_products = false;
+    const double t1 = now_s();
+    int rc = l3d::match_chain_turn(R->ctx, P->cv.data(), (int)P->n, &map, R->chain_summary.data(), r, W, 0, r > 0 ? &N.packages[(size_t)r - 1] : nullptr,
+                                   first ? &N.packages[(size_t)r] : nullptr, &N.store, share, &rep);
+    R->t_gpu_call += now_s() - t1;
+    if (rc) return R->fail(rc, std::string("match_chain_turn: ") + l3d_last_error(R->ctx));
+    if (share) {
+        R->resident_n_pot = rep.n_pot;
+        R->partitioned = true; R->part_exchange = l3d_exchange_node; R->part_user = N.comm;
+        rc = adopt_resident_products(R, *P);
+        if (rc) { R->partitioned = false; return rc; }
+        double st[4];
+        l3d_last_stats(R->ctx, st);
+        R->stat_pairs += st[0]; R->stat_raw += st[1];
+        R->t_match = now_s() - t0;
+        rc = greedy_selection_resident(R);                  // (l3d_products_hypotheses: nothing behind it reads the kept arena)
+        if (rc) return rc;
+        R->hyps_done = true;
+    }
+    rc = l3d_chain_release_records(R->ctx);
+    if (rc) return R->fail(rc, std::string("turn: ") + l3d_last_error(R->ctx));
+    return L3D_OK;
+}
+// a visit's report filed with the gate (the cross-check of the views two turns both held) and the node object's counters
+static void node_file_visit(L* h, TurnGate& G, int r, const l3d::TurnReport& rep, bool share)
+{
+    NodeRanks& N = *h->node;
+    L* R = N.ranks[(size_t)r];
+    ChainPlan* P = get_plan(R);
+    std::lock_guard<std::mutex> lk(G.mu);
+    N.turn_views[(size_t)r] += rep.views_computed;
+    N.turn_visits[(size_t)r] += 1;
+    G.keep[(size_t)r] = rep.held; G.hash[(size_t)r] = rep.hash; G.n_kept[(size_t)r] = rep.n_kept;
+    if (share) {
+        // the records its arena held when the share was built, plus -- as the chain's summary counts them -- the lists of the early-return views it held
+        int64_t recs = rep.arena_records;
+        for (size_t k = 0; P && k < P->n && k < rep.held.size() && k < R->chain_summary.size(); ++k)
+            if (rep.held[k] && P->n_tbm[k] == 0) recs += R->chain_summary[k].n_kept;
+        N.turn_records[(size_t)r] = recs;
+    }
+}
+// compute3Dmodel in turns, every turn computing its own piece of the chain: about one pass of matchViews plus the deferred turns' pieces instead of W passes
+static int node_compute_turns_handover(L* h, int perform_diffusion)
+{
+    NodeRanks& N = *h->node;
+    const int W = (int)N.ranks.size();
+    if (rank0(h)->views.size() < 4) return h->fail(L3D_ERR_INVALID, "not enough images! can't compute 3D model...");   // line3D.cc:347-351
+    N.turn_views.clear(); N.turn_visits.clear();
+    int rc = node_prepare_turns(h);
+    if (rc) return rc;
+    // the schedule is static: which turns are deferred, and whether the partition can take the scene at all, is known before the first turn
+    l3d::TurnSchedule S;
+    const char* why = nullptr;
+    for (int r = 1; r < W; ++r) if (N.devices[(size_t)r] != N.devices[0]) why = "the ranks do not share one device";
+    if (!why) {
+        match_begin(rank0(h));
+        ChainPlan* P = get_plan(rank0(h));
+        if (!P || P->n == 0) why = "the schedule is not static";
+        else if (l3d::turn_handover_schedule(P->cv.data(), (int)P->n, W, 0, &S) || !S.supported) why = "the blocks-of-views partition cannot take its early-return views";
+    }
+    if (why) {
+        if (h->verbose) printf("[L3D] node: no hand-over between the turns on this scene (%s) -- every turn computes the whole chain (plain mode 2)\n", why);
+        return node_compute_turns(h, perform_diffusion, true);
+    }
+    l3d::node_comm_rearm(N.comm);
+    h->chain_summary.clear();
+    N.turn_records.assign((size_t)W, 0);
+    N.turn_views.assign((size_t)W, 0); N.turn_visits.assign((size_t)W, 0);
+    node_drop_handover(N);
+    N.packages.assign((size_t)W, l3d::TurnHandover());
+    TurnGate G(N.devices);
+    std::vector<FillGateUser> gate_user((size_t)W);
+    std::vector<uint32_t> order_ids;
+    std::vector<std::vector<uint64_t>> first_hash((size_t)W);
+    std::vector<std::vector<int32_t>> first_kept((size_t)W);
+    rc = node_run(h, [&](int r) {
+        L* R = N.ranks[(size_t)r];
+        int rc2 = L3D_OK;
+        if (!G.begin_turn(r)) rc2 = R->fail(L3D_ERR_INVALID, "another rank failed in its turn");
+        else {
+            const bool deferred = S.turns[(size_t)r].deferred != 0;
+            l3d::TurnReport rep;
+            rc2 = node_turn_visit(h, r, true, !deferred, rep);
+            if (rc2 == L3D_OK) {
+                node_file_visit(h, G, r, rep, !deferred);
+                first_hash[(size_t)r] = rep.hash; first_kept[(size_t)r] = rep.n_kept;
+                // the package this turn started from is kept only for a second visit
+                if (r > 0 && !deferred) l3d::turn_handover_release(&N.packages[(size_t)r - 1]);
+            }
+            if (r == 0 && rc2 == L3D_OK) order_ids = R->order;          // (read by the last rank to finish, under the gate's lock)
+            // the second visits: under the same token, after the last first visit, before any rank enters a collective -- on this thread, the deferred
+            // ranks' own threads wait for the turns to end
+            for (int q = 0; q < W && r == W - 1 && rc2 == L3D_OK; ++q) {
+                if (!S.turns[(size_t)q].deferred) continue;
+                L* Q = N.ranks[(size_t)q];
+                l3d::TurnReport again;
+                int rcq = node_turn_visit(h, q, false, true, again);
+                if (rcq == L3D_OK && (again.hash != first_hash[(size_t)q] || again.n_kept != first_kept[(size_t)q]))
+                    rcq = Q->fail(L3D_ERR_INVALID, "the second visit of rank " + std::to_string(q) + " did not reproduce the kept lists of its first visit");
+                if (rcq == L3D_OK) { node_file_visit(h, G, q, again, true); if (q > 0) l3d::turn_handover_release(&N.packages[(size_t)q - 1]); }
+                else {
+                    { std::lock_guard<std::mutex> lk(G.mu); G.fail_locked(q, rcq, Q->err); }
+                    rc2 = R->fail(rcq, "the second visit of rank " + std::to_string(q) + " failed: " + Q->err);
+                }
+            }
+            G.end_turn(r, rc2, R->err, order_ids);
+        }
+        // no rank enters the first collective before every turn is over
+        if (rc2 == L3D_OK && !G.wait_all()) rc2 = R->fail(L3D_ERR_INVALID, "another rank failed in its turn");
+        if (rc2 == L3D_OK) {
+            long long n_pot_all = 0;            // (every share is built: the table's entries over all ranks, which no turn could know)
+            for (int q = 0; q < W; ++q) n_pot_all += N.ranks[(size_t)q]->resident_n_pot;
+            l3d::ctx_part_total(R->ctx, n_pot_all);
+            gate_user[(size_t)r] = { &G, r };
+            l3d::ctx_fill_gate(R->ctx, fill_gate_fn, &gate_user[(size_t)r]);
+            l3d::ctx_fill_collective_only(R->ctx, r != 0);
+            rc2 = l3d_line3d_finish_sharded(R, perform_diffusion, l3d_exchange_node, N.comm);
+            if (rc2) G.abort();
+        }
+        // the context is an ordinary rank's again; what a rank other than 0 still holds is nobody's result
+        l3d::ctx_fill_gate(R->ctx, nullptr, nullptr);
+        l3d::ctx_fill_collective_only(R->ctx, 0);
+        R->hyps_done = false;
+        if (r != 0) l3d::ctx_release_share(R->ctx);
+        return rc2;
+    });
+    node_drop_handover(N);
+    if (rc) {
+        N.turn_records.clear(); N.turn_views.clear(); N.turn_visits.clear();
+        if (G.failed_rank >= 0) return h->fail(G.failed_rc, rank_prefix(h, G.failed_rank) + G.failed_msg);
+        return rc;
+    }
+    node_merge_summary(h);
     return L3D_OK;
 }
 
@@ -315,8 +491,8 @@ static int node_compute(L* h, int perform_diffusion)
     NodeRanks& N = *h->node;
     const int W = (int)N.ranks.size();
     if (rank0(h)->views.size() < 4) return h->fail(L3D_ERR_INVALID, "not enough images! can't compute 3D model...");   // line3D.cc:347-351
-    if (N.mode == 2) return node_compute_turns(h, perform_diffusion);
-    N.turn_records.clear();
+    if (N.mode == 2) return N.handover ? node_compute_turns_handover(h, perform_diffusion) : node_compute_turns(h, perform_diffusion);
+    N.turn_records.clear(); N.turn_views.clear(); N.turn_visits.clear();
     int rc = node_run(h, [&](int r) { return prepare(N.ranks[(size_t)r]); });
     if (rc) return rc;
     int s_max = 0;
@@ -347,6 +523,7 @@ static int node_compute(L* h, int perform_diffusion)
 }
 static void node_destroy(L* h)
 {
+    node_drop_handover(*h->node);
     for (L* r : h->node->ranks) l3d_line3d_destroy(r);
     l3d_node_comm_destroy(h->node->comm);
     delete h->node;
@@ -429,6 +606,27 @@ int l3d_line3d_node_turn_records(const l3d_line3d* h, int rank, int64_t* records
     if (!h->node || rank < 0 || rank >= (int)h->node->ranks.size()) return const_cast<L*>(h)->fail(L3D_ERR_INVALID, "node_turn_records: no such rank of a node object");
     if ((int)h->node->turn_records.size() != (int)h->node->ranks.size()) return const_cast<L*>(h)->fail(L3D_ERR_INVALID, "node_turn_records: the last compute3Dmodel did not run in turns (l3d_line3d_set_node_mode 2)");
     *records = h->node->turn_records[(size_t)rank];
+    return L3D_OK;
+}
+
+int l3d_line3d_set_turn_handover(l3d_line3d* h, int on)
+{
+    if (!h) return L3D_ERR_INVALID;
+    if (!h->node) return h->fail(L3D_ERR_INVALID, "set_turn_handover: the turns are those of a node object (l3d_line3d_create_node with more than one rank)");
+    if (on != 0 && on != 1) return h->fail(L3D_ERR_INVALID, "set_turn_handover: 0 (every turn computes the whole chain) or 1 (a turn computes its piece, warm from its predecessor's tail)");
+    h->node->handover = on == 1;
+    return L3D_OK;
+}
+
+int l3d_line3d_node_turn_views(const l3d_line3d* h, int rank, int64_t* views_computed, int* visits)
+{
+    if (!h || !views_computed || !visits) return L3D_ERR_INVALID;
+    *views_computed = 0; *visits = 0;
+    if (!h->node || rank < 0 || rank >= (int)h->node->ranks.size()) return const_cast<L*>(h)->fail(L3D_ERR_INVALID, "node_turn_views: no such rank of a node object");
+    if (h->node->turn_views.size() != h->node->ranks.size() || h->node->turn_visits.size() != h->node->ranks.size())
+        return const_cast<L*>(h)->fail(L3D_ERR_INVALID, "node_turn_views: the last compute3Dmodel did not run in turns (l3d_line3d_set_node_mode 2)");
+    *views_computed = h->node->turn_views[(size_t)rank];
+    *visits = h->node->turn_visits[(size_t)rank];
     return L3D_OK;
 }
 

@@ -77,6 +77,18 @@ class Line3D:
         self._chk(self.lib.l3d_line3d_node_turn_records(self.h, C.c_int(int(rank)), C.byref(n)))
         return int(n.value)
 
+    def set_turn_handover(self, on=True):
+        """node mode 2 with a warm hand-over between the turns (l3d_line3d_set_turn_handover): a turn computes its own piece of the chain from the
+        tail its predecessor left, so matchViews costs between one and two passes instead of len(devices).  No effect unless the node mode is 2;
+        `on` is True / False (or 1 / 0)"""
+        self._chk(self.lib.l3d_line3d_set_turn_handover(self.h, C.c_int(int(on))))
+
+    def node_turn_views(self, rank: int):
+        """after compute3Dmodel in node mode 2: (chain views rank `rank` computed over all its visits, its visits) (l3d_line3d_node_turn_views)"""
+        n, v = C.c_int64(0), C.c_int(0)
+        self._chk(self.lib.l3d_line3d_node_turn_views(self.h, C.c_int(int(rank)), C.byref(n), C.byref(v)))
+        return int(n.value), int(v.value)
+
     def context(self) -> capi.Context:
         """The pipeline's l3d_ctx as a (non-owning) Context, for profiling (refused on a node object: one context per rank)."""
         c = capi.Context.__new__(capi.Context)

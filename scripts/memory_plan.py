@@ -142,11 +142,22 @@ def plan_segpart(V, S, N, W, kept_ratio, chain_world=0):
     return rows, idx, dict(chain_views=V, held_views=held_views, kept_view=kept_view, cand_view=cand_view)
 
 
-def plan_turns(V, S, N, W, kept_ratio):
+def plan_turns(V, S, N, W, kept_ratio, handover=False):
     """the rows of one turn (segpart at chain world 1) re-phased for a device its W ranks share: "turn" = live during the turn's chain and products only
     (released by l3d_chain_release_records), "others" = what the W - 1 other ranks keep on the device across the turns"""
     rows, idx, info = plan_segpart(V, S, N, W, kept_ratio, 1)
     out = []
+    if handover:
+        # l3d_line3d_set_turn_handover: a turn runs the single-GPU chain over its block + tail, warm from `check` views of its predecessor -- block + check + tail
+        # views of records (the same count as the keep set: check = tail = 2 x reach), no ring of slots; the node object holds the packages.
+        # ASSUMED, as everywhere in this script: a helix, reach = N / 2; and blocks longer than check + tail, where turn 0 alone is deferred and two
+        # packages are alive at a time.  With shorter blocks every deferred turn keeps one (l3d_turn_handover_plan says which: 24 views in 8 turns
+        # defer three), and a scene with scattered neighbourhoods has a larger reach (tests/test_gpu_node_handover.py: 12 and more at N = 8)
+        rows = [r for r in rows if not r[1].startswith("send + gathered slots")]
+        reach = N // 2
+        package = 2 * reach * (info["kept_view"] * 32 + S * 12)
+        out.append(("others", "hand-over packages of the node object: the tail for the successor and the one a deferred turn keeps for its second visit (2 x reach = %d views of records, best pairs and positions each; assumes reach = N / 2 and one deferred turn: blocks longer than 4 x reach)" % (2 * reach),
+                    2 * package, "l3d_chain.hip:match_chain_turn (TurnHandover), line3d_host.cpp:node_compute_turns_handover"))
     for phase, name, b, where in rows:
         released = name.startswith("kept arena") or name.startswith("side words") or name.startswith("camera tables")
         out.append(("turn" if phase == "all" and released else phase, name, b, where))
@@ -172,12 +183,16 @@ def main():
     ap.add_argument("--kept", type=float, nargs="+", default=[0.025, 0.25, 0.48])
     ap.add_argument("--mode", default="partition", choices=["partition", "segments", "segpart", "turns"])
     ap.add_argument("--chain-world", type=int, default=0, help="segpart only: the world size the CHAIN runs at (0 = --world); 1 = one rank's share exercised on one GPU")
+    ap.add_argument("--handover", action="store_true", help="turns only: the turns hand the chain over (l3d_line3d_set_turn_handover): no ring of slots, the parked packages")
     ap.add_argument("--rho", type=float, default=0.065, help="stage-1 candidates per segment pair (0.065: config 2; the 2048-view scene measures 0.11)")
     ap.add_argument("--json", action="store_true", help="the plan of the FIRST --kept value as one JSON object (scripts/run_rank_share.py compares it with a measured peak)")
     a = ap.parse_args()
     RHO[0] = a.rho
+    if a.handover and a.mode != "turns":
+        ap.error("--handover belongs to --mode turns")
     fn = dict(partition=plan_partition, segments=plan_segments, segpart=plan_segpart, turns=plan_turns)[a.mode]
-    plans = [fn(a.views, a.segments, a.neighbors, a.world, k, a.chain_world) if a.mode == "segpart" else fn(a.views, a.segments, a.neighbors, a.world, k) for k in a.kept]
+    plans = [fn(a.views, a.segments, a.neighbors, a.world, k, a.chain_world) if a.mode == "segpart" else fn(a.views, a.segments, a.neighbors, a.world, k, True) if a.handover else
+             fn(a.views, a.segments, a.neighbors, a.world, k) for k in a.kept]
     if a.json:
         import json
         p = plans[0]
@@ -191,6 +206,9 @@ def main():
             extra = dict(turn_peak_gb=round(max(phases.values()) / GB, 2), share_rows_gb=round(p[2]["share_rows_bytes"] / GB, 3), scene_copies_gb=round(copies / GB, 3), world=a.world,
                          per_turn_gb=dict(scene=round(p[2]["scene_bytes"] / GB, 3), arena_of_the_keep_set=round(g("turn") / GB, 3), chain_scratch=round(g("chain") / GB, 3)),
                          across_turns_gb=dict(shares_of_rows_and_hypotheses=round(a.world * p[2]["share_rows_bytes"] / GB, 3), one_fill_block=round(g("fill") / GB, 3)))
+            if a.handover:
+                extra["handover"] = True
+                extra["across_turns_gb"]["handover_packages"] = round(sum(r[2] for r in p[0] if r[1].startswith("hand-over packages")) / GB, 3)
             phases = {k: v + copies for k, v in phases.items()}
         print(json.dumps(dict(mode=a.mode, kept=a.kept[0], peak_gb=round(max(phases.values()) / GB, 2), phases_gb={k: round(v / GB, 2) for k, v in phases.items()},
                               rows=[dict(phase=r[0], what=r[1], gb=round(r[2] / GB, 3)) for r in p[0]], fields={k: float(v) for k, v in p[1].items()}, **extra)))
