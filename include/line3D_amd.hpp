@@ -1,8 +1,9 @@
 // line3D_amd.hpp -- C++ facade with the reference's public interface (class L3D::Line3D, line3D.h:61-101)
 // over the C ABI of include/line3d_amd.h.  Same method names, argument order and defaults (commons.h:42-61).
 // addImage / addImage_fixed_sim come in two families: (1) the reference's own signatures -- `image` (anything with .cols / .rows: cv::Mat),
-// K, R, t matrix-typed (anything with K(i, j) / t(i): Eigen's) -- whose segments come from the segment cache of the data directory, the
-// reference's own side door for precomputed segments (line3D.cc:143-168); (2) width, height and the segments the detector would have
+// K, R, t matrix-typed (anything with K(i, j) / t(i): Eigen's) -- whose segments are detected on the device from the image's pixels when
+// the image type carries them (.data / .step / .channels(), cv::Mat itself) and otherwise come from the segment cache of the data directory,
+// the reference's own side door for precomputed segments (line3D.cc:143-168); (2) width, height and the segments the detector would have
 // produced (std::vector<float4>, the side door of L3DSegments(list<float4>&, bool), segments.h:60), cameras as plain row-major arrays or
 // matrix types.  Neither OpenCV nor Eigen is needed to compile this header.
 #pragma once
@@ -24,6 +25,11 @@ namespace L3D {
 struct float4 { float x, y, z, w; };      // the reference gets this type from the CUDA headers
 #endif
 typedef std::array<double, 3> Vec3d;
+
+namespace detail {
+template <int N> struct prio : prio<N - 1> {};      // overload ranking: prio<1> is tried before prio<0>
+template <> struct prio<0> {};
+}  // namespace detail
 
 // commons.h:81-99
 class L3DSegment2D {
@@ -101,7 +107,7 @@ public:
                                        K, R, t, wps.data(), (int)wps.size(), data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0));
     }
     // addImage when "<data_directory>/segments_<id>_<w>x<h>_coll<0|1>.bin" of an earlier run exists (line3D.cc:143-168):
-    // the file's segments and collinearities stand in for the image (the detector is not part of this library).
+    // the file's segments and collinearities stand in for the image (no pixels are needed).
     // false: no such file, or it is not a segment cache (message printed)
     bool addImageFromCache(const unsigned int imageID, const unsigned int width, const unsigned int height,
                            const double K[9], const double R[9], const double t[3], std::list<unsigned int>& worldpointIDs)
@@ -150,11 +156,15 @@ public:
     }
     // The reference's OWN signatures (line3D.h:69-79): `image` as the second parameter -- cv::Mat in the reference, here any type with
     // `.cols` / `.rows` (cv::Mat itself when OpenCV is there; OpenCV is not a dependency of this header), K / R / t matrix-typed as above.
-    // main_vsfm.cpp:273 / main_bundler.cpp:287 compile against these unchanged.  The image gives the view its size; its PIXELS are not read:
-    // line-segment detection is not part of this library, so the segments come from the reference's side door, the segment cache
-    // "<data_directory>/segments_<id>_<w'>x<h'>_coll<0|1>.bin" of an earlier run (w' x h' after the maxImgWidth rule, line3D.cc:130-150).
-    // No such file: the error is printed and the call returns without a view (where the reference would run LSD, line3D.cc:169-190).
-    // loadAndStoreSegments = false removes the file like the reference does (line3D.cc:153-156) -- and then there is nothing to add.
+    // main_vsfm.cpp:273 / main_bundler.cpp:287 compile against these unchanged.
+    //   * An image type that also has `.data` (8-bit pixels), `.step` (bytes per row) and `.channels()` (1 or 3) -- cv::Mat -- takes the
+    //     reference's path (line3D.cc:143-191, l3d_line3d_add_image_pixels): the segment cache is loaded when it is there and
+    //     loadAndStoreSegments is set; otherwise the segments are detected on the device from the pixels, and the cache is written, or a
+    //     stale one removed.  An image without segments adds no view.
+    //   * A type with only `.cols` / `.rows` gives the view its size and nothing else: the segments come from the segment cache
+    //     "<data_directory>/segments_<id>_<w'>x<h'>_coll<0|1>.bin" of an earlier run (w' x h' after the maxImgWidth rule, line3D.cc:130-150).
+    //     No such file: the error is printed and the call returns without a view.  loadAndStoreSegments = false removes the file like the
+    //     reference does (line3D.cc:153-156) -- and then there is nothing to add.
     template <class Img, class M3, class V3, class = decltype(std::declval<const Img&>().cols), class = decltype(std::declval<const Img&>().rows),
               class = decltype(std::declval<const M3&>()(0, 0)), class = decltype(std::declval<const V3&>()(0))>
     void addImage(const unsigned int imageID, const Img& image, const M3& K, const M3& R, const V3& t, std::list<unsigned int>& worldpointIDs,
@@ -162,10 +172,8 @@ public:
     {
         double k[9], r[9], tt[3];
         flatten(K, R, t, k, r, tt);
-        const unsigned int w = image.cols > 0 ? (unsigned int)image.cols : 0u, h = image.rows > 0 ? (unsigned int)image.rows : 0u;
         std::vector<uint32_t> wps(worldpointIDs.begin(), worldpointIDs.end());
-        report(l3d_line3d_add_image_ex(h_, imageID, w, h, nullptr, 0, k, r, tt, wps.data(), (int)wps.size(), data_directory_.c_str(), maxImgWidth,
-                                       loadAndStoreSegments ? 1 : 0));
+        report(add_from_image(detail::prio<1>(), imageID, image, k, r, tt, wps.data(), nullptr, (int)wps.size(), maxImgWidth, loadAndStoreSegments));
     }
     template <class Img, class M3, class V3, class = decltype(std::declval<const Img&>().cols), class = decltype(std::declval<const Img&>().rows),
               class = decltype(std::declval<const M3&>()(0, 0)), class = decltype(std::declval<const V3&>()(0))>
@@ -174,12 +182,11 @@ public:
     {
         double k[9], r[9], tt[3];
         flatten(K, R, t, k, r, tt);
-        const unsigned int w = image.cols > 0 ? (unsigned int)image.cols : 0u, h = image.rows > 0 ? (unsigned int)image.rows : 0u;
         std::vector<uint32_t> ids;
         std::vector<float> sims;
         for (auto& kv : viewSimilarity) { ids.push_back(kv.first); sims.push_back(kv.second); }
-        report(l3d_line3d_add_image_fixed_sim_ex(h_, imageID, w, h, nullptr, 0, k, r, tt, ids.data(), sims.data(), (int)ids.size(), data_directory_.c_str(),
-                                                 maxImgWidth, loadAndStoreSegments ? 1 : 0));
+        sims.push_back(0.0f);       // (never null: `sims` tells the two kinds of links apart)
+        report(add_from_image(detail::prio<1>(), imageID, image, k, r, tt, ids.data(), sims.data(), (int)ids.size(), maxImgWidth, loadAndStoreSegments));
     }
     // line3D.h:82
     void compute3Dmodel(bool perform_diffusion = false) { report(l3d_line3d_compute3Dmodel(h_, perform_diffusion ? 1 : 0)); }
@@ -254,6 +261,27 @@ private:
     template <class M3, class V3> static void flatten(const M3& K, const M3& R, const V3& t, double* k, double* r, double* tt)
     {
         for (int i = 0; i < 3; ++i) { tt[i] = t(i); for (int j = 0; j < 3; ++j) { k[i * 3 + j] = K(i, j); r[i * 3 + j] = R(i, j); } }
+    }
+    // `image` with pixels (cv::Mat: .data, .step, .channels()): detect on the device.  links: world point ids (sims == nullptr) or view similarities
+    template <class Img, class = decltype(static_cast<const unsigned char*>(std::declval<const Img&>().data)),
+              class = decltype(static_cast<size_t>(std::declval<const Img&>().step)), class = decltype(static_cast<int>(std::declval<const Img&>().channels()))>
+    int add_from_image(detail::prio<1>, unsigned int imageID, const Img& image, const double* k, const double* r, const double* tt, const uint32_t* ids,
+                       const float* sims, int n, int maxImgWidth, bool loadAndStoreSegments)
+    {
+        const unsigned char* px = static_cast<const unsigned char*>(image.data);
+        const size_t step = static_cast<size_t>(image.step);
+        const int ch = static_cast<int>(image.channels()), w = (int)image.cols, h = (int)image.rows;
+        if (sims) return l3d_line3d_add_image_pixels_fixed_sim(h_, imageID, px, w, h, ch, step, k, r, tt, ids, sims, n, data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0);
+        return l3d_line3d_add_image_pixels(h_, imageID, px, w, h, ch, step, k, r, tt, ids, n, data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0);
+    }
+    // `image` with a size only: the segment cache or nothing
+    template <class Img>
+    int add_from_image(detail::prio<0>, unsigned int imageID, const Img& image, const double* k, const double* r, const double* tt, const uint32_t* ids,
+                       const float* sims, int n, int maxImgWidth, bool loadAndStoreSegments)
+    {
+        const unsigned int w = image.cols > 0 ? (unsigned int)image.cols : 0u, h = image.rows > 0 ? (unsigned int)image.rows : 0u;
+        if (sims) return l3d_line3d_add_image_fixed_sim_ex(h_, imageID, w, h, nullptr, 0, k, r, tt, ids, sims, n, data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0);
+        return l3d_line3d_add_image_ex(h_, imageID, w, h, nullptr, 0, k, r, tt, ids, n, data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0);
     }
     void report(int rc) { if (rc != L3D_OK) std::cerr << prefix_ << l3d_line3d_last_error(h_) << std::endl; }
     l3d_line3d* h_;

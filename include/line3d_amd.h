@@ -512,8 +512,9 @@ int l3d_test_sq_threshold(l3d_ctx* ctx, const float* u, int n, float* out_walk, 
  * Host pipeline behind the reference's public operator interface, class L3D::Line3D
  * (line3D.h:61-101): the same calls, argument meaning and error behaviour, with plain arrays in
  * place of cv::Mat / Eigen / std::list.  include/line3D_amd.hpp wraps these in a C++ class named
- * L3D::Line3D.  Images are replaced by their detected segments (the LSD front end is out of
- * scope): `segments` is what detectLineSegments would have produced (line3D.cc:1789-1871).
+ * L3D::Line3D.  Images are replaced by their detected segments: `segments` is what
+ * detectLineSegments would have produced (line3D.cc:1789-1871); l3d_line3d_add_image_pixels (below)
+ * takes the pixels and detects them on the device.
  * K, R (3x3 row-major) and t are doubles like the reference's Eigen arguments.
  * ================================================================================================= */
 typedef struct l3d_line3d l3d_line3d;
@@ -660,7 +661,8 @@ int l3d_line3d_stats(const l3d_line3d* h, double* stats12);
 /* =================================================================================================
  * SfM front ends of the reference's drivers: VisualSfM NVM (main_vsfm.cpp:121-223) and bundler
  * bundle.rd.out (main_bundler.cpp:110-204), reduced to what feeds Line3D::addImage -- focal length, R, t, distortion
- * coefficients, observed world point ids per camera.  Image decoding / undistortion / LSD stay outside.
+ * coefficients, observed world point ids per camera.  Image decoding / undistortion stay outside (line segment
+ * detection: l3d_detect_segments below).
  * A failed read still returns a scene object carrying the message (l3d_sfm_last_error); free it with l3d_sfm_free.
  * ================================================================================================= */
 typedef struct l3d_sfm_scene l3d_sfm_scene;
@@ -707,7 +709,8 @@ int l3d_line3d_add_image_cached(l3d_line3d* h, uint32_t image_id, unsigned width
  *   file exists, load_and_store != 0   segments AND collinearities come from the file, `segments` are ignored (:159-168)
  *   otherwise                          `segments` are used; with load_and_store != 0 the cache is written (:180-182) -- at
  *                                      prepare(), when the collinearities of all new views have been computed in one batch
- * `segments` is what detectLineSegments (line3D.cc:1789-1871: LSD, length filter, longest 3000) would have produced.
+ * `segments` is what detectLineSegments (line3D.cc:1789-1871: LSD, length filter, longest 3000) would have produced, e.g. by
+ * l3d_detect_segments; l3d_line3d_add_image_pixels does both steps.
  * links: observed world point ids (add_image_ex) or (view id, similarity) pairs (add_image_fixed_sim_ex). */
 int l3d_line3d_add_image_ex(l3d_line3d* h, uint32_t image_id, unsigned width, unsigned height, const float* segments, int n_segments,
                             const double* K, const double* R, const double* t, const uint32_t* worldpoint_ids, int n_worldpoints,
@@ -715,6 +718,41 @@ int l3d_line3d_add_image_ex(l3d_line3d* h, uint32_t image_id, unsigned width, un
 int l3d_line3d_add_image_fixed_sim_ex(l3d_line3d* h, uint32_t image_id, unsigned width, unsigned height, const float* segments, int n_segments,
                                       const double* K, const double* R, const double* t, const uint32_t* sim_ids, const float* sims, int n_sims,
                                       const char* data_directory, int max_img_width, int load_and_store);
+
+/* =================================================================================================
+ * Line segment detection on the device (line3d_amd/csrc/l3d_detect.hip): what Line3D::detectLineSegments (line3D.cc:1789-1871)
+ * does with the LSD detector (scale 0.8, sigma_scale 0.6, quant 2, ang_th 22.5 deg, log_eps 0, density_th 0.7).
+ *   pixels      8-bit, `channels` = 1 or 3 interleaved, rows `row_stride` bytes apart (>= width x channels)
+ *   rescale     when (new_width, new_height) differs from (width, height) (0, 0 = no rescale): bilinear, half-pixel centres, 8-bit
+ *               weights.  Per axis, output index i of n_out from n_in samples: num = max((2 i + 1) n_in - n_out, 0), den = 2 n_out,
+ *               i0 = num / den, a = ((num % den) 256 + den / 2) / den, and i0 = n_in - 1, a = 0 at the last sample; per channel
+ *               v = ((256-a)(256-b) p00 + a (256-b) p01 + (256-a) b p10 + a b p11 + 32768) >> 16.  Output coordinates are multiplied by
+ *               upscale_factor = 1 / (0.5 (new_width / width + new_height / height)) (float): they are original-image pixels
+ *   grey        3 channels, the way CV_RGB2GRAY sees the buffer: (299 c0 + 587 c1 + 114 c2 + 500) / 1000 (integers).  Parity with
+ *               OpenCV's fixed-point resize / convert is NOT claimed
+ *   detection   Gaussian sub-sampling, 2x2 gradient, level-line angle, line-support regions, rectangle by gradient-weighted
+ *               moments, density check, NFA with logNT = 5/2 (log10 X + log10 Y) + log10 11, output offset + 0.5, / scale.
+ *               The reference's region growing is a sequential greedy loop; the regions here are formed in parallel, without a seed
+ *               order.  The result AGREES with the reference detector (recall and precision pooled over the golden images are
+ *               held to the reference's own worst single-image repeatability under redrawn noise, tests/test_gpu_detect.py);
+ *               it is not identical to it.  It is deterministic: the same pixels give the same bytes
+ *   selection   length > min_length, length descending (ties: smallest pixel index of the region), at most max_segments
+ * Out (callee-allocated, l3d_free): 4 floats (x1, y1, x2, y2) per segment; *n = 0 when nothing is found.
+ * Images below 8x8, channels other than 1 or 3, a stride below width x channels: L3D_ERR_INVALID.
+ * Still outside the library: image decoding (JPEG / PNG), undistortion, the tclap command lines of the drivers.
+ * ================================================================================================= */
+int l3d_detect_segments(l3d_ctx* ctx, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, int new_width, int new_height,
+                        float min_length, int max_segments, float** segments, int* n);
+/* Line3D::addImage / addImage_fixed_sim from pixels (line3D.cc:95-217, 220-324): cache present and load_and_store != 0: the cache is
+ * loaded; otherwise the segments are detected (rescaled by the max_img_width rule, min_length = 0.005 sqrt(rows^2 + cols^2), at most 3000) and,
+ * with load_and_store != 0, the cache is written; load_and_store == 0 removes a stale cache first.  No segment found: L3D_OK and no view
+ * (line3D.cc:186-190).  On a node object the segments are detected once, on rank 0's device. */
+int l3d_line3d_add_image_pixels(l3d_line3d* h, uint32_t image_id, const unsigned char* pixels, int width, int height, int channels, size_t row_stride,
+                                const double* K, const double* R, const double* t, const uint32_t* worldpoint_ids, int n_worldpoints,
+                                const char* data_directory, int max_img_width, int load_and_store);
+int l3d_line3d_add_image_pixels_fixed_sim(l3d_line3d* h, uint32_t image_id, const unsigned char* pixels, int width, int height, int channels, size_t row_stride,
+                                          const double* K, const double* R, const double* t, const uint32_t* sim_ids, const float* sims, int n_sims,
+                                          const char* data_directory, int max_img_width, int load_and_store);
 
 #ifdef __cplusplus
 }

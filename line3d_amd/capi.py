@@ -70,6 +70,21 @@ def _p(a, t=C.c_void_p):
     return a.ctypes.data_as(t)
 
 
+def image_arguments(img):
+    """uint8 array H x W or H x W x C -> (pointer, width, height, channels, row stride in bytes) for the pixel-taking calls; an array whose
+    pixels are not contiguous within a row is copied.  The pointer refers to `img` (or the copy, kept alive on the returned object)."""
+    a = np.asarray(img)
+    if a.dtype != np.uint8 or a.ndim not in (2, 3):
+        raise TypeError("image must be a uint8 array H x W or H x W x C")
+    ch = 1 if a.ndim == 2 else a.shape[2]
+    inner_ok = a.strides[1] == ch and (a.ndim == 2 or a.strides[2] == 1)
+    if not inner_ok or a.strides[0] < a.shape[1] * ch:
+        a = np.ascontiguousarray(a)
+    ptr = C.c_void_p(a.ctypes.data)
+    ptr._keep = a
+    return ptr, int(a.shape[1]), int(a.shape[0]), int(ch), int(a.strides[0])
+
+
 class AffinityInput(C.Structure):
     """l3d_affinity_input (include/line3d_amd.h)"""
     _fields_ = [("n_views", C.c_int32), ("seg_base", C.c_void_p), ("view_hyp_begin", C.c_void_p), ("n_hyp", C.c_int32),
@@ -161,6 +176,22 @@ class Context:
         assert segs.dtype == np.float32 and segs.flags.c_contiguous
         self._keep.append(segs)
         self._chk(self.lib.l3d_register_segments(self.h, _p(segs), C.c_int(len(segs))))
+
+    # -- line segment detection (l3d_detect.hip) --------------------------------------------------
+    def detect_segments(self, img, new_size=None, min_length=None, max_segments=3000):
+        """l3d_detect_segments: uint8 image H x W or H x W x 3 (contiguous pixels, rows contiguous or strided) -> (n, 4) float32 segments
+        (x1, y1, x2, y2) in pixels of `img`, longest first.  new_size = (width, height) the detector works at (None: the image's own);
+        min_length None: the reference's 0.005 x the image diagonal."""
+        pix, w, h, ch, stride = image_arguments(img)
+        nw, nh = (w, h) if new_size is None else (int(new_size[0]), int(new_size[1]))
+        if min_length is None:
+            min_length = float(np.float32(0.005) * np.sqrt(np.float32(h * h + w * w)))
+        out, n = C.POINTER(C.c_float)(), C.c_int(0)
+        self._chk(self.lib.l3d_detect_segments(self.h, pix, C.c_int(w), C.c_int(h), C.c_int(ch), C.c_size_t(stride), C.c_int(nw), C.c_int(nh),
+                                               C.c_float(min_length), C.c_int(int(max_segments)), C.byref(out), C.byref(n)))
+        segs = np.ctypeslib.as_array(out, (n.value, 4)).copy() if n.value else np.zeros((0, 4), np.float32)
+        self.lib.l3d_free(out)
+        return segs
 
     # -- the three seam functions ---------------------------------------------------------------
     def compute_collinearity(self, segs, collin_s=2.0):

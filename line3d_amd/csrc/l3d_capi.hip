@@ -155,6 +155,7 @@ void l3d_ctx_destroy(l3d_ctx* c)
     for (auto* b : bufs) b->release();
     c->ch_bestpos.release(); c->ch_hdr.release();
     c->products.release();
+    c->det.release();
     c->pin_tab.release(); c->pin_ex.release(); c->pin_scal.release(); c->pin_best.release(); c->pin_kept.release();
     c->ch_pin_tables.release(); c->ch_pin_res.release(); c->ch_pin_kept.release(); c->ch_pin_best.release(); c->pin_arena.release();
     for (auto& kv : c->resident) if (!c->resident_arena_of.count(kv.first)) (void)hipFree(kv.second.first);

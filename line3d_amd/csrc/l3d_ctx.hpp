@@ -135,6 +135,18 @@ struct Products {
 // its own sources' targets only in part
 struct FillPart { int h0 = 0, h1 = 0; unsigned long long pos_base = 0; const int* loc2glob = nullptr; int assume_symmetric = 0; };     // loc2glob: device, global number of every local hypothesis
 
+// scratch of the line segment detector (l3d_detect.hip): sized to the largest image seen, reused across calls
+struct DetectBufs {
+    DevBuf pixels, grey, aux, img, mod, ang, bucket, active, parent, size, count, keys, keys2, vals, vals2, flag, pos, start, tmp, cand, ckeys, ckeys2, cvals, cvals2, out, ktab, scal;
+    int tab_w = 0, tab_h = 0;       // the image size the Gaussian sampler's tables in `ktab` were made for
+    void release()
+    {
+        DevBuf* b[] = { &pixels, &grey, &aux, &img, &mod, &ang, &bucket, &active, &parent, &size, &count, &keys, &keys2, &vals, &vals2, &flag, &pos, &start, &tmp, &cand, &ckeys, &ckeys2, &cvals, &cvals2, &out, &ktab, &scal };
+        for (DevBuf* x : b) x->release();
+        tab_w = tab_h = 0;
+    }
+};
+
 struct ProfEntry {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
     int64_t launches = 0;
@@ -162,6 +174,7 @@ struct l3d_ctx {
     l3d::DevBuf ch_hdr;                      // sharded run, ring mode: per-view arena offsets, header table, flags
     l3d::DevBuf ch_bestpos;                  // per segment of every view: position of its best kept match in the view's slice (resident runs)
     l3d::Products products;
+    l3d::DetectBufs det;                     // line segment detector (l3d_detect.hip)
     std::vector<l3d::RayJob> ray_jobs;       // job list of k_tgt_rays of the running chain
     l3d::PinArena pin_arena;                 // kept lists of the running / last chain (valid until the next chain starts)
     std::vector<int> h_cnt;

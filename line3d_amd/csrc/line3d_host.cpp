@@ -2,6 +2,7 @@
 // (addImage / addImage_fixed_sim / compute3Dmodel / getResult, line3D.h) over the host pipeline in line3d_host_views.cpp (views, seam path),
 // line3d_host_chain.cpp (resident matchViews) and line3d_host_finish.cpp (selection, affinity, diffusion, clustering, fit).
 #include "line3d_host_internal.hpp"
+#include "l3d_detect.hpp"
 #include "l3d_node.hpp"
 #include "l3d_turns.hpp"
 
@@ -776,7 +777,7 @@ int l3d_line3d_add_image_ex(l3d_line3d* h, uint32_t id, unsigned width, unsigned
     const int from_cache = add_from_cache_or_plan_write(h, id, width, height, K, R, t, data_directory, max_img_width, load_and_store, cache_path, &expected);
     if (from_cache < 0) return -from_cache;
     if (!from_cache) {
-        // the image-typed overloads of the facade bring no segments: where the reference would detect them (line3D.cc:169-190) this library stops
+        // a size-only image type of the facade brings neither segments nor pixels (pixels: l3d_line3d_add_image_pixels): nothing to add
         if (n <= 0 || !segs)
             return h->fail(L3D_ERR_INVALID, ("image [" + std::to_string(id) + "]: no segment cache " + expected + " and no segments given -- line segment "
                                              "detection is not part of this library (run the reference once with loadAndStoreSegments, or pass the segments)").c_str());
@@ -808,7 +809,7 @@ int l3d_line3d_add_image_fixed_sim_ex(l3d_line3d* h, uint32_t id, unsigned width
     const int from_cache = add_from_cache_or_plan_write(h, id, width, height, K, R, t, data_directory, max_img_width, load_and_store, cache_path, &expected);
     if (from_cache < 0) return -from_cache;
     if (!from_cache) {
-        // the image-typed overloads of the facade bring no segments: where the reference would detect them (line3D.cc:169-190) this library stops
+        // a size-only image type of the facade brings neither segments nor pixels (pixels: l3d_line3d_add_image_pixels): nothing to add
         if (n <= 0 || !segs)
             return h->fail(L3D_ERR_INVALID, ("image [" + std::to_string(id) + "]: no segment cache " + expected + " and no segments given -- line segment "
                                              "detection is not part of this library (run the reference once with loadAndStoreSegments, or pass the segments)").c_str());
@@ -819,6 +820,56 @@ int l3d_line3d_add_image_fixed_sim_ex(l3d_line3d* h, uint32_t id, unsigned width
     for (int i = 0; i < n_sims; ++i)                       // setViewSimilarity, :1938-1946
         if (sims[i] > 0.01f) h->view_similarities[id][sim_ids[i]] = sims[i];
     return L3D_OK;
+}
+
+// addImage / addImage_fixed_sim from pixels, line3D.cc:128-191: the cache decides first; without a usable cache the segments are detected on the
+// device and enter the calls above.  Returns 1: go on with `segs` (possibly none: the cache will be loaded), 0: no segment found, no view; < 0: error negated
+static int detect_for_add(l3d_line3d* h, uint32_t id, const unsigned char* pixels, int width, int height, int channels, size_t row_stride,
+                          const char* data_directory, int max_img_width, int load_and_store, std::vector<float>& segs)
+{
+    segs.clear();
+    L* owner = h->node ? rank0(h) : h;
+    if (width <= 0 || height <= 0) return -h->fail(L3D_ERR_INVALID, "image is empty!");
+    unsigned new_w = (unsigned)width, new_h = (unsigned)height;
+    if (max_img_width > 0 && std::max(width, height) > max_img_width) {                      // :133-138
+        const float scale = float(max_img_width) / fmaxf((float)height, (float)width);
+        new_w = (unsigned)roundf(float(width) * scale);
+        new_h = (unsigned)roundf(float(height) * scale);
+    }
+    char name[160];
+    if (l3d_segment_cache_filename(id, new_w, new_h, owner->use_collinearity ? 1 : 0, name, sizeof(name)) != L3D_OK) return -L3D_ERR_INVALID;
+    const std::string file = std::string(data_directory ? data_directory : "") + name;
+    FILE* f = fopen(file.c_str(), "rb");
+    if (f) { fclose(f); if (load_and_store) return 1; }                                     // :159-168: the cache stands in for the image
+    if (!owner->ctx) return -h->fail(L3D_ERR_INVALID, "no device context to detect line segments with");
+    const float min_length = 0.005f * sqrtf(float(height * height + width * width));         // :176, commons.h:43
+    const int rc = l3d::detect_segments(owner->ctx, pixels, width, height, channels, row_stride, (int)new_w, (int)new_h, min_length, 3000, segs);
+    if (rc != L3D_OK) return -h->fail(rc, l3d_last_error(owner->ctx));
+    if (segs.empty()) { if (f && !load_and_store) remove(file.c_str()); return 0; }          // :153-156, :186-190
+    return 1;
+}
+
+int l3d_line3d_add_image_pixels(l3d_line3d* h, uint32_t id, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, const double* K,
+                                const double* R, const double* t, const uint32_t* worldpoints, int n_wps, const char* data_directory, int max_img_width, int load_and_store)
+{
+    if (!h) return L3D_ERR_INVALID;
+    std::vector<float> segs;
+    const int go = detect_for_add(h, id, pixels, width, height, channels, row_stride, data_directory, max_img_width, load_and_store, segs);
+    if (go <= 0) return -go;
+    return l3d_line3d_add_image_ex(h, id, (unsigned)width, (unsigned)height, segs.empty() ? nullptr : segs.data(), (int)(segs.size() / 4), K, R, t, worldpoints, n_wps,
+                                   data_directory, max_img_width, load_and_store);
+}
+
+int l3d_line3d_add_image_pixels_fixed_sim(l3d_line3d* h, uint32_t id, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, const double* K,
+                                          const double* R, const double* t, const uint32_t* sim_ids, const float* sims, int n_sims, const char* data_directory,
+                                          int max_img_width, int load_and_store)
+{
+    if (!h) return L3D_ERR_INVALID;
+    std::vector<float> segs;
+    const int go = detect_for_add(h, id, pixels, width, height, channels, row_stride, data_directory, max_img_width, load_and_store, segs);
+    if (go <= 0) return -go;
+    return l3d_line3d_add_image_fixed_sim_ex(h, id, (unsigned)width, (unsigned)height, segs.empty() ? nullptr : segs.data(), (int)(segs.size() / 4), K, R, t, sim_ids, sims,
+                                             n_sims, data_directory, max_img_width, load_and_store);
 }
 
 int l3d_line3d_num_cameras(const l3d_line3d* h) { return !h ? 0 : h->node ? l3d_line3d_num_cameras(rank0(h)) : (int)h->views.size(); }

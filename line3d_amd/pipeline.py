@@ -142,6 +142,29 @@ class Line3D:
                                                   C.c_int(int(loadAndStoreSegments)))
         return rc == 0
 
+    def add_image_pixels(self, imageID, img, K, R, t, worldpointIDs, maxImgWidth=1920, loadAndStoreSegments=True):
+        """Line3D::addImage from pixels (l3d_line3d_add_image_pixels): uint8 image H x W or H x W x 3.  The segment cache in `data_directory` is
+        loaded when present (and loadAndStoreSegments); otherwise the segments are detected on the device, and the cache written or a stale one
+        removed.  An image without segments adds no view and is no error (line3D.cc:186-190)."""
+        pix, w, h, ch, stride = capi.image_arguments(img)
+        K, R, t = (np.ascontiguousarray(a, dtype=np.float64) for a in (K, R, t))
+        wps = np.ascontiguousarray(list(worldpointIDs), dtype=np.uint32)
+        rc = self.lib.l3d_line3d_add_image_pixels(self.h, C.c_uint32(imageID), pix, C.c_int(w), C.c_int(h), C.c_int(ch), C.c_size_t(stride), _p(K), _p(R), _p(t),
+                                                  _p(wps), C.c_int(len(wps)), C.c_char_p(self.data_directory.encode()), C.c_int(maxImgWidth),
+                                                  C.c_int(int(loadAndStoreSegments)))
+        return rc == 0
+
+    def add_image_pixels_fixed_sim(self, imageID, img, K, R, t, viewSimilarity, maxImgWidth=1920, loadAndStoreSegments=True):
+        """Line3D::addImage_fixed_sim from pixels (l3d_line3d_add_image_pixels_fixed_sim)"""
+        pix, w, h, ch, stride = capi.image_arguments(img)
+        K, R, t = (np.ascontiguousarray(a, dtype=np.float64) for a in (K, R, t))
+        ids = np.ascontiguousarray(sorted(viewSimilarity), dtype=np.uint32)
+        sims = np.ascontiguousarray([viewSimilarity[int(i)] for i in ids], dtype=np.float32)
+        rc = self.lib.l3d_line3d_add_image_pixels_fixed_sim(self.h, C.c_uint32(imageID), pix, C.c_int(w), C.c_int(h), C.c_int(ch), C.c_size_t(stride), _p(K), _p(R),
+                                                            _p(t), _p(ids), _p(sims), C.c_int(len(ids)), C.c_char_p(self.data_directory.encode()),
+                                                            C.c_int(maxImgWidth), C.c_int(int(loadAndStoreSegments)))
+        return rc == 0
+
     def addImage_fixed_sim(self, imageID, width, height, segments, K, R, t, viewSimilarity):
         segs = np.ascontiguousarray(segments, dtype=np.float32).reshape(-1, 4)
         K, R, t = (np.ascontiguousarray(a, dtype=np.float64) for a in (K, R, t))

@@ -91,7 +91,7 @@ def reconstruct(scene: SfmScene, segments, image_sizes, out_dir=None, neighbors=
         if isinstance(segments, (str, os.PathLike)):
             path = os.fspath(segments) + segment_cache_filename(i, w, h, line3d_kwargs.get("useCollinearity", True))
             if not os.path.exists(path):
-                raise RuntimeError("no segment cache %s (the detector is out of scope: segments must come from a cache or the caller)" % path)
+                raise RuntimeError("no segment cache %s (this flow reads no image files: segments come from a cache or the caller; pixels go through Line3D.add_image_pixels)" % path)
             l3d.addImage_cached(i, w, h, path, intrinsics(cam["focal"], w, h), cam["R"], cam["t"], cam["worldpoints"])
             continue
         l3d.addImage(i, w, h, segments[i], intrinsics(cam["focal"], w, h), cam["R"], cam["t"], cam["worldpoints"])
