@@ -754,6 +754,34 @@ int l3d_line3d_add_image_pixels_fixed_sim(l3d_line3d* h, uint32_t image_id, cons
                                           const double* K, const double* R, const double* t, const uint32_t* sim_ids, const float* sims, int n_sims,
                                           const char* data_directory, int max_img_width, int load_and_store);
 
+
+/* The detector's stages on their own, exported for tests (tests/test_gpu_detect_stages.py): the same kernels with the same launch shapes
+ * as l3d_detect_segments, results copied to caller-allocated arrays.  (N, M) = (ceil(0.8 new_width), ceil(0.8 new_height)) is the scaled image.
+ *   pixel stage   grey[new_width x new_height] after rescale + grey; img / mod / ang [N x M]: the Gaussian sampler's output, the 2x2 gradient's
+ *                 modulus and the level-line angle (-1024 = not defined); bucket[2 N M]: per pixel the angle's bucket in partition 0 and in
+ *                 partition 1 (255 = none)
+ *   label         bucket as above, active[N M] (0 / 1) -> parent[2 N M]: per partition the smallest pixel index of the pixel's component
+ *                 (-1 for an inactive pixel); key[N M]: the region the pixel votes for, partition x N M + root, 2 N M for none
+ *   regions       the region kernel on a given labelling (key as above) with every pixel active before it: one record per region of at
+ *                 least min_reg (>= 2) pixels, in ascending key order (callee-allocated, l3d_free), and the active map afterwards
+ *   nfa           -log10 NFA of (n[i], k[i], p[i]) as the region kernel computes it */
+typedef struct {
+    uint32_t minpix;                    /* smallest pixel index among the pixels used */
+    int32_t n_used, steps;              /* pixels within the last radius; shrink steps taken (0: the whole region) */
+    int32_t pts, alg;                   /* points in / aligned with the final rectangle */
+    int32_t scored, accepted;           /* density reached 0.7 and the rectangle was scored; it passed */
+    int32_t pad;
+    int32_t hist_n[8];                  /* pixels within the radius at steps 0..7 (0: step not reached) */
+    double cx, cy, x1, y1, x2, y2, width, theta, density;  /* the rectangle from the moments, scaled-image coordinates (before + 0.5, / 0.8) */
+    double fx1, fy1, fx2, fy2, fwidth, p, nfa;              /* the rectangle, probability and value after the retries */
+} l3d_detect_region_record;
+int l3d_test_detect_pixel_stage(l3d_ctx* ctx, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, int new_width, int new_height,
+                                float* grey, double* img, double* mod, double* ang, unsigned char* bucket, int* N, int* M);
+int l3d_test_detect_label(l3d_ctx* ctx, const unsigned char* bucket, const unsigned char* active, int N, int M, int32_t* parent, uint32_t* key);
+int l3d_test_detect_regions(l3d_ctx* ctx, int N, int M, const double* mod, const double* ang, const uint32_t* key, int min_reg,
+                            l3d_detect_region_record** rec, int* n_rec, unsigned char* active_out);
+int l3d_test_detect_nfa(l3d_ctx* ctx, const int32_t* n, const int32_t* k, const double* p, double logNT, int count, double* out);
+
 #ifdef __cplusplus
 }
 #endif

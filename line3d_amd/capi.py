@@ -18,7 +18,10 @@ EDGE_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("w", "<f4")])
 HYP_DTYPE = np.dtype([("P1", "<f8", (3,)), ("P2", "<f8", (3,)), ("dir", "<f8", (3,)),
                       ("depth_p1", "<f4"), ("depth_p2", "<f4"),
                       ("k_lower", "<f4"), ("k_upper", "<f4"), ("median_depth", "<f4"), ("pad", "<u4")])
-assert MATCH_DTYPE.itemsize == 32 and EDGE_DTYPE.itemsize == 12 and HYP_DTYPE.itemsize == 96
+REGION_DTYPE = np.dtype([("minpix", "<u4"), ("n_used", "<i4"), ("steps", "<i4"), ("pts", "<i4"), ("alg", "<i4"), ("scored", "<i4"), ("accepted", "<i4"),
+                         ("pad", "<i4"), ("hist_n", "<i4", (8,))] + [(k, "<f8") for k in ("cx", "cy", "x1", "y1", "x2", "y2", "width", "theta", "density",
+                                                                "fx1", "fy1", "fx2", "fy2", "fwidth", "p", "nfa")])
+assert MATCH_DTYPE.itemsize == 32 and EDGE_DTYPE.itemsize == 12 and HYP_DTYPE.itemsize == 96 and REGION_DTYPE.itemsize == 192
 
 _lib = None
 _lib_check = None
@@ -192,6 +195,56 @@ class Context:
         segs = np.ctypeslib.as_array(out, (n.value, 4)).copy() if n.value else np.zeros((0, 4), np.float32)
         self.lib.l3d_free(out)
         return segs
+
+    # -- the detector's stages on their own (tests): the same kernels and launch shapes as detect_segments
+    def test_detect_pixel_stage(self, img, new_size=None):
+        """l3d_test_detect_pixel_stage -> dict: grey (nh, nw) float32; img, mod, ang (M, N) float64; bucket (M, N, 2) uint8"""
+        pix, w, h, ch, stride = image_arguments(img)
+        nw, nh = (w, h) if new_size is None else (int(new_size[0]), int(new_size[1]))
+        N, M = int(np.ceil(nw * 0.8)), int(np.ceil(nh * 0.8))
+        out = {"grey": np.zeros((nh, nw), np.float32), "img": np.zeros((M, N)), "mod": np.zeros((M, N)), "ang": np.zeros((M, N)),
+               "bucket": np.zeros((M, N, 2), np.uint8)}
+        n, m = C.c_int(0), C.c_int(0)
+        self._chk(self.lib.l3d_test_detect_pixel_stage(self.h, pix, C.c_int(w), C.c_int(h), C.c_int(ch), C.c_size_t(stride), C.c_int(nw), C.c_int(nh),
+                                                       _p(out["grey"]), _p(out["img"]), _p(out["mod"]), _p(out["ang"]), _p(out["bucket"]),
+                                                       C.byref(n), C.byref(m)))
+        if (n.value, m.value) != (N, M):
+            raise L3DError("scaled size (%d, %d), expected (%d, %d)" % (n.value, m.value, N, M))
+        return out
+
+    def test_detect_label(self, bucket, active):
+        """l3d_test_detect_label: bucket (M, N, 2) uint8, active (M, N) -> parent (2, M, N) int32, key (M, N) uint32"""
+        bucket = np.ascontiguousarray(bucket, dtype=np.uint8)
+        active = np.ascontiguousarray(active, dtype=np.uint8)
+        M, N = active.shape
+        assert bucket.shape == (M, N, 2)
+        parent, key = np.zeros((2, M, N), np.int32), np.zeros((M, N), np.uint32)
+        self._chk(self.lib.l3d_test_detect_label(self.h, _p(bucket), _p(active), C.c_int(N), C.c_int(M), _p(parent), _p(key)))
+        return parent, key
+
+    def test_detect_regions(self, mod, ang, key, min_reg):
+        """l3d_test_detect_regions: mod, ang (M, N) float64, key (M, N) uint32 -> (records REGION_DTYPE, active_out (M, N) uint8)"""
+        mod, ang = np.ascontiguousarray(mod, dtype=np.float64), np.ascontiguousarray(ang, dtype=np.float64)
+        key = np.ascontiguousarray(key, dtype=np.uint32)
+        M, N = key.shape
+        assert mod.shape == (M, N) and ang.shape == (M, N)
+        rec, n = C.c_void_p(), C.c_int(0)
+        active = np.zeros((M, N), np.uint8)
+        self._chk(self.lib.l3d_test_detect_regions(self.h, C.c_int(N), C.c_int(M), _p(mod), _p(ang), _p(key), C.c_int(int(min_reg)),
+                                                   C.byref(rec), C.byref(n), _p(active)))
+        out = np.zeros(n.value, dtype=REGION_DTYPE)
+        if n.value:
+            C.memmove(out.ctypes.data, rec, n.value * REGION_DTYPE.itemsize)
+        self.lib.l3d_free(rec)
+        return out, active
+
+    def test_detect_nfa(self, n, k, p, logNT):
+        """l3d_test_detect_nfa: -log10 NFA per (n, k, p)"""
+        n, k = np.ascontiguousarray(n, dtype=np.int32), np.ascontiguousarray(k, dtype=np.int32)
+        p = np.ascontiguousarray(p, dtype=np.float64)
+        out = np.zeros(len(n))
+        self._chk(self.lib.l3d_test_detect_nfa(self.h, _p(n), _p(k), _p(p), C.c_double(float(logNT)), C.c_int(len(n)), _p(out)))
+        return out
 
     # -- the three seam functions ---------------------------------------------------------------
     def compute_collinearity(self, segs, collin_s=2.0):

@@ -74,6 +74,9 @@ __device__ inline int sym_index(int j, int n)
     return j >= n ? d - 1 - j : j;
 }
 constexpr int kXSpan = 96, kYRows = 16, kYSpan = 28;
+// the tap windows of a block's 64 columns / 16 rows fit its tile (the kernels skip an output whose window does not): the centres of outputs
+// j apart lie at most floor(j / kScale) + 1 apart: 63 columns 79, + 7 taps = 86 <= 96; 15 rows 19, + 7 = 26 <= 28
+static_assert((int)(63 / kScale) + 1 + kTaps <= kXSpan && (int)((kYRows - 1) / kScale) + 1 + kTaps <= kYSpan, "a block's taps exceed its tile");
 __global__ __launch_bounds__(256) void k_det_gauss_x(const float* __restrict__ grey, int W, int H, double* __restrict__ aux, int N,
                                                       const int* __restrict__ xc, const double* __restrict__ kw)
 {
@@ -245,7 +248,7 @@ __device__ inline double lgamma_short(double x)
     return a + log(b);
 }
 // -log10(number of false alarms) of k aligned among n points, probability p
-__device__ double det_nfa(int n, int k, double p, double logNT)
+__device__ __forceinline__ double det_nfa(int n, int k, double p, double logNT)     // (inlined: the tests' kernel is a third caller)
 {
     if (n == 0 || k == 0) return -logNT;
     if (n == k) return -logNT - (double)n * log10(p);
@@ -271,7 +274,8 @@ __device__ double det_nfa(int n, int k, double p, double logNT)
 struct DetRect { double x1, y1, x2, y2, width, dx, dy, theta, prec, p; };
 
 // pixels whose centre lies in the rectangle / those aligned with it within prec: lanes over the bounding box
-__device__ double rect_score(const DetRect& r, const double* __restrict__ ang, int N, int M, double logNT, int lane)
+struct DetScore { double v; int pts, alg; };      // the value; the counts it came from (read by the tests' trace only)
+__device__ DetScore rect_score(const DetRect& r, const double* __restrict__ ang, int N, int M, double logNT, int lane)
 {
     const double hx = -r.dy * r.width * 0.5, hy = r.dx * r.width * 0.5;
     const double minx = fmin(fmin(r.x1 - hx, r.x1 + hx), fmin(r.x2 - hx, r.x2 + hx)), maxx = fmax(fmax(r.x1 - hx, r.x1 + hx), fmax(r.x2 - hx, r.x2 + hx));
@@ -297,14 +301,14 @@ __device__ double rect_score(const DetRect& r, const double* __restrict__ ang, i
     }
     pts = wsumi(pts);
     alg = wsumi(alg);
-    return det_nfa(pts, alg, r.p, logNT);
+    return DetScore{ det_nfa(pts, alg, r.p, logNT), pts, alg };
 }
 
 // the rectangle variations tried for a region that fails the NFA: finer precision, narrower, one side in, the other side in, finer again
-__device__ double rect_retry(DetRect& rec, const double* __restrict__ ang, int N, int M, double logNT, int lane)
+__device__ DetScore rect_retry(DetRect& rec, const double* __restrict__ ang, int N, int M, double logNT, int lane)
 {
-    double best = rect_score(rec, ang, N, M, logNT, lane);
-    if (best > 0.0) return best;
+    DetScore best = rect_score(rec, ang, N, M, logNT, lane);
+    if (best.v > 0.0) return best;
     for (int stage = 0; stage < 5; ++stage) {
         DetRect r = rec;
         for (int n = 0; n < 5; ++n) {
@@ -315,10 +319,10 @@ __device__ double rect_retry(DetRect& rec, const double* __restrict__ ang, int N
                 r.x1 += -r.dy * s; r.y1 += r.dx * s; r.x2 += -r.dy * s; r.y2 += r.dx * s;
                 r.width -= 0.5;
             }
-            const double v = rect_score(r, ang, N, M, logNT, lane);
-            if (v > best) { best = v; rec = r; }
+            const DetScore v = rect_score(r, ang, N, M, logNT, lane);
+            if (v.v > best.v) { best = v; rec = r; }
         }
-        if (best > 0.0) return best;
+        if (best.v > 0.0) return best;
     }
     return best;
 }
@@ -326,7 +330,7 @@ __device__ double rect_retry(DetRect& rec, const double* __restrict__ ang, int N
 __global__ __launch_bounds__(256) void k_det_region(int N, int M, double logNT, int min_reg, const double* __restrict__ mod, const double* __restrict__ ang,
                                                      const unsigned* __restrict__ keys, const unsigned* __restrict__ vals, const int* __restrict__ count,
                                                      const int* __restrict__ start, const int* __restrict__ n_regions, unsigned char* __restrict__ active,
-                                                     DetCand* __restrict__ cand, int* __restrict__ n_cand, int cand_cap)
+                                                     DetCand* __restrict__ cand, int* __restrict__ n_cand, int cand_cap, l3d_detect_region_record* __restrict__ trace)
 {
     const int lane = threadIdx.x & 63;
     const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
@@ -347,6 +351,8 @@ __global__ __launch_bounds__(256) void k_det_region(int N, int M, double logNT, 
         const double sx = (double)(seed % (unsigned)N), sy = (double)(seed / (unsigned)N);
         double rad = -1.0;                      // < 0: the whole region
         DetRect rec;
+        l3d_detect_region_record* tr = trace && lane == 0 ? trace + reg : nullptr;      // (tests only: what this wave decides; the caller zeroes it)
+        if (tr) tr->minpix = px[0];
         for (int step = 0; step < 64; ++step) {
             double w = 0, wx = 0, wy = 0, cdx = 0, cdy = 0;
             int n = 0;
@@ -361,6 +367,7 @@ __global__ __launch_bounds__(256) void k_det_region(int N, int M, double logNT, 
                 first = min(first, q);
             }
             n = wsumi(n);
+            if (tr) { tr->steps = step; tr->n_used = n; if (step < 8) tr->hist_n[step] = n; }
             if (n < min_reg || n < 2) break;
             w = wsum(w); wx = wsum(wx); wy = wsum(wy); cdx = wsum(cdx); cdy = wsum(cdy);
             first = wminu(first);
@@ -392,8 +399,18 @@ __global__ __launch_bounds__(256) void k_det_region(int N, int M, double logNT, 
             rec.width = fmax(wmx - wmn, 1.0);
             rec.dx = dx; rec.dy = dy; rec.theta = theta; rec.prec = prec; rec.p = p;
             const double len = sqrt((rec.x2 - rec.x1) * (rec.x2 - rec.x1) + (rec.y2 - rec.y1) * (rec.y2 - rec.y1));
+            if (tr) {
+                tr->minpix = first; tr->cx = cx; tr->cy = cy; tr->density = (double)n / (len * rec.width);
+                tr->x1 = rec.x1; tr->y1 = rec.y1; tr->x2 = rec.x2; tr->y2 = rec.y2; tr->width = rec.width; tr->theta = theta;
+            }
             if ((double)n / (len * rec.width) >= kDensityTh) {
-                if (rect_retry(rec, ang, N, M, logNT, lane) > 0.0) {
+                const DetScore score = rect_retry(rec, ang, N, M, logNT, lane);
+                const double best = score.v;
+                if (tr) {
+                    tr->pts = score.pts; tr->alg = score.alg; tr->scored = 1; tr->accepted = best > 0.0;
+                    tr->fx1 = rec.x1; tr->fy1 = rec.y1; tr->fx2 = rec.x2; tr->fy2 = rec.y2; tr->fwidth = rec.width; tr->p = rec.p; tr->nfa = best;
+                }
+                if (best > 0.0) {
                     if (lane == 0) {
                         const int slot = atomicAdd(n_cand, 1);
                         if (slot < cand_cap) {
@@ -460,38 +477,38 @@ void sampler_table(int n_out, double sigma, int* centre, double* weights)
 
 }  // namespace
 
-int detect_segments(l3d_ctx* c, const unsigned char* pixels, int w, int h, int ch, size_t stride, int nw, int nh, float min_length, int max_segments,
-                    std::vector<float>& out)
+namespace {
+
+// what one image's run works at: sizes of the scaled image, thresholds, capacities
+struct DetPlan {
+    int w = 0, h = 0, ch = 1, nw = 0, nh = 0, N = 0, M = 0, np = 0, min_reg = 2, cand_cap = 0, key_bits = 1;
+    double rho = 0.0, logNT = 0.0;
+    float up = 1.0f;
+};
+// the part of the plan that follows from the scaled size alone
+void plan_scaled(DetPlan& p, int N, int M)
 {
-    out.clear();
-    if (!c) return L3D_ERR_INVALID;
-    if (!pixels || w < 8 || h < 8 || (ch != 1 && ch != 3) || stride < (size_t)w * ch) return fail(c, L3D_ERR_INVALID, "detect_segments: needs an image of at least 8x8 with 1 or 3 channels and a row stride of at least width x channels");
-    if (nw <= 0 || nh <= 0) { nw = w; nh = h; }
-    if (nw < 8 || nh < 8 || max_segments < 0) return fail(c, L3D_ERR_INVALID, "detect_segments: rescaled size below 8x8 or a negative cap");
-    const int N = (int)ceil(nw * kScale), M = (int)ceil(nh * kScale);
-    const long long np_ll = (long long)N * M;
-    if (np_ll > (1ll << 30) || (long long)w * h * ch > (1ll << 31)) return fail(c, L3D_ERR_UNSUPPORTED, "detect_segments: image too large");
-    const int np = (int)np_ll;
-    HIPCHK(c, hipSetDevice(c->device));
+    p.N = N; p.M = M; p.np = N * M;
+    p.rho = kQuant / sin(kPi * kAngTh / 180.0);
+    p.logNT = 5.0 * (log10((double)N) + log10((double)M)) / 2.0 + log10(11.0);
+    p.min_reg = std::max(2, (int)(-p.logNT / log10(kAngTh / 180.0)));
+    p.cand_cap = p.np / p.min_reg + 16;
+    p.key_bits = 1;
+    while ((1ull << p.key_bits) <= 2ull * (unsigned long long)p.np) ++p.key_bits;
+}
+
+int det_reserve(l3d_ctx* c, const DetPlan& p, int max_segments)
+{
     hipStream_t st = c->stream;
     DetectBufs& d = c->det;
-    const double prec = kPi * kAngTh / 180.0, rho = kQuant / sin(prec);
-    const double logNT = 5.0 * (log10((double)N) + log10((double)M)) / 2.0 + log10(11.0);
-    const int min_reg = std::max(2, (int)(-logNT / log10(kAngTh / 180.0)));
-    const int cand_cap = np / min_reg + 16;
-    float up = 1.0f;
-    if (nw != w || nh != h) up = 1.0f / (0.5f * (float(nw) / float(w) + float(nh) / float(h)));
-
-    // ---- scratch
+    const int np = p.np, cand_cap = p.cand_cap;
     size_t sort_bytes = 0, sort2_bytes = 0, scan_bytes = 0;
-    int key_bits = 1;
-    while ((1ull << key_bits) <= 2ull * (unsigned long long)np) ++key_bits;
-    HIPCHK(c, sort_pairs_u32_u32(nullptr, sort_bytes, (const unsigned*)nullptr, (unsigned*)nullptr, (const unsigned*)nullptr, (unsigned*)nullptr, np, 0, key_bits, st));
+    HIPCHK(c, sort_pairs_u32_u32(nullptr, sort_bytes, (const unsigned*)nullptr, (unsigned*)nullptr, (const unsigned*)nullptr, (unsigned*)nullptr, np, 0, p.key_bits, st));
     HIPCHK(c, sort_pairs_u64_u32(nullptr, sort2_bytes, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, (const unsigned*)nullptr, (unsigned*)nullptr, cand_cap, 0, 64, st));
     HIPCHK(c, exclusive_sum_int(nullptr, scan_bytes, (const int*)nullptr, (int*)nullptr, np + 1, st));
-    HIPCHK(c, d.pixels.reserve((size_t)w * h * ch));
-    HIPCHK(c, d.grey.reserve((size_t)nw * nh * 4));
-    HIPCHK(c, d.aux.reserve((size_t)N * nh * 8));
+    HIPCHK(c, d.pixels.reserve((size_t)p.w * p.h * p.ch));
+    HIPCHK(c, d.grey.reserve((size_t)p.nw * p.nh * 4));
+    HIPCHK(c, d.aux.reserve((size_t)p.N * p.nh * 8));
     HIPCHK(c, d.img.reserve((size_t)np * 8));
     HIPCHK(c, d.mod.reserve((size_t)np * 8));
     HIPCHK(c, d.ang.reserve((size_t)np * 8));
@@ -514,8 +531,16 @@ int detect_segments(l3d_ctx* c, const unsigned char* pixels, int w, int h, int c
     HIPCHK(c, d.cvals.reserve((size_t)cand_cap * 4));
     HIPCHK(c, d.cvals2.reserve((size_t)cand_cap * 4));
     HIPCHK(c, d.out.reserve((size_t)std::max(1, std::min(max_segments, cand_cap)) * 16));
-    HIPCHK(c, d.scal.reserve(64));
-    int* scal = d.scal.as<int>();               // [0] changed, [1] changed (ignored rounds), [2] candidates, [3] selected
+    HIPCHK(c, d.scal.reserve(64));              // ints: [0] changed, [1] changed (ignored rounds), [2] candidates, [3] selected
+    return L3D_OK;
+}
+
+// ---- pixel stage: upload, rescale + grey, the two sampler passes, gradient; leaves the scalars zeroed
+int det_pixel_stage(l3d_ctx* c, const DetPlan& p, const unsigned char* pixels, size_t stride)
+{
+    hipStream_t st = c->stream;
+    DetectBufs& d = c->det;
+    const int w = p.w, h = p.h, ch = p.ch, nw = p.nw, nh = p.nh, N = p.N, M = p.M;
     if (d.tab_w != nw || d.tab_h != nh) {
         std::vector<int> centre((size_t)N + M);
         std::vector<double> weights(((size_t)N + M) * kTaps);
@@ -530,41 +555,106 @@ int detect_segments(l3d_ctx* c, const unsigned char* pixels, int w, int h, int c
     }
     const double* kw = d.ktab.as<double>();
     const int* kc = reinterpret_cast<const int*>(static_cast<const char*>(d.ktab.p) + ((size_t)N + M) * kTaps * 8);
-
-    // ---- pixel stage
     HIPCHK(c, hipMemcpy2DAsync(d.pixels.p, (size_t)w * ch, pixels, stride, (size_t)w * ch, (size_t)h, hipMemcpyHostToDevice, st));
     const dim3 b256(256);
     { ProfScope ps(c, "k_det_grey"); hipLaunchKernelGGL(k_det_grey, dim3((nw + 255) / 256, nh), b256, 0, st, d.pixels.as<unsigned char>(), w, h, ch, nw, nh, d.grey.as<float>()); }
     { ProfScope ps(c, "k_det_gauss_x"); hipLaunchKernelGGL(k_det_gauss_x, dim3((N + 63) / 64, (nh + 3) / 4), dim3(64, 4), 0, st, d.grey.as<float>(), nw, nh, d.aux.as<double>(), N, kc, kw); }
     { ProfScope ps(c, "k_det_gauss_y"); hipLaunchKernelGGL(k_det_gauss_y, dim3((N + 63) / 64, (M + kYRows - 1) / kYRows), dim3(64, 4), 0, st, d.aux.as<double>(), N, nh, d.img.as<double>(), M, kc + N, kw + (size_t)N * kTaps); }
-    { ProfScope ps(c, "k_det_grad"); hipLaunchKernelGGL(k_det_grad, dim3((N + 255) / 256, M), b256, 0, st, d.img.as<double>(), N, M, rho, d.mod.as<double>(), d.ang.as<double>(), d.bucket.as<uchar2>(), d.active.as<unsigned char>()); }
-    HIPCHK(c, hipMemsetAsync(scal, 0, 64, st));
+    { ProfScope ps(c, "k_det_grad"); hipLaunchKernelGGL(k_det_grad, dim3((N + 255) / 256, M), b256, 0, st, d.img.as<double>(), N, M, p.rho, d.mod.as<double>(), d.ang.as<double>(), d.bucket.as<uchar2>(), d.active.as<unsigned char>()); }
+    HIPCHK(c, hipMemsetAsync(d.scal.p, 0, 64, st));
+    return L3D_OK;
+}
+
+// ---- labelling of the active pixels to the fixed point, component sizes, vote.  Between two compressions every tree is a star, and a
+// hooking round that changes anything turns at least one root into a child: at most np - 1 rounds change something, three rounds a look.
+int det_label(l3d_ctx* c, const DetPlan& p)
+{
+    hipStream_t st = c->stream;
+    DetectBufs& d = c->det;
+    const int N = p.N, M = p.M, np = p.np;
+    int* scal = d.scal.as<int>();
+    const dim3 b256(256), gnp((np + 255) / 256), g2np((2 * np + 255) / 256);
+    { ProfScope ps(c, "k_det_label_init"); hipLaunchKernelGGL(k_det_label_init, gnp, b256, 0, st, d.active.as<unsigned char>(), np, d.parent.as<int>()); }
+    const int max_looks = np / 3 + 2;
+    for (int it = 0; ; ++it) {
+        HIPCHK(c, hipMemsetAsync(scal, 0, 4, st));
+        for (int r = 0; r < 3; ++r) {                       // a few hooking rounds per look at the flag
+            { ProfScope ps(c, "k_det_label_hook"); hipLaunchKernelGGL(k_det_label_hook, dim3((N + 255) / 256, M, 2), b256, 0, st, d.bucket.as<uchar2>(), d.active.as<unsigned char>(), N, M, d.parent.as<int>(), scal + (r == 2 ? 0 : 1)); }
+            { ProfScope ps(c, "k_det_label_compress"); hipLaunchKernelGGL(k_det_label_compress, g2np, b256, 0, st, d.parent.as<int>(), 2 * np); }
+        }
+        int changed = 0;
+        HIPCHK(c, hipMemcpyAsync(&changed, scal, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        if (!changed) break;
+        if (it + 1 >= max_looks) return fail(c, L3D_ERR_UNSUPPORTED, "detect_segments: labelling did not converge");
+    }
+    HIPCHK(c, hipMemsetAsync(d.size.p, 0, (size_t)np * 8, st));
+    HIPCHK(c, hipMemsetAsync(d.count.p, 0, (size_t)np * 8 + 8, st));
+    { ProfScope ps(c, "k_det_sizes"); hipLaunchKernelGGL(k_det_sizes, g2np, b256, 0, st, d.parent.as<int>(), np, d.size.as<int>()); }
+    { ProfScope ps(c, "k_det_vote"); hipLaunchKernelGGL(k_det_vote, gnp, b256, 0, st, d.parent.as<int>(), d.size.as<int>(), np, d.keys.as<unsigned>(), d.vals.as<unsigned>(), d.count.as<int>()); }
+    return L3D_OK;
+}
+
+// ---- regions of the labelling in keys / vals / count: sort, heads, scan, starts, the region kernel.  trace: null outside the tests
+int det_regions(l3d_ctx* c, const DetPlan& p, l3d_detect_region_record* trace)
+{
+    hipStream_t st = c->stream;
+    DetectBufs& d = c->det;
+    const int N = p.N, M = p.M, np = p.np;
+    const dim3 b256(256), gnp((np + 255) / 256), gnp1((np + 256) / 256);
+    { ProfScope ps(c, "det_sort_pixels"); size_t tb = d.tmp.cap; HIPCHK(c, sort_pairs_u32_u32(d.tmp.p, tb, d.keys.as<unsigned>(), d.keys2.as<unsigned>(), d.vals.as<unsigned>(), d.vals2.as<unsigned>(), np, 0, p.key_bits, st)); }
+    { ProfScope ps(c, "k_det_heads"); hipLaunchKernelGGL(k_det_heads, gnp1, b256, 0, st, d.keys2.as<unsigned>(), d.count.as<int>(), np, p.min_reg, d.flag.as<int>()); }
+    { size_t tb = d.tmp.cap; HIPCHK(c, exclusive_sum_int(d.tmp.p, tb, d.flag.as<int>(), d.pos.as<int>(), np + 1, st)); }
+    { ProfScope ps(c, "k_det_starts"); hipLaunchKernelGGL(k_det_starts, gnp, b256, 0, st, d.flag.as<int>(), d.pos.as<int>(), np, d.start.as<int>()); }
+    { ProfScope ps(c, "k_det_region"); hipLaunchKernelGGL(k_det_region, dim3(1024), b256, 0, st, N, M, p.logNT, p.min_reg, d.mod.as<double>(), d.ang.as<double>(), d.keys2.as<unsigned>(), d.vals2.as<unsigned>(), d.count.as<int>(), d.start.as<int>(), d.pos.as<int>() + np, d.active.as<unsigned char>(), d.cand.as<DetCand>(), d.scal.as<int>() + 2, p.cand_cap, trace); }
+    return L3D_OK;
+}
+
+__global__ void k_det_nfa_test(const int* __restrict__ n, const int* __restrict__ k, const double* __restrict__ p, double logNT, int count, double* __restrict__ out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) out[i] = det_nfa(n[i], k[i], p[i], logNT);
+}
+
+int plan_image(l3d_ctx* c, DetPlan& p, const unsigned char* pixels, int w, int h, int ch, size_t stride, int nw, int nh)
+{
+    if (!pixels || w < 8 || h < 8 || (ch != 1 && ch != 3) || stride < (size_t)w * ch) return fail(c, L3D_ERR_INVALID, "detect_segments: needs an image of at least 8x8 with 1 or 3 channels and a row stride of at least width x channels");
+    if (nw <= 0 || nh <= 0) { nw = w; nh = h; }
+    if (nw < 8 || nh < 8) return fail(c, L3D_ERR_INVALID, "detect_segments: rescaled size below 8x8");
+    const int N = (int)ceil(nw * kScale), M = (int)ceil(nh * kScale);
+    const long long np_ll = (long long)N * M;
+    if (np_ll > (1ll << 30) || (long long)w * h * ch > (1ll << 31)) return fail(c, L3D_ERR_UNSUPPORTED, "detect_segments: image too large");
+    p.w = w; p.h = h; p.ch = ch; p.nw = nw; p.nh = nh;
+    plan_scaled(p, N, M);
+    p.up = 1.0f;
+    if (nw != w || nh != h) p.up = 1.0f / (0.5f * (float(nw) / float(w) + float(nh) / float(h)));
+    return L3D_OK;
+}
+
+}  // namespace
+
+int detect_segments(l3d_ctx* c, const unsigned char* pixels, int w, int h, int ch, size_t stride, int nw, int nh, float min_length, int max_segments,
+                    std::vector<float>& out)
+{
+    out.clear();
+    if (!c) return L3D_ERR_INVALID;
+    if (max_segments < 0) return fail(c, L3D_ERR_INVALID, "detect_segments: negative max_segments");
+    DetPlan plan;
+    if (int rc = plan_image(c, plan, pixels, w, h, ch, stride, nw, nh)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    DetectBufs& d = c->det;
+    if (int rc = det_reserve(c, plan, max_segments)) return rc;
+    int* scal = d.scal.as<int>();
+    const int cand_cap = plan.cand_cap;
+    const float up = plan.up;
+    const dim3 b256(256);
+    if (int rc = det_pixel_stage(c, plan, pixels, stride)) return rc;
 
     // ---- rounds: label, vote, sort, regions
-    const dim3 gnp((np + 255) / 256), gnp1((np + 256) / 256), g2np((2 * np + 255) / 256);
     for (int round = 0; round < kRounds; ++round) {
-        { ProfScope ps(c, "k_det_label_init"); hipLaunchKernelGGL(k_det_label_init, gnp, b256, 0, st, d.active.as<unsigned char>(), np, d.parent.as<int>()); }
-        for (int it = 0; it < 64; ++it) {
-            HIPCHK(c, hipMemsetAsync(scal, 0, 4, st));
-            for (int r = 0; r < 3; ++r) {                       // a few hooking rounds per look at the flag
-                { ProfScope ps(c, "k_det_label_hook"); hipLaunchKernelGGL(k_det_label_hook, dim3((N + 255) / 256, M, 2), b256, 0, st, d.bucket.as<uchar2>(), d.active.as<unsigned char>(), N, M, d.parent.as<int>(), scal + (r == 2 ? 0 : 1)); }
-                { ProfScope ps(c, "k_det_label_compress"); hipLaunchKernelGGL(k_det_label_compress, g2np, b256, 0, st, d.parent.as<int>(), 2 * np); }
-            }
-            int changed = 0;
-            HIPCHK(c, hipMemcpyAsync(&changed, scal, 4, hipMemcpyDeviceToHost, st));
-            HIPCHK(c, hipStreamSynchronize(st));
-            if (!changed) break;
-            if (it == 63) return fail(c, L3D_ERR_UNSUPPORTED, "detect_segments: labelling did not converge");
-        }
-        HIPCHK(c, hipMemsetAsync(d.size.p, 0, (size_t)np * 8, st));
-        HIPCHK(c, hipMemsetAsync(d.count.p, 0, (size_t)np * 8 + 8, st));
-        { ProfScope ps(c, "k_det_sizes"); hipLaunchKernelGGL(k_det_sizes, g2np, b256, 0, st, d.parent.as<int>(), np, d.size.as<int>()); }
-        { ProfScope ps(c, "k_det_vote"); hipLaunchKernelGGL(k_det_vote, gnp, b256, 0, st, d.parent.as<int>(), d.size.as<int>(), np, d.keys.as<unsigned>(), d.vals.as<unsigned>(), d.count.as<int>()); }
-        { ProfScope ps(c, "det_sort_pixels"); size_t tb = d.tmp.cap; HIPCHK(c, sort_pairs_u32_u32(d.tmp.p, tb, d.keys.as<unsigned>(), d.keys2.as<unsigned>(), d.vals.as<unsigned>(), d.vals2.as<unsigned>(), np, 0, key_bits, st)); }
-        { ProfScope ps(c, "k_det_heads"); hipLaunchKernelGGL(k_det_heads, gnp1, b256, 0, st, d.keys2.as<unsigned>(), d.count.as<int>(), np, min_reg, d.flag.as<int>()); }
-        { size_t tb = d.tmp.cap; HIPCHK(c, exclusive_sum_int(d.tmp.p, tb, d.flag.as<int>(), d.pos.as<int>(), np + 1, st)); }
-        { ProfScope ps(c, "k_det_starts"); hipLaunchKernelGGL(k_det_starts, gnp, b256, 0, st, d.flag.as<int>(), d.pos.as<int>(), np, d.start.as<int>()); }
-        { ProfScope ps(c, "k_det_region"); hipLaunchKernelGGL(k_det_region, dim3(1024), b256, 0, st, N, M, logNT, min_reg, d.mod.as<double>(), d.ang.as<double>(), d.keys2.as<unsigned>(), d.vals2.as<unsigned>(), d.count.as<int>(), d.start.as<int>(), d.pos.as<int>() + np, d.active.as<unsigned char>(), d.cand.as<DetCand>(), scal + 2, cand_cap); }
+        if (int rc = det_label(c, plan)) return rc;
+        if (int rc = det_regions(c, plan, nullptr)) return rc;
     }
 
     // ---- selection
@@ -603,4 +693,128 @@ int l3d_detect_segments(l3d_ctx* c, const unsigned char* pixels, int width, int 
     if (!out.empty()) memcpy(p, out.data(), out.size() * 4);
     *segments = p;
     return L3D_OK;
+}
+
+// ---- the stages on their own, for the tests: the functions above (the same kernels and launch shapes as l3d_detect_segments), results copied out
+int l3d_test_detect_pixel_stage(l3d_ctx* c, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, int new_width, int new_height,
+                                float* grey, double* img, double* mod, double* ang, unsigned char* bucket, int* N, int* M)
+{
+    using namespace l3d;
+    if (!c || !grey || !img || !mod || !ang || !bucket || !N || !M) return L3D_ERR_INVALID;
+    DetPlan p;
+    if (int rc = plan_image(c, p, pixels, width, height, channels, row_stride, new_width, new_height)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = det_reserve(c, p, 0)) return rc;
+    if (int rc = det_pixel_stage(c, p, pixels, row_stride)) return rc;
+    DetectBufs& d = c->det;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(grey, d.grey.p, (size_t)p.nw * p.nh * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(img, d.img.p, (size_t)p.np * 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(mod, d.mod.p, (size_t)p.np * 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(ang, d.ang.p, (size_t)p.np * 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(bucket, d.bucket.p, (size_t)p.np * 2, hipMemcpyDeviceToHost));
+    *N = p.N; *M = p.M;
+    return L3D_OK;
+}
+
+int l3d_test_detect_label(l3d_ctx* c, const unsigned char* bucket, const unsigned char* active, int N, int M, int32_t* parent, uint32_t* key)
+{
+    using namespace l3d;
+    if (!c || !bucket || !active || !parent || !key) return L3D_ERR_INVALID;
+    if (N < 1 || M < 1 || (long long)N * M > (1ll << 30)) return fail(c, L3D_ERR_INVALID, "test_detect_label: size");
+    DetPlan p;
+    plan_scaled(p, N, M);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = det_reserve(c, p, 0)) return rc;
+    DetectBufs& d = c->det;
+    HIPCHK(c, hipMemcpy(d.bucket.p, bucket, (size_t)p.np * 2, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d.active.p, active, (size_t)p.np, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemsetAsync(d.scal.p, 0, 64, c->stream));
+    if (int rc = det_label(c, p)) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(parent, d.parent.p, (size_t)p.np * 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(key, d.keys.p, (size_t)p.np * 4, hipMemcpyDeviceToHost));
+    return L3D_OK;
+}
+
+int l3d_test_detect_regions(l3d_ctx* c, int N, int M, const double* mod, const double* ang, const uint32_t* key, int min_reg,
+                            l3d_detect_region_record** rec, int* n_rec, unsigned char* active_out)
+{
+    using namespace l3d;
+    if (!c || !mod || !ang || !key || !rec || !n_rec || !active_out) return L3D_ERR_INVALID;
+    *rec = nullptr;
+    *n_rec = 0;
+    if (N < 1 || M < 1 || (long long)N * M > (1ll << 30) || min_reg < 2) return fail(c, L3D_ERR_INVALID, "test_detect_regions: size or min_reg");
+    DetPlan p;
+    plan_scaled(p, N, M);
+    p.min_reg = min_reg;
+    p.cand_cap = p.np / min_reg + 16;
+    const int np = p.np;
+    // the vote's other outputs, from the keys: pixel indices in order, pixels per key
+    std::vector<unsigned> vals((size_t)np);
+    std::vector<int> count(2 * (size_t)np + 2, 0);
+    for (int i = 0; i < np; ++i) {
+        vals[i] = (unsigned)i;
+        if (key[i] > 2u * (unsigned)np) return fail(c, L3D_ERR_INVALID, "test_detect_regions: key out of range");
+        if (key[i] < 2u * (unsigned)np) ++count[key[i]];
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = det_reserve(c, p, 0)) return rc;
+    DetectBufs& d = c->det;
+    DevBuf trace;
+    const size_t trace_bytes = (size_t)p.cand_cap * sizeof(l3d_detect_region_record);
+    HIPCHK(c, trace.reserve(trace_bytes));
+    int rc = L3D_OK, n = 0;
+    auto step = [&](hipError_t e) { if (rc == L3D_OK && e != hipSuccess) rc = fail(c, L3D_ERR_HIP, hipGetErrorString(e)); };
+    step(hipMemcpy(d.mod.p, mod, (size_t)np * 8, hipMemcpyHostToDevice));
+    step(hipMemcpy(d.ang.p, ang, (size_t)np * 8, hipMemcpyHostToDevice));
+    step(hipMemcpy(d.keys.p, key, (size_t)np * 4, hipMemcpyHostToDevice));
+    step(hipMemcpy(d.vals.p, vals.data(), (size_t)np * 4, hipMemcpyHostToDevice));
+    step(hipMemcpy(d.count.p, count.data(), (size_t)np * 8 + 8, hipMemcpyHostToDevice));
+    step(hipMemset(d.active.p, 1, (size_t)np));
+    step(hipMemset(trace.p, 0, trace_bytes));
+    step(hipMemsetAsync(d.scal.p, 0, 64, c->stream));
+    if (rc == L3D_OK) rc = det_regions(c, p, trace.as<l3d_detect_region_record>());
+    if (rc == L3D_OK) step(hipStreamSynchronize(c->stream));
+    if (rc == L3D_OK) step(hipMemcpy(&n, d.pos.as<int>() + np, 4, hipMemcpyDeviceToHost));
+    if (rc == L3D_OK && n > p.cand_cap) rc = fail(c, L3D_ERR_INVALID, "test_detect_regions: more regions than np / min_reg");
+    if (rc == L3D_OK) {
+        l3d_detect_region_record* out = static_cast<l3d_detect_region_record*>(malloc(std::max<size_t>(16, (size_t)n * sizeof(l3d_detect_region_record))));
+        if (!out) rc = fail(c, L3D_ERR_INVALID, "test_detect_regions: out of memory");
+        else {
+            if (n) step(hipMemcpy(out, trace.p, (size_t)n * sizeof(l3d_detect_region_record), hipMemcpyDeviceToHost));
+            step(hipMemcpy(active_out, d.active.p, (size_t)np, hipMemcpyDeviceToHost));
+            if (rc == L3D_OK) { *rec = out; *n_rec = n; } else free(out);
+        }
+    }
+    trace.release();
+    return rc;
+}
+
+int l3d_test_detect_nfa(l3d_ctx* c, const int32_t* n, const int32_t* k, const double* p, double logNT, int count, double* out)
+{
+    using namespace l3d;
+    if (!c || !n || !k || !p || !out || count < 0) return L3D_ERR_INVALID;
+    if (count == 0) return L3D_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf buf;
+    const size_t cnt = (size_t)count;
+    HIPCHK(c, buf.reserve(cnt * 24));
+    int* dn = buf.as<int>();
+    int* dk = dn + cnt;
+    double* dp = reinterpret_cast<double*>(dk + cnt);
+    double* dout = dp + cnt;
+    int rc = L3D_OK;
+    auto step = [&](hipError_t e) { if (rc == L3D_OK && e != hipSuccess) rc = fail(c, L3D_ERR_HIP, hipGetErrorString(e)); };
+    step(hipMemcpy(dn, n, cnt * 4, hipMemcpyHostToDevice));
+    step(hipMemcpy(dk, k, cnt * 4, hipMemcpyHostToDevice));
+    step(hipMemcpy(dp, p, cnt * 8, hipMemcpyHostToDevice));
+    if (rc == L3D_OK) {
+        hipLaunchKernelGGL(k_det_nfa_test, dim3((count + 255) / 256), dim3(256), 0, c->stream, dn, dk, dp, logNT, count, dout);
+        step(hipGetLastError());
+        step(hipStreamSynchronize(c->stream));
+        step(hipMemcpy(out, dout, cnt * 8, hipMemcpyDeviceToHost));
+    }
+    buf.release();
+    return rc;
 }
