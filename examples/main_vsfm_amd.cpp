@@ -1,8 +1,13 @@
 // main_vsfm_amd.cpp -- the flow of the reference's VisualSfM driver (main_vsfm.cpp:34-329) over this library, with the
-// segment caches of an earlier Line3D run standing in for the images (no OpenCV, no tclap, no boost):
+// segment caches of an earlier Line3D run standing in for the images, or with the images as binary PPM / PGM files (no OpenCV, no tclap,
+// no boost):
 //
-//   main_vsfm_amd <scene.nvm | bundle.rd.out> <data directory> [neighbors=10] [diffusion=0] [output folder=<data directory>]
+//   main_vsfm_amd <scene.nvm | bundle.rd.out> <data directory> [neighbors=10] [diffusion=0] [output folder=<data directory>] [image folder]
 //
+// With an image folder, camera i's image is "<image folder>/<camera name, extension replaced>.ppm" or ".pgm" (binary P6 / P5, maxval 255; convert
+// JPEG / PNG beforehand).  The camera name is the NVM file's image name; for a bundler file it is the camera index as %08d
+// ("00000000.ppm", ...: the drivers' visualize/%08d.jpg, main_bundler.cpp:208-236): it is undistorted with the scene file's coefficients and its segments are detected on the device
+// (addImageDistorted: main_vsfm.cpp:243-273), and the data directory receives the segment caches.  Without one:
 // For every camera of the NVM file the data directory ("<image folder>/L3D_data" of the reference, main_vsfm.cpp:108-116)
 // must hold "segments_<id>_<w>x<h>_coll1.bin" (line3D.cc:143-150) -- the image size is read off the file name, K is built
 // from the focal length and that size the way the driver does it (main_vsfm.cpp:232-241), addImage uses the cached segments
@@ -40,15 +45,68 @@ bool find_cache(const std::string& dir, unsigned id, unsigned& w, unsigned& h)
     return found;
 }
 
+// a binary PGM / PPM image: what addImageDistorted needs of a cv::Mat
+struct PnmImage {
+    int cols = 0, rows = 0, ch = 1;
+    size_t step = 0;
+    unsigned char* data = nullptr;
+    std::vector<unsigned char> store;
+    int channels() const { return ch; }
+};
+// the next header number, past white space and '#' comments.  The character after the number is consumed (the header's single white space before
+// the pixels); where it is a '#' ("640#c"), so is the comment it begins
+bool pnm_number(FILE* f, int& v)
+{
+    int c = fgetc(f);
+    while (c == '#' || c == ' ' || c == '\t' || c == '\n' || c == '\r') {
+        if (c == '#') while (c != '\n' && c != EOF) c = fgetc(f);
+        else c = fgetc(f);
+    }
+    if (c < '0' || c > '9') return false;
+    long long n = 0;
+    for (; c >= '0' && c <= '9' && n < (1ll << 31); c = fgetc(f)) n = n * 10 + (c - '0');      // (c: the single white space after the number)
+    if (c == '#') while (c != '\n' && c != EOF) c = fgetc(f);
+    v = (int)n;
+    return n < (1ll << 31);
+}
+bool read_pnm(const std::string& path, PnmImage& img)
+{
+    FILE* f = fopen(path.c_str(), "rb");
+    if (!f) return false;
+    int w = 0, h = 0, maxval = 0;
+    const int m0 = fgetc(f), m1 = fgetc(f);
+    bool ok = m0 == 'P' && (m1 == '5' || m1 == '6') && pnm_number(f, w) && pnm_number(f, h) && pnm_number(f, maxval) && maxval == 255 && w > 0 && h > 0;
+    if (ok) {
+        img.cols = w; img.rows = h; img.ch = m1 == '6' ? 3 : 1;
+        img.step = (size_t)w * img.ch;
+        img.store.resize(img.step * h);
+        ok = fread(img.store.data(), 1, img.store.size(), f) == img.store.size();
+        img.data = img.store.data();
+    }
+    fclose(f);
+    return ok;
+}
+// "<folder>/<name without its extension>.ppm", then ".pgm"
+bool load_camera_image(const std::string& folder, const std::string& name, PnmImage& img)
+{
+    const size_t slash = name.find_last_of("/\\"), dot = name.find_last_of('.');
+    const std::string stem = folder + "/" + (dot != std::string::npos && (slash == std::string::npos || dot > slash) ? name.substr(0, dot) : name);
+    return read_pnm(stem + ".ppm", img) || read_pnm(stem + ".pgm", img);
+}
+// K, R, t of the facade's matrix-typed calls over plain arrays
+struct Mat3 { const double* p; double operator()(int i, int j) const { return p[i * 3 + j]; } };
+struct Vec3 { const double* p; double operator()(int i) const { return p[i]; } };
+
 }  // namespace
 
 int main(int argc, char** argv)
 {
-    if (argc < 3) { fprintf(stderr, "usage: %s <scene.nvm | bundle.rd.out> <data directory> [neighbors=10] [diffusion=0] [output folder]\n", argv[0]); return 2; }
+    if (argc < 3) { fprintf(stderr, "usage: %s <scene.nvm | bundle.rd.out> <data directory> [neighbors=10] [diffusion=0] [output folder] [image folder]\n", argv[0]); return 2; }
     const std::string nvm = argv[1], data_dir = argv[2];
     const int neighbors = argc > 3 ? atoi(argv[3]) : 10;
     const bool diffusion = argc > 4 && atoi(argv[4]) != 0;
     const std::string out_dir = argc > 5 ? argv[5] : data_dir;
+    const std::string image_dir = argc > 6 ? argv[6] : "";
 
     l3d_sfm_scene* scene = nullptr;
     // a bundler file (bundle.rd.out, main_bundler.cpp:110-204) is read just as well: the rest of the two drivers is the same flow
@@ -67,14 +125,25 @@ int main(int argc, char** argv)
         double focal = 0, dist[2] = { 0, 0 }, R[9], t[3];
         int nwp = 0;
         l3d_sfm_camera(scene, i, &focal, dist, R, t, &nwp);
-        if (dist[0] != 0.0 || dist[1] != 0.0) { fprintf(stderr, "camera %d has lens distortion: the cached segments must come from undistorted images\n", i); continue; }
+        std::vector<uint32_t> ids((size_t)nwp);
+        l3d_sfm_camera_worldpoints(scene, i, ids.data());
+        std::list<unsigned int> wps(ids.begin(), ids.end());
+        if (!image_dir.empty()) {                   // main_vsfm.cpp:229-273: load, K from the image size, undistort, addImage
+            PnmImage img;
+            if (!load_camera_image(image_dir, l3d_sfm_camera_name(scene, i), img)) { fprintf(stderr, "camera %d: no binary .ppm / .pgm image (maxval 255) for %s in %s\n", i, l3d_sfm_camera_name(scene, i), image_dir.c_str()); continue; }
+            double K[9], k[2] = { 0, 0 };
+            l3d_sfm_intrinsics(focal, (unsigned)img.cols, (unsigned)img.rows, K);
+            l3d_sfm_camera_cv_distortion(scene, i, k);
+            const unsigned before = line3D.numCameras();
+            line3D.addImageDistorted((unsigned)i, img, Mat3{ K }, Mat3{ R }, Vec3{ t }, k[0], k[1], wps);
+            added += (int)(line3D.numCameras() - before);
+            continue;
+        }
+        if (dist[0] != 0.0 || dist[1] != 0.0) { fprintf(stderr, "camera %d has lens distortion: the cached segments must come from undistorted images (or give an image folder)\n", i); continue; }
         unsigned w = 0, h = 0;
         if (!find_cache(data_dir, (unsigned)i, w, h)) { fprintf(stderr, "camera %d: no segment cache in %s\n", i, data_dir.c_str()); continue; }
         double K[9];
         l3d_sfm_intrinsics(focal, w, h, K);
-        std::vector<uint32_t> ids((size_t)nwp);
-        l3d_sfm_camera_worldpoints(scene, i, ids.data());
-        std::list<unsigned int> wps(ids.begin(), ids.end());
         if (line3D.addImageFromCache((unsigned)i, w, h, K, R, t, wps)) ++added;
     }
     l3d_sfm_free(scene);

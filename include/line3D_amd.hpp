@@ -5,11 +5,13 @@
 // the image type carries them (.data / .step / .channels(), cv::Mat itself) and otherwise come from the segment cache of the data directory,
 // the reference's own side door for precomputed segments (line3D.cc:143-168); (2) width, height and the segments the detector would have
 // produced (std::vector<float4>, the side door of L3DSegments(list<float4>&, bool), segments.h:60), cameras as plain row-major arrays or
-// matrix types.  Neither OpenCV nor Eigen is needed to compile this header.
+// matrix types.  addImageDistorted / addImage_fixed_simDistorted / undistortImage cover the drivers' undistort block in front of addImage
+// (main_vsfm.cpp:243-270) without OpenCV's calib module.  Neither OpenCV nor Eigen is needed to compile this header.
 #pragma once
 
 #include <array>
 #include <cstdio>
+#include <cstring>
 #include <iostream>
 #include <list>
 #include <map>
@@ -188,6 +190,53 @@ public:
         sims.push_back(0.0f);       // (never null: `sims` tells the two kinds of links apart)
         report(add_from_image(detail::prio<1>(), imageID, image, k, r, tt, ids.data(), sims.data(), (int)ids.size(), maxImgWidth, loadAndStoreSegments));
     }
+    // The drivers' per-image step in front of addImage (main_vsfm.cpp:243-273, main_bundler.cpp:256-287): the image is undistorted on the device
+    // with OpenCV-convention radial coefficients k1, k2 and K's fx, fy, cx, cy (l3d_line3d_add_image_pixels_distorted), then detected.  For image
+    // types that carry pixels; one with a size only takes the cache path as above and the coefficients are ignored.
+    template <class Img, class M3, class V3, class = decltype(std::declval<const Img&>().cols), class = decltype(std::declval<const Img&>().rows),
+              class = decltype(std::declval<const M3&>()(0, 0)), class = decltype(std::declval<const V3&>()(0))>
+    void addImageDistorted(const unsigned int imageID, const Img& image, const M3& K, const M3& R, const V3& t, const double k1, const double k2,
+                           std::list<unsigned int>& worldpointIDs, const int maxImgWidth = 1920, const bool loadAndStoreSegments = true)
+    {
+        double k[9], r[9], tt[3];
+        flatten(K, R, t, k, r, tt);
+        const double dist[2] = { k1, k2 };
+        std::vector<uint32_t> wps(worldpointIDs.begin(), worldpointIDs.end());
+        report(add_from_image(detail::prio<1>(), imageID, image, k, r, tt, wps.data(), nullptr, (int)wps.size(), maxImgWidth, loadAndStoreSegments, dist));
+    }
+    template <class Img, class M3, class V3, class = decltype(std::declval<const Img&>().cols), class = decltype(std::declval<const Img&>().rows),
+              class = decltype(std::declval<const M3&>()(0, 0)), class = decltype(std::declval<const V3&>()(0))>
+    void addImage_fixed_simDistorted(const unsigned int imageID, const Img& image, const M3& K, const M3& R, const V3& t, const double k1, const double k2,
+                                     std::map<unsigned int, float>& viewSimilarity, const int maxImgWidth = 1920, const bool loadAndStoreSegments = true)
+    {
+        double k[9], r[9], tt[3];
+        flatten(K, R, t, k, r, tt);
+        const double dist[2] = { k1, k2 };
+        std::vector<uint32_t> ids;
+        std::vector<float> sims;
+        for (auto& kv : viewSimilarity) { ids.push_back(kv.first); sims.push_back(kv.second); }
+        sims.push_back(0.0f);
+        report(add_from_image(detail::prio<1>(), imageID, image, k, r, tt, ids.data(), sims.data(), (int)ids.size(), maxImgWidth, loadAndStoreSegments, dist));
+    }
+    // cv::initUndistortRectifyMap + cv::remap(image, image, ..., INTER_LINEAR, BORDER_CONSTANT) of the drivers, in place on image.data (staged
+    // through a temporary, as remap does when source and destination coincide): undistort, then addImage -- the drivers' own structure
+    template <class Img, class M3, class = decltype(static_cast<unsigned char*>(std::declval<Img&>().data)),
+              class = decltype(static_cast<size_t>(std::declval<const Img&>().step)), class = decltype(static_cast<int>(std::declval<const Img&>().channels())),
+              class = decltype(std::declval<const M3&>()(0, 0))>
+    bool undistortImage(Img& image, const M3& K, const double k1, const double k2)
+    {
+        double k[9];
+        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) k[i * 3 + j] = K(i, j);
+        const int w = (int)image.cols, h = (int)image.rows, ch = static_cast<int>(image.channels());
+        const size_t step = static_cast<size_t>(image.step), row = (size_t)(w > 0 ? w : 0) * (size_t)(ch > 0 ? ch : 0);
+        std::vector<unsigned char> tmp(row * (size_t)(h > 0 ? h : 0) + 1);
+        unsigned char* px = static_cast<unsigned char*>(image.data);
+        const int rc = l3d_line3d_undistort_image(h_, px, w, h, ch, step, k, k1, k2, tmp.data(), row);
+        report(rc);
+        if (rc != L3D_OK) return false;
+        for (int i = 0; i < h; ++i) memcpy(px + (size_t)i * step, tmp.data() + (size_t)i * row, row);
+        return true;
+    }
     // line3D.h:82
     void compute3Dmodel(bool perform_diffusion = false) { report(l3d_line3d_compute3Dmodel(h_, perform_diffusion ? 1 : 0)); }
     // line3D.h:85
@@ -266,18 +315,20 @@ private:
     template <class Img, class = decltype(static_cast<const unsigned char*>(std::declval<const Img&>().data)),
               class = decltype(static_cast<size_t>(std::declval<const Img&>().step)), class = decltype(static_cast<int>(std::declval<const Img&>().channels()))>
     int add_from_image(detail::prio<1>, unsigned int imageID, const Img& image, const double* k, const double* r, const double* tt, const uint32_t* ids,
-                       const float* sims, int n, int maxImgWidth, bool loadAndStoreSegments)
+                       const float* sims, int n, int maxImgWidth, bool loadAndStoreSegments, const double* dist = nullptr)
     {
         const unsigned char* px = static_cast<const unsigned char*>(image.data);
         const size_t step = static_cast<size_t>(image.step);
         const int ch = static_cast<int>(image.channels()), w = (int)image.cols, h = (int)image.rows;
+        if (dist && sims) return l3d_line3d_add_image_pixels_fixed_sim_distorted(h_, imageID, px, w, h, ch, step, k, r, tt, dist, ids, sims, n, data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0);
+        if (dist) return l3d_line3d_add_image_pixels_distorted(h_, imageID, px, w, h, ch, step, k, r, tt, dist, ids, n, data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0);
         if (sims) return l3d_line3d_add_image_pixels_fixed_sim(h_, imageID, px, w, h, ch, step, k, r, tt, ids, sims, n, data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0);
         return l3d_line3d_add_image_pixels(h_, imageID, px, w, h, ch, step, k, r, tt, ids, n, data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0);
     }
     // `image` with a size only: the segment cache or nothing
     template <class Img>
     int add_from_image(detail::prio<0>, unsigned int imageID, const Img& image, const double* k, const double* r, const double* tt, const uint32_t* ids,
-                       const float* sims, int n, int maxImgWidth, bool loadAndStoreSegments)
+                       const float* sims, int n, int maxImgWidth, bool loadAndStoreSegments, const double* = nullptr)
     {
         const unsigned int w = image.cols > 0 ? (unsigned int)image.cols : 0u, h = image.rows > 0 ? (unsigned int)image.rows : 0u;
         if (sims) return l3d_line3d_add_image_fixed_sim_ex(h_, imageID, w, h, nullptr, 0, k, r, tt, ids, sims, n, data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0);

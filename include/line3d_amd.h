@@ -661,8 +661,8 @@ int l3d_line3d_stats(const l3d_line3d* h, double* stats12);
 /* =================================================================================================
  * SfM front ends of the reference's drivers: VisualSfM NVM (main_vsfm.cpp:121-223) and bundler
  * bundle.rd.out (main_bundler.cpp:110-204), reduced to what feeds Line3D::addImage -- focal length, R, t, distortion
- * coefficients, observed world point ids per camera.  Image decoding / undistortion stay outside (line segment
- * detection: l3d_detect_segments below).
+ * coefficients, observed world point ids per camera.  Image decoding stays outside (undistortion and line segment
+ * detection: l3d_undistort_image, l3d_detect_segments below).
  * A failed read still returns a scene object carrying the message (l3d_sfm_last_error); free it with l3d_sfm_free.
  * ================================================================================================= */
 typedef struct l3d_sfm_scene l3d_sfm_scene;
@@ -673,6 +673,10 @@ const char* l3d_sfm_last_error(const l3d_sfm_scene* scene);
 int l3d_sfm_num_cameras(const l3d_sfm_scene* scene);
 int l3d_sfm_num_points(const l3d_sfm_scene* scene);
 int l3d_sfm_camera(const l3d_sfm_scene* scene, int i, double* focal, double dist[2], double R[9], double t[3], int* n_worldpoints);
+/* the camera's radial coefficients (k1, k2) in OpenCV's convention, as the drivers hand them to initUndistortRectifyMap -- what the
+ * *_distorted calls below take.  A scene read from an NVM file: k1 = -d, k2 = 0 (main_vsfm.cpp:259); from a bundler file: k1 = d1,
+ * k2 = d2 (main_bundler.cpp:273-274); d, d1, d2 as l3d_sfm_camera returns them */
+int l3d_sfm_camera_cv_distortion(const l3d_sfm_scene* scene, int i, double k[2]);
 const char* l3d_sfm_camera_name(const l3d_sfm_scene* scene, int i);
 int l3d_sfm_camera_worldpoints(const l3d_sfm_scene* scene, int i, uint32_t* ids);
 /* the drivers' K from a focal length and the image size (main_vsfm.cpp:232-241): [[f,0,w/2],[0,f,h/2],[0,0,1]] */
@@ -739,10 +743,36 @@ int l3d_line3d_add_image_fixed_sim_ex(l3d_line3d* h, uint32_t image_id, unsigned
  *   selection   length > min_length, length descending (ties: smallest pixel index of the region), at most max_segments
  * Out (callee-allocated, l3d_free): 4 floats (x1, y1, x2, y2) per segment; *n = 0 when nothing is found.
  * Images below 8x8, channels other than 1 or 3, a stride below width x channels: L3D_ERR_INVALID.
- * Still outside the library: image decoding (JPEG / PNG), undistortion, the tclap command lines of the drivers.
+ * Still outside the library: image decoding (JPEG / PNG), the tclap command lines of the drivers.
  * ================================================================================================= */
 int l3d_detect_segments(l3d_ctx* ctx, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, int new_width, int new_height,
                         float min_length, int max_segments, float** segments, int* n);
+/* Undistortion on the device (k_det_undistort, l3d_detect.hip): what the drivers do to an image before addImage sees it
+ * (main_vsfm.cpp:243-270, main_bundler.cpp:256-284): cv::initUndistortRectifyMap(K, dist, I, K) + cv::remap(INTER_LINEAR, BORDER_CONSTANT),
+ * same size, same K.  fx, fy, cx, cy: the camera; k1, k2: OpenCV-convention radial coefficients (tangential terms and k3 are zero in both
+ * drivers; a scene file's own numbers become k1, k2 by l3d_sfm_camera_cv_distortion).  For output pixel (column j, row i), in double:
+ *     x = (j - cx) / fx            y = (i - cy) / fy
+ *     r2 = x x + y y               kr = 1 + (k2 r2 + k1) r2
+ *     u = fx (x kr) + cx           v = fy (y kr) + cy
+ * u not in (-1, width) or v not in (-1, height) (NaN included; tested before any conversion to an integer): 0 in every channel.
+ * Otherwise, per channel:
+ *     iu = rint(32 u), iv = rint(32 v)           (nearest, ties to even)
+ *     x0 = floor(iu / 32), a = iu - 32 x0        (a in 0..31 for negative iu as well); y0, b from iv likewise
+ *     out = ((32-a)(32-b) p(y0,x0) + a (32-b) p(y0,x0+1) + (32-a) b p(y0+1,x0) + a b p(y0+1,x0+1) + 512) >> 10
+ * with a tap outside the image counting as 0 (BORDER_CONSTANT, black).  This is remap's arithmetic on the 16SC2 fixed-point maps of the
+ * drivers' call: 5 fractional bits per coordinate, bilinear weights in 1/32768 -- exact for these products.  Byte identity with OpenCV is
+ * NOT claimed: OpenCV accumulates x incrementally along a row, so a pixel can differ where 32 u or 32 v falls within rounding of a half-integer.
+ * Both |k1| and |k2| <= 1e-12 (L3D_EPS, commons.h:66, the drivers' condition): nothing is launched, the pixels pass through untouched.
+ * Undistortion, rescale and grey stay three 8-bit roundings, like remap -> resize -> cvtColor.
+ *   l3d_undistort_image            host in, host out (`out`: height rows of width x channels bytes, `out_row_stride` apart; may be `pixels`
+ *                                  itself with the same stride).  An image below 1x1, channels other than 1 or 3, a stride below
+ *                                  width x channels, fx or fy zero or not finite: L3D_ERR_INVALID
+ *   l3d_detect_segments_distorted  l3d_detect_segments with the undistortion between the upload and the rescale; the segments are in
+ *                                  pixels of the undistorted image */
+int l3d_undistort_image(l3d_ctx* ctx, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, double fx, double fy, double cx, double cy,
+                        double k1, double k2, unsigned char* out, size_t out_row_stride);
+int l3d_detect_segments_distorted(l3d_ctx* ctx, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, int new_width, int new_height,
+                                  float min_length, int max_segments, double fx, double fy, double cx, double cy, double k1, double k2, float** segments, int* n);
 /* Line3D::addImage / addImage_fixed_sim from pixels (line3D.cc:95-217, 220-324): cache present and load_and_store != 0: the cache is
  * loaded; otherwise the segments are detected (rescaled by the max_img_width rule, min_length = 0.005 sqrt(rows^2 + cols^2), at most 3000) and,
  * with load_and_store != 0, the cache is written; load_and_store == 0 removes a stale cache first.  No segment found: L3D_OK and no view
@@ -753,6 +783,19 @@ int l3d_line3d_add_image_pixels(l3d_line3d* h, uint32_t image_id, const unsigned
 int l3d_line3d_add_image_pixels_fixed_sim(l3d_line3d* h, uint32_t image_id, const unsigned char* pixels, int width, int height, int channels, size_t row_stride,
                                           const double* K, const double* R, const double* t, const uint32_t* sim_ids, const float* sims, int n_sims,
                                           const char* data_directory, int max_img_width, int load_and_store);
+/* The same with the drivers' undistort block in front of the detector (main_vsfm.cpp:243-273): dist = (k1, k2) as above; fx, fy, cx, cy are
+ * K[0], K[4], K[2], K[5] of the full-resolution K the caller passes, which the view keeps (the drivers undistort onto the same K).  Both
+ * coefficients within 1e-12: the calls above.  Non-zero coefficients with K[1] != 0 (skew): L3D_ERR_UNSUPPORTED.  The cache behaviour is
+ * unchanged: a cache that is present and wanted is loaded and the pixels are not touched (line3D.cc:143-168).  On a node object the work is
+ * done once, on rank 0's device.  l3d_line3d_undistort_image: l3d_undistort_image with the object's device and K. */
+int l3d_line3d_add_image_pixels_distorted(l3d_line3d* h, uint32_t image_id, const unsigned char* pixels, int width, int height, int channels, size_t row_stride,
+                                          const double* K, const double* R, const double* t, const double dist[2], const uint32_t* worldpoint_ids, int n_worldpoints,
+                                          const char* data_directory, int max_img_width, int load_and_store);
+int l3d_line3d_add_image_pixels_fixed_sim_distorted(l3d_line3d* h, uint32_t image_id, const unsigned char* pixels, int width, int height, int channels, size_t row_stride,
+                                                    const double* K, const double* R, const double* t, const double dist[2], const uint32_t* sim_ids, const float* sims,
+                                                    int n_sims, const char* data_directory, int max_img_width, int load_and_store);
+int l3d_line3d_undistort_image(l3d_line3d* h, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, const double* K, double k1, double k2,
+                               unsigned char* out, size_t out_row_stride);
 
 
 /* The detector's stages on their own, exported for tests (tests/test_gpu_detect_stages.py): the same kernels with the same launch shapes

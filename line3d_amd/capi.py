@@ -181,17 +181,36 @@ class Context:
         self._chk(self.lib.l3d_register_segments(self.h, _p(segs), C.c_int(len(segs))))
 
     # -- line segment detection (l3d_detect.hip) --------------------------------------------------
-    def detect_segments(self, img, new_size=None, min_length=None, max_segments=3000):
+    def undistort(self, img, K, k1, k2):
+        """l3d_undistort_image: uint8 image H x W or H x W x 3 -> the undistorted image, same shape (initUndistortRectifyMap + remap of the drivers,
+        the formulas of include/line3d_amd.h).  K: 3 x 3, its fx, fy, cx, cy are used; k1, k2: OpenCV-convention radial coefficients."""
+        pix, w, h, ch, stride = image_arguments(img)
+        K = np.asarray(K, dtype=np.float64).reshape(3, 3)
+        out = np.zeros(np.asarray(img).shape, np.uint8)
+        self._chk(self.lib.l3d_undistort_image(self.h, pix, C.c_int(w), C.c_int(h), C.c_int(ch), C.c_size_t(stride), C.c_double(K[0, 0]), C.c_double(K[1, 1]),
+                                               C.c_double(K[0, 2]), C.c_double(K[1, 2]), C.c_double(float(k1)), C.c_double(float(k2)), _p(out),
+                                               C.c_size_t(w * ch)))
+        return out
+
+    def detect_segments(self, img, new_size=None, min_length=None, max_segments=3000, camera=None):
         """l3d_detect_segments: uint8 image H x W or H x W x 3 (contiguous pixels, rows contiguous or strided) -> (n, 4) float32 segments
         (x1, y1, x2, y2) in pixels of `img`, longest first.  new_size = (width, height) the detector works at (None: the image's own);
-        min_length None: the reference's 0.005 x the image diagonal."""
+        min_length None: the reference's 0.005 x the image diagonal.  camera = (fx, fy, cx, cy, k1, k2): the image is undistorted on the device
+        first (l3d_detect_segments_distorted) and the segments are in pixels of the undistorted image."""
         pix, w, h, ch, stride = image_arguments(img)
         nw, nh = (w, h) if new_size is None else (int(new_size[0]), int(new_size[1]))
         if min_length is None:
             min_length = float(np.float32(0.005) * np.sqrt(np.float32(h * h + w * w)))
         out, n = C.POINTER(C.c_float)(), C.c_int(0)
-        self._chk(self.lib.l3d_detect_segments(self.h, pix, C.c_int(w), C.c_int(h), C.c_int(ch), C.c_size_t(stride), C.c_int(nw), C.c_int(nh),
-                                               C.c_float(min_length), C.c_int(int(max_segments)), C.byref(out), C.byref(n)))
+        if camera is not None:
+            cam = [C.c_double(float(v)) for v in camera]
+            if len(cam) != 6:
+                raise ValueError("camera must be (fx, fy, cx, cy, k1, k2)")
+            self._chk(self.lib.l3d_detect_segments_distorted(self.h, pix, C.c_int(w), C.c_int(h), C.c_int(ch), C.c_size_t(stride), C.c_int(nw), C.c_int(nh),
+                                                             C.c_float(min_length), C.c_int(int(max_segments)), *cam, C.byref(out), C.byref(n)))
+        else:
+            self._chk(self.lib.l3d_detect_segments(self.h, pix, C.c_int(w), C.c_int(h), C.c_int(ch), C.c_size_t(stride), C.c_int(nw), C.c_int(nh),
+                                                   C.c_float(min_length), C.c_int(int(max_segments)), C.byref(out), C.byref(n)))
         segs = np.ctypeslib.as_array(out, (n.value, 4)).copy() if n.value else np.zeros((0, 4), np.float32)
         self.lib.l3d_free(out)
         return segs

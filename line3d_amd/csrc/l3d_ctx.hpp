@@ -137,11 +137,12 @@ struct FillPart { int h0 = 0, h1 = 0; unsigned long long pos_base = 0; const int
 
 // scratch of the line segment detector (l3d_detect.hip): sized to the largest image seen, reused across calls
 struct DetectBufs {
-    DevBuf pixels, grey, aux, img, mod, ang, bucket, active, parent, size, count, keys, keys2, vals, vals2, flag, pos, start, tmp, cand, ckeys, ckeys2, cvals, cvals2, out, ktab, scal;
+    // undist: the undistorted image (k_det_undistort), reserved only when an image comes with distortion coefficients
+    DevBuf pixels, undist, grey, aux, img, mod, ang, bucket, active, parent, size, count, keys, keys2, vals, vals2, flag, pos, start, tmp, cand, ckeys, ckeys2, cvals, cvals2, out, ktab, scal;
     int tab_w = 0, tab_h = 0;       // the image size the Gaussian sampler's tables in `ktab` were made for
     void release()
     {
-        DevBuf* b[] = { &pixels, &grey, &aux, &img, &mod, &ang, &bucket, &active, &parent, &size, &count, &keys, &keys2, &vals, &vals2, &flag, &pos, &start, &tmp, &cand, &ckeys, &ckeys2, &cvals, &cvals2, &out, &ktab, &scal };
+        DevBuf* b[] = { &pixels, &undist, &grey, &aux, &img, &mod, &ang, &bucket, &active, &parent, &size, &count, &keys, &keys2, &vals, &vals2, &flag, &pos, &start, &tmp, &cand, &ckeys, &ckeys2, &cvals, &cvals2, &out, &ktab, &scal };
         for (DevBuf* x : b) x->release();
         tab_w = tab_h = 0;
     }

@@ -64,6 +64,36 @@ __global__ void k_det_grey(const unsigned char* __restrict__ px, int w, int h, i
     grey[(size_t)y * nw + x] = (float)g;
 }
 
+// ---- undistortion (radial k1, k2), in front of the rescale: the formulas stated in include/line3d_amd.h.  One thread per output pixel, the map in
+// doubles (none is stored), 5 fractional bits per coordinate, the four taps weighted in 1/1024 with black outside the image.  Blocks are 32 x 8:
+// the taps of a wave lie within a few source rows
+constexpr int kUndBx = 32, kUndBy = 8;
+__global__ __launch_bounds__(256) void k_det_undistort(const unsigned char* __restrict__ src, int w, int h, int ch, DetCamera cam, unsigned char* __restrict__ dst)
+{
+    const int j = blockIdx.x * kUndBx + threadIdx.x, i = blockIdx.y * kUndBy + threadIdx.y;
+    if (j >= w || i >= h) return;
+    const double x = ((double)j - cam.cx) / cam.fx, y = ((double)i - cam.cy) / cam.fy;
+    const double r2 = x * x + y * y, kr = 1.0 + (cam.k2 * r2 + cam.k1) * r2;
+    const double u = cam.fx * (x * kr) + cam.cx, v = cam.fy * (y * kr) + cam.cy;
+    unsigned char* o = dst + ((size_t)i * w + j) * ch;
+    if (!(u > -1.0 && u < (double)w && v > -1.0 && v < (double)h)) {         // NaN lands here; tested before any conversion to an integer
+        for (int k = 0; k < ch; ++k) o[k] = 0;
+        return;
+    }
+    const int iu = (int)rint(32.0 * u), iv = (int)rint(32.0 * v);             // in [-32, 32 w] x [-32, 32 h]
+    const int x0 = iu >> 5, a = iu & 31, y0 = iv >> 5, b = iv & 31;           // floor and remainder, for negative values as well
+    const bool cx0 = x0 >= 0 && x0 < w, cx1 = x0 + 1 >= 0 && x0 + 1 < w, ry0 = y0 >= 0 && y0 < h, ry1 = y0 + 1 >= 0 && y0 + 1 < h;
+    const int w00 = (32 - a) * (32 - b), w01 = a * (32 - b), w10 = (32 - a) * b, w11 = a * b;
+    const unsigned char* r0 = src + (size_t)(ry0 ? y0 : 0) * w * ch;
+    const unsigned char* r1 = src + (size_t)(ry1 ? y0 + 1 : 0) * w * ch;
+    const size_t c0 = (size_t)(cx0 ? x0 : 0) * ch, c1 = (size_t)(cx1 ? x0 + 1 : 0) * ch;
+    for (int k = 0; k < ch; ++k) {
+        const int p00 = ry0 && cx0 ? r0[c0 + k] : 0, p01 = ry0 && cx1 ? r0[c1 + k] : 0;
+        const int p10 = ry1 && cx0 ? r1[c0 + k] : 0, p11 = ry1 && cx1 ? r1[c1 + k] : 0;
+        o[k] = (unsigned char)((w00 * p00 + w01 * p01 + w10 * p10 + w11 * p11 + 512) >> 10);
+    }
+}
+
 // ---- Gaussian sub-sampling, separable, 7 taps; centres and weights per output column / row come from the host (computed as the
 // detector computes them); symmetric boundary
 __device__ inline int sym_index(int j, int n)
@@ -497,7 +527,7 @@ void plan_scaled(DetPlan& p, int N, int M)
     while ((1ull << p.key_bits) <= 2ull * (unsigned long long)p.np) ++p.key_bits;
 }
 
-int det_reserve(l3d_ctx* c, const DetPlan& p, int max_segments)
+int det_reserve(l3d_ctx* c, const DetPlan& p, int max_segments, bool undist = false)
 {
     hipStream_t st = c->stream;
     DetectBufs& d = c->det;
@@ -507,6 +537,7 @@ int det_reserve(l3d_ctx* c, const DetPlan& p, int max_segments)
     HIPCHK(c, sort_pairs_u64_u32(nullptr, sort2_bytes, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, (const unsigned*)nullptr, (unsigned*)nullptr, cand_cap, 0, 64, st));
     HIPCHK(c, exclusive_sum_int(nullptr, scan_bytes, (const int*)nullptr, (int*)nullptr, np + 1, st));
     HIPCHK(c, d.pixels.reserve((size_t)p.w * p.h * p.ch));
+    if (undist) HIPCHK(c, d.undist.reserve((size_t)p.w * p.h * p.ch));
     HIPCHK(c, d.grey.reserve((size_t)p.nw * p.nh * 4));
     HIPCHK(c, d.aux.reserve((size_t)p.N * p.nh * 8));
     HIPCHK(c, d.img.reserve((size_t)np * 8));
@@ -535,8 +566,25 @@ int det_reserve(l3d_ctx* c, const DetPlan& p, int max_segments)
     return L3D_OK;
 }
 
-// ---- pixel stage: upload, rescale + grey, the two sampler passes, gradient; leaves the scalars zeroed
-int det_pixel_stage(l3d_ctx* c, const DetPlan& p, const unsigned char* pixels, size_t stride)
+// the camera of an undistortion: fx, fy finite and not zero; *active: a coefficient above L3D_EPS (commons.h:66, the drivers' condition) -- otherwise
+// nothing is launched and the pixels pass through
+constexpr double kDistEps = 1e-12;
+int check_camera(l3d_ctx* c, const DetCamera& cam, int w, int h, bool* active)
+{
+    if (w > (1 << 24) || h > (1 << 24)) return fail(c, L3D_ERR_UNSUPPORTED, "undistort: image too large");      // 32 x a coordinate stays an int
+    if (!std::isfinite(cam.fx) || !std::isfinite(cam.fy) || cam.fx == 0.0 || cam.fy == 0.0) return fail(c, L3D_ERR_INVALID, "undistort: fx and fy must be finite and not zero");
+    *active = !(fabs(cam.k1) <= kDistEps && fabs(cam.k2) <= kDistEps);
+    return L3D_OK;
+}
+void launch_undistort(l3d_ctx* c, int w, int h, int ch, const DetCamera& cam)
+{
+    DetectBufs& d = c->det;
+    ProfScope ps(c, "k_det_undistort");
+    hipLaunchKernelGGL(k_det_undistort, dim3((w + kUndBx - 1) / kUndBx, (h + kUndBy - 1) / kUndBy), dim3(kUndBx, kUndBy), 0, c->stream, d.pixels.as<unsigned char>(), w, h, ch, cam, d.undist.as<unsigned char>());
+}
+
+// ---- pixel stage: upload, undistortion (cam: null or inactive = none), rescale + grey, the two sampler passes, gradient; leaves the scalars zeroed
+int det_pixel_stage(l3d_ctx* c, const DetPlan& p, const unsigned char* pixels, size_t stride, const DetCamera* cam = nullptr)
 {
     hipStream_t st = c->stream;
     DetectBufs& d = c->det;
@@ -557,7 +605,9 @@ int det_pixel_stage(l3d_ctx* c, const DetPlan& p, const unsigned char* pixels, s
     const int* kc = reinterpret_cast<const int*>(static_cast<const char*>(d.ktab.p) + ((size_t)N + M) * kTaps * 8);
     HIPCHK(c, hipMemcpy2DAsync(d.pixels.p, (size_t)w * ch, pixels, stride, (size_t)w * ch, (size_t)h, hipMemcpyHostToDevice, st));
     const dim3 b256(256);
-    { ProfScope ps(c, "k_det_grey"); hipLaunchKernelGGL(k_det_grey, dim3((nw + 255) / 256, nh), b256, 0, st, d.pixels.as<unsigned char>(), w, h, ch, nw, nh, d.grey.as<float>()); }
+    const unsigned char* image = d.pixels.as<unsigned char>();          // whichever buffer holds the image k_det_grey reads
+    if (cam) { launch_undistort(c, w, h, ch, *cam); image = d.undist.as<unsigned char>(); }
+    { ProfScope ps(c, "k_det_grey"); hipLaunchKernelGGL(k_det_grey, dim3((nw + 255) / 256, nh), b256, 0, st, image, w, h, ch, nw, nh, d.grey.as<float>()); }
     { ProfScope ps(c, "k_det_gauss_x"); hipLaunchKernelGGL(k_det_gauss_x, dim3((N + 63) / 64, (nh + 3) / 4), dim3(64, 4), 0, st, d.grey.as<float>(), nw, nh, d.aux.as<double>(), N, kc, kw); }
     { ProfScope ps(c, "k_det_gauss_y"); hipLaunchKernelGGL(k_det_gauss_y, dim3((N + 63) / 64, (M + kYRows - 1) / kYRows), dim3(64, 4), 0, st, d.aux.as<double>(), N, nh, d.img.as<double>(), M, kc + N, kw + (size_t)N * kTaps); }
     { ProfScope ps(c, "k_det_grad"); hipLaunchKernelGGL(k_det_grad, dim3((N + 255) / 256, M), b256, 0, st, d.img.as<double>(), N, M, p.rho, d.mod.as<double>(), d.ang.as<double>(), d.bucket.as<uchar2>(), d.active.as<unsigned char>()); }
@@ -634,22 +684,25 @@ int plan_image(l3d_ctx* c, DetPlan& p, const unsigned char* pixels, int w, int h
 }  // namespace
 
 int detect_segments(l3d_ctx* c, const unsigned char* pixels, int w, int h, int ch, size_t stride, int nw, int nh, float min_length, int max_segments,
-                    std::vector<float>& out)
+                    std::vector<float>& out, const DetCamera* cam)
 {
     out.clear();
     if (!c) return L3D_ERR_INVALID;
     if (max_segments < 0) return fail(c, L3D_ERR_INVALID, "detect_segments: negative max_segments");
     DetPlan plan;
     if (int rc = plan_image(c, plan, pixels, w, h, ch, stride, nw, nh)) return rc;
+    bool undist = false;
+    if (cam) { if (int rc = check_camera(c, *cam, w, h, &undist)) return rc; }
+    if (!undist) cam = nullptr;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     DetectBufs& d = c->det;
-    if (int rc = det_reserve(c, plan, max_segments)) return rc;
+    if (int rc = det_reserve(c, plan, max_segments, undist)) return rc;
     int* scal = d.scal.as<int>();
     const int cand_cap = plan.cand_cap;
     const float up = plan.up;
     const dim3 b256(256);
-    if (int rc = det_pixel_stage(c, plan, pixels, stride)) return rc;
+    if (int rc = det_pixel_stage(c, plan, pixels, stride, cam)) return rc;
 
     // ---- rounds: label, vote, sort, regions
     for (int round = 0; round < kRounds; ++round) {
@@ -676,16 +729,48 @@ int detect_segments(l3d_ctx* c, const unsigned char* pixels, int w, int h, int c
     return L3D_OK;
 }
 
+// host in, host out: upload, k_det_undistort, download (the detector's two image buffers)
+int undistort_image(l3d_ctx* c, const unsigned char* pixels, int w, int h, int ch, size_t stride, const DetCamera& cam, unsigned char* out, size_t out_stride)
+{
+    if (!c) return L3D_ERR_INVALID;
+    if (!pixels || !out || w < 1 || h < 1 || (ch != 1 && ch != 3) || stride < (size_t)w * ch || out_stride < (size_t)w * ch)
+        return fail(c, L3D_ERR_INVALID, "undistort: needs an image of at least 1x1 with 1 or 3 channels and row strides of at least width x channels");
+    if ((long long)w * h * ch > (1ll << 31)) return fail(c, L3D_ERR_UNSUPPORTED, "undistort: image too large");
+    bool active = false;
+    if (int rc = check_camera(c, cam, w, h, &active)) return rc;
+    const size_t row = (size_t)w * ch;
+    if (!active) {
+        if (out != pixels || out_stride != stride)
+            for (int i = 0; i < h; ++i) memmove(out + (size_t)i * out_stride, pixels + (size_t)i * stride, row);
+        return L3D_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    DetectBufs& d = c->det;
+    HIPCHK(c, d.pixels.reserve(row * h));
+    HIPCHK(c, d.undist.reserve(row * h));
+    HIPCHK(c, hipMemcpy2DAsync(d.pixels.p, row, pixels, stride, row, (size_t)h, hipMemcpyHostToDevice, c->stream));
+    launch_undistort(c, w, h, ch, cam);
+    HIPCHK(c, hipMemcpy2DAsync(out, out_stride, d.undist.p, row, row, (size_t)h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return L3D_OK;
+}
+
 }  // namespace l3d
 
-int l3d_detect_segments(l3d_ctx* c, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, int new_width, int new_height,
-                        float min_length, int max_segments, float** segments, int* n)
+int l3d_undistort_image(l3d_ctx* c, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, double fx, double fy, double cx, double cy,
+                        double k1, double k2, unsigned char* out, size_t out_row_stride)
+{
+    return l3d::undistort_image(c, pixels, width, height, channels, row_stride, l3d::DetCamera{ fx, fy, cx, cy, k1, k2 }, out, out_row_stride);
+}
+
+static int detect_to_c(l3d_ctx* c, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, int new_width, int new_height,
+                       float min_length, int max_segments, const l3d::DetCamera* cam, float** segments, int* n)
 {
     if (!c || !segments || !n) return L3D_ERR_INVALID;
     *segments = nullptr;
     *n = 0;
     std::vector<float> out;
-    const int rc = l3d::detect_segments(c, pixels, width, height, channels, row_stride, new_width, new_height, min_length, max_segments, out);
+    const int rc = l3d::detect_segments(c, pixels, width, height, channels, row_stride, new_width, new_height, min_length, max_segments, out, cam);
     if (rc != L3D_OK) return rc;
     *n = (int)(out.size() / 4);
     float* p = static_cast<float*>(malloc(std::max<size_t>(16, out.size() * 4)));
@@ -693,6 +778,19 @@ int l3d_detect_segments(l3d_ctx* c, const unsigned char* pixels, int width, int 
     if (!out.empty()) memcpy(p, out.data(), out.size() * 4);
     *segments = p;
     return L3D_OK;
+}
+
+int l3d_detect_segments_distorted(l3d_ctx* c, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, int new_width, int new_height,
+                                  float min_length, int max_segments, double fx, double fy, double cx, double cy, double k1, double k2, float** segments, int* n)
+{
+    const l3d::DetCamera cam{ fx, fy, cx, cy, k1, k2 };
+    return detect_to_c(c, pixels, width, height, channels, row_stride, new_width, new_height, min_length, max_segments, &cam, segments, n);
+}
+
+int l3d_detect_segments(l3d_ctx* c, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, int new_width, int new_height,
+                        float min_length, int max_segments, float** segments, int* n)
+{
+    return detect_to_c(c, pixels, width, height, channels, row_stride, new_width, new_height, min_length, max_segments, nullptr, segments, n);
 }
 
 // ---- the stages on their own, for the tests: the functions above (the same kernels and launch shapes as l3d_detect_segments), results copied out

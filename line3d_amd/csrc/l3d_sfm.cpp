@@ -1,8 +1,8 @@
 // l3d_sfm.cpp -- SfM front ends of the reference's two drivers without tclap / OpenCV / boost:
 // the VisualSfM NVM reader of main_vsfm.cpp:121-223 and the bundler reader of main_bundler.cpp:110-204, reduced to what
 // feeds Line3D::addImage: per camera focal length, rotation, translation, distortion coefficients and the list of
-// world points it observes (the similarity source of findVisualNeighbors, line3D.cc:1874-1935).  Image decoding,
-// undistortion and the LSD detector stay outside (segments are inputs); a camera's K is built by the caller from the
+// world points it observes (the similarity source of findVisualNeighbors, line3D.cc:1874-1935).  Image decoding
+// stays outside (undistortion and the detector: l3d_detect.hip, l3d_line3d_add_image_pixels_distorted); a camera's K is built by the caller from the
 // focal length and the image size the way the drivers do it (main_vsfm.cpp:232-241): [[f,0,w/2],[0,f,h/2],[0,0,1]].
 //
 // Parsing follows the drivers' own token order, including what they skip (header lines, the separator line before the
@@ -19,8 +19,9 @@
 
 struct l3d_sfm_scene {
     int n_cams = 0, n_points = 0;
+    bool nvm = false;                               // read from an NVM file: one coefficient, of the opposite sign (l3d_sfm_camera_cv_distortion)
     std::vector<double> focal, dist, R, t;          // n, 2n, 9n (row-major), 3n
-    std::vector<std::string> names;                 // image file names (NVM) or "" (bundler: %08d.jpg by convention)
+    std::vector<std::string> names;                 // image file names (NVM) or "%08d" of the camera index (bundler: visualize/%08d.jpg by convention)
     std::vector<std::vector<uint32_t>> wps;         // per camera: world point ids in file order
     std::string err;
 };
@@ -45,6 +46,7 @@ int l3d_sfm_read_nvm(const char* path, l3d_sfm_scene** out)
 {
     if (!path || !out) return L3D_ERR_INVALID;
     l3d_sfm_scene* s = new l3d_sfm_scene();
+    s->nvm = true;
     std::ifstream f(path);
     if (!f.is_open()) return fail(s, std::string("NVM file ") + path + " does not exist!", out);
     std::string line;
@@ -178,6 +180,15 @@ int l3d_sfm_camera(const l3d_sfm_scene* s, int i, double* focal, double dist[2],
     if (R) memcpy(R, &s->R[9 * (size_t)i], 72);
     if (t) memcpy(t, &s->t[3 * (size_t)i], 24);
     if (n_worldpoints) *n_worldpoints = (int)s->wps[(size_t)i].size();
+    return L3D_OK;
+}
+// the coefficients the drivers hand to OpenCV: NVM -d, 0 (main_vsfm.cpp:259); bundler d1, d2 (main_bundler.cpp:273-274)
+int l3d_sfm_camera_cv_distortion(const l3d_sfm_scene* s, int i, double k[2])
+{
+    if (!s || i < 0 || i >= s->n_cams || !k) return L3D_ERR_INVALID;
+    const double d1 = s->dist[2 * (size_t)i], d2 = s->dist[2 * (size_t)i + 1];
+    k[0] = s->nvm ? -d1 : d1;
+    k[1] = s->nvm ? 0.0 : d2;
     return L3D_OK;
 }
 const char* l3d_sfm_camera_name(const l3d_sfm_scene* s, int i) { return (s && i >= 0 && i < s->n_cams) ? s->names[(size_t)i].c_str() : ""; }

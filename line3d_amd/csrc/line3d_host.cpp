@@ -824,8 +824,9 @@ int l3d_line3d_add_image_fixed_sim_ex(l3d_line3d* h, uint32_t id, unsigned width
 
 // addImage / addImage_fixed_sim from pixels, line3D.cc:128-191: the cache decides first; without a usable cache the segments are detected on the
 // device and enter the calls above.  Returns 1: go on with `segs` (possibly none: the cache will be loaded), 0: no segment found, no view; < 0: error negated
+// cam: null, or the camera the pixels are undistorted with before the detector sees them (main_vsfm.cpp:243-270)
 static int detect_for_add(l3d_line3d* h, uint32_t id, const unsigned char* pixels, int width, int height, int channels, size_t row_stride,
-                          const char* data_directory, int max_img_width, int load_and_store, std::vector<float>& segs)
+                          const char* data_directory, int max_img_width, int load_and_store, std::vector<float>& segs, const l3d::DetCamera* cam = nullptr)
 {
     segs.clear();
     L* owner = h->node ? rank0(h) : h;
@@ -843,7 +844,7 @@ static int detect_for_add(l3d_line3d* h, uint32_t id, const unsigned char* pixel
     if (f) { fclose(f); if (load_and_store) return 1; }                                     // :159-168: the cache stands in for the image
     if (!owner->ctx) return -h->fail(L3D_ERR_INVALID, "no device context to detect line segments with");
     const float min_length = 0.005f * sqrtf(float(height * height + width * width));         // :176, commons.h:43
-    const int rc = l3d::detect_segments(owner->ctx, pixels, width, height, channels, row_stride, (int)new_w, (int)new_h, min_length, 3000, segs);
+    const int rc = l3d::detect_segments(owner->ctx, pixels, width, height, channels, row_stride, (int)new_w, (int)new_h, min_length, 3000, segs, cam);
     if (rc != L3D_OK) return -h->fail(rc, l3d_last_error(owner->ctx));
     if (segs.empty()) { if (f && !load_and_store) remove(file.c_str()); return 0; }          // :153-156, :186-190
     return 1;
@@ -870,6 +871,63 @@ int l3d_line3d_add_image_pixels_fixed_sim(l3d_line3d* h, uint32_t id, const unsi
     if (go <= 0) return -go;
     return l3d_line3d_add_image_fixed_sim_ex(h, id, (unsigned)width, (unsigned)height, segs.empty() ? nullptr : segs.data(), (int)(segs.size() / 4), K, R, t, sim_ids, sims,
                                              n_sims, data_directory, max_img_width, load_and_store);
+}
+
+// the camera of the _distorted entry points: fx, fy, cx, cy from the full-resolution K, as in the drivers (main_vsfm.cpp:250-262).  Returns 1 with
+// `cam` filled, 0 when both coefficients are within L3D_EPS (the plain path), < 0: error negated
+static int camera_for_add(l3d_line3d* h, const double* K, const double* dist, l3d::DetCamera& cam)
+{
+    if (!K) return -h->fail(L3D_ERR_INVALID, "undistortion: K is null");
+    if (!dist) return -h->fail(L3D_ERR_INVALID, "undistortion: dist (k1, k2) is null");
+    if (std::fabs(dist[0]) <= 1e-12 && std::fabs(dist[1]) <= 1e-12) return 0;
+    if (K[1] != 0.0) return -h->fail(L3D_ERR_UNSUPPORTED, "lens distortion with a skewed K (K[1] != 0) is not supported");
+    cam = l3d::DetCamera{ K[0], K[4], K[2], K[5], dist[0], dist[1] };
+    return 1;
+}
+
+int l3d_line3d_add_image_pixels_distorted(l3d_line3d* h, uint32_t id, const unsigned char* pixels, int width, int height, int channels, size_t row_stride,
+                                          const double* K, const double* R, const double* t, const double dist[2], const uint32_t* worldpoints, int n_wps,
+                                          const char* data_directory, int max_img_width, int load_and_store)
+{
+    if (!h) return L3D_ERR_INVALID;
+    l3d::DetCamera cam;
+    const int with = camera_for_add(h, K, dist, cam);
+    if (with < 0) return -with;
+    std::vector<float> segs;
+    const int go = detect_for_add(h, id, pixels, width, height, channels, row_stride, data_directory, max_img_width, load_and_store, segs, with ? &cam : nullptr);
+    if (go <= 0) return -go;
+    return l3d_line3d_add_image_ex(h, id, (unsigned)width, (unsigned)height, segs.empty() ? nullptr : segs.data(), (int)(segs.size() / 4), K, R, t, worldpoints, n_wps,
+                                   data_directory, max_img_width, load_and_store);
+}
+
+int l3d_line3d_add_image_pixels_fixed_sim_distorted(l3d_line3d* h, uint32_t id, const unsigned char* pixels, int width, int height, int channels, size_t row_stride,
+                                                    const double* K, const double* R, const double* t, const double dist[2], const uint32_t* sim_ids, const float* sims,
+                                                    int n_sims, const char* data_directory, int max_img_width, int load_and_store)
+{
+    if (!h) return L3D_ERR_INVALID;
+    l3d::DetCamera cam;
+    const int with = camera_for_add(h, K, dist, cam);
+    if (with < 0) return -with;
+    std::vector<float> segs;
+    const int go = detect_for_add(h, id, pixels, width, height, channels, row_stride, data_directory, max_img_width, load_and_store, segs, with ? &cam : nullptr);
+    if (go <= 0) return -go;
+    return l3d_line3d_add_image_fixed_sim_ex(h, id, (unsigned)width, (unsigned)height, segs.empty() ? nullptr : segs.data(), (int)(segs.size() / 4), K, R, t, sim_ids, sims,
+                                             n_sims, data_directory, max_img_width, load_and_store);
+}
+
+// the drivers' undistort block on its own (main_vsfm.cpp:243-270) with the object's device (a node object: rank 0's)
+int l3d_line3d_undistort_image(l3d_line3d* h, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, const double* K, double k1, double k2,
+                               unsigned char* out, size_t out_row_stride)
+{
+    if (!h) return L3D_ERR_INVALID;
+    L* owner = h->node ? rank0(h) : h;
+    if (!owner->ctx) return h->fail(L3D_ERR_INVALID, "no device context to undistort with");
+    const double dist[2] = { k1, k2 };
+    l3d::DetCamera cam{ 1.0, 1.0, 0.0, 0.0, 0.0, 0.0 };
+    const int with = camera_for_add(h, K, dist, cam);
+    if (with < 0) return -with;
+    const int rc = l3d::undistort_image(owner->ctx, pixels, width, height, channels, row_stride, cam, out, out_row_stride);
+    return rc == L3D_OK ? rc : h->fail(rc, l3d_last_error(owner->ctx));
 }
 
 int l3d_line3d_num_cameras(const l3d_line3d* h) { return !h ? 0 : h->node ? l3d_line3d_num_cameras(rank0(h)) : (int)h->views.size(); }

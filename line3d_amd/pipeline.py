@@ -142,24 +142,38 @@ class Line3D:
                                                   C.c_int(int(loadAndStoreSegments)))
         return rc == 0
 
-    def add_image_pixels(self, imageID, img, K, R, t, worldpointIDs, maxImgWidth=1920, loadAndStoreSegments=True):
+    def add_image_pixels(self, imageID, img, K, R, t, worldpointIDs, maxImgWidth=1920, loadAndStoreSegments=True, dist=None):
         """Line3D::addImage from pixels (l3d_line3d_add_image_pixels): uint8 image H x W or H x W x 3.  The segment cache in `data_directory` is
         loaded when present (and loadAndStoreSegments); otherwise the segments are detected on the device, and the cache written or a stale one
-        removed.  An image without segments adds no view and is no error (line3D.cc:186-190)."""
+        removed.  An image without segments adds no view and is no error (line3D.cc:186-190).  dist = (k1, k2), OpenCV-convention radial
+        coefficients: the image is undistorted on the device with K before the detector sees it (l3d_line3d_add_image_pixels_distorted)."""
         pix, w, h, ch, stride = capi.image_arguments(img)
         K, R, t = (np.ascontiguousarray(a, dtype=np.float64) for a in (K, R, t))
         wps = np.ascontiguousarray(list(worldpointIDs), dtype=np.uint32)
+        if dist is not None:
+            d = np.ascontiguousarray(dist, dtype=np.float64).reshape(2)
+            rc = self.lib.l3d_line3d_add_image_pixels_distorted(self.h, C.c_uint32(imageID), pix, C.c_int(w), C.c_int(h), C.c_int(ch), C.c_size_t(stride), _p(K), _p(R),
+                                                                _p(t), _p(d), _p(wps), C.c_int(len(wps)), C.c_char_p(self.data_directory.encode()),
+                                                                C.c_int(maxImgWidth), C.c_int(int(loadAndStoreSegments)))
+            return rc == 0
         rc = self.lib.l3d_line3d_add_image_pixels(self.h, C.c_uint32(imageID), pix, C.c_int(w), C.c_int(h), C.c_int(ch), C.c_size_t(stride), _p(K), _p(R), _p(t),
                                                   _p(wps), C.c_int(len(wps)), C.c_char_p(self.data_directory.encode()), C.c_int(maxImgWidth),
                                                   C.c_int(int(loadAndStoreSegments)))
         return rc == 0
 
-    def add_image_pixels_fixed_sim(self, imageID, img, K, R, t, viewSimilarity, maxImgWidth=1920, loadAndStoreSegments=True):
-        """Line3D::addImage_fixed_sim from pixels (l3d_line3d_add_image_pixels_fixed_sim)"""
+    def add_image_pixels_fixed_sim(self, imageID, img, K, R, t, viewSimilarity, maxImgWidth=1920, loadAndStoreSegments=True, dist=None):
+        """Line3D::addImage_fixed_sim from pixels (l3d_line3d_add_image_pixels_fixed_sim); dist as in add_image_pixels"""
         pix, w, h, ch, stride = capi.image_arguments(img)
         K, R, t = (np.ascontiguousarray(a, dtype=np.float64) for a in (K, R, t))
         ids = np.ascontiguousarray(sorted(viewSimilarity), dtype=np.uint32)
         sims = np.ascontiguousarray([viewSimilarity[int(i)] for i in ids], dtype=np.float32)
+        if dist is not None:
+            d = np.ascontiguousarray(dist, dtype=np.float64).reshape(2)
+            rc = self.lib.l3d_line3d_add_image_pixels_fixed_sim_distorted(self.h, C.c_uint32(imageID), pix, C.c_int(w), C.c_int(h), C.c_int(ch), C.c_size_t(stride),
+                                                                          _p(K), _p(R), _p(t), _p(d), _p(ids), _p(sims), C.c_int(len(ids)),
+                                                                          C.c_char_p(self.data_directory.encode()), C.c_int(maxImgWidth),
+                                                                          C.c_int(int(loadAndStoreSegments)))
+            return rc == 0
         rc = self.lib.l3d_line3d_add_image_pixels_fixed_sim(self.h, C.c_uint32(imageID), pix, C.c_int(w), C.c_int(h), C.c_int(ch), C.c_size_t(stride), _p(K), _p(R),
                                                             _p(t), _p(ids), _p(sims), C.c_int(len(ids)), C.c_char_p(self.data_directory.encode()),
                                                             C.c_int(maxImgWidth), C.c_int(int(loadAndStoreSegments)))

@@ -10,7 +10,8 @@ from .capi import load_library
 
 
 class SfmScene:
-    """cameras: list of dicts {name, focal, dist (2,), R (3,3), t (3,), worldpoints (uint32 array)}."""
+    """cameras: list of dicts {name, focal, dist (2,), cv_dist (2,), R (3,3), t (3,), worldpoints (uint32 array)}.  dist: the file's own numbers;
+    cv_dist: (k1, k2) in OpenCV's convention, as the drivers use them (l3d_sfm_camera_cv_distortion) -- what add_image_pixels(dist=...) takes."""
 
     def __init__(self, cameras, n_points):
         self.cameras = cameras
@@ -37,10 +38,12 @@ def _read(path: str, fn_name: str) -> SfmScene:
             t = (C.c_double * 3)()
             nw = C.c_int(0)
             lib.l3d_sfm_camera(h, C.c_int(i), C.byref(focal), dist, R, t, C.byref(nw))
+            cv = (C.c_double * 2)()
+            lib.l3d_sfm_camera_cv_distortion(h, C.c_int(i), cv)
             w = np.zeros(nw.value, dtype=np.uint32)
             if nw.value:
                 lib.l3d_sfm_camera_worldpoints(h, C.c_int(i), w.ctypes.data_as(C.c_void_p))
-            cams.append(dict(name=lib.l3d_sfm_camera_name(h, C.c_int(i)).decode(), focal=focal.value, dist=np.array(list(dist)),
+            cams.append(dict(name=lib.l3d_sfm_camera_name(h, C.c_int(i)).decode(), focal=focal.value, dist=np.array(list(dist)), cv_dist=np.array(list(cv)),
                              R=np.array(list(R)).reshape(3, 3), t=np.array(list(t)), worldpoints=w))
         return SfmScene(cams, lib.l3d_sfm_num_points(h))
     finally:
@@ -86,7 +89,8 @@ def reconstruct(scene: SfmScene, segments, image_sizes, out_dir=None, neighbors=
     l3d = Line3D("", matchingNeighbors=neighbors, device=device, **line3d_kwargs)
     for i, cam in enumerate(scene.cameras):
         if np.any(np.abs(cam["dist"]) > 1e-12):
-            raise RuntimeError("camera %d has lens distortion: undistort the image before detecting segments (out of scope here)" % i)
+            raise RuntimeError("camera %d has lens distortion: segments of the undistorted image cannot be made from it here -- "
+                               "reconstruct_from_images undistorts and detects from the pixels" % i)
         w, h = image_sizes[i]
         if isinstance(segments, (str, os.PathLike)):
             path = os.fspath(segments) + segment_cache_filename(i, w, h, line3d_kwargs.get("useCollinearity", True))
@@ -99,6 +103,31 @@ def reconstruct(scene: SfmScene, segments, image_sizes, out_dir=None, neighbors=
     if out_dir is not None:
         os.makedirs(out_dir, exist_ok=True)
         base = os.path.join(out_dir, result_basename(neighbors=neighbors, diffusion=diffusion))
+        l3d.save3DLinesAsSTL(base + ".stl")
+        l3d.save3DLinesAsTXT(base + ".txt")
+    return l3d
+
+
+def reconstruct_from_images(scene: SfmScene, load_image, data_directory, out_dir=None, neighbors=10, diffusion=False, max_width=1920,
+                            load_and_store_segments=True, device=0, **line3d_kwargs):
+    """The drivers' flow (main_vsfm.cpp:226-325) from pixels: per camera the image load_image(i, name) returns (uint8, H x W or H x W x 3;
+    decoding stays with the caller), K from the focal length and the image size, the image undistorted with the camera's coefficients and its
+    segments detected on the device (Line3D.add_image_pixels(..., dist=cam["cv_dist"])), compute3Dmodel, optional STL + TXT output under the
+    drivers' file name.  data_directory: the drivers' "<image folder>/L3D_data/" -- with load_and_store_segments (the drivers' default) the segment
+    caches are written there, and a cache of an earlier run stands in for the image (line3D.cc:143-168)."""
+    import os
+    from .pipeline import Line3D
+    l3d = Line3D(data_directory, matchingNeighbors=neighbors, device=device, **line3d_kwargs)
+    for i, cam in enumerate(scene.cameras):
+        img = np.asarray(load_image(i, cam["name"]))
+        h, w = img.shape[:2]
+        if not l3d.add_image_pixels(i, img, intrinsics(cam["focal"], w, h), cam["R"], cam["t"], cam["worldpoints"], maxImgWidth=max_width,
+                                    loadAndStoreSegments=load_and_store_segments, dist=cam["cv_dist"]):
+            raise RuntimeError("camera %d: %s" % (i, l3d.lib.l3d_line3d_last_error(l3d.h).decode()))
+    l3d.compute3Dmodel(diffusion)
+    if out_dir is not None:
+        os.makedirs(out_dir, exist_ok=True)
+        base = os.path.join(out_dir, result_basename(max_width=max_width, neighbors=neighbors, diffusion=diffusion))
         l3d.save3DLinesAsSTL(base + ".stl")
         l3d.save3DLinesAsTXT(base + ".txt")
     return l3d
