@@ -27,8 +27,8 @@
 #include "l3d_kept.hpp"
 #include "l3d_products.hpp"
 #include "l3d_chain_common.hpp"
+#include "l3d_chain_partition.hpp"
 #include "l3d_runtable.hpp"
-#include "l3d_turns.hpp"
 
 #ifndef L3D_AHEAD
 #define L3D_AHEAD 4
@@ -244,8 +244,6 @@ namespace {
 
 typedef l3d::ChainViewDev ViewDev;
 
-size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
-
 }  // namespace
 
 // cb: per-view delivery of the kept lists to the host (l3d_match_chain); map: products built on the device at the end of the chain
@@ -256,18 +254,9 @@ size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 // the per-view result records (c->ch_pin_res).
 // pre: the views [pre->k0, pre->k1 = k_begin) taken over from another rank (their kept lists, best depth pairs and positions): they are put at
 // the head of the arena with their result records, so the range's views find their TRUE sources -- a block of views re-run warm after its
-// cold-started speculation failed.
-namespace {
-struct ChainPreload {
-    int k0 = 0, k1 = 0;
-    const Match* records = nullptr;        // device: the views' kept lists, back to back
-    const float2* best = nullptr;          // device: best depth pairs of the verified views among them, back to back (S_src each)
-    const int* bestpos = nullptr;          // device: ... and the positions of the best kept matches
-    std::vector<int> n_kept, R;            // per view
-};
-}
-static int run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_chain_callback cb, void* user, const l3d_dense_map* map,
-                     l3d_chain_summary* summary, int64_t* n_pot, int k_begin = 0, int k_end = -1, const ChainPreload* pre = nullptr)
+// cold-started speculation failed, or a turn that its predecessor handed the chain over to (l3d_chain_partition.hip).
+int l3d::run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_chain_callback cb, void* user, const l3d_dense_map* map,
+                   l3d_chain_summary* summary, int64_t* n_pot, int k_begin, int k_end, const ChainPreload* pre)
 {
     if (!c) return L3D_ERR_INVALID;
     const bool ranged = k_end >= 0;
@@ -900,1180 +889,6 @@ extern "C" int l3d_match_chain_resident(l3d_ctx* c, const l3d_chain_view* views,
     if (!map || !map->view_ids || !map->seg_base || map->n_views < 0 || (n_views > 0 && !summary)) return fail(c, L3D_ERR_INVALID, "l3d_match_chain_resident: bad argument");
     if (n_pot) *n_pot = 0;
     return run_chain(c, views, n_views, nullptr, nullptr, map, summary, n_pot);
-}
-
-// =================================================================================================================================
-// matchViews sharded by BLOCKS OF VIEWS, speculatively, with exact verification (round 4).
-//
-// The chain over views has a short memory: started cold at view B - L (nothing known about earlier views), its kept lists become
-// bit-identical to the true chain's after about three neighbour windows (measured: scripts/speculate_blocks.py).  So rank r of `world`
-// runs the ordinary single-GPU chain -- full-width kernels, no per-view collective -- on views [B_r - warmup, B_{r+1}) only, and the ranks
-// then CHECK the speculation: every rank publishes a 64-bit digest of every kept list it computed; rank r's block is exact if rank r-1's is
-// and the `window` views in front of B_r came out of rank r's warm-up exactly as rank r-1 (whose block they belong to) computed them --
-// from B_r on every view then has the same inputs as in the one chain, and the same arithmetic.  All ranks read the same gathered table,
-// so all reach the same verdict without another collective.  When it holds, the ranks all-gather their blocks' kept records (+ best depth
-// pairs / positions), lay them out as the one chain's arena and build matchViews' products from it (l3d_products.hip, unchanged).  When it
-// does not, nothing is committed and the caller takes the segment-sharded run (l3d_shard_chain_run), whose result needs no speculation.
-namespace l3d {
-
-struct BlockDigest { unsigned long long hash; int n_kept, R; };      // per view of the chain; zero = not computed by this rank
-static_assert(sizeof(BlockDigest) == 16, "digest entry");
-
-// order-sensitive 64-bit digest of a view's kept records: sum over records of a mix of (index, the record's eight words)
-__global__ __launch_bounds__(256) void k_block_digest(const Match* __restrict__ arena, const ChainResult* __restrict__ res, int k_begin, BlockDigest* __restrict__ out)
-{
-    const int k = k_begin + blockIdx.y;
-    const ChainResult r = res[k];
-    unsigned long long h = 0;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < r.n_kept; i += gridDim.x * 256) {
-        const uint4* w = reinterpret_cast<const uint4*>(arena + r.kept_base + i);
-        const uint4 a = w[0], b = w[1];
-        unsigned long long x = 0x9E3779B97F4A7C15ull * (unsigned long long)(i + 1);
-        const unsigned v[8] = { a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w };
-#pragma unroll
-        for (int q = 0; q < 8; ++q) { x ^= v[q]; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 29; }
-        h += x;
-    }
-    for (int o = 32; o > 0; o >>= 1) h += __shfl_down(h, o);
-    if ((threadIdx.x & 63) == 0 && h) atomicAdd(&out[k].hash, h);
-    if (blockIdx.x == 0 && threadIdx.x == 0) { out[k].n_kept = r.n_kept; out[k].R = r.R; }
-}
-
-}  // namespace l3d
-
-// k_block_digest over the kept lists of the resident products, whoever built them: hash[k] / n_kept[k] of every chain view (0 / 0: nothing of
-// the view is held here).  What two ranks that took turns on one device compare of the views both held, before the records are released.
-extern "C" int l3d_chain_records_digest(l3d_ctx* c, uint64_t* hash, int32_t* n_kept, int n)
-{
-    if (!c) return L3D_ERR_INVALID;
-    Products& P = c->products;
-    if (!hash || !n_kept || n < 0) return fail(c, L3D_ERR_INVALID, "l3d_chain_records_digest: bad argument");
-    if (!P.valid || n != P.n_chain || (int)P.res.size() != n) return fail(c, L3D_ERR_INVALID, "l3d_chain_records_digest: no resident products of that many chain views");
-    if (c->records_released) return fail(c, L3D_ERR_INVALID, "l3d_chain_records_digest: the kept records of this chain were released (l3d_chain_release_records)");
-    if (n == 0) return L3D_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    // every list must lie inside the arena: the kernel trusts the records' table
-    for (int k = 0; k < n; ++k) {
-        const ChainResult& r = P.res[(size_t)k];
-        if (r.n_kept < 0 || (r.n_kept > 0 && ((size_t)r.kept_base + (size_t)r.n_kept) * sizeof(Match) > c->ch_kept.cap))
-            return fail(c, L3D_ERR_INVALID, "l3d_chain_records_digest: a kept list lies outside the arena");
-    }
-    const size_t o_dig = ((size_t)n * sizeof(ChainResult) + 255) & ~(size_t)255;
-    HIPCHK(c, c->g7.reserve(o_dig + (size_t)n * sizeof(BlockDigest) + 64));
-    ChainResult* dres = c->g7.as<ChainResult>();
-    BlockDigest* dd = reinterpret_cast<BlockDigest*>(c->g7.as<unsigned char>() + o_dig);
-    HIPCHK(c, hipMemcpyAsync(dres, P.res.data(), (size_t)n * sizeof(ChainResult), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemsetAsync(dd, 0, (size_t)n * sizeof(BlockDigest), st));
-    for (int k0 = 0; k0 < n; k0 += 32768)        // (a launch's second grid dimension holds 65 535 blocks)
-        hipLaunchKernelGGL(k_block_digest, dim3(16, (unsigned)std::min(32768, n - k0)), dim3(256), 0, st, c->ch_kept.as<Match>(), dres, k0, dd);
-    std::vector<BlockDigest> hd((size_t)n);
-    HIPCHK(c, hipMemcpyAsync(hd.data(), dd, (size_t)n * sizeof(BlockDigest), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    HIPCHK(c, hipGetLastError());
-    for (int k = 0; k < n; ++k) { hash[k] = hd[(size_t)k].hash; n_kept[k] = hd[(size_t)k].n_kept; }
-    return L3D_OK;
-}
-
-namespace l3d {
-
-// one source's records that point at an early-return view, in list order (stable): out == nullptr counts only
-__global__ __launch_bounds__(256) void k_early_pack(const Match* __restrict__ arena, const ChainResult* __restrict__ res, const int* __restrict__ group_src,
-                                                    const unsigned* __restrict__ early_ids, int n_early, const long long* __restrict__ out_off, Match* __restrict__ out, int* __restrict__ counts)
-{
-    __shared__ int s_w[4];
-    const ChainResult r = res[group_src[blockIdx.x]];
-    const Match* kept = arena + r.kept_base;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    long long off = out ? out_off[blockIdx.x] : 0;
-    int total = 0;
-    for (int b = 0; b < r.n_kept; b += 256) {
-        const int i = b + tid;
-        Match m;
-        bool on = false;
-        if (i < r.n_kept) { m = kept[i]; for (int e = 0; e < n_early; ++e) on = on || m.camID2 == early_ids[e]; }
-        const unsigned long long bal = __ballot(on);
-        if (lane == 0) s_w[wave] = __popcll(bal);
-        __syncthreads();
-        int before = 0, all = 0;
-        for (int w = 0; w < 4; ++w) { if (w < wave) before += s_w[w]; all += s_w[w]; }
-        if (on && out) out[off + before + __popcll(bal & ((1ull << lane) - 1ull))] = m;
-        off += all; total += all;
-        __syncthreads();
-    }
-    if (tid == 0 && !out) counts[blockIdx.x] = total;
-}
-
-// one view's best matches as a package other ranks can build its hypotheses from: [view, R, n, S | position of every segment's best match in the
-// compact list or -1 | best depth pairs | the best records, compact, in segment order (room for S)]
-__global__ __launch_bounds__(256) void k_alias_pack(const Match* __restrict__ arena, const ChainResult* __restrict__ res, const int* __restrict__ pk_view, const int* __restrict__ pk_S,
-                                                    const long long* __restrict__ pk_best_off, const long long* __restrict__ pk_out_off, const float2* __restrict__ best_all,
-                                                    const int* __restrict__ bestpos_all, unsigned char* __restrict__ out)
-{
-    __shared__ int s_w[4];
-    const int k = pk_view[blockIdx.x], S = pk_S[blockIdx.x];
-    const ChainResult r = res[k];
-    const float2* best = best_all + pk_best_off[blockIdx.x];
-    const int* bestpos = bestpos_all + pk_best_off[blockIdx.x];
-    unsigned char* o = out + pk_out_off[blockIdx.x];
-    int* o_pos = reinterpret_cast<int*>(o + 16);
-    float2* o_best = reinterpret_cast<float2*>(o + 16 + (size_t)S * 4);
-    Match* o_rec = reinterpret_cast<Match*>(o + 16 + (size_t)S * 12);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int off = 0;
-    for (int b = 0; b < S; b += 256) {
-        const int s = b + tid;
-        const int p = s < S ? bestpos[s] : -1;
-        const bool on = p >= 0 && r.n_kept > 0;
-        const unsigned long long bal = __ballot(on);
-        if (lane == 0) s_w[wave] = __popcll(bal);
-        __syncthreads();
-        int before = 0, all = 0;
-        for (int w = 0; w < 4; ++w) { if (w < wave) before += s_w[w]; all += s_w[w]; }
-        if (s < S) {
-            const int q = on ? off + before + __popcll(bal & ((1ull << lane) - 1ull)) : -1;
-            o_pos[s] = q; o_best[s] = best[s];
-            if (on) o_rec[q] = arena[r.kept_base + p];
-        }
-        off += all;
-        __syncthreads();
-    }
-    if (tid == 0) { int* h = reinterpret_cast<int*>(o); h[0] = k; h[1] = r.R; h[2] = off; h[3] = S; }
-}
-
-}  // namespace l3d
-
-namespace {
-
-// `used` bytes of the kept arena kept across a growth (DevBuf::reserve drops the content)
-int arena_grow_keep(l3d_ctx* c, size_t records, size_t used_records)
-{
-    if (records * sizeof(Match) <= c->ch_kept.cap) return L3D_OK;
-    const size_t want = records * sizeof(Match) + records * sizeof(Match) / 8 + 4096;
-    void* np = nullptr;
-    if (hipMalloc(&np, want) != hipSuccess) { (void)hipGetLastError(); return fail(c, L3D_ERR_NOMEM, "growing the kept arena to " + std::to_string(want >> 20) + " MB"); }
-    if (used_records && c->ch_kept.p) HIPCHK(c, hipMemcpy(np, c->ch_kept.p, used_records * sizeof(Match), hipMemcpyDeviceToDevice));
-    if (c->ch_kept.p) (void)hipFree(c->ch_kept.p);
-    c->ch_kept.p = np; c->ch_kept.cap = want;
-    return L3D_OK;
-}
-
-}  // namespace
-
-// partition = 0: every rank ends up with the whole arena and the whole table (replicas for the finishing stages: l3d_match_chain_blocks).
-// partition = 1: nothing is replicated (l3d_match_chain_partition, include/line3d_amd.h).
-static int chain_blocks_impl(l3d_ctx* c, const l3d_chain_view* views, int n_views, const l3d_dense_map* map, l3d_chain_summary* summary, int64_t* n_pot,
-                             int rank, int world, int warmup_views, int window, l3d_exchange_fn exchange, void* exchange_user, int* verdict, int partition)
-{
-    if (!c) return L3D_ERR_INVALID;
-    if (!views || n_views <= 0 || !map || !summary || !exchange || !verdict || world < 1 || rank < 0 || rank >= world || warmup_views < 0 || window < 0)
-        return fail(c, L3D_ERR_INVALID, "l3d_match_chain_blocks: bad argument");
-    *verdict = 1;
-    if (n_pot) *n_pot = 0;
-    c->products.valid = false;
-    c->products.part = ProductsPart();
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    auto block_begin = [&](int r) { return (int)(((long long)n_views * r) / world); };
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    // reach: the largest distance, in chain positions, between a view and one of its neighbours (every rank computes the same number)
-    int reach = window;
-    {
-        std::vector<std::pair<unsigned, int>> idx((size_t)n_views);
-        for (int k = 0; k < n_views; ++k) idx[(size_t)k] = { views[k].view_id, k };
-        std::sort(idx.begin(), idx.end());
-        for (int k = 0; k < n_views; ++k)
-            for (int q = 0; q < views[k].N; ++q) {
-                if (!views[k].local2global) continue;
-                auto it = std::lower_bound(idx.begin(), idx.end(), std::make_pair(views[k].local2global[q], -1));
-                if (it != idx.end() && it->first == views[k].local2global[q]) reach = std::max(reach, std::abs(it->second - k));
-            }
-    }
-    // partitioned: a rank runs its chain 2 x reach views PAST its block and must be exact 2 x reach views in front of it -- everything the rows of
-    // its block, their flags and the hypotheses they name can depend on is then computed locally (DESIGN.md section 6 iv)
-    const int tail = partition ? 2 * reach : 0;
-    const int check = partition ? std::max(window, 2 * reach) : window;
-    const int own0 = block_begin(rank), own1 = block_begin(rank + 1);
-    int first = rank == 0 ? 0 : std::max(0, own0 - warmup_views);
-    const int last = std::min(n_views, own1 + tail);
-    const double t0 = now_s();
-    // ---- this rank's chain: its block and the warm-up views in front of it, started cold
-    // (a rank whose chain fails must not leave the others waiting in the first collective: it still publishes its table, with a mark that
-    // every rank reads -- they all return an error then, without entering another collective)
-    int chain_rc = run_chain(c, views, n_views, nullptr, nullptr, nullptr, nullptr, nullptr, first, last);
-    std::string chain_err;
-    if (chain_rc) { std::lock_guard<std::mutex> lk(c->err_mu); chain_err = c->err; }
-    // partitioned: the job is sized by memory, not by the time of a second pass -- what only a running chain needs (candidate store and its ring,
-    // window scratch, bit rows, viewing rays, row counters: 10-15 GB at 4000 segments x 24 neighbours) is given back before the products are built
-    auto release_chain_scratch = [&]() {
-        if (!partition || c->opt.part_release == 0) return;
-        (void)hipStreamSynchronize(st); (void)hipStreamSynchronize(c->stage1_stream);
-        DevBuf* b[] = { &c->ch_ringA_meta, &c->ch_ringA_depths, &c->cand_meta, &c->cand_depths, &c->cand_conf, &c->vw_scratch, &c->ch_mask, &c->ch_rays, &c->ch_rowcnt, &c->ch_rowA };
-        for (DevBuf* x : b) x->release();
-    };
-    release_chain_scratch();
-    const ChainResult* hres = c->ch_pin_res.as<ChainResult>();
-    double t1 = now_s();
-    // useful work of this rank = its own block (the warm-up is the price of the speculation)
-    {
-        double p = 0;
-        for (int k = own0; k < own1; ++k)
-            for (int j = 0; j < views[k].n_tbm; ++j) p += (double)views[k].S_src * views[k].offsets[2 * views[k].to_be_matched[j] + 1];
-        c->stats[0] = p;
-    }
-    // Everything a rank can fail in ON ITS OWN between two collectives (an allocation, a copy, a launch) is collected in local_rc and travels
-    // with the next exchange: a failed rank still enters it, with a mark every rank reads, and then all of them return -- nobody is left waiting.
-    const size_t tab_bytes = al((size_t)n_views * sizeof(BlockDigest));
-    int local_rc = chain_rc;
-    std::string local_err = chain_err;
-    auto note = [&](int rc) { if (rc && !local_rc) { local_rc = rc; std::lock_guard<std::mutex> lk(c->err_mu); local_err = c->err; } };
-#define L3D_SOFT(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) note(fail(c, L3D_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_))); } while (0)
-    {   // (sized once for the digest tables AND the status words: no reallocation between collectives)
-        hipError_t e = c->ch_hdr.reserve(tab_bytes * (size_t)(world + 1) + 512 * (size_t)(world + 2) + 256);
-        if (e != hipSuccess) return fail(c, L3D_ERR_NOMEM, "l3d_match_chain_blocks: digest tables");     // (before the first collective of this call: every rank of the job is configured alike)
-    }
-    BlockDigest* dtab_own = c->ch_hdr.as<BlockDigest>();
-    BlockDigest* dtab_all = reinterpret_cast<BlockDigest*>(c->ch_hdr.as<unsigned char>() + tab_bytes);
-    long long* st_own = reinterpret_cast<long long*>(c->ch_hdr.as<unsigned char>() + tab_bytes * (size_t)(world + 1));
-    long long* st_all = reinterpret_cast<long long*>(c->ch_hdr.as<unsigned char>() + tab_bytes * (size_t)(world + 1) + 256);
-    std::vector<BlockDigest> tab((size_t)world * (size_t)n_views);
-    std::vector<long long> words((size_t)world, 0);
-    // publishes `mine` (negative = this rank failed with code -mine), reads everybody's; non-zero return: somebody failed (this rank's own message is kept)
-    auto all_gather_word = [&](long long mine, const char* what) -> int {
-        if (local_rc && mine >= 0) mine = -(long long)local_rc;
-        hipError_t e = hipMemcpyAsync(st_own, &mine, 8, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);                   // (`mine` is a stack word)
-        if (e != hipSuccess) { note(fail(c, L3D_ERR_HIP, std::string("l3d_match_chain_blocks: status word: ") + hipGetErrorString(e))); (void)hipMemsetAsync(st_own, 0xff, 8, st); }   // (all ones = -1: failed)
-        if (exchange(exchange_user, -3, st_own, st_all, 256, world, (void*)st)) return fail(c, L3D_ERR_HIP, std::string("l3d_match_chain_blocks: the exchange of the status words failed (") + what + ")");
-        e = hipSuccess;
-        for (int r = 0; r < world && e == hipSuccess; ++r) e = hipMemcpyAsync(&words[(size_t)r], reinterpret_cast<const unsigned char*>(st_all) + (size_t)r * 256, 8, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return fail(c, L3D_ERR_HIP, std::string("l3d_match_chain_blocks: status word: ") + hipGetErrorString(e));     // (after the collective: nobody waits for this rank any more)
-        if (local_rc) return fail(c, local_rc, local_err);
-        for (int r = 0; r < world; ++r)
-            if (words[(size_t)r] < 0) return fail(c, L3D_ERR_HIP, "l3d_match_chain_blocks: rank " + std::to_string(r) + " failed (code " + std::to_string(-words[(size_t)r]) + ") while " + what);
-        return L3D_OK;
-    };
-    auto owner = [&](int k) { int r = (int)(((long long)k * world) / n_views); while (r + 1 < world && block_begin(r + 1) <= k) ++r; while (r > 0 && block_begin(r) > k) --r; return r; };
-    // offsets of the views' slices in the whole-run arrays of best pairs / positions (chain_assign_arenas: verified views back to back)
-    std::vector<long long> best_off((size_t)n_views + 1, 0);
-    for (int k = 0; k < n_views; ++k) best_off[(size_t)k + 1] = best_off[(size_t)k] + (views[k].n_tbm > 0 ? views[k].S_src : 0);
-
-    // ---- digests of every list this rank computed, all-gathered; the verdict; a block whose speculation failed is re-run WARM from its
-    // predecessor's true lists (the first one that failed: everything in front of it is exact), then the digests are exchanged again -- a miss
-    // costs one block, not the pass
-    int arena_first = first;                // first view whose records sit in this rank's arena
-    std::vector<int> comp_from((size_t)world, 0);       // per rank: the first view it computed (or took over); every rank keeps the same table
-    for (int r = 1; r < world; ++r) comp_from[(size_t)r] = std::max(0, block_begin(r) - warmup_views);
-    double t2 = t1;
-    int rounds = 0, blocks_rerun = 0;
-    for (;; ++rounds) {
-        L3D_SOFT(hipMemsetAsync(dtab_own, 0, tab_bytes, st));
-        if (local_rc) {
-            BlockDigest mark; mark.hash = ~0ull; mark.n_kept = -1; mark.R = local_rc;
-            (void)hipMemcpyAsync(dtab_own, &mark, sizeof(mark), hipMemcpyHostToDevice, st);
-            (void)hipStreamSynchronize(st);
-        } else if (last > arena_first) {
-            L3D_SOFT(hipMemcpyAsync(c->ch_res.p, hres, (size_t)n_views * sizeof(ChainResult), hipMemcpyHostToDevice, st));     // (the final records: a restart rewrites them)
-            hipLaunchKernelGGL(k_block_digest, dim3(16, last - arena_first), dim3(256), 0, st, c->ch_kept.as<Match>(), c->ch_res.as<ChainResult>(), arena_first, dtab_own);
-        }
-        if (exchange(exchange_user, -1, dtab_own, dtab_all, tab_bytes, world, (void*)st)) return fail(c, L3D_ERR_HIP, "l3d_match_chain_blocks: the exchange of the digests failed");
-        {
-            hipError_t e = hipSuccess;
-            for (int r = 0; r < world && e == hipSuccess; ++r)
-                e = hipMemcpyAsync(tab.data() + (size_t)r * n_views, reinterpret_cast<const unsigned char*>(dtab_all) + (size_t)r * tab_bytes, (size_t)n_views * sizeof(BlockDigest), hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) {
-                // this rank cannot read the table: it cannot know the verdict the others reach.  The status-word exchange below (entered by every
-                // rank after every digest exchange) carries the failure to them.
-                note(fail(c, L3D_ERR_HIP, std::string("l3d_match_chain_blocks: reading the digest tables: ") + hipGetErrorString(e)));
-            }
-        }
-        t2 = now_s();
-        if (local_rc == L3D_OK)
-            for (int r = 0; r < world; ++r)
-                if (tab[(size_t)r * n_views].n_kept == -1 && tab[(size_t)r * n_views].hash == ~0ull) { note(fail(c, L3D_ERR_HIP, "l3d_match_chain_blocks: the chain of rank " + std::to_string(r) + " failed (code " + std::to_string(tab[(size_t)r * n_views].R) + ")")); break; }
-        if (int a_rc = all_gather_word(0, "computing its block")) return a_rc;
-        // ---- the verdict (the same on every rank: same table).  miss[r]: the `check` views in front of rank r's block did not come out of its warm-up as
-        // its predecessor computed them.  No miss anywhere = every rank exact (rank 0 is; rank r's check views equal rank r-1's, which are then the
-        // one chain's, and from them on rank r's chain had the one chain's inputs).
-        bool hopeless = false;
-        int n_miss = 0;
-        std::vector<char> miss((size_t)world, 0);
-        for (int r = 1; r < world; ++r) {
-            const int b = block_begin(r), lo = std::max(0, b - check);
-            // a warm-up shorter than the check leaves views the rank never computed: a miss (the warm re-run below takes them over)
-            bool ok = lo >= comp_from[(size_t)r];
-            // (replicas: a block shorter than the window cannot vouch for its successor's sources -- the blocks are what gets gathered; partitioned: the
-            // predecessor's exact range reaches back as far as this rank's check)
-            if (!partition && b - check < block_begin(r - 1)) { ok = false; hopeless = true; }
-            for (int k = lo; k < b && ok; ++k) {
-                const BlockDigest &x = tab[(size_t)r * n_views + k], &y = tab[(size_t)(r - 1) * n_views + k];
-                // (the kept LIST must be the same; the number of candidates it was chosen from may differ while the warm-up converges)
-                if (x.hash != y.hash || x.n_kept != y.n_kept) {
-                    ok = false;
-                    if (c->opt.timing) fprintf(stderr, "[l3d chain_blocks] rank %d's warm-up view %d differs from rank %d's (%d vs %d kept)\n", r, k, r - 1, x.n_kept, y.n_kept);
-                }
-            }
-            if (ok && partition) {          // the predecessor's tail against this rank's block: both are the one chain's, or something is wrong
-                const int e = std::min(std::min(n_views, b + tail), block_begin(r + 1));
-                for (int k = b; k < e && ok; ++k) {
-                    const BlockDigest &x = tab[(size_t)r * n_views + k], &y = tab[(size_t)(r - 1) * n_views + k];
-                    if (x.hash != y.hash || x.n_kept != y.n_kept) ok = false;
-                }
-            }
-            miss[(size_t)r] = ok ? 0 : 1;
-            n_miss += ok ? 0 : 1;
-        }
-        if (c->opt.timing) fprintf(stderr, "[l3d chain_blocks rank %d/%d] round %d: views %d..%d (block from %d): chain %.2f ms, digests + exchange %.2f ms, %d rank(s) missed\n",
-                                   rank, world, rounds, arena_first, last - 1, own0, (t1 - t0) * 1e3, (t2 - t1) * 1e3, n_miss);
-        if (n_miss == 0) break;
-        // option block_recover = 0 (A/B, tests of the fall-through): the round-4 behaviour -- any miss sends the pass to the caller's other mode
-        if (hopeless || c->opt.block_recover == 0 || rounds >= world) return L3D_OK;                  // *verdict = 1: nothing committed
-        // ---- recovery, all missed blocks at once: every rank that missed takes over its predecessor's last `check` views (records, best depth
-        // pairs, best positions: one all-gather, the one primitive of the protocol) and re-runs its block WARM from them.  A predecessor that missed
-        // too hands over what its cold start produced -- usually already the one chain's by the end of a block; if not, the next round's digests
-        // show it and that rank runs again.  After round j rank j is exact whatever happened (it took over from rank j-1, exact since round j-1).
-        blocks_rerun += n_miss;
-        long long max_rec = 0, max_seg = 0;
-        std::vector<long long> t_rec((size_t)world, 0), t_seg((size_t)world, 0);
-        std::vector<int> t_first((size_t)world, -1);               // (a tail's records are contiguous in the sender's arena from its first verified view on)
-        for (int r = 1; r < world; ++r) {
-            if (!miss[(size_t)r]) continue;
-            const int s_ = r - 1, fb = block_begin(r), k0 = std::max(0, fb - check);
-            for (int k = k0; k < fb; ++k) { t_rec[(size_t)s_] += tab[(size_t)s_ * n_views + k].n_kept; if (views[k].n_tbm > 0) { t_seg[(size_t)s_] += views[k].S_src; if (t_first[(size_t)s_] < 0) t_first[(size_t)s_] = k; } }
-            max_rec = std::max(max_rec, t_rec[(size_t)s_]); max_seg = std::max(max_seg, t_seg[(size_t)s_]);
-        }
-        // a tail as one byte stream [records | best depth pairs | best positions], the same offsets on every rank; it travels in CHUNKS (option
-        // handover_chunk_kb, 256 MB): an all-gather hands every rank every slot, and a whole tail per slot would cost world x tail bytes on every
-        // rank (52 GB at 4000 x 24 x 8 ranks) for the one slot a rank reads -- a chunk per slot costs world x 256 MB
-        const size_t o_best = al((size_t)max_rec * sizeof(Match)), o_bpos = o_best + al((size_t)max_seg * 8), slot = o_bpos + al((size_t)max_seg * 4) + 256;
-        const size_t chunk = std::min(slot, al((size_t)std::max(1, c->opt.handover_chunk_kb) << 10));
-        const bool sends = rank + 1 < world && miss[(size_t)rank + 1], takes = miss[(size_t)rank] != 0;
-        {
-            hipError_t e = c->ch_send.reserve(chunk + 256);
-            if (e == hipSuccess) e = c->ch_gathered.reserve(chunk * (size_t)world + 256);
-            if (e == hipSuccess && takes) e = c->ch_stage.reserve(slot + 256);
-            if (e != hipSuccess) note(fail(c, L3D_ERR_NOMEM, "l3d_match_chain_blocks: the hand-over of a block's sources"));
-        }
-        if (int a_rc = all_gather_word(0, "staging the hand-over of a block's sources")) return a_rc;
-        for (size_t off = 0; off < slot; off += chunk) {
-            const size_t n = std::min(chunk, slot - off);
-            if (sends && !local_rc) {
-                const int k0 = std::max(0, block_begin(rank + 1) - check);
-                struct Piece { size_t at, len; const unsigned char* src; } pieces[3] = {
-                    { 0, (size_t)t_rec[(size_t)rank] * sizeof(Match), t_first[(size_t)rank] >= 0 ? reinterpret_cast<const unsigned char*>(c->ch_kept.as<Match>() + hres[t_first[(size_t)rank]].kept_base) : nullptr },
-                    { o_best, (size_t)t_seg[(size_t)rank] * 8, reinterpret_cast<const unsigned char*>(c->ch_best.as<float2>() + best_off[(size_t)k0]) },
-                    { o_bpos, (size_t)t_seg[(size_t)rank] * 4, reinterpret_cast<const unsigned char*>(c->ch_bestpos.as<int>() + best_off[(size_t)k0]) } };
-                for (const Piece& q : pieces) {
-                    const size_t lo = std::max(q.at, off), hi = std::min(q.at + q.len, off + n);
-                    if (q.src && hi > lo) L3D_SOFT(hipMemcpyAsync(c->ch_send.as<unsigned char>() + (lo - off), q.src + (lo - q.at), hi - lo, hipMemcpyDeviceToDevice, st));
-                }
-            }
-            if (exchange(exchange_user, -5, c->ch_send.p, c->ch_gathered.p, n, world, (void*)st)) return fail(c, L3D_ERR_HIP, "l3d_match_chain_blocks: the hand-over exchange failed");
-            if (takes && !local_rc) L3D_SOFT(hipMemcpyAsync(c->ch_stage.as<unsigned char>() + off, c->ch_gathered.as<unsigned char>() + (size_t)(rank - 1) * n, n, hipMemcpyDeviceToDevice, st));
-            if (off + chunk < slot) L3D_SOFT(hipStreamSynchronize(st));       // (the next chunk reuses the send and gathered buffers)
-        }
-        for (int r = 1; r < world; ++r) if (miss[(size_t)r]) comp_from[(size_t)r] = std::max(0, block_begin(r) - check);
-        if (miss[(size_t)rank]) {
-            const int src_rank = rank - 1, fb = own0, k0 = std::max(0, fb - check);
-            ChainPreload pre;
-            pre.k0 = k0; pre.k1 = fb;
-            const unsigned char* G = c->ch_stage.as<unsigned char>();
-            pre.records = reinterpret_cast<const Match*>(G);
-            pre.best = reinterpret_cast<const float2*>(G + o_best);
-            pre.bestpos = reinterpret_cast<const int*>(G + o_bpos);
-            for (int k = k0; k < fb; ++k) { pre.n_kept.push_back(tab[(size_t)src_rank * n_views + k].n_kept); pre.R.push_back(tab[(size_t)src_rank * n_views + k].R); }
-            const double tr0 = now_s();
-            const int rc = run_chain(c, views, n_views, nullptr, nullptr, nullptr, nullptr, nullptr, fb, last, &pre);
-            if (rc) note(rc);
-            release_chain_scratch();
-            hres = c->ch_pin_res.as<ChainResult>();
-            arena_first = k0;
-            t1 += now_s() - tr0;
-            if (c->opt.timing) fprintf(stderr, "[l3d chain_blocks rank %d/%d] block re-run warm from rank %d's last %d views: %.2f ms\n", rank, world, src_rank, fb - k0, (now_s() - tr0) * 1e3);
-        }
-    }
-    c->products.part.recovery_rounds = rounds; c->products.part.blocks_rerun = blocks_rerun;
-    // first view from which this rank's lists are the one chain's
-    const int exact_from = rank == 0 ? 0 : std::max(arena_first, own0 - check);
-    (void)comp_from;
-
-    const int nvd = map->n_views;
-    auto dense_of = [&](int k) {                                   // the dense view a chain view is (ids ascend in both)
-        if (k >= n_views) return nvd;
-        const uint32_t* it = std::lower_bound(map->view_ids, map->view_ids + nvd, views[k].view_id);
-        return (int)(it - map->view_ids);
-    };
-    Products& P = c->products;
-
-    if (partition) {
-        // =========================================================================================================================
-        // Nothing is replicated.  This rank holds the exact records of the views [exact_from, last) and builds from them, locally: the rows
-        // of the table for the views within `reach` of its block, best matches and medians for every view it holds.  What the early-return
-        // quirk (cudawrapper.cu:877-878) files under LOCAL camera numbers read as view ids can name any view of the scene: the records that
-        // point at an early-return view -- a sliver of their sources' lists -- are all-gathered, each source's by the rank that owns it.
-        std::vector<ChainResult> hloc((size_t)n_views);
-        for (int k = 0; k < n_views; ++k) { hloc[(size_t)k] = ChainResult(); if (k >= exact_from && k < last) hloc[(size_t)k] = hres[k]; }
-        long long used = 0;
-        for (int k = exact_from; k < last; ++k) used = std::max(used, (long long)hres[k].kept_base + hres[k].n_kept);
-        // ---- early-return views: groups = their sources; sender = the owner of the source
-        std::vector<unsigned> early_ids;
-        std::vector<int> groups_all;                               // every source of an early-return view, ascending, unique
-        for (int k = 0; k < n_views; ++k) {
-            if (views[k].n_tbm != 0 || views[k].n_sources == 0) continue;
-            early_ids.push_back(views[k].view_id);
-            for (int q = 0; q < views[k].n_sources; ++q) if (views[k].source_index[q] >= 0 && views[k].source_index[q] < k && views[views[k].source_index[q]].n_tbm > 0) groups_all.push_back(views[k].source_index[q]);
-        }
-        std::sort(groups_all.begin(), groups_all.end());
-        groups_all.erase(std::unique(groups_all.begin(), groups_all.end()), groups_all.end());
-        if (early_ids.size() > 64 || groups_all.size() > 480) return L3D_OK;    // (a schedule full of early returns: the replicated mode takes it; the same on every rank)
-        if (!groups_all.empty() && world > 1) {
-            std::vector<int> mine;
-            for (int si : groups_all) if (owner(si) == rank) mine.push_back(si);
-            const size_t o_ids = 0, o_grp = 256, o_off = o_grp + 2048, o_cnt = o_off + 4096, ctl = o_cnt + 2048;
-            std::vector<int> cnt(mine.size(), 0);
-            long long total = 0;
-            {
-                hipError_t e = c->ch_send.reserve(ctl + 256);
-                if (e != hipSuccess) note(fail(c, L3D_ERR_NOMEM, "l3d_match_chain_partition: early-return control block"));
-                else if (!mine.empty()) {
-                    unsigned char* S0 = c->ch_send.as<unsigned char>();
-                    L3D_SOFT(hipMemcpyAsync(S0 + o_ids, early_ids.data(), early_ids.size() * 4, hipMemcpyHostToDevice, st));
-                    L3D_SOFT(hipMemcpyAsync(S0 + o_grp, mine.data(), mine.size() * 4, hipMemcpyHostToDevice, st));
-                    hipLaunchKernelGGL(k_early_pack, dim3((unsigned)mine.size()), dim3(256), 0, st, c->ch_kept.as<Match>(), c->ch_res.as<ChainResult>(), reinterpret_cast<const int*>(S0 + o_grp),
-                                       reinterpret_cast<const unsigned*>(S0 + o_ids), (int)early_ids.size(), (const long long*)nullptr, (Match*)nullptr, reinterpret_cast<int*>(S0 + o_cnt));
-                    L3D_SOFT(hipMemcpyAsync(cnt.data(), S0 + o_cnt, mine.size() * 4, hipMemcpyDeviceToHost, st));
-                    L3D_SOFT(hipStreamSynchronize(st));
-                    for (int x : cnt) total += x;
-                }
-            }
-            if (int a_rc = all_gather_word(total, "counting the records that point at early-return views")) return a_rc;
-            long long max_total = 0;
-            for (int r = 0; r < world; ++r) max_total = std::max(max_total, words[(size_t)r]);
-            const size_t hdr = 4096, eslot = hdr + al((size_t)max_total * sizeof(Match)) + 256;
-            {
-                // slot: [int n_groups | (int source, int count) x n_groups] [records of the groups, back to back]; staged in ch_stage (ch_send holds the control block)
-                hipError_t e = c->ch_stage.reserve(eslot + 256);
-                if (e == hipSuccess) e = c->ch_gathered.reserve(eslot * (size_t)world + 256);
-                if (e != hipSuccess) note(fail(c, L3D_ERR_NOMEM, "l3d_match_chain_partition: early-return slots"));
-                else {
-                    std::vector<int> h((size_t)1 + 2 * mine.size(), 0);
-                    std::vector<long long> offs(mine.size(), 0);
-                    h[0] = (int)mine.size();
-                    long long o = 0;
-                    for (size_t g = 0; g < mine.size(); ++g) { h[1 + 2 * g] = mine[g]; h[2 + 2 * g] = cnt[g]; offs[g] = o; o += cnt[g]; }
-                    unsigned char* S0 = c->ch_send.as<unsigned char>();
-                    unsigned char* E0 = c->ch_stage.as<unsigned char>();
-                    L3D_SOFT(hipMemcpyAsync(E0, h.data(), h.size() * 4, hipMemcpyHostToDevice, st));
-                    if (total > 0) {
-                        L3D_SOFT(hipMemcpyAsync(S0 + o_off, offs.data(), offs.size() * 8, hipMemcpyHostToDevice, st));
-                        hipLaunchKernelGGL(k_early_pack, dim3((unsigned)mine.size()), dim3(256), 0, st, c->ch_kept.as<Match>(), c->ch_res.as<ChainResult>(), reinterpret_cast<const int*>(S0 + o_grp),
-                                           reinterpret_cast<const unsigned*>(S0 + o_ids), (int)early_ids.size(), reinterpret_cast<const long long*>(S0 + o_off), reinterpret_cast<Match*>(E0 + hdr), (int*)nullptr);
-                    }
-                    L3D_SOFT(hipStreamSynchronize(st));        // (h / offs are stack vectors)
-                }
-            }
-            if (int a_rc = all_gather_word(0, "staging the records that point at early-return views")) return a_rc;
-            if (exchange(exchange_user, -6, c->ch_stage.p, c->ch_gathered.p, eslot, world, (void*)st)) return fail(c, L3D_ERR_HIP, "l3d_match_chain_partition: the exchange of the early-return records failed");
-            // a source this rank does not hold gets a list of its own: just those records, in list order
-            const unsigned char* G = c->ch_gathered.as<unsigned char>();
-            std::vector<int> hh(1024);
-            for (int r = 0; r < world && !local_rc; ++r) {
-                if (r == rank) continue;
-                L3D_SOFT(hipMemcpyAsync(hh.data(), G + (size_t)r * eslot, hdr, hipMemcpyDeviceToHost, st));
-                L3D_SOFT(hipStreamSynchronize(st));
-                if (local_rc) break;
-                long long o = 0;
-                for (int g = 0; g < hh[0] && g < 480; ++g) {
-                    const int si = hh[1 + 2 * g], n = hh[2 + 2 * g];
-                    if (si >= 0 && si < n_views && n > 0 && !(si >= exact_from && si < last)) {
-                        if (int rc = arena_grow_keep(c, (size_t)(used + n) + 64, (size_t)used)) { note(rc); break; }
-                        L3D_SOFT(hipMemcpyAsync(c->ch_kept.as<Match>() + used, G + (size_t)r * eslot + hdr + (size_t)o * sizeof(Match), (size_t)n * sizeof(Match), hipMemcpyDeviceToDevice, st));
-                        ChainResult& x = hloc[(size_t)si];
-                        x.kept_base = (uint64_t)used; x.n_kept = n; x.R = n; x.overflow = 0;
-                        used += n;
-                    }
-                    o += n;
-                }
-            }
-        }
-        // ---- the views an early return's LOCAL camera numbers name (cudawrapper.cu:877-878 hands the list back with local numbers, line3D.cc:861-865
-        // files the entries under them read as view ids): rows of an early-return view point at their segments, whoever holds them.  The affinity fill
-        // only asks whether such a segment has a hypothesis and where it stands in the order -- the views' best matches (one record per segment:
-        // a few hundred KB per view) are all-gathered, each view's by the rank that owns it
-        std::vector<char> alias_known((size_t)n_views, 0);
-        if (!early_ids.empty() && world > 1) {
-            std::vector<std::pair<unsigned, int>> idx((size_t)n_views);
-            for (int k = 0; k < n_views; ++k) idx[(size_t)k] = { views[k].view_id, k };
-            std::sort(idx.begin(), idx.end());
-            std::vector<int> alias;
-            for (int k = 0; k < n_views; ++k) {
-                if (views[k].n_tbm != 0 || views[k].n_sources == 0) continue;
-                for (int q = 0; q < views[k].n_sources; ++q) {
-                    auto it = std::lower_bound(idx.begin(), idx.end(), std::make_pair((unsigned)views[k].source_cam[q], -1));
-                    if (it != idx.end() && it->first == (unsigned)views[k].source_cam[q] && views[it->second].n_tbm > 0) alias.push_back(it->second);
-                }
-            }
-            std::sort(alias.begin(), alias.end());
-            alias.erase(std::unique(alias.begin(), alias.end()), alias.end());
-            auto pk_bytes = [&](int b) { return al(16 + (size_t)views[b].S_src * (12 + sizeof(Match))); };
-            std::vector<size_t> slot_of((size_t)world, 0);
-            for (int b : alias) slot_of[(size_t)owner(b)] += pk_bytes(b);
-            size_t aslot = 256;
-            for (int r = 0; r < world; ++r) aslot = std::max(aslot, slot_of[(size_t)r] + 256);
-            if (!alias.empty()) {
-                std::vector<int> pk_view, pk_S;
-                std::vector<long long> pk_bo, pk_oo;
-                size_t o = 0;
-                for (int b : alias) if (owner(b) == rank) { pk_view.push_back(b); pk_S.push_back(views[b].S_src); pk_bo.push_back(best_off[(size_t)b]); pk_oo.push_back((long long)o); o += pk_bytes(b); }
-                {
-                    const size_t n = pk_view.size(), ctl = al(n * 4) * 2 + al(n * 8) * 2 + 256;
-                    hipError_t e = c->ch_stage.reserve(aslot + 256);
-                    if (e == hipSuccess) e = c->ch_gathered.reserve(aslot * (size_t)world + 256);
-                    if (e == hipSuccess) e = c->ch_send.reserve(ctl);
-                    if (e != hipSuccess) note(fail(c, L3D_ERR_NOMEM, "l3d_match_chain_partition: alias-view packages"));
-                    else if (n > 0) {
-                        unsigned char* S0 = c->ch_send.as<unsigned char>();
-                        const size_t o1 = al(n * 4), o2 = 2 * al(n * 4), o3 = o2 + al(n * 8);
-                        L3D_SOFT(hipMemcpyAsync(S0, pk_view.data(), n * 4, hipMemcpyHostToDevice, st));
-                        L3D_SOFT(hipMemcpyAsync(S0 + o1, pk_S.data(), n * 4, hipMemcpyHostToDevice, st));
-                        L3D_SOFT(hipMemcpyAsync(S0 + o2, pk_bo.data(), n * 8, hipMemcpyHostToDevice, st));
-                        L3D_SOFT(hipMemcpyAsync(S0 + o3, pk_oo.data(), n * 8, hipMemcpyHostToDevice, st));
-                        hipLaunchKernelGGL(k_alias_pack, dim3((unsigned)n), dim3(256), 0, st, c->ch_kept.as<Match>(), c->ch_res.as<ChainResult>(), reinterpret_cast<const int*>(S0), reinterpret_cast<const int*>(S0 + o1),
-                                           reinterpret_cast<const long long*>(S0 + o2), reinterpret_cast<const long long*>(S0 + o3), c->ch_best.as<float2>(), c->ch_bestpos.as<int>(), c->ch_stage.as<unsigned char>());
-                        L3D_SOFT(hipStreamSynchronize(st));        // (the control vectors are on the stack)
-                    }
-                }
-                if (int a_rc = all_gather_word(0, "packing the best matches of the views early returns name")) return a_rc;
-                if (exchange(exchange_user, -11, c->ch_stage.p, c->ch_gathered.p, aslot, world, (void*)st)) return fail(c, L3D_ERR_HIP, "l3d_match_chain_partition: the exchange of the alias views' best matches failed");
-                const unsigned char* G = c->ch_gathered.as<unsigned char>();
-                std::vector<size_t> at((size_t)world, 0);
-                for (int b : alias) {
-                    const int r = owner(b);
-                    const unsigned char* pk = G + (size_t)r * aslot + at[(size_t)r];
-                    at[(size_t)r] += pk_bytes(b);
-                    if (local_rc || (b >= exact_from && b < last)) continue;              // (held: its own records say it all)
-                    int h[4] = { 0, 0, 0, 0 };
-                    L3D_SOFT(hipMemcpyAsync(h, pk, 16, hipMemcpyDeviceToHost, st));
-                    L3D_SOFT(hipStreamSynchronize(st));
-                    const int S = views[b].S_src;
-                    if (local_rc) break;
-                    if (h[0] != b || h[3] != S || h[2] < 0 || h[2] > S) { note(fail(c, L3D_ERR_INVALID, "l3d_match_chain_partition: a package of best matches does not name the view it should")); break; }
-                    //  a view this rank does not hold can be BOTH a source of an early-return view -- its list here is then the all-gathered sliver of
-                    // records that point at that view -- and a view an early return's local numbers name: one list cannot be both, and the best matches
-                    // would replace the sliver silently.  No scene of the tests does this; a job that does is refused here, on every rank alike (the
-                    // status words carry it), and takes the segment-sharded partition (l3d_shard_chain_partition), which keeps such views whole
-                    if (hloc[(size_t)b].n_kept > 0) { note(fail(c, L3D_ERR_UNSUPPORTED, "l3d_match_chain_partition: view " + std::to_string(views[b].view_id) + " is a source of an early-return view and named by an early return's local camera number: use the segment-sharded partition")); break; }
-                    if (int rc = arena_grow_keep(c, (size_t)(used + h[2]) + 64, (size_t)used)) { note(rc); break; }
-                    if (h[2] > 0) L3D_SOFT(hipMemcpyAsync(c->ch_kept.as<Match>() + used, pk + 16 + (size_t)S * 12, (size_t)h[2] * sizeof(Match), hipMemcpyDeviceToDevice, st));
-                    L3D_SOFT(hipMemcpyAsync(c->ch_bestpos.as<int>() + best_off[(size_t)b], pk + 16, (size_t)S * 4, hipMemcpyDeviceToDevice, st));
-                    L3D_SOFT(hipMemcpyAsync(c->ch_best.as<float2>() + best_off[(size_t)b], pk + 16 + (size_t)S * 4, (size_t)S * 8, hipMemcpyDeviceToDevice, st));
-                    ChainResult& x = hloc[(size_t)b];
-                    x.kept_base = (uint64_t)used; x.n_kept = h[2]; x.R = h[1]; x.overflow = 0;
-                    used += h[2];
-                    alias_known[(size_t)b] = 1;
-                }
-            }
-        }
-        // ---- the local products
-        std::vector<ProdChainView> pvh((size_t)n_views);
-        for (int k = 0; k < n_views; ++k) {
-            const bool ver = views[k].n_tbm > 0, held = (k >= exact_from && k < last) || alias_known[(size_t)k];
-            pvh[(size_t)k].verified = ver ? 1 : 0;
-            pvh[(size_t)k].best = ver && held ? c->ch_best.as<float2>() + best_off[(size_t)k] : nullptr;
-            pvh[(size_t)k].bestpos = ver && held ? c->ch_bestpos.as<int>() + best_off[(size_t)k] : nullptr;
-        }
-        const int row0 = std::max(rank == 0 ? 0 : exact_from, own0 - reach), row1 = std::min(last, own1 + reach);
-        ProductsPart part;
-        part.active = true; part.rank = rank; part.world = world;
-        part.own_dv0 = dense_of(own0); part.own_dv1 = dense_of(own1);
-        part.row_dv0 = dense_of(row0); part.row_dv1 = dense_of(row1);
-        part.held_dv0 = dense_of(exact_from); part.held_dv1 = dense_of(last);
-        part.recovery_rounds = rounds; part.blocks_rerun = blocks_rerun;
-        int64_t n_local = 0;
-        const double t3 = now_s();
-        if (!local_rc) {
-            std::vector<char> held((size_t)n_views, 0);
-            for (int k = exact_from; k < last; ++k) held[(size_t)k] = 1;
-            note(build_products(c, views, n_views, pvh.data(), hloc.data(), map, summary, &n_local, part.row_dv0, part.row_dv1, held.data()));
-        }
-        if (int a_rc = all_gather_word(n_local, "building its rows of the products")) return a_rc;
-        part.n_pot_all = 0;
-        for (int r = 0; r < world; ++r) part.n_pot_all += words[(size_t)r];
-        P.part = part;
-        P.n_pot = n_local;
-        P.valid = true;
-        if (n_pot) *n_pot = n_local;
-        memcpy(c->ch_pin_res.as<ChainResult>(), hloc.data(), (size_t)n_views * sizeof(ChainResult));       // (what l3d_chain_kept_list reads)
-        { double kept = 0, raw = 0; for (int k = own0; k < own1; ++k) { kept += hloc[(size_t)k].n_kept; raw += hloc[(size_t)k].R; } c->stats[3] = kept; c->stats[1] = raw; }      // (this rank's block)
-        if (c->opt.timing) fprintf(stderr, "[l3d chain_partition rank %d/%d] exact from view %d, chain to view %d, rows of views %d..%d, %lld potential correspondences here of %lld: products %.2f ms\n",
-                                   rank, world, exact_from, last - 1, row0, row1 - 1, (long long)n_local, part.n_pot_all, (now_s() - t3) * 1e3);
-        *verdict = 0;
-        return L3D_OK;
-    }
-
-    // ---- all-gather of the blocks: [records of the block's views][best depth pairs][best positions], padded to the largest block
-    std::vector<long long> rec_of((size_t)world, 0), seg_of((size_t)world, 0);
-    for (int k = 0; k < n_views; ++k) {
-        const int r = owner(k);
-        rec_of[(size_t)r] += tab[(size_t)r * n_views + k].n_kept;
-        if (views[k].n_tbm > 0) seg_of[(size_t)r] += views[k].S_src;
-    }
-    long long max_rec = 0, max_seg = 0, total = 0;
-    for (int r = 0; r < world; ++r) { max_rec = std::max(max_rec, rec_of[(size_t)r]); max_seg = std::max(max_seg, seg_of[(size_t)r]); total += rec_of[(size_t)r]; }
-    const size_t o_best = al((size_t)max_rec * sizeof(Match)), o_bpos = o_best + al((size_t)max_seg * 8), slot = o_bpos + al((size_t)max_seg * 4);
-    {
-        hipError_t e = c->ch_send.reserve(slot + 256);
-        if (e == hipSuccess) e = c->ch_gathered.reserve(slot * (size_t)world + 256);
-        if (e != hipSuccess) { (void)hipGetLastError(); note(fail(c, L3D_ERR_NOMEM, "l3d_match_chain_blocks: the blocks' slots (" + std::to_string(world) + " x " + std::to_string(slot >> 20) + " MB: " + std::to_string(max_rec) + " kept matches in the largest block)")); }
-        else {
-            unsigned char* send = c->ch_send.as<unsigned char>();
-            long long own_start = 0;                                    // (this rank's arena: the views it holds, back to back from arena_first)
-            for (int k = arena_first; k < own0; ++k) own_start += hres[k].n_kept;
-            if (rec_of[(size_t)rank] > 0)
-                L3D_SOFT(hipMemcpyAsync(send, c->ch_kept.as<Match>() + own_start, (size_t)rec_of[(size_t)rank] * sizeof(Match), hipMemcpyDeviceToDevice, st));
-            if (seg_of[(size_t)rank] > 0) {
-                L3D_SOFT(hipMemcpyAsync(send + o_best, c->ch_best.as<float2>() + best_off[(size_t)own0], (size_t)seg_of[(size_t)rank] * 8, hipMemcpyDeviceToDevice, st));
-                L3D_SOFT(hipMemcpyAsync(send + o_bpos, c->ch_bestpos.as<int>() + best_off[(size_t)own0], (size_t)seg_of[(size_t)rank] * 4, hipMemcpyDeviceToDevice, st));
-            }
-        }
-    }
-    if (int a_rc = all_gather_word(0, "staging its block")) return a_rc;
-    if (exchange(exchange_user, -2, c->ch_send.p, c->ch_gathered.p, slot, world, (void*)st)) return fail(c, L3D_ERR_HIP, "l3d_match_chain_blocks: the exchange of the kept lists failed");
-    // ---- the one chain's arena: blocks in rank order = views in order; then matchViews' products: every rank builds the rows of its OWN block
-    // of views (sort + unique of the keys whose source lies in the block: its views' records and their neighbours', all of them in the arena now),
-    // the pieces are all-gathered and put together -- 1/world of the sort per rank instead of all of it on every rank
-    std::vector<ChainResult> hres_all((size_t)n_views);
-    std::vector<ProdChainView> pvh((size_t)n_views);
-    std::vector<int> dvb((size_t)world + 1);
-    for (int r = 0; r <= world; ++r) dvb[(size_t)r] = r == 0 ? 0 : (r == world ? nvd : dense_of(block_begin(r)));
-    for (int r = 1; r <= world; ++r) if (dvb[(size_t)r] < dvb[(size_t)r - 1]) return fail(c, L3D_ERR_INVALID, "l3d_match_chain_blocks: the chain's views do not ascend with the dense map");     // (the same on every rank)
-    int64_t n_local = 0;
-    double t3 = 0;
-    const auto assemble_and_build = [&]() -> int {
-        HIPCHK(c, hipStreamSynchronize(st));            // (the arena below may be reallocated: everything that reads the old one is done)
-        if (c->ch_kept.reserve(((size_t)total + 64) * sizeof(Match)) != hipSuccess) {
-            (void)hipGetLastError();
-            size_t fr = 0, tot = 0;
-            (void)hipMemGetInfo(&fr, &tot);
-            return fail(c, L3D_ERR_NOMEM, "l3d_match_chain_blocks: the one chain's arena of " + std::to_string(total) + " kept matches (" + std::to_string(((size_t)total * sizeof(Match)) >> 20) +
-                                              " MB) does not fit (" + std::to_string(fr >> 20) + " of " + std::to_string(tot >> 20) + " MB free; l3d_match_chain_partition keeps every rank's records where they are)");
-        }
-        long long base = 0;
-        for (int k = 0; k < n_views; ++k) {
-            const BlockDigest& e = tab[(size_t)owner(k) * n_views + k];
-            ChainResult& r = hres_all[(size_t)k];
-            r.kept_base = (uint64_t)base; r.n_kept = e.n_kept; r.R = e.R; r.overflow = 0;
-            base += e.n_kept;
-            const bool ver = views[k].n_tbm > 0;
-            pvh[(size_t)k].verified = ver ? 1 : 0;
-            pvh[(size_t)k].best = ver ? c->ch_best.as<float2>() + best_off[(size_t)k] : nullptr;
-            pvh[(size_t)k].bestpos = ver ? c->ch_bestpos.as<int>() + best_off[(size_t)k] : nullptr;
-        }
-        long long at = 0;
-        const unsigned char* G = c->ch_gathered.as<unsigned char>();
-        for (int r = 0; r < world; ++r) {
-            const int b0 = block_begin(r);
-            if (rec_of[(size_t)r]) HIPCHK(c, hipMemcpyAsync(c->ch_kept.as<Match>() + at, G + (size_t)r * slot, (size_t)rec_of[(size_t)r] * sizeof(Match), hipMemcpyDeviceToDevice, st));
-            if (seg_of[(size_t)r]) {
-                HIPCHK(c, hipMemcpyAsync(c->ch_best.as<float2>() + best_off[(size_t)b0], G + (size_t)r * slot + o_best, (size_t)seg_of[(size_t)r] * 8, hipMemcpyDeviceToDevice, st));
-                HIPCHK(c, hipMemcpyAsync(c->ch_bestpos.as<int>() + best_off[(size_t)b0], G + (size_t)r * slot + o_bpos, (size_t)seg_of[(size_t)r] * 4, hipMemcpyDeviceToDevice, st));
-            }
-            at += rec_of[(size_t)r];
-        }
-        t3 = now_s();
-        return build_products(c, views, n_views, pvh.data(), hres_all.data(), map, summary, &n_local, dvb[(size_t)rank], dvb[(size_t)rank + 1]);
-    };
-    // counts first (a piece is padded to the largest; a negative count = this rank failed), then [row starts of the block, numbered from 0 | entries]
-    { note(assemble_and_build()); if (int a_rc = all_gather_word((long long)n_local, "building its rows of the products")) return a_rc; }
-    const std::vector<long long> cnts = words;
-    long long max_cnt = 0, max_rows = 0, n_pot_all = 0;
-    for (int r = 0; r < world; ++r) {
-        max_cnt = std::max(max_cnt, cnts[(size_t)r]); n_pot_all += cnts[(size_t)r];
-        max_rows = std::max(max_rows, (long long)map->seg_base[dvb[(size_t)r + 1]] - map->seg_base[dvb[(size_t)r]]);
-    }
-    const size_t o_ent = al((size_t)max_rows * 8), pslot = o_ent + al((size_t)max_cnt * 4 + 4);
-    {
-        hipError_t e = c->ch_send.reserve(pslot + 256);
-        if (e == hipSuccess) e = c->ch_gathered.reserve(pslot * (size_t)world + 256);
-        if (e != hipSuccess) note(fail(c, L3D_ERR_NOMEM, "l3d_match_chain_blocks: the pieces' slots"));
-        else {
-            const long long r0 = map->seg_base[dvb[(size_t)rank]], nr = (long long)map->seg_base[dvb[(size_t)rank + 1]] - r0;
-            unsigned char* sp = c->ch_send.as<unsigned char>();
-            if (nr > 0) L3D_SOFT(hipMemcpyAsync(sp, P.pot_start.as<long long>() + r0, (size_t)nr * 8, hipMemcpyDeviceToDevice, st));
-            if (n_local > 0) L3D_SOFT(hipMemcpyAsync(sp + o_ent, P.pot_tgt.p, (size_t)n_local * 4, hipMemcpyDeviceToDevice, st));
-        }
-    }
-    if (int a_rc = all_gather_word(0, "staging its piece of the products")) return a_rc;
-    if (exchange(exchange_user, -4, c->ch_send.p, c->ch_gathered.p, pslot, world, (void*)st)) return fail(c, L3D_ERR_HIP, "l3d_match_chain_blocks: the exchange of the table pieces failed");
-    // (past the last collective: a failure from here on is this rank's alone)
-    HIPCHK(c, hipStreamSynchronize(st));
-    HIPCHK(c, P.pot_tgt.reserve(((size_t)n_pot_all + 2) * 4));
-    {
-        const unsigned char* G = c->ch_gathered.as<unsigned char>();
-        long long base = 0;
-        for (int r = 0; r < world; ++r) {
-            const long long r0 = map->seg_base[dvb[(size_t)r]], nr = (long long)map->seg_base[dvb[(size_t)r + 1]] - r0;
-            launch_prod_shift_rows(reinterpret_cast<const long long*>(G + (size_t)r * pslot), nr, base, P.pot_start.as<long long>() + r0, st);
-            if (cnts[(size_t)r]) HIPCHK(c, hipMemcpyAsync(P.pot_tgt.as<int>() + base, G + (size_t)r * pslot + o_ent, (size_t)cnts[(size_t)r] * 4, hipMemcpyDeviceToDevice, st));
-            base += cnts[(size_t)r];
-        }
-        HIPCHK(c, hipMemcpyAsync(P.pot_start.as<long long>() + map->seg_base[nvd], &n_pot_all, 8, hipMemcpyHostToDevice, st));     // the closing row start
-        HIPCHK(c, hipStreamSynchronize(st));
-        HIPCHK(c, hipGetLastError());
-    }
-    P.n_pot = n_pot_all;
-    P.valid = true;
-    if (n_pot) *n_pot = n_pot_all;
-    memcpy(c->ch_pin_res.as<ChainResult>(), hres_all.data(), (size_t)n_views * sizeof(ChainResult));       // (what l3d_chain_kept_list reads)
-    c->stats[3] = (double)total;
-    { double raw = 0; for (int k = own0; k < own1; ++k) raw += tab[(size_t)rank * n_views + k].R; c->stats[1] = raw; }      // (this rank's useful share)
-    if (c->opt.timing) fprintf(stderr, "[l3d chain_blocks rank %d/%d] gather of the blocks %.2f ms, products (own rows + gather of the pieces) %.2f ms\n", rank, world, (t3 - t2) * 1e3, (now_s() - t3) * 1e3);
-    *verdict = 0;
-    return L3D_OK;
-#undef L3D_SOFT
-}
-
-extern "C" int l3d_match_chain_blocks(l3d_ctx* c, const l3d_chain_view* views, int n_views, const l3d_dense_map* map, l3d_chain_summary* summary, int64_t* n_pot,
-                                      int rank, int world, int warmup_views, int window, l3d_exchange_fn exchange, void* exchange_user, int* verdict)
-{
-    return chain_blocks_impl(c, views, n_views, map, summary, n_pot, rank, world, warmup_views, window, exchange, exchange_user, verdict, 0);
-}
-
-extern "C" int l3d_match_chain_partition(l3d_ctx* c, const l3d_chain_view* views, int n_views, const l3d_dense_map* map, l3d_chain_summary* summary, int64_t* n_pot,
-                                         int rank, int world, int warmup_views, int window, l3d_exchange_fn exchange, void* exchange_user, int* verdict)
-{
-    return chain_blocks_impl(c, views, n_views, map, summary, n_pot, rank, world, warmup_views, window, exchange, exchange_user, verdict, 1);
-}
-
-extern "C" int l3d_partition_info(l3d_ctx* c, int info[10], int64_t* n_pot_all)
-{
-    if (!c) return L3D_ERR_INVALID;
-    const ProductsPart& q = c->products.part;
-    if (info) { const int v[10] = { q.rank, q.world, q.own_dv0, q.own_dv1, q.row_dv0, q.row_dv1, q.held_dv0, q.held_dv1, q.recovery_rounds, q.blocks_rerun }; memcpy(info, v, sizeof(v)); }
-    if (n_pot_all) *n_pot_all = q.active ? q.n_pot_all : c->products.n_pot;
-    return L3D_OK;                      // (info[1] = world of the partition; not partitioned: the defaults, world 1)
-}
-
-// =================================================================================================================================
-// Turns that hand the chain over (l3d_turns.hpp; line3d_host.cpp: node mode 2 with l3d_line3d_set_turn_handover).  The parts of the
-// blocks-of-views partition above that involve no collective, composed SEQUENTIALLY: the ranks of one device run one after the other, so a
-// successor needs no speculation -- it is given its predecessor's tail (ChainPreload, as the recovery path gives it after a miss).
-namespace {
-
-// the early-return views of a schedule with what the quirk couples them to (cudawrapper.cu:877-878, line3D.cc:861-865)
-struct TurnEarly {
-    int view = 0;
-    std::vector<int> src;           // verified earlier views whose records point at it (ProdSrc of l3d_products.hip)
-    std::vector<int> alias_rows;    // the views those sources' LOCAL camera numbers name: their rows get entries that name this view's segments
-    std::vector<int> alias_best;    // the verified views any of its local camera numbers names: k_alias_pack packages
-};
-struct TurnNeeds { std::vector<char> in_E; std::vector<int> src, alias_req, alias_opt; };
-
-void turn_early_views(const l3d_chain_view* views, int n, std::vector<TurnEarly>& out, std::vector<int>& groups_all)
-{
-    std::vector<std::pair<unsigned, int>> idx((size_t)n);
-    for (int k = 0; k < n; ++k) idx[(size_t)k] = { views[k].view_id, k };
-    std::sort(idx.begin(), idx.end());
-    auto find = [&](unsigned id) { auto it = std::lower_bound(idx.begin(), idx.end(), std::make_pair(id, -1)); return it != idx.end() && it->first == id ? it->second : -1; };
-    for (int k = 0; k < n; ++k) {
-        if (views[k].n_tbm != 0 || views[k].n_sources == 0) continue;
-        TurnEarly e;
-        e.view = k;
-        for (int q = 0; q < views[k].n_sources; ++q) {
-            const int si = views[k].source_index[q], b = find((unsigned)views[k].source_cam[q]);
-            const bool valid = si >= 0 && si < k && views[si].n_tbm > 0;
-            if (valid) { e.src.push_back(si); groups_all.push_back(si); if (b >= 0) e.alias_rows.push_back(b); }
-            if (b >= 0 && views[b].n_tbm > 0) e.alias_best.push_back(b);
-        }
-        out.push_back(e);
-    }
-    std::sort(groups_all.begin(), groups_all.end());
-    groups_all.erase(std::unique(groups_all.begin(), groups_all.end()), groups_all.end());
-}
-
-// what the share of a turn with these ranges ingests.  in_E: the early-return views it builds hypotheses and entries of -- the ones it holds and the
-// ones whose entries land in its rows; every other one is left out of its products (a partial list of sources would give it hypotheses its owner
-// does not have)
-void turn_needs(const std::vector<TurnEarly>& early, const l3d::TurnRange& t, TurnNeeds& o)
-{
-    auto held = [&](int k) { return k >= t.pre0 && k < t.run1; };
-    auto in_rows = [&](int k) { return k >= t.row0 && k < t.row1; };
-    o.in_E.assign(early.size(), 0);
-    for (size_t i = 0; i < early.size(); ++i) {
-        const TurnEarly& e = early[i];
-        bool in = held(e.view);
-        for (int b : e.alias_rows) in = in || in_rows(b);
-        if (!in) continue;
-        o.in_E[i] = 1;
-        for (int si : e.src) if (!held(si)) o.src.push_back(si);
-        for (int b : e.alias_best) if (!held(b)) { o.alias_opt.push_back(b); if (in_rows(e.view)) o.alias_req.push_back(b); }
-    }
-    for (std::vector<int>* v : { &o.src, &o.alias_req, &o.alias_opt }) { std::sort(v->begin(), v->end()); v->erase(std::unique(v->begin(), v->end()), v->end()); }
-}
-
-int turn_owner(int k, int n, int world)
-{
-    int r = (int)(((long long)k * world) / n);
-    auto bb = [&](int q) { return (int)(((long long)n * q) / world); };
-    while (r + 1 < world && bb(r + 1) <= k) ++r;
-    while (r > 0 && bb(r) > k) --r;
-    return r;
-}
-
-}  // namespace
-
-int l3d::turn_handover_schedule(const l3d_chain_view* views, int n_views, int world, int window, TurnSchedule* out)
-{
-    if (!views || n_views <= 0 || world < 1 || !out) return L3D_ERR_INVALID;
-    for (int k = 0; k < n_views; ++k) {
-        if (views[k].N < 0 || views[k].n_sources < 0 || (views[k].N > 0 && !views[k].local2global) || (views[k].n_sources > 0 && (!views[k].source_cam || !views[k].source_index))) return L3D_ERR_INVALID;
-        for (int q = 0; q < views[k].n_sources; ++q) if (views[k].source_index[q] >= n_views) return L3D_ERR_INVALID;
-    }
-    if (window <= 0) {
-        window = 1;
-        for (int k = 0; k < n_views; ++k) for (int q = 0; q < views[k].n_sources; ++q) if (views[k].source_index[q] >= 0) window = std::max(window, k - views[k].source_index[q]);
-    }
-    // reach, check and tail as chain_blocks_impl (partition = 1) computes them
-    int reach = window;
-    {
-        std::vector<std::pair<unsigned, int>> idx((size_t)n_views);
-        for (int k = 0; k < n_views; ++k) idx[(size_t)k] = { views[k].view_id, k };
-        std::sort(idx.begin(), idx.end());
-        for (int k = 0; k < n_views; ++k)
-            for (int q = 0; q < views[k].N; ++q) {
-                auto it = std::lower_bound(idx.begin(), idx.end(), std::make_pair(views[k].local2global[q], -1));
-                if (it != idx.end() && it->first == views[k].local2global[q]) reach = std::max(reach, std::abs(it->second - k));
-            }
-    }
-    TurnSchedule& S = *out;
-    S.reach = reach; S.tail = 2 * reach; S.check = std::max(window, 2 * reach); S.supported = true;
-    S.turns.assign((size_t)world, TurnRange());
-    for (int r = 0; r < world; ++r) {
-        TurnRange& t = S.turns[(size_t)r];
-        t.own0 = (int)(((long long)n_views * r) / world); t.own1 = (int)(((long long)n_views * (r + 1)) / world);
-        t.run1 = std::min(n_views, t.own1 + S.tail);
-        t.pre0 = r == 0 ? 0 : std::max(0, t.own0 - S.check);
-        t.run0 = r == 0 ? 0 : t.own0;
-        t.row0 = std::max(t.pre0, t.own0 - reach); t.row1 = std::min(t.run1, t.own1 + reach);
-        t.deferred = 0;
-    }
-    std::vector<TurnEarly> early;
-    std::vector<int> groups_all;
-    turn_early_views(views, n_views, early, groups_all);
-    if (early.size() > 64 || groups_all.size() > 480) S.supported = false;
-    for (int r = 0; r < world && world > 1; ++r) {
-        TurnNeeds need;
-        turn_needs(early, S.turns[(size_t)r], need);
-        for (int si : need.src) if (turn_owner(si, n_views, world) > r) S.turns[(size_t)r].deferred = 1;
-        for (int b : need.alias_req) if (turn_owner(b, n_views, world) > r) S.turns[(size_t)r].deferred = 1;
-        // (chain_blocks_impl: one list cannot be both the sliver of records that point at an early-return view and the view's best matches)
-        for (int b : need.alias_opt) if (std::binary_search(need.src.begin(), need.src.end(), b)) S.supported = false;
-    }
-    return L3D_OK;
-}
-
-extern "C" int l3d_turn_handover_plan(const l3d_chain_view* views, int n_views, int world, int32_t* out, int32_t* info)
-{
-    if (!out) return L3D_ERR_INVALID;
-    l3d::TurnSchedule S;
-    if (const int rc = l3d::turn_handover_schedule(views, n_views, world, 0, &S)) return rc;
-    for (int r = 0; r < world; ++r) {
-        const l3d::TurnRange& t = S.turns[(size_t)r];
-        const int v[8] = { t.pre0, t.run0, t.run1, t.row0, t.row1, t.own0, t.own1, t.deferred };
-        memcpy(out + 8 * r, v, sizeof(v));
-    }
-    if (info) { info[0] = S.reach; info[1] = S.check; info[2] = S.tail; info[3] = S.supported ? 1 : 0; }
-    return L3D_OK;
-}
-
-void l3d::turn_handover_release(TurnHandover* p)
-{
-    if (!p) return;
-    if (p->dev) { if (p->device >= 0) (void)hipSetDevice(p->device); (void)hipFree(p->dev); }
-    *p = TurnHandover();
-}
-void l3d::turn_store_release(TurnStore* s)
-{
-    if (!s) return;
-    if (s->device >= 0) (void)hipSetDevice(s->device);
-    for (auto& x : s->early) if (x.owns && x.base) (void)hipFree(x.base);
-    for (auto& x : s->alias) if (x.owns && x.base) (void)hipFree(x.base);
-    *s = TurnStore();
-}
-
-int l3d::match_chain_turn(l3d_ctx* c, const l3d_chain_view* views, int n_views, const l3d_dense_map* map, l3d_chain_summary* summary, int rank, int world, int window,
-                          const TurnHandover* in, TurnHandover* out, TurnStore* store, bool build_share, TurnReport* report)
-{
-    if (!c) return L3D_ERR_INVALID;
-    if (!views || n_views <= 0 || !map || !summary || !store || !report || world < 1 || rank < 0 || rank >= world || window < 0) return fail(c, L3D_ERR_INVALID, "match_chain_turn: bad argument");
-    TurnSchedule S;
-    if (turn_handover_schedule(views, n_views, world, window, &S)) return fail(c, L3D_ERR_INVALID, "match_chain_turn: bad schedule");
-    if (!S.supported) return fail(c, L3D_ERR_UNSUPPORTED, "match_chain_turn: a schedule the blocks-of-views partition refuses (early returns)");
-    const TurnRange T = S.turns[(size_t)rank];
-    const int last = T.run1, exact_from = T.pre0;
-    // option regrow_free_mb (tests: a card with less room): what the turn's arena may hold, records with their side words -- run_chain's first guess
-    // and regrow and the slices of step 4 all stay within it (the compact arena of a plain turn: l3d_line3d_shard_run)
-    struct RoomGuard { l3d_ctx* c; ~RoomGuard() { c->turn_arena_room = 0; } } room_guard{ c };
-    c->turn_arena_room = c->opt.regrow_free_mb > 0 ? ((size_t)c->opt.regrow_free_mb << 20) / (sizeof(Match) + 4) : 0;
-    const size_t room = c->turn_arena_room;
-    auto grow_within_room = [&](long long records, long long used_records) -> int {
-        if (room && (size_t)records > room)
-            return fail(c, L3D_ERR_NOMEM, "match_chain_turn: the arena of rank " + std::to_string(rank) + " needs " + std::to_string(records) + " records with the slices of the views it does not hold, there is room for " +
-                                          std::to_string(room) + " (" + std::to_string(c->opt.regrow_free_mb) + " MB at " + std::to_string(sizeof(Match) + 4) + " B per record)");
-        return arena_grow_keep(c, (size_t)records + 64, (size_t)used_records);
-    };
-    c->products.valid = false;
-    c->products.part = ProductsPart();
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    if (store->device < 0) { store->device = c->device; store->early.assign((size_t)n_views, TurnStore::Piece()); store->alias.assign((size_t)n_views, TurnStore::Piece()); store->has_early.assign((size_t)n_views, 0); store->has_alias.assign((size_t)n_views, 0); }
-    if (store->device != c->device || (int)store->early.size() != n_views) return fail(c, L3D_ERR_INVALID, "match_chain_turn: the store belongs to another device or scene");
-    // offsets of the views' slices in the whole-run arrays of best pairs / positions (chain_assign_arenas: verified views back to back)
-    std::vector<long long> best_off((size_t)n_views + 1, 0);
-    for (int k = 0; k < n_views; ++k) best_off[(size_t)k + 1] = best_off[(size_t)k] + (views[k].n_tbm > 0 ? views[k].S_src : 0);
-
-    // ---- 1. the chain piece: cold from view 0 (turn 0), else warm from the predecessor's tail
-    const double t0 = now_s();
-    if (T.run0 > T.pre0) {
-        if (!in || !in->dev || in->device != c->device || in->k0 != T.pre0 || in->k1 != T.run0 || (int)in->n_kept.size() != T.run0 - T.pre0 || (int)in->R.size() != T.run0 - T.pre0)
-            return fail(c, L3D_ERR_INVALID, "match_chain_turn: rank " + std::to_string(rank) + " was not handed the views " + std::to_string(T.pre0) + ".." + std::to_string(T.run0 - 1) + " of its predecessor");
-        ChainPreload pre;
-        pre.k0 = T.pre0; pre.k1 = T.run0;
-        const unsigned char* G = static_cast<const unsigned char*>(in->dev);
-        pre.records = reinterpret_cast<const Match*>(G);
-        pre.best = reinterpret_cast<const float2*>(G + in->o_best);
-        pre.bestpos = reinterpret_cast<const int*>(G + in->o_bpos);
-        pre.n_kept = in->n_kept; pre.R = in->R;
-        if (int rc = run_chain(c, views, n_views, nullptr, nullptr, nullptr, nullptr, nullptr, T.run0, last, &pre)) return rc;
-    } else if (int rc = run_chain(c, views, n_views, nullptr, nullptr, nullptr, nullptr, nullptr, T.run0, last)) return rc;
-    report->views_computed = last - T.run0;
-    // (a job sized by memory: what only a running chain needs goes back before anything else is allocated -- as the partition does)
-    if (c->opt.part_release != 0) {
-        HIPCHK(c, hipStreamSynchronize(st)); HIPCHK(c, hipStreamSynchronize(c->stage1_stream));
-        DevBuf* b[] = { &c->ch_ringA_meta, &c->ch_ringA_depths, &c->cand_meta, &c->cand_depths, &c->cand_conf, &c->vw_scratch, &c->ch_mask, &c->ch_rays, &c->ch_rowcnt, &c->ch_rowA };
-        for (DevBuf* x : b) x->release();
-    }
-    const ChainResult* hres = c->ch_pin_res.as<ChainResult>();
-    const double t1 = now_s();
-    {
-        double p = 0;
-        for (int k = T.own0; k < T.own1; ++k)
-            for (int j = 0; j < views[k].n_tbm; ++j) p += (double)views[k].S_src * views[k].offsets[2 * views[k].to_be_matched[j] + 1];
-        c->stats[0] = p;
-    }
-    std::vector<ChainResult> hloc((size_t)n_views);
-    long long used = 0;
-    for (int k = 0; k < n_views; ++k) { hloc[(size_t)k] = ChainResult(); if (k >= exact_from && k < last) { hloc[(size_t)k] = hres[k]; used = std::max(used, (long long)hres[k].kept_base + hres[k].n_kept); } }
-    if ((size_t)used * sizeof(Match) > c->ch_kept.cap) return fail(c, L3D_ERR_INVALID, "match_chain_turn: the chain's result records point outside its arena");
-    // the final records on the device (a restart rewrites them) and the digests of every view held
-    HIPCHK(c, hipMemcpyAsync(c->ch_res.p, hloc.data(), (size_t)n_views * sizeof(ChainResult), hipMemcpyHostToDevice, st));
-    report->hash.assign((size_t)n_views, 0); report->n_kept.assign((size_t)n_views, 0); report->held.assign((size_t)n_views, 0);
-    for (int k = exact_from; k < last; ++k) report->held[(size_t)k] = 1;
-    {
-        const size_t tab_bytes = al((size_t)n_views * sizeof(BlockDigest));
-        HIPCHK(c, c->ch_hdr.reserve(tab_bytes + 256));
-        BlockDigest* dd = c->ch_hdr.as<BlockDigest>();
-        HIPCHK(c, hipMemsetAsync(dd, 0, tab_bytes, st));
-        for (int k0 = exact_from; k0 < last; k0 += 32768)
-            hipLaunchKernelGGL(k_block_digest, dim3(16, (unsigned)std::min(32768, last - k0)), dim3(256), 0, st, c->ch_kept.as<Match>(), c->ch_res.as<ChainResult>(), k0, dd);
-        std::vector<BlockDigest> hd((size_t)n_views);
-        HIPCHK(c, hipMemcpyAsync(hd.data(), dd, (size_t)n_views * sizeof(BlockDigest), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        HIPCHK(c, hipGetLastError());
-        for (int k = exact_from; k < last; ++k) { report->hash[(size_t)k] = hd[(size_t)k].hash; report->n_kept[(size_t)k] = hd[(size_t)k].n_kept; }
-    }
-    report->arena_records = used;
-
-    // ---- 2. the tail for the successor, before the records go: [records | best depth pairs | best positions] of the last `check` views of the block
-    if (out && rank + 1 < world) {
-        turn_handover_release(out);
-        const TurnRange& N = S.turns[(size_t)rank + 1];
-        const int k0 = N.pre0, k1 = N.run0;
-        if (k0 < exact_from || k1 > last || k1 < k0) return fail(c, L3D_ERR_INVALID, "match_chain_turn: the successor's preload is not covered by what this rank holds");
-        long long t_rec = 0, t_seg = 0;
-        for (int k = k0; k < k1; ++k) { t_rec += hloc[(size_t)k].n_kept; if (views[k].n_tbm > 0) t_seg += views[k].S_src; }
-        out->device = c->device; out->k0 = k0; out->k1 = k1;
-        out->o_best = al((size_t)t_rec * sizeof(Match)); out->o_bpos = out->o_best + al((size_t)t_seg * 8); out->bytes = out->o_bpos + al((size_t)t_seg * 4) + 256;
-        if (hipMalloc(&out->dev, out->bytes) != hipSuccess) { (void)hipGetLastError(); out->dev = nullptr; return fail(c, L3D_ERR_NOMEM, "match_chain_turn: the hand-over package of " + std::to_string(out->bytes >> 20) + " MB"); }
-        unsigned char* G = static_cast<unsigned char*>(out->dev);
-        long long at = 0;
-        for (int k = k0; k < k1; ++k) {
-            const ChainResult& r = hloc[(size_t)k];
-            out->n_kept.push_back(r.n_kept); out->R.push_back(r.R);
-            if (r.n_kept > 0) HIPCHK(c, hipMemcpyAsync(G + (size_t)at * sizeof(Match), c->ch_kept.as<Match>() + r.kept_base, (size_t)r.n_kept * sizeof(Match), hipMemcpyDeviceToDevice, st));
-            at += r.n_kept;
-        }
-        if (t_seg > 0) {
-            HIPCHK(c, hipMemcpyAsync(G + out->o_best, c->ch_best.as<float2>() + best_off[(size_t)k0], (size_t)t_seg * 8, hipMemcpyDeviceToDevice, st));
-            HIPCHK(c, hipMemcpyAsync(G + out->o_bpos, c->ch_bestpos.as<int>() + best_off[(size_t)k0], (size_t)t_seg * 4, hipMemcpyDeviceToDevice, st));
-        }
-        HIPCHK(c, hipStreamSynchronize(st));
-    }
-
-    // ---- 3. the quirk store: what this rank's block owes the other turns (filed once: a second visit finds its pieces there)
-    std::vector<TurnEarly> early;
-    std::vector<int> groups_all;
-    turn_early_views(views, n_views, early, groups_all);
-    std::vector<unsigned> early_ids;
-    for (const TurnEarly& e : early) early_ids.push_back(views[e.view].view_id);
-    if (world > 1 && !groups_all.empty()) {
-        std::vector<int> mine;
-        for (int si : groups_all) if (turn_owner(si, n_views, world) == rank && !store->has_early[(size_t)si]) mine.push_back(si);
-        if (!mine.empty()) {
-            // (control block as in the partition: 64 ids, 480 groups -- turn_handover_schedule refuses more)
-            const size_t o_ids = 0, o_grp = 256, o_off = o_grp + 2048, o_cnt = o_off + 4096, ctl = o_cnt + 2048;
-            HIPCHK(c, c->ch_send.reserve(ctl + 256));
-            unsigned char* S0 = c->ch_send.as<unsigned char>();
-            std::vector<int> cnt(mine.size(), 0);
-            HIPCHK(c, hipMemcpyAsync(S0 + o_ids, early_ids.data(), early_ids.size() * 4, hipMemcpyHostToDevice, st));
-            HIPCHK(c, hipMemcpyAsync(S0 + o_grp, mine.data(), mine.size() * 4, hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(k_early_pack, dim3((unsigned)mine.size()), dim3(256), 0, st, c->ch_kept.as<Match>(), c->ch_res.as<ChainResult>(), reinterpret_cast<const int*>(S0 + o_grp),
-                               reinterpret_cast<const unsigned*>(S0 + o_ids), (int)early_ids.size(), (const long long*)nullptr, (Match*)nullptr, reinterpret_cast<int*>(S0 + o_cnt));
-            HIPCHK(c, hipMemcpyAsync(cnt.data(), S0 + o_cnt, mine.size() * 4, hipMemcpyDeviceToHost, st));
-            HIPCHK(c, hipStreamSynchronize(st));
-            std::vector<long long> offs(mine.size(), 0);
-            long long total = 0;
-            for (size_t g = 0; g < mine.size(); ++g) { offs[g] = total; total += cnt[g]; }
-            // one allocation for this rank's sources (the first piece owns it), a slice per source
-            void* buf = nullptr;
-            if (hipMalloc(&buf, (size_t)std::max<long long>(total, 1) * sizeof(Match)) != hipSuccess) { (void)hipGetLastError(); return fail(c, L3D_ERR_NOMEM, "match_chain_turn: the records that point at early-return views"); }
-            // (filed at once: whatever fails below, the store owns the allocation)
-            for (size_t g = 0; g < mine.size(); ++g) {
-                TurnStore::Piece& x = store->early[(size_t)mine[g]];
-                x.base = buf; x.off = (size_t)offs[g] * sizeof(Match); x.n = cnt[g]; x.owns = g == 0;
-            }
-            if (total > 0) {
-                HIPCHK(c, hipMemcpyAsync(S0 + o_off, offs.data(), offs.size() * 8, hipMemcpyHostToDevice, st));
-                hipLaunchKernelGGL(k_early_pack, dim3((unsigned)mine.size()), dim3(256), 0, st, c->ch_kept.as<Match>(), c->ch_res.as<ChainResult>(), reinterpret_cast<const int*>(S0 + o_grp),
-                                   reinterpret_cast<const unsigned*>(S0 + o_ids), (int)early_ids.size(), reinterpret_cast<const long long*>(S0 + o_off), static_cast<Match*>(buf), (int*)nullptr);
-            }
-            const hipError_t e = hipStreamSynchronize(st);
-            if (e != hipSuccess) return fail(c, L3D_ERR_HIP, std::string("match_chain_turn: packing the early-return records: ") + hipGetErrorString(e));
-            for (int si : mine) store->has_early[(size_t)si] = 1;
-        }
-    }
-    auto pk_bytes = [&](int b) { return al(16 + (size_t)views[b].S_src * (12 + sizeof(Match))); };
-    if (world > 1 && !early.empty()) {
-        std::vector<int> alias;
-        for (const TurnEarly& e : early) alias.insert(alias.end(), e.alias_best.begin(), e.alias_best.end());
-        std::sort(alias.begin(), alias.end());
-        alias.erase(std::unique(alias.begin(), alias.end()), alias.end());
-        std::vector<int> pk_view, pk_S;
-        std::vector<long long> pk_bo, pk_oo;
-        size_t o = 0;
-        for (int b : alias) if (turn_owner(b, n_views, world) == rank && !store->has_alias[(size_t)b]) { pk_view.push_back(b); pk_S.push_back(views[b].S_src); pk_bo.push_back(best_off[(size_t)b]); pk_oo.push_back((long long)o); o += pk_bytes(b); }
-        const size_t n = pk_view.size();
-        if (n > 0) {
-            const size_t o1 = al(n * 4), o2 = 2 * al(n * 4), o3 = o2 + al(n * 8), ctl = al(n * 4) * 2 + al(n * 8) * 2 + 256;
-            HIPCHK(c, c->ch_send.reserve(ctl));
-            void* buf = nullptr;
-            if (hipMalloc(&buf, o + 256) != hipSuccess) { (void)hipGetLastError(); return fail(c, L3D_ERR_NOMEM, "match_chain_turn: alias-view packages"); }
-            unsigned char* S0 = c->ch_send.as<unsigned char>();
-            hipError_t e = hipMemcpyAsync(S0, pk_view.data(), n * 4, hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(S0 + o1, pk_S.data(), n * 4, hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(S0 + o2, pk_bo.data(), n * 8, hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(S0 + o3, pk_oo.data(), n * 8, hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) {
-                hipLaunchKernelGGL(k_alias_pack, dim3((unsigned)n), dim3(256), 0, st, c->ch_kept.as<Match>(), c->ch_res.as<ChainResult>(), reinterpret_cast<const int*>(S0), reinterpret_cast<const int*>(S0 + o1),
-                                   reinterpret_cast<const long long*>(S0 + o2), reinterpret_cast<const long long*>(S0 + o3), c->ch_best.as<float2>(), c->ch_bestpos.as<int>(), static_cast<unsigned char*>(buf));
-                e = hipStreamSynchronize(st);
-            }
-            if (e != hipSuccess) { (void)hipFree(buf); return fail(c, L3D_ERR_HIP, std::string("match_chain_turn: packing the alias views' best matches: ") + hipGetErrorString(e)); }
-            for (size_t i = 0; i < n; ++i) {
-                TurnStore::Piece& x = store->alias[(size_t)pk_view[i]];
-                x.base = buf; x.off = (size_t)pk_oo[i]; x.n = pk_S[i]; x.owns = i == 0;
-                store->has_alias[(size_t)pk_view[i]] = 1;
-            }
-        }
-    }
-    if (!build_share) {
-        if (c->opt.timing) fprintf(stderr, "[l3d chain_turn rank %d/%d] views %d..%d warm from %d: chain %.2f ms, tail and store %.2f ms; the share is deferred\n", rank, world, T.run0, last - 1, T.pre0, (t1 - t0) * 1e3, (now_s() - t1) * 1e3);
-        return L3D_OK;
-    }
-
-    // ---- 4. the share: the slices of the views this rank does not hold come out of the store (the partition reads them from the gathered buffers)
-    TurnNeeds need;
-    turn_needs(early, T, need);
-    for (int si : need.src) {
-        if (!store->has_early[(size_t)si]) return fail(c, L3D_ERR_INVALID, "match_chain_turn: rank " + std::to_string(rank) + " builds its share before the records of view " + std::to_string(views[si].view_id) + " that point at early-return views are filed");
-        const int n = store->early[(size_t)si].n;
-        const Match* src = reinterpret_cast<const Match*>(static_cast<const unsigned char*>(store->early[(size_t)si].base) + store->early[(size_t)si].off);
-        if (n <= 0) continue;
-        if (!store->early[(size_t)si].base) return fail(c, L3D_ERR_INVALID, "match_chain_turn: a filed slice has no allocation");
-        if (int rc = grow_within_room(used + n, used)) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->ch_kept.as<Match>() + used, src, (size_t)n * sizeof(Match), hipMemcpyDeviceToDevice, st));
-        ChainResult& x = hloc[(size_t)si];
-        x.kept_base = (uint64_t)used; x.n_kept = n; x.R = n; x.overflow = 0;
-        used += n;
-    }
-    std::vector<char> alias_known((size_t)n_views, 0);
-    for (int b : need.alias_opt) {
-        if (!store->has_alias[(size_t)b]) {
-            if (std::binary_search(need.alias_req.begin(), need.alias_req.end(), b)) return fail(c, L3D_ERR_INVALID, "match_chain_turn: rank " + std::to_string(rank) + " builds its share before the best matches of view " + std::to_string(views[b].view_id) + " are filed");
-            continue;
-        }
-        const unsigned char* pk = static_cast<const unsigned char*>(store->alias[(size_t)b].base) + store->alias[(size_t)b].off;
-        if (!store->alias[(size_t)b].base) return fail(c, L3D_ERR_INVALID, "match_chain_turn: a filed package has no allocation");
-        int h[4] = { 0, 0, 0, 0 };
-        HIPCHK(c, hipMemcpyAsync(h, pk, 16, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        const int Sb = views[b].S_src;
-        if (h[0] != b || h[3] != Sb || h[2] < 0 || h[2] > Sb) return fail(c, L3D_ERR_INVALID, "match_chain_turn: a package of best matches does not name the view it should");
-        if (hloc[(size_t)b].n_kept > 0) return fail(c, L3D_ERR_UNSUPPORTED, "match_chain_turn: view " + std::to_string(views[b].view_id) + " is a source of an early-return view and named by an early return's local camera number");
-        if (int rc = grow_within_room(used + h[2], used)) return rc;
-        if (h[2] > 0) HIPCHK(c, hipMemcpyAsync(c->ch_kept.as<Match>() + used, pk + 16 + (size_t)Sb * 12, (size_t)h[2] * sizeof(Match), hipMemcpyDeviceToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(c->ch_bestpos.as<int>() + best_off[(size_t)b], pk + 16, (size_t)Sb * 4, hipMemcpyDeviceToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(c->ch_best.as<float2>() + best_off[(size_t)b], pk + 16 + (size_t)Sb * 4, (size_t)Sb * 8, hipMemcpyDeviceToDevice, st));
-        ChainResult& x = hloc[(size_t)b];
-        x.kept_base = (uint64_t)used; x.n_kept = h[2]; x.R = h[1]; x.overflow = 0;
-        used += h[2];
-        alias_known[(size_t)b] = 1;
-    }
-    report->arena_records = used;
-    // an early-return view outside the set this share is about contributes nothing here: its entries land in other ranks' rows, and a partial list of
-    // its sources would give it hypotheses its owner does not have
-    std::vector<l3d_chain_view> vloc(views, views + n_views);
-    for (size_t i = 0; i < early.size(); ++i) if (!need.in_E[i]) vloc[(size_t)early[i].view].n_sources = 0;
-    const int nvd = map->n_views;
-    auto dense_of = [&](int k) {
-        if (k >= n_views) return nvd;
-        const uint32_t* it = std::lower_bound(map->view_ids, map->view_ids + nvd, views[k].view_id);
-        return (int)(it - map->view_ids);
-    };
-    std::vector<ProdChainView> pvh((size_t)n_views);
-    for (int k = 0; k < n_views; ++k) {
-        const bool ver = views[k].n_tbm > 0, held = (k >= exact_from && k < last) || alias_known[(size_t)k];
-        pvh[(size_t)k].verified = ver ? 1 : 0;
-        pvh[(size_t)k].best = ver && held ? c->ch_best.as<float2>() + best_off[(size_t)k] : nullptr;
-        pvh[(size_t)k].bestpos = ver && held ? c->ch_bestpos.as<int>() + best_off[(size_t)k] : nullptr;
-    }
-    const int row0 = T.row0, row1 = T.row1;
-    ProductsPart part;
-    part.active = true; part.rank = rank; part.world = world;
-    part.own_dv0 = dense_of(T.own0); part.own_dv1 = dense_of(T.own1);
-    part.row_dv0 = dense_of(row0); part.row_dv1 = dense_of(row1);
-    part.held_dv0 = dense_of(exact_from); part.held_dv1 = dense_of(last);
-    int64_t n_local = 0;
-    const double t3 = now_s();
-    {
-        std::vector<char> held((size_t)n_views, 0);
-        for (int k = exact_from; k < last; ++k) held[(size_t)k] = 1;
-        if (int rc = build_products(c, vloc.data(), n_views, pvh.data(), hloc.data(), map, summary, &n_local, part.row_dv0, part.row_dv1, held.data())) return rc;
-    }
-    Products& P = c->products;
-    part.n_pot_all = n_local;           // (no collective here: the node object adds the other turns' counts when all of them are through -- ctx_part_total)
-    report->n_pot = n_local;
-    P.part = part;
-    P.n_pot = n_local;
-    P.valid = true;
-    memcpy(c->ch_pin_res.as<ChainResult>(), hloc.data(), (size_t)n_views * sizeof(ChainResult));       // (what l3d_chain_kept_list reads)
-    { double kept = 0, raw = 0; for (int k = T.own0; k < T.own1; ++k) { kept += hloc[(size_t)k].n_kept; raw += hloc[(size_t)k].R; } c->stats[3] = kept; c->stats[1] = raw; }
-    if (c->opt.timing) fprintf(stderr, "[l3d chain_turn rank %d/%d] views %d..%d warm from %d: chain %.2f ms, rows of views %d..%d, %lld potential correspondences: products %.2f ms\n",
-                               rank, world, T.run0, last - 1, T.pre0, (t1 - t0) * 1e3, row0, row1 - 1, (long long)n_local, (now_s() - t3) * 1e3);
-    return L3D_OK;
 }
 
 void l3d::warm_chain() { touch_kernel(reinterpret_cast<const void*>(&k_exist_count)); }

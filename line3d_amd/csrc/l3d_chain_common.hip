@@ -329,4 +329,50 @@ void chain_launch_verify(l3d_ctx* c, VerifyArgs& va, const ChainViewDev& d, cons
     }
 }
 
+ScheduleIndex::ScheduleIndex(const l3d_chain_view* views_, int n_views) : views(views_), n(n_views), idx((size_t)std::max(0, n_views))
+{
+    for (int k = 0; k < n; ++k) idx[(size_t)k] = { views[k].view_id, k };
+    std::sort(idx.begin(), idx.end());
+}
+int ScheduleIndex::find(unsigned view_id) const
+{
+    const auto it = std::lower_bound(idx.begin(), idx.end(), std::make_pair(view_id, -1));
+    return it != idx.end() && it->first == view_id ? it->second : -1;
+}
+int ScheduleIndex::neighbour_reach() const
+{
+    int reach = 0;
+    for (int k = 0; k < n; ++k) {
+        if (!views[k].local2global) continue;
+        for (int q = 0; q < views[k].N; ++q) { const int j = find(views[k].local2global[q]); if (j >= 0) reach = std::max(reach, std::abs(j - k)); }
+    }
+    return reach;
+}
+
+int release_chain_scratch(l3d_ctx* c, std::initializer_list<DevBuf*> extra)
+{
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stage1_stream));
+    DevBuf* b[] = { &c->ch_ringA_meta, &c->ch_ringA_depths, &c->cand_meta, &c->cand_depths, &c->cand_conf, &c->vw_scratch, &c->ch_mask, &c->ch_rays, &c->ch_rowcnt, &c->ch_rowA };
+    for (DevBuf* x : b) x->release();
+    for (DevBuf* x : extra) x->release();
+    return L3D_OK;
+}
+
+int chain_dense_view(const l3d_chain_view* views, int n_views, const l3d_dense_map* map, int k)
+{
+    if (k >= n_views) return map->n_views;
+    return (int)(std::lower_bound(map->view_ids, map->view_ids + map->n_views, views[k].view_id) - map->view_ids);
+}
+ProductsPart products_part(const l3d_chain_view* views, int n_views, const l3d_dense_map* map, int rank, int world, int own0, int own1, int row0, int row1, int held0, int held1)
+{
+    const auto dv = [&](int k) { return chain_dense_view(views, n_views, map, k); };
+    ProductsPart part;
+    part.active = true; part.rank = rank; part.world = world;
+    part.own_dv0 = dv(own0); part.own_dv1 = dv(own1);
+    part.row_dv0 = dv(row0); part.row_dv1 = dv(row1);
+    part.held_dv0 = dv(held0); part.held_dv1 = dv(held1);
+    return part;
+}
+
 }  // namespace l3d

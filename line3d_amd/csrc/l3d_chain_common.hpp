@@ -2,8 +2,12 @@
 // validation of the caller's view descriptions, the layout and upload of the static tables, the per-view slices of the whole-run
 // arenas, the argument blocks of the kernels and the sizing rules (first capacity guesses, LDS image of the window kernel).  One copy
 // of every rule; the two files differ in what happens BETWEEN the views (an arena slice vs. a slot and an exchange).
+// Behind those: what the partitioned jobs on top of either chain share (l3d_chain_partition.hip, l3d_shard_chain_partition) -- the index of a
+// schedule's view ids, the release of the chain's scratch, a rank's ranges as views of the dense map.
 #pragma once
 
+#include <initializer_list>
+#include <utility>
 #include <vector>
 
 #include "l3d_ctx.hpp"
@@ -59,5 +63,31 @@ void chain_launch_verify(l3d_ctx* c, VerifyArgs& va, const ChainViewDev& d, cons
 // first guess of the candidate capacity from the largest view's pair count (raw density ~6 % + reverse matches; guarded on the device)
 inline size_t chain_first_cand_cap(double max_pairs) { return (size_t)(max_pairs * 0.12) + 65536; }
 inline size_t chain_align16(size_t x) { return (x + 15) & ~(size_t)15; }
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// internal to the library: not among its dynamic symbols
+#define L3D_HIDDEN __attribute__((visibility("hidden")))
+
+// The chain position of a view id, over one schedule.  Host only: no context, no device.
+struct L3D_HIDDEN ScheduleIndex {
+    ScheduleIndex(const l3d_chain_view* views, int n_views);
+    int find(unsigned view_id) const;       // chain position, or -1
+    // the largest distance, in chain positions, between a view and one of its neighbours (0: no neighbour is in the schedule)
+    int neighbour_reach() const;
+private:
+    const l3d_chain_view* views;
+    int n;
+    std::vector<std::pair<unsigned, int>> idx;      // (view_id, position), sorted
+};
+
+// What only a running chain needs (candidate store and its ring, window scratch, bit rows, viewing rays, row counters: 10-15 GB at 4000 segments x 24
+// neighbours), given back once both streams are idle -- a job sized by memory does this before it builds its products.  extra: the caller's own.
+L3D_HIDDEN int release_chain_scratch(l3d_ctx* c, std::initializer_list<DevBuf*> extra = {});
+
+// the dense view a chain view is (ids ascend in both; k >= n_views: one past the last)
+L3D_HIDDEN int chain_dense_view(const l3d_chain_view* views, int n_views, const l3d_dense_map* map, int k);
+// a rank's share of partitioned products from its ranges in chain positions: its block, the views whose rows it builds, the views it holds
+L3D_HIDDEN ProductsPart products_part(const l3d_chain_view* views, int n_views, const l3d_dense_map* map, int rank, int world,
+                                      int own0, int own1, int row0, int row1, int held0, int held1);
 
 }  // namespace l3d

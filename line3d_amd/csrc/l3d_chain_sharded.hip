@@ -1164,21 +1164,14 @@ static int shard_products_local(l3d_shard_chain* h, const l3d_dense_map* map, l3
         h->kept_total = (double)total;
         if (h->partition) {
             // this rank's share: rows of the views within reach of its block, best matches / medians of every view it kept
-            auto dense_of = [&](int k) { if (k >= nv) return map->n_views; const uint32_t* it = std::lower_bound(map->view_ids, map->view_ids + map->n_views, h->views[k].view_id); return (int)(it - map->view_ids); };
-            ProductsPart part;
-            part.active = true; part.rank = h->rank; part.world = h->world;
+            const int own0 = h->part_own0, own1 = h->part_own1, reach = h->part_reach;
+            ProductsPart part = products_part(h->views, nv, map, h->rank, h->world, own0, own1, std::max(0, own0 - reach), std::min(nv, own1 + reach), std::max(0, own0 - 2 * reach), std::min(nv, own1 + 2 * reach));
             // (a turn of a node object whose ranks share a device: the share was computed alone -- world 1 -- and joins the collective finish as the rank it stands for)
             if (c->turn_share && h->world == 1 && c->opt.part_vworld > 0) { part.world = c->opt.part_vworld; part.rank = std::max(0, std::min(c->opt.part_vrank, part.world - 1)); }
-            part.own_dv0 = dense_of(h->part_own0); part.own_dv1 = dense_of(h->part_own1);
-            part.row_dv0 = dense_of(std::max(0, h->part_own0 - h->part_reach)); part.row_dv1 = dense_of(std::min(nv, h->part_own1 + h->part_reach));
-            part.held_dv0 = dense_of(std::max(0, h->part_own0 - 2 * h->part_reach)); part.held_dv1 = dense_of(std::min(nv, h->part_own1 + 2 * h->part_reach));
             int64_t n_local = 0;
             if (c->opt.part_release != 0) {
-                // the job is sized by memory: what only the running chain needed -- the rings of slots, the candidate store and its ring, window scratch,
-                // bit rows, viewing rays, row counters -- is given back before the products are built (as l3d_match_chain_partition does)
-                (void)hipStreamSynchronize(st); (void)hipStreamSynchronize(c->stage1_stream);
-                DevBuf* b[] = { &c->ch_gathered, &c->ch_send, &c->ch_ringA_meta, &c->ch_ringA_depths, &c->cand_meta, &c->cand_depths, &c->cand_conf, &c->vw_scratch, &c->ch_mask, &c->ch_rays, &c->ch_rowcnt, &c->ch_rowA };
-                for (DevBuf* x : b) x->release();
+                // the job is sized by memory: the chain's scratch and the rings of slots are given back before the products are built (as l3d_match_chain_partition does)
+                if (int rc = release_chain_scratch(c, { &c->ch_gathered, &c->ch_send })) return rc;
                 h->gathered = nullptr;
             }
             const int rc = build_products(c, h->views, nv, pvh.data(), hres.data(), map, summary, &n_local, part.row_dv0, part.row_dv1, reinterpret_cast<const char*>(h->keep.data()), qt_arena);
@@ -1215,13 +1208,8 @@ int l3d_partition_keep_views(const l3d_chain_view* views, int nv, int own_begin,
 {
     // (host logic only: no context, no device -- tests/test_partition_keep_cpu.py runs it without a GPU)
     if (!views || !keep || nv < 0 || own_begin < 0 || own_end > nv || own_begin > own_end) return L3D_ERR_INVALID;
-    std::vector<std::pair<unsigned, int>> idx((size_t)nv);
-    for (int k = 0; k < nv; ++k) idx[(size_t)k] = { views[k].view_id, k };
-    std::sort(idx.begin(), idx.end());
-    auto chain_of = [&](unsigned id) { auto it = std::lower_bound(idx.begin(), idx.end(), std::make_pair(id, -1)); return it != idx.end() && it->first == id ? it->second : -1; };
-    int reach = 1;
-    for (int k = 0; k < nv; ++k)
-        for (int q = 0; q < views[k].N; ++q) { const int j = views[k].local2global ? chain_of(views[k].local2global[q]) : -1; if (j >= 0) reach = std::max(reach, std::abs(j - k)); }
+    const ScheduleIndex index(views, nv);
+    const int reach = std::max(1, index.neighbour_reach());
     std::fill(keep, keep + nv, (unsigned char)0);
     for (int k = std::max(0, own_begin - 2 * reach); k < std::min(nv, own_end + 2 * reach); ++k) keep[k] = 1;
     for (int k = 0; k < nv; ++k) {
@@ -1230,7 +1218,7 @@ int l3d_partition_keep_views(const l3d_chain_view* views, int nv, int own_begin,
         for (int q = 0; q < views[k].n_sources; ++q) {
             const int si = views[k].source_index[q];                            // ... its sources, whose lists hold the records that point at it ...
             if (si >= 0 && si < nv) keep[si] = 1;
-            const int av = chain_of((unsigned)views[k].source_cam[q]);          // ... and the view its LOCAL camera number names (line3D.cc:861-865)
+            const int av = index.find((unsigned)views[k].source_cam[q]);        // ... and the view its LOCAL camera number names (line3D.cc:861-865)
             if (av >= 0) keep[av] = 1;
         }
     }

@@ -1,4 +1,4 @@
-// l3d_ctx.hpp -- the context behind the C ABI (shared by l3d_capi.hip and l3d_chain.hip): device arenas,
+// l3d_ctx.hpp -- the context behind the C ABI (shared by l3d_capi.hip, l3d_chain.hip and l3d_chain_partition.hip): device arenas,
 // pinned staging, per-kernel HIP-event profiling.
 #pragma once
 

@@ -1,5 +1,5 @@
 // l3d_products.hpp -- what Line3D::performMatching leaves behind (line3D.cc:834-884), kept on the device: shared by the resident
-// chain (l3d_chain.hip), the builder (l3d_products.hip) and the affinity fill on resident tables (l3d_affinity.hip).
+// chain (l3d_chain.hip) and its partitions (l3d_chain_partition.hip), the builder (l3d_products.hip) and the affinity fill on resident tables (l3d_affinity.hip).
 #pragma once
 
 #include "l3d_ctx.hpp"

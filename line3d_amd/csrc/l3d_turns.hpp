@@ -62,7 +62,7 @@ struct TurnReport {
     std::vector<unsigned char> held;
 };
 // One visit of turn `rank` of `world`: chain piece, hand-over out, quirk store, and -- build_share -- this rank's share of the products as
-// l3d_match_chain_partition leaves it (ProductsPart rank / world).  No collective.  L3D_ERR_UNSUPPORTED: a scene turn_handover_schedule refuses.
+// l3d_match_chain_partition leaves it (ProductsPart rank / world), by the same code (l3d_chain_partition.hip).  No collective.  L3D_ERR_UNSUPPORTED: a scene turn_handover_schedule refuses.
 int match_chain_turn(l3d_ctx* c, const l3d_chain_view* views, int n_views, const l3d_dense_map* map, l3d_chain_summary* summary, int rank, int world, int window,
                      const TurnHandover* in, TurnHandover* out, TurnStore* store, bool build_share, TurnReport* report);
 }  // namespace l3d

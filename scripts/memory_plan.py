@@ -157,7 +157,7 @@ def plan_turns(V, S, N, W, kept_ratio, handover=False):
         reach = N // 2
         package = 2 * reach * (info["kept_view"] * 32 + S * 12)
         out.append(("others", "hand-over packages of the node object: the tail for the successor and the one a deferred turn keeps for its second visit (2 x reach = %d views of records, best pairs and positions each; assumes reach = N / 2 and one deferred turn: blocks longer than 4 x reach)" % (2 * reach),
-                    2 * package, "l3d_chain.hip:match_chain_turn (TurnHandover), line3d_host.cpp:node_compute_turns_handover"))
+                    2 * package, "l3d_chain_partition.hip:match_chain_turn (TurnHandover), line3d_host.cpp:node_compute_turns_handover"))
     for phase, name, b, where in rows:
         released = name.startswith("kept arena") or name.startswith("side words") or name.startswith("camera tables")
         out.append(("turn" if phase == "all" and released else phase, name, b, where))

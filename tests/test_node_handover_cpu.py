@@ -172,7 +172,7 @@ def test_plan_refuses_what_the_partition_refuses():
         turns, info = plan(lib, _alternating(n_early), 4)
         assert info["supported"] == supported, (n_early, info)
         assert [t["deferred"] for t in turns] == [0] * 4       # (every source sits right in front of its early return: held by whoever holds that)
-    # a view a turn would ingest BOTH as the sliver of a source and as a named view (l3d_chain.hip: the alias-and-source case of the partition): 40 views
+    # a view a turn would ingest BOTH as the sliver of a source and as a named view (l3d_chain_partition.hip: the alias-and-source case of the partition): 40 views
     # in 2 turns, view 12 returns early with view 7 as its source under the local camera number 7 -- which, read as a view id, names view 7 again.
     # Turn 1 holds the views from 10 on (check = 2 x reach = 10): it holds 12, not 7, and would need 7's sliver and 7's best matches in one list
     v = [dict(id=k, l2g=np.array([k + 1], np.uint32), n_tbm=1, src_cam=np.array([], np.int32), src_idx=np.array([], np.int32)) for k in range(40)]
