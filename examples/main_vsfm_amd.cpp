@@ -1,11 +1,12 @@
 // main_vsfm_amd.cpp -- the flow of the reference's VisualSfM driver (main_vsfm.cpp:34-329) over this library, with the
-// segment caches of an earlier Line3D run standing in for the images, or with the images as binary PPM / PGM files (no OpenCV, no tclap,
-// no boost):
+// segment caches of an earlier Line3D run standing in for the images, or with the images as binary PPM / PGM files or baseline JPEG files (no
+// OpenCV, no tclap, no boost):
 //
 //   main_vsfm_amd <scene.nvm | bundle.rd.out> <data directory> [neighbors=10] [diffusion=0] [output folder=<data directory>] [image folder]
 //
-// With an image folder, camera i's image is "<image folder>/<camera name, extension replaced>.ppm" or ".pgm" (binary P6 / P5, maxval 255; convert
-// JPEG / PNG beforehand).  The camera name is the NVM file's image name; for a bundler file it is the camera index as %08d
+// With an image folder, camera i's image is "<image folder>/<camera name, extension replaced>.ppm" or ".pgm" (binary P6 / P5, maxval 255), or the
+// camera's own file "<image folder>/<camera name>" when it ends in .jpg / .jpeg (baseline JPEG, decoded on the device: addImageJPEGDistorted;
+// convert PNG and progressive JPEG beforehand).  The camera name is the NVM file's image name; for a bundler file it is the camera index as %08d
 // ("00000000.ppm", ...: the drivers' visualize/%08d.jpg, main_bundler.cpp:208-236): it is undistorted with the scene file's coefficients and its segments are detected on the device
 // (addImageDistorted: main_vsfm.cpp:243-273), and the data directory receives the segment caches.  Without one:
 // For every camera of the NVM file the data directory ("<image folder>/L3D_data" of the reference, main_vsfm.cpp:108-116)
@@ -17,6 +18,7 @@
 // Build:  g++ -std=c++17 -Iinclude examples/main_vsfm_amd.cpp -Lline3d_amd -lline3d_amd -Wl,-rpath,$PWD/line3d_amd -o main_vsfm_amd
 #include <dirent.h>
 
+#include <cctype>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -93,6 +95,22 @@ bool load_camera_image(const std::string& folder, const std::string& name, PnmIm
     const std::string stem = folder + "/" + (dot != std::string::npos && (slash == std::string::npos || dot > slash) ? name.substr(0, dot) : name);
     return read_pnm(stem + ".ppm", img) || read_pnm(stem + ".pgm", img);
 }
+// "<folder>/<name>" itself when the name ends in .jpg / .jpeg (any case): the file's bytes
+bool load_camera_jpeg(const std::string& folder, const std::string& name, std::vector<unsigned char>& bytes)
+{
+    const size_t dot = name.find_last_of('.');
+    if (dot == std::string::npos) return false;
+    std::string ext = name.substr(dot + 1);
+    for (char& c : ext) c = (char)tolower((unsigned char)c);
+    if (ext != "jpg" && ext != "jpeg") return false;
+    FILE* f = fopen((folder + "/" + name).c_str(), "rb");
+    if (!f) return false;
+    bytes.clear();
+    unsigned char buf[65536];
+    for (size_t got; (got = fread(buf, 1, sizeof(buf), f)) > 0;) bytes.insert(bytes.end(), buf, buf + got);
+    fclose(f);
+    return !bytes.empty();
+}
 // K, R, t of the facade's matrix-typed calls over plain arrays
 struct Mat3 { const double* p; double operator()(int i, int j) const { return p[i * 3 + j]; } };
 struct Vec3 { const double* p; double operator()(int i) const { return p[i]; } };
@@ -130,8 +148,19 @@ int main(int argc, char** argv)
         std::list<unsigned int> wps(ids.begin(), ids.end());
         if (!image_dir.empty()) {                   // main_vsfm.cpp:229-273: load, K from the image size, undistort, addImage
             PnmImage img;
-            if (!load_camera_image(image_dir, l3d_sfm_camera_name(scene, i), img)) { fprintf(stderr, "camera %d: no binary .ppm / .pgm image (maxval 255) for %s in %s\n", i, l3d_sfm_camera_name(scene, i), image_dir.c_str()); continue; }
             double K[9], k[2] = { 0, 0 };
+            if (!load_camera_image(image_dir, l3d_sfm_camera_name(scene, i), img)) {
+                std::vector<unsigned char> file;
+                unsigned jw = 0, jh = 0, jch = 0;
+                if (!load_camera_jpeg(image_dir, l3d_sfm_camera_name(scene, i), file)) { fprintf(stderr, "camera %d: no binary .ppm / .pgm image (maxval 255) and no .jpg / .jpeg file for %s in %s\n", i, l3d_sfm_camera_name(scene, i), image_dir.c_str()); continue; }
+                if (!L3D::Line3D::jpegSize(file.data(), file.size(), jw, jh, jch)) { fprintf(stderr, "camera %d: %s\n", i, l3d_jpeg_last_error()); continue; }
+                l3d_sfm_intrinsics(focal, jw, jh, K);
+                l3d_sfm_camera_cv_distortion(scene, i, k);
+                const unsigned before = line3D.numCameras();
+                line3D.addImageJPEGDistorted((unsigned)i, file.data(), file.size(), Mat3{ K }, Mat3{ R }, Vec3{ t }, k[0], k[1], wps);
+                added += (int)(line3D.numCameras() - before);
+                continue;
+            }
             l3d_sfm_intrinsics(focal, (unsigned)img.cols, (unsigned)img.rows, K);
             l3d_sfm_camera_cv_distortion(scene, i, k);
             const unsigned before = line3D.numCameras();

@@ -237,6 +237,54 @@ public:
         for (int i = 0; i < h; ++i) memcpy(px + (size_t)i * step, tmp.data() + (size_t)i * row, row);
         return true;
     }
+    // The drivers' cv::imread in front of that block, for baseline JPEG files: `bytes` are the file's contents; it is decoded on the device
+    // (include/line3d_amd.h: byte-identical to libjpeg's default decoder, three channels B, G, R as cv::imread gives them) straight into the
+    // detector, undistorted first in the ...Distorted forms.  The cache rules are addImage's; a cache that is present and wanted is loaded
+    // without decoding the file.  A file the decoder refuses (progressive, CMYK, corrupt, ...) is reported and adds no view.
+    template <class M3, class V3, class = decltype(std::declval<const M3&>()(0, 0)), class = decltype(std::declval<const V3&>()(0))>
+    void addImageJPEG(const unsigned int imageID, const unsigned char* bytes, const size_t n, const M3& K, const M3& R, const V3& t,
+                      std::list<unsigned int>& worldpointIDs, const int maxImgWidth = 1920, const bool loadAndStoreSegments = true)
+    {
+        add_jpeg(imageID, bytes, n, K, R, t, nullptr, &worldpointIDs, nullptr, maxImgWidth, loadAndStoreSegments);
+    }
+    template <class M3, class V3, class = decltype(std::declval<const M3&>()(0, 0)), class = decltype(std::declval<const V3&>()(0))>
+    void addImageJPEGDistorted(const unsigned int imageID, const unsigned char* bytes, const size_t n, const M3& K, const M3& R, const V3& t, const double k1,
+                               const double k2, std::list<unsigned int>& worldpointIDs, const int maxImgWidth = 1920, const bool loadAndStoreSegments = true)
+    {
+        const double dist[2] = { k1, k2 };
+        add_jpeg(imageID, bytes, n, K, R, t, dist, &worldpointIDs, nullptr, maxImgWidth, loadAndStoreSegments);
+    }
+    template <class M3, class V3, class = decltype(std::declval<const M3&>()(0, 0)), class = decltype(std::declval<const V3&>()(0))>
+    void addImage_fixed_simJPEG(const unsigned int imageID, const unsigned char* bytes, const size_t n, const M3& K, const M3& R, const V3& t,
+                                std::map<unsigned int, float>& viewSimilarity, const int maxImgWidth = 1920, const bool loadAndStoreSegments = true)
+    {
+        add_jpeg(imageID, bytes, n, K, R, t, nullptr, nullptr, &viewSimilarity, maxImgWidth, loadAndStoreSegments);
+    }
+    template <class M3, class V3, class = decltype(std::declval<const M3&>()(0, 0)), class = decltype(std::declval<const V3&>()(0))>
+    void addImage_fixed_simJPEGDistorted(const unsigned int imageID, const unsigned char* bytes, const size_t n, const M3& K, const M3& R, const V3& t,
+                                         const double k1, const double k2, std::map<unsigned int, float>& viewSimilarity, const int maxImgWidth = 1920,
+                                         const bool loadAndStoreSegments = true)
+    {
+        const double dist[2] = { k1, k2 };
+        add_jpeg(imageID, bytes, n, K, R, t, dist, nullptr, &viewSimilarity, maxImgWidth, loadAndStoreSegments);
+    }
+    // the size and channel count (1: grey, 3: B, G, R) a JPEG file decodes to, from its headers alone -- no device; false: not a file the decoder takes
+    static bool jpegSize(const unsigned char* bytes, const size_t n, unsigned int& width, unsigned int& height, unsigned int& channels)
+    {
+        int w = 0, h = 0, ch = 0;
+        if (l3d_jpeg_info(bytes, n, &w, &h, &ch) != L3D_OK) return false;
+        width = (unsigned int)w; height = (unsigned int)h; channels = (unsigned int)ch;
+        return true;
+    }
+    // the decoded image: height rows of width x channels bytes into `pixels` (resized), B, G, R for three channels
+    bool decodeJPEG(const unsigned char* bytes, const size_t n, std::vector<unsigned char>& pixels, unsigned int& width, unsigned int& height, unsigned int& channels)
+    {
+        if (!jpegSize(bytes, n, width, height, channels)) { std::cerr << prefix_ << l3d_jpeg_last_error() << std::endl; return false; }
+        pixels.assign((size_t)width * height * channels, 0);
+        const int rc = l3d_line3d_decode_jpeg(h_, bytes, n, pixels.data(), (size_t)width * channels);
+        report(rc);
+        return rc == L3D_OK;
+    }
     // line3D.h:82
     void compute3Dmodel(bool perform_diffusion = false) { report(l3d_line3d_compute3Dmodel(h_, perform_diffusion ? 1 : 0)); }
     // line3D.h:85
@@ -333,6 +381,23 @@ private:
         const unsigned int w = image.cols > 0 ? (unsigned int)image.cols : 0u, h = image.rows > 0 ? (unsigned int)image.rows : 0u;
         if (sims) return l3d_line3d_add_image_fixed_sim_ex(h_, imageID, w, h, nullptr, 0, k, r, tt, ids, sims, n, data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0);
         return l3d_line3d_add_image_ex(h_, imageID, w, h, nullptr, 0, k, r, tt, ids, n, data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0);
+    }
+    template <class M3, class V3>
+    void add_jpeg(unsigned int imageID, const unsigned char* bytes, size_t n, const M3& K, const M3& R, const V3& t, const double* dist,
+                  std::list<unsigned int>* worldpointIDs, std::map<unsigned int, float>* viewSimilarity, int maxImgWidth, bool loadAndStoreSegments)
+    {
+        double k[9], r[9], tt[3];
+        flatten(K, R, t, k, r, tt);
+        if (worldpointIDs) {
+            std::vector<uint32_t> wps(worldpointIDs->begin(), worldpointIDs->end());
+            report(l3d_line3d_add_image_jpeg(h_, imageID, bytes, n, k, r, tt, dist, wps.data(), (int)wps.size(), data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0));
+            return;
+        }
+        std::vector<uint32_t> ids;
+        std::vector<float> sims;
+        for (auto& kv : *viewSimilarity) { ids.push_back(kv.first); sims.push_back(kv.second); }
+        report(l3d_line3d_add_image_jpeg_fixed_sim(h_, imageID, bytes, n, k, r, tt, dist, ids.data(), sims.data(), (int)ids.size(), data_directory_.c_str(), maxImgWidth,
+                                                   loadAndStoreSegments ? 1 : 0));
     }
     void report(int rc) { if (rc != L3D_OK) std::cerr << prefix_ << l3d_line3d_last_error(h_) << std::endl; }
     l3d_line3d* h_;

@@ -661,8 +661,8 @@ int l3d_line3d_stats(const l3d_line3d* h, double* stats12);
 /* =================================================================================================
  * SfM front ends of the reference's drivers: VisualSfM NVM (main_vsfm.cpp:121-223) and bundler
  * bundle.rd.out (main_bundler.cpp:110-204), reduced to what feeds Line3D::addImage -- focal length, R, t, distortion
- * coefficients, observed world point ids per camera.  Image decoding stays outside (undistortion and line segment
- * detection: l3d_undistort_image, l3d_detect_segments below).
+ * coefficients, observed world point ids per camera.  The images themselves: baseline JPEG files are decoded, undistorted and their line segments
+ * detected on the device (l3d_line3d_add_image_jpeg, l3d_decode_jpeg, l3d_undistort_image, l3d_detect_segments below).
  * A failed read still returns a scene object carrying the message (l3d_sfm_last_error); free it with l3d_sfm_free.
  * ================================================================================================= */
 typedef struct l3d_sfm_scene l3d_sfm_scene;
@@ -743,7 +743,7 @@ int l3d_line3d_add_image_fixed_sim_ex(l3d_line3d* h, uint32_t image_id, unsigned
  *   selection   length > min_length, length descending (ties: smallest pixel index of the region), at most max_segments
  * Out (callee-allocated, l3d_free): 4 floats (x1, y1, x2, y2) per segment; *n = 0 when nothing is found.
  * Images below 8x8, channels other than 1 or 3, a stride below width x channels: L3D_ERR_INVALID.
- * Still outside the library: image decoding (JPEG / PNG), the tclap command lines of the drivers.
+ * Still outside the library: PNG and progressive JPEG decoding (baseline JPEG: l3d_decode_jpeg below), the tclap command lines of the drivers.
  * ================================================================================================= */
 int l3d_detect_segments(l3d_ctx* ctx, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, int new_width, int new_height,
                         float min_length, int max_segments, float** segments, int* n);
@@ -797,6 +797,78 @@ int l3d_line3d_add_image_pixels_fixed_sim_distorted(l3d_line3d* h, uint32_t imag
 int l3d_line3d_undistort_image(l3d_line3d* h, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, const double* K, double k1, double k2,
                                unsigned char* out, size_t out_row_stride);
 
+
+/* =================================================================================================
+ * Baseline JPEG input (line3d_amd/csrc/l3d_jpeg.cpp, l3d_jpeg_device.hip): the cv::imread in front of the drivers' undistort -> addImage block
+ * (main_vsfm.cpp:229-273, main_bundler.cpp:242-287).  The host parses the file and decodes the entropy-coded data; dequantisation, inverse DCT,
+ * chroma upsampling and colour conversion run on the device and write straight into the detector's pixel buffer.  The result is byte-identical
+ * to the IJG / libjpeg-turbo decoder at its default settings (JDCT_ISLOW, fancy upsampling) -- the decoder behind cv::imread.
+ * All arithmetic is in exact integers; >> is an arithmetic shift (a floor).
+ *
+ * Accepted   SOF0 and SOF1 with Huffman coding, 8-bit samples.  1 component: grey, 1 channel out.  3 components with sampling 1x1 for all, or
+ *            luma 2x1 / 2x2 with chroma 1x1 (4:4:4, 4:2:2, 4:2:0).  DQT with 8- or 16-bit entries; DHT may be redefined between segments;
+ *            DRI / RSTn are honoured (at each restart interval the decoder byte-aligns, checks RST m mod 8 and resets the DC predictors);
+ *            fill bytes FF FF before markers; APPn / COM are skipped; anything after EOI is ignored and a missing EOI after the last MCU is
+ *            accepted.  EXIF orientation is ignored: the SfM poses refer to the stored pixel grid.
+ * Colour     libjpeg's rule: a JFIF APP0 means YCbCr; otherwise an Adobe APP14 decides by its transform byte (0: the components are R, G, B;
+ *            1: YCbCr); otherwise component ids 'R', 'G', 'B' mean RGB; otherwise YCbCr.
+ * Output     three components come out B, G, R INTERLEAVED -- what cv::imread hands the reference, whose CV_RGB2GRAY on that buffer
+ *            (line3D.cc:1814) puts the weight 299 on blue; the grey formula of l3d_detect_segments on c0, c1, c2 reproduces exactly that for
+ *            this buffer.  (An RGB buffer from elsewhere, e.g. a PPM, gets 299 on red, as before.)
+ * Refused    L3D_ERR_UNSUPPORTED, the message naming the cause: progressive (SOF2), lossless, arithmetic coding, 12-bit; 2 or 4 components
+ *            (CMYK / YCCK); any other sampling (1x2 / 4:4:0 / 4:1:1 included); more than one scan for a baseline frame.  Also a frame of more
+ *            than 2^24 8x8 blocks over all components (about a gigapixel): decided from the headers, before anything is allocated.
+ *            L3D_ERR_INVALID: truncated or corrupt data, a Huffman code not in the table, a coefficient index past 63, a DC predictor leaving
+ *            the int16 range, a missing table, zero dimensions.  None of these reads or writes outside a buffer.
+ * Coefficients  quantised, int16, de-zigzagged by the host into natural (row-major) order; per component, per block row, per block column,
+ *            over whole MCUs.
+ * Inverse DCT   c[k] = coef[k] q[k], then IJG's jidctint in 64-bit integers, constants at 13 bits: FIX(0.298631336) = 2446, (0.390180644) 3196,
+ *            (0.541196100) 4433, (0.765366865) 6270, (0.899976223) 7373, (1.175875602) 9633, (1.501321110) 12299, (1.847759065) 15137,
+ *            (1.961570560) 16069, (2.053119869) 16819, (2.562915447) 20995, (3.072711026) 25172.  A 1-D pass on v[0..7]:
+ *              z1 = (v2 + v6) 4433; t2 = z1 - v6 15137; t3 = z1 + v2 6270; t0 = (v0 + v4) << 13; t1 = (v0 - v4) << 13;
+ *              t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+ *              a0 = v7, a1 = v5, a2 = v3, a3 = v1; z1 = a0 + a3, z2 = a1 + a2, z3 = a0 + a2, z4 = a1 + a3; z5 = (z3 + z4) 9633;
+ *              a0 *= 2446; a1 *= 16819; a2 *= 25172; a3 *= 12299; z1 *= -7373; z2 *= -20995; z3 = z3 (-16069) + z5; z4 = z4 (-3196) + z5;
+ *              a0 += z1 + z3; a1 += z2 + z4; a2 += z2 + z3; a3 += z1 + z4;
+ *              out: t10 + a3, t11 + a2, t12 + a1, t13 + a0, t13 - a0, t12 - a1, t11 - a2, t10 - a3
+ *            Pass 1 over the columns, each output (x + 1024) >> 11; pass 2 over the rows of that, each output
+ *            clamp(((x + 131072) >> 18) + 128, 0, 255).  (libjpeg's range-limit table wraps where this clamps, but only for values no accepted
+ *            stream produces: not part of the contract.)
+ * Upsampling    the component's real size is cw = ceil(W h / hmax), chh = ceil(H v / vmax); edge samples replicate at that size, not at the
+ *            padded MCU size.  2x1: out[2i] = (3 s[i] + s[i-1] + 1) >> 2, out[2i+1] = (3 s[i] + s[i+1] + 2) >> 2.  2x2: for output row 2r + k the
+ *            neighbour row is nb = r - 1 (k = 0) or r + 1 (k = 1), replicated at top and bottom; t[i] = 3 s[r][i] + s[nb][i];
+ *            out[2i] = (3 t[i] + t[i-1] + 8) >> 4, out[2i+1] = (3 t[i] + t[i+1] + 7) >> 4, t replicated at both row ends.
+ * YCbCr -> RGB  cb' = cb - 128, cr' = cr - 128: R = y + ((91881 cr' + 32768) >> 16), B = y + ((116130 cb' + 32768) >> 16),
+ *            G = y + ((-22554 cb' - 46802 cr' + 32768) >> 16), each clamped to 0..255; the output is cropped to W x H.
+ *
+ *   l3d_jpeg_info              headers only, no context and no device: width, height, channels (1 or 3) of the decoded image; the message of a
+ *                              refusal: l3d_jpeg_last_error (of the calling thread's last context-free call)
+ *   l3d_decode_jpeg            host bytes in, host pixels out (height rows of width x channels bytes, `out_row_stride` apart), any size from 1x1
+ *   l3d_detect_segments_jpeg   l3d_detect_segments on the decoded image, which stays on the device; camera: NULL, or (fx, fy, cx, cy, k1, k2) of
+ *                              l3d_detect_segments_distorted.  Images below 8x8 are refused as l3d_detect_segments refuses them
+ *   l3d_line3d_add_image_jpeg, l3d_line3d_add_image_jpeg_fixed_sim
+ *                              l3d_line3d_add_image_pixels_distorted / ..._fixed_sim_distorted with the file in place of the pixels.  dist NULL, or
+ *                              both coefficients within 1e-12: no undistortion.  The cache rules are unchanged; the size for the cache name and
+ *                              the max_img_width rule comes from the headers, and a cache that is present and wanted is loaded WITHOUT
+ *                              entropy-decoding the file.  On a node object rank 0's device does the work once
+ *   l3d_line3d_decode_jpeg     l3d_decode_jpeg with the object's device
+ *   l3d_test_jpeg_coefficients (tests) host only: the quantised blocks as above (callee-allocated, l3d_free), qt[3][64] per component in natural
+ *                              order, layout[27] = width, height, components, hmax, vmax, MCUs per row, MCU rows, restart interval, rgb, then per
+ *                              component h, v, blocks per row, block rows, cw, chh
+ * ================================================================================================= */
+int l3d_jpeg_info(const unsigned char* bytes, size_t n, int* width, int* height, int* channels);
+const char* l3d_jpeg_last_error(void);
+int l3d_decode_jpeg(l3d_ctx* ctx, const unsigned char* bytes, size_t n, unsigned char* out, size_t out_row_stride);
+int l3d_detect_segments_jpeg(l3d_ctx* ctx, const unsigned char* bytes, size_t n, int new_width, int new_height, float min_length, int max_segments,
+                             const double* camera, float** segments, int* n_segments);
+int l3d_line3d_add_image_jpeg(l3d_line3d* h, uint32_t image_id, const unsigned char* bytes, size_t n, const double* K, const double* R, const double* t,
+                              const double dist[2], const uint32_t* worldpoint_ids, int n_worldpoints, const char* data_directory, int max_img_width,
+                              int load_and_store);
+int l3d_line3d_add_image_jpeg_fixed_sim(l3d_line3d* h, uint32_t image_id, const unsigned char* bytes, size_t n, const double* K, const double* R, const double* t,
+                                        const double dist[2], const uint32_t* sim_ids, const float* sims, int n_sims, const char* data_directory,
+                                        int max_img_width, int load_and_store);
+int l3d_line3d_decode_jpeg(l3d_line3d* h, const unsigned char* bytes, size_t n, unsigned char* out, size_t out_row_stride);
+int l3d_test_jpeg_coefficients(const unsigned char* bytes, size_t n, int16_t** coef, size_t* n_blocks, uint16_t* qt, int32_t* layout);
 
 /* The detector's stages on their own, exported for tests (tests/test_gpu_detect_stages.py): the same kernels with the same launch shapes
  * as l3d_detect_segments, results copied to caller-allocated arrays.  (N, M) = (ceil(0.8 new_width), ceil(0.8 new_height)) is the scaled image.

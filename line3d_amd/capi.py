@@ -88,6 +88,49 @@ def image_arguments(img):
     return ptr, int(a.shape[1]), int(a.shape[0]), int(ch), int(a.strides[0])
 
 
+def _bytes_arguments(data):
+    """bytes-like (or a uint8 array) -> (pointer, length); the buffer is kept alive on the pointer"""
+    a = np.frombuffer(bytes(data) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8).tobytes(), dtype=np.uint8)
+    ptr = C.c_void_p(a.ctypes.data if len(a) else None)
+    ptr._keep = a
+    return ptr, C.c_size_t(len(a))
+
+
+def jpeg_info(data):
+    """l3d_jpeg_info: (width, height, channels) of a baseline JPEG file from its headers alone -- no context, no device.  A file the decoder
+    refuses raises L3DError carrying the status in .code (5: unsupported, 1: invalid) and the cause in its text."""
+    lib = load_library()
+    lib.l3d_jpeg_last_error.restype = C.c_char_p
+    ptr, n = _bytes_arguments(data)
+    w, h, ch = C.c_int(0), C.c_int(0), C.c_int(0)
+    rc = lib.l3d_jpeg_info(ptr, n, C.byref(w), C.byref(h), C.byref(ch))
+    if rc != 0:
+        e = L3DError("line3d_amd error %d: %s" % (rc, lib.l3d_jpeg_last_error().decode()))
+        e.code = rc
+        raise e
+    return w.value, h.value, ch.value
+
+
+def test_jpeg_coefficients(data):
+    """l3d_test_jpeg_coefficients (host only): (coef int16 (n_blocks, 64), qt uint16 (3, 64), layout int32 (27,)) as include/line3d_amd.h lists them"""
+    lib = load_library()
+    lib.l3d_jpeg_last_error.restype = C.c_char_p
+    ptr, n = _bytes_arguments(data)
+    coef, nb = C.POINTER(C.c_int16)(), C.c_size_t(0)
+    qt, layout = np.zeros((3, 64), np.uint16), np.zeros(27, np.int32)
+    rc = lib.l3d_test_jpeg_coefficients(ptr, n, C.byref(coef), C.byref(nb), _p(qt), _p(layout))
+    if rc != 0:
+        e = L3DError("line3d_amd error %d: %s" % (rc, lib.l3d_jpeg_last_error().decode()))
+        e.code = rc
+        raise e
+    out = np.ctypeslib.as_array(coef, (nb.value, 64)).copy()
+    lib.l3d_free(coef)
+    return out, qt, layout
+
+
+test_jpeg_coefficients.__test__ = False
+
+
 class AffinityInput(C.Structure):
     """l3d_affinity_input (include/line3d_amd.h)"""
     _fields_ = [("n_views", C.c_int32), ("seg_base", C.c_void_p), ("view_hyp_begin", C.c_void_p), ("n_hyp", C.c_int32),
@@ -121,7 +164,9 @@ class Context:
 
     def _chk(self, rc):
         if rc != 0:
-            raise L3DError("line3d_amd error %d: %s" % (rc, self.lib.l3d_last_error(self.h).decode()))
+            e = L3DError("line3d_amd error %d: %s" % (rc, self.lib.l3d_last_error(self.h).decode()))
+            e.code = rc
+            raise e
 
     # -- measurement --------------------------------------------------------------------------
     def profile_enable(self, on=True):
@@ -212,6 +257,35 @@ class Context:
             self._chk(self.lib.l3d_detect_segments(self.h, pix, C.c_int(w), C.c_int(h), C.c_int(ch), C.c_size_t(stride), C.c_int(nw), C.c_int(nh),
                                                    C.c_float(min_length), C.c_int(int(max_segments)), C.byref(out), C.byref(n)))
         segs = np.ctypeslib.as_array(out, (n.value, 4)).copy() if n.value else np.zeros((0, 4), np.float32)
+        self.lib.l3d_free(out)
+        return segs
+
+    # -- baseline JPEG input (l3d_jpeg.cpp, l3d_jpeg_device.hip) ------------------------------------
+    def decode_jpeg(self, data):
+        """l3d_decode_jpeg: the bytes of a baseline JPEG file -> uint8 H x W (grey) or H x W x 3 (B, G, R, as cv::imread gives them),
+        byte-identical to libjpeg's default decoder."""
+        w, h, ch = jpeg_info(data)
+        ptr, n = _bytes_arguments(data)
+        out = np.zeros((h, w) if ch == 1 else (h, w, ch), np.uint8)
+        self._chk(self.lib.l3d_decode_jpeg(self.h, ptr, n, _p(out), C.c_size_t(w * ch)))
+        return out
+
+    def detect_segments_jpeg(self, data, new_size=None, min_length=None, max_segments=3000, camera=None):
+        """l3d_detect_segments_jpeg: detect_segments on the image of a baseline JPEG file, decoded on the device (arguments as detect_segments)"""
+        w, h, _ = jpeg_info(data)
+        ptr, n = _bytes_arguments(data)
+        nw, nh = (w, h) if new_size is None else (int(new_size[0]), int(new_size[1]))
+        if min_length is None:
+            min_length = float(np.float32(0.005) * np.sqrt(np.float32(h * h + w * w)))
+        cam = None
+        if camera is not None:
+            if len(camera) != 6:
+                raise ValueError("camera must be (fx, fy, cx, cy, k1, k2)")
+            cam = (C.c_double * 6)(*[float(v) for v in camera])
+        out, cnt = C.POINTER(C.c_float)(), C.c_int(0)
+        self._chk(self.lib.l3d_detect_segments_jpeg(self.h, ptr, n, C.c_int(nw), C.c_int(nh), C.c_float(min_length), C.c_int(int(max_segments)), cam,
+                                                    C.byref(out), C.byref(cnt)))
+        segs = np.ctypeslib.as_array(out, (cnt.value, 4)).copy() if cnt.value else np.zeros((0, 4), np.float32)
         self.lib.l3d_free(out)
         return segs
 

@@ -139,11 +139,16 @@ struct FillPart { int h0 = 0, h1 = 0; unsigned long long pos_base = 0; const int
 struct DetectBufs {
     // undist: the undistorted image (k_det_undistort), reserved only when an image comes with distortion coefficients
     DevBuf pixels, undist, grey, aux, img, mod, ang, bucket, active, parent, size, count, keys, keys2, vals, vals2, flag, pos, start, tmp, cand, ckeys, ckeys2, cvals, cvals2, out, ktab, scal;
+    // JPEG input (l3d_jpeg_device.hip), reserved only when a JPEG is decoded: the quantisation tables and the quantised coefficients as the host's entropy
+    // decoder wrote them into the pinned `jstage`, and the uint8 component planes over whole MCUs
+    DevBuf jcoef, jplanes;
+    PinBuf jstage;
     int tab_w = 0, tab_h = 0;       // the image size the Gaussian sampler's tables in `ktab` were made for
     void release()
     {
         DevBuf* b[] = { &pixels, &undist, &grey, &aux, &img, &mod, &ang, &bucket, &active, &parent, &size, &count, &keys, &keys2, &vals, &vals2, &flag, &pos, &start, &tmp, &cand, &ckeys, &ckeys2, &cvals, &cvals2, &out, &ktab, &scal };
         for (DevBuf* x : b) x->release();
+        jcoef.release(); jplanes.release(); jstage.release();
         tab_w = tab_h = 0;
     }
 };

@@ -19,6 +19,7 @@
 #include <cmath>
 
 #include "l3d_ctx.hpp"
+#include "l3d_jpeg.hpp"
 #include "l3d_sort.hpp"
 
 namespace l3d {
@@ -583,7 +584,8 @@ void launch_undistort(l3d_ctx* c, int w, int h, int ch, const DetCamera& cam)
     hipLaunchKernelGGL(k_det_undistort, dim3((w + kUndBx - 1) / kUndBx, (h + kUndBy - 1) / kUndBy), dim3(kUndBx, kUndBy), 0, c->stream, d.pixels.as<unsigned char>(), w, h, ch, cam, d.undist.as<unsigned char>());
 }
 
-// ---- pixel stage: upload, undistortion (cam: null or inactive = none), rescale + grey, the two sampler passes, gradient; leaves the scalars zeroed
+// ---- pixel stage: upload (pixels null: the image is in d.pixels already -- a decoded JPEG), undistortion (cam: null or inactive = none), rescale + grey,
+// the two sampler passes, gradient; leaves the scalars zeroed
 int det_pixel_stage(l3d_ctx* c, const DetPlan& p, const unsigned char* pixels, size_t stride, const DetCamera* cam = nullptr)
 {
     hipStream_t st = c->stream;
@@ -603,7 +605,7 @@ int det_pixel_stage(l3d_ctx* c, const DetPlan& p, const unsigned char* pixels, s
     }
     const double* kw = d.ktab.as<double>();
     const int* kc = reinterpret_cast<const int*>(static_cast<const char*>(d.ktab.p) + ((size_t)N + M) * kTaps * 8);
-    HIPCHK(c, hipMemcpy2DAsync(d.pixels.p, (size_t)w * ch, pixels, stride, (size_t)w * ch, (size_t)h, hipMemcpyHostToDevice, st));
+    if (pixels) HIPCHK(c, hipMemcpy2DAsync(d.pixels.p, (size_t)w * ch, pixels, stride, (size_t)w * ch, (size_t)h, hipMemcpyHostToDevice, st));
     const dim3 b256(256);
     const unsigned char* image = d.pixels.as<unsigned char>();          // whichever buffer holds the image k_det_grey reads
     if (cam) { launch_undistort(c, w, h, ch, *cam); image = d.undist.as<unsigned char>(); }
@@ -666,9 +668,10 @@ __global__ void k_det_nfa_test(const int* __restrict__ n, const int* __restrict_
     if (i < count) out[i] = det_nfa(n[i], k[i], p[i], logNT);
 }
 
-int plan_image(l3d_ctx* c, DetPlan& p, const unsigned char* pixels, int w, int h, int ch, size_t stride, int nw, int nh)
+// have_image: host pixels were given, or the image will be decoded on the device
+int plan_image(l3d_ctx* c, DetPlan& p, bool have_image, int w, int h, int ch, size_t stride, int nw, int nh)
 {
-    if (!pixels || w < 8 || h < 8 || (ch != 1 && ch != 3) || stride < (size_t)w * ch) return fail(c, L3D_ERR_INVALID, "detect_segments: needs an image of at least 8x8 with 1 or 3 channels and a row stride of at least width x channels");
+    if (!have_image || w < 8 || h < 8 || (ch != 1 && ch != 3) || stride < (size_t)w * ch) return fail(c, L3D_ERR_INVALID, "detect_segments: needs an image of at least 8x8 with 1 or 3 channels and a row stride of at least width x channels");
     if (nw <= 0 || nh <= 0) { nw = w; nh = h; }
     if (nw < 8 || nh < 8) return fail(c, L3D_ERR_INVALID, "detect_segments: rescaled size below 8x8");
     const int N = (int)ceil(nw * kScale), M = (int)ceil(nh * kScale);
@@ -681,16 +684,13 @@ int plan_image(l3d_ctx* c, DetPlan& p, const unsigned char* pixels, int w, int h
     return L3D_OK;
 }
 
-}  // namespace
-
-int detect_segments(l3d_ctx* c, const unsigned char* pixels, int w, int h, int ch, size_t stride, int nw, int nh, float min_length, int max_segments,
-                    std::vector<float>& out, const DetCamera* cam)
+// the detector on one image: `pixels` (host), or with jpeg_bytes the file whose parsed headers are `frame`, decoded on the device into d.pixels
+int detect_core(l3d_ctx* c, const unsigned char* pixels, int w, int h, int ch, size_t stride, int nw, int nh, float min_length, int max_segments,
+                std::vector<float>& out, const DetCamera* cam, const unsigned char* jpeg_bytes = nullptr, size_t jpeg_n = 0, const JpegFrame* frame = nullptr)
 {
-    out.clear();
-    if (!c) return L3D_ERR_INVALID;
     if (max_segments < 0) return fail(c, L3D_ERR_INVALID, "detect_segments: negative max_segments");
     DetPlan plan;
-    if (int rc = plan_image(c, plan, pixels, w, h, ch, stride, nw, nh)) return rc;
+    if (int rc = plan_image(c, plan, frame != nullptr || pixels != nullptr, w, h, ch, stride, nw, nh)) return rc;
     bool undist = false;
     if (cam) { if (int rc = check_camera(c, *cam, w, h, &undist)) return rc; }
     if (!undist) cam = nullptr;
@@ -702,7 +702,8 @@ int detect_segments(l3d_ctx* c, const unsigned char* pixels, int w, int h, int c
     const int cand_cap = plan.cand_cap;
     const float up = plan.up;
     const dim3 b256(256);
-    if (int rc = det_pixel_stage(c, plan, pixels, stride, cam)) return rc;
+    if (frame) { if (int rc = jpeg_decode_to_pixels(c, jpeg_bytes, jpeg_n, *frame)) return rc; }
+    if (int rc = det_pixel_stage(c, plan, frame ? nullptr : pixels, stride, cam)) return rc;
 
     // ---- rounds: label, vote, sort, regions
     for (int round = 0; round < kRounds; ++round) {
@@ -727,6 +728,27 @@ int detect_segments(l3d_ctx* c, const unsigned char* pixels, int w, int h, int c
     out.resize((size_t)n_out * 4);
     if (n_out) HIPCHK(c, hipMemcpy(out.data(), d.out.p, (size_t)n_out * 16, hipMemcpyDeviceToHost));
     return L3D_OK;
+}
+}  // namespace
+
+int detect_segments(l3d_ctx* c, const unsigned char* pixels, int w, int h, int ch, size_t stride, int nw, int nh, float min_length, int max_segments,
+                    std::vector<float>& out, const DetCamera* cam)
+{
+    out.clear();
+    if (!c) return L3D_ERR_INVALID;
+    return detect_core(c, pixels, w, h, ch, stride, nw, nh, min_length, max_segments, out, cam);
+}
+
+int detect_segments_jpeg(l3d_ctx* c, const unsigned char* bytes, size_t n, int nw, int nh, float min_length, int max_segments, std::vector<float>& out,
+                         const DetCamera* cam)
+{
+    out.clear();
+    if (!c) return L3D_ERR_INVALID;
+    if (!bytes) return fail(c, L3D_ERR_INVALID, "detect_segments_jpeg: null argument");
+    JpegFrame f;
+    std::string err;
+    if (int rc = jpeg_parse(bytes, n, f, err)) return fail(c, rc, err);
+    return detect_core(c, nullptr, f.width, f.height, f.ncomp, (size_t)f.width * f.ncomp, nw, nh, min_length, max_segments, out, cam, bytes, n, &f);
 }
 
 // host in, host out: upload, k_det_undistort, download (the detector's two image buffers)
@@ -763,6 +785,17 @@ int l3d_undistort_image(l3d_ctx* c, const unsigned char* pixels, int width, int 
     return l3d::undistort_image(c, pixels, width, height, channels, row_stride, l3d::DetCamera{ fx, fy, cx, cy, k1, k2 }, out, out_row_stride);
 }
 
+// the segments as the C ABI hands them out: callee-allocated (l3d_free), 4 floats each
+static int segments_to_c(l3d_ctx* c, const std::vector<float>& out, float** segments, int* n)
+{
+    float* p = static_cast<float*>(malloc(std::max<size_t>(16, out.size() * 4)));
+    if (!p) return l3d::fail(c, L3D_ERR_INVALID, "detect_segments: out of memory");
+    if (!out.empty()) memcpy(p, out.data(), out.size() * 4);
+    *segments = p;
+    *n = (int)(out.size() / 4);
+    return L3D_OK;
+}
+
 static int detect_to_c(l3d_ctx* c, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, int new_width, int new_height,
                        float min_length, int max_segments, const l3d::DetCamera* cam, float** segments, int* n)
 {
@@ -771,13 +804,7 @@ static int detect_to_c(l3d_ctx* c, const unsigned char* pixels, int width, int h
     *n = 0;
     std::vector<float> out;
     const int rc = l3d::detect_segments(c, pixels, width, height, channels, row_stride, new_width, new_height, min_length, max_segments, out, cam);
-    if (rc != L3D_OK) return rc;
-    *n = (int)(out.size() / 4);
-    float* p = static_cast<float*>(malloc(std::max<size_t>(16, out.size() * 4)));
-    if (!p) return l3d::fail(c, L3D_ERR_INVALID, "detect_segments: out of memory");
-    if (!out.empty()) memcpy(p, out.data(), out.size() * 4);
-    *segments = p;
-    return L3D_OK;
+    return rc != L3D_OK ? rc : segments_to_c(c, out, segments, n);
 }
 
 int l3d_detect_segments_distorted(l3d_ctx* c, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, int new_width, int new_height,
@@ -793,6 +820,19 @@ int l3d_detect_segments(l3d_ctx* c, const unsigned char* pixels, int width, int 
     return detect_to_c(c, pixels, width, height, channels, row_stride, new_width, new_height, min_length, max_segments, nullptr, segments, n);
 }
 
+int l3d_detect_segments_jpeg(l3d_ctx* c, const unsigned char* bytes, size_t n, int new_width, int new_height, float min_length, int max_segments,
+                             const double* camera, float** segments, int* n_segments)
+{
+    if (!c || !segments || !n_segments) return L3D_ERR_INVALID;
+    *segments = nullptr;
+    *n_segments = 0;
+    l3d::DetCamera cam{ 1.0, 1.0, 0.0, 0.0, 0.0, 0.0 };
+    if (camera) cam = l3d::DetCamera{ camera[0], camera[1], camera[2], camera[3], camera[4], camera[5] };
+    std::vector<float> out;
+    const int rc = l3d::detect_segments_jpeg(c, bytes, n, new_width, new_height, min_length, max_segments, out, camera ? &cam : nullptr);
+    return rc != L3D_OK ? rc : segments_to_c(c, out, segments, n_segments);
+}
+
 // ---- the stages on their own, for the tests: the functions above (the same kernels and launch shapes as l3d_detect_segments), results copied out
 int l3d_test_detect_pixel_stage(l3d_ctx* c, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, int new_width, int new_height,
                                 float* grey, double* img, double* mod, double* ang, unsigned char* bucket, int* N, int* M)
@@ -800,7 +840,7 @@ int l3d_test_detect_pixel_stage(l3d_ctx* c, const unsigned char* pixels, int wid
     using namespace l3d;
     if (!c || !grey || !img || !mod || !ang || !bucket || !N || !M) return L3D_ERR_INVALID;
     DetPlan p;
-    if (int rc = plan_image(c, p, pixels, width, height, channels, row_stride, new_width, new_height)) return rc;
+    if (int rc = plan_image(c, p, pixels != nullptr, width, height, channels, row_stride, new_width, new_height)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = det_reserve(c, p, 0)) return rc;
     if (int rc = det_pixel_stage(c, p, pixels, row_stride)) return rc;

@@ -21,4 +21,15 @@ int detect_segments(l3d_ctx* c, const unsigned char* pixels, int width, int heig
 int undistort_image(l3d_ctx* c, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, const DetCamera& cam, unsigned char* out,
                     size_t out_row_stride);
 
+// ---- JPEG input (l3d_jpeg.cpp, l3d_jpeg_device.hip): baseline files decoded into the detector's pixel buffer; three components come out B, G, R
+struct JpegFrame;
+// f: the parsed headers of `bytes`.  Entropy decoding on the host, inverse DCT, upsampling and colour on the device, into DetectBufs::pixels
+// (reserved by the caller); returns with the work enqueued on the context's stream
+int jpeg_decode_to_pixels(l3d_ctx* c, const unsigned char* bytes, size_t n, const JpegFrame& f);
+// host bytes in, host pixels out (height rows of width x channels bytes), any size from 1x1
+int decode_jpeg(l3d_ctx* c, const unsigned char* bytes, size_t n, unsigned char* out, size_t out_row_stride);
+// detect_segments on the decoded image, which never crosses the host; images below 8x8 are refused as detect_segments refuses them
+int detect_segments_jpeg(l3d_ctx* c, const unsigned char* bytes, size_t n, int new_width, int new_height, float min_length, int max_segments,
+                         std::vector<float>& out, const DetCamera* cam = nullptr);
+
 }  // namespace l3d

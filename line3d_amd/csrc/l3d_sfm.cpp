@@ -1,8 +1,9 @@
 // l3d_sfm.cpp -- SfM front ends of the reference's two drivers without tclap / OpenCV / boost:
 // the VisualSfM NVM reader of main_vsfm.cpp:121-223 and the bundler reader of main_bundler.cpp:110-204, reduced to what
 // feeds Line3D::addImage: per camera focal length, rotation, translation, distortion coefficients and the list of
-// world points it observes (the similarity source of findVisualNeighbors, line3D.cc:1874-1935).  Image decoding
-// stays outside (undistortion and the detector: l3d_detect.hip, l3d_line3d_add_image_pixels_distorted); a camera's K is built by the caller from the
+// world points it observes (the similarity source of findVisualNeighbors, line3D.cc:1874-1935).  The images
+// themselves go through l3d_line3d_add_image_jpeg / l3d_line3d_add_image_pixels_distorted (decoding of baseline JPEG, undistortion and the detector:
+// l3d_jpeg.cpp, l3d_jpeg_device.hip, l3d_detect.hip); a camera's K is built by the caller from the
 // focal length and the image size the way the drivers do it (main_vsfm.cpp:232-241): [[f,0,w/2],[0,f,h/2],[0,0,1]].
 //
 // Parsing follows the drivers' own token order, including what they skip (header lines, the separator line before the

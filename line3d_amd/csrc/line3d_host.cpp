@@ -826,7 +826,8 @@ int l3d_line3d_add_image_fixed_sim_ex(l3d_line3d* h, uint32_t id, unsigned width
 // device and enter the calls above.  Returns 1: go on with `segs` (possibly none: the cache will be loaded), 0: no segment found, no view; < 0: error negated
 // cam: null, or the camera the pixels are undistorted with before the detector sees them (main_vsfm.cpp:243-270)
 static int detect_for_add(l3d_line3d* h, uint32_t id, const unsigned char* pixels, int width, int height, int channels, size_t row_stride,
-                          const char* data_directory, int max_img_width, int load_and_store, std::vector<float>& segs, const l3d::DetCamera* cam = nullptr)
+                          const char* data_directory, int max_img_width, int load_and_store, std::vector<float>& segs, const l3d::DetCamera* cam = nullptr,
+                          const unsigned char* jpeg = nullptr, size_t jpeg_n = 0)
 {
     segs.clear();
     L* owner = h->node ? rank0(h) : h;
@@ -844,7 +845,9 @@ static int detect_for_add(l3d_line3d* h, uint32_t id, const unsigned char* pixel
     if (f) { fclose(f); if (load_and_store) return 1; }                                     // :159-168: the cache stands in for the image
     if (!owner->ctx) return -h->fail(L3D_ERR_INVALID, "no device context to detect line segments with");
     const float min_length = 0.005f * sqrtf(float(height * height + width * width));         // :176, commons.h:43
-    const int rc = l3d::detect_segments(owner->ctx, pixels, width, height, channels, row_stride, (int)new_w, (int)new_h, min_length, 3000, segs, cam);
+    // jpeg: the file the size came from (pixels null): decoded on the device into the detector -- only here, behind the cache decision
+    const int rc = jpeg ? l3d::detect_segments_jpeg(owner->ctx, jpeg, jpeg_n, (int)new_w, (int)new_h, min_length, 3000, segs, cam)
+                        : l3d::detect_segments(owner->ctx, pixels, width, height, channels, row_stride, (int)new_w, (int)new_h, min_length, 3000, segs, cam);
     if (rc != L3D_OK) return -h->fail(rc, l3d_last_error(owner->ctx));
     if (segs.empty()) { if (f && !load_and_store) remove(file.c_str()); return 0; }          // :153-156, :186-190
     return 1;
@@ -927,6 +930,58 @@ int l3d_line3d_undistort_image(l3d_line3d* h, const unsigned char* pixels, int w
     const int with = camera_for_add(h, K, dist, cam);
     if (with < 0) return -with;
     const int rc = l3d::undistort_image(owner->ctx, pixels, width, height, channels, row_stride, cam, out, out_row_stride);
+    return rc == L3D_OK ? rc : h->fail(rc, l3d_last_error(owner->ctx));
+}
+
+// addImage / addImage_fixed_sim from a baseline JPEG file in memory: the size (cache name, max_img_width rule) comes from the headers; the entropy-coded
+// data is touched only when the detector runs
+static int jpeg_size_for_add(l3d_line3d* h, const unsigned char* bytes, size_t n, int& width, int& height, int& channels)
+{
+    if (!bytes) return -h->fail(L3D_ERR_INVALID, "jpeg: null argument");
+    const int rc = l3d_jpeg_info(bytes, n, &width, &height, &channels);
+    return rc == L3D_OK ? 0 : -h->fail(rc, l3d_jpeg_last_error());
+}
+
+int l3d_line3d_add_image_jpeg(l3d_line3d* h, uint32_t id, const unsigned char* bytes, size_t n, const double* K, const double* R, const double* t, const double dist[2],
+                              const uint32_t* worldpoints, int n_wps, const char* data_directory, int max_img_width, int load_and_store)
+{
+    if (!h) return L3D_ERR_INVALID;
+    int width = 0, height = 0, channels = 0;
+    if (const int e = jpeg_size_for_add(h, bytes, n, width, height, channels)) return -e;
+    l3d::DetCamera cam;
+    const int with = dist ? camera_for_add(h, K, dist, cam) : 0;
+    if (with < 0) return -with;
+    std::vector<float> segs;
+    const int go = detect_for_add(h, id, nullptr, width, height, channels, (size_t)width * channels, data_directory, max_img_width, load_and_store, segs, with ? &cam : nullptr, bytes, n);
+    if (go <= 0) return -go;
+    return l3d_line3d_add_image_ex(h, id, (unsigned)width, (unsigned)height, segs.empty() ? nullptr : segs.data(), (int)(segs.size() / 4), K, R, t, worldpoints, n_wps,
+                                   data_directory, max_img_width, load_and_store);
+}
+
+int l3d_line3d_add_image_jpeg_fixed_sim(l3d_line3d* h, uint32_t id, const unsigned char* bytes, size_t n, const double* K, const double* R, const double* t,
+                                        const double dist[2], const uint32_t* sim_ids, const float* sims, int n_sims, const char* data_directory, int max_img_width,
+                                        int load_and_store)
+{
+    if (!h) return L3D_ERR_INVALID;
+    int width = 0, height = 0, channels = 0;
+    if (const int e = jpeg_size_for_add(h, bytes, n, width, height, channels)) return -e;
+    l3d::DetCamera cam;
+    const int with = dist ? camera_for_add(h, K, dist, cam) : 0;
+    if (with < 0) return -with;
+    std::vector<float> segs;
+    const int go = detect_for_add(h, id, nullptr, width, height, channels, (size_t)width * channels, data_directory, max_img_width, load_and_store, segs, with ? &cam : nullptr, bytes, n);
+    if (go <= 0) return -go;
+    return l3d_line3d_add_image_fixed_sim_ex(h, id, (unsigned)width, (unsigned)height, segs.empty() ? nullptr : segs.data(), (int)(segs.size() / 4), K, R, t, sim_ids, sims,
+                                             n_sims, data_directory, max_img_width, load_and_store);
+}
+
+// l3d_decode_jpeg with the object's device (a node object: rank 0's)
+int l3d_line3d_decode_jpeg(l3d_line3d* h, const unsigned char* bytes, size_t n, unsigned char* out, size_t out_row_stride)
+{
+    if (!h) return L3D_ERR_INVALID;
+    L* owner = h->node ? rank0(h) : h;
+    if (!owner->ctx) return h->fail(L3D_ERR_INVALID, "no device context to decode with");
+    const int rc = l3d::decode_jpeg(owner->ctx, bytes, n, out, out_row_stride);
     return rc == L3D_OK ? rc : h->fail(rc, l3d_last_error(owner->ctx));
 }
 

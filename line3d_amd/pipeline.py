@@ -45,6 +45,7 @@ class Line3D:
                 raise L3DError("l3d_line3d_create failed (code %d): no usable MI355X / HIP device -- no CPU fallback" % rc)
         self.h = h
         self._keep = []
+        self.last_rc = 0          # status of the last add_image_jpeg / add_image_jpeg_fixed_sim (they return a bool, as the other adders do)
 
     def close(self):
         if getattr(self, "h", None):
@@ -178,6 +179,39 @@ class Line3D:
                                                             _p(t), _p(ids), _p(sims), C.c_int(len(ids)), C.c_char_p(self.data_directory.encode()),
                                                             C.c_int(maxImgWidth), C.c_int(int(loadAndStoreSegments)))
         return rc == 0
+
+    def add_image_jpeg(self, imageID, data, K, R, t, worldpointIDs, maxImgWidth=1920, loadAndStoreSegments=True, dist=None):
+        """Line3D::addImage from the bytes of a baseline JPEG file (l3d_line3d_add_image_jpeg): decoded, undistorted (dist = (k1, k2), None: not)
+        and its segments detected on the device.  Cache rules as add_image_pixels; a cache that is present and wanted is loaded without decoding
+        the file.  A file the decoder refuses adds no view and returns False (the cause: l3d_line3d_last_error)."""
+        ptr, n = capi._bytes_arguments(data)
+        K, R, t = (np.ascontiguousarray(a, dtype=np.float64) for a in (K, R, t))
+        wps = np.ascontiguousarray(list(worldpointIDs), dtype=np.uint32)
+        d = None if dist is None else np.ascontiguousarray(dist, dtype=np.float64).reshape(2)
+        self.last_rc = self.lib.l3d_line3d_add_image_jpeg(self.h, C.c_uint32(imageID), ptr, n, _p(K), _p(R), _p(t), None if d is None else _p(d), _p(wps),
+                                                          C.c_int(len(wps)), C.c_char_p(self.data_directory.encode()), C.c_int(maxImgWidth),
+                                                          C.c_int(int(loadAndStoreSegments)))
+        return self.last_rc == 0
+
+    def add_image_jpeg_fixed_sim(self, imageID, data, K, R, t, viewSimilarity, maxImgWidth=1920, loadAndStoreSegments=True, dist=None):
+        """Line3D::addImage_fixed_sim from the bytes of a baseline JPEG file (l3d_line3d_add_image_jpeg_fixed_sim); as add_image_jpeg"""
+        ptr, n = capi._bytes_arguments(data)
+        K, R, t = (np.ascontiguousarray(a, dtype=np.float64) for a in (K, R, t))
+        ids = np.ascontiguousarray(sorted(viewSimilarity), dtype=np.uint32)
+        sims = np.ascontiguousarray([viewSimilarity[int(i)] for i in ids], dtype=np.float32)
+        d = None if dist is None else np.ascontiguousarray(dist, dtype=np.float64).reshape(2)
+        self.last_rc = self.lib.l3d_line3d_add_image_jpeg_fixed_sim(self.h, C.c_uint32(imageID), ptr, n, _p(K), _p(R), _p(t), None if d is None else _p(d),
+                                                                    _p(ids), _p(sims), C.c_int(len(ids)), C.c_char_p(self.data_directory.encode()),
+                                                                    C.c_int(maxImgWidth), C.c_int(int(loadAndStoreSegments)))
+        return self.last_rc == 0
+
+    def decode_jpeg(self, data):
+        """l3d_line3d_decode_jpeg: Context.decode_jpeg with the object's device (a node object: rank 0's)"""
+        w, h, ch = capi.jpeg_info(data)
+        ptr, n = capi._bytes_arguments(data)
+        out = np.zeros((h, w) if ch == 1 else (h, w, ch), np.uint8)
+        self._chk(self.lib.l3d_line3d_decode_jpeg(self.h, ptr, n, _p(out), C.c_size_t(w * ch)))
+        return out
 
     def addImage_fixed_sim(self, imageID, width, height, segments, K, R, t, viewSimilarity):
         segs = np.ascontiguousarray(segments, dtype=np.float32).reshape(-1, 4)
