@@ -285,6 +285,65 @@ public:
         report(rc);
         return rc == L3D_OK;
     }
+    // Many images in one call (l3d_line3d_add_images): what a loop over addImage / addImageDistorted / addImageJPEG[Distorted] and their _fixed_sim
+    // forms adds, in entry order, with the detector run once over all images whose cache does not stand in for them.  An entry is built by makeEntry
+    // from what those calls take: an image type with pixels (.cols / .rows / .data / .step / .channels(): cv::Mat) or the bytes of a baseline JPEG
+    // file, matrix-typed K, R, t, and the links -- a std::list of world point ids or a std::map of view similarities.  .distorted(k1, k2) on the
+    // entry gives the ...Distorted forms.  The pixels / bytes are not copied: they have to live until addImages returns.
+    struct ImageEntry {
+        unsigned int imageID = 0;
+        const unsigned char *pixels = nullptr, *jpeg = nullptr;
+        int width = 0, height = 0, channels = 0;
+        size_t step = 0, jpeg_bytes = 0;
+        double K[9], R[9], t[3], dist[2] = { 0.0, 0.0 };
+        bool has_dist = false, fixed_sim = false;
+        std::vector<uint32_t> link_ids;
+        std::vector<float> sims;
+        ImageEntry& distorted(const double k1, const double k2) { dist[0] = k1; dist[1] = k2; has_dist = true; return *this; }
+    };
+    template <class Img, class M3, class V3, class Links, class = decltype(static_cast<const unsigned char*>(std::declval<const Img&>().data)),
+              class = decltype(static_cast<size_t>(std::declval<const Img&>().step)), class = decltype(static_cast<int>(std::declval<const Img&>().channels())),
+              class = decltype(std::declval<const M3&>()(0, 0)), class = decltype(std::declval<const V3&>()(0))>
+    static ImageEntry makeEntry(const unsigned int imageID, const Img& image, const M3& K, const M3& R, const V3& t, const Links& links)
+    {
+        ImageEntry e;
+        e.imageID = imageID;
+        e.pixels = static_cast<const unsigned char*>(image.data);
+        e.width = (int)image.cols; e.height = (int)image.rows; e.channels = static_cast<int>(image.channels()); e.step = static_cast<size_t>(image.step);
+        flatten(K, R, t, e.K, e.R, e.t);
+        set_links(e, links);
+        return e;
+    }
+    template <class M3, class V3, class Links, class = decltype(std::declval<const M3&>()(0, 0)), class = decltype(std::declval<const V3&>()(0))>
+    static ImageEntry makeEntry(const unsigned int imageID, const unsigned char* bytes, const size_t n, const M3& K, const M3& R, const V3& t, const Links& links)
+    {
+        ImageEntry e;
+        e.imageID = imageID;
+        e.jpeg = bytes; e.jpeg_bytes = n;
+        flatten(K, R, t, e.K, e.R, e.t);
+        set_links(e, links);
+        return e;
+    }
+    // the per-entry statuses (L3D_OK, or the code the single call would have failed with); the causes are printed, one line per failed entry
+    std::vector<int> addImages(const std::vector<ImageEntry>& entries, const int maxImgWidth = 1920, const bool loadAndStoreSegments = true)
+    {
+        std::vector<l3d_image_entry> e(entries.size());
+        for (size_t i = 0; i < entries.size(); ++i) {
+            const ImageEntry& s = entries[i];
+            l3d_image_entry& d = e[i];
+            d.image_id = s.imageID;
+            d.pixels = s.pixels; d.width = s.width; d.height = s.height; d.channels = s.channels; d.row_stride = s.step;
+            d.jpeg = s.jpeg; d.jpeg_bytes = s.jpeg_bytes;
+            d.K = s.K; d.R = s.R; d.t = s.t; d.dist = s.has_dist ? s.dist : nullptr;
+            d.link_ids = s.link_ids.data(); d.sims = s.fixed_sim ? s.sims.data() : nullptr; d.n_links = (int)s.link_ids.size();
+        }
+        std::vector<int> status(entries.size(), L3D_ERR_INVALID);        // (a call refused as a whole -- no object -- leaves them)
+        const int rc = l3d_line3d_add_images(h_, e.data(), (int)e.size(), data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0, status.data());
+        bool any = rc != L3D_OK;
+        for (int st : status) any = any || st != L3D_OK;
+        if (any) std::cerr << prefix_ << l3d_line3d_last_error(h_) << std::endl;
+        return status;
+    }
     // line3D.h:82
     void compute3Dmodel(bool perform_diffusion = false) { report(l3d_line3d_compute3Dmodel(h_, perform_diffusion ? 1 : 0)); }
     // line3D.h:85
@@ -398,6 +457,13 @@ private:
         for (auto& kv : *viewSimilarity) { ids.push_back(kv.first); sims.push_back(kv.second); }
         report(l3d_line3d_add_image_jpeg_fixed_sim(h_, imageID, bytes, n, k, r, tt, dist, ids.data(), sims.data(), (int)ids.size(), data_directory_.c_str(), maxImgWidth,
                                                    loadAndStoreSegments ? 1 : 0));
+    }
+    static void set_links(ImageEntry& e, const std::list<unsigned int>& worldpointIDs) { e.link_ids.assign(worldpointIDs.begin(), worldpointIDs.end()); }
+    static void set_links(ImageEntry& e, const std::map<unsigned int, float>& viewSimilarity)
+    {
+        for (auto& kv : viewSimilarity) { e.link_ids.push_back(kv.first); e.sims.push_back(kv.second); }
+        e.sims.push_back(0.0f);       // (never null: `sims` tells the two kinds of links apart)
+        e.fixed_sim = true;
     }
     void report(int rc) { if (rc != L3D_OK) std::cerr << prefix_ << l3d_line3d_last_error(h_) << std::endl; }
     l3d_line3d* h_;

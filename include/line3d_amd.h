@@ -870,6 +870,49 @@ int l3d_line3d_add_image_jpeg_fixed_sim(l3d_line3d* h, uint32_t image_id, const 
 int l3d_line3d_decode_jpeg(l3d_line3d* h, const unsigned char* bytes, size_t n, unsigned char* out, size_t out_row_stride);
 int l3d_test_jpeg_coefficients(const unsigned char* bytes, size_t n, int16_t** coef, size_t* n_blocks, uint16_t* qt, int32_t* layout);
 
+/* =================================================================================================
+ * Images in batches: one pass of the detector over many images.
+ *
+ * l3d_detect_segments_batch   n entries, each 8-bit pixels (as l3d_detect_segments takes them) or, with pixels == NULL, a baseline JPEG file (as
+ *                             l3d_detect_segments_jpeg takes it); camera: NULL, or (fx, fy, cx, cy, k1, k2) of l3d_detect_segments_distorted.
+ *                             *segments (callee-allocated, l3d_free) holds the segments of all entries one after the other, those of entry i at
+ *                             offsets[i] .. offsets[i + 1] (in segments of 4 floats; offsets has n + 1 places): BYTE FOR BYTE what the single call
+ *                             gives for that entry alone, whatever else is in the batch and in whatever order.  Entries of the same sizes (width,
+ *                             height, channels, new size) run through the detector together, in chunks: every stage is launched once per chunk
+ *                             and the host waits once per look of the labelling and twice more per chunk, not per image.  A chunk holds as many
+ *                             images as the option L3D_DET_BATCH_IMAGES allows (0: no limit of its own), as keep the chunk's scaled pixels within
+ *                             2^30, and as fit half of the device memory that is free at the time; at most 1024.  status[i] is what the single
+ *                             call would have returned for entry i: a refused entry (a progressive file, an image below 8x8, a corrupt entropy
+ *                             stream ...) fails alone and has no segments, the others are not affected.  The call returns L3D_OK when the batch
+ *                             was processed, else the code of a device failure (entries not finished by then carry it in their status);
+ *                             l3d_last_error then holds one line per failed entry, "entry <i>: <message>".
+ * l3d_line3d_add_images       exactly the sequence of l3d_line3d_add_image_pixels[_fixed_sim][_distorted] / l3d_line3d_add_image_jpeg[_fixed_sim]
+ *                             calls, in entry order: the cache decision is taken per entry (an entry whose cache is present and wanted is neither
+ *                             decoded nor detected), every other entry goes through the batched detector, then the views are added in entry
+ *                             order.  sims == NULL: link_ids are world point ids; otherwise view ids with their similarities.  dist NULL, or both
+ *                             coefficients within 1e-12: no undistortion.  status[i] (may be NULL) is what the single call would have returned;
+ *                             a failed entry fails alone with the single call's message, an image without segments is L3D_OK and no view.  The
+ *                             call returns L3D_OK when the batch was processed, else a device failure's code (entries added before it stay added);
+ *                             l3d_line3d_last_error holds one line per failed entry, "image <id>: <message>".  On a node object rank 0's device
+ *                             does the detection.
+ * ================================================================================================= */
+typedef struct l3d_detect_entry {
+    const unsigned char* pixels; int width, height, channels; size_t row_stride;   /* or: */
+    const unsigned char* jpeg; size_t jpeg_bytes;                                   /* pixels == NULL: a baseline JPEG file */
+    int new_width, new_height; float min_length; int max_segments;
+    const double* camera;                                                           /* NULL, or fx, fy, cx, cy, k1, k2 */
+} l3d_detect_entry;
+int l3d_detect_segments_batch(l3d_ctx* ctx, const l3d_detect_entry* e, int n, float** segments, int* offsets /* n + 1 */, int* status /* n */);
+
+typedef struct l3d_image_entry {
+    uint32_t image_id;
+    const unsigned char* pixels; int width, height, channels; size_t row_stride;
+    const unsigned char* jpeg; size_t jpeg_bytes;
+    const double *K, *R, *t, *dist;                 /* dist: NULL or k1, k2 */
+    const uint32_t* link_ids; const float* sims; int n_links;   /* sims == NULL: world point ids; else view similarities */
+} l3d_image_entry;
+int l3d_line3d_add_images(l3d_line3d* h, const l3d_image_entry* e, int n, const char* data_directory, int max_img_width, int load_and_store, int* status);
+
 /* The detector's stages on their own, exported for tests (tests/test_gpu_detect_stages.py): the same kernels with the same launch shapes
  * as l3d_detect_segments, results copied to caller-allocated arrays.  (N, M) = (ceil(0.8 new_width), ceil(0.8 new_height)) is the scaled image.
  *   pixel stage   grey[new_width x new_height] after rescale + grey; img / mod / ang [N x M]: the Gaussian sampler's output, the 2x2 gradient's

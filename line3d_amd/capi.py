@@ -131,6 +131,65 @@ def test_jpeg_coefficients(data):
 test_jpeg_coefficients.__test__ = False
 
 
+class DetectEntry(C.Structure):
+    """l3d_detect_entry (include/line3d_amd.h)"""
+    _fields_ = [("pixels", C.c_void_p), ("width", C.c_int), ("height", C.c_int), ("channels", C.c_int), ("row_stride", C.c_size_t),
+                ("jpeg", C.c_void_p), ("jpeg_bytes", C.c_size_t), ("new_width", C.c_int), ("new_height", C.c_int), ("min_length", C.c_float),
+                ("max_segments", C.c_int), ("camera", C.c_void_p)]
+
+
+class ImageEntry(C.Structure):
+    """l3d_image_entry (include/line3d_amd.h)"""
+    _fields_ = [("image_id", C.c_uint32), ("pixels", C.c_void_p), ("width", C.c_int), ("height", C.c_int), ("channels", C.c_int),
+                ("row_stride", C.c_size_t), ("jpeg", C.c_void_p), ("jpeg_bytes", C.c_size_t), ("K", C.c_void_p), ("R", C.c_void_p), ("t", C.c_void_p),
+                ("dist", C.c_void_p), ("link_ids", C.c_void_p), ("sims", C.c_void_p), ("n_links", C.c_int)]
+
+
+def _per_image(value, n, what):
+    """None, or one entry per image"""
+    if value is None:
+        return [None] * n
+    value = list(value)
+    if len(value) != n:
+        raise ValueError("%s: %d entries for %d images" % (what, len(value), n))
+    return value
+
+
+def detect_entries(images, new_sizes=None, min_lengths=None, max_segments=3000, cameras=None):
+    """The l3d_detect_entry array of Context.detect_segments_batch, and what keeps its pointers alive.  Everything malformed is refused here,
+    before any device call: an image that is neither a uint8 array nor bytes, a camera that is not six numbers, lists of the wrong length."""
+    images = list(images)
+    n = len(images)
+    new_sizes, min_lengths, cameras = _per_image(new_sizes, n, "new_sizes"), _per_image(min_lengths, n, "min_lengths"), _per_image(cameras, n, "cameras")
+    caps = [int(max_segments)] * n if np.isscalar(max_segments) else [int(v) for v in _per_image(max_segments, n, "max_segments")]
+    entries, keep = (DetectEntry * max(1, n))(), []
+    for i, img in enumerate(images):
+        e = entries[i]
+        if isinstance(img, (bytes, bytearray, memoryview)):
+            ptr, nbytes = _bytes_arguments(img)
+            try:
+                w, h, _ = jpeg_info(img)
+            except L3DError:                # the library refuses the entry with its own status and message
+                w, h = 0, 0
+            e.jpeg, e.jpeg_bytes = ptr.value, nbytes.value
+        elif isinstance(img, np.ndarray):
+            ptr, w, h, ch, stride = image_arguments(img)
+            e.pixels, e.width, e.height, e.channels, e.row_stride = ptr.value, w, h, ch, stride
+        else:
+            raise TypeError("image %d must be a uint8 array or the bytes of a JPEG file" % i)
+        keep.append(ptr)
+        e.new_width, e.new_height = (w, h) if new_sizes[i] is None else (int(new_sizes[i][0]), int(new_sizes[i][1]))
+        e.min_length = float(np.float32(0.005) * np.sqrt(np.float32(h * h + w * w))) if min_lengths[i] is None else float(min_lengths[i])
+        e.max_segments = caps[i]
+        if cameras[i] is not None:
+            if len(cameras[i]) != 6:
+                raise ValueError("camera must be (fx, fy, cx, cy, k1, k2)")
+            cam = (C.c_double * 6)(*[float(v) for v in cameras[i]])
+            keep.append(cam)
+            e.camera = C.addressof(cam)
+    return entries, keep
+
+
 class AffinityInput(C.Structure):
     """l3d_affinity_input (include/line3d_amd.h)"""
     _fields_ = [("n_views", C.c_int32), ("seg_base", C.c_void_p), ("view_hyp_begin", C.c_void_p), ("n_hyp", C.c_int32),
@@ -287,6 +346,35 @@ class Context:
                                                     C.byref(out), C.byref(cnt)))
         segs = np.ctypeslib.as_array(out, (cnt.value, 4)).copy() if cnt.value else np.zeros((0, 4), np.float32)
         self.lib.l3d_free(out)
+        return segs
+
+    # -- images in batches: one pass of the detector over many images ---------------------------------
+    def detect_segments_batch(self, images, new_sizes=None, min_lengths=None, max_segments=3000, cameras=None, return_status=False):
+        """l3d_detect_segments_batch: a list of images -- uint8 arrays (as detect_segments takes them) or `bytes` of baseline JPEG files (as
+        detect_segments_jpeg takes them) -> a list of (n, 4) float32 arrays, each byte for byte what the single call gives for that image.
+        new_sizes, min_lengths, max_segments, cameras: None, one value for all (max_segments), or a list with one entry (possibly None) per image,
+        with the single calls' meanings and defaults.  An entry the single call would refuse raises L3DError (its .code the first such entry's
+        status, .statuses all of them); return_status=True: no raise, the result is (segments, statuses)."""
+        images = list(images)
+        entries, keep = detect_entries(images, new_sizes, min_lengths, max_segments, cameras)
+        n = len(images)
+        out, offsets, status = C.POINTER(C.c_float)(), (C.c_int * (n + 1))(), (C.c_int * max(1, n))()
+        rc = self.lib.l3d_detect_segments_batch(self.h, entries, C.c_int(n), C.byref(out), offsets, status)
+        statuses = [int(status[i]) for i in range(n)]
+        segs = []
+        if rc == 0:
+            total = int(offsets[n])
+            flat = np.ctypeslib.as_array(out, (total, 4)).copy() if total else np.zeros((0, 4), np.float32)
+            segs = [flat[offsets[i]:offsets[i + 1]].copy() for i in range(n)]
+        self.lib.l3d_free(out)
+        self._chk(rc)
+        if return_status:
+            return segs, statuses
+        bad = [st for st in statuses if st != 0]
+        if bad:
+            e = L3DError("line3d_amd error %d: %s" % (bad[0], self.lib.l3d_last_error(self.h).decode()))
+            e.code, e.statuses = bad[0], statuses
+            raise e
         return segs
 
     # -- the detector's stages on their own (tests): the same kernels and launch shapes as detect_segments

@@ -138,7 +138,9 @@ struct FillPart { int h0 = 0, h1 = 0; unsigned long long pos_base = 0; const int
 // scratch of the line segment detector (l3d_detect.hip): sized to the largest image seen, reused across calls
 struct DetectBufs {
     // undist: the undistorted image (k_det_undistort), reserved only when an image comes with distortion coefficients
-    DevBuf pixels, undist, grey, aux, img, mod, ang, bucket, active, parent, size, count, keys, keys2, vals, vals2, flag, pos, start, tmp, cand, ckeys, ckeys2, cvals, cvals2, out, ktab, scal;
+    // a chunk of B images of one size (l3d_detect.hip) holds them one after the other in every per-pixel buffer; cimg, cimg2: the image of a packed
+    // candidate; prm: what varies between the images of a chunk (camera, length filter, cap)
+    DevBuf pixels, undist, grey, aux, img, mod, ang, bucket, active, parent, size, count, keys, keys2, vals, vals2, flag, pos, start, tmp, cand, ckeys, ckeys2, cvals, cvals2, cimg, cimg2, prm, out, ktab, scal;
     // JPEG input (l3d_jpeg_device.hip), reserved only when a JPEG is decoded: the quantisation tables and the quantised coefficients as the host's entropy
     // decoder wrote them into the pinned `jstage`, and the uint8 component planes over whole MCUs
     DevBuf jcoef, jplanes;
@@ -146,10 +148,19 @@ struct DetectBufs {
     int tab_w = 0, tab_h = 0;       // the image size the Gaussian sampler's tables in `ktab` were made for
     void release()
     {
-        DevBuf* b[] = { &pixels, &undist, &grey, &aux, &img, &mod, &ang, &bucket, &active, &parent, &size, &count, &keys, &keys2, &vals, &vals2, &flag, &pos, &start, &tmp, &cand, &ckeys, &ckeys2, &cvals, &cvals2, &out, &ktab, &scal };
-        for (DevBuf* x : b) x->release();
-        jcoef.release(); jplanes.release(); jstage.release();
+        for (DevBuf* x : all()) x->release();
+        jstage.release();
         tab_w = tab_h = 0;
+    }
+    size_t held()                   // device bytes these buffers hold (the chunk rule counts them as available)
+    {
+        size_t n = 0;
+        for (DevBuf* x : all()) n += x->cap;
+        return n;
+    }
+    std::vector<DevBuf*> all()
+    {
+        return { &pixels, &undist, &grey, &aux, &img, &mod, &ang, &bucket, &active, &parent, &size, &count, &keys, &keys2, &vals, &vals2, &flag, &pos, &start, &tmp, &cand, &ckeys, &ckeys2, &cvals, &cvals2, &cimg, &cimg2, &prm, &out, &ktab, &scal, &jcoef, &jplanes };
     }
 };
 

@@ -14,6 +14,11 @@
 // The result therefore AGREES with the reference detector (tests/detect_metric.py) and is not identical to it.  It is deterministic:
 // labels are component minima, sizes and votes are integer atomics, every floating-point sum runs in a fixed order (no float atomics),
 // and the final order is (length descending, smallest pixel index).
+//
+// A BATCH: images with the same plan (w, h, ch, nw, nh) run B at a time through these kernels.  Every per-pixel array holds the B images one after the
+// other (image b at b * np), the pixel kernels take the image from blockIdx.z, and from the labelling on the stack is ONE set of NP = B * np pixels:
+// parents, region keys (partition * NP + root) and the pixel sort range over the stack, a region never leaves its image (the hook kernel links
+// inside an image only), and the region kernel works in the image's own coordinates (pixel index minus b * np).  One image is a batch of one.
 #include "l3d_detect.hpp"
 
 #include <cmath>
@@ -32,6 +37,8 @@ constexpr int kTaps = 7, kHalf = 3;         // sigma = 0.6 / 0.8: h = ceil(sigma
 constexpr int kRounds = 3;
 
 struct DetCand { double x1, y1, x2, y2; unsigned minpix, pad; };
+// what differs between the images of one chunk, on the device: the camera (on: the image is undistorted), the selection's filter and cap
+struct DetImgParam { DetCamera cam; int cam_on; float min_length; int max_segments; int pad; };
 
 // ---- rescale (bilinear, half-pixel centres, 8-bit weights) + grey: the integer formulas stated in include/line3d_amd.h
 __device__ inline void axis_taps(int i, int n_out, int n_in, int& i0, int& i1, int& a)
@@ -48,6 +55,8 @@ __global__ void k_det_grey(const unsigned char* __restrict__ px, int w, int h, i
 {
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= nw || y >= nh) return;
+    px += (size_t)blockIdx.z * w * h * ch;
+    grey += (size_t)blockIdx.z * nw * nh;
     int v[3] = { 0, 0, 0 };
     if (nw == w && nh == h) {
         for (int k = 0; k < ch; ++k) v[k] = px[((size_t)y * w + x) * ch + k];
@@ -69,10 +78,20 @@ __global__ void k_det_grey(const unsigned char* __restrict__ px, int w, int h, i
 // doubles (none is stored), 5 fractional bits per coordinate, the four taps weighted in 1/1024 with black outside the image.  Blocks are 32 x 8:
 // the taps of a wave lie within a few source rows
 constexpr int kUndBx = 32, kUndBy = 8;
-__global__ __launch_bounds__(256) void k_det_undistort(const unsigned char* __restrict__ src, int w, int h, int ch, DetCamera cam, unsigned char* __restrict__ dst)
+// prm: the cameras of a chunk's images (blockIdx.z), an image without one is copied; null: `one` for the single image
+__global__ __launch_bounds__(256) void k_det_undistort(const unsigned char* __restrict__ src, int w, int h, int ch, DetCamera one, const DetImgParam* __restrict__ prm,
+                                                        unsigned char* __restrict__ dst)
 {
     const int j = blockIdx.x * kUndBx + threadIdx.x, i = blockIdx.y * kUndBy + threadIdx.y;
     if (j >= w || i >= h) return;
+    src += (size_t)blockIdx.z * w * h * ch;
+    dst += (size_t)blockIdx.z * w * h * ch;
+    if (prm && !prm[blockIdx.z].cam_on) {
+        const size_t at = ((size_t)i * w + j) * ch;
+        for (int k = 0; k < ch; ++k) dst[at + k] = src[at + k];
+        return;
+    }
+    const DetCamera cam = prm ? prm[blockIdx.z].cam : one;
     const double x = ((double)j - cam.cx) / cam.fx, y = ((double)i - cam.cy) / cam.fy;
     const double r2 = x * x + y * y, kr = 1.0 + (cam.k2 * r2 + cam.k1) * r2;
     const double u = cam.fx * (x * kr) + cam.cx, v = cam.fy * (y * kr) + cam.cy;
@@ -112,6 +131,8 @@ __global__ __launch_bounds__(256) void k_det_gauss_x(const float* __restrict__ g
                                                       const int* __restrict__ xc, const double* __restrict__ kw)
 {
     __shared__ float tile[4][kXSpan];
+    grey += (size_t)blockIdx.z * W * H;
+    aux += (size_t)blockIdx.z * N * H;
     const int x0 = blockIdx.x * 64, y = blockIdx.y * 4 + threadIdx.y, xl = min(x0 + 63, N - 1);
     const int lo = xc[x0] - kHalf, span = min(xc[xl] + kHalf - lo + 1, kXSpan);
     if (y < H)
@@ -129,6 +150,8 @@ __global__ __launch_bounds__(256) void k_det_gauss_y(const double* __restrict__ 
                                                       const int* __restrict__ yc, const double* __restrict__ kw)
 {
     __shared__ double tile[kYSpan][64];
+    aux += (size_t)blockIdx.z * N * H;
+    img += (size_t)blockIdx.z * N * M;
     const int x = blockIdx.x * 64 + threadIdx.x, y0 = blockIdx.y * kYRows, yl = min(y0 + kYRows - 1, M - 1);
     const int lo = yc[y0] - kHalf, span = min(yc[yl] + kHalf - lo + 1, kYSpan);
     for (int r = threadIdx.y; r < span; r += 4) tile[r][threadIdx.x] = x < N ? aux[(size_t)sym_index(lo + r, H) * N + x] : 0.0;
@@ -151,6 +174,8 @@ __global__ void k_det_grad(const double* __restrict__ img, int N, int M, double 
 {
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= N || y >= M) return;
+    const size_t at = (size_t)blockIdx.z * N * M;       // the last row and column of EACH image have no gradient
+    img += at; mod += at; ang += at; bucket += at; active += at;
     const size_t i = (size_t)y * N + x;
     double m = 0.0, a = kNotDef;
     if (x < N - 1 && y < M - 1) {
@@ -171,7 +196,8 @@ __global__ void k_det_grad(const double* __restrict__ img, int N, int M, double 
     active[i] = a != kNotDef;
 }
 
-// ---- labelling: both partitions in one grid (blockIdx.y); another workgroup's parents are touched through atomics only
+// ---- labelling: both partitions of every image in one grid (blockIdx.z = 2 image + partition); another workgroup's parents are touched through
+// atomics only.  np here and below, where no image size goes with it: the pixels of the whole stack; parents are indices into the stack
 __global__ void k_det_label_init(const unsigned char* __restrict__ active, int np, int* __restrict__ parent)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -189,16 +215,17 @@ __device__ inline int det_root(int* par, int a)
 __global__ void k_det_label_hook(const uchar2* __restrict__ bucket, const unsigned char* __restrict__ active, int N, int M, int* __restrict__ parent,
                                  int* __restrict__ changed)
 {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, p = blockIdx.z;
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, p = blockIdx.z & 1;
     if (x >= N || y >= M) return;
-    const int i = y * N + x;
+    const int at = (int)(blockIdx.z >> 1) * N * M;          // neighbours are sought within the image: x, y are its own
+    const int i = at + y * N + x;
     if (!active[i]) return;
-    int* par = parent + (size_t)p * N * M;
+    int* par = parent + (size_t)p * (gridDim.z >> 1) * N * M;
     const unsigned char bi = p ? bucket[i].y : bucket[i].x;
     const int nx[4] = { x + 1, x - 1, x, x + 1 }, ny[4] = { y, y + 1, y + 1, y + 1 };
     for (int k = 0; k < 4; ++k) {
         if (nx[k] < 0 || nx[k] >= N || ny[k] >= M) continue;
-        const int j = ny[k] * N + nx[k];
+        const int j = at + ny[k] * N + nx[k];
         if (!active[j]) continue;
         const unsigned char bj = p ? bucket[j].y : bucket[j].x;
         if (bj != bi) continue;
@@ -358,10 +385,12 @@ __device__ DetScore rect_retry(DetRect& rec, const double* __restrict__ ang, int
     return best;
 }
 
-__global__ __launch_bounds__(256) void k_det_region(int N, int M, double logNT, int min_reg, const double* __restrict__ mod, const double* __restrict__ ang,
+// the waves range over the regions of all images of the stack.  A region lies in one image (vals / (N M)); its pixels are taken relative to that image,
+// so coordinates, sums, the rectangle scan's clipping and minpix are what the image alone gives.  cand / n_cand: cand_cap slots and a counter per image
+__global__ __launch_bounds__(256) void k_det_region(int N, int M, double logNT, int min_reg, const double* __restrict__ mod_all, const double* __restrict__ ang_all,
                                                      const unsigned* __restrict__ keys, const unsigned* __restrict__ vals, const int* __restrict__ count,
-                                                     const int* __restrict__ start, const int* __restrict__ n_regions, unsigned char* __restrict__ active,
-                                                     DetCand* __restrict__ cand, int* __restrict__ n_cand, int cand_cap, l3d_detect_region_record* __restrict__ trace)
+                                                     const int* __restrict__ start, const int* __restrict__ n_regions, unsigned char* __restrict__ active_all,
+                                                     DetCand* __restrict__ cand_all, int* __restrict__ n_cand_all, int cand_cap, l3d_detect_region_record* __restrict__ trace)
 {
     const int lane = threadIdx.x & 63;
     const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
@@ -370,12 +399,16 @@ __global__ __launch_bounds__(256) void k_det_region(int N, int M, double logNT, 
     for (int reg = wave; reg < n_reg; reg += n_waves) {
         const int s0 = start[reg], n_all = count[keys[s0]];
         const unsigned* px = vals + s0;
+        const unsigned image = px[0] / (unsigned)(N * M), at = image * (unsigned)(N * M);
+        const double* mod = mod_all + at;
+        const double* ang = ang_all + at;
+        unsigned char* active = active_all + at;
         // the strongest pixel (tie: the smallest index): the centre the region shrinks about
         double best_m = -1.0;
         unsigned best_i = 0xffffffffu;
         for (int i = lane; i < n_all; i += 64) {
-            const double m = mod[px[i]];
-            if (m > best_m) { best_m = m; best_i = px[i]; }
+            const double m = mod[px[i] - at];
+            if (m > best_m) { best_m = m; best_i = px[i] - at; }
         }
         const double top = wmax(best_m);
         const unsigned seed = wminu(best_m == top ? best_i : 0xffffffffu);
@@ -383,13 +416,13 @@ __global__ __launch_bounds__(256) void k_det_region(int N, int M, double logNT, 
         double rad = -1.0;                      // < 0: the whole region
         DetRect rec;
         l3d_detect_region_record* tr = trace && lane == 0 ? trace + reg : nullptr;      // (tests only: what this wave decides; the caller zeroes it)
-        if (tr) tr->minpix = px[0];
+        if (tr) tr->minpix = px[0] - at;
         for (int step = 0; step < 64; ++step) {
             double w = 0, wx = 0, wy = 0, cdx = 0, cdy = 0;
             int n = 0;
             unsigned first = 0xffffffffu;
             for (int i = lane; i < n_all; i += 64) {
-                const unsigned q = px[i];
+                const unsigned q = px[i] - at;
                 const double x = (double)(q % (unsigned)N), y = (double)(q / (unsigned)N);
                 if (rad >= 0.0 && sqrt((x - sx) * (x - sx) + (y - sy) * (y - sy)) > rad) continue;
                 const double m = mod[q], t = ang[q];
@@ -406,7 +439,7 @@ __global__ __launch_bounds__(256) void k_det_region(int N, int M, double logNT, 
             const double cx = wx / w, cy = wy / w;
             double ixx = 0, iyy = 0, ixy = 0;
             for (int i = lane; i < n_all; i += 64) {
-                const unsigned q = px[i];
+                const unsigned q = px[i] - at;
                 const double x = (double)(q % (unsigned)N), y = (double)(q / (unsigned)N);
                 if (rad >= 0.0 && sqrt((x - sx) * (x - sx) + (y - sy) * (y - sy)) > rad) continue;
                 const double m = mod[q];
@@ -419,7 +452,7 @@ __global__ __launch_bounds__(256) void k_det_region(int N, int M, double logNT, 
             const double dx = cos(theta), dy = sin(theta);
             double lmin = 0, lmax = 0, wmn = 0, wmx = 0;
             for (int i = lane; i < n_all; i += 64) {
-                const unsigned q = px[i];
+                const unsigned q = px[i] - at;
                 const double x = (double)(q % (unsigned)N), y = (double)(q / (unsigned)N);
                 if (rad >= 0.0 && sqrt((x - sx) * (x - sx) + (y - sy) * (y - sy)) > rad) continue;
                 const double l = (x - cx) * dx + (y - cy) * dy, ww = -(x - cx) * dy + (y - cy) * dx;
@@ -443,16 +476,16 @@ __global__ __launch_bounds__(256) void k_det_region(int N, int M, double logNT, 
                 }
                 if (best > 0.0) {
                     if (lane == 0) {
-                        const int slot = atomicAdd(n_cand, 1);
+                        const int slot = atomicAdd(n_cand_all + image, 1);
                         if (slot < cand_cap) {
                             DetCand c;
                             c.x1 = (rec.x1 + 0.5) / kScale; c.y1 = (rec.y1 + 0.5) / kScale; c.x2 = (rec.x2 + 0.5) / kScale; c.y2 = (rec.y2 + 0.5) / kScale;
                             c.minpix = first; c.pad = 0;
-                            cand[slot] = c;
+                            cand_all[(size_t)image * cand_cap + slot] = c;
                         }
                     }
                     for (int i = lane; i < n_all; i += 64) {            // consumed: everything else of the region is released
-                        const unsigned q = px[i];
+                        const unsigned q = px[i] - at;
                         const double x = (double)(q % (unsigned)N), y = (double)(q / (unsigned)N);
                         if (rad >= 0.0 && sqrt((x - sx) * (x - sx) + (y - sy) * (y - sy)) > rad) continue;
                         active[q] = 0;
@@ -474,22 +507,52 @@ __device__ inline float4 cand_coords(const DetCand& c, float up)
 {
     return make_float4((float)c.x1 * up, (float)c.y1 * up, (float)c.x2 * up, (float)c.y2 * up);
 }
-__global__ void k_det_select_keys(const DetCand* __restrict__ cand, int n, float up, float min_length, unsigned long long* __restrict__ keys, unsigned* __restrict__ vals)
+// per image: its candidates (at most cand_cap) and the slots its segments can take (at most max_segments of them), as running sums over the chunk;
+// the counts the gather will write start at zero
+__global__ void k_det_select_plan(const int* __restrict__ n_cand, const DetImgParam* __restrict__ prm, int B, int cand_cap, int* __restrict__ coff, int* __restrict__ ooff,
+                                  int* __restrict__ n_out)
 {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float4 s = cand_coords(cand[i], up);
-    const float dx = s.x - s.z, dy = s.y - s.w, len = sqrtf(dx * dx + dy * dy);
-    vals[i] = (unsigned)i;
-    keys[i] = len > min_length ? ((unsigned long long)(~__float_as_uint(len)) << 32) | cand[i].minpix : ~0ull;
+    if (blockIdx.x || threadIdx.x) return;
+    int c = 0, o = 0;
+    for (int b = 0; b < B; ++b) {
+        const int n = max(0, min(n_cand[b], cand_cap));
+        coff[b] = c; ooff[b] = o; n_out[b] = 0;
+        c += n; o += min(n, max(0, prm[b].max_segments));
+    }
+    coff[B] = c; ooff[B] = o;
 }
-__global__ void k_det_select_gather(const DetCand* __restrict__ cand, const unsigned long long* __restrict__ keys, const unsigned* __restrict__ vals, int n, int limit,
-                                    float up, float4* __restrict__ out, int* __restrict__ n_out)
+// the candidates of all images, packed in image order (blockIdx.y: the image).  The key has no room for the image: the order of one image's
+// candidates comes from the sort by this key, the images are put apart again by a stable sort on imgs (k_det_select_image)
+__global__ void k_det_select_keys(const DetCand* __restrict__ cand, const int* __restrict__ coff, int cand_cap, float up, const DetImgParam* __restrict__ prm,
+                                  unsigned long long* __restrict__ keys, unsigned* __restrict__ vals, unsigned* __restrict__ imgs)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (i >= coff[b + 1] - coff[b]) return;
+    const DetCand& c = cand[(size_t)b * cand_cap + i];
+    const float4 s = cand_coords(c, up);
+    const float dx = s.x - s.z, dy = s.y - s.w, len = sqrtf(dx * dx + dy * dy);
+    const int at = coff[b] + i;
+    vals[at] = (unsigned)at;
+    imgs[at] = (unsigned)b;
+    keys[at] = len > prm[b].min_length ? ((unsigned long long)(~__float_as_uint(len)) << 32) | c.minpix : ~0ull;
+}
+__global__ void k_det_select_image(const unsigned* __restrict__ vals, const unsigned* __restrict__ imgs, int n, unsigned* __restrict__ img_sorted)
 {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n || j >= limit || keys[j] == ~0ull) return;
-    out[j] = cand_coords(cand[vals[j]], up);
-    if (j + 1 == n || j + 1 == limit || keys[j + 1] == ~0ull) *n_out = j + 1;
+    if (j < n) img_sorted[j] = imgs[vals[j]];
+}
+// vals: the packed candidates, images apart, each image's by key.  keys, imgs: by packed index.  The image's r-th is its r-th segment
+__global__ void k_det_select_gather(const DetCand* __restrict__ cand, const unsigned long long* __restrict__ keys, const unsigned* __restrict__ vals,
+                                    const unsigned* __restrict__ imgs, const int* __restrict__ coff, const int* __restrict__ ooff, int B, int cand_cap, float up,
+                                    const DetImgParam* __restrict__ prm, float4* __restrict__ out, int* __restrict__ n_out)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= coff[B]) return;
+    const unsigned v = vals[j], b = imgs[v];
+    const int r = j - coff[b], n = coff[b + 1] - coff[b], limit = prm[b].max_segments;
+    if (r >= limit || keys[v] == ~0ull) return;
+    out[ooff[b] + r] = cand_coords(cand[(size_t)b * cand_cap + (v - coff[b])], up);
+    if (r + 1 == n || r + 1 == limit || keys[vals[j + 1]] == ~0ull) n_out[b] = r + 1;
 }
 
 // the Gaussian sampler's centre and weights of every output column (or row), as the detector computes them, on the host
@@ -510,12 +573,21 @@ void sampler_table(int n_out, double sigma, int* centre, double* weights)
 
 namespace {
 
-// what one image's run works at: sizes of the scaled image, thresholds, capacities
+// what one chunk's run works at: sizes of an image and of its scaled image, thresholds, capacities (per image), and the images in the chunk
 struct DetPlan {
-    int w = 0, h = 0, ch = 1, nw = 0, nh = 0, N = 0, M = 0, np = 0, min_reg = 2, cand_cap = 0, key_bits = 1;
+    int w = 0, h = 0, ch = 1, nw = 0, nh = 0, N = 0, M = 0, np = 0, min_reg = 2, cand_cap = 0, key_bits = 1, B = 1;
     double rho = 0.0, logNT = 0.0;
     float up = 1.0f;
+    int stack() const { return B * np; }        // pixels of the chunk's stack (at most 2^30)
+    bool same_group(const DetPlan& o) const { return w == o.w && h == o.h && ch == o.ch && nw == o.nw && nh == o.nh; }
 };
+// the pixel sort's keys reach 2 x the stack
+void plan_chunk(DetPlan& p, int B)
+{
+    p.B = B;
+    p.key_bits = 1;
+    while ((1ull << p.key_bits) <= 2ull * (unsigned long long)B * (unsigned long long)p.np) ++p.key_bits;
+}
 // the part of the plan that follows from the scaled size alone
 void plan_scaled(DetPlan& p, int N, int M)
 {
@@ -524,73 +596,102 @@ void plan_scaled(DetPlan& p, int N, int M)
     p.logNT = 5.0 * (log10((double)N) + log10((double)M)) / 2.0 + log10(11.0);
     p.min_reg = std::max(2, (int)(-p.logNT / log10(kAngTh / 180.0)));
     p.cand_cap = p.np / p.min_reg + 16;
-    p.key_bits = 1;
-    while ((1ull << p.key_bits) <= 2ull * (unsigned long long)p.np) ++p.key_bits;
+    plan_chunk(p, 1);
 }
 
-int det_reserve(l3d_ctx* c, const DetPlan& p, int max_segments, bool undist = false)
+// the scalars, ints: [0] changed, [1] changed (ignored rounds); from [16] per image: candidates | first packed candidate (B + 1) | first output slot (B + 1)
+constexpr int kScalHead = 16;
+inline int* det_n_cand(DetectBufs& d) { return d.scal.as<int>() + kScalHead; }
+inline size_t det_out_head(int B) { return ((size_t)B * 4 + 15) & ~(size_t)15; }      // d.out: the images' segment counts, then the segments
+
+// bytes of the device buffers one image of a chunk takes (what det_reserve sums up, with the buffers' slack): the chunk rule's memory term
+size_t det_image_bytes(const DetPlan& p, bool undist, size_t jpeg_blocks)
+{
+    const size_t np = (size_t)p.np, cc = (size_t)p.cand_cap;
+    size_t b = (size_t)p.w * p.h * p.ch * (undist ? 2 : 1) + (size_t)p.nw * p.nh * 4 + (size_t)p.N * p.nh * 8;
+    b += np * (8 + 8 + 8 + 2 + 1 + 8 + 8 + 8 + 4 * 4 + 4 + 4 + 2) + np * 16 /* the sorts' scratch */ + cc * (sizeof(DetCand) + 8 + 8 + 4 * 4 + 4 + 16);
+    b += jpeg_blocks * (128 + 128 + 64);
+    return b + b / 4;
+}
+
+int det_reserve(l3d_ctx* c, const DetPlan& p, size_t out_slots, bool undist = false)
 {
     hipStream_t st = c->stream;
     DetectBufs& d = c->det;
-    const int np = p.np, cand_cap = p.cand_cap;
-    size_t sort_bytes = 0, sort2_bytes = 0, scan_bytes = 0;
-    HIPCHK(c, sort_pairs_u32_u32(nullptr, sort_bytes, (const unsigned*)nullptr, (unsigned*)nullptr, (const unsigned*)nullptr, (unsigned*)nullptr, np, 0, p.key_bits, st));
-    HIPCHK(c, sort_pairs_u64_u32(nullptr, sort2_bytes, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, (const unsigned*)nullptr, (unsigned*)nullptr, cand_cap, 0, 64, st));
-    HIPCHK(c, exclusive_sum_int(nullptr, scan_bytes, (const int*)nullptr, (int*)nullptr, np + 1, st));
-    HIPCHK(c, d.pixels.reserve((size_t)p.w * p.h * p.ch));
-    if (undist) HIPCHK(c, d.undist.reserve((size_t)p.w * p.h * p.ch));
-    HIPCHK(c, d.grey.reserve((size_t)p.nw * p.nh * 4));
-    HIPCHK(c, d.aux.reserve((size_t)p.N * p.nh * 8));
-    HIPCHK(c, d.img.reserve((size_t)np * 8));
-    HIPCHK(c, d.mod.reserve((size_t)np * 8));
-    HIPCHK(c, d.ang.reserve((size_t)np * 8));
-    HIPCHK(c, d.bucket.reserve((size_t)np * 2));
-    HIPCHK(c, d.active.reserve((size_t)np));
-    HIPCHK(c, d.parent.reserve((size_t)np * 8));
-    HIPCHK(c, d.size.reserve((size_t)np * 8));
-    HIPCHK(c, d.count.reserve((size_t)np * 8 + 8));
-    HIPCHK(c, d.keys.reserve((size_t)np * 4));
-    HIPCHK(c, d.keys2.reserve((size_t)np * 4));
-    HIPCHK(c, d.vals.reserve((size_t)np * 4));
-    HIPCHK(c, d.vals2.reserve((size_t)np * 4));
-    HIPCHK(c, d.flag.reserve((size_t)(np + 1) * 4));
-    HIPCHK(c, d.pos.reserve((size_t)(np + 1) * 4));
-    HIPCHK(c, d.start.reserve((size_t)cand_cap * 4 + (size_t)np / 2 * 4));
-    HIPCHK(c, d.tmp.reserve(std::max(std::max(sort_bytes, sort2_bytes), scan_bytes)));
-    HIPCHK(c, d.cand.reserve((size_t)cand_cap * sizeof(DetCand)));
-    HIPCHK(c, d.ckeys.reserve((size_t)cand_cap * 8));
-    HIPCHK(c, d.ckeys2.reserve((size_t)cand_cap * 8));
-    HIPCHK(c, d.cvals.reserve((size_t)cand_cap * 4));
-    HIPCHK(c, d.cvals2.reserve((size_t)cand_cap * 4));
-    HIPCHK(c, d.out.reserve((size_t)std::max(1, std::min(max_segments, cand_cap)) * 16));
-    HIPCHK(c, d.scal.reserve(64));              // ints: [0] changed, [1] changed (ignored rounds), [2] candidates, [3] selected
+    const size_t B = (size_t)p.B, np = (size_t)p.stack(), cand_cap = (size_t)p.cand_cap * B;
+    size_t sort_bytes = 0, sort2_bytes = 0, sort3_bytes = 0, scan_bytes = 0;
+    HIPCHK(c, sort_pairs_u32_u32(nullptr, sort_bytes, (const unsigned*)nullptr, (unsigned*)nullptr, (const unsigned*)nullptr, (unsigned*)nullptr, (int)np, 0, p.key_bits, st));
+    HIPCHK(c, sort_pairs_u64_u32(nullptr, sort2_bytes, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, (const unsigned*)nullptr, (unsigned*)nullptr, (int)cand_cap, 0, 64, st));
+    HIPCHK(c, sort_pairs_u32_u32(nullptr, sort3_bytes, (const unsigned*)nullptr, (unsigned*)nullptr, (const unsigned*)nullptr, (unsigned*)nullptr, (int)cand_cap, 0, 32, st));
+    HIPCHK(c, exclusive_sum_int(nullptr, scan_bytes, (const int*)nullptr, (int*)nullptr, (int)np + 1, st));
+    HIPCHK(c, d.pixels.reserve(B * p.w * p.h * p.ch));
+    if (undist) HIPCHK(c, d.undist.reserve(B * p.w * p.h * p.ch));
+    HIPCHK(c, d.grey.reserve(B * p.nw * p.nh * 4));
+    HIPCHK(c, d.aux.reserve(B * p.N * p.nh * 8));
+    HIPCHK(c, d.img.reserve(np * 8));
+    HIPCHK(c, d.mod.reserve(np * 8));
+    HIPCHK(c, d.ang.reserve(np * 8));
+    HIPCHK(c, d.bucket.reserve(np * 2));
+    HIPCHK(c, d.active.reserve(np));
+    HIPCHK(c, d.parent.reserve(np * 8));
+    HIPCHK(c, d.size.reserve(np * 8));
+    HIPCHK(c, d.count.reserve(np * 8 + 8));
+    HIPCHK(c, d.keys.reserve(np * 4));
+    HIPCHK(c, d.keys2.reserve(np * 4));
+    HIPCHK(c, d.vals.reserve(np * 4));
+    HIPCHK(c, d.vals2.reserve(np * 4));
+    HIPCHK(c, d.flag.reserve((np + 1) * 4));
+    HIPCHK(c, d.pos.reserve((np + 1) * 4));
+    HIPCHK(c, d.start.reserve(cand_cap * 4 + np / 2 * 4));
+    HIPCHK(c, d.tmp.reserve(std::max(std::max(sort_bytes, sort2_bytes), std::max(sort3_bytes, scan_bytes))));
+    HIPCHK(c, d.cand.reserve(cand_cap * sizeof(DetCand)));
+    HIPCHK(c, d.ckeys.reserve(cand_cap * 8));
+    HIPCHK(c, d.ckeys2.reserve(cand_cap * 8));
+    HIPCHK(c, d.cvals.reserve(cand_cap * 4));
+    HIPCHK(c, d.cvals2.reserve(cand_cap * 4));
+    HIPCHK(c, d.cimg.reserve(cand_cap * 4));
+    HIPCHK(c, d.cimg2.reserve(cand_cap * 4));
+    HIPCHK(c, d.out.reserve(det_out_head(p.B) + std::max<size_t>(1, out_slots) * 16));
+    HIPCHK(c, d.prm.reserve(B * sizeof(DetImgParam)));
+    HIPCHK(c, d.scal.reserve(((size_t)kScalHead + 3 * B + 2) * 4));
     return L3D_OK;
 }
+// the flags and the images' candidate counters
+hipError_t det_zero_scalars(l3d_ctx* c, int B) { return hipMemsetAsync(c->det.scal.p, 0, ((size_t)kScalHead + B) * 4, c->stream); }
 
 // the camera of an undistortion: fx, fy finite and not zero; *active: a coefficient above L3D_EPS (commons.h:66, the drivers' condition) -- otherwise
 // nothing is launched and the pixels pass through
 constexpr double kDistEps = 1e-12;
-int check_camera(l3d_ctx* c, const DetCamera& cam, int w, int h, bool* active)
+int check_camera(const DetCamera& cam, int w, int h, bool* active, std::string& err)
 {
-    if (w > (1 << 24) || h > (1 << 24)) return fail(c, L3D_ERR_UNSUPPORTED, "undistort: image too large");      // 32 x a coordinate stays an int
-    if (!std::isfinite(cam.fx) || !std::isfinite(cam.fy) || cam.fx == 0.0 || cam.fy == 0.0) return fail(c, L3D_ERR_INVALID, "undistort: fx and fy must be finite and not zero");
+    if (w > (1 << 24) || h > (1 << 24)) { err = "undistort: image too large"; return L3D_ERR_UNSUPPORTED; }      // 32 x a coordinate stays an int
+    if (!std::isfinite(cam.fx) || !std::isfinite(cam.fy) || cam.fx == 0.0 || cam.fy == 0.0) { err = "undistort: fx and fy must be finite and not zero"; return L3D_ERR_INVALID; }
     *active = !(fabs(cam.k1) <= kDistEps && fabs(cam.k2) <= kDistEps);
     return L3D_OK;
 }
-void launch_undistort(l3d_ctx* c, int w, int h, int ch, const DetCamera& cam)
+// d.pixels -> d.undist, B images: each with its camera of `prm` (device; an image without one is copied), or all (B = 1) with `one` when prm is null
+void launch_undistort(l3d_ctx* c, int w, int h, int ch, int B, const DetCamera& one, const DetImgParam* prm)
 {
     DetectBufs& d = c->det;
     ProfScope ps(c, "k_det_undistort");
-    hipLaunchKernelGGL(k_det_undistort, dim3((w + kUndBx - 1) / kUndBx, (h + kUndBy - 1) / kUndBy), dim3(kUndBx, kUndBy), 0, c->stream, d.pixels.as<unsigned char>(), w, h, ch, cam, d.undist.as<unsigned char>());
+    hipLaunchKernelGGL(k_det_undistort, dim3((w + kUndBx - 1) / kUndBx, (h + kUndBy - 1) / kUndBy, B), dim3(kUndBx, kUndBy), 0, c->stream, d.pixels.as<unsigned char>(), w, h, ch, one, prm,
+                       d.undist.as<unsigned char>());
 }
 
-// ---- pixel stage: upload (pixels null: the image is in d.pixels already -- a decoded JPEG), undistortion (cam: null or inactive = none), rescale + grey,
-// the two sampler passes, gradient; leaves the scalars zeroed
-int det_pixel_stage(l3d_ctx* c, const DetPlan& p, const unsigned char* pixels, size_t stride, const DetCamera* cam = nullptr)
+// image b of the chunk: host pixels into its slot of d.pixels
+hipError_t det_upload(l3d_ctx* c, const DetPlan& p, int b, const unsigned char* pixels, size_t stride)
+{
+    const size_t row = (size_t)p.w * p.ch;
+    return hipMemcpy2DAsync(c->det.pixels.as<unsigned char>() + (size_t)b * row * p.h, row, pixels, stride, row, (size_t)p.h, hipMemcpyHostToDevice, c->stream);
+}
+
+// ---- pixel stage on the chunk's images in d.pixels (uploaded, or decoded JPEG): undistortion (undist: some image has a camera, d.prm says which),
+// rescale + grey, the two sampler passes, gradient -- one launch each, the image in blockIdx.z; leaves the scalars zeroed
+int det_pixel_stage(l3d_ctx* c, const DetPlan& p, bool undist = false)
 {
     hipStream_t st = c->stream;
     DetectBufs& d = c->det;
-    const int w = p.w, h = p.h, ch = p.ch, nw = p.nw, nh = p.nh, N = p.N, M = p.M;
+    const int w = p.w, h = p.h, ch = p.ch, nw = p.nw, nh = p.nh, N = p.N, M = p.M, B = p.B;
     if (d.tab_w != nw || d.tab_h != nh) {
         std::vector<int> centre((size_t)N + M);
         std::vector<double> weights(((size_t)N + M) * kTaps);
@@ -605,33 +706,34 @@ int det_pixel_stage(l3d_ctx* c, const DetPlan& p, const unsigned char* pixels, s
     }
     const double* kw = d.ktab.as<double>();
     const int* kc = reinterpret_cast<const int*>(static_cast<const char*>(d.ktab.p) + ((size_t)N + M) * kTaps * 8);
-    if (pixels) HIPCHK(c, hipMemcpy2DAsync(d.pixels.p, (size_t)w * ch, pixels, stride, (size_t)w * ch, (size_t)h, hipMemcpyHostToDevice, st));
     const dim3 b256(256);
-    const unsigned char* image = d.pixels.as<unsigned char>();          // whichever buffer holds the image k_det_grey reads
-    if (cam) { launch_undistort(c, w, h, ch, *cam); image = d.undist.as<unsigned char>(); }
-    { ProfScope ps(c, "k_det_grey"); hipLaunchKernelGGL(k_det_grey, dim3((nw + 255) / 256, nh), b256, 0, st, image, w, h, ch, nw, nh, d.grey.as<float>()); }
-    { ProfScope ps(c, "k_det_gauss_x"); hipLaunchKernelGGL(k_det_gauss_x, dim3((N + 63) / 64, (nh + 3) / 4), dim3(64, 4), 0, st, d.grey.as<float>(), nw, nh, d.aux.as<double>(), N, kc, kw); }
-    { ProfScope ps(c, "k_det_gauss_y"); hipLaunchKernelGGL(k_det_gauss_y, dim3((N + 63) / 64, (M + kYRows - 1) / kYRows), dim3(64, 4), 0, st, d.aux.as<double>(), N, nh, d.img.as<double>(), M, kc + N, kw + (size_t)N * kTaps); }
-    { ProfScope ps(c, "k_det_grad"); hipLaunchKernelGGL(k_det_grad, dim3((N + 255) / 256, M), b256, 0, st, d.img.as<double>(), N, M, p.rho, d.mod.as<double>(), d.ang.as<double>(), d.bucket.as<uchar2>(), d.active.as<unsigned char>()); }
-    HIPCHK(c, hipMemsetAsync(d.scal.p, 0, 64, st));
+    const unsigned char* image = d.pixels.as<unsigned char>();          // whichever buffer holds the images k_det_grey reads
+    if (undist) { launch_undistort(c, w, h, ch, B, DetCamera{ 1.0, 1.0, 0.0, 0.0, 0.0, 0.0 }, d.prm.as<DetImgParam>()); image = d.undist.as<unsigned char>(); }
+    { ProfScope ps(c, "k_det_grey"); hipLaunchKernelGGL(k_det_grey, dim3((nw + 255) / 256, nh, B), b256, 0, st, image, w, h, ch, nw, nh, d.grey.as<float>()); }
+    { ProfScope ps(c, "k_det_gauss_x"); hipLaunchKernelGGL(k_det_gauss_x, dim3((N + 63) / 64, (nh + 3) / 4, B), dim3(64, 4), 0, st, d.grey.as<float>(), nw, nh, d.aux.as<double>(), N, kc, kw); }
+    { ProfScope ps(c, "k_det_gauss_y"); hipLaunchKernelGGL(k_det_gauss_y, dim3((N + 63) / 64, (M + kYRows - 1) / kYRows, B), dim3(64, 4), 0, st, d.aux.as<double>(), N, nh, d.img.as<double>(), M, kc + N, kw + (size_t)N * kTaps); }
+    { ProfScope ps(c, "k_det_grad"); hipLaunchKernelGGL(k_det_grad, dim3((N + 255) / 256, M, B), b256, 0, st, d.img.as<double>(), N, M, p.rho, d.mod.as<double>(), d.ang.as<double>(), d.bucket.as<uchar2>(), d.active.as<unsigned char>()); }
+    HIPCHK(c, det_zero_scalars(c, B));
     return L3D_OK;
 }
 
 // ---- labelling of the active pixels to the fixed point, component sizes, vote.  Between two compressions every tree is a star, and a
 // hooking round that changes anything turns at least one root into a child: at most np - 1 rounds change something, three rounds a look.
+// All images of the chunk share the grids and the flag: an image that has reached its fixed point sees further rounds, which change nothing in it
+// (its labels are component minima already); the flag only ends the loop, after as many looks as the slowest image needs.
 int det_label(l3d_ctx* c, const DetPlan& p)
 {
     hipStream_t st = c->stream;
     DetectBufs& d = c->det;
-    const int N = p.N, M = p.M, np = p.np;
+    const int N = p.N, M = p.M, np = p.stack();
     int* scal = d.scal.as<int>();
-    const dim3 b256(256), gnp((np + 255) / 256), g2np((2 * np + 255) / 256);
+    const dim3 b256(256), gnp((np + 255) / 256), g2np((unsigned)((2ll * np + 255) / 256));
     { ProfScope ps(c, "k_det_label_init"); hipLaunchKernelGGL(k_det_label_init, gnp, b256, 0, st, d.active.as<unsigned char>(), np, d.parent.as<int>()); }
-    const int max_looks = np / 3 + 2;
+    const int max_looks = p.np / 3 + 2;
     for (int it = 0; ; ++it) {
         HIPCHK(c, hipMemsetAsync(scal, 0, 4, st));
         for (int r = 0; r < 3; ++r) {                       // a few hooking rounds per look at the flag
-            { ProfScope ps(c, "k_det_label_hook"); hipLaunchKernelGGL(k_det_label_hook, dim3((N + 255) / 256, M, 2), b256, 0, st, d.bucket.as<uchar2>(), d.active.as<unsigned char>(), N, M, d.parent.as<int>(), scal + (r == 2 ? 0 : 1)); }
+            { ProfScope ps(c, "k_det_label_hook"); hipLaunchKernelGGL(k_det_label_hook, dim3((N + 255) / 256, M, 2 * p.B), b256, 0, st, d.bucket.as<uchar2>(), d.active.as<unsigned char>(), N, M, d.parent.as<int>(), scal + (r == 2 ? 0 : 1)); }
             { ProfScope ps(c, "k_det_label_compress"); hipLaunchKernelGGL(k_det_label_compress, g2np, b256, 0, st, d.parent.as<int>(), 2 * np); }
         }
         int changed = 0;
@@ -652,13 +754,13 @@ int det_regions(l3d_ctx* c, const DetPlan& p, l3d_detect_region_record* trace)
 {
     hipStream_t st = c->stream;
     DetectBufs& d = c->det;
-    const int N = p.N, M = p.M, np = p.np;
+    const int N = p.N, M = p.M, np = p.stack();
     const dim3 b256(256), gnp((np + 255) / 256), gnp1((np + 256) / 256);
     { ProfScope ps(c, "det_sort_pixels"); size_t tb = d.tmp.cap; HIPCHK(c, sort_pairs_u32_u32(d.tmp.p, tb, d.keys.as<unsigned>(), d.keys2.as<unsigned>(), d.vals.as<unsigned>(), d.vals2.as<unsigned>(), np, 0, p.key_bits, st)); }
     { ProfScope ps(c, "k_det_heads"); hipLaunchKernelGGL(k_det_heads, gnp1, b256, 0, st, d.keys2.as<unsigned>(), d.count.as<int>(), np, p.min_reg, d.flag.as<int>()); }
     { size_t tb = d.tmp.cap; HIPCHK(c, exclusive_sum_int(d.tmp.p, tb, d.flag.as<int>(), d.pos.as<int>(), np + 1, st)); }
     { ProfScope ps(c, "k_det_starts"); hipLaunchKernelGGL(k_det_starts, gnp, b256, 0, st, d.flag.as<int>(), d.pos.as<int>(), np, d.start.as<int>()); }
-    { ProfScope ps(c, "k_det_region"); hipLaunchKernelGGL(k_det_region, dim3(1024), b256, 0, st, N, M, p.logNT, p.min_reg, d.mod.as<double>(), d.ang.as<double>(), d.keys2.as<unsigned>(), d.vals2.as<unsigned>(), d.count.as<int>(), d.start.as<int>(), d.pos.as<int>() + np, d.active.as<unsigned char>(), d.cand.as<DetCand>(), d.scal.as<int>() + 2, p.cand_cap, trace); }
+    { ProfScope ps(c, "k_det_region"); hipLaunchKernelGGL(k_det_region, dim3(1024), b256, 0, st, N, M, p.logNT, p.min_reg, d.mod.as<double>(), d.ang.as<double>(), d.keys2.as<unsigned>(), d.vals2.as<unsigned>(), d.count.as<int>(), d.start.as<int>(), d.pos.as<int>() + np, d.active.as<unsigned char>(), d.cand.as<DetCand>(), det_n_cand(d), p.cand_cap, trace); }
     return L3D_OK;
 }
 
@@ -669,14 +771,17 @@ __global__ void k_det_nfa_test(const int* __restrict__ n, const int* __restrict_
 }
 
 // have_image: host pixels were given, or the image will be decoded on the device
-int plan_image(l3d_ctx* c, DetPlan& p, bool have_image, int w, int h, int ch, size_t stride, int nw, int nh)
+int plan_image(DetPlan& p, bool have_image, int w, int h, int ch, size_t stride, int nw, int nh, std::string& err)
 {
-    if (!have_image || w < 8 || h < 8 || (ch != 1 && ch != 3) || stride < (size_t)w * ch) return fail(c, L3D_ERR_INVALID, "detect_segments: needs an image of at least 8x8 with 1 or 3 channels and a row stride of at least width x channels");
+    if (!have_image || w < 8 || h < 8 || (ch != 1 && ch != 3) || stride < (size_t)w * ch) {
+        err = "detect_segments: needs an image of at least 8x8 with 1 or 3 channels and a row stride of at least width x channels";
+        return L3D_ERR_INVALID;
+    }
     if (nw <= 0 || nh <= 0) { nw = w; nh = h; }
-    if (nw < 8 || nh < 8) return fail(c, L3D_ERR_INVALID, "detect_segments: rescaled size below 8x8");
+    if (nw < 8 || nh < 8) { err = "detect_segments: rescaled size below 8x8"; return L3D_ERR_INVALID; }
     const int N = (int)ceil(nw * kScale), M = (int)ceil(nh * kScale);
     const long long np_ll = (long long)N * M;
-    if (np_ll > (1ll << 30) || (long long)w * h * ch > (1ll << 31)) return fail(c, L3D_ERR_UNSUPPORTED, "detect_segments: image too large");
+    if (np_ll > (1ll << 30) || (long long)w * h * ch > (1ll << 31)) { err = "detect_segments: image too large"; return L3D_ERR_UNSUPPORTED; }
     p.w = w; p.h = h; p.ch = ch; p.nw = nw; p.nh = nh;
     plan_scaled(p, N, M);
     p.up = 1.0f;
@@ -684,59 +789,210 @@ int plan_image(l3d_ctx* c, DetPlan& p, bool have_image, int w, int h, int ch, si
     return L3D_OK;
 }
 
-// the detector on one image: `pixels` (host), or with jpeg_bytes the file whose parsed headers are `frame`, decoded on the device into d.pixels
-int detect_core(l3d_ctx* c, const unsigned char* pixels, int w, int h, int ch, size_t stride, int nw, int nh, float min_length, int max_segments,
-                std::vector<float>& out, const DetCamera* cam, const unsigned char* jpeg_bytes = nullptr, size_t jpeg_n = 0, const JpegFrame* frame = nullptr)
+// one image of a chunk: where it comes from, what varies inside a chunk, where its segments go
+struct DetItem {
+    const unsigned char* pixels = nullptr;      // host pixels, or with null the file `jpeg` staged at jpeg->stage_at
+    size_t stride = 0;
+    const JpegStaged* jpeg = nullptr;
+    DetImgParam prm;
+    std::vector<float>* out = nullptr;
+};
+
+// the detector on the B images of one chunk (p.B): every stage enqueued once; the host waits for the labelling's flag, for the candidate counts
+// and for the segments
+int detect_chunk(l3d_ctx* c, const DetPlan& p, const DetItem* items)
 {
-    if (max_segments < 0) return fail(c, L3D_ERR_INVALID, "detect_segments: negative max_segments");
-    DetPlan plan;
-    if (int rc = plan_image(c, plan, frame != nullptr || pixels != nullptr, w, h, ch, stride, nw, nh)) return rc;
-    bool undist = false;
-    if (cam) { if (int rc = check_camera(c, *cam, w, h, &undist)) return rc; }
-    if (!undist) cam = nullptr;
-    HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     DetectBufs& d = c->det;
-    if (int rc = det_reserve(c, plan, max_segments, undist)) return rc;
-    int* scal = d.scal.as<int>();
-    const int cand_cap = plan.cand_cap;
-    const float up = plan.up;
-    const dim3 b256(256);
-    if (frame) { if (int rc = jpeg_decode_to_pixels(c, jpeg_bytes, jpeg_n, *frame)) return rc; }
-    if (int rc = det_pixel_stage(c, plan, frame ? nullptr : pixels, stride, cam)) return rc;
+    const int B = p.B, cand_cap = p.cand_cap;
+    bool undist = false, jpeg = false;
+    size_t out_slots = 0;
+    std::vector<DetImgParam> prm((size_t)B);
+    for (int b = 0; b < B; ++b) {
+        prm[b] = items[b].prm;
+        undist = undist || prm[b].cam_on;
+        jpeg = jpeg || !items[b].pixels;
+        out_slots += (size_t)std::min(prm[b].max_segments, cand_cap);
+    }
+    if (int rc = det_reserve(c, p, out_slots, undist)) return rc;
+    if (jpeg) {
+        std::vector<const JpegStaged*> files((size_t)B, nullptr);
+        for (int b = 0; b < B; ++b) if (!items[b].pixels) files[b] = items[b].jpeg;
+        if (int rc = jpeg_staged_to_pixels(c, files.data(), B)) return rc;
+    }
+    for (int b = 0; b < B; ++b) if (items[b].pixels) HIPCHK(c, det_upload(c, p, b, items[b].pixels, items[b].stride));
+    // (from pageable memory on purpose: a few dozen bytes go faster through the runtime's staging than as a DMA from pinned memory -- measured, 0.03 ms per call)
+    HIPCHK(c, hipMemcpyAsync(d.prm.p, prm.data(), (size_t)B * sizeof(DetImgParam), hipMemcpyHostToDevice, st));
+    if (int rc = det_pixel_stage(c, p, undist)) return rc;
 
     // ---- rounds: label, vote, sort, regions
     for (int round = 0; round < kRounds; ++round) {
-        if (int rc = det_label(c, plan)) return rc;
-        if (int rc = det_regions(c, plan, nullptr)) return rc;
+        if (int rc = det_label(c, p)) return rc;
+        if (int rc = det_regions(c, p, nullptr)) return rc;
     }
 
     // ---- selection
-    int n_cand = 0;
-    HIPCHK(c, hipMemcpyAsync(&n_cand, scal + 2, 4, hipMemcpyDeviceToHost, st));
+    int* n_cand_d = det_n_cand(d);
+    int *coff = n_cand_d + B, *ooff = coff + B + 1, *n_out_d = d.out.as<int>();
+    const DetImgParam* prm_d = d.prm.as<DetImgParam>();
+    float4* out_d = reinterpret_cast<float4*>(static_cast<char*>(d.out.p) + det_out_head(B));
+    const dim3 b256(256);
+    { ProfScope ps(c, "k_det_select_plan"); hipLaunchKernelGGL(k_det_select_plan, dim3(1), dim3(64), 0, st, n_cand_d, prm_d, B, cand_cap, coff, ooff, n_out_d); }
+    std::vector<int> n_cand((size_t)B, 0);
+    HIPCHK(c, hipMemcpyAsync(n_cand.data(), n_cand_d, (size_t)B * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    n_cand = std::min(n_cand, cand_cap);
-    if (n_cand <= 0 || max_segments == 0) return L3D_OK;
-    const dim3 gc((n_cand + 255) / 256);
-    { ProfScope ps(c, "k_det_select_keys"); hipLaunchKernelGGL(k_det_select_keys, gc, b256, 0, st, d.cand.as<DetCand>(), n_cand, up, min_length, d.ckeys.as<unsigned long long>(), d.cvals.as<unsigned>()); }
-    { size_t tb = d.tmp.cap; HIPCHK(c, sort_pairs_u64_u32(d.tmp.p, tb, d.ckeys.as<unsigned long long>(), d.ckeys2.as<unsigned long long>(), d.cvals.as<unsigned>(), d.cvals2.as<unsigned>(), n_cand, 0, 64, st)); }
-    { ProfScope ps(c, "k_det_select_gather"); hipLaunchKernelGGL(k_det_select_gather, gc, b256, 0, st, d.cand.as<DetCand>(), d.ckeys2.as<unsigned long long>(), d.cvals2.as<unsigned>(), n_cand, max_segments, up, d.out.as<float4>(), scal + 3); }
-    int n_out = 0;
-    HIPCHK(c, hipMemcpyAsync(&n_out, scal + 3, 4, hipMemcpyDeviceToHost, st));
+    int total = 0, most = 0;
+    size_t slots = 0;
+    std::vector<size_t> slot0((size_t)B + 1, 0);
+    for (int b = 0; b < B; ++b) {
+        n_cand[b] = std::max(0, std::min(n_cand[b], cand_cap));
+        total += n_cand[b]; most = std::max(most, n_cand[b]);
+        slot0[b] = slots;
+        slots += (size_t)std::min(n_cand[b], std::max(0, prm[b].max_segments));
+    }
+    slot0[B] = slots;
+    if (total <= 0 || slots == 0) return L3D_OK;
+    const dim3 gc((total + 255) / 256);
+    { ProfScope ps(c, "k_det_select_keys"); hipLaunchKernelGGL(k_det_select_keys, dim3((most + 255) / 256, B), b256, 0, st, d.cand.as<DetCand>(), coff, cand_cap, p.up, prm_d, d.ckeys.as<unsigned long long>(), d.cvals.as<unsigned>(), d.cimg.as<unsigned>()); }
+    { size_t tb = d.tmp.cap; HIPCHK(c, sort_pairs_u64_u32(d.tmp.p, tb, d.ckeys.as<unsigned long long>(), d.ckeys2.as<unsigned long long>(), d.cvals.as<unsigned>(), d.cvals2.as<unsigned>(), total, 0, 64, st)); }
+    const unsigned* order = d.cvals2.as<unsigned>();
+    if (B > 1) {            // the images apart again, each keeping the order of its keys (ckeys2 and cvals are free: scratch of the second sort)
+        int bits = 1;
+        while ((1 << bits) < B) ++bits;
+        { ProfScope ps(c, "k_det_select_image"); hipLaunchKernelGGL(k_det_select_image, gc, b256, 0, st, d.cvals2.as<unsigned>(), d.cimg.as<unsigned>(), total, d.cimg2.as<unsigned>()); }
+        { size_t tb = d.tmp.cap; HIPCHK(c, sort_pairs_u32_u32(d.tmp.p, tb, d.cimg2.as<unsigned>(), d.ckeys2.as<unsigned>(), d.cvals2.as<unsigned>(), d.cvals.as<unsigned>(), total, 0, bits, st)); }
+        order = d.cvals.as<unsigned>();
+    }
+    { ProfScope ps(c, "k_det_select_gather"); hipLaunchKernelGGL(k_det_select_gather, gc, b256, 0, st, d.cand.as<DetCand>(), d.ckeys.as<unsigned long long>(), order, d.cimg.as<unsigned>(), coff, ooff, B, cand_cap, p.up, prm_d, out_d, n_out_d); }
+    const size_t head = det_out_head(B);
+    std::vector<unsigned char> host(head + slots * 16);
+    HIPCHK(c, hipMemcpyAsync(host.data(), d.out.p, host.size(), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    n_out = std::max(0, std::min(n_out, std::min(n_cand, max_segments)));
-    out.resize((size_t)n_out * 4);
-    if (n_out) HIPCHK(c, hipMemcpy(out.data(), d.out.p, (size_t)n_out * 16, hipMemcpyDeviceToHost));
+    const int* n_out = reinterpret_cast<const int*>(host.data());
+    for (int b = 0; b < B; ++b) {
+        const int n = std::max(0, std::min(n_out[b], (int)(slot0[b + 1] - slot0[b])));
+        items[b].out->resize((size_t)n * 4);
+        if (n) memcpy(items[b].out->data(), host.data() + head + slot0[b] * 16, (size_t)n * 16);
+    }
     return L3D_OK;
 }
+
+// images per chunk of a group of n: the option, the index widths (the stack within 2^30 pixels), and half of the HBM that is free or held by the
+// detector's own buffers already
+int chunk_images(l3d_ctx* c, const DetPlan& p, int n, bool undist, size_t jpeg_blocks)
+{
+    long long lim = std::min<long long>(n, 1024);
+    lim = std::min(lim, std::max(1ll, (1ll << 30) / p.np));
+    if (c->opt.det_batch_images > 0) lim = std::min<long long>(lim, c->opt.det_batch_images);
+    if (lim > 1) {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return 1; }
+        const size_t budget = (free_b + c->det.held()) / 2;
+        lim = std::min<long long>(lim, std::max<size_t>(1, budget / det_image_bytes(p, undist, jpeg_blocks)));
+    }
+    return (int)lim;
+}
 }  // namespace
+
+int detect_segments_batch(l3d_ctx* c, const DetEntry* e, int n, std::vector<std::vector<float>>& out, std::vector<int>& status, std::vector<std::string>& message)
+{
+    out.assign((size_t)std::max(0, n), std::vector<float>());
+    status.assign((size_t)std::max(0, n), L3D_OK);
+    message.assign((size_t)std::max(0, n), std::string());
+    if (!c) return L3D_ERR_INVALID;
+    if (n < 0 || (n > 0 && !e)) return fail(c, L3D_ERR_INVALID, "detect_segments_batch: null argument");
+    // ---- per entry, in order, on the caller's thread: headers, plan, camera.  An entry refused here fails alone
+    struct Work { DetPlan plan; DetImgParam prm; JpegStaged file; bool todo = false, done = false; };
+    std::vector<Work> work((size_t)n);
+    std::vector<JpegFrame> frames((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        Work& k = work[i];
+        const DetEntry& en = e[i];
+        int w = en.width, h = en.height, ch = en.channels;
+        size_t stride = en.row_stride;
+        if (!en.pixels && en.jpeg) {
+            if ((status[i] = jpeg_parse(en.jpeg, en.jpeg_bytes, frames[i], message[i])) != L3D_OK) continue;
+            w = frames[i].width; h = frames[i].height; ch = frames[i].ncomp; stride = (size_t)w * ch;
+            k.file.bytes = en.jpeg; k.file.n = en.jpeg_bytes; k.file.f = &frames[i];
+        }
+        if (en.max_segments < 0) { status[i] = L3D_ERR_INVALID; message[i] = "detect_segments: negative max_segments"; continue; }
+        if ((status[i] = plan_image(k.plan, en.pixels != nullptr || en.jpeg != nullptr, w, h, ch, stride, en.new_width, en.new_height, message[i])) != L3D_OK) continue;
+        bool undist = false;
+        if (en.cam) { if ((status[i] = check_camera(*en.cam, w, h, &undist, message[i])) != L3D_OK) continue; }
+        k.prm.cam = undist ? *en.cam : DetCamera{ 1.0, 1.0, 0.0, 0.0, 0.0, 0.0 };
+        k.prm.cam_on = undist; k.prm.min_length = en.min_length; k.prm.max_segments = en.max_segments; k.prm.pad = 0;
+        k.todo = true;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    // ---- groups of equal plans in the order of their first entries; a group in chunks
+    int rc = L3D_OK;
+    for (int first = 0; first < n && rc == L3D_OK; ++first) {
+        if (!work[first].todo) continue;
+        std::vector<int> group;
+        bool undist = false;
+        size_t blocks = 0;
+        for (int i = first; i < n; ++i)
+            if (work[i].todo && work[i].plan.same_group(work[first].plan)) {
+                group.push_back(i); work[i].todo = false;
+                undist = undist || work[i].prm.cam_on;
+                if (work[i].file.f) blocks = std::max(blocks, work[i].file.f->n_blocks);
+            }
+        const int per = chunk_images(c, work[first].plan, (int)group.size(), undist, blocks);
+        for (size_t at = 0; at < group.size() && rc == L3D_OK; at += (size_t)per) {
+            const size_t end = std::min(group.size(), at + (size_t)per);
+            // the chunk's files: entropy decoding on the host threads, each into its own slice of the staging buffer; a file that fails leaves the chunk
+            std::vector<JpegStaged*> files;
+            for (size_t g = at; g < end; ++g) if (work[group[g]].file.f) files.push_back(&work[group[g]].file);
+            if (!files.empty()) rc = jpeg_stage_files(c, files.data(), (int)files.size());
+            if (rc != L3D_OK) break;
+            std::vector<DetItem> items;
+            std::vector<int> entry;
+            for (size_t g = at; g < end; ++g) {
+                const int i = group[g];
+                Work& k = work[i];
+                if (k.file.f && k.file.status != L3D_OK) { status[i] = k.file.status; message[i] = k.file.err; continue; }
+                DetItem it;
+                it.pixels = k.file.f ? nullptr : e[i].pixels; it.stride = e[i].row_stride; it.jpeg = k.file.f ? &k.file : nullptr; it.prm = k.prm; it.out = &out[i];
+                items.push_back(it);
+                entry.push_back(i);
+            }
+            if (items.empty()) continue;
+            DetPlan plan = work[first].plan;
+            plan_chunk(plan, (int)items.size());
+            rc = detect_chunk(c, plan, items.data());
+            if (rc == L3D_OK) for (int i : entry) work[i].done = true;
+        }
+        if (rc != L3D_OK) {         // a device failure ends the call: what was not finished carries its code
+            std::string why;
+            { std::lock_guard<std::mutex> lk(c->err_mu); why = c->err; }
+            for (int i : group) if (status[i] == L3D_OK && !work[i].done) { out[i].clear(); status[i] = rc; message[i] = why; }
+            for (int i = 0; i < n; ++i) if (work[i].todo) { status[i] = rc; message[i] = why; }
+        }
+    }
+    return rc;
+}
+
+// one image: a batch of one, its outcome the call's
+static int detect_one(l3d_ctx* c, const DetEntry& en, std::vector<float>& out)
+{
+    std::vector<std::vector<float>> outs;
+    std::vector<int> status;
+    std::vector<std::string> message;
+    if (int rc = detect_segments_batch(c, &en, 1, outs, status, message)) return rc;
+    if (status[0] != L3D_OK) return fail(c, status[0], message[0]);
+    out.swap(outs[0]);
+    return L3D_OK;
+}
 
 int detect_segments(l3d_ctx* c, const unsigned char* pixels, int w, int h, int ch, size_t stride, int nw, int nh, float min_length, int max_segments,
                     std::vector<float>& out, const DetCamera* cam)
 {
     out.clear();
     if (!c) return L3D_ERR_INVALID;
-    return detect_core(c, pixels, w, h, ch, stride, nw, nh, min_length, max_segments, out, cam);
+    DetEntry en;
+    en.pixels = pixels; en.width = w; en.height = h; en.channels = ch; en.row_stride = stride;
+    en.new_width = nw; en.new_height = nh; en.min_length = min_length; en.max_segments = max_segments; en.cam = cam;
+    return detect_one(c, en, out);
 }
 
 int detect_segments_jpeg(l3d_ctx* c, const unsigned char* bytes, size_t n, int nw, int nh, float min_length, int max_segments, std::vector<float>& out,
@@ -745,10 +1001,10 @@ int detect_segments_jpeg(l3d_ctx* c, const unsigned char* bytes, size_t n, int n
     out.clear();
     if (!c) return L3D_ERR_INVALID;
     if (!bytes) return fail(c, L3D_ERR_INVALID, "detect_segments_jpeg: null argument");
-    JpegFrame f;
-    std::string err;
-    if (int rc = jpeg_parse(bytes, n, f, err)) return fail(c, rc, err);
-    return detect_core(c, nullptr, f.width, f.height, f.ncomp, (size_t)f.width * f.ncomp, nw, nh, min_length, max_segments, out, cam, bytes, n, &f);
+    DetEntry en;
+    en.jpeg = bytes; en.jpeg_bytes = n;
+    en.new_width = nw; en.new_height = nh; en.min_length = min_length; en.max_segments = max_segments; en.cam = cam;
+    return detect_one(c, en, out);
 }
 
 // host in, host out: upload, k_det_undistort, download (the detector's two image buffers)
@@ -759,7 +1015,7 @@ int undistort_image(l3d_ctx* c, const unsigned char* pixels, int w, int h, int c
         return fail(c, L3D_ERR_INVALID, "undistort: needs an image of at least 1x1 with 1 or 3 channels and row strides of at least width x channels");
     if ((long long)w * h * ch > (1ll << 31)) return fail(c, L3D_ERR_UNSUPPORTED, "undistort: image too large");
     bool active = false;
-    if (int rc = check_camera(c, cam, w, h, &active)) return rc;
+    { std::string err; if (int rc = check_camera(cam, w, h, &active, err)) return fail(c, rc, err); }
     const size_t row = (size_t)w * ch;
     if (!active) {
         if (out != pixels || out_stride != stride)
@@ -771,7 +1027,7 @@ int undistort_image(l3d_ctx* c, const unsigned char* pixels, int w, int h, int c
     HIPCHK(c, d.pixels.reserve(row * h));
     HIPCHK(c, d.undist.reserve(row * h));
     HIPCHK(c, hipMemcpy2DAsync(d.pixels.p, row, pixels, stride, row, (size_t)h, hipMemcpyHostToDevice, c->stream));
-    launch_undistort(c, w, h, ch, cam);
+    launch_undistort(c, w, h, ch, 1, cam, nullptr);
     HIPCHK(c, hipMemcpy2DAsync(out, out_stride, d.undist.p, row, row, (size_t)h, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return L3D_OK;
@@ -833,6 +1089,38 @@ int l3d_detect_segments_jpeg(l3d_ctx* c, const unsigned char* bytes, size_t n, i
     return rc != L3D_OK ? rc : segments_to_c(c, out, segments, n_segments);
 }
 
+int l3d_detect_segments_batch(l3d_ctx* c, const l3d_detect_entry* e, int n, float** segments, int* offsets, int* status)
+{
+    if (!c || !segments || !offsets || !status || n < 0 || (n > 0 && !e)) return L3D_ERR_INVALID;
+    *segments = nullptr;
+    std::vector<l3d::DetEntry> entries((size_t)n);
+    std::vector<l3d::DetCamera> cams((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        l3d::DetEntry& d = entries[i];
+        d.pixels = e[i].pixels; d.width = e[i].width; d.height = e[i].height; d.channels = e[i].channels; d.row_stride = e[i].row_stride;
+        d.jpeg = e[i].jpeg; d.jpeg_bytes = e[i].jpeg_bytes;
+        d.new_width = e[i].new_width; d.new_height = e[i].new_height; d.min_length = e[i].min_length; d.max_segments = e[i].max_segments;
+        if (const double* k = e[i].camera) { cams[i] = l3d::DetCamera{ k[0], k[1], k[2], k[3], k[4], k[5] }; d.cam = &cams[i]; }
+    }
+    std::vector<std::vector<float>> out;
+    std::vector<int> st;
+    std::vector<std::string> msg;
+    const int rc = l3d::detect_segments_batch(c, entries.data(), n, out, st, msg);
+    std::string lines;
+    std::vector<float> all;
+    offsets[0] = 0;
+    for (int i = 0; i < n; ++i) {
+        status[i] = st[i];
+        if (st[i] != L3D_OK) { out[i].clear(); lines += (lines.empty() ? "entry " : "\nentry ") + std::to_string(i) + ": " + msg[i]; }
+        all.insert(all.end(), out[i].begin(), out[i].end());
+        offsets[i + 1] = (int)(all.size() / 4);
+    }
+    if (!lines.empty()) l3d::fail(c, rc, lines);
+    int total = 0;
+    const int rc2 = segments_to_c(c, all, segments, &total);
+    return rc != L3D_OK ? rc : rc2;
+}
+
 // ---- the stages on their own, for the tests: the functions above (the same kernels and launch shapes as l3d_detect_segments), results copied out
 int l3d_test_detect_pixel_stage(l3d_ctx* c, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, int new_width, int new_height,
                                 float* grey, double* img, double* mod, double* ang, unsigned char* bucket, int* N, int* M)
@@ -840,10 +1128,11 @@ int l3d_test_detect_pixel_stage(l3d_ctx* c, const unsigned char* pixels, int wid
     using namespace l3d;
     if (!c || !grey || !img || !mod || !ang || !bucket || !N || !M) return L3D_ERR_INVALID;
     DetPlan p;
-    if (int rc = plan_image(c, p, pixels != nullptr, width, height, channels, row_stride, new_width, new_height)) return rc;
+    { std::string err; if (int rc = plan_image(p, pixels != nullptr, width, height, channels, row_stride, new_width, new_height, err)) return fail(c, rc, err); }
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = det_reserve(c, p, 0)) return rc;
-    if (int rc = det_pixel_stage(c, p, pixels, row_stride)) return rc;
+    HIPCHK(c, det_upload(c, p, 0, pixels, row_stride));
+    if (int rc = det_pixel_stage(c, p)) return rc;
     DetectBufs& d = c->det;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(grey, d.grey.p, (size_t)p.nw * p.nh * 4, hipMemcpyDeviceToHost));
@@ -867,7 +1156,7 @@ int l3d_test_detect_label(l3d_ctx* c, const unsigned char* bucket, const unsigne
     DetectBufs& d = c->det;
     HIPCHK(c, hipMemcpy(d.bucket.p, bucket, (size_t)p.np * 2, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(d.active.p, active, (size_t)p.np, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemsetAsync(d.scal.p, 0, 64, c->stream));
+    HIPCHK(c, det_zero_scalars(c, 1));
     if (int rc = det_label(c, p)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(parent, d.parent.p, (size_t)p.np * 8, hipMemcpyDeviceToHost));
@@ -911,7 +1200,7 @@ int l3d_test_detect_regions(l3d_ctx* c, int N, int M, const double* mod, const d
     step(hipMemcpy(d.count.p, count.data(), (size_t)np * 8 + 8, hipMemcpyHostToDevice));
     step(hipMemset(d.active.p, 1, (size_t)np));
     step(hipMemset(trace.p, 0, trace_bytes));
-    step(hipMemsetAsync(d.scal.p, 0, 64, c->stream));
+    step(det_zero_scalars(c, 1));
     if (rc == L3D_OK) rc = det_regions(c, p, trace.as<l3d_detect_region_record>());
     if (rc == L3D_OK) step(hipStreamSynchronize(c->stream));
     if (rc == L3D_OK) step(hipMemcpy(&n, d.pos.as<int>() + np, 4, hipMemcpyDeviceToHost));

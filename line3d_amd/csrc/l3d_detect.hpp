@@ -3,6 +3,7 @@
 #pragma once
 
 #include <cstddef>
+#include <string>
 #include <vector>
 
 struct l3d_ctx;
@@ -17,15 +18,45 @@ int detect_segments(l3d_ctx* c, const unsigned char* pixels, int width, int heig
                     float min_length, int max_segments, std::vector<float>& out, const DetCamera* cam = nullptr);
 // cam: null = the pixels as they are; otherwise they are undistorted on the device between the upload and the rescale
 
+// ---- many images in one call.  An entry is host pixels, or (pixels null) a baseline JPEG file; cam as above
+struct DetEntry {
+    const unsigned char* pixels = nullptr;
+    int width = 0, height = 0, channels = 0;
+    size_t row_stride = 0;
+    const unsigned char* jpeg = nullptr;
+    size_t jpeg_bytes = 0;
+    int new_width = 0, new_height = 0;
+    float min_length = 0.0f;
+    int max_segments = 0;
+    const DetCamera* cam = nullptr;
+};
+// out[i]: the segments detect_segments / detect_segments_jpeg gives for entry i alone, byte for byte.  Entries with the same sizes run together, in
+// chunks (option det_batch_images, the index widths, half of the free HBM).  status[i] / message[i]: what the single call would have returned and
+// said -- a refused entry fails alone.  The return value is L3D_OK, or a device failure's code (entries not finished by then carry it)
+int detect_segments_batch(l3d_ctx* c, const DetEntry* e, int n, std::vector<std::vector<float>>& out, std::vector<int>& status, std::vector<std::string>& message);
+
 // host in, host out, same size and channels; coefficients at or below 1e-12: the pixels are copied
 int undistort_image(l3d_ctx* c, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, const DetCamera& cam, unsigned char* out,
                     size_t out_row_stride);
 
 // ---- JPEG input (l3d_jpeg.cpp, l3d_jpeg_device.hip): baseline files decoded into the detector's pixel buffer; three components come out B, G, R
 struct JpegFrame;
-// f: the parsed headers of `bytes`.  Entropy decoding on the host, inverse DCT, upsampling and colour on the device, into DetectBufs::pixels
-// (reserved by the caller); returns with the work enqueued on the context's stream
-int jpeg_decode_to_pixels(l3d_ctx* c, const unsigned char* bytes, size_t n, const JpegFrame& f);
+// a file on its way into DetectBufs::pixels: bytes and parsed headers in; where its quantisation tables and coefficients stand in the pinned
+// staging buffer, and how its entropy decoding went, out
+struct JpegStaged {
+    const unsigned char* bytes = nullptr;
+    size_t n = 0;
+    const JpegFrame* f = nullptr;
+    size_t stage_at = 0;
+    int status = 0;
+    std::string err;
+};
+// entropy decoding of n files on the host threads, each into its own slice of the staging buffer.  A file that fails says so in its status; the
+// return value is a device failure's
+int jpeg_stage_files(l3d_ctx* c, JpegStaged* const* files, int n);
+// the staged files into their slots of DetectBufs::pixels (reserved by the caller; slot b = entry b of `files`, null: not a file, the slot is left
+// alone; all of one size): one upload, then inverse DCT, upsampling and colour per file.  Returns with the work enqueued on the context's stream
+int jpeg_staged_to_pixels(l3d_ctx* c, const JpegStaged* const* files, int B);
 // host bytes in, host pixels out (height rows of width x channels bytes), any size from 1x1
 int decode_jpeg(l3d_ctx* c, const unsigned char* bytes, size_t n, unsigned char* out, size_t out_row_stride);
 // detect_segments on the decoded image, which never crosses the host; images below 8x8 are refused as detect_segments refuses them

@@ -48,4 +48,16 @@ int jpeg_parse(const unsigned char* bytes, size_t n, JpegFrame& f, std::string& 
 // written in full (absent coefficients are zero)
 int jpeg_decode_coefficients(const unsigned char* bytes, size_t n, const JpegFrame& f, int16_t* coef, std::string& err);
 
+// several files at once (l3d_jpeg_batch.cpp): jpeg_decode_coefficients of every job on up to `threads` host threads.  Each job has its own buffer,
+// status and message; the outcome of a job does not depend on the others or on the number of threads
+struct JpegDecodeJob {
+    const unsigned char* bytes = nullptr;
+    size_t n = 0;
+    const JpegFrame* f = nullptr;
+    int16_t* coef = nullptr;
+    int status = 0;
+    std::string err;
+};
+void jpeg_decode_many(JpegDecodeJob* jobs, int n, unsigned threads);
+
 }  // namespace l3d

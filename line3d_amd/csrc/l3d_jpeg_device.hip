@@ -8,6 +8,7 @@
 #include "l3d_detect.hpp"
 
 #include "l3d_ctx.hpp"
+#include "l3d_hostsort.hpp"
 #include "l3d_jpeg.hpp"
 
 namespace l3d {
@@ -128,41 +129,90 @@ __global__ __launch_bounds__(256) void k_jpg_assemble(const unsigned char* __res
 
 }  // namespace
 
-// the file's image into DetectBufs::pixels (tight stride, f.ncomp channels), which the caller has reserved: entropy decoding on the host into the
-// pinned staging buffer, one upload, the two kernels.  Returns with the work enqueued on the context's stream
-int jpeg_decode_to_pixels(l3d_ctx* c, const unsigned char* bytes, size_t n, const JpegFrame& f)
+// entropy decoding of the files on the host threads, each into its own slice of the pinned staging buffer (its quantisation tables, then its
+// coefficients).  The per-file outcome goes into the file's status and message -- nothing is read from a thread's last-error string
+int jpeg_stage_files(l3d_ctx* c, JpegStaged* const* files, int n)
+{
+    DetectBufs& d = c->det;
+    size_t stage_bytes = 0;
+    for (int i = 0; i < n; ++i) {
+        const JpegFrame& f = *files[i]->f;
+        if (f.n_blocks == 0 || f.n_blocks > kJpgMaxBlocks) return fail(c, L3D_ERR_INVALID, "jpeg: no parsed frame");       // (jpeg_parse's bound: byte offsets of the planes stay ints)
+        files[i]->stage_at = stage_bytes;
+        stage_bytes += kQtBytes + f.n_blocks * 64 * sizeof(int16_t);
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));            // (the staging buffer is about to be rewritten)
+    HIPCHK(c, d.jstage.reserve(stage_bytes));
+    unsigned char* stage = d.jstage.as<unsigned char>();
+    std::vector<JpegDecodeJob> jobs((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        unsigned char* at = stage + files[i]->stage_at;
+        memset(at, 0, kQtBytes);
+        memcpy(at, files[i]->f->qt, sizeof(files[i]->f->qt));
+        jobs[i].bytes = files[i]->bytes; jobs[i].n = files[i]->n; jobs[i].f = files[i]->f; jobs[i].coef = reinterpret_cast<int16_t*>(at + kQtBytes);
+    }
+    jpeg_decode_many(jobs.data(), n, host_threads());
+    for (int i = 0; i < n; ++i) { files[i]->status = jobs[i].status; files[i]->err = jobs[i].err; }
+    return L3D_OK;
+}
+
+// the staged files into their slots of DetectBufs::pixels (tight stride, f.ncomp channels), which the caller has reserved: one upload of the staged
+// range, the two kernels per file (a file's layout is a kernel argument).  Returns with the work enqueued on the context's stream
+int jpeg_staged_to_pixels(l3d_ctx* c, const JpegStaged* const* files, int B)
 {
     DetectBufs& d = c->det;
     hipStream_t st = c->stream;
-    if (f.n_blocks == 0 || f.n_blocks > kJpgMaxBlocks) return fail(c, L3D_ERR_INVALID, "jpeg: no parsed frame");       // (jpeg_parse's bound: byte offsets of the planes stay ints)
-    if (d.pixels.cap < (size_t)f.width * f.height * f.ncomp) return fail(c, L3D_ERR_INVALID, "jpeg: the pixel buffer was not reserved");
-    const size_t coef_bytes = f.n_blocks * 64 * sizeof(int16_t), stage_bytes = kQtBytes + coef_bytes;
-    HIPCHK(c, hipStreamSynchronize(st));            // (the staging buffer is about to be rewritten)
-    HIPCHK(c, d.jstage.reserve(stage_bytes));
-    HIPCHK(c, d.jcoef.reserve(stage_bytes));
-    HIPCHK(c, d.jplanes.reserve(f.n_blocks * 64));
-    unsigned char* stage = d.jstage.as<unsigned char>();
-    memset(stage, 0, kQtBytes);
-    memcpy(stage, f.qt, sizeof(f.qt));
-    std::string err;
-    if (int rc = jpeg_decode_coefficients(bytes, n, f, reinterpret_cast<int16_t*>(stage + kQtBytes), err)) return fail(c, rc, err);
-    JpgLayout L;
-    L.n_blocks = (int)f.n_blocks; L.ncomp = f.ncomp; L.width = f.width; L.height = f.height; L.hs = f.hmax; L.vs = f.vmax; L.rgb = f.rgb;
-    int plane_at = 0;
-    for (int i = 0; i < 3; ++i) {
-        const JpegComp& k = f.comp[i < f.ncomp ? i : 0];
-        L.block0[i] = i < f.ncomp ? (int)k.block0 : L.n_blocks;
-        L.bw[i] = k.bw; L.pw[i] = k.bw * 8; L.cw[i] = k.cw; L.chh[i] = k.chh;
-        L.plane0[i] = i < f.ncomp ? plane_at : 0;
-        if (i < f.ncomp) plane_at += k.bw * k.bh * 64;
+    size_t lo = ~(size_t)0, hi = 0, plane_bytes = 0, slot = 0;
+    for (int b = 0; b < B; ++b) {
+        if (!files[b]) continue;
+        const JpegFrame& f = *files[b]->f;
+        lo = std::min(lo, files[b]->stage_at);
+        hi = std::max(hi, files[b]->stage_at + kQtBytes + f.n_blocks * 64 * sizeof(int16_t));
+        plane_bytes += f.n_blocks * 64;
+        slot = (size_t)f.width * f.height * f.ncomp;
     }
-    { ProfScope ps(c, "jpg_upload"); HIPCHK(c, hipMemcpyAsync(d.jcoef.p, stage, stage_bytes, hipMemcpyHostToDevice, st)); }
-    const unsigned short* qt = d.jcoef.as<unsigned short>();
-    const short* coef = reinterpret_cast<const short*>(static_cast<const char*>(d.jcoef.p) + kQtBytes);
-    { ProfScope ps(c, "k_jpg_idct"); hipLaunchKernelGGL(k_jpg_idct, dim3((L.n_blocks + kIdctBlocks - 1) / kIdctBlocks), dim3(kIdctThreads), 0, st, coef, qt, L, d.jplanes.as<unsigned char>()); }
-    { ProfScope ps(c, "k_jpg_assemble"); hipLaunchKernelGGL(k_jpg_assemble, dim3((f.width + 255) / 256, f.height), dim3(256), 0, st, d.jplanes.as<unsigned char>(), L, d.pixels.as<unsigned char>()); }
+    if (hi == 0) return L3D_OK;
+    if (d.jstage.cap < hi) return fail(c, L3D_ERR_INVALID, "jpeg: the files were not staged");
+    if (d.pixels.cap < slot * B) return fail(c, L3D_ERR_INVALID, "jpeg: the pixel buffer was not reserved");
+    HIPCHK(c, d.jcoef.reserve(hi));
+    HIPCHK(c, d.jplanes.reserve(plane_bytes));
+    { ProfScope ps(c, "jpg_upload"); HIPCHK(c, hipMemcpyAsync(static_cast<char*>(d.jcoef.p) + lo, d.jstage.as<unsigned char>() + lo, hi - lo, hipMemcpyHostToDevice, st)); }
+    size_t plane_at = 0;
+    for (int b = 0; b < B; ++b) {
+        if (!files[b]) continue;
+        const JpegFrame& f = *files[b]->f;
+        if ((size_t)f.width * f.height * f.ncomp != slot) return fail(c, L3D_ERR_INVALID, "jpeg: files of different sizes in one chunk");
+        JpgLayout L;
+        L.n_blocks = (int)f.n_blocks; L.ncomp = f.ncomp; L.width = f.width; L.height = f.height; L.hs = f.hmax; L.vs = f.vmax; L.rgb = f.rgb;
+        int comp_at = 0;
+        for (int i = 0; i < 3; ++i) {
+            const JpegComp& k = f.comp[i < f.ncomp ? i : 0];
+            L.block0[i] = i < f.ncomp ? (int)k.block0 : L.n_blocks;
+            L.bw[i] = k.bw; L.pw[i] = k.bw * 8; L.cw[i] = k.cw; L.chh[i] = k.chh;
+            L.plane0[i] = i < f.ncomp ? comp_at : 0;
+            if (i < f.ncomp) comp_at += k.bw * k.bh * 64;
+        }
+        const char* staged = static_cast<const char*>(d.jcoef.p) + files[b]->stage_at;
+        const unsigned short* qt = reinterpret_cast<const unsigned short*>(staged);
+        const short* coef = reinterpret_cast<const short*>(staged + kQtBytes);
+        unsigned char* planes = d.jplanes.as<unsigned char>() + plane_at;
+        { ProfScope ps(c, "k_jpg_idct"); hipLaunchKernelGGL(k_jpg_idct, dim3((L.n_blocks + kIdctBlocks - 1) / kIdctBlocks), dim3(kIdctThreads), 0, st, coef, qt, L, planes); }
+        { ProfScope ps(c, "k_jpg_assemble"); hipLaunchKernelGGL(k_jpg_assemble, dim3((f.width + 255) / 256, f.height), dim3(256), 0, st, planes, L, d.pixels.as<unsigned char>() + slot * b); }
+        plane_at += f.n_blocks * 64;
+    }
     HIPCHK(c, hipGetLastError());
     return L3D_OK;
+}
+
+// one file into DetectBufs::pixels
+static int jpeg_decode_to_pixels(l3d_ctx* c, const unsigned char* bytes, size_t n, const JpegFrame& f)
+{
+    JpegStaged file;
+    file.bytes = bytes; file.n = n; file.f = &f;
+    JpegStaged* files[1] = { &file };
+    if (int rc = jpeg_stage_files(c, files, 1)) return rc;
+    if (file.status != L3D_OK) return fail(c, file.status, file.err);
+    return jpeg_staged_to_pixels(c, files, 1);
 }
 
 // host bytes in, host pixels out, device in between

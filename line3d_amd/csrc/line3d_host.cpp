@@ -823,16 +823,15 @@ int l3d_line3d_add_image_fixed_sim_ex(l3d_line3d* h, uint32_t id, unsigned width
 }
 
 // addImage / addImage_fixed_sim from pixels, line3D.cc:128-191: the cache decides first; without a usable cache the segments are detected on the
-// device and enter the calls above.  Returns 1: go on with `segs` (possibly none: the cache will be loaded), 0: no segment found, no view; < 0: error negated
-// cam: null, or the camera the pixels are undistorted with before the detector sees them (main_vsfm.cpp:243-270)
-static int detect_for_add(l3d_line3d* h, uint32_t id, const unsigned char* pixels, int width, int height, int channels, size_t row_stride,
-                          const char* data_directory, int max_img_width, int load_and_store, std::vector<float>& segs, const l3d::DetCamera* cam = nullptr,
-                          const unsigned char* jpeg = nullptr, size_t jpeg_n = 0)
+// device and enter the calls above.
+// The decision on its own (taken per image, by the single calls and per entry of l3d_line3d_add_images).  Returns 1: the cache stands in for the image,
+// 2: the detector has to run -- at new_w x new_h with min_length; < 0: error negated.  file / had_file: the cache's path, and whether it exists
+static int cache_or_detect(l3d_line3d* h, uint32_t id, int width, int height, const char* data_directory, int max_img_width, int load_and_store, unsigned& new_w,
+                           unsigned& new_h, float& min_length, std::string& file, bool& had_file)
 {
-    segs.clear();
     L* owner = h->node ? rank0(h) : h;
     if (width <= 0 || height <= 0) return -h->fail(L3D_ERR_INVALID, "image is empty!");
-    unsigned new_w = (unsigned)width, new_h = (unsigned)height;
+    new_w = (unsigned)width; new_h = (unsigned)height;
     if (max_img_width > 0 && std::max(width, height) > max_img_width) {                      // :133-138
         const float scale = float(max_img_width) / fmaxf((float)height, (float)width);
         new_w = (unsigned)roundf(float(width) * scale);
@@ -840,16 +839,39 @@ static int detect_for_add(l3d_line3d* h, uint32_t id, const unsigned char* pixel
     }
     char name[160];
     if (l3d_segment_cache_filename(id, new_w, new_h, owner->use_collinearity ? 1 : 0, name, sizeof(name)) != L3D_OK) return -L3D_ERR_INVALID;
-    const std::string file = std::string(data_directory ? data_directory : "") + name;
+    file = std::string(data_directory ? data_directory : "") + name;
     FILE* f = fopen(file.c_str(), "rb");
+    had_file = f != nullptr;
     if (f) { fclose(f); if (load_and_store) return 1; }                                     // :159-168: the cache stands in for the image
     if (!owner->ctx) return -h->fail(L3D_ERR_INVALID, "no device context to detect line segments with");
-    const float min_length = 0.005f * sqrtf(float(height * height + width * width));         // :176, commons.h:43
+    min_length = 0.005f * sqrtf(float(height * height + width * width));                     // :176, commons.h:43
+    return 2;
+}
+// an image the detector found nothing in adds no view; a stale cache goes with the flag off (:153-156, :186-190)
+static void no_segments(const std::string& file, bool had_file, int load_and_store)
+{
+    if (had_file && !load_and_store) remove(file.c_str());
+}
+
+// Returns 1: go on with `segs` (possibly none: the cache will be loaded), 0: no segment found, no view; < 0: error negated
+// cam: null, or the camera the pixels are undistorted with before the detector sees them (main_vsfm.cpp:243-270)
+static int detect_for_add(l3d_line3d* h, uint32_t id, const unsigned char* pixels, int width, int height, int channels, size_t row_stride,
+                          const char* data_directory, int max_img_width, int load_and_store, std::vector<float>& segs, const l3d::DetCamera* cam = nullptr,
+                          const unsigned char* jpeg = nullptr, size_t jpeg_n = 0)
+{
+    segs.clear();
+    L* owner = h->node ? rank0(h) : h;
+    unsigned new_w = 0, new_h = 0;
+    float min_length = 0.0f;
+    std::string file;
+    bool had_file = false;
+    const int what = cache_or_detect(h, id, width, height, data_directory, max_img_width, load_and_store, new_w, new_h, min_length, file, had_file);
+    if (what <= 1) return what;
     // jpeg: the file the size came from (pixels null): decoded on the device into the detector -- only here, behind the cache decision
     const int rc = jpeg ? l3d::detect_segments_jpeg(owner->ctx, jpeg, jpeg_n, (int)new_w, (int)new_h, min_length, 3000, segs, cam)
                         : l3d::detect_segments(owner->ctx, pixels, width, height, channels, row_stride, (int)new_w, (int)new_h, min_length, 3000, segs, cam);
     if (rc != L3D_OK) return -h->fail(rc, l3d_last_error(owner->ctx));
-    if (segs.empty()) { if (f && !load_and_store) remove(file.c_str()); return 0; }          // :153-156, :186-190
+    if (segs.empty()) { no_segments(file, had_file, load_and_store); return 0; }
     return 1;
 }
 
@@ -973,6 +995,76 @@ int l3d_line3d_add_image_jpeg_fixed_sim(l3d_line3d* h, uint32_t id, const unsign
     if (go <= 0) return -go;
     return l3d_line3d_add_image_fixed_sim_ex(h, id, (unsigned)width, (unsigned)height, segs.empty() ? nullptr : segs.data(), (int)(segs.size() / 4), K, R, t, sim_ids, sims,
                                              n_sims, data_directory, max_img_width, load_and_store);
+}
+
+// Many images in one call: the sequence of the single calls above in entry order, with the detector run once over all entries that need it.
+// Per entry: the checks of its single call and the cache decision; then the batched detector (l3d_detect.hip) on the entries without a usable cache;
+// then the views, in entry order, through l3d_line3d_add_image_ex / _fixed_sim_ex.  An entry fails alone, with its single call's code and message
+int l3d_line3d_add_images(l3d_line3d* h, const l3d_image_entry* e, int n, const char* data_directory, int max_img_width, int load_and_store, int* status)
+{
+    if (!h) return L3D_ERR_INVALID;
+    if (n < 0 || (n > 0 && !e)) return h->fail(L3D_ERR_INVALID, "add_images: null argument");
+    L* owner = h->node ? rank0(h) : h;
+    struct Item { int rc = L3D_OK, what = 0, width = 0, height = 0; bool had_file = false; std::string file, msg; l3d::DetCamera cam; int detect_at = -1; };
+    std::vector<Item> items((size_t)n);
+    std::vector<l3d::DetEntry> todo;
+    todo.reserve((size_t)n);
+    auto refuse = [&](Item& it, int rc) { it.rc = rc; it.msg = h->err; };
+    for (int i = 0; i < n; ++i) {
+        Item& it = items[i];
+        const l3d_image_entry& en = e[i];
+        if ((en.pixels != nullptr) == (en.jpeg != nullptr)) { refuse(it, h->fail(L3D_ERR_INVALID, "add_images: an entry needs either pixels or a JPEG file")); continue; }
+        int channels = en.channels;
+        it.width = en.width; it.height = en.height;
+        if (en.jpeg) { if (const int bad = jpeg_size_for_add(h, en.jpeg, en.jpeg_bytes, it.width, it.height, channels)) { refuse(it, -bad); continue; } }
+        const int with = en.dist ? camera_for_add(h, en.K, en.dist, it.cam) : 0;
+        if (with < 0) { refuse(it, -with); continue; }
+        unsigned new_w = 0, new_h = 0;
+        float min_length = 0.0f;
+        it.what = cache_or_detect(h, en.image_id, it.width, it.height, data_directory, max_img_width, load_and_store, new_w, new_h, min_length, it.file, it.had_file);
+        if (it.what < 0) { refuse(it, -it.what); continue; }
+        if (it.what != 2) continue;
+        l3d::DetEntry d;
+        d.pixels = en.pixels; d.width = it.width; d.height = it.height; d.channels = channels; d.row_stride = en.jpeg ? (size_t)it.width * channels : en.row_stride;
+        d.jpeg = en.jpeg; d.jpeg_bytes = en.jpeg_bytes;
+        d.new_width = (int)new_w; d.new_height = (int)new_h; d.min_length = min_length; d.max_segments = 3000;
+        d.cam = with ? &it.cam : nullptr;           // (items does not grow: the address holds)
+        it.detect_at = (int)todo.size();
+        todo.push_back(d);
+    }
+    std::vector<std::vector<float>> segs;
+    std::vector<int> det_status;
+    std::vector<std::string> det_msg;
+    int rc_all = L3D_OK;
+    if (!todo.empty()) {
+        rc_all = l3d::detect_segments_batch(owner->ctx, todo.data(), (int)todo.size(), segs, det_status, det_msg);       // (one status per entry, whatever it returns)
+    }
+    std::string lines;
+    for (int i = 0; i < n; ++i) {
+        Item& it = items[i];
+        const l3d_image_entry& en = e[i];
+        if (it.rc == L3D_OK && it.what >= 1) {
+            const float* s = nullptr;
+            int ns = 0;
+            bool add = true;
+            if (it.detect_at >= 0) {
+                if (det_status[it.detect_at] != L3D_OK) { it.rc = det_status[it.detect_at]; it.msg = det_msg[it.detect_at]; add = false; }
+                else if (segs[it.detect_at].empty()) { no_segments(it.file, it.had_file, load_and_store); add = false; }      // L3D_OK and no view
+                else { s = segs[it.detect_at].data(); ns = (int)(segs[it.detect_at].size() / 4); }
+            }
+            if (add) {
+                it.rc = en.sims ? l3d_line3d_add_image_fixed_sim_ex(h, en.image_id, (unsigned)it.width, (unsigned)it.height, s, ns, en.K, en.R, en.t, en.link_ids, en.sims, en.n_links,
+                                                                    data_directory, max_img_width, load_and_store)
+                                : l3d_line3d_add_image_ex(h, en.image_id, (unsigned)it.width, (unsigned)it.height, s, ns, en.K, en.R, en.t, en.link_ids, en.n_links, data_directory,
+                                                          max_img_width, load_and_store);
+                if (it.rc != L3D_OK) it.msg = h->err;
+            }
+        }
+        if (status) status[i] = it.rc;
+        if (it.rc != L3D_OK) lines += (lines.empty() ? "image " : "\nimage ") + std::to_string(en.image_id) + ": " + it.msg;
+    }
+    h->err = lines;
+    return rc_all;
 }
 
 // l3d_decode_jpeg with the object's device (a node object: rank 0's)

@@ -14,6 +14,51 @@ from .capi import MATCH_DTYPE, EDGE_DTYPE, L3DError, _p
 SUMMARY_DTYPE = np.dtype([("verified", np.int32), ("n_kept", np.int32), ("n_candidates", np.int64), ("median_depth", np.float32), ("pad", np.int32)])
 
 
+def image_entries(entries):
+    """The l3d_image_entry array of Line3D.add_images and what keeps its pointers alive.  Everything malformed is refused here, before any
+    library call: neither or both of img and data, an image that is not uint8, neither or both kinds of links, links without ids."""
+    entries = list(entries)
+    arr, keep = (capi.ImageEntry * max(1, len(entries)))(), []
+
+    def pointer(a):
+        keep.append(a)
+        return a.ctypes.data
+
+    for i, en in enumerate(entries):
+        e = arr[i]
+        unknown = set(en) - {"imageID", "img", "data", "K", "R", "t", "dist", "worldpointIDs", "viewSimilarity"}
+        if unknown:
+            raise ValueError("entry %d: unknown keys %s" % (i, sorted(unknown)))
+        if (en.get("img") is None) == (en.get("data") is None):
+            raise ValueError("entry %d needs either img (pixels) or data (a JPEG file), not both" % i)
+        if (en.get("worldpointIDs") is None) == (en.get("viewSimilarity") is None):
+            raise ValueError("entry %d needs either worldpointIDs or viewSimilarity, not both" % i)
+        e.image_id = int(en["imageID"])
+        if en.get("img") is not None:
+            pix, w, h, ch, stride = capi.image_arguments(en["img"])
+            keep.append(pix)
+            e.pixels, e.width, e.height, e.channels, e.row_stride = pix.value, w, h, ch, stride
+        else:
+            if not isinstance(en["data"], (bytes, bytearray, memoryview)):
+                raise TypeError("entry %d: data must be the bytes of a JPEG file" % i)
+            ptr, nbytes = capi._bytes_arguments(en["data"])
+            keep.append(ptr)
+            e.jpeg, e.jpeg_bytes = ptr.value, nbytes.value
+        e.K, e.R, e.t = (pointer(np.ascontiguousarray(en[k], dtype=np.float64)) for k in ("K", "R", "t"))
+        if en.get("dist") is not None:
+            e.dist = pointer(np.ascontiguousarray(en["dist"], dtype=np.float64).reshape(2))
+        if en.get("viewSimilarity") is not None:
+            sim = en["viewSimilarity"]
+            ids = np.ascontiguousarray(sorted(sim), dtype=np.uint32)
+            e.sims = pointer(np.ascontiguousarray([sim[int(k)] for k in ids] + [0.0], dtype=np.float32))      # (never a null pointer: it says which kind of links)
+        else:
+            ids = np.ascontiguousarray(list(en["worldpointIDs"]), dtype=np.uint32)
+        if ids.ndim != 1:
+            raise ValueError("entry %d: link ids must be a flat list" % i)
+        e.link_ids, e.n_links = pointer(np.concatenate([ids, np.zeros(1, np.uint32)])), len(ids)
+    return arr, keep
+
+
 class Line3D:
     def __init__(self, data_directory: str = "", matchingNeighbors: int = 10, uncertainty_t_upper_2D: float = 5.0,
                  uncertainty_t_lower_2D: float = 1.0, sigma_p: float = 3.5, sigma_a: float = 10.0,
@@ -204,6 +249,19 @@ class Line3D:
                                                                     _p(ids), _p(sims), C.c_int(len(ids)), C.c_char_p(self.data_directory.encode()),
                                                                     C.c_int(maxImgWidth), C.c_int(int(loadAndStoreSegments)))
         return self.last_rc == 0
+
+    def add_images(self, entries, maxImgWidth=1920, loadAndStoreSegments=True):
+        """l3d_line3d_add_images: many images in one call -- exactly the add_image_pixels[_fixed_sim] / add_image_jpeg[_fixed_sim] calls in entry order,
+        with the detector run once over all entries whose cache does not stand in for them.  An entry is a dict with the single calls' argument
+        names: imageID, K, R, t; img (a uint8 array) or data (the bytes of a baseline JPEG file); worldpointIDs or viewSimilarity ({view id:
+        similarity}); optionally dist = (k1, k2).  Returns the list of statuses, one per entry: 0, or the code the single call would have failed
+        with (the causes: l3d_line3d_last_error, one line per failed entry).  A malformed entry raises before anything is added."""
+        arr, keep = image_entries(entries)
+        n = len(entries)
+        status = (C.c_int * max(1, n))()
+        self._chk(self.lib.l3d_line3d_add_images(self.h, arr, C.c_int(n), C.c_char_p(self.data_directory.encode()), C.c_int(int(maxImgWidth)),
+                                                 C.c_int(int(loadAndStoreSegments)), status))
+        return [int(status[i]) for i in range(n)]
 
     def decode_jpeg(self, data):
         """l3d_line3d_decode_jpeg: Context.decode_jpeg with the object's device (a node object: rank 0's)"""

@@ -109,29 +109,41 @@ def reconstruct(scene: SfmScene, segments, image_sizes, out_dir=None, neighbors=
 
 
 def reconstruct_from_images(scene: SfmScene, load_image, data_directory, out_dir=None, neighbors=10, diffusion=False, max_width=1920,
-                            load_and_store_segments=True, device=0, **line3d_kwargs):
+                            load_and_store_segments=True, device=0, batch=16, **line3d_kwargs):
     """The drivers' flow (main_vsfm.cpp:226-325) from pixels: per camera the image load_image(i, name) returns -- `bytes`: the contents of a
     baseline JPEG file, decoded on the device (Line3D.add_image_jpeg); or a uint8 array H x W or H x W x 3, decoded by the caller --, K from the focal length and the image size, the image undistorted with the camera's coefficients and its
     segments detected on the device (Line3D.add_image_pixels(..., dist=cam["cv_dist"])), compute3Dmodel, optional STL + TXT output under the
     drivers' file name.  data_directory: the drivers' "<image folder>/L3D_data/" -- with load_and_store_segments (the drivers' default) the segment
-    caches are written there, and a cache of an earlier run stands in for the image (line3D.cc:143-168)."""
+    caches are written there, and a cache of an earlier run stands in for the image (line3D.cc:143-168).  The images go to the library `batch`
+    at a time (Line3D.add_images): the same views as one call per image, with the detector run once per batch."""
     import os
     from .pipeline import Line3D
     l3d = Line3D(data_directory, matchingNeighbors=neighbors, device=device, **line3d_kwargs)
-    for i, cam in enumerate(scene.cameras):
+    entries = []
+
+    def flush():
+        for en, st in zip(entries, l3d.add_images(entries, maxImgWidth=max_width, loadAndStoreSegments=load_and_store_segments)):
+            if st != 0:
+                raise RuntimeError("camera %d: %s" % (en["imageID"], l3d.lib.l3d_line3d_last_error(l3d.h).decode()))
+        del entries[:]
+
+    for i, cam in enumerate(scene.cameras):         # `batch` images per add_images call: the detector runs over them together
         img = load_image(i, cam["name"])
+        en = dict(imageID=i, R=cam["R"], t=cam["t"], worldpointIDs=cam["worldpoints"], dist=cam["cv_dist"])
         if isinstance(img, (bytes, bytearray, memoryview)):
             from .capi import jpeg_info
             w, h, _ = jpeg_info(img)
-            if not l3d.add_image_jpeg(i, img, intrinsics(cam["focal"], w, h), cam["R"], cam["t"], cam["worldpoints"], maxImgWidth=max_width,
-                                      loadAndStoreSegments=load_and_store_segments, dist=cam["cv_dist"]):
-                raise RuntimeError("camera %d: %s" % (i, l3d.lib.l3d_line3d_last_error(l3d.h).decode()))
-            continue
-        img = np.asarray(img)
-        h, w = img.shape[:2]
-        if not l3d.add_image_pixels(i, img, intrinsics(cam["focal"], w, h), cam["R"], cam["t"], cam["worldpoints"], maxImgWidth=max_width,
-                                    loadAndStoreSegments=load_and_store_segments, dist=cam["cv_dist"]):
-            raise RuntimeError("camera %d: %s" % (i, l3d.lib.l3d_line3d_last_error(l3d.h).decode()))
+            en["data"] = bytes(img)
+        else:
+            img = np.asarray(img)
+            h, w = img.shape[:2]
+            en["img"] = img
+        en["K"] = intrinsics(cam["focal"], w, h)
+        entries.append(en)
+        if len(entries) >= batch:
+            flush()
+    if entries:
+        flush()
     l3d.compute3Dmodel(diffusion)
     if out_dir is not None:
         os.makedirs(out_dir, exist_ok=True)
