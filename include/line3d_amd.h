@@ -507,6 +507,9 @@ int l3d_test_contract_math(l3d_ctx* ctx, const float* x, int n, float* out_expf,
 /* the squared-distance gate threshold T(u) = largest float whose correctly rounded square root is <= u:
  * the ulp walk and the closed form the kernels use, evaluated on the device (tests) */
 int l3d_test_sq_threshold(l3d_ctx* ctx, const float* u, int n, float* out_walk, float* out_closed);
+/* the library's exclusive scan of ints on its own (tests): out[i] = in[0] + ... + in[i-1], wrapping as int32; in and out are host
+ * arrays of n entries and may not overlap */
+int l3d_test_exclusive_sum(l3d_ctx* ctx, const int32_t* in, int n, int32_t* out);
 
 /* =================================================================================================
  * Host pipeline behind the reference's public operator interface, class L3D::Line3D

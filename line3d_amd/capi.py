@@ -645,6 +645,13 @@ class Context:
         self._chk(self.lib.l3d_test_contract_math(self.h, _p(x), C.c_int(len(x)), _p(e), _p(ac), _p(acd)))
         return e, ac, acd
 
+    def test_exclusive_sum(self, x):
+        """l3d_test_exclusive_sum: int32 (n,) -> its exclusive prefix sums, int32 (n,)"""
+        x = np.ascontiguousarray(x, dtype=np.int32)
+        out = np.zeros(len(x), np.int32)
+        self._chk(self.lib.l3d_test_exclusive_sum(self.h, _p(x), C.c_int(len(x)), _p(out)))
+        return out
+
 
 class NodeComm:
     """The in-process all-gather of the ranks of one process (l3d_node_comm_*, the adapter l3d_exchange_node): rank r on devices[r], a device may

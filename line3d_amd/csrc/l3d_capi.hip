@@ -18,6 +18,7 @@
 
 #include "l3d_ctx.hpp"
 #include "l3d_hostsort.hpp"
+#include "l3d_sort.hpp"
 #include "l3d_turns.hpp"
 
 using namespace l3d;
@@ -805,6 +806,23 @@ int l3d_test_contract_math(l3d_ctx* c, const float* x, int n, float* e, float* a
     HIPCHK(c, hipMemcpyAsync(e, c->g1.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipMemcpyAsync(ac, c->g2.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipMemcpyAsync(acd, c->g3.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, hipGetLastError());
+    return L3D_OK;
+}
+
+int l3d_test_exclusive_sum(l3d_ctx* c, const int32_t* in, int n, int32_t* out)
+{
+    if (!c || n < 0 || (n > 0 && (!in || !out))) return L3D_ERR_INVALID;
+    if (n == 0) return L3D_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    size_t tb = 0;
+    HIPCHK(c, exclusive_sum_int(nullptr, tb, (const int*)nullptr, (int*)nullptr, n, st));
+    HIPCHK(c, c->g0.reserve((size_t)n * 4)); HIPCHK(c, c->g1.reserve((size_t)n * 4)); HIPCHK(c, c->g2.reserve(tb + 256));
+    HIPCHK(c, hipMemcpyAsync(c->g0.p, in, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(c, exclusive_sum_int(c->g2.p, tb, c->g0.as<int>(), c->g1.as<int>(), n, st));
+    HIPCHK(c, hipMemcpyAsync(out, c->g1.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, hipGetLastError());
     return L3D_OK;
