@@ -943,6 +943,41 @@ int l3d_test_detect_regions(l3d_ctx* ctx, int N, int M, const double* mod, const
                             l3d_detect_region_record** rec, int* n_rec, unsigned char* active_out);
 int l3d_test_detect_nfa(l3d_ctx* ctx, const int32_t* n, const int32_t* k, const double* p, double logNT, int count, double* out);
 
+/* Stage 2 (K_verify_matches) on a candidate list of the caller's, exported for tests (tests/test_gpu_verify_variants.py): one source view's
+ * packed candidates as stage 1 leaves them, through the product's own argument set-up and launchers, on the path `sel` names.
+ *   src_segs S x 4, tgt_segs n_tgt x 4, offsets N x (start, count), P N x 3 x 4, RtKinv_src 3 x 3, C_src 3: as l3d_compute_pairwise_matches
+ *   row_start     S*N + 1   row = segment * N + camera; row_start[S*N] == R
+ *   cand_meta     R x (target id within its camera, camera); cand_depths R x 4 (the first two are the hypothesis' depths, positive by contract)
+ * sel->path 0: the all-pairs kernel and the epilogue launch.  1: the per-view seam call's launches -- the window kernel on the segments that fit
+ * the LDS image, again on a global scratch when one outgrows it, the epilogue launch.  2: the chains' single launch with the fused epilogue;
+ * gb = 1 keeps the bucket starts in global memory when N > 16, split_unit > 0 (a multiple of 256) verifies the long segments in units of that
+ * many hypotheses by a second launch, seg_order (NULL or a permutation of the segments; path 2 only) is the order the workgroups take them in.
+ * mmax: 0 = the LDS image sized as the call site sizes it from the largest segment, else that many candidates, cut down to what the LDS budget
+ * allows either way.  wide_max: launches of up to this many segments may take the 8-wave kernel (0: never).
+ * Out: conf[R], kept_cnt[S] (confidence > 1), best_depths[S x 2] (the first candidate with the segment's largest confidence; (-1, -1) when
+ * that is not above 0.5); sel->mmax_used, sel->kernels (L3D_VK_*: the kernels launched).
+ * Checked before anything is launched, L3D_ERR_INVALID with a message otherwise: row_start ascends from 0 to R, every candidate's camera is its
+ * row's, every target id is below its camera's count, the offsets stay inside n_tgt, R < 2^24, 1 <= N <= 255, the selection's ranges, and for
+ * paths 1 and 2 that the window kernels take N neighbours. */
+#define L3D_VK_ALL_PAIRS 1u
+#define L3D_VK_SEG_POST 2u
+#define L3D_VK_WINDOW_256 4u     /* k_verify_window, 4 waves */
+#define L3D_VK_WINDOW_512 8u     /* k_verify_window, 8 waves */
+#define L3D_VK_WINDOW_GB 16u     /* k_verify_window_gb */
+#define L3D_VK_BUILD 32u         /* k_verify_window_build */
+#define L3D_VK_WALK 64u          /* k_vw_walk, bucket starts in LDS */
+#define L3D_VK_WALK_GB 128u      /* k_vw_walk, bucket starts in global memory */
+typedef struct l3d_test_verify_path {
+    int32_t path, gb, split_unit, mmax, wide_max;
+    int32_t mmax_used;              /* out */
+    uint32_t kernels;               /* out */
+    int32_t pad;
+    const int32_t* seg_order;
+} l3d_test_verify_path;
+int l3d_test_verify_candidates(l3d_ctx* ctx, int S, int N, const float* src_segs, const float* tgt_segs, int n_tgt, const int32_t* offsets, const float* P,
+                               const float* RtKinv_src, const float* C_src, const int32_t* row_start, const uint32_t* cand_meta, const float* cand_depths, int R,
+                               float sigma_p, float sigma_a, float spatial_k, l3d_test_verify_path* sel, float* conf, int32_t* kept_cnt, float* best_depths);
+
 #ifdef __cplusplus
 }
 #endif

@@ -145,6 +145,16 @@ class ImageEntry(C.Structure):
                 ("dist", C.c_void_p), ("link_ids", C.c_void_p), ("sims", C.c_void_p), ("n_links", C.c_int)]
 
 
+class VerifyPath(C.Structure):
+    """l3d_test_verify_path (include/line3d_amd.h)"""
+    _fields_ = [("path", C.c_int32), ("gb", C.c_int32), ("split_unit", C.c_int32), ("mmax", C.c_int32), ("wide_max", C.c_int32),
+                ("mmax_used", C.c_int32), ("kernels", C.c_uint32), ("pad", C.c_int32), ("seg_order", C.c_void_p)]
+
+
+# L3D_VK_*: the stage-2 kernels a test_verify_candidates call launched
+VK_ALL_PAIRS, VK_SEG_POST, VK_WINDOW_256, VK_WINDOW_512, VK_WINDOW_GB, VK_BUILD, VK_WALK, VK_WALK_GB = 1, 2, 4, 8, 16, 32, 64, 128
+
+
 def _per_image(value, n, what):
     """None, or one entry per image"""
     if value is None:
@@ -426,6 +436,28 @@ class Context:
         out = np.zeros(len(n))
         self._chk(self.lib.l3d_test_detect_nfa(self.h, _p(n), _p(k), _p(p), C.c_double(float(logNT)), C.c_int(len(n)), _p(out)))
         return out
+
+    def test_verify_candidates(self, src_segs, tgt_segs, offsets, P, RtKinv_src, C_src, row_start, cand_meta, cand_depths, sigma_p, sigma_a, spatial_k,
+                               path=0, gb=0, split_unit=0, mmax=0, wide_max=0, seg_order=None):
+        """l3d_test_verify_candidates: stage 2 on a packed candidate list -> (conf (R,), kept_cnt (S,), best_depths (S, 2), mmax_used, kernels).
+        Nothing is checked here: a broken table is the library's to refuse."""
+        f = lambda a: np.ascontiguousarray(a, dtype=np.float32)
+        src_segs, tgt_segs, P, RtKinv_src, C_src, cand_depths = f(src_segs), f(tgt_segs), f(P), f(RtKinv_src), f(C_src), f(cand_depths)
+        offsets, row_start = np.ascontiguousarray(offsets, dtype=np.int32), np.ascontiguousarray(row_start, dtype=np.int32)
+        cand_meta = np.ascontiguousarray(cand_meta, dtype=np.uint32)
+        S, N, R, n_tgt = len(src_segs), len(offsets), len(cand_meta), len(tgt_segs.reshape(-1, 4))
+        assert row_start.shape == (S * N + 1,) and cand_meta.shape == (R, 2) and cand_depths.shape == (R, 4) and P.size == N * 12
+        sel = VerifyPath(int(path), int(gb), int(split_unit), int(mmax), int(wide_max), 0, 0, 0, None)
+        if seg_order is not None:
+            seg_order = np.ascontiguousarray(seg_order, dtype=np.int32)
+            assert seg_order.shape == (S,)
+            sel.seg_order = seg_order.ctypes.data
+        conf, kept, best = np.zeros(R, np.float32), np.zeros(S, np.int32), np.zeros((S, 2), np.float32)
+        self._chk(self.lib.l3d_test_verify_candidates(self.h, C.c_int(S), C.c_int(N), _p(src_segs), _p(tgt_segs), C.c_int(n_tgt), _p(offsets), _p(P),
+                                                      _p(RtKinv_src), _p(C_src), _p(row_start), _p(cand_meta), _p(cand_depths), C.c_int(R),
+                                                      C.c_float(float(sigma_p)), C.c_float(float(sigma_a)), C.c_float(float(spatial_k)), C.byref(sel),
+                                                      _p(conf), _p(kept), _p(best)))
+        return conf, kept, best, int(sel.mmax_used), int(sel.kernels)
 
     # -- the three seam functions ---------------------------------------------------------------
     def compute_collinearity(self, segs, collin_s=2.0):

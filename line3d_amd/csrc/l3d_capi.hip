@@ -17,6 +17,7 @@
 #include <thread>
 
 #include "l3d_ctx.hpp"
+#include "l3d_chain_common.hpp"
 #include "l3d_hostsort.hpp"
 #include "l3d_sort.hpp"
 #include "l3d_turns.hpp"
@@ -26,6 +27,8 @@ using namespace l3d;
 static_assert(sizeof(l3d_match) == sizeof(Match), "l3d_match layout");
 static_assert(sizeof(l3d_match) == 32, "l3d_match is 32 bytes");
 static_assert(sizeof(l3d_hypothesis) == sizeof(Hypothesis), "l3d_hypothesis layout");
+static_assert(kVKAllPairs == L3D_VK_ALL_PAIRS && kVKSegPost == L3D_VK_SEG_POST && kVKWindow256 == L3D_VK_WINDOW_256 && kVKWindow512 == L3D_VK_WINDOW_512 &&
+              kVKWindowGB == L3D_VK_WINDOW_GB && kVKBuild == L3D_VK_BUILD && kVKWalk == L3D_VK_WALK && kVKWalkGB == L3D_VK_WALK_GB, "L3D_VK_* of the header");
 
 namespace {
 const char* kProfNames = "pair_mask;row_count;scan;pair_fill;cand_move;exist;verify;verify_window;seg_post;kept_write;collinearity;collinearity_fill;rownorm;diffusion_step;similarity;tgt_rays;prod_keys;prod_sort;prod_rows;hypotheses;uf_components";
@@ -59,6 +62,52 @@ void ctx_release_share(l3d_ctx* c)
     c->resident_hyp = 0; c->resident_edges = 0; c->kept_edges = 0; c->resident_nodes = 0; c->resident_labels = 0;
 }
 }  // namespace l3d
+
+namespace {
+// Stage 2 of the per-view seam call (l3d_compute_pairwise_matches; l3d_test_verify_candidates hands it candidate lists of its own).
+// The arguments: tables and candidate arrays, no reverse-match runs to order, the epilogue as a launch of its own.
+int seam_verify_args(l3d_ctx* c, VerifyArgs& va, const float4* d_src, const float4* d_tgt, const int2* offsets, const float* P, const float* RtKinv_src,
+                     const float* C_src, int N, int seg_begin, int seg_end, size_t nrow, float sigma_p, float sigma_a, float spatial_k)
+{
+    va.exist_cams = nullptr; va.n_exist_cams = 0;
+    va.src_segs = d_src; va.tgt_segs = d_tgt; va.offsets = offsets;
+    va.P = P;
+    va.RtKinv_src = RtKinv_src; va.C_src = C_src;
+    va.row_start = c->row_start.as<int>();
+    va.cand_meta = c->cand_meta.as<uint2>(); va.cand_depths = c->cand_depths.as<float4>(); va.cand_conf = c->cand_conf.as<float>();
+    va.N = N; va.seg_begin = seg_begin; va.seg_end = seg_end; va.nrow_total = (int)nrow;
+    va.sigma_p = sigma_p; va.sigma_a = sigma_a; va.spatial_k = spatial_k;
+    va.mmax = 0; va.only_above = -1; va.skip_above = 0; va.cand_cap = 0; va.res = nullptr; va.bstart_g = nullptr;
+    va.big = 0; va.scratch = nullptr; va.scratch_stride = 0; va.kept_cnt = nullptr; va.best_depths = nullptr; va.seg_order = nullptr;
+    va.debug = c->opt.vw_debug;
+    va.stamps = nullptr;
+    if (c->opt.vw_stamps) {
+        if (!c->stamps.p) { HIPCHK(c, c->stamps.reserve(128)); HIPCHK(c, hipMemsetAsync(c->stamps.p, 0, 128, c->stream)); }
+        va.stamps = c->stamps.as<unsigned long long>();
+    }
+    return L3D_OK;
+}
+// The launches: the window kernel on the segments that fit the LDS image and, when one outgrows it, again on a global scratch -- or the
+// all-pairs kernel (all-pairs mode, beyond ~50 neighbours) --, then the per-segment epilogue.  mmax: the largest segment; mmax_given > 0
+// (tests): that image instead, under the same budget; R: the number of candidates.
+int seam_launch_verify(l3d_ctx* c, VerifyArgs& va, bool window, int mmax, int mmax_given, int R, hipStream_t st)
+{
+    va.mmax = mmax;
+    if (window) {
+        // segments that fit the LDS image in one launch, the (few) bigger ones in a second launch on a global scratch
+        const int mfit = verify_window_fit_mmax(mmax_given > 0 ? mmax_given : mmax, va.N, c->opt.vw_lds);
+        va.mmax = mfit; va.skip_above = 1;
+        { ProfScope p(c, "verify_window"); launch_verify_window(va, st, c->opt.vw_wide_max); }
+        if (mfit < mmax) {
+            HIPCHK(c, c->vw_scratch.reserve(((size_t)R + kVWSlack) * 16));
+            va.big = 1; va.scratch = c->vw_scratch.as<float>(); va.scratch_stride = (long long)R + kVWSlack;
+            ProfScope p(c, "verify_window"); launch_verify_window(va, st, c->opt.vw_wide_max);
+        }
+    } else { ProfScope p(c, "verify"); launch_verify(va, st); }
+    { ProfScope p(c, "seg_post"); launch_seg_post(va, c->kept_cnt.as<int>(), c->best.as<float2>(), st); }
+    return L3D_OK;
+}
+}  // namespace
 
 extern "C" {
 
@@ -529,35 +578,9 @@ int l3d_compute_pairwise_matches(l3d_ctx* c,
     { ProfScope p(c, "exist"); launch_exist_place(c->exist.as<ExistRec>(), n_ex, N, c->row_start.as<int>(), c->cand_meta.as<uint2>(), c->cand_depths.as<float4>(), st); }
 
     VerifyArgs va;
-    va.exist_cams = nullptr; va.n_exist_cams = 0;
-    va.src_segs = d_src; va.tgt_segs = d_tgt; va.offsets = pa.offsets;
-    va.P = reinterpret_cast<const float*>(tb + o_P);
-    va.RtKinv_src = pa.RtKinv_src; va.C_src = pa.C_src;
-    va.row_start = c->row_start.as<int>();
-    va.cand_meta = c->cand_meta.as<uint2>(); va.cand_depths = c->cand_depths.as<float4>(); va.cand_conf = c->cand_conf.as<float>();
-    va.N = N; va.seg_begin = seg_begin; va.seg_end = seg_end; va.nrow_total = (int)nrow;
-    va.sigma_p = sigma_p; va.sigma_a = sigma_a; va.spatial_k = spatial_k;
-    va.mmax = mmax; va.only_above = -1; va.skip_above = 0; va.cand_cap = 0; va.res = nullptr; va.bstart_g = nullptr;
-    va.big = 0; va.scratch = nullptr; va.scratch_stride = 0; va.kept_cnt = nullptr; va.best_depths = nullptr; va.seg_order = nullptr;
-    va.debug = c->opt.vw_debug;
-    va.stamps = nullptr;
-    if (c->opt.vw_stamps) {
-        if (!c->stamps.p) { HIPCHK(c, c->stamps.reserve(128)); HIPCHK(c, hipMemsetAsync(c->stamps.p, 0, 128, st)); }
-        va.stamps = c->stamps.as<unsigned long long>();
-    }
-    if (c->verify_mode == 0 && verify_window_supported(N)) {
-        // segments that fit the LDS image in one launch, the (few) bigger ones in a second launch on a global scratch
-        int mfit = mmax;
-        while (mfit > 64 && verify_window_lds_bytes(mfit, N) > verify_window_max_lds(c->opt.vw_lds)) mfit = mfit * 3 / 4;
-        va.mmax = mfit; va.skip_above = 1;
-        { ProfScope p(c, "verify_window"); launch_verify_window(va, st, c->opt.vw_wide_max); }
-        if (mfit < mmax) {
-            HIPCHK(c, c->vw_scratch.reserve(((size_t)R + kVWSlack) * 16));
-            va.big = 1; va.scratch = c->vw_scratch.as<float>(); va.scratch_stride = (long long)R + kVWSlack;
-            ProfScope p(c, "verify_window"); launch_verify_window(va, st, c->opt.vw_wide_max);
-        }
-    } else { ProfScope p(c, "verify"); launch_verify(va, st); }
-    { ProfScope p(c, "seg_post"); launch_seg_post(va, c->kept_cnt.as<int>(), c->best.as<float2>(), st); }
+    if ((rc = seam_verify_args(c, va, d_src, d_tgt, pa.offsets, reinterpret_cast<const float*>(tb + o_P), pa.RtKinv_src, pa.C_src, N, seg_begin, seg_end,
+                               nrow, sigma_p, sigma_a, spatial_k))) return rc;
+    if ((rc = seam_launch_verify(c, va, c->verify_mode == 0 && verify_window_supported(N), mmax, 0, R, st))) return rc;
     { ProfScope p(c, "scan"); launch_scan(c->kept_cnt.as<int>(), c->kept_start.as<int>(), S_src, nullptr, st); }
     { ProfScope p(c, "kept_write"); launch_kept_write(va, c->kept_start.as<int>(), d_l2g, c->kept.as<Match>(), st); }
     TPHASE(4);
@@ -823,6 +846,129 @@ int l3d_test_exclusive_sum(l3d_ctx* c, const int32_t* in, int n, int32_t* out)
     HIPCHK(c, hipMemcpyAsync(c->g0.p, in, (size_t)n * 4, hipMemcpyHostToDevice, st));
     HIPCHK(c, exclusive_sum_int(c->g2.p, tb, c->g0.as<int>(), c->g1.as<int>(), n, st));
     HIPCHK(c, hipMemcpyAsync(out, c->g1.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, hipGetLastError());
+    return L3D_OK;
+}
+
+// Stage 2 on a candidate list of the caller's (tests/test_gpu_verify_variants.py): the tables are validated on the host, then the product's own
+// set-up and launchers run -- seam_verify_args / seam_launch_verify (paths 0 and 1), chain_verify_args / chain_launch_verify (path 2: the chain's
+// switches are the context's options, set for this one launch and put back).
+int l3d_test_verify_candidates(l3d_ctx* c, int S, int N, const float* src_segs, const float* tgt_segs, int n_tgt, const int32_t* offsets, const float* P,
+                               const float* RtKinv_src, const float* C_src, const int32_t* row_start, const uint32_t* cand_meta, const float* cand_depths, int R,
+                               float sigma_p, float sigma_a, float spatial_k, l3d_test_verify_path* sel, float* conf, int32_t* kept_cnt, float* best_depths)
+{
+    if (!c) return L3D_ERR_INVALID;
+    if (!sel || S < 0 || N < 1 || N > 255 || n_tgt < 0 || R < 0 || !offsets || !P || !RtKinv_src || !C_src || !row_start ||
+        (S > 0 && (!src_segs || !kept_cnt || !best_depths)) || (n_tgt > 0 && !tgt_segs) || (R > 0 && (!cand_meta || !cand_depths || !conf)))
+        return fail(c, L3D_ERR_INVALID, "verify_candidates: bad argument");
+    sel->mmax_used = 0; sel->kernels = 0;
+    if (R >= (1 << 24)) return fail(c, L3D_ERR_INVALID, "verify_candidates: 2^24 candidates or more (a position inside a segment is kept in 24 bits)");
+    if ((long long)S * N >= 0x7fffffffll) return fail(c, L3D_ERR_INVALID, "verify_candidates: too many rows");
+    if (sel->path < 0 || sel->path > 2) return fail(c, L3D_ERR_INVALID, "verify_candidates: path must be 0, 1 or 2");
+    if (sel->path != 0 && !verify_window_supported(N)) return fail(c, L3D_ERR_INVALID, "verify_candidates: the window kernels do not take this many neighbours");
+    if (sel->mmax < 0 || sel->wide_max < 0 || (sel->gb != 0 && sel->gb != 1) || sel->split_unit < 0 || sel->split_unit % 256 != 0)
+        return fail(c, L3D_ERR_INVALID, "verify_candidates: mmax / wide_max below 0, gb not 0 / 1 or split_unit no multiple of 256");
+    for (int i = 0; i < N; ++i)
+        if (offsets[2 * i] < 0 || offsets[2 * i + 1] < 0 || (long long)offsets[2 * i] + offsets[2 * i + 1] > n_tgt)
+            return fail(c, L3D_ERR_INVALID, "verify_candidates: offsets outside the target segments");
+    const size_t nrow = (size_t)S * N;
+    if (row_start[0] != 0 || row_start[nrow] != R) return fail(c, L3D_ERR_INVALID, "verify_candidates: row_start must run from 0 to the number of candidates");
+    int mmax = 0;
+    for (size_t i = 0; i < nrow; ++i) {
+        if (row_start[i + 1] < row_start[i] || row_start[i + 1] > R) return fail(c, L3D_ERR_INVALID, "verify_candidates: row_start does not ascend");
+        const unsigned cam = (unsigned)(i % (size_t)N);
+        for (int r = row_start[i]; r < row_start[i + 1]; ++r) {
+            if (cand_meta[2 * (size_t)r + 1] != cam) return fail(c, L3D_ERR_INVALID, "verify_candidates: a candidate's camera is not its row's");
+            if (cand_meta[2 * (size_t)r] >= (unsigned)offsets[2 * cam + 1]) return fail(c, L3D_ERR_INVALID, "verify_candidates: a target id past its camera's segments");
+        }
+    }
+    for (int y = 0; y < S; ++y) mmax = std::max(mmax, row_start[(size_t)(y + 1) * N] - row_start[(size_t)y * N]);
+    if (sel->seg_order) {
+        if (sel->path != 2) return fail(c, L3D_ERR_INVALID, "verify_candidates: seg_order is the chain's (path 2)");
+        std::vector<char> seen((size_t)S, 0);
+        for (int i = 0; i < S; ++i) {
+            const int y = sel->seg_order[i];
+            if (y < 0 || y >= S || seen[(size_t)y]) return fail(c, L3D_ERR_INVALID, "verify_candidates: seg_order is no permutation of the segments");
+            seen[(size_t)y] = 1;
+        }
+    }
+    if (S == 0) return L3D_OK;
+
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const float4 *d_src = nullptr, *d_tgt = nullptr;
+    int rc;
+    if ((rc = to_device(c, c->src_segs, src_segs, (size_t)S * 16, &d_src))) return rc;
+    if ((rc = to_device(c, c->tgt_segs, tgt_segs, (size_t)n_tgt * 16, &d_tgt))) return rc;
+    ChainViewDev d;                                     // the table block in the chains' terms: offsets | P | RtKinv_src | C_src
+    d.src = d_src; d.tgt = d_tgt; d.s0 = 0; d.s1 = S;
+    d.o_off = 0; d.o_P = (size_t)N * 8; d.o_Rs = d.o_P + (size_t)N * 48; d.o_Cs = d.o_Rs + 36;
+    const size_t t_bytes = d.o_Cs + 12;
+    HIPCHK(c, c->pin_tab.reserve(t_bytes));
+    unsigned char* tab = c->pin_tab.as<unsigned char>();
+    memcpy(tab + d.o_off, offsets, (size_t)N * 8); memcpy(tab + d.o_P, P, (size_t)N * 48); memcpy(tab + d.o_Rs, RtKinv_src, 36); memcpy(tab + d.o_Cs, C_src, 12);
+    HIPCHK(c, c->tables.reserve(t_bytes));
+    HIPCHK(c, hipMemcpyAsync(c->tables.p, tab, t_bytes, hipMemcpyHostToDevice, st));
+    const unsigned char* tb = c->tables.as<unsigned char>();
+
+    struct OptionsBack { l3d_ctx* c; Options o; ~OptionsBack() { c->opt = o; } } back{ c, c->opt };
+    c->opt.vw_wide_max = sel->wide_max;
+    c->opt.vw_split = sel->split_unit > 0 ? 1 : 0;
+    if (sel->split_unit > 0) c->opt.vw_unit = sel->split_unit;
+    c->opt.vw_gb = sel->gb;
+    c->opt.vw_stamps = 0; c->opt.vw_debug = 0;
+
+    const size_t cand_cap = (size_t)std::max(R, 1);
+    HIPCHK(c, c->row_start.reserve((nrow + 1) * 4));
+    HIPCHK(c, c->kept_cnt.reserve((size_t)S * 4 + 4));
+    HIPCHK(c, c->best.reserve((size_t)S * 8 + 8));
+    d.best = c->best.as<float2>();
+    if (sel->path == 2) {
+        ChainLayout L;
+        L.maxS = S; L.maxN = N;
+        if ((rc = chain_reserve_candidates(c, L, cand_cap, 0))) return rc;
+        HIPCHK(c, c->ch_segorder.reserve((size_t)S * 4 + 16));
+    } else {
+        HIPCHK(c, c->cand_meta.reserve(cand_cap * 8));
+        HIPCHK(c, c->cand_depths.reserve(cand_cap * 16));
+        HIPCHK(c, c->cand_conf.reserve(cand_cap * 4));
+    }
+    HIPCHK(c, hipMemcpyAsync(c->row_start.p, row_start, (nrow + 1) * 4, hipMemcpyHostToDevice, st));
+    if (R) {
+        HIPCHK(c, hipMemcpyAsync(c->cand_meta.p, cand_meta, (size_t)R * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(c->cand_depths.p, cand_depths, (size_t)R * 16, hipMemcpyHostToDevice, st));
+    }
+    // what no kernel writes stays recognisable: NaN confidences and best depths, kept counts of -1
+    HIPCHK(c, hipMemsetAsync(c->cand_conf.p, 0xff, cand_cap * 4, st));
+    HIPCHK(c, hipMemsetAsync(c->kept_cnt.p, 0xff, (size_t)S * 4, st));
+    HIPCHK(c, hipMemsetAsync(c->best.p, 0xff, (size_t)S * 8, st));
+
+    (void)verify_launched(true);
+    VerifyArgs va;
+    if (sel->path == 2) {
+        l3d_chain_view v = {};
+        v.S_src = S; v.N = N; v.sigma_p = sigma_p; v.sigma_a = sigma_a; v.spatial_k = spatial_k;
+        va = chain_verify_args(c, v, d, tb, cand_cap);
+        va.seg_order = nullptr;
+        if (sel->seg_order) {
+            HIPCHK(c, hipMemcpyAsync(c->ch_segorder.p, sel->seg_order, (size_t)S * 4, hipMemcpyHostToDevice, st));
+            va.seg_order = c->ch_segorder.as<int>();
+        }
+        const int mode = c->verify_mode;
+        c->verify_mode = 0;
+        chain_launch_verify(c, va, d, nullptr, 0, mmax, cand_cap, st, sel->mmax);
+        c->verify_mode = mode;
+    } else {
+        if ((rc = seam_verify_args(c, va, d_src, d_tgt, reinterpret_cast<const int2*>(tb + d.o_off), reinterpret_cast<const float*>(tb + d.o_P),
+                                   reinterpret_cast<const float*>(tb + d.o_Rs), reinterpret_cast<const float*>(tb + d.o_Cs), N, 0, S, nrow, sigma_p, sigma_a, spatial_k))) return rc;
+        if ((rc = seam_launch_verify(c, va, sel->path == 1, mmax, sel->mmax, R, st))) return rc;
+    }
+    sel->mmax_used = va.mmax;
+    sel->kernels = verify_launched(true);
+    if (R) HIPCHK(c, hipMemcpyAsync(conf, c->cand_conf.p, (size_t)R * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(kept_cnt, c->kept_cnt.p, (size_t)S * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(best_depths, c->best.p, (size_t)S * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, hipGetLastError());
     return L3D_OK;

@@ -286,13 +286,13 @@ VerifyArgs chain_verify_args(l3d_ctx* c, const l3d_chain_view& v, const ChainVie
     return va;
 }
 
-void chain_launch_verify(l3d_ctx* c, VerifyArgs& va, const ChainViewDev& d, const int* exist_cams, int n_exist_cams, int raw_max_per_segment, size_t cand_cap, hipStream_t st)
+void chain_launch_verify(l3d_ctx* c, VerifyArgs& va, const ChainViewDev& d, const int* exist_cams, int n_exist_cams, int raw_max_per_segment, size_t cand_cap, hipStream_t st, int mmax_given)
 {
     // LDS budget from the raw statistics (+ room for reverse matches); bigger segments take the global-scratch blocks
     // (raw_max_per_segment < 0: no statistics -- the largest image the budget allows; the budget, not the image, sets the occupancy)
-    int mmax = raw_max_per_segment < 0 ? 16384 : raw_max_per_segment + raw_max_per_segment / 4 + 64;
-    while (mmax > 64 && verify_window_lds_bytes(mmax, va.N) > verify_window_max_lds(c->opt.vw_lds)) mmax = mmax * 3 / 4;
-    va.mmax = mmax;
+    // (mmax_given > 0, tests: that image instead of the estimate, under the same budget)
+    const int want_mmax = mmax_given > 0 ? mmax_given : raw_max_per_segment < 0 ? 16384 : raw_max_per_segment + raw_max_per_segment / 4 + 64;
+    va.mmax = verify_window_fit_mmax(want_mmax, va.N, c->opt.vw_lds);
     if (va.seg_end <= va.seg_begin) return;
     if (c->verify_mode == 0 && verify_window_supported(va.N)) {
         // one launch: segments that fit the LDS image, the ones that outgrow it (reverse matches are not in the estimate) on a global

@@ -58,7 +58,7 @@ PairArgs chain_pair_args(const l3d_ctx* c, const l3d_chain_view& v, const ChainV
 VerifyArgs chain_verify_args(l3d_ctx* c, const l3d_chain_view& v, const ChainViewDev& d, const unsigned char* dtab, size_t cand_cap);
 // the window kernel's launch on those arguments (LDS image from the raw maximum per segment, or the largest the budget allows), or the
 // all-pairs kernel + per-segment epilogue beyond ~50 neighbours / in all-pairs mode
-void chain_launch_verify(l3d_ctx* c, VerifyArgs& va, const ChainViewDev& d, const int* exist_cams, int n_exist_cams, int raw_max_per_segment, size_t cand_cap, hipStream_t st);
+void chain_launch_verify(l3d_ctx* c, VerifyArgs& va, const ChainViewDev& d, const int* exist_cams, int n_exist_cams, int raw_max_per_segment, size_t cand_cap, hipStream_t st, int mmax_given = 0);
 
 // first guess of the candidate capacity from the largest view's pair count (raw density ~6 % + reverse matches; guarded on the device)
 inline size_t chain_first_cand_cap(double max_pairs) { return (size_t)(max_pairs * 0.12) + 65536; }

@@ -965,10 +965,12 @@ void launch_exist_place(const ExistRec* ex, int n, int N, const int* row_start, 
 void launch_verify(const VerifyArgs& a, hipStream_t st)
 {
     hipLaunchKernelGGL(k_verify, dim3(a.seg_end - a.seg_begin), dim3(256), 0, st, a);
+    verify_launch_note(kVKAllPairs);
 }
 void launch_seg_post(const VerifyArgs& a, int* kept_cnt, float2* best, hipStream_t st)
 {
     hipLaunchKernelGGL(k_seg_post, dim3((a.seg_end - a.seg_begin + 3) / 4), dim3(256), 0, st, a, kept_cnt, best);
+    verify_launch_note(kVKSegPost);
 }
 void launch_kept_write(const VerifyArgs& a, const int* kept_start, const unsigned* l2g, Match* out, hipStream_t st)
 {

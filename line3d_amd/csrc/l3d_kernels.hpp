@@ -150,6 +150,15 @@ void launch_verify(const VerifyArgs& a, hipStream_t st);
 void launch_verify_window(const VerifyArgs& a, hipStream_t st, int wide_max = 640, const VWSplitArgs* split = nullptr);
 size_t verify_window_lds_bytes(int mmax, int N);
 size_t verify_window_max_lds(int vw_lds_opt = 0);
+// capacity of the LDS image: `want` candidates per segment, cut down by quarters (never below 64) until the image fits the budget -- the
+// one sizing rule of the per-view seam call and of the chains
+int verify_window_fit_mmax(int want, int N, int vw_lds_opt);
+// Which stage-2 kernels the launchers above started on this host thread since the last verify_launched(true) (== L3D_VK_* of
+// include/line3d_amd.h): l3d_test_verify_candidates reports it, so a launch that quietly takes another variant fails a test.  Host-side
+// bookkeeping of the launchers (one OR per launch); the kernels know nothing of it.
+enum : unsigned { kVKAllPairs = 1u, kVKSegPost = 2u, kVKWindow256 = 4u, kVKWindow512 = 8u, kVKWindowGB = 16u, kVKBuild = 32u, kVKWalk = 64u, kVKWalkGB = 128u };
+void verify_launch_note(unsigned bit);
+unsigned verify_launched(bool reset);
 bool verify_window_supported(int N);
 void verify_window_set_lds_budget(size_t bytes);
 void launch_seg_mmax(const int* row_start, int N, int seg_begin, int seg_end, int* out, hipStream_t st);

@@ -612,6 +612,14 @@ size_t verify_window_max_lds(int vw_lds_opt)
 // The per-(hypothesis lane, camera) maxima alone need 1 KB per camera: beyond ~50 neighbours the kernel does not fit the
 // 64 KB a workgroup may ask for and the caller takes the all-pairs kernel.
 bool verify_window_supported(int N) { return verify_window_lds_bytes(64, N) <= 60 * 1024; }
+int verify_window_fit_mmax(int want, int N, int vw_lds_opt)
+{
+    while (want > 64 && verify_window_lds_bytes(want, N) > verify_window_max_lds(vw_lds_opt)) want = want * 3 / 4;
+    return want;
+}
+static thread_local unsigned t_launched = 0;
+void verify_launch_note(unsigned bit) { t_launched |= bit; }
+unsigned verify_launched(bool reset) { const unsigned r = t_launched; if (reset) t_launched = 0; return r; }
 // hipFuncAttributeMaxDynamicSharedMemorySize applies to the CURRENT device: the opt-in is tracked per (device, kernel
 // instantiation), under a mutex (several contexts on several GPUs may launch from different threads).  A refused opt-in
 // leaves the launch error for the caller's hipGetLastError check: nothing is launched with an LDS request the device
@@ -640,6 +648,7 @@ void launch_verify_window(const VerifyArgs& a, hipStream_t st, int wide_max, con
         const size_t lds = std::max(verify_window_lds_bytes(a.mmax, a.N), verify_window_lds_bytes_big(a.N, 256));
         if (!lds_opt_in(reinterpret_cast<const void*>(k_verify_window_build<256>), 2)) return;
         hipLaunchKernelGGL(k_verify_window_build<256>, dim3(2 * nseg + 1), dim3(256), lds, st, a, *sp);
+        verify_launch_note(kVKBuild | (a.N > 16 ? kVKWalkGB : kVKWalk));
         if (a.N > 16) hipLaunchKernelGGL((k_vw_walk<256, true>), dim3((unsigned)std::max(1, sp->units_max)), dim3(256), verify_window_lds_bytes_big(a.N, 256), st, a, *sp);
         else hipLaunchKernelGGL((k_vw_walk<256, false>), dim3((unsigned)std::max(1, sp->units_max)), dim3(256), verify_window_lds_bytes_big(a.N, 256), st, a, *sp);
         return;
@@ -651,15 +660,18 @@ void launch_verify_window(const VerifyArgs& a, hipStream_t st, int wide_max, con
     if (nseg <= wide_max && lds512 <= (size_t)kWideLdsMax) {
         if (!lds_opt_in(reinterpret_cast<const void*>(k_verify_window<512>), 1)) return;
         hipLaunchKernelGGL(k_verify_window<512>, grid, dim3(512), lds512, st, a);
+        verify_launch_note(kVKWindow512);
     } else {
         const size_t lds = a.big == 1 ? verify_window_lds_bytes_big(a.N, 256) : std::max(verify_window_lds_bytes(a.mmax, a.N), verify_window_lds_bytes_big(a.N, 256));
         if (a.bstart_g && a.N > 16 && a.big == 2) {         // (the maxima + rings of 17+ cameras hold the build's two tables: 256 * 17 * 4 + 8192 > 16.4 KB)
             if (!lds_opt_in(reinterpret_cast<const void*>(k_verify_window_gb<256>), 3)) return;
             hipLaunchKernelGGL(k_verify_window_gb<256>, grid, dim3(256), lds, st, a);
+            verify_launch_note(kVKWindowGB);
             return;
         }
         if (!lds_opt_in(reinterpret_cast<const void*>(k_verify_window<256>), 0)) return;
         hipLaunchKernelGGL(k_verify_window<256>, grid, dim3(256), lds, st, a);
+        verify_launch_note(kVKWindow256);
     }
 }
 void launch_seg_mmax(const int* row_start, int N, int seg_begin, int seg_end, int* out, hipStream_t st)
