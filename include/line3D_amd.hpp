@@ -172,51 +172,33 @@ public:
     void addImage(const unsigned int imageID, const Img& image, const M3& K, const M3& R, const V3& t, std::list<unsigned int>& worldpointIDs,
                   const int maxImgWidth = 1920, const bool loadAndStoreSegments = true)
     {
-        double k[9], r[9], tt[3];
-        flatten(K, R, t, k, r, tt);
-        std::vector<uint32_t> wps(worldpointIDs.begin(), worldpointIDs.end());
-        report(add_from_image(detail::prio<1>(), imageID, image, k, r, tt, wps.data(), nullptr, (int)wps.size(), maxImgWidth, loadAndStoreSegments));
+        add_from_image(detail::prio<1>(), imageID, image, K, R, t, worldpointIDs, nullptr, maxImgWidth, loadAndStoreSegments);
     }
     template <class Img, class M3, class V3, class = decltype(std::declval<const Img&>().cols), class = decltype(std::declval<const Img&>().rows),
               class = decltype(std::declval<const M3&>()(0, 0)), class = decltype(std::declval<const V3&>()(0))>
     void addImage_fixed_sim(const unsigned int imageID, const Img& image, const M3& K, const M3& R, const V3& t, std::map<unsigned int, float>& viewSimilarity,
                             const int maxImgWidth = 1920, const bool loadAndStoreSegments = true)
     {
-        double k[9], r[9], tt[3];
-        flatten(K, R, t, k, r, tt);
-        std::vector<uint32_t> ids;
-        std::vector<float> sims;
-        for (auto& kv : viewSimilarity) { ids.push_back(kv.first); sims.push_back(kv.second); }
-        sims.push_back(0.0f);       // (never null: `sims` tells the two kinds of links apart)
-        report(add_from_image(detail::prio<1>(), imageID, image, k, r, tt, ids.data(), sims.data(), (int)ids.size(), maxImgWidth, loadAndStoreSegments));
+        add_from_image(detail::prio<1>(), imageID, image, K, R, t, viewSimilarity, nullptr, maxImgWidth, loadAndStoreSegments);
     }
     // The drivers' per-image step in front of addImage (main_vsfm.cpp:243-273, main_bundler.cpp:256-287): the image is undistorted on the device
-    // with OpenCV-convention radial coefficients k1, k2 and K's fx, fy, cx, cy (l3d_line3d_add_image_pixels_distorted), then detected.  For image
+    // with OpenCV-convention radial coefficients k1, k2 and K's fx, fy, cx, cy (an image entry with dist, include/line3d_amd.h), then detected.  For image
     // types that carry pixels; one with a size only takes the cache path as above and the coefficients are ignored.
     template <class Img, class M3, class V3, class = decltype(std::declval<const Img&>().cols), class = decltype(std::declval<const Img&>().rows),
               class = decltype(std::declval<const M3&>()(0, 0)), class = decltype(std::declval<const V3&>()(0))>
     void addImageDistorted(const unsigned int imageID, const Img& image, const M3& K, const M3& R, const V3& t, const double k1, const double k2,
                            std::list<unsigned int>& worldpointIDs, const int maxImgWidth = 1920, const bool loadAndStoreSegments = true)
     {
-        double k[9], r[9], tt[3];
-        flatten(K, R, t, k, r, tt);
         const double dist[2] = { k1, k2 };
-        std::vector<uint32_t> wps(worldpointIDs.begin(), worldpointIDs.end());
-        report(add_from_image(detail::prio<1>(), imageID, image, k, r, tt, wps.data(), nullptr, (int)wps.size(), maxImgWidth, loadAndStoreSegments, dist));
+        add_from_image(detail::prio<1>(), imageID, image, K, R, t, worldpointIDs, dist, maxImgWidth, loadAndStoreSegments);
     }
     template <class Img, class M3, class V3, class = decltype(std::declval<const Img&>().cols), class = decltype(std::declval<const Img&>().rows),
               class = decltype(std::declval<const M3&>()(0, 0)), class = decltype(std::declval<const V3&>()(0))>
     void addImage_fixed_simDistorted(const unsigned int imageID, const Img& image, const M3& K, const M3& R, const V3& t, const double k1, const double k2,
                                      std::map<unsigned int, float>& viewSimilarity, const int maxImgWidth = 1920, const bool loadAndStoreSegments = true)
     {
-        double k[9], r[9], tt[3];
-        flatten(K, R, t, k, r, tt);
         const double dist[2] = { k1, k2 };
-        std::vector<uint32_t> ids;
-        std::vector<float> sims;
-        for (auto& kv : viewSimilarity) { ids.push_back(kv.first); sims.push_back(kv.second); }
-        sims.push_back(0.0f);
-        report(add_from_image(detail::prio<1>(), imageID, image, k, r, tt, ids.data(), sims.data(), (int)ids.size(), maxImgWidth, loadAndStoreSegments, dist));
+        add_from_image(detail::prio<1>(), imageID, image, K, R, t, viewSimilarity, dist, maxImgWidth, loadAndStoreSegments);
     }
     // cv::initUndistortRectifyMap + cv::remap(image, image, ..., INTER_LINEAR, BORDER_CONSTANT) of the drivers, in place on image.data (staged
     // through a temporary, as remap does when source and destination coincide): undistort, then addImage -- the drivers' own structure
@@ -245,28 +227,26 @@ public:
     void addImageJPEG(const unsigned int imageID, const unsigned char* bytes, const size_t n, const M3& K, const M3& R, const V3& t,
                       std::list<unsigned int>& worldpointIDs, const int maxImgWidth = 1920, const bool loadAndStoreSegments = true)
     {
-        add_jpeg(imageID, bytes, n, K, R, t, nullptr, &worldpointIDs, nullptr, maxImgWidth, loadAndStoreSegments);
+        add_one(makeEntry(imageID, bytes, n, K, R, t, worldpointIDs), maxImgWidth, loadAndStoreSegments);
     }
     template <class M3, class V3, class = decltype(std::declval<const M3&>()(0, 0)), class = decltype(std::declval<const V3&>()(0))>
     void addImageJPEGDistorted(const unsigned int imageID, const unsigned char* bytes, const size_t n, const M3& K, const M3& R, const V3& t, const double k1,
                                const double k2, std::list<unsigned int>& worldpointIDs, const int maxImgWidth = 1920, const bool loadAndStoreSegments = true)
     {
-        const double dist[2] = { k1, k2 };
-        add_jpeg(imageID, bytes, n, K, R, t, dist, &worldpointIDs, nullptr, maxImgWidth, loadAndStoreSegments);
+        add_one(makeEntry(imageID, bytes, n, K, R, t, worldpointIDs).distorted(k1, k2), maxImgWidth, loadAndStoreSegments);
     }
     template <class M3, class V3, class = decltype(std::declval<const M3&>()(0, 0)), class = decltype(std::declval<const V3&>()(0))>
     void addImage_fixed_simJPEG(const unsigned int imageID, const unsigned char* bytes, const size_t n, const M3& K, const M3& R, const V3& t,
                                 std::map<unsigned int, float>& viewSimilarity, const int maxImgWidth = 1920, const bool loadAndStoreSegments = true)
     {
-        add_jpeg(imageID, bytes, n, K, R, t, nullptr, nullptr, &viewSimilarity, maxImgWidth, loadAndStoreSegments);
+        add_one(makeEntry(imageID, bytes, n, K, R, t, viewSimilarity), maxImgWidth, loadAndStoreSegments);
     }
     template <class M3, class V3, class = decltype(std::declval<const M3&>()(0, 0)), class = decltype(std::declval<const V3&>()(0))>
     void addImage_fixed_simJPEGDistorted(const unsigned int imageID, const unsigned char* bytes, const size_t n, const M3& K, const M3& R, const V3& t,
                                          const double k1, const double k2, std::map<unsigned int, float>& viewSimilarity, const int maxImgWidth = 1920,
                                          const bool loadAndStoreSegments = true)
     {
-        const double dist[2] = { k1, k2 };
-        add_jpeg(imageID, bytes, n, K, R, t, dist, nullptr, &viewSimilarity, maxImgWidth, loadAndStoreSegments);
+        add_one(makeEntry(imageID, bytes, n, K, R, t, viewSimilarity).distorted(k1, k2), maxImgWidth, loadAndStoreSegments);
     }
     // the size and channel count (1: grey, 3: B, G, R) a JPEG file decodes to, from its headers alone -- no device; false: not a file the decoder takes
     static bool jpegSize(const unsigned char* bytes, const size_t n, unsigned int& width, unsigned int& height, unsigned int& channels)
@@ -327,16 +307,8 @@ public:
     // the per-entry statuses (L3D_OK, or the code the single call would have failed with); the causes are printed, one line per failed entry
     std::vector<int> addImages(const std::vector<ImageEntry>& entries, const int maxImgWidth = 1920, const bool loadAndStoreSegments = true)
     {
-        std::vector<l3d_image_entry> e(entries.size());
-        for (size_t i = 0; i < entries.size(); ++i) {
-            const ImageEntry& s = entries[i];
-            l3d_image_entry& d = e[i];
-            d.image_id = s.imageID;
-            d.pixels = s.pixels; d.width = s.width; d.height = s.height; d.channels = s.channels; d.row_stride = s.step;
-            d.jpeg = s.jpeg; d.jpeg_bytes = s.jpeg_bytes;
-            d.K = s.K; d.R = s.R; d.t = s.t; d.dist = s.has_dist ? s.dist : nullptr;
-            d.link_ids = s.link_ids.data(); d.sims = s.fixed_sim ? s.sims.data() : nullptr; d.n_links = (int)s.link_ids.size();
-        }
+        std::vector<l3d_image_entry> e;
+        for (const ImageEntry& s : entries) e.push_back(to_c(s));
         std::vector<int> status(entries.size(), L3D_ERR_INVALID);        // (a call refused as a whole -- no object -- leaves them)
         const int rc = l3d_line3d_add_images(h_, e.data(), (int)e.size(), data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0, status.data());
         bool any = rc != L3D_OK;
@@ -418,45 +390,50 @@ private:
     {
         for (int i = 0; i < 3; ++i) { tt[i] = t(i); for (int j = 0; j < 3; ++j) { k[i * 3 + j] = K(i, j); r[i * 3 + j] = R(i, j); } }
     }
-    // `image` with pixels (cv::Mat: .data, .step, .channels()): detect on the device.  links: world point ids (sims == nullptr) or view similarities
-    template <class Img, class = decltype(static_cast<const unsigned char*>(std::declval<const Img&>().data)),
-              class = decltype(static_cast<size_t>(std::declval<const Img&>().step)), class = decltype(static_cast<int>(std::declval<const Img&>().channels()))>
-    int add_from_image(detail::prio<1>, unsigned int imageID, const Img& image, const double* k, const double* r, const double* tt, const uint32_t* ids,
-                       const float* sims, int n, int maxImgWidth, bool loadAndStoreSegments, const double* dist = nullptr)
+    // the l3d_image_entry of an entry (it points into `s`)
+    static l3d_image_entry to_c(const ImageEntry& s)
     {
-        const unsigned char* px = static_cast<const unsigned char*>(image.data);
-        const size_t step = static_cast<size_t>(image.step);
-        const int ch = static_cast<int>(image.channels()), w = (int)image.cols, h = (int)image.rows;
-        if (dist && sims) return l3d_line3d_add_image_pixels_fixed_sim_distorted(h_, imageID, px, w, h, ch, step, k, r, tt, dist, ids, sims, n, data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0);
-        if (dist) return l3d_line3d_add_image_pixels_distorted(h_, imageID, px, w, h, ch, step, k, r, tt, dist, ids, n, data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0);
-        if (sims) return l3d_line3d_add_image_pixels_fixed_sim(h_, imageID, px, w, h, ch, step, k, r, tt, ids, sims, n, data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0);
-        return l3d_line3d_add_image_pixels(h_, imageID, px, w, h, ch, step, k, r, tt, ids, n, data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0);
+        l3d_image_entry d;
+        d.image_id = s.imageID;
+        d.pixels = s.pixels; d.width = s.width; d.height = s.height; d.channels = s.channels; d.row_stride = s.step;
+        d.jpeg = s.jpeg; d.jpeg_bytes = s.jpeg_bytes;
+        d.K = s.K; d.R = s.R; d.t = s.t; d.dist = s.has_dist ? s.dist : nullptr;
+        d.link_ids = s.link_ids.data(); d.sims = s.fixed_sim ? s.sims.data() : nullptr; d.n_links = (int)s.link_ids.size();
+        return d;
+    }
+    // every image and JPEG form: one entry through the library's one route (l3d_line3d_add_image_entry)
+    void add_one(const ImageEntry& s, int maxImgWidth, bool loadAndStoreSegments)
+    {
+        const l3d_image_entry e = to_c(s);
+        report(l3d_line3d_add_image_entry(h_, &e, data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0));
+    }
+    // `image` with pixels (cv::Mat: .data, .step, .channels()): detect on the device.  links: world point ids or view similarities; dist: null or k1, k2
+    template <class Img, class M3, class V3, class Links, class = decltype(static_cast<const unsigned char*>(std::declval<const Img&>().data)),
+              class = decltype(static_cast<size_t>(std::declval<const Img&>().step)), class = decltype(static_cast<int>(std::declval<const Img&>().channels()))>
+    void add_from_image(detail::prio<1>, unsigned int imageID, const Img& image, const M3& K, const M3& R, const V3& t, const Links& links, const double* dist,
+                        int maxImgWidth, bool loadAndStoreSegments)
+    {
+        ImageEntry e = makeEntry(imageID, image, K, R, t, links);
+        if (dist) { add_one(e.distorted(dist[0], dist[1]), maxImgWidth, loadAndStoreSegments); return; }
+        // without coefficients: the two calls named after the image, which are that entry with dist left out
+        const int n = (int)e.link_ids.size(), store = loadAndStoreSegments ? 1 : 0;
+        report(e.fixed_sim ? l3d_line3d_add_image_pixels_fixed_sim(h_, imageID, e.pixels, e.width, e.height, e.channels, e.step, e.K, e.R, e.t, e.link_ids.data(), e.sims.data(), n,
+                                                                   data_directory_.c_str(), maxImgWidth, store)
+                           : l3d_line3d_add_image_pixels(h_, imageID, e.pixels, e.width, e.height, e.channels, e.step, e.K, e.R, e.t, e.link_ids.data(), n, data_directory_.c_str(),
+                                                         maxImgWidth, store));
     }
     // `image` with a size only: the segment cache or nothing
-    template <class Img>
-    int add_from_image(detail::prio<0>, unsigned int imageID, const Img& image, const double* k, const double* r, const double* tt, const uint32_t* ids,
-                       const float* sims, int n, int maxImgWidth, bool loadAndStoreSegments, const double* = nullptr)
+    template <class Img, class M3, class V3, class Links>
+    void add_from_image(detail::prio<0>, unsigned int imageID, const Img& image, const M3& K, const M3& R, const V3& t, const Links& links, const double*,
+                        int maxImgWidth, bool loadAndStoreSegments)
     {
+        ImageEntry e;
+        flatten(K, R, t, e.K, e.R, e.t);
+        set_links(e, links);
         const unsigned int w = image.cols > 0 ? (unsigned int)image.cols : 0u, h = image.rows > 0 ? (unsigned int)image.rows : 0u;
-        if (sims) return l3d_line3d_add_image_fixed_sim_ex(h_, imageID, w, h, nullptr, 0, k, r, tt, ids, sims, n, data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0);
-        return l3d_line3d_add_image_ex(h_, imageID, w, h, nullptr, 0, k, r, tt, ids, n, data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0);
-    }
-    template <class M3, class V3>
-    void add_jpeg(unsigned int imageID, const unsigned char* bytes, size_t n, const M3& K, const M3& R, const V3& t, const double* dist,
-                  std::list<unsigned int>* worldpointIDs, std::map<unsigned int, float>* viewSimilarity, int maxImgWidth, bool loadAndStoreSegments)
-    {
-        double k[9], r[9], tt[3];
-        flatten(K, R, t, k, r, tt);
-        if (worldpointIDs) {
-            std::vector<uint32_t> wps(worldpointIDs->begin(), worldpointIDs->end());
-            report(l3d_line3d_add_image_jpeg(h_, imageID, bytes, n, k, r, tt, dist, wps.data(), (int)wps.size(), data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0));
-            return;
-        }
-        std::vector<uint32_t> ids;
-        std::vector<float> sims;
-        for (auto& kv : *viewSimilarity) { ids.push_back(kv.first); sims.push_back(kv.second); }
-        report(l3d_line3d_add_image_jpeg_fixed_sim(h_, imageID, bytes, n, k, r, tt, dist, ids.data(), sims.data(), (int)ids.size(), data_directory_.c_str(), maxImgWidth,
-                                                   loadAndStoreSegments ? 1 : 0));
+        const int n = (int)e.link_ids.size(), store = loadAndStoreSegments ? 1 : 0;
+        report(e.fixed_sim ? l3d_line3d_add_image_fixed_sim_ex(h_, imageID, w, h, nullptr, 0, e.K, e.R, e.t, e.link_ids.data(), e.sims.data(), n, data_directory_.c_str(), maxImgWidth, store)
+                           : l3d_line3d_add_image_ex(h_, imageID, w, h, nullptr, 0, e.K, e.R, e.t, e.link_ids.data(), n, data_directory_.c_str(), maxImgWidth, store));
     }
     static void set_links(ImageEntry& e, const std::list<unsigned int>& worldpointIDs) { e.link_ids.assign(worldpointIDs.begin(), worldpointIDs.end()); }
     static void set_links(ImageEntry& e, const std::map<unsigned int, float>& viewSimilarity)

@@ -776,21 +776,17 @@ int l3d_undistort_image(l3d_ctx* ctx, const unsigned char* pixels, int width, in
                         double k1, double k2, unsigned char* out, size_t out_row_stride);
 int l3d_detect_segments_distorted(l3d_ctx* ctx, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, int new_width, int new_height,
                                   float min_length, int max_segments, double fx, double fy, double cx, double cy, double k1, double k2, float** segments, int* n);
-/* Line3D::addImage / addImage_fixed_sim from pixels (line3D.cc:95-217, 220-324): cache present and load_and_store != 0: the cache is
- * loaded; otherwise the segments are detected (rescaled by the max_img_width rule, min_length = 0.005 sqrt(rows^2 + cols^2), at most 3000) and,
- * with load_and_store != 0, the cache is written; load_and_store == 0 removes a stale cache first.  No segment found: L3D_OK and no view
- * (line3D.cc:186-190).  On a node object the segments are detected once, on rank 0's device. */
+/* Line3D::addImage / addImage_fixed_sim from pixels (line3D.cc:95-217, 220-324): the image entry (THE ADD FAMILY, below) with pixels filled and no
+ * dist.  The detector runs at the size the max_img_width rule gives, with min_length = 0.005 sqrt(rows^2 + cols^2) and at most 3000 segments. */
 int l3d_line3d_add_image_pixels(l3d_line3d* h, uint32_t image_id, const unsigned char* pixels, int width, int height, int channels, size_t row_stride,
                                 const double* K, const double* R, const double* t, const uint32_t* worldpoint_ids, int n_worldpoints,
                                 const char* data_directory, int max_img_width, int load_and_store);
 int l3d_line3d_add_image_pixels_fixed_sim(l3d_line3d* h, uint32_t image_id, const unsigned char* pixels, int width, int height, int channels, size_t row_stride,
                                           const double* K, const double* R, const double* t, const uint32_t* sim_ids, const float* sims, int n_sims,
                                           const char* data_directory, int max_img_width, int load_and_store);
-/* The same with the drivers' undistort block in front of the detector (main_vsfm.cpp:243-273): dist = (k1, k2) as above; fx, fy, cx, cy are
- * K[0], K[4], K[2], K[5] of the full-resolution K the caller passes, which the view keeps (the drivers undistort onto the same K).  Both
- * coefficients within 1e-12: the calls above.  Non-zero coefficients with K[1] != 0 (skew): L3D_ERR_UNSUPPORTED.  The cache behaviour is
- * unchanged: a cache that is present and wanted is loaded and the pixels are not touched (line3D.cc:143-168).  On a node object the work is
- * done once, on rank 0's device.  l3d_line3d_undistort_image: l3d_undistort_image with the object's device and K. */
+/* The same with the drivers' undistort block in front of the detector (main_vsfm.cpp:243-273): the entry with dist = (k1, k2) as above, which
+ * may not be NULL here; fx, fy, cx, cy are K[0], K[4], K[2], K[5] of the full-resolution K the caller passes, which the view keeps (the drivers
+ * undistort onto the same K).  l3d_line3d_undistort_image: l3d_undistort_image with the object's device and K. */
 int l3d_line3d_add_image_pixels_distorted(l3d_line3d* h, uint32_t image_id, const unsigned char* pixels, int width, int height, int channels, size_t row_stride,
                                           const double* K, const double* R, const double* t, const double dist[2], const uint32_t* worldpoint_ids, int n_worldpoints,
                                           const char* data_directory, int max_img_width, int load_and_store);
@@ -850,10 +846,7 @@ int l3d_line3d_undistort_image(l3d_line3d* h, const unsigned char* pixels, int w
  *   l3d_detect_segments_jpeg   l3d_detect_segments on the decoded image, which stays on the device; camera: NULL, or (fx, fy, cx, cy, k1, k2) of
  *                              l3d_detect_segments_distorted.  Images below 8x8 are refused as l3d_detect_segments refuses them
  *   l3d_line3d_add_image_jpeg, l3d_line3d_add_image_jpeg_fixed_sim
- *                              l3d_line3d_add_image_pixels_distorted / ..._fixed_sim_distorted with the file in place of the pixels.  dist NULL, or
- *                              both coefficients within 1e-12: no undistortion.  The cache rules are unchanged; the size for the cache name and
- *                              the max_img_width rule comes from the headers, and a cache that is present and wanted is loaded WITHOUT
- *                              entropy-decoding the file.  On a node object rank 0's device does the work once
+ *                              the image entry (THE ADD FAMILY, below) with the file in place of the pixels; dist may be NULL
  *   l3d_line3d_decode_jpeg     l3d_decode_jpeg with the object's device
  *   l3d_test_jpeg_coefficients (tests) host only: the quantised blocks as above (callee-allocated, l3d_free), qt[3][64] per component in natural
  *                              order, layout[27] = width, height, components, hmax, vmax, MCUs per row, MCU rows, restart interval, rgb, then per
@@ -889,15 +882,7 @@ int l3d_test_jpeg_coefficients(const unsigned char* bytes, size_t n, int16_t** c
  *                             stream ...) fails alone and has no segments, the others are not affected.  The call returns L3D_OK when the batch
  *                             was processed, else the code of a device failure (entries not finished by then carry it in their status);
  *                             l3d_last_error then holds one line per failed entry, "entry <i>: <message>".
- * l3d_line3d_add_images       exactly the sequence of l3d_line3d_add_image_pixels[_fixed_sim][_distorted] / l3d_line3d_add_image_jpeg[_fixed_sim]
- *                             calls, in entry order: the cache decision is taken per entry (an entry whose cache is present and wanted is neither
- *                             decoded nor detected), every other entry goes through the batched detector, then the views are added in entry
- *                             order.  sims == NULL: link_ids are world point ids; otherwise view ids with their similarities.  dist NULL, or both
- *                             coefficients within 1e-12: no undistortion.  status[i] (may be NULL) is what the single call would have returned;
- *                             a failed entry fails alone with the single call's message, an image without segments is L3D_OK and no view.  The
- *                             call returns L3D_OK when the batch was processed, else a device failure's code (entries added before it stay added);
- *                             l3d_line3d_last_error holds one line per failed entry, "image <id>: <message>".  On a node object rank 0's device
- *                             does the detection.
+ * l3d_line3d_add_images       THE ADD FAMILY, below
  * ================================================================================================= */
 typedef struct l3d_detect_entry {
     const unsigned char* pixels; int width, height, channels; size_t row_stride;   /* or: */
@@ -907,6 +892,47 @@ typedef struct l3d_detect_entry {
 } l3d_detect_entry;
 int l3d_detect_segments_batch(l3d_ctx* ctx, const l3d_detect_entry* e, int n, float** segments, int* offsets /* n + 1 */, int* status /* n */);
 
+/* =================================================================================================
+ * THE ADD FAMILY: Line3D::addImage / addImage_fixed_sim (line3D.cc:95-342) in every form the library takes an image in.
+ *
+ * An image to add is an ENTRY: its id; the image -- 8-bit pixels (as l3d_detect_segments takes them) or a baseline JPEG file in memory, exactly one
+ * of the two -- the camera K, R, t; dist, NULL or OpenCV-convention k1, k2 (the image is undistorted on the device with K's fx, fy, cx, cy before
+ * the detector sees it; both within 1e-12: as NULL); and the links, of one of two kinds: sims == NULL: link_ids are the world point ids the view
+ * observes (addImage); otherwise view ids with their similarities (addImage_fixed_sim).  The segment-taking forms (l3d_line3d_add_image[_fixed_sim],
+ * ..._ex, ..._cached, above) bring segments, or an opened segment cache, where the entry has its image.
+ *
+ * ONE ROUTE adds an entry (line3d_amd/csrc/line3d_host.cpp: add_one), and every form below only fills an entry and takes it.  Its decisions,
+ * in order -- the first that applies ends the call with its code, the message in l3d_line3d_last_error:
+ *   1. the image: a JPEG file's headers give the size (a file the decoder refuses: its code and message); dist given: K NULL is
+ *      L3D_ERR_INVALID, non-zero coefficients with K[1] != 0 (skew) L3D_ERR_UNSUPPORTED; a size below 1x1: "image is empty!"
+ *   2. the cache decision, once: the file is "<data_directory>/segments_<id>_<w'>x<h'>_coll<0|1>.bin", (w', h') the size after the max_img_width
+ *      down-scaling the detector works at (line3D.cc:133-138; the view keeps the original size).  Present and load_and_store != 0: it stands in for
+ *      the image, which is neither decoded nor detected.  Present and load_and_store == 0: stale, to be removed.  Absent: to be written when
+ *      load_and_store != 0
+ *   3. unless the cache stands in: the detector (a JPEG file is entropy-decoded only here), on a node object once, on rank 0's device.  No
+ *      segment found: L3D_OK and no view (line3D.cc:186-190); a stale cache is removed
+ *   4. the guards, on every rank of a node object: "reconstruction already performed...", "imageID already in use!", "unlinked images cannot be
+ *      added!" (n_links == 0), "image is empty!" (a size of 0; in the forms with a data directory also K, R or t NULL -- the forms without
+ *      one, l3d_line3d_add_image[_fixed_sim] and ..._cached, answer a NULL K, R or t with "no segments" in step 5)
+ *   5. the view: segments AND collinearities from the cache file (a file that cannot be read: its code and message), or the stale file removed
+ *      and the detected segments, the cache noted to be written by prepare() (by rank 0 only); then the links
+ * The guards come after the detector: a second image of an id in use in which nothing is detected is L3D_OK (and removes a stale cache).
+ *
+ * l3d_line3d_add_image_entry  the single call for an entry.  Returns the code; l3d_line3d_last_error holds the bare message.  An entry whose pixels
+ *                             and jpeg are both NULL is here still the image its fields state, and is refused in the words of the call named
+ *                             after it: any of width, height, channels, row_stride set: pixels ("image is empty!" for a size below 1x1); none
+ *                             set: a JPEG file ("jpeg: null argument").  Both given: L3D_ERR_INVALID, as in l3d_line3d_add_images
+ * l3d_line3d_add_images       n entries in one call: steps 1 and 2 per entry, ONE run of l3d_detect_segments_batch over all entries that need the
+ *                             detector, then steps 3 to 5 per entry in entry order -- exactly the sequence of the single calls (but an entry with
+ *                             neither or both of pixels and jpeg is L3D_ERR_INVALID, "an entry needs either ...").  status[i] (may be
+ *                             NULL) is what the single call would have returned: a failed entry fails alone, an image without segments is L3D_OK and
+ *                             no view.  The call returns L3D_OK when the batch was processed, else a device failure's code (entries added before
+ *                             it stay added); l3d_line3d_last_error holds one line per failed entry, "image <id>: <message>"
+ * The named forms are the entry with these fields filled:
+ *   l3d_line3d_add_image_pixels[_fixed_sim]             pixels, dist NULL
+ *   l3d_line3d_add_image_pixels[_fixed_sim]_distorted   pixels, dist -- which may not be NULL here: L3D_ERR_INVALID
+ *   l3d_line3d_add_image_jpeg[_fixed_sim]               jpeg, dist or NULL
+ * ================================================================================================= */
 typedef struct l3d_image_entry {
     uint32_t image_id;
     const unsigned char* pixels; int width, height, channels; size_t row_stride;
@@ -914,6 +940,7 @@ typedef struct l3d_image_entry {
     const double *K, *R, *t, *dist;                 /* dist: NULL or k1, k2 */
     const uint32_t* link_ids; const float* sims; int n_links;   /* sims == NULL: world point ids; else view similarities */
 } l3d_image_entry;
+int l3d_line3d_add_image_entry(l3d_line3d* h, const l3d_image_entry* e, const char* data_directory, int max_img_width, int load_and_store);
 int l3d_line3d_add_images(l3d_line3d* h, const l3d_image_entry* e, int n, const char* data_directory, int max_img_width, int load_and_store, int* status);
 
 /* The detector's stages on their own, exported for tests (tests/test_gpu_detect_stages.py): the same kernels with the same launch shapes

@@ -663,242 +663,110 @@ int l3d_line3d_reset(l3d_line3d* h)
     return L3D_OK;
 }
 
-static int add_common(l3d_line3d* h, uint32_t id, unsigned width, unsigned height, const float* segs, int n,
-                      const double* K, const double* R, const double* t, int n_links)
+// ---- the add family: every exported form fills a request, and one route adds it ---------------------------------------------------------------
+// (Line3D::addImage / addImage_fixed_sim, line3D.cc:95-342.)  The order of the route's decisions, for every form:
+//   1. an image (pixels or a JPEG file) only: the JPEG headers, the camera of the undistortion, "image is empty!" for a size below 1x1
+//   2. the forms with a data directory: the cache decision (cache_decision), taken once and handed on
+//   3. an image whose cache does not stand in for it: the detector, on rank 0's device.  Nothing found: no view, L3D_OK, a stale cache removed
+//   4. per rank (add_entry): the guards, then the decision's outcome -- the view from the cache file, or the stale file removed and the view from
+//      the segments, its cache noted for prepare() to write -- then the links
+// The guards (4) come AFTER the detector (3) for an image: a second image of an id in use in which nothing is detected is L3D_OK and adds nothing.
+// That is the behaviour the forms had one by one (tests/golden/add_table.json records it); moving the cheap guards to the front changes it.
+namespace l3dh {
+enum class AddKind { Segments, Cached, Pixels, Jpeg };
+// an l3d_image_entry, or in place of its image the caller's segments or an opened segment cache
+struct AddRequest {
+    AddKind kind = AddKind::Segments;
+    l3d_image_entry e{};                            // image_id, the image, width x height, K, R, t, dist, the links
+    const float* segs = nullptr; int n = 0;         // Segments
+    const l3d_segment_cache* cache = nullptr;       // Cached
+    bool cache_rules = false;                       // the form has a data directory: every one but add_image, add_image_fixed_sim, add_image_cached
+    bool dist_required = false;                     // the _distorted forms: a null dist is refused (elsewhere it means no distortion)
+    bool image() const { return kind == AddKind::Pixels || kind == AddKind::Jpeg; }
+};
+enum class Cache { None, Load, Stale, Write };      // no cache rules or nothing to do | read the file | remove the file | note the file for prepare()
+// what steps 1 and 2 found out about a request
+struct AddPlan {
+    unsigned width = 0, height = 0;                 // of the view (a JPEG file: from its headers)
+    int channels = 0;
+    bool undistort = false;
+    l3d::DetCamera cam;
+    Cache cache = Cache::None;
+    std::string file;                               // the cache file's path
+    bool detect = false;
+    unsigned new_w = 0, new_h = 0;                  // the size the detector works at
+    float min_length = 0.0f;
+};
+
+static AddRequest add_request(AddKind kind, uint32_t id, unsigned width, unsigned height, const double* K, const double* R, const double* t, const uint32_t* link_ids,
+                              const float* sims, int n_links, bool cache_rules = true)
 {
-    if (!h) return L3D_ERR_INVALID;
-    // the guards of addImage, line3D.cc:101-127 (print-and-return in the reference; a status here)
+    AddRequest rq;
+    rq.kind = kind; rq.cache_rules = cache_rules;
+    rq.e.image_id = id; rq.e.width = (int)width; rq.e.height = (int)height;
+    rq.e.K = K; rq.e.R = R; rq.e.t = t;
+    rq.e.link_ids = link_ids; rq.e.sims = sims; rq.e.n_links = n_links;
+    return rq;
+}
+static AddRequest pixels_request(uint32_t id, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, const double* K, const double* R,
+                                 const double* t, const double* dist, bool dist_required, const uint32_t* link_ids, const float* sims, int n_links)
+{
+    AddRequest rq = add_request(AddKind::Pixels, id, (unsigned)width, (unsigned)height, K, R, t, link_ids, sims, n_links);
+    rq.e.pixels = pixels; rq.e.channels = channels; rq.e.row_stride = row_stride;
+    rq.e.dist = dist; rq.dist_required = dist_required;
+    return rq;
+}
+static AddRequest jpeg_request(uint32_t id, const unsigned char* bytes, size_t n, const double* K, const double* R, const double* t, const double* dist,
+                               const uint32_t* link_ids, const float* sims, int n_links)
+{
+    AddRequest rq = add_request(AddKind::Jpeg, id, 0, 0, K, R, t, link_ids, sims, n_links);
+    rq.e.jpeg = bytes; rq.e.jpeg_bytes = n; rq.e.dist = dist;
+    return rq;
+}
+// single: l3d_line3d_add_image_entry, where an entry without an image is still the image its fields state -- any of width, height, channels,
+// row_stride set: pixels, else a JPEG file -- so that a null image is refused in the words of the call named after it
+static int entry_request(L* h, const l3d_image_entry& e, AddRequest& rq, bool single)
+{
+    const bool none = !e.pixels && !e.jpeg;
+    if ((e.pixels && e.jpeg) || (none && !single)) return h->fail(L3D_ERR_INVALID, "add_images: an entry needs either pixels or a JPEG file");
+    const bool pixels = e.pixels || (none && (e.width || e.height || e.channels || e.row_stride));
+    rq.kind = pixels ? AddKind::Pixels : AddKind::Jpeg;
+    rq.e = e; rq.cache_rules = true;
+    return L3D_OK;
+}
+
+// the guards of addImage, line3D.cc:101-127 (print-and-return in the reference; a status here), and the null checks
+static int add_guards(L* h, const AddRequest& rq, const AddPlan& p)
+{
+    const l3d_image_entry& e = rq.e;
+    if (rq.kind == AddKind::Cached && !rq.cache) return h->fail(L3D_ERR_INVALID, "null segment cache");
     if (h->computation) return h->fail(L3D_ERR_INVALID, "reconstruction already performed! cannot add more images (try reset first)");
-    if (h->views.count(id)) return h->fail(L3D_ERR_INVALID, "imageID already in use!");
-    if (n_links == 0) return h->fail(L3D_ERR_INVALID, "unlinked images cannot be added!");
-    if (width == 0 || height == 0) return h->fail(L3D_ERR_INVALID, "image is empty!");
-    if (n <= 0 || !segs || !K || !R || !t) return h->fail(L3D_ERR_INVALID, "no segments");   // detectLineSegments failed: no view, :186-190
-    return make_view(h, id, width, height, segs, n, K, R, t);
-}
-
-// addImage_fixed_sim with precomputed segments (the detector is out of scope), line3D.cc:220-342
-int l3d_line3d_add_image_fixed_sim(l3d_line3d* h, uint32_t id, unsigned width, unsigned height, const float* segs, int n,
-                                   const double* K, const double* R, const double* t,
-                                   const uint32_t* sim_ids, const float* sims, int n_sims)
-{
-    if (h && h->node) return node_each(h, [&](L* r) { return l3d_line3d_add_image_fixed_sim(r, id, width, height, segs, n, K, R, t, sim_ids, sims, n_sims); });
-    int rc = add_common(h, id, width, height, segs, n, K, R, t, n_sims);
-    if (rc) return rc;
-    for (int i = 0; i < n_sims; ++i)                       // setViewSimilarity, :1938-1946
-        if (sims[i] > 0.01f) h->view_similarities[id][sim_ids[i]] = sims[i];
+    if (h->views.count(e.image_id)) return h->fail(L3D_ERR_INVALID, "imageID already in use!");
+    if (e.n_links == 0) return h->fail(L3D_ERR_INVALID, "unlinked images cannot be added!");
+    if (p.width == 0 || p.height == 0 || (rq.cache_rules && (!e.K || !e.R || !e.t))) return h->fail(L3D_ERR_INVALID, "image is empty!");
     return L3D_OK;
 }
 
-// addImage with precomputed segments, line3D.cc:95-217
-int l3d_line3d_add_image(l3d_line3d* h, uint32_t id, unsigned width, unsigned height, const float* segs, int n,
-                         const double* K, const double* R, const double* t, const uint32_t* worldpoints, int n_wps)
+// line3D.cc:128-199: the cache file of the view -- named after the size the detector works at (:133-138) -- probed once
+static int cache_decision(L* h, uint32_t id, unsigned width, unsigned height, const char* data_directory, int max_img_width, int load_and_store, AddPlan& p)
 {
-    if (h && h->node) return node_each(h, [&](L* r) { return l3d_line3d_add_image(r, id, width, height, segs, n, K, R, t, worldpoints, n_wps); });
-    int rc = add_common(h, id, width, height, segs, n, K, R, t, n_wps);
-    if (rc) return rc;
-    process_worldpoints(h, id, worldpoints, n_wps);
-    return L3D_OK;
-}
-
-// addImage when the segment cache exists, line3D.cc:160-168: segments and collinearities come from the file
-int l3d_line3d_add_image_cached(l3d_line3d* h, uint32_t id, unsigned width, unsigned height, const l3d_segment_cache* cache,
-                                const double* K, const double* R, const double* t, const uint32_t* worldpoints, int n_wps)
-{
-    if (!h) return L3D_ERR_INVALID;
-    if (h->node) return node_each(h, [&](L* r) { return l3d_line3d_add_image_cached(r, id, width, height, cache, K, R, t, worldpoints, n_wps); });
-    if (!cache) return h->fail(L3D_ERR_INVALID, "null segment cache");
-    const int n = l3d_segment_cache_num_segments(cache), nc = l3d_segment_cache_num_collinearities(cache);
-    std::vector<float> segs((size_t)n * 4 + 1), cw((size_t)nc + 1);
-    std::vector<int32_t> ci((size_t)nc + 1), cj((size_t)nc + 1);
-    l3d_segment_cache_get(cache, segs.data(), ci.data(), cj.data(), cw.data());
-    if (h->computation) return h->fail(L3D_ERR_INVALID, "reconstruction already performed! cannot add more images (try reset first)");
-    if (h->views.count(id)) return h->fail(L3D_ERR_INVALID, "imageID already in use!");
-    if (n_wps == 0) return h->fail(L3D_ERR_INVALID, "unlinked images cannot be added!");
-    if (width == 0 || height == 0) return h->fail(L3D_ERR_INVALID, "image is empty!");
-    if (n <= 0 || !K || !R || !t) return h->fail(L3D_ERR_INVALID, "no segments");
-    int rc = make_view(h, id, width, height, segs.data(), n, K, R, t, ci.data(), cj.data(), cw.data(), nc);
-    if (rc) return rc;
-    process_worldpoints(h, id, worldpoints, n_wps);
-    return L3D_OK;
-}
-
-// the cache decisions of addImage / addImage_fixed_sim, line3D.cc:128-199: returns 1 when the view was added from the cache file,
-// 0 when the caller's segments are to be used (cache_path set when the file is to be written), < 0: error code negated
-static int add_from_cache_or_plan_write(l3d_line3d* h, uint32_t id, unsigned width, unsigned height, const double* K, const double* R, const double* t,
-                                        const char* data_directory, int max_img_width, int load_and_store, std::string& cache_path, std::string* expected = nullptr)
-{
-    unsigned new_w = width, new_h = height;
+    p.new_w = width; p.new_h = height;
     if (max_img_width > 0 && (int)std::max(width, height) > max_img_width) {                 // :133-138
         const float scale = float(max_img_width) / fmaxf((float)height, (float)width);
-        new_w = (unsigned)roundf(float(width) * scale);
-        new_h = (unsigned)roundf(float(height) * scale);
+        p.new_w = (unsigned)roundf(float(width) * scale);
+        p.new_h = (unsigned)roundf(float(height) * scale);
     }
     char name[160];
-    if (l3d_segment_cache_filename(id, new_w, new_h, h->use_collinearity ? 1 : 0, name, sizeof(name)) != L3D_OK) return -L3D_ERR_INVALID;
-    const std::string file = std::string(data_directory ? data_directory : "") + name;
-    if (expected) *expected = file;
-    FILE* f = fopen(file.c_str(), "rb");
-    const bool exists = f != nullptr;
+    if (l3d_segment_cache_filename(id, p.new_w, p.new_h, (h->node ? rank0(h) : h)->use_collinearity ? 1 : 0, name, sizeof(name)) != L3D_OK) return L3D_ERR_INVALID;
+    p.file = std::string(data_directory ? data_directory : "") + name;
+    FILE* f = fopen(p.file.c_str(), "rb");
     if (f) fclose(f);
-    cache_path.clear();
-    if (exists && !load_and_store) { remove(file.c_str()); return 0; }                        // :153-156
-    if (exists) {                                                                            // :159-168
-        l3d_segment_cache* cache = nullptr;
-        int rc = l3d_segment_cache_read(file.c_str(), &cache);
-        if (rc != L3D_OK) { h->fail(rc, l3d_segment_cache_last_error(cache)); l3d_segment_cache_free(cache); return -rc; }   // (the reference exits, serialization.h:63)
-        const int n = l3d_segment_cache_num_segments(cache), nc = l3d_segment_cache_num_collinearities(cache);
-        std::vector<float> segs((size_t)n * 4 + 1), cw((size_t)nc + 1);
-        std::vector<int32_t> ci((size_t)nc + 1), cj((size_t)nc + 1);
-        l3d_segment_cache_get(cache, segs.data(), ci.data(), cj.data(), cw.data());
-        l3d_segment_cache_free(cache);
-        if (n <= 0) return -h->fail(L3D_ERR_INVALID, "no segments");
-        rc = make_view(h, id, width, height, segs.data(), n, K, R, t, ci.data(), cj.data(), cw.data(), nc);
-        return rc ? -rc : 1;
-    }
-    if (load_and_store) cache_path = file;                                                   // :180-182
-    return 0;
-}
-
-int l3d_line3d_add_image_ex(l3d_line3d* h, uint32_t id, unsigned width, unsigned height, const float* segs, int n, const double* K, const double* R,
-                            const double* t, const uint32_t* worldpoints, int n_wps, const char* data_directory, int max_img_width, int load_and_store)
-{
-    if (!h) return L3D_ERR_INVALID;
-    if (h->node)        // (every rank makes the cache decision of the reference; the file is written once, by rank 0)
-        return node_each(h, [&](L* r) {
-            const int rc = l3d_line3d_add_image_ex(r, id, width, height, segs, n, K, R, t, worldpoints, n_wps, data_directory, max_img_width, load_and_store);
-            if (rc == L3D_OK && r != rank0(h)) r->views[id].cache_to_write.clear();
-            return rc;
-        });
-    if (h->computation) return h->fail(L3D_ERR_INVALID, "reconstruction already performed! cannot add more images (try reset first)");
-    if (h->views.count(id)) return h->fail(L3D_ERR_INVALID, "imageID already in use!");
-    if (n_wps == 0) return h->fail(L3D_ERR_INVALID, "unlinked images cannot be added!");
-    if (width == 0 || height == 0 || !K || !R || !t) return h->fail(L3D_ERR_INVALID, "image is empty!");
-    std::string cache_path, expected;
-    const int from_cache = add_from_cache_or_plan_write(h, id, width, height, K, R, t, data_directory, max_img_width, load_and_store, cache_path, &expected);
-    if (from_cache < 0) return -from_cache;
-    if (!from_cache) {
-        // a size-only image type of the facade brings neither segments nor pixels (pixels: l3d_line3d_add_image_pixels): nothing to add
-        if (n <= 0 || !segs)
-            return h->fail(L3D_ERR_INVALID, ("image [" + std::to_string(id) + "]: no segment cache " + expected + " and no segments given -- line segment "
-                                             "detection is not part of this library (run the reference once with loadAndStoreSegments, or pass the segments)").c_str());
-        const int rc = add_common(h, id, width, height, segs, n, K, R, t, n_wps);
-        if (rc) return rc;
-        h->views[id].cache_to_write = cache_path;
-    }
-    process_worldpoints(h, id, worldpoints, n_wps);
+    p.cache = f ? (load_and_store ? Cache::Load : Cache::Stale)                              // :159-168 | :153-156
+                : (load_and_store ? Cache::Write : Cache::None);                             // :180-182
     return L3D_OK;
 }
 
-int l3d_line3d_add_image_fixed_sim_ex(l3d_line3d* h, uint32_t id, unsigned width, unsigned height, const float* segs, int n, const double* K, const double* R,
-                                      const double* t, const uint32_t* sim_ids, const float* sims, int n_sims, const char* data_directory, int max_img_width,
-                                      int load_and_store)
-{
-    if (!h) return L3D_ERR_INVALID;
-    if (h->node)
-        return node_each(h, [&](L* r) {
-            const int rc = l3d_line3d_add_image_fixed_sim_ex(r, id, width, height, segs, n, K, R, t, sim_ids, sims, n_sims, data_directory, max_img_width,
-                                                            load_and_store);
-            if (rc == L3D_OK && r != rank0(h)) r->views[id].cache_to_write.clear();
-            return rc;
-        });
-    if (h->computation) return h->fail(L3D_ERR_INVALID, "reconstruction already performed! cannot add more images (try reset first)");
-    if (h->views.count(id)) return h->fail(L3D_ERR_INVALID, "imageID already in use!");
-    if (n_sims == 0) return h->fail(L3D_ERR_INVALID, "unlinked images cannot be added!");
-    if (width == 0 || height == 0 || !K || !R || !t) return h->fail(L3D_ERR_INVALID, "image is empty!");
-    std::string cache_path, expected;
-    const int from_cache = add_from_cache_or_plan_write(h, id, width, height, K, R, t, data_directory, max_img_width, load_and_store, cache_path, &expected);
-    if (from_cache < 0) return -from_cache;
-    if (!from_cache) {
-        // a size-only image type of the facade brings neither segments nor pixels (pixels: l3d_line3d_add_image_pixels): nothing to add
-        if (n <= 0 || !segs)
-            return h->fail(L3D_ERR_INVALID, ("image [" + std::to_string(id) + "]: no segment cache " + expected + " and no segments given -- line segment "
-                                             "detection is not part of this library (run the reference once with loadAndStoreSegments, or pass the segments)").c_str());
-        const int rc = add_common(h, id, width, height, segs, n, K, R, t, n_sims);
-        if (rc) return rc;
-        h->views[id].cache_to_write = cache_path;
-    }
-    for (int i = 0; i < n_sims; ++i)                       // setViewSimilarity, :1938-1946
-        if (sims[i] > 0.01f) h->view_similarities[id][sim_ids[i]] = sims[i];
-    return L3D_OK;
-}
-
-// addImage / addImage_fixed_sim from pixels, line3D.cc:128-191: the cache decides first; without a usable cache the segments are detected on the
-// device and enter the calls above.
-// The decision on its own (taken per image, by the single calls and per entry of l3d_line3d_add_images).  Returns 1: the cache stands in for the image,
-// 2: the detector has to run -- at new_w x new_h with min_length; < 0: error negated.  file / had_file: the cache's path, and whether it exists
-static int cache_or_detect(l3d_line3d* h, uint32_t id, int width, int height, const char* data_directory, int max_img_width, int load_and_store, unsigned& new_w,
-                           unsigned& new_h, float& min_length, std::string& file, bool& had_file)
-{
-    L* owner = h->node ? rank0(h) : h;
-    if (width <= 0 || height <= 0) return -h->fail(L3D_ERR_INVALID, "image is empty!");
-    new_w = (unsigned)width; new_h = (unsigned)height;
-    if (max_img_width > 0 && std::max(width, height) > max_img_width) {                      // :133-138
-        const float scale = float(max_img_width) / fmaxf((float)height, (float)width);
-        new_w = (unsigned)roundf(float(width) * scale);
-        new_h = (unsigned)roundf(float(height) * scale);
-    }
-    char name[160];
-    if (l3d_segment_cache_filename(id, new_w, new_h, owner->use_collinearity ? 1 : 0, name, sizeof(name)) != L3D_OK) return -L3D_ERR_INVALID;
-    file = std::string(data_directory ? data_directory : "") + name;
-    FILE* f = fopen(file.c_str(), "rb");
-    had_file = f != nullptr;
-    if (f) { fclose(f); if (load_and_store) return 1; }                                     // :159-168: the cache stands in for the image
-    if (!owner->ctx) return -h->fail(L3D_ERR_INVALID, "no device context to detect line segments with");
-    min_length = 0.005f * sqrtf(float(height * height + width * width));                     // :176, commons.h:43
-    return 2;
-}
-// an image the detector found nothing in adds no view; a stale cache goes with the flag off (:153-156, :186-190)
-static void no_segments(const std::string& file, bool had_file, int load_and_store)
-{
-    if (had_file && !load_and_store) remove(file.c_str());
-}
-
-// Returns 1: go on with `segs` (possibly none: the cache will be loaded), 0: no segment found, no view; < 0: error negated
-// cam: null, or the camera the pixels are undistorted with before the detector sees them (main_vsfm.cpp:243-270)
-static int detect_for_add(l3d_line3d* h, uint32_t id, const unsigned char* pixels, int width, int height, int channels, size_t row_stride,
-                          const char* data_directory, int max_img_width, int load_and_store, std::vector<float>& segs, const l3d::DetCamera* cam = nullptr,
-                          const unsigned char* jpeg = nullptr, size_t jpeg_n = 0)
-{
-    segs.clear();
-    L* owner = h->node ? rank0(h) : h;
-    unsigned new_w = 0, new_h = 0;
-    float min_length = 0.0f;
-    std::string file;
-    bool had_file = false;
-    const int what = cache_or_detect(h, id, width, height, data_directory, max_img_width, load_and_store, new_w, new_h, min_length, file, had_file);
-    if (what <= 1) return what;
-    // jpeg: the file the size came from (pixels null): decoded on the device into the detector -- only here, behind the cache decision
-    const int rc = jpeg ? l3d::detect_segments_jpeg(owner->ctx, jpeg, jpeg_n, (int)new_w, (int)new_h, min_length, 3000, segs, cam)
-                        : l3d::detect_segments(owner->ctx, pixels, width, height, channels, row_stride, (int)new_w, (int)new_h, min_length, 3000, segs, cam);
-    if (rc != L3D_OK) return -h->fail(rc, l3d_last_error(owner->ctx));
-    if (segs.empty()) { no_segments(file, had_file, load_and_store); return 0; }
-    return 1;
-}
-
-int l3d_line3d_add_image_pixels(l3d_line3d* h, uint32_t id, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, const double* K,
-                                const double* R, const double* t, const uint32_t* worldpoints, int n_wps, const char* data_directory, int max_img_width, int load_and_store)
-{
-    if (!h) return L3D_ERR_INVALID;
-    std::vector<float> segs;
-    const int go = detect_for_add(h, id, pixels, width, height, channels, row_stride, data_directory, max_img_width, load_and_store, segs);
-    if (go <= 0) return -go;
-    return l3d_line3d_add_image_ex(h, id, (unsigned)width, (unsigned)height, segs.empty() ? nullptr : segs.data(), (int)(segs.size() / 4), K, R, t, worldpoints, n_wps,
-                                   data_directory, max_img_width, load_and_store);
-}
-
-int l3d_line3d_add_image_pixels_fixed_sim(l3d_line3d* h, uint32_t id, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, const double* K,
-                                          const double* R, const double* t, const uint32_t* sim_ids, const float* sims, int n_sims, const char* data_directory,
-                                          int max_img_width, int load_and_store)
-{
-    if (!h) return L3D_ERR_INVALID;
-    std::vector<float> segs;
-    const int go = detect_for_add(h, id, pixels, width, height, channels, row_stride, data_directory, max_img_width, load_and_store, segs);
-    if (go <= 0) return -go;
-    return l3d_line3d_add_image_fixed_sim_ex(h, id, (unsigned)width, (unsigned)height, segs.empty() ? nullptr : segs.data(), (int)(segs.size() / 4), K, R, t, sim_ids, sims,
-                                             n_sims, data_directory, max_img_width, load_and_store);
-}
-
-// the camera of the _distorted entry points: fx, fy, cx, cy from the full-resolution K, as in the drivers (main_vsfm.cpp:250-262).  Returns 1 with
+// the camera of the undistortion: fx, fy, cx, cy from the full-resolution K, as in the drivers (main_vsfm.cpp:250-262).  Returns 1 with
 // `cam` filled, 0 when both coefficients are within L3D_EPS (the plain path), < 0: error negated
 static int camera_for_add(l3d_line3d* h, const double* K, const double* dist, l3d::DetCamera& cam)
 {
@@ -910,34 +778,177 @@ static int camera_for_add(l3d_line3d* h, const double* K, const double* dist, l3
     return 1;
 }
 
+// steps 1 and 2.  A JPEG file's size (cache name, max_img_width rule) comes from its headers; the entropy-coded data is touched only when the detector runs
+static int add_plan(L* h, const AddRequest& rq, const char* data_directory, int max_img_width, int load_and_store, AddPlan& p)
+{
+    const l3d_image_entry& e = rq.e;
+    int width = e.width, height = e.height;
+    p.channels = e.channels;
+    if (rq.kind == AddKind::Jpeg) {
+        if (!e.jpeg) return h->fail(L3D_ERR_INVALID, "jpeg: null argument");
+        const int rc = l3d_jpeg_info(e.jpeg, e.jpeg_bytes, &width, &height, &p.channels);
+        if (rc != L3D_OK) return h->fail(rc, l3d_jpeg_last_error());
+    }
+    if (rq.image()) {
+        const int with = (e.dist || rq.dist_required) ? camera_for_add(h, e.K, e.dist, p.cam) : 0;
+        if (with < 0) return -with;
+        p.undistort = with != 0;
+        if (width <= 0 || height <= 0) return h->fail(L3D_ERR_INVALID, "image is empty!");
+    }
+    p.width = (unsigned)width; p.height = (unsigned)height;
+    if (!rq.cache_rules) return L3D_OK;
+    if (const int rc = cache_decision(h, e.image_id, p.width, p.height, data_directory, max_img_width, load_and_store, p)) return rc;
+    p.detect = rq.image() && p.cache != Cache::Load;                                         // (a cache that is present and wanted stands in for the image)
+    if (!p.detect) return L3D_OK;
+    if (!(h->node ? rank0(h) : h)->ctx) return h->fail(L3D_ERR_INVALID, "no device context to detect line segments with");
+    p.min_length = 0.005f * sqrtf(float(height * height + width * width));                   // :176, commons.h:43
+    return L3D_OK;
+}
+
+// segments and collinearities of an opened cache as the view's (line3D.cc:160-168): nothing is recomputed
+static int view_from_cache(L* h, const AddRequest& rq, const AddPlan& p, const l3d_segment_cache* cache)
+{
+    const int n = l3d_segment_cache_num_segments(cache), nc = l3d_segment_cache_num_collinearities(cache);
+    std::vector<float> segs((size_t)n * 4 + 1), cw((size_t)nc + 1);
+    std::vector<int32_t> ci((size_t)nc + 1), cj((size_t)nc + 1);
+    l3d_segment_cache_get(cache, segs.data(), ci.data(), cj.data(), cw.data());
+    if (n <= 0 || !rq.e.K || !rq.e.R || !rq.e.t) return h->fail(L3D_ERR_INVALID, "no segments");
+    return make_view(h, rq.e.image_id, p.width, p.height, segs.data(), n, rq.e.K, rq.e.R, rq.e.t, ci.data(), cj.data(), cw.data(), nc);
+}
+
+static void file_links(L* h, uint32_t id, const l3d_image_entry& e)
+{
+    if (!e.sims) { process_worldpoints(h, id, e.link_ids, e.n_links); return; }
+    for (int i = 0; i < e.n_links; ++i)                    // setViewSimilarity, :1938-1946
+        if (e.sims[i] > 0.01f) h->view_similarities[id][e.link_ids[i]] = e.sims[i];
+}
+
+// step 4 (and the second half of 3).  detected: null, or what the detector found in the request's image
+static int add_entry(L* h, const AddRequest& rq, const AddPlan& p, const std::vector<float>* detected)
+{
+    if (detected && detected->empty()) {                   // no view and no error (:186-190); a stale cache goes with the flag off (:153-156)
+        if (p.cache == Cache::Stale) remove(p.file.c_str());
+        return L3D_OK;
+    }
+    const uint32_t id = rq.e.image_id;
+    if (h->node)        // (every rank adds the view; the cache file is written once, by rank 0)
+        return node_each(h, [&](L* r) {
+            const int rc = add_entry(r, rq, p, detected);
+            if (rc == L3D_OK && r != rank0(h)) r->views[id].cache_to_write.clear();
+            return rc;
+        });
+    int rc = add_guards(h, rq, p);
+    if (rc) return rc;
+    if (rq.kind == AddKind::Cached) rc = view_from_cache(h, rq, p, rq.cache);
+    else if (p.cache == Cache::Load) {
+        l3d_segment_cache* cache = nullptr;
+        rc = l3d_segment_cache_read(p.file.c_str(), &cache);
+        rc = rc != L3D_OK ? h->fail(rc, l3d_segment_cache_last_error(cache)) : view_from_cache(h, rq, p, cache);      // (the reference exits, serialization.h:63)
+        l3d_segment_cache_free(cache);
+    } else {
+        if (p.cache == Cache::Stale) remove(p.file.c_str());
+        const float* segs = detected ? detected->data() : rq.segs;
+        const int n = detected ? (int)(detected->size() / 4) : rq.n;
+        // a size-only image type of the facade brings neither segments nor pixels: nothing to add
+        if (rq.cache_rules && (n <= 0 || !segs))
+            return h->fail(L3D_ERR_INVALID, ("image [" + std::to_string(id) + "]: no segment cache " + p.file + " and no segments given -- line segment "
+                                             "detection is not part of this library (run the reference once with loadAndStoreSegments, or pass the segments)").c_str());
+        if (n <= 0 || !segs || !rq.e.K || !rq.e.R || !rq.e.t) return h->fail(L3D_ERR_INVALID, "no segments");   // detectLineSegments failed: no view, :186-190
+        rc = make_view(h, id, p.width, p.height, segs, n, rq.e.K, rq.e.R, rq.e.t);
+        if (rc == L3D_OK && p.cache == Cache::Write) h->views[id].cache_to_write = p.file;
+    }
+    if (rc) return rc;
+    file_links(h, id, rq.e);
+    return L3D_OK;
+}
+
+// the route for one request
+static int add_one(L* h, const AddRequest& rq, const char* data_directory = nullptr, int max_img_width = 0, int load_and_store = 0)
+{
+    if (!h) return L3D_ERR_INVALID;
+    AddPlan p;
+    if (const int rc = add_plan(h, rq, data_directory, max_img_width, load_and_store, p)) return rc;
+    if (!p.detect) return add_entry(h, rq, p, nullptr);
+    l3d_ctx* ctx = (h->node ? rank0(h) : h)->ctx;
+    const l3d_image_entry& e = rq.e;
+    std::vector<float> segs;
+    const l3d::DetCamera* cam = p.undistort ? &p.cam : nullptr;
+    // a JPEG file is decoded on the device into the detector -- only here, behind the cache decision
+    const int rc = rq.kind == AddKind::Jpeg ? l3d::detect_segments_jpeg(ctx, e.jpeg, e.jpeg_bytes, (int)p.new_w, (int)p.new_h, p.min_length, 3000, segs, cam)
+                                            : l3d::detect_segments(ctx, e.pixels, e.width, e.height, e.channels, e.row_stride, (int)p.new_w, (int)p.new_h, p.min_length, 3000, segs, cam);
+    if (rc != L3D_OK) return h->fail(rc, l3d_last_error(ctx));
+    return add_entry(h, rq, p, &segs);
+}
+}  // namespace l3dh
+
+// addImage / addImage_fixed_sim with precomputed segments, line3D.cc:95-217, 220-342
+int l3d_line3d_add_image(l3d_line3d* h, uint32_t id, unsigned width, unsigned height, const float* segs, int n,
+                         const double* K, const double* R, const double* t, const uint32_t* worldpoints, int n_wps)
+{
+    AddRequest rq = add_request(AddKind::Segments, id, width, height, K, R, t, worldpoints, nullptr, n_wps, false);
+    rq.segs = segs; rq.n = n;
+    return add_one(h, rq);
+}
+int l3d_line3d_add_image_fixed_sim(l3d_line3d* h, uint32_t id, unsigned width, unsigned height, const float* segs, int n,
+                                   const double* K, const double* R, const double* t,
+                                   const uint32_t* sim_ids, const float* sims, int n_sims)
+{
+    AddRequest rq = add_request(AddKind::Segments, id, width, height, K, R, t, sim_ids, sims, n_sims, false);
+    rq.segs = segs; rq.n = n;
+    return add_one(h, rq);
+}
+// addImage when the segment cache exists, line3D.cc:160-168: segments and collinearities come from the file
+int l3d_line3d_add_image_cached(l3d_line3d* h, uint32_t id, unsigned width, unsigned height, const l3d_segment_cache* cache,
+                                const double* K, const double* R, const double* t, const uint32_t* worldpoints, int n_wps)
+{
+    AddRequest rq = add_request(AddKind::Cached, id, width, height, K, R, t, worldpoints, nullptr, n_wps, false);
+    rq.cache = cache;
+    return add_one(h, rq);
+}
+// the same with the cache rules, line3D.cc:128-199
+int l3d_line3d_add_image_ex(l3d_line3d* h, uint32_t id, unsigned width, unsigned height, const float* segs, int n, const double* K, const double* R,
+                            const double* t, const uint32_t* worldpoints, int n_wps, const char* data_directory, int max_img_width, int load_and_store)
+{
+    AddRequest rq = add_request(AddKind::Segments, id, width, height, K, R, t, worldpoints, nullptr, n_wps);
+    rq.segs = segs; rq.n = n;
+    return add_one(h, rq, data_directory, max_img_width, load_and_store);
+}
+int l3d_line3d_add_image_fixed_sim_ex(l3d_line3d* h, uint32_t id, unsigned width, unsigned height, const float* segs, int n, const double* K, const double* R,
+                                      const double* t, const uint32_t* sim_ids, const float* sims, int n_sims, const char* data_directory, int max_img_width,
+                                      int load_and_store)
+{
+    AddRequest rq = add_request(AddKind::Segments, id, width, height, K, R, t, sim_ids, sims, n_sims);
+    rq.segs = segs; rq.n = n;
+    return add_one(h, rq, data_directory, max_img_width, load_and_store);
+}
+
+// from pixels: the entry with pixels filled; _distorted: with dist, which may not be null there
+int l3d_line3d_add_image_pixels(l3d_line3d* h, uint32_t id, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, const double* K,
+                                const double* R, const double* t, const uint32_t* worldpoints, int n_wps, const char* data_directory, int max_img_width, int load_and_store)
+{
+    return add_one(h, pixels_request(id, pixels, width, height, channels, row_stride, K, R, t, nullptr, false, worldpoints, nullptr, n_wps), data_directory, max_img_width,
+                   load_and_store);
+}
+int l3d_line3d_add_image_pixels_fixed_sim(l3d_line3d* h, uint32_t id, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, const double* K,
+                                          const double* R, const double* t, const uint32_t* sim_ids, const float* sims, int n_sims, const char* data_directory,
+                                          int max_img_width, int load_and_store)
+{
+    return add_one(h, pixels_request(id, pixels, width, height, channels, row_stride, K, R, t, nullptr, false, sim_ids, sims, n_sims), data_directory, max_img_width,
+                   load_and_store);
+}
 int l3d_line3d_add_image_pixels_distorted(l3d_line3d* h, uint32_t id, const unsigned char* pixels, int width, int height, int channels, size_t row_stride,
                                           const double* K, const double* R, const double* t, const double dist[2], const uint32_t* worldpoints, int n_wps,
                                           const char* data_directory, int max_img_width, int load_and_store)
 {
-    if (!h) return L3D_ERR_INVALID;
-    l3d::DetCamera cam;
-    const int with = camera_for_add(h, K, dist, cam);
-    if (with < 0) return -with;
-    std::vector<float> segs;
-    const int go = detect_for_add(h, id, pixels, width, height, channels, row_stride, data_directory, max_img_width, load_and_store, segs, with ? &cam : nullptr);
-    if (go <= 0) return -go;
-    return l3d_line3d_add_image_ex(h, id, (unsigned)width, (unsigned)height, segs.empty() ? nullptr : segs.data(), (int)(segs.size() / 4), K, R, t, worldpoints, n_wps,
-                                   data_directory, max_img_width, load_and_store);
+    return add_one(h, pixels_request(id, pixels, width, height, channels, row_stride, K, R, t, dist, true, worldpoints, nullptr, n_wps), data_directory, max_img_width,
+                   load_and_store);
 }
-
 int l3d_line3d_add_image_pixels_fixed_sim_distorted(l3d_line3d* h, uint32_t id, const unsigned char* pixels, int width, int height, int channels, size_t row_stride,
                                                     const double* K, const double* R, const double* t, const double dist[2], const uint32_t* sim_ids, const float* sims,
                                                     int n_sims, const char* data_directory, int max_img_width, int load_and_store)
 {
-    if (!h) return L3D_ERR_INVALID;
-    l3d::DetCamera cam;
-    const int with = camera_for_add(h, K, dist, cam);
-    if (with < 0) return -with;
-    std::vector<float> segs;
-    const int go = detect_for_add(h, id, pixels, width, height, channels, row_stride, data_directory, max_img_width, load_and_store, segs, with ? &cam : nullptr);
-    if (go <= 0) return -go;
-    return l3d_line3d_add_image_fixed_sim_ex(h, id, (unsigned)width, (unsigned)height, segs.empty() ? nullptr : segs.data(), (int)(segs.size() / 4), K, R, t, sim_ids, sims,
-                                             n_sims, data_directory, max_img_width, load_and_store);
+    return add_one(h, pixels_request(id, pixels, width, height, channels, row_stride, K, R, t, dist, true, sim_ids, sims, n_sims), data_directory, max_img_width,
+                   load_and_store);
 }
 
 // the drivers' undistort block on its own (main_vsfm.cpp:243-270) with the object's device (a node object: rank 0's)
@@ -955,80 +966,51 @@ int l3d_line3d_undistort_image(l3d_line3d* h, const unsigned char* pixels, int w
     return rc == L3D_OK ? rc : h->fail(rc, l3d_last_error(owner->ctx));
 }
 
-// addImage / addImage_fixed_sim from a baseline JPEG file in memory: the size (cache name, max_img_width rule) comes from the headers; the entropy-coded
-// data is touched only when the detector runs
-static int jpeg_size_for_add(l3d_line3d* h, const unsigned char* bytes, size_t n, int& width, int& height, int& channels)
-{
-    if (!bytes) return -h->fail(L3D_ERR_INVALID, "jpeg: null argument");
-    const int rc = l3d_jpeg_info(bytes, n, &width, &height, &channels);
-    return rc == L3D_OK ? 0 : -h->fail(rc, l3d_jpeg_last_error());
-}
-
+// from a baseline JPEG file in memory: the entry with jpeg filled
 int l3d_line3d_add_image_jpeg(l3d_line3d* h, uint32_t id, const unsigned char* bytes, size_t n, const double* K, const double* R, const double* t, const double dist[2],
                               const uint32_t* worldpoints, int n_wps, const char* data_directory, int max_img_width, int load_and_store)
 {
-    if (!h) return L3D_ERR_INVALID;
-    int width = 0, height = 0, channels = 0;
-    if (const int e = jpeg_size_for_add(h, bytes, n, width, height, channels)) return -e;
-    l3d::DetCamera cam;
-    const int with = dist ? camera_for_add(h, K, dist, cam) : 0;
-    if (with < 0) return -with;
-    std::vector<float> segs;
-    const int go = detect_for_add(h, id, nullptr, width, height, channels, (size_t)width * channels, data_directory, max_img_width, load_and_store, segs, with ? &cam : nullptr, bytes, n);
-    if (go <= 0) return -go;
-    return l3d_line3d_add_image_ex(h, id, (unsigned)width, (unsigned)height, segs.empty() ? nullptr : segs.data(), (int)(segs.size() / 4), K, R, t, worldpoints, n_wps,
-                                   data_directory, max_img_width, load_and_store);
+    return add_one(h, jpeg_request(id, bytes, n, K, R, t, dist, worldpoints, nullptr, n_wps), data_directory, max_img_width, load_and_store);
 }
-
 int l3d_line3d_add_image_jpeg_fixed_sim(l3d_line3d* h, uint32_t id, const unsigned char* bytes, size_t n, const double* K, const double* R, const double* t,
                                         const double dist[2], const uint32_t* sim_ids, const float* sims, int n_sims, const char* data_directory, int max_img_width,
                                         int load_and_store)
 {
-    if (!h) return L3D_ERR_INVALID;
-    int width = 0, height = 0, channels = 0;
-    if (const int e = jpeg_size_for_add(h, bytes, n, width, height, channels)) return -e;
-    l3d::DetCamera cam;
-    const int with = dist ? camera_for_add(h, K, dist, cam) : 0;
-    if (with < 0) return -with;
-    std::vector<float> segs;
-    const int go = detect_for_add(h, id, nullptr, width, height, channels, (size_t)width * channels, data_directory, max_img_width, load_and_store, segs, with ? &cam : nullptr, bytes, n);
-    if (go <= 0) return -go;
-    return l3d_line3d_add_image_fixed_sim_ex(h, id, (unsigned)width, (unsigned)height, segs.empty() ? nullptr : segs.data(), (int)(segs.size() / 4), K, R, t, sim_ids, sims,
-                                             n_sims, data_directory, max_img_width, load_and_store);
+    return add_one(h, jpeg_request(id, bytes, n, K, R, t, dist, sim_ids, sims, n_sims), data_directory, max_img_width, load_and_store);
 }
 
-// Many images in one call: the sequence of the single calls above in entry order, with the detector run once over all entries that need it.
-// Per entry: the checks of its single call and the cache decision; then the batched detector (l3d_detect.hip) on the entries without a usable cache;
-// then the views, in entry order, through l3d_line3d_add_image_ex / _fixed_sim_ex.  An entry fails alone, with its single call's code and message
+// the single call for an l3d_image_entry: what the named image forms above fill in
+int l3d_line3d_add_image_entry(l3d_line3d* h, const l3d_image_entry* e, const char* data_directory, int max_img_width, int load_and_store)
+{
+    if (!h) return L3D_ERR_INVALID;
+    if (!e) return h->fail(L3D_ERR_INVALID, "add_image_entry: null argument");
+    AddRequest rq;
+    if (const int rc = entry_request(h, *e, rq, true)) return rc;
+    return add_one(h, rq, data_directory, max_img_width, load_and_store);
+}
+
+// Many images in one call: the route above per entry, in entry order, with the detector run once (batched, l3d_detect.hip) over all entries that
+// need it.  An entry fails alone, with its single call's code and message
 int l3d_line3d_add_images(l3d_line3d* h, const l3d_image_entry* e, int n, const char* data_directory, int max_img_width, int load_and_store, int* status)
 {
     if (!h) return L3D_ERR_INVALID;
     if (n < 0 || (n > 0 && !e)) return h->fail(L3D_ERR_INVALID, "add_images: null argument");
-    L* owner = h->node ? rank0(h) : h;
-    struct Item { int rc = L3D_OK, what = 0, width = 0, height = 0; bool had_file = false; std::string file, msg; l3d::DetCamera cam; int detect_at = -1; };
+    struct Item { int rc = L3D_OK; std::string msg; AddRequest rq; AddPlan p; int detect_at = -1; };
     std::vector<Item> items((size_t)n);
     std::vector<l3d::DetEntry> todo;
     todo.reserve((size_t)n);
-    auto refuse = [&](Item& it, int rc) { it.rc = rc; it.msg = h->err; };
     for (int i = 0; i < n; ++i) {
         Item& it = items[i];
-        const l3d_image_entry& en = e[i];
-        if ((en.pixels != nullptr) == (en.jpeg != nullptr)) { refuse(it, h->fail(L3D_ERR_INVALID, "add_images: an entry needs either pixels or a JPEG file")); continue; }
-        int channels = en.channels;
-        it.width = en.width; it.height = en.height;
-        if (en.jpeg) { if (const int bad = jpeg_size_for_add(h, en.jpeg, en.jpeg_bytes, it.width, it.height, channels)) { refuse(it, -bad); continue; } }
-        const int with = en.dist ? camera_for_add(h, en.K, en.dist, it.cam) : 0;
-        if (with < 0) { refuse(it, -with); continue; }
-        unsigned new_w = 0, new_h = 0;
-        float min_length = 0.0f;
-        it.what = cache_or_detect(h, en.image_id, it.width, it.height, data_directory, max_img_width, load_and_store, new_w, new_h, min_length, it.file, it.had_file);
-        if (it.what < 0) { refuse(it, -it.what); continue; }
-        if (it.what != 2) continue;
+        it.rc = entry_request(h, e[i], it.rq, false);
+        if (it.rc == L3D_OK) it.rc = add_plan(h, it.rq, data_directory, max_img_width, load_and_store, it.p);
+        if (it.rc != L3D_OK) { it.msg = h->err; continue; }
+        if (!it.p.detect) continue;
         l3d::DetEntry d;
-        d.pixels = en.pixels; d.width = it.width; d.height = it.height; d.channels = channels; d.row_stride = en.jpeg ? (size_t)it.width * channels : en.row_stride;
-        d.jpeg = en.jpeg; d.jpeg_bytes = en.jpeg_bytes;
-        d.new_width = (int)new_w; d.new_height = (int)new_h; d.min_length = min_length; d.max_segments = 3000;
-        d.cam = with ? &it.cam : nullptr;           // (items does not grow: the address holds)
+        d.pixels = e[i].pixels; d.width = (int)it.p.width; d.height = (int)it.p.height; d.channels = it.p.channels;
+        d.row_stride = e[i].jpeg ? (size_t)it.p.width * it.p.channels : e[i].row_stride;
+        d.jpeg = e[i].jpeg; d.jpeg_bytes = e[i].jpeg_bytes;
+        d.new_width = (int)it.p.new_w; d.new_height = (int)it.p.new_h; d.min_length = it.p.min_length; d.max_segments = 3000;
+        d.cam = it.p.undistort ? &it.p.cam : nullptr;           // (items does not grow: the address holds)
         it.detect_at = (int)todo.size();
         todo.push_back(d);
     }
@@ -1036,32 +1018,18 @@ int l3d_line3d_add_images(l3d_line3d* h, const l3d_image_entry* e, int n, const 
     std::vector<int> det_status;
     std::vector<std::string> det_msg;
     int rc_all = L3D_OK;
-    if (!todo.empty()) {
-        rc_all = l3d::detect_segments_batch(owner->ctx, todo.data(), (int)todo.size(), segs, det_status, det_msg);       // (one status per entry, whatever it returns)
-    }
+    if (!todo.empty())
+        rc_all = l3d::detect_segments_batch((h->node ? rank0(h) : h)->ctx, todo.data(), (int)todo.size(), segs, det_status, det_msg);   // (one status per entry, whatever it returns)
     std::string lines;
     for (int i = 0; i < n; ++i) {
         Item& it = items[i];
-        const l3d_image_entry& en = e[i];
-        if (it.rc == L3D_OK && it.what >= 1) {
-            const float* s = nullptr;
-            int ns = 0;
-            bool add = true;
-            if (it.detect_at >= 0) {
-                if (det_status[it.detect_at] != L3D_OK) { it.rc = det_status[it.detect_at]; it.msg = det_msg[it.detect_at]; add = false; }
-                else if (segs[it.detect_at].empty()) { no_segments(it.file, it.had_file, load_and_store); add = false; }      // L3D_OK and no view
-                else { s = segs[it.detect_at].data(); ns = (int)(segs[it.detect_at].size() / 4); }
-            }
-            if (add) {
-                it.rc = en.sims ? l3d_line3d_add_image_fixed_sim_ex(h, en.image_id, (unsigned)it.width, (unsigned)it.height, s, ns, en.K, en.R, en.t, en.link_ids, en.sims, en.n_links,
-                                                                    data_directory, max_img_width, load_and_store)
-                                : l3d_line3d_add_image_ex(h, en.image_id, (unsigned)it.width, (unsigned)it.height, s, ns, en.K, en.R, en.t, en.link_ids, en.n_links, data_directory,
-                                                          max_img_width, load_and_store);
-                if (it.rc != L3D_OK) it.msg = h->err;
-            }
+        if (it.rc == L3D_OK && it.detect_at >= 0 && det_status[it.detect_at] != L3D_OK) { it.rc = det_status[it.detect_at]; it.msg = det_msg[it.detect_at]; }
+        else if (it.rc == L3D_OK) {
+            it.rc = add_entry(h, it.rq, it.p, it.detect_at >= 0 ? &segs[it.detect_at] : nullptr);
+            if (it.rc != L3D_OK) it.msg = h->err;
         }
         if (status) status[i] = it.rc;
-        if (it.rc != L3D_OK) lines += (lines.empty() ? "image " : "\nimage ") + std::to_string(en.image_id) + ": " + it.msg;
+        if (it.rc != L3D_OK) lines += (lines.empty() ? "image " : "\nimage ") + std::to_string(e[i].image_id) + ": " + it.msg;
     }
     h->err = lines;
     return rc_all;

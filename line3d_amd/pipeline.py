@@ -39,7 +39,7 @@ def image_entries(entries):
             keep.append(pix)
             e.pixels, e.width, e.height, e.channels, e.row_stride = pix.value, w, h, ch, stride
         else:
-            if not isinstance(en["data"], (bytes, bytearray, memoryview)):
+            if not isinstance(en["data"], (bytes, bytearray, memoryview, np.ndarray)):
                 raise TypeError("entry %d: data must be the bytes of a JPEG file" % i)
             ptr, nbytes = capi._bytes_arguments(en["data"])
             keep.append(ptr)
@@ -57,6 +57,19 @@ def image_entries(entries):
             raise ValueError("entry %d: link ids must be a flat list" % i)
         e.link_ids, e.n_links = pointer(np.concatenate([ids, np.zeros(1, np.uint32)])), len(ids)
     return arr, keep
+
+
+def _camera_and_links(K, R, t, links, fixed_sim):
+    """The K, R, t and link arguments of the segment-taking calls, and the arrays behind them.  links: world point ids, or {view id: similarity}
+    with fixed_sim"""
+    arrays = [np.ascontiguousarray(a, dtype=np.float64) for a in (K, R, t)]
+    if fixed_sim:
+        ids = np.ascontiguousarray(sorted(links), dtype=np.uint32)
+        arrays += [ids, np.ascontiguousarray([links[int(i)] for i in ids], dtype=np.float32)]
+    else:
+        ids = np.ascontiguousarray(list(links), dtype=np.uint32)
+        arrays.append(ids)
+    return [_p(a) for a in arrays] + [C.c_int(len(ids))], arrays
 
 
 class Line3D:
@@ -90,7 +103,7 @@ class Line3D:
                 raise L3DError("l3d_line3d_create failed (code %d): no usable MI355X / HIP device -- no CPU fallback" % rc)
         self.h = h
         self._keep = []
-        self.last_rc = 0          # status of the last add_image_jpeg / add_image_jpeg_fixed_sim (they return a bool, as the other adders do)
+        self.last_rc = 0          # status of the last add_image_pixels* / add_image_jpeg* (they return a bool, as the other adders do)
 
     def close(self):
         if getattr(self, "h", None):
@@ -150,21 +163,23 @@ class Line3D:
     # -- reference interface ------------------------------------------------------------------
     def addImage(self, imageID, width, height, segments, K, R, t, worldpointIDs):
         segs = np.ascontiguousarray(segments, dtype=np.float32).reshape(-1, 4)
-        K, R, t = (np.ascontiguousarray(a, dtype=np.float64) for a in (K, R, t))
-        wps = np.ascontiguousarray(list(worldpointIDs), dtype=np.uint32)
-        rc = self.lib.l3d_line3d_add_image(self.h, C.c_uint32(imageID), C.c_uint(width), C.c_uint(height), _p(segs),
-                                           C.c_int(len(segs)), _p(K), _p(R), _p(t), _p(wps), C.c_int(len(wps)))
+        args, keep = _camera_and_links(K, R, t, worldpointIDs, False)
+        rc = self.lib.l3d_line3d_add_image(self.h, C.c_uint32(imageID), C.c_uint(width), C.c_uint(height), _p(segs), C.c_int(len(segs)), *args)
         return rc == 0          # the reference prints to cerr and returns (line3D.cc:101-127)
+
+    def addImage_fixed_sim(self, imageID, width, height, segments, K, R, t, viewSimilarity):
+        segs = np.ascontiguousarray(segments, dtype=np.float32).reshape(-1, 4)
+        args, keep = _camera_and_links(K, R, t, viewSimilarity, True)
+        rc = self.lib.l3d_line3d_add_image_fixed_sim(self.h, C.c_uint32(imageID), C.c_uint(width), C.c_uint(height), _p(segs), C.c_int(len(segs)), *args)
+        return rc == 0
 
     def addImage_cached(self, imageID, width, height, cache_path, K, R, t, worldpointIDs):
         """addImage when the segment cache file exists (line3D.cc:160-168): segments and collinearities from the file."""
         from .io import open_segment_cache, close_segment_cache
-        K, R, t = (np.ascontiguousarray(a, dtype=np.float64) for a in (K, R, t))
-        wps = np.ascontiguousarray(list(worldpointIDs), dtype=np.uint32)
+        args, keep = _camera_and_links(K, R, t, worldpointIDs, False)
         cache = open_segment_cache(cache_path)
         try:
-            rc = self.lib.l3d_line3d_add_image_cached(self.h, C.c_uint32(imageID), C.c_uint(width), C.c_uint(height), cache,
-                                                      _p(K), _p(R), _p(t), _p(wps), C.c_int(len(wps)))
+            rc = self.lib.l3d_line3d_add_image_cached(self.h, C.c_uint32(imageID), C.c_uint(width), C.c_uint(height), cache, *args)
         finally:
             close_segment_cache(cache)
         return rc == 0
@@ -173,82 +188,42 @@ class Line3D:
         """addImage / addImage_fixed_sim with the reference's segment-cache behaviour in `data_directory` (line3D.cc:128-199): the cache
         file is removed, read instead of `segments`, or written.  links: world point ids, or {view id: similarity} with fixed_sim."""
         segs = np.ascontiguousarray(segments, dtype=np.float32).reshape(-1, 4)
-        K, R, t = (np.ascontiguousarray(a, dtype=np.float64) for a in (K, R, t))
-        d = self.data_directory.encode()
-        if fixed_sim:
-            ids = np.ascontiguousarray(sorted(links), dtype=np.uint32)
-            sims = np.ascontiguousarray([links[int(i)] for i in ids], dtype=np.float32)
-            rc = self.lib.l3d_line3d_add_image_fixed_sim_ex(self.h, C.c_uint32(imageID), C.c_uint(width), C.c_uint(height), _p(segs), C.c_int(len(segs)),
-                                                            _p(K), _p(R), _p(t), _p(ids), _p(sims), C.c_int(len(ids)), C.c_char_p(d), C.c_int(maxImgWidth),
-                                                            C.c_int(int(loadAndStoreSegments)))
-        else:
-            wps = np.ascontiguousarray(list(links), dtype=np.uint32)
-            rc = self.lib.l3d_line3d_add_image_ex(self.h, C.c_uint32(imageID), C.c_uint(width), C.c_uint(height), _p(segs), C.c_int(len(segs)),
-                                                  _p(K), _p(R), _p(t), _p(wps), C.c_int(len(wps)), C.c_char_p(d), C.c_int(maxImgWidth),
-                                                  C.c_int(int(loadAndStoreSegments)))
+        args, keep = _camera_and_links(K, R, t, links, fixed_sim)
+        add = self.lib.l3d_line3d_add_image_fixed_sim_ex if fixed_sim else self.lib.l3d_line3d_add_image_ex
+        rc = add(self.h, C.c_uint32(imageID), C.c_uint(width), C.c_uint(height), _p(segs), C.c_int(len(segs)), *args,
+                 C.c_char_p(self.data_directory.encode()), C.c_int(maxImgWidth), C.c_int(int(loadAndStoreSegments)))
         return rc == 0
+
+    def _add_entry(self, en, maxImgWidth, loadAndStoreSegments):
+        """one image entry (as add_images takes them) through l3d_line3d_add_image_entry: True when it was taken; the status stays in last_rc.
+        What is no image or no file raises TypeError, as image_arguments and bytes() do; image_entries speaks of "entry 0" in what it refuses"""
+        if "data" in en and not isinstance(en["data"], (bytes, bytearray, memoryview, np.ndarray)):
+            en["data"] = bytes(en["data"])            # (whatever bytes() takes, as before; None or a str: TypeError)
+        arr, keep = image_entries([en])
+        self.last_rc = self.lib.l3d_line3d_add_image_entry(self.h, arr, C.c_char_p(self.data_directory.encode()), C.c_int(int(maxImgWidth)),
+                                                           C.c_int(int(loadAndStoreSegments)))
+        return self.last_rc == 0
 
     def add_image_pixels(self, imageID, img, K, R, t, worldpointIDs, maxImgWidth=1920, loadAndStoreSegments=True, dist=None):
-        """Line3D::addImage from pixels (l3d_line3d_add_image_pixels): uint8 image H x W or H x W x 3.  The segment cache in `data_directory` is
-        loaded when present (and loadAndStoreSegments); otherwise the segments are detected on the device, and the cache written or a stale one
-        removed.  An image without segments adds no view and is no error (line3D.cc:186-190).  dist = (k1, k2), OpenCV-convention radial
-        coefficients: the image is undistorted on the device with K before the detector sees it (l3d_line3d_add_image_pixels_distorted)."""
-        pix, w, h, ch, stride = capi.image_arguments(img)
-        K, R, t = (np.ascontiguousarray(a, dtype=np.float64) for a in (K, R, t))
-        wps = np.ascontiguousarray(list(worldpointIDs), dtype=np.uint32)
-        if dist is not None:
-            d = np.ascontiguousarray(dist, dtype=np.float64).reshape(2)
-            rc = self.lib.l3d_line3d_add_image_pixels_distorted(self.h, C.c_uint32(imageID), pix, C.c_int(w), C.c_int(h), C.c_int(ch), C.c_size_t(stride), _p(K), _p(R),
-                                                                _p(t), _p(d), _p(wps), C.c_int(len(wps)), C.c_char_p(self.data_directory.encode()),
-                                                                C.c_int(maxImgWidth), C.c_int(int(loadAndStoreSegments)))
-            return rc == 0
-        rc = self.lib.l3d_line3d_add_image_pixels(self.h, C.c_uint32(imageID), pix, C.c_int(w), C.c_int(h), C.c_int(ch), C.c_size_t(stride), _p(K), _p(R), _p(t),
-                                                  _p(wps), C.c_int(len(wps)), C.c_char_p(self.data_directory.encode()), C.c_int(maxImgWidth),
-                                                  C.c_int(int(loadAndStoreSegments)))
-        return rc == 0
+        """Line3D::addImage from pixels (an image entry with img, include/line3d_amd.h): uint8 image H x W or H x W x 3.  The segment cache in
+        `data_directory` is loaded when present (and loadAndStoreSegments); otherwise the segments are detected on the device, and the cache written
+        or a stale one removed.  An image without segments adds no view and is no error (line3D.cc:186-190).  dist = (k1, k2), OpenCV-convention
+        radial coefficients: the image is undistorted on the device with K before the detector sees it."""
+        return self._add_entry(dict(imageID=imageID, img=np.asarray(img), K=K, R=R, t=t, worldpointIDs=list(worldpointIDs), dist=dist), maxImgWidth, loadAndStoreSegments)
 
     def add_image_pixels_fixed_sim(self, imageID, img, K, R, t, viewSimilarity, maxImgWidth=1920, loadAndStoreSegments=True, dist=None):
-        """Line3D::addImage_fixed_sim from pixels (l3d_line3d_add_image_pixels_fixed_sim); dist as in add_image_pixels"""
-        pix, w, h, ch, stride = capi.image_arguments(img)
-        K, R, t = (np.ascontiguousarray(a, dtype=np.float64) for a in (K, R, t))
-        ids = np.ascontiguousarray(sorted(viewSimilarity), dtype=np.uint32)
-        sims = np.ascontiguousarray([viewSimilarity[int(i)] for i in ids], dtype=np.float32)
-        if dist is not None:
-            d = np.ascontiguousarray(dist, dtype=np.float64).reshape(2)
-            rc = self.lib.l3d_line3d_add_image_pixels_fixed_sim_distorted(self.h, C.c_uint32(imageID), pix, C.c_int(w), C.c_int(h), C.c_int(ch), C.c_size_t(stride),
-                                                                          _p(K), _p(R), _p(t), _p(d), _p(ids), _p(sims), C.c_int(len(ids)),
-                                                                          C.c_char_p(self.data_directory.encode()), C.c_int(maxImgWidth),
-                                                                          C.c_int(int(loadAndStoreSegments)))
-            return rc == 0
-        rc = self.lib.l3d_line3d_add_image_pixels_fixed_sim(self.h, C.c_uint32(imageID), pix, C.c_int(w), C.c_int(h), C.c_int(ch), C.c_size_t(stride), _p(K), _p(R),
-                                                            _p(t), _p(ids), _p(sims), C.c_int(len(ids)), C.c_char_p(self.data_directory.encode()),
-                                                            C.c_int(maxImgWidth), C.c_int(int(loadAndStoreSegments)))
-        return rc == 0
+        """Line3D::addImage_fixed_sim from pixels; dist as in add_image_pixels"""
+        return self._add_entry(dict(imageID=imageID, img=np.asarray(img), K=K, R=R, t=t, viewSimilarity=dict(viewSimilarity), dist=dist), maxImgWidth, loadAndStoreSegments)
 
     def add_image_jpeg(self, imageID, data, K, R, t, worldpointIDs, maxImgWidth=1920, loadAndStoreSegments=True, dist=None):
-        """Line3D::addImage from the bytes of a baseline JPEG file (l3d_line3d_add_image_jpeg): decoded, undistorted (dist = (k1, k2), None: not)
+        """Line3D::addImage from the bytes of a baseline JPEG file (an image entry with data): decoded, undistorted (dist = (k1, k2), None: not)
         and its segments detected on the device.  Cache rules as add_image_pixels; a cache that is present and wanted is loaded without decoding
         the file.  A file the decoder refuses adds no view and returns False (the cause: l3d_line3d_last_error)."""
-        ptr, n = capi._bytes_arguments(data)
-        K, R, t = (np.ascontiguousarray(a, dtype=np.float64) for a in (K, R, t))
-        wps = np.ascontiguousarray(list(worldpointIDs), dtype=np.uint32)
-        d = None if dist is None else np.ascontiguousarray(dist, dtype=np.float64).reshape(2)
-        self.last_rc = self.lib.l3d_line3d_add_image_jpeg(self.h, C.c_uint32(imageID), ptr, n, _p(K), _p(R), _p(t), None if d is None else _p(d), _p(wps),
-                                                          C.c_int(len(wps)), C.c_char_p(self.data_directory.encode()), C.c_int(maxImgWidth),
-                                                          C.c_int(int(loadAndStoreSegments)))
-        return self.last_rc == 0
+        return self._add_entry(dict(imageID=imageID, data=data, K=K, R=R, t=t, worldpointIDs=list(worldpointIDs), dist=dist), maxImgWidth, loadAndStoreSegments)
 
     def add_image_jpeg_fixed_sim(self, imageID, data, K, R, t, viewSimilarity, maxImgWidth=1920, loadAndStoreSegments=True, dist=None):
-        """Line3D::addImage_fixed_sim from the bytes of a baseline JPEG file (l3d_line3d_add_image_jpeg_fixed_sim); as add_image_jpeg"""
-        ptr, n = capi._bytes_arguments(data)
-        K, R, t = (np.ascontiguousarray(a, dtype=np.float64) for a in (K, R, t))
-        ids = np.ascontiguousarray(sorted(viewSimilarity), dtype=np.uint32)
-        sims = np.ascontiguousarray([viewSimilarity[int(i)] for i in ids], dtype=np.float32)
-        d = None if dist is None else np.ascontiguousarray(dist, dtype=np.float64).reshape(2)
-        self.last_rc = self.lib.l3d_line3d_add_image_jpeg_fixed_sim(self.h, C.c_uint32(imageID), ptr, n, _p(K), _p(R), _p(t), None if d is None else _p(d),
-                                                                    _p(ids), _p(sims), C.c_int(len(ids)), C.c_char_p(self.data_directory.encode()),
-                                                                    C.c_int(maxImgWidth), C.c_int(int(loadAndStoreSegments)))
-        return self.last_rc == 0
+        """Line3D::addImage_fixed_sim from the bytes of a baseline JPEG file; as add_image_jpeg"""
+        return self._add_entry(dict(imageID=imageID, data=data, K=K, R=R, t=t, viewSimilarity=dict(viewSimilarity), dist=dist), maxImgWidth, loadAndStoreSegments)
 
     def add_images(self, entries, maxImgWidth=1920, loadAndStoreSegments=True):
         """l3d_line3d_add_images: many images in one call -- exactly the add_image_pixels[_fixed_sim] / add_image_jpeg[_fixed_sim] calls in entry order,
@@ -270,15 +245,6 @@ class Line3D:
         out = np.zeros((h, w) if ch == 1 else (h, w, ch), np.uint8)
         self._chk(self.lib.l3d_line3d_decode_jpeg(self.h, ptr, n, _p(out), C.c_size_t(w * ch)))
         return out
-
-    def addImage_fixed_sim(self, imageID, width, height, segments, K, R, t, viewSimilarity):
-        segs = np.ascontiguousarray(segments, dtype=np.float32).reshape(-1, 4)
-        K, R, t = (np.ascontiguousarray(a, dtype=np.float64) for a in (K, R, t))
-        ids = np.ascontiguousarray(sorted(viewSimilarity), dtype=np.uint32)
-        sims = np.ascontiguousarray([viewSimilarity[int(i)] for i in ids], dtype=np.float32)
-        rc = self.lib.l3d_line3d_add_image_fixed_sim(self.h, C.c_uint32(imageID), C.c_uint(width), C.c_uint(height), _p(segs),
-                                                     C.c_int(len(segs)), _p(K), _p(R), _p(t), _p(ids), _p(sims), C.c_int(len(ids)))
-        return rc == 0
 
     def compute3Dmodel(self, perform_diffusion: bool = False):
         self._chk(self.lib.l3d_line3d_compute3Dmodel(self.h, C.c_int(int(perform_diffusion))))
