@@ -1005,6 +1005,43 @@ int l3d_test_verify_candidates(l3d_ctx* ctx, int S, int N, const float* src_segs
                                const float* RtKinv_src, const float* C_src, const int32_t* row_start, const uint32_t* cand_meta, const float* cand_depths, int R,
                                float sigma_p, float sigma_a, float spatial_k, l3d_test_verify_path* sel, float* conf, int32_t* kept_cnt, float* best_depths);
 
+/* Stage 1 (K_pairwise_matches and the packing of its candidates) of one source view, exported for tests (tests/test_gpu_stage1_paths.py): the
+ * product's own argument set-up and launchers on the launch sequence `sel->path` names, with no existing matches.
+ *   S, N, src_segs, tgt_segs (n_tgt x 4), offsets, F, RtKinv, centers, RtKinv_src, C_src, to_be_matched: as l3d_compute_pairwise_matches
+ * path 0: the per-view seam call -- bit rows with the depth test inside, k_row_count, the row scan, k_pair_fill.
+ * path 1: the resident chain with fused row starts (N <= 96) -- k_pair_mask counts upper bounds and their 256-row block sums, k_pair_fill forms
+ *         the row starts from them, triangulates, drops the pairs without four positive depths, packs the row and writes its true count.
+ * path 2: the chains with a scan launch in between -- over all rows when the range is [0, S) (resident chain, N > 96), over the range's rows
+ *         otherwise (sharded chain).
+ * pretest: the stage-1 filter mask 0..7 (option "pretest").  spb: 0 = the launcher's rule, else source segments per k_pair_mask workgroup
+ * (option "pair_spb").  [seg_begin, seg_end): the source segments processed.  Paths 1 and 2 only: ray_tables 1 = the viewing-ray tables of
+ * k_tgt_rays as the chains make them, 0 = none (k_pair_fill normalises the rays itself); cand_cap = the candidate capacity the kernels guard
+ * (0: the sum of the upper bounds, i.e. exactly enough).  capacity: slots of the caller's cand_meta / cand_depths.
+ * Out, rows indexed segment * N + camera:
+ *   row_upper  S*N      what k_pair_mask counted: pairs that pass the overlap test (paths 1, 2); on path 0 k_row_count's result (== row_count)
+ *   row_count  S*N      candidates of the row (four positive depths); with sel->overflow on paths 1 and 2: the upper bounds
+ *   row_start  S*N + 1  path 0: exclusive prefix of row_count over all rows, [S*N] = their total.  Paths 1 and 2: exclusive prefix of
+ *                       row_upper -- a row's candidates are packed at the front of the room of its upper bound.  Path 1 writes the rows with
+ *                       row_upper > 0 only, path 2 with a partial range the rows [seg_begin * N, seg_end * N] and [S*N].
+ *   cand_meta  capacity x (target id within its camera, camera); cand_depths capacity x 4
+ *   sel->total, sel->largest: sum and largest per-segment sum of the counts the path scans (path 0: row_count, path 2: row_upper; path 1
+ *   computes none: -1); sel->spb_used; sel->overflow (paths 1, 2: the upper bounds exceed cand_cap -- no candidate is written); sel->needed:
+ *   the slots the result takes (path 0: the candidates, paths 1 and 2: the sum of the upper bounds).
+ * The row starts and max(capacity, needed) candidate slots on the device are filled with 0xff bytes before the launches: what no kernel wrote
+ * stays recognisable.  (The row counters are zeroed as the product zeroes them: its kernels add into them.)  capacity < needed: L3D_ERR_INVALID
+ * with the number in the message and in sel->needed, row_upper / row_count / row_start filled in, no candidates.
+ * Refused before any launch, L3D_ERR_INVALID with a message: a camera of to_be_matched with more than 16384 segments, to_be_matched not strictly
+ * ascending or outside [0, N), offsets outside n_tgt, a range outside [0, S], path / pretest / spb out of range, path 1 with N > 96, N > 255,
+ * cand_cap or ray_tables set on path 0. */
+typedef struct l3d_test_pair_path {
+    int32_t path, pretest, spb, seg_begin, seg_end, ray_tables, cand_cap, capacity;
+    int32_t needed, total, largest, spb_used, overflow;     /* out */
+    int32_t pad;
+} l3d_test_pair_path;
+int l3d_test_pair_candidates(l3d_ctx* ctx, int S, int N, const float* src_segs, const float* tgt_segs, int n_tgt, const int32_t* offsets, const float* F,
+                             const float* RtKinv, const float* centers, const float* RtKinv_src, const float* C_src, const int32_t* to_be_matched, int n_tbm,
+                             l3d_test_pair_path* sel, int32_t* row_upper, int32_t* row_count, int32_t* row_start, uint32_t* cand_meta, float* cand_depths);
+
 #ifdef __cplusplus
 }
 #endif

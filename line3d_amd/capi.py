@@ -151,6 +151,12 @@ class VerifyPath(C.Structure):
                 ("mmax_used", C.c_int32), ("kernels", C.c_uint32), ("pad", C.c_int32), ("seg_order", C.c_void_p)]
 
 
+class PairPath(C.Structure):
+    """l3d_test_pair_path (include/line3d_amd.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("path", "pretest", "spb", "seg_begin", "seg_end", "ray_tables", "cand_cap", "capacity",
+                                          "needed", "total", "largest", "spb_used", "overflow", "pad")]
+
+
 # L3D_VK_*: the stage-2 kernels a test_verify_candidates call launched
 VK_ALL_PAIRS, VK_SEG_POST, VK_WINDOW_256, VK_WINDOW_512, VK_WINDOW_GB, VK_BUILD, VK_WALK, VK_WALK_GB = 1, 2, 4, 8, 16, 32, 64, 128
 
@@ -458,6 +464,32 @@ class Context:
                                                       C.c_float(float(sigma_p)), C.c_float(float(sigma_a)), C.c_float(float(spatial_k)), C.byref(sel),
                                                       _p(conf), _p(kept), _p(best)))
         return conf, kept, best, int(sel.mmax_used), int(sel.kernels)
+
+    def test_pair_candidates(self, src_segs, tgt_segs, offsets, F, RtKinv, centers, RtKinv_src, C_src, to_be_matched, path=0, pretest=3, spb=0,
+                             seg_range=None, ray_tables=None, cand_cap=0, capacity=0):
+        """l3d_test_pair_candidates: stage 1 of one source view on one launch sequence -> dict(row_upper (S*N,), row_count (S*N,), row_start (S*N + 1,),
+        cand_meta (capacity, 2), cand_depths (capacity, 4), total, largest, spb_used, overflow, needed).  ray_tables None: 1 on paths 1 and 2.
+        Nothing is checked here: a broken table is the library's to refuse (the L3DError then carries the slots needed in .needed)."""
+        f = lambda a: np.ascontiguousarray(a, dtype=np.float32)
+        src_segs, tgt_segs, F, RtKinv, centers, RtKinv_src, C_src = f(src_segs), f(tgt_segs), f(F), f(RtKinv), f(centers), f(RtKinv_src), f(C_src)
+        offsets, tbm = np.ascontiguousarray(offsets, dtype=np.int32), np.ascontiguousarray(to_be_matched, dtype=np.int32)
+        S, N, n_tgt = len(src_segs.reshape(-1, 4)), len(offsets), len(tgt_segs.reshape(-1, 4))
+        assert F.size == N * 9 and RtKinv.size == N * 9 and centers.size == N * 3 and RtKinv_src.size == 9 and C_src.size == 3
+        s0, s1 = (0, S) if seg_range is None else seg_range
+        if ray_tables is None:
+            ray_tables = 1 if path in (1, 2) else 0
+        sel = PairPath(int(path), int(pretest), int(spb), int(s0), int(s1), int(ray_tables), int(cand_cap), int(capacity))
+        out = dict(row_upper=np.zeros(S * N, np.int32), row_count=np.zeros(S * N, np.int32), row_start=np.zeros(S * N + 1, np.int32),
+                   cand_meta=np.zeros((int(capacity), 2), np.uint32), cand_depths=np.zeros((int(capacity), 4), np.float32))
+        try:
+            self._chk(self.lib.l3d_test_pair_candidates(self.h, C.c_int(S), C.c_int(N), _p(src_segs), _p(tgt_segs), C.c_int(n_tgt), _p(offsets), _p(F), _p(RtKinv),
+                                                        _p(centers), _p(RtKinv_src), _p(C_src), _p(tbm), C.c_int(len(tbm)), C.byref(sel), _p(out["row_upper"]),
+                                                        _p(out["row_count"]), _p(out["row_start"]), _p(out["cand_meta"]), _p(out["cand_depths"])))
+        except L3DError as e:
+            e.needed = int(sel.needed)
+            raise
+        out.update(total=int(sel.total), largest=int(sel.largest), spb_used=int(sel.spb_used), overflow=int(sel.overflow), needed=int(sel.needed))
+        return out
 
     # -- the three seam functions ---------------------------------------------------------------
     def compute_collinearity(self, segs, collin_s=2.0):

@@ -107,6 +107,151 @@ int seam_launch_verify(l3d_ctx* c, VerifyArgs& va, bool window, int mmax, int mm
     { ProfScope p(c, "seg_post"); launch_seg_post(va, c->kept_cnt.as<int>(), c->best.as<float2>(), st); }
     return L3D_OK;
 }
+
+// Stage 1 of the per-view seam call (l3d_compute_pairwise_matches; l3d_test_pair_candidates runs it with no existing matches): the tables, the
+// bit rows with the depth test inside (k_pair_mask<true>), the row counts, the existing matches ordered on the host meanwhile and counted into
+// their rows, the row starts, the candidate total and the largest segment read back, the candidate records (k_pair_fill, k_exist_place).
+struct SeamStage1 {
+    const float4 *d_src = nullptr, *d_tgt = nullptr;
+    const unsigned char* tb = nullptr;      // the table block on the device; P at o_P
+    size_t o_P = 0, nrow = 0;
+    const unsigned* d_l2g = nullptr;
+    PairArgs pa;
+    int R = 0, mmax = 0;                    // candidates, the largest segment's
+};
+#define TPHASE(k) do { const double t_ = now_s(); c->tacc[k] += t_ - tp; tp = t_; } while (0)
+// fill_slots > 0 (tests): the row starts and that many candidate slots (at least) are filled with 0xff bytes before the kernels that write them
+int seam_stage1(l3d_ctx* c, SeamStage1& s1, const float* src_segs, int S_src, const float* RtKinv_src, const float* C_src, const float* tgt_segs, int total_tgt,
+                const int32_t* offsets, int N, const float* F, const float* RtKinv, const float* centers, const float* P, const int32_t* to_be_matched, int n_tbm,
+                int maxW, int W64, const l3d_match* in_matches, int n_in, const uint32_t* local2global, int seg_begin, int seg_end, size_t fill_slots, double& tp)
+{
+    hipStream_t st = c->stream;
+    // ---- small tables: offsets | F | RtKinv | centers | P | RtKinv_src | C_src | tbm | l2g -> one pinned block, one H2D
+    const float4 *d_src = nullptr, *d_tgt = nullptr;
+    int rc;
+    if ((rc = to_device(c, c->src_segs, src_segs, (size_t)S_src * 16, &d_src))) return rc;
+    if ((rc = to_device(c, c->tgt_segs, tgt_segs, (size_t)total_tgt * 16, &d_tgt))) return rc;
+    const size_t o_off = 0, o_F = o_off + (size_t)N * 8, o_R = o_F + (size_t)N * 36, o_C = o_R + (size_t)N * 36,
+                 o_P = o_C + (size_t)N * 12, o_Rs = o_P + (size_t)N * 48, o_Cs = o_Rs + 36, o_tbm = o_Cs + 12,
+                 o_l2g = o_tbm + (size_t)n_tbm * 4, t_bytes = o_l2g + (size_t)N * 4;
+    HIPCHK(c, c->pin_tab.reserve(t_bytes));
+    unsigned char* tab = c->pin_tab.as<unsigned char>();
+    memcpy(tab + o_off, offsets, (size_t)N * 8);
+    memcpy(tab + o_F, F, (size_t)N * 36);
+    memcpy(tab + o_R, RtKinv, (size_t)N * 36);
+    memcpy(tab + o_C, centers, (size_t)N * 12);
+    memcpy(tab + o_P, P, (size_t)N * 48);
+    memcpy(tab + o_Rs, RtKinv_src, 36);
+    memcpy(tab + o_Cs, C_src, 12);
+    memcpy(tab + o_tbm, to_be_matched, (size_t)n_tbm * 4);
+    memcpy(tab + o_l2g, local2global, (size_t)N * 4);
+    HIPCHK(c, c->tables.reserve(t_bytes));
+    HIPCHK(c, hipMemcpyAsync(c->tables.p, tab, t_bytes, hipMemcpyHostToDevice, st));
+    const unsigned char* tb = c->tables.as<unsigned char>();
+
+    const size_t nrow = (size_t)S_src * N;
+    HIPCHK(c, c->mask.reserve((size_t)n_tbm * S_src * W64 * 8));
+    HIPCHK(c, c->rowcnt.reserve(nrow * 4));
+    HIPCHK(c, c->row_start.reserve((nrow + 1) * 4));
+    HIPCHK(c, c->kept_cnt.reserve((size_t)S_src * 4 + 4));
+    HIPCHK(c, c->kept_start.reserve((size_t)S_src * 4 + 8));
+    HIPCHK(c, c->best.reserve((size_t)S_src * 8 + 8));
+    HIPCHK(c, c->scal.reserve(64));
+    HIPCHK(c, c->pin_scal.reserve(64));
+    HIPCHK(c, hipMemsetAsync(c->rowcnt.p, 0, nrow * 4, st));
+    HIPCHK(c, hipMemsetAsync(c->kept_cnt.p, 0, (size_t)S_src * 4, st));
+    HIPCHK(c, hipMemsetAsync(c->scal.p, 0, 4, st));
+    if (fill_slots) HIPCHK(c, hipMemsetAsync(c->row_start.p, 0xff, (nrow + 1) * 4, st));
+
+    PairArgs& pa = s1.pa;
+    pa.src_segs = d_src; pa.tgt_segs = d_tgt;
+    pa.offsets = reinterpret_cast<const int2*>(tb + o_off);
+    pa.F = reinterpret_cast<const float*>(tb + o_F);
+    pa.RtKinv = reinterpret_cast<const float*>(tb + o_R);
+    pa.centers = reinterpret_cast<const float*>(tb + o_C);
+    pa.RtKinv_src = reinterpret_cast<const float*>(tb + o_Rs);
+    pa.C_src = reinterpret_cast<const float*>(tb + o_Cs);
+    pa.tbm = reinterpret_cast<const int*>(tb + o_tbm);
+    pa.mask = c->mask.as<unsigned long long>();
+    pa.S_src = S_src; pa.N = N; pa.n_tbm = n_tbm; pa.W64 = W64;
+    pa.seg_begin = seg_begin; pa.seg_end = seg_end; pa.cand_cap = 0; pa.wedge_pretest = c->wedge_pretest; pa.dbg = c->pair_dbg; pa.dbg_view = -1; pa.rowcnt = nullptr;
+    s1.d_src = d_src; s1.d_tgt = d_tgt; s1.tb = tb; s1.o_P = o_P; s1.nrow = nrow;
+    s1.d_l2g = reinterpret_cast<const unsigned*>(tb + o_l2g);
+
+    // stage 1 starts now; the host orders the existing matches meanwhile
+    if (seg_end > seg_begin) {
+        { ProfScope p(c, "pair_mask"); launch_pair_mask(pa, maxW, st, c->opt.pair_spb); }
+        { ProfScope p(c, "row_count"); launch_row_count(pa, c->rowcnt.as<int>(), st); }
+    }
+    TPHASE(0);
+
+    // ---- existing matches: localized by the caller; keep those of the processed range, order them
+    // (segment, camera, target) and rank them inside their (segment, camera) run
+    HIPCHK(c, c->pin_ex.reserve((size_t)n_in * sizeof(ExistRec) + 16));
+    ExistRec* ex = c->pin_ex.as<ExistRec>();
+    int n_ex = 0;
+    {
+        // Callers that append the reverse matches view by view (ascending camera) hand them over sorted by
+        // (camera, origin order); a stable counting sort on the segment then already yields the final order --
+        // verified in one pass, general sort otherwise.
+        std::vector<int>& cnt = c->h_cnt;
+        cnt.assign((size_t)S_src + 1, 0);
+        for (int i = 0; i < n_in; ++i) {
+            const l3d_match& m = in_matches[i];
+            if ((int)m.segID1 < seg_begin || (int)m.segID1 >= seg_end) continue;
+            if ((int)m.camID2 >= N) return fail(c, L3D_ERR_INVALID, "in_matches camera index out of range");
+            cnt[(size_t)m.segID1 + 1]++;
+        }
+        for (int i = 0; i < S_src; ++i) cnt[(size_t)i + 1] += cnt[(size_t)i];
+        n_ex = cnt[(size_t)S_src];
+        for (int i = 0; i < n_in; ++i) {
+            const l3d_match& m = in_matches[i];
+            if ((int)m.segID1 < seg_begin || (int)m.segID1 >= seg_end) continue;
+            ExistRec& r = ex[cnt[(size_t)m.segID1]++];
+            r.seg = (int)m.segID1; r.cam = (int)m.camID2; r.tgt = m.segID2; r.rank = 0;
+            memcpy(r.d, m.depths, 16);
+        }
+        auto less = [](const ExistRec& a, const ExistRec& b) {
+            if (a.seg != b.seg) return a.seg < b.seg;
+            if (a.cam != b.cam) return a.cam < b.cam;
+            return a.tgt < b.tgt;
+        };
+        bool sorted = true;
+        for (int i = 1; i < n_ex && sorted; ++i) sorted = !less(ex[i], ex[i - 1]);
+        if (!sorted) std::stable_sort(ex, ex + n_ex, less);
+        for (int i = 1; i < n_ex; ++i)
+            if (ex[i].seg == ex[i - 1].seg && ex[i].cam == ex[i - 1].cam) ex[i].rank = ex[i - 1].rank + 1;
+    }
+    TPHASE(1);
+    HIPCHK(c, c->exist.reserve((size_t)n_ex * sizeof(ExistRec) + 16));
+    if (n_ex) HIPCHK(c, hipMemcpyAsync(c->exist.p, ex, (size_t)n_ex * sizeof(ExistRec), hipMemcpyHostToDevice, st));
+    { ProfScope p(c, "exist"); launch_exist_hist(c->exist.as<ExistRec>(), n_ex, N, c->rowcnt.as<int>(), st); }
+    { ProfScope p(c, "scan"); launch_scan(c->rowcnt.as<int>(), c->row_start.as<int>(), (int)nrow, nullptr, st); }
+    launch_seg_mmax(c->row_start.as<int>(), N, seg_begin, seg_end, c->scal.as<int>(), st);
+    int* hs = c->pin_scal.as<int>();
+    HIPCHK(c, hipMemcpyAsync(hs, c->row_start.as<int>() + nrow, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(hs + 1, c->scal.p, 4, hipMemcpyDeviceToHost, st));
+    TPHASE(2);
+    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, hipGetLastError());
+    TPHASE(3);
+    s1.R = hs[0]; s1.mmax = hs[1];
+    const size_t slots = std::max((size_t)s1.R, fill_slots);
+    if (slots == 0) return L3D_OK;
+    HIPCHK(c, c->cand_meta.reserve(slots * 8));
+    HIPCHK(c, c->cand_depths.reserve(slots * 16));
+    if (fill_slots) {
+        HIPCHK(c, hipMemsetAsync(c->cand_meta.p, 0xff, slots * 8, st));
+        HIPCHK(c, hipMemsetAsync(c->cand_depths.p, 0xff, slots * 16, st));
+    }
+    if (s1.R == 0) return L3D_OK;
+    if (seg_end > seg_begin) {
+        ProfScope p(c, "pair_fill");
+        launch_pair_fill(pa, c->row_start.as<int>(), c->cand_meta.as<uint2>(), c->cand_depths.as<float4>(), st);
+    }
+    { ProfScope p(c, "exist"); launch_exist_place(c->exist.as<ExistRec>(), n_ex, N, c->row_start.as<int>(), c->cand_meta.as<uint2>(), c->cand_depths.as<float4>(), st); }
+    return L3D_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -449,133 +594,25 @@ int l3d_compute_pairwise_matches(l3d_ctx* c,
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     double tp = now_s();
-#define TPHASE(k) do { const double t_ = now_s(); c->tacc[k] += t_ - tp; tp = t_; } while (0)
-
-    // ---- small tables: offsets | F | RtKinv | centers | P | RtKinv_src | C_src | tbm | l2g -> one pinned block, one H2D
-    const float4 *d_src = nullptr, *d_tgt = nullptr;
+    SeamStage1 s1;
     int rc;
-    if ((rc = to_device(c, c->src_segs, src_segs, (size_t)S_src * 16, &d_src))) return rc;
-    if ((rc = to_device(c, c->tgt_segs, tgt_segs, (size_t)total_tgt * 16, &d_tgt))) return rc;
-    const size_t o_off = 0, o_F = o_off + (size_t)N * 8, o_R = o_F + (size_t)N * 36, o_C = o_R + (size_t)N * 36,
-                 o_P = o_C + (size_t)N * 12, o_Rs = o_P + (size_t)N * 48, o_Cs = o_Rs + 36, o_tbm = o_Cs + 12,
-                 o_l2g = o_tbm + (size_t)n_tbm * 4, t_bytes = o_l2g + (size_t)N * 4;
-    HIPCHK(c, c->pin_tab.reserve(t_bytes));
-    unsigned char* tab = c->pin_tab.as<unsigned char>();
-    memcpy(tab + o_off, offsets, (size_t)N * 8);
-    memcpy(tab + o_F, F, (size_t)N * 36);
-    memcpy(tab + o_R, RtKinv, (size_t)N * 36);
-    memcpy(tab + o_C, centers, (size_t)N * 12);
-    memcpy(tab + o_P, P, (size_t)N * 48);
-    memcpy(tab + o_Rs, RtKinv_src, 36);
-    memcpy(tab + o_Cs, C_src, 12);
-    memcpy(tab + o_tbm, to_be_matched, (size_t)n_tbm * 4);
-    memcpy(tab + o_l2g, local2global, (size_t)N * 4);
-    HIPCHK(c, c->tables.reserve(t_bytes));
-    HIPCHK(c, hipMemcpyAsync(c->tables.p, tab, t_bytes, hipMemcpyHostToDevice, st));
-    const unsigned char* tb = c->tables.as<unsigned char>();
-
-    const size_t nrow = (size_t)S_src * N;
-    HIPCHK(c, c->mask.reserve((size_t)n_tbm * S_src * W64 * 8));
-    HIPCHK(c, c->rowcnt.reserve(nrow * 4));
-    HIPCHK(c, c->row_start.reserve((nrow + 1) * 4));
-    HIPCHK(c, c->kept_cnt.reserve((size_t)S_src * 4 + 4));
-    HIPCHK(c, c->kept_start.reserve((size_t)S_src * 4 + 8));
-    HIPCHK(c, c->best.reserve((size_t)S_src * 8 + 8));
-    HIPCHK(c, c->scal.reserve(64));
-    HIPCHK(c, c->pin_scal.reserve(64));
-    HIPCHK(c, hipMemsetAsync(c->rowcnt.p, 0, nrow * 4, st));
-    HIPCHK(c, hipMemsetAsync(c->kept_cnt.p, 0, (size_t)S_src * 4, st));
-    HIPCHK(c, hipMemsetAsync(c->scal.p, 0, 4, st));
-
-    PairArgs pa;
-    pa.src_segs = d_src; pa.tgt_segs = d_tgt;
-    pa.offsets = reinterpret_cast<const int2*>(tb + o_off);
-    pa.F = reinterpret_cast<const float*>(tb + o_F);
-    pa.RtKinv = reinterpret_cast<const float*>(tb + o_R);
-    pa.centers = reinterpret_cast<const float*>(tb + o_C);
-    pa.RtKinv_src = reinterpret_cast<const float*>(tb + o_Rs);
-    pa.C_src = reinterpret_cast<const float*>(tb + o_Cs);
-    pa.tbm = reinterpret_cast<const int*>(tb + o_tbm);
-    pa.mask = c->mask.as<unsigned long long>();
-    pa.S_src = S_src; pa.N = N; pa.n_tbm = n_tbm; pa.W64 = W64;
-    pa.seg_begin = seg_begin; pa.seg_end = seg_end; pa.cand_cap = 0; pa.wedge_pretest = c->wedge_pretest; pa.dbg = c->pair_dbg; pa.dbg_view = -1; pa.rowcnt = nullptr;
-    const unsigned* d_l2g = reinterpret_cast<const unsigned*>(tb + o_l2g);
-
-    // stage 1 starts now; the host orders the existing matches meanwhile
-    if (seg_end > seg_begin) {
-        { ProfScope p(c, "pair_mask"); launch_pair_mask(pa, maxW, st, c->opt.pair_spb); }
-        { ProfScope p(c, "row_count"); launch_row_count(pa, c->rowcnt.as<int>(), st); }
-    }
-    TPHASE(0);
-
-    // ---- existing matches: localized by the caller; keep those of the processed range, order them
-    // (segment, camera, target) and rank them inside their (segment, camera) run
-    HIPCHK(c, c->pin_ex.reserve((size_t)n_in * sizeof(ExistRec) + 16));
-    ExistRec* ex = c->pin_ex.as<ExistRec>();
-    int n_ex = 0;
-    {
-        // Callers that append the reverse matches view by view (ascending camera) hand them over sorted by
-        // (camera, origin order); a stable counting sort on the segment then already yields the final order --
-        // verified in one pass, general sort otherwise.
-        std::vector<int>& cnt = c->h_cnt;
-        cnt.assign((size_t)S_src + 1, 0);
-        for (int i = 0; i < n_in; ++i) {
-            const l3d_match& m = in_matches[i];
-            if ((int)m.segID1 < seg_begin || (int)m.segID1 >= seg_end) continue;
-            if ((int)m.camID2 >= N) return fail(c, L3D_ERR_INVALID, "in_matches camera index out of range");
-            cnt[(size_t)m.segID1 + 1]++;
-        }
-        for (int i = 0; i < S_src; ++i) cnt[(size_t)i + 1] += cnt[(size_t)i];
-        n_ex = cnt[(size_t)S_src];
-        for (int i = 0; i < n_in; ++i) {
-            const l3d_match& m = in_matches[i];
-            if ((int)m.segID1 < seg_begin || (int)m.segID1 >= seg_end) continue;
-            ExistRec& r = ex[cnt[(size_t)m.segID1]++];
-            r.seg = (int)m.segID1; r.cam = (int)m.camID2; r.tgt = m.segID2; r.rank = 0;
-            memcpy(r.d, m.depths, 16);
-        }
-        auto less = [](const ExistRec& a, const ExistRec& b) {
-            if (a.seg != b.seg) return a.seg < b.seg;
-            if (a.cam != b.cam) return a.cam < b.cam;
-            return a.tgt < b.tgt;
-        };
-        bool sorted = true;
-        for (int i = 1; i < n_ex && sorted; ++i) sorted = !less(ex[i], ex[i - 1]);
-        if (!sorted) std::stable_sort(ex, ex + n_ex, less);
-        for (int i = 1; i < n_ex; ++i)
-            if (ex[i].seg == ex[i - 1].seg && ex[i].cam == ex[i - 1].cam) ex[i].rank = ex[i - 1].rank + 1;
-    }
-    TPHASE(1);
-    HIPCHK(c, c->exist.reserve((size_t)n_ex * sizeof(ExistRec) + 16));
-    if (n_ex) HIPCHK(c, hipMemcpyAsync(c->exist.p, ex, (size_t)n_ex * sizeof(ExistRec), hipMemcpyHostToDevice, st));
-    { ProfScope p(c, "exist"); launch_exist_hist(c->exist.as<ExistRec>(), n_ex, N, c->rowcnt.as<int>(), st); }
-    { ProfScope p(c, "scan"); launch_scan(c->rowcnt.as<int>(), c->row_start.as<int>(), (int)nrow, nullptr, st); }
-    launch_seg_mmax(c->row_start.as<int>(), N, seg_begin, seg_end, c->scal.as<int>(), st);
-    int* hs = c->pin_scal.as<int>();
-    HIPCHK(c, hipMemcpyAsync(hs, c->row_start.as<int>() + nrow, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(hs + 1, c->scal.p, 4, hipMemcpyDeviceToHost, st));
-    TPHASE(2);
-    HIPCHK(c, hipStreamSynchronize(st));
-    HIPCHK(c, hipGetLastError());
-    TPHASE(3);
-    const int R = hs[0], mmax = hs[1];
+    if ((rc = seam_stage1(c, s1, src_segs, S_src, RtKinv_src, C_src, tgt_segs, total_tgt, offsets, N, F, RtKinv, centers, P, to_be_matched, n_tbm, maxW, W64,
+                          in_matches, n_in, local2global, seg_begin, seg_end, 0, tp))) return rc;
+    const int R = s1.R, mmax = s1.mmax;
     if (mmax > c->mmax_seen) c->mmax_seen = mmax;
     c->stats[1] = R;
     if (R == 0) {            // cudawrapper.cu:955-956: matches stays empty, median_depth untouched
         *out_matches = (l3d_match*)malloc(sizeof(l3d_match));
         return L3D_OK;
     }
-
-    HIPCHK(c, c->cand_meta.reserve((size_t)R * 8));
-    HIPCHK(c, c->cand_depths.reserve((size_t)R * 16));
     HIPCHK(c, c->cand_conf.reserve((size_t)R * 4));
     HIPCHK(c, c->kept.reserve((size_t)R * sizeof(Match)));
-
-    if (seg_end > seg_begin) {
-        ProfScope p(c, "pair_fill");
-        launch_pair_fill(pa, c->row_start.as<int>(), c->cand_meta.as<uint2>(), c->cand_depths.as<float4>(), st);
-    }
-    { ProfScope p(c, "exist"); launch_exist_place(c->exist.as<ExistRec>(), n_ex, N, c->row_start.as<int>(), c->cand_meta.as<uint2>(), c->cand_depths.as<float4>(), st); }
+    const float4 *d_src = s1.d_src, *d_tgt = s1.d_tgt;
+    const PairArgs& pa = s1.pa;
+    const unsigned char* tb = s1.tb;
+    const size_t o_P = s1.o_P, nrow = s1.nrow;
+    const unsigned* d_l2g = s1.d_l2g;
+    int* hs = c->pin_scal.as<int>();
 
     VerifyArgs va;
     if ((rc = seam_verify_args(c, va, d_src, d_tgt, pa.offsets, reinterpret_cast<const float*>(tb + o_P), pa.RtKinv_src, pa.C_src, N, seg_begin, seg_end,
@@ -971,6 +1008,157 @@ int l3d_test_verify_candidates(l3d_ctx* c, int S, int N, const float* src_segs, 
     HIPCHK(c, hipMemcpyAsync(best_depths, c->best.p, (size_t)S * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, hipGetLastError());
+    return L3D_OK;
+}
+
+// Stage 1 of one source view on the launch sequence the caller names (tests/test_gpu_stage1_paths.py): the tables are validated on the host, then the
+// product's own set-up and launchers run -- seam_stage1 (path 0), chain_assign_arenas / chain_view_ray_jobs / chain_pair_args / chain_mask_args /
+// chain_fill_args and the chains' scan launches (paths 1 and 2: the filter mask and the workgroup shape are the context's, set for this call and put back).
+int l3d_test_pair_candidates(l3d_ctx* c, int S, int N, const float* src_segs, const float* tgt_segs, int n_tgt, const int32_t* offsets, const float* F,
+                             const float* RtKinv, const float* centers, const float* RtKinv_src, const float* C_src, const int32_t* to_be_matched, int n_tbm,
+                             l3d_test_pair_path* sel, int32_t* row_upper, int32_t* row_count, int32_t* row_start, uint32_t* cand_meta, float* cand_depths)
+{
+    if (!c) return L3D_ERR_INVALID;
+    if (!sel || S < 0 || N < 1 || N > 255 || n_tgt < 0 || n_tbm < 0 || n_tbm > N || !offsets || !F || !RtKinv || !centers || !RtKinv_src || !C_src ||
+        (n_tbm > 0 && !to_be_matched) || (S > 0 && !src_segs) || (n_tgt > 0 && !tgt_segs) || !row_upper || !row_count || !row_start ||
+        sel->capacity < 0 || (sel->capacity > 0 && (!cand_meta || !cand_depths)))
+        return fail(c, L3D_ERR_INVALID, "pair_candidates: bad argument");
+    sel->needed = 0; sel->total = -1; sel->largest = -1; sel->spb_used = 0; sel->overflow = 0;
+    if ((long long)S * N >= 0x7fffffffll) return fail(c, L3D_ERR_INVALID, "pair_candidates: too many rows");
+    if (sel->path < 0 || sel->path > 2) return fail(c, L3D_ERR_INVALID, "pair_candidates: path must be 0, 1 or 2");
+    if (sel->pretest < 0 || sel->pretest > 7) return fail(c, L3D_ERR_INVALID, "pair_candidates: pretest must be 0..7");
+    if (sel->spb < 0 || sel->spb > kSrcPerBlock) return fail(c, L3D_ERR_INVALID, "pair_candidates: spb must be 0 (the launcher's rule) or 1..64");
+    if (sel->seg_begin < 0 || sel->seg_end > S || sel->seg_end < sel->seg_begin) return fail(c, L3D_ERR_INVALID, "pair_candidates: segment range outside [0, S]");
+    if (sel->path == 1 && !chain_fused_rows(N)) return fail(c, L3D_ERR_INVALID, "pair_candidates: fused row starts take up to 96 neighbours");
+    if (sel->path == 0 && (sel->cand_cap != 0 || sel->ray_tables != 0)) return fail(c, L3D_ERR_INVALID, "pair_candidates: cand_cap and ray_tables are the chains' (paths 1 and 2)");
+    if (sel->cand_cap < 0 || (sel->ray_tables != 0 && sel->ray_tables != 1)) return fail(c, L3D_ERR_INVALID, "pair_candidates: cand_cap below 0 or ray_tables not 0 / 1");
+    for (int i = 0; i < N; ++i)
+        if (offsets[2 * i] < 0 || offsets[2 * i + 1] < 0 || (long long)offsets[2 * i] + offsets[2 * i + 1] > n_tgt)
+            return fail(c, L3D_ERR_INVALID, "pair_candidates: offsets outside the target segments");
+    int maxW = 0;
+    for (int j = 0; j < n_tbm; ++j) {
+        if (to_be_matched[j] < 0 || to_be_matched[j] >= N || (j > 0 && to_be_matched[j] <= to_be_matched[j - 1]))
+            return fail(c, L3D_ERR_INVALID, "pair_candidates: to_be_matched must ascend strictly inside [0, N)");
+        maxW = std::max(maxW, offsets[2 * to_be_matched[j] + 1]);
+    }
+    const int W64 = 4 * ((maxW + 255) / 256);
+    if (W64 > kMaxW64) return fail(c, L3D_ERR_INVALID, "pair_candidates: a neighbour has more than 16384 segments");
+    const size_t nrow = (size_t)S * N, capacity = (size_t)sel->capacity;
+    const int s0 = sel->seg_begin, s1 = sel->seg_end;
+    for (size_t i = 0; i < nrow; ++i) row_upper[i] = row_count[i] = 0;
+    memset(row_start, 0xff, (nrow + 1) * 4);
+    if (capacity) { memset(cand_meta, 0xff, capacity * 8); memset(cand_depths, 0xff, capacity * 16); }
+    if (S == 0 || n_tbm == 0) return L3D_OK;
+
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    struct Back { l3d_ctx* c; Options o; int pretest; ~Back() { c->opt = o; c->wedge_pretest = pretest; } } back{ c, c->opt, c->wedge_pretest };
+    c->wedge_pretest = sel->pretest;
+    c->opt.pair_spb = sel->spb;
+    sel->spb_used = pair_mask_src_per_block(s1 - s0, maxW, n_tbm, sel->spb);
+    int rc;
+    const uint2* g_meta = nullptr;
+    const float4* g_depths = nullptr;
+    const int* g_start = nullptr;
+    const int* g_count = nullptr;
+    long long needed = 0;
+
+    if (sel->path == 0) {
+        std::vector<float> P((size_t)N * 12, 0.0f);         // (stage 2's tables: not read)
+        std::vector<uint32_t> l2g((size_t)N);
+        for (int i = 0; i < N; ++i) l2g[(size_t)i] = (uint32_t)i;
+        SeamStage1 s;
+        double tp = now_s();
+        if ((rc = seam_stage1(c, s, src_segs, S, RtKinv_src, C_src, tgt_segs, n_tgt, offsets, N, F, RtKinv, centers, P.data(), to_be_matched, n_tbm, maxW, W64,
+                              nullptr, 0, l2g.data(), s0, s1, std::max(capacity, (size_t)1), tp))) return rc;
+        sel->total = s.R; sel->largest = s.mmax;
+        needed = s.R;
+        g_meta = c->cand_meta.as<uint2>(); g_depths = c->cand_depths.as<float4>(); g_start = c->row_start.as<int>(); g_count = c->rowcnt.as<int>();
+        HIPCHK(c, hipMemcpyAsync(row_upper, g_count, nrow * 4, hipMemcpyDeviceToHost, st));
+    } else {
+        const bool fused = sel->path == 1;
+        l3d_chain_view v = {};
+        v.S_src = S; v.N = N; v.n_tgt = n_tgt; v.n_tbm = n_tbm;
+        std::vector<ChainViewDev> vd(1);
+        ChainViewDev& d = vd[0];
+        if ((rc = to_device(c, c->src_segs, src_segs, (size_t)S * 16, &d.src))) return rc;
+        if ((rc = to_device(c, c->tgt_segs, tgt_segs, (size_t)n_tgt * 16, &d.tgt))) return rc;
+        d.verified = true; d.s0 = s0; d.s1 = s1; d.maxW = maxW; d.W64 = W64;
+        // the table block in the chains' terms: offsets | F | RtKinv | centers | RtKinv_src | C_src | tbm
+        d.o_off = 0; d.o_F = d.o_off + (size_t)N * 8; d.o_R = d.o_F + (size_t)N * 36; d.o_C = d.o_R + (size_t)N * 36; d.o_Rs = d.o_C + (size_t)N * 12;
+        d.o_Cs = d.o_Rs + 36; d.o_tbm = d.o_Cs + 12;
+        const size_t t_bytes = d.o_tbm + (size_t)n_tbm * 4;
+        HIPCHK(c, c->pin_tab.reserve(t_bytes));
+        unsigned char* tab = c->pin_tab.as<unsigned char>();
+        memcpy(tab + d.o_off, offsets, (size_t)N * 8); memcpy(tab + d.o_F, F, (size_t)N * 36); memcpy(tab + d.o_R, RtKinv, (size_t)N * 36);
+        memcpy(tab + d.o_C, centers, (size_t)N * 12); memcpy(tab + d.o_Rs, RtKinv_src, 36); memcpy(tab + d.o_Cs, C_src, 12);
+        memcpy(tab + d.o_tbm, to_be_matched, (size_t)n_tbm * 4);
+        HIPCHK(c, c->tables.reserve(t_bytes));
+        HIPCHK(c, hipMemcpyAsync(c->tables.p, tab, t_bytes, hipMemcpyHostToDevice, st));
+        const unsigned char* tb = c->tables.as<unsigned char>();
+
+        ChainLayout L;
+        L.maxS = S; L.maxN = N;
+        L.mask_bytes = L.max_mask_bytes = chain_align16((size_t)n_tbm * S * W64 * 8);
+        L.rowcnt_ints = nrow; L.best_elems = (size_t)S;
+        if ((rc = chain_assign_arenas(c, &v, 1, vd, L, fused, false, 0, st))) return rc;     // (zeroes the counters k_pair_mask adds into)
+        HIPCHK(c, hipMemsetAsync(d.rowA, 0xff, (nrow + 1) * 4, st));
+        HIPCHK(c, c->scal.reserve(64));
+        HIPCHK(c, c->pin_scal.reserve(64));
+        int* d_stats = c->scal.as<int>();
+        int* hs = c->pin_scal.as<int>();
+        hs[0] = hs[1] = -1;
+        if (sel->ray_tables) {
+            std::vector<RayJob>& jobs = c->ray_jobs;
+            jobs.clear();
+            const size_t n_ray = (size_t)n_tgt + (size_t)S;
+            HIPCHK(c, c->ch_rays.reserve(n_ray * 32 + 2 * sizeof(RayJob) + 512));
+            RayJob* djobs = reinterpret_cast<RayJob*>(c->ch_rays.as<unsigned char>() + ((n_ray * 32 + 255) & ~(size_t)255));
+            size_t ro = 0;
+            chain_view_ray_jobs(v, d, tb, c->ch_rays.as<float4>(), ro, jobs);
+            HIPCHK(c, hipMemsetAsync(c->ch_rays.p, 0xff, n_ray * 32, st));                   // (an entry k_tgt_rays leaves out is a NaN ray)
+            HIPCHK(c, hipMemcpyAsync(djobs, jobs.data(), jobs.size() * sizeof(RayJob), hipMemcpyHostToDevice, st));
+            ProfScope p(c, "tgt_rays", st);
+            launch_tgt_rays(djobs, (int)jobs.size(), std::max(n_tgt, S), st);
+        }
+        const PairArgs pa = chain_pair_args(c, v, d, tb);
+        if (s1 > s0) {
+            { ProfScope p(c, "pair_mask", st); launch_pair_mask(chain_mask_args(pa, d, fused), maxW, st, c->opt.pair_spb); }
+            if (!fused) {
+                ProfScope p(c, "scan", st);
+                if (s0 == 0 && s1 == S) launch_scan(d.rowcnt, d.rowA, (int)nrow, nullptr, st, nullptr, N, 0, S, d_stats);
+                else launch_scan_range(d.rowcnt, d.rowA, N, s0, s1, (int)nrow, nullptr, nullptr, st, d_stats);
+                HIPCHK(c, hipMemcpyAsync(hs, d_stats, 8, hipMemcpyDeviceToHost, st));
+            }
+        }
+        HIPCHK(c, hipMemcpyAsync(row_upper, fused ? d.rowub : d.rowcnt, nrow * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        HIPCHK(c, hipGetLastError());
+        for (size_t i = 0; i < nrow; ++i) needed += row_upper[i];
+        if (!fused && s1 > s0) { sel->total = hs[0]; sel->largest = hs[1]; }
+        const size_t cand_cap = sel->cand_cap > 0 ? (size_t)sel->cand_cap : (size_t)std::max(needed, 1ll);
+        const size_t slots = std::max(std::max((size_t)needed, capacity), (size_t)1);
+        if ((rc = chain_reserve_candidates(c, L, slots, 1))) return rc;
+        HIPCHK(c, hipMemsetAsync(c->ch_ringA_meta.p, 0xff, slots * 8, st));
+        HIPCHK(c, hipMemsetAsync(c->ch_ringA_depths.p, 0xff, slots * 16, st));
+        sel->overflow = (size_t)needed > cand_cap ? 1 : 0;
+        if (s1 > s0) {
+            ProfScope p(c, "pair_fill", st);
+            launch_pair_fill(chain_fill_args(pa, d, fused, cand_cap), d.rowA, c->ch_ringA_meta.as<uint2>(), c->ch_ringA_depths.as<float4>(), st);
+        }
+        g_meta = c->ch_ringA_meta.as<uint2>(); g_depths = c->ch_ringA_depths.as<float4>(); g_start = d.rowA; g_count = d.rowcnt;
+    }
+    sel->needed = (int32_t)needed;
+    HIPCHK(c, hipMemcpyAsync(row_count, g_count, nrow * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(row_start, g_start, (nrow + 1) * 4, hipMemcpyDeviceToHost, st));
+    const bool fits = (size_t)needed <= capacity;
+    if (fits && capacity) {
+        HIPCHK(c, hipMemcpyAsync(cand_meta, g_meta, capacity * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(cand_depths, g_depths, capacity * 16, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, hipGetLastError());
+    if (!fits) return fail(c, L3D_ERR_INVALID, "pair_candidates: the candidates take " + std::to_string(needed) + " slots, the caller gave " + std::to_string(capacity));
     return L3D_OK;
 }
 

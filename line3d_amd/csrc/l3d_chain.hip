@@ -522,13 +522,10 @@ int l3d::run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_cha
     // pass that leaves the candidates cache-hot for the latency-bound kernels that follow.)
     // the row starts of the stage-1 candidates are formed inside k_pair_fill from k_pair_mask's counters and their block sums: no
     // scan launch on the stage-1 stream (the longer of the two), no statistics for the host to wait for -- up to 96 neighbours
-    const bool fused_rows = maxN <= 96;      // (k_pair_mask's LDS block sums: 64 rows N apart span <= 32 blocks)
+    const bool fused_rows = chain_fused_rows(maxN);
     auto enqueue_fillA = [&](int k, hipStream_t s) {
         const ViewDev& d = vd[(size_t)k];
-        PairArgs pa = pair_args(k);
-        pa.cand_cap = (int)cand_cap;
-        pa.rowcnt = d.rowcnt;
-        if (fused_rows) { pa.rowub = d.rowub; pa.rowblk = d.rowblk; pa.rowstart_out = d.rowA; }
+        const PairArgs pa = chain_fill_args(pair_args(k), d, fused_rows, cand_cap);
         { ProfScope p(c, "pair_fill", s); launch_pair_fill(pa, d.rowA, ringA_meta(k), ringA_depths(k), s); }
     };
     auto enqueue_stage1 = [&](int k) -> int {
@@ -537,9 +534,7 @@ int l3d::run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_cha
         if (views[k].S_src > 0) {
             const PairArgs pa = pair_args(k);
             {   // bit rows + row counts (added into the rows zeroed at chain start) in one launch
-                PairArgs pm = pa;
-                pm.rowcnt = fused_rows ? vd[(size_t)k].rowub : vd[(size_t)k].rowcnt;
-                if (fused_rows) pm.rowblk = vd[(size_t)k].rowblk;
+                const PairArgs pm = chain_mask_args(pa, vd[(size_t)k], fused_rows);
                 ProfScope p(c, "pair_mask", s1);
                 launch_pair_mask(pm, vd[(size_t)k].maxW, s1, c->opt.pair_spb);
             }

@@ -162,11 +162,7 @@ int chain_upload_tables(l3d_ctx* c, const l3d_chain_view* views, int n_views, st
     for (int k = 0; k < n_views; ++k) {
         ChainViewDev& d = vd[(size_t)k];
         if (!d.verified || views[k].n_tbm == 0) continue;
-        d.rays = rbase + 2 * ro; ro += (size_t)views[k].n_tgt;
-        jobs.push_back(RayJob{ d.tgt, reinterpret_cast<const int2*>(L.dtab + d.o_off), reinterpret_cast<const float*>(L.dtab + d.o_R), d.rays, views[k].n_tgt, views[k].N });
-        // (the view's own segments under its own camera: what k_pair_fill needs once per (segment, camera) row)
-        d.src_rays = rbase + 2 * ro; ro += (size_t)views[k].S_src;
-        jobs.push_back(RayJob{ d.src, nullptr, reinterpret_cast<const float*>(L.dtab + d.o_Rs), d.src_rays, views[k].S_src, 1 });
+        chain_view_ray_jobs(views[k], d, L.dtab, rbase, ro, jobs);
         max_n_tgt = std::max(max_n_tgt, std::max(views[k].n_tgt, views[k].S_src));
     }
     if (!jobs.empty()) {
@@ -264,6 +260,32 @@ PairArgs chain_pair_args(const l3d_ctx* c, const l3d_chain_view& v, const ChainV
     pa.depth_in_fill = 1;               // the four depths of a stage-1 pair are triangulated once, by k_pair_fill
     pa.tgt_rays = d.rays; pa.src_rays = d.src_rays;
     return pa;
+}
+
+PairArgs chain_mask_args(const PairArgs& pa, const ChainViewDev& d, bool fused_rows)
+{
+    PairArgs pm = pa;                   // bit rows + row counts (added into rows zeroed at chain start) in one launch
+    pm.rowcnt = fused_rows ? d.rowub : d.rowcnt;
+    if (fused_rows) pm.rowblk = d.rowblk;
+    return pm;
+}
+
+PairArgs chain_fill_args(const PairArgs& pa, const ChainViewDev& d, bool fused_rows, size_t cand_cap)
+{
+    PairArgs pf = pa;
+    pf.cand_cap = (int)cand_cap;
+    pf.rowcnt = d.rowcnt;               // (the row's true count replaces k_pair_mask's upper bound)
+    if (fused_rows) { pf.rowub = d.rowub; pf.rowblk = d.rowblk; pf.rowstart_out = d.rowA; }
+    return pf;
+}
+
+void chain_view_ray_jobs(const l3d_chain_view& v, ChainViewDev& d, const unsigned char* dtab, float4* rbase, size_t& ro, std::vector<RayJob>& jobs)
+{
+    d.rays = rbase + 2 * ro; ro += (size_t)v.n_tgt;
+    jobs.push_back(RayJob{ d.tgt, reinterpret_cast<const int2*>(dtab + d.o_off), reinterpret_cast<const float*>(dtab + d.o_R), d.rays, v.n_tgt, v.N });
+    // (the view's own segments under its own camera: what k_pair_fill needs once per (segment, camera) row)
+    d.src_rays = rbase + 2 * ro; ro += (size_t)v.S_src;
+    jobs.push_back(RayJob{ d.src, nullptr, reinterpret_cast<const float*>(dtab + d.o_Rs), d.src_rays, v.S_src, 1 });
 }
 
 VerifyArgs chain_verify_args(l3d_ctx* c, const l3d_chain_view& v, const ChainViewDev& d, const unsigned char* dtab, size_t cand_cap)

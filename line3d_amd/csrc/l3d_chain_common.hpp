@@ -54,6 +54,17 @@ int chain_assign_arenas(l3d_ctx* c, const l3d_chain_view* views, int n_views, st
 int chain_reserve_candidates(l3d_ctx* c, const ChainLayout& L, size_t cand_cap, int ring);
 
 PairArgs chain_pair_args(const l3d_ctx* c, const l3d_chain_view& v, const ChainViewDev& d, const unsigned char* dtab);
+// Stage 1 of a chain view, from chain_pair_args(): the arguments of its k_pair_mask launch and of its k_pair_fill launch (the chains and
+// l3d_test_pair_candidates).  fused_rows: no scan launch in between -- k_pair_mask adds its (upper-bound) counts into rowub and their 256-row
+// block sums into rowblk, k_pair_fill forms a row's start from them, writes it to rowA and the row's true count to rowcnt; else k_pair_mask
+// adds into rowcnt, a scan launch turns that into rowA, and k_pair_fill replaces the row's count by the true one.
+// (k_pair_mask sums the blocks of one workgroup's rows -- up to 64, N apart -- in an LDS table of 26 entries: up to 96 neighbours)
+inline bool chain_fused_rows(int maxN) { return maxN <= 96; }
+PairArgs chain_mask_args(const PairArgs& pa, const ChainViewDev& d, bool fused_rows);
+PairArgs chain_fill_args(const PairArgs& pa, const ChainViewDev& d, bool fused_rows, size_t cand_cap);
+// One view's two jobs of k_tgt_rays (its targets under their cameras, its own segments under its own) appended to `jobs`, the view's slices of the
+// ray table at rbase + 2 * ro handed to it (ro advances by the entries taken).
+void chain_view_ray_jobs(const l3d_chain_view& v, ChainViewDev& d, const unsigned char* dtab, float4* rbase, size_t& ro, std::vector<RayJob>& jobs);
 // everything of VerifyArgs that does not depend on the chain flavour (candidate arrays of the context, tables, range, parameters)
 VerifyArgs chain_verify_args(l3d_ctx* c, const l3d_chain_view& v, const ChainViewDev& d, const unsigned char* dtab, size_t cand_cap);
 // the window kernel's launch on those arguments (LDS image from the raw maximum per segment, or the largest the budget allows), or the

@@ -510,8 +510,7 @@ static int shard_stage1(l3d_shard_chain* h, int k)
     if (d.s1 > d.s0) {
         const PairArgs pa = shard_pair_args(h, k);
         {   // bit rows + row counts (added into the rows zeroed when the chain was opened) in one launch
-            PairArgs pm = pa;
-            pm.rowcnt = d.rowcnt;
+            const PairArgs pm = chain_mask_args(pa, d, false);
             ProfScope p(c, "pair_mask", s1);
             launch_pair_mask(pm, d.maxW, s1, c->opt.pair_spb);
         }
@@ -520,9 +519,7 @@ static int shard_stage1(l3d_shard_chain* h, int k)
         // depth records of the stage-1 candidates, in their own row order, into the ring slot last used by view k - kRingA
         // (its completion event is recorded by l3d_shard_chain_mark before this view's stage 1 is enqueued)
         if (k - l3d_shard_chain::kRingA >= 0) HIPCHK(c, hipStreamWaitEvent(s1, h->ev2[(size_t)(k - l3d_shard_chain::kRingA)], 0));
-        PairArgs pf = pa;
-        pf.cand_cap = (int)h->cand_cap;
-        pf.rowcnt = d.rowcnt;           // (the row's true count replaces k_pair_mask's upper bound)
+        const PairArgs pf = chain_fill_args(pa, d, false, h->cand_cap);
         { ProfScope p(c, "pair_fill", s1); launch_pair_fill(pf, d.rowA, c->ch_ringA_meta.as<uint2>() + (size_t)(k % l3d_shard_chain::kRingA) * h->cand_cap,
                                                              c->ch_ringA_depths.as<float4>() + (size_t)(k % l3d_shard_chain::kRingA) * h->cand_cap, s1); }
     }

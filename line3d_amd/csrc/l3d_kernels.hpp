@@ -77,8 +77,8 @@ struct PairArgs {
     const float4* src_rays = nullptr;   // ... and of the view's own end points (2 per source segment)
     int depth_in_fill = 0;          // resident chain: k_pair_mask stops after the exact overlap test (its bits and row counts are then an UPPER
                                     // bound), the four depths are triangulated ONCE, in k_pair_fill, which drops the pairs without four positive
-                                    // depths (cudawrapper.cu:931), packs the row and writes its true count back into rowcnt; 0: the bit already
-                                    // says "four positive depths" (per-view seam call, sharded chain)
+                                    // depths (cudawrapper.cu:931), packs the row and writes its true count back into rowcnt (both chains:
+                                    // chain_pair_args); 0: the bit already says "four positive depths" (per-view seam call)
 };
 
 struct VerifyArgs {
@@ -134,6 +134,7 @@ inline void touch_kernel(const void* f) { hipFuncAttributes a; (void)hipFuncGetA
 
 // forced_spb / wide_max / vw_lds_opt: the context's own switches (options pair_spb, vw_wide_max, vw_lds) -- per context, not process-wide
 void launch_pair_mask(const PairArgs& a, int maxW, hipStream_t st, int forced_spb = 0);
+int pair_mask_src_per_block(int n_src, int maxW, int n_tbm, int forced);    // launch_pair_mask's rule (l3d_test_pair_candidates reports it)
 void launch_row_count(const PairArgs& a, int* rowcnt, hipStream_t st);
 void launch_exist_hist(const ExistRec* ex, int n, int N, int* rowcnt, hipStream_t st);
 struct RayJob {                     // one view of k_tgt_rays

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import l3d_oracle_pipeline as op
+from helpers import sector_rejected as _sector_rejected
 
 pytestmark = pytest.mark.gpu
 
@@ -248,20 +249,6 @@ def test_pair_pretest_is_conservative(gpu_ctx):
         if step == 0.12:
             assert res[0][3] > 10000
     assert total_pairs > 1e8
-
-
-def _sector_rejected(mv, cam, accepted):
-    """Oracle-accepted pairs of (source view, local camera `cam`) whose target segment lies inside ONE same-sign sector of the
-    source endpoints' epipolar lines -- the pairs a sector test without the e_d condition would drop (float64 geometry)."""
-    o0, n = mv["offsets"][cam]
-    s1 = mv["src_segs"].astype(np.float64)
-    s2 = mv["tgt_segs"][o0:o0 + n].astype(np.float64)
-    F = mv["F"][cam].astype(np.float64)
-    one = lambda a: np.concatenate([a, np.ones((len(a), 1))], 1)
-    e1, e2 = one(s1[:, :2]) @ F.T, one(s1[:, 2:]) @ F.T
-    q1, q2 = one(s2[:, :2]), one(s2[:, 2:])
-    a = np.stack([e1 @ q1.T, e1 @ q2.T, e2 @ q1.T, e2 @ q2.T])
-    return int((accepted & ((a > 0).all(0) | (a < 0).all(0))).sum())
 
 
 def test_pair_pretest_wrapping_epipolar_transfer(gpu_ctx, oracle_lib):
