@@ -316,6 +316,103 @@ public:
         if (any) std::cerr << prefix_ << l3d_line3d_last_error(h_) << std::endl;
         return status;
     }
+    // Images in DEVICE memory (include/line3d_amd.h, "Images in DEVICE memory"): a cv::cuda::GpuMat, a frame of a decoder, a tensor's pointer.
+    // A GpuMat has cv::Mat's members (.data, .step, .cols, .rows, .channels()), so the overloads above would take its pointer for host memory:
+    // the device forms have NAMES OF THEIR OWN and nothing is detected automatically.  An image type with those members is taken as 8-bit
+    // interleaved pixels with `step` in bytes; every other layout and type (planar, float, 16-bit, strided, flipped) comes as an
+    // l3d_device_image, filled by the caller.  `stream`: the hipStream_t the pixels were produced on (nullptr: the null stream); the library
+    // waits for it before reading, and every call returns with the image consumed (an output: written).  The cache rules are addImage's: a
+    // cache that is present and wanted stands in for the image, whose memory is then not touched.
+    template <class Img, class = decltype(static_cast<const unsigned char*>(std::declval<const Img&>().data)),
+              class = decltype(static_cast<size_t>(std::declval<const Img&>().step)), class = decltype(static_cast<int>(std::declval<const Img&>().channels()))>
+    static l3d_device_image deviceImage(const Img& image, void* stream = nullptr)
+    {
+        l3d_device_image d;
+        d.ptr = static_cast<const unsigned char*>(image.data);
+        d.width = (int)image.cols; d.height = (int)image.rows; d.channels = static_cast<int>(image.channels());
+        d.dtype = L3D_U8;
+        d.stride_y = (long long)static_cast<size_t>(image.step); d.stride_x = d.channels; d.stride_c = 1;
+        d.chan[0] = 0; d.chan[1] = 1; d.chan[2] = 2;
+        d.scale = 1.0f;
+        d.stream = stream;
+        return d;
+    }
+    struct DeviceEntry {
+        ImageEntry base;                // the id, the camera, dist and the links; no pixels and no file
+        l3d_device_image image;
+        DeviceEntry& distorted(const double k1, const double k2) { base.distorted(k1, k2); return *this; }
+    };
+    template <class M3, class V3, class Links, class = decltype(std::declval<const M3&>()(0, 0)), class = decltype(std::declval<const V3&>()(0))>
+    static DeviceEntry makeDeviceEntry(const unsigned int imageID, const l3d_device_image& image, const M3& K, const M3& R, const V3& t, const Links& links)
+    {
+        DeviceEntry e;
+        e.base.imageID = imageID;
+        e.image = image;
+        flatten(K, R, t, e.base.K, e.base.R, e.base.t);
+        set_links(e.base, links);
+        return e;
+    }
+    template <class Img, class M3, class V3, class Links, class = decltype(static_cast<const unsigned char*>(std::declval<const Img&>().data)),
+              class = decltype(static_cast<size_t>(std::declval<const Img&>().step)), class = decltype(static_cast<int>(std::declval<const Img&>().channels())),
+              class = decltype(std::declval<const M3&>()(0, 0)), class = decltype(std::declval<const V3&>()(0))>
+    static DeviceEntry makeDeviceEntry(const unsigned int imageID, const Img& image, const M3& K, const M3& R, const V3& t, const Links& links, void* stream = nullptr)
+    {
+        return makeDeviceEntry(imageID, deviceImage(image, stream), K, R, t, links);
+    }
+    // `image`: an l3d_device_image, or an image type with a GpuMat's members (on the null stream; another stream: makeDeviceEntry + addImagesDevice)
+    template <class Img, class M3, class V3>
+    void addImageDevice(const unsigned int imageID, const Img& image, const M3& K, const M3& R, const V3& t, std::list<unsigned int>& worldpointIDs,
+                        const int maxImgWidth = 1920, const bool loadAndStoreSegments = true)
+    {
+        add_device(makeDeviceEntry(imageID, image, K, R, t, worldpointIDs), maxImgWidth, loadAndStoreSegments);
+    }
+    template <class Img, class M3, class V3>
+    void addImageDeviceDistorted(const unsigned int imageID, const Img& image, const M3& K, const M3& R, const V3& t, const double k1, const double k2,
+                                 std::list<unsigned int>& worldpointIDs, const int maxImgWidth = 1920, const bool loadAndStoreSegments = true)
+    {
+        add_device(makeDeviceEntry(imageID, image, K, R, t, worldpointIDs).distorted(k1, k2), maxImgWidth, loadAndStoreSegments);
+    }
+    template <class Img, class M3, class V3>
+    void addImage_fixed_simDevice(const unsigned int imageID, const Img& image, const M3& K, const M3& R, const V3& t, std::map<unsigned int, float>& viewSimilarity,
+                                  const int maxImgWidth = 1920, const bool loadAndStoreSegments = true)
+    {
+        add_device(makeDeviceEntry(imageID, image, K, R, t, viewSimilarity), maxImgWidth, loadAndStoreSegments);
+    }
+    template <class Img, class M3, class V3>
+    void addImage_fixed_simDeviceDistorted(const unsigned int imageID, const Img& image, const M3& K, const M3& R, const V3& t, const double k1, const double k2,
+                                           std::map<unsigned int, float>& viewSimilarity, const int maxImgWidth = 1920, const bool loadAndStoreSegments = true)
+    {
+        add_device(makeDeviceEntry(imageID, image, K, R, t, viewSimilarity).distorted(k1, k2), maxImgWidth, loadAndStoreSegments);
+    }
+    // addImages for device images (l3d_line3d_add_device_images): one run of the detector, one gather launch per chunk; statuses as addImages
+    std::vector<int> addImagesDevice(const std::vector<DeviceEntry>& entries, const int maxImgWidth = 1920, const bool loadAndStoreSegments = true)
+    {
+        std::vector<l3d_device_entry> e;
+        for (const DeviceEntry& s : entries) e.push_back(to_c(s));
+        std::vector<int> status(entries.size(), L3D_ERR_INVALID);
+        const int rc = l3d_line3d_add_device_images(h_, e.data(), (int)e.size(), data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0, status.data());
+        bool any = rc != L3D_OK;
+        for (int st : status) any = any || st != L3D_OK;
+        if (any) std::cerr << prefix_ << l3d_line3d_last_error(h_) << std::endl;
+        return status;
+    }
+    // decodeJPEG into the caller's device memory: out's size and channels (1, or 3 / 4 for a colour file) must be the file's (jpegSize)
+    bool decodeJPEGDevice(const unsigned char* bytes, const size_t n, const l3d_device_image& out)
+    {
+        const int rc = l3d_line3d_decode_jpeg_device(h_, bytes, n, &out);
+        report(rc);
+        return rc == L3D_OK;
+    }
+    // undistortImage on the device: `in` and `out` of one size and channel count; they may describe the same memory
+    template <class M3, class = decltype(std::declval<const M3&>()(0, 0))>
+    bool undistortImageDevice(const l3d_device_image& in, const M3& K, const double k1, const double k2, const l3d_device_image& out)
+    {
+        double k[9];
+        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) k[i * 3 + j] = K(i, j);
+        const int rc = l3d_line3d_undistort_image_device(h_, &in, k, k1, k2, &out);
+        report(rc);
+        return rc == L3D_OK;
+    }
     // line3D.h:82
     void compute3Dmodel(bool perform_diffusion = false) { report(l3d_line3d_compute3Dmodel(h_, perform_diffusion ? 1 : 0)); }
     // line3D.h:85
@@ -400,6 +497,20 @@ private:
         d.K = s.K; d.R = s.R; d.t = s.t; d.dist = s.has_dist ? s.dist : nullptr;
         d.link_ids = s.link_ids.data(); d.sims = s.fixed_sim ? s.sims.data() : nullptr; d.n_links = (int)s.link_ids.size();
         return d;
+    }
+    static l3d_device_entry to_c(const DeviceEntry& s)
+    {
+        l3d_device_entry d;
+        d.image_id = s.base.imageID;
+        d.image = s.image;
+        d.K = s.base.K; d.R = s.base.R; d.t = s.base.t; d.dist = s.base.has_dist ? s.base.dist : nullptr;
+        d.link_ids = s.base.link_ids.data(); d.sims = s.base.fixed_sim ? s.base.sims.data() : nullptr; d.n_links = (int)s.base.link_ids.size();
+        return d;
+    }
+    void add_device(const DeviceEntry& s, int maxImgWidth, bool loadAndStoreSegments)
+    {
+        const l3d_device_entry e = to_c(s);
+        report(l3d_line3d_add_device_entry(h_, &e, data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0));
     }
     // every image and JPEG form: one entry through the library's one route (l3d_line3d_add_image_entry)
     void add_one(const ImageEntry& s, int maxImgWidth, bool loadAndStoreSegments)

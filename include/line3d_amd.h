@@ -893,6 +893,84 @@ typedef struct l3d_detect_entry {
 int l3d_detect_segments_batch(l3d_ctx* ctx, const l3d_detect_entry* e, int n, float** segments, int* offsets /* n + 1 */, int* status /* n */);
 
 /* =================================================================================================
+ * Images in DEVICE memory (line3d_amd/csrc/l3d_device_image.hip): a decoded video frame, a tensor, a GpuMat -- described where they lie and gathered
+ * by one kernel (k_det_ingest, one launch per chunk of the batch detector) into the detector's pixel buffer, the place the upload of host pixels and
+ * the JPEG kernels fill.  Nothing crosses the host.
+ *
+ * The descriptor.  Element (y, x, c) is at ptr + (y stride_y + x stride_x + c stride_c) sizeof(element); strides are in ELEMENTS and signed, 0 is
+ * allowed (a broadcast channel).  One form covers H x W x C, C x H x W, cropped, strided and flipped views and one image of an N x ... batch.
+ * channels is the SOURCE's: 1, 3 or 4.  A source of 1 channel gives the detector 1 channel, one of 3 or 4 gives it 3: detector channel k is read
+ * from source channel chan[k] (ignored for channels == 1).  The detector applies CV_RGB2GRAY's weights to its buffer as it stands (`grey` above), so
+ * an R, G, B tensor that must give the segments of the cv::imread (B, G, R) image passes chan = {2, 1, 0}.
+ *
+ * THE CONVERSION RULE to the detector's 8 bits, exact:
+ *     L3D_U8                     copied as is (scale is ignored)
+ *     L3D_U16, L3D_F16, L3D_F32  x converted to f32 (exact), y = x * scale (ONE f32 multiplication, nothing fused), r = rint(y) (ties to even),
+ *                                NaN gives 0, the result is clamped to 0 .. 255
+ * A tensor in [0, 1] passes scale = 255, a 16-bit image scale = 1 / 257.  The way back (k_det_egress, the ..._device output calls): U8 as is;
+ * F32 (float)v * scale; F16 that f32 rounded to nearest even; U16 clamp(rint(v * scale), 0, 65535).  Output channel chan[k] receives detector
+ * channel k; a fourth channel of the output is left as it is.
+ *
+ * Checked without a device (pure host functions):
+ *   l3d_device_image_check    the fields: a size of at least 1x1 (the detector itself needs 8x8 and says so in l3d_detect_segments' words),
+ *                             channels 1, 3 or 4, a dtype of the list, chan within the source's channels, scale finite (every dtype but U8).
+ *                             L3D_ERR_INVALID with the cause in msg (n bytes, may be NULL)
+ *   l3d_device_image_extent   *lo, *hi: the lowest and one past the highest BYTE offset from ptr the image addresses (only the channels of chan
+ *                             count).  L3D_ERR_UNSUPPORTED when a product or the sum leaves 2^62 in magnitude, or width x height x 3 exceeds the
+ *                             detector's 2^31; L3D_ERR_INVALID for fields l3d_device_image_check refuses
+ * Checked BEFORE THE FIRST LAUNCH that reads or writes ptr (l3d_test_device_image_pointer is that routine alone: it returns the code and launches
+ * nothing): hipPointerGetAttributes must say device memory of the context's device (a node object: rank 0's, where its detector runs) -- else
+ * L3D_ERR_INVALID naming the kind of memory or both devices; and the extent must lie inside the allocation hipMemGetAddressRange reports for ptr --
+ * else L3D_ERR_INVALID with the numbers.  Where the runtime reports no range for device memory (virtual-memory allocations) the extent check
+ * is skipped.  Nothing is launched on a refusal.
+ *
+ * STREAM ORDER.  `stream` is the hipStream_t the pixels were produced on (NULL: the null stream).  Before the launch an event (one per context,
+ * reused) is recorded on it and the context's stream waits for it: work enqueued there before the call is seen.  Every call taking a descriptor ends in
+ * a synchronise of the context's stream: when it returns an input has been consumed and an output has been written -- the caller may reuse or
+ * free the memory at once and read an output from any stream.
+ *
+ *   l3d_detect_segments_device        l3d_detect_segments on the image the descriptor gives; camera: NULL, or (fx, fy, cx, cy, k1, k2) of
+ *                                     l3d_detect_segments_distorted.  The segments are byte for byte those of the host call on the converted pixels
+ *   l3d_detect_segments_device_batch  l3d_detect_segments_batch's contract word for word, the entries device images: each entry's segments are
+ *                                     byte for byte the single call's, the chunk's images are ingested by ONE launch, a refused entry (fields,
+ *                                     memory kind, extent) fails alone, one line per failure in l3d_last_error
+ *   l3d_decode_jpeg_device            l3d_decode_jpeg into the caller's device memory (`out`, written through k_det_egress); out's width, height
+ *                                     and detector channel count (1 for channels == 1, else 3) must be the file's: L3D_ERR_INVALID otherwise
+ *   l3d_undistort_image_device        ingest, k_det_undistort, egress: in and out of one size and detector channel count, and they may describe the
+ *                                     same memory; both coefficients within 1e-12: ingest and egress only
+ *   l3d_test_device_ingest            (tests) check, stream wait and the k_det_ingest launch of the product for a chunk of n images of one size and
+ *                                     detector channel count; out: their slots of the pixel buffer, n x height x width x (1 or 3) bytes
+ * ================================================================================================= */
+#define L3D_U8 0
+#define L3D_U16 1
+#define L3D_F16 2
+#define L3D_F32 3
+typedef struct l3d_device_image {
+    const void* ptr;                 /* device memory; element (y, x, c) is at ptr + (y*stride_y + x*stride_x + c*stride_c) * sizeof(element) */
+    int width, height, channels;     /* channels of the SOURCE: 1, 3 or 4 */
+    int dtype;                       /* L3D_U8, L3D_U16, L3D_F16, L3D_F32 */
+    long long stride_y, stride_x, stride_c;   /* in ELEMENTS, signed; 0 allowed (a broadcast channel) */
+    int chan[3];                     /* detector channel k is read from source channel chan[k]; ignored for channels == 1 */
+    float scale;                     /* see the conversion rule; ignored for L3D_U8 */
+    void* stream;                    /* the hipStream_t the pixels were produced on; NULL: the null stream */
+} l3d_device_image;
+typedef struct l3d_detect_device_entry {
+    l3d_device_image image;
+    int new_width, new_height; float min_length; int max_segments;
+    const double* camera;                                                           /* NULL, or fx, fy, cx, cy, k1, k2 */
+} l3d_detect_device_entry;
+int l3d_device_image_check(const l3d_device_image* image, char* msg, size_t n);
+int l3d_device_image_extent(const l3d_device_image* image, long long* lo, long long* hi);
+int l3d_test_device_image_pointer(l3d_ctx* ctx, const l3d_device_image* image);
+int l3d_test_device_ingest(l3d_ctx* ctx, const l3d_device_image* images, int n, unsigned char* out);
+int l3d_detect_segments_device(l3d_ctx* ctx, const l3d_device_image* image, int new_width, int new_height, float min_length, int max_segments,
+                               const double* camera /* NULL or fx, fy, cx, cy, k1, k2 */, float** segments, int* n);
+int l3d_detect_segments_device_batch(l3d_ctx* ctx, const l3d_detect_device_entry* e, int n, float** segments, int* offsets /* n + 1 */, int* status /* n */);
+int l3d_decode_jpeg_device(l3d_ctx* ctx, const unsigned char* bytes, size_t n, const l3d_device_image* out);
+int l3d_undistort_image_device(l3d_ctx* ctx, const l3d_device_image* in, double fx, double fy, double cx, double cy, double k1, double k2,
+                               const l3d_device_image* out);
+
+/* =================================================================================================
  * THE ADD FAMILY: Line3D::addImage / addImage_fixed_sim (line3D.cc:95-342) in every form the library takes an image in.
  *
  * An image to add is an ENTRY: its id; the image -- 8-bit pixels (as l3d_detect_segments takes them) or a baseline JPEG file in memory, exactly one
@@ -942,6 +1020,29 @@ typedef struct l3d_image_entry {
 } l3d_image_entry;
 int l3d_line3d_add_image_entry(l3d_line3d* h, const l3d_image_entry* e, const char* data_directory, int max_img_width, int load_and_store);
 int l3d_line3d_add_images(l3d_line3d* h, const l3d_image_entry* e, int n, const char* data_directory, int max_img_width, int load_and_store, int* status);
+
+/* The add family for an image in DEVICE memory (l3d_device_image, above): the entry with a descriptor where l3d_image_entry has pixels or a file.  It
+ * takes the ONE ROUTE above, with these words for its image:
+ *   1. l3d_device_image_check on the descriptor (its code and message), the camera of the undistortion as above; the view's size is the
+ *      descriptor's, the detector's channels 1 (channels == 1) or 3
+ *   2. the cache decision, unchanged
+ *   3. only where the detector runs: the pointer check, the extent check, the stream wait, k_det_ingest, the detector.  A cache that is present and
+ *      wanted stands in for the image, whose memory is then never touched and never checked -- as a JPEG file's entropy data is not
+ *   4., 5. unchanged; the guards come after the detector
+ * l3d_line3d_add_device_entry is the single call, l3d_line3d_add_device_images the batch with l3d_line3d_add_images' contract (one run of the batch
+ * detector, one k_det_ingest launch per chunk, an entry fails alone, "image <id>: <message>" per failure).  A batch that mixes host, JPEG and device
+ * entries in one call is not offered.  l3d_line3d_decode_jpeg_device / l3d_line3d_undistort_image_device: the context calls on the object's device
+ * (a node object: rank 0's), the latter with the object's K rule (l3d_line3d_undistort_image). */
+typedef struct l3d_device_entry {
+    uint32_t image_id;
+    l3d_device_image image;
+    const double *K, *R, *t, *dist;                 /* dist: NULL or k1, k2 */
+    const uint32_t* link_ids; const float* sims; int n_links;   /* sims == NULL: world point ids; else view similarities */
+} l3d_device_entry;
+int l3d_line3d_add_device_entry(l3d_line3d* h, const l3d_device_entry* e, const char* data_directory, int max_img_width, int load_and_store);
+int l3d_line3d_add_device_images(l3d_line3d* h, const l3d_device_entry* e, int n, const char* data_directory, int max_img_width, int load_and_store, int* status);
+int l3d_line3d_decode_jpeg_device(l3d_line3d* h, const unsigned char* bytes, size_t n, const l3d_device_image* out);
+int l3d_line3d_undistort_image_device(l3d_line3d* h, const l3d_device_image* in, const double* K, double k1, double k2, const l3d_device_image* out);
 
 /* The detector's stages on their own, exported for tests (tests/test_gpu_detect_stages.py): the same kernels with the same launch shapes
  * as l3d_detect_segments, results copied to caller-allocated arrays.  (N, M) = (ceil(0.8 new_width), ceil(0.8 new_height)) is the scaled image.

@@ -145,6 +145,158 @@ class ImageEntry(C.Structure):
                 ("dist", C.c_void_p), ("link_ids", C.c_void_p), ("sims", C.c_void_p), ("n_links", C.c_int)]
 
 
+# dtype codes of l3d_device_image (L3D_U8 ...)
+U8, U16, F16, F32 = 0, 1, 2, 3
+_TYPESTR = {"|u1": U8, "<u2": U16, "<f2": F16, "<f4": F32}
+_ELEMENT_BYTES = {U8: 1, U16: 2, F16: 2, F32: 4}
+
+
+class DeviceImage(C.Structure):
+    """l3d_device_image (include/line3d_amd.h): an image in device memory, where it lies and how it converts to the detector's 8 bits"""
+    _fields_ = [("ptr", C.c_void_p), ("width", C.c_int), ("height", C.c_int), ("channels", C.c_int), ("dtype", C.c_int),
+                ("stride_y", C.c_longlong), ("stride_x", C.c_longlong), ("stride_c", C.c_longlong), ("chan", C.c_int * 3), ("scale", C.c_float),
+                ("stream", C.c_void_p)]
+
+
+class DetectDeviceEntry(C.Structure):
+    """l3d_detect_device_entry (include/line3d_amd.h)"""
+    _fields_ = [("image", DeviceImage), ("new_width", C.c_int), ("new_height", C.c_int), ("min_length", C.c_float), ("max_segments", C.c_int),
+                ("camera", C.c_void_p)]
+
+
+class DeviceEntry(C.Structure):
+    """l3d_device_entry (include/line3d_amd.h)"""
+    _fields_ = [("image_id", C.c_uint32), ("image", DeviceImage), ("K", C.c_void_p), ("R", C.c_void_p), ("t", C.c_void_p), ("dist", C.c_void_p),
+                ("link_ids", C.c_void_p), ("sims", C.c_void_p), ("n_links", C.c_int)]
+
+
+def is_device_object(obj):
+    """a DeviceImage, or anything that carries __cuda_array_interface__ (torch device tensors do, on ROCm builds as well; a host tensor does not)"""
+    return isinstance(obj, DeviceImage) or hasattr(obj, "__cuda_array_interface__")
+
+
+def all_device_objects(images, what):
+    """True: every image of the list is a device object; False: none is.  A list that mixes the two raises ValueError -- before any library call"""
+    kinds = [is_device_object(im) for im in images]
+    if any(kinds) and not all(kinds):
+        raise ValueError("%s: a list mixes images in device memory with host images or files; give them in separate calls" % what)
+    return bool(kinds) and all(kinds)
+
+
+def device_image(obj, layout=None, chan=None, scale=None, stream=None):
+    """The l3d_device_image of anything with __cuda_array_interface__ (a DeviceImage passes through).  Layout: 2-D is H x W; 3-D with a last
+    dimension of 1, 3 or 4 is H x W x C (an ambiguous 3 x 5 x 3 too) unless layout="CHW" says planar.  Strides come from the interface's
+    bytes (ValueError when they are no whole elements); typestr |u1, <u2, <f2, <f4 (TypeError otherwise).  chan defaults to (0, 1, 2),
+    scale to 255 for the float types, 1 / 257 for 16-bit integers and 1 for 8-bit.  stream: an integer handle or an object with .cuda_stream;
+    None: the current stream of a torch tensor's device, else the interface's `stream` entry, else the null stream.  The object is kept
+    alive on the descriptor."""
+    if isinstance(obj, DeviceImage):
+        return obj
+    iface = obj.__cuda_array_interface__
+    typestr = str(iface["typestr"])
+    if typestr not in _TYPESTR:
+        raise TypeError("device image: typestr %r is not one of |u1, <u2, <f2, <f4" % typestr)
+    dtype = _TYPESTR[typestr]
+    es = _ELEMENT_BYTES[dtype]
+    shape = tuple(int(v) for v in iface["shape"])
+    strides = iface.get("strides")
+    if strides is None:                 # contiguous, C order
+        strides, acc = [], es
+        for dim in reversed(shape):
+            strides.insert(0, acc)
+            acc *= dim
+    strides = [int(v) for v in strides]
+    if any(v % es for v in strides):
+        raise ValueError("device image: byte strides %s are no whole elements of %d bytes" % (strides, es))
+    strides = [v // es for v in strides]
+    if layout not in (None, "HWC", "CHW", "HW"):
+        raise ValueError("device image: layout must be None, 'HW', 'HWC' or 'CHW'")
+    if len(shape) == 2 and layout in (None, "HW"):
+        layout, (h, w), ch = "HW", shape, 1
+        sy, sx, sc = strides[0], strides[1], 0
+    elif len(shape) == 3 and layout == "CHW":
+        ch, h, w = shape
+        sc, sy, sx = strides
+    elif len(shape) == 3 and layout in (None, "HWC"):
+        if layout is None and shape[2] not in (1, 3, 4):
+            raise ValueError("device image: a shape of %s is no H x W x C image of 1, 3 or 4 channels; planar images pass layout='CHW'" % (shape,))
+        layout, (h, w, ch) = "HWC", shape
+        sy, sx, sc = strides
+    else:
+        raise ValueError("device image: a shape of %s does not fit layout %r" % (shape, layout))
+    d = DeviceImage()
+    d.ptr = int(iface["data"][0]) or None
+    d.width, d.height, d.channels, d.dtype = w, h, ch, dtype
+    d.stride_y, d.stride_x, d.stride_c = sy, sx, sc
+    chan = (0, 1, 2) if chan is None else tuple(int(v) for v in chan)
+    if len(chan) != 3:
+        raise ValueError("device image: chan has three entries")
+    d.chan[0], d.chan[1], d.chan[2] = chan
+    d.scale = float(scale) if scale is not None else {U8: 1.0, U16: 1.0 / 257.0}.get(dtype, 255.0)
+    if stream is None:
+        if type(obj).__module__.split(".")[0] == "torch":
+            import torch
+            stream = torch.cuda.current_stream(obj.device).cuda_stream
+        else:
+            stream = iface.get("stream")
+            stream = 0 if stream in (None, 1) else int(stream)         # (the interface's 1 is the legacy default stream)
+    elif hasattr(stream, "cuda_stream"):
+        stream = stream.cuda_stream
+    d.stream = int(stream) or None
+    d._keep, d._layout, d._shape = obj, layout, shape
+    return d
+
+
+def device_image_check(d):
+    """l3d_device_image_check (no device): (status, message) for a descriptor's fields"""
+    msg = C.create_string_buffer(256)
+    rc = load_library().l3d_device_image_check(C.byref(d), msg, C.c_size_t(256))
+    return int(rc), msg.value.decode()
+
+
+def device_image_extent(d):
+    """l3d_device_image_extent (no device): (status, lo, hi) -- the lowest and one past the highest byte offset from ptr the image addresses"""
+    lo, hi = C.c_longlong(0), C.c_longlong(0)
+    rc = load_library().l3d_device_image_extent(C.byref(d), C.byref(lo), C.byref(hi))
+    return int(rc), int(lo.value), int(hi.value)
+
+
+def detect_device_entries(images, new_sizes=None, min_lengths=None, max_segments=3000, cameras=None):
+    """The l3d_detect_device_entry array of Context.detect_segments_batch for a list of device objects, and what keeps its pointers alive"""
+    images = [device_image(im) for im in images]
+    n = len(images)
+    new_sizes, min_lengths, cameras = _per_image(new_sizes, n, "new_sizes"), _per_image(min_lengths, n, "min_lengths"), _per_image(cameras, n, "cameras")
+    caps = [int(max_segments)] * n if np.isscalar(max_segments) else [int(v) for v in _per_image(max_segments, n, "max_segments")]
+    entries, keep = (DetectDeviceEntry * max(1, n))(), list(images)
+    for i, im in enumerate(images):
+        e = entries[i]
+        e.image = im
+        w, h = im.width, im.height
+        e.new_width, e.new_height = (w, h) if new_sizes[i] is None else (int(new_sizes[i][0]), int(new_sizes[i][1]))
+        e.min_length = float(np.float32(0.005) * np.sqrt(np.float32(h * h + w * w))) if min_lengths[i] is None else float(min_lengths[i])
+        e.max_segments = caps[i]
+        if cameras[i] is not None:
+            if len(cameras[i]) != 6:
+                raise ValueError("camera must be (fx, fy, cx, cy, k1, k2)")
+            cam = (C.c_double * 6)(*[float(v) for v in cameras[i]])
+            keep.append(cam)
+            e.camera = C.addressof(cam)
+    return entries, keep
+
+
+def device_output_like(d, device_index=0):
+    """A zero-filled torch uint8 tensor of the shape the descriptor `d` was made from (an H x W[x 3] one for a hand-made descriptor) on its
+    device, and its descriptor: same layout and chan, on the same stream -- where the ..._device output calls write"""
+    import torch
+    src = getattr(d, "_keep", None)
+    shape = getattr(d, "_shape", None) or ((d.height, d.width) if d.channels == 1 else (d.height, d.width, 3))
+    layout = getattr(d, "_layout", None)
+    dev = src.device if src is not None and type(src).__module__.split(".")[0] == "torch" else "cuda:%d" % device_index
+    out = torch.zeros(shape, dtype=torch.uint8, device=dev)
+    o = device_image(out, layout=layout, chan=tuple(d.chan) if len(shape) == 3 else None, scale=1.0, stream=d.stream or 0)
+    return out, o
+
+
 class VerifyPath(C.Structure):
     """l3d_test_verify_path (include/line3d_amd.h)"""
     _fields_ = [("path", C.c_int32), ("gb", C.c_int32), ("split_unit", C.c_int32), ("mmax", C.c_int32), ("wide_max", C.c_int32),
@@ -224,6 +376,7 @@ class Context:
         if rc != 0:
             raise L3DError("l3d_ctx_create failed (code %d): no usable MI355X / HIP device -- this package has no CPU fallback" % rc)
         self.h = h
+        self.device = int(device)
         self._keep = []
 
     def close(self):
@@ -303,9 +456,17 @@ class Context:
     # -- line segment detection (l3d_detect.hip) --------------------------------------------------
     def undistort(self, img, K, k1, k2):
         """l3d_undistort_image: uint8 image H x W or H x W x 3 -> the undistorted image, same shape (initUndistortRectifyMap + remap of the drivers,
-        the formulas of include/line3d_amd.h).  K: 3 x 3, its fx, fy, cx, cy are used; k1, k2: OpenCV-convention radial coefficients."""
-        pix, w, h, ch, stride = image_arguments(img)
+        the formulas of include/line3d_amd.h).  K: 3 x 3, its fx, fy, cx, cy are used; k1, k2: OpenCV-convention radial coefficients.
+        A device object (device_image) stays on the device (l3d_undistort_image_device): the result is a torch uint8 tensor of the input's
+        shape on its device."""
         K = np.asarray(K, dtype=np.float64).reshape(3, 3)
+        if is_device_object(img):
+            d = device_image(img)
+            out, o = device_output_like(d, getattr(self, "device", 0))
+            self._chk(self.lib.l3d_undistort_image_device(self.h, C.byref(d), C.c_double(K[0, 0]), C.c_double(K[1, 1]), C.c_double(K[0, 2]), C.c_double(K[1, 2]),
+                                                          C.c_double(float(k1)), C.c_double(float(k2)), C.byref(o)))
+            return out
+        pix, w, h, ch, stride = image_arguments(img)
         out = np.zeros(np.asarray(img).shape, np.uint8)
         self._chk(self.lib.l3d_undistort_image(self.h, pix, C.c_int(w), C.c_int(h), C.c_int(ch), C.c_size_t(stride), C.c_double(K[0, 0]), C.c_double(K[1, 1]),
                                                C.c_double(K[0, 2]), C.c_double(K[1, 2]), C.c_double(float(k1)), C.c_double(float(k2)), _p(out),
@@ -316,7 +477,26 @@ class Context:
         """l3d_detect_segments: uint8 image H x W or H x W x 3 (contiguous pixels, rows contiguous or strided) -> (n, 4) float32 segments
         (x1, y1, x2, y2) in pixels of `img`, longest first.  new_size = (width, height) the detector works at (None: the image's own);
         min_length None: the reference's 0.005 x the image diagonal.  camera = (fx, fy, cx, cy, k1, k2): the image is undistorted on the device
-        first (l3d_detect_segments_distorted) and the segments are in pixels of the undistorted image."""
+        first (l3d_detect_segments_distorted) and the segments are in pixels of the undistorted image.
+        A device object (a torch device tensor, anything with __cuda_array_interface__, a device_image descriptor) is read where it lies
+        (l3d_detect_segments_device): the segments are those of the host call on the converted pixels."""
+        if is_device_object(img):
+            d = device_image(img)
+            w, h = d.width, d.height
+            nw, nh = (w, h) if new_size is None else (int(new_size[0]), int(new_size[1]))
+            if min_length is None:
+                min_length = float(np.float32(0.005) * np.sqrt(np.float32(h * h + w * w)))
+            cam = None
+            if camera is not None:
+                if len(camera) != 6:
+                    raise ValueError("camera must be (fx, fy, cx, cy, k1, k2)")
+                cam = (C.c_double * 6)(*[float(v) for v in camera])
+            out, n = C.POINTER(C.c_float)(), C.c_int(0)
+            self._chk(self.lib.l3d_detect_segments_device(self.h, C.byref(d), C.c_int(nw), C.c_int(nh), C.c_float(min_length), C.c_int(int(max_segments)), cam,
+                                                          C.byref(out), C.byref(n)))
+            segs = np.ctypeslib.as_array(out, (n.value, 4)).copy() if n.value else np.zeros((0, 4), np.float32)
+            self.lib.l3d_free(out)
+            return segs
         pix, w, h, ch, stride = image_arguments(img)
         nw, nh = (w, h) if new_size is None else (int(new_size[0]), int(new_size[1]))
         if min_length is None:
@@ -336,11 +516,18 @@ class Context:
         return segs
 
     # -- baseline JPEG input (l3d_jpeg.cpp, l3d_jpeg_device.hip) ------------------------------------
-    def decode_jpeg(self, data):
+    def decode_jpeg(self, data, device=False):
         """l3d_decode_jpeg: the bytes of a baseline JPEG file -> uint8 H x W (grey) or H x W x 3 (B, G, R, as cv::imread gives them),
-        byte-identical to libjpeg's default decoder."""
+        byte-identical to libjpeg's default decoder.  device=True: the same pixels as a torch uint8 tensor on the context's device
+        (l3d_decode_jpeg_device), readable from any stream when the call returns."""
         w, h, ch = jpeg_info(data)
         ptr, n = _bytes_arguments(data)
+        if device:
+            import torch
+            out = torch.zeros((h, w) if ch == 1 else (h, w, ch), dtype=torch.uint8, device="cuda:%d" % getattr(self, "device", 0))
+            o = device_image(out)
+            self._chk(self.lib.l3d_decode_jpeg_device(self.h, ptr, n, C.byref(o)))
+            return out
         out = np.zeros((h, w) if ch == 1 else (h, w, ch), np.uint8)
         self._chk(self.lib.l3d_decode_jpeg(self.h, ptr, n, _p(out), C.c_size_t(w * ch)))
         return out
@@ -370,12 +557,16 @@ class Context:
         detect_segments_jpeg takes them) -> a list of (n, 4) float32 arrays, each byte for byte what the single call gives for that image.
         new_sizes, min_lengths, max_segments, cameras: None, one value for all (max_segments), or a list with one entry (possibly None) per image,
         with the single calls' meanings and defaults.  An entry the single call would refuse raises L3DError (its .code the first such entry's
-        status, .statuses all of them); return_status=True: no raise, the result is (segments, statuses)."""
+        status, .statuses all of them); return_status=True: no raise, the result is (segments, statuses).
+        A list of device objects (as detect_segments takes them) goes through l3d_detect_segments_device_batch; a list that mixes them with
+        host images or files raises ValueError before any call."""
         images = list(images)
-        entries, keep = detect_entries(images, new_sizes, min_lengths, max_segments, cameras)
+        on_device = all_device_objects(images, "detect_segments_batch")
+        entries, keep = (detect_device_entries if on_device else detect_entries)(images, new_sizes, min_lengths, max_segments, cameras)
         n = len(images)
         out, offsets, status = C.POINTER(C.c_float)(), (C.c_int * (n + 1))(), (C.c_int * max(1, n))()
-        rc = self.lib.l3d_detect_segments_batch(self.h, entries, C.c_int(n), C.byref(out), offsets, status)
+        call = self.lib.l3d_detect_segments_device_batch if on_device else self.lib.l3d_detect_segments_batch
+        rc = call(self.h, entries, C.c_int(n), C.byref(out), offsets, status)
         statuses = [int(status[i]) for i in range(n)]
         segs = []
         if rc == 0:
@@ -392,6 +583,27 @@ class Context:
             e.code, e.statuses = bad[0], statuses
             raise e
         return segs
+
+    # -- images in device memory (l3d_device_image.hip), the pieces on their own (tests)
+    def test_device_image_pointer(self, d):
+        """l3d_test_device_image_pointer: what the library establishes about a descriptor's memory before a launch -> (status, message); launches nothing"""
+        rc = int(self.lib.l3d_test_device_image_pointer(self.h, C.byref(d)))
+        return rc, (self.lib.l3d_last_error(self.h).decode() if rc else "")
+
+    def test_device_ingest(self, descriptors):
+        """l3d_test_device_ingest: check, stream wait and ONE k_det_ingest launch for a chunk of same-size descriptors -> uint8 (n, H, W, 1 or 3)"""
+        n = len(descriptors)
+        arr = (DeviceImage * n)(*descriptors)
+        ch = 1 if descriptors[0].channels == 1 else 3
+        out = np.zeros((n, descriptors[0].height, descriptors[0].width, ch), np.uint8)
+        self._chk(self.lib.l3d_test_device_ingest(self.h, arr, C.c_int(n), _p(out)))
+        return out
+
+    def decode_jpeg_into(self, data, out):
+        """l3d_decode_jpeg_device into the memory the descriptor (or device object) `out` describes"""
+        ptr, n = _bytes_arguments(data)
+        o = device_image(out)
+        self._chk(self.lib.l3d_decode_jpeg_device(self.h, ptr, n, C.byref(o)))
 
     # -- the detector's stages on their own (tests): the same kernels and launch shapes as detect_segments
     def test_detect_pixel_stage(self, img, new_size=None):

@@ -145,11 +145,17 @@ struct DetectBufs {
     // decoder wrote them into the pinned `jstage`, and the uint8 component planes over whole MCUs
     DevBuf jcoef, jplanes;
     PinBuf jstage;
+    // images in device memory (l3d_device_image.hip): the chunk's descriptor table beside `prm`, and the event that orders the context's stream behind
+    // the stream an image was produced on (one per context, created on first use)
+    DevBuf ingest;
+    std::vector<unsigned char> ingest_host;     // the table's host copy: it outlives the asynchronous upload (every call ends in a synchronise)
+    hipEvent_t dev_event = nullptr;
     int tab_w = 0, tab_h = 0;       // the image size the Gaussian sampler's tables in `ktab` were made for
     void release()
     {
         for (DevBuf* x : all()) x->release();
         jstage.release();
+        if (dev_event) { (void)hipEventDestroy(dev_event); dev_event = nullptr; }
         tab_w = tab_h = 0;
     }
     size_t held()                   // device bytes these buffers hold (the chunk rule counts them as available)
@@ -160,7 +166,7 @@ struct DetectBufs {
     }
     std::vector<DevBuf*> all()
     {
-        return { &pixels, &undist, &grey, &aux, &img, &mod, &ang, &bucket, &active, &parent, &size, &count, &keys, &keys2, &vals, &vals2, &flag, &pos, &start, &tmp, &cand, &ckeys, &ckeys2, &cvals, &cvals2, &cimg, &cimg2, &prm, &out, &ktab, &scal, &jcoef, &jplanes };
+        return { &pixels, &undist, &grey, &aux, &img, &mod, &ang, &bucket, &active, &parent, &size, &count, &keys, &keys2, &vals, &vals2, &flag, &pos, &start, &tmp, &cand, &ckeys, &ckeys2, &cvals, &cvals2, &cimg, &cimg2, &prm, &out, &ktab, &scal, &jcoef, &jplanes, &ingest };
     }
 };
 

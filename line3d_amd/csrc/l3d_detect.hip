@@ -794,6 +794,7 @@ struct DetItem {
     const unsigned char* pixels = nullptr;      // host pixels, or with null the file `jpeg` staged at jpeg->stage_at
     size_t stride = 0;
     const JpegStaged* jpeg = nullptr;
+    const l3d_device_image* dev = nullptr;      // an image in device memory (pixels and jpeg null), checked by device_image_pointer
     DetImgParam prm;
     std::vector<float>* out = nullptr;
 };
@@ -805,20 +806,26 @@ int detect_chunk(l3d_ctx* c, const DetPlan& p, const DetItem* items)
     hipStream_t st = c->stream;
     DetectBufs& d = c->det;
     const int B = p.B, cand_cap = p.cand_cap;
-    bool undist = false, jpeg = false;
+    bool undist = false, jpeg = false, dev = false;
     size_t out_slots = 0;
     std::vector<DetImgParam> prm((size_t)B);
     for (int b = 0; b < B; ++b) {
         prm[b] = items[b].prm;
         undist = undist || prm[b].cam_on;
-        jpeg = jpeg || !items[b].pixels;
+        jpeg = jpeg || (!items[b].pixels && !items[b].dev);
+        dev = dev || items[b].dev;
         out_slots += (size_t)std::min(prm[b].max_segments, cand_cap);
     }
     if (int rc = det_reserve(c, p, out_slots, undist)) return rc;
     if (jpeg) {
         std::vector<const JpegStaged*> files((size_t)B, nullptr);
-        for (int b = 0; b < B; ++b) if (!items[b].pixels) files[b] = items[b].jpeg;
+        for (int b = 0; b < B; ++b) if (!items[b].pixels && !items[b].dev) files[b] = items[b].jpeg;
         if (int rc = jpeg_staged_to_pixels(c, files.data(), B)) return rc;
+    }
+    if (dev) {              // the chunk's device images: one launch gathers them into their slots
+        std::vector<const l3d_device_image*> images((size_t)B, nullptr);
+        for (int b = 0; b < B; ++b) images[b] = items[b].dev;
+        if (int rc = device_ingest(c, images.data(), B, p.w, p.h, p.ch, d.pixels.as<unsigned char>())) return rc;
     }
     for (int b = 0; b < B; ++b) if (items[b].pixels) HIPCHK(c, det_upload(c, p, b, items[b].pixels, items[b].stride));
     // (from pageable memory on purpose: a few dozen bytes go faster through the runtime's staging than as a DMA from pinned memory -- measured, 0.03 ms per call)
@@ -910,13 +917,18 @@ int detect_segments_batch(l3d_ctx* c, const DetEntry* e, int n, std::vector<std:
         const DetEntry& en = e[i];
         int w = en.width, h = en.height, ch = en.channels;
         size_t stride = en.row_stride;
+        const bool dev = !en.pixels && !en.jpeg && en.dev;
+        if (dev) {
+            if ((status[i] = device_image_check(*en.dev, message[i])) != L3D_OK) continue;
+            w = en.dev->width; h = en.dev->height; ch = device_image_det_channels(en.dev->channels); stride = (size_t)w * ch;
+        }
         if (!en.pixels && en.jpeg) {
             if ((status[i] = jpeg_parse(en.jpeg, en.jpeg_bytes, frames[i], message[i])) != L3D_OK) continue;
             w = frames[i].width; h = frames[i].height; ch = frames[i].ncomp; stride = (size_t)w * ch;
             k.file.bytes = en.jpeg; k.file.n = en.jpeg_bytes; k.file.f = &frames[i];
         }
         if (en.max_segments < 0) { status[i] = L3D_ERR_INVALID; message[i] = "detect_segments: negative max_segments"; continue; }
-        if ((status[i] = plan_image(k.plan, en.pixels != nullptr || en.jpeg != nullptr, w, h, ch, stride, en.new_width, en.new_height, message[i])) != L3D_OK) continue;
+        if ((status[i] = plan_image(k.plan, en.pixels != nullptr || en.jpeg != nullptr || dev, w, h, ch, stride, en.new_width, en.new_height, message[i])) != L3D_OK) continue;
         bool undist = false;
         if (en.cam) { if ((status[i] = check_camera(*en.cam, w, h, &undist, message[i])) != L3D_OK) continue; }
         k.prm.cam = undist ? *en.cam : DetCamera{ 1.0, 1.0, 0.0, 0.0, 0.0, 0.0 };
@@ -952,6 +964,10 @@ int detect_segments_batch(l3d_ctx* c, const DetEntry* e, int n, std::vector<std:
                 Work& k = work[i];
                 if (k.file.f && k.file.status != L3D_OK) { status[i] = k.file.status; message[i] = k.file.err; continue; }
                 DetItem it;
+                if (!e[i].pixels && !k.file.f && e[i].dev) {          // a device image: its memory is looked at here, before the chunk's launch; refused, it leaves the chunk
+                    if ((status[i] = device_image_pointer(c, *e[i].dev, message[i])) != L3D_OK) continue;
+                    it.dev = e[i].dev;
+                }
                 it.pixels = k.file.f ? nullptr : e[i].pixels; it.stride = e[i].row_stride; it.jpeg = k.file.f ? &k.file : nullptr; it.prm = k.prm; it.out = &out[i];
                 items.push_back(it);
                 entry.push_back(i);
@@ -1007,6 +1023,16 @@ int detect_segments_jpeg(l3d_ctx* c, const unsigned char* bytes, size_t n, int n
     return detect_one(c, en, out);
 }
 
+int detect_segments_device(l3d_ctx* c, const l3d_device_image& image, int nw, int nh, float min_length, int max_segments, std::vector<float>& out, const DetCamera* cam)
+{
+    out.clear();
+    if (!c) return L3D_ERR_INVALID;
+    DetEntry en;
+    en.dev = &image;
+    en.new_width = nw; en.new_height = nh; en.min_length = min_length; en.max_segments = max_segments; en.cam = cam;
+    return detect_one(c, en, out);
+}
+
 // host in, host out: upload, k_det_undistort, download (the detector's two image buffers)
 int undistort_image(l3d_ctx* c, const unsigned char* pixels, int w, int h, int ch, size_t stride, const DetCamera& cam, unsigned char* out, size_t out_stride)
 {
@@ -1033,7 +1059,41 @@ int undistort_image(l3d_ctx* c, const unsigned char* pixels, int w, int h, int c
     return L3D_OK;
 }
 
+// device in, device out (which may be the same memory): ingest, k_det_undistort, egress -- the ingest is complete before the egress starts
+int undistort_image_device(l3d_ctx* c, const l3d_device_image& in, const DetCamera& cam, const l3d_device_image& out)
+{
+    std::string err;
+    if (int rc = device_image_check(in, err)) return fail(c, rc, err);
+    if (int rc = device_image_check(out, err)) return fail(c, rc, err);
+    const int w = in.width, h = in.height, ch = device_image_det_channels(in.channels);
+    if (out.width != w || out.height != h || device_image_det_channels(out.channels) != ch)
+        return fail(c, L3D_ERR_INVALID, "undistort: the output's size and channels must be the input's");
+    if ((long long)w * h * ch > (1ll << 31)) return fail(c, L3D_ERR_UNSUPPORTED, "undistort: image too large");
+    bool active = false;
+    if (int rc = check_camera(cam, w, h, &active, err)) return fail(c, rc, err);
+    if (int rc = device_image_pointer(c, in, err)) return fail(c, rc, err);
+    if (int rc = device_image_pointer(c, out, err)) return fail(c, rc, err);
+    HIPCHK(c, hipSetDevice(c->device));
+    DetectBufs& d = c->det;
+    const size_t bytes = (size_t)w * ch * h;
+    HIPCHK(c, d.pixels.reserve(bytes));
+    if (active) HIPCHK(c, d.undist.reserve(bytes));
+    const l3d_device_image* one[1] = { &in };
+    if (int rc = device_ingest(c, one, 1, w, h, ch, d.pixels.as<unsigned char>())) return rc;
+    if (active) launch_undistort(c, w, h, ch, 1, cam, nullptr);
+    if (int rc = device_egress(c, active ? d.undist.as<unsigned char>() : d.pixels.as<unsigned char>(), out)) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return L3D_OK;
+}
+
 }  // namespace l3d
+
+int l3d_undistort_image_device(l3d_ctx* c, const l3d_device_image* in, double fx, double fy, double cx, double cy, double k1, double k2, const l3d_device_image* out)
+{
+    if (!c) return L3D_ERR_INVALID;
+    if (!in || !out) return l3d::fail(c, L3D_ERR_INVALID, "undistort: null argument");
+    return l3d::undistort_image_device(c, *in, l3d::DetCamera{ fx, fy, cx, cy, k1, k2 }, *out);
+}
 
 int l3d_undistort_image(l3d_ctx* c, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, double fx, double fy, double cx, double cy,
                         double k1, double k2, unsigned char* out, size_t out_row_stride)
@@ -1089,6 +1149,8 @@ int l3d_detect_segments_jpeg(l3d_ctx* c, const unsigned char* bytes, size_t n, i
     return rc != L3D_OK ? rc : segments_to_c(c, out, segments, n_segments);
 }
 
+static int batch_to_c(l3d_ctx* c, const std::vector<l3d::DetEntry>& entries, float** segments, int* offsets, int* status);
+
 int l3d_detect_segments_batch(l3d_ctx* c, const l3d_detect_entry* e, int n, float** segments, int* offsets, int* status)
 {
     if (!c || !segments || !offsets || !status || n < 0 || (n > 0 && !e)) return L3D_ERR_INVALID;
@@ -1102,6 +1164,42 @@ int l3d_detect_segments_batch(l3d_ctx* c, const l3d_detect_entry* e, int n, floa
         d.new_width = e[i].new_width; d.new_height = e[i].new_height; d.min_length = e[i].min_length; d.max_segments = e[i].max_segments;
         if (const double* k = e[i].camera) { cams[i] = l3d::DetCamera{ k[0], k[1], k[2], k[3], k[4], k[5] }; d.cam = &cams[i]; }
     }
+    return batch_to_c(c, entries, segments, offsets, status);
+}
+
+int l3d_detect_segments_device(l3d_ctx* c, const l3d_device_image* image, int new_width, int new_height, float min_length, int max_segments, const double* camera,
+                               float** segments, int* n)
+{
+    if (!c || !segments || !n) return L3D_ERR_INVALID;
+    *segments = nullptr;
+    *n = 0;
+    if (!image) return l3d::fail(c, L3D_ERR_INVALID, "detect_segments: null argument");
+    l3d::DetCamera cam{ 1.0, 1.0, 0.0, 0.0, 0.0, 0.0 };
+    if (camera) cam = l3d::DetCamera{ camera[0], camera[1], camera[2], camera[3], camera[4], camera[5] };
+    std::vector<float> out;
+    const int rc = l3d::detect_segments_device(c, *image, new_width, new_height, min_length, max_segments, out, camera ? &cam : nullptr);
+    return rc != L3D_OK ? rc : segments_to_c(c, out, segments, n);
+}
+
+int l3d_detect_segments_device_batch(l3d_ctx* c, const l3d_detect_device_entry* e, int n, float** segments, int* offsets, int* status)
+{
+    if (!c || !segments || !offsets || !status || n < 0 || (n > 0 && !e)) return L3D_ERR_INVALID;
+    *segments = nullptr;
+    std::vector<l3d::DetEntry> entries((size_t)n);
+    std::vector<l3d::DetCamera> cams((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        l3d::DetEntry& d = entries[i];
+        d.dev = &e[i].image;
+        d.new_width = e[i].new_width; d.new_height = e[i].new_height; d.min_length = e[i].min_length; d.max_segments = e[i].max_segments;
+        if (const double* k = e[i].camera) { cams[i] = l3d::DetCamera{ k[0], k[1], k[2], k[3], k[4], k[5] }; d.cam = &cams[i]; }
+    }
+    return batch_to_c(c, entries, segments, offsets, status);
+}
+
+// the batch detector's outcome as the C ABI hands it out: the segments of all entries one after the other, one line per failed entry
+static int batch_to_c(l3d_ctx* c, const std::vector<l3d::DetEntry>& entries, float** segments, int* offsets, int* status)
+{
+    const int n = (int)entries.size();
     std::vector<std::vector<float>> out;
     std::vector<int> st;
     std::vector<std::string> msg;

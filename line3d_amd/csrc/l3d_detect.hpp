@@ -7,8 +7,23 @@
 #include <vector>
 
 struct l3d_ctx;
+struct l3d_device_image;
 
 namespace l3d {
+
+// ---- images in device memory (l3d_device_image.hip; the descriptor and its conversion rule: include/line3d_amd.h)
+// the detector's channel count for a source: 1, or 3 for 3 and 4 channels
+inline int device_image_det_channels(int source_channels) { return source_channels == 1 ? 1 : 3; }
+// the fields (no device): L3D_OK, or the code with the cause in err
+int device_image_check(const l3d_device_image& im, std::string& err);
+// what comes before the first launch that touches im.ptr: device memory of the context's device, the extent inside its allocation.  Launches nothing
+int device_image_pointer(l3d_ctx* c, const l3d_device_image& im, std::string& err);
+// B images (checked by the two above, all w x h with ch detector channels; a null entry's slot is left alone) into B tight slots at dst (device):
+// per image the context's stream waits for the image's stream, then ONE launch of k_det_ingest.  Returns with the work enqueued
+int device_ingest(l3d_ctx* c, const l3d_device_image* const* images, int B, int w, int h, int ch, unsigned char* dst);
+// the inverse for one image: tight 8-bit pixels at src (device) into the memory `out` describes (checked as above), after the context's stream
+// waits for out's stream.  Returns with the work enqueued
+int device_egress(l3d_ctx* c, const unsigned char* src, const l3d_device_image& out);
 
 // the camera of an undistortion (include/line3d_amd.h): focal lengths, principal point, OpenCV-convention radial coefficients
 struct DetCamera { double fx, fy, cx, cy, k1, k2; };
@@ -29,11 +44,18 @@ struct DetEntry {
     float min_length = 0.0f;
     int max_segments = 0;
     const DetCamera* cam = nullptr;
+    const l3d_device_image* dev = nullptr;      // a third source (pixels and jpeg null): an image in device memory (l3d_device_image.hip)
 };
 // out[i]: the segments detect_segments / detect_segments_jpeg gives for entry i alone, byte for byte.  Entries with the same sizes run together, in
 // chunks (option det_batch_images, the index widths, half of the free HBM).  status[i] / message[i]: what the single call would have returned and
 // said -- a refused entry fails alone.  The return value is L3D_OK, or a device failure's code (entries not finished by then carry it)
 int detect_segments_batch(l3d_ctx* c, const DetEntry* e, int n, std::vector<std::vector<float>>& out, std::vector<int>& status, std::vector<std::string>& message);
+
+// detect_segments on an image in device memory (checked, ingested by k_det_ingest); an image below 8x8 is refused as detect_segments refuses it
+int detect_segments_device(l3d_ctx* c, const l3d_device_image& image, int new_width, int new_height, float min_length, int max_segments, std::vector<float>& out,
+                           const DetCamera* cam = nullptr);
+// device in, device out (may be the same memory), same size and detector channels; coefficients at or below 1e-12: ingest and egress only
+int undistort_image_device(l3d_ctx* c, const l3d_device_image& in, const DetCamera& cam, const l3d_device_image& out);
 
 // host in, host out, same size and channels; coefficients at or below 1e-12: the pixels are copied
 int undistort_image(l3d_ctx* c, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, const DetCamera& cam, unsigned char* out,

@@ -670,19 +670,22 @@ int l3d_line3d_reset(l3d_line3d* h)
 //   3. an image whose cache does not stand in for it: the detector, on rank 0's device.  Nothing found: no view, L3D_OK, a stale cache removed
 //   4. per rank (add_entry): the guards, then the decision's outcome -- the view from the cache file, or the stale file removed and the view from
 //      the segments, its cache noted for prepare() to write -- then the links
+// An image in device memory (AddKind::Device) is an image like the other two: step 1 checks its descriptor's fields, step 3 is the only place where its
+// memory is looked at (pointer and extent check, stream wait, k_det_ingest) -- a cache that stands in for it leaves the memory untouched.
 // The guards (4) come AFTER the detector (3) for an image: a second image of an id in use in which nothing is detected is L3D_OK and adds nothing.
 // That is the behaviour the forms had one by one (tests/golden/add_table.json records it); moving the cheap guards to the front changes it.
 namespace l3dh {
-enum class AddKind { Segments, Cached, Pixels, Jpeg };
+enum class AddKind { Segments, Cached, Pixels, Jpeg, Device };
 // an l3d_image_entry, or in place of its image the caller's segments or an opened segment cache
 struct AddRequest {
     AddKind kind = AddKind::Segments;
     l3d_image_entry e{};                            // image_id, the image, width x height, K, R, t, dist, the links
     const float* segs = nullptr; int n = 0;         // Segments
     const l3d_segment_cache* cache = nullptr;       // Cached
+    const l3d_device_image* dev = nullptr;          // Device: the image in device memory (e carries its size and the detector's channel count)
     bool cache_rules = false;                       // the form has a data directory: every one but add_image, add_image_fixed_sim, add_image_cached
     bool dist_required = false;                     // the _distorted forms: a null dist is refused (elsewhere it means no distortion)
-    bool image() const { return kind == AddKind::Pixels || kind == AddKind::Jpeg; }
+    bool image() const { return kind == AddKind::Pixels || kind == AddKind::Jpeg || kind == AddKind::Device; }
 };
 enum class Cache { None, Load, Stale, Write };      // no cache rules or nothing to do | read the file | remove the file | note the file for prepare()
 // what steps 1 and 2 found out about a request
@@ -721,6 +724,15 @@ static AddRequest jpeg_request(uint32_t id, const unsigned char* bytes, size_t n
 {
     AddRequest rq = add_request(AddKind::Jpeg, id, 0, 0, K, R, t, link_ids, sims, n_links);
     rq.e.jpeg = bytes; rq.e.jpeg_bytes = n; rq.e.dist = dist;
+    return rq;
+}
+// an l3d_device_entry: the image stays where it is, the request carries its size
+static AddRequest device_request(const l3d_device_entry& d)
+{
+    AddRequest rq = add_request(AddKind::Device, d.image_id, (unsigned)std::max(0, d.image.width), (unsigned)std::max(0, d.image.height), d.K, d.R, d.t, d.link_ids, d.sims, d.n_links);
+    rq.e.channels = d.image.channels == 1 ? 1 : 3;
+    rq.e.dist = d.dist;
+    rq.dev = &d.image;
     return rq;
 }
 // single: l3d_line3d_add_image_entry, where an entry without an image is still the image its fields state -- any of width, height, channels,
@@ -788,6 +800,11 @@ static int add_plan(L* h, const AddRequest& rq, const char* data_directory, int 
         if (!e.jpeg) return h->fail(L3D_ERR_INVALID, "jpeg: null argument");
         const int rc = l3d_jpeg_info(e.jpeg, e.jpeg_bytes, &width, &height, &p.channels);
         if (rc != L3D_OK) return h->fail(rc, l3d_jpeg_last_error());
+    }
+    if (rq.kind == AddKind::Device) {           // the descriptor's fields; its memory is looked at only where the detector runs
+        char msg[160];
+        const int rc = l3d_device_image_check(rq.dev, msg, sizeof(msg));
+        if (rc != L3D_OK) return h->fail(rc, msg);
     }
     if (rq.image()) {
         const int with = (e.dist || rq.dist_required) ? camera_for_add(h, e.K, e.dist, p.cam) : 0;
@@ -874,7 +891,9 @@ static int add_one(L* h, const AddRequest& rq, const char* data_directory = null
     std::vector<float> segs;
     const l3d::DetCamera* cam = p.undistort ? &p.cam : nullptr;
     // a JPEG file is decoded on the device into the detector -- only here, behind the cache decision
+    // a device image's memory is checked and gathered only here as well
     const int rc = rq.kind == AddKind::Jpeg ? l3d::detect_segments_jpeg(ctx, e.jpeg, e.jpeg_bytes, (int)p.new_w, (int)p.new_h, p.min_length, 3000, segs, cam)
+                 : rq.kind == AddKind::Device ? l3d::detect_segments_device(ctx, *rq.dev, (int)p.new_w, (int)p.new_h, p.min_length, 3000, segs, cam)
                                             : l3d::detect_segments(ctx, e.pixels, e.width, e.height, e.channels, e.row_stride, (int)p.new_w, (int)p.new_h, p.min_length, 3000, segs, cam);
     if (rc != L3D_OK) return h->fail(rc, l3d_last_error(ctx));
     return add_entry(h, rq, p, &segs);
@@ -991,24 +1010,27 @@ int l3d_line3d_add_image_entry(l3d_line3d* h, const l3d_image_entry* e, const ch
 
 // Many images in one call: the route above per entry, in entry order, with the detector run once (batched, l3d_detect.hip) over all entries that
 // need it.  An entry fails alone, with its single call's code and message
-int l3d_line3d_add_images(l3d_line3d* h, const l3d_image_entry* e, int n, const char* data_directory, int max_img_width, int load_and_store, int* status)
+namespace l3dh {
+// one request of a batch: what filling it said (rc, msg), the request, then its plan and its place among the detector's entries
+struct AddItem { int rc = L3D_OK; std::string msg; AddRequest rq; AddPlan p; int detect_at = -1; };
+// the batch body of every ..._add_images form: steps 1 and 2 per request, one run of the batch detector, steps 3 to 5 in request order
+static int add_batch(L* h, std::vector<AddItem>& items, const char* data_directory, int max_img_width, int load_and_store, int* status)
 {
-    if (!h) return L3D_ERR_INVALID;
-    if (n < 0 || (n > 0 && !e)) return h->fail(L3D_ERR_INVALID, "add_images: null argument");
-    struct Item { int rc = L3D_OK; std::string msg; AddRequest rq; AddPlan p; int detect_at = -1; };
-    std::vector<Item> items((size_t)n);
+    const int n = (int)items.size();
     std::vector<l3d::DetEntry> todo;
     todo.reserve((size_t)n);
     for (int i = 0; i < n; ++i) {
-        Item& it = items[i];
-        it.rc = entry_request(h, e[i], it.rq, false);
-        if (it.rc == L3D_OK) it.rc = add_plan(h, it.rq, data_directory, max_img_width, load_and_store, it.p);
+        AddItem& it = items[i];
+        const l3d_image_entry& e = it.rq.e;
+        if (it.rc != L3D_OK) continue;          // refused when it was filled: msg says why
+        it.rc = add_plan(h, it.rq, data_directory, max_img_width, load_and_store, it.p);
         if (it.rc != L3D_OK) { it.msg = h->err; continue; }
         if (!it.p.detect) continue;
         l3d::DetEntry d;
-        d.pixels = e[i].pixels; d.width = (int)it.p.width; d.height = (int)it.p.height; d.channels = it.p.channels;
-        d.row_stride = e[i].jpeg ? (size_t)it.p.width * it.p.channels : e[i].row_stride;
-        d.jpeg = e[i].jpeg; d.jpeg_bytes = e[i].jpeg_bytes;
+        d.pixels = e.pixels; d.width = (int)it.p.width; d.height = (int)it.p.height; d.channels = it.p.channels;
+        d.row_stride = e.jpeg ? (size_t)it.p.width * it.p.channels : e.row_stride;
+        d.jpeg = e.jpeg; d.jpeg_bytes = e.jpeg_bytes;
+        d.dev = it.rq.dev;
         d.new_width = (int)it.p.new_w; d.new_height = (int)it.p.new_h; d.min_length = it.p.min_length; d.max_segments = 3000;
         d.cam = it.p.undistort ? &it.p.cam : nullptr;           // (items does not grow: the address holds)
         it.detect_at = (int)todo.size();
@@ -1022,17 +1044,69 @@ int l3d_line3d_add_images(l3d_line3d* h, const l3d_image_entry* e, int n, const 
         rc_all = l3d::detect_segments_batch((h->node ? rank0(h) : h)->ctx, todo.data(), (int)todo.size(), segs, det_status, det_msg);   // (one status per entry, whatever it returns)
     std::string lines;
     for (int i = 0; i < n; ++i) {
-        Item& it = items[i];
+        AddItem& it = items[i];
         if (it.rc == L3D_OK && it.detect_at >= 0 && det_status[it.detect_at] != L3D_OK) { it.rc = det_status[it.detect_at]; it.msg = det_msg[it.detect_at]; }
         else if (it.rc == L3D_OK) {
             it.rc = add_entry(h, it.rq, it.p, it.detect_at >= 0 ? &segs[it.detect_at] : nullptr);
             if (it.rc != L3D_OK) it.msg = h->err;
         }
         if (status) status[i] = it.rc;
-        if (it.rc != L3D_OK) lines += (lines.empty() ? "image " : "\nimage ") + std::to_string(e[i].image_id) + ": " + it.msg;
+        if (it.rc != L3D_OK) lines += (lines.empty() ? "image " : "\nimage ") + std::to_string(it.rq.e.image_id) + ": " + it.msg;
     }
     h->err = lines;
     return rc_all;
+}
+}  // namespace l3dh
+
+int l3d_line3d_add_images(l3d_line3d* h, const l3d_image_entry* e, int n, const char* data_directory, int max_img_width, int load_and_store, int* status)
+{
+    if (!h) return L3D_ERR_INVALID;
+    if (n < 0 || (n > 0 && !e)) return h->fail(L3D_ERR_INVALID, "add_images: null argument");
+    std::vector<AddItem> items((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        items[i].rc = entry_request(h, e[i], items[i].rq, false);
+        if (items[i].rc != L3D_OK) { items[i].msg = h->err; items[i].rq.e.image_id = e[i].image_id; }
+    }
+    return add_batch(h, items, data_directory, max_img_width, load_and_store, status);
+}
+
+// ---- images in device memory: the entry with a descriptor where the others have pixels or a file
+int l3d_line3d_add_device_entry(l3d_line3d* h, const l3d_device_entry* e, const char* data_directory, int max_img_width, int load_and_store)
+{
+    if (!h) return L3D_ERR_INVALID;
+    if (!e) return h->fail(L3D_ERR_INVALID, "add_device_entry: null argument");
+    return add_one(h, device_request(*e), data_directory, max_img_width, load_and_store);
+}
+int l3d_line3d_add_device_images(l3d_line3d* h, const l3d_device_entry* e, int n, const char* data_directory, int max_img_width, int load_and_store, int* status)
+{
+    if (!h) return L3D_ERR_INVALID;
+    if (n < 0 || (n > 0 && !e)) return h->fail(L3D_ERR_INVALID, "add_device_images: null argument");
+    std::vector<AddItem> items((size_t)n);
+    for (int i = 0; i < n; ++i) items[i].rq = device_request(e[i]);
+    return add_batch(h, items, data_directory, max_img_width, load_and_store, status);
+}
+
+// l3d_decode_jpeg_device / l3d_undistort_image_device with the object's device (a node object: rank 0's) and, for the latter, the object's K rule
+int l3d_line3d_decode_jpeg_device(l3d_line3d* h, const unsigned char* bytes, size_t n, const l3d_device_image* out)
+{
+    if (!h) return L3D_ERR_INVALID;
+    L* owner = h->node ? rank0(h) : h;
+    if (!owner->ctx) return h->fail(L3D_ERR_INVALID, "no device context to decode with");
+    const int rc = l3d_decode_jpeg_device(owner->ctx, bytes, n, out);
+    return rc == L3D_OK ? rc : h->fail(rc, l3d_last_error(owner->ctx));
+}
+int l3d_line3d_undistort_image_device(l3d_line3d* h, const l3d_device_image* in, const double* K, double k1, double k2, const l3d_device_image* out)
+{
+    if (!h) return L3D_ERR_INVALID;
+    L* owner = h->node ? rank0(h) : h;
+    if (!owner->ctx) return h->fail(L3D_ERR_INVALID, "no device context to undistort with");
+    if (!in || !out) return h->fail(L3D_ERR_INVALID, "undistort: null argument");
+    const double dist[2] = { k1, k2 };
+    l3d::DetCamera cam{ 1.0, 1.0, 0.0, 0.0, 0.0, 0.0 };
+    const int with = camera_for_add(h, K, dist, cam);
+    if (with < 0) return -with;
+    const int rc = l3d::undistort_image_device(owner->ctx, *in, cam, *out);
+    return rc == L3D_OK ? rc : h->fail(rc, l3d_last_error(owner->ctx));
 }
 
 // l3d_decode_jpeg with the object's device (a node object: rank 0's)

@@ -59,6 +59,49 @@ def image_entries(entries):
     return arr, keep
 
 
+def device_entries(entries):
+    """The l3d_device_entry array of Line3D.add_images for entries whose img is a device object (capi.device_image), and what keeps its pointers
+    alive; refusals as image_entries"""
+    entries = list(entries)
+    arr, keep = (capi.DeviceEntry * max(1, len(entries)))(), []
+
+    def pointer(a):
+        keep.append(a)
+        return a.ctypes.data
+
+    for i, en in enumerate(entries):
+        e = arr[i]
+        unknown = set(en) - {"imageID", "img", "data", "K", "R", "t", "dist", "worldpointIDs", "viewSimilarity"}
+        if unknown:
+            raise ValueError("entry %d: unknown keys %s" % (i, sorted(unknown)))
+        if en.get("img") is None or en.get("data") is not None:
+            raise ValueError("entry %d needs img (an image in device memory) and no data" % i)
+        if (en.get("worldpointIDs") is None) == (en.get("viewSimilarity") is None):
+            raise ValueError("entry %d needs either worldpointIDs or viewSimilarity, not both" % i)
+        e.image_id = int(en["imageID"])
+        d = capi.device_image(en["img"])
+        e.image = d
+        keep.append(d)                  # (the descriptor keeps the object it was made from alive)
+        e.K, e.R, e.t = (pointer(np.ascontiguousarray(en[k], dtype=np.float64)) for k in ("K", "R", "t"))
+        if en.get("dist") is not None:
+            e.dist = pointer(np.ascontiguousarray(en["dist"], dtype=np.float64).reshape(2))
+        if en.get("viewSimilarity") is not None:
+            sim = en["viewSimilarity"]
+            ids = np.ascontiguousarray(sorted(sim), dtype=np.uint32)
+            e.sims = pointer(np.ascontiguousarray([sim[int(k)] for k in ids] + [0.0], dtype=np.float32))      # (never a null pointer: it says which kind of links)
+        else:
+            ids = np.ascontiguousarray(list(en["worldpointIDs"]), dtype=np.uint32)
+        if ids.ndim != 1:
+            raise ValueError("entry %d: link ids must be a flat list" % i)
+        e.link_ids, e.n_links = pointer(np.concatenate([ids, np.zeros(1, np.uint32)])), len(ids)
+    return arr, keep
+
+
+def _entries_on_device(entries, what):
+    """True when every entry's img is a device object, False when none is; a mixed list raises ValueError before any library call"""
+    return capi.all_device_objects([en.get("img") for en in entries], what)
+
+
 def _camera_and_links(K, R, t, links, fixed_sim):
     """The K, R, t and link arguments of the segment-taking calls, and the arrays behind them.  links: world point ids, or {view id: similarity}
     with fixed_sim"""
@@ -102,6 +145,7 @@ class Line3D:
             if rc != 0:
                 raise L3DError("l3d_line3d_create failed (code %d): no usable MI355X / HIP device -- no CPU fallback" % rc)
         self.h = h
+        self._device = int(devices[0]) if devices is not None and len(devices) else int(device or 0)      # where the detector runs (a node object: rank 0's)
         self._keep = []
         self.last_rc = 0          # status of the last add_image_pixels* / add_image_jpeg* (they return a bool, as the other adders do)
 
@@ -197,6 +241,11 @@ class Line3D:
     def _add_entry(self, en, maxImgWidth, loadAndStoreSegments):
         """one image entry (as add_images takes them) through l3d_line3d_add_image_entry: True when it was taken; the status stays in last_rc.
         What is no image or no file raises TypeError, as image_arguments and bytes() do; image_entries speaks of "entry 0" in what it refuses"""
+        if capi.is_device_object(en.get("img")):
+            arr, keep = device_entries([en])
+            self.last_rc = self.lib.l3d_line3d_add_device_entry(self.h, arr, C.c_char_p(self.data_directory.encode()), C.c_int(int(maxImgWidth)),
+                                                                C.c_int(int(loadAndStoreSegments)))
+            return self.last_rc == 0
         if "data" in en and not isinstance(en["data"], (bytes, bytearray, memoryview, np.ndarray)):
             en["data"] = bytes(en["data"])            # (whatever bytes() takes, as before; None or a str: TypeError)
         arr, keep = image_entries([en])
@@ -208,12 +257,13 @@ class Line3D:
         """Line3D::addImage from pixels (an image entry with img, include/line3d_amd.h): uint8 image H x W or H x W x 3.  The segment cache in
         `data_directory` is loaded when present (and loadAndStoreSegments); otherwise the segments are detected on the device, and the cache written
         or a stale one removed.  An image without segments adds no view and is no error (line3D.cc:186-190).  dist = (k1, k2), OpenCV-convention
-        radial coefficients: the image is undistorted on the device with K before the detector sees it."""
-        return self._add_entry(dict(imageID=imageID, img=np.asarray(img), K=K, R=R, t=t, worldpointIDs=list(worldpointIDs), dist=dist), maxImgWidth, loadAndStoreSegments)
+        radial coefficients: the image is undistorted on the device with K before the detector sees it.
+        img may be a device object (a torch device tensor, a capi.device_image descriptor): it is read where it lies (l3d_line3d_add_device_entry)."""
+        return self._add_entry(dict(imageID=imageID, img=img if capi.is_device_object(img) else np.asarray(img), K=K, R=R, t=t, worldpointIDs=list(worldpointIDs), dist=dist), maxImgWidth, loadAndStoreSegments)
 
     def add_image_pixels_fixed_sim(self, imageID, img, K, R, t, viewSimilarity, maxImgWidth=1920, loadAndStoreSegments=True, dist=None):
-        """Line3D::addImage_fixed_sim from pixels; dist as in add_image_pixels"""
-        return self._add_entry(dict(imageID=imageID, img=np.asarray(img), K=K, R=R, t=t, viewSimilarity=dict(viewSimilarity), dist=dist), maxImgWidth, loadAndStoreSegments)
+        """Line3D::addImage_fixed_sim from pixels; dist and device objects as in add_image_pixels"""
+        return self._add_entry(dict(imageID=imageID, img=img if capi.is_device_object(img) else np.asarray(img), K=K, R=R, t=t, viewSimilarity=dict(viewSimilarity), dist=dist), maxImgWidth, loadAndStoreSegments)
 
     def add_image_jpeg(self, imageID, data, K, R, t, worldpointIDs, maxImgWidth=1920, loadAndStoreSegments=True, dist=None):
         """Line3D::addImage from the bytes of a baseline JPEG file (an image entry with data): decoded, undistorted (dist = (k1, k2), None: not)
@@ -230,18 +280,29 @@ class Line3D:
         with the detector run once over all entries whose cache does not stand in for them.  An entry is a dict with the single calls' argument
         names: imageID, K, R, t; img (a uint8 array) or data (the bytes of a baseline JPEG file); worldpointIDs or viewSimilarity ({view id:
         similarity}); optionally dist = (k1, k2).  Returns the list of statuses, one per entry: 0, or the code the single call would have failed
-        with (the causes: l3d_line3d_last_error, one line per failed entry).  A malformed entry raises before anything is added."""
-        arr, keep = image_entries(entries)
+        with (the causes: l3d_line3d_last_error, one line per failed entry).  A malformed entry raises before anything is added.
+        The img of every entry may be a device object instead (l3d_line3d_add_device_images); a list that mixes device objects with host
+        images or files raises ValueError before any call."""
+        entries = list(entries)
+        on_device = _entries_on_device(entries, "add_images")
+        arr, keep = (device_entries if on_device else image_entries)(entries)
         n = len(entries)
         status = (C.c_int * max(1, n))()
-        self._chk(self.lib.l3d_line3d_add_images(self.h, arr, C.c_int(n), C.c_char_p(self.data_directory.encode()), C.c_int(int(maxImgWidth)),
+        call = self.lib.l3d_line3d_add_device_images if on_device else self.lib.l3d_line3d_add_images
+        self._chk(call(self.h, arr, C.c_int(n), C.c_char_p(self.data_directory.encode()), C.c_int(int(maxImgWidth)),
                                                  C.c_int(int(loadAndStoreSegments)), status))
         return [int(status[i]) for i in range(n)]
 
-    def decode_jpeg(self, data):
-        """l3d_line3d_decode_jpeg: Context.decode_jpeg with the object's device (a node object: rank 0's)"""
+    def decode_jpeg(self, data, device=False):
+        """l3d_line3d_decode_jpeg: Context.decode_jpeg with the object's device (a node object: rank 0's); device=True: a torch uint8 tensor there"""
         w, h, ch = capi.jpeg_info(data)
         ptr, n = capi._bytes_arguments(data)
+        if device:
+            import torch
+            out = torch.zeros((h, w) if ch == 1 else (h, w, ch), dtype=torch.uint8, device="cuda:%d" % self._device)
+            o = capi.device_image(out)
+            self._chk(self.lib.l3d_line3d_decode_jpeg_device(self.h, ptr, n, C.byref(o)))
+            return out
         out = np.zeros((h, w) if ch == 1 else (h, w, ch), np.uint8)
         self._chk(self.lib.l3d_line3d_decode_jpeg(self.h, ptr, n, _p(out), C.c_size_t(w * ch)))
         return out

@@ -6,6 +6,7 @@ import ctypes as C
 
 import numpy as np
 
+from . import capi
 from .capi import load_library
 
 
@@ -111,7 +112,8 @@ def reconstruct(scene: SfmScene, segments, image_sizes, out_dir=None, neighbors=
 def reconstruct_from_images(scene: SfmScene, load_image, data_directory, out_dir=None, neighbors=10, diffusion=False, max_width=1920,
                             load_and_store_segments=True, device=0, batch=16, **line3d_kwargs):
     """The drivers' flow (main_vsfm.cpp:226-325) from pixels: per camera the image load_image(i, name) returns -- `bytes`: the contents of a
-    baseline JPEG file, decoded on the device (Line3D.add_image_jpeg); or a uint8 array H x W or H x W x 3, decoded by the caller --, K from the focal length and the image size, the image undistorted with the camera's coefficients and its
+    baseline JPEG file, decoded on the device (Line3D.add_image_jpeg); or a uint8 array H x W or H x W x 3, decoded by the caller; or an image
+    in device memory (a torch device tensor, a capi.device_image descriptor), read where it lies --, K from the focal length and the image size, the image undistorted with the camera's coefficients and its
     segments detected on the device (Line3D.add_image_pixels(..., dist=cam["cv_dist"])), compute3Dmodel, optional STL + TXT output under the
     drivers' file name.  data_directory: the drivers' "<image folder>/L3D_data/" -- with load_and_store_segments (the drivers' default) the segment
     caches are written there, and a cache of an earlier run stands in for the image (line3D.cc:143-168).  The images go to the library `batch`
@@ -134,10 +136,20 @@ def reconstruct_from_images(scene: SfmScene, load_image, data_directory, out_dir
             from .capi import jpeg_info
             w, h, _ = jpeg_info(img)
             en["data"] = bytes(img)
+            if entries and capi.is_device_object(entries[-1].get("img")):
+                flush()
+        elif capi.is_device_object(img):
+            d = capi.device_image(img)
+            w, h = d.width, d.height
+            en["img"] = d
+            if entries and not capi.is_device_object(entries[-1].get("img")):      # (a call takes device images or host images and files, not both)
+                flush()
         else:
             img = np.asarray(img)
             h, w = img.shape[:2]
             en["img"] = img
+            if entries and capi.is_device_object(entries[-1].get("img")):
+                flush()
         en["K"] = intrinsics(cam["focal"], w, h)
         entries.append(en)
         if len(entries) >= batch:
