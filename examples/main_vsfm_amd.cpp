@@ -2,8 +2,10 @@
 // segment caches of an earlier Line3D run standing in for the images, or with the images as binary PPM / PGM files or baseline JPEG files (no
 // OpenCV, no tclap, no boost):
 //
-//   main_vsfm_amd <scene.nvm | bundle.rd.out> <data directory> [neighbors=10] [diffusion=0] [output folder=<data directory>] [image folder]
+//   main_vsfm_amd [--refine] <scene.nvm | bundle.rd.out> <data directory> [neighbors=10] [diffusion=0] [output folder=<data directory>] [image folder]
 //
+// --refine (anywhere on the line): the 3-D lines are refined against the 2-D segments of their clusters before they are written (setRefinement: the
+// reference has no such step; its successor Line3D++ added one) -- the segments of a line in the STL / TXT files are then collinear.
 // With an image folder, camera i's image is "<image folder>/<camera name, extension replaced>.ppm" or ".pgm" (binary P6 / P5, maxval 255), or the
 // camera's own file "<image folder>/<camera name>" when it ends in .jpg / .jpeg (baseline JPEG, decoded on the device: addImageJPEGDistorted;
 // convert PNG and progressive JPEG beforehand).  The camera name is the NVM file's image name; for a bundler file it is the camera index as %08d
@@ -119,7 +121,13 @@ struct Vec3 { const double* p; double operator()(int i) const { return p[i]; } }
 
 int main(int argc, char** argv)
 {
-    if (argc < 3) { fprintf(stderr, "usage: %s <scene.nvm | bundle.rd.out> <data directory> [neighbors=10] [diffusion=0] [output folder] [image folder]\n", argv[0]); return 2; }
+    bool refine = false;
+    {
+        int k = 1;
+        for (int i = 1; i < argc; ++i) { if (std::string(argv[i]) == "--refine") refine = true; else argv[k++] = argv[i]; }
+        argc = k;
+    }
+    if (argc < 3) { fprintf(stderr, "usage: %s [--refine] <scene.nvm | bundle.rd.out> <data directory> [neighbors=10] [diffusion=0] [output folder] [image folder]\n", argv[0]); return 2; }
     const std::string nvm = argv[1], data_dir = argv[2];
     const int neighbors = argc > 3 ? atoi(argv[3]) : 10;
     const bool diffusion = argc > 4 && atoi(argv[4]) != 0;
@@ -138,6 +146,7 @@ int main(int argc, char** argv)
     // Line3D(data_directory, matchingNeighbors, ...) with the driver's defaults (main_vsfm.cpp:60-99)
     L3D::Line3D line3D(data_dir, neighbors, 5.0f, 1.0f, 3.5f, 10.0f, 0.25f, true, true);
     if (!line3D.valid()) { l3d_sfm_free(scene); return 1; }
+    if (refine) line3D.setRefinement(true);
     int added = 0;
     for (int i = 0; i < n; ++i) {
         double focal = 0, dist[2] = { 0, 0 }, R[9], t[3];

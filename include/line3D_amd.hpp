@@ -415,6 +415,23 @@ public:
     }
     // line3D.h:82
     void compute3Dmodel(bool perform_diffusion = false) { report(l3d_line3d_compute3Dmodel(h_, perform_diffusion ? 1 : 0)); }
+    // Refinement of the result (no counterpart in the reference; l3d_line3d_set_refinement): with it on, compute3Dmodel refines every 3-D line against the
+    // 2-D segments of its cluster and replaces its 3-D segments by collinear ones -- lines, their order and their 2-D segments stay.  Off by default; reset()
+    // keeps the setting.  huberPx: scale of the Huber loss in pixels, 0 = plain least squares.
+    void setRefinement(bool on, int maxIterations = 20, double huberPx = 2.0) { report(l3d_line3d_set_refinement(h_, on ? 1 : 0, maxIterations, huberPx)); }
+    // one entry per line of getResult(): pixel rms of the members' 2-D end points before and after, and the status (0 refined, 1 starting line kept, 2 degenerate,
+    // 3 refined sweep empty: unrefined segments kept).  false (and empty vectors) when the last compute3Dmodel ran without the refinement.
+    bool getRefinement(std::vector<double>& rmsBefore, std::vector<double>& rmsAfter, std::vector<int>& status)
+    {
+        rmsBefore.clear(); rmsAfter.clear(); status.clear();
+        int nl = 0;
+        if (l3d_line3d_result_sizes(h_, &nl, nullptr, nullptr) != L3D_OK) return false;
+        std::vector<double> rb((size_t)nl), ra((size_t)nl);
+        std::vector<int32_t> st((size_t)nl);
+        if (l3d_line3d_get_refinement(h_, rb.data(), ra.data(), nullptr, st.data()) != L3D_OK) return false;
+        rmsBefore = rb; rmsAfter = ra; status.assign(st.begin(), st.end());
+        return true;
+    }
     // line3D.h:85
     void getResult(std::list<L3DFinalLine3D>& result)
     {

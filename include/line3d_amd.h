@@ -208,6 +208,29 @@ int l3d_fit_labelled_clusters(l3d_ctx* ctx, const int32_t* labels, const int32_t
                               const uint32_t* hyp_cam, int n_hyp, const double* Rinv, double scale_inv, const double* tneg,
                               int32_t** group_start, int32_t** member_hyp, int* n_groups, int32_t** seg_count, double** segs, int* n_segs);
 
+/* Refinement of 3-D lines against the 2-D segments of their clusters (no counterpart in the reference; formulas: line3d_amd/csrc/l3d_refine.hpp,
+ * DESIGN.md 4g).  Every cluster gets a Levenberg-Marquardt fit of its line (4 local parameters, Huber loss on the pixel distance of the members'
+ * 2-D end points to the projected line, f64), one wave per cluster, and its members' end points are taken onto the refined line by their viewing
+ * rays and swept as l3d_fit_clusters sweeps them -- the emitted segments of a cluster lie on one line.
+ * A cluster = its members in key order: group_start (n_groups + 1) into member_cam (index into `cameras`), member_seg (x1, y1, x2, y2) and
+ * member_pts (the hypothesis' two 3-D end points); cameras: n_cameras 3x4 matrices P = [M | p4], row-major, in the frame of the points.
+ * params == NULL: 20 iterations, huber_px 2.0; huber_px 0: plain least squares.
+ * Outputs per cluster (caller-allocated): line (point A, unit direction d), rms_before / rms_after (pixels, unweighted), iterations (trials
+ * made), status (0 refined, 1 no trial lowered the cost: the starting line, 2 degenerate -- fewer than two usable members or an input that is not
+ * finite: the starting line).  seg_count / segs / n_segs: callee-allocated (l3d_free), as l3d_fit_clusters.
+ * Refused with L3D_ERR_INVALID before anything is launched: a group_start that does not ascend from 0, a camera index outside the table, a negative
+ * max_iterations or huber_px, a camera matrix that is not finite.  n_groups == 0: empty outputs, L3D_OK. */
+typedef struct l3d_refine_params { int32_t max_iterations; int32_t pad; double huber_px; } l3d_refine_params;
+int l3d_refine_lines(l3d_ctx* ctx, const int32_t* group_start, int n_groups, const int32_t* member_cam, const float* member_seg, const double* member_pts,
+                     const double* cameras, int n_cameras, const l3d_refine_params* params, double* line, double* rms_before, double* rms_after,
+                     int32_t* iterations, int32_t* status, int32_t** seg_count, double** segs, int* n_segs);
+/* the same arithmetic on the host (the shared functions of l3d_refine.hpp with 64 lanes run one after the other): needs no device; bit-equal to
+ * l3d_refine_lines.  A refusal's cause: l3d_refine_last_error (per thread). */
+int l3d_test_refine_host(const int32_t* group_start, int n_groups, const int32_t* member_cam, const float* member_seg, const double* member_pts,
+                         const double* cameras, int n_cameras, const l3d_refine_params* params, double* line, double* rms_before, double* rms_after,
+                         int32_t* iterations, int32_t* status, int32_t** seg_count, double** segs, int* n_segs);
+const char* l3d_refine_last_error(void);
+
 
 /* ---- Line3D::matchViews as one device-resident chain --------------------------------------------------------
  * The schedule of matchViews (line3D.cc:620-648) is static: which neighbours a view still has to match and
@@ -589,6 +612,18 @@ int l3d_line3d_compute3Dmodel(l3d_line3d* h, int perform_diffusion);
 int l3d_line3d_prepare(l3d_line3d* h);          /* findVisualNeighbors + transformGeometry; inputs become HBM-resident */
 int l3d_line3d_match_views(l3d_line3d* h);      /* Line3D::matchViews, line3D.cc:620-648 (re-runnable) */
 int l3d_line3d_finish(l3d_line3d* h, int perform_diffusion);   /* optimizeLocalMatches + clusterSegments2D */
+/* Refinement of the result (l3d_refine_lines), off by default: with it on, finish / compute3Dmodel refine every line of the result against the 2-D
+ * segments of its cluster, in the normalised frame, and replace its 3-D segments by the refined ones (status 3: the refined sweep emitted nothing, the
+ * line keeps its unrefined segments); the lines, their order and their 2-D segments do not change.  reset keeps the setting.  A node object refines
+ * on rank 0's context, which holds the result.  get: one entry per result line (any pointer may be NULL); L3D_ERR_INVALID after a finish without
+ * the option. */
+int l3d_line3d_set_refinement(l3d_line3d* h, int on, int max_iterations, double huber_px);
+int l3d_line3d_get_refinement(const l3d_line3d* h, double* rms_before, double* rms_after, int32_t* iterations, int32_t* status);
+/* inspection (tests): what a refinement of the current result is fed with, in the normalised frame -- counts[3] = lines, members, cameras; then (any may be
+ * NULL; sizes from a first call) group_start (lines + 1), member_cam, member_seg (4 each), member_pts (6 each), cameras (12 each, views in ascending id), and
+ * Line3D::inverseTransform (line3D.cc:1782-1786) as transform[13] = Rinv (9, row-major), scale_inv, tneg (3): X = Rinv (P scale_inv + tneg). */
+int l3d_line3d_refinement_input(l3d_line3d* h, int32_t* counts, int32_t* group_start, int32_t* member_cam, float* member_seg, double* member_pts, double* cameras,
+                                double* transform);
 /* step-wise matchViews for view sharding: begin; for each view in match_order: compute a source-segment
  * range, (all-gather), commit the merged kept list; end. */
 int l3d_line3d_match_begin(l3d_line3d* h, int* n_order);

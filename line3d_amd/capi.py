@@ -131,6 +131,49 @@ def test_jpeg_coefficients(data):
 test_jpeg_coefficients.__test__ = False
 
 
+class RefineParams(C.Structure):
+    """l3d_refine_params"""
+    _fields_ = [("max_iterations", C.c_int32), ("pad", C.c_int32), ("huber_px", C.c_double)]
+
+
+def _refine_call(fn, head, group_start, member_cam, member_seg, member_pts, cameras, max_iterations, huber_px):
+    """the argument list l3d_refine_lines and l3d_test_refine_host share (head: the context, or nothing) -> (rc, result dict)"""
+    gs = np.ascontiguousarray(group_start, np.int32)
+    mc = np.ascontiguousarray(member_cam, np.int32)
+    ms = np.ascontiguousarray(member_seg, np.float32).reshape(-1, 4)
+    mp = np.ascontiguousarray(member_pts, np.float64).reshape(-1, 6)
+    cams = np.ascontiguousarray(cameras, np.float64).reshape(-1, 12)
+    ng = max(len(gs) - 1, 0)
+    if not (len(mc) == len(ms) == len(mp)) or (ng and gs[-1] > len(mc)):
+        raise ValueError("refine_lines: the member arrays do not match the group table")
+    prm = None if max_iterations is None and huber_px is None else RefineParams(20 if max_iterations is None else int(max_iterations), 0, 2.0 if huber_px is None else float(huber_px))
+    line, rb, ra = np.zeros((ng, 6)), np.zeros(ng), np.zeros(ng)
+    it, st = np.zeros(ng, np.int32), np.zeros(ng, np.int32)
+    cnt, segs, n = C.POINTER(C.c_int32)(), C.POINTER(C.c_double)(), C.c_int(0)
+    rc = fn(*head, _p(gs), C.c_int(ng), _p(mc), _p(ms), _p(mp), _p(cams), C.c_int(len(cams)), C.byref(prm) if prm is not None else None, _p(line), _p(rb), _p(ra), _p(it), _p(st),
+            C.byref(cnt), C.byref(segs), C.byref(n))
+    if rc != 0:
+        return rc, None
+    counts = np.ctypeslib.as_array(cnt, (ng,)).copy() if ng else np.zeros(0, np.int32)
+    flat = np.ctypeslib.as_array(segs, (n.value * 6,)).copy().reshape(-1, 6) if n.value else np.zeros((0, 6))
+    lib = load_library()
+    lib.l3d_free(cnt)
+    lib.l3d_free(segs)
+    return 0, {"line": line, "rms_before": rb, "rms_after": ra, "iterations": it, "status": st, "seg_count": counts, "segs": flat}
+
+
+def refine_lines_host(group_start, member_cam, member_seg, member_pts, cameras, max_iterations=None, huber_px=None):
+    """l3d_test_refine_host: the refinement's arithmetic on the host -- no context, no device.  Arguments and result as Context.refine_lines."""
+    lib = load_library()
+    lib.l3d_refine_last_error.restype = C.c_char_p
+    rc, out = _refine_call(lib.l3d_test_refine_host, (), group_start, member_cam, member_seg, member_pts, cameras, max_iterations, huber_px)
+    if rc != 0:
+        e = L3DError("line3d_amd error %d: %s" % (rc, lib.l3d_refine_last_error().decode()))
+        e.code = rc
+        raise e
+    return out
+
+
 class DetectEntry(C.Structure):
     """l3d_detect_entry (include/line3d_amd.h)"""
     _fields_ = [("pixels", C.c_void_p), ("width", C.c_int), ("height", C.c_int), ("channels", C.c_int), ("row_stride", C.c_size_t),
@@ -886,6 +929,14 @@ class Context:
         for c in counts:
             out.append([(flat[k + i, :3].copy(), flat[k + i, 3:].copy()) for i in range(c)])
             k += int(c)
+        return out
+
+    def refine_lines(self, group_start, member_cam, member_seg, member_pts, cameras, max_iterations=None, huber_px=None):
+        """l3d_refine_lines: clusters as group_start (n_groups + 1) into member_cam (n,), member_seg (n, 4) float32, member_pts (n, 6) float64; cameras
+        (n_cameras, 3, 4).  max_iterations and huber_px both None: the defaults (20, 2.0).  -> dict of line (n_groups, 6), rms_before, rms_after,
+        iterations, status, seg_count (n_groups,) and segs (n_segs, 6), the clusters' segments back to back."""
+        rc, out = _refine_call(self.lib.l3d_refine_lines, (self.h,), group_start, member_cam, member_seg, member_pts, cameras, max_iterations, huber_px)
+        self._chk(rc)
         return out
 
     def fit_labelled_clusters(self, labels, node_hyp, hyp, hyp_cam, Rinv, scale_inv, tneg):

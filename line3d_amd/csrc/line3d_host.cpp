@@ -658,6 +658,7 @@ int l3d_line3d_reset(l3d_line3d* h)
     h->views.clear(); h->vlist.clear(); h->view_similarities.clear(); h->num_wps.clear(); h->common_wps.clear();
     h->worldpoints2views.clear(); h->visual_neighbors.clear(); h->fundamentals.clear(); h->matched.clear();
     h->pot.clear(); h->pot_foreign.clear(); h->hyps.clear(); h->best_idx.clear(); h->A.clear(); h->n_edges = 0; h->A_on_host = true; h->local2global.clear(); h->result.clear();
+    h->refine_valid = false;                               // (the setting itself stays)
     h->computation = false; h->prepared = false;
     drop_plan(h);
     return L3D_OK;
@@ -1153,12 +1154,53 @@ int l3d_line3d_finish(l3d_line3d* h, int perform_diffusion)
     else if (h->resident_products) { const int rg = greedy_selection_resident(h); if (rg) return rg; }
     else greedy_selection(h);                              // optimizeLocalMatches, :888-896
     if (hopt(h).timing) fprintf(stderr, "[l3d finish] %-28s %8.2f ms\n", "greedy selection", (now_s() - t0) * 1e3);
-    const int rc = cluster_segments_2D(h, perform_diffusion != 0);
+    int rc = cluster_segments_2D(h, perform_diffusion != 0);
+    h->refine_valid = false;
+    if (!rc && h->refine_on) rc = refine_result(h);
     if (hopt(h).timing) fprintf(stderr, "[l3d finish] %-28s %8.2f ms\n", "total", (now_s() - t0) * 1e3);
     if (!rc && h->verbose)      // line3D.cc:959-961, 1226-1229, 1251
         printf("[L3D] #clusterable_segments:  %zu\n[L3D] A: #num_entries = %zu\n[L3D] A: #num_rows    = %zu\n[L3D] %zu 3D lines found!\n",
                h->hyps.size(), h->n_edges, h->local2global.size(), h->result.size());
     return rc;
+}
+// the refinement of the result (refine_result, line3d_host_finish.cpp).  A node object refines on rank 0, which holds the result: the other ranks keep it off
+int l3d_line3d_set_refinement(l3d_line3d* h, int on, int max_iterations, double huber_px)
+{
+    if (!h) return L3D_ERR_INVALID;
+    if (max_iterations < 0 || !(huber_px >= 0.0) || huber_px - huber_px != 0.0) return h->fail(L3D_ERR_INVALID, "set_refinement: max_iterations and huber_px must not be negative");
+    if (h->node) return l3d_line3d_set_refinement(rank0(h), on, max_iterations, huber_px);
+    h->refine_on = on != 0; h->refine_max_iterations = max_iterations; h->refine_huber_px = huber_px;
+    return L3D_OK;
+}
+int l3d_line3d_get_refinement(const l3d_line3d* h, double* rms_before, double* rms_after, int32_t* iterations, int32_t* status)
+{
+    if (!h) return L3D_ERR_INVALID;
+    if (h->node) return l3d_line3d_get_refinement(rank0(h), rms_before, rms_after, iterations, status);
+    if (!h->refine_valid || h->ref_status.size() != h->result.size()) return const_cast<L*>(h)->fail(L3D_ERR_INVALID, "get_refinement: the last finish ran without the refinement");
+    const size_t n = h->result.size();
+    if (n && rms_before) memcpy(rms_before, h->ref_rms_before.data(), n * 8);
+    if (n && rms_after) memcpy(rms_after, h->ref_rms_after.data(), n * 8);
+    if (n && iterations) memcpy(iterations, h->ref_iterations.data(), n * 4);
+    if (n && status) memcpy(status, h->ref_status.data(), n * 4);
+    return L3D_OK;
+}
+// inspection (tests): what a refinement of the CURRENT result would be fed with -- counts[3] = lines, members, cameras; then (any may be NULL) group_start
+// (lines + 1), member_cam, member_seg (4 each), member_pts (6 each), cameras (12 each), and Line3D::inverseTransform as transform[13] = Rinv (9), scale_inv, tneg (3)
+int l3d_line3d_refinement_input(l3d_line3d* h, int32_t* counts, int32_t* group_start, int32_t* member_cam, float* member_seg, double* member_pts, double* cameras, double* transform)
+{
+    if (!h) return L3D_ERR_INVALID;
+    if (h->node) return l3d_line3d_refinement_input(rank0(h), counts, group_start, member_cam, member_seg, member_pts, cameras, transform);
+    RefineInput in;
+    if (const int rc = refine_input(h, in)) return rc;
+    const size_t nl = h->result.size(), nm = (size_t)in.gstart[nl], nv = h->vlist.size();
+    if (counts) { counts[0] = (int32_t)nl; counts[1] = (int32_t)nm; counts[2] = (int32_t)nv; }
+    if (group_start) memcpy(group_start, in.gstart.data(), (nl + 1) * 4);
+    if (member_cam && nm) memcpy(member_cam, in.mcam.data(), nm * 4);
+    if (member_seg && nm) memcpy(member_seg, in.mseg.data(), nm * 16);
+    if (member_pts && nm) memcpy(member_pts, in.mpts.data(), nm * 48);
+    if (cameras && nv) memcpy(cameras, in.cameras.data(), nv * 96);
+    if (transform) { memcpy(transform, h->transf_Rinv.m, 72); transform[9] = h->transf_scale_inv; transform[10] = h->transf_tneg.x; transform[11] = h->transf_tneg.y; transform[12] = h->transf_tneg.z; }
+    return L3D_OK;
 }
 // Line3D::compute3Dmodel, line3D.cc:345-374
 int l3d_line3d_compute3Dmodel(l3d_line3d* h, int perform_diffusion)

@@ -716,5 +716,85 @@ int cluster_segments_2D(L* h, bool perform_diff)
     return L3D_OK;
 }
 
+// The refinement of the result (l3d_refine_lines; l3d_refine.hpp), after whichever fit path built the list: members are every line's segs2D, their 2-D
+// segments View::segs, cameras View::P and points the hypotheses' P1 / P2 -- all in the normalised frame transform_geometry left them in, which is better
+// conditioned than the caller's; the emitted points go back through inverse_transform.  The member arrays are uploaded from the host (72 bytes per member).
+int refine_input(L* h, RefineInput& in)
+{
+    const size_t nl = h->result.size(), nv = h->vlist.size(), nh = h->hyps.size();
+    // the hypotheses' end points: on the host when greedy selection ran there, else the table the affinity fill left on the device
+    std::vector<l3d_hypothesis> table;
+    const bool host_points = !h->resident_products && !h->partitioned;
+    if (!host_points && nl) {
+        table.resize(nh + 1);
+        const int rc = l3d::fetch_fill_hypotheses(h->ctx, (int)nh, table.data());
+        if (rc) return h->fail(rc, std::string("refinement: ") + l3d_last_error(h->ctx));
+    }
+    in.cameras.assign(12 * nv + 1, 0.0);
+    for (size_t i = 0; i < nv; ++i) memcpy(&in.cameras[12 * i], h->vlist[i]->P, 96);
+    in.gstart.assign(nl + 1, 0);
+    for (size_t l = 0; l < nl; ++l) in.gstart[l + 1] = in.gstart[l] + (int32_t)h->result[l].segs2D.size();
+    const size_t nm = (size_t)in.gstart[nl];
+    in.mcam.assign(nm + 1, 0); in.mseg.assign(4 * nm + 4, 0.0f); in.mpts.assign(6 * nm + 6, 0.0);
+    std::vector<int32_t>& gstart = in.gstart; std::vector<int32_t>& mcam = in.mcam; std::vector<float>& mseg = in.mseg; std::vector<double>& mpts = in.mpts;
+    std::atomic<int> bad{ 0 };
+    parallel_slices(nl, finish_threads(), [&](size_t l0, size_t l1, unsigned) {
+        for (size_t l = l0; l < l1; ++l) {
+            size_t m = (size_t)gstart[l];
+            for (Key k : h->result[l].segs2D) {
+                auto vt = h->views.find(kcam(k));
+                // (the hypotheses are in key order: greedy selection numbers them view by view, segment by segment)
+                auto hy = std::lower_bound(h->hyps.begin(), h->hyps.end(), k, [](const Hyp& a, Key b) { return a.src < b; });
+                if (vt == h->views.end() || kseg(k) >= (uint32_t)vt->second.S() || hy == h->hyps.end() || hy->src != k) { bad.store(1, std::memory_order_relaxed); break; }
+                mcam[m] = vt->second.index;
+                memcpy(&mseg[4 * m], &vt->second.segs[(size_t)kseg(k) * 4], 16);
+                double* q = &mpts[6 * m];
+                if (host_points) { q[0] = hy->P1.x; q[1] = hy->P1.y; q[2] = hy->P1.z; q[3] = hy->P2.x; q[4] = hy->P2.y; q[5] = hy->P2.z; }
+                else { const l3d_hypothesis& t = table[(size_t)(hy - h->hyps.begin())]; memcpy(q, t.P1, 24); memcpy(q + 3, t.P2, 24); }
+                ++m;
+            }
+        }
+    });
+    if (bad.load()) return h->fail(L3D_ERR_INVALID, "refinement: a 2-D segment of the result has no view or no hypothesis");
+    for (size_t i = 0; i < nv; ++i) if (h->vlist[i]->index != (int)i) return h->fail(L3D_ERR_INVALID, "refinement: views are not indexed in ascending id order");
+    return L3D_OK;
+}
+
+int refine_result(L* h)
+{
+    h->refine_valid = false;
+    h->ref_rms_before.clear(); h->ref_rms_after.clear(); h->ref_iterations.clear(); h->ref_status.clear();
+    const size_t nl = h->result.size(), nv = h->vlist.size();
+    const double t0 = now_s();
+    if (nl == 0) { h->refine_valid = true; return L3D_OK; }
+    RefineInput in;
+    if (const int ri = refine_input(h, in)) return ri;
+    const std::vector<int32_t>& gstart = in.gstart; const std::vector<int32_t>& mcam = in.mcam; const std::vector<float>& mseg = in.mseg; const std::vector<double>& mpts = in.mpts;
+    const std::vector<double>& cameras = in.cameras;
+    const size_t nm = (size_t)gstart[nl];
+    l3d_refine_params prm;
+    prm.max_iterations = h->refine_max_iterations; prm.pad = 0; prm.huber_px = h->refine_huber_px;
+    std::vector<double> line(6 * nl);
+    h->ref_rms_before.resize(nl); h->ref_rms_after.resize(nl); h->ref_iterations.resize(nl); h->ref_status.resize(nl);
+    int32_t* cnt = nullptr; double* segs = nullptr; int n_segs = 0;
+    const int rc = l3d_refine_lines(h->ctx, gstart.data(), (int)nl, mcam.data(), mseg.data(), mpts.data(), cameras.data(), (int)nv, &prm, line.data(), h->ref_rms_before.data(),
+                                    h->ref_rms_after.data(), h->ref_iterations.data(), h->ref_status.data(), &cnt, &segs, &n_segs);
+    if (rc) return h->fail(rc, std::string("refinement: ") + l3d_last_error(h->ctx));
+    size_t at = 0;
+    for (size_t l = 0; l < nl; ++l) {
+        if (cnt[l] == 0) { if (h->ref_status[l] != 2) h->ref_status[l] = 3; continue; }      // (nothing emitted: the line keeps its unrefined segments)
+        FinalLine& fl = h->result[l];
+        fl.segs3D.clear();
+        for (int k = 0; k < cnt[l]; ++k, ++at) {
+            const double* q = segs + 6 * at;
+            fl.segs3D.emplace_back(inverse_transform(h, V3{ q[0], q[1], q[2] }), inverse_transform(h, V3{ q[3], q[4], q[5] }));
+        }
+    }
+    l3d_free(cnt); l3d_free(segs);
+    h->refine_valid = true;
+    if (hopt(h).timing) fprintf(stderr, "[l3d finish] %-28s %8.2f ms (%zu lines, %zu members)\n", "refinement", (now_s() - t0) * 1e3, nl, nm);
+    return L3D_OK;
+}
+
 
 }  // namespace l3dh

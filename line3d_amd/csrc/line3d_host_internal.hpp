@@ -229,6 +229,13 @@ struct l3d_line3d {
     std::vector<FinalLine> result;
     std::vector<size_t> hyp_begin;                             // per view index: first hypothesis (greedy_selection)
 
+    // refinement of the result (l3d_line3d_set_refinement; off by default, reset keeps it) and what the last finish with it on recorded per line
+    bool refine_on = false, refine_valid = false;
+    int refine_max_iterations = 20;
+    double refine_huber_px = 2.0;
+    std::vector<double> ref_rms_before, ref_rms_after;
+    std::vector<int32_t> ref_iterations, ref_status;
+
     // flat tables of the device affinity fill (l3d_affinity_input): kept between calls (no allocation, no page faults); the
     // collinearity part only changes with the set of views (drop_plan)
     struct AffTables {
@@ -261,6 +268,11 @@ static inline const l3d::Options& hopt(const l3d_line3d* h) { return l3d::ctx_op
 
 
 typedef l3d_line3d L;
+
+namespace l3d {
+// l3d_refine.hip: the hypothesis table the last affinity fill left on the device (n_hyp must match), copied to the host
+int fetch_fill_hypotheses(l3d_ctx* c, int n_hyp, l3d_hypothesis* out);
+}
 
 namespace l3dh {
 
@@ -353,5 +365,9 @@ void align_cluster(const std::vector<std::pair<Key, std::pair<V3, V3>>>& t3, std
 void pack_collinearities(L* h, const std::vector<size_t>& voff);
 int fill_affinity_resident(L* h);
 void destroy_finalizer(L* h);                       // joins the finaliser's worker threads
+// what refine_result hands to l3d_refine_lines: the result's lines as groups, the members' tables, the views' matrices (ascending id), normalised frame
+struct RefineInput { std::vector<int32_t> gstart, mcam; std::vector<float> mseg; std::vector<double> mpts, cameras; };
+int refine_input(L* h, RefineInput& in);
+int refine_result(L* h);
 
 }  // namespace l3dh

@@ -341,6 +341,34 @@ class Line3D:
     def save3DLinesAsTXT(self, filename: str):
         self._chk(self.lib.l3d_line3d_save_result(self.h, filename.encode(), C.c_int(1)))
 
+    # -- refinement of the result against the clusters' 2-D segments (no counterpart in the reference) --------------------
+    def set_refinement(self, on=True, max_iterations=20, huber_px=2.0):
+        """l3d_line3d_set_refinement: with it on, finish / compute3Dmodel refine every line of the result (Levenberg-Marquardt on the members' 2-D end
+        points, Huber loss of scale huber_px, 0 = least squares) and replace its 3-D segments by collinear ones; off by default; reset keeps it."""
+        self._chk(self.lib.l3d_line3d_set_refinement(self.h, C.c_int(int(bool(on))), C.c_int(int(max_iterations)), C.c_double(float(huber_px))))
+
+    def refinement(self):
+        """l3d_line3d_get_refinement: dict of rms_before, rms_after (pixels), iterations, status -- one entry per line of getResult().  status 0 refined,
+        1 starting line (no trial lowered the cost), 2 degenerate, 3 the refined sweep emitted nothing: unrefined segments kept."""
+        nl = C.c_int(0)
+        self._chk(self.lib.l3d_line3d_result_sizes(self.h, C.byref(nl), None, None))
+        n = nl.value
+        rb, ra, it, st = np.zeros(n), np.zeros(n), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        self._chk(self.lib.l3d_line3d_get_refinement(self.h, _p(rb), _p(ra), _p(it), _p(st)))
+        return {"rms_before": rb, "rms_after": ra, "iterations": it, "status": st}
+
+    def refinement_input(self):
+        """l3d_line3d_refinement_input (inspection): what a refinement of the current result is fed with -- dict of group_start, member_cam, member_seg,
+        member_pts, cameras (normalised frame) and Rinv (3, 3), scale_inv, tneg (3,) of Line3D::inverseTransform."""
+        cnt = np.zeros(3, np.int32)
+        self._chk(self.lib.l3d_line3d_refinement_input(self.h, _p(cnt), None, None, None, None, None, None))
+        nl, nm, nv = (int(x) for x in cnt)
+        gs, mc, ms, mp = np.zeros(nl + 1, np.int32), np.zeros(nm, np.int32), np.zeros((nm, 4), np.float32), np.zeros((nm, 6))
+        cams, tr = np.zeros((nv, 3, 4)), np.zeros(13)
+        self._chk(self.lib.l3d_line3d_refinement_input(self.h, _p(cnt), _p(gs), _p(mc), _p(ms), _p(mp), _p(cams), _p(tr)))
+        return {"group_start": gs, "member_cam": mc, "member_seg": ms, "member_pts": mp, "cameras": cams, "Rinv": tr[:9].reshape(3, 3).copy(), "scale_inv": float(tr[9]),
+                "tneg": tr[10:13].copy()}
+
     def numCameras(self):
         return self.lib.l3d_line3d_num_cameras(self.h)
 

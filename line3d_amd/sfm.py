@@ -110,17 +110,20 @@ def reconstruct(scene: SfmScene, segments, image_sizes, out_dir=None, neighbors=
 
 
 def reconstruct_from_images(scene: SfmScene, load_image, data_directory, out_dir=None, neighbors=10, diffusion=False, max_width=1920,
-                            load_and_store_segments=True, device=0, batch=16, **line3d_kwargs):
+                            load_and_store_segments=True, device=0, batch=16, refine=False, **line3d_kwargs):
     """The drivers' flow (main_vsfm.cpp:226-325) from pixels: per camera the image load_image(i, name) returns -- `bytes`: the contents of a
     baseline JPEG file, decoded on the device (Line3D.add_image_jpeg); or a uint8 array H x W or H x W x 3, decoded by the caller; or an image
     in device memory (a torch device tensor, a capi.device_image descriptor), read where it lies --, K from the focal length and the image size, the image undistorted with the camera's coefficients and its
     segments detected on the device (Line3D.add_image_pixels(..., dist=cam["cv_dist"])), compute3Dmodel, optional STL + TXT output under the
     drivers' file name.  data_directory: the drivers' "<image folder>/L3D_data/" -- with load_and_store_segments (the drivers' default) the segment
     caches are written there, and a cache of an earlier run stands in for the image (line3D.cc:143-168).  The images go to the library `batch`
-    at a time (Line3D.add_images): the same views as one call per image, with the detector run once per batch."""
+    at a time (Line3D.add_images): the same views as one call per image, with the detector run once per batch.
+    refine: the 3-D lines are refined against the 2-D segments of their clusters (Line3D.set_refinement, defaults) before they are written."""
     import os
     from .pipeline import Line3D
     l3d = Line3D(data_directory, matchingNeighbors=neighbors, device=device, **line3d_kwargs)
+    if refine:
+        l3d.set_refinement(True)
     entries = []
 
     def flush():
