@@ -219,6 +219,36 @@ public:
         for (int i = 0; i < h; ++i) memcpy(px + (size_t)i * step, tmp.data() + (size_t)i * row, row);
         return true;
     }
+    // The same with a LENS (include/line3d_amd.h, "A LENS": l3d_lens -- tangential, rational and fisheye models): the image is resampled from the
+    // lens's source camera onto K, which the view keeps.  For image types that carry pixels, as addImageDistorted
+    template <class Img, class M3, class V3, class = decltype(std::declval<const Img&>().cols), class = decltype(std::declval<const Img&>().rows),
+              class = decltype(std::declval<const M3&>()(0, 0)), class = decltype(std::declval<const V3&>()(0))>
+    void addImageLens(const unsigned int imageID, const Img& image, const M3& K, const M3& R, const V3& t, const l3d_lens& lens, std::list<unsigned int>& worldpointIDs,
+                      const int maxImgWidth = 1920, const bool loadAndStoreSegments = true)
+    {
+        add_one(makeEntry(imageID, image, K, R, t, worldpointIDs).withLens(lens), maxImgWidth, loadAndStoreSegments);
+    }
+    template <class Img, class M3, class V3, class = decltype(std::declval<const Img&>().cols), class = decltype(std::declval<const Img&>().rows),
+              class = decltype(std::declval<const M3&>()(0, 0)), class = decltype(std::declval<const V3&>()(0))>
+    void addImage_fixed_simLens(const unsigned int imageID, const Img& image, const M3& K, const M3& R, const V3& t, const l3d_lens& lens,
+                                std::map<unsigned int, float>& viewSimilarity, const int maxImgWidth = 1920, const bool loadAndStoreSegments = true)
+    {
+        add_one(makeEntry(imageID, image, K, R, t, viewSimilarity).withLens(lens), maxImgWidth, loadAndStoreSegments);
+    }
+    // undistortImage with a lens: in place on image.data, K the output camera
+    template <class Img, class M3, class = decltype(static_cast<unsigned char*>(std::declval<Img&>().data)),
+              class = decltype(static_cast<size_t>(std::declval<const Img&>().step)), class = decltype(static_cast<int>(std::declval<const Img&>().channels())),
+              class = decltype(std::declval<const M3&>()(0, 0))>
+    bool undistortImage(Img& image, const M3& K, const l3d_lens& lens)
+    {
+        double k[9];
+        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) k[i * 3 + j] = K(i, j);
+        unsigned char* px = static_cast<unsigned char*>(image.data);
+        const size_t step = static_cast<size_t>(image.step);
+        const int rc = l3d_line3d_undistort_image_lens(h_, px, (int)image.cols, (int)image.rows, static_cast<int>(image.channels()), step, k, &lens, px, step);   // (in place: the library stages the image on the device)
+        report(rc);
+        return rc == L3D_OK;
+    }
     // The drivers' cv::imread in front of that block, for baseline JPEG files: `bytes` are the file's contents; it is decoded on the device
     // (include/line3d_amd.h: byte-identical to libjpeg's default decoder, three channels B, G, R as cv::imread gives them) straight into the
     // detector, undistorted first in the ...Distorted forms.  The cache rules are addImage's; a cache that is present and wanted is loaded
@@ -248,6 +278,12 @@ public:
     {
         add_one(makeEntry(imageID, bytes, n, K, R, t, viewSimilarity).distorted(k1, k2), maxImgWidth, loadAndStoreSegments);
     }
+    template <class M3, class V3, class Links, class = decltype(std::declval<const M3&>()(0, 0)), class = decltype(std::declval<const V3&>()(0))>
+    void addImageJPEGLens(const unsigned int imageID, const unsigned char* bytes, const size_t n, const M3& K, const M3& R, const V3& t, const l3d_lens& lens,
+                          const Links& links /* world point ids, or view similarities */, const int maxImgWidth = 1920, const bool loadAndStoreSegments = true)
+    {
+        add_one(makeEntry(imageID, bytes, n, K, R, t, links).withLens(lens), maxImgWidth, loadAndStoreSegments);
+    }
     // the size and channel count (1: grey, 3: B, G, R) a JPEG file decodes to, from its headers alone -- no device; false: not a file the decoder takes
     static bool jpegSize(const unsigned char* bytes, const size_t n, unsigned int& width, unsigned int& height, unsigned int& channels)
     {
@@ -276,10 +312,12 @@ public:
         int width = 0, height = 0, channels = 0;
         size_t step = 0, jpeg_bytes = 0;
         double K[9], R[9], t[3], dist[2] = { 0.0, 0.0 };
-        bool has_dist = false, fixed_sim = false;
+        bool has_dist = false, fixed_sim = false, has_lens = false;
+        l3d_lens lens = l3d_lens();     // in the place of dist (withLens); an entry with both is refused
         std::vector<uint32_t> link_ids;
         std::vector<float> sims;
         ImageEntry& distorted(const double k1, const double k2) { dist[0] = k1; dist[1] = k2; has_dist = true; return *this; }
+        ImageEntry& withLens(const l3d_lens& l) { lens = l; has_lens = true; return *this; }
     };
     template <class Img, class M3, class V3, class Links, class = decltype(static_cast<const unsigned char*>(std::declval<const Img&>().data)),
               class = decltype(static_cast<size_t>(std::declval<const Img&>().step)), class = decltype(static_cast<int>(std::declval<const Img&>().channels())),
@@ -308,9 +346,10 @@ public:
     std::vector<int> addImages(const std::vector<ImageEntry>& entries, const int maxImgWidth = 1920, const bool loadAndStoreSegments = true)
     {
         std::vector<l3d_image_entry> e;
-        for (const ImageEntry& s : entries) e.push_back(to_c(s));
+        std::vector<const l3d_lens*> lens;
+        for (const ImageEntry& s : entries) { e.push_back(to_c(s)); lens.push_back(s.has_lens ? &s.lens : nullptr); }
         std::vector<int> status(entries.size(), L3D_ERR_INVALID);        // (a call refused as a whole -- no object -- leaves them)
-        const int rc = l3d_line3d_add_images(h_, e.data(), (int)e.size(), data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0, status.data());
+        const int rc = l3d_line3d_add_images_lens(h_, e.data(), lens.data(), (int)e.size(), data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0, status.data());
         bool any = rc != L3D_OK;
         for (int st : status) any = any || st != L3D_OK;
         if (any) std::cerr << prefix_ << l3d_line3d_last_error(h_) << std::endl;
@@ -341,6 +380,7 @@ public:
         ImageEntry base;                // the id, the camera, dist and the links; no pixels and no file
         l3d_device_image image;
         DeviceEntry& distorted(const double k1, const double k2) { base.distorted(k1, k2); return *this; }
+        DeviceEntry& withLens(const l3d_lens& l) { base.withLens(l); return *this; }
     };
     template <class M3, class V3, class Links, class = decltype(std::declval<const M3&>()(0, 0)), class = decltype(std::declval<const V3&>()(0))>
     static DeviceEntry makeDeviceEntry(const unsigned int imageID, const l3d_device_image& image, const M3& K, const M3& R, const V3& t, const Links& links)
@@ -372,6 +412,13 @@ public:
     {
         add_device(makeDeviceEntry(imageID, image, K, R, t, worldpointIDs).distorted(k1, k2), maxImgWidth, loadAndStoreSegments);
     }
+    // with a lens; links: world point ids or view similarities
+    template <class Img, class M3, class V3, class Links>
+    void addImageDeviceLens(const unsigned int imageID, const Img& image, const M3& K, const M3& R, const V3& t, const l3d_lens& lens, const Links& links,
+                            const int maxImgWidth = 1920, const bool loadAndStoreSegments = true)
+    {
+        add_device(makeDeviceEntry(imageID, image, K, R, t, links).withLens(lens), maxImgWidth, loadAndStoreSegments);
+    }
     template <class Img, class M3, class V3>
     void addImage_fixed_simDevice(const unsigned int imageID, const Img& image, const M3& K, const M3& R, const V3& t, std::map<unsigned int, float>& viewSimilarity,
                                   const int maxImgWidth = 1920, const bool loadAndStoreSegments = true)
@@ -388,9 +435,10 @@ public:
     std::vector<int> addImagesDevice(const std::vector<DeviceEntry>& entries, const int maxImgWidth = 1920, const bool loadAndStoreSegments = true)
     {
         std::vector<l3d_device_entry> e;
-        for (const DeviceEntry& s : entries) e.push_back(to_c(s));
+        std::vector<const l3d_lens*> lens;
+        for (const DeviceEntry& s : entries) { e.push_back(to_c(s)); lens.push_back(s.base.has_lens ? &s.base.lens : nullptr); }
         std::vector<int> status(entries.size(), L3D_ERR_INVALID);
-        const int rc = l3d_line3d_add_device_images(h_, e.data(), (int)e.size(), data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0, status.data());
+        const int rc = l3d_line3d_add_device_images_lens(h_, e.data(), lens.data(), (int)e.size(), data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0, status.data());
         bool any = rc != L3D_OK;
         for (int st : status) any = any || st != L3D_OK;
         if (any) std::cerr << prefix_ << l3d_line3d_last_error(h_) << std::endl;
@@ -527,13 +575,13 @@ private:
     void add_device(const DeviceEntry& s, int maxImgWidth, bool loadAndStoreSegments)
     {
         const l3d_device_entry e = to_c(s);
-        report(l3d_line3d_add_device_entry(h_, &e, data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0));
+        report(l3d_line3d_add_device_entry_lens(h_, &e, s.base.has_lens ? &s.base.lens : nullptr, data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0));
     }
     // every image and JPEG form: one entry through the library's one route (l3d_line3d_add_image_entry)
     void add_one(const ImageEntry& s, int maxImgWidth, bool loadAndStoreSegments)
     {
         const l3d_image_entry e = to_c(s);
-        report(l3d_line3d_add_image_entry(h_, &e, data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0));
+        report(l3d_line3d_add_image_entry_lens(h_, &e, s.has_lens ? &s.lens : nullptr, data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0));
     }
     // `image` with pixels (cv::Mat: .data, .step, .channels()): detect on the device.  links: world point ids or view similarities; dist: null or k1, k2
     template <class Img, class M3, class V3, class Links, class = decltype(static_cast<const unsigned char*>(std::declval<const Img&>().data)),

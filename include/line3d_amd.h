@@ -717,6 +717,28 @@ int l3d_sfm_camera(const l3d_sfm_scene* scene, int i, double* focal, double dist
 int l3d_sfm_camera_cv_distortion(const l3d_sfm_scene* scene, int i, double k[2]);
 const char* l3d_sfm_camera_name(const l3d_sfm_scene* scene, int i);
 int l3d_sfm_camera_worldpoints(const l3d_sfm_scene* scene, int i, uint32_t* ids);
+/* A COLMAP model (a sparse reconstruction's folder): cameras.bin + images.bin when both are there, else cameras.txt + images.txt; points3D is not
+ * needed.  A camera of the scene is one IMAGE of the model, in the file's order: R from its world-to-camera quaternion (w, x, y, z), t as it is --
+ * what addImage takes --, its name, and as world point ids the POINT3D_IDs of its observations that are not -1 (l3d_sfm_num_points: the largest
+ * id + 1).  The accessors above work on such a scene; focal is the model's f, or fx where it has two; l3d_sfm_camera's dist and
+ * l3d_sfm_camera_cv_distortion answer for SIMPLE_PINHOLE, PINHOLE, SIMPLE_RADIAL and RADIAL with fx == fy ((0, 0), (k, 0), (k1, k2)) and are
+ * L3D_ERR_UNSUPPORTED for the others.  The models and their parameters, in the file's order:
+ *     SIMPLE_PINHOLE f cx cy | PINHOLE fx fy cx cy | SIMPLE_RADIAL f cx cy k | RADIAL f cx cy k1 k2 | OPENCV fx fy cx cy k1 k2 p1 p2 |
+ *     OPENCV_FISHEYE fx fy cx cy k1 k2 k3 k4 | FULL_OPENCV fx fy cx cy k1 k2 p1 p2 k3 k4 k5 k6 | FOV fx fy cx cy omega |
+ *     SIMPLE_RADIAL_FISHEYE f cx cy k | RADIAL_FISHEYE f cx cy k1 k2 | THIN_PRISM_FISHEYE fx fy cx cy k1 k2 p1 p2 k3 k4 sx1 sy1
+ *   l3d_sfm_camera_model   the image's camera as the file has it: the model's name, its parameters (n of them), untouched
+ *   l3d_sfm_camera_lens    the l3d_lens (see A LENS, below) and K of the image's camera, and its size.  THE PIXEL CENTRE: COLMAP puts the centre of
+ *                          the top-left pixel at (0.5, 0.5), the formulas here -- like remap -- at (0, 0): the lens and K carry cx - 0.5, cy - 0.5.
+ *                          The pinhole and radial models give BROWN, the three fisheye models FISHEYE; FOV and THIN_PRISM_FISHEYE read fine but
+ *                          have no lens here: L3D_ERR_UNSUPPORTED, the message (l3d_sfm_last_error) naming the model.  On an NVM or bundler scene:
+ *                          BROWN with the l3d_sfm_camera_cv_distortion coefficients, a zero source camera ("the output camera"), K zeroed and size 0
+ * Refused with a message on the scene object, L3D_ERR_INVALID: a missing or truncated file, a model id or name that is not of the list, a camera id
+ * without a camera, counts that the file cannot hold. */
+struct l3d_lens;
+int l3d_sfm_read_colmap(const char* model_dir, l3d_sfm_scene** out);
+int l3d_sfm_camera_model(const l3d_sfm_scene* scene, int i, const char** name, const double** params, int* n);
+int l3d_sfm_camera_lens(l3d_sfm_scene* scene, int i, struct l3d_lens* lens, double K[9], int* width, int* height);
+int l3d_sfm_camera_id(const l3d_sfm_scene* scene, int i);      /* the COLMAP camera id of image i; -1 on another kind of scene */
 /* the drivers' K from a focal length and the image size (main_vsfm.cpp:232-241): [[f,0,w/2],[0,f,h/2],[0,0,1]] */
 void l3d_sfm_intrinsics(double focal, unsigned int width, unsigned int height, double K[9]);
 
@@ -811,6 +833,53 @@ int l3d_undistort_image(l3d_ctx* ctx, const unsigned char* pixels, int width, in
                         double k1, double k2, unsigned char* out, size_t out_row_stride);
 int l3d_detect_segments_distorted(l3d_ctx* ctx, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, int new_width, int new_height,
                                   float min_length, int max_segments, double fx, double fy, double cx, double cy, double k1, double k2, float** segments, int* n);
+/* A LENS: undistortion with tangential, rational and fisheye models, onto a camera matrix of the caller's choice (k_det_undistort_lens,
+ * l3d_detect.hip).  The calls above know two radial coefficients and resample onto the same camera; the ..._lens calls take an l3d_lens and an
+ * OUTPUT camera (fx', fy', cx', cy') -- at context level four doubles, in the add family the entry's K, which is also the view's K.  The lens
+ * carries the SOURCE camera, that of the distorted image; fx == 0 && fy == 0 there says "the output camera".  When the two differ the image is
+ * resampled onto the new camera matrix, at the same size: that is what makes a fisheye usable, the caller can zoom out (fx' < fx).  Another
+ * output size, cropping and choosing the new matrix automatically are not offered.
+ * For output pixel (column j, row i), in double, nothing fused, in this order of operations:
+ *     x = (j - cx') / fx'      y = (i - cy') / fy'      r2 = x x + y y
+ *     BROWN:    num = 1 + ((k3 r2 + k2) r2 + k1) r2      den = 1 + ((k6 r2 + k5) r2 + k4) r2      kr = num / den
+ *               xd = x kr + ((2 p1) x y + p2 (r2 + 2 (x x)))
+ *               yd = y kr + (p1 (r2 + 2 (y y)) + (2 p2) x y)
+ *     FISHEYE:  r = sqrt(r2)   th = atan(r)   t2 = th th
+ *               td = th (1 + (((k4 t2 + k3) t2 + k2) t2 + k1) t2)
+ *               s = r > 1e-8 ? td / r : 1      xd = x s      yd = y s
+ *     u = fx xd + cx           v = fy yd + cy            (fx, fy, cx, cy: the source camera)
+ * (products run left to right: (2 p1) x y is ((2 p1) x) y).  The rest is the rule above, word for word: u not in (-1, width) or v not in
+ * (-1, height) (NaN included -- a rational lens whose denominator crosses zero gives inf and NaN; tested before any conversion to an integer): 0 in
+ * every channel; otherwise iu = rint(32 u), iv = rint(32 v), the four taps weighted in 1/1024, black outside.  Division and square root are IEEE;
+ * atan is the one operation whose bits the device does not share with a host libm (tests/lens_model.py holds its cases to a margin that a few ulp
+ * cannot cross).  BROWN with p1 = p2 = k3..k6 = 0 and the source camera equal to the output camera performs exactly the operations of the rule
+ * above (0 r2 + k2, num / 1 and x kr + 0 are exact): it gives the same bytes.
+ * Pass-through: a BROWN lens whose eight coefficients all lie within 1e-12, with equal cameras, launches nothing.  A FISHEYE lens is always active
+ * (zero coefficients are the equidistant projection, not the identity).
+ * Refused before anything is launched: an unknown model, a field that is not finite, exactly one of fx, fy zero, an output fx' or fy' that is
+ * zero or not finite, a non-zero k[4..7] on FISHEYE: L3D_ERR_INVALID.  Skew K[1] != 0 with an active lens (the add family and
+ * l3d_line3d_undistort_image_lens, which take K): L3D_ERR_UNSUPPORTED, as with dist.  An entry that carries both dist (at context level: a camera
+ * whose k1 or k2 is not zero) and a lens: L3D_ERR_INVALID.
+ *   l3d_undistort_image_lens              l3d_undistort_image with a lens; in place allowed
+ *   l3d_undistort_image_device_lens       l3d_undistort_image_device with a lens
+ *   l3d_detect_segments_batch_lens, l3d_detect_segments_device_batch_lens
+ *                                         the batch calls with, beside the entry array, an array of n lens pointers (the array or an element may be
+ *                                         NULL: the entry's own camera rule).  With a lens the entry's camera must be given: its fx, fy, cx, cy are the
+ *                                         output camera, its k1, k2 must be 0.  One chunk may mix models, lens-less images and k1, k2 cameras: a chunk
+ *                                         in which every camera is of the k1, k2 kind (or absent) launches k_det_undistort as before, any other chunk
+ *                                         launches k_det_undistort_lens once (a k1, k2 camera goes in as BROWN: the same bytes).  A single image is a
+ *                                         batch of one
+ *   l3d_line3d_add_image_entry_lens, l3d_line3d_add_images_lens, l3d_line3d_add_device_entry_lens, l3d_line3d_add_device_images_lens
+ *                                         THE ADD FAMILY (below) with the lens in the place of dist in step 1 of the ONE ROUTE
+ *   l3d_line3d_undistort_image_lens       l3d_undistort_image_lens with the object's device and K */
+enum { L3D_LENS_BROWN = 1, L3D_LENS_FISHEYE = 2 };
+typedef struct l3d_lens {
+    int model;               /* L3D_LENS_BROWN, L3D_LENS_FISHEYE; 0 is invalid: a zeroed struct is refused */
+    double fx, fy, cx, cy;   /* the SOURCE camera (of the distorted image); fx == 0 && fy == 0: the output camera */
+    double k[8];             /* BROWN: k1 k2 p1 p2 k3 k4 k5 k6 (OpenCV's order);  FISHEYE: k1 k2 k3 k4, the rest must be 0 */
+} l3d_lens;
+int l3d_undistort_image_lens(l3d_ctx* ctx, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, double fx, double fy, double cx,
+                             double cy, const l3d_lens* lens, unsigned char* out, size_t out_row_stride);
 /* Line3D::addImage / addImage_fixed_sim from pixels (line3D.cc:95-217, 220-324): the image entry (THE ADD FAMILY, below) with pixels filled and no
  * dist.  The detector runs at the size the max_img_width rule gives, with min_length = 0.005 sqrt(rows^2 + cols^2) and at most 3000 segments. */
 int l3d_line3d_add_image_pixels(l3d_line3d* h, uint32_t image_id, const unsigned char* pixels, int width, int height, int channels, size_t row_stride,
@@ -926,6 +995,9 @@ typedef struct l3d_detect_entry {
     const double* camera;                                                           /* NULL, or fx, fy, cx, cy, k1, k2 */
 } l3d_detect_entry;
 int l3d_detect_segments_batch(l3d_ctx* ctx, const l3d_detect_entry* e, int n, float** segments, int* offsets /* n + 1 */, int* status /* n */);
+/* with lenses (A LENS, above): lens NULL, or n pointers of which any may be NULL */
+int l3d_detect_segments_batch_lens(l3d_ctx* ctx, const l3d_detect_entry* e, const l3d_lens* const* lens, int n, float** segments, int* offsets /* n + 1 */,
+                                   int* status /* n */);
 
 /* =================================================================================================
  * Images in DEVICE memory (line3d_amd/csrc/l3d_device_image.hip): a decoded video frame, a tensor, a GpuMat -- described where they lie and gathered
@@ -1004,6 +1076,11 @@ int l3d_detect_segments_device_batch(l3d_ctx* ctx, const l3d_detect_device_entry
 int l3d_decode_jpeg_device(l3d_ctx* ctx, const unsigned char* bytes, size_t n, const l3d_device_image* out);
 int l3d_undistort_image_device(l3d_ctx* ctx, const l3d_device_image* in, double fx, double fy, double cx, double cy, double k1, double k2,
                                const l3d_device_image* out);
+/* with lenses (A LENS, above); fx, fy, cx, cy: the output camera */
+int l3d_detect_segments_device_batch_lens(l3d_ctx* ctx, const l3d_detect_device_entry* e, const l3d_lens* const* lens, int n, float** segments,
+                                          int* offsets /* n + 1 */, int* status /* n */);
+int l3d_undistort_image_device_lens(l3d_ctx* ctx, const l3d_device_image* in, double fx, double fy, double cx, double cy, const l3d_lens* lens,
+                                    const l3d_device_image* out);
 
 /* =================================================================================================
  * THE ADD FAMILY: Line3D::addImage / addImage_fixed_sim (line3D.cc:95-342) in every form the library takes an image in.
@@ -1055,6 +1132,15 @@ typedef struct l3d_image_entry {
 } l3d_image_entry;
 int l3d_line3d_add_image_entry(l3d_line3d* h, const l3d_image_entry* e, const char* data_directory, int max_img_width, int load_and_store);
 int l3d_line3d_add_images(l3d_line3d* h, const l3d_image_entry* e, int n, const char* data_directory, int max_img_width, int load_and_store, int* status);
+/* The entry with a lens (A LENS, above) in the place of dist: the same route, step 1 reading "a lens given: K NULL, a lens the checks refuse or an
+ * entry that also carries dist is L3D_ERR_INVALID, an active lens with K[1] != 0 (skew) L3D_ERR_UNSUPPORTED".  The image is resampled from the
+ * lens's source camera onto the entry's K, which the view keeps.  lens: NULL (then exactly the calls above), or one pointer per entry of which any
+ * may be NULL: that entry's own dist rule */
+int l3d_line3d_add_image_entry_lens(l3d_line3d* h, const l3d_image_entry* e, const l3d_lens* lens, const char* data_directory, int max_img_width, int load_and_store);
+int l3d_line3d_add_images_lens(l3d_line3d* h, const l3d_image_entry* e, const l3d_lens* const* lens, int n, const char* data_directory, int max_img_width,
+                               int load_and_store, int* status);
+int l3d_line3d_undistort_image_lens(l3d_line3d* h, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, const double* K,
+                                    const l3d_lens* lens, unsigned char* out, size_t out_row_stride);
 
 /* The add family for an image in DEVICE memory (l3d_device_image, above): the entry with a descriptor where l3d_image_entry has pixels or a file.  It
  * takes the ONE ROUTE above, with these words for its image:
@@ -1078,6 +1164,10 @@ int l3d_line3d_add_device_entry(l3d_line3d* h, const l3d_device_entry* e, const 
 int l3d_line3d_add_device_images(l3d_line3d* h, const l3d_device_entry* e, int n, const char* data_directory, int max_img_width, int load_and_store, int* status);
 int l3d_line3d_decode_jpeg_device(l3d_line3d* h, const unsigned char* bytes, size_t n, const l3d_device_image* out);
 int l3d_line3d_undistort_image_device(l3d_line3d* h, const l3d_device_image* in, const double* K, double k1, double k2, const l3d_device_image* out);
+/* the device entry with a lens: as l3d_line3d_add_image_entry_lens / l3d_line3d_add_images_lens */
+int l3d_line3d_add_device_entry_lens(l3d_line3d* h, const l3d_device_entry* e, const l3d_lens* lens, const char* data_directory, int max_img_width, int load_and_store);
+int l3d_line3d_add_device_images_lens(l3d_line3d* h, const l3d_device_entry* e, const l3d_lens* const* lens, int n, const char* data_directory, int max_img_width,
+                                      int load_and_store, int* status);
 
 /* The detector's stages on their own, exported for tests (tests/test_gpu_detect_stages.py): the same kernels with the same launch shapes
  * as l3d_detect_segments, results copied to caller-allocated arrays.  (N, M) = (ceil(0.8 new_width), ceil(0.8 new_height)) is the scaled image.

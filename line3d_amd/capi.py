@@ -188,6 +188,64 @@ class ImageEntry(C.Structure):
                 ("dist", C.c_void_p), ("link_ids", C.c_void_p), ("sims", C.c_void_p), ("n_links", C.c_int)]
 
 
+# l3d_lens (include/line3d_amd.h, "A LENS")
+LENS_BROWN, LENS_FISHEYE = 1, 2
+
+
+class Lens(C.Structure):
+    """l3d_lens: model, the source camera fx, fy, cx, cy (all zero: the output camera), k[8]"""
+    _fields_ = [("model", C.c_int), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("k", C.c_double * 8)]
+
+
+def lens(model, coeffs, camera=None):
+    """An l3d_lens.  model: LENS_BROWN / "brown" (coeffs k1 k2 p1 p2 k3 k4 k5 k6, OpenCV's order) or LENS_FISHEYE / "fisheye" (k1 k2 k3 k4); fewer
+    coefficients are filled up with zeros.  camera = (fx, fy, cx, cy) of the distorted image; None: the camera the image is undistorted onto.
+    What the library refuses (an unknown model number, values that are not finite, ...) is left to it; only the shapes are checked here."""
+    m = {"brown": LENS_BROWN, "fisheye": LENS_FISHEYE}.get(model.lower() if isinstance(model, str) else None, model)
+    if isinstance(m, str):
+        raise ValueError("lens model must be 'brown', 'fisheye' or a model number")
+    k = [float(v) for v in coeffs]
+    if len(k) > 8:
+        raise ValueError("a lens has at most 8 coefficients")
+    out = Lens()
+    out.model = int(m)
+    if camera is not None:
+        if len(camera) != 4:
+            raise ValueError("camera must be (fx, fy, cx, cy)")
+        out.fx, out.fy, out.cx, out.cy = (float(v) for v in camera)
+    for i, v in enumerate(k):
+        out.k[i] = v
+    return out
+
+
+def _lens_camera(lens_, camera):
+    """The camera entry (6 doubles) that goes with a lens: the output camera (4 numbers, or 6 of which the library wants k1 = k2 = 0); None: the
+    lens's own source camera"""
+    if camera is None:
+        if lens_.fx == 0.0 and lens_.fy == 0.0:
+            raise ValueError("a lens without a source camera needs camera = (fx, fy, cx, cy), the camera to undistort onto")
+        camera = (lens_.fx, lens_.fy, lens_.cx, lens_.cy)
+    if len(camera) not in (4, 6):
+        raise ValueError("camera must be (fx, fy, cx, cy) beside a lens")
+    return (C.c_double * 6)(*([float(v) for v in camera] + [0.0, 0.0])[:6])
+
+
+def lens_pointers(lenses, n):
+    """the `const l3d_lens* const*` argument of the ..._lens calls for a list with one Lens or None per entry (None: a null array), and what keeps it alive"""
+    if lenses is None or all(l is None for l in lenses):
+        return None, []
+    lenses = list(lenses)
+    if len(lenses) != n:
+        raise ValueError("lenses: %d entries for %d images" % (len(lenses), n))
+    arr = (C.c_void_p * max(1, n))()
+    for i, l in enumerate(lenses):
+        if l is not None:
+            if not isinstance(l, Lens):
+                raise TypeError("lens %d must come from capi.lens()" % i)
+            arr[i] = C.addressof(l)
+    return arr, lenses
+
+
 # dtype codes of l3d_device_image (L3D_U8 ...)
 U8, U16, F16, F32 = 0, 1, 2, 3
 _TYPESTR = {"|u1": U8, "<u2": U16, "<f2": F16, "<f4": F32}
@@ -304,11 +362,12 @@ def device_image_extent(d):
     return int(rc), int(lo.value), int(hi.value)
 
 
-def detect_device_entries(images, new_sizes=None, min_lengths=None, max_segments=3000, cameras=None):
+def detect_device_entries(images, new_sizes=None, min_lengths=None, max_segments=3000, cameras=None, lenses=None):
     """The l3d_detect_device_entry array of Context.detect_segments_batch for a list of device objects, and what keeps its pointers alive"""
     images = [device_image(im) for im in images]
     n = len(images)
     new_sizes, min_lengths, cameras = _per_image(new_sizes, n, "new_sizes"), _per_image(min_lengths, n, "min_lengths"), _per_image(cameras, n, "cameras")
+    lenses = _per_image(lenses, n, "lenses")
     caps = [int(max_segments)] * n if np.isscalar(max_segments) else [int(v) for v in _per_image(max_segments, n, "max_segments")]
     entries, keep = (DetectDeviceEntry * max(1, n))(), list(images)
     for i, im in enumerate(images):
@@ -318,7 +377,11 @@ def detect_device_entries(images, new_sizes=None, min_lengths=None, max_segments
         e.new_width, e.new_height = (w, h) if new_sizes[i] is None else (int(new_sizes[i][0]), int(new_sizes[i][1]))
         e.min_length = float(np.float32(0.005) * np.sqrt(np.float32(h * h + w * w))) if min_lengths[i] is None else float(min_lengths[i])
         e.max_segments = caps[i]
-        if cameras[i] is not None:
+        if lenses[i] is not None:
+            cam = _lens_camera(lenses[i], cameras[i])
+            keep.append(cam)
+            e.camera = C.addressof(cam)
+        elif cameras[i] is not None:
             if len(cameras[i]) != 6:
                 raise ValueError("camera must be (fx, fy, cx, cy, k1, k2)")
             cam = (C.c_double * 6)(*[float(v) for v in cameras[i]])
@@ -366,12 +429,13 @@ def _per_image(value, n, what):
     return value
 
 
-def detect_entries(images, new_sizes=None, min_lengths=None, max_segments=3000, cameras=None):
+def detect_entries(images, new_sizes=None, min_lengths=None, max_segments=3000, cameras=None, lenses=None):
     """The l3d_detect_entry array of Context.detect_segments_batch, and what keeps its pointers alive.  Everything malformed is refused here,
     before any device call: an image that is neither a uint8 array nor bytes, a camera that is not six numbers, lists of the wrong length."""
     images = list(images)
     n = len(images)
     new_sizes, min_lengths, cameras = _per_image(new_sizes, n, "new_sizes"), _per_image(min_lengths, n, "min_lengths"), _per_image(cameras, n, "cameras")
+    lenses = _per_image(lenses, n, "lenses")
     caps = [int(max_segments)] * n if np.isscalar(max_segments) else [int(v) for v in _per_image(max_segments, n, "max_segments")]
     entries, keep = (DetectEntry * max(1, n))(), []
     for i, img in enumerate(images):
@@ -392,7 +456,11 @@ def detect_entries(images, new_sizes=None, min_lengths=None, max_segments=3000, 
         e.new_width, e.new_height = (w, h) if new_sizes[i] is None else (int(new_sizes[i][0]), int(new_sizes[i][1]))
         e.min_length = float(np.float32(0.005) * np.sqrt(np.float32(h * h + w * w))) if min_lengths[i] is None else float(min_lengths[i])
         e.max_segments = caps[i]
-        if cameras[i] is not None:
+        if lenses[i] is not None:
+            cam = _lens_camera(lenses[i], cameras[i])
+            keep.append(cam)
+            e.camera = C.addressof(cam)
+        elif cameras[i] is not None:
             if len(cameras[i]) != 6:
                 raise ValueError("camera must be (fx, fy, cx, cy, k1, k2)")
             cam = (C.c_double * 6)(*[float(v) for v in cameras[i]])
@@ -497,12 +565,20 @@ class Context:
         self._chk(self.lib.l3d_register_segments(self.h, _p(segs), C.c_int(len(segs))))
 
     # -- line segment detection (l3d_detect.hip) --------------------------------------------------
-    def undistort(self, img, K, k1, k2):
+    def undistort(self, img, K, k1=None, k2=None, lens=None, in_place=False):
         """l3d_undistort_image: uint8 image H x W or H x W x 3 -> the undistorted image, same shape (initUndistortRectifyMap + remap of the drivers,
         the formulas of include/line3d_amd.h).  K: 3 x 3, its fx, fy, cx, cy are used; k1, k2: OpenCV-convention radial coefficients.
         A device object (device_image) stays on the device (l3d_undistort_image_device): the result is a torch uint8 tensor of the input's
-        shape on its device."""
+        shape on its device.
+        lens (capi.lens(...)) in the place of k1, k2: l3d_undistort_image[_device]_lens -- tangential, rational and fisheye models, resampled from
+        the lens's source camera onto K.  in_place (with a lens): a host array is overwritten and returned, a device object is its own output."""
         K = np.asarray(K, dtype=np.float64).reshape(3, 3)
+        if lens is not None:
+            if k1 is not None or k2 is not None:
+                raise ValueError("undistort takes k1, k2 or a lens, not both")
+            return self._undistort_lens(img, K, lens, in_place)
+        if k1 is None or k2 is None or in_place:
+            raise ValueError("undistort needs k1 and k2, or a lens (in_place goes with a lens)")
         if is_device_object(img):
             d = device_image(img)
             out, o = device_output_like(d, getattr(self, "device", 0))
@@ -516,13 +592,36 @@ class Context:
                                                C.c_size_t(w * ch)))
         return out
 
-    def detect_segments(self, img, new_size=None, min_length=None, max_segments=3000, camera=None):
+    def _undistort_lens(self, img, K, lens_, in_place):
+        cam = [C.c_double(K[0, 0]), C.c_double(K[1, 1]), C.c_double(K[0, 2]), C.c_double(K[1, 2])]
+        if is_device_object(img):
+            d = device_image(img)
+            out, o = (img, d) if in_place else device_output_like(d, getattr(self, "device", 0))
+            self._chk(self.lib.l3d_undistort_image_device_lens(self.h, C.byref(d), *cam, C.byref(lens_), C.byref(o)))
+            return out
+        if in_place:
+            a = np.asarray(img)
+            pix, w, h, ch, stride = image_arguments(a)
+            if pix._keep is not a:
+                raise ValueError("in_place needs an array whose pixels are contiguous within a row")
+            self._chk(self.lib.l3d_undistort_image_lens(self.h, pix, C.c_int(w), C.c_int(h), C.c_int(ch), C.c_size_t(stride), *cam, C.byref(lens_), pix, C.c_size_t(stride)))
+            return a
+        pix, w, h, ch, stride = image_arguments(img)
+        out = np.zeros(np.asarray(img).shape, np.uint8)
+        self._chk(self.lib.l3d_undistort_image_lens(self.h, pix, C.c_int(w), C.c_int(h), C.c_int(ch), C.c_size_t(stride), *cam, C.byref(lens_), _p(out), C.c_size_t(w * ch)))
+        return out
+
+    def detect_segments(self, img, new_size=None, min_length=None, max_segments=3000, camera=None, lens=None):
         """l3d_detect_segments: uint8 image H x W or H x W x 3 (contiguous pixels, rows contiguous or strided) -> (n, 4) float32 segments
         (x1, y1, x2, y2) in pixels of `img`, longest first.  new_size = (width, height) the detector works at (None: the image's own);
         min_length None: the reference's 0.005 x the image diagonal.  camera = (fx, fy, cx, cy, k1, k2): the image is undistorted on the device
         first (l3d_detect_segments_distorted) and the segments are in pixels of the undistorted image.
         A device object (a torch device tensor, anything with __cuda_array_interface__, a device_image descriptor) is read where it lies
-        (l3d_detect_segments_device): the segments are those of the host call on the converted pixels."""
+        (l3d_detect_segments_device): the segments are those of the host call on the converted pixels.
+        lens (capi.lens(...)): the image is undistorted with it first, onto camera = (fx, fy, cx, cy) (None: the lens's own source camera) -- a
+        batch of one through l3d_detect_segments[_device]_batch_lens."""
+        if lens is not None:
+            return self.detect_segments_batch([img], None if new_size is None else [new_size], None if min_length is None else [min_length], max_segments, [camera], lenses=[lens])[0]
         if is_device_object(img):
             d = device_image(img)
             w, h = d.width, d.height
@@ -575,8 +674,10 @@ class Context:
         self._chk(self.lib.l3d_decode_jpeg(self.h, ptr, n, _p(out), C.c_size_t(w * ch)))
         return out
 
-    def detect_segments_jpeg(self, data, new_size=None, min_length=None, max_segments=3000, camera=None):
+    def detect_segments_jpeg(self, data, new_size=None, min_length=None, max_segments=3000, camera=None, lens=None):
         """l3d_detect_segments_jpeg: detect_segments on the image of a baseline JPEG file, decoded on the device (arguments as detect_segments)"""
+        if lens is not None:
+            return self.detect_segments_batch([bytes(data)], None if new_size is None else [new_size], None if min_length is None else [min_length], max_segments, [camera], lenses=[lens])[0]
         w, h, _ = jpeg_info(data)
         ptr, n = _bytes_arguments(data)
         nw, nh = (w, h) if new_size is None else (int(new_size[0]), int(new_size[1]))
@@ -595,21 +696,28 @@ class Context:
         return segs
 
     # -- images in batches: one pass of the detector over many images ---------------------------------
-    def detect_segments_batch(self, images, new_sizes=None, min_lengths=None, max_segments=3000, cameras=None, return_status=False):
+    def detect_segments_batch(self, images, new_sizes=None, min_lengths=None, max_segments=3000, cameras=None, return_status=False, lenses=None):
         """l3d_detect_segments_batch: a list of images -- uint8 arrays (as detect_segments takes them) or `bytes` of baseline JPEG files (as
         detect_segments_jpeg takes them) -> a list of (n, 4) float32 arrays, each byte for byte what the single call gives for that image.
         new_sizes, min_lengths, max_segments, cameras: None, one value for all (max_segments), or a list with one entry (possibly None) per image,
         with the single calls' meanings and defaults.  An entry the single call would refuse raises L3DError (its .code the first such entry's
         status, .statuses all of them); return_status=True: no raise, the result is (segments, statuses).
         A list of device objects (as detect_segments takes them) goes through l3d_detect_segments_device_batch; a list that mixes them with
-        host images or files raises ValueError before any call."""
+        host images or files raises ValueError before any call.
+        lenses: None, or a list with one capi.lens(...) or None per image (l3d_detect_segments[_device]_batch_lens); an image with a lens is
+        undistorted onto its entry of cameras, (fx, fy, cx, cy) -- None: the lens's own source camera."""
         images = list(images)
         on_device = all_device_objects(images, "detect_segments_batch")
-        entries, keep = (detect_device_entries if on_device else detect_entries)(images, new_sizes, min_lengths, max_segments, cameras)
+        entries, keep = (detect_device_entries if on_device else detect_entries)(images, new_sizes, min_lengths, max_segments, cameras, lenses)
         n = len(images)
         out, offsets, status = C.POINTER(C.c_float)(), (C.c_int * (n + 1))(), (C.c_int * max(1, n))()
-        call = self.lib.l3d_detect_segments_device_batch if on_device else self.lib.l3d_detect_segments_batch
-        rc = call(self.h, entries, C.c_int(n), C.byref(out), offsets, status)
+        lens_arr, lens_keep = lens_pointers(lenses, n)
+        if lens_arr is not None:
+            call = self.lib.l3d_detect_segments_device_batch_lens if on_device else self.lib.l3d_detect_segments_batch_lens
+            rc = call(self.h, entries, lens_arr, C.c_int(n), C.byref(out), offsets, status)
+        else:
+            call = self.lib.l3d_detect_segments_device_batch if on_device else self.lib.l3d_detect_segments_batch
+            rc = call(self.h, entries, C.c_int(n), C.byref(out), offsets, status)
         statuses = [int(status[i]) for i in range(n)]
         segs = []
         if rc == 0:

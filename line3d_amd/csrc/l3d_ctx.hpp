@@ -139,7 +139,9 @@ struct FillPart { int h0 = 0, h1 = 0; unsigned long long pos_base = 0; const int
 struct DetectBufs {
     // undist: the undistorted image (k_det_undistort), reserved only when an image comes with distortion coefficients
     // a chunk of B images of one size (l3d_detect.hip) holds them one after the other in every per-pixel buffer; cimg, cimg2: the image of a packed
-    // candidate; prm: what varies between the images of a chunk (camera, length filter, cap)
+    // candidate; prm: what varies between the images of a chunk (camera, length filter, cap); lens: the chunk's lenses (k_det_undistort_lens), reserved
+    // only when an image comes with one
+    DevBuf lens;
     DevBuf pixels, undist, grey, aux, img, mod, ang, bucket, active, parent, size, count, keys, keys2, vals, vals2, flag, pos, start, tmp, cand, ckeys, ckeys2, cvals, cvals2, cimg, cimg2, prm, out, ktab, scal;
     // JPEG input (l3d_jpeg_device.hip), reserved only when a JPEG is decoded: the quantisation tables and the quantised coefficients as the host's entropy
     // decoder wrote them into the pinned `jstage`, and the uint8 component planes over whole MCUs
@@ -166,7 +168,7 @@ struct DetectBufs {
     }
     std::vector<DevBuf*> all()
     {
-        return { &pixels, &undist, &grey, &aux, &img, &mod, &ang, &bucket, &active, &parent, &size, &count, &keys, &keys2, &vals, &vals2, &flag, &pos, &start, &tmp, &cand, &ckeys, &ckeys2, &cvals, &cvals2, &cimg, &cimg2, &prm, &out, &ktab, &scal, &jcoef, &jplanes, &ingest };
+        return { &pixels, &undist, &grey, &aux, &img, &mod, &ang, &bucket, &active, &parent, &size, &count, &keys, &keys2, &vals, &vals2, &flag, &pos, &start, &tmp, &cand, &ckeys, &ckeys2, &cvals, &cvals2, &cimg, &cimg2, &prm, &out, &ktab, &scal, &jcoef, &jplanes, &ingest, &lens };
     }
 };
 

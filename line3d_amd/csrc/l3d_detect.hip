@@ -114,6 +114,59 @@ __global__ __launch_bounds__(256) void k_det_undistort(const unsigned char* __re
     }
 }
 
+// ---- undistortion with a lens (BROWN: radial, tangential, rational; FISHEYE) onto an output camera: "A LENS" in include/line3d_amd.h, every operation
+// in the order stated there.  The launch shape, the inside test and the taps are k_det_undistort's; that kernel is left as it is (its own copy of the
+// taps included) so that a chunk of k1, k2 cameras keeps its instruction stream.  The lens comes per image from the chunk's table: blockIdx.z is the
+// image, so the load is scalar and the branch on the model is uniform across a block.  tab: the chunk's lenses (model 0: the image is copied); a
+// single image comes with a table of one (a choice between the table and a by-value argument made the compiler read the lens with per-lane loads)
+__global__ __launch_bounds__(256) void k_det_undistort_lens(const unsigned char* __restrict__ src, int w, int h, int ch, const DetLens* __restrict__ tab,
+                                                             unsigned char* __restrict__ dst)
+{
+    const int j = blockIdx.x * kUndBx + threadIdx.x, i = blockIdx.y * kUndBy + threadIdx.y;
+    if (j >= w || i >= h) return;
+    src += (size_t)blockIdx.z * w * h * ch;
+    dst += (size_t)blockIdx.z * w * h * ch;
+    const DetLens L = tab[blockIdx.z];
+    unsigned char* o = dst + ((size_t)i * w + j) * ch;
+    if (L.model == 0) {
+        const unsigned char* s = src + ((size_t)i * w + j) * ch;
+        for (int k = 0; k < ch; ++k) o[k] = s[k];
+        return;
+    }
+    const double x = ((double)j - L.ocx) / L.ofx, y = ((double)i - L.ocy) / L.ofy;
+    const double r2 = x * x + y * y;
+    double xd, yd;
+    if (L.model == L3D_LENS_BROWN) {
+        const double k1 = L.k[0], k2 = L.k[1], p1 = L.k[2], p2 = L.k[3], k3 = L.k[4], k4 = L.k[5], k5 = L.k[6], k6 = L.k[7];
+        const double num = 1.0 + ((k3 * r2 + k2) * r2 + k1) * r2, den = 1.0 + ((k6 * r2 + k5) * r2 + k4) * r2;
+        const double kr = num / den;
+        xd = x * kr + ((2.0 * p1) * x * y + p2 * (r2 + 2.0 * (x * x)));
+        yd = y * kr + (p1 * (r2 + 2.0 * (y * y)) + (2.0 * p2) * x * y);
+    } else {
+        const double r = __builtin_sqrt(r2), th = atan(r), t2 = th * th;
+        const double td = th * (1.0 + (((L.k[3] * t2 + L.k[2]) * t2 + L.k[1]) * t2 + L.k[0]) * t2);
+        const double s = r > 1e-8 ? td / r : 1.0;
+        xd = x * s; yd = y * s;
+    }
+    const double u = L.fx * xd + L.cx, v = L.fy * yd + L.cy;
+    if (!(u > -1.0 && u < (double)w && v > -1.0 && v < (double)h)) {         // NaN and inf land here; tested before any conversion to an integer
+        for (int k = 0; k < ch; ++k) o[k] = 0;
+        return;
+    }
+    const int iu = (int)rint(32.0 * u), iv = (int)rint(32.0 * v);             // in [-32, 32 w] x [-32, 32 h]
+    const int x0 = iu >> 5, a = iu & 31, y0 = iv >> 5, b = iv & 31;
+    const bool cx0 = x0 >= 0 && x0 < w, cx1 = x0 + 1 >= 0 && x0 + 1 < w, ry0 = y0 >= 0 && y0 < h, ry1 = y0 + 1 >= 0 && y0 + 1 < h;
+    const int w00 = (32 - a) * (32 - b), w01 = a * (32 - b), w10 = (32 - a) * b, w11 = a * b;
+    const unsigned char* r0 = src + (size_t)(ry0 ? y0 : 0) * w * ch;           // (an index that is off the image is never formed: row and column 0 stand in)
+    const unsigned char* r1 = src + (size_t)(ry1 ? y0 + 1 : 0) * w * ch;
+    const size_t c0 = (size_t)(cx0 ? x0 : 0) * ch, c1 = (size_t)(cx1 ? x0 + 1 : 0) * ch;
+    for (int k = 0; k < ch; ++k) {
+        const int p00 = ry0 && cx0 ? r0[c0 + k] : 0, p01 = ry0 && cx1 ? r0[c1 + k] : 0;
+        const int p10 = ry1 && cx0 ? r1[c0 + k] : 0, p11 = ry1 && cx1 ? r1[c1 + k] : 0;
+        o[k] = (unsigned char)((w00 * p00 + w01 * p01 + w10 * p10 + w11 * p11 + 512) >> 10);
+    }
+}
+
 // ---- Gaussian sub-sampling, separable, 7 taps; centres and weights per output column / row come from the host (computed as the
 // detector computes them); symmetric boundary
 __device__ inline int sym_index(int j, int n)
@@ -678,6 +731,27 @@ void launch_undistort(l3d_ctx* c, int w, int h, int ch, int B, const DetCamera& 
                        d.undist.as<unsigned char>());
 }
 
+// the same with lenses: the B entries of `tab` (host; it has to live until the stream has been synchronised) go to d.lens, one launch follows
+int launch_undistort_lens(l3d_ctx* c, int w, int h, int ch, int B, const DetLens* tab)
+{
+    DetectBufs& d = c->det;
+    HIPCHK(c, d.lens.reserve((size_t)B * sizeof(DetLens)));
+    HIPCHK(c, hipMemcpyAsync(d.lens.p, tab, (size_t)B * sizeof(DetLens), hipMemcpyHostToDevice, c->stream));
+    ProfScope ps(c, "k_det_undistort_lens");
+    hipLaunchKernelGGL(k_det_undistort_lens, dim3((w + kUndBx - 1) / kUndBx, (h + kUndBy - 1) / kUndBy, B), dim3(kUndBx, kUndBy), 0, c->stream, d.pixels.as<unsigned char>(), w, h,
+                       ch, d.lens.as<DetLens>(), d.undist.as<unsigned char>());
+    return L3D_OK;
+}
+// a k1, k2 camera as the lens that performs its operations (BROWN, the cameras equal): the place of such an image in a chunk that has lenses
+DetLens lens_of_camera(const DetCamera& cam)
+{
+    DetLens l{};
+    l.model = L3D_LENS_BROWN;
+    l.fx = l.ofx = cam.fx; l.fy = l.ofy = cam.fy; l.cx = l.ocx = cam.cx; l.cy = l.ocy = cam.cy;
+    l.k[0] = cam.k1; l.k[1] = cam.k2;
+    return l;
+}
+
 // image b of the chunk: host pixels into its slot of d.pixels
 hipError_t det_upload(l3d_ctx* c, const DetPlan& p, int b, const unsigned char* pixels, size_t stride)
 {
@@ -685,9 +759,10 @@ hipError_t det_upload(l3d_ctx* c, const DetPlan& p, int b, const unsigned char* 
     return hipMemcpy2DAsync(c->det.pixels.as<unsigned char>() + (size_t)b * row * p.h, row, pixels, stride, row, (size_t)p.h, hipMemcpyHostToDevice, c->stream);
 }
 
-// ---- pixel stage on the chunk's images in d.pixels (uploaded, or decoded JPEG): undistortion (undist: some image has a camera, d.prm says which),
+// ---- pixel stage on the chunk's images in d.pixels (uploaded, or decoded JPEG): undistortion (undist: some image has a camera, d.prm says which;
+// lens_tab: some image has a lens, and this table on the host holds every image's -- then k_det_undistort_lens runs in place of k_det_undistort),
 // rescale + grey, the two sampler passes, gradient -- one launch each, the image in blockIdx.z; leaves the scalars zeroed
-int det_pixel_stage(l3d_ctx* c, const DetPlan& p, bool undist = false)
+int det_pixel_stage(l3d_ctx* c, const DetPlan& p, bool undist = false, const DetLens* lens_tab = nullptr)
 {
     hipStream_t st = c->stream;
     DetectBufs& d = c->det;
@@ -708,7 +783,8 @@ int det_pixel_stage(l3d_ctx* c, const DetPlan& p, bool undist = false)
     const int* kc = reinterpret_cast<const int*>(static_cast<const char*>(d.ktab.p) + ((size_t)N + M) * kTaps * 8);
     const dim3 b256(256);
     const unsigned char* image = d.pixels.as<unsigned char>();          // whichever buffer holds the images k_det_grey reads
-    if (undist) { launch_undistort(c, w, h, ch, B, DetCamera{ 1.0, 1.0, 0.0, 0.0, 0.0, 0.0 }, d.prm.as<DetImgParam>()); image = d.undist.as<unsigned char>(); }
+    if (lens_tab) { if (int rc = launch_undistort_lens(c, w, h, ch, B, lens_tab)) return rc; image = d.undist.as<unsigned char>(); }
+    else if (undist) { launch_undistort(c, w, h, ch, B, DetCamera{ 1.0, 1.0, 0.0, 0.0, 0.0, 0.0 }, d.prm.as<DetImgParam>()); image = d.undist.as<unsigned char>(); }
     { ProfScope ps(c, "k_det_grey"); hipLaunchKernelGGL(k_det_grey, dim3((nw + 255) / 256, nh, B), b256, 0, st, image, w, h, ch, nw, nh, d.grey.as<float>()); }
     { ProfScope ps(c, "k_det_gauss_x"); hipLaunchKernelGGL(k_det_gauss_x, dim3((N + 63) / 64, (nh + 3) / 4, B), dim3(64, 4), 0, st, d.grey.as<float>(), nw, nh, d.aux.as<double>(), N, kc, kw); }
     { ProfScope ps(c, "k_det_gauss_y"); hipLaunchKernelGGL(k_det_gauss_y, dim3((N + 63) / 64, (M + kYRows - 1) / kYRows, B), dim3(64, 4), 0, st, d.aux.as<double>(), N, nh, d.img.as<double>(), M, kc + N, kw + (size_t)N * kTaps); }
@@ -796,6 +872,8 @@ struct DetItem {
     const JpegStaged* jpeg = nullptr;
     const l3d_device_image* dev = nullptr;      // an image in device memory (pixels and jpeg null), checked by device_image_pointer
     DetImgParam prm;
+    bool lens_on = false;                       // the image has an active lens (then prm.cam_on is 0)
+    DetLens lens;
     std::vector<float>* out = nullptr;
 };
 
@@ -806,12 +884,13 @@ int detect_chunk(l3d_ctx* c, const DetPlan& p, const DetItem* items)
     hipStream_t st = c->stream;
     DetectBufs& d = c->det;
     const int B = p.B, cand_cap = p.cand_cap;
-    bool undist = false, jpeg = false, dev = false;
+    bool undist = false, lens = false, jpeg = false, dev = false;
     size_t out_slots = 0;
     std::vector<DetImgParam> prm((size_t)B);
     for (int b = 0; b < B; ++b) {
         prm[b] = items[b].prm;
-        undist = undist || prm[b].cam_on;
+        undist = undist || prm[b].cam_on || items[b].lens_on;
+        lens = lens || items[b].lens_on;
         jpeg = jpeg || (!items[b].pixels && !items[b].dev);
         dev = dev || items[b].dev;
         out_slots += (size_t)std::min(prm[b].max_segments, cand_cap);
@@ -830,7 +909,13 @@ int detect_chunk(l3d_ctx* c, const DetPlan& p, const DetItem* items)
     for (int b = 0; b < B; ++b) if (items[b].pixels) HIPCHK(c, det_upload(c, p, b, items[b].pixels, items[b].stride));
     // (from pageable memory on purpose: a few dozen bytes go faster through the runtime's staging than as a DMA from pinned memory -- measured, 0.03 ms per call)
     HIPCHK(c, hipMemcpyAsync(d.prm.p, prm.data(), (size_t)B * sizeof(DetImgParam), hipMemcpyHostToDevice, st));
-    if (int rc = det_pixel_stage(c, p, undist)) return rc;
+    // a chunk in which every camera is of the k1, k2 kind keeps k_det_undistort; one lens, and the chunk's table goes to k_det_undistort_lens
+    std::vector<DetLens> lens_tab;
+    if (lens) {
+        lens_tab.assign((size_t)B, DetLens{});
+        for (int b = 0; b < B; ++b) lens_tab[b] = items[b].lens_on ? items[b].lens : prm[b].cam_on ? lens_of_camera(prm[b].cam) : DetLens{};
+    }
+    if (int rc = det_pixel_stage(c, p, undist, lens ? lens_tab.data() : nullptr)) return rc;
 
     // ---- rounds: label, vote, sort, regions
     for (int round = 0; round < kRounds; ++round) {
@@ -909,7 +994,7 @@ int detect_segments_batch(l3d_ctx* c, const DetEntry* e, int n, std::vector<std:
     if (!c) return L3D_ERR_INVALID;
     if (n < 0 || (n > 0 && !e)) return fail(c, L3D_ERR_INVALID, "detect_segments_batch: null argument");
     // ---- per entry, in order, on the caller's thread: headers, plan, camera.  An entry refused here fails alone
-    struct Work { DetPlan plan; DetImgParam prm; JpegStaged file; bool todo = false, done = false; };
+    struct Work { DetPlan plan; DetImgParam prm; DetLens lens; JpegStaged file; bool lens_on = false, todo = false, done = false; };
     std::vector<Work> work((size_t)n);
     std::vector<JpegFrame> frames((size_t)n);
     for (int i = 0; i < n; ++i) {
@@ -930,7 +1015,9 @@ int detect_segments_batch(l3d_ctx* c, const DetEntry* e, int n, std::vector<std:
         if (en.max_segments < 0) { status[i] = L3D_ERR_INVALID; message[i] = "detect_segments: negative max_segments"; continue; }
         if ((status[i] = plan_image(k.plan, en.pixels != nullptr || en.jpeg != nullptr || dev, w, h, ch, stride, en.new_width, en.new_height, message[i])) != L3D_OK) continue;
         bool undist = false;
+        if (en.cam && en.lens) { status[i] = L3D_ERR_INVALID; message[i] = "undistort: an image carries both distortion coefficients (k1, k2) and a lens"; continue; }
         if (en.cam) { if ((status[i] = check_camera(*en.cam, w, h, &undist, message[i])) != L3D_OK) continue; }
+        if (en.lens) { k.lens = *en.lens; if ((status[i] = lens_check(k.lens, w, h, &k.lens_on, message[i])) != L3D_OK) continue; }
         k.prm.cam = undist ? *en.cam : DetCamera{ 1.0, 1.0, 0.0, 0.0, 0.0, 0.0 };
         k.prm.cam_on = undist; k.prm.min_length = en.min_length; k.prm.max_segments = en.max_segments; k.prm.pad = 0;
         k.todo = true;
@@ -946,7 +1033,7 @@ int detect_segments_batch(l3d_ctx* c, const DetEntry* e, int n, std::vector<std:
         for (int i = first; i < n; ++i)
             if (work[i].todo && work[i].plan.same_group(work[first].plan)) {
                 group.push_back(i); work[i].todo = false;
-                undist = undist || work[i].prm.cam_on;
+                undist = undist || work[i].prm.cam_on || work[i].lens_on;
                 if (work[i].file.f) blocks = std::max(blocks, work[i].file.f->n_blocks);
             }
         const int per = chunk_images(c, work[first].plan, (int)group.size(), undist, blocks);
@@ -968,7 +1055,7 @@ int detect_segments_batch(l3d_ctx* c, const DetEntry* e, int n, std::vector<std:
                     if ((status[i] = device_image_pointer(c, *e[i].dev, message[i])) != L3D_OK) continue;
                     it.dev = e[i].dev;
                 }
-                it.pixels = k.file.f ? nullptr : e[i].pixels; it.stride = e[i].row_stride; it.jpeg = k.file.f ? &k.file : nullptr; it.prm = k.prm; it.out = &out[i];
+                it.pixels = k.file.f ? nullptr : e[i].pixels; it.stride = e[i].row_stride; it.jpeg = k.file.f ? &k.file : nullptr; it.prm = k.prm; it.lens_on = k.lens_on; it.lens = k.lens; it.out = &out[i];
                 items.push_back(it);
                 entry.push_back(i);
             }
@@ -1001,47 +1088,54 @@ static int detect_one(l3d_ctx* c, const DetEntry& en, std::vector<float>& out)
 }
 
 int detect_segments(l3d_ctx* c, const unsigned char* pixels, int w, int h, int ch, size_t stride, int nw, int nh, float min_length, int max_segments,
-                    std::vector<float>& out, const DetCamera* cam)
+                    std::vector<float>& out, const DetCamera* cam, const DetLens* lens)
 {
     out.clear();
     if (!c) return L3D_ERR_INVALID;
     DetEntry en;
+    en.lens = lens;
     en.pixels = pixels; en.width = w; en.height = h; en.channels = ch; en.row_stride = stride;
     en.new_width = nw; en.new_height = nh; en.min_length = min_length; en.max_segments = max_segments; en.cam = cam;
     return detect_one(c, en, out);
 }
 
 int detect_segments_jpeg(l3d_ctx* c, const unsigned char* bytes, size_t n, int nw, int nh, float min_length, int max_segments, std::vector<float>& out,
-                         const DetCamera* cam)
+                         const DetCamera* cam, const DetLens* lens)
 {
     out.clear();
     if (!c) return L3D_ERR_INVALID;
     if (!bytes) return fail(c, L3D_ERR_INVALID, "detect_segments_jpeg: null argument");
     DetEntry en;
+    en.lens = lens;
     en.jpeg = bytes; en.jpeg_bytes = n;
     en.new_width = nw; en.new_height = nh; en.min_length = min_length; en.max_segments = max_segments; en.cam = cam;
     return detect_one(c, en, out);
 }
 
-int detect_segments_device(l3d_ctx* c, const l3d_device_image& image, int nw, int nh, float min_length, int max_segments, std::vector<float>& out, const DetCamera* cam)
+int detect_segments_device(l3d_ctx* c, const l3d_device_image& image, int nw, int nh, float min_length, int max_segments, std::vector<float>& out, const DetCamera* cam,
+                           const DetLens* lens)
 {
     out.clear();
     if (!c) return L3D_ERR_INVALID;
     DetEntry en;
+    en.lens = lens;
     en.dev = &image;
     en.new_width = nw; en.new_height = nh; en.min_length = min_length; en.max_segments = max_segments; en.cam = cam;
     return detect_one(c, en, out);
 }
 
 // host in, host out: upload, k_det_undistort, download (the detector's two image buffers)
-int undistort_image(l3d_ctx* c, const unsigned char* pixels, int w, int h, int ch, size_t stride, const DetCamera& cam, unsigned char* out, size_t out_stride)
+int undistort_image(l3d_ctx* c, const unsigned char* pixels, int w, int h, int ch, size_t stride, const DetCamera& cam, unsigned char* out, size_t out_stride,
+                    const DetLens* lens)
 {
     if (!c) return L3D_ERR_INVALID;
     if (!pixels || !out || w < 1 || h < 1 || (ch != 1 && ch != 3) || stride < (size_t)w * ch || out_stride < (size_t)w * ch)
         return fail(c, L3D_ERR_INVALID, "undistort: needs an image of at least 1x1 with 1 or 3 channels and row strides of at least width x channels");
     if ((long long)w * h * ch > (1ll << 31)) return fail(c, L3D_ERR_UNSUPPORTED, "undistort: image too large");
     bool active = false;
-    { std::string err; if (int rc = check_camera(cam, w, h, &active, err)) return fail(c, rc, err); }
+    DetLens L{};
+    if (lens) L = *lens;
+    { std::string err; if (int rc = lens ? lens_check(L, w, h, &active, err) : check_camera(cam, w, h, &active, err)) return fail(c, rc, err); }
     const size_t row = (size_t)w * ch;
     if (!active) {
         if (out != pixels || out_stride != stride)
@@ -1053,14 +1147,15 @@ int undistort_image(l3d_ctx* c, const unsigned char* pixels, int w, int h, int c
     HIPCHK(c, d.pixels.reserve(row * h));
     HIPCHK(c, d.undist.reserve(row * h));
     HIPCHK(c, hipMemcpy2DAsync(d.pixels.p, row, pixels, stride, row, (size_t)h, hipMemcpyHostToDevice, c->stream));
-    launch_undistort(c, w, h, ch, 1, cam, nullptr);
+    if (lens) { if (int rc = launch_undistort_lens(c, w, h, ch, 1, &L)) return rc; }
+    else launch_undistort(c, w, h, ch, 1, cam, nullptr);
     HIPCHK(c, hipMemcpy2DAsync(out, out_stride, d.undist.p, row, row, (size_t)h, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return L3D_OK;
 }
 
 // device in, device out (which may be the same memory): ingest, k_det_undistort, egress -- the ingest is complete before the egress starts
-int undistort_image_device(l3d_ctx* c, const l3d_device_image& in, const DetCamera& cam, const l3d_device_image& out)
+int undistort_image_device(l3d_ctx* c, const l3d_device_image& in, const DetCamera& cam, const l3d_device_image& out, const DetLens* lens)
 {
     std::string err;
     if (int rc = device_image_check(in, err)) return fail(c, rc, err);
@@ -1070,7 +1165,9 @@ int undistort_image_device(l3d_ctx* c, const l3d_device_image& in, const DetCame
         return fail(c, L3D_ERR_INVALID, "undistort: the output's size and channels must be the input's");
     if ((long long)w * h * ch > (1ll << 31)) return fail(c, L3D_ERR_UNSUPPORTED, "undistort: image too large");
     bool active = false;
-    if (int rc = check_camera(cam, w, h, &active, err)) return fail(c, rc, err);
+    DetLens L{};
+    if (lens) L = *lens;
+    if (int rc = lens ? lens_check(L, w, h, &active, err) : check_camera(cam, w, h, &active, err)) return fail(c, rc, err);
     if (int rc = device_image_pointer(c, in, err)) return fail(c, rc, err);
     if (int rc = device_image_pointer(c, out, err)) return fail(c, rc, err);
     HIPCHK(c, hipSetDevice(c->device));
@@ -1080,9 +1177,40 @@ int undistort_image_device(l3d_ctx* c, const l3d_device_image& in, const DetCame
     if (active) HIPCHK(c, d.undist.reserve(bytes));
     const l3d_device_image* one[1] = { &in };
     if (int rc = device_ingest(c, one, 1, w, h, ch, d.pixels.as<unsigned char>())) return rc;
-    if (active) launch_undistort(c, w, h, ch, 1, cam, nullptr);
+    if (active && lens) { if (int rc = launch_undistort_lens(c, w, h, ch, 1, &L)) return rc; }
+    else if (active) launch_undistort(c, w, h, ch, 1, cam, nullptr);
     if (int rc = device_egress(c, active ? d.undist.as<unsigned char>() : d.pixels.as<unsigned char>(), out)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return L3D_OK;
+}
+
+DetLens make_lens(const l3d_lens& lens, double ofx, double ofy, double ocx, double ocy)
+{
+    DetLens l{};
+    l.model = lens.model;
+    l.fx = lens.fx; l.fy = lens.fy; l.cx = lens.cx; l.cy = lens.cy;
+    l.ofx = ofx; l.ofy = ofy; l.ocx = ocx; l.ocy = ocy;
+    for (int k = 0; k < 8; ++k) l.k[k] = lens.k[k];
+    return l;
+}
+
+int lens_check(DetLens& l, int w, int h, bool* active, std::string& err)
+{
+    *active = false;
+    if (w > (1 << 24) || h > (1 << 24)) { err = "undistort: image too large"; return L3D_ERR_UNSUPPORTED; }      // 32 x a coordinate stays an int
+    if (l.model != L3D_LENS_BROWN && l.model != L3D_LENS_FISHEYE) { err = "lens: unknown model " + std::to_string(l.model) + " (L3D_LENS_BROWN or L3D_LENS_FISHEYE)"; return L3D_ERR_INVALID; }
+    bool finite = std::isfinite(l.fx) && std::isfinite(l.fy) && std::isfinite(l.cx) && std::isfinite(l.cy);
+    for (int k = 0; k < 8; ++k) finite = finite && std::isfinite(l.k[k]);
+    if (!finite) { err = "lens: a field is not finite"; return L3D_ERR_INVALID; }
+    if ((l.fx == 0.0) != (l.fy == 0.0)) { err = "lens: exactly one of fx, fy is zero (both zero: the output camera)"; return L3D_ERR_INVALID; }
+    if (l.model == L3D_LENS_FISHEYE && (l.k[4] != 0.0 || l.k[5] != 0.0 || l.k[6] != 0.0 || l.k[7] != 0.0)) { err = "lens: a fisheye lens has four coefficients, k[4..7] must be 0"; return L3D_ERR_INVALID; }
+    if (!std::isfinite(l.ofx) || !std::isfinite(l.ofy) || !std::isfinite(l.ocx) || !std::isfinite(l.ocy) || l.ofx == 0.0 || l.ofy == 0.0) {
+        err = "undistort: fx and fy must be finite and not zero"; return L3D_ERR_INVALID;
+    }
+    if (l.fx == 0.0) { l.fx = l.ofx; l.fy = l.ofy; l.cx = l.ocx; l.cy = l.ocy; }
+    bool small = true;
+    for (int k = 0; k < 8; ++k) small = small && fabs(l.k[k]) <= kDistEps;
+    *active = l.model == L3D_LENS_FISHEYE || !small || l.fx != l.ofx || l.fy != l.ofy || l.cx != l.ocx || l.cy != l.ocy;
     return L3D_OK;
 }
 
@@ -1093,6 +1221,23 @@ int l3d_undistort_image_device(l3d_ctx* c, const l3d_device_image* in, double fx
     if (!c) return L3D_ERR_INVALID;
     if (!in || !out) return l3d::fail(c, L3D_ERR_INVALID, "undistort: null argument");
     return l3d::undistort_image_device(c, *in, l3d::DetCamera{ fx, fy, cx, cy, k1, k2 }, *out);
+}
+
+int l3d_undistort_image_device_lens(l3d_ctx* c, const l3d_device_image* in, double fx, double fy, double cx, double cy, const l3d_lens* lens, const l3d_device_image* out)
+{
+    if (!c) return L3D_ERR_INVALID;
+    if (!in || !out || !lens) return l3d::fail(c, L3D_ERR_INVALID, "undistort: null argument");
+    const l3d::DetLens l = l3d::make_lens(*lens, fx, fy, cx, cy);
+    return l3d::undistort_image_device(c, *in, l3d::DetCamera{ fx, fy, cx, cy, 0.0, 0.0 }, *out, &l);
+}
+
+int l3d_undistort_image_lens(l3d_ctx* c, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, double fx, double fy, double cx, double cy,
+                             const l3d_lens* lens, unsigned char* out, size_t out_row_stride)
+{
+    if (!c) return L3D_ERR_INVALID;
+    if (!lens) return l3d::fail(c, L3D_ERR_INVALID, "undistort: null argument");
+    const l3d::DetLens l = l3d::make_lens(*lens, fx, fy, cx, cy);
+    return l3d::undistort_image(c, pixels, width, height, channels, row_stride, l3d::DetCamera{ fx, fy, cx, cy, 0.0, 0.0 }, out, out_row_stride, &l);
 }
 
 int l3d_undistort_image(l3d_ctx* c, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, double fx, double fy, double cx, double cy,
@@ -1151,20 +1296,37 @@ int l3d_detect_segments_jpeg(l3d_ctx* c, const unsigned char* bytes, size_t n, i
 
 static int batch_to_c(l3d_ctx* c, const std::vector<l3d::DetEntry>& entries, float** segments, int* offsets, int* status);
 
-int l3d_detect_segments_batch(l3d_ctx* c, const l3d_detect_entry* e, int n, float** segments, int* offsets, int* status)
+// the camera and the lens of a batch entry: `camera` alone is the k1, k2 camera; with a lens it is the output camera, and coefficients beside the lens
+// leave both set, which the batch refuses for that entry ("both ... and a lens"); a lens without a camera has no output camera: fx' = fy' = 0, refused as well
+static void entry_camera(const double* k, const l3d_lens* lens, l3d::DetCamera& cam, l3d::DetLens& dl, l3d::DetEntry& d)
+{
+    if (k) cam = l3d::DetCamera{ k[0], k[1], k[2], k[3], k[4], k[5] };
+    if (!lens) { if (k) d.cam = &cam; return; }
+    if (!k) { dl = l3d::make_lens(*lens, 0.0, 0.0, 0.0, 0.0); d.lens = &dl; return; }
+    dl = l3d::make_lens(*lens, k[0], k[1], k[2], k[3]);
+    d.lens = &dl;
+    if (k[4] != 0.0 || k[5] != 0.0) d.cam = &cam;
+}
+
+int l3d_detect_segments_batch_lens(l3d_ctx* c, const l3d_detect_entry* e, const l3d_lens* const* lens, int n, float** segments, int* offsets, int* status)
 {
     if (!c || !segments || !offsets || !status || n < 0 || (n > 0 && !e)) return L3D_ERR_INVALID;
     *segments = nullptr;
     std::vector<l3d::DetEntry> entries((size_t)n);
     std::vector<l3d::DetCamera> cams((size_t)n);
+    std::vector<l3d::DetLens> lenses((size_t)n);
     for (int i = 0; i < n; ++i) {
         l3d::DetEntry& d = entries[i];
         d.pixels = e[i].pixels; d.width = e[i].width; d.height = e[i].height; d.channels = e[i].channels; d.row_stride = e[i].row_stride;
         d.jpeg = e[i].jpeg; d.jpeg_bytes = e[i].jpeg_bytes;
         d.new_width = e[i].new_width; d.new_height = e[i].new_height; d.min_length = e[i].min_length; d.max_segments = e[i].max_segments;
-        if (const double* k = e[i].camera) { cams[i] = l3d::DetCamera{ k[0], k[1], k[2], k[3], k[4], k[5] }; d.cam = &cams[i]; }
+        entry_camera(e[i].camera, lens ? lens[i] : nullptr, cams[i], lenses[i], d);
     }
     return batch_to_c(c, entries, segments, offsets, status);
+}
+int l3d_detect_segments_batch(l3d_ctx* c, const l3d_detect_entry* e, int n, float** segments, int* offsets, int* status)
+{
+    return l3d_detect_segments_batch_lens(c, e, nullptr, n, segments, offsets, status);
 }
 
 int l3d_detect_segments_device(l3d_ctx* c, const l3d_device_image* image, int new_width, int new_height, float min_length, int max_segments, const double* camera,
@@ -1181,19 +1343,24 @@ int l3d_detect_segments_device(l3d_ctx* c, const l3d_device_image* image, int ne
     return rc != L3D_OK ? rc : segments_to_c(c, out, segments, n);
 }
 
-int l3d_detect_segments_device_batch(l3d_ctx* c, const l3d_detect_device_entry* e, int n, float** segments, int* offsets, int* status)
+int l3d_detect_segments_device_batch_lens(l3d_ctx* c, const l3d_detect_device_entry* e, const l3d_lens* const* lens, int n, float** segments, int* offsets, int* status)
 {
     if (!c || !segments || !offsets || !status || n < 0 || (n > 0 && !e)) return L3D_ERR_INVALID;
     *segments = nullptr;
     std::vector<l3d::DetEntry> entries((size_t)n);
     std::vector<l3d::DetCamera> cams((size_t)n);
+    std::vector<l3d::DetLens> lenses((size_t)n);
     for (int i = 0; i < n; ++i) {
         l3d::DetEntry& d = entries[i];
         d.dev = &e[i].image;
         d.new_width = e[i].new_width; d.new_height = e[i].new_height; d.min_length = e[i].min_length; d.max_segments = e[i].max_segments;
-        if (const double* k = e[i].camera) { cams[i] = l3d::DetCamera{ k[0], k[1], k[2], k[3], k[4], k[5] }; d.cam = &cams[i]; }
+        entry_camera(e[i].camera, lens ? lens[i] : nullptr, cams[i], lenses[i], d);
     }
     return batch_to_c(c, entries, segments, offsets, status);
+}
+int l3d_detect_segments_device_batch(l3d_ctx* c, const l3d_detect_device_entry* e, int n, float** segments, int* offsets, int* status)
+{
+    return l3d_detect_segments_device_batch_lens(c, e, nullptr, n, segments, offsets, status);
 }
 
 // the batch detector's outcome as the C ABI hands it out: the segments of all entries one after the other, one line per failed entry

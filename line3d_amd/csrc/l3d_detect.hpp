@@ -8,6 +8,7 @@
 
 struct l3d_ctx;
 struct l3d_device_image;
+struct l3d_lens;
 
 namespace l3d {
 
@@ -27,11 +28,18 @@ int device_egress(l3d_ctx* c, const unsigned char* src, const l3d_device_image& 
 
 // the camera of an undistortion (include/line3d_amd.h): focal lengths, principal point, OpenCV-convention radial coefficients
 struct DetCamera { double fx, fy, cx, cy, k1, k2; };
+// a lens (include/line3d_amd.h, "A LENS": l3d_lens) together with the output camera it is resampled onto; model 0 in a chunk's table: no camera, the
+// image is copied.  As make_lens leaves it the source camera may still be zero ("the output camera"); lens_check resolves that
+struct DetLens { int model, pad; double fx, fy, cx, cy, ofx, ofy, ocx, ocy, k[8]; };
+DetLens make_lens(const l3d_lens& lens, double ofx, double ofy, double ocx, double ocy);
+// the refusals of the header (no device): L3D_OK with the source camera resolved and *active set (false: the pixels pass through), or the code with
+// the cause in err
+int lens_check(DetLens& lens, int width, int height, bool* active, std::string& err);
 
 // pixels: host, `channels` (1 or 3) interleaved bytes per pixel, rows `row_stride` bytes apart.  out: 4 floats per segment.
 int detect_segments(l3d_ctx* c, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, int new_width, int new_height,
-                    float min_length, int max_segments, std::vector<float>& out, const DetCamera* cam = nullptr);
-// cam: null = the pixels as they are; otherwise they are undistorted on the device between the upload and the rescale
+                    float min_length, int max_segments, std::vector<float>& out, const DetCamera* cam = nullptr, const DetLens* lens = nullptr);
+// cam, lens: both null = the pixels as they are; otherwise they are undistorted on the device between the upload and the rescale (both given: refused)
 
 // ---- many images in one call.  An entry is host pixels, or (pixels null) a baseline JPEG file; cam as above
 struct DetEntry {
@@ -44,6 +52,7 @@ struct DetEntry {
     float min_length = 0.0f;
     int max_segments = 0;
     const DetCamera* cam = nullptr;
+    const DetLens* lens = nullptr;              // as make_lens gives it; checked per entry (lens_check)
     const l3d_device_image* dev = nullptr;      // a third source (pixels and jpeg null): an image in device memory (l3d_device_image.hip)
 };
 // out[i]: the segments detect_segments / detect_segments_jpeg gives for entry i alone, byte for byte.  Entries with the same sizes run together, in
@@ -53,13 +62,14 @@ int detect_segments_batch(l3d_ctx* c, const DetEntry* e, int n, std::vector<std:
 
 // detect_segments on an image in device memory (checked, ingested by k_det_ingest); an image below 8x8 is refused as detect_segments refuses it
 int detect_segments_device(l3d_ctx* c, const l3d_device_image& image, int new_width, int new_height, float min_length, int max_segments, std::vector<float>& out,
-                           const DetCamera* cam = nullptr);
-// device in, device out (may be the same memory), same size and detector channels; coefficients at or below 1e-12: ingest and egress only
-int undistort_image_device(l3d_ctx* c, const l3d_device_image& in, const DetCamera& cam, const l3d_device_image& out);
+                           const DetCamera* cam = nullptr, const DetLens* lens = nullptr);
+// device in, device out (may be the same memory), same size and detector channels; coefficients at or below 1e-12: ingest and egress only.
+// lens given: it stands in for cam, which is not looked at
+int undistort_image_device(l3d_ctx* c, const l3d_device_image& in, const DetCamera& cam, const l3d_device_image& out, const DetLens* lens = nullptr);
 
-// host in, host out, same size and channels; coefficients at or below 1e-12: the pixels are copied
+// host in, host out, same size and channels; coefficients at or below 1e-12: the pixels are copied.  lens given: it stands in for cam
 int undistort_image(l3d_ctx* c, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, const DetCamera& cam, unsigned char* out,
-                    size_t out_row_stride);
+                    size_t out_row_stride, const DetLens* lens = nullptr);
 
 // ---- JPEG input (l3d_jpeg.cpp, l3d_jpeg_device.hip): baseline files decoded into the detector's pixel buffer; three components come out B, G, R
 struct JpegFrame;
@@ -83,6 +93,6 @@ int jpeg_staged_to_pixels(l3d_ctx* c, const JpegStaged* const* files, int B);
 int decode_jpeg(l3d_ctx* c, const unsigned char* bytes, size_t n, unsigned char* out, size_t out_row_stride);
 // detect_segments on the decoded image, which never crosses the host; images below 8x8 are refused as detect_segments refuses them
 int detect_segments_jpeg(l3d_ctx* c, const unsigned char* bytes, size_t n, int new_width, int new_height, float min_length, int max_segments,
-                         std::vector<float>& out, const DetCamera* cam = nullptr);
+                         std::vector<float>& out, const DetCamera* cam = nullptr, const DetLens* lens = nullptr);
 
 }  // namespace l3d

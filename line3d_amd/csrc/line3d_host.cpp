@@ -686,6 +686,7 @@ struct AddRequest {
     const l3d_device_image* dev = nullptr;          // Device: the image in device memory (e carries its size and the detector's channel count)
     bool cache_rules = false;                       // the form has a data directory: every one but add_image, add_image_fixed_sim, add_image_cached
     bool dist_required = false;                     // the _distorted forms: a null dist is refused (elsewhere it means no distortion)
+    const l3d_lens* lens = nullptr;                 // the ..._lens forms: a lens in the place of dist (both: refused)
     bool image() const { return kind == AddKind::Pixels || kind == AddKind::Jpeg || kind == AddKind::Device; }
 };
 enum class Cache { None, Load, Stale, Write };      // no cache rules or nothing to do | read the file | remove the file | note the file for prepare()
@@ -695,6 +696,8 @@ struct AddPlan {
     int channels = 0;
     bool undistort = false;
     l3d::DetCamera cam;
+    bool lens_on = false;                           // an active lens (then undistort is false): resampled from the lens's camera onto K
+    l3d::DetLens lens;
     Cache cache = Cache::None;
     std::string file;                               // the cache file's path
     bool detect = false;
@@ -790,6 +793,19 @@ static int camera_for_add(l3d_line3d* h, const double* K, const double* dist, l3
     cam = l3d::DetCamera{ K[0], K[4], K[2], K[5], dist[0], dist[1] };
     return 1;
 }
+// the same for a lens: K is the output camera.  Returns 1 with `out` filled and checked, 0 when the lens passes the pixels through, < 0: error negated
+static int lens_for_add(l3d_line3d* h, const double* K, const double* dist, const l3d_lens* lens, int width, int height, l3d::DetLens& out)
+{
+    if (dist) return -h->fail(L3D_ERR_INVALID, "undistortion: an entry carries both dist (k1, k2) and a lens");
+    if (!K) return -h->fail(L3D_ERR_INVALID, "undistortion: K is null");
+    out = l3d::make_lens(*lens, K[0], K[4], K[2], K[5]);
+    bool active = false;
+    std::string err;
+    if (const int rc = l3d::lens_check(out, width, height, &active, err)) return -h->fail(rc, err.c_str());
+    if (!active) return 0;
+    if (K[1] != 0.0) return -h->fail(L3D_ERR_UNSUPPORTED, "lens distortion with a skewed K (K[1] != 0) is not supported");
+    return 1;
+}
 
 // steps 1 and 2.  A JPEG file's size (cache name, max_img_width rule) comes from its headers; the entropy-coded data is touched only when the detector runs
 static int add_plan(L* h, const AddRequest& rq, const char* data_directory, int max_img_width, int load_and_store, AddPlan& p)
@@ -808,9 +824,10 @@ static int add_plan(L* h, const AddRequest& rq, const char* data_directory, int 
         if (rc != L3D_OK) return h->fail(rc, msg);
     }
     if (rq.image()) {
-        const int with = (e.dist || rq.dist_required) ? camera_for_add(h, e.K, e.dist, p.cam) : 0;
+        const int with = rq.lens ? lens_for_add(h, e.K, e.dist, rq.lens, width, height, p.lens) : (e.dist || rq.dist_required) ? camera_for_add(h, e.K, e.dist, p.cam) : 0;
         if (with < 0) return -with;
-        p.undistort = with != 0;
+        p.undistort = with != 0 && !rq.lens;
+        p.lens_on = with != 0 && rq.lens;
         if (width <= 0 || height <= 0) return h->fail(L3D_ERR_INVALID, "image is empty!");
     }
     p.width = (unsigned)width; p.height = (unsigned)height;
@@ -891,11 +908,12 @@ static int add_one(L* h, const AddRequest& rq, const char* data_directory = null
     const l3d_image_entry& e = rq.e;
     std::vector<float> segs;
     const l3d::DetCamera* cam = p.undistort ? &p.cam : nullptr;
+    const l3d::DetLens* lens = p.lens_on ? &p.lens : nullptr;
     // a JPEG file is decoded on the device into the detector -- only here, behind the cache decision
     // a device image's memory is checked and gathered only here as well
-    const int rc = rq.kind == AddKind::Jpeg ? l3d::detect_segments_jpeg(ctx, e.jpeg, e.jpeg_bytes, (int)p.new_w, (int)p.new_h, p.min_length, 3000, segs, cam)
-                 : rq.kind == AddKind::Device ? l3d::detect_segments_device(ctx, *rq.dev, (int)p.new_w, (int)p.new_h, p.min_length, 3000, segs, cam)
-                                            : l3d::detect_segments(ctx, e.pixels, e.width, e.height, e.channels, e.row_stride, (int)p.new_w, (int)p.new_h, p.min_length, 3000, segs, cam);
+    const int rc = rq.kind == AddKind::Jpeg ? l3d::detect_segments_jpeg(ctx, e.jpeg, e.jpeg_bytes, (int)p.new_w, (int)p.new_h, p.min_length, 3000, segs, cam, lens)
+                 : rq.kind == AddKind::Device ? l3d::detect_segments_device(ctx, *rq.dev, (int)p.new_w, (int)p.new_h, p.min_length, 3000, segs, cam, lens)
+                                            : l3d::detect_segments(ctx, e.pixels, e.width, e.height, e.channels, e.row_stride, (int)p.new_w, (int)p.new_h, p.min_length, 3000, segs, cam, lens);
     if (rc != L3D_OK) return h->fail(rc, l3d_last_error(ctx));
     return add_entry(h, rq, p, &segs);
 }
@@ -986,6 +1004,22 @@ int l3d_line3d_undistort_image(l3d_line3d* h, const unsigned char* pixels, int w
     return rc == L3D_OK ? rc : h->fail(rc, l3d_last_error(owner->ctx));
 }
 
+// l3d_undistort_image_lens with the object's device and K, the output camera (a skewed K with an active lens: refused, as with k1, k2)
+int l3d_line3d_undistort_image_lens(l3d_line3d* h, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, const double* K,
+                                    const l3d_lens* lens, unsigned char* out, size_t out_row_stride)
+{
+    if (!h) return L3D_ERR_INVALID;
+    L* owner = h->node ? rank0(h) : h;
+    if (!owner->ctx) return h->fail(L3D_ERR_INVALID, "no device context to undistort with");
+    if (!lens) return h->fail(L3D_ERR_INVALID, "undistort: null argument");
+    l3d::DetLens dl;
+    const int with = lens_for_add(h, K, nullptr, lens, width, height, dl);
+    if (with < 0) return -with;
+    // (a lens that passes the pixels through goes on as it is: the context call copies them)
+    const int rc = l3d::undistort_image(owner->ctx, pixels, width, height, channels, row_stride, l3d::DetCamera{ 1.0, 1.0, 0.0, 0.0, 0.0, 0.0 }, out, out_row_stride, &dl);
+    return rc == L3D_OK ? rc : h->fail(rc, l3d_last_error(owner->ctx));
+}
+
 // from a baseline JPEG file in memory: the entry with jpeg filled
 int l3d_line3d_add_image_jpeg(l3d_line3d* h, uint32_t id, const unsigned char* bytes, size_t n, const double* K, const double* R, const double* t, const double dist[2],
                               const uint32_t* worldpoints, int n_wps, const char* data_directory, int max_img_width, int load_and_store)
@@ -1000,13 +1034,18 @@ int l3d_line3d_add_image_jpeg_fixed_sim(l3d_line3d* h, uint32_t id, const unsign
 }
 
 // the single call for an l3d_image_entry: what the named image forms above fill in
-int l3d_line3d_add_image_entry(l3d_line3d* h, const l3d_image_entry* e, const char* data_directory, int max_img_width, int load_and_store)
+int l3d_line3d_add_image_entry_lens(l3d_line3d* h, const l3d_image_entry* e, const l3d_lens* lens, const char* data_directory, int max_img_width, int load_and_store)
 {
     if (!h) return L3D_ERR_INVALID;
     if (!e) return h->fail(L3D_ERR_INVALID, "add_image_entry: null argument");
     AddRequest rq;
     if (const int rc = entry_request(h, *e, rq, true)) return rc;
+    rq.lens = lens;
     return add_one(h, rq, data_directory, max_img_width, load_and_store);
+}
+int l3d_line3d_add_image_entry(l3d_line3d* h, const l3d_image_entry* e, const char* data_directory, int max_img_width, int load_and_store)
+{
+    return l3d_line3d_add_image_entry_lens(h, e, nullptr, data_directory, max_img_width, load_and_store);
 }
 
 // Many images in one call: the route above per entry, in entry order, with the detector run once (batched, l3d_detect.hip) over all entries that
@@ -1034,6 +1073,7 @@ static int add_batch(L* h, std::vector<AddItem>& items, const char* data_directo
         d.dev = it.rq.dev;
         d.new_width = (int)it.p.new_w; d.new_height = (int)it.p.new_h; d.min_length = it.p.min_length; d.max_segments = 3000;
         d.cam = it.p.undistort ? &it.p.cam : nullptr;           // (items does not grow: the address holds)
+        d.lens = it.p.lens_on ? &it.p.lens : nullptr;
         it.detect_at = (int)todo.size();
         todo.push_back(d);
     }
@@ -1059,7 +1099,8 @@ static int add_batch(L* h, std::vector<AddItem>& items, const char* data_directo
 }
 }  // namespace l3dh
 
-int l3d_line3d_add_images(l3d_line3d* h, const l3d_image_entry* e, int n, const char* data_directory, int max_img_width, int load_and_store, int* status)
+int l3d_line3d_add_images_lens(l3d_line3d* h, const l3d_image_entry* e, const l3d_lens* const* lens, int n, const char* data_directory, int max_img_width,
+                               int load_and_store, int* status)
 {
     if (!h) return L3D_ERR_INVALID;
     if (n < 0 || (n > 0 && !e)) return h->fail(L3D_ERR_INVALID, "add_images: null argument");
@@ -1067,24 +1108,40 @@ int l3d_line3d_add_images(l3d_line3d* h, const l3d_image_entry* e, int n, const 
     for (int i = 0; i < n; ++i) {
         items[i].rc = entry_request(h, e[i], items[i].rq, false);
         if (items[i].rc != L3D_OK) { items[i].msg = h->err; items[i].rq.e.image_id = e[i].image_id; }
+        items[i].rq.lens = lens ? lens[i] : nullptr;
     }
     return add_batch(h, items, data_directory, max_img_width, load_and_store, status);
 }
+int l3d_line3d_add_images(l3d_line3d* h, const l3d_image_entry* e, int n, const char* data_directory, int max_img_width, int load_and_store, int* status)
+{
+    return l3d_line3d_add_images_lens(h, e, nullptr, n, data_directory, max_img_width, load_and_store, status);
+}
 
 // ---- images in device memory: the entry with a descriptor where the others have pixels or a file
-int l3d_line3d_add_device_entry(l3d_line3d* h, const l3d_device_entry* e, const char* data_directory, int max_img_width, int load_and_store)
+int l3d_line3d_add_device_entry_lens(l3d_line3d* h, const l3d_device_entry* e, const l3d_lens* lens, const char* data_directory, int max_img_width, int load_and_store)
 {
     if (!h) return L3D_ERR_INVALID;
     if (!e) return h->fail(L3D_ERR_INVALID, "add_device_entry: null argument");
-    return add_one(h, device_request(*e), data_directory, max_img_width, load_and_store);
+    AddRequest rq = device_request(*e);
+    rq.lens = lens;
+    return add_one(h, rq, data_directory, max_img_width, load_and_store);
 }
-int l3d_line3d_add_device_images(l3d_line3d* h, const l3d_device_entry* e, int n, const char* data_directory, int max_img_width, int load_and_store, int* status)
+int l3d_line3d_add_device_entry(l3d_line3d* h, const l3d_device_entry* e, const char* data_directory, int max_img_width, int load_and_store)
+{
+    return l3d_line3d_add_device_entry_lens(h, e, nullptr, data_directory, max_img_width, load_and_store);
+}
+int l3d_line3d_add_device_images_lens(l3d_line3d* h, const l3d_device_entry* e, const l3d_lens* const* lens, int n, const char* data_directory, int max_img_width,
+                                      int load_and_store, int* status)
 {
     if (!h) return L3D_ERR_INVALID;
     if (n < 0 || (n > 0 && !e)) return h->fail(L3D_ERR_INVALID, "add_device_images: null argument");
     std::vector<AddItem> items((size_t)n);
-    for (int i = 0; i < n; ++i) items[i].rq = device_request(e[i]);
+    for (int i = 0; i < n; ++i) { items[i].rq = device_request(e[i]); items[i].rq.lens = lens ? lens[i] : nullptr; }
     return add_batch(h, items, data_directory, max_img_width, load_and_store, status);
+}
+int l3d_line3d_add_device_images(l3d_line3d* h, const l3d_device_entry* e, int n, const char* data_directory, int max_img_width, int load_and_store, int* status)
+{
+    return l3d_line3d_add_device_images_lens(h, e, nullptr, n, data_directory, max_img_width, load_and_store, status);
 }
 
 // l3d_decode_jpeg_device / l3d_undistort_image_device with the object's device (a node object: rank 0's) and, for the latter, the object's K rule

@@ -26,7 +26,7 @@ def image_entries(entries):
 
     for i, en in enumerate(entries):
         e = arr[i]
-        unknown = set(en) - {"imageID", "img", "data", "K", "R", "t", "dist", "worldpointIDs", "viewSimilarity"}
+        unknown = set(en) - {"imageID", "img", "data", "K", "R", "t", "dist", "lens", "worldpointIDs", "viewSimilarity"}
         if unknown:
             raise ValueError("entry %d: unknown keys %s" % (i, sorted(unknown)))
         if (en.get("img") is None) == (en.get("data") is None):
@@ -71,7 +71,7 @@ def device_entries(entries):
 
     for i, en in enumerate(entries):
         e = arr[i]
-        unknown = set(en) - {"imageID", "img", "data", "K", "R", "t", "dist", "worldpointIDs", "viewSimilarity"}
+        unknown = set(en) - {"imageID", "img", "data", "K", "R", "t", "dist", "lens", "worldpointIDs", "viewSimilarity"}
         if unknown:
             raise ValueError("entry %d: unknown keys %s" % (i, sorted(unknown)))
         if en.get("img") is None or en.get("data") is not None:
@@ -240,46 +240,53 @@ class Line3D:
 
     def _add_entry(self, en, maxImgWidth, loadAndStoreSegments):
         """one image entry (as add_images takes them) through l3d_line3d_add_image_entry: True when it was taken; the status stays in last_rc.
-        What is no image or no file raises TypeError, as image_arguments and bytes() do; image_entries speaks of "entry 0" in what it refuses"""
+        What is no image or no file raises TypeError, as image_arguments and bytes() do; image_entries speaks of "entry 0" in what it refuses.
+        An entry with a lens goes through the ..._entry_lens form of the same call"""
+        if en.get("lens") is None:
+            en.pop("lens", None)
+        lens = en.get("lens")
+        if lens is not None and not isinstance(lens, capi.Lens):
+            raise TypeError("lens must come from capi.lens()")
+        tail = (C.c_char_p(self.data_directory.encode()), C.c_int(int(maxImgWidth)), C.c_int(int(loadAndStoreSegments)))
         if capi.is_device_object(en.get("img")):
             arr, keep = device_entries([en])
-            self.last_rc = self.lib.l3d_line3d_add_device_entry(self.h, arr, C.c_char_p(self.data_directory.encode()), C.c_int(int(maxImgWidth)),
-                                                                C.c_int(int(loadAndStoreSegments)))
+            self.last_rc = self.lib.l3d_line3d_add_device_entry(self.h, arr, *tail) if lens is None else self.lib.l3d_line3d_add_device_entry_lens(self.h, arr, C.byref(lens), *tail)
             return self.last_rc == 0
         if "data" in en and not isinstance(en["data"], (bytes, bytearray, memoryview, np.ndarray)):
             en["data"] = bytes(en["data"])            # (whatever bytes() takes, as before; None or a str: TypeError)
         arr, keep = image_entries([en])
-        self.last_rc = self.lib.l3d_line3d_add_image_entry(self.h, arr, C.c_char_p(self.data_directory.encode()), C.c_int(int(maxImgWidth)),
-                                                           C.c_int(int(loadAndStoreSegments)))
+        self.last_rc = self.lib.l3d_line3d_add_image_entry(self.h, arr, *tail) if lens is None else self.lib.l3d_line3d_add_image_entry_lens(self.h, arr, C.byref(lens), *tail)
         return self.last_rc == 0
 
-    def add_image_pixels(self, imageID, img, K, R, t, worldpointIDs, maxImgWidth=1920, loadAndStoreSegments=True, dist=None):
+    def add_image_pixels(self, imageID, img, K, R, t, worldpointIDs, maxImgWidth=1920, loadAndStoreSegments=True, dist=None, lens=None):
         """Line3D::addImage from pixels (an image entry with img, include/line3d_amd.h): uint8 image H x W or H x W x 3.  The segment cache in
         `data_directory` is loaded when present (and loadAndStoreSegments); otherwise the segments are detected on the device, and the cache written
         or a stale one removed.  An image without segments adds no view and is no error (line3D.cc:186-190).  dist = (k1, k2), OpenCV-convention
         radial coefficients: the image is undistorted on the device with K before the detector sees it.
-        img may be a device object (a torch device tensor, a capi.device_image descriptor): it is read where it lies (l3d_line3d_add_device_entry)."""
-        return self._add_entry(dict(imageID=imageID, img=img if capi.is_device_object(img) else np.asarray(img), K=K, R=R, t=t, worldpointIDs=list(worldpointIDs), dist=dist), maxImgWidth, loadAndStoreSegments)
+        img may be a device object (a torch device tensor, a capi.device_image descriptor): it is read where it lies (l3d_line3d_add_device_entry).
+        lens (capi.lens(...)) in the place of dist: tangential, rational and fisheye models, the image resampled from the lens's source camera onto
+        K, which the view keeps (l3d_line3d_add_image_entry_lens).  dist and lens together are refused by the library."""
+        return self._add_entry(dict(imageID=imageID, img=img if capi.is_device_object(img) else np.asarray(img), K=K, R=R, t=t, worldpointIDs=list(worldpointIDs), dist=dist, lens=lens), maxImgWidth, loadAndStoreSegments)
 
-    def add_image_pixels_fixed_sim(self, imageID, img, K, R, t, viewSimilarity, maxImgWidth=1920, loadAndStoreSegments=True, dist=None):
+    def add_image_pixels_fixed_sim(self, imageID, img, K, R, t, viewSimilarity, maxImgWidth=1920, loadAndStoreSegments=True, dist=None, lens=None):
         """Line3D::addImage_fixed_sim from pixels; dist and device objects as in add_image_pixels"""
-        return self._add_entry(dict(imageID=imageID, img=img if capi.is_device_object(img) else np.asarray(img), K=K, R=R, t=t, viewSimilarity=dict(viewSimilarity), dist=dist), maxImgWidth, loadAndStoreSegments)
+        return self._add_entry(dict(imageID=imageID, img=img if capi.is_device_object(img) else np.asarray(img), K=K, R=R, t=t, viewSimilarity=dict(viewSimilarity), dist=dist, lens=lens), maxImgWidth, loadAndStoreSegments)
 
-    def add_image_jpeg(self, imageID, data, K, R, t, worldpointIDs, maxImgWidth=1920, loadAndStoreSegments=True, dist=None):
+    def add_image_jpeg(self, imageID, data, K, R, t, worldpointIDs, maxImgWidth=1920, loadAndStoreSegments=True, dist=None, lens=None):
         """Line3D::addImage from the bytes of a baseline JPEG file (an image entry with data): decoded, undistorted (dist = (k1, k2), None: not)
         and its segments detected on the device.  Cache rules as add_image_pixels; a cache that is present and wanted is loaded without decoding
         the file.  A file the decoder refuses adds no view and returns False (the cause: l3d_line3d_last_error)."""
-        return self._add_entry(dict(imageID=imageID, data=data, K=K, R=R, t=t, worldpointIDs=list(worldpointIDs), dist=dist), maxImgWidth, loadAndStoreSegments)
+        return self._add_entry(dict(imageID=imageID, data=data, K=K, R=R, t=t, worldpointIDs=list(worldpointIDs), dist=dist, lens=lens), maxImgWidth, loadAndStoreSegments)
 
-    def add_image_jpeg_fixed_sim(self, imageID, data, K, R, t, viewSimilarity, maxImgWidth=1920, loadAndStoreSegments=True, dist=None):
+    def add_image_jpeg_fixed_sim(self, imageID, data, K, R, t, viewSimilarity, maxImgWidth=1920, loadAndStoreSegments=True, dist=None, lens=None):
         """Line3D::addImage_fixed_sim from the bytes of a baseline JPEG file; as add_image_jpeg"""
-        return self._add_entry(dict(imageID=imageID, data=data, K=K, R=R, t=t, viewSimilarity=dict(viewSimilarity), dist=dist), maxImgWidth, loadAndStoreSegments)
+        return self._add_entry(dict(imageID=imageID, data=data, K=K, R=R, t=t, viewSimilarity=dict(viewSimilarity), dist=dist, lens=lens), maxImgWidth, loadAndStoreSegments)
 
     def add_images(self, entries, maxImgWidth=1920, loadAndStoreSegments=True):
         """l3d_line3d_add_images: many images in one call -- exactly the add_image_pixels[_fixed_sim] / add_image_jpeg[_fixed_sim] calls in entry order,
         with the detector run once over all entries whose cache does not stand in for them.  An entry is a dict with the single calls' argument
         names: imageID, K, R, t; img (a uint8 array) or data (the bytes of a baseline JPEG file); worldpointIDs or viewSimilarity ({view id:
-        similarity}); optionally dist = (k1, k2).  Returns the list of statuses, one per entry: 0, or the code the single call would have failed
+        similarity}); optionally dist = (k1, k2) or lens = capi.lens(...) (l3d_line3d_add_images_lens).  Returns the list of statuses, one per entry: 0, or the code the single call would have failed
         with (the causes: l3d_line3d_last_error, one line per failed entry).  A malformed entry raises before anything is added.
         The img of every entry may be a device object instead (l3d_line3d_add_device_images); a list that mixes device objects with host
         images or files raises ValueError before any call."""
@@ -288,9 +295,14 @@ class Line3D:
         arr, keep = (device_entries if on_device else image_entries)(entries)
         n = len(entries)
         status = (C.c_int * max(1, n))()
-        call = self.lib.l3d_line3d_add_device_images if on_device else self.lib.l3d_line3d_add_images
-        self._chk(call(self.h, arr, C.c_int(n), C.c_char_p(self.data_directory.encode()), C.c_int(int(maxImgWidth)),
-                                                 C.c_int(int(loadAndStoreSegments)), status))
+        lens_arr, lens_keep = capi.lens_pointers([en.get("lens") for en in entries], n)
+        tail = (C.c_int(n), C.c_char_p(self.data_directory.encode()), C.c_int(int(maxImgWidth)), C.c_int(int(loadAndStoreSegments)), status)
+        if lens_arr is not None:
+            call = self.lib.l3d_line3d_add_device_images_lens if on_device else self.lib.l3d_line3d_add_images_lens
+            self._chk(call(self.h, arr, lens_arr, *tail))
+        else:
+            call = self.lib.l3d_line3d_add_device_images if on_device else self.lib.l3d_line3d_add_images
+            self._chk(call(self.h, arr, *tail))
         return [int(status[i]) for i in range(n)]
 
     def decode_jpeg(self, data, device=False):

@@ -12,7 +12,11 @@ from .capi import load_library
 
 class SfmScene:
     """cameras: list of dicts {name, focal, dist (2,), cv_dist (2,), R (3,3), t (3,), worldpoints (uint32 array)}.  dist: the file's own numbers;
-    cv_dist: (k1, k2) in OpenCV's convention, as the drivers use them (l3d_sfm_camera_cv_distortion) -- what add_image_pixels(dist=...) takes."""
+    cv_dist: (k1, k2) in OpenCV's convention, as the drivers use them (l3d_sfm_camera_cv_distortion) -- what add_image_pixels(dist=...) takes.
+    A camera of a COLMAP model (read_colmap) has in addition: camera_id, model and params (the file's own numbers), size = (width, height), and --
+    unless the model has no lens in this library (FOV, THIN_PRISM_FISHEYE: lens_error says so) -- lens (capi.lens: what add_image_pixels(lens=...)
+    takes) and K (3 x 3), both with the principal point moved by half a pixel (include/line3d_amd.h).  cv_dist is None where the model has no
+    (k1, k2) form."""
 
     def __init__(self, cameras, n_points):
         self.cameras = cameras
@@ -40,12 +44,22 @@ def _read(path: str, fn_name: str) -> SfmScene:
             nw = C.c_int(0)
             lib.l3d_sfm_camera(h, C.c_int(i), C.byref(focal), dist, R, t, C.byref(nw))
             cv = (C.c_double * 2)()
-            lib.l3d_sfm_camera_cv_distortion(h, C.c_int(i), cv)
+            has_cv = lib.l3d_sfm_camera_cv_distortion(h, C.c_int(i), cv) == 0
             w = np.zeros(nw.value, dtype=np.uint32)
             if nw.value:
                 lib.l3d_sfm_camera_worldpoints(h, C.c_int(i), w.ctypes.data_as(C.c_void_p))
-            cams.append(dict(name=lib.l3d_sfm_camera_name(h, C.c_int(i)).decode(), focal=focal.value, dist=np.array(list(dist)), cv_dist=np.array(list(cv)),
-                             R=np.array(list(R)).reshape(3, 3), t=np.array(list(t)), worldpoints=w))
+            cams.append(dict(name=lib.l3d_sfm_camera_name(h, C.c_int(i)).decode(), focal=focal.value, dist=np.array(list(dist)),
+                             cv_dist=np.array(list(cv)) if has_cv else None, R=np.array(list(R)).reshape(3, 3), t=np.array(list(t)), worldpoints=w))
+            if fn_name == "l3d_sfm_read_colmap":
+                name, params, n = C.c_char_p(), C.POINTER(C.c_double)(), C.c_int(0)
+                lib.l3d_sfm_camera_model(h, C.c_int(i), C.byref(name), C.byref(params), C.byref(n))
+                lens, K, width, height = capi.Lens(), (C.c_double * 9)(), C.c_int(0), C.c_int(0)
+                lib.l3d_sfm_camera_id.restype = C.c_int
+                cams[-1].update(camera_id=int(lib.l3d_sfm_camera_id(h, C.c_int(i))), model=name.value.decode(), params=np.array([params[k] for k in range(n.value)]))
+                if lib.l3d_sfm_camera_lens(h, C.c_int(i), C.byref(lens), K, C.byref(width), C.byref(height)) == 0:
+                    cams[-1].update(lens=lens, K=np.array(list(K)).reshape(3, 3), size=(width.value, height.value))
+                else:
+                    cams[-1].update(lens=None, K=None, size=None, lens_error=lib.l3d_sfm_last_error(h).decode())
         return SfmScene(cams, lib.l3d_sfm_num_points(h))
     finally:
         if h:
@@ -60,6 +74,17 @@ def read_nvm(path: str) -> SfmScene:
 def read_bundler(path: str) -> SfmScene:
     """main_bundler.cpp:110-204 (bundle.rd.out)"""
     return _read(path, "l3d_sfm_read_bundler")
+
+
+def read_colmap(model_dir: str) -> SfmScene:
+    """A COLMAP model folder: cameras.bin + images.bin, else cameras.txt + images.txt (l3d_sfm_read_colmap); one camera of the scene per image"""
+    return _read(model_dir, "l3d_sfm_read_colmap")
+
+
+def _lens_active(cam) -> bool:
+    """the camera has a lens that changes the image (a fisheye always does)"""
+    lens = cam.get("lens")
+    return lens is not None and (lens.model != capi.LENS_BROWN or any(abs(v) > 1e-12 for v in lens.k))
 
 
 def intrinsics(focal: float, width: int, height: int) -> np.ndarray:
@@ -89,7 +114,7 @@ def reconstruct(scene: SfmScene, segments, image_sizes, out_dir=None, neighbors=
     from .io import segment_cache_filename
     l3d = Line3D("", matchingNeighbors=neighbors, device=device, **line3d_kwargs)
     for i, cam in enumerate(scene.cameras):
-        if np.any(np.abs(cam["dist"]) > 1e-12):
+        if np.any(np.abs(cam["dist"]) > 1e-12) or _lens_active(cam):
             raise RuntimeError("camera %d has lens distortion: segments of the undistorted image cannot be made from it here -- "
                                "reconstruct_from_images undistorts and detects from the pixels" % i)
         w, h = image_sizes[i]
@@ -114,7 +139,8 @@ def reconstruct_from_images(scene: SfmScene, load_image, data_directory, out_dir
     """The drivers' flow (main_vsfm.cpp:226-325) from pixels: per camera the image load_image(i, name) returns -- `bytes`: the contents of a
     baseline JPEG file, decoded on the device (Line3D.add_image_jpeg); or a uint8 array H x W or H x W x 3, decoded by the caller; or an image
     in device memory (a torch device tensor, a capi.device_image descriptor), read where it lies --, K from the focal length and the image size, the image undistorted with the camera's coefficients and its
-    segments detected on the device (Line3D.add_image_pixels(..., dist=cam["cv_dist"])), compute3Dmodel, optional STL + TXT output under the
+    segments detected on the device (Line3D.add_image_pixels(..., dist=cam["cv_dist"])); a camera that has `lens` and `K` (read_colmap) is added with
+    those instead (Line3D.add_image_pixels(..., lens=cam["lens"]) with its own K); then compute3Dmodel, optional STL + TXT output under the
     drivers' file name.  data_directory: the drivers' "<image folder>/L3D_data/" -- with load_and_store_segments (the drivers' default) the segment
     caches are written there, and a cache of an earlier run stands in for the image (line3D.cc:143-168).  The images go to the library `batch`
     at a time (Line3D.add_images): the same views as one call per image, with the detector run once per batch.
@@ -134,7 +160,13 @@ def reconstruct_from_images(scene: SfmScene, load_image, data_directory, out_dir
 
     for i, cam in enumerate(scene.cameras):         # `batch` images per add_images call: the detector runs over them together
         img = load_image(i, cam["name"])
-        en = dict(imageID=i, R=cam["R"], t=cam["t"], worldpointIDs=cam["worldpoints"], dist=cam["cv_dist"])
+        en = dict(imageID=i, R=cam["R"], t=cam["t"], worldpointIDs=cam["worldpoints"])
+        if cam.get("lens") is not None and cam.get("K") is not None:       # a COLMAP camera: its own lens and K
+            en["lens"] = cam["lens"]
+        elif "lens_error" in cam:
+            raise RuntimeError(cam["lens_error"])
+        else:
+            en["dist"] = cam["cv_dist"]
         if isinstance(img, (bytes, bytearray, memoryview)):
             from .capi import jpeg_info
             w, h, _ = jpeg_info(img)
@@ -153,7 +185,7 @@ def reconstruct_from_images(scene: SfmScene, load_image, data_directory, out_dir
             en["img"] = img
             if entries and capi.is_device_object(entries[-1].get("img")):
                 flush()
-        en["K"] = intrinsics(cam["focal"], w, h)
+        en["K"] = cam["K"] if "lens" in en else intrinsics(cam["focal"], w, h)
         entries.append(en)
         if len(entries) >= batch:
             flush()
