@@ -284,6 +284,61 @@ public:
     {
         add_one(makeEntry(imageID, bytes, n, K, R, t, links).withLens(lens), maxImgWidth, loadAndStoreSegments);
     }
+    // With a REMAP (include/line3d_amd.h, "A REMAP": l3d_remap -- a lens, another output size, the caller's mask in the source grid, border_mask): K is
+    // the OUTPUT camera, which the view keeps; the view and its segment cache file have the remap's output size, and maxImgWidth acts on it.  No
+    // line segment starts where a blank or masked pixel contributed to the gradient.  links: world point ids or view similarities
+    template <class Img, class M3, class V3, class Links, class = decltype(std::declval<const Img&>().cols), class = decltype(std::declval<const Img&>().rows),
+              class = decltype(std::declval<const M3&>()(0, 0)), class = decltype(std::declval<const V3&>()(0))>
+    void addImageRemap(const unsigned int imageID, const Img& image, const M3& K, const M3& R, const V3& t, const l3d_remap& remap, const Links& links,
+                       const int maxImgWidth = 1920, const bool loadAndStoreSegments = true)
+    {
+        add_one(makeEntry(imageID, image, K, R, t, links).withRemap(remap), maxImgWidth, loadAndStoreSegments);
+    }
+    template <class M3, class V3, class Links, class = decltype(std::declval<const M3&>()(0, 0)), class = decltype(std::declval<const V3&>()(0))>
+    void addImageJPEGRemap(const unsigned int imageID, const unsigned char* bytes, const size_t n, const M3& K, const M3& R, const V3& t, const l3d_remap& remap,
+                           const Links& links, const int maxImgWidth = 1920, const bool loadAndStoreSegments = true)
+    {
+        add_one(makeEntry(imageID, bytes, n, K, R, t, links).withRemap(remap), maxImgWidth, loadAndStoreSegments);
+    }
+    // undistortImage with a remap: `out` (and `mask_out`, if given: one channel, 255 = valid) are images of the caller's with the remap's output size --
+    // the source's when the remap names none -- and the input's channels; K the output camera.  false: refused, or an output of another size
+    template <class Img, class M3, class = decltype(static_cast<unsigned char*>(std::declval<Img&>().data)),
+              class = decltype(static_cast<size_t>(std::declval<const Img&>().step)), class = decltype(static_cast<int>(std::declval<const Img&>().channels())),
+              class = decltype(std::declval<const M3&>()(0, 0))>
+    bool undistortImage(const Img& image, const M3& K, const l3d_remap& remap, Img& out, Img* mask_out = nullptr)
+    {
+        double k[9];
+        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) k[i * 3 + j] = K(i, j);
+        const int ow = remap.out_width > 0 ? remap.out_width : (int)image.cols, oh = remap.out_height > 0 ? remap.out_height : (int)image.rows;
+        const int ch = static_cast<int>(image.channels());
+        if ((int)out.cols != ow || (int)out.rows != oh || static_cast<int>(out.channels()) != ch ||
+            (mask_out && ((int)mask_out->cols != ow || (int)mask_out->rows != oh || static_cast<int>(mask_out->channels()) != 1))) {
+            std::cerr << prefix_ << "undistortImage: out (and mask_out) must have the remap's output size, " << ow << " x " << oh << std::endl;
+            return false;
+        }
+        const int rc = l3d_line3d_undistort_image_remap(h_, static_cast<const unsigned char*>(image.data), (int)image.cols, (int)image.rows, ch, static_cast<size_t>(image.step), k,
+                                                        &remap, static_cast<unsigned char*>(out.data), static_cast<size_t>(out.step),
+                                                        mask_out ? static_cast<unsigned char*>(mask_out->data) : nullptr, mask_out ? static_cast<size_t>(mask_out->step) : 0);
+        report(rc);
+        return rc == L3D_OK;
+    }
+    // The planner of include/line3d_amd.h ("A REMAP", l3d_undistort_plan): the output camera K_out and size for a lens that carries its source camera
+    // -- no device.  alpha 0: no blank pixel in the output, 1: every source pixel inside fov_max_deg is kept; out_width, out_height: the size, 0 0 for
+    // the source's, -1 -1 for the size that keeps the focal length (scaled down to max_dim when that is positive).  false: refused (the cause on cerr)
+    template <class M3, class = decltype(std::declval<M3&>()(0, 0) = 0.0)>
+    static bool undistortPlan(const l3d_lens& lens, const int width, const int height, const double alpha, M3& K_out, int& out_width, int& out_height,
+                              const int max_dim = 0, const double fov_max_deg = 120.0)
+    {
+        double k[9];
+        int w = 0, h = 0;
+        if (l3d_undistort_plan(&lens, width, height, alpha, out_width, out_height, max_dim, fov_max_deg, k, &w, &h) != L3D_OK) {
+            std::cerr << "[L3D-AMD] " << l3d_undistort_plan_error() << std::endl;
+            return false;
+        }
+        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) K_out(i, j) = k[i * 3 + j];
+        out_width = w; out_height = h;
+        return true;
+    }
     // the size and channel count (1: grey, 3: B, G, R) a JPEG file decodes to, from its headers alone -- no device; false: not a file the decoder takes
     static bool jpegSize(const unsigned char* bytes, const size_t n, unsigned int& width, unsigned int& height, unsigned int& channels)
     {
@@ -318,6 +373,24 @@ public:
         std::vector<float> sims;
         ImageEntry& distorted(const double k1, const double k2) { dist[0] = k1; dist[1] = k2; has_dist = true; return *this; }
         ImageEntry& withLens(const l3d_lens& l) { lens = l; has_lens = true; return *this; }
+        // a remap (include/line3d_amd.h, "A REMAP") in the place of dist and lens: K is the OUTPUT camera (undistortPlan chooses one), the view has the
+        // remap's output size.  The remap's lens is copied into the entry; its mask is not -- it has to live until the add call returns
+        bool has_remap = false, remap_has_lens = false;
+        l3d_remap remap = l3d_remap();
+        ImageEntry& withRemap(const l3d_remap& r)
+        {
+            remap = r; has_remap = true; remap_has_lens = r.lens != nullptr;
+            if (r.lens) lens = *r.lens;
+            remap.lens = nullptr;           // (set where the entry is handed over: the entry may be copied in between)
+            return *this;
+        }
+        // what the ..._remap calls take for this entry: its remap, a lens alone as a remap that asks for nothing more, or null
+        const l3d_remap* remap_for_call(l3d_remap& store) const
+        {
+            if (has_remap) { store = remap; store.lens = remap_has_lens ? &lens : nullptr; return &store; }
+            if (has_lens) { store = l3d_remap(); store.lens = &lens; return &store; }
+            return nullptr;
+        }
     };
     template <class Img, class M3, class V3, class Links, class = decltype(static_cast<const unsigned char*>(std::declval<const Img&>().data)),
               class = decltype(static_cast<size_t>(std::declval<const Img&>().step)), class = decltype(static_cast<int>(std::declval<const Img&>().channels())),
@@ -349,7 +422,13 @@ public:
         std::vector<const l3d_lens*> lens;
         for (const ImageEntry& s : entries) { e.push_back(to_c(s)); lens.push_back(s.has_lens ? &s.lens : nullptr); }
         std::vector<int> status(entries.size(), L3D_ERR_INVALID);        // (a call refused as a whole -- no object -- leaves them)
-        const int rc = l3d_line3d_add_images_lens(h_, e.data(), lens.data(), (int)e.size(), data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0, status.data());
+        bool remaps = false;
+        for (const ImageEntry& s : entries) remaps = remaps || s.has_remap;
+        std::vector<l3d_remap> store(entries.size());
+        std::vector<const l3d_remap*> remap;
+        if (remaps) for (size_t i = 0; i < entries.size(); ++i) remap.push_back(entries[i].remap_for_call(store[i]));
+        const int rc = remaps ? l3d_line3d_add_images_remap(h_, e.data(), remap.data(), (int)e.size(), data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0, status.data())
+                              : l3d_line3d_add_images_lens(h_, e.data(), lens.data(), (int)e.size(), data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0, status.data());
         bool any = rc != L3D_OK;
         for (int st : status) any = any || st != L3D_OK;
         if (any) std::cerr << prefix_ << l3d_line3d_last_error(h_) << std::endl;
@@ -381,6 +460,7 @@ public:
         l3d_device_image image;
         DeviceEntry& distorted(const double k1, const double k2) { base.distorted(k1, k2); return *this; }
         DeviceEntry& withLens(const l3d_lens& l) { base.withLens(l); return *this; }
+        DeviceEntry& withRemap(const l3d_remap& r) { base.withRemap(r); return *this; }
     };
     template <class M3, class V3, class Links, class = decltype(std::declval<const M3&>()(0, 0)), class = decltype(std::declval<const V3&>()(0))>
     static DeviceEntry makeDeviceEntry(const unsigned int imageID, const l3d_device_image& image, const M3& K, const M3& R, const V3& t, const Links& links)
@@ -419,6 +499,13 @@ public:
     {
         add_device(makeDeviceEntry(imageID, image, K, R, t, links).withLens(lens), maxImgWidth, loadAndStoreSegments);
     }
+    // with a remap (see addImageRemap); a mask in device memory: remap.mask_on_device
+    template <class Img, class M3, class V3, class Links>
+    void addImageDeviceRemap(const unsigned int imageID, const Img& image, const M3& K, const M3& R, const V3& t, const l3d_remap& remap, const Links& links,
+                             const int maxImgWidth = 1920, const bool loadAndStoreSegments = true)
+    {
+        add_device(makeDeviceEntry(imageID, image, K, R, t, links).withRemap(remap), maxImgWidth, loadAndStoreSegments);
+    }
     template <class Img, class M3, class V3>
     void addImage_fixed_simDevice(const unsigned int imageID, const Img& image, const M3& K, const M3& R, const V3& t, std::map<unsigned int, float>& viewSimilarity,
                                   const int maxImgWidth = 1920, const bool loadAndStoreSegments = true)
@@ -438,7 +525,13 @@ public:
         std::vector<const l3d_lens*> lens;
         for (const DeviceEntry& s : entries) { e.push_back(to_c(s)); lens.push_back(s.base.has_lens ? &s.base.lens : nullptr); }
         std::vector<int> status(entries.size(), L3D_ERR_INVALID);
-        const int rc = l3d_line3d_add_device_images_lens(h_, e.data(), lens.data(), (int)e.size(), data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0, status.data());
+        bool remaps = false;
+        for (const DeviceEntry& s : entries) remaps = remaps || s.base.has_remap;
+        std::vector<l3d_remap> store(entries.size());
+        std::vector<const l3d_remap*> remap;
+        if (remaps) for (size_t i = 0; i < entries.size(); ++i) remap.push_back(entries[i].base.remap_for_call(store[i]));
+        const int rc = remaps ? l3d_line3d_add_device_images_remap(h_, e.data(), remap.data(), (int)e.size(), data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0, status.data())
+                              : l3d_line3d_add_device_images_lens(h_, e.data(), lens.data(), (int)e.size(), data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0, status.data());
         bool any = rc != L3D_OK;
         for (int st : status) any = any || st != L3D_OK;
         if (any) std::cerr << prefix_ << l3d_line3d_last_error(h_) << std::endl;
@@ -575,12 +668,16 @@ private:
     void add_device(const DeviceEntry& s, int maxImgWidth, bool loadAndStoreSegments)
     {
         const l3d_device_entry e = to_c(s);
+        l3d_remap store;
+        if (s.base.has_remap) { report(l3d_line3d_add_device_entry_remap(h_, &e, s.base.remap_for_call(store), data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0)); return; }
         report(l3d_line3d_add_device_entry_lens(h_, &e, s.base.has_lens ? &s.base.lens : nullptr, data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0));
     }
     // every image and JPEG form: one entry through the library's one route (l3d_line3d_add_image_entry)
     void add_one(const ImageEntry& s, int maxImgWidth, bool loadAndStoreSegments)
     {
         const l3d_image_entry e = to_c(s);
+        l3d_remap store;
+        if (s.has_remap) { report(l3d_line3d_add_image_entry_remap(h_, &e, s.remap_for_call(store), data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0)); return; }
         report(l3d_line3d_add_image_entry_lens(h_, &e, s.has_lens ? &s.lens : nullptr, data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0));
     }
     // `image` with pixels (cv::Mat: .data, .step, .channels()): detect on the device.  links: world point ids or view similarities; dist: null or k1, k2

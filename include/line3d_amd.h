@@ -838,7 +838,7 @@ int l3d_detect_segments_distorted(l3d_ctx* ctx, const unsigned char* pixels, int
  * OUTPUT camera (fx', fy', cx', cy') -- at context level four doubles, in the add family the entry's K, which is also the view's K.  The lens
  * carries the SOURCE camera, that of the distorted image; fx == 0 && fy == 0 there says "the output camera".  When the two differ the image is
  * resampled onto the new camera matrix, at the same size: that is what makes a fisheye usable, the caller can zoom out (fx' < fx).  Another
- * output size, cropping and choosing the new matrix automatically are not offered.
+ * output size, cropping and choosing the new matrix automatically: A REMAP, below.
  * For output pixel (column j, row i), in double, nothing fused, in this order of operations:
  *     x = (j - cx') / fx'      y = (i - cy') / fy'      r2 = x x + y y
  *     BROWN:    num = 1 + ((k3 r2 + k2) r2 + k1) r2      den = 1 + ((k6 r2 + k5) r2 + k4) r2      kr = num / den
@@ -880,6 +880,94 @@ typedef struct l3d_lens {
 } l3d_lens;
 int l3d_undistort_image_lens(l3d_ctx* ctx, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, double fx, double fy, double cx,
                              double cy, const l3d_lens* lens, unsigned char* out, size_t out_row_stride);
+/* A REMAP: undistortion onto a PLANNED camera and ANOTHER SIZE, with a VALIDITY PLANE (l3d_remap_plan.cpp; k_det_undistort_remap, l3d_detect.hip).
+ *
+ * THE PLANNER, l3d_undistort_plan: host code in double, no context and no device.  lens: a lens WITH its source camera (fx, fy > 0); model 0 means
+ * a pinhole camera (the coefficients are not read).  width, height: the source image.
+ *   Border points: every pixel (j, i) on the four edges of the source image, 2 (w + h) - 4 of them.  xd = (j - cx) / fx, yd = (i - cy) / fy, and
+ *   the distortion is inverted:
+ *     BROWN    Newton on the two forward formulas of A LENS with their analytic Jacobian, from (x, y) = (xd, yd);
+ *     FISHEYE  Newton on theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8) = sqrt(xd^2 + yd^2), from theta = that value; then
+ *              r = tan(theta) and (x, y) = (xd, yd) r / sqrt(xd^2 + yd^2)  (below 1e-8: (xd, yd)).
+ *   An iteration ends with the first step whose components are all within 1e-12, after at most 50 steps.  A point cannot be used as it is when the
+ *   iteration does not end that way or takes a step that is not finite; when the Jacobian's determinant (FISHEYE: the derivative of the left side)
+ *   is not positive at the solution or at one of the 15 points that divide the segment from the optical axis to the solution into 16 equal parts
+ *   -- the lens folds over, its radial function is not monotone --; when the solution lies on the other side of the axis (x xd + y yd < 0);
+ *   when theta is outside [0, pi/2); or when the undistorted radius exceeds r_max = tan(fov_max_deg / 2 in radians).  Such a point is CLAMPED to radius r_max: along its own direction when only
+ *   the radius is too large, along (xd, yd) otherwise.  fov_max_deg = 120 is the bindings' default: a choice (beyond it a rectilinear image spends
+ *   most of its pixels on the periphery), not a measurement.
+ *   Rectangles in normalised coordinates: OUTER, min and max of x and of y over all border points; INNER, max of x over the left edge, min of x over
+ *   the right edge, max of y over the top edge, min of y over the bottom edge.  alpha in [0, 1] interpolates the four bounds linearly, 0 = inner
+ *   (no blank pixel in the output), 1 = outer (every source pixel inside the limit is kept): l, r, t, b.
+ *   The output camera: fy' = fx' (fy / fx) -- the pixel aspect is kept --, and all extents are measured between PIXEL CENTRES (an output of w'
+ *   columns spans (w' - 1) / fx'), so that a camera without distortion gets its own K back at its own size:
+ *     fx'(0) = max((w' - 1) / (inner r - inner l), (h' - 1) / ((fy / fx) (inner b - inner t)))     the smallest that keeps the output inside the inner rectangle
+ *     fx'(1) = min((w' - 1) / (outer r - outer l), (h' - 1) / ((fy / fx) (outer b - outer t)))     the largest that keeps the outer rectangle inside the output
+ *     fx' = fx'(0) + alpha (fx'(1) - fx'(0))
+ *     cx' = (w' - 1) / 2 - fx' (l + r) / 2          cy' = (h' - 1) / 2 - fy' (t + b) / 2
+ *   The output size: (out_width, out_height) as given; (0, 0): the source size; (-1, -1): the size at which fx' = fx (COLMAP's behaviour) --
+ *   then fx' = fx, w' = floor(fx' (r - l) + 1e-6) + 1, h' = floor(fy' (b - t) + 1e-6) + 1, and when max_dim > 0 and one of them exceeds it,
+ *   fx' = fx max_dim / max(w', h') and both are computed again.
+ *   Refused, L3D_ERR_INVALID with the cause in l3d_undistort_plan_error() (per thread): a null argument; a lens that A LENS refuses or that has no
+ *   positive source camera; alpha outside [0, 1]; fov_max_deg outside (0, 180); a negative max_dim; another combination of out_width, out_height;
+ *   a degenerate rectangle (inner r <= inner l or inner b <= inner t); a source or output size below 8 in a direction, above 2^24, or of more
+ *   than 2^31 bytes at three channels (the detector's limits).
+ *
+ * THE RESAMPLING, k_det_undistort_remap: one thread per pixel of the OUTPUT, w' x h' (32 x 8 blocks, the image in blockIdx.z), the source w x h.
+ * The map, the inside test and the taps are A LENS's word for word with (j, i) running over the output and (fx', fy', cx', cy') the output camera.
+ * Beside the pixel the kernel writes ONE BYTE OF VALIDITY: a pixel is valid iff the inside test passed, every tap with a non-zero weight lies
+ * inside the source, and -- where the caller gave a mask in the source grid -- every such tap is non-zero in the mask.  A pixel outside is written 0
+ * as before; a pixel inside is written as A LENS writes it, valid or not.  border_mask == 0 leaves the first two conditions out: only the
+ * caller's mask makes a pixel invalid.
+ *   l3d_remap.lens        NULL: nothing is resampled, the mask is the validity plane (out size: 0 or the source's).  model 0, or BROWN with every
+ *                         coefficient within 1e-12: a pinhole camera -- with the cameras and the sizes equal nothing is launched, otherwise the
+ *                         image is resampled through the same kernel
+ *   out_width, out_height the output size; both 0: the source's.  A size that differs from the source's without a lens: L3D_ERR_INVALID
+ *   mask                  NULL, or width x height bytes in the SOURCE grid, rows mask_row_stride bytes apart, non-zero = valid.  mask_width and
+ *                         mask_height state the plane's extent: they must be the source image's (a file's: its headers'), else L3D_ERR_INVALID
+ *                         before anything is read -- the library reads width x height bytes and has no other way to know.  mask_on_device: it
+ *                         is device memory (checked as an l3d_device_image is: memory kind and extent, L3D_ERR_INVALID), else host memory
+ *   l3d_undistort_image_remap, l3d_undistort_image_device_remap
+ *                         out: out_width x out_height pixels of the input's channels.  valid: NULL, or the validity plane, one byte per output
+ *                         pixel, 255 = valid and 0 = invalid (the device call: a one-channel L3D_U8 image of the output size).  The calls with a
+ *                         lens and without out size, mask or validity output are l3d_undistort_image[_device]_lens.
+ *
+ * THE VALIDITY PLANE THROUGH THE DETECTOR (k_det_valid_grey, k_det_valid_x, k_det_valid_y, k_det_valid_apply).  One rule: A GRADIENT PIXEL IS
+ * UNDEFINED IF ANY PIXEL THAT CONTRIBUTED TO ITS VALUE IS INVALID.  The plane is carried beside the pixel stages, one AND over each stage's taps:
+ *     the rescale     where the detector rescales, the 2 x 2 taps of the rescale's rule whose weight ((256 - a) or a, times (256 - b) or b) is not
+ *                     zero; otherwise the pixel itself
+ *     the sampler     the 7 taps about the centre xc = floor(x / 0.8 + 0.5) of every output column, then the 7 about yc of every output row, an
+ *                     index outside the image reflected as the sampler reflects it (symmetric boundary)
+ *     the gradient    the 2 x 2 stencil (x, y), (x + 1, y), (x, y + 1), (x + 1, y + 1), clipped at the last column and row
+ * and one kernel behind the gradient gives an undefined pixel what a pixel below the gradient threshold has: magnitude 0, no angle, no bucket,
+ * inactive.  No line-support region starts at or grows into such a pixel; inside a candidate rectangle it counts as a point that is not aligned.
+ * What the invalid pixels HOLD therefore cannot reach the segments.  The gradient kernel and everything behind it are unchanged, a call without a
+ * remap launches what it launched before, and an all-valid plane gives the bytes of the call without one.
+ *   l3d_detect_segments_batch_remap, l3d_detect_segments_device_batch_remap
+ *                         the batch calls with, beside the entry array, an array of n remap pointers (the array or an element may be NULL: the
+ *                         entry's own camera rule).  With a lens in the remap the entry's camera must be given: its fx, fy, cx, cy are the output
+ *                         camera, its k1, k2 must be 0 (L3D_ERR_INVALID otherwise).  The detector sees the remap's OUTPUT: new_width, new_height,
+ *                         min_length and the segments' pixel coordinates refer to it, and an output below 8 x 8 is refused as a source is.
+ *                         Entries run together when their source sizes AND their output sizes (and working sizes) agree.  A chunk in which a
+ *                         remap resamples an image launches k_det_undistort_remap once and neither of the other two undistortion kernels: a
+ *                         plain lens and a k1, k2 camera go through it with the same bytes and an all-valid plane, an image without a camera
+ *                         is copied.  A chunk whose remaps are masks alone resamples nothing: the masks are the planes.  A chunk without a remap
+ *                         launches none of the new kernels.  A remap that asks for nothing (a lens alone, border_mask 0, no mask, the source's
+ *                         size) is the ..._lens call.  A refused entry fails alone. */
+typedef struct l3d_remap {
+    const l3d_lens* lens;
+    int32_t out_width, out_height;
+    const void* mask;
+    size_t mask_row_stride;
+    int32_t mask_width, mask_height;
+    int32_t mask_on_device;
+    int32_t border_mask;
+} l3d_remap;
+int l3d_undistort_plan(const l3d_lens* lens, int width, int height, double alpha, int out_width, int out_height, int max_dim, double fov_max_deg,
+                       double K_out[9], int* w_out, int* h_out);
+const char* l3d_undistort_plan_error(void);
+int l3d_undistort_image_remap(l3d_ctx* ctx, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, double fx, double fy, double cx,
+                              double cy, const l3d_remap* remap, unsigned char* out, size_t out_row_stride, unsigned char* valid, size_t valid_row_stride);
 /* Line3D::addImage / addImage_fixed_sim from pixels (line3D.cc:95-217, 220-324): the image entry (THE ADD FAMILY, below) with pixels filled and no
  * dist.  The detector runs at the size the max_img_width rule gives, with min_length = 0.005 sqrt(rows^2 + cols^2) and at most 3000 segments. */
 int l3d_line3d_add_image_pixels(l3d_line3d* h, uint32_t image_id, const unsigned char* pixels, int width, int height, int channels, size_t row_stride,
@@ -995,6 +1083,12 @@ typedef struct l3d_detect_entry {
     const double* camera;                                                           /* NULL, or fx, fy, cx, cy, k1, k2 */
 } l3d_detect_entry;
 int l3d_detect_segments_batch(l3d_ctx* ctx, const l3d_detect_entry* e, int n, float** segments, int* offsets /* n + 1 */, int* status /* n */);
+/* with remaps (A REMAP, above): remap NULL, or n pointers of which any may be NULL (then the entry's own camera rule) */
+int l3d_detect_segments_batch_remap(l3d_ctx* ctx, const l3d_detect_entry* e, const l3d_remap* const* remap, int n, float** segments, int* offsets /* n + 1 */,
+                                    int* status /* n */);
+/* (tests) the defined / undefined plane of A REMAP, N x M bytes (255 = defined), that the last detector call of the context left for the first image
+ * of its last chunk; *N = *M = 0 when that chunk carried no validity plane.  capacity: the bytes `defined` can take */
+int l3d_test_detect_defined_plane(l3d_ctx* ctx, unsigned char* defined, size_t capacity, int* N, int* M);
 /* with lenses (A LENS, above): lens NULL, or n pointers of which any may be NULL */
 int l3d_detect_segments_batch_lens(l3d_ctx* ctx, const l3d_detect_entry* e, const l3d_lens* const* lens, int n, float** segments, int* offsets /* n + 1 */,
                                    int* status /* n */);
@@ -1076,11 +1170,17 @@ int l3d_detect_segments_device_batch(l3d_ctx* ctx, const l3d_detect_device_entry
 int l3d_decode_jpeg_device(l3d_ctx* ctx, const unsigned char* bytes, size_t n, const l3d_device_image* out);
 int l3d_undistort_image_device(l3d_ctx* ctx, const l3d_device_image* in, double fx, double fy, double cx, double cy, double k1, double k2,
                                const l3d_device_image* out);
+/* with remaps (A REMAP, above): remap NULL, or n pointers of which any may be NULL; the entry's camera is the output camera */
+int l3d_detect_segments_device_batch_remap(l3d_ctx* ctx, const l3d_detect_device_entry* e, const l3d_remap* const* remap, int n, float** segments, int* offsets,
+                                           int* status);
 /* with lenses (A LENS, above); fx, fy, cx, cy: the output camera */
 int l3d_detect_segments_device_batch_lens(l3d_ctx* ctx, const l3d_detect_device_entry* e, const l3d_lens* const* lens, int n, float** segments,
                                           int* offsets /* n + 1 */, int* status /* n */);
 int l3d_undistort_image_device_lens(l3d_ctx* ctx, const l3d_device_image* in, double fx, double fy, double cx, double cy, const l3d_lens* lens,
                                     const l3d_device_image* out);
+/* A REMAP (above): out of remap's output size; valid: NULL, or a one-channel L3D_U8 image of that size */
+int l3d_undistort_image_device_remap(l3d_ctx* ctx, const l3d_device_image* in, double fx, double fy, double cx, double cy, const l3d_remap* remap,
+                                     const l3d_device_image* out, const l3d_device_image* valid);
 
 /* =================================================================================================
  * THE ADD FAMILY: Line3D::addImage / addImage_fixed_sim (line3D.cc:95-342) in every form the library takes an image in.
@@ -1137,6 +1237,16 @@ int l3d_line3d_add_images(l3d_line3d* h, const l3d_image_entry* e, int n, const 
  * lens's source camera onto the entry's K, which the view keeps.  lens: NULL (then exactly the calls above), or one pointer per entry of which any
  * may be NULL: that entry's own dist rule */
 int l3d_line3d_add_image_entry_lens(l3d_line3d* h, const l3d_image_entry* e, const l3d_lens* lens, const char* data_directory, int max_img_width, int load_and_store);
+/* The entry with a remap (A REMAP, above) in the place of dist and lens -- an entry that also carries dist: L3D_ERR_INVALID.  The entry's K is the
+ * OUTPUT camera and the view's K; the view's width and height are the remap's OUTPUT size, which therefore also names the segment cache file;
+ * max_img_width acts on the output size; a cache that is present and wanted still stands in for the image.  Skew (K[1] != 0) with a remap that
+ * resamples: L3D_ERR_UNSUPPORTED.  remap: NULL (then exactly the calls above), or one pointer per entry of which any may be NULL */
+/* l3d_undistort_image_remap with the object's device and K, the output camera (a skewed K with a remap that resamples: refused) */
+int l3d_line3d_undistort_image_remap(l3d_line3d* h, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, const double* K,
+                                     const l3d_remap* remap, unsigned char* out, size_t out_row_stride, unsigned char* valid, size_t valid_row_stride);
+int l3d_line3d_add_image_entry_remap(l3d_line3d* h, const l3d_image_entry* e, const l3d_remap* remap, const char* data_directory, int max_img_width, int load_and_store);
+int l3d_line3d_add_images_remap(l3d_line3d* h, const l3d_image_entry* e, const l3d_remap* const* remap, int n, const char* data_directory, int max_img_width,
+                                int load_and_store, int* status);
 int l3d_line3d_add_images_lens(l3d_line3d* h, const l3d_image_entry* e, const l3d_lens* const* lens, int n, const char* data_directory, int max_img_width,
                                int load_and_store, int* status);
 int l3d_line3d_undistort_image_lens(l3d_line3d* h, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, const double* K,
@@ -1166,6 +1276,10 @@ int l3d_line3d_decode_jpeg_device(l3d_line3d* h, const unsigned char* bytes, siz
 int l3d_line3d_undistort_image_device(l3d_line3d* h, const l3d_device_image* in, const double* K, double k1, double k2, const l3d_device_image* out);
 /* the device entry with a lens: as l3d_line3d_add_image_entry_lens / l3d_line3d_add_images_lens */
 int l3d_line3d_add_device_entry_lens(l3d_line3d* h, const l3d_device_entry* e, const l3d_lens* lens, const char* data_directory, int max_img_width, int load_and_store);
+/* the device entry with a remap: as l3d_line3d_add_image_entry_remap / l3d_line3d_add_images_remap */
+int l3d_line3d_add_device_entry_remap(l3d_line3d* h, const l3d_device_entry* e, const l3d_remap* remap, const char* data_directory, int max_img_width, int load_and_store);
+int l3d_line3d_add_device_images_remap(l3d_line3d* h, const l3d_device_entry* e, const l3d_remap* const* remap, int n, const char* data_directory, int max_img_width,
+                                       int load_and_store, int* status);
 int l3d_line3d_add_device_images_lens(l3d_line3d* h, const l3d_device_entry* e, const l3d_lens* const* lens, int n, const char* data_directory, int max_img_width,
                                       int load_and_store, int* status);
 

@@ -246,6 +246,101 @@ def lens_pointers(lenses, n):
     return arr, lenses
 
 
+# l3d_remap (include/line3d_amd.h, "A REMAP")
+class Remap(C.Structure):
+    """l3d_remap: the lens, the output size (0, 0: the source's), the caller's mask in the source grid, and whether blank pixels are invalid"""
+    _fields_ = [("lens", C.c_void_p), ("out_width", C.c_int32), ("out_height", C.c_int32), ("mask", C.c_void_p), ("mask_row_stride", C.c_size_t), ("mask_width", C.c_int32), ("mask_height", C.c_int32),
+                ("mask_on_device", C.c_int32), ("border_mask", C.c_int32)]
+
+
+def remap(lens=None, out_size=None, mask=None, border_mask=True):
+    """An l3d_remap.  lens: capi.lens(...) or None; out_size = (width, height), None: the source's; mask: None, a uint8 / bool array H x W in the
+    SOURCE grid (non-zero = valid), or a device object of that shape (a torch uint8 device tensor, anything with __cuda_array_interface__);
+    border_mask: pixels the resampling leaves blank are invalid.  What it points at is kept alive on the returned object."""
+    r = Remap()
+    r._keep = []
+    if lens is not None:
+        if not isinstance(lens, Lens):
+            raise TypeError("lens must come from capi.lens()")
+        r.lens = C.addressof(lens)
+        r._keep.append(lens)
+    if out_size is not None:
+        r.out_width, r.out_height = int(out_size[0]), int(out_size[1])
+    if mask is not None:
+        if hasattr(mask, "__cuda_array_interface__"):
+            iface = mask.__cuda_array_interface__
+            shape, strides = tuple(iface["shape"]), iface.get("strides")
+            if len(shape) != 2 or str(iface["typestr"]) not in ("|u1", "|b1") or (strides is not None and int(strides[1]) != 1):
+                raise TypeError("a device mask must be an H x W array of bytes whose rows are contiguous")
+            r.mask, r.mask_row_stride, r.mask_on_device = int(iface["data"][0]), int(shape[1] if strides is None else strides[0]), 1
+            r._keep.append(mask)
+            r._mask_shape = (int(shape[0]), int(shape[1]))
+            r.mask_height, r.mask_width = r._mask_shape
+        else:
+            m = np.asarray(mask)
+            if m.ndim != 2 or m.dtype not in (np.uint8, np.bool_):
+                raise TypeError("mask must be a uint8 or bool array H x W")
+            m = np.ascontiguousarray(m).view(np.uint8)
+            r.mask, r.mask_row_stride, r.mask_on_device = m.ctypes.data, m.strides[0], 0
+            r._keep.append(m)
+            r._mask_shape = m.shape
+            r.mask_height, r.mask_width = m.shape
+    r.border_mask = 1 if border_mask else 0
+    return r
+
+
+def remap_of(lens, out_size, mask, border_mask, source_size):
+    """The Remap of the lens=, out_size=, mask=, border_mask= keywords (None when only a lens, or nothing, was given: the call as it was);
+    source_size = (width, height) of the image the mask must match"""
+    if out_size is None and mask is None and border_mask is None:
+        return None
+    r = remap(lens, out_size, mask, True if border_mask is None else border_mask)
+    if mask is not None and tuple(r._mask_shape) != (int(source_size[1]), int(source_size[0])):
+        raise ValueError("mask: shape %s, the source image is %d x %d (H x W)" % (tuple(r._mask_shape), source_size[1], source_size[0]))
+    return r
+
+
+def undistort_plan(lens_, size, alpha=0.0, out_size=None, max_dim=0, fov_max_deg=120.0):
+    """l3d_undistort_plan (host, no context and no device): the output camera and size for a lens that carries its source camera.
+    size = (width, height) of the source image; alpha in [0, 1]: 0 = no blank pixel in the output, 1 = every source pixel inside fov_max_deg is
+    kept; out_size: (width, height), None for the source size, or "keep_focal" / (-1, -1) for the size at which fx' = fx, scaled down to max_dim
+    when that is positive.  -> (K 3 x 3 float64, (width, height)).  A refusal raises L3DError carrying the status in .code."""
+    lib = load_library()
+    lib.l3d_undistort_plan_error.restype = C.c_char_p
+    if not isinstance(lens_, Lens):
+        raise TypeError("lens must come from capi.lens()")
+    ow, oh = (0, 0) if out_size is None else (-1, -1) if isinstance(out_size, str) and out_size == "keep_focal" else (int(out_size[0]), int(out_size[1]))
+    K = np.zeros(9, np.float64)
+    w, h = C.c_int(0), C.c_int(0)
+    rc = lib.l3d_undistort_plan(C.byref(lens_), C.c_int(int(size[0])), C.c_int(int(size[1])), C.c_double(float(alpha)), C.c_int(ow), C.c_int(oh),
+                                C.c_int(int(max_dim)), C.c_double(float(fov_max_deg)), _p(K), C.byref(w), C.byref(h))
+    if rc != 0:
+        e = L3DError("line3d_amd error %d: %s" % (rc, lib.l3d_undistort_plan_error().decode()))
+        e.code = rc
+        raise e
+    return K.reshape(3, 3), (w.value, h.value)
+
+
+
+def remap_pointers(lenses, out_sizes, masks, border_masks, n):
+    """the `const l3d_remap* const*` argument of the ..._remap calls, or None when no image asks for another size, a mask or a border rule (then
+    the ..._lens call, or the plain one, is the call to make), and what keeps it alive.  An image with only a lens gets a remap that says nothing more
+    (border_mask 0): the library treats it as the lens alone"""
+    lenses, out_sizes, masks, border_masks = (_per_image(v, n, what) for v, what in ((lenses, "lenses"), (out_sizes, "out_sizes"), (masks, "masks"),
+                                                                                     (border_masks, "border_masks")))
+    if all(o is None and m is None and b is None for o, m, b in zip(out_sizes, masks, border_masks)):
+        return None, []
+    arr, keep = (C.c_void_p * max(1, n))(), [None] * n             # (keep: one entry per image)
+    for i in range(n):
+        asks = out_sizes[i] is not None or masks[i] is not None or border_masks[i] is not None
+        if not asks and lenses[i] is None:
+            continue
+        r = remap(lenses[i], out_sizes[i], masks[i], (True if border_masks[i] is None else border_masks[i]) if asks else False)
+        arr[i] = C.addressof(r)
+        keep[i] = r
+    return arr, keep
+
+
 # dtype codes of l3d_device_image (L3D_U8 ...)
 U8, U16, F16, F32 = 0, 1, 2, 3
 _TYPESTR = {"|u1": U8, "<u2": U16, "<f2": F16, "<f4": F32}
@@ -362,18 +457,18 @@ def device_image_extent(d):
     return int(rc), int(lo.value), int(hi.value)
 
 
-def detect_device_entries(images, new_sizes=None, min_lengths=None, max_segments=3000, cameras=None, lenses=None):
+def detect_device_entries(images, new_sizes=None, min_lengths=None, max_segments=3000, cameras=None, lenses=None, out_sizes=None):
     """The l3d_detect_device_entry array of Context.detect_segments_batch for a list of device objects, and what keeps its pointers alive"""
     images = [device_image(im) for im in images]
     n = len(images)
     new_sizes, min_lengths, cameras = _per_image(new_sizes, n, "new_sizes"), _per_image(min_lengths, n, "min_lengths"), _per_image(cameras, n, "cameras")
-    lenses = _per_image(lenses, n, "lenses")
+    lenses, out_sizes = _per_image(lenses, n, "lenses"), _per_image(out_sizes, n, "out_sizes")
     caps = [int(max_segments)] * n if np.isscalar(max_segments) else [int(v) for v in _per_image(max_segments, n, "max_segments")]
     entries, keep = (DetectDeviceEntry * max(1, n))(), list(images)
     for i, im in enumerate(images):
         e = entries[i]
         e.image = im
-        w, h = im.width, im.height
+        w, h = (im.width, im.height) if out_sizes[i] is None else (int(out_sizes[i][0]), int(out_sizes[i][1]))       # (a remap's output: what the detector sees)
         e.new_width, e.new_height = (w, h) if new_sizes[i] is None else (int(new_sizes[i][0]), int(new_sizes[i][1]))
         e.min_length = float(np.float32(0.005) * np.sqrt(np.float32(h * h + w * w))) if min_lengths[i] is None else float(min_lengths[i])
         e.max_segments = caps[i]
@@ -429,13 +524,13 @@ def _per_image(value, n, what):
     return value
 
 
-def detect_entries(images, new_sizes=None, min_lengths=None, max_segments=3000, cameras=None, lenses=None):
+def detect_entries(images, new_sizes=None, min_lengths=None, max_segments=3000, cameras=None, lenses=None, out_sizes=None):
     """The l3d_detect_entry array of Context.detect_segments_batch, and what keeps its pointers alive.  Everything malformed is refused here,
     before any device call: an image that is neither a uint8 array nor bytes, a camera that is not six numbers, lists of the wrong length."""
     images = list(images)
     n = len(images)
     new_sizes, min_lengths, cameras = _per_image(new_sizes, n, "new_sizes"), _per_image(min_lengths, n, "min_lengths"), _per_image(cameras, n, "cameras")
-    lenses = _per_image(lenses, n, "lenses")
+    lenses, out_sizes = _per_image(lenses, n, "lenses"), _per_image(out_sizes, n, "out_sizes")
     caps = [int(max_segments)] * n if np.isscalar(max_segments) else [int(v) for v in _per_image(max_segments, n, "max_segments")]
     entries, keep = (DetectEntry * max(1, n))(), []
     for i, img in enumerate(images):
@@ -453,6 +548,8 @@ def detect_entries(images, new_sizes=None, min_lengths=None, max_segments=3000, 
         else:
             raise TypeError("image %d must be a uint8 array or the bytes of a JPEG file" % i)
         keep.append(ptr)
+        if out_sizes[i] is not None:            # a remap's output: what the detector sees
+            w, h = int(out_sizes[i][0]), int(out_sizes[i][1])
         e.new_width, e.new_height = (w, h) if new_sizes[i] is None else (int(new_sizes[i][0]), int(new_sizes[i][1]))
         e.min_length = float(np.float32(0.005) * np.sqrt(np.float32(h * h + w * w))) if min_lengths[i] is None else float(min_lengths[i])
         e.max_segments = caps[i]
@@ -565,14 +662,21 @@ class Context:
         self._chk(self.lib.l3d_register_segments(self.h, _p(segs), C.c_int(len(segs))))
 
     # -- line segment detection (l3d_detect.hip) --------------------------------------------------
-    def undistort(self, img, K, k1=None, k2=None, lens=None, in_place=False):
+    def undistort(self, img, K, k1=None, k2=None, lens=None, in_place=False, out_size=None, mask=None, border_mask=None, return_mask=False):
         """l3d_undistort_image: uint8 image H x W or H x W x 3 -> the undistorted image, same shape (initUndistortRectifyMap + remap of the drivers,
         the formulas of include/line3d_amd.h).  K: 3 x 3, its fx, fy, cx, cy are used; k1, k2: OpenCV-convention radial coefficients.
         A device object (device_image) stays on the device (l3d_undistort_image_device): the result is a torch uint8 tensor of the input's
         shape on its device.
         lens (capi.lens(...)) in the place of k1, k2: l3d_undistort_image[_device]_lens -- tangential, rational and fisheye models, resampled from
-        the lens's source camera onto K.  in_place (with a lens): a host array is overwritten and returned, a device object is its own output."""
+        the lens's source camera onto K.  in_place (with a lens): a host array is overwritten and returned, a device object is its own output.
+        out_size, mask, border_mask, return_mask (any of them: l3d_undistort_image[_device]_remap, "A REMAP"): the output has out_size =
+        (width, height); mask (capi.remap's) is the caller's validity in the source grid; return_mask: -> (image, validity plane), the plane
+        H' x W' uint8 with 255 = valid -- a torch tensor where the image is one."""
         K = np.asarray(K, dtype=np.float64).reshape(3, 3)
+        if out_size is not None or mask is not None or border_mask is not None or return_mask:
+            if k1 is not None or k2 is not None or in_place:
+                raise ValueError("out_size, mask, border_mask and return_mask go with a lens (or none), not with k1, k2 or in_place")
+            return self._undistort_remap(img, K, lens, out_size, mask, border_mask, return_mask)
         if lens is not None:
             if k1 is not None or k2 is not None:
                 raise ValueError("undistort takes k1, k2 or a lens, not both")
@@ -591,6 +695,30 @@ class Context:
                                                C.c_double(K[0, 2]), C.c_double(K[1, 2]), C.c_double(float(k1)), C.c_double(float(k2)), _p(out),
                                                C.c_size_t(w * ch)))
         return out
+
+    def _undistort_remap(self, img, K, lens_, out_size, mask, border_mask, return_mask):
+        cam = [C.c_double(K[0, 0]), C.c_double(K[1, 1]), C.c_double(K[0, 2]), C.c_double(K[1, 2])]
+        if is_device_object(img):
+            import torch
+            d = device_image(img)
+            r = remap(lens_, out_size, mask, True if border_mask is None else border_mask)
+            ow, oh = (d.width, d.height) if out_size is None else (int(out_size[0]), int(out_size[1]))
+            src = getattr(d, "_keep", None)
+            dev = src.device if src is not None and type(src).__module__.split(".")[0] == "torch" else "cuda:%d" % getattr(self, "device", 0)
+            out = torch.zeros((max(oh, 0), max(ow, 0)) if d.channels == 1 else (max(oh, 0), max(ow, 0), 3), dtype=torch.uint8, device=dev)
+            valid = torch.zeros((max(oh, 0), max(ow, 0)), dtype=torch.uint8, device=dev)
+            o = device_image(out, chan=tuple(d.chan) if d.channels != 1 else None, scale=1.0, stream=d.stream or 0) if out.numel() else DeviceImage()
+            v = device_image(valid, scale=1.0, stream=d.stream or 0) if valid.numel() else DeviceImage()
+            self._chk(self.lib.l3d_undistort_image_device_remap(self.h, C.byref(d), *cam, C.byref(r), C.byref(o), C.byref(v) if return_mask else None))
+            return (out, valid) if return_mask else out
+        pix, w, h, ch, stride = image_arguments(img)
+        r = remap_of(lens_, out_size, mask, border_mask, (w, h)) or remap(lens_)
+        ow, oh = (w, h) if out_size is None else (int(out_size[0]), int(out_size[1]))
+        out = np.zeros((max(oh, 0), max(ow, 0)) + np.asarray(img).shape[2:], np.uint8)
+        valid = np.zeros((max(oh, 0), max(ow, 0)), np.uint8)
+        self._chk(self.lib.l3d_undistort_image_remap(self.h, pix, C.c_int(w), C.c_int(h), C.c_int(ch), C.c_size_t(stride), *cam, C.byref(r), _p(out),
+                                                     C.c_size_t(max(ow, 0) * ch), _p(valid) if return_mask else None, C.c_size_t(max(ow, 0))))
+        return (out, valid) if return_mask else out
 
     def _undistort_lens(self, img, K, lens_, in_place):
         cam = [C.c_double(K[0, 0]), C.c_double(K[1, 1]), C.c_double(K[0, 2]), C.c_double(K[1, 2])]
@@ -611,7 +739,7 @@ class Context:
         self._chk(self.lib.l3d_undistort_image_lens(self.h, pix, C.c_int(w), C.c_int(h), C.c_int(ch), C.c_size_t(stride), *cam, C.byref(lens_), _p(out), C.c_size_t(w * ch)))
         return out
 
-    def detect_segments(self, img, new_size=None, min_length=None, max_segments=3000, camera=None, lens=None):
+    def detect_segments(self, img, new_size=None, min_length=None, max_segments=3000, camera=None, lens=None, out_size=None, mask=None, border_mask=None):
         """l3d_detect_segments: uint8 image H x W or H x W x 3 (contiguous pixels, rows contiguous or strided) -> (n, 4) float32 segments
         (x1, y1, x2, y2) in pixels of `img`, longest first.  new_size = (width, height) the detector works at (None: the image's own);
         min_length None: the reference's 0.005 x the image diagonal.  camera = (fx, fy, cx, cy, k1, k2): the image is undistorted on the device
@@ -619,7 +747,11 @@ class Context:
         A device object (a torch device tensor, anything with __cuda_array_interface__, a device_image descriptor) is read where it lies
         (l3d_detect_segments_device): the segments are those of the host call on the converted pixels.
         lens (capi.lens(...)): the image is undistorted with it first, onto camera = (fx, fy, cx, cy) (None: the lens's own source camera) -- a
-        batch of one through l3d_detect_segments[_device]_batch_lens."""
+        batch of one through l3d_detect_segments[_device]_batch_lens.  out_size, mask, border_mask: as detect_segments_batch's out_sizes, masks,
+        border_masks -- a batch of one through l3d_detect_segments[_device]_batch_remap."""
+        if out_size is not None or mask is not None or border_mask is not None:
+            return self.detect_segments_batch([img], None if new_size is None else [new_size], None if min_length is None else [min_length], max_segments, [camera],
+                                              lenses=[lens], out_sizes=[out_size], masks=[mask], border_masks=[border_mask])[0]
         if lens is not None:
             return self.detect_segments_batch([img], None if new_size is None else [new_size], None if min_length is None else [min_length], max_segments, [camera], lenses=[lens])[0]
         if is_device_object(img):
@@ -674,8 +806,11 @@ class Context:
         self._chk(self.lib.l3d_decode_jpeg(self.h, ptr, n, _p(out), C.c_size_t(w * ch)))
         return out
 
-    def detect_segments_jpeg(self, data, new_size=None, min_length=None, max_segments=3000, camera=None, lens=None):
+    def detect_segments_jpeg(self, data, new_size=None, min_length=None, max_segments=3000, camera=None, lens=None, out_size=None, mask=None, border_mask=None):
         """l3d_detect_segments_jpeg: detect_segments on the image of a baseline JPEG file, decoded on the device (arguments as detect_segments)"""
+        if out_size is not None or mask is not None or border_mask is not None:
+            return self.detect_segments_batch([bytes(data)], None if new_size is None else [new_size], None if min_length is None else [min_length], max_segments, [camera],
+                                              lenses=[lens], out_sizes=[out_size], masks=[mask], border_masks=[border_mask])[0]
         if lens is not None:
             return self.detect_segments_batch([bytes(data)], None if new_size is None else [new_size], None if min_length is None else [min_length], max_segments, [camera], lenses=[lens])[0]
         w, h, _ = jpeg_info(data)
@@ -696,7 +831,8 @@ class Context:
         return segs
 
     # -- images in batches: one pass of the detector over many images ---------------------------------
-    def detect_segments_batch(self, images, new_sizes=None, min_lengths=None, max_segments=3000, cameras=None, return_status=False, lenses=None):
+    def detect_segments_batch(self, images, new_sizes=None, min_lengths=None, max_segments=3000, cameras=None, return_status=False, lenses=None,
+                              out_sizes=None, masks=None, border_masks=None):
         """l3d_detect_segments_batch: a list of images -- uint8 arrays (as detect_segments takes them) or `bytes` of baseline JPEG files (as
         detect_segments_jpeg takes them) -> a list of (n, 4) float32 arrays, each byte for byte what the single call gives for that image.
         new_sizes, min_lengths, max_segments, cameras: None, one value for all (max_segments), or a list with one entry (possibly None) per image,
@@ -705,14 +841,28 @@ class Context:
         A list of device objects (as detect_segments takes them) goes through l3d_detect_segments_device_batch; a list that mixes them with
         host images or files raises ValueError before any call.
         lenses: None, or a list with one capi.lens(...) or None per image (l3d_detect_segments[_device]_batch_lens); an image with a lens is
-        undistorted onto its entry of cameras, (fx, fy, cx, cy) -- None: the lens's own source camera."""
+        undistorted onto its entry of cameras, (fx, fy, cx, cy) -- None: the lens's own source camera.
+        out_sizes, masks, border_masks (lists with one entry or None per image; l3d_detect_segments[_device]_batch_remap, "A REMAP"): the image is
+        resampled onto out_size = (width, height) -- which new_size and min_length then default from --, mask (capi.remap's) is the caller's
+        validity plane in the source grid, and border_mask (default true where one of the three is given) makes the blank pixels of the
+        resampling invalid: no line-support region starts where an invalid pixel contributed to the gradient."""
         images = list(images)
         on_device = all_device_objects(images, "detect_segments_batch")
-        entries, keep = (detect_device_entries if on_device else detect_entries)(images, new_sizes, min_lengths, max_segments, cameras, lenses)
+        entries, keep = (detect_device_entries if on_device else detect_entries)(images, new_sizes, min_lengths, max_segments, cameras, lenses, out_sizes)
         n = len(images)
         out, offsets, status = C.POINTER(C.c_float)(), (C.c_int * (n + 1))(), (C.c_int * max(1, n))()
+        remap_arr, remap_keep = remap_pointers(lenses, out_sizes, masks, border_masks, n)
+        # a mask is in the grid of the image as it arrives: an early ValueError where the size is at hand (the library refuses a mask whose stated
+        # extent, l3d_remap.mask_width x mask_height, is not the source's on every path -- a file's size it reads from the headers)
+        for i, r in enumerate(remap_keep):
+            src = (entries[i].image.height, entries[i].image.width) if on_device else (entries[i].height, entries[i].width)
+            if remap_arr is not None and getattr(r, "_mask_shape", None) is not None and src[0] > 0 and tuple(r._mask_shape) != src:
+                raise ValueError("mask: shape %s, the source image is %d x %d (H x W)" % (tuple(r._mask_shape), src[0], src[1]))
         lens_arr, lens_keep = lens_pointers(lenses, n)
-        if lens_arr is not None:
+        if remap_arr is not None:
+            call = self.lib.l3d_detect_segments_device_batch_remap if on_device else self.lib.l3d_detect_segments_batch_remap
+            rc = call(self.h, entries, remap_arr, C.c_int(n), C.byref(out), offsets, status)
+        elif lens_arr is not None:
             call = self.lib.l3d_detect_segments_device_batch_lens if on_device else self.lib.l3d_detect_segments_batch_lens
             rc = call(self.h, entries, lens_arr, C.c_int(n), C.byref(out), offsets, status)
         else:
@@ -757,6 +907,17 @@ class Context:
         self._chk(self.lib.l3d_decode_jpeg_device(self.h, ptr, n, C.byref(o)))
 
     # -- the detector's stages on their own (tests): the same kernels and launch shapes as detect_segments
+    def test_detect_defined_plane(self):
+        """l3d_test_detect_defined_plane: the defined / undefined plane (M, N) uint8, 255 = defined, that the last detector call left for the first
+        image of its last chunk; None when that chunk carried no validity plane"""
+        n, m = C.c_int(0), C.c_int(0)
+        self._chk(self.lib.l3d_test_detect_defined_plane(self.h, None, C.c_size_t(0), C.byref(n), C.byref(m)))
+        if n.value == 0 or m.value == 0:
+            return None
+        out = np.zeros((m.value, n.value), np.uint8)
+        self._chk(self.lib.l3d_test_detect_defined_plane(self.h, _p(out), C.c_size_t(out.size), C.byref(n), C.byref(m)))
+        return out
+
     def test_detect_pixel_stage(self, img, new_size=None):
         """l3d_test_detect_pixel_stage -> dict: grey (nh, nw) float32; img, mod, ang (M, N) float64; bucket (M, N, 2) uint8"""
         pix, w, h, ch, stride = image_arguments(img)

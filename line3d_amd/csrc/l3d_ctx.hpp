@@ -142,6 +142,11 @@ struct DetectBufs {
     // candidate; prm: what varies between the images of a chunk (camera, length filter, cap); lens: the chunk's lenses (k_det_undistort_lens), reserved
     // only when an image comes with one
     DevBuf lens;
+    // a remap (k_det_undistort_remap), reserved only when an image comes with one: the chunk's flags, the callers' masks in the source grid, and the
+    // validity plane in the output grid
+    DevBuf rflags, smask, valid;
+    // the validity plane beside the pixel stages (k_det_valid_*): after the rescale, after each sampler pass, and the defined / undefined plane at N x M
+    DevBuf vgrey, vaux, vimg, vdef;
     DevBuf pixels, undist, grey, aux, img, mod, ang, bucket, active, parent, size, count, keys, keys2, vals, vals2, flag, pos, start, tmp, cand, ckeys, ckeys2, cvals, cvals2, cimg, cimg2, prm, out, ktab, scal;
     // JPEG input (l3d_jpeg_device.hip), reserved only when a JPEG is decoded: the quantisation tables and the quantised coefficients as the host's entropy
     // decoder wrote them into the pinned `jstage`, and the uint8 component planes over whole MCUs
@@ -153,12 +158,14 @@ struct DetectBufs {
     std::vector<unsigned char> ingest_host;     // the table's host copy: it outlives the asynchronous upload (every call ends in a synchronise)
     hipEvent_t dev_event = nullptr;
     int tab_w = 0, tab_h = 0;       // the image size the Gaussian sampler's tables in `ktab` were made for
+    int vdef_n = 0, vdef_m = 0;     // the size of the defined / undefined plane the last pixel stage left in `vdef` (0: it carried no validity plane)
     void release()
     {
         for (DevBuf* x : all()) x->release();
         jstage.release();
         if (dev_event) { (void)hipEventDestroy(dev_event); dev_event = nullptr; }
         tab_w = tab_h = 0;
+        vdef_n = vdef_m = 0;
     }
     size_t held()                   // device bytes these buffers hold (the chunk rule counts them as available)
     {
@@ -168,7 +175,7 @@ struct DetectBufs {
     }
     std::vector<DevBuf*> all()
     {
-        return { &pixels, &undist, &grey, &aux, &img, &mod, &ang, &bucket, &active, &parent, &size, &count, &keys, &keys2, &vals, &vals2, &flag, &pos, &start, &tmp, &cand, &ckeys, &ckeys2, &cvals, &cvals2, &cimg, &cimg2, &prm, &out, &ktab, &scal, &jcoef, &jplanes, &ingest, &lens };
+        return { &pixels, &undist, &grey, &aux, &img, &mod, &ang, &bucket, &active, &parent, &size, &count, &keys, &keys2, &vals, &vals2, &flag, &pos, &start, &tmp, &cand, &ckeys, &ckeys2, &cvals, &cvals2, &cimg, &cimg2, &prm, &out, &ktab, &scal, &jcoef, &jplanes, &ingest, &lens, &rflags, &smask, &valid, &vgrey, &vaux, &vimg, &vdef };
     }
 };
 

@@ -36,6 +36,18 @@ DetLens make_lens(const l3d_lens& lens, double ofx, double ofy, double ocx, doub
 // the cause in err
 int lens_check(DetLens& lens, int width, int height, bool* active, std::string& err);
 
+// ---- a remap (include/line3d_amd.h, "A REMAP"): the lens as make_lens gives it (has_lens false: none; model 0: a pinhole camera), the output size
+// (0, 0: the source's), the caller's mask in the source grid
+struct DetRemap {
+    bool has_lens = false;
+    DetLens lens{};
+    int out_w = 0, out_h = 0;
+    const void* mask = nullptr;
+    size_t mask_stride = 0;
+    int mask_w = 0, mask_h = 0;                 // the extent the caller states for the mask: it must be the source's
+    bool mask_on_device = false, border_mask = true;
+};
+
 // pixels: host, `channels` (1 or 3) interleaved bytes per pixel, rows `row_stride` bytes apart.  out: 4 floats per segment.
 int detect_segments(l3d_ctx* c, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, int new_width, int new_height,
                     float min_length, int max_segments, std::vector<float>& out, const DetCamera* cam = nullptr, const DetLens* lens = nullptr);
@@ -54,6 +66,7 @@ struct DetEntry {
     const DetCamera* cam = nullptr;
     const DetLens* lens = nullptr;              // as make_lens gives it; checked per entry (lens_check)
     const l3d_device_image* dev = nullptr;      // a third source (pixels and jpeg null): an image in device memory (l3d_device_image.hip)
+    const DetRemap* remap = nullptr;            // a remap (then cam and lens are null): the lens as make_lens gives it, checked per entry (remap_check)
 };
 // out[i]: the segments detect_segments / detect_segments_jpeg gives for entry i alone, byte for byte.  Entries with the same sizes run together, in
 // chunks (option det_batch_images, the index widths, half of the free HBM).  status[i] / message[i]: what the single call would have returned and
@@ -70,6 +83,15 @@ int undistort_image_device(l3d_ctx* c, const l3d_device_image& in, const DetCame
 // host in, host out, same size and channels; coefficients at or below 1e-12: the pixels are copied.  lens given: it stands in for cam
 int undistort_image(l3d_ctx* c, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, const DetCamera& cam, unsigned char* out,
                     size_t out_row_stride, const DetLens* lens = nullptr);
+
+// ---- a remap's calls
+// the refusals of the header that need no device: L3D_OK with the output size and the lens resolved and *active set (false: nothing is resampled)
+int remap_check(DetRemap& r, int width, int height, int channels, bool* active, std::string& err);
+// host in, host out (out_w x out_h); valid: null, or out_w x out_h bytes, 255 / 0
+int undistort_image_remap(l3d_ctx* c, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, const DetRemap& remap, unsigned char* out,
+                          size_t out_row_stride, unsigned char* valid, size_t valid_row_stride);
+// device in, device out; valid: null, or a one-channel image of the output size
+int undistort_image_device_remap(l3d_ctx* c, const l3d_device_image& in, const DetRemap& remap, const l3d_device_image& out, const l3d_device_image* valid);
 
 // ---- JPEG input (l3d_jpeg.cpp, l3d_jpeg_device.hip): baseline files decoded into the detector's pixel buffer; three components come out B, G, R
 struct JpegFrame;

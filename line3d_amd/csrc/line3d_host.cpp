@@ -687,6 +687,7 @@ struct AddRequest {
     bool cache_rules = false;                       // the form has a data directory: every one but add_image, add_image_fixed_sim, add_image_cached
     bool dist_required = false;                     // the _distorted forms: a null dist is refused (elsewhere it means no distortion)
     const l3d_lens* lens = nullptr;                 // the ..._lens forms: a lens in the place of dist (both: refused)
+    const l3d_remap* remap = nullptr;               // the ..._remap forms ("A REMAP"): in the place of dist and lens; K is the output camera
     bool image() const { return kind == AddKind::Pixels || kind == AddKind::Jpeg || kind == AddKind::Device; }
 };
 enum class Cache { None, Load, Stale, Write };      // no cache rules or nothing to do | read the file | remove the file | note the file for prepare()
@@ -698,6 +699,9 @@ struct AddPlan {
     l3d::DetCamera cam;
     bool lens_on = false;                           // an active lens (then undistort is false): resampled from the lens's camera onto K
     l3d::DetLens lens;
+    bool remap_on = false;                          // a remap: width x height above are its OUTPUT (the view's size, the cache file's name)
+    l3d::DetRemap remap;
+    unsigned src_w = 0, src_h = 0;                  // the image as it arrives
     Cache cache = Cache::None;
     std::string file;                               // the cache file's path
     bool detect = false;
@@ -807,6 +811,25 @@ static int lens_for_add(l3d_line3d* h, const double* K, const double* dist, cons
     return 1;
 }
 
+// the same for a remap: K is the output camera.  L3D_OK with `out` filled as the detector takes it (it checks its own copy again) and the output size,
+// or the refusal's code: what remap_check refuses, and a skewed K where the remap resamples
+static int remap_for_add(l3d_line3d* h, const double* K, const l3d_remap& m, int width, int height, int channels, l3d::DetRemap& out, int& out_w, int& out_h)
+{
+    out = l3d::DetRemap();
+    out.has_lens = m.lens != nullptr;
+    if (out.has_lens) out.lens = l3d::make_lens(*m.lens, K[0], K[4], K[2], K[5]);
+    out.out_w = m.out_width; out.out_h = m.out_height;
+    out.mask = m.mask; out.mask_stride = m.mask_row_stride; out.mask_w = m.mask_width; out.mask_h = m.mask_height;
+    out.mask_on_device = m.mask_on_device != 0; out.border_mask = m.border_mask != 0;
+    l3d::DetRemap checked = out;
+    bool active = false;
+    std::string err;
+    if (const int rc = l3d::remap_check(checked, width, height, channels, &active, err)) return h->fail(rc, err.c_str());
+    if (active && K[1] != 0.0) return h->fail(L3D_ERR_UNSUPPORTED, "lens distortion with a skewed K (K[1] != 0) is not supported");
+    out_w = checked.out_w; out_h = checked.out_h;
+    return L3D_OK;
+}
+
 // steps 1 and 2.  A JPEG file's size (cache name, max_img_width rule) comes from its headers; the entropy-coded data is touched only when the detector runs
 static int add_plan(L* h, const AddRequest& rq, const char* data_directory, int max_img_width, int load_and_store, AddPlan& p)
 {
@@ -823,7 +846,16 @@ static int add_plan(L* h, const AddRequest& rq, const char* data_directory, int 
         const int rc = l3d_device_image_check(rq.dev, msg, sizeof(msg));
         if (rc != L3D_OK) return h->fail(rc, msg);
     }
-    if (rq.image()) {
+    p.src_w = (unsigned)std::max(0, width); p.src_h = (unsigned)std::max(0, height);
+    if (rq.image() && rq.remap) {               // a remap: checked at the source size, the view is its output
+        if (rq.lens || e.dist) return h->fail(L3D_ERR_INVALID, "undistortion: an entry carries a remap beside dist (k1, k2) or a lens");
+        if (!e.K) return h->fail(L3D_ERR_INVALID, "undistortion: K is null");
+        if (width <= 0 || height <= 0) return h->fail(L3D_ERR_INVALID, "image is empty!");
+        int out_w = 0, out_h = 0;
+        if (const int rc = remap_for_add(h, e.K, *rq.remap, width, height, p.channels == 1 ? 1 : 3, p.remap, out_w, out_h)) return rc;
+        p.remap_on = true;
+        width = out_w; height = out_h;
+    } else if (rq.image()) {
         const int with = rq.lens ? lens_for_add(h, e.K, e.dist, rq.lens, width, height, p.lens) : (e.dist || rq.dist_required) ? camera_for_add(h, e.K, e.dist, p.cam) : 0;
         if (with < 0) return -with;
         p.undistort = with != 0 && !rq.lens;
@@ -897,6 +929,20 @@ static int add_entry(L* h, const AddRequest& rq, const AddPlan& p, const std::ve
     return L3D_OK;
 }
 
+// the detector's entry for a request whose plan says detect (p does not move while the entry is in use: it points into it)
+static void det_entry(const AddRequest& rq, const AddPlan& p, l3d::DetEntry& d)
+{
+    const l3d_image_entry& e = rq.e;
+    d.pixels = e.pixels; d.width = (int)p.src_w; d.height = (int)p.src_h; d.channels = p.channels;
+    d.row_stride = e.jpeg ? (size_t)p.src_w * p.channels : e.row_stride;
+    d.jpeg = e.jpeg; d.jpeg_bytes = e.jpeg_bytes;
+    d.dev = rq.dev;
+    d.new_width = (int)p.new_w; d.new_height = (int)p.new_h; d.min_length = p.min_length; d.max_segments = 3000;
+    d.cam = p.undistort ? &p.cam : nullptr;
+    d.lens = p.lens_on ? &p.lens : nullptr;
+    d.remap = p.remap_on ? &p.remap : nullptr;
+}
+
 // the route for one request
 static int add_one(L* h, const AddRequest& rq, const char* data_directory = nullptr, int max_img_width = 0, int load_and_store = 0)
 {
@@ -907,6 +953,17 @@ static int add_one(L* h, const AddRequest& rq, const char* data_directory = null
     l3d_ctx* ctx = (h->node ? rank0(h) : h)->ctx;
     const l3d_image_entry& e = rq.e;
     std::vector<float> segs;
+    if (p.remap_on) {                           // a batch of one: the entry with its remap
+        l3d::DetEntry d;
+        det_entry(rq, p, d);
+        std::vector<std::vector<float>> outs;
+        std::vector<int> st;
+        std::vector<std::string> msg;
+        const int rc = l3d::detect_segments_batch(ctx, &d, 1, outs, st, msg);
+        if (rc != L3D_OK) return h->fail(rc, l3d_last_error(ctx));
+        if (st[0] != L3D_OK) return h->fail(st[0], msg[0].c_str());
+        return add_entry(h, rq, p, &outs[0]);
+    }
     const l3d::DetCamera* cam = p.undistort ? &p.cam : nullptr;
     const l3d::DetLens* lens = p.lens_on ? &p.lens : nullptr;
     // a JPEG file is decoded on the device into the detector -- only here, behind the cache decision
@@ -1020,6 +1077,22 @@ int l3d_line3d_undistort_image_lens(l3d_line3d* h, const unsigned char* pixels, 
     return rc == L3D_OK ? rc : h->fail(rc, l3d_last_error(owner->ctx));
 }
 
+// l3d_undistort_image_remap with the object's device and K, the output camera: out of the remap's output size, valid NULL or one byte per output pixel
+int l3d_line3d_undistort_image_remap(l3d_line3d* h, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, const double* K,
+                                     const l3d_remap* remap, unsigned char* out, size_t out_row_stride, unsigned char* valid, size_t valid_row_stride)
+{
+    if (!h) return L3D_ERR_INVALID;
+    L* owner = h->node ? rank0(h) : h;
+    if (!owner->ctx) return h->fail(L3D_ERR_INVALID, "no device context to undistort with");
+    if (!remap || !K) return h->fail(L3D_ERR_INVALID, "undistort: null argument");
+    if (width < 1 || height < 1) return h->fail(L3D_ERR_INVALID, "image is empty!");
+    l3d::DetRemap r;
+    int out_w = 0, out_h = 0;
+    if (const int rc = remap_for_add(h, K, *remap, width, height, channels == 1 ? 1 : 3, r, out_w, out_h)) return rc;
+    const int rc = l3d::undistort_image_remap(owner->ctx, pixels, width, height, channels, row_stride, r, out, out_row_stride, valid, valid_row_stride);
+    return rc == L3D_OK ? rc : h->fail(rc, l3d_last_error(owner->ctx));
+}
+
 // from a baseline JPEG file in memory: the entry with jpeg filled
 int l3d_line3d_add_image_jpeg(l3d_line3d* h, uint32_t id, const unsigned char* bytes, size_t n, const double* K, const double* R, const double* t, const double dist[2],
                               const uint32_t* worldpoints, int n_wps, const char* data_directory, int max_img_width, int load_and_store)
@@ -1043,6 +1116,16 @@ int l3d_line3d_add_image_entry_lens(l3d_line3d* h, const l3d_image_entry* e, con
     rq.lens = lens;
     return add_one(h, rq, data_directory, max_img_width, load_and_store);
 }
+// the entry with a remap ("A REMAP") in the place of dist and lens: K is the output camera, the view has the remap's output size
+int l3d_line3d_add_image_entry_remap(l3d_line3d* h, const l3d_image_entry* e, const l3d_remap* remap, const char* data_directory, int max_img_width, int load_and_store)
+{
+    if (!h) return L3D_ERR_INVALID;
+    if (!e) return h->fail(L3D_ERR_INVALID, "add_image_entry: null argument");
+    AddRequest rq;
+    if (const int rc = entry_request(h, *e, rq, true)) return rc;
+    rq.remap = remap;
+    return add_one(h, rq, data_directory, max_img_width, load_and_store);
+}
 int l3d_line3d_add_image_entry(l3d_line3d* h, const l3d_image_entry* e, const char* data_directory, int max_img_width, int load_and_store)
 {
     return l3d_line3d_add_image_entry_lens(h, e, nullptr, data_directory, max_img_width, load_and_store);
@@ -1061,19 +1144,12 @@ static int add_batch(L* h, std::vector<AddItem>& items, const char* data_directo
     todo.reserve((size_t)n);
     for (int i = 0; i < n; ++i) {
         AddItem& it = items[i];
-        const l3d_image_entry& e = it.rq.e;
         if (it.rc != L3D_OK) continue;          // refused when it was filled: msg says why
         it.rc = add_plan(h, it.rq, data_directory, max_img_width, load_and_store, it.p);
         if (it.rc != L3D_OK) { it.msg = h->err; continue; }
         if (!it.p.detect) continue;
         l3d::DetEntry d;
-        d.pixels = e.pixels; d.width = (int)it.p.width; d.height = (int)it.p.height; d.channels = it.p.channels;
-        d.row_stride = e.jpeg ? (size_t)it.p.width * it.p.channels : e.row_stride;
-        d.jpeg = e.jpeg; d.jpeg_bytes = e.jpeg_bytes;
-        d.dev = it.rq.dev;
-        d.new_width = (int)it.p.new_w; d.new_height = (int)it.p.new_h; d.min_length = it.p.min_length; d.max_segments = 3000;
-        d.cam = it.p.undistort ? &it.p.cam : nullptr;           // (items does not grow: the address holds)
-        d.lens = it.p.lens_on ? &it.p.lens : nullptr;
+        det_entry(it.rq, it.p, d);                              // (items does not grow: the addresses hold)
         it.detect_at = (int)todo.size();
         todo.push_back(d);
     }
@@ -1112,6 +1188,19 @@ int l3d_line3d_add_images_lens(l3d_line3d* h, const l3d_image_entry* e, const l3
     }
     return add_batch(h, items, data_directory, max_img_width, load_and_store, status);
 }
+int l3d_line3d_add_images_remap(l3d_line3d* h, const l3d_image_entry* e, const l3d_remap* const* remap, int n, const char* data_directory, int max_img_width,
+                                int load_and_store, int* status)
+{
+    if (!h) return L3D_ERR_INVALID;
+    if (n < 0 || (n > 0 && !e)) return h->fail(L3D_ERR_INVALID, "add_images: null argument");
+    std::vector<AddItem> items((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        items[i].rc = entry_request(h, e[i], items[i].rq, false);
+        if (items[i].rc != L3D_OK) { items[i].msg = h->err; items[i].rq.e.image_id = e[i].image_id; }
+        items[i].rq.remap = remap ? remap[i] : nullptr;
+    }
+    return add_batch(h, items, data_directory, max_img_width, load_and_store, status);
+}
 int l3d_line3d_add_images(l3d_line3d* h, const l3d_image_entry* e, int n, const char* data_directory, int max_img_width, int load_and_store, int* status)
 {
     return l3d_line3d_add_images_lens(h, e, nullptr, n, data_directory, max_img_width, load_and_store, status);
@@ -1125,6 +1214,23 @@ int l3d_line3d_add_device_entry_lens(l3d_line3d* h, const l3d_device_entry* e, c
     AddRequest rq = device_request(*e);
     rq.lens = lens;
     return add_one(h, rq, data_directory, max_img_width, load_and_store);
+}
+int l3d_line3d_add_device_entry_remap(l3d_line3d* h, const l3d_device_entry* e, const l3d_remap* remap, const char* data_directory, int max_img_width, int load_and_store)
+{
+    if (!h) return L3D_ERR_INVALID;
+    if (!e) return h->fail(L3D_ERR_INVALID, "add_device_entry: null argument");
+    AddRequest rq = device_request(*e);
+    rq.remap = remap;
+    return add_one(h, rq, data_directory, max_img_width, load_and_store);
+}
+int l3d_line3d_add_device_images_remap(l3d_line3d* h, const l3d_device_entry* e, const l3d_remap* const* remap, int n, const char* data_directory, int max_img_width,
+                                       int load_and_store, int* status)
+{
+    if (!h) return L3D_ERR_INVALID;
+    if (n < 0 || (n > 0 && !e)) return h->fail(L3D_ERR_INVALID, "add_device_images: null argument");
+    std::vector<AddItem> items((size_t)n);
+    for (int i = 0; i < n; ++i) { items[i].rq = device_request(e[i]); items[i].rq.remap = remap ? remap[i] : nullptr; }
+    return add_batch(h, items, data_directory, max_img_width, load_and_store, status);
 }
 int l3d_line3d_add_device_entry(l3d_line3d* h, const l3d_device_entry* e, const char* data_directory, int max_img_width, int load_and_store)
 {

@@ -26,7 +26,7 @@ def image_entries(entries):
 
     for i, en in enumerate(entries):
         e = arr[i]
-        unknown = set(en) - {"imageID", "img", "data", "K", "R", "t", "dist", "lens", "worldpointIDs", "viewSimilarity"}
+        unknown = set(en) - {"imageID", "img", "data", "K", "R", "t", "dist", "lens", "out_size", "mask", "border_mask", "worldpointIDs", "viewSimilarity"}
         if unknown:
             raise ValueError("entry %d: unknown keys %s" % (i, sorted(unknown)))
         if (en.get("img") is None) == (en.get("data") is None):
@@ -71,7 +71,7 @@ def device_entries(entries):
 
     for i, en in enumerate(entries):
         e = arr[i]
-        unknown = set(en) - {"imageID", "img", "data", "K", "R", "t", "dist", "lens", "worldpointIDs", "viewSimilarity"}
+        unknown = set(en) - {"imageID", "img", "data", "K", "R", "t", "dist", "lens", "out_size", "mask", "border_mask", "worldpointIDs", "viewSimilarity"}
         if unknown:
             raise ValueError("entry %d: unknown keys %s" % (i, sorted(unknown)))
         if en.get("img") is None or en.get("data") is not None:
@@ -248,6 +248,15 @@ class Line3D:
         if lens is not None and not isinstance(lens, capi.Lens):
             raise TypeError("lens must come from capi.lens()")
         tail = (C.c_char_p(self.data_directory.encode()), C.c_int(int(maxImgWidth)), C.c_int(int(loadAndStoreSegments)))
+        remap_arr, remap_keep = capi.remap_pointers([lens], [en.get("out_size")], [en.get("mask")], [en.get("border_mask")], 1)
+        if remap_arr is not None:           # another size, a mask or a border rule: the ..._entry_remap form
+            if "data" in en and not isinstance(en["data"], (bytes, bytearray, memoryview, np.ndarray)):
+                en["data"] = bytes(en["data"])
+            on_device = capi.is_device_object(en.get("img"))
+            arr, keep = (device_entries if on_device else image_entries)([en])
+            call = self.lib.l3d_line3d_add_device_entry_remap if on_device else self.lib.l3d_line3d_add_image_entry_remap
+            self.last_rc = call(self.h, arr, C.byref(remap_keep[0]), *tail)
+            return self.last_rc == 0
         if capi.is_device_object(en.get("img")):
             arr, keep = device_entries([en])
             self.last_rc = self.lib.l3d_line3d_add_device_entry(self.h, arr, *tail) if lens is None else self.lib.l3d_line3d_add_device_entry_lens(self.h, arr, C.byref(lens), *tail)
@@ -258,29 +267,33 @@ class Line3D:
         self.last_rc = self.lib.l3d_line3d_add_image_entry(self.h, arr, *tail) if lens is None else self.lib.l3d_line3d_add_image_entry_lens(self.h, arr, C.byref(lens), *tail)
         return self.last_rc == 0
 
-    def add_image_pixels(self, imageID, img, K, R, t, worldpointIDs, maxImgWidth=1920, loadAndStoreSegments=True, dist=None, lens=None):
+    def add_image_pixels(self, imageID, img, K, R, t, worldpointIDs, maxImgWidth=1920, loadAndStoreSegments=True, dist=None, lens=None, out_size=None, mask=None, border_mask=None):
         """Line3D::addImage from pixels (an image entry with img, include/line3d_amd.h): uint8 image H x W or H x W x 3.  The segment cache in
         `data_directory` is loaded when present (and loadAndStoreSegments); otherwise the segments are detected on the device, and the cache written
         or a stale one removed.  An image without segments adds no view and is no error (line3D.cc:186-190).  dist = (k1, k2), OpenCV-convention
         radial coefficients: the image is undistorted on the device with K before the detector sees it.
         img may be a device object (a torch device tensor, a capi.device_image descriptor): it is read where it lies (l3d_line3d_add_device_entry).
         lens (capi.lens(...)) in the place of dist: tangential, rational and fisheye models, the image resampled from the lens's source camera onto
-        K, which the view keeps (l3d_line3d_add_image_entry_lens).  dist and lens together are refused by the library."""
-        return self._add_entry(dict(imageID=imageID, img=img if capi.is_device_object(img) else np.asarray(img), K=K, R=R, t=t, worldpointIDs=list(worldpointIDs), dist=dist, lens=lens), maxImgWidth, loadAndStoreSegments)
+        K, which the view keeps (l3d_line3d_add_image_entry_lens).  dist and lens together are refused by the library.
+        out_size = (width, height), mask, border_mask ("A REMAP", l3d_line3d_add_image_entry_remap; also on the other image-taking add calls and as
+        keys of add_images' entries): the image is resampled onto out_size -- the view's size, which names the cache file and which maxImgWidth
+        acts on --, K is the output camera (capi.undistort_plan chooses one), mask (capi.remap's) is the caller's validity plane in the source
+        grid, and no segment starts where a blank or masked pixel contributed to the gradient (border_mask, default true)."""
+        return self._add_entry(dict(imageID=imageID, img=img if capi.is_device_object(img) else np.asarray(img), K=K, R=R, t=t, worldpointIDs=list(worldpointIDs), dist=dist, lens=lens, out_size=out_size, mask=mask, border_mask=border_mask), maxImgWidth, loadAndStoreSegments)
 
-    def add_image_pixels_fixed_sim(self, imageID, img, K, R, t, viewSimilarity, maxImgWidth=1920, loadAndStoreSegments=True, dist=None, lens=None):
+    def add_image_pixels_fixed_sim(self, imageID, img, K, R, t, viewSimilarity, maxImgWidth=1920, loadAndStoreSegments=True, dist=None, lens=None, out_size=None, mask=None, border_mask=None):
         """Line3D::addImage_fixed_sim from pixels; dist and device objects as in add_image_pixels"""
-        return self._add_entry(dict(imageID=imageID, img=img if capi.is_device_object(img) else np.asarray(img), K=K, R=R, t=t, viewSimilarity=dict(viewSimilarity), dist=dist, lens=lens), maxImgWidth, loadAndStoreSegments)
+        return self._add_entry(dict(imageID=imageID, img=img if capi.is_device_object(img) else np.asarray(img), K=K, R=R, t=t, viewSimilarity=dict(viewSimilarity), dist=dist, lens=lens, out_size=out_size, mask=mask, border_mask=border_mask), maxImgWidth, loadAndStoreSegments)
 
-    def add_image_jpeg(self, imageID, data, K, R, t, worldpointIDs, maxImgWidth=1920, loadAndStoreSegments=True, dist=None, lens=None):
+    def add_image_jpeg(self, imageID, data, K, R, t, worldpointIDs, maxImgWidth=1920, loadAndStoreSegments=True, dist=None, lens=None, out_size=None, mask=None, border_mask=None):
         """Line3D::addImage from the bytes of a baseline JPEG file (an image entry with data): decoded, undistorted (dist = (k1, k2), None: not)
         and its segments detected on the device.  Cache rules as add_image_pixels; a cache that is present and wanted is loaded without decoding
         the file.  A file the decoder refuses adds no view and returns False (the cause: l3d_line3d_last_error)."""
-        return self._add_entry(dict(imageID=imageID, data=data, K=K, R=R, t=t, worldpointIDs=list(worldpointIDs), dist=dist, lens=lens), maxImgWidth, loadAndStoreSegments)
+        return self._add_entry(dict(imageID=imageID, data=data, K=K, R=R, t=t, worldpointIDs=list(worldpointIDs), dist=dist, lens=lens, out_size=out_size, mask=mask, border_mask=border_mask), maxImgWidth, loadAndStoreSegments)
 
-    def add_image_jpeg_fixed_sim(self, imageID, data, K, R, t, viewSimilarity, maxImgWidth=1920, loadAndStoreSegments=True, dist=None, lens=None):
+    def add_image_jpeg_fixed_sim(self, imageID, data, K, R, t, viewSimilarity, maxImgWidth=1920, loadAndStoreSegments=True, dist=None, lens=None, out_size=None, mask=None, border_mask=None):
         """Line3D::addImage_fixed_sim from the bytes of a baseline JPEG file; as add_image_jpeg"""
-        return self._add_entry(dict(imageID=imageID, data=data, K=K, R=R, t=t, viewSimilarity=dict(viewSimilarity), dist=dist, lens=lens), maxImgWidth, loadAndStoreSegments)
+        return self._add_entry(dict(imageID=imageID, data=data, K=K, R=R, t=t, viewSimilarity=dict(viewSimilarity), dist=dist, lens=lens, out_size=out_size, mask=mask, border_mask=border_mask), maxImgWidth, loadAndStoreSegments)
 
     def add_images(self, entries, maxImgWidth=1920, loadAndStoreSegments=True):
         """l3d_line3d_add_images: many images in one call -- exactly the add_image_pixels[_fixed_sim] / add_image_jpeg[_fixed_sim] calls in entry order,
@@ -296,8 +309,12 @@ class Line3D:
         n = len(entries)
         status = (C.c_int * max(1, n))()
         lens_arr, lens_keep = capi.lens_pointers([en.get("lens") for en in entries], n)
+        remap_arr, remap_keep = capi.remap_pointers(*([en.get(k) for en in entries] for k in ("lens", "out_size", "mask", "border_mask")), n)
         tail = (C.c_int(n), C.c_char_p(self.data_directory.encode()), C.c_int(int(maxImgWidth)), C.c_int(int(loadAndStoreSegments)), status)
-        if lens_arr is not None:
+        if remap_arr is not None:
+            call = self.lib.l3d_line3d_add_device_images_remap if on_device else self.lib.l3d_line3d_add_images_remap
+            self._chk(call(self.h, arr, remap_arr, *tail))
+        elif lens_arr is not None:
             call = self.lib.l3d_line3d_add_device_images_lens if on_device else self.lib.l3d_line3d_add_images_lens
             self._chk(call(self.h, arr, lens_arr, *tail))
         else:

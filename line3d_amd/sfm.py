@@ -135,7 +135,7 @@ def reconstruct(scene: SfmScene, segments, image_sizes, out_dir=None, neighbors=
 
 
 def reconstruct_from_images(scene: SfmScene, load_image, data_directory, out_dir=None, neighbors=10, diffusion=False, max_width=1920,
-                            load_and_store_segments=True, device=0, batch=16, refine=False, **line3d_kwargs):
+                            load_and_store_segments=True, device=0, batch=16, refine=False, alpha=None, out_size=None, **line3d_kwargs):
     """The drivers' flow (main_vsfm.cpp:226-325) from pixels: per camera the image load_image(i, name) returns -- `bytes`: the contents of a
     baseline JPEG file, decoded on the device (Line3D.add_image_jpeg); or a uint8 array H x W or H x W x 3, decoded by the caller; or an image
     in device memory (a torch device tensor, a capi.device_image descriptor), read where it lies --, K from the focal length and the image size, the image undistorted with the camera's coefficients and its
@@ -144,13 +144,17 @@ def reconstruct_from_images(scene: SfmScene, load_image, data_directory, out_dir
     drivers' file name.  data_directory: the drivers' "<image folder>/L3D_data/" -- with load_and_store_segments (the drivers' default) the segment
     caches are written there, and a cache of an earlier run stands in for the image (line3D.cc:143-168).  The images go to the library `batch`
     at a time (Line3D.add_images): the same views as one call per image, with the detector run once per batch.
-    refine: the 3-D lines are refined against the 2-D segments of their clusters (Line3D.set_refinement, defaults) before they are written."""
+    refine: the 3-D lines are refined against the 2-D segments of their clusters (Line3D.set_refinement, defaults) before they are written.
+    alpha, out_size (either given; "A REMAP" in include/line3d_amd.h): a camera with an active lens -- a COLMAP camera's, or an NVM / bundler camera's
+    k1, k2 as a BROWN lens -- is PLANNED (capi.undistort_plan(lens, size, alpha or 0, out_size), once per distinct camera) and the view is added
+    with the planned K and size, the blank pixels of the resampling invalid for the detector.  Neither given: what it did before."""
     import os
     from .pipeline import Line3D
     l3d = Line3D(data_directory, matchingNeighbors=neighbors, device=device, **line3d_kwargs)
     if refine:
         l3d.set_refinement(True)
     entries = []
+    planned = {}            # (lens, source size) -> (K, size): one plan per distinct camera
 
     def flush():
         for en, st in zip(entries, l3d.add_images(entries, maxImgWidth=max_width, loadAndStoreSegments=load_and_store_segments)):
@@ -186,6 +190,20 @@ def reconstruct_from_images(scene: SfmScene, load_image, data_directory, out_dir
             if entries and capi.is_device_object(entries[-1].get("img")):
                 flush()
         en["K"] = cam["K"] if "lens" in en else intrinsics(cam["focal"], w, h)
+        if alpha is not None or out_size is not None:
+            K = np.asarray(en["K"], dtype=np.float64).reshape(3, 3)
+            lens = en.get("lens")
+            if lens is None and en.get("dist") is not None and any(abs(float(c)) > 1e-12 for c in en["dist"]):
+                lens = capi.lens("brown", [float(c) for c in en["dist"]], camera=(K[0, 0], K[1, 1], K[0, 2], K[1, 2]))
+            active = lens is not None and (lens.model == capi.LENS_FISHEYE or any(abs(c) > 1e-12 for c in lens.k))
+            if active and K[0, 1] == 0.0:
+                if lens.fx == 0.0 and lens.fy == 0.0:           # a lens without a camera of its own: the entry's K is its source camera
+                    lens = capi.lens(lens.model, list(lens.k), camera=(K[0, 0], K[1, 1], K[0, 2], K[1, 2]))
+                key = (lens.model, lens.fx, lens.fy, lens.cx, lens.cy, tuple(lens.k), w, h)
+                if key not in planned:
+                    planned[key] = capi.undistort_plan(lens, (w, h), 0.0 if alpha is None else alpha, out_size)
+                en.pop("dist", None)
+                en["lens"], en["K"], en["out_size"] = lens, planned[key][0], planned[key][1]
         entries.append(en)
         if len(entries) >= batch:
             flush()
