@@ -1382,6 +1382,41 @@ int l3d_test_pair_candidates(l3d_ctx* ctx, int S, int N, const float* src_segs, 
                              const float* RtKinv, const float* centers, const float* RtKinv_src, const float* C_src, const int32_t* to_be_matched, int n_tbm,
                              l3d_test_pair_path* sel, int32_t* row_upper, int32_t* row_count, int32_t* row_start, uint32_t* cand_meta, float* cand_depths);
 
+/* The products of matchViews (l3d_match_chain_resident's last step: the table of potential correspondences, the best-match references, the medians,
+ * the early-return quirk) built from kept lists the CALLER hands in, exported for tests (tests/test_gpu_products_paths.py): the lists go where a
+ * chain leaves them (the kept arena, the best depth pairs, the best positions), then the product's own builder runs on them.  No chain runs.
+ *   views, n_views   the schedule; read: view_id, S_src (<= 16384), N (<= 255), local2global, n_tbm (0 = the view returned early), source_cam,
+ *                    source_index, n_sources
+ *   map              the dense map (every chain view is in it, with S_src segments)
+ *   kept, n_kept     the kept lists of the chain views one after the other, GLOBAL camera ids; n_kept[k] records of view k (0 for an early return)
+ *   n_candidates     per chain view, the candidates its verification saw (0: the median stays 1.0)
+ *   best, bestpos    per segment of every chain view, view after view (S_src entries each, those of early-return views unread): the depth pair of the
+ *                    best hypothesis ((-1, -1): none) and the position of the best kept match in the view's list (-1: none; checked against n_kept)
+ * sel in:  side_arrays 0 = the builder rebuilds the side words and run tables of the lists block by block; 1 = they are made here first, for every
+ *          list, by the launchers the chains use for lists taken over (l3d_runtable.hpp), and handed over as the chain hands its own.  Lists those
+ *          launchers find unordered get none: the builder is then called as with 0, and side_arrays_used says so.
+ *          early_pairs 1 (needs side_arrays 1): the (view, camera) pairs are transposed view by view as the chain does on its side stream.
+ *          [dv0, dv1) with dv1 >= 0: the rows of these dense views only, numbered from 0; held (NULL or one byte per chain view): with a row range,
+ *          the rows outside it are left empty and the whole of pot_start is valid.
+ * sel out: build (1 transposed, 2 sorted), refused (why the transposed build handed over to the sort: 0 it did not, 1 a view of more than 16000
+ *          segments, 2 a list that is not ordered or names a camera that is no neighbour), n_blocks, max_touch (the most views a row of the transposed
+ *          build touches), early_cap / early_g and, for the first block_capacity blocks of the transposed build, block_cap / block_staged / block_g
+ *          (any of the three may be NULL): the LDS image of the pair transposes' two-level scatter in entries (0: direct scatter, -1: no transpose was
+ *          launched for the block), whether short rows are staged by the counting pass, the lanes that share a run.
+ * Afterwards l3d_chain_products_get, l3d_chain_kept_list and l3d_chain_records_digest answer as after l3d_match_chain_resident (with a row range:
+ * the rows of the range, and *n_pot their entries).  Refused with L3D_ERR_INVALID before anything is uploaded: counts out of range, a best position
+ * outside its list, records for an early-return view, early_pairs without side_arrays or with a view of more than 16382 segments. */
+typedef struct l3d_test_products_path {
+    int32_t side_arrays, early_pairs, dv0, dv1;
+    const unsigned char* held;
+    int32_t block_capacity;
+    int32_t side_arrays_used, build, refused, n_blocks, max_touch, early_cap, early_g;     /* out */
+    int32_t* block_cap; int32_t* block_staged; int32_t* block_g;                            /* out, block_capacity entries each */
+} l3d_test_products_path;
+int l3d_test_products(l3d_ctx* ctx, const l3d_chain_view* views, int n_views, const l3d_dense_map* map, const l3d_match* kept, const int32_t* n_kept,
+                      const int64_t* n_candidates, const float* best, const int32_t* bestpos, l3d_test_products_path* sel,
+                      l3d_chain_summary* summary, int64_t* n_pot);
+
 #ifdef __cplusplus
 }
 #endif

@@ -510,6 +510,36 @@ class PairPath(C.Structure):
                                           "needed", "total", "largest", "spb_used", "overflow", "pad")]
 
 
+class ChainView(C.Structure):
+    """l3d_chain_view (include/line3d_amd.h)"""
+    _fields_ = [("view_id", C.c_uint32), ("src_segs", C.c_void_p), ("S_src", C.c_int32), ("RtKinv_src", C.c_void_p), ("C_src", C.c_void_p),
+                ("tgt_segs", C.c_void_p), ("n_tgt", C.c_int32), ("offsets", C.c_void_p), ("N", C.c_int32), ("F", C.c_void_p), ("RtKinv", C.c_void_p),
+                ("centers", C.c_void_p), ("P", C.c_void_p), ("to_be_matched", C.c_void_p), ("n_tbm", C.c_int32), ("local2global", C.c_void_p),
+                ("source_cam", C.c_void_p), ("source_index", C.c_void_p), ("n_sources", C.c_int32),
+                ("sigma_p", C.c_float), ("sigma_a", C.c_float), ("spatial_k", C.c_float)]
+
+
+class DenseMap(C.Structure):
+    """l3d_dense_map (include/line3d_amd.h)"""
+    _fields_ = [("n_views", C.c_int32), ("view_ids", C.c_void_p), ("seg_base", C.c_void_p)]
+
+
+SUMMARY_DTYPE = np.dtype([("verified", "<i4"), ("n_kept", "<i4"), ("n_candidates", "<i8"), ("median_depth", "<f4"), ("pad", "<i4")])   # l3d_chain_summary
+
+
+class ProductsPath(C.Structure):
+    """l3d_test_products_path (include/line3d_amd.h)"""
+    _fields_ = [("side_arrays", C.c_int32), ("early_pairs", C.c_int32), ("dv0", C.c_int32), ("dv1", C.c_int32), ("held", C.c_void_p),
+                ("block_capacity", C.c_int32), ("side_arrays_used", C.c_int32), ("build", C.c_int32), ("refused", C.c_int32), ("n_blocks", C.c_int32),
+                ("max_touch", C.c_int32), ("early_cap", C.c_int32), ("early_g", C.c_int32),
+                ("block_cap", C.c_void_p), ("block_staged", C.c_void_p), ("block_g", C.c_void_p)]
+
+
+# l3d_test_products_path: build / refused
+PROD_TRANSPOSED, PROD_SORTED = 1, 2
+PROD_REFUSED_WIDE_VIEW, PROD_REFUSED_UNORDERED = 1, 2
+
+
 # L3D_VK_*: the stage-2 kernels a test_verify_candidates call launched
 VK_ALL_PAIRS, VK_SEG_POST, VK_WINDOW_256, VK_WINDOW_512, VK_WINDOW_GB, VK_BUILD, VK_WALK, VK_WALK_GB = 1, 2, 4, 8, 16, 32, 64, 128
 
@@ -1014,6 +1044,61 @@ class Context:
             raise
         out.update(total=int(sel.total), largest=int(sel.largest), spb_used=int(sel.spb_used), overflow=int(sel.overflow), needed=int(sel.needed))
         return out
+
+    def chain_products_get(self, n_dense: int, n_pot: int, slack: int = 0):
+        """l3d_chain_products_get: (pot_start int64 (n_dense + 1,), pot_tgt int32 (n_pot + slack,), best MATCH_DTYPE (n_dense,)).  The slots of
+        pot_tgt behind n_pot are filled with -1 (0xffffffff) before the call: the library must leave them alone."""
+        pot_start = np.zeros(n_dense + 1, np.int64)
+        pot_tgt = np.full(n_pot + slack, -1, np.int32)
+        best = np.zeros(n_dense, dtype=MATCH_DTYPE)
+        self._chk(self.lib.l3d_chain_products_get(self.h, _p(pot_start), _p(pot_tgt), _p(best)))
+        return pot_start, pot_tgt, best
+
+    def test_products(self, views, view_ids, seg_base, side_arrays=0, early_pairs=0, rows=None, held=None, slack=64, max_blocks=1024):
+        """l3d_test_products: the products of matchViews from kept lists handed in.  views: one dict per chain view, in chain order -- id, S, l2g
+        (global ids of its N neighbours), n_tbm (0: early return), source_cam, source_index, kept (MATCH_DTYPE, GLOBAL camera ids), R, best (S, 2)
+        float32, bestpos (S,) int32.  view_ids / seg_base: the dense map.  rows: None or (dv0, dv1); held: None or one flag per chain view.
+        -> dict(pot_start, pot_tgt (n_pot + slack entries, -1 behind n_pot), best, n_pot, summary (SUMMARY_DTYPE), report)."""
+        n = len(views)
+        arr, keep = (ChainView * max(1, n))(), []
+        for k, v in enumerate(views):
+            l2g = np.ascontiguousarray(v["l2g"], dtype=np.uint32)
+            sc, si = np.ascontiguousarray(v["source_cam"], dtype=np.int32), np.ascontiguousarray(v["source_index"], dtype=np.int32)
+            assert len(sc) == len(si)
+            keep += [l2g, sc, si]
+            e = arr[k]
+            e.view_id, e.S_src, e.N, e.n_tbm, e.n_sources = int(v["id"]), int(v["S"]), len(l2g), int(v["n_tbm"]), len(sc)
+            e.local2global, e.source_cam, e.source_index = l2g.ctypes.data, sc.ctypes.data, si.ctypes.data
+        kept = [np.ascontiguousarray(v["kept"], dtype=MATCH_DTYPE) for v in views]
+        n_kept = np.array([len(a) for a in kept], np.int32)
+        kept_all = np.concatenate(kept) if n else np.zeros(0, MATCH_DTYPE)
+        R = np.array([int(v["R"]) for v in views], np.int64)
+        best = np.ascontiguousarray(np.concatenate([np.asarray(v["best"], np.float32).reshape(-1, 2) for v in views]), dtype=np.float32)
+        bestpos = np.ascontiguousarray(np.concatenate([np.asarray(v["bestpos"], np.int32).reshape(-1) for v in views]), dtype=np.int32)
+        assert len(best) == len(bestpos) == sum(int(v["S"]) for v in views)
+        ids, sb = np.ascontiguousarray(view_ids, dtype=np.uint32), np.ascontiguousarray(seg_base, dtype=np.int32)
+        assert len(sb) == len(ids) + 1
+        dm = DenseMap(len(ids), ids.ctypes.data, sb.ctypes.data)
+        blk = [np.full(max_blocks, -9, np.int32) for _ in range(3)]
+        sel = ProductsPath()
+        sel.side_arrays, sel.early_pairs = int(side_arrays), int(early_pairs)
+        sel.dv0, sel.dv1 = (0, -1) if rows is None else (int(rows[0]), int(rows[1]))
+        hb = None if held is None else np.ascontiguousarray(held, dtype=np.uint8)
+        assert hb is None or len(hb) == n
+        sel.held = None if hb is None else hb.ctypes.data
+        sel.block_capacity = max_blocks
+        sel.block_cap, sel.block_staged, sel.block_g = (b.ctypes.data for b in blk)
+        summary = np.zeros(max(1, n), dtype=SUMMARY_DTYPE)
+        n_pot = C.c_int64(0)
+        self._chk(self.lib.l3d_test_products(self.h, arr, C.c_int(n), C.byref(dm), _p(kept_all), _p(n_kept), _p(R), _p(best), _p(bestpos), C.byref(sel),
+                                             _p(summary), C.byref(n_pot)))
+        nd = int(sb[-1])
+        pot_start, pot_tgt, bm = self.chain_products_get(nd, n_pot.value, slack)
+        nb = min(max_blocks, int(sel.n_blocks)) if sel.build == PROD_TRANSPOSED else 0
+        report = dict(side_arrays_used=int(sel.side_arrays_used), build=int(sel.build), refused=int(sel.refused), n_blocks=int(sel.n_blocks),
+                      max_touch=int(sel.max_touch), early_cap=int(sel.early_cap), early_g=int(sel.early_g),
+                      block_cap=blk[0][:nb].tolist(), block_staged=blk[1][:nb].tolist(), block_g=blk[2][:nb].tolist())
+        return dict(pot_start=pot_start, pot_tgt=pot_tgt, best=bm, n_pot=int(n_pot.value), summary=summary[:n], report=report)
 
     # -- the three seam functions ---------------------------------------------------------------
     def compute_collinearity(self, segs, collin_s=2.0):

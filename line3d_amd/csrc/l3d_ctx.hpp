@@ -99,10 +99,20 @@ struct ProductsPart {
     int blocks_rerun = 0;               // blocks re-run in those rounds (whole job)
 };
 
+// what the builder of the products decided on its way (l3d_test_products hands it out): values it computes anyway, recorded
+struct ProductsReport {
+    int build = 0;                  // 1: the rows came out of the transposed build, 2: out of the sort
+    int refused = 0;                // the transposed build sent the lists to the sort: 1 = a view of more than 16000 segments, 2 = a list that is not ordered / names a camera that is no neighbour
+    int n_blocks = 0, max_touch = 0; // blocks of the build that made the rows; the most views a row of the transposed build touches
+    int early_cap = -1, early_g = -1; // launch_early_transposes: the LDS image of its two-level scatter and the lanes per run (-1: not launched)
+    std::vector<int> block_cap, block_staged, block_g;   // per block of the transposed build: LDS image of the pair transposes (-1: none launched), short rows staged, lanes per run
+};
+
 // Device-resident products of the last resident chain (l3d_products.hip) and the hypothesis table built from them
 struct Products {
     bool valid = false, hyp_valid = false;
     ProductsPart part;
+    ProductsReport report;
     int n_dense = 0, n_views_all = 0, n_chain = 0, n_hyp = 0;
     long long n_pot = 0, total_kept = 0;
     DevBuf keys, keys2, flag, pos, tmp, pot_start, pot_tgt, best_ref, median, tables, ttab, rowstage, tstage;

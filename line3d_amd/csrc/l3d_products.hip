@@ -123,6 +123,18 @@ __global__ __launch_bounds__(256) void k_prod_keys_early(const Match* __restrict
     }
 }
 
+// the views of the map a verified view's records name (sorted build over several blocks: which lists a block has to read)
+__global__ __launch_bounds__(256) void k_prod_names(const Match* __restrict__ arena, const ProdView* __restrict__ pv, const unsigned* __restrict__ ids, int n_all,
+                                                    unsigned char* __restrict__ names)
+{
+    const ProdView v = pv[blockIdx.y];
+    if (v.early) return;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < v.n_kept; i += gridDim.x * 256) {
+        const int t = find_view(ids, n_all, arena[v.kept_base + i].camID2);
+        if (t >= 0) names[(size_t)blockIdx.y * n_all + t] = 1;
+    }
+}
+
 // best match per segment as a reference into the arena: verified views from the kept writer's positions, early-return views
 // from the atomicMin keys (-> record index, "read reversed")
 __global__ __launch_bounds__(256) void k_prod_best(const ProdView* __restrict__ pv, long long* __restrict__ best_ref)
@@ -649,6 +661,7 @@ void l3d::launch_early_transposes(l3d_ctx* c, const EarlyView* views_dev, int k0
         while (cap > 1024 && ((size_t)maxSt + 2 + 2 * (size_t)cap) * 4 > 64 * 1024) cap -= 1024;
         if (((size_t)maxSt + 2 + 2 * (size_t)cap) * 4 > 64 * 1024) cap = 0;
     }
+    c->products.report.early_cap = cap; c->products.report.early_g = g;
     ProfScope p(c, "prod_keys", st);
     hipLaunchKernelGGL(k_prode_counts, dim3((unsigned)maxN, (unsigned)nb), dim3(256), 0, st, views_dev, k0, maxN, res, pcnt_kq);
     hipLaunchKernelGGL(k_prode_transpose, dim3((unsigned)maxN, (unsigned)nb), dim3(kPairThreads), ((size_t)maxSt + 2 + 2 * (size_t)cap) * 4, st, views_dev, k0, maxN, res, qt_arena, (const int*)pcnt_kq, poff_kq, g,
@@ -661,6 +674,9 @@ int l3d::build_products(l3d_ctx* c, const l3d_chain_view* views, int n_views, co
     Products& P = c->products;
     P.valid = false; P.hyp_valid = false;
     c->records_released = false;
+    ProductsReport& rep = P.report;
+    rep.build = 0; rep.refused = 0; rep.n_blocks = 0; rep.max_touch = 0;
+    rep.block_cap.clear(); rep.block_staged.clear(); rep.block_g.clear();
     hipStream_t st = c->stream;
     const int nv = map->n_views;
     if (nv <= 0) return fail(c, L3D_ERR_INVALID, "products: empty dense map");
@@ -755,7 +771,8 @@ int l3d::build_products(l3d_ctx* c, const l3d_chain_view* views, int n_views, co
     }
     std::vector<ProdBlock> blocks;
     std::vector<long long> off_tab;                         // per block: out_off of every chain view, then of every early pair
-    {
+    auto plan_blocks = [&]() -> int {
+        blocks.clear(); off_tab.clear();
         std::vector<int> mark_v((size_t)n_views, -1), mark_s(ps.size(), -1);
         int x = dv0;
         while (x < dv1) {
@@ -779,10 +796,12 @@ int l3d::build_products(l3d_ctx* c, const l3d_chain_view* views, int n_views, co
             blocks.push_back(B);
             x = x1;
         }
-    }
+        return L3D_OK;
+    };
+    if (int rc = plan_blocks()) return rc;
     long long max_slots = 0;
     for (const ProdBlock& B : blocks) max_slots = std::max(max_slots, B.slots);
-    const long long n_keys_max = max_slots + 1;            // (+ the sentinel)
+    long long n_keys_max = max_slots + 1;                  // (+ the sentinel)
 
     // ---- upload tables: [ProdView n_views][ProdSrc][ids nv][seg_base nv+1][chain view ids][out_off tables of all blocks]
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
@@ -817,7 +836,7 @@ int l3d::build_products(l3d_ctx* c, const l3d_chain_view* views, int n_views, co
     const unsigned* dids = reinterpret_cast<const unsigned*>(tb + o_ids);
     const int* dsb = reinterpret_cast<const int*>(tb + o_sb);
     const unsigned* dcv = reinterpret_cast<const unsigned*>(tb + o_cv);
-    const long long* doff = reinterpret_cast<const long long*>(tb + o_off);
+    const long long* doff = reinterpret_cast<const long long*>(tb + o_off);     // (the sorted build may plan its blocks again: then its own copy)
     const ProdViewQ* devq = reinterpret_cast<const ProdViewQ*>(tb + o_evq);
     const int* dslot = reinterpret_cast<const int*>(tb + o_slot);
 
@@ -847,7 +866,7 @@ int l3d::build_products(l3d_ctx* c, const l3d_chain_view* views, int n_views, co
     auto transposed = [&](long long& n_pot_out) -> int {
         const double t_t0 = now_s();
         auto seg_count = [&](int x) { return P.seg_base[(size_t)x + 1] - P.seg_base[(size_t)x]; };
-        for (int x = dv0; x < dv1; ++x) if (seg_count(x) > 16000) return kSortInstead;                                  // (the pair transposes keep a view's segments in 64 KB of LDS)
+        for (int x = dv0; x < dv1; ++x) if (seg_count(x) > 16000) { rep.refused = 1; return kSortInstead; }                              // (the pair transposes keep a view's segments in 64 KB of LDS)
         const bool rebuild = !native_rt;                        // (a list without a run table: all are rebuilt, block by block)
         const bool use_early = early && !rebuild && early->E && early->boff && early->poff_kq;      // the chain transposed every pair behind its view's kept writer
         // T(x): the dense views a row of view x can name -- its chain view's neighbours, the views it is a neighbour of, the early-return aliases
@@ -920,6 +939,7 @@ int l3d::build_products(l3d_ctx* c, const l3d_chain_view* views, int n_views, co
             r.t1 = (int)tl.size();
             max_touch = std::max(max_touch, r.t1 - r.t0);
         }
+        rep.max_touch = max_touch;
         // where the pairs of view x start in `pairs` (the blocks below cut the list at view boundaries)
         std::vector<int> pair_begin((size_t)nv + 1, 0);
         {
@@ -1023,6 +1043,7 @@ int l3d::build_products(l3d_ctx* c, const l3d_chain_view* views, int n_views, co
         for (const TBlock& B : tblocks) {
             const int d0 = P.seg_base[(size_t)B.x0], d1 = P.seg_base[(size_t)B.x1], rows = d1 - d0, n_pairs = B.pair1 - B.pair0;
             int scal[2] = { 0, 0 };                                            // {entries of the block, error count}
+            rep.block_cap.push_back(-1); rep.block_staged.push_back(0); rep.block_g.push_back(-1);
             if (rows > 0) {
                 unsigned* ent = use_early ? P.keys2.as<unsigned>() : E + B.rec_n;      // (early-return entries behind the transposed ones; the chain's transposes: a buffer of their own)
                 {
@@ -1047,7 +1068,10 @@ int l3d::build_products(l3d_ctx* c, const l3d_chain_view* views, int n_views, co
                         HIPCHK(c, hipMemcpyAsync(tt + q_vq, vqh.data(), vqh.size() * sizeof(ProdViewQ), hipMemcpyHostToDevice, st));
                         launch_qt_from_records(djob, (int)jobs.size(), max_n, err, st);
                         launch_rt_from_qt(djob, (int)jobs.size(), max_cells, st);
+                        HIPCHK(c, hipMemcpyAsync(&scal[1], err, 4, hipMemcpyDeviceToHost, st));
                         HIPCHK(c, hipStreamSynchronize(st));                   // (the host vectors above are re-used by the next block)
+                        // a list that is not ordered leaves run tables whose runs overlap: the transposes below would write more entries than were counted for them
+                        if (scal[1]) { rep.refused = 2; return kSortInstead; }
                     }
                     if (n_pairs > 0 && !use_early) {
                         hipLaunchKernelGGL(k_prodv_pair_counts, dim3((unsigned)n_pairs), dim3(256), 0, st, dpr + B.pair0, dvq, dpv, pcnt);
@@ -1068,6 +1092,7 @@ int l3d::build_products(l3d_ctx* c, const l3d_chain_view* views, int n_views, co
                         if (((size_t)B.maxS + 2 + 2 * (size_t)cap) * 4 <= 64 * 1024) { HIPCHK(c, P.tstage.reserve((size_t)max_rec * 4 + 256)); T = P.tstage.as<unsigned>(); } else cap = 0;
                         hipLaunchKernelGGL(k_prodv_pair_transpose, dim3((unsigned)n_pairs), dim3(kPairThreads), ((size_t)B.maxS + 2 + 2 * (size_t)cap) * 4, st, dpr + B.pair0, dvq, dpv, dnb,
                                            (const int*)poff, g, boff, E, T, cap);
+                        rep.block_cap.back() = cap; rep.block_g.back() = g;
                     }
                     if (B.n_srcs) {
                         HIPCHK(c, hipMemsetAsync(cnt, 0, ((size_t)rows + 1) * 4, st));
@@ -1087,6 +1112,7 @@ int l3d::build_products(l3d_ctx* c, const l3d_chain_view* views, int n_views, co
                 // short rows (on average at most 48 entries before the duplicates go) are left sorted in a staging row of 64 ints by the counting pass; the writing pass copies
                 int* stage = nullptr;
                 if (2.0 * (double)B.rec_n <= 48.0 * rows && (size_t)rows * 256 <= ((size_t)1 << 30)) { HIPCHK(c, P.rowstage.reserve((size_t)rows * 256 + 256)); stage = P.rowstage.as<int>(); }
+                rep.block_staged.back() = stage ? 1 : 0;
                 {
                     ProfScope p(c, "prod_rows", st);
                     HIPCHK(c, hipMemsetAsync(ucnt + rows, 0, 4, st));
@@ -1098,7 +1124,7 @@ int l3d::build_products(l3d_ctx* c, const l3d_chain_view* views, int n_views, co
                 HIPCHK(c, hipMemcpyAsync(&scal[0], ustart + rows, 4, hipMemcpyDeviceToHost, st));
                 HIPCHK(c, hipMemcpyAsync(&scal[1], err, 4, hipMemcpyDeviceToHost, st));
                 HIPCHK(c, hipStreamSynchronize(st));
-                if (scal[1]) return kSortInstead;
+                if (scal[1]) { rep.refused = 2; return kSortInstead; }
                 if (tblocks.size() == 1) HIPCHK(c, P.pot_tgt.reserve(((size_t)scal[0] + 2) * 4));
                 {
                     ProfScope p(c, "prod_rows", st);
@@ -1112,6 +1138,7 @@ int l3d::build_products(l3d_ctx* c, const l3d_chain_view* views, int n_views, co
             base += scal[0];
         }
         if (tblocks.empty()) HIPCHK(c, P.pot_tgt.reserve(64));
+        rep.build = 1; rep.n_blocks = (int)tblocks.size();
         n_pot_out = base;
         return L3D_OK;
     };
@@ -1125,6 +1152,34 @@ int l3d::build_products(l3d_ctx* c, const l3d_chain_view* views, int n_views, co
     }
     if (!rows_built) {
         // ---- the sorted build (rounds 3-5; A/B: L3D_PROD_TRANSPOSE=0, and the way out for slices the transposed build refuses)
+        if (blocks.size() > 1 && max_kept > 0) {
+            // Several blocks: a block reads the lists that `touch_view` says can have a key in it -- a view's own list and its neighbours'.  A list that names a
+            // camera which is no neighbour of its view (one of the refusals above) has backward keys in a block that does not read it: the views every list
+            // really names are looked up, and the blocks are planned again when that adds a list to a view.
+            HIPCHK(c, P.flag.reserve((size_t)n_views * nv + 256));
+            HIPCHK(c, hipMemsetAsync(P.flag.p, 0, (size_t)n_views * nv, st));
+            hipLaunchKernelGGL(k_prod_names, dim3(gx, n_views), dim3(256), 0, st, arena, dpv, dids, nv, P.flag.as<unsigned char>());
+            std::vector<unsigned char> names((size_t)n_views * nv);
+            HIPCHK(c, hipMemcpyAsync(names.data(), P.flag.p, names.size(), hipMemcpyDeviceToHost, st));
+            HIPCHK(c, hipStreamSynchronize(st));
+            bool added = false;
+            for (int k = 0; k < n_views; ++k) for (int t = 0; t < nv; ++t) {
+                std::vector<int>& tv = touch_view[(size_t)t];
+                if (names[(size_t)k * nv + t] && std::find(tv.begin(), tv.end(), k) == tv.end()) { tv.push_back(k); added = true; }
+            }
+            if (added) {
+                if (int rc = plan_blocks()) return rc;
+                max_slots = 0;
+                for (const ProdBlock& B : blocks) max_slots = std::max(max_slots, B.slots);
+                n_keys_max = max_slots + 1;
+                HIPCHK(c, P.ttab.reserve(off_tab.size() * 8 + 256));     // (the tables of the transposed build, which did not make the rows)
+                HIPCHK(c, hipMemcpyAsync(P.ttab.p, off_tab.data(), off_tab.size() * 8, hipMemcpyHostToDevice, st));
+                HIPCHK(c, hipStreamSynchronize(st));
+                doff = P.ttab.as<long long>();
+            }
+        }
+        rep.build = 2; rep.n_blocks = (int)blocks.size();
+        rep.block_cap.clear(); rep.block_staged.clear(); rep.block_g.clear();
         HIPCHK(c, P.keys.reserve((size_t)n_keys_max * 8 + 64));
         HIPCHK(c, P.keys2.reserve((size_t)n_keys_max * 8 + 64));
         HIPCHK(c, P.flag.reserve(((size_t)n_keys_max + 2) * 4));
@@ -1428,6 +1483,182 @@ int l3d_chain_products_get(l3d_ctx* c, int64_t* pot_start, int32_t* pot_tgt, l3d
         HIPCHK(c, hipMemcpyAsync(best_match, dout, (size_t)P.n_dense * sizeof(Match), hipMemcpyDeviceToHost, st));
     }
     HIPCHK(c, hipStreamSynchronize(st));
+    return L3D_OK;
+}
+
+// The builder on lists the caller hands in (tests): what a chain leaves behind is put in place -- records, best depth pairs, best positions; on request the
+// side words and run tables, by the launchers the chains use for lists taken over, and the chain's early pair transposes -- then build_products runs.
+int l3d_test_products(l3d_ctx* c, const l3d_chain_view* views, int n_views, const l3d_dense_map* map, const l3d_match* kept, const int32_t* n_kept,
+                      const int64_t* n_candidates, const float* best, const int32_t* bestpos, l3d_test_products_path* sel,
+                      l3d_chain_summary* summary, int64_t* n_pot)
+{
+    if (!c) return L3D_ERR_INVALID;
+    if (!views || n_views <= 0 || !map || !map->view_ids || !map->seg_base || !n_kept || !n_candidates || !best || !bestpos || !sel || !summary)
+        return fail(c, L3D_ERR_INVALID, "l3d_test_products: bad argument");
+    if ((sel->side_arrays | 1) != 1 || (sel->early_pairs | 1) != 1 || (sel->early_pairs && !sel->side_arrays))
+        return fail(c, L3D_ERR_INVALID, "l3d_test_products: side_arrays and early_pairs are 0 or 1, early_pairs needs side_arrays");
+    if (n_pot) *n_pot = 0;
+    sel->side_arrays_used = 0; sel->build = 0; sel->refused = 0; sel->n_blocks = 0; sel->max_touch = 0; sel->early_cap = -1; sel->early_g = -1;
+    const size_t nvs = (size_t)n_views;
+    std::vector<ChainResult> hres(nvs);
+    std::vector<ProdChainView> pvh(nvs);
+    std::vector<size_t> seg_off(nvs + 1, 0), rt_off(nvs + 1, 0);
+    long long total = 0;
+    int maxN = 0, maxS = 1;
+    for (int k = 0; k < n_views; ++k) {
+        const l3d_chain_view& v = views[k];
+        const std::string w = "l3d_test_products: view " + std::to_string(k);
+        if (v.S_src < 0 || v.S_src > 16384 || v.N < 0 || v.N > 255 || (v.N > 0 && !v.local2global)) return fail(c, L3D_ERR_INVALID, w + ": segments or neighbours out of range");
+        if (v.n_sources < 0 || (v.n_sources > 0 && (!v.source_cam || !v.source_index))) return fail(c, L3D_ERR_INVALID, w + ": bad source list");
+        if (n_kept[k] < 0 || (n_kept[k] > 0 && (!kept || v.n_tbm <= 0))) return fail(c, L3D_ERR_INVALID, w + ": records without a list to hold them");
+        if (n_candidates[k] < 0 || n_candidates[k] > 0x7fffffffll) return fail(c, L3D_ERR_INVALID, w + ": candidate count out of range");
+        const bool verified = v.n_tbm > 0;
+        if (verified) for (int s = 0; s < v.S_src; ++s) {
+            const int p = bestpos[seg_off[(size_t)k] + (size_t)s];
+            if (p < -1 || p >= n_kept[k]) return fail(c, L3D_ERR_INVALID, w + ": a best position outside the list");
+        }
+        ChainResult& r = hres[(size_t)k];
+        r.kept_base = (uint64_t)total; r.n_kept = verified ? n_kept[k] : 0; r.R = verified ? (int)n_candidates[k] : 0; r.overflow = 0; r.n_want = 0;
+        total += r.n_kept;
+        seg_off[(size_t)k + 1] = seg_off[(size_t)k] + (size_t)v.S_src;
+        rt_off[(size_t)k + 1] = rt_off[(size_t)k] + (verified ? ((size_t)v.N + 1) * (size_t)v.S_src : 0);
+        maxN = std::max(maxN, v.N); maxS = std::max(maxS, v.S_src);
+    }
+    if (total > 0x7ffffff0ll) return fail(c, L3D_ERR_INVALID, "l3d_test_products: too many records");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const size_t n_seg = seg_off[nvs];
+    HIPCHK(c, c->ch_kept.reserve(((size_t)total + 64) * sizeof(Match)));
+    HIPCHK(c, c->ch_best.reserve(n_seg * 8 + 64));
+    HIPCHK(c, c->ch_bestpos.reserve(n_seg * 4 + 64));
+    if (total > 0) HIPCHK(c, hipMemcpyAsync(c->ch_kept.p, kept, (size_t)total * sizeof(Match), hipMemcpyHostToDevice, st));
+    if (n_seg > 0) {
+        HIPCHK(c, hipMemcpyAsync(c->ch_best.p, best, n_seg * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(c->ch_bestpos.p, bestpos, n_seg * 4, hipMemcpyHostToDevice, st));
+    }
+    for (int k = 0; k < n_views; ++k) {
+        const bool verified = views[k].n_tbm > 0;
+        pvh[(size_t)k] = ProdChainView{ verified ? c->ch_best.as<float2>() + seg_off[(size_t)k] : nullptr, verified ? c->ch_bestpos.as<int>() + seg_off[(size_t)k] : nullptr, verified ? 1 : 0, nullptr };
+    }
+    // ---- the side words and run tables of every list, as the chains make them for lists that did not come out of their own kept writer
+    const unsigned* qt_arena = nullptr;
+    if (sel->side_arrays) {
+        std::vector<RtJob> jobs;
+        std::vector<unsigned> ids;
+        std::vector<int> qs;
+        std::vector<size_t> at;
+        HIPCHK(c, c->ch_keptcam.reserve((size_t)total * 4 + 64));
+        HIPCHK(c, c->ch_rt.reserve(rt_off[nvs] * 4 + 64));
+        for (int k = 0; k < n_views; ++k) {
+            if (views[k].n_tbm <= 0 || views[k].S_src == 0) continue;
+            std::vector<std::pair<unsigned, int>> byid;
+            for (int q = 0; q < views[k].N; ++q) byid.push_back({ views[k].local2global[q], q });
+            std::sort(byid.begin(), byid.end());
+            at.push_back(ids.size());
+            for (auto& e : byid) { ids.push_back(e.first); qs.push_back(e.second); }
+            RtJob j;
+            j.recs = c->ch_kept.as<Match>() + hres[(size_t)k].kept_base; j.qt = c->ch_keptcam.as<unsigned>() + hres[(size_t)k].kept_base; j.rt = c->ch_rt.as<int>() + rt_off[(size_t)k];
+            j.ids = nullptr; j.qs = nullptr; j.n = hres[(size_t)k].n_kept; j.S = views[k].S_src; j.N = views[k].N; j.pad = 0; j.skey = nullptr;
+            jobs.push_back(j);
+        }
+        int bad = 0;
+        if (!jobs.empty()) {
+            auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+            const size_t o_ids = al(jobs.size() * sizeof(RtJob)), o_qs = o_ids + al(ids.size() * 4 + 16), o_err = o_qs + al(qs.size() * 4 + 16), o_key = o_err + 256;
+            HIPCHK(c, c->ch_rtjobs.reserve(o_key + (size_t)total * 4 + 256));
+            unsigned char* sb = c->ch_rtjobs.as<unsigned char>();
+            int max_n = 0, max_cells = 0;
+            size_t ko = 0;
+            for (size_t i = 0; i < jobs.size(); ++i) {
+                jobs[i].ids = reinterpret_cast<const unsigned*>(sb + o_ids) + at[i]; jobs[i].qs = reinterpret_cast<const int*>(sb + o_qs) + at[i];
+                jobs[i].skey = reinterpret_cast<unsigned*>(sb + o_key) + ko; ko += (size_t)jobs[i].n;
+                max_n = std::max(max_n, jobs[i].n); max_cells = std::max(max_cells, (jobs[i].N + 1) * jobs[i].S);
+            }
+            HIPCHK(c, hipMemcpyAsync(sb, jobs.data(), jobs.size() * sizeof(RtJob), hipMemcpyHostToDevice, st));
+            if (!ids.empty()) {
+                HIPCHK(c, hipMemcpyAsync(sb + o_ids, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, st));
+                HIPCHK(c, hipMemcpyAsync(sb + o_qs, qs.data(), qs.size() * 4, hipMemcpyHostToDevice, st));
+            }
+            HIPCHK(c, hipMemsetAsync(sb + o_err, 0, 4, st));
+            launch_qt_from_records(reinterpret_cast<const RtJob*>(sb), (int)jobs.size(), max_n, reinterpret_cast<int*>(sb + o_err), st);
+            launch_rt_from_qt(reinterpret_cast<const RtJob*>(sb), (int)jobs.size(), max_cells, st);
+            HIPCHK(c, hipMemcpyAsync(&bad, sb + o_err, 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(c, hipStreamSynchronize(st));
+        }
+        if (!bad) {
+            qt_arena = c->ch_keptcam.as<unsigned>();
+            for (int k = 0; k < n_views; ++k) if (views[k].n_tbm > 0 && views[k].S_src > 0) pvh[(size_t)k].rt = c->ch_rt.as<int>() + rt_off[(size_t)k];
+            sel->side_arrays_used = 1;
+        }
+    }
+    // ---- the chain's early pair transposes (l3d_chain.hip), view by view
+    Products& PE = c->products;
+    PE.report.early_cap = -1; PE.report.early_g = -1;
+    ProdEarly pe;
+    bool early = sel->early_pairs && qt_arena && maxN > 0;
+    if (early) {
+        std::vector<int> tab(nvs * maxN * 2 + nvs * (sizeof(EarlyView) / 4), 0);
+        PE.e_boff_off.assign(nvs * maxN, 0);
+        long long nb = 0;
+        int early_maxSt = 1;
+        for (int k = 0; k < n_views; ++k) {
+            if (views[k].n_tbm <= 0) continue;
+            for (int q = 0; q < views[k].N; ++q) {
+                const uint32_t* it = std::lower_bound(map->view_ids, map->view_ids + map->n_views, views[k].local2global[q]);
+                if (it == map->view_ids + map->n_views || *it != views[k].local2global[q]) continue;
+                const int t = (int)(it - map->view_ids), St = map->seg_base[t + 1] - map->seg_base[t];
+                if (St <= 0) continue;
+                tab[(size_t)k * maxN + q] = St;
+                tab[nvs * maxN + (size_t)k * maxN + q] = (int)nb;
+                PE.e_boff_off[(size_t)k * maxN + q] = (int)nb;
+                nb += St + 1;
+                early_maxSt = std::max(early_maxSt, St);
+            }
+        }
+        if (nb > 0x7ffffff0ll) return fail(c, L3D_ERR_INVALID, "l3d_test_products: too many column starts for the early transposes");
+        if (early_maxSt > 16382) return fail(c, L3D_ERR_INVALID, "l3d_test_products: early_pairs with a view of more than 16382 segments");
+        HIPCHK(c, PE.e_tab.reserve(tab.size() * 4 + 64));
+        static_assert(sizeof(EarlyView) % 8 == 0, "descriptor size");
+        const int* dt = PE.e_tab.as<int>();
+        EarlyView* hv = reinterpret_cast<EarlyView*>(tab.data() + nvs * maxN * 2);
+        for (int k = 0; k < n_views; ++k) {
+            EarlyView e;
+            e.rt = pvh[(size_t)k].rt;
+            e.St = dt + (size_t)k * maxN; e.boff_off = dt + nvs * maxN + (size_t)k * maxN;
+            e.k = k; e.S = views[k].S_src; e.N = views[k].N; e.pad = 0;
+            hv[k] = e;
+        }
+        HIPCHK(c, PE.e_cnt.reserve(nvs * maxN * 4 + 64));
+        HIPCHK(c, PE.e_poff.reserve(nvs * maxN * 4 + 64));
+        HIPCHK(c, PE.e_boff.reserve((size_t)nb * 4 + 64));
+        HIPCHK(c, PE.e_E.reserve((size_t)total * 4 + 64));
+        HIPCHK(c, PE.e_T.reserve((size_t)total * 4 + 64));
+        HIPCHK(c, c->ch_res.reserve(nvs * sizeof(ChainResult) + 64));
+        HIPCHK(c, hipMemcpyAsync(PE.e_tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(c->ch_res.p, hres.data(), nvs * sizeof(ChainResult), hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipStreamSynchronize(st));                    // (`tab` is pageable and leaves scope)
+        const double avg_run = (double)total / n_views / std::max(1.0, (double)maxS * maxN);
+        const EarlyView* dv = reinterpret_cast<const EarlyView*>(PE.e_tab.as<int>() + nvs * maxN * 2);
+        for (int k = 0; k < n_views; ++k)
+            launch_early_transposes(c, dv, k, 1, maxN, early_maxSt, c->ch_res.as<ChainResult>(), qt_arena, PE.e_cnt.as<int>(), PE.e_poff.as<unsigned>(), PE.e_boff.as<int>(),
+                                    PE.e_E.as<unsigned>(), PE.e_T.as<unsigned>(), avg_run, st);
+        pe.pcnt_kq = PE.e_cnt.as<int>(); pe.poff_kq = PE.e_poff.as<unsigned>(); pe.boff = PE.e_boff.as<int>(); pe.E = PE.e_E.as<unsigned>();
+        pe.boff_off_host = PE.e_boff_off.data(); pe.maxN = maxN;
+    }
+    const bool partial = sel->dv1 >= 0;
+    int64_t n_local = 0;
+    const int rc = build_products(c, views, n_views, pvh.data(), hres.data(), map, summary, &n_local, partial ? sel->dv0 : 0, partial ? sel->dv1 : -1,
+                                  partial ? reinterpret_cast<const char*>(sel->held) : nullptr, qt_arena, early ? &pe : nullptr);
+    const ProductsReport& rep = PE.report;
+    sel->build = rep.build; sel->refused = rep.refused; sel->n_blocks = rep.n_blocks; sel->max_touch = rep.max_touch; sel->early_cap = rep.early_cap; sel->early_g = rep.early_g;
+    for (int b = 0; b < sel->block_capacity && b < (int)rep.block_cap.size(); ++b) {
+        if (sel->block_cap) sel->block_cap[b] = rep.block_cap[(size_t)b];
+        if (sel->block_staged) sel->block_staged[b] = rep.block_staged[(size_t)b];
+        if (sel->block_g) sel->block_g[b] = rep.block_g[(size_t)b];
+    }
+    if (rc) return rc;
+    PE.valid = true;                // (a row range: the getters hand out its rows, as on a rank of the partitioned products)
+    if (n_pot) *n_pot = n_local;
     return L3D_OK;
 }
 

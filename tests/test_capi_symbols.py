@@ -36,11 +36,14 @@ def test_struct_layouts(tmp_path):
     assert capi.MATCH_DTYPE.itemsize == 32 and capi.EDGE_DTYPE.itemsize == 12 and capi.HYP_DTYPE.itemsize == 96
     src = tmp_path / "layout.c"
     src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "line3d_amd.h"\n'
-                   'int main(void) { printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(l3d_match), sizeof(l3d_edge), sizeof(l3d_hypothesis),\n'
+                   'int main(void) { printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(l3d_match), sizeof(l3d_edge), sizeof(l3d_hypothesis),\n'
                    '  sizeof(l3d_affinity_input), offsetof(l3d_affinity_input, seg_base), offsetof(l3d_affinity_input, n_hyp), offsetof(l3d_affinity_input, hyp),\n'
                    '  offsetof(l3d_affinity_input, coll_w), offsetof(l3d_affinity_input, sigma_a),\n'
                    '  sizeof(l3d_test_verify_path), offsetof(l3d_test_verify_path, wide_max), offsetof(l3d_test_verify_path, kernels), offsetof(l3d_test_verify_path, seg_order),\n'
-                   '  sizeof(l3d_test_pair_path), offsetof(l3d_test_pair_path, seg_begin), offsetof(l3d_test_pair_path, capacity), offsetof(l3d_test_pair_path, overflow)); return 0; }\n')
+                   '  sizeof(l3d_test_pair_path), offsetof(l3d_test_pair_path, seg_begin), offsetof(l3d_test_pair_path, capacity), offsetof(l3d_test_pair_path, overflow),\n'
+                   '  sizeof(l3d_test_products_path), offsetof(l3d_test_products_path, held), offsetof(l3d_test_products_path, block_capacity),\n'
+                   '  offsetof(l3d_test_products_path, early_g), offsetof(l3d_test_products_path, block_cap), offsetof(l3d_test_products_path, block_g),\n'
+                   '  sizeof(l3d_chain_view), offsetof(l3d_chain_view, local2global), offsetof(l3d_chain_view, spatial_k), sizeof(l3d_chain_summary)); return 0; }\n')
     exe = str(tmp_path / "layout")
     subprocess.check_call(["gcc", "-std=c99", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe])
     got = [int(x) for x in subprocess.run([exe], capture_output=True, text=True).stdout.split()]
@@ -48,7 +51,10 @@ def test_struct_layouts(tmp_path):
     assert got == [capi.MATCH_DTYPE.itemsize, capi.EDGE_DTYPE.itemsize, capi.HYP_DTYPE.itemsize, ctypes.sizeof(A), A.seg_base.offset, A.n_hyp.offset,
                    A.hyp.offset, A.coll_w.offset, A.sigma_a.offset,
                    ctypes.sizeof(capi.VerifyPath), capi.VerifyPath.wide_max.offset, capi.VerifyPath.kernels.offset, capi.VerifyPath.seg_order.offset,
-                   ctypes.sizeof(capi.PairPath), capi.PairPath.seg_begin.offset, capi.PairPath.capacity.offset, capi.PairPath.overflow.offset], got
+                   ctypes.sizeof(capi.PairPath), capi.PairPath.seg_begin.offset, capi.PairPath.capacity.offset, capi.PairPath.overflow.offset,
+                   ctypes.sizeof(capi.ProductsPath), capi.ProductsPath.held.offset, capi.ProductsPath.block_capacity.offset, capi.ProductsPath.early_g.offset,
+                   capi.ProductsPath.block_cap.offset, capi.ProductsPath.block_g.offset,
+                   ctypes.sizeof(capi.ChainView), capi.ChainView.local2global.offset, capi.ChainView.spatial_k.offset, capi.SUMMARY_DTYPE.itemsize], got
 
 
 def test_no_gpu_fails_loudly():
