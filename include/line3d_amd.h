@@ -807,7 +807,7 @@ int l3d_line3d_add_image_fixed_sim_ex(l3d_line3d* h, uint32_t image_id, unsigned
  * ================================================================================================= */
 int l3d_detect_segments(l3d_ctx* ctx, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, int new_width, int new_height,
                         float min_length, int max_segments, float** segments, int* n);
-/* Undistortion on the device (k_det_undistort, l3d_detect.hip): what the drivers do to an image before addImage sees it
+/* Undistortion on the device (k_det_undistort, l3d_undistort.hip): what the drivers do to an image before addImage sees it
  * (main_vsfm.cpp:243-270, main_bundler.cpp:256-284): cv::initUndistortRectifyMap(K, dist, I, K) + cv::remap(INTER_LINEAR, BORDER_CONSTANT),
  * same size, same K.  fx, fy, cx, cy: the camera; k1, k2: OpenCV-convention radial coefficients (tangential terms and k3 are zero in both
  * drivers; a scene file's own numbers become k1, k2 by l3d_sfm_camera_cv_distortion).  For output pixel (column j, row i), in double:
@@ -834,7 +834,7 @@ int l3d_undistort_image(l3d_ctx* ctx, const unsigned char* pixels, int width, in
 int l3d_detect_segments_distorted(l3d_ctx* ctx, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, int new_width, int new_height,
                                   float min_length, int max_segments, double fx, double fy, double cx, double cy, double k1, double k2, float** segments, int* n);
 /* A LENS: undistortion with tangential, rational and fisheye models, onto a camera matrix of the caller's choice (k_det_undistort_lens,
- * l3d_detect.hip).  The calls above know two radial coefficients and resample onto the same camera; the ..._lens calls take an l3d_lens and an
+ * l3d_undistort.hip).  The calls above know two radial coefficients and resample onto the same camera; the ..._lens calls take an l3d_lens and an
  * OUTPUT camera (fx', fy', cx', cy') -- at context level four doubles, in the add family the entry's K, which is also the view's K.  The lens
  * carries the SOURCE camera, that of the distorted image; fx == 0 && fy == 0 there says "the output camera".  When the two differ the image is
  * resampled onto the new camera matrix, at the same size: that is what makes a fisheye usable, the caller can zoom out (fx' < fx).  Another
@@ -880,7 +880,7 @@ typedef struct l3d_lens {
 } l3d_lens;
 int l3d_undistort_image_lens(l3d_ctx* ctx, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, double fx, double fy, double cx,
                              double cy, const l3d_lens* lens, unsigned char* out, size_t out_row_stride);
-/* A REMAP: undistortion onto a PLANNED camera and ANOTHER SIZE, with a VALIDITY PLANE (l3d_remap_plan.cpp; k_det_undistort_remap, l3d_detect.hip).
+/* A REMAP: undistortion onto a PLANNED camera and ANOTHER SIZE, with a VALIDITY PLANE (l3d_remap_plan.cpp; k_det_undistort_remap, l3d_undistort.hip).
  *
  * THE PLANNER, l3d_undistort_plan: host code in double, no context and no device.  lens: a lens WITH its source camera (fx, fy > 0); model 0 means
  * a pinhole camera (the coefficients are not read).  width, height: the source image.
@@ -968,6 +968,12 @@ int l3d_undistort_plan(const l3d_lens* lens, int width, int height, double alpha
 const char* l3d_undistort_plan_error(void);
 int l3d_undistort_image_remap(l3d_ctx* ctx, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, double fx, double fy, double cx,
                               double cy, const l3d_remap* remap, unsigned char* out, size_t out_row_stride, unsigned char* valid, size_t valid_row_stride);
+/* (tests) host only, no context and no device: what the batch calls make of an entry with this camera (NULL, or fx, fy, cx, cy, k1, k2), lens and
+ * remap (either may be NULL) for an image of width x height x channels -- the refusals above with their codes, the cause in msg (n bytes), or L3D_OK
+ * with *route: 0 nothing is launched, 1 k_det_undistort, 2 k_det_undistort_lens, 3 k_det_undistort_remap; *plane: 1 when the image carries a
+ * validity plane through the detector (a mask, or a remap that resamples); and the size the detector sees */
+int l3d_test_undistort_route(const double* camera /* NULL or 6 */, const l3d_lens* lens, const l3d_remap* remap, int width, int height, int channels, int* route,
+                             int* plane, int* out_width, int* out_height, char* msg, size_t n);
 /* Line3D::addImage / addImage_fixed_sim from pixels (line3D.cc:95-217, 220-324): the image entry (THE ADD FAMILY, below) with pixels filled and no
  * dist.  The detector runs at the size the max_img_width rule gives, with min_length = 0.005 sqrt(rows^2 + cols^2) and at most 3000 segments. */
 int l3d_line3d_add_image_pixels(l3d_line3d* h, uint32_t image_id, const unsigned char* pixels, int width, int height, int channels, size_t row_stride,

@@ -321,6 +321,21 @@ def undistort_plan(lens_, size, alpha=0.0, out_size=None, max_dim=0, fov_max_deg
     return K.reshape(3, 3), (w.value, h.value)
 
 
+def undistort_route(camera, lens_, remap_, size, channels=1):
+    """l3d_test_undistort_route (host only, no context and no device): what a batch entry with this camera (None or fx, fy, cx, cy, k1, k2), lens
+    and remap (capi.lens / capi.remap or None) makes of an image of size = (width, height) -> (code, message, route, plane, (out_width, out_height));
+    route: 0 none, 1 k_det_undistort, 2 k_det_undistort_lens, 3 k_det_undistort_remap.  A refusal is returned, not raised."""
+    lib = load_library()
+    cam = None if camera is None else np.ascontiguousarray(camera, np.float64)
+    route, plane, ow, oh = C.c_int(-1), C.c_int(-1), C.c_int(-1), C.c_int(-1)
+    msg = C.create_string_buffer(256)
+    rc = lib.l3d_test_undistort_route(None if cam is None else _p(cam), None if lens_ is None else C.byref(lens_), None if remap_ is None else C.byref(remap_),
+                                      C.c_int(int(size[0])), C.c_int(int(size[1])), C.c_int(int(channels)), C.byref(route), C.byref(plane), C.byref(ow), C.byref(oh),
+                                      msg, C.c_size_t(len(msg)))
+    return rc, msg.value.decode(), route.value, plane.value, (ow.value, oh.value)
+
+
+
 
 def remap_pointers(lenses, out_sizes, masks, border_masks, n):
     """the `const l3d_remap* const*` argument of the ..._remap calls, or None when no image asks for another size, a mask or a border rule (then

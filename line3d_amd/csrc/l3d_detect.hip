@@ -37,8 +37,6 @@ constexpr int kTaps = 7, kHalf = 3;         // sigma = 0.6 / 0.8: h = ceil(sigma
 constexpr int kRounds = 3;
 
 struct DetCand { double x1, y1, x2, y2; unsigned minpix, pad; };
-// what differs between the images of one chunk, on the device: the camera (on: the image is undistorted), the selection's filter and cap
-struct DetImgParam { DetCamera cam; int cam_on; float min_length; int max_segments; int pad; };
 
 // ---- rescale (bilinear, half-pixel centres, 8-bit weights) + grey: the integer formulas stated in include/line3d_amd.h
 __device__ inline void axis_taps(int i, int n_out, int n_in, int& i0, int& i1, int& a)
@@ -72,99 +70,6 @@ __global__ void k_det_grey(const unsigned char* __restrict__ px, int w, int h, i
     }
     const int g = ch == 1 ? v[0] : (299 * v[0] + 587 * v[1] + 114 * v[2] + 500) / 1000;
     grey[(size_t)y * nw + x] = (float)g;
-}
-
-// ---- undistortion (radial k1, k2), in front of the rescale: the formulas stated in include/line3d_amd.h.  One thread per output pixel, the map in
-// doubles (none is stored), 5 fractional bits per coordinate, the four taps weighted in 1/1024 with black outside the image.  Blocks are 32 x 8:
-// the taps of a wave lie within a few source rows
-constexpr int kUndBx = 32, kUndBy = 8;
-// prm: the cameras of a chunk's images (blockIdx.z), an image without one is copied; null: `one` for the single image
-__global__ __launch_bounds__(256) void k_det_undistort(const unsigned char* __restrict__ src, int w, int h, int ch, DetCamera one, const DetImgParam* __restrict__ prm,
-                                                        unsigned char* __restrict__ dst)
-{
-    const int j = blockIdx.x * kUndBx + threadIdx.x, i = blockIdx.y * kUndBy + threadIdx.y;
-    if (j >= w || i >= h) return;
-    src += (size_t)blockIdx.z * w * h * ch;
-    dst += (size_t)blockIdx.z * w * h * ch;
-    if (prm && !prm[blockIdx.z].cam_on) {
-        const size_t at = ((size_t)i * w + j) * ch;
-        for (int k = 0; k < ch; ++k) dst[at + k] = src[at + k];
-        return;
-    }
-    const DetCamera cam = prm ? prm[blockIdx.z].cam : one;
-    const double x = ((double)j - cam.cx) / cam.fx, y = ((double)i - cam.cy) / cam.fy;
-    const double r2 = x * x + y * y, kr = 1.0 + (cam.k2 * r2 + cam.k1) * r2;
-    const double u = cam.fx * (x * kr) + cam.cx, v = cam.fy * (y * kr) + cam.cy;
-    unsigned char* o = dst + ((size_t)i * w + j) * ch;
-    if (!(u > -1.0 && u < (double)w && v > -1.0 && v < (double)h)) {         // NaN lands here; tested before any conversion to an integer
-        for (int k = 0; k < ch; ++k) o[k] = 0;
-        return;
-    }
-    const int iu = (int)rint(32.0 * u), iv = (int)rint(32.0 * v);             // in [-32, 32 w] x [-32, 32 h]
-    const int x0 = iu >> 5, a = iu & 31, y0 = iv >> 5, b = iv & 31;           // floor and remainder, for negative values as well
-    const bool cx0 = x0 >= 0 && x0 < w, cx1 = x0 + 1 >= 0 && x0 + 1 < w, ry0 = y0 >= 0 && y0 < h, ry1 = y0 + 1 >= 0 && y0 + 1 < h;
-    const int w00 = (32 - a) * (32 - b), w01 = a * (32 - b), w10 = (32 - a) * b, w11 = a * b;
-    const unsigned char* r0 = src + (size_t)(ry0 ? y0 : 0) * w * ch;
-    const unsigned char* r1 = src + (size_t)(ry1 ? y0 + 1 : 0) * w * ch;
-    const size_t c0 = (size_t)(cx0 ? x0 : 0) * ch, c1 = (size_t)(cx1 ? x0 + 1 : 0) * ch;
-    for (int k = 0; k < ch; ++k) {
-        const int p00 = ry0 && cx0 ? r0[c0 + k] : 0, p01 = ry0 && cx1 ? r0[c1 + k] : 0;
-        const int p10 = ry1 && cx0 ? r1[c0 + k] : 0, p11 = ry1 && cx1 ? r1[c1 + k] : 0;
-        o[k] = (unsigned char)((w00 * p00 + w01 * p01 + w10 * p10 + w11 * p11 + 512) >> 10);
-    }
-}
-
-// ---- undistortion with a lens (BROWN: radial, tangential, rational; FISHEYE) onto an output camera: "A LENS" in include/line3d_amd.h, every operation
-// in the order stated there.  The launch shape, the inside test and the taps are k_det_undistort's; that kernel is left as it is (its own copy of the
-// taps included) so that a chunk of k1, k2 cameras keeps its instruction stream.  The lens comes per image from the chunk's table: blockIdx.z is the
-// image, so the load is scalar and the branch on the model is uniform across a block.  tab: the chunk's lenses (model 0: the image is copied); a
-// single image comes with a table of one (a choice between the table and a by-value argument made the compiler read the lens with per-lane loads)
-__global__ __launch_bounds__(256) void k_det_undistort_lens(const unsigned char* __restrict__ src, int w, int h, int ch, const DetLens* __restrict__ tab,
-                                                             unsigned char* __restrict__ dst)
-{
-    const int j = blockIdx.x * kUndBx + threadIdx.x, i = blockIdx.y * kUndBy + threadIdx.y;
-    if (j >= w || i >= h) return;
-    src += (size_t)blockIdx.z * w * h * ch;
-    dst += (size_t)blockIdx.z * w * h * ch;
-    const DetLens L = tab[blockIdx.z];
-    unsigned char* o = dst + ((size_t)i * w + j) * ch;
-    if (L.model == 0) {
-        const unsigned char* s = src + ((size_t)i * w + j) * ch;
-        for (int k = 0; k < ch; ++k) o[k] = s[k];
-        return;
-    }
-    const double x = ((double)j - L.ocx) / L.ofx, y = ((double)i - L.ocy) / L.ofy;
-    const double r2 = x * x + y * y;
-    double xd, yd;
-    if (L.model == L3D_LENS_BROWN) {
-        const double k1 = L.k[0], k2 = L.k[1], p1 = L.k[2], p2 = L.k[3], k3 = L.k[4], k4 = L.k[5], k5 = L.k[6], k6 = L.k[7];
-        const double num = 1.0 + ((k3 * r2 + k2) * r2 + k1) * r2, den = 1.0 + ((k6 * r2 + k5) * r2 + k4) * r2;
-        const double kr = num / den;
-        xd = x * kr + ((2.0 * p1) * x * y + p2 * (r2 + 2.0 * (x * x)));
-        yd = y * kr + (p1 * (r2 + 2.0 * (y * y)) + (2.0 * p2) * x * y);
-    } else {
-        const double r = __builtin_sqrt(r2), th = atan(r), t2 = th * th;
-        const double td = th * (1.0 + (((L.k[3] * t2 + L.k[2]) * t2 + L.k[1]) * t2 + L.k[0]) * t2);
-        const double s = r > 1e-8 ? td / r : 1.0;
-        xd = x * s; yd = y * s;
-    }
-    const double u = L.fx * xd + L.cx, v = L.fy * yd + L.cy;
-    if (!(u > -1.0 && u < (double)w && v > -1.0 && v < (double)h)) {         // NaN and inf land here; tested before any conversion to an integer
-        for (int k = 0; k < ch; ++k) o[k] = 0;
-        return;
-    }
-    const int iu = (int)rint(32.0 * u), iv = (int)rint(32.0 * v);             // in [-32, 32 w] x [-32, 32 h]
-    const int x0 = iu >> 5, a = iu & 31, y0 = iv >> 5, b = iv & 31;
-    const bool cx0 = x0 >= 0 && x0 < w, cx1 = x0 + 1 >= 0 && x0 + 1 < w, ry0 = y0 >= 0 && y0 < h, ry1 = y0 + 1 >= 0 && y0 + 1 < h;
-    const int w00 = (32 - a) * (32 - b), w01 = a * (32 - b), w10 = (32 - a) * b, w11 = a * b;
-    const unsigned char* r0 = src + (size_t)(ry0 ? y0 : 0) * w * ch;           // (an index that is off the image is never formed: row and column 0 stand in)
-    const unsigned char* r1 = src + (size_t)(ry1 ? y0 + 1 : 0) * w * ch;
-    const size_t c0 = (size_t)(cx0 ? x0 : 0) * ch, c1 = (size_t)(cx1 ? x0 + 1 : 0) * ch;
-    for (int k = 0; k < ch; ++k) {
-        const int p00 = ry0 && cx0 ? r0[c0 + k] : 0, p01 = ry0 && cx1 ? r0[c1 + k] : 0;
-        const int p10 = ry1 && cx0 ? r1[c0 + k] : 0, p11 = ry1 && cx1 ? r1[c1 + k] : 0;
-        o[k] = (unsigned char)((w00 * p00 + w01 * p01 + w10 * p10 + w11 * p11 + 512) >> 10);
-    }
 }
 
 // ---- Gaussian sub-sampling, separable, 7 taps; centres and weights per output column / row come from the host (computed as the
@@ -247,83 +152,6 @@ __global__ void k_det_grad(const double* __restrict__ img, int N, int M, double 
     }
     bucket[i] = b;
     active[i] = a != kNotDef;
-}
-
-// ---- undistortion onto another size, with a validity plane: "A REMAP" in include/line3d_amd.h.  One thread per pixel of the OUTPUT (ow x oh), the
-// source stack is w x h; the map and the taps are k_det_undistort_lens's, word for word (that kernel and k_det_undistort are left as they are; this one stands behind k_det_grad in the file so that
-// the listings of the kernels before it keep even their label numbers).
-// tab: the chunk's lenses -- model 0: the image is copied, which the host allows only where the two sizes are equal.  flags, per image:
-// kRemapMask: smask holds a plane of the caller's for this image (w x h bytes per image, non-zero = valid; smask may be null when no image has the
-// flag); kRemapBorder: a pixel outside, or with a weighted tap off the source, is invalid.  valid: ow x oh bytes per image, 255 or 0
-constexpr int kRemapMask = 1, kRemapBorder = 2;
-__global__ __launch_bounds__(256) void k_det_undistort_remap(const unsigned char* __restrict__ src, int w, int h, int ch, const DetLens* __restrict__ tab,
-                                                              const int* __restrict__ flags, const unsigned char* __restrict__ smask, unsigned char* __restrict__ dst,
-                                                              int ow, int oh, unsigned char* __restrict__ valid)
-{
-    const int j = blockIdx.x * kUndBx + threadIdx.x, i = blockIdx.y * kUndBy + threadIdx.y;
-    if (j >= ow || i >= oh) return;
-    src += (size_t)blockIdx.z * w * h * ch;
-    dst += (size_t)blockIdx.z * ow * oh * ch;
-    valid += (size_t)blockIdx.z * ow * oh;
-    const DetLens L = tab[blockIdx.z];
-    const int fl = flags[blockIdx.z];
-    const unsigned char* mk = (fl & kRemapMask) ? smask + (size_t)blockIdx.z * w * h : nullptr;
-    unsigned char* o = dst + ((size_t)i * ow + j) * ch;
-    unsigned char* vo = valid + (size_t)i * ow + j;
-    if (L.model == 0) {
-        if (j >= w || i >= h) { for (int k = 0; k < ch; ++k) o[k] = 0; *vo = 0; return; }       // (not reached: the host keeps ow == w, oh == h here)
-        const unsigned char* s = src + ((size_t)i * w + j) * ch;
-        for (int k = 0; k < ch; ++k) o[k] = s[k];
-        *vo = !mk || mk[(size_t)i * w + j] ? 255 : 0;
-        return;
-    }
-    const double x = ((double)j - L.ocx) / L.ofx, y = ((double)i - L.ocy) / L.ofy;
-    const double r2 = x * x + y * y;
-    double xd, yd;
-    if (L.model == L3D_LENS_BROWN) {
-        const double k1 = L.k[0], k2 = L.k[1], p1 = L.k[2], p2 = L.k[3], k3 = L.k[4], k4 = L.k[5], k5 = L.k[6], k6 = L.k[7];
-        const double num = 1.0 + ((k3 * r2 + k2) * r2 + k1) * r2, den = 1.0 + ((k6 * r2 + k5) * r2 + k4) * r2;
-        const double kr = num / den;
-        xd = x * kr + ((2.0 * p1) * x * y + p2 * (r2 + 2.0 * (x * x)));
-        yd = y * kr + (p1 * (r2 + 2.0 * (y * y)) + (2.0 * p2) * x * y);
-    } else {
-        const double r = __builtin_sqrt(r2), th = atan(r), t2 = th * th;
-        const double td = th * (1.0 + (((L.k[3] * t2 + L.k[2]) * t2 + L.k[1]) * t2 + L.k[0]) * t2);
-        const double s = r > 1e-8 ? td / r : 1.0;
-        xd = x * s; yd = y * s;
-    }
-    const double u = L.fx * xd + L.cx, v = L.fy * yd + L.cy;
-    if (!(u > -1.0 && u < (double)w && v > -1.0 && v < (double)h)) {         // NaN and inf land here; tested before any conversion to an integer
-        for (int k = 0; k < ch; ++k) o[k] = 0;
-        *vo = (fl & kRemapBorder) ? 0 : 255;
-        return;
-    }
-    const int iu = (int)rint(32.0 * u), iv = (int)rint(32.0 * v);             // in [-32, 32 w] x [-32, 32 h]
-    const int x0 = iu >> 5, a = iu & 31, y0 = iv >> 5, b = iv & 31;
-    const bool cx0 = x0 >= 0 && x0 < w, cx1 = x0 + 1 >= 0 && x0 + 1 < w, ry0 = y0 >= 0 && y0 < h, ry1 = y0 + 1 >= 0 && y0 + 1 < h;
-    const int w00 = (32 - a) * (32 - b), w01 = a * (32 - b), w10 = (32 - a) * b, w11 = a * b;
-    const size_t q0 = (size_t)(ry0 ? y0 : 0) * w, q1 = (size_t)(ry1 ? y0 + 1 : 0) * w;    // (an index that is off the image is never formed: row and column 0 stand in)
-    const size_t e0 = (size_t)(cx0 ? x0 : 0), e1 = (size_t)(cx1 ? x0 + 1 : 0);
-    const unsigned char* r0 = src + q0 * ch;
-    const unsigned char* r1 = src + q1 * ch;
-    const size_t c0 = e0 * ch, c1 = e1 * ch;
-    for (int k = 0; k < ch; ++k) {
-        const int p00 = ry0 && cx0 ? r0[c0 + k] : 0, p01 = ry0 && cx1 ? r0[c1 + k] : 0;
-        const int p10 = ry1 && cx0 ? r1[c0 + k] : 0, p11 = ry1 && cx1 ? r1[c1 + k] : 0;
-        o[k] = (unsigned char)((w00 * p00 + w01 * p01 + w10 * p10 + w11 * p11 + 512) >> 10);
-    }
-    // a tap counts iff its weight is not zero: it must lie inside the source (the border rule) and be valid in the caller's plane (a tap off the
-    // source has no entry there and is left to the border rule)
-    const bool i00 = ry0 && cx0, i01 = ry0 && cx1, i10 = ry1 && cx0, i11 = ry1 && cx1;
-    bool ok = true;
-    if (fl & kRemapBorder) ok = (!w00 || i00) && (!w01 || i01) && (!w10 || i10) && (!w11 || i11);
-    if (mk) {
-        if (w00 && i00) ok = ok && mk[q0 + e0];
-        if (w01 && i01) ok = ok && mk[q0 + e1];
-        if (w10 && i10) ok = ok && mk[q1 + e0];
-        if (w11 && i11) ok = ok && mk[q1 + e1];
-    }
-    *vo = ok ? 255 : 0;
 }
 
 // ---- the validity plane beside the pixel stages ("A REMAP" in include/line3d_amd.h): a gradient pixel is UNDEFINED if any pixel that contributed to
@@ -800,8 +628,9 @@ inline int* det_n_cand(DetectBufs& d) { return d.scal.as<int>() + kScalHead; }
 inline size_t det_out_head(int B) { return ((size_t)B * 4 + 15) & ~(size_t)15; }      // d.out: the images' segment counts, then the segments
 
 // bytes of the device buffers one image of a chunk takes (what det_reserve sums up, with the buffers' slack): the chunk rule's memory term
-size_t det_image_bytes(const DetPlan& p, bool undist, size_t jpeg_blocks, bool valid = false)
+size_t det_image_bytes(const DetPlan& p, WarpRoute route, size_t jpeg_blocks, bool valid)
 {
+    const bool undist = route != WarpRoute::None;
     const size_t np = (size_t)p.np, cc = (size_t)p.cand_cap;
     size_t b = (size_t)p.sw * p.sh * p.ch + (undist ? (size_t)p.w * p.h * p.ch : 0) + (size_t)p.nw * p.nh * 4 + (size_t)p.N * p.nh * 8;
     if (valid) b += (size_t)p.sw * p.sh + (size_t)p.w * p.h + (size_t)p.nw * p.nh + (size_t)p.N * p.nh + 2 * np;
@@ -810,8 +639,10 @@ size_t det_image_bytes(const DetPlan& p, bool undist, size_t jpeg_blocks, bool v
     return b + b / 4;
 }
 
-int det_reserve(l3d_ctx* c, const DetPlan& p, size_t out_slots, bool undist = false, bool valid = false)
+// route, valid: the chunk's kernel and whether it carries validity planes (detect_chunk)
+int det_reserve(l3d_ctx* c, const DetPlan& p, size_t out_slots, WarpRoute route = WarpRoute::None, bool valid = false)
 {
+    const bool undist = route != WarpRoute::None;
     hipStream_t st = c->stream;
     DetectBufs& d = c->det;
     const size_t B = (size_t)p.B, np = (size_t)p.stack(), cand_cap = (size_t)p.cand_cap * B;
@@ -862,96 +693,6 @@ int det_reserve(l3d_ctx* c, const DetPlan& p, size_t out_slots, bool undist = fa
 // the flags and the images' candidate counters
 hipError_t det_zero_scalars(l3d_ctx* c, int B) { return hipMemsetAsync(c->det.scal.p, 0, ((size_t)kScalHead + B) * 4, c->stream); }
 
-// the camera of an undistortion: fx, fy finite and not zero; *active: a coefficient above L3D_EPS (commons.h:66, the drivers' condition) -- otherwise
-// nothing is launched and the pixels pass through
-constexpr double kDistEps = 1e-12;
-int check_camera(const DetCamera& cam, int w, int h, bool* active, std::string& err)
-{
-    if (w > (1 << 24) || h > (1 << 24)) { err = "undistort: image too large"; return L3D_ERR_UNSUPPORTED; }      // 32 x a coordinate stays an int
-    if (!std::isfinite(cam.fx) || !std::isfinite(cam.fy) || cam.fx == 0.0 || cam.fy == 0.0) { err = "undistort: fx and fy must be finite and not zero"; return L3D_ERR_INVALID; }
-    *active = !(fabs(cam.k1) <= kDistEps && fabs(cam.k2) <= kDistEps);
-    return L3D_OK;
-}
-// d.pixels -> d.undist, B images: each with its camera of `prm` (device; an image without one is copied), or all (B = 1) with `one` when prm is null
-void launch_undistort(l3d_ctx* c, int w, int h, int ch, int B, const DetCamera& one, const DetImgParam* prm)
-{
-    DetectBufs& d = c->det;
-    ProfScope ps(c, "k_det_undistort");
-    hipLaunchKernelGGL(k_det_undistort, dim3((w + kUndBx - 1) / kUndBx, (h + kUndBy - 1) / kUndBy, B), dim3(kUndBx, kUndBy), 0, c->stream, d.pixels.as<unsigned char>(), w, h, ch, one, prm,
-                       d.undist.as<unsigned char>());
-}
-
-// the same with lenses: the B entries of `tab` (host; it has to live until the stream has been synchronised) go to d.lens, one launch follows
-int launch_undistort_lens(l3d_ctx* c, int w, int h, int ch, int B, const DetLens* tab)
-{
-    DetectBufs& d = c->det;
-    HIPCHK(c, d.lens.reserve((size_t)B * sizeof(DetLens)));
-    HIPCHK(c, hipMemcpyAsync(d.lens.p, tab, (size_t)B * sizeof(DetLens), hipMemcpyHostToDevice, c->stream));
-    ProfScope ps(c, "k_det_undistort_lens");
-    hipLaunchKernelGGL(k_det_undistort_lens, dim3((w + kUndBx - 1) / kUndBx, (h + kUndBy - 1) / kUndBy, B), dim3(kUndBx, kUndBy), 0, c->stream, d.pixels.as<unsigned char>(), w, h,
-                       ch, d.lens.as<DetLens>(), d.undist.as<unsigned char>());
-    return L3D_OK;
-}
-// a k1, k2 camera as the lens that performs its operations (BROWN, the cameras equal): the place of such an image in a chunk that has lenses
-DetLens lens_of_camera(const DetCamera& cam)
-{
-    DetLens l{};
-    l.model = L3D_LENS_BROWN;
-    l.fx = l.ofx = cam.fx; l.fy = l.ofy = cam.fy; l.cx = l.ocx = cam.cx; l.cy = l.ocy = cam.cy;
-    l.k[0] = cam.k1; l.k[1] = cam.k2;
-    return l;
-}
-
-// ---- a remap's helpers: the mask as a plane, the mask's way to the device, the launch
-__global__ void k_det_valid_from_mask(const unsigned char* __restrict__ smask, size_t n, unsigned char* __restrict__ valid)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) valid[i] = smask[i] ? 255 : 0;
-}
-
-// the caller's mask into slot b of d.smask (reserved by the caller for the chunk): a device mask is checked as an l3d_device_image is, before the copy
-int remap_mask_upload(l3d_ctx* c, const DetRemap& r, int w, int h, int b)
-{
-    if (r.mask_on_device) {
-        l3d_device_image im{};
-        im.ptr = r.mask; im.width = w; im.height = h; im.channels = 1; im.dtype = L3D_U8; im.stride_y = (long long)r.mask_stride; im.stride_x = 1; im.stride_c = 0;
-        std::string err;
-        if (int rc = device_image_pointer(c, im, err)) return fail(c, rc, "remap mask: " + err);
-    }
-    HIPCHK(c, hipMemcpy2DAsync(c->det.smask.as<unsigned char>() + (size_t)b * w * h, (size_t)w, r.mask, r.mask_stride, (size_t)w, (size_t)h,
-                               r.mask_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
-    return L3D_OK;
-}
-
-// the validity plane of an image that is NOT resampled, into slot b of d.valid (n = w x h bytes per slot, reserved by the caller): the caller's mask
-// (already in slot b of d.smask) as 255 / 0, or all valid
-int plane_without_resample(l3d_ctx* c, bool has_mask, size_t n, int b)
-{
-    DetectBufs& d = c->det;
-    unsigned char* v = d.valid.as<unsigned char>() + (size_t)b * n;
-    if (!has_mask) { HIPCHK(c, hipMemsetAsync(v, 255, n, c->stream)); return L3D_OK; }
-    ProfScope ps(c, "k_det_valid_from_mask");
-    hipLaunchKernelGGL(k_det_valid_from_mask, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, d.smask.as<unsigned char>() + (size_t)b * n, n, v);
-    return L3D_OK;
-}
-
-// d.pixels (B images, w x h) -> d.undist (ow x oh) and d.valid: `tab` and `flags` (host; they live until the stream has been synchronised) go to
-// d.lens and d.rflags, one launch follows.  d.smask holds the masks of the images whose flag says so
-int launch_undistort_remap(l3d_ctx* c, int w, int h, int ch, int ow, int oh, int B, const DetLens* tab, const int* flags)
-{
-    DetectBufs& d = c->det;
-    HIPCHK(c, d.lens.reserve((size_t)B * sizeof(DetLens)));
-    HIPCHK(c, d.rflags.reserve((size_t)B * sizeof(int)));
-    HIPCHK(c, d.undist.reserve((size_t)B * ow * oh * ch));
-    HIPCHK(c, d.valid.reserve((size_t)B * ow * oh));
-    HIPCHK(c, hipMemcpyAsync(d.lens.p, tab, (size_t)B * sizeof(DetLens), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d.rflags.p, flags, (size_t)B * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    ProfScope ps(c, "k_det_undistort_remap");
-    hipLaunchKernelGGL(k_det_undistort_remap, dim3((ow + kUndBx - 1) / kUndBx, (oh + kUndBy - 1) / kUndBy, B), dim3(kUndBx, kUndBy), 0, c->stream, d.pixels.as<unsigned char>(), w, h,
-                       ch, d.lens.as<DetLens>(), d.rflags.as<int>(), d.smask.as<unsigned char>(), d.undist.as<unsigned char>(), ow, oh, d.valid.as<unsigned char>());
-    return L3D_OK;
-}
-
 // image b of the chunk: host pixels into its slot of d.pixels
 hipError_t det_upload(l3d_ctx* c, const DetPlan& p, int b, const unsigned char* pixels, size_t stride)
 {
@@ -959,12 +700,11 @@ hipError_t det_upload(l3d_ctx* c, const DetPlan& p, int b, const unsigned char* 
     return hipMemcpy2DAsync(c->det.pixels.as<unsigned char>() + (size_t)b * row * p.sh, row, pixels, stride, row, (size_t)p.sh, hipMemcpyHostToDevice, c->stream);
 }
 
-// ---- pixel stage on the chunk's images in d.pixels (uploaded, or decoded JPEG): undistortion (undist: some image has a camera, d.prm says which;
-// lens_tab: some image has a lens, and this table on the host holds every image's -- then k_det_undistort_lens runs in place of k_det_undistort),
-// rescale + grey, the two sampler passes, gradient -- one launch each, the image in blockIdx.z; leaves the scalars zeroed
-// remap_flags: some image is resampled by a remap -- lens_tab and these flags (host) hold every image's, k_det_undistort_remap runs in the place of both
-// other kernels and writes d.valid; valid: d.valid holds the chunk's validity planes (w x h each) and is carried beside the stages
-int det_pixel_stage(l3d_ctx* c, const DetPlan& p, bool undist = false, const DetLens* lens_tab = nullptr, const int* remap_flags = nullptr, bool valid = false)
+// ---- pixel stage on the chunk's images in d.pixels (uploaded, or decoded JPEG): the chunk's undistortion kernel, rescale + grey, the two sampler passes,
+// gradient -- one launch each, the image in blockIdx.z; leaves the scalars zeroed.  route: the strongest any image needs -- Radial reads the cameras
+// in d.prm, Lens and Resample take every image's entry of lens_tab (host) and Resample every image's flags as well, and writes d.valid.  valid: d.valid
+// holds the chunk's validity planes (w x h each) and is carried beside the stages
+int det_pixel_stage(l3d_ctx* c, const DetPlan& p, WarpRoute route = WarpRoute::None, bool valid = false, const DetLens* lens_tab = nullptr, const int* remap_flags = nullptr)
 {
     hipStream_t st = c->stream;
     DetectBufs& d = c->det;
@@ -985,9 +725,10 @@ int det_pixel_stage(l3d_ctx* c, const DetPlan& p, bool undist = false, const Det
     const int* kc = reinterpret_cast<const int*>(static_cast<const char*>(d.ktab.p) + ((size_t)N + M) * kTaps * 8);
     const dim3 b256(256);
     const unsigned char* image = d.pixels.as<unsigned char>();          // whichever buffer holds the images k_det_grey reads
-    if (remap_flags) { if (int rc = launch_undistort_remap(c, p.sw, p.sh, ch, w, h, B, lens_tab, remap_flags)) return rc; image = d.undist.as<unsigned char>(); }
-    else if (lens_tab) { if (int rc = launch_undistort_lens(c, w, h, ch, B, lens_tab)) return rc; image = d.undist.as<unsigned char>(); }
-    else if (undist) { launch_undistort(c, w, h, ch, B, DetCamera{ 1.0, 1.0, 0.0, 0.0, 0.0, 0.0 }, d.prm.as<DetImgParam>()); image = d.undist.as<unsigned char>(); }
+    if (route == WarpRoute::Resample) { if (int rc = launch_undistort_remap(c, p.sw, p.sh, ch, w, h, B, lens_tab, remap_flags)) return rc; }
+    else if (route == WarpRoute::Lens) { if (int rc = launch_undistort_lens(c, w, h, ch, B, lens_tab)) return rc; }
+    else if (route == WarpRoute::Radial) launch_undistort(c, w, h, ch, B, DetCamera{ 1.0, 1.0, 0.0, 0.0, 0.0, 0.0 }, d.prm.as<DetImgParam>());
+    if (route != WarpRoute::None) image = d.undist.as<unsigned char>();
     { ProfScope ps(c, "k_det_grey"); hipLaunchKernelGGL(k_det_grey, dim3((nw + 255) / 256, nh, B), b256, 0, st, image, w, h, ch, nw, nh, d.grey.as<float>()); }
     { ProfScope ps(c, "k_det_gauss_x"); hipLaunchKernelGGL(k_det_gauss_x, dim3((N + 63) / 64, (nh + 3) / 4, B), dim3(64, 4), 0, st, d.grey.as<float>(), nw, nh, d.aux.as<double>(), N, kc, kw); }
     { ProfScope ps(c, "k_det_gauss_y"); hipLaunchKernelGGL(k_det_gauss_y, dim3((N + 63) / 64, (M + kYRows - 1) / kYRows, B), dim3(64, 4), 0, st, d.aux.as<double>(), N, nh, d.img.as<double>(), M, kc + N, kw + (size_t)N * kTaps); }
@@ -1083,12 +824,8 @@ struct DetItem {
     size_t stride = 0;
     const JpegStaged* jpeg = nullptr;
     const l3d_device_image* dev = nullptr;      // an image in device memory (pixels and jpeg null), checked by device_image_pointer
-    DetImgParam prm;
-    bool lens_on = false;                       // the image has an active lens (then prm.cam_on is 0)
-    DetLens lens;
-    bool remap_on = false;                      // the image has a validity plane: a remap that resamples it (then lens is the remap's, lens_on 0), or a mask alone
-    bool resample = false;
-    DetRemap remap;                             // checked (remap_check): the mask, border_mask
+    DetImgParam prm;                            // (cam_on: the image's route is Radial)
+    WarpPlan warp;                              // checked (warp_check)
     std::vector<float>* out = nullptr;
 };
 
@@ -1099,25 +836,25 @@ int detect_chunk(l3d_ctx* c, const DetPlan& p, const DetItem* items)
     hipStream_t st = c->stream;
     DetectBufs& d = c->det;
     const int B = p.B, cand_cap = p.cand_cap;
-    bool undist = false, lens = false, jpeg = false, dev = false, valid = false, resample = false, masks = false;
+    // the chunk's kernel is the strongest route any of its images needs (a weaker image rides along as WarpPlan::L); it carries planes if an image does
+    WarpRoute route = WarpRoute::None;
+    bool jpeg = false, dev = false, valid = false, masks = false;
     size_t out_slots = 0;
     std::vector<DetImgParam> prm((size_t)B);
     for (int b = 0; b < B; ++b) {
         prm[b] = items[b].prm;
-        undist = undist || prm[b].cam_on || items[b].lens_on || items[b].resample;
-        lens = lens || items[b].lens_on;
-        valid = valid || items[b].remap_on;
-        resample = resample || items[b].resample;
-        masks = masks || (items[b].remap_on && items[b].remap.mask);
+        route = std::max(route, items[b].warp.route);
+        valid = valid || items[b].warp.plane;
+        masks = masks || (items[b].warp.flags & kRemapMask);
         jpeg = jpeg || (!items[b].pixels && !items[b].dev);
         dev = dev || items[b].dev;
         out_slots += (size_t)std::min(prm[b].max_segments, cand_cap);
     }
-    if (int rc = det_reserve(c, p, out_slots, undist, valid)) return rc;
+    if (int rc = det_reserve(c, p, out_slots, route, valid)) return rc;
     if (masks) {            // the callers' masks, each into its image's slot (a device mask is checked first)
         HIPCHK(c, d.smask.reserve((size_t)B * p.sw * p.sh));
         for (int b = 0; b < B; ++b)
-            if (items[b].remap_on && items[b].remap.mask) { if (int rc = remap_mask_upload(c, items[b].remap, p.sw, p.sh, b)) return rc; }
+            if (items[b].warp.flags & kRemapMask) { if (int rc = remap_mask_upload(c, items[b].warp, p.sw, p.sh, b)) return rc; }
     }
     if (jpeg) {
         std::vector<const JpegStaged*> files((size_t)B, nullptr);
@@ -1132,28 +869,17 @@ int detect_chunk(l3d_ctx* c, const DetPlan& p, const DetItem* items)
     for (int b = 0; b < B; ++b) if (items[b].pixels) HIPCHK(c, det_upload(c, p, b, items[b].pixels, items[b].stride));
     // (from pageable memory on purpose: a few dozen bytes go faster through the runtime's staging than as a DMA from pinned memory -- measured, 0.03 ms per call)
     HIPCHK(c, hipMemcpyAsync(d.prm.p, prm.data(), (size_t)B * sizeof(DetImgParam), hipMemcpyHostToDevice, st));
-    // a chunk in which every camera is of the k1, k2 kind keeps k_det_undistort; one lens, and the chunk's table goes to k_det_undistort_lens
+    // Lens and Resample: the chunk's table and, for Resample, the flags (a plain lens and a k1, k2 camera have none: every byte of their plane comes
+    // out valid).  A chunk that carries planes and resamples nothing takes them from the masks alone, at the source size
     std::vector<DetLens> lens_tab;
-    if (lens) {
-        lens_tab.assign((size_t)B, DetLens{});
-        for (int b = 0; b < B; ++b) lens_tab[b] = items[b].lens_on ? items[b].lens : prm[b].cam_on ? lens_of_camera(prm[b].cam) : DetLens{};
-    }
-    // a chunk in which a remap resamples an image sends every image through k_det_undistort_remap: a plain lens and a k1, k2 camera with no flag (every
-    // byte of their plane comes out valid), an image without a camera as a copy.  Otherwise the planes come from the masks alone, at the source size
     std::vector<int> rflags;
-    if (resample) {
-        lens_tab.assign((size_t)B, DetLens{});
-        rflags.assign((size_t)B, 0);
-        for (int b = 0; b < B; ++b) {
-            const DetItem& it = items[b];
-            lens_tab[b] = it.resample || it.lens_on ? it.lens : prm[b].cam_on ? lens_of_camera(prm[b].cam) : DetLens{};
-            if (it.remap_on) rflags[b] = (it.remap.mask ? kRemapMask : 0) | (it.resample && it.remap.border_mask ? kRemapBorder : 0);
-        }
-    } else if (valid) {
+    if (route >= WarpRoute::Lens)
+        for (int b = 0; b < B; ++b) { lens_tab.push_back(items[b].warp.L); rflags.push_back(items[b].warp.flags); }
+    if (valid && route != WarpRoute::Resample) {
         for (int b = 0; b < B; ++b)
-            if (int rc = plane_without_resample(c, items[b].remap_on && items[b].remap.mask, (size_t)p.w * p.h, b)) return rc;
+            if (int rc = plane_without_resample(c, items[b].warp.flags & kRemapMask, (size_t)p.w * p.h, b)) return rc;
     }
-    if (int rc = det_pixel_stage(c, p, undist && !resample, lens || resample ? lens_tab.data() : nullptr, resample ? rflags.data() : nullptr, valid)) return rc;
+    if (int rc = det_pixel_stage(c, p, route, valid, lens_tab.data(), rflags.data())) return rc;
 
     // ---- rounds: label, vote, sort, regions
     for (int round = 0; round < kRounds; ++round) {
@@ -1209,7 +935,7 @@ int detect_chunk(l3d_ctx* c, const DetPlan& p, const DetItem* items)
 
 // images per chunk of a group of n: the option, the index widths (the stack within 2^30 pixels), and half of the HBM that is free or held by the
 // detector's own buffers already
-int chunk_images(l3d_ctx* c, const DetPlan& p, int n, bool undist, size_t jpeg_blocks, bool valid = false)
+int chunk_images(l3d_ctx* c, const DetPlan& p, int n, WarpRoute route, size_t jpeg_blocks, bool valid)
 {
     long long lim = std::min<long long>(n, 1024);
     lim = std::min(lim, std::max(1ll, (1ll << 30) / p.np));
@@ -1218,7 +944,7 @@ int chunk_images(l3d_ctx* c, const DetPlan& p, int n, bool undist, size_t jpeg_b
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return 1; }
         const size_t budget = (free_b + c->det.held()) / 2;
-        lim = std::min<long long>(lim, std::max<size_t>(1, budget / det_image_bytes(p, undist, jpeg_blocks, valid)));
+        lim = std::min<long long>(lim, std::max<size_t>(1, budget / det_image_bytes(p, route, jpeg_blocks, valid)));
     }
     return (int)lim;
 }
@@ -1231,8 +957,8 @@ int detect_segments_batch(l3d_ctx* c, const DetEntry* e, int n, std::vector<std:
     message.assign((size_t)std::max(0, n), std::string());
     if (!c) return L3D_ERR_INVALID;
     if (n < 0 || (n > 0 && !e)) return fail(c, L3D_ERR_INVALID, "detect_segments_batch: null argument");
-    // ---- per entry, in order, on the caller's thread: headers, plan, camera.  An entry refused here fails alone
-    struct Work { DetPlan plan; DetImgParam prm; DetLens lens; DetRemap remap; JpegStaged file; bool lens_on = false, remap_on = false, resample = false, todo = false, done = false; };
+    // ---- per entry, in order, on the caller's thread: headers, plan, warp.  An entry refused here fails alone
+    struct Work { DetPlan plan; DetImgParam prm; WarpPlan warp; JpegStaged file; bool todo = false, done = false; };
     std::vector<Work> work((size_t)n);
     std::vector<JpegFrame> frames((size_t)n);
     for (int i = 0; i < n; ++i) {
@@ -1251,29 +977,24 @@ int detect_segments_batch(l3d_ctx* c, const DetEntry* e, int n, std::vector<std:
             k.file.bytes = en.jpeg; k.file.n = en.jpeg_bytes; k.file.f = &frames[i];
         }
         if (en.max_segments < 0) { status[i] = L3D_ERR_INVALID; message[i] = "detect_segments: negative max_segments"; continue; }
-        // a remap: checked at the source size; the detector's image is its output (plan_image), and the plan remembers the source size
-        int ow = w, oh = h;
-        if (en.remap) {
-            if (en.cam || en.lens) { status[i] = L3D_ERR_INVALID; message[i] = "remap: an image carries a remap beside distortion coefficients or a lens of its own"; continue; }
-            // (plan_image below sees the remap's output: what it asks of an image is asked of the source here)
-            if (!(en.pixels != nullptr || en.jpeg != nullptr || dev) || w < 8 || h < 8 || (ch != 1 && ch != 3) || stride < (size_t)w * ch) {
+        // a remap is checked before the plan, at the source size: the detector's image is its output (plan_image), and the plan remembers the source
+        // size.  Everything else is checked behind the plan
+        const bool has_image = en.pixels != nullptr || en.jpeg != nullptr || dev, remap = en.warp.has_remap;
+        if (remap) {
+            // (plan_image below sees the remap's output: what it asks of an image is asked of the source here -- behind the remap's first refusal,
+            // of coefficients or a lens beside it, which is warp_check's first as well)
+            if (!(en.warp.has_cam || en.warp.has_lens) && (!has_image || w < 8 || h < 8 || (ch != 1 && ch != 3) || stride < (size_t)w * ch)) {
                 status[i] = L3D_ERR_INVALID; message[i] = "detect_segments: needs an image of at least 8x8 with 1 or 3 channels and a row stride of at least width x channels"; continue;
             }
-            k.remap = *en.remap;
-            if ((status[i] = remap_check(k.remap, w, h, ch, &k.resample, message[i])) != L3D_OK) continue;
-            ow = k.remap.out_w; oh = k.remap.out_h;
-            const bool plane = k.remap.mask || (k.resample && k.remap.border_mask);
-            if (!plane && k.resample && ow == w && oh == h) { k.lens = k.remap.lens; k.lens_on = true; k.resample = false; }      // a lens alone: its own kernel
-            else if (plane || k.resample) { k.remap_on = true; k.lens = k.remap.lens; }
+            if ((status[i] = warp_check(en.warp, w, h, ch, k.warp, message[i])) != L3D_OK) continue;
         }
-        if ((status[i] = plan_image(k.plan, en.pixels != nullptr || en.jpeg != nullptr || dev, ow, oh, ch, ow == w ? stride : (size_t)ow * ch, en.new_width, en.new_height, message[i])) != L3D_OK) continue;
+        const int ow = remap ? k.warp.out_w : w, oh = remap ? k.warp.out_h : h;
+        if ((status[i] = plan_image(k.plan, has_image, ow, oh, ch, ow == w ? stride : (size_t)ow * ch, en.new_width, en.new_height, message[i])) != L3D_OK) continue;
         k.plan.sw = w; k.plan.sh = h;
-        bool undist = false;
-        if (en.cam && en.lens) { status[i] = L3D_ERR_INVALID; message[i] = "undistort: an image carries both distortion coefficients (k1, k2) and a lens"; continue; }
-        if (en.cam) { if ((status[i] = check_camera(*en.cam, w, h, &undist, message[i])) != L3D_OK) continue; }
-        if (en.lens) { k.lens = *en.lens; if ((status[i] = lens_check(k.lens, w, h, &k.lens_on, message[i])) != L3D_OK) continue; }
-        k.prm.cam = undist ? *en.cam : DetCamera{ 1.0, 1.0, 0.0, 0.0, 0.0, 0.0 };
-        k.prm.cam_on = undist; k.prm.min_length = en.min_length; k.prm.max_segments = en.max_segments; k.prm.pad = 0;
+        if (!remap && (status[i] = warp_check(en.warp, w, h, ch, k.warp, message[i])) != L3D_OK) continue;
+        const bool radial = k.warp.route == WarpRoute::Radial;
+        k.prm.cam = k.warp.cam;                 // (the identity camera unless the route is Radial)
+        k.prm.cam_on = radial; k.prm.min_length = en.min_length; k.prm.max_segments = en.max_segments; k.prm.pad = 0;
         k.todo = true;
     }
     HIPCHK(c, hipSetDevice(c->device));
@@ -1282,16 +1003,17 @@ int detect_segments_batch(l3d_ctx* c, const DetEntry* e, int n, std::vector<std:
     for (int first = 0; first < n && rc == L3D_OK; ++first) {
         if (!work[first].todo) continue;
         std::vector<int> group;
-        bool undist = false, valid = false;
+        WarpRoute route = WarpRoute::None;
+        bool valid = false;
         size_t blocks = 0;
         for (int i = first; i < n; ++i)
             if (work[i].todo && work[i].plan.same_group(work[first].plan)) {
                 group.push_back(i); work[i].todo = false;
-                undist = undist || work[i].prm.cam_on || work[i].lens_on || work[i].resample;
-                valid = valid || work[i].remap_on;
+                route = std::max(route, work[i].warp.route);
+                valid = valid || work[i].warp.plane;
                 if (work[i].file.f) blocks = std::max(blocks, work[i].file.f->n_blocks);
             }
-        const int per = chunk_images(c, work[first].plan, (int)group.size(), undist, blocks, valid);
+        const int per = chunk_images(c, work[first].plan, (int)group.size(), route, blocks, valid);
         for (size_t at = 0; at < group.size() && rc == L3D_OK; at += (size_t)per) {
             const size_t end = std::min(group.size(), at + (size_t)per);
             // the chunk's files: entropy decoding on the host threads, each into its own slice of the staging buffer; a file that fails leaves the chunk
@@ -1310,7 +1032,7 @@ int detect_segments_batch(l3d_ctx* c, const DetEntry* e, int n, std::vector<std:
                     if ((status[i] = device_image_pointer(c, *e[i].dev, message[i])) != L3D_OK) continue;
                     it.dev = e[i].dev;
                 }
-                it.pixels = k.file.f ? nullptr : e[i].pixels; it.stride = e[i].row_stride; it.jpeg = k.file.f ? &k.file : nullptr; it.prm = k.prm; it.lens_on = k.lens_on; it.lens = k.lens; it.remap_on = k.remap_on; it.resample = k.resample; it.remap = k.remap; it.out = &out[i];
+                it.pixels = k.file.f ? nullptr : e[i].pixels; it.stride = e[i].row_stride; it.jpeg = k.file.f ? &k.file : nullptr; it.prm = k.prm; it.warp = k.warp; it.out = &out[i];
                 items.push_back(it);
                 entry.push_back(i);
             }
@@ -1331,8 +1053,9 @@ int detect_segments_batch(l3d_ctx* c, const DetEntry* e, int n, std::vector<std:
 }
 
 // one image: a batch of one, its outcome the call's
-static int detect_one(l3d_ctx* c, const DetEntry& en, std::vector<float>& out)
+int detect_one(l3d_ctx* c, const DetEntry& en, std::vector<float>& out)
 {
+    out.clear();
     std::vector<std::vector<float>> outs;
     std::vector<int> status;
     std::vector<std::string> message;
@@ -1342,288 +1065,26 @@ static int detect_one(l3d_ctx* c, const DetEntry& en, std::vector<float>& out)
     return L3D_OK;
 }
 
-int detect_segments(l3d_ctx* c, const unsigned char* pixels, int w, int h, int ch, size_t stride, int nw, int nh, float min_length, int max_segments,
-                    std::vector<float>& out, const DetCamera* cam, const DetLens* lens)
-{
-    out.clear();
-    if (!c) return L3D_ERR_INVALID;
-    DetEntry en;
-    en.lens = lens;
-    en.pixels = pixels; en.width = w; en.height = h; en.channels = ch; en.row_stride = stride;
-    en.new_width = nw; en.new_height = nh; en.min_length = min_length; en.max_segments = max_segments; en.cam = cam;
-    return detect_one(c, en, out);
-}
-
-int detect_segments_jpeg(l3d_ctx* c, const unsigned char* bytes, size_t n, int nw, int nh, float min_length, int max_segments, std::vector<float>& out,
-                         const DetCamera* cam, const DetLens* lens)
-{
-    out.clear();
-    if (!c) return L3D_ERR_INVALID;
-    if (!bytes) return fail(c, L3D_ERR_INVALID, "detect_segments_jpeg: null argument");
-    DetEntry en;
-    en.lens = lens;
-    en.jpeg = bytes; en.jpeg_bytes = n;
-    en.new_width = nw; en.new_height = nh; en.min_length = min_length; en.max_segments = max_segments; en.cam = cam;
-    return detect_one(c, en, out);
-}
-
-int detect_segments_device(l3d_ctx* c, const l3d_device_image& image, int nw, int nh, float min_length, int max_segments, std::vector<float>& out, const DetCamera* cam,
-                           const DetLens* lens)
-{
-    out.clear();
-    if (!c) return L3D_ERR_INVALID;
-    DetEntry en;
-    en.lens = lens;
-    en.dev = &image;
-    en.new_width = nw; en.new_height = nh; en.min_length = min_length; en.max_segments = max_segments; en.cam = cam;
-    return detect_one(c, en, out);
-}
-
-// host in, host out: upload, k_det_undistort, download (the detector's two image buffers)
-int undistort_image(l3d_ctx* c, const unsigned char* pixels, int w, int h, int ch, size_t stride, const DetCamera& cam, unsigned char* out, size_t out_stride,
-                    const DetLens* lens)
-{
-    if (!c) return L3D_ERR_INVALID;
-    if (!pixels || !out || w < 1 || h < 1 || (ch != 1 && ch != 3) || stride < (size_t)w * ch || out_stride < (size_t)w * ch)
-        return fail(c, L3D_ERR_INVALID, "undistort: needs an image of at least 1x1 with 1 or 3 channels and row strides of at least width x channels");
-    if ((long long)w * h * ch > (1ll << 31)) return fail(c, L3D_ERR_UNSUPPORTED, "undistort: image too large");
-    bool active = false;
-    DetLens L{};
-    if (lens) L = *lens;
-    { std::string err; if (int rc = lens ? lens_check(L, w, h, &active, err) : check_camera(cam, w, h, &active, err)) return fail(c, rc, err); }
-    const size_t row = (size_t)w * ch;
-    if (!active) {
-        if (out != pixels || out_stride != stride)
-            for (int i = 0; i < h; ++i) memmove(out + (size_t)i * out_stride, pixels + (size_t)i * stride, row);
-        return L3D_OK;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    DetectBufs& d = c->det;
-    HIPCHK(c, d.pixels.reserve(row * h));
-    HIPCHK(c, d.undist.reserve(row * h));
-    HIPCHK(c, hipMemcpy2DAsync(d.pixels.p, row, pixels, stride, row, (size_t)h, hipMemcpyHostToDevice, c->stream));
-    if (lens) { if (int rc = launch_undistort_lens(c, w, h, ch, 1, &L)) return rc; }
-    else launch_undistort(c, w, h, ch, 1, cam, nullptr);
-    HIPCHK(c, hipMemcpy2DAsync(out, out_stride, d.undist.p, row, row, (size_t)h, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return L3D_OK;
-}
-
-// device in, device out (which may be the same memory): ingest, k_det_undistort, egress -- the ingest is complete before the egress starts
-int undistort_image_device(l3d_ctx* c, const l3d_device_image& in, const DetCamera& cam, const l3d_device_image& out, const DetLens* lens)
-{
-    std::string err;
-    if (int rc = device_image_check(in, err)) return fail(c, rc, err);
-    if (int rc = device_image_check(out, err)) return fail(c, rc, err);
-    const int w = in.width, h = in.height, ch = device_image_det_channels(in.channels);
-    if (out.width != w || out.height != h || device_image_det_channels(out.channels) != ch)
-        return fail(c, L3D_ERR_INVALID, "undistort: the output's size and channels must be the input's");
-    if ((long long)w * h * ch > (1ll << 31)) return fail(c, L3D_ERR_UNSUPPORTED, "undistort: image too large");
-    bool active = false;
-    DetLens L{};
-    if (lens) L = *lens;
-    if (int rc = lens ? lens_check(L, w, h, &active, err) : check_camera(cam, w, h, &active, err)) return fail(c, rc, err);
-    if (int rc = device_image_pointer(c, in, err)) return fail(c, rc, err);
-    if (int rc = device_image_pointer(c, out, err)) return fail(c, rc, err);
-    HIPCHK(c, hipSetDevice(c->device));
-    DetectBufs& d = c->det;
-    const size_t bytes = (size_t)w * ch * h;
-    HIPCHK(c, d.pixels.reserve(bytes));
-    if (active) HIPCHK(c, d.undist.reserve(bytes));
-    const l3d_device_image* one[1] = { &in };
-    if (int rc = device_ingest(c, one, 1, w, h, ch, d.pixels.as<unsigned char>())) return rc;
-    if (active && lens) { if (int rc = launch_undistort_lens(c, w, h, ch, 1, &L)) return rc; }
-    else if (active) launch_undistort(c, w, h, ch, 1, cam, nullptr);
-    if (int rc = device_egress(c, active ? d.undist.as<unsigned char>() : d.pixels.as<unsigned char>(), out)) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return L3D_OK;
-}
-
-DetLens make_lens(const l3d_lens& lens, double ofx, double ofy, double ocx, double ocy)
-{
-    DetLens l{};
-    l.model = lens.model;
-    l.fx = lens.fx; l.fy = lens.fy; l.cx = lens.cx; l.cy = lens.cy;
-    l.ofx = ofx; l.ofy = ofy; l.ocx = ocx; l.ocy = ocy;
-    for (int k = 0; k < 8; ++k) l.k[k] = lens.k[k];
-    return l;
-}
-
-int lens_check(DetLens& l, int w, int h, bool* active, std::string& err)
-{
-    *active = false;
-    if (w > (1 << 24) || h > (1 << 24)) { err = "undistort: image too large"; return L3D_ERR_UNSUPPORTED; }      // 32 x a coordinate stays an int
-    if (l.model != L3D_LENS_BROWN && l.model != L3D_LENS_FISHEYE) { err = "lens: unknown model " + std::to_string(l.model) + " (L3D_LENS_BROWN or L3D_LENS_FISHEYE)"; return L3D_ERR_INVALID; }
-    bool finite = std::isfinite(l.fx) && std::isfinite(l.fy) && std::isfinite(l.cx) && std::isfinite(l.cy);
-    for (int k = 0; k < 8; ++k) finite = finite && std::isfinite(l.k[k]);
-    if (!finite) { err = "lens: a field is not finite"; return L3D_ERR_INVALID; }
-    if ((l.fx == 0.0) != (l.fy == 0.0)) { err = "lens: exactly one of fx, fy is zero (both zero: the output camera)"; return L3D_ERR_INVALID; }
-    if (l.model == L3D_LENS_FISHEYE && (l.k[4] != 0.0 || l.k[5] != 0.0 || l.k[6] != 0.0 || l.k[7] != 0.0)) { err = "lens: a fisheye lens has four coefficients, k[4..7] must be 0"; return L3D_ERR_INVALID; }
-    if (!std::isfinite(l.ofx) || !std::isfinite(l.ofy) || !std::isfinite(l.ocx) || !std::isfinite(l.ocy) || l.ofx == 0.0 || l.ofy == 0.0) {
-        err = "undistort: fx and fy must be finite and not zero"; return L3D_ERR_INVALID;
-    }
-    if (l.fx == 0.0) { l.fx = l.ofx; l.fy = l.ofy; l.cx = l.ocx; l.cy = l.ocy; }
-    bool small = true;
-    for (int k = 0; k < 8; ++k) small = small && fabs(l.k[k]) <= kDistEps;
-    *active = l.model == L3D_LENS_FISHEYE || !small || l.fx != l.ofx || l.fy != l.ofy || l.cx != l.ocx || l.cy != l.ocy;
-    return L3D_OK;
-}
-
-// ---- a remap: checks, the mask's way to the device, the launch, and the two undistortion calls
-int remap_check(DetRemap& r, int w, int h, int ch, bool* active, std::string& err)
-{
-    *active = false;
-    if ((r.out_w == 0) != (r.out_h == 0) || r.out_w < 0 || r.out_h < 0) { err = "remap: the output size is (width, height), or (0, 0) for the source's"; return L3D_ERR_INVALID; }
-    if (r.out_w == 0) { r.out_w = w; r.out_h = h; }
-    if (r.out_w > (1 << 24) || r.out_h > (1 << 24) || (long long)r.out_w * r.out_h * ch > (1ll << 31)) { err = "remap: output image too large"; return L3D_ERR_UNSUPPORTED; }
-    if (r.mask && (r.mask_w != w || r.mask_h != h)) {
-        err = "remap: the mask is " + std::to_string(r.mask_w) + " x " + std::to_string(r.mask_h) + ", the source image " + std::to_string(w) + " x " + std::to_string(h);
-        return L3D_ERR_INVALID;
-    }
-    if (r.mask && r.mask_stride < (size_t)w) { err = "remap: the mask's row stride is below the source width"; return L3D_ERR_INVALID; }
-    const bool resized = r.out_w != w || r.out_h != h;
-    if (!r.has_lens) {
-        if (resized) { err = "remap: an output size that differs from the source's needs a lens (model 0: a pinhole camera) to resample with"; return L3D_ERR_INVALID; }
-        return L3D_OK;
-    }
-    if (r.lens.model == 0) { r.lens.model = L3D_LENS_BROWN; for (double& k : r.lens.k) k = 0.0; }       // a pinhole camera
-    if (int rc = lens_check(r.lens, w, h, active, err)) return rc;
-    *active = *active || resized;
-    return L3D_OK;
-}
-
-int undistort_image_remap(l3d_ctx* c, const unsigned char* pixels, int w, int h, int ch, size_t stride, const DetRemap& remap, unsigned char* out, size_t out_stride,
-                          unsigned char* valid, size_t valid_stride)
-{
-    if (!c) return L3D_ERR_INVALID;
-    if (!pixels || !out || w < 1 || h < 1 || (ch != 1 && ch != 3) || stride < (size_t)w * ch)
-        return fail(c, L3D_ERR_INVALID, "undistort: needs an image of at least 1x1 with 1 or 3 channels and row strides of at least width x channels");
-    if ((long long)w * h * ch > (1ll << 31)) return fail(c, L3D_ERR_UNSUPPORTED, "undistort: image too large");
-    DetRemap r = remap;
-    bool active = false;
-    { std::string err; if (int rc = remap_check(r, w, h, ch, &active, err)) return fail(c, rc, err); }
-    const int ow = r.out_w, oh = r.out_h;
-    if (out_stride < (size_t)ow * ch || (valid && valid_stride < (size_t)ow)) return fail(c, L3D_ERR_INVALID, "undistort: an output row stride is below the output width");
-    const size_t row = (size_t)w * ch, orow = (size_t)ow * ch;
-    if (!active && (out != pixels || out_stride != stride))      // nothing is resampled: the pixels pass through
-        for (int i = 0; i < h; ++i) memmove(out + (size_t)i * out_stride, pixels + (size_t)i * stride, row);
-    if (!active && !valid) return L3D_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    DetectBufs& d = c->det;
-    HIPCHK(c, d.valid.reserve((size_t)ow * oh));
-    if (r.mask) {
-        HIPCHK(c, d.smask.reserve((size_t)w * h));
-        if (int rc = remap_mask_upload(c, r, w, h, 0)) return rc;
-    }
-    if (active) {
-        const int flags = (r.mask ? kRemapMask : 0) | (r.border_mask ? kRemapBorder : 0);
-        HIPCHK(c, d.pixels.reserve(row * h));
-        HIPCHK(c, hipMemcpy2DAsync(d.pixels.p, row, pixels, stride, row, (size_t)h, hipMemcpyHostToDevice, c->stream));
-        if (int rc = launch_undistort_remap(c, w, h, ch, ow, oh, 1, &r.lens, &flags)) return rc;
-        HIPCHK(c, hipMemcpy2DAsync(out, out_stride, d.undist.p, orow, orow, (size_t)oh, hipMemcpyDeviceToHost, c->stream));
-    } else if (int rc = plane_without_resample(c, r.mask != nullptr, (size_t)w * h, 0)) return rc;      // the mask is the plane
-    if (valid) HIPCHK(c, hipMemcpy2DAsync(valid, valid_stride, d.valid.p, (size_t)ow, (size_t)ow, (size_t)oh, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return L3D_OK;
-}
-
-int undistort_image_device_remap(l3d_ctx* c, const l3d_device_image& in, const DetRemap& remap, const l3d_device_image& out, const l3d_device_image* valid)
-{
-    std::string err;
-    if (int rc = device_image_check(in, err)) return fail(c, rc, err);
-    if (int rc = device_image_check(out, err)) return fail(c, rc, err);
-    if (valid) { if (int rc = device_image_check(*valid, err)) return fail(c, rc, err); }
-    const int w = in.width, h = in.height, ch = device_image_det_channels(in.channels);
-    if ((long long)w * h * ch > (1ll << 31)) return fail(c, L3D_ERR_UNSUPPORTED, "undistort: image too large");
-    DetRemap r = remap;
-    bool active = false;
-    if (int rc = remap_check(r, w, h, ch, &active, err)) return fail(c, rc, err);
-    const int ow = r.out_w, oh = r.out_h;
-    if (out.width != ow || out.height != oh || device_image_det_channels(out.channels) != ch)
-        return fail(c, L3D_ERR_INVALID, "undistort: the output's size must be the remap's output size and its channels the input's");
-    if (valid && (valid->width != ow || valid->height != oh || valid->channels != 1 || valid->dtype != L3D_U8))
-        return fail(c, L3D_ERR_INVALID, "undistort: the validity plane is a one-channel L3D_U8 image of the output size");
-    if (int rc = device_image_pointer(c, in, err)) return fail(c, rc, err);
-    if (int rc = device_image_pointer(c, out, err)) return fail(c, rc, err);
-    if (valid) { if (int rc = device_image_pointer(c, *valid, err)) return fail(c, rc, err); }
-    HIPCHK(c, hipSetDevice(c->device));
-    DetectBufs& d = c->det;
-    HIPCHK(c, d.pixels.reserve((size_t)w * ch * h));
-    HIPCHK(c, d.valid.reserve((size_t)ow * oh));
-    if (r.mask) {
-        HIPCHK(c, d.smask.reserve((size_t)w * h));
-        if (int rc = remap_mask_upload(c, r, w, h, 0)) return rc;
-    }
-    const l3d_device_image* one[1] = { &in };
-    if (int rc = device_ingest(c, one, 1, w, h, ch, d.pixels.as<unsigned char>())) return rc;
-    if (active) {
-        const int flags = (r.mask ? kRemapMask : 0) | (r.border_mask ? kRemapBorder : 0);
-        if (int rc = launch_undistort_remap(c, w, h, ch, ow, oh, 1, &r.lens, &flags)) return rc;
-    } else if (valid) { if (int rc = plane_without_resample(c, r.mask != nullptr, (size_t)w * h, 0)) return rc; }
-    if (int rc = device_egress(c, active ? d.undist.as<unsigned char>() : d.pixels.as<unsigned char>(), out)) return rc;
-    if (valid) { if (int rc = device_egress(c, d.valid.as<unsigned char>(), *valid)) return rc; }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return L3D_OK;
-}
-
 }  // namespace l3d
 
-// an l3d_remap and the output camera as the detector's DetRemap
-static l3d::DetRemap remap_of(const l3d_remap& m, double fx, double fy, double cx, double cy)
+// ---- the C calls.  An entry of either kind as the detector's (its warp: warp_of_entry on its camera and the lens or remap that comes beside it)
+static l3d::DetEntry det_entry(const l3d_detect_entry& e)
 {
-    l3d::DetRemap r;
-    r.has_lens = m.lens != nullptr;
-    if (m.lens) r.lens = l3d::make_lens(*m.lens, fx, fy, cx, cy);
-    r.out_w = m.out_width; r.out_h = m.out_height;
-    r.mask = m.mask; r.mask_stride = m.mask_row_stride; r.mask_w = m.mask_width; r.mask_h = m.mask_height; r.mask_on_device = m.mask_on_device != 0; r.border_mask = m.border_mask != 0;
-    return r;
+    l3d::DetEntry d;
+    d.pixels = e.pixels; d.width = e.width; d.height = e.height; d.channels = e.channels; d.row_stride = e.row_stride;
+    d.jpeg = e.jpeg; d.jpeg_bytes = e.jpeg_bytes;
+    d.new_width = e.new_width; d.new_height = e.new_height; d.min_length = e.min_length; d.max_segments = e.max_segments;
+    return d;
 }
-
-int l3d_undistort_image_remap(l3d_ctx* c, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, double fx, double fy, double cx, double cy,
-                              const l3d_remap* remap, unsigned char* out, size_t out_row_stride, unsigned char* valid, size_t valid_row_stride)
+static l3d::DetEntry det_entry(const l3d_detect_device_entry& e)
 {
-    if (!c) return L3D_ERR_INVALID;
-    if (!remap) return l3d::fail(c, L3D_ERR_INVALID, "undistort: null argument");
-    return l3d::undistort_image_remap(c, pixels, width, height, channels, row_stride, remap_of(*remap, fx, fy, cx, cy), out, out_row_stride, valid, valid_row_stride);
+    l3d::DetEntry d;
+    d.dev = &e.image;
+    d.new_width = e.new_width; d.new_height = e.new_height; d.min_length = e.min_length; d.max_segments = e.max_segments;
+    return d;
 }
-
-int l3d_undistort_image_device_remap(l3d_ctx* c, const l3d_device_image* in, double fx, double fy, double cx, double cy, const l3d_remap* remap, const l3d_device_image* out,
-                                     const l3d_device_image* valid)
-{
-    if (!c) return L3D_ERR_INVALID;
-    if (!in || !out || !remap) return l3d::fail(c, L3D_ERR_INVALID, "undistort: null argument");
-    return l3d::undistort_image_device_remap(c, *in, remap_of(*remap, fx, fy, cx, cy), *out, valid);
-}
-
-int l3d_undistort_image_device(l3d_ctx* c, const l3d_device_image* in, double fx, double fy, double cx, double cy, double k1, double k2, const l3d_device_image* out)
-{
-    if (!c) return L3D_ERR_INVALID;
-    if (!in || !out) return l3d::fail(c, L3D_ERR_INVALID, "undistort: null argument");
-    return l3d::undistort_image_device(c, *in, l3d::DetCamera{ fx, fy, cx, cy, k1, k2 }, *out);
-}
-
-int l3d_undistort_image_device_lens(l3d_ctx* c, const l3d_device_image* in, double fx, double fy, double cx, double cy, const l3d_lens* lens, const l3d_device_image* out)
-{
-    if (!c) return L3D_ERR_INVALID;
-    if (!in || !out || !lens) return l3d::fail(c, L3D_ERR_INVALID, "undistort: null argument");
-    const l3d::DetLens l = l3d::make_lens(*lens, fx, fy, cx, cy);
-    return l3d::undistort_image_device(c, *in, l3d::DetCamera{ fx, fy, cx, cy, 0.0, 0.0 }, *out, &l);
-}
-
-int l3d_undistort_image_lens(l3d_ctx* c, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, double fx, double fy, double cx, double cy,
-                             const l3d_lens* lens, unsigned char* out, size_t out_row_stride)
-{
-    if (!c) return L3D_ERR_INVALID;
-    if (!lens) return l3d::fail(c, L3D_ERR_INVALID, "undistort: null argument");
-    const l3d::DetLens l = l3d::make_lens(*lens, fx, fy, cx, cy);
-    return l3d::undistort_image(c, pixels, width, height, channels, row_stride, l3d::DetCamera{ fx, fy, cx, cy, 0.0, 0.0 }, out, out_row_stride, &l);
-}
-
-int l3d_undistort_image(l3d_ctx* c, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, double fx, double fy, double cx, double cy,
-                        double k1, double k2, unsigned char* out, size_t out_row_stride)
-{
-    return l3d::undistort_image(c, pixels, width, height, channels, row_stride, l3d::DetCamera{ fx, fy, cx, cy, k1, k2 }, out, out_row_stride);
-}
+static l3d::DetWarp entry_warp(const double* camera, const l3d_lens* lens) { return l3d::warp_of_entry(camera, lens, nullptr); }
+static l3d::DetWarp entry_warp(const double* camera, const l3d_remap* remap) { return l3d::warp_of_entry(camera, nullptr, remap); }
 
 // the segments as the C ABI hands them out: callee-allocated (l3d_free), 4 floats each
 static int segments_to_c(l3d_ctx* c, const std::vector<float>& out, float** segments, int* n)
@@ -1636,172 +1097,50 @@ static int segments_to_c(l3d_ctx* c, const std::vector<float>& out, float** segm
     return L3D_OK;
 }
 
-static int detect_to_c(l3d_ctx* c, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, int new_width, int new_height,
-                       float min_length, int max_segments, const l3d::DetCamera* cam, float** segments, int* n)
+// one entry (null: the message names the missing argument) through the detector
+template <class E>
+static int one_to_c(l3d_ctx* c, const E& e, const char* missing, float** segments, int* n)
 {
     if (!c || !segments || !n) return L3D_ERR_INVALID;
     *segments = nullptr;
     *n = 0;
+    if (missing) return l3d::fail(c, L3D_ERR_INVALID, missing);
+    l3d::DetEntry d = det_entry(e);
+    d.warp = entry_warp(e.camera, (const l3d_lens*)nullptr);
     std::vector<float> out;
-    const int rc = l3d::detect_segments(c, pixels, width, height, channels, row_stride, new_width, new_height, min_length, max_segments, out, cam);
+    const int rc = l3d::detect_one(c, d, out);
     return rc != L3D_OK ? rc : segments_to_c(c, out, segments, n);
 }
 
 int l3d_detect_segments_distorted(l3d_ctx* c, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, int new_width, int new_height,
                                   float min_length, int max_segments, double fx, double fy, double cx, double cy, double k1, double k2, float** segments, int* n)
 {
-    const l3d::DetCamera cam{ fx, fy, cx, cy, k1, k2 };
-    return detect_to_c(c, pixels, width, height, channels, row_stride, new_width, new_height, min_length, max_segments, &cam, segments, n);
+    const double cam[6] = { fx, fy, cx, cy, k1, k2 };
+    const l3d_detect_entry e{ pixels, width, height, channels, row_stride, nullptr, 0, new_width, new_height, min_length, max_segments, cam };
+    return one_to_c(c, e, nullptr, segments, n);
 }
 
 int l3d_detect_segments(l3d_ctx* c, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, int new_width, int new_height,
                         float min_length, int max_segments, float** segments, int* n)
 {
-    return detect_to_c(c, pixels, width, height, channels, row_stride, new_width, new_height, min_length, max_segments, nullptr, segments, n);
+    const l3d_detect_entry e{ pixels, width, height, channels, row_stride, nullptr, 0, new_width, new_height, min_length, max_segments, nullptr };
+    return one_to_c(c, e, nullptr, segments, n);
 }
 
 int l3d_detect_segments_jpeg(l3d_ctx* c, const unsigned char* bytes, size_t n, int new_width, int new_height, float min_length, int max_segments,
                              const double* camera, float** segments, int* n_segments)
 {
-    if (!c || !segments || !n_segments) return L3D_ERR_INVALID;
-    *segments = nullptr;
-    *n_segments = 0;
-    l3d::DetCamera cam{ 1.0, 1.0, 0.0, 0.0, 0.0, 0.0 };
-    if (camera) cam = l3d::DetCamera{ camera[0], camera[1], camera[2], camera[3], camera[4], camera[5] };
-    std::vector<float> out;
-    const int rc = l3d::detect_segments_jpeg(c, bytes, n, new_width, new_height, min_length, max_segments, out, camera ? &cam : nullptr);
-    return rc != L3D_OK ? rc : segments_to_c(c, out, segments, n_segments);
-}
-
-static int batch_to_c(l3d_ctx* c, const std::vector<l3d::DetEntry>& entries, float** segments, int* offsets, int* status);
-
-// the camera and the lens of a batch entry: `camera` alone is the k1, k2 camera; with a lens it is the output camera, and coefficients beside the lens
-// leave both set, which the batch refuses for that entry ("both ... and a lens"); a lens without a camera has no output camera: fx' = fy' = 0, refused as well
-static void entry_camera(const double* k, const l3d_lens* lens, l3d::DetCamera& cam, l3d::DetLens& dl, l3d::DetEntry& d)
-{
-    if (k) cam = l3d::DetCamera{ k[0], k[1], k[2], k[3], k[4], k[5] };
-    if (!lens) { if (k) d.cam = &cam; return; }
-    if (!k) { dl = l3d::make_lens(*lens, 0.0, 0.0, 0.0, 0.0); d.lens = &dl; return; }
-    dl = l3d::make_lens(*lens, k[0], k[1], k[2], k[3]);
-    d.lens = &dl;
-    if (k[4] != 0.0 || k[5] != 0.0) d.cam = &cam;
-}
-
-int l3d_detect_segments_batch_lens(l3d_ctx* c, const l3d_detect_entry* e, const l3d_lens* const* lens, int n, float** segments, int* offsets, int* status)
-{
-    if (!c || !segments || !offsets || !status || n < 0 || (n > 0 && !e)) return L3D_ERR_INVALID;
-    *segments = nullptr;
-    std::vector<l3d::DetEntry> entries((size_t)n);
-    std::vector<l3d::DetCamera> cams((size_t)n);
-    std::vector<l3d::DetLens> lenses((size_t)n);
-    for (int i = 0; i < n; ++i) {
-        l3d::DetEntry& d = entries[i];
-        d.pixels = e[i].pixels; d.width = e[i].width; d.height = e[i].height; d.channels = e[i].channels; d.row_stride = e[i].row_stride;
-        d.jpeg = e[i].jpeg; d.jpeg_bytes = e[i].jpeg_bytes;
-        d.new_width = e[i].new_width; d.new_height = e[i].new_height; d.min_length = e[i].min_length; d.max_segments = e[i].max_segments;
-        entry_camera(e[i].camera, lens ? lens[i] : nullptr, cams[i], lenses[i], d);
-    }
-    return batch_to_c(c, entries, segments, offsets, status);
-}
-// a batch entry with a remap: the entry's camera is the output camera (coefficients beside it leave cam set, which the batch refuses for that entry)
-static void entry_remap(const double* k, const l3d_remap& m, l3d::DetCamera& cam, l3d::DetRemap& r, l3d::DetEntry& d)
-{
-    r = k ? remap_of(m, k[0], k[1], k[2], k[3]) : remap_of(m, 0.0, 0.0, 0.0, 0.0);
-    d.remap = &r;
-    if (k && (k[4] != 0.0 || k[5] != 0.0)) { cam = l3d::DetCamera{ k[0], k[1], k[2], k[3], k[4], k[5] }; d.cam = &cam; }
-}
-
-int l3d_detect_segments_batch_remap(l3d_ctx* c, const l3d_detect_entry* e, const l3d_remap* const* remap, int n, float** segments, int* offsets, int* status)
-{
-    if (!c || !segments || !offsets || !status || n < 0 || (n > 0 && !e)) return L3D_ERR_INVALID;
-    *segments = nullptr;
-    std::vector<l3d::DetEntry> entries((size_t)n);
-    std::vector<l3d::DetCamera> cams((size_t)n);
-    std::vector<l3d::DetLens> lenses((size_t)n);
-    std::vector<l3d::DetRemap> remaps((size_t)n);
-    for (int i = 0; i < n; ++i) {
-        l3d::DetEntry& d = entries[i];
-        d.pixels = e[i].pixels; d.width = e[i].width; d.height = e[i].height; d.channels = e[i].channels; d.row_stride = e[i].row_stride;
-        d.jpeg = e[i].jpeg; d.jpeg_bytes = e[i].jpeg_bytes;
-        d.new_width = e[i].new_width; d.new_height = e[i].new_height; d.min_length = e[i].min_length; d.max_segments = e[i].max_segments;
-        if (remap && remap[i]) entry_remap(e[i].camera, *remap[i], cams[i], remaps[i], d);
-        else entry_camera(e[i].camera, nullptr, cams[i], lenses[i], d);
-    }
-    return batch_to_c(c, entries, segments, offsets, status);
-}
-
-int l3d_detect_segments_device_batch_remap(l3d_ctx* c, const l3d_detect_device_entry* e, const l3d_remap* const* remap, int n, float** segments, int* offsets, int* status)
-{
-    if (!c || !segments || !offsets || !status || n < 0 || (n > 0 && !e)) return L3D_ERR_INVALID;
-    *segments = nullptr;
-    std::vector<l3d::DetEntry> entries((size_t)n);
-    std::vector<l3d::DetCamera> cams((size_t)n);
-    std::vector<l3d::DetLens> lenses((size_t)n);
-    std::vector<l3d::DetRemap> remaps((size_t)n);
-    for (int i = 0; i < n; ++i) {
-        l3d::DetEntry& d = entries[i];
-        d.dev = &e[i].image;
-        d.new_width = e[i].new_width; d.new_height = e[i].new_height; d.min_length = e[i].min_length; d.max_segments = e[i].max_segments;
-        if (remap && remap[i]) entry_remap(e[i].camera, *remap[i], cams[i], remaps[i], d);
-        else entry_camera(e[i].camera, nullptr, cams[i], lenses[i], d);
-    }
-    return batch_to_c(c, entries, segments, offsets, status);
-}
-
-// (tests) the defined / undefined plane, N x M bytes (255 / 0), that the LAST detector call of this context left for the first image of its last chunk;
-// 0 x 0 when that chunk carried no validity plane
-int l3d_test_detect_defined_plane(l3d_ctx* c, unsigned char* defined, size_t capacity, int* N, int* M)
-{
-    using namespace l3d;
-    if (!c || !N || !M) return L3D_ERR_INVALID;
-    DetectBufs& d = c->det;
-    *N = d.vdef_n; *M = d.vdef_m;
-    const size_t n = (size_t)d.vdef_n * d.vdef_m;
-    if (n == 0 || !defined) return L3D_OK;          // (defined NULL: the size alone)
-    if (capacity < n) return fail(c, L3D_ERR_INVALID, "test_detect_defined_plane: the buffer is too small");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(defined, d.vdef.p, n, hipMemcpyDeviceToHost));
-    return L3D_OK;
-}
-
-int l3d_detect_segments_batch(l3d_ctx* c, const l3d_detect_entry* e, int n, float** segments, int* offsets, int* status)
-{
-    return l3d_detect_segments_batch_lens(c, e, nullptr, n, segments, offsets, status);
+    const l3d_detect_entry e{ nullptr, 0, 0, 0, 0, bytes, n, new_width, new_height, min_length, max_segments, camera };
+    return one_to_c(c, e, bytes ? nullptr : "detect_segments_jpeg: null argument", segments, n_segments);
 }
 
 int l3d_detect_segments_device(l3d_ctx* c, const l3d_device_image* image, int new_width, int new_height, float min_length, int max_segments, const double* camera,
                                float** segments, int* n)
 {
-    if (!c || !segments || !n) return L3D_ERR_INVALID;
-    *segments = nullptr;
-    *n = 0;
-    if (!image) return l3d::fail(c, L3D_ERR_INVALID, "detect_segments: null argument");
-    l3d::DetCamera cam{ 1.0, 1.0, 0.0, 0.0, 0.0, 0.0 };
-    if (camera) cam = l3d::DetCamera{ camera[0], camera[1], camera[2], camera[3], camera[4], camera[5] };
-    std::vector<float> out;
-    const int rc = l3d::detect_segments_device(c, *image, new_width, new_height, min_length, max_segments, out, camera ? &cam : nullptr);
-    return rc != L3D_OK ? rc : segments_to_c(c, out, segments, n);
-}
-
-int l3d_detect_segments_device_batch_lens(l3d_ctx* c, const l3d_detect_device_entry* e, const l3d_lens* const* lens, int n, float** segments, int* offsets, int* status)
-{
-    if (!c || !segments || !offsets || !status || n < 0 || (n > 0 && !e)) return L3D_ERR_INVALID;
-    *segments = nullptr;
-    std::vector<l3d::DetEntry> entries((size_t)n);
-    std::vector<l3d::DetCamera> cams((size_t)n);
-    std::vector<l3d::DetLens> lenses((size_t)n);
-    for (int i = 0; i < n; ++i) {
-        l3d::DetEntry& d = entries[i];
-        d.dev = &e[i].image;
-        d.new_width = e[i].new_width; d.new_height = e[i].new_height; d.min_length = e[i].min_length; d.max_segments = e[i].max_segments;
-        entry_camera(e[i].camera, lens ? lens[i] : nullptr, cams[i], lenses[i], d);
-    }
-    return batch_to_c(c, entries, segments, offsets, status);
-}
-int l3d_detect_segments_device_batch(l3d_ctx* c, const l3d_detect_device_entry* e, int n, float** segments, int* offsets, int* status)
-{
-    return l3d_detect_segments_device_batch_lens(c, e, nullptr, n, segments, offsets, status);
+    l3d_detect_device_entry e{};
+    if (image) e.image = *image;
+    e.new_width = new_width; e.new_height = new_height; e.min_length = min_length; e.max_segments = max_segments; e.camera = camera;
+    return one_to_c(c, e, image ? nullptr : "detect_segments: null argument", segments, n);
 }
 
 // the batch detector's outcome as the C ABI hands it out: the segments of all entries one after the other, one line per failed entry
@@ -1825,6 +1164,62 @@ static int batch_to_c(l3d_ctx* c, const std::vector<l3d::DetEntry>& entries, flo
     int total = 0;
     const int rc2 = segments_to_c(c, all, segments, &total);
     return rc != L3D_OK ? rc : rc2;
+}
+
+// n entries of either kind, each with the lens or the remap of `with` (the array or an element may be null: the entry's own camera rule)
+template <class E, class X>
+static int entries_to_c(l3d_ctx* c, const E* e, const X* const* with, int n, float** segments, int* offsets, int* status)
+{
+    if (!c || !segments || !offsets || !status || n < 0 || (n > 0 && !e)) return L3D_ERR_INVALID;
+    *segments = nullptr;
+    std::vector<l3d::DetEntry> entries((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        entries[i] = det_entry(e[i]);
+        entries[i].warp = entry_warp(e[i].camera, with ? with[i] : nullptr);
+    }
+    return batch_to_c(c, entries, segments, offsets, status);
+}
+
+int l3d_detect_segments_batch_lens(l3d_ctx* c, const l3d_detect_entry* e, const l3d_lens* const* lens, int n, float** segments, int* offsets, int* status)
+{
+    return entries_to_c(c, e, lens, n, segments, offsets, status);
+}
+int l3d_detect_segments_batch_remap(l3d_ctx* c, const l3d_detect_entry* e, const l3d_remap* const* remap, int n, float** segments, int* offsets, int* status)
+{
+    return entries_to_c(c, e, remap, n, segments, offsets, status);
+}
+int l3d_detect_segments_batch(l3d_ctx* c, const l3d_detect_entry* e, int n, float** segments, int* offsets, int* status)
+{
+    return l3d_detect_segments_batch_lens(c, e, nullptr, n, segments, offsets, status);
+}
+int l3d_detect_segments_device_batch_lens(l3d_ctx* c, const l3d_detect_device_entry* e, const l3d_lens* const* lens, int n, float** segments, int* offsets, int* status)
+{
+    return entries_to_c(c, e, lens, n, segments, offsets, status);
+}
+int l3d_detect_segments_device_batch_remap(l3d_ctx* c, const l3d_detect_device_entry* e, const l3d_remap* const* remap, int n, float** segments, int* offsets, int* status)
+{
+    return entries_to_c(c, e, remap, n, segments, offsets, status);
+}
+int l3d_detect_segments_device_batch(l3d_ctx* c, const l3d_detect_device_entry* e, int n, float** segments, int* offsets, int* status)
+{
+    return l3d_detect_segments_device_batch_lens(c, e, nullptr, n, segments, offsets, status);
+}
+
+// (tests) the defined / undefined plane, N x M bytes (255 / 0), that the LAST detector call of this context left for the first image of its last chunk;
+// 0 x 0 when that chunk carried no validity plane
+int l3d_test_detect_defined_plane(l3d_ctx* c, unsigned char* defined, size_t capacity, int* N, int* M)
+{
+    using namespace l3d;
+    if (!c || !N || !M) return L3D_ERR_INVALID;
+    DetectBufs& d = c->det;
+    *N = d.vdef_n; *M = d.vdef_m;
+    const size_t n = (size_t)d.vdef_n * d.vdef_m;
+    if (n == 0 || !defined) return L3D_OK;          // (defined NULL: the size alone)
+    if (capacity < n) return fail(c, L3D_ERR_INVALID, "test_detect_defined_plane: the buffer is too small");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(defined, d.vdef.p, n, hipMemcpyDeviceToHost));
+    return L3D_OK;
 }
 
 // ---- the stages on their own, for the tests: the functions above (the same kernels and launch shapes as l3d_detect_segments), results copied out

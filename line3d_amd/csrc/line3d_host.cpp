@@ -677,6 +677,14 @@ int l3d_line3d_reset(l3d_line3d* h)
 // That is the behaviour the forms had one by one (tests/golden/add_table.json records it); moving the cheap guards to the front changes it.
 namespace l3dh {
 enum class AddKind { Segments, Cached, Pixels, Jpeg, Device };
+// the undistortion a request asks for beside its entry's dist; more than one of dist, lens and remap is refused (warp_for_add)
+struct AddWarp {
+    bool dist_required = false;                     // the _distorted forms: a null dist is refused (elsewhere it means no distortion)
+    const l3d_lens* lens = nullptr;                 // the ..._lens forms: a lens in the place of dist
+    const l3d_remap* remap = nullptr;               // the ..._remap forms ("A REMAP"): in the place of dist and lens; K is the output camera
+    bool identity_camera = false;                   // the undistort calls: dist within L3D_EPS goes on as the identity camera, so that the context's
+                                                    // call still makes its checks of the image before it passes the pixels through
+};
 // an l3d_image_entry, or in place of its image the caller's segments or an opened segment cache
 struct AddRequest {
     AddKind kind = AddKind::Segments;
@@ -685,9 +693,7 @@ struct AddRequest {
     const l3d_segment_cache* cache = nullptr;       // Cached
     const l3d_device_image* dev = nullptr;          // Device: the image in device memory (e carries its size and the detector's channel count)
     bool cache_rules = false;                       // the form has a data directory: every one but add_image, add_image_fixed_sim, add_image_cached
-    bool dist_required = false;                     // the _distorted forms: a null dist is refused (elsewhere it means no distortion)
-    const l3d_lens* lens = nullptr;                 // the ..._lens forms: a lens in the place of dist (both: refused)
-    const l3d_remap* remap = nullptr;               // the ..._remap forms ("A REMAP"): in the place of dist and lens; K is the output camera
+    AddWarp warp;                                   // what the form asks for beside e.dist
     bool image() const { return kind == AddKind::Pixels || kind == AddKind::Jpeg || kind == AddKind::Device; }
 };
 enum class Cache { None, Load, Stale, Write };      // no cache rules or nothing to do | read the file | remove the file | note the file for prepare()
@@ -695,12 +701,7 @@ enum class Cache { None, Load, Stale, Write };      // no cache rules or nothing
 struct AddPlan {
     unsigned width = 0, height = 0;                 // of the view (a JPEG file: from its headers)
     int channels = 0;
-    bool undistort = false;
-    l3d::DetCamera cam;
-    bool lens_on = false;                           // an active lens (then undistort is false): resampled from the lens's camera onto K
-    l3d::DetLens lens;
-    bool remap_on = false;                          // a remap: width x height above are its OUTPUT (the view's size, the cache file's name)
-    l3d::DetRemap remap;
+    l3d::DetWarp warp;                              // as the detector takes it, which checks it (warp_for_add); a remap: width x height above are its OUTPUT
     unsigned src_w = 0, src_h = 0;                  // the image as it arrives
     Cache cache = Cache::None;
     std::string file;                               // the cache file's path
@@ -724,7 +725,7 @@ static AddRequest pixels_request(uint32_t id, const unsigned char* pixels, int w
 {
     AddRequest rq = add_request(AddKind::Pixels, id, (unsigned)width, (unsigned)height, K, R, t, link_ids, sims, n_links);
     rq.e.pixels = pixels; rq.e.channels = channels; rq.e.row_stride = row_stride;
-    rq.e.dist = dist; rq.dist_required = dist_required;
+    rq.e.dist = dist; rq.warp.dist_required = dist_required;
     return rq;
 }
 static AddRequest jpeg_request(uint32_t id, const unsigned char* bytes, size_t n, const double* K, const double* R, const double* t, const double* dist,
@@ -786,47 +787,36 @@ static int cache_decision(L* h, uint32_t id, unsigned width, unsigned height, co
     return L3D_OK;
 }
 
-// the camera of the undistortion: fx, fy, cx, cy from the full-resolution K, as in the drivers (main_vsfm.cpp:250-262).  Returns 1 with
-// `cam` filled, 0 when both coefficients are within L3D_EPS (the plain path), < 0: error negated
-static int camera_for_add(l3d_line3d* h, const double* K, const double* dist, l3d::DetCamera& cam)
+// the warp of an image in the add family.  K is the camera of the undistortion -- fx, fy, cx, cy = K[0], K[4], K[2], K[5] of the full-resolution K, as
+// in the drivers (main_vsfm.cpp:250-262) -- and beside a lens or a remap the OUTPUT camera.  L3D_OK with `out` as the detector takes it (dist within
+// L3D_EPS: nothing given, the plain path -- or, where the request says so, the identity camera) and out_w x out_h the size of the view, or the
+// refusal's code with the message in h->err: what warp_check refuses for a lens or a remap, and a skewed K where the image is resampled.  (The
+// fields of a k1, k2 camera are checked where the detector runs, behind the cache decision: a cache that stands in for the image leaves them unread)
+static int warp_for_add(l3d_line3d* h, const double* K, const double* dist, const AddWarp& rq, int width, int height, int channels, l3d::DetWarp& out, int& out_w, int& out_h)
 {
-    if (!K) return -h->fail(L3D_ERR_INVALID, "undistortion: K is null");
-    if (!dist) return -h->fail(L3D_ERR_INVALID, "undistortion: dist (k1, k2) is null");
-    if (std::fabs(dist[0]) <= 1e-12 && std::fabs(dist[1]) <= 1e-12) return 0;
-    if (K[1] != 0.0) return -h->fail(L3D_ERR_UNSUPPORTED, "lens distortion with a skewed K (K[1] != 0) is not supported");
-    cam = l3d::DetCamera{ K[0], K[4], K[2], K[5], dist[0], dist[1] };
-    return 1;
-}
-// the same for a lens: K is the output camera.  Returns 1 with `out` filled and checked, 0 when the lens passes the pixels through, < 0: error negated
-static int lens_for_add(l3d_line3d* h, const double* K, const double* dist, const l3d_lens* lens, int width, int height, l3d::DetLens& out)
-{
-    if (dist) return -h->fail(L3D_ERR_INVALID, "undistortion: an entry carries both dist (k1, k2) and a lens");
-    if (!K) return -h->fail(L3D_ERR_INVALID, "undistortion: K is null");
-    out = l3d::make_lens(*lens, K[0], K[4], K[2], K[5]);
-    bool active = false;
+    const char* skewed = "lens distortion with a skewed K (K[1] != 0) is not supported";
+    out = l3d::DetWarp();
+    out_w = width; out_h = height;
+    if (rq.remap && (rq.lens || dist)) return h->fail(L3D_ERR_INVALID, "undistortion: an entry carries a remap beside dist (k1, k2) or a lens");
+    if (rq.lens && dist) return h->fail(L3D_ERR_INVALID, "undistortion: an entry carries both dist (k1, k2) and a lens");
+    if (!rq.remap && !rq.lens && !dist && !rq.dist_required) return L3D_OK;
+    if (!K) return h->fail(L3D_ERR_INVALID, "undistortion: K is null");
+    if (!rq.remap && !rq.lens) {
+        if (!dist) return h->fail(L3D_ERR_INVALID, "undistortion: dist (k1, k2) is null");
+        if (std::fabs(dist[0]) <= 1e-12 && std::fabs(dist[1]) <= 1e-12) { out.has_cam = rq.identity_camera; return L3D_OK; }
+        if (K[1] != 0.0) return h->fail(L3D_ERR_UNSUPPORTED, skewed);
+        out.has_cam = true;
+        out.cam = l3d::DetCamera{ K[0], K[4], K[2], K[5], dist[0], dist[1] };
+        return L3D_OK;
+    }
+    if (rq.remap && (width <= 0 || height <= 0)) return h->fail(L3D_ERR_INVALID, "image is empty!");
+    const double camera[6] = { K[0], K[4], K[2], K[5], 0.0, 0.0 };
+    out = l3d::warp_of_entry(camera, rq.lens, rq.remap);
+    l3d::WarpPlan plan;
     std::string err;
-    if (const int rc = l3d::lens_check(out, width, height, &active, err)) return -h->fail(rc, err.c_str());
-    if (!active) return 0;
-    if (K[1] != 0.0) return -h->fail(L3D_ERR_UNSUPPORTED, "lens distortion with a skewed K (K[1] != 0) is not supported");
-    return 1;
-}
-
-// the same for a remap: K is the output camera.  L3D_OK with `out` filled as the detector takes it (it checks its own copy again) and the output size,
-// or the refusal's code: what remap_check refuses, and a skewed K where the remap resamples
-static int remap_for_add(l3d_line3d* h, const double* K, const l3d_remap& m, int width, int height, int channels, l3d::DetRemap& out, int& out_w, int& out_h)
-{
-    out = l3d::DetRemap();
-    out.has_lens = m.lens != nullptr;
-    if (out.has_lens) out.lens = l3d::make_lens(*m.lens, K[0], K[4], K[2], K[5]);
-    out.out_w = m.out_width; out.out_h = m.out_height;
-    out.mask = m.mask; out.mask_stride = m.mask_row_stride; out.mask_w = m.mask_width; out.mask_h = m.mask_height;
-    out.mask_on_device = m.mask_on_device != 0; out.border_mask = m.border_mask != 0;
-    l3d::DetRemap checked = out;
-    bool active = false;
-    std::string err;
-    if (const int rc = l3d::remap_check(checked, width, height, channels, &active, err)) return h->fail(rc, err.c_str());
-    if (active && K[1] != 0.0) return h->fail(L3D_ERR_UNSUPPORTED, "lens distortion with a skewed K (K[1] != 0) is not supported");
-    out_w = checked.out_w; out_h = checked.out_h;
+    if (const int rc = l3d::warp_check(out, width, height, channels, plan, err)) return h->fail(rc, err.c_str());
+    if (plan.route != l3d::WarpRoute::None && K[1] != 0.0) return h->fail(L3D_ERR_UNSUPPORTED, skewed);
+    out_w = plan.out_w; out_h = plan.out_h;
     return L3D_OK;
 }
 
@@ -847,19 +837,8 @@ static int add_plan(L* h, const AddRequest& rq, const char* data_directory, int 
         if (rc != L3D_OK) return h->fail(rc, msg);
     }
     p.src_w = (unsigned)std::max(0, width); p.src_h = (unsigned)std::max(0, height);
-    if (rq.image() && rq.remap) {               // a remap: checked at the source size, the view is its output
-        if (rq.lens || e.dist) return h->fail(L3D_ERR_INVALID, "undistortion: an entry carries a remap beside dist (k1, k2) or a lens");
-        if (!e.K) return h->fail(L3D_ERR_INVALID, "undistortion: K is null");
-        if (width <= 0 || height <= 0) return h->fail(L3D_ERR_INVALID, "image is empty!");
-        int out_w = 0, out_h = 0;
-        if (const int rc = remap_for_add(h, e.K, *rq.remap, width, height, p.channels == 1 ? 1 : 3, p.remap, out_w, out_h)) return rc;
-        p.remap_on = true;
-        width = out_w; height = out_h;
-    } else if (rq.image()) {
-        const int with = rq.lens ? lens_for_add(h, e.K, e.dist, rq.lens, width, height, p.lens) : (e.dist || rq.dist_required) ? camera_for_add(h, e.K, e.dist, p.cam) : 0;
-        if (with < 0) return -with;
-        p.undistort = with != 0 && !rq.lens;
-        p.lens_on = with != 0 && rq.lens;
+    if (rq.image()) {                           // (a remap is checked at the source size, the view is its output)
+        if (const int rc = warp_for_add(h, e.K, e.dist, rq.warp, width, height, p.channels == 1 ? 1 : 3, p.warp, width, height)) return rc;
         if (width <= 0 || height <= 0) return h->fail(L3D_ERR_INVALID, "image is empty!");
     }
     p.width = (unsigned)width; p.height = (unsigned)height;
@@ -929,7 +908,7 @@ static int add_entry(L* h, const AddRequest& rq, const AddPlan& p, const std::ve
     return L3D_OK;
 }
 
-// the detector's entry for a request whose plan says detect (p does not move while the entry is in use: it points into it)
+// the detector's entry for a request whose plan says detect
 static void det_entry(const AddRequest& rq, const AddPlan& p, l3d::DetEntry& d)
 {
     const l3d_image_entry& e = rq.e;
@@ -938,9 +917,7 @@ static void det_entry(const AddRequest& rq, const AddPlan& p, l3d::DetEntry& d)
     d.jpeg = e.jpeg; d.jpeg_bytes = e.jpeg_bytes;
     d.dev = rq.dev;
     d.new_width = (int)p.new_w; d.new_height = (int)p.new_h; d.min_length = p.min_length; d.max_segments = 3000;
-    d.cam = p.undistort ? &p.cam : nullptr;
-    d.lens = p.lens_on ? &p.lens : nullptr;
-    d.remap = p.remap_on ? &p.remap : nullptr;
+    d.warp = p.warp;
 }
 
 // the route for one request
@@ -951,26 +928,11 @@ static int add_one(L* h, const AddRequest& rq, const char* data_directory = null
     if (const int rc = add_plan(h, rq, data_directory, max_img_width, load_and_store, p)) return rc;
     if (!p.detect) return add_entry(h, rq, p, nullptr);
     l3d_ctx* ctx = (h->node ? rank0(h) : h)->ctx;
-    const l3d_image_entry& e = rq.e;
+    // a JPEG file is decoded on the device into the detector, and a device image's memory is checked and gathered -- only here, behind the cache decision
+    l3d::DetEntry d;
+    det_entry(rq, p, d);
     std::vector<float> segs;
-    if (p.remap_on) {                           // a batch of one: the entry with its remap
-        l3d::DetEntry d;
-        det_entry(rq, p, d);
-        std::vector<std::vector<float>> outs;
-        std::vector<int> st;
-        std::vector<std::string> msg;
-        const int rc = l3d::detect_segments_batch(ctx, &d, 1, outs, st, msg);
-        if (rc != L3D_OK) return h->fail(rc, l3d_last_error(ctx));
-        if (st[0] != L3D_OK) return h->fail(st[0], msg[0].c_str());
-        return add_entry(h, rq, p, &outs[0]);
-    }
-    const l3d::DetCamera* cam = p.undistort ? &p.cam : nullptr;
-    const l3d::DetLens* lens = p.lens_on ? &p.lens : nullptr;
-    // a JPEG file is decoded on the device into the detector -- only here, behind the cache decision
-    // a device image's memory is checked and gathered only here as well
-    const int rc = rq.kind == AddKind::Jpeg ? l3d::detect_segments_jpeg(ctx, e.jpeg, e.jpeg_bytes, (int)p.new_w, (int)p.new_h, p.min_length, 3000, segs, cam, lens)
-                 : rq.kind == AddKind::Device ? l3d::detect_segments_device(ctx, *rq.dev, (int)p.new_w, (int)p.new_h, p.min_length, 3000, segs, cam, lens)
-                                            : l3d::detect_segments(ctx, e.pixels, e.width, e.height, e.channels, e.row_stride, (int)p.new_w, (int)p.new_h, p.min_length, 3000, segs, cam, lens);
+    const int rc = l3d::detect_one(ctx, d, segs);
     if (rc != L3D_OK) return h->fail(rc, l3d_last_error(ctx));
     return add_entry(h, rq, p, &segs);
 }
@@ -1046,51 +1008,47 @@ int l3d_line3d_add_image_pixels_fixed_sim_distorted(l3d_line3d* h, uint32_t id, 
                    load_and_store);
 }
 
-// the drivers' undistort block on its own (main_vsfm.cpp:243-270) with the object's device (a node object: rank 0's)
+// ---- the undistort calls of an object: the context's call with the object's device (a node object: rank 0's) and the add family's K rule
+// (warp_for_add: K is the camera, beside a lens or a remap the output camera; a skewed K with an image that is resampled is refused)
+static int undistort_with(l3d_line3d* h, bool arguments, const double* K, const double* dist, const AddWarp& rq, const l3d::WarpIo& io)
+{
+    if (!h) return L3D_ERR_INVALID;
+    L* owner = h->node ? rank0(h) : h;
+    if (!owner->ctx) return h->fail(L3D_ERR_INVALID, "no device context to undistort with");
+    if (!arguments) return h->fail(L3D_ERR_INVALID, "undistort: null argument");
+    const int width = io.in ? io.in->width : io.width, height = io.in ? io.in->height : io.height, channels = io.in ? io.in->channels : io.channels;
+    l3d::DetWarp warp;
+    int out_w = 0, out_h = 0;
+    if (const int rc = warp_for_add(h, K, dist, rq, width, height, channels == 1 ? 1 : 3, warp, out_w, out_h)) return rc;
+    const int rc = l3d::undistort_one(owner->ctx, io, warp);
+    return rc == L3D_OK ? rc : h->fail(rc, l3d_last_error(owner->ctx));
+}
+// the drivers' undistort block on its own (main_vsfm.cpp:243-270)
 int l3d_line3d_undistort_image(l3d_line3d* h, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, const double* K, double k1, double k2,
                                unsigned char* out, size_t out_row_stride)
 {
-    if (!h) return L3D_ERR_INVALID;
-    L* owner = h->node ? rank0(h) : h;
-    if (!owner->ctx) return h->fail(L3D_ERR_INVALID, "no device context to undistort with");
     const double dist[2] = { k1, k2 };
-    l3d::DetCamera cam{ 1.0, 1.0, 0.0, 0.0, 0.0, 0.0 };
-    const int with = camera_for_add(h, K, dist, cam);
-    if (with < 0) return -with;
-    const int rc = l3d::undistort_image(owner->ctx, pixels, width, height, channels, row_stride, cam, out, out_row_stride);
-    return rc == L3D_OK ? rc : h->fail(rc, l3d_last_error(owner->ctx));
+    return undistort_with(h, true, K, dist, AddWarp{ true, nullptr, nullptr, true }, l3d::WarpIo{ pixels, width, height, channels, row_stride, out, out_row_stride });
 }
-
-// l3d_undistort_image_lens with the object's device and K, the output camera (a skewed K with an active lens: refused, as with k1, k2)
+int l3d_line3d_undistort_image_device(l3d_line3d* h, const l3d_device_image* in, const double* K, double k1, double k2, const l3d_device_image* out)
+{
+    const double dist[2] = { k1, k2 };
+    l3d::WarpIo io;
+    io.in = in; io.dout = out;
+    return undistort_with(h, in && out, K, dist, AddWarp{ true, nullptr, nullptr, true }, io);
+}
+// l3d_undistort_image_lens (a lens that passes the pixels through goes on as it is: the context call copies them)
 int l3d_line3d_undistort_image_lens(l3d_line3d* h, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, const double* K,
                                     const l3d_lens* lens, unsigned char* out, size_t out_row_stride)
 {
-    if (!h) return L3D_ERR_INVALID;
-    L* owner = h->node ? rank0(h) : h;
-    if (!owner->ctx) return h->fail(L3D_ERR_INVALID, "no device context to undistort with");
-    if (!lens) return h->fail(L3D_ERR_INVALID, "undistort: null argument");
-    l3d::DetLens dl;
-    const int with = lens_for_add(h, K, nullptr, lens, width, height, dl);
-    if (with < 0) return -with;
-    // (a lens that passes the pixels through goes on as it is: the context call copies them)
-    const int rc = l3d::undistort_image(owner->ctx, pixels, width, height, channels, row_stride, l3d::DetCamera{ 1.0, 1.0, 0.0, 0.0, 0.0, 0.0 }, out, out_row_stride, &dl);
-    return rc == L3D_OK ? rc : h->fail(rc, l3d_last_error(owner->ctx));
+    return undistort_with(h, lens != nullptr, K, nullptr, AddWarp{ false, lens, nullptr }, l3d::WarpIo{ pixels, width, height, channels, row_stride, out, out_row_stride });
 }
-
-// l3d_undistort_image_remap with the object's device and K, the output camera: out of the remap's output size, valid NULL or one byte per output pixel
+// l3d_undistort_image_remap: out of the remap's output size, valid NULL or one byte per output pixel
 int l3d_line3d_undistort_image_remap(l3d_line3d* h, const unsigned char* pixels, int width, int height, int channels, size_t row_stride, const double* K,
                                      const l3d_remap* remap, unsigned char* out, size_t out_row_stride, unsigned char* valid, size_t valid_row_stride)
 {
-    if (!h) return L3D_ERR_INVALID;
-    L* owner = h->node ? rank0(h) : h;
-    if (!owner->ctx) return h->fail(L3D_ERR_INVALID, "no device context to undistort with");
-    if (!remap || !K) return h->fail(L3D_ERR_INVALID, "undistort: null argument");
-    if (width < 1 || height < 1) return h->fail(L3D_ERR_INVALID, "image is empty!");
-    l3d::DetRemap r;
-    int out_w = 0, out_h = 0;
-    if (const int rc = remap_for_add(h, K, *remap, width, height, channels == 1 ? 1 : 3, r, out_w, out_h)) return rc;
-    const int rc = l3d::undistort_image_remap(owner->ctx, pixels, width, height, channels, row_stride, r, out, out_row_stride, valid, valid_row_stride);
-    return rc == L3D_OK ? rc : h->fail(rc, l3d_last_error(owner->ctx));
+    return undistort_with(h, remap && K, K, nullptr, AddWarp{ false, nullptr, remap },
+                          l3d::WarpIo{ pixels, width, height, channels, row_stride, out, out_row_stride, valid, valid_row_stride });
 }
 
 // from a baseline JPEG file in memory: the entry with jpeg filled
@@ -1104,31 +1062,6 @@ int l3d_line3d_add_image_jpeg_fixed_sim(l3d_line3d* h, uint32_t id, const unsign
                                         int load_and_store)
 {
     return add_one(h, jpeg_request(id, bytes, n, K, R, t, dist, sim_ids, sims, n_sims), data_directory, max_img_width, load_and_store);
-}
-
-// the single call for an l3d_image_entry: what the named image forms above fill in
-int l3d_line3d_add_image_entry_lens(l3d_line3d* h, const l3d_image_entry* e, const l3d_lens* lens, const char* data_directory, int max_img_width, int load_and_store)
-{
-    if (!h) return L3D_ERR_INVALID;
-    if (!e) return h->fail(L3D_ERR_INVALID, "add_image_entry: null argument");
-    AddRequest rq;
-    if (const int rc = entry_request(h, *e, rq, true)) return rc;
-    rq.lens = lens;
-    return add_one(h, rq, data_directory, max_img_width, load_and_store);
-}
-// the entry with a remap ("A REMAP") in the place of dist and lens: K is the output camera, the view has the remap's output size
-int l3d_line3d_add_image_entry_remap(l3d_line3d* h, const l3d_image_entry* e, const l3d_remap* remap, const char* data_directory, int max_img_width, int load_and_store)
-{
-    if (!h) return L3D_ERR_INVALID;
-    if (!e) return h->fail(L3D_ERR_INVALID, "add_image_entry: null argument");
-    AddRequest rq;
-    if (const int rc = entry_request(h, *e, rq, true)) return rc;
-    rq.remap = remap;
-    return add_one(h, rq, data_directory, max_img_width, load_and_store);
-}
-int l3d_line3d_add_image_entry(l3d_line3d* h, const l3d_image_entry* e, const char* data_directory, int max_img_width, int load_and_store)
-{
-    return l3d_line3d_add_image_entry_lens(h, e, nullptr, data_directory, max_img_width, load_and_store);
 }
 
 // Many images in one call: the route above per entry, in entry order, with the detector run once (batched, l3d_detect.hip) over all entries that
@@ -1173,64 +1106,76 @@ static int add_batch(L* h, std::vector<AddItem>& items, const char* data_directo
     h->err = lines;
     return rc_all;
 }
+
+// ---- the entry forms: an l3d_image_entry or an l3d_device_entry (an image in device memory: a descriptor where the other has pixels or a file),
+// alone or n of them, each with a lens or a remap beside it or neither.  One filler per entry kind, one body for the single forms and one for the batches
+static int fill_request(L* h, const l3d_image_entry& e, AddRequest& rq, bool single) { return entry_request(h, e, rq, single); }
+static int fill_request(L*, const l3d_device_entry& e, AddRequest& rq, bool) { rq = device_request(e); return L3D_OK; }
+static const char* form_name(const l3d_image_entry*, bool single) { return single ? "add_image_entry: null argument" : "add_images: null argument"; }
+static const char* form_name(const l3d_device_entry*, bool single) { return single ? "add_device_entry: null argument" : "add_device_images: null argument"; }
+static void beside(AddWarp& w, const l3d_lens* lens) { w.lens = lens; }
+static void beside(AddWarp& w, const l3d_remap* remap) { w.remap = remap; }
+
+extern "C++" {
+template <class E, class X>
+static int add_entry_with(L* h, const E* e, const X* x, const char* data_directory, int max_img_width, int load_and_store)
+{
+    if (!h) return L3D_ERR_INVALID;
+    if (!e) return h->fail(L3D_ERR_INVALID, form_name(e, true));
+    AddRequest rq;
+    if (const int rc = fill_request(h, *e, rq, true)) return rc;
+    beside(rq.warp, x);
+    return add_one(h, rq, data_directory, max_img_width, load_and_store);
+}
+template <class E, class X>
+static int add_entries_with(L* h, const E* e, const X* const* x, int n, const char* data_directory, int max_img_width, int load_and_store, int* status)
+{
+    if (!h) return L3D_ERR_INVALID;
+    if (n < 0 || (n > 0 && !e)) return h->fail(L3D_ERR_INVALID, form_name(e, false));
+    std::vector<AddItem> items((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        items[i].rc = fill_request(h, e[i], items[i].rq, false);
+        if (items[i].rc != L3D_OK) { items[i].msg = h->err; items[i].rq.e.image_id = e[i].image_id; }
+        beside(items[i].rq.warp, x ? x[i] : nullptr);
+    }
+    return add_batch(h, items, data_directory, max_img_width, load_and_store, status);
+}
+}  // extern "C++"
 }  // namespace l3dh
 
+int l3d_line3d_add_image_entry_lens(l3d_line3d* h, const l3d_image_entry* e, const l3d_lens* lens, const char* data_directory, int max_img_width, int load_and_store)
+{
+    return add_entry_with(h, e, lens, data_directory, max_img_width, load_and_store);
+}
+int l3d_line3d_add_image_entry_remap(l3d_line3d* h, const l3d_image_entry* e, const l3d_remap* remap, const char* data_directory, int max_img_width, int load_and_store)
+{
+    return add_entry_with(h, e, remap, data_directory, max_img_width, load_and_store);
+}
+int l3d_line3d_add_image_entry(l3d_line3d* h, const l3d_image_entry* e, const char* data_directory, int max_img_width, int load_and_store)
+{
+    return l3d_line3d_add_image_entry_lens(h, e, nullptr, data_directory, max_img_width, load_and_store);
+}
 int l3d_line3d_add_images_lens(l3d_line3d* h, const l3d_image_entry* e, const l3d_lens* const* lens, int n, const char* data_directory, int max_img_width,
                                int load_and_store, int* status)
 {
-    if (!h) return L3D_ERR_INVALID;
-    if (n < 0 || (n > 0 && !e)) return h->fail(L3D_ERR_INVALID, "add_images: null argument");
-    std::vector<AddItem> items((size_t)n);
-    for (int i = 0; i < n; ++i) {
-        items[i].rc = entry_request(h, e[i], items[i].rq, false);
-        if (items[i].rc != L3D_OK) { items[i].msg = h->err; items[i].rq.e.image_id = e[i].image_id; }
-        items[i].rq.lens = lens ? lens[i] : nullptr;
-    }
-    return add_batch(h, items, data_directory, max_img_width, load_and_store, status);
+    return add_entries_with(h, e, lens, n, data_directory, max_img_width, load_and_store, status);
 }
 int l3d_line3d_add_images_remap(l3d_line3d* h, const l3d_image_entry* e, const l3d_remap* const* remap, int n, const char* data_directory, int max_img_width,
                                 int load_and_store, int* status)
 {
-    if (!h) return L3D_ERR_INVALID;
-    if (n < 0 || (n > 0 && !e)) return h->fail(L3D_ERR_INVALID, "add_images: null argument");
-    std::vector<AddItem> items((size_t)n);
-    for (int i = 0; i < n; ++i) {
-        items[i].rc = entry_request(h, e[i], items[i].rq, false);
-        if (items[i].rc != L3D_OK) { items[i].msg = h->err; items[i].rq.e.image_id = e[i].image_id; }
-        items[i].rq.remap = remap ? remap[i] : nullptr;
-    }
-    return add_batch(h, items, data_directory, max_img_width, load_and_store, status);
+    return add_entries_with(h, e, remap, n, data_directory, max_img_width, load_and_store, status);
 }
 int l3d_line3d_add_images(l3d_line3d* h, const l3d_image_entry* e, int n, const char* data_directory, int max_img_width, int load_and_store, int* status)
 {
     return l3d_line3d_add_images_lens(h, e, nullptr, n, data_directory, max_img_width, load_and_store, status);
 }
-
-// ---- images in device memory: the entry with a descriptor where the others have pixels or a file
 int l3d_line3d_add_device_entry_lens(l3d_line3d* h, const l3d_device_entry* e, const l3d_lens* lens, const char* data_directory, int max_img_width, int load_and_store)
 {
-    if (!h) return L3D_ERR_INVALID;
-    if (!e) return h->fail(L3D_ERR_INVALID, "add_device_entry: null argument");
-    AddRequest rq = device_request(*e);
-    rq.lens = lens;
-    return add_one(h, rq, data_directory, max_img_width, load_and_store);
+    return add_entry_with(h, e, lens, data_directory, max_img_width, load_and_store);
 }
 int l3d_line3d_add_device_entry_remap(l3d_line3d* h, const l3d_device_entry* e, const l3d_remap* remap, const char* data_directory, int max_img_width, int load_and_store)
 {
-    if (!h) return L3D_ERR_INVALID;
-    if (!e) return h->fail(L3D_ERR_INVALID, "add_device_entry: null argument");
-    AddRequest rq = device_request(*e);
-    rq.remap = remap;
-    return add_one(h, rq, data_directory, max_img_width, load_and_store);
-}
-int l3d_line3d_add_device_images_remap(l3d_line3d* h, const l3d_device_entry* e, const l3d_remap* const* remap, int n, const char* data_directory, int max_img_width,
-                                       int load_and_store, int* status)
-{
-    if (!h) return L3D_ERR_INVALID;
-    if (n < 0 || (n > 0 && !e)) return h->fail(L3D_ERR_INVALID, "add_device_images: null argument");
-    std::vector<AddItem> items((size_t)n);
-    for (int i = 0; i < n; ++i) { items[i].rq = device_request(e[i]); items[i].rq.remap = remap ? remap[i] : nullptr; }
-    return add_batch(h, items, data_directory, max_img_width, load_and_store, status);
+    return add_entry_with(h, e, remap, data_directory, max_img_width, load_and_store);
 }
 int l3d_line3d_add_device_entry(l3d_line3d* h, const l3d_device_entry* e, const char* data_directory, int max_img_width, int load_and_store)
 {
@@ -1239,18 +1184,19 @@ int l3d_line3d_add_device_entry(l3d_line3d* h, const l3d_device_entry* e, const 
 int l3d_line3d_add_device_images_lens(l3d_line3d* h, const l3d_device_entry* e, const l3d_lens* const* lens, int n, const char* data_directory, int max_img_width,
                                       int load_and_store, int* status)
 {
-    if (!h) return L3D_ERR_INVALID;
-    if (n < 0 || (n > 0 && !e)) return h->fail(L3D_ERR_INVALID, "add_device_images: null argument");
-    std::vector<AddItem> items((size_t)n);
-    for (int i = 0; i < n; ++i) { items[i].rq = device_request(e[i]); items[i].rq.lens = lens ? lens[i] : nullptr; }
-    return add_batch(h, items, data_directory, max_img_width, load_and_store, status);
+    return add_entries_with(h, e, lens, n, data_directory, max_img_width, load_and_store, status);
+}
+int l3d_line3d_add_device_images_remap(l3d_line3d* h, const l3d_device_entry* e, const l3d_remap* const* remap, int n, const char* data_directory, int max_img_width,
+                                       int load_and_store, int* status)
+{
+    return add_entries_with(h, e, remap, n, data_directory, max_img_width, load_and_store, status);
 }
 int l3d_line3d_add_device_images(l3d_line3d* h, const l3d_device_entry* e, int n, const char* data_directory, int max_img_width, int load_and_store, int* status)
 {
     return l3d_line3d_add_device_images_lens(h, e, nullptr, n, data_directory, max_img_width, load_and_store, status);
 }
 
-// l3d_decode_jpeg_device / l3d_undistort_image_device with the object's device (a node object: rank 0's) and, for the latter, the object's K rule
+// l3d_decode_jpeg_device with the object's device (a node object: rank 0's)
 int l3d_line3d_decode_jpeg_device(l3d_line3d* h, const unsigned char* bytes, size_t n, const l3d_device_image* out)
 {
     if (!h) return L3D_ERR_INVALID;
@@ -1259,20 +1205,6 @@ int l3d_line3d_decode_jpeg_device(l3d_line3d* h, const unsigned char* bytes, siz
     const int rc = l3d_decode_jpeg_device(owner->ctx, bytes, n, out);
     return rc == L3D_OK ? rc : h->fail(rc, l3d_last_error(owner->ctx));
 }
-int l3d_line3d_undistort_image_device(l3d_line3d* h, const l3d_device_image* in, const double* K, double k1, double k2, const l3d_device_image* out)
-{
-    if (!h) return L3D_ERR_INVALID;
-    L* owner = h->node ? rank0(h) : h;
-    if (!owner->ctx) return h->fail(L3D_ERR_INVALID, "no device context to undistort with");
-    if (!in || !out) return h->fail(L3D_ERR_INVALID, "undistort: null argument");
-    const double dist[2] = { k1, k2 };
-    l3d::DetCamera cam{ 1.0, 1.0, 0.0, 0.0, 0.0, 0.0 };
-    const int with = camera_for_add(h, K, dist, cam);
-    if (with < 0) return -with;
-    const int rc = l3d::undistort_image_device(owner->ctx, *in, cam, *out);
-    return rc == L3D_OK ? rc : h->fail(rc, l3d_last_error(owner->ctx));
-}
-
 // l3d_decode_jpeg with the object's device (a node object: rank 0's)
 int l3d_line3d_decode_jpeg(l3d_line3d* h, const unsigned char* bytes, size_t n, unsigned char* out, size_t out_row_stride)
 {

@@ -1,4 +1,4 @@
-"""Undistortion with a lens on the device (k_det_undistort_lens, l3d_detect.hip) against the contract of include/line3d_amd.h ("A LENS") as
+"""Undistortion with a lens on the device (k_det_undistort_lens, l3d_undistort.hip) against the contract of include/line3d_amd.h ("A LENS") as
 tests/lens_model.py states it: byte for byte, no pixel left out.  The margins that make this exact for the fisheye cases are checked without a
 device (tests/test_lens_cases_cpu.py).  Then the wiring into the detector, single and batched, the dispatch between the two undistortion
 kernels, and the refusals."""

@@ -1,4 +1,4 @@
-"""Undistortion onto another size with a validity plane on the device (k_det_undistort_remap, l3d_detect.hip) against the contract of
+"""Undistortion onto another size with a validity plane on the device (k_det_undistort_remap, l3d_undistort.hip) against the contract of
 include/line3d_amd.h ("A REMAP") as tests/remap_model.py states it: pixels AND validity byte for byte, no pixel left out.  The margins that make
 this exact for the fisheye cases are checked without a device (tests/test_remap_cases_cpu.py).  Then the planner's camera through the call, the
 kernels launched, and the refusals."""

@@ -1,4 +1,4 @@
-"""Undistortion on the device (k_det_undistort, l3d_detect.hip) against the contract of include/line3d_amd.h as tests/undistort_model.py states
+"""Undistortion on the device (k_det_undistort, l3d_undistort.hip) against the contract of include/line3d_amd.h as tests/undistort_model.py states
 it: byte for byte.  The margins that make this exact are checked without a device (tests/test_undistort_cpu.py).  Then the wiring into the
 detector and into addImage (exact), and one agreement test of the geometry through the detector, held to the bar of tests/test_gpu_detect.py.
 
