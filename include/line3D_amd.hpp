@@ -33,6 +33,37 @@ template <int N> struct prio : prio<N - 1> {};      // overload ranking: prio<1>
 template <> struct prio<0> {};
 }  // namespace detail
 
+// A segment mask (include/line3d_amd.h, "A SEGMENT MASK": l3d_segment_mask) for Line3D::addImageMasked.  `mask`: width x height bytes, rows
+// row_stride bytes apart (0: width), in host memory -- onDevice(): in device memory --, which has to live until the call that takes it returns.
+// Without a lens the mask lies in the view's grid and has its size; withLens(): in the grid of the lens's distorted image, fx, fy, cx, cy being
+// the view's camera.  The mode is one of drop (keep a segment when at least keep_permille of its samples are valid), clip (its longest valid
+// stretch) and split (every valid stretch); threshold: the byte value from which a mask pixel counts as valid
+class SegmentMask {
+public:
+    SegmentMask(const void* mask, const int width, const int height, const size_t row_stride = 0) : m_()
+    {
+        m_.mask = mask; m_.mask_width = width; m_.mask_height = height; m_.mask_row_stride = row_stride ? row_stride : (size_t)(width > 0 ? width : 0);
+        m_.mode = L3D_SEGMASK_DROP; m_.threshold = 1; m_.keep_permille = 500;
+    }
+    SegmentMask& onDevice(const bool on = true) { m_.mask_on_device = on ? 1 : 0; return *this; }
+    SegmentMask& withLens(const l3d_lens& lens, const double fx, const double fy, const double cx, const double cy)
+    {
+        lens_ = lens; has_lens_ = true;
+        m_.fx = fx; m_.fy = fy; m_.cx = cx; m_.cy = cy;
+        return *this;
+    }
+    SegmentMask& threshold(const int t) { m_.threshold = t; return *this; }
+    SegmentMask& drop(const int keep_permille = 500) { m_.mode = L3D_SEGMASK_DROP; m_.keep_permille = keep_permille; return *this; }
+    SegmentMask& clip(const double min_length = 0.0, const int max_gap = 0) { m_.mode = L3D_SEGMASK_CLIP; m_.min_length = min_length; m_.max_gap = max_gap; return *this; }
+    SegmentMask& split(const double min_length = 0.0, const int max_gap = 0) { m_.mode = L3D_SEGMASK_SPLIT; m_.min_length = min_length; m_.max_gap = max_gap; return *this; }
+    // the struct as the C ABI takes it (valid while this object lives and is not changed)
+    const l3d_segment_mask* get() const { m_.lens = has_lens_ ? &lens_ : nullptr; return &m_; }
+private:
+    mutable l3d_segment_mask m_;
+    l3d_lens lens_ = l3d_lens();
+    bool has_lens_ = false;
+};
+
 // commons.h:81-99
 class L3DSegment2D {
 public:
@@ -135,6 +166,30 @@ public:
         for (auto& kv : viewSimilarity) { ids.push_back(kv.first); sims.push_back(kv.second); }
         report(l3d_line3d_add_image_fixed_sim_ex(h_, imageID, width, height, segments.empty() ? nullptr : &segments[0].x, (int)segments.size(), K, R, t,
                                                  ids.data(), sims.data(), (int)ids.size(), data_directory_.c_str(), maxImgWidth, loadAndStoreSegments ? 1 : 0));
+    }
+    // Segments of the caller's behind a SEGMENT MASK (include/line3d_amd.h, "A SEGMENT MASK": l3d_line3d_add_image_masked): the segments are dropped,
+    // clipped or split at the mask on the device, then added as addImage / addImage_fixed_sim add them -- without the segment cache (nothing is
+    // read, written or removed).  Segments that all fall to the mask add no view.  false: refused (message printed)
+    bool addImageMasked(const unsigned int imageID, const unsigned int width, const unsigned int height, const std::vector<float4>& segments,
+                        const double K[9], const double R[9], const double t[3], std::list<unsigned int>& worldpointIDs, const SegmentMask& mask)
+    {
+        std::vector<uint32_t> wps(worldpointIDs.begin(), worldpointIDs.end());
+        const int rc = l3d_line3d_add_image_masked(h_, imageID, width, height, segments.empty() ? nullptr : &segments[0].x, (int)segments.size(), K, R, t,
+                                                   wps.data(), nullptr, (int)wps.size(), mask.get());
+        report(rc);
+        return rc == L3D_OK;
+    }
+    bool addImageMasked(const unsigned int imageID, const unsigned int width, const unsigned int height, const std::vector<float4>& segments,
+                        const double K[9], const double R[9], const double t[3], std::map<unsigned int, float>& viewSimilarity, const SegmentMask& mask)
+    {
+        std::vector<uint32_t> ids;
+        std::vector<float> sims;
+        for (auto& kv : viewSimilarity) { ids.push_back(kv.first); sims.push_back(kv.second); }
+        if (sims.empty()) sims.push_back(0.0f);             // (no links: refused by the call, as a similarity list -- not read as world points)
+        const int rc = l3d_line3d_add_image_masked(h_, imageID, width, height, segments.empty() ? nullptr : &segments[0].x, (int)segments.size(), K, R, t,
+                                                   ids.data(), sims.data(), (int)ids.size(), mask.get());
+        report(rc);
+        return rc == L3D_OK;
     }
     // The same two calls with matrix-typed cameras, as the reference's drivers pass them (Eigen::Matrix3d K, R; Eigen::Vector3d t,
     // main_vsfm.cpp:273-281): any type with K(i, j) / t(i) access -- Eigen is not a dependency of this header.

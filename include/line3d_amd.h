@@ -1289,6 +1289,82 @@ int l3d_line3d_add_device_images_remap(l3d_line3d* h, const l3d_device_entry* e,
 int l3d_line3d_add_device_images_lens(l3d_line3d* h, const l3d_device_entry* e, const l3d_lens* const* lens, int n, const char* data_directory, int max_img_width,
                                       int load_and_store, int* status);
 
+/* =================================================================================================
+ * A SEGMENT MASK: a mask applied to line SEGMENTS -- whole segments dropped, or segments clipped or split at the mask's edges -- on the device
+ * (line3d_amd/csrc/l3d_segmask.hip, l3d_segmask.hpp).  The validity plane of A REMAP keeps masked pixels out of the detector; segments that come from
+ * the caller, from a segment cache, or from a cache that stands in for the image on the pixel route never pass that plane.  This is the mask for them.
+ *
+ * Numeric rules: all arithmetic is f64, every product and sum rounded on its own (nothing fused); integer arithmetic is int64.
+ *
+ * THE SEGMENT AND ITS SAMPLES.  A segment is x1, y1, x2, y2 (f32); pixel (j, i) has its centre at (j, i).
+ *     dx = x2 - x1      dy = y2 - y1      m = max(|dx|, |dy|)      n = floor(m) + 1
+ *     sample k, k = 0..n (n + 1 samples):  t = k / n      px = x1 + t dx      py = y1 + t dy
+ *   Without a lens the sample reads mask pixel (floor(px + 0.5), floor(py + 0.5)).  A sample outside mask_width x mask_height is invalid; otherwise
+ *   it is valid when its byte is >= threshold.  threshold runs 1..255, and 0 reads as 1: this is how a weighted (soft) mask is read, any other
+ *   weighting is out of scope.
+ * A LENS.  With an active lens the mask lies in the lens's SOURCE grid (the distorted image) and the segments in the grid of the camera fx, fy, cx, cy
+ *   given beside it: (px, py) goes through the formulas of A LENS with j = px, i = py and (fx', fy', cx', cy') = (fx, fy, cx, cy), giving (u, v), and
+ *   the sample reads mask pixel (floor(u + 0.5), floor(v + 0.5)).  A u or v that is not finite is invalid.  The lens is checked as A LENS checks it,
+ *   with its codes (the mask's extent in the place of the image's).  lens NULL, or a lens that is not active (BROWN, every coefficient within
+ *   1e-12, equal cameras): the mask is in the segments' grid and fx, fy, cx, cy are not read.
+ * ALWAYS DROPPED, in every mode: a segment with a coordinate that is not finite, with dx == dy == 0, or with m >= 65536.
+ * MODE DROP.  V = the number of valid samples.  The segment is kept iff V 1000 >= keep_permille (n + 1), keep_permille in 0..1000.  A kept segment
+ *   keeps its bits.
+ * MODES CLIP AND SPLIT.  Bridging: a run of at most max_gap (>= 0) invalid samples strictly between two valid samples counts as valid.  A run [a, b]
+ *   is a maximal run of valid samples with a < b.  Length test: with s = (b - a) / n and L2 = dx dx + dy dy the run passes iff
+ *   (s s) L2 >= min_length min_length.  CLIP emits the run with the largest b - a (the first on a tie) if it passes, otherwise nothing.  SPLIT emits
+ *   every passing run, in ascending a.  An emitted end point is the sample's (px, py) rounded to f32; where a == 0 the bits of x1, y1 are emitted,
+ *   where b == n the bits of x2, y2: an all-valid mask returns the input byte for byte.
+ * OUTPUT.  The segments in input order, the runs of one segment in order along it; an int32 src_index per output segment names the input segment it
+ *   came from.  Both callee-allocated (l3d_free); *n_out may exceed n (SPLIT).
+ * REFUSED, L3D_ERR_INVALID, before anything is launched or read: a NULL mask (the struct or its plane); an extent below 1 x 1; a row stride below the
+ *   width; a mode, threshold (0..255), keep_permille, max_gap or min_length (finite, >= 0) out of range; what A LENS refuses; a device mask (or device
+ *   segment array) whose memory kind or extent fails the check an l3d_device_image gets.  More than 2^31 - 1 output segments: L3D_ERR_UNSUPPORTED.
+ *
+ * THE KERNELS.  One wave per segment, four waves per workgroup; lanes stride over the samples, a ballot gives the validity of 64 samples as one word,
+ * bridging and run search work on those words, uniformly across the wave.  k_segmask_count counts every segment's outputs, k_segmask_scan (one
+ * workgroup, l3d_scan.hpp) turns the counts into positions, k_segmask_write writes the segments and src_index there: the order is fixed by the scan,
+ * never by atomics, and the number of launches (three) does not depend on n.  Profile names segmask_count, segmask_scan, segmask_write.  A host mask is
+ * uploaded once per call; a device mask and a device segment array are read in place (the caller has synchronised whatever wrote them).
+ *   l3d_mask_segments              segments: n x 4 floats in host memory
+ *   l3d_mask_segments_device       the same with the segments in device memory; the outputs are host memory as above
+ *   l3d_test_mask_segments_host    the same arguments without the context; needs no device (mask_on_device: refused).  It runs the functions the
+ *                                  kernels run, lane after lane, and is bit-equal to the device call -- but for atan in a FISHEYE lens, whose bits
+ *                                  the device does not share with a host libm (A LENS).  l3d_segmask_last_error (per thread) holds its message
+ *   l3d_line3d_add_image_masked    l3d_line3d_add_image (sims == NULL: link_ids are world point ids) or ..._fixed_sim with the segments filtered
+ *                                  first.  mask NULL: L3D_ERR_INVALID.  Without an active lens the mask's extent must be the view's width x height,
+ *                                  else L3D_ERR_INVALID.  Nothing left after the filter: L3D_OK and no view, as when the detector finds nothing.
+ *                                  On a node object the filter runs once, on rank 0's device, and every rank gets the result
+ *   l3d_line3d_add_image_cached_masked
+ *                                  the cache's segments go through the filter; the cache's collinearities are discarded and the view computes its
+ *                                  own, as it does for given segments.  No cache file is written or changed
+ * On the pixel route a cache that is "present and wanted" stands in for the image (THE ADD FAMILY, step 2), so a mask that changed since the cache was
+ * written has no effect there; that behaviour stays.  The masked forms are the way round it: read the cache and add it through
+ * l3d_line3d_add_image_cached_masked.
+ * ================================================================================================= */
+enum { L3D_SEGMASK_DROP = 0, L3D_SEGMASK_CLIP = 1, L3D_SEGMASK_SPLIT = 2 };
+typedef struct l3d_segment_mask {
+    const void* mask;               /* mask_width x mask_height bytes, rows mask_row_stride bytes apart */
+    size_t mask_row_stride;
+    int32_t mask_width, mask_height;
+    int32_t mask_on_device;         /* the plane is device memory */
+    const l3d_lens* lens;           /* NULL: the mask is in the segments' grid */
+    double fx, fy, cx, cy;          /* the segments' camera (read only with a lens) */
+    int32_t mode;                   /* L3D_SEGMASK_DROP, _CLIP, _SPLIT */
+    int32_t threshold;              /* 1..255; 0 reads as 1 */
+    int32_t keep_permille;          /* DROP: 0..1000 */
+    int32_t max_gap;                /* CLIP, SPLIT: >= 0 */
+    double min_length;              /* CLIP, SPLIT: pixels, >= 0 */
+} l3d_segment_mask;
+int l3d_mask_segments(l3d_ctx* ctx, const float* segments, int n, const l3d_segment_mask* mask, float** out, int32_t** src_index, int* n_out);
+int l3d_mask_segments_device(l3d_ctx* ctx, const float* segments, int n, const l3d_segment_mask* mask, float** out, int32_t** src_index, int* n_out);
+int l3d_test_mask_segments_host(const float* segments, int n, const l3d_segment_mask* mask, float** out, int32_t** src_index, int* n_out);
+const char* l3d_segmask_last_error(void);
+int l3d_line3d_add_image_masked(l3d_line3d* h, uint32_t image_id, unsigned width, unsigned height, const float* segments, int n_segments, const double* K,
+                                const double* R, const double* t, const uint32_t* link_ids, const float* sims, int n_links, const l3d_segment_mask* mask);
+int l3d_line3d_add_image_cached_masked(l3d_line3d* h, uint32_t image_id, unsigned width, unsigned height, const l3d_segment_cache* cache, const double* K,
+                                       const double* R, const double* t, const uint32_t* link_ids, const float* sims, int n_links, const l3d_segment_mask* mask);
+
 /* The detector's stages on their own, exported for tests (tests/test_gpu_detect_stages.py): the same kernels with the same launch shapes
  * as l3d_detect_segments, results copied to caller-allocated arrays.  (N, M) = (ceil(0.8 new_width), ceil(0.8 new_height)) is the scaled image.
  *   pixel stage   grey[new_width x new_height] after rescale + grey; img / mod / ang [N x M]: the Gaussian sampler's output, the 2x2 gradient's

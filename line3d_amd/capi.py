@@ -356,6 +356,100 @@ def remap_pointers(lenses, out_sizes, masks, border_masks, n):
     return arr, keep
 
 
+# l3d_segment_mask (include/line3d_amd.h, "A SEGMENT MASK")
+SEGMASK_DROP, SEGMASK_CLIP, SEGMASK_SPLIT = 0, 1, 2
+
+
+class SegmentMask(C.Structure):
+    """l3d_segment_mask: the plane, the lens and the segments' camera, the mode and its parameters"""
+    _fields_ = [("mask", C.c_void_p), ("mask_row_stride", C.c_size_t), ("mask_width", C.c_int32), ("mask_height", C.c_int32), ("mask_on_device", C.c_int32),
+                ("lens", C.c_void_p), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("mode", C.c_int32), ("threshold", C.c_int32),
+                ("keep_permille", C.c_int32), ("max_gap", C.c_int32), ("min_length", C.c_double)]
+
+
+def segment_mask(mask, lens=None, camera=None, mode="drop", threshold=1, keep_permille=500, max_gap=0, min_length=0.0):
+    """An l3d_segment_mask.  mask: a uint8 / bool array H x W whose rows are contiguous (they may lie further apart than W: a view into a wider
+    array is taken as it is), or a device object of that shape (a torch uint8 device tensor, anything with __cuda_array_interface__); a byte
+    >= threshold is valid.  lens: capi.lens(...) when the mask lies in the distorted image's grid, with camera = (fx, fy, cx, cy) of the grid the
+    segments lie in; None: the mask is in the segments' grid.  mode: "drop" (keep a segment when at least keep_permille of its samples are valid),
+    "clip" (the longest valid stretch) or "split" (every valid stretch), the latter two bridging gaps of up to max_gap samples and keeping
+    stretches of at least min_length pixels; or a mode number.  What the library refuses is left to it.  What the struct points at is kept alive
+    on the returned object."""
+    m = SegmentMask()
+    m._keep = []
+    if hasattr(mask, "__cuda_array_interface__"):
+        iface = mask.__cuda_array_interface__
+        shape, strides = tuple(iface["shape"]), iface.get("strides")
+        if len(shape) != 2 or str(iface["typestr"]) not in ("|u1", "|b1") or (strides is not None and int(strides[1]) != 1):
+            raise TypeError("a device mask must be an H x W array of bytes whose rows are contiguous")
+        m.mask, m.mask_row_stride, m.mask_on_device = int(iface["data"][0]), int(shape[1] if strides is None else strides[0]), 1
+        m.mask_height, m.mask_width = int(shape[0]), int(shape[1])
+        m._keep.append(mask)
+    elif mask is not None:
+        a = np.asarray(mask)
+        if a.ndim != 2 or a.dtype not in (np.uint8, np.bool_):
+            raise TypeError("mask must be a uint8 or bool array H x W")
+        if a.shape[0] > 1 and a.shape[1] > 0 and (a.strides[1] != 1 or a.strides[0] < a.shape[1]):
+            a = np.ascontiguousarray(a)
+        a = a.view(np.uint8)
+        m.mask = a.ctypes.data if a.size else None
+        m.mask_row_stride = max(int(a.strides[0]), int(a.shape[1]))
+        m.mask_height, m.mask_width = int(a.shape[0]), int(a.shape[1])
+        m._keep.append(a)
+    if lens is not None:
+        if not isinstance(lens, Lens):
+            raise TypeError("lens must come from capi.lens()")
+        m.lens = C.addressof(lens)
+        m._keep.append(lens)
+    if camera is not None:
+        if len(camera) != 4:
+            raise ValueError("camera must be (fx, fy, cx, cy)")
+        m.fx, m.fy, m.cx, m.cy = (float(v) for v in camera)
+    mode_ = {"drop": SEGMASK_DROP, "clip": SEGMASK_CLIP, "split": SEGMASK_SPLIT}.get(mode.lower() if isinstance(mode, str) else None, mode)
+    if isinstance(mode_, str):
+        raise ValueError("mode must be 'drop', 'clip', 'split' or a mode number")
+    m.mode, m.threshold, m.keep_permille, m.max_gap, m.min_length = int(mode_), int(threshold), int(keep_permille), int(max_gap), float(min_length)
+    return m
+
+
+def _as_segment_mask(mask, kw):
+    if isinstance(mask, SegmentMask):
+        if kw:
+            raise TypeError("a capi.segment_mask() carries its parameters: %s given beside it" % sorted(kw))
+        return mask
+    return segment_mask(mask, **kw)
+
+
+def _mask_segments_call(fn, head, seg_ptr, n, m):
+    """the argument list the segment-mask calls share (head: the context, or nothing) -> (rc, segments (k, 4) float32, src_index (k,) int32)"""
+    out, src, n_out = C.POINTER(C.c_float)(), C.POINTER(C.c_int32)(), C.c_int(0)
+    rc = fn(*head, seg_ptr, C.c_int(n), C.byref(m) if m is not None else None, C.byref(out), C.byref(src), C.byref(n_out))
+    if rc != 0:
+        return rc, None, None
+    k = n_out.value
+    segs = np.ctypeslib.as_array(out, (k * 4,)).copy().reshape(-1, 4) if k else np.zeros((0, 4), np.float32)
+    idx = np.ctypeslib.as_array(src, (k,)).copy() if k else np.zeros(0, np.int32)
+    lib = load_library()
+    lib.l3d_free(out)
+    lib.l3d_free(src)
+    return 0, segs, idx
+
+
+def mask_segments_host(segments, mask, **kw):
+    """l3d_test_mask_segments_host: the segment mask's arithmetic on the host -- no context, no device.  Arguments and result as
+    Context.mask_segments (host arrays only).  A refusal raises L3DError carrying the status in .code."""
+    lib = load_library()
+    lib.l3d_segmask_last_error.restype = C.c_char_p
+    m = None if mask is None else _as_segment_mask(mask, kw)
+    s = np.ascontiguousarray(segments, np.float32).reshape(-1, 4)
+    rc, segs, idx = _mask_segments_call(lib.l3d_test_mask_segments_host, (), _p(s) if len(s) else None, len(s), m)
+    if rc != 0:
+        e = L3DError("line3d_amd error %d: %s" % (rc, lib.l3d_segmask_last_error().decode()))
+        e.code = rc
+        raise e
+    return segs, idx
+
+
 # dtype codes of l3d_device_image (L3D_U8 ...)
 U8, U16, F16, F32 = 0, 1, 2, 3
 _TYPESTR = {"|u1": U8, "<u2": U16, "<f2": F16, "<f4": F32}
@@ -1307,6 +1401,25 @@ class Context:
         rc, out = _refine_call(self.lib.l3d_refine_lines, (self.h,), group_start, member_cam, member_seg, member_pts, cameras, max_iterations, huber_px)
         self._chk(rc)
         return out
+
+    def mask_segments(self, segments, mask, **kw):
+        """l3d_mask_segments: segments (n, 4) float32 through a segment mask ("A SEGMENT MASK") -> (segments (k, 4) float32, src_index (k,) int32),
+        the input segment every output came from.  mask: a capi.segment_mask(...), or a mask array / device object with segment_mask's keywords
+        (lens=, camera=, mode=, threshold=, keep_permille=, max_gap=, min_length=).  segments may be a device object (a float32 (n, 4) device
+        tensor, contiguous and 16-byte aligned): it is read in place (l3d_mask_segments_device), like a device mask; the caller has synchronised
+        whatever wrote them.  The result is host memory either way."""
+        m = None if mask is None else _as_segment_mask(mask, kw)
+        if hasattr(segments, "__cuda_array_interface__"):
+            iface = segments.__cuda_array_interface__
+            shape, strides = tuple(int(v) for v in iface["shape"]), iface.get("strides")
+            if len(shape) != 2 or shape[1] != 4 or str(iface["typestr"]) != "<f4" or (strides is not None and tuple(int(v) for v in strides) != (16, 4)):
+                raise TypeError("device segments must be a contiguous float32 array n x 4")
+            rc, segs, idx = _mask_segments_call(self.lib.l3d_mask_segments_device, (self.h,), C.c_void_p(int(iface["data"][0]) or None), shape[0], m)
+        else:
+            s = np.ascontiguousarray(segments, np.float32).reshape(-1, 4)
+            rc, segs, idx = _mask_segments_call(self.lib.l3d_mask_segments, (self.h,), _p(s) if len(s) else None, len(s), m)
+        self._chk(rc)
+        return segs, idx
 
     def fit_labelled_clusters(self, labels, node_hyp, hyp, hyp_cam, Rinv, scale_inv, tneg):
         """l3d_fit_labelled_clusters: -> (group_start, member_hyp, list per fitted cluster of (start, end))."""

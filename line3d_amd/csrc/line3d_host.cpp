@@ -962,6 +962,60 @@ int l3d_line3d_add_image_cached(l3d_line3d* h, uint32_t id, unsigned width, unsi
     rq.cache = cache;
     return add_one(h, rq);
 }
+// ---- the segment-taking forms behind a segment mask ("A SEGMENT MASK"): the filter once, on the object's device (a node object: rank 0's), then
+// the existing add with what it left.  Nothing left: no view and no error, as when the detector finds nothing (the guards come after the filter)
+static int add_masked(l3d_line3d* h, uint32_t id, unsigned width, unsigned height, const float* segs, int n, const double* K, const double* R, const double* t,
+                      const uint32_t* link_ids, const float* sims, int n_links, const l3d_segment_mask* mask)
+{
+    if (!h) return L3D_ERR_INVALID;
+    if (!mask) return h->fail(L3D_ERR_INVALID, "segment mask: the mask is null");
+    L* owner = h->node ? rank0(h) : h;
+    if (!owner->ctx) return h->fail(L3D_ERR_INVALID, "no device context to mask line segments with");
+    // without an active lens the mask lies in the view's grid and has its extent (a lens the checks refuse: the filter says so, below)
+    bool in_view_grid = true;
+    if (mask->lens) {
+        l3d::DetWarp w;
+        w.has_lens = true;
+        w.lens = l3d::make_lens(*mask->lens, mask->fx, mask->fy, mask->cx, mask->cy);
+        l3d::WarpPlan plan;
+        std::string err;
+        in_view_grid = l3d::warp_check(w, mask->mask_width, mask->mask_height, 1, plan, err) == L3D_OK && plan.route == l3d::WarpRoute::None;
+    }
+    if (in_view_grid && mask->mask && mask->mask_width >= 1 && mask->mask_height >= 1 && ((unsigned)mask->mask_width != width || (unsigned)mask->mask_height != height))
+        return h->fail(L3D_ERR_INVALID, ("segment mask: the mask is " + std::to_string(mask->mask_width) + " x " + std::to_string(mask->mask_height) + ", the view " +
+                                         std::to_string(width) + " x " + std::to_string(height)).c_str());
+    float* out = nullptr;
+    int32_t* src = nullptr;
+    int n_out = 0;
+    const int rc = l3d_mask_segments(owner->ctx, segs, n, mask, &out, &src, &n_out);
+    if (rc != L3D_OK) return h->fail(rc, l3d_last_error(owner->ctx));
+    int ret = L3D_OK;
+    if (n_out > 0) {
+        AddRequest rq = add_request(AddKind::Segments, id, width, height, K, R, t, link_ids, sims, n_links, false);
+        rq.segs = out; rq.n = n_out;
+        ret = add_one(h, rq);
+    }
+    l3d_free(out);
+    l3d_free(src);
+    return ret;
+}
+int l3d_line3d_add_image_masked(l3d_line3d* h, uint32_t id, unsigned width, unsigned height, const float* segs, int n, const double* K, const double* R, const double* t,
+                                const uint32_t* link_ids, const float* sims, int n_links, const l3d_segment_mask* mask)
+{
+    return add_masked(h, id, width, height, segs, n, K, R, t, link_ids, sims, n_links, mask);
+}
+// the cache's segments through the filter; its collinearities are not taken over, the view computes its own.  No cache file is touched
+int l3d_line3d_add_image_cached_masked(l3d_line3d* h, uint32_t id, unsigned width, unsigned height, const l3d_segment_cache* cache, const double* K, const double* R,
+                                       const double* t, const uint32_t* link_ids, const float* sims, int n_links, const l3d_segment_mask* mask)
+{
+    if (!h) return L3D_ERR_INVALID;
+    if (!cache) return h->fail(L3D_ERR_INVALID, "null segment cache");
+    const int n = l3d_segment_cache_num_segments(cache), nc = l3d_segment_cache_num_collinearities(cache);
+    std::vector<float> segs((size_t)std::max(n, 0) * 4 + 1), cw((size_t)std::max(nc, 0) + 1);
+    std::vector<int32_t> ci((size_t)std::max(nc, 0) + 1), cj((size_t)std::max(nc, 0) + 1);
+    l3d_segment_cache_get(cache, segs.data(), ci.data(), cj.data(), cw.data());
+    return add_masked(h, id, width, height, segs.data(), std::max(n, 0), K, R, t, link_ids, sims, n_links, mask);
+}
 // the same with the cache rules, line3D.cc:128-199
 int l3d_line3d_add_image_ex(l3d_line3d* h, uint32_t id, unsigned width, unsigned height, const float* segs, int n, const double* K, const double* R,
                             const double* t, const uint32_t* worldpoints, int n_wps, const char* data_directory, int max_img_width, int load_and_store)

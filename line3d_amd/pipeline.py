@@ -205,24 +205,49 @@ class Line3D:
         return c
 
     # -- reference interface ------------------------------------------------------------------
-    def addImage(self, imageID, width, height, segments, K, R, t, worldpointIDs):
+    def _add_masked(self, imageID, width, height, segments, cache, K, R, t, links, fixed_sim, segment_mask):
+        """the segment-taking adds behind a segment mask (l3d_line3d_add_image_masked / ..._cached_masked); the status stays in last_rc"""
+        if not isinstance(segment_mask, capi.SegmentMask):
+            raise TypeError("segment_mask must come from capi.segment_mask()")
+        args, keep = _camera_and_links(K, R, t, links, fixed_sim)
+        links_args = args[3:] if fixed_sim else [args[3], None, args[4]]           # link_ids, sims (None: world point ids), n_links
+        head = [self.h, C.c_uint32(imageID), C.c_uint(width), C.c_uint(height)]
+        if cache is not None:
+            rc = self.lib.l3d_line3d_add_image_cached_masked(*head, cache, *args[:3], *links_args, C.byref(segment_mask))
+        else:
+            segs = np.ascontiguousarray(segments, dtype=np.float32).reshape(-1, 4)
+            rc = self.lib.l3d_line3d_add_image_masked(*head, _p(segs) if len(segs) else None, C.c_int(len(segs)), *args[:3], *links_args, C.byref(segment_mask))
+        self.last_rc = int(rc)
+        return rc == 0
+
+    def addImage(self, imageID, width, height, segments, K, R, t, worldpointIDs, segment_mask=None):
+        """segment_mask: None, or a capi.segment_mask(...) the segments go through first ("A SEGMENT MASK": dropped, clipped or split on the device;
+        without a lens the mask has the view's size; segments that all fall to it add no view and the call is still True)"""
+        if segment_mask is not None:
+            return self._add_masked(imageID, width, height, segments, None, K, R, t, worldpointIDs, False, segment_mask)
         segs = np.ascontiguousarray(segments, dtype=np.float32).reshape(-1, 4)
         args, keep = _camera_and_links(K, R, t, worldpointIDs, False)
         rc = self.lib.l3d_line3d_add_image(self.h, C.c_uint32(imageID), C.c_uint(width), C.c_uint(height), _p(segs), C.c_int(len(segs)), *args)
         return rc == 0          # the reference prints to cerr and returns (line3D.cc:101-127)
 
-    def addImage_fixed_sim(self, imageID, width, height, segments, K, R, t, viewSimilarity):
+    def addImage_fixed_sim(self, imageID, width, height, segments, K, R, t, viewSimilarity, segment_mask=None):
+        if segment_mask is not None:
+            return self._add_masked(imageID, width, height, segments, None, K, R, t, viewSimilarity, True, segment_mask)
         segs = np.ascontiguousarray(segments, dtype=np.float32).reshape(-1, 4)
         args, keep = _camera_and_links(K, R, t, viewSimilarity, True)
         rc = self.lib.l3d_line3d_add_image_fixed_sim(self.h, C.c_uint32(imageID), C.c_uint(width), C.c_uint(height), _p(segs), C.c_int(len(segs)), *args)
         return rc == 0
 
-    def addImage_cached(self, imageID, width, height, cache_path, K, R, t, worldpointIDs):
-        """addImage when the segment cache file exists (line3D.cc:160-168): segments and collinearities from the file."""
+    def addImage_cached(self, imageID, width, height, cache_path, K, R, t, worldpointIDs, segment_mask=None):
+        """addImage when the segment cache file exists (line3D.cc:160-168): segments and collinearities from the file.  With a segment_mask the
+        file's segments go through the mask and the view computes its own collinearities; the file is not changed (there the links may also be
+        {view id: similarity}, as addImage_fixed_sim takes them)."""
         from .io import open_segment_cache, close_segment_cache
-        args, keep = _camera_and_links(K, R, t, worldpointIDs, False)
         cache = open_segment_cache(cache_path)
         try:
+            if segment_mask is not None:        # (the masked form also takes {view id: similarity} in the place of the world point ids)
+                return self._add_masked(imageID, width, height, None, cache, K, R, t, worldpointIDs, isinstance(worldpointIDs, dict), segment_mask)
+            args, keep = _camera_and_links(K, R, t, worldpointIDs, False)
             rc = self.lib.l3d_line3d_add_image_cached(self.h, C.c_uint32(imageID), C.c_uint(width), C.c_uint(height), cache, *args)
         finally:
             close_segment_cache(cache)

@@ -103,16 +103,27 @@ def result_basename(max_width=-1, neighbors=10, min_uncertainty=1.0, max_uncerta
                "COLLIN" if collinearity else "NO_COLLIN", "DIFFUSION" if diffusion else "NO_DIFFUSION"))
 
 
-def reconstruct(scene: SfmScene, segments, image_sizes, out_dir=None, neighbors=10, diffusion=False, device=0, **line3d_kwargs):
+def reconstruct(scene: SfmScene, segments, image_sizes, out_dir=None, neighbors=10, diffusion=False, device=0, masks=None, mask_mode="split", mask_threshold=1,
+                mask_keep_permille=500, mask_max_gap=0, mask_min_length=0.0, **line3d_kwargs):
     """The drivers' flow (main_vsfm.cpp:226-325) with detected segments in place of images: K from focal and image size,
     addImage with the world point lists, compute3Dmodel, optional STL + TXT output under the drivers' file name.
     segments[i]: (S,4) float32 of camera i (undistorted image coordinates); image_sizes[i]: (width, height).
     segments may also be a DIRECTORY: the reference's data directory (main_vsfm.cpp:108-116, "<image folder>/L3D_data"),
-    whose segment caches "segments_<id>_<w>x<h>_coll<0|1>.bin" of an earlier run are replayed (line3D.cc:143-168)."""
+    whose segment caches "segments_<id>_<w>x<h>_coll<0|1>.bin" of an earlier run are replayed (line3D.cc:143-168).
+    masks: None, or a callable image name -> mask (a uint8 / bool array H x W of the image's size, or a device object; a byte >= mask_threshold is
+    valid) or None for an image without one (COLMAP's mask_path read by the caller).  The image's segments -- given, or replayed from a cache, whose
+    collinearities are then computed anew -- go through the mask on the device first ("A SEGMENT MASK", capi.segment_mask): mask_mode "drop",
+    "clip" or "split" with mask_keep_permille, mask_max_gap and mask_min_length beside it.  An image whose segments all fall to its mask adds no view."""
     import os
+    from . import capi
     from .pipeline import Line3D
     from .io import segment_cache_filename
     l3d = Line3D("", matchingNeighbors=neighbors, device=device, **line3d_kwargs)
+
+    def mask_of(cam):
+        m = masks(cam["name"]) if masks is not None else None
+        return None if m is None else capi.segment_mask(m, mode=mask_mode, threshold=mask_threshold, keep_permille=mask_keep_permille, max_gap=mask_max_gap,
+                                                        min_length=mask_min_length)
     for i, cam in enumerate(scene.cameras):
         if np.any(np.abs(cam["dist"]) > 1e-12) or _lens_active(cam):
             raise RuntimeError("camera %d has lens distortion: segments of the undistorted image cannot be made from it here -- "
@@ -122,9 +133,13 @@ def reconstruct(scene: SfmScene, segments, image_sizes, out_dir=None, neighbors=
             path = os.fspath(segments) + segment_cache_filename(i, w, h, line3d_kwargs.get("useCollinearity", True))
             if not os.path.exists(path):
                 raise RuntimeError("no segment cache %s (this flow reads no image files: segments come from a cache or the caller; pixels go through Line3D.add_image_pixels)" % path)
-            l3d.addImage_cached(i, w, h, path, intrinsics(cam["focal"], w, h), cam["R"], cam["t"], cam["worldpoints"])
+            m = mask_of(cam)
+            if not l3d.addImage_cached(i, w, h, path, intrinsics(cam["focal"], w, h), cam["R"], cam["t"], cam["worldpoints"], segment_mask=m) and m is not None:
+                raise RuntimeError("camera %d: %s" % (i, l3d.lib.l3d_line3d_last_error(l3d.h).decode()))      # (a mask of another size than the image, ...)
             continue
-        l3d.addImage(i, w, h, segments[i], intrinsics(cam["focal"], w, h), cam["R"], cam["t"], cam["worldpoints"])
+        m = mask_of(cam)
+        if not l3d.addImage(i, w, h, segments[i], intrinsics(cam["focal"], w, h), cam["R"], cam["t"], cam["worldpoints"], segment_mask=m) and m is not None:
+            raise RuntimeError("camera %d: %s" % (i, l3d.lib.l3d_line3d_last_error(l3d.h).decode()))
     l3d.compute3Dmodel(diffusion)
     if out_dir is not None:
         os.makedirs(out_dir, exist_ok=True)
