@@ -524,6 +524,14 @@ const char* l3d_profile_names(void);
  * [0] stage-1 pairs evaluated, [1] raw candidates (incl. existing), [2] verify inner iterations
  * (sum over segments of m^2), [3] kept matches */
 int l3d_last_stats(l3d_ctx* ctx, double stats[4]);
+/* the last resident chain of the context (l3d_match_chain, l3d_match_chain_resident and the ranged chains built on them): how many views were
+ * enqueued collecting their reverse matches by scanning their sources' records (k_exist_count / k_place) and through their sources' run tables
+ * (k_exist_count_rt + k_exist_combine / k_place_rt; options long_list, rt_g), counted where the chain decides.  A view the chain runs again
+ * after an overflow counts again. */
+int l3d_last_chain_routes(l3d_ctx* ctx, int* n_scanned, int* n_run_tables);
+/* the lanes that share a run on the run-table route, from option rt_g and the average run of the lists seen so far (tests; host only, no
+ * context): a power of two in [1, 64] whatever the option holds */
+int l3d_test_rt_lanes(int opt, double avg_run);
 
 /* contract math exported for tests (device evaluation of c_expf / c_acosf / c_acos) */
 int l3d_test_contract_math(l3d_ctx* ctx, const float* x, int n, float* out_expf, float* out_acosf, double* out_acos);
@@ -1422,6 +1430,10 @@ typedef struct l3d_test_verify_path {
     uint32_t kernels;               /* out */
     int32_t pad;
     const int32_t* seg_order;
+    const int32_t* exist_cams;      /* path 2: n_exist_cams local cameras, ascending, whose rows hold their candidates in ANY order: the window kernel */
+    int32_t n_exist_cams, pad2;     /* puts each (segment, camera) run into ascending target order before it verifies, as it does with reverse matches */
+    uint32_t* cand_meta_out;        /* out (NULL or R x 2, R x 4): the candidate arrays as the kernels left them */
+    float* cand_depths_out;
 } l3d_test_verify_path;
 int l3d_test_verify_candidates(l3d_ctx* ctx, int S, int N, const float* src_segs, const float* tgt_segs, int n_tgt, const int32_t* offsets, const float* P,
                                const float* RtKinv_src, const float* C_src, const int32_t* row_start, const uint32_t* cand_meta, const float* cand_depths, int R,
@@ -1498,6 +1510,83 @@ typedef struct l3d_test_products_path {
 int l3d_test_products(l3d_ctx* ctx, const l3d_chain_view* views, int n_views, const l3d_dense_map* map, const l3d_match* kept, const int32_t* n_kept,
                       const int64_t* n_candidates, const float* best, const int32_t* bestpos, l3d_test_products_path* sel,
                       l3d_chain_summary* summary, int64_t* n_pot);
+
+/* The step of the resident chain between stage 1 and the verification, on ONE view and on kept lists the caller hands in, exported for tests
+ * (tests/test_gpu_collect_paths.py): the reverse matches counted out of the earlier views' lists, the row scan, stage-1 rows and reverse matches merged
+ * into one candidate list in (segment, camera, target) order.  The lists go where a chain leaves them (arena, result records; side words and run tables
+ * made by the launchers the chains use for lists taken over), then the chain's own code for the step runs with the chain's own rules.
+ *   views, n_views   the schedule as l3d_test_products reads it: view_id, S_src (<= 16384), N (<= 255), local2global, n_tbm (0: never verified -- no list,
+ *                    no run table), to_be_matched, source_cam, source_index, n_sources; k: the view under test (n_tbm > 0)
+ *   kept, n_kept     the kept lists of the views [0, k) one after the other, GLOBAL camera ids, each in (segment, local camera) order; overflowed (NULL or
+ *                    one byte per view): the view's result record carries overflow bit 2 and n_kept = 0, as the writer leaves it; its records stay
+ *                    in the arena, unread
+ *   rowA, metaA, depthsA, n_A   view k's stage-1 rows: start per row (read for the cameras to be matched; gaps allowed), n_A candidates
+ *   rowcnt           S*N true stage-1 row counts (0 for cameras that are not to be matched)
+ * sel in:  route 0 = records scanned (k_exist_count / k_place), 1 = run tables (k_exist_count_rt + k_exist_combine / k_place_rt); rt_g = option rt_g for
+ *          this call; avg_kept = the average kept per view the chain's rules (workgroups per source, lanes per run) are fed with; cand_cap = the
+ *          candidate capacity the kernels guard, also the entries of cand_meta / cand_depths; sort_apart 1 = the separate sort launch runs.
+ * out:     row_start S*N + 1, cursor S*N (zeroed by the scan, advanced by the scatter), seg_order S, cand_meta cand_cap x 2 and cand_depths cand_cap x 4
+ *          (0xff bytes where no kernel wrote); sel->kernels (L3D_CK_*), g, bps (workgroups per source of the route taken), blocks_move, R.
+ * Refused with L3D_ERR_INVALID before anything is launched: sizes out of range, a source that is not an earlier view or whose camera is also to be
+ * matched, a record whose segment is past its view's, a list that is not ordered or names a camera that is no neighbour, a stage-1 row outside n_A, a
+ * stage-1 count for a camera that is not to be matched. */
+#define L3D_CK_EXIST_COUNT 1u
+#define L3D_CK_EXIST_COUNT_RT 2u /* k_exist_count_rt + k_exist_combine */
+#define L3D_CK_SCAN 4u
+#define L3D_CK_PLACE 8u
+#define L3D_CK_PLACE_RT 16u
+#define L3D_CK_SORT_RUNS 32u
+typedef struct l3d_test_collect_path {
+    int32_t route, rt_g, sort_apart, cand_cap;
+    double avg_kept;
+    const unsigned char* overflowed;
+    uint32_t kernels;                                   /* out */
+    int32_t g, bps, blocks_move, R, pad;                /* out */
+} l3d_test_collect_path;
+int l3d_test_collect_candidates(l3d_ctx* ctx, const l3d_chain_view* views, int n_views, int k, const l3d_match* kept, const int32_t* n_kept,
+                                const int32_t* rowA, const uint32_t* metaA, const float* depthsA, int n_A, const int32_t* rowcnt,
+                                l3d_test_collect_path* sel, int32_t* row_start, uint32_t* cand_meta, float* cand_depths, int32_t* cursor, int32_t* seg_order);
+
+/* The kept writer of the chains (k_kept_write_chain: records, side words, run table, best positions, result record) on ONE view's verified
+ * candidates, handed in by the caller, and the rebuild of side words and run tables from records (the launchers the chains use for lists taken
+ * over from another rank), exported for tests (tests/test_gpu_kept_write.py).  No chain runs; the product's own launchers do.
+ *   row_start S*N + 1, cand_meta R x (target, local camera), cand_depths R x 4, cand_conf R: as the verification leaves them
+ *   kept_cnt S            candidates of the segment with a confidence above 1 (checked on the host: the writer places a segment behind the
+ *                         counts in front of it)
+ *   local2global N        the view's neighbours
+ * sel in:  writer 0 = the chain's writer: the view's slice starts at prev_base + prev_n_kept when has_prev is set (the result record of the view
+ *          before it), at 0 otherwise; cand_cap and arena_cap are what the kernel guards (R > cand_cap: overflow bit 1; a slice that ends past
+ *          arena_cap records: bit 2, n_want = the view's count, n_kept = 0; nothing is written either way).  writer 1 = the per-view seam call's
+ *          writer behind the scan of kept_cnt: records only, from position 0; arena_cap must hold them.
+ *          jobs, n_jobs: lists to rebuild side words and run tables of afterwards, all in one launch -- records == NULL: the list the writer just
+ *          left (S, N, local2global of the call; n is filled in), else n records of the caller's with GLOBAL camera ids, any order.
+ * out:     records / side (arena_cap entries each: the whole arena, 0xff bytes where no kernel wrote), rt ((N + 1) x S, rows S apart; 0xff bytes likewise),
+ *          best_pos (S; 0x7f bytes where no kernel wrote, -1 being the writer's "no kept match"): what the writer left; side, rt and best_pos may be NULL with writer 1, which writes none of them.
+ *          sel->kept_base, n_kept, R, overflow, n_want: the result record (device and host-mapped copy are compared by the hook; writer 1: n_kept
+ *          is the scan's total, the rest 0).  Per job qt (n words) and rt ((N + 1) x S); sel->rebuild_err = the launch's error count (records whose
+ *          camera is no neighbour + descents of the (segment, camera) order), sel->rebuild_blocks = workgroups per job of the pass over the records.
+ * Refused with L3D_ERR_INVALID before anything is launched: N outside [1, 255], row_start not ascending from 0, a candidate whose camera is not its
+ * row's or whose target id does not fit 16 bits, kept_cnt that is not the count of confidences above 1, writer 1 with arena_cap below the total. */
+typedef struct l3d_test_kept_job {
+    const l3d_match* records;
+    const uint32_t* local2global;
+    uint32_t* qt;                   /* out */
+    int32_t* rt;                    /* out */
+    int32_t n, S, N, pad;
+} l3d_test_kept_job;
+typedef struct l3d_test_kept_path {
+    int32_t writer, has_prev;
+    uint64_t prev_base;
+    int32_t prev_n_kept, cand_cap;
+    uint64_t arena_cap;
+    l3d_test_kept_job* jobs;
+    int32_t n_jobs;
+    int32_t n_kept, R, overflow, n_want, rebuild_err, rebuild_blocks, pad;      /* out */
+    uint64_t kept_base;                                                          /* out */
+} l3d_test_kept_path;
+int l3d_test_kept_write(l3d_ctx* ctx, int S, int N, const int32_t* row_start, const uint32_t* cand_meta, const float* cand_depths, const float* cand_conf,
+                        const int32_t* kept_cnt, const uint32_t* local2global, l3d_test_kept_path* sel, l3d_match* records, uint32_t* side, int32_t* rt,
+                        int32_t* best_pos);
 
 #ifdef __cplusplus
 }

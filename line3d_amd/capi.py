@@ -450,6 +450,11 @@ def mask_segments_host(segments, mask, **kw):
     return segs, idx
 
 
+def rt_lanes(opt: int, avg_run: float) -> int:
+    """l3d_test_rt_lanes: the lanes that share a run on the chain's run-table route for option rt_g = opt -- host only, no context, no device"""
+    return int(load_library().l3d_test_rt_lanes(C.c_int(int(opt)), C.c_double(float(avg_run))))
+
+
 # dtype codes of l3d_device_image (L3D_U8 ...)
 U8, U16, F16, F32 = 0, 1, 2, 3
 _TYPESTR = {"|u1": U8, "<u2": U16, "<f2": F16, "<f4": F32}
@@ -610,7 +615,8 @@ def device_output_like(d, device_index=0):
 class VerifyPath(C.Structure):
     """l3d_test_verify_path (include/line3d_amd.h)"""
     _fields_ = [("path", C.c_int32), ("gb", C.c_int32), ("split_unit", C.c_int32), ("mmax", C.c_int32), ("wide_max", C.c_int32),
-                ("mmax_used", C.c_int32), ("kernels", C.c_uint32), ("pad", C.c_int32), ("seg_order", C.c_void_p)]
+                ("mmax_used", C.c_int32), ("kernels", C.c_uint32), ("pad", C.c_int32), ("seg_order", C.c_void_p),
+                ("exist_cams", C.c_void_p), ("n_exist_cams", C.c_int32), ("pad2", C.c_int32), ("cand_meta_out", C.c_void_p), ("cand_depths_out", C.c_void_p)]
 
 
 class PairPath(C.Structure):
@@ -642,6 +648,31 @@ class ProductsPath(C.Structure):
                 ("block_capacity", C.c_int32), ("side_arrays_used", C.c_int32), ("build", C.c_int32), ("refused", C.c_int32), ("n_blocks", C.c_int32),
                 ("max_touch", C.c_int32), ("early_cap", C.c_int32), ("early_g", C.c_int32),
                 ("block_cap", C.c_void_p), ("block_staged", C.c_void_p), ("block_g", C.c_void_p)]
+
+
+class CollectPath(C.Structure):
+    """l3d_test_collect_path (include/line3d_amd.h)"""
+    _fields_ = [("route", C.c_int32), ("rt_g", C.c_int32), ("sort_apart", C.c_int32), ("cand_cap", C.c_int32), ("avg_kept", C.c_double),
+                ("overflowed", C.c_void_p), ("kernels", C.c_uint32), ("g", C.c_int32), ("bps", C.c_int32), ("blocks_move", C.c_int32),
+                ("R", C.c_int32), ("pad", C.c_int32)]
+
+
+# L3D_CK_*: the kernels a test_collect_candidates call launched
+CK_EXIST_COUNT, CK_EXIST_COUNT_RT, CK_SCAN, CK_PLACE, CK_PLACE_RT, CK_SORT_RUNS = 1, 2, 4, 8, 16, 32
+
+
+class KeptJob(C.Structure):
+    """l3d_test_kept_job (include/line3d_amd.h)"""
+    _fields_ = [("records", C.c_void_p), ("local2global", C.c_void_p), ("qt", C.c_void_p), ("rt", C.c_void_p),
+                ("n", C.c_int32), ("S", C.c_int32), ("N", C.c_int32), ("pad", C.c_int32)]
+
+
+class KeptPath(C.Structure):
+    """l3d_test_kept_path (include/line3d_amd.h)"""
+    _fields_ = [("writer", C.c_int32), ("has_prev", C.c_int32), ("prev_base", C.c_uint64), ("prev_n_kept", C.c_int32), ("cand_cap", C.c_int32),
+                ("arena_cap", C.c_uint64), ("jobs", C.c_void_p), ("n_jobs", C.c_int32),
+                ("n_kept", C.c_int32), ("R", C.c_int32), ("overflow", C.c_int32), ("n_want", C.c_int32), ("rebuild_err", C.c_int32),
+                ("rebuild_blocks", C.c_int32), ("pad", C.c_int32), ("kept_base", C.c_uint64)]
 
 
 # l3d_test_products_path: build / refused
@@ -789,6 +820,12 @@ class Context:
         v = C.c_int(0)
         self._chk(self.lib.l3d_get_option(self.h, name.encode(), C.byref(v)))
         return v.value
+
+    def last_chain_routes(self):
+        """l3d_last_chain_routes: (views that scanned their sources' records, views that read their sources' run tables) of the last resident chain"""
+        a, b = C.c_int(0), C.c_int(0)
+        self._chk(self.lib.l3d_last_chain_routes(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def last_stats(self):
         s = (C.c_double * 4)()
@@ -1107,9 +1144,10 @@ class Context:
         return out
 
     def test_verify_candidates(self, src_segs, tgt_segs, offsets, P, RtKinv_src, C_src, row_start, cand_meta, cand_depths, sigma_p, sigma_a, spatial_k,
-                               path=0, gb=0, split_unit=0, mmax=0, wide_max=0, seg_order=None):
+                               path=0, gb=0, split_unit=0, mmax=0, wide_max=0, seg_order=None, exist_cams=None):
         """l3d_test_verify_candidates: stage 2 on a packed candidate list -> (conf (R,), kept_cnt (S,), best_depths (S, 2), mmax_used, kernels).
-        Nothing is checked here: a broken table is the library's to refuse."""
+        exist_cams (path 2): the local cameras whose rows are handed in unordered; the result then ends with cand_meta (R, 2) and cand_depths (R, 4)
+        as the kernels left them.  Nothing is checked here: a broken table is the library's to refuse."""
         f = lambda a: np.ascontiguousarray(a, dtype=np.float32)
         src_segs, tgt_segs, P, RtKinv_src, C_src, cand_depths = f(src_segs), f(tgt_segs), f(P), f(RtKinv_src), f(C_src), f(cand_depths)
         offsets, row_start = np.ascontiguousarray(offsets, dtype=np.int32), np.ascontiguousarray(row_start, dtype=np.int32)
@@ -1122,10 +1160,17 @@ class Context:
             assert seg_order.shape == (S,)
             sel.seg_order = seg_order.ctypes.data
         conf, kept, best = np.zeros(R, np.float32), np.zeros(S, np.int32), np.zeros((S, 2), np.float32)
+        if exist_cams is not None:
+            exist_cams = np.ascontiguousarray(exist_cams, dtype=np.int32)
+            meta_out, depths_out = np.zeros((R, 2), np.uint32), np.zeros((R, 4), np.float32)
+            sel.exist_cams, sel.n_exist_cams = exist_cams.ctypes.data, len(exist_cams)
+            sel.cand_meta_out, sel.cand_depths_out = meta_out.ctypes.data, depths_out.ctypes.data
         self._chk(self.lib.l3d_test_verify_candidates(self.h, C.c_int(S), C.c_int(N), _p(src_segs), _p(tgt_segs), C.c_int(n_tgt), _p(offsets), _p(P),
                                                       _p(RtKinv_src), _p(C_src), _p(row_start), _p(cand_meta), _p(cand_depths), C.c_int(R),
                                                       C.c_float(float(sigma_p)), C.c_float(float(sigma_a)), C.c_float(float(spatial_k)), C.byref(sel),
                                                       _p(conf), _p(kept), _p(best)))
+        if exist_cams is not None:
+            return conf, kept, best, int(sel.mmax_used), int(sel.kernels), meta_out, depths_out
         return conf, kept, best, int(sel.mmax_used), int(sel.kernels)
 
     def test_pair_candidates(self, src_segs, tgt_segs, offsets, F, RtKinv, centers, RtKinv_src, C_src, to_be_matched, path=0, pretest=3, spb=0,
@@ -1153,6 +1198,84 @@ class Context:
             raise
         out.update(total=int(sel.total), largest=int(sel.largest), spb_used=int(sel.spb_used), overflow=int(sel.overflow), needed=int(sel.needed))
         return out
+
+    def test_collect_candidates(self, views, k, rowA, metaA, depthsA, rowcnt, route=0, rt_g=-1, sort_apart=0, cand_cap=0, avg_kept=0.0, overflowed=None):
+        """l3d_test_collect_candidates: the collect step of the resident chain for view k of a schedule.  views: one dict per chain view, in chain
+        order -- id, S, l2g, n_tbm, tbm (cameras to be matched), source_cam, source_index, kept (MATCH_DTYPE, global camera ids; read for the views
+        in front of k).  -> dict(row_start, cand_meta (cand_cap, 2), cand_depths (cand_cap, 4), cursor, seg_order, kernels, g, bps, blocks_move, R).
+        Nothing is checked here: a broken table is the library's to refuse."""
+        n = len(views)
+        arr, keep = (ChainView * max(1, n))(), []
+        for j, v in enumerate(views):
+            l2g, tbm = np.ascontiguousarray(v["l2g"], dtype=np.uint32), np.ascontiguousarray(v["tbm"], dtype=np.int32)
+            sc, si = np.ascontiguousarray(v["source_cam"], dtype=np.int32), np.ascontiguousarray(v["source_index"], dtype=np.int32)
+            keep += [l2g, tbm, sc, si]
+            e = arr[j]
+            e.view_id, e.S_src, e.N, e.n_tbm, e.n_sources = int(v["id"]), int(v["S"]), len(l2g), int(v["n_tbm"]), len(sc)
+            e.local2global, e.to_be_matched, e.source_cam, e.source_index = l2g.ctypes.data, tbm.ctypes.data, sc.ctypes.data, si.ctypes.data
+        lists = [np.ascontiguousarray(v["kept"], dtype=MATCH_DTYPE) for v in views[:k]]
+        n_kept = np.array([len(a) for a in lists] + [0] * (n - k), np.int32)
+        kept_all = np.concatenate(lists) if lists else np.zeros(0, MATCH_DTYPE)
+        S, N = int(views[k]["S"]), len(views[k]["l2g"])
+        rowA, rowcnt = np.ascontiguousarray(rowA, dtype=np.int32), np.ascontiguousarray(rowcnt, dtype=np.int32)
+        metaA, depthsA = np.ascontiguousarray(metaA, dtype=np.uint32).reshape(-1, 2), np.ascontiguousarray(depthsA, dtype=np.float32).reshape(-1, 4)
+        assert rowA.shape == rowcnt.shape == (S * N,) and len(metaA) == len(depthsA)
+        sel = CollectPath()
+        sel.route, sel.rt_g, sel.sort_apart, sel.cand_cap, sel.avg_kept = int(route), int(rt_g), int(sort_apart), int(cand_cap), float(avg_kept)
+        ov = None if overflowed is None else np.ascontiguousarray(overflowed, dtype=np.uint8)
+        assert ov is None or len(ov) == n
+        sel.overflowed = None if ov is None else ov.ctypes.data
+        out = dict(row_start=np.zeros(S * N + 1, np.int32), cand_meta=np.zeros((int(cand_cap), 2), np.uint32), cand_depths=np.zeros((int(cand_cap), 4), np.float32),
+                   cursor=np.zeros(S * N, np.int32), seg_order=np.zeros(S, np.int32))
+        nz = lambda a: _p(a) if a.size else None
+        self._chk(self.lib.l3d_test_collect_candidates(self.h, arr, C.c_int(n), C.c_int(int(k)), nz(kept_all), _p(n_kept), nz(rowA), nz(metaA), nz(depthsA),
+                                                       C.c_int(len(metaA)), nz(rowcnt), C.byref(sel), _p(out["row_start"]), nz(out["cand_meta"]),
+                                                       nz(out["cand_depths"]), nz(out["cursor"]), nz(out["seg_order"])))
+        out.update(kernels=int(sel.kernels), g=int(sel.g), bps=int(sel.bps), blocks_move=int(sel.blocks_move), R=int(sel.R))
+        return out
+
+    def test_kept_write(self, N, row_start, cand_meta, cand_depths, cand_conf, kept_cnt, l2g, writer=0, prev=None, cand_cap=None, arena_cap=0, jobs=()):
+        """l3d_test_kept_write: the kept writer on one view's verified candidates, then (jobs) the rebuild of side words and run tables.
+        prev: None or (kept_base, n_kept) of the view before; cand_cap None: exactly R.  jobs: None = the list the writer just left, or a dict
+        records (MATCH_DTYPE, global camera ids), S, l2g.  -> dict(records (arena_cap,) MATCH_DTYPE, side (arena_cap,) uint32, rt (N + 1, S),
+        best_pos (S,), kept_base, n_kept, R, overflow, n_want, rebuild_err, rebuild_blocks, jobs = [dict(n, qt, rt)]); what no kernel wrote is
+        0xff bytes.  Nothing is checked here: a broken table is the library's to refuse."""
+        row_start = np.ascontiguousarray(row_start, dtype=np.int32)
+        cand_meta = np.ascontiguousarray(cand_meta, dtype=np.uint32).reshape(-1, 2)
+        cand_depths = np.ascontiguousarray(cand_depths, dtype=np.float32).reshape(-1, 4)
+        cand_conf = np.ascontiguousarray(cand_conf, dtype=np.float32)
+        kept_cnt, l2g = np.ascontiguousarray(kept_cnt, dtype=np.int32), np.ascontiguousarray(l2g, dtype=np.uint32)
+        S, R = len(kept_cnt), len(cand_conf)
+        assert row_start.shape == (S * N + 1,) and len(cand_meta) == R and len(cand_depths) == R and l2g.shape == (N,)
+        sel = KeptPath()
+        sel.writer, sel.has_prev = int(writer), 0 if prev is None else 1
+        if prev is not None:
+            sel.prev_base, sel.prev_n_kept = int(prev[0]), int(prev[1])
+        sel.cand_cap, sel.arena_cap = R if cand_cap is None else int(cand_cap), int(arena_cap)
+        cj = (KeptJob * max(1, len(jobs)))()
+        keep, outs = [], []
+        for i, j in enumerate(jobs):
+            if j is None:
+                n, jS, jN = int(kept_cnt.sum()), S, N
+            else:
+                recs = np.ascontiguousarray(j["records"], dtype=MATCH_DTYPE)
+                jl = np.ascontiguousarray(j["l2g"], dtype=np.uint32)
+                n, jS, jN = len(recs), int(j["S"]), len(jl)
+                keep += [recs, jl]
+                cj[i].records, cj[i].local2global = recs.ctypes.data, jl.ctypes.data
+            qt, rt = np.full(max(1, n), 0xffffffff, np.uint32), np.full((jN + 1, jS), -1, np.int32)
+            cj[i].qt, cj[i].rt, cj[i].n, cj[i].S, cj[i].N = qt.ctypes.data, rt.ctypes.data if rt.size else None, n, jS, jN
+            outs.append((qt, rt))
+        sel.jobs, sel.n_jobs = C.addressof(cj), len(jobs)
+        records = np.zeros(int(arena_cap), dtype=MATCH_DTYPE)
+        side = np.zeros(int(arena_cap), np.uint32)
+        rt, best_pos = np.zeros((N + 1, S), np.int32), np.zeros(S, np.int32)
+        nz = lambda a: _p(a) if a.size else None
+        self._chk(self.lib.l3d_test_kept_write(self.h, C.c_int(S), C.c_int(N), _p(row_start), nz(cand_meta), nz(cand_depths), nz(cand_conf), nz(kept_cnt), _p(l2g),
+                                               C.byref(sel), nz(records), nz(side), nz(rt), nz(best_pos)))
+        return dict(records=records, side=side, rt=rt, best_pos=best_pos, kept_base=int(sel.kept_base), n_kept=int(sel.n_kept), R=int(sel.R),
+                    overflow=int(sel.overflow), n_want=int(sel.n_want), rebuild_err=int(sel.rebuild_err), rebuild_blocks=int(sel.rebuild_blocks),
+                    jobs=[dict(n=int(cj[i].n), qt=outs[i][0][:int(cj[i].n)], rt=outs[i][1]) for i in range(len(jobs))])
 
     def chain_products_get(self, n_dense: int, n_pot: int, slack: int = 0):
         """l3d_chain_products_get: (pot_start int64 (n_dense + 1,), pot_tgt int32 (n_pot + slack,), best MATCH_DTYPE (n_dense,)).  The slots of

@@ -930,14 +930,21 @@ int l3d_test_verify_candidates(l3d_ctx* c, int S, int N, const float* src_segs, 
             seen[(size_t)y] = 1;
         }
     }
+    if (sel->n_exist_cams < 0 || (sel->n_exist_cams > 0 && (!sel->exist_cams || sel->path != 2)))
+        return fail(c, L3D_ERR_INVALID, "verify_candidates: exist_cams are the chain's (path 2)");
+    for (int i = 0; i < sel->n_exist_cams; ++i)
+        if (sel->exist_cams[i] < 0 || sel->exist_cams[i] >= N || (i > 0 && sel->exist_cams[i] <= sel->exist_cams[i - 1]))
+            return fail(c, L3D_ERR_INVALID, "verify_candidates: exist_cams must ascend inside [0, N)");
     if (S == 0) return L3D_OK;
 
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     const float4 *d_src = nullptr, *d_tgt = nullptr;
+    const int* d_exist = nullptr;
     int rc;
     if ((rc = to_device(c, c->src_segs, src_segs, (size_t)S * 16, &d_src))) return rc;
     if ((rc = to_device(c, c->tgt_segs, tgt_segs, (size_t)n_tgt * 16, &d_tgt))) return rc;
+    if (sel->n_exist_cams > 0 && (rc = to_device(c, c->tbm, sel->exist_cams, (size_t)sel->n_exist_cams * 4, &d_exist))) return rc;
     ChainViewDev d;                                     // the table block in the chains' terms: offsets | P | RtKinv_src | C_src
     d.src = d_src; d.tgt = d_tgt; d.s0 = 0; d.s1 = S;
     d.o_off = 0; d.o_P = (size_t)N * 8; d.o_Rs = d.o_P + (size_t)N * 48; d.o_Cs = d.o_Rs + 36;
@@ -994,7 +1001,7 @@ int l3d_test_verify_candidates(l3d_ctx* c, int S, int N, const float* src_segs, 
         }
         const int mode = c->verify_mode;
         c->verify_mode = 0;
-        chain_launch_verify(c, va, d, nullptr, 0, mmax, cand_cap, st, sel->mmax);
+        chain_launch_verify(c, va, d, d_exist, sel->n_exist_cams, mmax, cand_cap, st, sel->mmax);       // (exist_cams: runs the window kernel orders itself)
         c->verify_mode = mode;
     } else {
         if ((rc = seam_verify_args(c, va, d_src, d_tgt, reinterpret_cast<const int2*>(tb + d.o_off), reinterpret_cast<const float*>(tb + d.o_P),
@@ -1006,6 +1013,8 @@ int l3d_test_verify_candidates(l3d_ctx* c, int S, int N, const float* src_segs, 
     if (R) HIPCHK(c, hipMemcpyAsync(conf, c->cand_conf.p, (size_t)R * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipMemcpyAsync(kept_cnt, c->kept_cnt.p, (size_t)S * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipMemcpyAsync(best_depths, c->best.p, (size_t)S * 8, hipMemcpyDeviceToHost, st));
+    if (R && sel->cand_meta_out) HIPCHK(c, hipMemcpyAsync(sel->cand_meta_out, c->cand_meta.p, (size_t)R * 8, hipMemcpyDeviceToHost, st));
+    if (R && sel->cand_depths_out) HIPCHK(c, hipMemcpyAsync(sel->cand_depths_out, c->cand_depths.p, (size_t)R * 16, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, hipGetLastError());
     return L3D_OK;

@@ -42,9 +42,8 @@ namespace l3d {
 // reverse matches for view `view_id` out of the kept lists of earlier views (blockIdx.y = source): count per
 // (segment, camera) row.  (seg, tgt) swap roles and the depth pairs swap, line3D.cc:847-856.
 // Short lists -- config 2 keeps 36 k matches per view, 1.2 MB -- are scanned record by record: one pass over cache-resident data beats the run tables' extra
-// level of dependent loads (12.2 vs 12.9 ms per config-2 pass).  Once the views keep more than kLongList records each on average, the following views
-// read their sources' runs instead (k_exist_count_rt, k_place_rt), and the chain transposes the products' pairs itself (L3D_PROD_EARLY=1).
-constexpr int kLongList = 262144;
+// level of dependent loads (12.2 vs 12.9 ms per config-2 pass).  Once the views keep more than chain_long_list() records each on average (2^18; option
+// long_list), the following views read their sources' runs instead (k_exist_count_rt, k_place_rt), and the chain transposes the products' pairs itself (L3D_PROD_EARLY=1).
 __global__ void k_exist_count(const Match* __restrict__ arena, const ChainResult* __restrict__ res, const int* __restrict__ src_index,
                               const int* __restrict__ src_cam, unsigned view_id, int N, int S, int* __restrict__ rowcnt)
 {
@@ -66,6 +65,7 @@ __global__ void k_exist_count(const Match* __restrict__ arena, const ChainResult
 // 14 G/s whatever fed them (144 us per view at 40 x 4000 x 24, with or without the run tables).  A source's segments are cut into kExistChunks chunks; a
 // workgroup per (chunk, source) counts its runs' targets in LDS and leaves its S counters in `part`; k_exist_combine sums every (source, target segment)'s
 // chunk counts into the row count (and leaves the chunk bases, exclusive sums, in `part`).
+static thread_local unsigned t_collect_launched = 0;      // L3D_CK_*: the kernels the launchers below started on this host thread since the last reset (one OR per launch: l3d_test_collect_candidates reports it)
 constexpr int kExistChunks = 16;
 constexpr int kExistThreads = 1024;         // (sixteen waves per (chunk, source): a workgroup's critical path is its runs / waves dependent load pairs)
 __global__ __launch_bounds__(kExistThreads) void k_exist_count_rt(const unsigned* __restrict__ qt_arena, const RtInfo* __restrict__ info, const ChainResult* __restrict__ res,
@@ -202,14 +202,14 @@ __global__ __launch_bounds__(256) void k_kept_write_chain(VerifyArgs a, const in
 void launch_exist_count(const Match* arena, const ChainResult* res, const int* src_index, const int* src_cam, int n_src, unsigned view_id,
                         int N, int S, int* rowcnt, hipStream_t st, int bps)
 {
-    if (n_src > 0) hipLaunchKernelGGL(k_exist_count, dim3(std::max(1, bps), n_src), dim3(256), 0, st, arena, res, src_index, src_cam, view_id, N, S, rowcnt);
+    if (n_src > 0) { hipLaunchKernelGGL(k_exist_count, dim3(std::max(1, bps), n_src), dim3(256), 0, st, arena, res, src_index, src_cam, view_id, N, S, rowcnt); t_collect_launched |= L3D_CK_EXIST_COUNT; }
 }
 void launch_exist_sort_runs(const int* cams, int n_cams, int N, int S, const int* row_start, uint2* meta, float4* depths, int cap, hipStream_t st,
                             int seg_begin, int seg_end, float* stage, long long stage_stride, unsigned* stage_key)
 {
     if (seg_end < 0) seg_end = S;
     const int runs = (seg_end - seg_begin) * n_cams;
-    if (runs > 0) hipLaunchKernelGGL(k_exist_sort_runs, dim3((runs + 3) / 4), dim3(256), 0, st, cams, n_cams, N, S, seg_begin, seg_end, row_start, meta, depths, cap, stage, stage_stride, stage_key);
+    if (runs > 0) { hipLaunchKernelGGL(k_exist_sort_runs, dim3((runs + 3) / 4), dim3(256), 0, st, cams, n_cams, N, S, seg_begin, seg_end, row_start, meta, depths, cap, stage, stage_stride, stage_key); t_collect_launched |= L3D_CK_SORT_RUNS; }
 }
 void launch_place(const int* tbm, int n_tbm, int N, int S, const int* rowA, const uint2* metaA, const float4* depthsA,
                   const Match* arena, const ChainResult* res, const int* src_index, const int* src_cam, int n_src, unsigned view_id,
@@ -223,6 +223,7 @@ void launch_place(const int* tbm, int n_tbm, int N, int S, const int* rowA, cons
                                                          N, S, row_start, cursor, meta, depths, cand_cap, info, src_slot, std::max(1, g)); }
     else if (blocks > 0) hipLaunchKernelGGL(k_place, dim3(blocks), dim3(256), 0, st, blocks_move, bps, tbm, n_tbm, rowA, metaA, depthsA, arena, res, src_index, src_cam,
                                             view_id, N, S, row_start, cursor, meta, depths, cand_cap);
+    if (blocks > 0) t_collect_launched |= info ? L3D_CK_PLACE_RT : L3D_CK_PLACE;
 }
 void launch_exist_count_rt(const unsigned* qt_arena, const RtInfo* info, const ChainResult* res, const int* src_index, const int* src_cam, const int* src_slot, int n_src, int g,
                            int N, int S, int* rowcnt, int* part, hipStream_t st)
@@ -230,6 +231,7 @@ void launch_exist_count_rt(const unsigned* qt_arena, const RtInfo* info, const C
     if (n_src <= 0 || S <= 0) return;
     hipLaunchKernelGGL(k_exist_count_rt, dim3(kExistChunks, n_src), dim3(kExistThreads), (size_t)S * 4, st, qt_arena, info, res, src_index, src_slot, std::max(1, g), S, part);
     hipLaunchKernelGGL(k_exist_combine, dim3((S + 255) / 256, n_src), dim3(256), 0, st, part, src_cam, N, S, rowcnt);
+    t_collect_launched |= L3D_CK_EXIST_COUNT_RT;
 }
 int exist_chunks() { return kExistChunks; }
 void launch_kept_write_chain(const VerifyArgs& a, const int* kept_cnt, int nrow, const ChainResult* prev, unsigned long long arena_cap, ChainResult* res,
@@ -243,6 +245,98 @@ void launch_kept_write_chain(const VerifyArgs& a, const int* kept_cnt, int nrow,
 namespace {
 
 typedef l3d::ChainViewDev ViewDev;
+
+// Side words and run tables of lists that did not come out of the chain's kept writer, rebuilt from their records (l3d_runtable.hpp): jobs[i] names
+// the records, the outputs and the sizes, l2g[i] the list's neighbours (N global ids).  The neighbours sorted by id, their local numbers, the key
+// scratch and the error counter go into ch_rtjobs behind the job array; *bad = records whose camera is no neighbour + descents of the (segment,
+// camera) order, over all jobs.  Returns with the stream idle.
+int rebuild_run_tables(l3d_ctx* c, std::vector<RtJob>& jobs, const std::vector<const unsigned*>& l2g, hipStream_t st, int* bad, int* max_n_out = nullptr)
+{
+    *bad = 0;
+    if (max_n_out) *max_n_out = 0;
+    if (jobs.empty()) return L3D_OK;
+    std::vector<unsigned> ids;
+    std::vector<int> qs;
+    std::vector<size_t> at;
+    for (size_t i = 0; i < jobs.size(); ++i) {
+        std::vector<std::pair<unsigned, int>> byid;
+        for (int q = 0; q < jobs[i].N; ++q) byid.push_back({ l2g[i][q], q });
+        std::sort(byid.begin(), byid.end());
+        at.push_back(ids.size());
+        for (auto& e : byid) { ids.push_back(e.first); qs.push_back(e.second); }
+    }
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t o_ids = al(jobs.size() * sizeof(RtJob)), o_qs = o_ids + al(ids.size() * 4), o_err = o_qs + al(qs.size() * 4), o_key = o_err + 256;
+    size_t n_keys = 0;
+    for (const RtJob& j : jobs) n_keys += (size_t)j.n;
+    HIPCHK(c, c->ch_rtjobs.reserve(o_key + n_keys * 4 + 256));       // (not ch_stage: the taken-over records may live there)
+    unsigned char* sb = c->ch_rtjobs.as<unsigned char>();
+    int max_n = 0, max_cells = 0;
+    size_t ko = 0;
+    for (size_t i = 0; i < jobs.size(); ++i) {
+        jobs[i].ids = reinterpret_cast<const unsigned*>(sb + o_ids) + at[i]; jobs[i].qs = reinterpret_cast<const int*>(sb + o_qs) + at[i];
+        jobs[i].skey = reinterpret_cast<unsigned*>(sb + o_key) + ko; ko += (size_t)jobs[i].n;
+        max_n = std::max(max_n, jobs[i].n); max_cells = std::max(max_cells, (jobs[i].N + 1) * jobs[i].S);
+    }
+    HIPCHK(c, hipMemcpyAsync(sb, jobs.data(), jobs.size() * sizeof(RtJob), hipMemcpyHostToDevice, st));
+    if (!ids.empty()) {
+        HIPCHK(c, hipMemcpyAsync(sb + o_ids, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(sb + o_qs, qs.data(), qs.size() * 4, hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(c, hipMemsetAsync(sb + o_err, 0, 4, st));
+    launch_qt_from_records(reinterpret_cast<const RtJob*>(sb), (int)jobs.size(), max_n, reinterpret_cast<int*>(sb + o_err), st);
+    launch_rt_from_qt(reinterpret_cast<const RtJob*>(sb), (int)jobs.size(), max_cells, st);
+    HIPCHK(c, hipMemcpyAsync(bad, sb + o_err, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (max_n_out) *max_n_out = max_n;
+    return L3D_OK;
+}
+
+// One view's candidates collected on the chain's stream (run_chain per view; l3d_test_collect_candidates on crafted lists): its reverse matches counted
+// out of its sources' kept lists into the row counts stage 1 left (records scanned, or the sources' runs towards this view read through their run
+// tables), the combined row starts (+ zeroed scatter cursors, + the segments ordered longest first for the verification launch), stage-1 rows moved
+// and reverse matches scattered in one launch, and -- unless the window kernel orders them itself -- the runs put into target order.
+struct CollectIn {
+    const Match* arena; const ChainResult* dres; const unsigned* cams; const RtInfo* info;
+    const int *d_sc, *d_si, *d_ss, *d_tbm;          // source cameras, source views, this view's slot in each source's neighbour list, cameras to be matched (device)
+    int n_sources, n_tbm; unsigned view_id; int S, N;
+    int* rowcnt; const int* rowA; const uint2* metaA; const float4* depthsA;
+    size_t cand_cap; bool sort_apart;
+};
+void enqueue_collect(l3d_ctx* c, const CollectIn& in, const CollectRule& r, hipStream_t st)
+{
+    const int S = in.S, N = in.N;
+    if (r.rt) {
+        ProfScope p(c, "exist");
+        launch_exist_count_rt(in.cams, in.info, in.dres, in.d_si, in.d_sc, in.d_ss, in.n_sources, r.rt_g, N, S, in.rowcnt, c->ch_existpart.as<int>(), st);
+    } else {
+        ProfScope p(c, "exist");
+        launch_exist_count(in.arena, in.dres, in.d_si, in.d_sc, in.n_sources, in.view_id, N, S, in.rowcnt, st, r.bps);
+    }
+    { ProfScope p(c, "scan"); launch_scan(in.rowcnt, c->row_start.as<int>(), S * N, c->ch_cursor.as<int>(), st, c->ch_segorder.as<int>(), N, 0, S); t_collect_launched |= L3D_CK_SCAN; }
+    {
+        ProfScope p(c, "cand_move");
+        launch_place(in.d_tbm, in.n_tbm, N, S, in.rowA, in.metaA, in.depthsA, in.arena, in.dres, in.d_si, in.d_sc, in.n_sources, in.view_id,
+                     c->row_start.as<int>(), c->ch_cursor.as<int>(), (int)in.cand_cap, c->cand_meta.as<uint2>(), c->cand_depths.as<float4>(), st, r.rt ? r.rt_bps : r.bps,
+                     r.rt ? in.info : nullptr, in.d_ss, r.rt_g);
+    }
+    if (in.n_sources && in.sort_apart) {
+        ProfScope p(c, "exist");
+        launch_exist_sort_runs(in.d_sc, in.n_sources, N, S, c->row_start.as<int>(), c->cand_meta.as<uint2>(), c->cand_depths.as<float4>(), (int)in.cand_cap, st, 0, -1,
+                               c->vw_scratch.as<float>(), (long long)in.cand_cap + kVWSlack, c->cand_conf.as<unsigned>());
+    }
+}
+// the run tables' descriptors of every view of a schedule (rt[k]: null = none) and the room for the chunk counts of a view's sources, on `st`
+int upload_rtinfo(l3d_ctx* c, const l3d_chain_view* views, int n_views, const std::vector<const int*>& rt, int maxS, int maxN, hipStream_t st)
+{
+    std::vector<RtInfo>& info = c->rtinfo_host;     // (lives in the context: the upload is asynchronous)
+    info.resize((size_t)n_views);
+    for (int k = 0; k < n_views; ++k) info[(size_t)k] = RtInfo{ rt[(size_t)k], views[k].S_src, views[k].N };
+    HIPCHK(c, c->ch_rtinfo.reserve((size_t)n_views * sizeof(RtInfo) + 64));
+    HIPCHK(c, c->ch_existpart.reserve((size_t)std::max(1, maxN) * exist_chunks() * (size_t)std::max(1, maxS) * 4 + 256));     // chunk counts / bases of a view's sources
+    HIPCHK(c, hipMemcpyAsync(c->ch_rtinfo.p, info.data(), info.size() * sizeof(RtInfo), hipMemcpyHostToDevice, st));
+    return L3D_OK;
+}
 
 }  // namespace
 
@@ -263,6 +357,7 @@ int l3d::run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_cha
     if (!ranged) { k_begin = 0; k_end = n_views; }
     if (n_views < 0 || (n_views > 0 && (!views || (!cb && !map && !ranged))) || k_begin < 0 || k_end > n_views || k_begin > k_end) return fail(c, L3D_ERR_INVALID, "l3d_match_chain: bad argument");
     c->products.valid = false;
+    c->chain_routes[0] = c->chain_routes[1] = 0;
     if (n_views == 0) return L3D_OK;
     const double t_enter = now_s();
     HIPCHK(c, hipSetDevice(c->device));
@@ -288,12 +383,9 @@ int l3d::run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_cha
     // (ch_keptcam); later views and the products read runs instead of scanning lists
     if (int rc = chain_assign_arenas(c, views, n_views, vd, L, true, true, kRing, st, true)) return rc;
     {
-        std::vector<RtInfo>& info = c->rtinfo_host;     // (lives in the context: the upload is asynchronous)
-        info.resize((size_t)n_views);
-        for (int k = 0; k < n_views; ++k) info[(size_t)k] = RtInfo{ vd[(size_t)k].rt, views[k].S_src, views[k].N };
-        HIPCHK(c, c->ch_rtinfo.reserve((size_t)n_views * sizeof(RtInfo) + 64));
-        HIPCHK(c, c->ch_existpart.reserve((size_t)std::max(1, L.maxN) * exist_chunks() * (size_t)std::max(1, L.maxS) * 4 + 256));     // chunk counts / bases of a view's sources
-        HIPCHK(c, hipMemcpyAsync(c->ch_rtinfo.p, info.data(), info.size() * sizeof(RtInfo), hipMemcpyHostToDevice, st));
+        std::vector<const int*> rts((size_t)n_views);
+        for (int k = 0; k < n_views; ++k) rts[(size_t)k] = vd[(size_t)k].rt;
+        if (int rc = upload_rtinfo(c, views, n_views, rts, L.maxS, L.maxN, st)) return rc;
     }
     const unsigned char* dtab = L.dtab;
     const int maxN = L.maxN;
@@ -395,7 +487,7 @@ int l3d::run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_cha
     int early_batch = c->opt.prod_early == 3 ? 8 : 1;
     if (early && c->opt.prod_early == 1) {
         const double per_view = (same_scene && c->chain_seen_kept > 0 ? c->chain_seen_kept : pairs * 0.004) / std::max(1, n_views);
-        early = per_view > (double)kLongList;
+        early = per_view > (double)chain_long_list(c->opt);
     }
     int early_next = 0;                 // views [0, early_next) have their transposes launched
     hipStream_t sp = nullptr;
@@ -470,45 +562,19 @@ int l3d::run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_cha
         if (base > 0) {
             // the taken-over lists did not come out of this chain's kept writer: their side array and run tables are rebuilt from the records
             std::vector<RtJob> jobs;
-            std::vector<unsigned> ids;
-            std::vector<int> qs;
-            std::vector<size_t> at;
+            std::vector<const unsigned*> l2g;
             for (int k = pre->k0; k < pre->k1; ++k) {
                 if (!has_rec[(size_t)k] || hres[k].n_kept == 0) continue;
                 if (!vd[(size_t)k].rt) return fail(c, L3D_ERR_INVALID, "match_chain: view " + std::to_string(k) + " was taken over with records but has no run table");
-                std::vector<std::pair<unsigned, int>> byid;
-                for (int q = 0; q < views[k].N; ++q) byid.push_back({ views[k].local2global[q], q });
-                std::sort(byid.begin(), byid.end());
-                at.push_back(ids.size());
-                for (auto& e : byid) { ids.push_back(e.first); qs.push_back(e.second); }
                 RtJob j;
                 j.recs = c->ch_kept.as<Match>() + hres[k].kept_base; j.qt = c->ch_keptcam.as<unsigned>() + hres[k].kept_base; j.rt = vd[(size_t)k].rt;
                 j.ids = nullptr; j.qs = nullptr; j.n = hres[k].n_kept; j.S = views[k].S_src; j.N = views[k].N; j.pad = 0;
                 jobs.push_back(j);
+                l2g.push_back(views[k].local2global);
             }
             if (!jobs.empty()) {
-                auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-                const size_t o_ids = al(jobs.size() * sizeof(RtJob)), o_qs = o_ids + al(ids.size() * 4), o_err = o_qs + al(qs.size() * 4), o_key = o_err + 256;
-                size_t n_keys = 0;
-                for (const RtJob& j : jobs) n_keys += (size_t)j.n;
-                HIPCHK(c, c->ch_rtjobs.reserve(o_key + n_keys * 4 + 256));       // (not ch_stage: the taken-over records may live there)
-                unsigned char* sb = c->ch_rtjobs.as<unsigned char>();
-                int max_n = 0, max_cells = 0;
-                size_t ko = 0;
-                for (size_t i = 0; i < jobs.size(); ++i) {
-                    jobs[i].ids = reinterpret_cast<const unsigned*>(sb + o_ids) + at[i]; jobs[i].qs = reinterpret_cast<const int*>(sb + o_qs) + at[i];
-                    jobs[i].skey = reinterpret_cast<unsigned*>(sb + o_key) + ko; ko += (size_t)jobs[i].n;
-                    max_n = std::max(max_n, jobs[i].n); max_cells = std::max(max_cells, (jobs[i].N + 1) * jobs[i].S);
-                }
-                HIPCHK(c, hipMemcpyAsync(sb, jobs.data(), jobs.size() * sizeof(RtJob), hipMemcpyHostToDevice, st));
-                HIPCHK(c, hipMemcpyAsync(sb + o_ids, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, st));
-                HIPCHK(c, hipMemcpyAsync(sb + o_qs, qs.data(), qs.size() * 4, hipMemcpyHostToDevice, st));
-                HIPCHK(c, hipMemsetAsync(sb + o_err, 0, 4, st));
-                launch_qt_from_records(reinterpret_cast<const RtJob*>(sb), (int)jobs.size(), max_n, reinterpret_cast<int*>(sb + o_err), st);
-                launch_rt_from_qt(reinterpret_cast<const RtJob*>(sb), (int)jobs.size(), max_cells, st);
                 int bad = 0;
-                HIPCHK(c, hipMemcpyAsync(&bad, sb + o_err, 4, hipMemcpyDeviceToHost, st));
-                HIPCHK(c, hipStreamSynchronize(st));
+                if (int rc = rebuild_run_tables(c, jobs, l2g, st, &bad)) return rc;
                 if (bad) return fail(c, L3D_ERR_INVALID, "match_chain: the lists taken over from another rank are not ordered (segment, camera) -- no run tables");
             }
         }
@@ -571,35 +637,17 @@ int l3d::run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_cha
         (void)hipGetLastError();
         const int* d_si = reinterpret_cast<const int*>(dtab + d.o_si);
         unsigned* cams = c->ch_keptcam.as<unsigned>();
-        // workgroups per source view of the two scans of the sources' lists: a thread walks its stride of a list with dependent loads, so the list
-        // must be spread over enough of them -- 32 x 256 threads take config 2's 36 k records in 5 steps, but 3.5 M records (4000 x 24) in 430:
-        // sized from the lists the chain has seen so far (the host trails a few views behind)
-        const int bps = (int)std::min(512.0, std::max(32.0, (views_seen > 0 ? kept_seen / views_seen : 0.0) / 4096.0));
-        // run tables: g lanes per run (the average run of the lists seen so far, rounded up to a power of two), workgroups per source to cover its segments
-        const int* d_ss = reinterpret_cast<const int*>(dtab + d.o_ss);
-        const RtInfo* d_info = c->ch_rtinfo.as<RtInfo>();
-        const double avg_run = views_seen > 0 ? kept_seen / views_seen / std::max(1.0, (double)S * std::max(1, N)) : 1.0;
-        int rt_g = 1;
-        while (rt_g < 64 && rt_g < avg_run) rt_g <<= 1;
-        if (c->opt.rt_g > 0) rt_g = c->opt.rt_g;
-        const int rt_bps = std::max(1, std::min(512, (L.maxS * std::max(1, rt_g) + 255) / 256));
-        // short lists (config 2 keeps 36 k matches per view) are scanned record by record: k_exist_count
-        const bool rt_exist = views_seen > 0 && kept_seen / views_seen > (double)kLongList;
-        if (rt_exist) { ProfScope p(c, "exist"); launch_exist_count_rt(cams, d_info, dres, d_si, d_sc, d_ss, v.n_sources, rt_g, N, S, d.rowcnt, c->ch_existpart.as<int>(), st); }
-        else { ProfScope p(c, "exist"); launch_exist_count(arena, dres, d_si, d_sc, v.n_sources, v.view_id, N, S, d.rowcnt, st, bps); }
-        // combined row starts (+ zeroed scatter cursors, + the segments ordered longest first for the verification launch)
-        { ProfScope p(c, "scan"); launch_scan(d.rowcnt, c->row_start.as<int>(), (int)nrow, c->ch_cursor.as<int>(), st, c->ch_segorder.as<int>(), N, 0, S); }
-        {
-            ProfScope p(c, "cand_move");
-            launch_place(pa.tbm, v.n_tbm, N, S, d.rowA, ringA_meta(k), ringA_depths(k), arena, dres, d_si, d_sc, v.n_sources, v.view_id,
-                         c->row_start.as<int>(), c->ch_cursor.as<int>(), (int)cand_cap, c->cand_meta.as<uint2>(), c->cand_depths.as<float4>(), st, rt_exist ? rt_bps : bps,
-                         rt_exist ? d_info : nullptr, d_ss, rt_g);
-        }
-        if (v.n_sources && !(c->verify_mode == 0 && verify_window_supported(N))) {     // (the window kernel orders the runs itself)
-            ProfScope p(c, "exist");
-            launch_exist_sort_runs(d_sc, v.n_sources, N, S, c->row_start.as<int>(), c->cand_meta.as<uint2>(), c->cand_depths.as<float4>(), (int)cand_cap, st, 0, -1,
-                                   c->vw_scratch.as<float>(), (long long)cand_cap + kVWSlack, c->cand_conf.as<unsigned>());
-        }
+        // sized from the lists the chain has seen so far (the host trails a few views behind); short lists (config 2 keeps 36 k matches per view) are
+        // scanned record by record
+        const CollectRule rule = chain_collect_rule(c->opt, views_seen > 0, views_seen > 0 ? kept_seen / views_seen : 0.0, S, N, L.maxS);
+        const double avg_run = rule.avg_run;
+        ++c->chain_routes[rule.rt ? 1 : 0];
+        CollectIn ci;
+        ci.arena = arena; ci.dres = dres; ci.cams = cams; ci.info = c->ch_rtinfo.as<RtInfo>(); ci.d_sc = d_sc; ci.d_si = d_si;
+        ci.d_ss = reinterpret_cast<const int*>(dtab + d.o_ss); ci.d_tbm = pa.tbm; ci.n_sources = v.n_sources; ci.n_tbm = v.n_tbm; ci.view_id = v.view_id; ci.S = S; ci.N = N;
+        ci.rowcnt = d.rowcnt; ci.rowA = d.rowA; ci.metaA = ringA_meta(k); ci.depthsA = ringA_depths(k); ci.cand_cap = cand_cap;
+        ci.sort_apart = !(c->verify_mode == 0 && verify_window_supported(N));     // (the window kernel orders the runs itself)
+        enqueue_collect(c, ci, rule, st);
         VerifyArgs va = chain_verify_args(c, v, d, dtab, cand_cap);
         va.res = dres + k;
         // (fused row starts: no statistics -- the largest LDS image the budget allows)
@@ -884,6 +932,303 @@ extern "C" int l3d_match_chain_resident(l3d_ctx* c, const l3d_chain_view* views,
     if (!map || !map->view_ids || !map->seg_base || map->n_views < 0 || (n_views > 0 && !summary)) return fail(c, L3D_ERR_INVALID, "l3d_match_chain_resident: bad argument");
     if (n_pot) *n_pot = 0;
     return run_chain(c, views, n_views, nullptr, nullptr, map, summary, n_pot);
+}
+
+extern "C" int l3d_last_chain_routes(l3d_ctx* c, int* n_scanned, int* n_run_tables)
+{
+    if (!c || !n_scanned || !n_run_tables) return L3D_ERR_INVALID;
+    *n_scanned = c->chain_routes[0]; *n_run_tables = c->chain_routes[1];
+    return L3D_OK;
+}
+
+// host only: no context, no device
+extern "C" int l3d_test_rt_lanes(int opt, double avg_run) { return rt_lanes_per_run(opt, avg_run); }
+
+// One view's collect step on kept lists of the caller's (tests/test_gpu_collect_paths.py): everything is validated on the host, the lists go into the
+// arena with result records, side words and run tables (rebuild_run_tables), the outputs are filled with 0xff bytes, then enqueue_collect runs under
+// chain_collect_rule's numbers -- what run_chain does per view.
+extern "C" int l3d_test_collect_candidates(l3d_ctx* c, const l3d_chain_view* views, int n_views, int k, const l3d_match* kept, const int32_t* n_kept,
+                                           const int32_t* rowA, const uint32_t* metaA, const float* depthsA, int n_A, const int32_t* rowcnt,
+                                           l3d_test_collect_path* sel, int32_t* row_start, uint32_t* cand_meta, float* cand_depths, int32_t* cursor, int32_t* seg_order)
+{
+    if (!c) return L3D_ERR_INVALID;
+    if (!sel || !views || n_views < 1 || k < 0 || k >= n_views || !n_kept || !row_start || n_A < 0 || sel->cand_cap < 0 || (sel->route != 0 && sel->route != 1) ||
+        !(sel->avg_kept >= 0.0) || (sel->cand_cap > 0 && (!cand_meta || !cand_depths)) || (n_A > 0 && (!metaA || !depthsA)))
+        return fail(c, L3D_ERR_INVALID, "collect_candidates: bad argument");
+    const l3d_chain_view& v = views[k];
+    const int S = v.S_src, N = v.N;
+    if (S < 0 || S > 16384 || N < 1 || N > 255 || v.n_tbm < 1 || v.n_tbm > N || !v.to_be_matched || !v.local2global || v.n_sources < 0 ||
+        (v.n_sources && (!v.source_cam || !v.source_index)) || (S > 0 && (!rowA || !rowcnt || !cursor || !seg_order)))
+        return fail(c, L3D_ERR_INVALID, "collect_candidates: the view under test is not a verified view of at most 16384 segments and 255 neighbours");
+    std::vector<char> is_tbm((size_t)N, 0), is_src((size_t)N, 0);
+    for (int j = 0; j < v.n_tbm; ++j) {
+        const int cam = v.to_be_matched[j];
+        if (cam < 0 || cam >= N || is_tbm[(size_t)cam]) return fail(c, L3D_ERR_INVALID, "collect_candidates: to_be_matched out of range or repeated");
+        is_tbm[(size_t)cam] = 1;
+    }
+    for (int q = 0; q < v.n_sources; ++q) {
+        const int cam = v.source_cam[q], si = v.source_index[q];
+        if (si < 0 || si >= k || cam < 0 || cam >= N || is_tbm[(size_t)cam] || is_src[(size_t)cam])
+            return fail(c, L3D_ERR_INVALID, "collect_candidates: a source must be an earlier view, its camera a neighbour that is not to be matched, named once");
+        is_src[(size_t)cam] = 1;
+    }
+    size_t n_rec = 0, rt_ints = 0;
+    int maxS = S, maxN = std::max(N, v.n_sources);
+    for (int j = 0; j < k; ++j) {
+        const l3d_chain_view& w = views[j];
+        if (w.S_src < 0 || w.S_src > 65536 || w.N < 0 || w.N > 255 || n_kept[j] < 0 || (w.N > 0 && !w.local2global) || (w.n_tbm <= 0 && n_kept[j] != 0) || (n_kept[j] > 0 && (!kept || w.N < 1)))
+            return fail(c, L3D_ERR_INVALID, "collect_candidates: an earlier view's sizes are out of range, or a view that was never verified has records");
+        for (int i = 0; i < n_kept[j]; ++i)
+            if (kept[n_rec + (size_t)i].segID1 >= (unsigned)w.S_src) return fail(c, L3D_ERR_INVALID, "collect_candidates: a record's segment is past its view's");
+        n_rec += (size_t)n_kept[j];
+        if (w.n_tbm > 0) rt_ints += (((size_t)w.N + 1) * w.S_src + 3) & ~(size_t)3;
+        maxS = std::max(maxS, w.S_src); maxN = std::max(maxN, w.N);
+    }
+    if (n_rec >= (1u << 30)) return fail(c, L3D_ERR_INVALID, "collect_candidates: too many records");
+    const size_t nrow = (size_t)S * N;
+    for (size_t row = 0; row < nrow; ++row) {
+        const bool tbm = is_tbm[row % (size_t)N] != 0;
+        if (rowcnt[row] < 0 || (!tbm && rowcnt[row] != 0)) return fail(c, L3D_ERR_INVALID, "collect_candidates: a stage-1 count below 0, or above 0 for a camera that is not to be matched");
+        if (tbm && (rowA[row] < 0 || (long long)rowA[row] + rowcnt[row] > n_A)) return fail(c, L3D_ERR_INVALID, "collect_candidates: a stage-1 row outside the stage-1 candidates");
+    }
+    sel->kernels = 0; sel->g = sel->bps = sel->blocks_move = sel->R = 0;
+
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    (void)hipGetLastError();
+    struct OptionsBack { l3d_ctx* c; Options o; ~OptionsBack() { c->opt = o; } } back{ c, c->opt };
+    c->opt.rt_g = sel->rt_g;
+    const size_t cap = (size_t)sel->cand_cap, ccap = std::max<size_t>(cap, 1);
+    // ---- the earlier views' lists where a chain leaves them
+    HIPCHK(c, c->ch_kept.reserve(n_rec * sizeof(Match) + 64)); HIPCHK(c, c->ch_keptcam.reserve(n_rec * 4 + 64));
+    HIPCHK(c, c->ch_rt.reserve(rt_ints * 4 + 64)); HIPCHK(c, c->ch_res.reserve((size_t)n_views * sizeof(ChainResult) + 16));
+    if (n_rec) HIPCHK(c, hipMemcpyAsync(c->ch_kept.p, kept, n_rec * sizeof(Match), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemsetAsync(c->ch_keptcam.p, 0xff, n_rec * 4 + 64, st));
+    HIPCHK(c, hipMemsetAsync(c->ch_rt.p, 0xff, rt_ints * 4 + 64, st));
+    std::vector<ChainResult> res((size_t)n_views);
+    std::vector<const int*> rts((size_t)n_views, nullptr);
+    std::vector<RtJob> jobs;
+    std::vector<const unsigned*> l2g;
+    {
+        size_t ro = 0, to = 0;
+        for (int j = 0; j < n_views; ++j) {
+            ChainResult& r = res[(size_t)j];
+            memset(&r, 0, sizeof(r));
+            if (j >= k) continue;
+            const l3d_chain_view& w = views[j];
+            const bool over = sel->overflowed && sel->overflowed[j];
+            r.kept_base = ro; r.n_kept = over ? 0 : n_kept[j]; r.overflow = over ? 2 : 0; r.n_want = over ? n_kept[j] : 0;
+            if (w.n_tbm > 0) {
+                rts[(size_t)j] = c->ch_rt.as<int>() + to;
+                if (n_kept[j] > 0) {        // (an overflowed view's tables too: stale ones are what a chain would hold -- its n_kept = 0 must keep every reader out)
+                    RtJob jb;
+                    memset(&jb, 0, sizeof(jb));
+                    jb.recs = c->ch_kept.as<Match>() + ro; jb.qt = c->ch_keptcam.as<unsigned>() + ro; jb.rt = c->ch_rt.as<int>() + to; jb.n = n_kept[j]; jb.S = w.S_src; jb.N = w.N;
+                    jobs.push_back(jb); l2g.push_back(w.local2global);
+                } else if (w.S_src > 0) HIPCHK(c, hipMemsetAsync(c->ch_rt.as<int>() + to, 0, ((size_t)w.N + 1) * w.S_src * 4, st));     // (an empty list: every run starts and ends at 0)
+                to += (((size_t)w.N + 1) * w.S_src + 3) & ~(size_t)3;
+            }
+            ro += (size_t)n_kept[j];
+        }
+    }
+    int bad = 0;
+    if (int rc = rebuild_run_tables(c, jobs, l2g, st, &bad)) return rc;
+    if (bad) return fail(c, L3D_ERR_INVALID, "collect_candidates: a list is not in (segment, camera) order or names a camera that is no neighbour");
+    HIPCHK(c, hipMemcpyAsync(c->ch_res.p, res.data(), res.size() * sizeof(ChainResult), hipMemcpyHostToDevice, st));
+    if (int rc = upload_rtinfo(c, views, n_views, rts, maxS, maxN, st)) return rc;
+    // ---- view k: its tables (cameras to be matched | source cameras | source views | its slot in each source's list), stage-1 rows and counts
+    std::vector<int> tab;
+    tab.insert(tab.end(), v.to_be_matched, v.to_be_matched + v.n_tbm);
+    const size_t o_sc = tab.size();
+    if (v.n_sources) tab.insert(tab.end(), v.source_cam, v.source_cam + v.n_sources);
+    const size_t o_si = tab.size();
+    if (v.n_sources) tab.insert(tab.end(), v.source_index, v.source_index + v.n_sources);
+    const size_t o_ss = tab.size();
+    for (int q = 0; q < v.n_sources; ++q) tab.push_back(chain_source_slot(views, v, q));
+    HIPCHK(c, c->tables.reserve(tab.size() * 4 + 16));
+    HIPCHK(c, hipMemcpyAsync(c->tables.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, st));
+    const int* dt = c->tables.as<int>();
+    ChainLayout L;
+    L.maxS = S; L.maxN = N;
+    if (int rc = chain_reserve_candidates(c, L, ccap, 0)) return rc;
+    HIPCHK(c, c->rowcnt.reserve(nrow * 4 + 16)); HIPCHK(c, c->ch_rowA.reserve(nrow * 4 + 16));
+    HIPCHK(c, c->ch_ringA_meta.reserve((size_t)std::max(n_A, 1) * 8)); HIPCHK(c, c->ch_ringA_depths.reserve((size_t)std::max(n_A, 1) * 16));
+    HIPCHK(c, c->row_start.reserve((nrow + 1) * 4)); HIPCHK(c, c->ch_cursor.reserve(nrow * 4 + 16)); HIPCHK(c, c->ch_segorder.reserve((size_t)S * 4 + 16));
+    if (nrow) {
+        HIPCHK(c, hipMemcpyAsync(c->rowcnt.p, rowcnt, nrow * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(c->ch_rowA.p, rowA, nrow * 4, hipMemcpyHostToDevice, st));
+    }
+    if (n_A) {
+        HIPCHK(c, hipMemcpyAsync(c->ch_ringA_meta.p, metaA, (size_t)n_A * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(c->ch_ringA_depths.p, depthsA, (size_t)n_A * 16, hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(c, hipMemsetAsync(c->row_start.p, 0xff, (nrow + 1) * 4, st));
+    HIPCHK(c, hipMemsetAsync(c->ch_cursor.p, 0xff, nrow * 4 + 16, st));
+    HIPCHK(c, hipMemsetAsync(c->ch_segorder.p, 0xff, (size_t)S * 4 + 16, st));
+    HIPCHK(c, hipMemsetAsync(c->cand_meta.p, 0xff, ccap * 8, st));
+    HIPCHK(c, hipMemsetAsync(c->cand_depths.p, 0xff, ccap * 16, st));
+
+    CollectRule rule = chain_collect_rule(c->opt, true, sel->avg_kept, S, N, maxS);
+    rule.rt = sel->route == 1;                          // (the route is the caller's; everything else the chain's rule)
+    CollectIn ci;
+    ci.arena = c->ch_kept.as<Match>(); ci.dres = c->ch_res.as<ChainResult>(); ci.cams = c->ch_keptcam.as<unsigned>(); ci.info = c->ch_rtinfo.as<RtInfo>();
+    ci.d_tbm = dt; ci.d_sc = dt + o_sc; ci.d_si = dt + o_si; ci.d_ss = dt + o_ss; ci.n_sources = v.n_sources; ci.n_tbm = v.n_tbm; ci.view_id = v.view_id; ci.S = S; ci.N = N;
+    ci.rowcnt = c->rowcnt.as<int>(); ci.rowA = c->ch_rowA.as<int>(); ci.metaA = c->ch_ringA_meta.as<uint2>(); ci.depthsA = c->ch_ringA_depths.as<float4>();
+    ci.cand_cap = cap; ci.sort_apart = sel->sort_apart != 0;
+    t_collect_launched = 0;
+    enqueue_collect(c, ci, rule, st);
+    sel->kernels = t_collect_launched; sel->g = rule.rt_g; sel->bps = rule.rt ? rule.rt_bps : rule.bps; sel->blocks_move = (S * v.n_tbm + 3) / 4;
+    HIPCHK(c, hipMemcpyAsync(row_start, c->row_start.p, (nrow + 1) * 4, hipMemcpyDeviceToHost, st));
+    if (nrow) HIPCHK(c, hipMemcpyAsync(cursor, c->ch_cursor.p, nrow * 4, hipMemcpyDeviceToHost, st));
+    if (S) HIPCHK(c, hipMemcpyAsync(seg_order, c->ch_segorder.p, (size_t)S * 4, hipMemcpyDeviceToHost, st));
+    if (cap) {
+        HIPCHK(c, hipMemcpyAsync(cand_meta, c->cand_meta.p, cap * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(cand_depths, c->cand_depths.p, cap * 16, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, hipGetLastError());
+    sel->R = row_start[nrow];
+    return L3D_OK;
+}
+
+// The kept writers and the rebuild of side words and run tables on one view's candidates of the caller's (tests/test_gpu_kept_write.py): everything is
+// validated on the host, the arena and every output are filled with 0xff bytes, then the product's launchers run -- launch_kept_write_chain, or
+// launch_scan + launch_kept_write, and rebuild_run_tables (what run_chain calls for lists taken over).
+extern "C" int l3d_test_kept_write(l3d_ctx* c, int S, int N, const int32_t* row_start, const uint32_t* cand_meta, const float* cand_depths, const float* cand_conf,
+                                   const int32_t* kept_cnt, const uint32_t* local2global, l3d_test_kept_path* sel, l3d_match* records, uint32_t* side, int32_t* rt,
+                                   int32_t* best_pos)
+{
+    if (!c) return L3D_ERR_INVALID;
+    if (!sel || S < 0 || N < 1 || N > 255 || !row_start || !local2global || (S > 0 && !kept_cnt) || (sel->writer != 0 && sel->writer != 1) || sel->n_jobs < 0 ||
+        (sel->n_jobs > 0 && !sel->jobs) || sel->cand_cap < 0 || (sel->has_prev && sel->prev_n_kept < 0))
+        return fail(c, L3D_ERR_INVALID, "kept_write: bad argument");
+    if ((long long)S * (N + 1) >= 0x7fffffffll || sel->arena_cap >= (1ull << 31) || (sel->has_prev && sel->prev_base >= (1ull << 40))) return fail(c, L3D_ERR_INVALID, "kept_write: too many rows or records");
+    const size_t nrow = (size_t)S * N, acap = (size_t)sel->arena_cap;
+    if (sel->writer == 0 && S > 0 && (!side || !rt || !best_pos)) return fail(c, L3D_ERR_INVALID, "kept_write: the chain's writer needs side, rt and best_pos");
+    if (acap > 0 && (!records || (sel->writer == 0 && !side))) return fail(c, L3D_ERR_INVALID, "kept_write: no room for the arena");
+    if (row_start[0] != 0) return fail(c, L3D_ERR_INVALID, "kept_write: row_start must start at 0");
+    for (size_t i = 0; i < nrow; ++i) if (row_start[i + 1] < row_start[i]) return fail(c, L3D_ERR_INVALID, "kept_write: row_start does not ascend");
+    const int R = row_start[nrow];
+    if (R > 0 && (!cand_meta || !cand_depths || !cand_conf)) return fail(c, L3D_ERR_INVALID, "kept_write: candidates missing");
+    long long total = 0;
+    for (int y = 0; y < S; ++y) {
+        int kept = 0;
+        for (int q = 0; q < N; ++q)
+            for (int r = row_start[(size_t)y * N + q]; r < row_start[(size_t)y * N + q + 1]; ++r) {
+                if (cand_meta[2 * (size_t)r + 1] != (unsigned)q) return fail(c, L3D_ERR_INVALID, "kept_write: a candidate's camera is not its row's");
+                if (cand_meta[2 * (size_t)r] >= 65536u) return fail(c, L3D_ERR_INVALID, "kept_write: a target id does not fit 16 bits");
+                kept += cand_conf[r] > 1.0f ? 1 : 0;
+            }
+        if (kept_cnt[y] != kept) return fail(c, L3D_ERR_INVALID, "kept_write: kept_cnt of segment " + std::to_string(y) + " is not its count of confidences above 1");
+        total += kept;
+    }
+    if (sel->writer == 1 && (unsigned long long)total > sel->arena_cap) return fail(c, L3D_ERR_INVALID, "kept_write: the seam writer needs room for " + std::to_string(total) + " records");
+    size_t job_recs = 0, job_cells = 0;
+    for (int i = 0; i < sel->n_jobs; ++i) {
+        const l3d_test_kept_job& j = sel->jobs[i];
+        if (!j.records) { if (sel->writer != 0) return fail(c, L3D_ERR_INVALID, "kept_write: only the chain's writer leaves a list to rebuild"); job_recs += (size_t)total; job_cells += (size_t)(N + 1) * S; continue; }
+        if (j.n < 0 || j.S < 0 || j.N < 1 || j.N > 255 || !j.local2global || (long long)j.S * (j.N + 1) >= 0x7fffffffll || (j.n > 0 && !j.qt) || (j.S > 0 && !j.rt))
+            return fail(c, L3D_ERR_INVALID, "kept_write: bad rebuild job");
+        job_recs += (size_t)j.n; job_cells += (size_t)(j.N + 1) * j.S;
+    }
+    sel->n_kept = sel->R = sel->overflow = sel->n_want = sel->rebuild_err = sel->rebuild_blocks = 0; sel->kept_base = 0;
+
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    (void)hipGetLastError();
+    const size_t rcap = (size_t)std::max(R, 1);
+    HIPCHK(c, c->row_start.reserve((nrow + 1) * 4));
+    HIPCHK(c, c->cand_meta.reserve(rcap * 8)); HIPCHK(c, c->cand_depths.reserve(rcap * 16)); HIPCHK(c, c->cand_conf.reserve(rcap * 4));
+    HIPCHK(c, c->kept_cnt.reserve((size_t)S * 4 + 4)); HIPCHK(c, c->kept_start.reserve((size_t)S * 4 + 8));
+    HIPCHK(c, c->l2g.reserve((size_t)N * 4));
+    HIPCHK(c, c->ch_kept.reserve(acap * sizeof(Match) + 64)); HIPCHK(c, c->ch_keptcam.reserve(acap * 4 + 64));
+    HIPCHK(c, c->ch_rt.reserve((size_t)(N + 1) * S * 4 + 64)); HIPCHK(c, c->ch_bestpos.reserve((size_t)S * 4 + 64));
+    HIPCHK(c, c->ch_res.reserve(2 * sizeof(ChainResult))); HIPCHK(c, c->ch_pin_res.reserve(sizeof(ChainResult)));
+    HIPCHK(c, hipMemcpyAsync(c->row_start.p, row_start, (nrow + 1) * 4, hipMemcpyHostToDevice, st));
+    if (R) {
+        HIPCHK(c, hipMemcpyAsync(c->cand_meta.p, cand_meta, (size_t)R * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(c->cand_depths.p, cand_depths, (size_t)R * 16, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(c->cand_conf.p, cand_conf, (size_t)R * 4, hipMemcpyHostToDevice, st));
+    }
+    if (S) HIPCHK(c, hipMemcpyAsync(c->kept_cnt.p, kept_cnt, (size_t)S * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->l2g.p, local2global, (size_t)N * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemsetAsync(c->ch_kept.p, 0xff, acap * sizeof(Match) + 64, st));
+    HIPCHK(c, hipMemsetAsync(c->ch_keptcam.p, 0xff, acap * 4 + 64, st));
+    HIPCHK(c, hipMemsetAsync(c->ch_rt.p, 0xff, (size_t)(N + 1) * S * 4 + 64, st));
+    HIPCHK(c, hipMemsetAsync(c->ch_bestpos.p, 0x7f, (size_t)S * 4 + 64, st));          // (-1 is an answer of the writer's: no kept match)
+    ChainResult* dres = c->ch_res.as<ChainResult>();
+    ChainResult* hres = c->ch_pin_res.as<ChainResult>();
+    ChainResult prev;
+    prev.kept_base = sel->prev_base; prev.n_kept = sel->prev_n_kept; prev.R = 0; prev.overflow = 0; prev.n_want = 0;
+    HIPCHK(c, hipMemsetAsync(dres, 0xff, 2 * sizeof(ChainResult), st));
+    if (sel->has_prev) HIPCHK(c, hipMemcpyAsync(dres, &prev, sizeof(ChainResult), hipMemcpyHostToDevice, st));
+    memset(hres, 0xff, sizeof(ChainResult));
+    ChainResult* hres_dev = nullptr;
+    HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&hres_dev), hres, 0));
+
+    VerifyArgs va;
+    memset(&va, 0, sizeof(va));
+    va.row_start = c->row_start.as<int>(); va.cand_meta = c->cand_meta.as<uint2>(); va.cand_depths = c->cand_depths.as<float4>(); va.cand_conf = c->cand_conf.as<float>();
+    va.N = N; va.seg_begin = 0; va.seg_end = S; va.nrow_total = (int)nrow; va.cand_cap = sel->cand_cap; va.only_above = -1;
+    ChainResult got;
+    memset(&got, 0, sizeof(got));
+    if (sel->writer == 0) {
+        ProfScope p(c, "kept_write");
+        launch_kept_write_chain(va, c->kept_cnt.as<int>(), (int)nrow, sel->has_prev ? dres : nullptr, (unsigned long long)sel->arena_cap, dres + 1, hres_dev, c->l2g.as<unsigned>(),
+                                c->ch_kept.as<Match>(), st, c->ch_bestpos.as<int>(), c->ch_keptcam.as<unsigned>(), c->ch_rt.as<int>(), S);
+    } else {
+        { ProfScope p(c, "scan"); launch_scan(c->kept_cnt.as<int>(), c->kept_start.as<int>(), S, nullptr, st); }
+        { ProfScope p(c, "kept_write"); launch_kept_write(va, c->kept_start.as<int>(), c->l2g.as<unsigned>(), c->ch_kept.as<Match>(), st); }
+    }
+    if (sel->writer == 0) HIPCHK(c, hipMemcpyAsync(&got, dres + 1, sizeof(ChainResult), hipMemcpyDeviceToHost, st));
+    else HIPCHK(c, hipMemcpyAsync(&got.n_kept, c->kept_start.as<int>() + S, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, hipGetLastError());
+    if (sel->writer == 0 && memcmp(&got, hres, sizeof(ChainResult)) != 0) return fail(c, L3D_ERR_INVALID, "kept_write: the device and the host-mapped result record differ");
+    if (sel->writer == 1) got.R = R;
+    sel->kept_base = got.kept_base; sel->n_kept = got.n_kept; sel->R = got.R; sel->overflow = got.overflow; sel->n_want = got.n_want;
+    if (acap) HIPCHK(c, hipMemcpyAsync(records, c->ch_kept.p, acap * sizeof(Match), hipMemcpyDeviceToHost, st));
+    if (acap && side) HIPCHK(c, hipMemcpyAsync(side, c->ch_keptcam.p, acap * 4, hipMemcpyDeviceToHost, st));
+    if (S && rt) HIPCHK(c, hipMemcpyAsync(rt, c->ch_rt.p, (size_t)(N + 1) * S * 4, hipMemcpyDeviceToHost, st));
+    if (S && best_pos) HIPCHK(c, hipMemcpyAsync(best_pos, c->ch_bestpos.p, (size_t)S * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+
+    if (sel->n_jobs > 0) {
+        // crafted records | every job's side words | every job's run table: apart from what the writer left
+        HIPCHK(c, c->g0.reserve(job_recs * sizeof(Match) + 64)); HIPCHK(c, c->g1.reserve(job_recs * 4 + 64)); HIPCHK(c, c->g2.reserve(job_cells * 4 + 64));
+        HIPCHK(c, hipMemsetAsync(c->g1.p, 0xff, job_recs * 4 + 64, st));
+        HIPCHK(c, hipMemsetAsync(c->g2.p, 0xff, job_cells * 4 + 64, st));
+        std::vector<RtJob> jobs((size_t)sel->n_jobs);
+        std::vector<const unsigned*> l2g((size_t)sel->n_jobs);
+        size_t ro = 0, co = 0;
+        for (int i = 0; i < sel->n_jobs; ++i) {
+            l3d_test_kept_job& tj = sel->jobs[i];
+            RtJob& j = jobs[(size_t)i];
+            memset(&j, 0, sizeof(j));
+            if (!tj.records) {
+                tj.n = got.n_kept; tj.S = S; tj.N = N;
+                j.recs = c->ch_kept.as<Match>() + got.kept_base; l2g[(size_t)i] = local2global;
+            } else {
+                j.recs = c->g0.as<Match>() + ro; l2g[(size_t)i] = tj.local2global;
+                if (tj.n) HIPCHK(c, hipMemcpyAsync(c->g0.as<Match>() + ro, tj.records, (size_t)tj.n * sizeof(Match), hipMemcpyHostToDevice, st));
+            }
+            j.qt = c->g1.as<unsigned>() + ro; j.rt = c->g2.as<int>() + co; j.n = tj.n; j.S = tj.S; j.N = tj.N;
+            ro += (size_t)tj.n; co += (size_t)(tj.N + 1) * tj.S;
+        }
+        int bad = 0, max_n = 0;
+        if (int rc = rebuild_run_tables(c, jobs, l2g, st, &bad, &max_n)) return rc;
+        HIPCHK(c, hipGetLastError());
+        sel->rebuild_err = bad; sel->rebuild_blocks = max_n > 0 ? qt_from_records_blocks(max_n) : 0;
+        for (int i = 0; i < sel->n_jobs; ++i) {
+            const l3d_test_kept_job& tj = sel->jobs[i];
+            const RtJob& j = jobs[(size_t)i];
+            if (tj.n && tj.qt) HIPCHK(c, hipMemcpyAsync(tj.qt, j.qt, (size_t)tj.n * 4, hipMemcpyDeviceToHost, st));
+            if (tj.S && tj.rt) HIPCHK(c, hipMemcpyAsync(tj.rt, j.rt, (size_t)(tj.N + 1) * tj.S * 4, hipMemcpyDeviceToHost, st));
+        }
+        HIPCHK(c, hipStreamSynchronize(st));
+    }
+    HIPCHK(c, hipGetLastError());
+    return L3D_OK;
 }
 
 void l3d::warm_chain() { touch_kernel(reinterpret_cast<const void*>(&k_exist_count)); }

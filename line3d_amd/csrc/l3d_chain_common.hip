@@ -109,10 +109,11 @@ __global__ __launch_bounds__(256) void k_rt_from_qt(const RtJob* __restrict__ jo
         j.rt[c] = lo;
     }
 }
+int qt_from_records_blocks(int max_n) { return std::max(1, std::min(512, (max_n + 1023) / 1024)); }
 void launch_qt_from_records(const RtJob* jobs_dev, int n_jobs, int max_n, int* err, hipStream_t st)
 {
     if (n_jobs > 0 && max_n > 0) {
-        hipLaunchKernelGGL(k_qt_from_records, dim3((unsigned)std::max(1, std::min(512, (max_n + 1023) / 1024)), (unsigned)n_jobs), dim3(256), 0, st, jobs_dev, err);
+        hipLaunchKernelGGL(k_qt_from_records, dim3((unsigned)qt_from_records_blocks(max_n), (unsigned)n_jobs), dim3(256), 0, st, jobs_dev, err);
         hipLaunchKernelGGL(k_qt_order_seams, dim3((unsigned)std::max(1, std::min(64, (max_n / 64 + 255) / 256)), (unsigned)n_jobs), dim3(256), 0, st, jobs_dev, err);
     }
 }
@@ -138,9 +139,7 @@ int chain_upload_tables(l3d_ctx* c, const l3d_chain_view* views, int n_views, st
         if (v.n_sources) { memcpy(tab + d.o_sc, v.source_cam, (size_t)v.n_sources * 4); memcpy(tab + d.o_si, v.source_index, (size_t)v.n_sources * 4); }
         // the LOCAL camera number this view has in each source's neighbour list (run tables: which runs of the source's list point here); -1: not listed
         for (int q = 0; q < v.n_sources; ++q) {
-            const l3d_chain_view& w = views[v.source_index[q]];
-            int slot = -1;
-            for (int j = 0; j < w.N && w.local2global; ++j) if (w.local2global[j] == v.view_id) { slot = j; break; }
+            const int slot = chain_source_slot(views, v, q);
             memcpy(tab + d.o_ss + (size_t)q * 4, &slot, 4);
         }
     }

@@ -6,6 +6,7 @@
 // schedule's view ids, the release of the chain's scratch, a rank's ranges as views of the dense map.
 #pragma once
 
+#include <algorithm>
 #include <initializer_list>
 #include <utility>
 #include <vector>
@@ -73,6 +74,46 @@ void chain_launch_verify(l3d_ctx* c, VerifyArgs& va, const ChainViewDev& d, cons
 
 // first guess of the candidate capacity from the largest view's pair count (raw density ~6 % + reverse matches; guarded on the device)
 inline size_t chain_first_cand_cap(double max_pairs) { return (size_t)(max_pairs * 0.12) + 65536; }
+// Lanes that share a run when a view collects its reverse matches through the run tables (k_exist_count_rt, k_place_rt): always a power of two in
+// [1, 64] -- both kernels cut their workgroup into groups of g lanes (256 / g and 1024 / g of them) and step their segment loops by the number of
+// groups, so a g above the workgroup would make that step 0 (the loop never ends) and a g that does not divide it would let the last, partial group
+// take the next workgroup's first segments a second time.  opt (option rt_g) < 0: the average run of the lists seen so far rounded up to a power of
+// two; 0: a run per thread; > 0: that many, rounded DOWN to a power of two and clamped to 64.
+inline int rt_lanes_per_run(int opt, double avg_run)
+{
+    if (opt == 0) return 1;
+    int g = 1;
+    if (opt < 0) { while (g < 64 && g < avg_run) g <<= 1; return g; }
+    while (g < 64 && 2 * g <= opt) g <<= 1;
+    return g;
+}
+// Views keep more than this many records each on average (option long_list; 0: 2^18): the following views read their sources' runs instead of
+// scanning their lists (k_exist_count_rt / k_place_rt), and the chain transposes the products' pairs itself (prod_early = 1).
+inline int chain_long_list(const Options& o) { return o.long_list > 0 ? o.long_list : 262144; }
+// How a view of the resident chain collects its reverse matches, from the lists seen so far (avg_kept records per view; any_seen: the host has read a
+// result record yet) -- shared by run_chain and l3d_test_collect_candidates:
+//   bps     workgroups per source view of the two scans of the sources' lists: a thread walks its stride of a list with dependent loads, so the list must
+//           be spread over enough of them -- 32 x 256 threads take config 2's 36 k records in 5 steps, but 3.5 M records (4000 x 24) in 430
+//   rt      the run-table route (long lists); rt_g lanes per run, rt_bps workgroups per source to cover its segments
+struct CollectRule { int bps, rt_g, rt_bps; bool rt; double avg_run; };
+inline CollectRule chain_collect_rule(const Options& o, bool any_seen, double avg_kept, int S, int N, int maxS)
+{
+    CollectRule r;
+    if (!any_seen) avg_kept = 0.0;
+    r.bps = (int)std::min(512.0, std::max(32.0, avg_kept / 4096.0));
+    r.avg_run = any_seen ? avg_kept / std::max(1.0, (double)S * std::max(1, N)) : 1.0;
+    r.rt_g = rt_lanes_per_run(o.rt_g, r.avg_run);
+    r.rt_bps = std::max(1, std::min(512, (maxS * std::max(1, r.rt_g) + 255) / 256));
+    r.rt = any_seen && avg_kept > (double)chain_long_list(o);
+    return r;
+}
+// the LOCAL camera number view v has in the neighbour list of its q-th source (run tables: which runs of the source's list point at v); -1: not listed
+inline int chain_source_slot(const l3d_chain_view* views, const l3d_chain_view& v, int q)
+{
+    const l3d_chain_view& w = views[v.source_index[q]];
+    for (int j = 0; j < w.N && w.local2global; ++j) if (w.local2global[j] == v.view_id) return j;
+    return -1;
+}
 inline size_t chain_align16(size_t x) { return (x + 15) & ~(size_t)15; }
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 

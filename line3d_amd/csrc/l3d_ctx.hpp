@@ -231,6 +231,7 @@ struct l3d_ctx {
     size_t turn_arena_room = 0;                     // match_chain_turn under option regrow_free_mb: the records the turn's arena may hold (0: no cap); set around its chain and share only
     bool records_released = false;                  // l3d_chain_release_records: the products' kept records are gone (l3d_chain_kept_list refuses)
     std::vector<int> shard_view_kept;               // the last sharded run: every chain view's kept count from its slot headers, whatever this rank retired
+    int chain_routes[2] = { 0, 0 };                 // l3d_last_chain_routes: views of the last resident chain that collected their reverse matches by scanning records / through run tables
     size_t test_cand_cap = 0, test_arena_cap = 0;   // tests: initial capacities of the resident chain (0 = estimate)
     int chain_seen_views = 0; double chain_seen_pairs = 0; size_t chain_seen_cand_cap = 0, chain_seen_arena_cap = 0; double chain_seen_kept = 0;   // what the last chain over this scene needed (and kept)
     unsigned long long* pair_dbg = nullptr;   // L3D_PAIR_STATS=1: device counters of k_pair_mask's levels (printed at destroy)

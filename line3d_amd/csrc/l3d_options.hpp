@@ -48,7 +48,8 @@ namespace l3d {
     X(retire_apart, "L3D_RETIRE_APART", 1, "sharded chain, ring mode: batches of views are retired into the compact arena on a side stream; the chain waits only before it overwrites their ring blocks (0: on the chain's stream)") \
     X(arena_guess, "L3D_ARENA_GUESS", 50, "resident chain: first guess of the kept arena in thousandths of the scene's segment pairs, within 35 % of the free HBM (4: the small guess of rounds 1-5, grown on overflow)") \
     X(slot_scan_grain, "L3D_SLOT_SCAN_GRAIN", 0, "sharded chain: records of a slot per workgroup of the two scans of the sources' slots (0: 4096)") \
-    X(rt_g, "L3D_RT_G", -1, "resident chain with run tables: lanes sharing a run when a view collects its reverse matches (-1: by the average run, 0: a run per thread)") \
+    X(rt_g, "L3D_RT_G", -1, "resident chain with run tables: lanes sharing a run when a view collects its reverse matches (-1: by the average run, 0: a run per thread, n > 0: n rounded down to a power of two, at most 64)") \
+    X(long_list, "L3D_LONG_LIST", 0, "resident chain: views that keep more than this many records each on average send the following views through the run tables and have their pairs transposed early (0: 262144; tests: 1 sends every view behind the first results through the run tables)") \
     X(part_vrank, "L3D_PART_VRANK", 0, "with part_vworld: the rank of the job whose block of views a world-1 partitioned run keeps") \
     X(part_vworld, "L3D_PART_VWORLD", 0, "a world-1 shard_run with commit 3 keeps the block of views rank part_vrank of a job of this many ranks would own: ONE rank's share of a job that does not fit one GPU, exercised on one GPU (scripts/run_rank_share.py); l3d_set_option only") \
     X(slot_ring, "L3D_SLOT_RING", -1, "sharded run: 1 = always retire old gathered blocks into the compact arena (ring of window + 18 views), 0 = never, -1 = when all blocks exceed 8 GB") \

@@ -23,6 +23,7 @@ struct RtJob {                      // one view's list
 
 // qt of every job's records; *err counts records whose camera is not a neighbour or whose (segment, camera) order descends (the tables would be wrong)
 void launch_qt_from_records(const RtJob* jobs_dev, int n_jobs, int max_n, int* err, hipStream_t st);
+int qt_from_records_blocks(int max_n);      // workgroups per job of that pass (each walks its job's records with a stride of 256 x this many)
 // rt of every job from its records and qt (lower bounds: one thread per (segment, camera) cell)
 void launch_rt_from_qt(const RtJob* jobs_dev, int n_jobs, int max_cells, hipStream_t st);
 

@@ -43,7 +43,14 @@ def test_struct_layouts(tmp_path):
                    '  sizeof(l3d_test_pair_path), offsetof(l3d_test_pair_path, seg_begin), offsetof(l3d_test_pair_path, capacity), offsetof(l3d_test_pair_path, overflow),\n'
                    '  sizeof(l3d_test_products_path), offsetof(l3d_test_products_path, held), offsetof(l3d_test_products_path, block_capacity),\n'
                    '  offsetof(l3d_test_products_path, early_g), offsetof(l3d_test_products_path, block_cap), offsetof(l3d_test_products_path, block_g),\n'
-                   '  sizeof(l3d_chain_view), offsetof(l3d_chain_view, local2global), offsetof(l3d_chain_view, spatial_k), sizeof(l3d_chain_summary)); return 0; }\n')
+                   '  sizeof(l3d_chain_view), offsetof(l3d_chain_view, local2global), offsetof(l3d_chain_view, spatial_k), sizeof(l3d_chain_summary));\n'
+                   '  printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", offsetof(l3d_test_verify_path, exist_cams), offsetof(l3d_test_verify_path, n_exist_cams),\n'
+                   '  offsetof(l3d_test_verify_path, cand_meta_out), offsetof(l3d_test_verify_path, cand_depths_out),\n'
+                   '  sizeof(l3d_test_kept_job), offsetof(l3d_test_kept_job, rt), offsetof(l3d_test_kept_job, N),\n'
+                   '  sizeof(l3d_test_kept_path), offsetof(l3d_test_kept_path, arena_cap), offsetof(l3d_test_kept_path, n_jobs), offsetof(l3d_test_kept_path, rebuild_blocks),\n'
+                   '  offsetof(l3d_test_kept_path, kept_base));\n'
+                   '  printf("%zu %zu %zu %zu %zu\\n", sizeof(l3d_test_collect_path), offsetof(l3d_test_collect_path, avg_kept), offsetof(l3d_test_collect_path, overflowed),\n'
+                   '  offsetof(l3d_test_collect_path, kernels), offsetof(l3d_test_collect_path, R)); return 0; }\n')
     exe = str(tmp_path / "layout")
     subprocess.check_call(["gcc", "-std=c99", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe])
     got = [int(x) for x in subprocess.run([exe], capture_output=True, text=True).stdout.split()]
@@ -54,7 +61,13 @@ def test_struct_layouts(tmp_path):
                    ctypes.sizeof(capi.PairPath), capi.PairPath.seg_begin.offset, capi.PairPath.capacity.offset, capi.PairPath.overflow.offset,
                    ctypes.sizeof(capi.ProductsPath), capi.ProductsPath.held.offset, capi.ProductsPath.block_capacity.offset, capi.ProductsPath.early_g.offset,
                    capi.ProductsPath.block_cap.offset, capi.ProductsPath.block_g.offset,
-                   ctypes.sizeof(capi.ChainView), capi.ChainView.local2global.offset, capi.ChainView.spatial_k.offset, capi.SUMMARY_DTYPE.itemsize], got
+                   ctypes.sizeof(capi.ChainView), capi.ChainView.local2global.offset, capi.ChainView.spatial_k.offset, capi.SUMMARY_DTYPE.itemsize,
+                   capi.VerifyPath.exist_cams.offset, capi.VerifyPath.n_exist_cams.offset, capi.VerifyPath.cand_meta_out.offset, capi.VerifyPath.cand_depths_out.offset,
+                   ctypes.sizeof(capi.KeptJob), capi.KeptJob.rt.offset, capi.KeptJob.N.offset,
+                   ctypes.sizeof(capi.KeptPath), capi.KeptPath.arena_cap.offset, capi.KeptPath.n_jobs.offset, capi.KeptPath.rebuild_blocks.offset,
+                   capi.KeptPath.kept_base.offset,
+                   ctypes.sizeof(capi.CollectPath), capi.CollectPath.avg_kept.offset, capi.CollectPath.overflowed.offset, capi.CollectPath.kernels.offset,
+                   capi.CollectPath.R.offset], got
 
 
 def test_no_gpu_fails_loudly():

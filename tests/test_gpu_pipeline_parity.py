@@ -855,6 +855,49 @@ def test_products_variants_agree(small_scene, small_oracle):
             assert d == digests[0], i
 
 
+def test_run_table_route_equals_the_scanned_route(small_scene, small_oracle):
+    """A view collects its reverse matches by scanning its sources' records (k_exist_count / k_place) or, once the lists are long, through their run
+    tables (k_exist_count_rt + k_exist_combine / k_place_rt).  L3D_LONG_LIST=1 sends every view enqueued after the first result was read through the
+    run tables, with the default lanes per run and with 1 and 8: kept lists, medians, products and lines are the default run's byte for byte (and the
+    oracle's on the small scene), l3d_last_chain_routes reports views on both routes, and none on the run-table route by default."""
+    from line3d_amd.pipeline import Line3D, load_scene
+    from line3d_amd.synth import make_scene
+    for scene, N in ((small_scene, 6), (make_scene(10, 700, 8, seed=5, noise_px=0.05, step=0.05), 8)):
+        ids = [v["id"] for v in scene.views]
+        digests = []
+        for opts in (dict(), dict(L3D_LONG_LIST=1), dict(L3D_LONG_LIST=1, L3D_RT_G=1), dict(L3D_LONG_LIST=1, L3D_RT_G=8)):
+            l = Line3D("", matchingNeighbors=N)
+            l.keep_view_matches(True)
+            load_scene(l, scene)
+            l.prepare()
+            for k, v in opts.items():
+                l.context().set_option(k, v)
+            l.context().set_option("L3D_CHECK_POT", 1)
+            l.match_views()
+            assert l.match_path() == 0
+            scanned, run_tables = l.context().last_chain_routes()
+            if opts:
+                assert scanned >= 1 and run_tables >= 1, (opts, scanned, run_tables)
+            else:
+                assert scanned >= 1 and run_tables == 0, (scanned, run_tables)
+            l.finish(False)
+            d = _products_digest(l)
+            for v in ids:
+                m, med = l.view_matches(v)
+                d["kept_%d" % v], d["median_%d" % v] = m.tobytes(), np.float32(med).tobytes()
+            d["lines"] = repr([(list(s2), np.asarray(s3).tobytes()) for s2, s3 in l.getResult()])
+            digests.append(d)
+            if scene is small_scene:
+                for v in sorted(small_oracle.trace):
+                    assert l.view_matches(v)[0].tobytes() == small_oracle.trace[v]["matches"].tobytes(), (opts, v)
+                assert_lines_equal(l.getResult(), small_oracle.result, 1e-4)
+            l.close()
+        assert sum(len(digests[0]["kept_%d" % v]) for v in ids) > 0 and len(digests[0]["pot_tgt"]) > 0
+        for i, d in enumerate(digests[1:], 1):
+            assert d.keys() == digests[0].keys()
+            assert [k for k in d if d[k] != digests[0][k]] == [], i
+
+
 def test_products_of_a_hub_view_touched_by_more_than_64_views():
     """A view that (nearly) all 79 other views list as a neighbour (and that lists two of them): its rows of the table collect entries from 79 (view, camera) pairs -- the rows
     kernel's lanes look the touched views up 64 at a time, the short-row path does not apply.  Transposed products (at the end and early, by the chain)

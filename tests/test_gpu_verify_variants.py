@@ -28,6 +28,8 @@ def get_case(name):
             k = [kw["seed"] for kw in vc.CASES].index(int(name[5:]))
             case = vc.make_case(**vc.CASES[k])
             ref = np.load(os.path.join(HERE, "golden", "verify_ref.npz"))["c%d_conf" % k]
+        elif name in [kw["name"] for kw in vc.EXIST_CASES]:     # (no reference vector of its own)
+            case, ref = vc.make_edge_case(name), None
         else:
             case = vc.make_edge_case(**[kw for kw in vc.EDGE_CASES if kw["name"] == name][0])
             ref = np.load(os.path.join(HERE, "golden", "verify_edges_ref.npz"))[name + "_conf"]
@@ -95,7 +97,8 @@ def check(case, conf, ref, got, kernels, kw, what):
     kept, best = expected_epilogue(case, conf)
     assert np.array_equal(g_kept, kept), (what, "kept counts")
     assert g_best.tobytes() == best.tobytes(), (what, "best depths", np.flatnonzero((g_best != best).any(1))[:8])
-    assert np.max(np.abs(g_conf - ref), initial=0) <= 5e-6 and np.array_equal(g_conf > 1.0, ref > 1.0), (what, "reference vectors")
+    if ref is not None:
+        assert np.max(np.abs(g_conf - ref), initial=0) <= 5e-6 and np.array_equal(g_conf > 1.0, ref > 1.0), (what, "reference vectors")
     if kw["path"] != 0:
         N, largest = len(case["camera_offsets"]), int(case["match_offsets"][:, 1].max())
         want = vc.vw_fit_mmax(kw["mmax"], N) if kw.get("mmax") else vc.vw_mmax(largest, N, kw["path"])
@@ -209,3 +212,46 @@ def test_refused_sizes_and_selections(gpu_ctx):
     conf, kept, best, _, ran = gpu_ctx.test_verify_candidates(path=0, **wide)
     assert len(conf) == 0 and kept.tolist() == [0] and best.tolist() == [[-1.0, -1.0]] and ran == capi.VK_ALL_PAIRS | capi.VK_SEG_POST
     check(*run_variant(gpu_ctx, "seed_1", "chain_4wave")[:6], ("seed_1 after the refusals", "chain_4wave"))
+
+
+# ---- unordered reverse-match runs: the window kernel orders the rows of the cameras it is told hold reverse matches (k_verify_window, sort_exist_run)
+EXIST_CAMS = {"seed_2": (1, 4, 6), "one_camera": (1, 2), "sizes": (0, 3), "many_cameras_17": (2, 9, 16), "long_runs": (1, 3)}
+EXIST_VARIANTS = ("chain_4wave", "chain_8wave", "chain_mmax64", "chain_gb", "chain_split256", "chain_longest_first")
+EXIST_RUNS = [(n, v) for n in EXIST_CAMS for v in EXIST_VARIANTS if VARIANTS[v][2] is None or VARIANTS[v][2](CASE_N.get(n, 5))]
+_sorted_runs = set()
+
+
+@pytest.mark.parametrize("name,variant", EXIST_RUNS)
+def test_unordered_runs_are_ordered_by_the_window_kernel(gpu_ctx, name, variant):
+    """The rows of the chosen cameras shuffled (fixed seed) and named as exist_cams: the candidate arrays come back in the unshuffled order, and
+    confidences, kept counts and best depths are the unshuffled run's byte for byte -- which is held to the contract oracle."""
+    case, (row_start, meta), conf, ref = get_case(name)
+    cams = EXIST_CAMS[name]
+    N = len(case["camera_offsets"])
+    runs = []
+    for row in range(len(row_start) - 1):        # (on the CPU: one right order per shuffled row)
+        if row % N in cams:
+            assert np.all(np.diff(meta[row_start[row]:row_start[row + 1], 0].astype(np.int64)) > 0), (name, row)
+            runs.append(int(row_start[row + 1] - row_start[row]))
+    assert max(runs) >= 2
+    got0 = run_variant(gpu_ctx, name, variant)
+    check(*got0[:6], (name, variant, "ordered"))
+    kw = got0[5]
+    meta_s, depths_s, perm = vc.shuffle_rows(row_start, meta, case["matches_depths"], N, cams, 11)
+    assert (perm != np.arange(len(perm))).sum() >= 2
+    got = gpu_ctx.test_verify_candidates(case["src_segs"], case["tgt_segs"], case["camera_offsets"], case["P"], case["RtKinv"], case["C_src"], row_start, meta_s,
+                                         depths_s, case["sigma_p"], case["sigma_a"], case["spatial_k"], exist_cams=cams, **kw)
+    assert got[4] == got0[4], "kernels launched"
+    assert np.array_equal(got[5], meta), "the candidates' metadata did not come back in target order"
+    assert got[6].tobytes() == case["matches_depths"].tobytes(), "the depths did not follow their candidates"
+    for k, what in ((0, "confidences"), (1, "kept counts"), (2, "best depths")):
+        assert got[k].tobytes() == got0[3][k].tobytes(), what
+    assert got[3] == got0[3][3]
+    _sorted_runs.update(runs)
+
+
+def test_both_orderings_of_a_run_were_reached():
+    """runs a wave ranks in registers (2 .. 256 entries) and runs it stages (above 256: two passes; above 512: three)"""
+    assert len(_sorted_runs) > 0, "run with the tests above"
+    assert any(2 <= r <= 64 for r in _sorted_runs) and any(64 < r <= 256 for r in _sorted_runs) and 256 in _sorted_runs and 257 in _sorted_runs
+    assert any(256 < r <= 512 for r in _sorted_runs) and any(r > 512 for r in _sorted_runs)

@@ -342,3 +342,27 @@ def test_reference_vectors_of_the_edge_cases(edge):
         want = g[name + "_conf"]
         assert op.verify_case(libm, case).tobytes() == want.tobytes(), name
         assert np.max(np.abs(conf - want), initial=0) <= 5e-6 and np.array_equal(conf > 1.0, want > 1.0), name
+
+
+def test_long_runs_case():
+    """EXIST_CASES: (segment, camera) runs of 300 and 600, of exactly 256 and 257, of 513 -- and shorter ones -- with distinct, ascending targets, so
+    that a shuffled row has one right order; the shuffle moves entries inside the chosen cameras' rows only and really moves them"""
+    assert [kw["name"] for kw in vc.EXIST_CASES] == ["long_runs"]
+    case = vc.make_edge_case("long_runs")
+    row_start, meta = vc.to_rows(case)
+    N = 5
+    assert np.diff(row_start).reshape(-1, N).tolist() == [list(r) for r in vc.RUN_SIZES]
+    runs = np.diff(row_start).reshape(-1, N)[:, [1, 3]].reshape(-1).tolist()
+    assert sorted(runs) == [0, 1, 2, 256, 257, 300, 513, 600]
+    for row in range(len(row_start) - 1):
+        assert np.all(np.diff(meta[row_start[row]:row_start[row + 1], 0].astype(np.int64)) > 0), row
+    assert (case["matches_depths"][:, :2] > 0).all()
+    conf = op.verify_case(op.load_lib(libm=False), case)
+    assert 0 < (conf > 1.0).sum() < len(conf)
+    m2, d2, perm = vc.shuffle_rows(row_start, meta, case["matches_depths"], N, (1, 3), 5)
+    moved = perm != np.arange(len(perm))
+    assert set(meta[moved, 1].tolist()) == {1, 3} and moved.sum() > 1800
+    assert np.array_equal(np.sort(perm), np.arange(len(perm))) and np.array_equal(m2[:, 1], meta[:, 1])
+    for row in range(len(row_start) - 1):        # a shuffled row holds the same entries
+        a, b = row_start[row], row_start[row + 1]
+        assert sorted(m2[a:b, 0].tolist()) == meta[a:b, 0].tolist()

@@ -373,7 +373,36 @@ def make_edge_case(name, **kw):
         order = rng.permutation(len(ms))
         src = _src_segments(rng, len(ms))
         return _pack(scene, src, [_mixed(rng, scene, src[s], ms[order[s]]) for s in range(len(ms))], 0.02, 2.5, 10.0)
+    if name == "long_runs":
+        # (segment, camera) runs at and around the 256 entries a wave orders in registers and the 512 of two staged passes -- what the window kernel has
+        # to order itself when the rows hold reverse matches (RUN_SIZES: per segment, candidates per camera)
+        scene = _Scene(5)
+        src = _src_segments(rng, len(RUN_SIZES))
+        segs = []
+        for s, per_cam in enumerate(RUN_SIZES):
+            cam = np.repeat(np.arange(5), per_cam)
+            g = _mixed(rng, scene, src[s], len(cam), cluster=0.7)
+            g["cam"] = cam
+            g["q"] = scene.targets(src[s], cam, g["d1"], g["d2"], rng.normal(0, 1.0, (len(cam), 4)))
+            segs.append(g)
+        return _pack(scene, src, segs, 0.02, 2.5, 10.0)
     raise KeyError(name)
+
+
+RUN_SIZES = ((50, 300, 20, 600, 0), (0, 256, 7, 257, 3), (10, 513, 0, 2, 1), (9, 1, 12, 0, 8))
+# lists for the ordering of unordered runs (no reference vector of their own: held to the contract oracle and to their ordered twin)
+EXIST_CASES = [dict(name="long_runs")]
+
+
+def shuffle_rows(row_start, meta, depths, N, cams, seed):
+    """the entries of every row of the cameras `cams` in a seeded random order (metadata and depths together), everything else in place"""
+    rng = np.random.default_rng(seed)
+    perm = np.arange(len(meta))
+    for row in range(len(row_start) - 1):
+        if row % N in cams:
+            a, b = int(row_start[row]), int(row_start[row + 1])
+            perm[a:b] = a + rng.permutation(b - a)
+    return meta[perm].copy(), depths[perm].copy(), perm
 
 
 def hash_name(name):
