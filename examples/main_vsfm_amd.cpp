@@ -2,10 +2,12 @@
 // segment caches of an earlier Line3D run standing in for the images, or with the images as binary PPM / PGM files or baseline JPEG files (no
 // OpenCV, no tclap, no boost):
 //
-//   main_vsfm_amd [--refine] <scene.nvm | bundle.rd.out> <data directory> [neighbors=10] [diffusion=0] [output folder=<data directory>] [image folder]
+//   main_vsfm_amd [--refine] [--device-covisibility] <scene.nvm | bundle.rd.out> <data directory> [neighbors=10] [diffusion=0] [output folder=<data directory>] [image folder]
 //
 // --refine (anywhere on the line): the 3-D lines are refined against the 2-D segments of their clusters before they are written (setRefinement: the
 // reference has no such step; its successor Line3D++ added one) -- the segments of a line in the STL / TXT files are then collinear.
+// --device-covisibility (anywhere on the line): the cameras' world point lists are counted on the GPU when compute3Dmodel starts, instead of one
+// observation at a time as the images are added (setDeviceCovisibility: the same neighbours, the same lines; it pays on models of many images).
 // With an image folder, camera i's image is "<image folder>/<camera name, extension replaced>.ppm" or ".pgm" (binary P6 / P5, maxval 255), or the
 // camera's own file "<image folder>/<camera name>" when it ends in .jpg / .jpeg (baseline JPEG, decoded on the device: addImageJPEGDistorted;
 // convert PNG and progressive JPEG beforehand).  The camera name is the NVM file's image name; for a bundler file it is the camera index as %08d
@@ -121,13 +123,13 @@ struct Vec3 { const double* p; double operator()(int i) const { return p[i]; } }
 
 int main(int argc, char** argv)
 {
-    bool refine = false;
+    bool refine = false, device_covis = false;
     {
         int k = 1;
-        for (int i = 1; i < argc; ++i) { if (std::string(argv[i]) == "--refine") refine = true; else argv[k++] = argv[i]; }
+        for (int i = 1; i < argc; ++i) { if (std::string(argv[i]) == "--refine") refine = true; else if (std::string(argv[i]) == "--device-covisibility") device_covis = true; else argv[k++] = argv[i]; }
         argc = k;
     }
-    if (argc < 3) { fprintf(stderr, "usage: %s [--refine] <scene.nvm | bundle.rd.out> <data directory> [neighbors=10] [diffusion=0] [output folder] [image folder]\n", argv[0]); return 2; }
+    if (argc < 3) { fprintf(stderr, "usage: %s [--refine] [--device-covisibility] <scene.nvm | bundle.rd.out> <data directory> [neighbors=10] [diffusion=0] [output folder] [image folder]\n", argv[0]); return 2; }
     const std::string nvm = argv[1], data_dir = argv[2];
     const int neighbors = argc > 3 ? atoi(argv[3]) : 10;
     const bool diffusion = argc > 4 && atoi(argv[4]) != 0;
@@ -147,6 +149,7 @@ int main(int argc, char** argv)
     L3D::Line3D line3D(data_dir, neighbors, 5.0f, 1.0f, 3.5f, 10.0f, 0.25f, true, true);
     if (!line3D.valid()) { l3d_sfm_free(scene); return 1; }
     if (refine) line3D.setRefinement(true);
+    if (device_covis) line3D.setDeviceCovisibility(true);
     int added = 0;
     for (int i = 0; i < n; ++i) {
         double focal = 0, dist[2] = { 0, 0 }, R[9], t[3];

@@ -628,6 +628,31 @@ public:
         rmsBefore = rb; rmsAfter = ra; status.assign(st.begin(), st.end());
         return true;
     }
+    // Where addImage's world point links are filed (no counterpart in the reference; l3d_line3d_set_covisibility): false, the default, on the host as every
+    // view is added; true: the lists are stored and compute3Dmodel counts them on the device -- the same neighbours and the same result.  Refused while the
+    // object holds views; reset() keeps the setting.
+    void setDeviceCovisibility(bool on) { report(l3d_line3d_set_covisibility(h_, on ? 1 : 0)); }
+    // what compute3Dmodel chose (valid behind it): the visual neighbours of a view, ascending ids
+    std::vector<unsigned int> getNeighbors(const unsigned int camID)
+    {
+        int n = 0;
+        if (l3d_line3d_get_neighbors(h_, camID, nullptr, 0, &n) != L3D_OK || n <= 0) return {};
+        std::vector<uint32_t> ids((size_t)n);
+        l3d_line3d_get_neighbors(h_, camID, ids.data(), n, &n);
+        return std::vector<unsigned int>(ids.begin(), ids.end());
+    }
+    // ... and its similarities by the other view's id
+    std::map<unsigned int, float> getViewSimilarities(const unsigned int camID)
+    {
+        std::map<unsigned int, float> out;
+        int n = 0;
+        if (l3d_line3d_get_view_similarities(h_, camID, nullptr, nullptr, 0, &n) != L3D_OK || n <= 0) return out;
+        std::vector<uint32_t> ids((size_t)n);
+        std::vector<float> sims((size_t)n);
+        l3d_line3d_get_view_similarities(h_, camID, ids.data(), sims.data(), n, &n);
+        for (size_t i = 0; i < ids.size(); ++i) out[ids[i]] = sims[i];
+        return out;
+    }
     // line3D.h:85
     void getResult(std::list<L3DFinalLine3D>& result)
     {

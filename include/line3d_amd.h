@@ -1373,6 +1373,46 @@ int l3d_line3d_add_image_masked(l3d_line3d* h, uint32_t image_id, unsigned width
 int l3d_line3d_add_image_cached_masked(l3d_line3d* h, uint32_t image_id, unsigned width, unsigned height, const l3d_segment_cache* cache, const double* K,
                                        const double* R, const double* t, const uint32_t* link_ids, const float* sims, int n_links, const l3d_segment_mask* mask);
 
+/* =================================================================================================
+ * CO-VISIBILITY.  What Line3D::processWorldpointList (line3D.cc:1874-1935) files for the world point lists of the views, counted at once.
+ *   point_ids    the lists one after the other, in add order; any uint32 is an id, all 32 bits count
+ *   list_start   n_lists + 1 ascending offsets into point_ids, list_start[0] == 0; list i is view index i
+ * Out (callee-allocated, l3d_free): num_wps[n_lists]; the non-zero common_wps as a CSR over view indices -- row_start[n_lists + 1], col (ascending
+ * within a row) and count, both row_start[n_lists] long (one spare element each); *path: 0 = the closed form on the device, 1 = the host replay.
+ * THE CLOSED FORM (no list names an id twice): a point whose track has fewer than three views counts nothing; a point with L >= 3 views adds 1 to
+ *   common_wps[a][b] for every ordered pair a != b of its views and 1 to num_wps of each.  The add order does not matter.
+ * PATH 1.  A list that names an id twice leaves the closed form (the function counts self pairs): the device finds that out (equal neighbours in the
+ *   sorted keys) and the lists are replayed through the function itself, in add order.
+ * REFUSED before anything is launched: a NULL argument (point_ids may be NULL without observations), n_lists < 0, offsets that do not start at 0 or
+ *   descend: L3D_ERR_INVALID.  2^31 - 1 observations or more, or 2^31 - 1 views or more: L3D_ERR_UNSUPPORTED.  So is a result of more than 2^31 - 1
+ *   non-zero counts.
+ * THE KERNELS.  k_covis_keys packs (point, view index) keys, one radix sort orders them (the observation's position rides along), k_covis_runs hands
+ *   every observation its track (start and length in the sorted order) and flags equal neighbours.  k_covis_count: one workgroup per view and column
+ *   tile walks the view's tracks of three or more views into an LDS histogram over the tile's view indices (a lane walks a short track alone, the
+ *   wave shares a long one) and counts the non-zeros; k_covis_scan turns the counts into positions; k_covis_write repeats the walk and writes col and
+ *   count in ascending order.  Counters are 32 bits wide.  Six launches (profile names covis_keys, covis_sort, covis_runs, covis_count, covis_scan,
+ *   covis_write) whatever the number of observations; the column tiles are a dimension of the grid.  Option L3D_COVIS_TILE: columns per tile (0: 8192,
+ *   the most).  No allocation grows with n_lists squared, and all device memory of the call is released before it returns.
+ *   l3d_test_covisibility_host   the same arguments without the context, no device: always the replay.  l3d_covis_last_error (per thread): its message
+ *   l3d_line3d_set_covisibility  0 (default): a view's links are filed on the host as it is added.  1: the add only stores the list, and prepare()
+ *                                counts all lists when one arrived since the last count, replacing num_wps and common_wps; everything behind them
+ *                                (findVisualNeighbors) is the same code.  Refused while the object holds views; reset keeps the setting.  A node object
+ *                                counts once, on rank 0's device
+ *   l3d_line3d_covisibility_path the path of the last count (0 before any)
+ *   l3d_line3d_get_neighbors / l3d_line3d_get_view_similarities
+ *                                after prepare, in either mode: the view's neighbours (ascending ids) / its similarities (ascending by the other
+ *                                view).  *n is the number there is; at most cap are written (ids, sims may be NULL)
+ * ================================================================================================= */
+int l3d_covisibility(l3d_ctx* ctx, const uint32_t* point_ids, const int64_t* list_start, int n_lists, uint32_t** num_wps, int32_t** row_start, int32_t** col,
+                     uint32_t** count, int* path);
+int l3d_test_covisibility_host(const uint32_t* point_ids, const int64_t* list_start, int n_lists, uint32_t** num_wps, int32_t** row_start, int32_t** col,
+                               uint32_t** count, int* path);
+const char* l3d_covis_last_error(void);
+int l3d_line3d_set_covisibility(l3d_line3d* h, int mode);
+int l3d_line3d_covisibility_path(const l3d_line3d* h);
+int l3d_line3d_get_neighbors(l3d_line3d* h, uint32_t view_id, uint32_t* ids, int cap, int* n);
+int l3d_line3d_get_view_similarities(l3d_line3d* h, uint32_t view_id, uint32_t* ids, float* sims, int cap, int* n);
+
 /* The detector's stages on their own, exported for tests (tests/test_gpu_detect_stages.py): the same kernels with the same launch shapes
  * as l3d_detect_segments, results copied to caller-allocated arrays.  (N, M) = (ceil(0.8 new_width), ceil(0.8 new_height)) is the scaled image.
  *   pixel stage   grey[new_width x new_height] after rescale + grey; img / mod / ang [N x M]: the Gaussian sampler's output, the 2x2 gradient's

@@ -450,6 +450,49 @@ def mask_segments_host(segments, mask, **kw):
     return segs, idx
 
 
+def covisibility_arguments(lists):
+    """The views' world point lists -> (point_ids uint32, list_start int64 of len(lists) + 1): the lists one after the other, in add order"""
+    arrs = [np.ascontiguousarray(a, dtype=np.uint32).reshape(-1) for a in lists]
+    start = np.zeros(len(arrs) + 1, np.int64)
+    if arrs:
+        start[1:] = np.cumsum([len(a) for a in arrs])
+    ids = np.concatenate(arrs + [np.zeros(1, np.uint32)])           # (one spare element: never a null pointer)
+    return ids, start
+
+
+def _covisibility_call(fn, head, ids, start, n_lists):
+    """the argument list the co-visibility calls share (head: the context, or nothing) -> (rc, (num_wps, row_start, col, count, path))"""
+    num, rs = C.POINTER(C.c_uint32)(), C.POINTER(C.c_int32)()
+    col, cnt, path = C.POINTER(C.c_int32)(), C.POINTER(C.c_uint32)(), C.c_int(-1)
+    rc = fn(*head, ids, start, C.c_int(n_lists), C.byref(num), C.byref(rs), C.byref(col), C.byref(cnt), C.byref(path))
+    if rc != 0:
+        return rc, None
+    n = max(0, n_lists)
+    row_start = np.ctypeslib.as_array(rs, (n + 1,)).copy()
+    nnz = int(row_start[n])
+    out = (np.ctypeslib.as_array(num, (n,)).copy() if n else np.zeros(0, np.uint32), row_start,
+           np.ctypeslib.as_array(col, (nnz,)).copy() if nnz else np.zeros(0, np.int32),
+           np.ctypeslib.as_array(cnt, (nnz,)).copy() if nnz else np.zeros(0, np.uint32), path.value)
+    lib = load_library()
+    for q in (num, rs, col, cnt):
+        lib.l3d_free(q)
+    return 0, out
+
+
+def covisibility_host(lists):
+    """l3d_test_covisibility_host: the views' world point lists through Line3D::processWorldpointList itself, in add order -- no context, no device.
+    -> (num_wps (V,) uint32, row_start (V + 1,) int32, col int32, count uint32, path): the non-zero common_wps as a CSR over list indices"""
+    lib = load_library()
+    lib.l3d_covis_last_error.restype = C.c_char_p
+    ids, start = covisibility_arguments(lists)
+    rc, out = _covisibility_call(lib.l3d_test_covisibility_host, (), _p(ids), _p(start), len(start) - 1)
+    if rc != 0:
+        e = L3DError("line3d_amd error %d: %s" % (rc, lib.l3d_covis_last_error().decode()))
+        e.code = rc
+        raise e
+    return out
+
+
 def rt_lanes(opt: int, avg_run: float) -> int:
     """l3d_test_rt_lanes: the lanes that share a run on the chain's run-table route for option rt_g = opt -- host only, no context, no device"""
     return int(load_library().l3d_test_rt_lanes(C.c_int(int(opt)), C.c_double(float(avg_run))))
@@ -1543,6 +1586,15 @@ class Context:
             rc, segs, idx = _mask_segments_call(self.lib.l3d_mask_segments, (self.h,), _p(s) if len(s) else None, len(s), m)
         self._chk(rc)
         return segs, idx
+
+    def covisibility(self, lists):
+        """l3d_covisibility: what Line3D::processWorldpointList files for the views' world point lists (one array of uint32 ids per view, in add
+        order), counted on the device ("CO-VISIBILITY") -> (num_wps (V,) uint32, row_start (V + 1,) int32, col int32, count uint32, path): the
+        non-zero common_wps as a CSR over list indices, columns ascending; path 1: a list named an id twice and the lists were replayed on the host"""
+        ids, start = covisibility_arguments(lists)
+        rc, out = _covisibility_call(self.lib.l3d_covisibility, (self.h,), _p(ids), _p(start), len(start) - 1)
+        self._chk(rc)
+        return out
 
     def fit_labelled_clusters(self, labels, node_hyp, hyp, hyp_cam, Rinv, scale_inv, tneg):
         """l3d_fit_labelled_clusters: -> (group_start, member_hyp, list per fitted cluster of (start, end))."""

@@ -176,6 +176,21 @@ static int node_run(L* h, const std::function<int(int)>& fn)
     if (r < 0 || rcs[(size_t)r] == L3D_OK) r = first.load();
     return r < 0 ? L3D_OK : h->fail(rcs[(size_t)r], rank_prefix(h, r) + N.ranks[(size_t)r]->err);
 }
+// l3d_line3d_set_covisibility 1 on a node object: rank 0 holds the lists and counts them once, on its device, before the ranks prepare; every
+// other rank is handed the two tables
+static int node_count_covisibility(L* h)
+{
+    L* R0 = rank0(h);
+    if (R0->covis_mode != 1 || !R0->covis_dirty) return L3D_OK;
+    if (const int rc = count_covisibility(R0)) return h->fail(rc, rank_prefix(h, 0) + R0->err);
+    for (size_t r = 1; r < h->node->ranks.size(); ++r) {
+        L* R = h->node->ranks[r];
+        R->num_wps = R0->num_wps; R->common_wps = R0->common_wps;
+        R->covis_path = R0->covis_path; R->covis_dirty = false;
+    }
+    return L3D_OK;
+}
+
 // the per-view summary of the one chain: a rank's own lists only cover the views it holds -- view k from the rank whose block holds it
 // (every mode cuts the chain's views into blocks n * r / W)
 static void node_merge_summary(L* h)
@@ -261,7 +276,8 @@ static int node_prepare_turns(L* h)
         (void)l3d_get_option(N.ranks[(size_t)r]->ctx, "L3D_RESERVE_HINT", &hint[(size_t)r]);
         if (const int rc = l3d_set_option(N.ranks[(size_t)r]->ctx, "L3D_RESERVE_HINT", 0)) return h->fail(rc, l3d_last_error(N.ranks[(size_t)r]->ctx));
     }
-    const int rc = node_run(h, [&](int r) { return prepare(N.ranks[(size_t)r]); });
+    int rc = node_count_covisibility(h);
+    if (!rc) rc = node_run(h, [&](int r) { return prepare(N.ranks[(size_t)r]); });
     for (int r = 0; r < W; ++r) (void)l3d_set_option(N.ranks[(size_t)r]->ctx, "L3D_RESERVE_HINT", hint[(size_t)r]);      // (read by prepare alone: the other modes keep theirs)
     return rc;
 }
@@ -494,7 +510,8 @@ static int node_compute(L* h, int perform_diffusion)
     if (rank0(h)->views.size() < 4) return h->fail(L3D_ERR_INVALID, "not enough images! can't compute 3D model...");   // line3D.cc:347-351
     if (N.mode == 2) return N.handover ? node_compute_turns_handover(h, perform_diffusion) : node_compute_turns(h, perform_diffusion);
     N.turn_records.clear(); N.turn_views.clear(); N.turn_visits.clear();
-    int rc = node_run(h, [&](int r) { return prepare(N.ranks[(size_t)r]); });
+    int rc = node_count_covisibility(h);
+    if (!rc) rc = node_run(h, [&](int r) { return prepare(N.ranks[(size_t)r]); });
     if (rc) return rc;
     int s_max = 0;
     for (const View* v : rank0(h)->vlist) s_max = std::max(s_max, v->S());
@@ -582,6 +599,7 @@ int l3d_line3d_create_node(const int* devices, int n, int matching_neighbors, fl
         rc = l3d_line3d_create(devices[r], matching_neighbors, unc_upper, unc_lower, sigma_p, sigma_a, min_baseline, use_collinearity, r == 0 ? verbose : 0, &R);
         if (rc == L3D_OK) {
             h->node->ranks.push_back(R);
+            R->covis_store = r == 0;
             rc = l3d_node_comm_bind(comm, r, l3d_ctx_stream(R->ctx));
         }
     }
@@ -659,6 +677,7 @@ int l3d_line3d_reset(l3d_line3d* h)
     h->worldpoints2views.clear(); h->visual_neighbors.clear(); h->fundamentals.clear(); h->matched.clear();
     h->pot.clear(); h->pot_foreign.clear(); h->hyps.clear(); h->best_idx.clear(); h->A.clear(); h->n_edges = 0; h->A_on_host = true; h->local2global.clear(); h->result.clear();
     h->refine_valid = false;                               // (the setting itself stays)
+    h->covis_ids.clear(); h->covis_views.clear(); h->covis_start.assign(1, 0); h->covis_dirty = false; h->covis_path = 0;      // (covis_mode stays)
     h->computation = false; h->prepared = false;
     drop_plan(h);
     return L3D_OK;
@@ -864,6 +883,14 @@ static int view_from_cache(L* h, const AddRequest& rq, const AddPlan& p, const l
 
 static void file_links(L* h, uint32_t id, const l3d_image_entry& e)
 {
+    if (!e.sims && h->covis_mode == 1) {                   // l3d_line3d_set_covisibility: the list is kept, prepare() counts
+        h->covis_dirty = true;
+        if (!h->covis_store) return;
+        h->covis_ids.insert(h->covis_ids.end(), e.link_ids, e.link_ids + e.n_links);
+        h->covis_views.push_back(id);
+        h->covis_start.push_back((int64_t)h->covis_ids.size());
+        return;
+    }
     if (!e.sims) { process_worldpoints(h, id, e.link_ids, e.n_links); return; }
     for (int i = 0; i < e.n_links; ++i)                    // setViewSimilarity, :1938-1946
         if (e.sims[i] > 0.01f) h->view_similarities[id][e.link_ids[i]] = e.sims[i];
@@ -1284,7 +1311,10 @@ static int match_views_reported(l3d_line3d* h)
 
 int l3d_line3d_prepare(l3d_line3d* h)
 {
-    if (h && h->node) return node_run(h, [h](int r) { return prepare(h->node->ranks[(size_t)r]); });
+    if (h && h->node) {
+        const int rc = node_count_covisibility(h);
+        return rc ? rc : node_run(h, [h](int r) { return prepare(h->node->ranks[(size_t)r]); });
+    }
     return h ? prepare(h) : L3D_ERR_INVALID;
 }
 int l3d_line3d_match_views(l3d_line3d* h)
@@ -1319,6 +1349,59 @@ int l3d_line3d_set_refinement(l3d_line3d* h, int on, int max_iterations, double 
     if (max_iterations < 0 || !(huber_px >= 0.0) || huber_px - huber_px != 0.0) return h->fail(L3D_ERR_INVALID, "set_refinement: max_iterations and huber_px must not be negative");
     if (h->node) return l3d_line3d_set_refinement(rank0(h), on, max_iterations, huber_px);
     h->refine_on = on != 0; h->refine_max_iterations = max_iterations; h->refine_huber_px = huber_px;
+    return L3D_OK;
+}
+// where the world point links are filed ("CO-VISIBILITY"): 0 on the host as each view is added, 1 by prepare() on the device.  A node object: every rank
+// takes the setting, rank 0 counts
+int l3d_line3d_set_covisibility(l3d_line3d* h, int mode)
+{
+    if (!h) return L3D_ERR_INVALID;
+    if (mode != 0 && mode != 1) return h->fail(L3D_ERR_INVALID, "set_covisibility: 0 (links filed on the host as views are added) or 1 (counted on the device by prepare)");
+    if (l3d_line3d_num_cameras(h) > 0) return h->fail(L3D_ERR_INVALID, "set_covisibility: the object holds views (reset first)");
+    if (h->node) return node_each(h, [mode](L* r) { return l3d_line3d_set_covisibility(r, mode); });
+    h->covis_mode = mode;
+    return L3D_OK;
+}
+int l3d_line3d_covisibility_path(const l3d_line3d* h)
+{
+    if (!h) return -1;
+    return h->node ? rank0(h)->covis_path : h->covis_path;
+}
+// what prepare() chose (findVisualNeighbors): a view's neighbours, ascending, and its similarities, ascending by the other view
+int l3d_line3d_get_neighbors(l3d_line3d* h, uint32_t view_id, uint32_t* ids, int cap, int* n)
+{
+    if (!h || !n) return L3D_ERR_INVALID;
+    *n = 0;
+    if (h->node) {
+        const int rc = l3d_line3d_get_neighbors(rank0(h), view_id, ids, cap, n);
+        return rc ? h->fail(rc, rank0(h)->err) : rc;
+    }
+    if (!h->prepared) return h->fail(L3D_ERR_INVALID, "get_neighbors: prepare first");
+    if (!h->find_view(view_id)) return h->fail(L3D_ERR_INVALID, "get_neighbors: unknown view");
+    auto it = h->visual_neighbors.find(view_id);
+    if (it == h->visual_neighbors.end()) return L3D_OK;
+    *n = (int)it->second.size();
+    if (ids) for (int i = 0; i < *n && i < cap; ++i) ids[i] = it->second[(size_t)i];
+    return L3D_OK;
+}
+int l3d_line3d_get_view_similarities(l3d_line3d* h, uint32_t view_id, uint32_t* ids, float* sims, int cap, int* n)
+{
+    if (!h || !n) return L3D_ERR_INVALID;
+    *n = 0;
+    if (h->node) {
+        const int rc = l3d_line3d_get_view_similarities(rank0(h), view_id, ids, sims, cap, n);
+        return rc ? h->fail(rc, rank0(h)->err) : rc;
+    }
+    if (!h->prepared) return h->fail(L3D_ERR_INVALID, "get_view_similarities: prepare first");
+    if (!h->find_view(view_id)) return h->fail(L3D_ERR_INVALID, "get_view_similarities: unknown view");
+    auto it = h->view_similarities.find(view_id);
+    if (it == h->view_similarities.end()) return L3D_OK;
+    int i = 0;
+    for (auto& kv : it->second) {
+        if (i < cap) { if (ids) ids[i] = kv.first; if (sims) sims[i] = kv.second; }
+        ++i;
+    }
+    *n = i;
     return L3D_OK;
 }
 int l3d_line3d_get_refinement(const l3d_line3d* h, double* rms_before, double* rms_after, int32_t* iterations, int32_t* status)

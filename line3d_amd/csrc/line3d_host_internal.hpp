@@ -27,6 +27,7 @@
 #include "l3d_unproject.hpp"
 #include "l3d_hostsort.hpp"
 #include "l3d_options.hpp"
+#include "l3d_covis.hpp"
 
 using namespace l3d::la;
 
@@ -236,6 +237,15 @@ struct l3d_line3d {
     std::vector<double> ref_rms_before, ref_rms_after;
     std::vector<int32_t> ref_iterations, ref_status;
 
+    // co-visibility counted on the device (l3d_line3d_set_covisibility; 0 by default, reset keeps the setting): the views' world point lists in add
+    // order, 4 bytes per observation, counted by prepare() when a list arrived since the last count
+    int covis_mode = 0;
+    bool covis_store = true;                                   // (a node object: rank 0 holds the lists and counts, the other ranks are handed its tables)
+    bool covis_dirty = false;
+    int covis_path = 0;                                        // l3d_line3d_covisibility_path: how the last count ran
+    std::vector<uint32_t> covis_ids, covis_views;              // the lists one after the other | the view of every list
+    std::vector<int64_t> covis_start{ 0 };
+
     // flat tables of the device affinity fill (l3d_affinity_input): kept between calls (no allocation, no page faults); the
     // collinearity part only changes with the set of views (drop_plan)
     struct AffTables {
@@ -326,6 +336,7 @@ void chain_notify(ChainFinalizer* f, int k);
 void add_matches(View& v, const l3d_match* m, size_t n, bool remove_old, bool only_best);
 V3 inverse_transform(const L* h, V3 P);
 void process_worldpoints(L* h, uint32_t viewID, const uint32_t* wps, int n);
+int count_covisibility(L* h);                       // mode 1: num_wps and common_wps from the stored lists, when one arrived since the last count
 int make_view(L* h, uint32_t id, unsigned width, unsigned height, const float* segs, int n,
               const double* K, const double* R, const double* t,
               const int32_t* coll_i = nullptr, const int32_t* coll_j = nullptr, const float* coll_w = nullptr, int n_coll = -1);

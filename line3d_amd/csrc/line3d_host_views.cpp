@@ -87,29 +87,36 @@ int make_view(L* h, uint32_t id, unsigned width, unsigned height, const float* s
     return L3D_OK;
 }
 
-// Line3D::processWorldpointList, line3D.cc:1874-1935
+// Line3D::processWorldpointList, line3D.cc:1874-1935 (the function: l3d_covis.hpp) on the object's own tables
 void process_worldpoints(L* h, uint32_t viewID, const uint32_t* wps, int n)
 {
-    h->num_wps[viewID] = 0;
-    for (int i = 0; i < n; ++i) {
-        std::vector<uint32_t>& w2v = h->worldpoints2views[wps[i]];
-        std::sort(w2v.begin(), w2v.end());
-        if (w2v.size() == 2) {
-            const uint32_t v1 = w2v[0], v2 = w2v[1];
-            h->common_wps[v1][v2] += 1;
-            h->common_wps[v2][v1] += 1;
-            ++h->num_wps[v1];
-            ++h->num_wps[v2];
-        }
-        if (w2v.size() >= 2) {
-            for (uint32_t v : w2v) {
-                h->common_wps[v][viewID] += 1;
-                h->common_wps[viewID][v] += 1;
-            }
-            ++h->num_wps[viewID];
-        }
-        if (std::find(w2v.begin(), w2v.end(), viewID) == w2v.end()) w2v.push_back(viewID);
+    l3d::process_worldpoints(h->num_wps, h->common_wps, h->worldpoints2views, viewID, wps, n);
+}
+
+// l3d_line3d_set_covisibility 1: the tables process_worldpoints would have filed list by list, counted from all stored lists at once
+// (l3d_covisibility) and put in their place.  The rows come by list index; the tables are keyed by view id
+int count_covisibility(L* h)
+{
+    if (h->covis_mode != 1 || !h->covis_dirty || !h->covis_store) return L3D_OK;
+    const int n_lists = (int)h->covis_views.size();
+    uint32_t *num = nullptr, *count = nullptr;
+    int32_t *row_start = nullptr, *col = nullptr;
+    int path = 0;
+    const int rc = l3d_covisibility(h->ctx, h->covis_ids.data(), h->covis_start.data(), n_lists, &num, &row_start, &col, &count, &path);
+    if (rc) return h->fail(rc, std::string("covisibility: ") + l3d_last_error(h->ctx));
+    h->num_wps.clear();
+    h->common_wps.clear();
+    for (int i = 0; i < n_lists; ++i) {
+        const uint32_t id = h->covis_views[(size_t)i];
+        h->num_wps[id] = num[i];
+        if (row_start[i] == row_start[i + 1]) continue;
+        std::map<uint32_t, unsigned>& row = h->common_wps[id];
+        for (int q = row_start[i]; q < row_start[i + 1]; ++q) row[h->covis_views[(size_t)col[q]]] = count[q];
     }
+    l3d_free(num); l3d_free(row_start); l3d_free(col); l3d_free(count);
+    h->covis_path = path;
+    h->covis_dirty = false;
+    return L3D_OK;
 }
 
 // Line3D::findVisualNeighbors, line3D.cc:476-549
@@ -501,8 +508,10 @@ int prepare(L* h)
     double tl = now_s();
     auto lap = [&](const char* what) { if (timing) { const double t = now_s(); fprintf(stderr, "[l3d prepare] %-28s %8.2f ms\n", what, (t - tl) * 1e3); tl = t; } };
     h->computation = true;
+    int rc = count_covisibility(h);
+    if (rc) return rc;
     find_visual_neighbors(h);
-    int rc = transform_geometry(h);
+    rc = transform_geometry(h);
     if (rc) return rc;
     lap("neighbours + normalisation");
     h->vlist.clear();

@@ -423,6 +423,35 @@ class Line3D:
         return {"group_start": gs, "member_cam": mc, "member_seg": ms, "member_pts": mp, "cameras": cams, "Rinv": tr[:9].reshape(3, 3).copy(), "scale_inv": float(tr[9]),
                 "tneg": tr[10:13].copy()}
 
+    # -- co-visibility: where the world point links are filed, and what prepare() chose from them -----------------------
+    def set_covisibility(self, mode="device"):
+        """l3d_line3d_set_covisibility: "host" (default) files a view's world point links as it is added; "device" stores the list and has prepare()
+        count all lists on the GPU.  Refused while the object holds views; reset keeps the setting."""
+        m = {"host": 0, "device": 1}.get(mode, mode)
+        if m not in (0, 1):
+            raise ValueError('set_covisibility: "host" or "device"')
+        self._chk(self.lib.l3d_line3d_set_covisibility(self.h, C.c_int(int(m))))
+
+    def covisibility_path(self):
+        """l3d_line3d_covisibility_path: 0 the closed form on the device, 1 the host replay (a list named an id twice) -- of the last count"""
+        return int(self.lib.l3d_line3d_covisibility_path(self.h))
+
+    def neighbors(self, view_id):
+        """l3d_line3d_get_neighbors: the view's visual neighbours after prepare, ascending ids (uint32)"""
+        n = C.c_int(0)
+        self._chk(self.lib.l3d_line3d_get_neighbors(self.h, C.c_uint32(view_id), None, C.c_int(0), C.byref(n)))
+        ids = np.zeros(n.value, np.uint32)
+        self._chk(self.lib.l3d_line3d_get_neighbors(self.h, C.c_uint32(view_id), _p(ids), C.c_int(len(ids)), C.byref(n)))
+        return ids
+
+    def view_similarities(self, view_id):
+        """l3d_line3d_get_view_similarities: (ids uint32, similarities float32) of the view after prepare, ascending by the other view's id"""
+        n = C.c_int(0)
+        self._chk(self.lib.l3d_line3d_get_view_similarities(self.h, C.c_uint32(view_id), None, None, C.c_int(0), C.byref(n)))
+        ids, sims = np.zeros(n.value, np.uint32), np.zeros(n.value, np.float32)
+        self._chk(self.lib.l3d_line3d_get_view_similarities(self.h, C.c_uint32(view_id), _p(ids), _p(sims), C.c_int(len(ids)), C.byref(n)))
+        return ids, sims
+
     def numCameras(self):
         return self.lib.l3d_line3d_num_cameras(self.h)
 

@@ -104,7 +104,7 @@ def result_basename(max_width=-1, neighbors=10, min_uncertainty=1.0, max_uncerta
 
 
 def reconstruct(scene: SfmScene, segments, image_sizes, out_dir=None, neighbors=10, diffusion=False, device=0, masks=None, mask_mode="split", mask_threshold=1,
-                mask_keep_permille=500, mask_max_gap=0, mask_min_length=0.0, **line3d_kwargs):
+                mask_keep_permille=500, mask_max_gap=0, mask_min_length=0.0, covisibility="host", **line3d_kwargs):
     """The drivers' flow (main_vsfm.cpp:226-325) with detected segments in place of images: K from focal and image size,
     addImage with the world point lists, compute3Dmodel, optional STL + TXT output under the drivers' file name.
     segments[i]: (S,4) float32 of camera i (undistorted image coordinates); image_sizes[i]: (width, height).
@@ -113,12 +113,16 @@ def reconstruct(scene: SfmScene, segments, image_sizes, out_dir=None, neighbors=
     masks: None, or a callable image name -> mask (a uint8 / bool array H x W of the image's size, or a device object; a byte >= mask_threshold is
     valid) or None for an image without one (COLMAP's mask_path read by the caller).  The image's segments -- given, or replayed from a cache, whose
     collinearities are then computed anew -- go through the mask on the device first ("A SEGMENT MASK", capi.segment_mask): mask_mode "drop",
-    "clip" or "split" with mask_keep_permille, mask_max_gap and mask_min_length beside it.  An image whose segments all fall to its mask adds no view."""
+    "clip" or "split" with mask_keep_permille, mask_max_gap and mask_min_length beside it.  An image whose segments all fall to its mask adds no view.
+    covisibility: "host" files the world point links as the views are added, "device" counts them on the GPU in compute3Dmodel
+    (Line3D.set_covisibility: the same neighbours and lines)."""
     import os
     from . import capi
     from .pipeline import Line3D
     from .io import segment_cache_filename
     l3d = Line3D("", matchingNeighbors=neighbors, device=device, **line3d_kwargs)
+    if covisibility != "host":
+        l3d.set_covisibility(covisibility)
 
     def mask_of(cam):
         m = masks(cam["name"]) if masks is not None else None
@@ -150,7 +154,7 @@ def reconstruct(scene: SfmScene, segments, image_sizes, out_dir=None, neighbors=
 
 
 def reconstruct_from_images(scene: SfmScene, load_image, data_directory, out_dir=None, neighbors=10, diffusion=False, max_width=1920,
-                            load_and_store_segments=True, device=0, batch=16, refine=False, alpha=None, out_size=None, **line3d_kwargs):
+                            load_and_store_segments=True, device=0, batch=16, refine=False, alpha=None, out_size=None, covisibility="host", **line3d_kwargs):
     """The drivers' flow (main_vsfm.cpp:226-325) from pixels: per camera the image load_image(i, name) returns -- `bytes`: the contents of a
     baseline JPEG file, decoded on the device (Line3D.add_image_jpeg); or a uint8 array H x W or H x W x 3, decoded by the caller; or an image
     in device memory (a torch device tensor, a capi.device_image descriptor), read where it lies --, K from the focal length and the image size, the image undistorted with the camera's coefficients and its
@@ -162,12 +166,15 @@ def reconstruct_from_images(scene: SfmScene, load_image, data_directory, out_dir
     refine: the 3-D lines are refined against the 2-D segments of their clusters (Line3D.set_refinement, defaults) before they are written.
     alpha, out_size (either given; "A REMAP" in include/line3d_amd.h): a camera with an active lens -- a COLMAP camera's, or an NVM / bundler camera's
     k1, k2 as a BROWN lens -- is PLANNED (capi.undistort_plan(lens, size, alpha or 0, out_size), once per distinct camera) and the view is added
-    with the planned K and size, the blank pixels of the resampling invalid for the detector.  Neither given: what it did before."""
+    with the planned K and size, the blank pixels of the resampling invalid for the detector.  Neither given: what it did before.
+    covisibility: as in reconstruct."""
     import os
     from .pipeline import Line3D
     l3d = Line3D(data_directory, matchingNeighbors=neighbors, device=device, **line3d_kwargs)
     if refine:
         l3d.set_refinement(True)
+    if covisibility != "host":
+        l3d.set_covisibility(covisibility)
     entries = []
     planned = {}            # (lens, source size) -> (K, size): one plan per distinct camera
 
