@@ -532,6 +532,12 @@ int l3d_last_chain_routes(l3d_ctx* ctx, int* n_scanned, int* n_run_tables);
 /* the lanes that share a run on the run-table route, from option rt_g and the average run of the lists seen so far (tests; host only, no
  * context): a power of two in [1, 64] whatever the option holds */
 int l3d_test_rt_lanes(int opt, double avg_run);
+/* the size the single-GPU chain grows its kept arena to after a view overflowed it (tests; host only, no context, no device): arena_cap records
+ * overflowed with kept_base in use, the view keeps n_want, `done` of the call's `span` views are finished, free_bytes of HBM are free (UINT64_MAX:
+ * not known), turn_room records are a turn's room (0: none), the chain transposes early / builds the products.  out = { new capacity, records
+ * needed, records that fit, bytes counted per record, bytes kept back }; L3D_OK, or L3D_ERR_NOMEM when what fits does not do */
+int l3d_test_arena_regrow(uint64_t arena_cap, uint64_t kept_base, int n_want, int done, int span, uint64_t free_bytes, uint64_t turn_room,
+                          int early, int products, uint64_t out[5]);
 
 /* contract math exported for tests (device evaluation of c_expf / c_acosf / c_acos) */
 int l3d_test_contract_math(l3d_ctx* ctx, const float* x, int n, float* out_expf, float* out_acosf, double* out_acos);

@@ -498,6 +498,17 @@ def rt_lanes(opt: int, avg_run: float) -> int:
     return int(load_library().l3d_test_rt_lanes(C.c_int(int(opt)), C.c_double(float(avg_run))))
 
 
+def arena_regrow(arena_cap, kept_base, n_want, done, span, free_bytes, turn_room, early, products) -> dict:
+    """l3d_test_arena_regrow: the size the chain grows its kept arena to after an overflow (free_bytes 2**64 - 1: not known) -- host only, no
+    context, no device.  -> dict(ok, new_cap, need, fits, per_rec, reserve); ok False: the chain would fail with L3D_ERR_NOMEM"""
+    out = (C.c_uint64 * 5)()
+    rc = load_library().l3d_test_arena_regrow(C.c_uint64(arena_cap), C.c_uint64(kept_base), C.c_int(n_want), C.c_int(done), C.c_int(span),
+                                              C.c_uint64(free_bytes), C.c_uint64(turn_room), C.c_int(bool(early)), C.c_int(bool(products)), out)
+    if rc not in (0, 3):
+        raise L3DError("l3d_test_arena_regrow: error %d" % rc)
+    return dict(ok=rc == 0, new_cap=int(out[0]), need=int(out[1]), fits=int(out[2]), per_rec=int(out[3]), reserve=int(out[4]))
+
+
 # dtype codes of l3d_device_image (L3D_U8 ...)
 U8, U16, F16, F32 = 0, 1, 2, 3
 _TYPESTR = {"|u1": U8, "<u2": U16, "<f2": F16, "<f4": F32}

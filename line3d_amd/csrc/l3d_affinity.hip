@@ -535,16 +535,14 @@ int scan_excl(l3d_ctx* c, const int* in, int* out, int n, hipStream_t st)
 
 namespace {
 
-// a device buffer grown WITHOUT losing its first `used` bytes (DevBuf::reserve drops the content)
+// a list of passed candidates grown with half as much again on top, its first `used` bytes kept (DevBuf::grow_keep)
 int grow_keep(l3d_ctx* c, DevBuf& b, size_t bytes, size_t used, hipStream_t st)
 {
     if (bytes <= b.cap) return L3D_OK;
     const size_t want = bytes + bytes / 2 + 4096;
-    void* np = nullptr;
-    if (hipMalloc(&np, want) != hipSuccess) { (void)hipGetLastError(); return fail(c, L3D_ERR_NOMEM, "affinity fill: growing the list of passed candidates to " + std::to_string(want >> 20) + " MB"); }
-    if (used && b.p) { HIPCHK(c, hipMemcpyAsync(np, b.p, used, hipMemcpyDeviceToDevice, st)); HIPCHK(c, hipStreamSynchronize(st)); }
-    if (b.p) (void)hipFree(b.p);
-    b.p = np; b.cap = want;
+    const hipError_t e = b.grow_keep(want, used, st);
+    if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(c, L3D_ERR_NOMEM, "affinity fill: growing the list of passed candidates to " + std::to_string(want >> 20) + " MB"); }
+    if (e != hipSuccess) return fail(c, L3D_ERR_HIP, std::string("affinity fill: copying the passed candidates over: ") + hipGetErrorString(e));
     return L3D_OK;
 }
 

@@ -340,6 +340,605 @@ int upload_rtinfo(l3d_ctx* c, const l3d_chain_view* views, int n_views, const st
 
 }  // namespace
 
+namespace {
+
+// run-ahead depths, A/B measured on one box (ms per config-2 pass): (12, 24) 19.1, (6, 12) 18.7, (4, 8) 18.4, (2, 4) 18.3,
+// (24, 40) 20.0 -- a shallow queue keeps the stage-1 candidates of a view cache-warm until its chain consumes them
+// the ring covers every view that can be in flight between the one being collected and the newest stage 1: after an
+// overflow ALL of them are refilled before any of their chains runs again (bit rows and stage-1 candidates alike)
+constexpr int kAhead = L3D_AHEAD, kStage1Ahead = L3D_S1AHEAD, kRing = kAhead + kStage1Ahead + 3;
+
+// The delivery thread of a chain with a callback: finished views are handed to it in order (push); it copies a view's kept slice and depth pairs to
+// the host (copy stream, SDMA) and runs the caller's bookkeeping -- so the ~13 launches per view of the enqueueing thread are never held up by host
+// work.  A resident run (no callback) hands nothing to the host: no thread, push only counts the kept records.
+class Delivery {
+public:
+    Delivery(l3d_ctx* c_, const l3d_chain_view* views_, const std::vector<ViewDev>& vd_, l3d_chain_callback cb_, void* user_)
+        : c(c_), views(views_), vd(vd_), cb(cb_), user(user_) { if (cb) th = std::thread([this]() { run(); }); }
+    ~Delivery() { finish(); }
+    void push(int k, int verified, const ChainResult& r)
+    {
+        if (!cb) { if (verified) kept_total += r.n_kept; return; }
+        { std::lock_guard<std::mutex> lk(mu); work.push_back(Item{ k, verified, r }); }
+        cv_work.notify_one();
+    }
+    void wait_idle()                                    // every handed-over view has left the device arena
+    {
+        if (!cb) return;
+        std::unique_lock<std::mutex> lk(mu);
+        cv_idle.wait(lk, [&]() { return work.empty() && !busy; });
+    }
+    bool failed() { std::lock_guard<std::mutex> lk(mu); return rc != L3D_OK; }
+    // the queue drained and the thread joined: the first delivery's error (text: its message), or L3D_OK
+    int finish(std::string* text = nullptr)
+    {
+        if (th.joinable()) {
+            { std::lock_guard<std::mutex> lk(mu); done = true; }
+            cv_work.notify_one();
+            th.join();
+        }
+        if (text) *text = err;
+        return rc;
+    }
+    double kept_total = 0, t_cb = 0, t_d2h = 0;
+
+private:
+    struct Item { int k; int verified; ChainResult r; };
+    void run()
+    {
+        (void)hipSetDevice(c->device);
+        for (;;) {
+            Item it;
+            {
+                std::unique_lock<std::mutex> lk(mu);
+                cv_work.wait(lk, [&]() { return done || !work.empty(); });
+                if (work.empty()) return;
+                it = work.front();
+                work.pop_front();
+                busy = true;
+            }
+            int it_rc = L3D_OK;
+            std::string it_err;
+            if (rc == L3D_OK) deliver(it, it_rc, it_err);
+            {
+                std::lock_guard<std::mutex> lk(mu);
+                if (it_rc && rc == L3D_OK) { rc = it_rc; err = it_err; }
+                busy = false;
+            }
+            cv_idle.notify_all();
+        }
+    }
+    void deliver(const Item& it, int& it_rc, std::string& it_err)
+    {
+        const l3d_chain_view& v = views[it.k];
+        const ViewDev& d = vd[(size_t)it.k];
+        if (!it.verified) {                     // cudawrapper.cu:877-878: nothing to match, the caller keeps its list
+            if (cb(user, it.k, 0, nullptr, 0, nullptr, 0, 0)) { it_rc = L3D_ERR_INVALID; it_err = "callback failed"; }
+            return;
+        }
+        const double td0 = now_s();
+        // the kept list lands in the pinned arena, where it stays valid for the caller until the next chain starts
+        hipError_t e = hipSuccess;
+        l3d_match* kept_host = static_cast<l3d_match*>(c->pin_arena.alloc((size_t)it.r.n_kept * sizeof(Match) + 16, &e));
+        if (e == hipSuccess) e = c->ch_pin_best.reserve((size_t)v.S_src * 8 + 16);
+        if (e == hipSuccess && it.r.n_kept)
+            e = hipMemcpyAsync(kept_host, c->ch_kept.as<Match>() + it.r.kept_base, (size_t)it.r.n_kept * sizeof(Match), hipMemcpyDeviceToHost, c->copy_stream);
+        if (e == hipSuccess && v.S_src) e = hipMemcpyAsync(c->ch_pin_best.p, d.best, (size_t)v.S_src * 8, hipMemcpyDeviceToHost, c->copy_stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->copy_stream);
+        if (e != hipSuccess) { it_rc = L3D_ERR_HIP; it_err = std::string("chain delivery, view ") + std::to_string(it.k) + ": " + hipGetErrorString(e); return; }
+        float* best = c->ch_pin_best.as<float>();
+        int nb = 0;
+        if (it.r.R > 0)
+            for (int s = 0; s < v.S_src; ++s)
+                if (best[2 * s] != -1.0f) { best[2 * nb] = best[2 * s]; best[2 * nb + 1] = best[2 * s + 1]; ++nb; }   // in place: nb <= s
+        kept_total += it.r.n_kept;
+        const double tc0 = now_s();
+        t_d2h += tc0 - td0;
+        if (cb(user, it.k, 1, kept_host, it.r.n_kept, best, nb, it.r.R)) { it_rc = L3D_ERR_INVALID; it_err = "callback failed"; }
+        t_cb += now_s() - tc0;
+    }
+
+    l3d_ctx* c; const l3d_chain_view* views; const std::vector<ViewDev>& vd; l3d_chain_callback cb; void* user;
+    std::mutex mu;
+    std::condition_variable cv_work, cv_idle;
+    std::deque<Item> work;
+    bool done = false, busy = false;
+    int rc = L3D_OK;
+    std::string err;
+    std::thread th;
+};
+
+// One call of run_chain: what its phases share.  The phases run in the order run_chain names them; every HIP call keeps its stream and its place.
+struct ChainRun {
+    l3d_ctx* c; const l3d_chain_view* views; int n_views; l3d_chain_callback cb; const l3d_dense_map* map; int k_begin, k_end; const ChainPreload* pre; bool ranged;
+    hipStream_t st = nullptr, s1 = nullptr, sp = nullptr;   // phase 2 (the chain proper) | stage 1, running ahead | the early transposes' side stream
+    std::vector<ViewDev> vd;
+    ChainLayout L;
+    const unsigned char* dtab = nullptr;
+    int maxN = 0;
+    bool fused_rows = false;
+    // per-view results are written by the kernels straight into host-mapped pinned memory (no copy operations on the streams)
+    ChainResult *hres = nullptr, *hres_dev = nullptr;
+    int *hstats = nullptr, *hstats_dev = nullptr;
+    std::vector<hipEvent_t> ev1, ev;    // a view's stage 1 / its chain is through
+    int k_p1 = 0, k_enq = 0;            // next view whose stage 1 / whose phase 2 is enqueued
+    double pairs = 0;
+    size_t cand_cap = 0, arena_cap = 0, turn_room = 0;
+    bool same_scene = false;
+    std::vector<char> has_rec;          // views that own a slice of the arena: the range's verified views and the preloaded ones (a view's slice starts where the previous such view's ended)
+    long long pre_records = 0;
+    Products& PE;
+    bool early = false;
+    int early_batch = 1, early_next = 0, early_maxSt = 1;   // views [0, early_next) have their transposes launched
+    double t_ev1 = 0, t_wait = 0;       // host time spent waiting for stage-1 statistics / for view results
+    double kept_seen = 0;               // kept records / views whose result record the host has read (sizes the source scans)
+    int views_seen = 0;
+    double raw_sum = 0;
+    int rc_final = L3D_OK;
+    double t_enter = 0, t_setup0 = 0, t_loop0 = 0;
+
+    ChainRun(l3d_ctx* c_, const l3d_chain_view* views_, int n_views_, l3d_chain_callback cb_, const l3d_dense_map* map_, int k_begin_, int k_end_, const ChainPreload* pre_, bool ranged_)
+        : c(c_), views(views_), n_views(n_views_), cb(cb_), map(map_), k_begin(k_begin_), k_end(k_end_), pre(pre_), ranged(ranged_),
+          ev1((size_t)n_views_, nullptr), ev((size_t)n_views_, nullptr), has_rec((size_t)n_views_, 0), PE(c_->products) {}
+
+    bool hip_ok(hipError_t e, const char* what)
+    {
+        if (e == hipSuccess) return true;
+        rc_final = fail(c, L3D_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+        return false;
+    }
+    // (the four depths of a stage-1 pair are triangulated once, by k_pair_fill: it runs ahead on the stage-1 stream, its true row counts are in place
+    // before the chain counts the view's reverse matches on top)
+    PairArgs pair_args(int k) const { return chain_pair_args(c, views[k], vd[(size_t)k], dtab); }
+    uint2* ringA_meta(int k) const { return c->ch_ringA_meta.as<uint2>() + (size_t)(k % kRing) * cand_cap; }
+    float4* ringA_depths(int k) const { return c->ch_ringA_depths.as<float4>() + (size_t)(k % kRing) * cand_cap; }
+    bool early_fits() const { return early && arena_cap < 0x7ffffff0ull; }      // (beyond 2^31 records the end transposes block by block)
+
+    int setup();
+    void restrict_to_range();
+    int plan_capacities();
+    int plan_early();
+    int reserve_caps();
+    int take_over_preload();
+    void enqueue_fillA(int k, hipStream_t s);
+    int enqueue_stage1(int k);
+    int enqueue_view(int k);
+    void launch_early(int k0, int n, double avg_run, hipStream_t s);
+    bool grow_buffer(DevBuf& b, size_t bytes, size_t used, const char* what);
+    bool grow_arena(int k, const ChainResult& r);
+    bool restart_at(int k, const ChainResult& r, Delivery& dl);
+    int products_tail(l3d_chain_summary* summary, int64_t* n_pot);
+    int finish(const Delivery& dl, double t_prod0);
+};
+
+// ---- streams, validation, table layout and upload, per-view slices of the whole-run arenas (l3d_chain_common.hip: shared with the sharded chain),
+// the result records and the event that lets stage 1 start
+int ChainRun::setup()
+{
+    c->pin_arena.reset();
+    st = c->stream;
+    s1 = c->stage1_stream;              // stage 1 runs ahead here, concurrently with the latency-bound kernels of phase 2
+    if (c->opt.chain_serial != 0) s1 = st;      // diagnostic: one stream, kernels one at a time (isolated durations)
+    (void)hipGetLastError();            // errors of earlier, already reported calls are not ours
+    if (int rc = chain_plan_views(c, views, n_views, 0, 1, vd, L, "l3d_match_chain")) return rc;
+    if (int rc = chain_upload_tables(c, views, n_views, vd, L, st)) return rc;
+    // run tables (round 6): the kept writer fills one per view and leaves a (local camera << 16 | target) word per record in the side array
+    // (ch_keptcam); later views and the products read runs instead of scanning lists
+    if (int rc = chain_assign_arenas(c, views, n_views, vd, L, true, true, kRing, st, true)) return rc;
+    {
+        std::vector<const int*> rts((size_t)n_views);
+        for (int k = 0; k < n_views; ++k) rts[(size_t)k] = vd[(size_t)k].rt;
+        if (int rc = upload_rtinfo(c, views, n_views, rts, L.maxS, L.maxN, st)) return rc;
+    }
+    dtab = L.dtab;
+    maxN = L.maxN;
+    // the row starts of the stage-1 candidates are formed inside k_pair_fill from k_pair_mask's counters and their block sums: no
+    // scan launch on the stage-1 stream (the longer of the two), no statistics for the host to wait for -- up to 96 neighbours
+    fused_rows = chain_fused_rows(maxN);
+    if (ranged) restrict_to_range();    // (after the arenas are laid out for all views: a view keeps its slices whatever the range is)
+    HIPCHK(c, c->ch_res.reserve((size_t)n_views * sizeof(ChainResult) + 16));
+    HIPCHK(c, c->ch_flags.reserve(64));
+    HIPCHK(c, c->ch_pin_res.reserve((size_t)n_views * (sizeof(ChainResult) + 8) + 64));
+    HIPCHK(c, hipMemsetAsync(c->ch_res.p, 0, (size_t)n_views * sizeof(ChainResult), st));
+    HIPCHK(c, hipMemsetAsync(c->ch_flags.p, 0, 64, st));
+    {   // stage 1 starts after the tables and the zeroed row counts are in place
+        hipEvent_t ready = get_local_event(c);
+        HIPCHK(c, hipEventRecord(ready, st));
+        HIPCHK(c, hipStreamWaitEvent(s1, ready, 0));
+        put_local_event(c, ready);
+    }
+    hres = c->ch_pin_res.as<ChainResult>();
+    hstats = reinterpret_cast<int*>(c->ch_pin_res.as<unsigned char>() + (size_t)n_views * sizeof(ChainResult));
+    if (ranged) memset(hres, 0, (size_t)n_views * sizeof(ChainResult));          // (views outside the range: no records, whatever an earlier chain left here)
+    HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&hres_dev), hres, 0));
+    hstats_dev = reinterpret_cast<int*>(reinterpret_cast<unsigned char*>(hres_dev) + (size_t)n_views * sizeof(ChainResult));
+    { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return fail(c, L3D_ERR_HIP, std::string("chain setup: ") + hipGetErrorString(e_)); }
+    return L3D_OK;
+}
+
+// views outside [k_begin, k_end) launch nothing; the pair counts that size the capacities are the range's
+void ChainRun::restrict_to_range()
+{
+    double p_range = 0, p_max = 0;
+    for (int k = 0; k < n_views; ++k) {
+        if (k < k_begin || k >= k_end) { vd[(size_t)k].verified = false; continue; }
+        if (!vd[(size_t)k].verified) continue;
+        double p = 0;
+        for (int j = 0; j < views[k].n_tbm; ++j) p += (double)views[k].S_src * views[k].offsets[2 * views[k].to_be_matched[j] + 1];
+        p_range += p; p_max = std::max(p_max, p);
+    }
+    L.pairs = p_range; L.max_pairs = p_max;
+}
+
+// ---- capacities (guarded on the device; an overflow restarts the chain at that view with more room): first guesses, what the last pass over the
+// same scene ended with, option arena_guess, the tests' caps, the records of a preload, a turn's room
+int ChainRun::plan_capacities()
+{
+    pairs = L.pairs;
+    c->stats[0] = pairs;
+    // first guess from the pair counts (raw density ~6 %, kept ~0.2 % of the pairs on the synthetic scenes)
+    cand_cap = chain_first_cand_cap(L.max_pairs);
+    // The kept arena's first guess is GENEROUS (5 % of the pairs: the densest synthetic scene keeps 4.5 %, config 2 0.16 %) within 35 % of the free HBM: memory that is
+    // never written costs an allocation of a millisecond when it is the process's first big one, while growing later means a hipMalloc of tens of GB in a process that
+    // has freed big buffers before -- measured at 256 x 4000 x 24: 0.5 ms for the first 59 GB, 1.8-2.2 s for 75 GB at the second regrow, 25 ms per GB at 40 views in one
+    // run of three (profiles/r6_first_pass_allocations.txt).  A job sized by memory gives its capacities (l3d_set_chain_capacities) or the old guess (L3D_ARENA_GUESS=4)
+    arena_cap = (size_t)(pairs * 0.004) + 1048576;
+    // a pass over the same scene (same number of views, same pair count) starts with what the previous one ended up needing: no
+    // overflow, no restart, no allocation after the first pass
+    same_scene = c->chain_seen_views == n_views && c->chain_seen_pairs == pairs;
+    if (same_scene) { cand_cap = std::max(cand_cap, c->chain_seen_cand_cap); arena_cap = std::max(arena_cap, c->chain_seen_arena_cap); }
+    else if (c->opt.arena_guess > 4 && !ranged && !pre) {      // (a block of views of a partitioned job is sized by memory: it keeps the small guess and grows)
+        size_t fr = 0, tot = 0;
+        if (hipMemGetInfo(&fr, &tot) == hipSuccess) {
+            const size_t want = (size_t)(pairs * 0.001 * c->opt.arena_guess) + 1048576, fits = (size_t)((double)fr * 0.35 / 40.0);
+            arena_cap = std::max(arena_cap, std::min(want, fits));
+        }
+        (void)hipGetLastError();
+    }
+    if (c->test_cand_cap) cand_cap = c->test_cand_cap;      // tests: force the overflow / restart path
+    if (c->test_arena_cap) arena_cap = c->test_arena_cap;
+    for (int k = 0; k < n_views; ++k) has_rec[(size_t)k] = vd[(size_t)k].verified ? 1 : 0;
+    if (pre) {
+        if (pre->k1 != k_begin || pre->k0 < 0 || pre->k0 > pre->k1 || (int)pre->n_kept.size() != pre->k1 - pre->k0 || (int)pre->R.size() != pre->k1 - pre->k0) return fail(c, L3D_ERR_INVALID, "match_chain: bad preload");
+        for (int k = pre->k0; k < pre->k1; ++k) { pre_records += pre->n_kept[(size_t)(k - pre->k0)]; has_rec[(size_t)k] = views[k].n_tbm > 0 ? 1 : 0; }
+        arena_cap += (size_t)pre_records;
+        kept_seen = (double)pre_records;
+        views_seen = pre->k1 - pre->k0;
+    }
+    // a turn of a node object that hands the chain over (match_chain_turn) under option regrow_free_mb: the room binds on everything the turn's arena
+    // takes -- this first guess, the regrow below, the slices its share puts behind the records -- as it does on the compact arena of a plain turn
+    turn_room = c->turn_arena_room;
+    if (turn_room) {
+        if ((size_t)pre_records + 65536 > turn_room)
+            return fail(c, L3D_ERR_NOMEM, "match_chain: the " + std::to_string(pre_records) + " records taken over from the turn before need more than the room for " + std::to_string(turn_room) + " records (" +
+                                          std::to_string(c->opt.regrow_free_mb) + " MB at " + std::to_string(sizeof(Match) + 4) + " B per record)");
+        arena_cap = std::min(arena_cap, turn_room);
+    }
+    return L3D_OK;
+}
+
+// early pair transposes (round 6, l3d_products.hip): a (view, camera) pair of the potential-correspondence build depends on that view's kept list alone, so
+// it is transposed on a side stream right behind the view's kept writer -- next to the following views' chains -- and the end of matchViews finds only the rows
+// left.  Entries live in an array aligned with the kept arena (a view's pairs hold exactly its records).  L3D_PROD_EARLY=0: all transposes at the end (A/B)
+// Long lists only (> 2^18 records per view: what the last pass over this scene kept, or the arena's first guess), view by view.  At config 2 (36 k records per view)
+// two launches and an event per view cost more than the 0.2 ms of transposes they take off the end (12.60 vs 12.41 ms per pass); eight views per launch still lose
+// (12.52 vs 12.41; the first pass pays 5 ms for the side stream and its buffers).  Option values 2 / 3 force a view / eight views per launch (tests)
+int ChainRun::plan_early()
+{
+    early = map && !ranged && !pre && !cb && c->opt.prod_early != 0 && c->opt.prod_transpose != 0 && maxN > 0;
+    early_batch = c->opt.prod_early == 3 ? 8 : 1;
+    if (early && c->opt.prod_early == 1) {
+        const double per_view = (same_scene && c->chain_seen_kept > 0 ? c->chain_seen_kept : pairs * 0.004) / std::max(1, n_views);
+        early = per_view > (double)chain_long_list(c->opt);
+    }
+    if (!early) return L3D_OK;
+    std::vector<int> tab((size_t)n_views * maxN * 2 + (size_t)n_views * (sizeof(EarlyView) / 4), 0);       // [St | boff_off], n_views x maxN each; the views' descriptors behind them
+    PE.e_boff_off.assign((size_t)n_views * maxN, 0);
+    long long nb = 0;
+    for (int k = 0; k < n_views && early; ++k) {
+        if (!vd[(size_t)k].verified) continue;
+        for (int q = 0; q < views[k].N; ++q) {
+            const uint32_t* it = std::lower_bound(map->view_ids, map->view_ids + map->n_views, views[k].local2global[q]);
+            if (it == map->view_ids + map->n_views || *it != views[k].local2global[q]) continue;
+            const int t = (int)(it - map->view_ids), St = map->seg_base[t + 1] - map->seg_base[t];
+            if (St <= 0) continue;
+            tab[(size_t)k * maxN + q] = St;
+            tab[(size_t)n_views * maxN + (size_t)k * maxN + q] = (int)nb;
+            PE.e_boff_off[(size_t)k * maxN + q] = (int)nb;
+            nb += St + 1;
+            early_maxSt = std::max(early_maxSt, St);
+            if (nb > 0x7ffffff0ll) early = false;
+        }
+    }
+    if (!early) return L3D_OK;
+    if (!c->prod_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->prod_stream, hipStreamNonBlocking));
+    sp = c->prod_stream;
+    HIPCHK(c, PE.e_tab.reserve(tab.size() * 4 + 64));
+    static_assert(sizeof(EarlyView) % 8 == 0, "descriptor size");
+    {
+        const int* dt = PE.e_tab.as<int>();
+        EarlyView* hv = reinterpret_cast<EarlyView*>(tab.data() + (size_t)n_views * maxN * 2);       // (n_views * maxN * 2 ints: 8-byte aligned)
+        for (int k = 0; k < n_views; ++k) {
+            EarlyView e;
+            e.rt = vd[(size_t)k].verified ? vd[(size_t)k].rt : nullptr;
+            e.St = dt + (size_t)k * maxN; e.boff_off = dt + (size_t)n_views * maxN + (size_t)k * maxN;
+            e.k = k; e.S = views[k].S_src; e.N = views[k].N; e.pad = 0;
+            hv[k] = e;
+        }
+    }
+    HIPCHK(c, PE.e_cnt.reserve((size_t)n_views * maxN * 4 + 64));
+    HIPCHK(c, PE.e_poff.reserve((size_t)n_views * maxN * 4 + 64));
+    HIPCHK(c, PE.e_boff.reserve((size_t)nb * 4 + 64));
+    HIPCHK(c, hipMemcpyAsync(PE.e_tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipStreamSynchronize(st));                    // (`tab` is pageable and leaves scope)
+    return L3D_OK;
+}
+
+// the buffers sized by the capacities (at the start, and again after an overflow)
+int ChainRun::reserve_caps()
+{
+    if (int rc = chain_reserve_candidates(c, L, cand_cap, kRing)) return rc;
+    HIPCHK(c, c->ch_kept.reserve(arena_cap * sizeof(Match)));
+    HIPCHK(c, c->ch_keptcam.reserve(arena_cap * 4 + 64));
+    if (early_fits()) { HIPCHK(c, PE.e_E.reserve(arena_cap * 4 + 64)); HIPCHK(c, PE.e_T.reserve(arena_cap * 4 + 64)); }
+    return L3D_OK;
+}
+
+// the views [pre->k0, pre->k1) taken over from another rank: their records at the head of the arena with their result records, their best depth pairs
+// and positions in their own slices, their side words and run tables rebuilt
+int ChainRun::take_over_preload()
+{
+    if (!pre || pre->k1 <= pre->k0) return L3D_OK;
+    long long base = 0;
+    size_t so = 0;
+    for (int k = pre->k0; k < pre->k1; ++k) {
+        ChainResult r;
+        r.kept_base = (uint64_t)base; r.n_want = 0; r.n_kept = has_rec[(size_t)k] ? pre->n_kept[(size_t)(k - pre->k0)] : 0; r.R = pre->R[(size_t)(k - pre->k0)]; r.overflow = 0;
+        hres[k] = r;
+        base += r.n_kept;
+        if (views[k].n_tbm > 0) {
+            // (chain_assign_arenas gave every verified view of the schedule its slices, whatever the range)
+            ChainViewDev& d = vd[(size_t)k];
+            if (views[k].S_src > 0 && d.best && pre->best) HIPCHK(c, hipMemcpyAsync(d.best, pre->best + so, (size_t)views[k].S_src * 8, hipMemcpyDeviceToDevice, st));
+            if (views[k].S_src > 0 && d.bestpos && pre->bestpos) HIPCHK(c, hipMemcpyAsync(d.bestpos, pre->bestpos + so, (size_t)views[k].S_src * 4, hipMemcpyDeviceToDevice, st));
+            so += (size_t)views[k].S_src;
+        }
+    }
+    if (base > 0) HIPCHK(c, hipMemcpyAsync(c->ch_kept.p, pre->records, (size_t)base * sizeof(Match), hipMemcpyDeviceToDevice, st));
+    if (base > 0) {
+        // the taken-over lists did not come out of this chain's kept writer: their side array and run tables are rebuilt from the records
+        std::vector<RtJob> jobs;
+        std::vector<const unsigned*> l2g;
+        for (int k = pre->k0; k < pre->k1; ++k) {
+            if (!has_rec[(size_t)k] || hres[k].n_kept == 0) continue;
+            if (!vd[(size_t)k].rt) return fail(c, L3D_ERR_INVALID, "match_chain: view " + std::to_string(k) + " was taken over with records but has no run table");
+            RtJob j;
+            j.recs = c->ch_kept.as<Match>() + hres[k].kept_base; j.qt = c->ch_keptcam.as<unsigned>() + hres[k].kept_base; j.rt = vd[(size_t)k].rt;
+            j.ids = nullptr; j.qs = nullptr; j.n = hres[k].n_kept; j.S = views[k].S_src; j.N = views[k].N; j.pad = 0;
+            jobs.push_back(j);
+            l2g.push_back(views[k].local2global);
+        }
+        if (!jobs.empty()) {
+            int bad = 0;
+            if (int rc = rebuild_run_tables(c, jobs, l2g, st, &bad)) return rc;
+            if (bad) return fail(c, L3D_ERR_INVALID, "match_chain: the lists taken over from another rank are not ordered (segment, camera) -- no run tables");
+        }
+    }
+    HIPCHK(c, hipMemcpyAsync(c->ch_res.as<ChainResult>() + pre->k0, hres + pre->k0, (size_t)(pre->k1 - pre->k0) * sizeof(ChainResult), hipMemcpyHostToDevice, st));
+    return L3D_OK;
+}
+
+// ---- phase 1 (stage 1 of a view: pair test -> bit rows -> row counts -> statistics) is independent of the
+// chain; it is enqueued a window ahead of phase 2 so that the GPU always has work while the host trails behind
+// row starts + depth records of a view's stage-1 candidates alone (its reverse matches are not known yet), into the view's ring slot; k_place
+// later moves them into the combined order on the chain stream, which stays short.  (Measured: triangulating on the chain stream instead was 5 %
+// slower on config 2; letting the verification read the stage-1 candidates in place instead of copying them 20 % SLOWER -- the copy is a streaming
+// pass that leaves the candidates cache-hot for the latency-bound kernels that follow.)
+void ChainRun::enqueue_fillA(int k, hipStream_t s)
+{
+    const ViewDev& d = vd[(size_t)k];
+    const PairArgs pa = chain_fill_args(pair_args(k), d, fused_rows, cand_cap);
+    { ProfScope p(c, "pair_fill", s); launch_pair_fill(pa, d.rowA, ringA_meta(k), ringA_depths(k), s); }
+}
+int ChainRun::enqueue_stage1(int k)
+{
+    if (!vd[(size_t)k].verified) return L3D_OK;
+    hstats[2 * k] = hstats[2 * k + 1] = 0;
+    if (views[k].S_src > 0) {
+        const PairArgs pa = pair_args(k);
+        {   // bit rows + row counts (added into the rows zeroed at chain start) in one launch
+            const PairArgs pm = chain_mask_args(pa, vd[(size_t)k], fused_rows);
+            ProfScope p(c, "pair_mask", s1);
+            launch_pair_mask(pm, vd[(size_t)k].maxW, s1, c->opt.pair_spb);
+        }
+        // (unfused) row starts of the stage-1 candidates + their statistics straight into host-mapped memory (one launch)
+        if (!fused_rows) { ProfScope p(c, "scan", s1); launch_scan(vd[(size_t)k].rowcnt, vd[(size_t)k].rowA, views[k].S_src * views[k].N, nullptr, s1, nullptr, views[k].N, 0, views[k].S_src, hstats_dev + 2 * k); }
+        // the ring slot was last used by view k - kRing: wait until its chain has consumed it
+        for (int j = k - kRing; j >= 0; j -= kRing) if (ev[(size_t)j]) { HIPCHK(c, hipStreamWaitEvent(s1, ev[(size_t)j], 0)); break; }
+        enqueue_fillA(k, s1);
+    }
+    ev1[(size_t)k] = get_local_event(c);
+    HIPCHK(c, hipEventRecord(ev1[(size_t)k], s1));
+    return L3D_OK;
+}
+
+// ---- phase 2 of view k on the chain stream (behind the stage 1 of the views up to kStage1Ahead in front of it): its candidates collected, verified, its
+// kept records written behind the previous view's, the event the host trails on -- and the early transposes of the views that are due
+int ChainRun::enqueue_view(int k)
+{
+    const l3d_chain_view& v = views[k];
+    const ViewDev& d = vd[(size_t)k];
+    while (k_p1 < n_views && k_p1 <= k + kStage1Ahead) { int rc = enqueue_stage1(k_p1); if (rc) return rc; ++k_p1; }
+    if (!d.verified) return L3D_OK;
+    const double te0 = now_s();
+    if (!fused_rows) HIPCHK(c, hipEventSynchronize(ev1[(size_t)k]));          // its stage-1 statistics (enqueued a window earlier)
+    t_ev1 += now_s() - te0;
+    HIPCHK(c, hipStreamWaitEvent(st, ev1[(size_t)k], 0));
+    PairArgs pa = pair_args(k);
+    pa.cand_cap = (int)cand_cap;
+    const int S = v.S_src, N = v.N;
+    const size_t nrow = (size_t)S * N;
+    Match* arena = c->ch_kept.as<Match>();
+    ChainResult* dres = c->ch_res.as<ChainResult>();
+    const int* d_sc = reinterpret_cast<const int*>(dtab + d.o_sc);
+    (void)hipGetLastError();
+    const int* d_si = reinterpret_cast<const int*>(dtab + d.o_si);
+    unsigned* cams = c->ch_keptcam.as<unsigned>();
+    // sized from the lists the chain has seen so far (the host trails a few views behind); short lists (config 2 keeps 36 k matches per view) are
+    // scanned record by record
+    const CollectRule rule = chain_collect_rule(c->opt, views_seen > 0, views_seen > 0 ? kept_seen / views_seen : 0.0, S, N, L.maxS);
+    ++c->chain_routes[rule.rt ? 1 : 0];
+    CollectIn ci;
+    ci.arena = arena; ci.dres = dres; ci.cams = cams; ci.info = c->ch_rtinfo.as<RtInfo>(); ci.d_sc = d_sc; ci.d_si = d_si;
+    ci.d_ss = reinterpret_cast<const int*>(dtab + d.o_ss); ci.d_tbm = pa.tbm; ci.n_sources = v.n_sources; ci.n_tbm = v.n_tbm; ci.view_id = v.view_id; ci.S = S; ci.N = N;
+    ci.rowcnt = d.rowcnt; ci.rowA = d.rowA; ci.metaA = ringA_meta(k); ci.depthsA = ringA_depths(k); ci.cand_cap = cand_cap;
+    ci.sort_apart = !(c->verify_mode == 0 && verify_window_supported(N));     // (the window kernel orders the runs itself)
+    enqueue_collect(c, ci, rule, st);
+    VerifyArgs va = chain_verify_args(c, v, d, dtab, cand_cap);
+    va.res = dres + k;
+    // (fused row starts: no statistics -- the largest LDS image the budget allows)
+    chain_launch_verify(c, va, d, d_sc, v.n_sources, fused_rows ? -1 : hstats[2 * k + 1], cand_cap, st);
+    {
+        ProfScope p(c, "kept_write");
+        int pv = k - 1;
+        while (pv >= 0 && !has_rec[(size_t)pv]) --pv;                    // the arena slice starts where the previous verified (or preloaded) view's ended
+        launch_kept_write_chain(va, c->kept_cnt.as<int>(), (int)nrow, pv >= 0 ? dres + pv : nullptr, (unsigned long long)arena_cap, dres + k, hres_dev + k,
+                                reinterpret_cast<const unsigned*>(dtab + d.o_l2g), arena, st, (map || ranged) ? d.bestpos : nullptr, cams, d.rt, S);
+    }
+    { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return fail(c, L3D_ERR_HIP, std::string("chain launch, view ") + std::to_string(k) + ": " + hipGetErrorString(e_)); }
+    // (with a delivery callback the host starts D2H copies of device memory once it has seen this event: a default, fenced event then)
+    if (!ev[(size_t)k]) ev[(size_t)k] = cb ? get_event(c) : get_local_event(c);
+    HIPCHK(c, hipEventRecord(ev[(size_t)k], st));
+    if (early_fits() && k + 1 - early_next >= early_batch) {
+        HIPCHK(c, hipStreamWaitEvent(sp, ev[(size_t)k], 0));
+        launch_early(early_next, k + 1 - early_next, rule.avg_run, sp);
+        early_next = k + 1;
+    }
+    return L3D_OK;
+}
+// the transposes of the views [k0, k0 + n) on stream s
+void ChainRun::launch_early(int k0, int n, double avg_run, hipStream_t s)
+{
+    launch_early_transposes(c, reinterpret_cast<const EarlyView*>(PE.e_tab.as<int>() + (size_t)n_views * maxN * 2), k0, n, maxN, early_maxSt, c->ch_res.as<ChainResult>(), c->ch_keptcam.as<unsigned>(),
+                            PE.e_cnt.as<int>(), PE.e_poff.as<unsigned>(), PE.e_boff.as<int>(), PE.e_E.as<unsigned>(), PE.e_T.as<unsigned>(), avg_run, s);
+}
+
+// ---- an overflow.  The arena cannot be reallocated without losing earlier lists that later views still read: its used part is copied over
+// (DevBuf::grow_keep), and so are the side words and -- the earlier views' transposed entries move with their records -- the early transposes' entries.
+bool ChainRun::grow_buffer(DevBuf& b, size_t bytes, size_t used, const char* what)
+{
+    const hipError_t e = b.grow_keep(bytes, used, st);
+    return hip_ok(e, e == hipErrorOutOfMemory ? what : "hipMemcpy");
+}
+bool ChainRun::grow_arena(int k, const ChainResult& r)
+{
+    const int n_pre = pre ? pre->k1 - pre->k0 : 0;
+    size_t fr = 0, tot = 0;
+    const bool known = hipMemGetInfo(&fr, &tot) == hipSuccess;
+    if (known && c->opt.regrow_free_mb > 0) fr = std::min(fr, (size_t)c->opt.regrow_free_mb << 20);     // (tests: a card with less room)
+    (void)hipGetLastError();
+    const ArenaRegrow g = chain_arena_regrow(arena_cap, r.kept_base, r.n_want, k - k_begin + n_pre, k_end - k_begin + n_pre, known ? fr : kRegrowFreeUnknown, turn_room, early, map != nullptr);
+    if (!g.ok) {
+        rc_final = fail(c, L3D_ERR_NOMEM, "match_chain: the kept arena of " + std::to_string(arena_cap) + " records is full at view " + std::to_string(k) + " of " + std::to_string(n_views) + " (" +
+                                              std::to_string((size_t)r.kept_base) + " records in use, the view keeps " + std::to_string(r.n_want) + ") and an arena of " +
+                                              std::to_string(g.need) + " records does not fit beside it (room for " + std::to_string(g.fits) + " at " + std::to_string(g.per_rec) + " B per record, " +
+                                              std::to_string(g.reserve >> 20) + " MB kept back; " + std::to_string(fr >> 20) + " of " + std::to_string(tot >> 20) +
+                                              " MB free): l3d_set_chain_capacities sizes the arena up front");
+        return false;
+    }
+    const size_t new_cap = g.new_cap, used = (size_t)r.kept_base;
+    double ms[3] = { 0, 0, 0 };
+    const hipError_t e = c->ch_kept.grow_keep(new_cap * sizeof(Match), used * sizeof(Match), st, ms);
+    if (e == hipErrorOutOfMemory) {
+        (void)hipMemGetInfo(&fr, &tot);
+        rc_final = fail(c, L3D_ERR_NOMEM, "match_chain: growing the kept arena to " + std::to_string(new_cap * sizeof(Match) >> 20) + " MB at view " + std::to_string(k) + " of " + std::to_string(n_views) +
+                                          " (" + std::to_string(used * sizeof(Match) >> 20) + " MB in use, " + std::to_string(fr >> 20) + " of " + std::to_string(tot >> 20) + " MB free): " + hipGetErrorString(e));
+        return false;
+    }
+    if (!hip_ok(e, "hipMemcpy")) return false;
+    if (c->opt.timing) fprintf(stderr, "[l3d match_chain]   arena of %zu MB: hipMalloc %.2f ms, copy of %zu MB %.2f ms, hipFree of the old one %.2f ms\n", new_cap * sizeof(Match) >> 20, ms[0],
+                               used * sizeof(Match) >> 20, ms[1], ms[2]);
+    if (!grow_buffer(c->ch_keptcam, new_cap * 4 + 64, used * 4, "hipMalloc (side words of the kept arena)")) return false;
+    if (early && new_cap < 0x7ffffff0ull && !grow_buffer(PE.e_E, new_cap * 4 + 64, used * 4, "hipMalloc (transposed entries of the kept arena)")) return false;
+    arena_cap = new_cap;
+    return true;
+}
+// View k came back without room for its candidates (1) / its kept matches (2): everything before it is valid and stays in the arena.  The queue and
+// the delivery of earlier views drain, the buffers grow, the ring is refilled and the enqueueing rewinds to k.  false: rc_final says why not
+bool ChainRun::restart_at(int k, const ChainResult& r, Delivery& dl)
+{
+    if (!hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize") || !hip_ok(hipStreamSynchronize(s1), "hipStreamSynchronize")) return false;
+    if (sp && !hip_ok(hipStreamSynchronize(sp), "hipStreamSynchronize")) return false;
+    const double t_restart0 = now_s();
+    dl.wait_idle();
+    if (r.overflow & 1) cand_cap = (size_t)r.R + (size_t)r.R / 4 + 65536;
+    if ((r.overflow & 2) && !grow_arena(k, r)) return false;
+    { int rc = reserve_caps(); if (rc) { rc_final = rc; return false; } }
+    if (c->opt.timing) fprintf(stderr, "[l3d match_chain] view %d of %d overflowed (%d): candidates %zu, arena %zu records; regrown in %.2f ms, %.2f ms into the loop\n", k, n_views, r.overflow, cand_cap, arena_cap,
+                               (now_s() - t_restart0) * 1e3, (now_s() - t_loop0) * 1e3);
+    // the row counts of the views enqueued after k were already incremented by their reverse matches: rebuild
+    // and the stage-1 candidate buffers of every view in flight live in the (re-sized) ring: refill them
+    for (int j = k; j < k_p1; ++j) {
+        if (!vd[(size_t)j].verified || views[j].S_src == 0) continue;
+        if (j < k_enq) {
+            if (!hip_ok(hipMemsetAsync(vd[(size_t)j].rowcnt, 0, (size_t)views[j].S_src * views[j].N * 4, st), "hipMemsetAsync")) return false;
+            if (!fused_rows) launch_row_count(pair_args(j), vd[(size_t)j].rowcnt, st);      // (fused: the upper bounds live in rowub, untouched)
+        }
+        enqueue_fillA(j, st);
+    }
+    k_enq = k;
+    early_next = std::min(early_next, k);           // (the views run again are transposed again)
+    return true;
+}
+
+// ---- the products of matchViews, on the device, from the arena (l3d_products.hip); enqueued behind the last view
+int ChainRun::products_tail(l3d_chain_summary* summary, int64_t* n_pot)
+{
+    std::vector<ProdChainView> pv((size_t)n_views);
+    for (int k = 0; k < n_views; ++k) pv[(size_t)k] = ProdChainView{ vd[(size_t)k].verified ? vd[(size_t)k].best : nullptr, vd[(size_t)k].verified ? vd[(size_t)k].bestpos : nullptr, vd[(size_t)k].verified ? 1 : 0,
+                                                                     vd[(size_t)k].verified ? vd[(size_t)k].rt : nullptr };
+    ProdEarly pe;
+    const bool early_done = early_fits();
+    if (early_done) {
+        if (early_next < n_views) {                     // the last batch's remainder: on the chain's stream, behind the last view
+            launch_early(early_next, n_views - early_next, views_seen > 0 ? kept_seen / views_seen / std::max(1.0, (double)L.maxS * std::max(1, maxN)) : 1.0, st);
+            early_next = n_views;
+        }
+        hipEvent_t e = get_local_event(c);
+        (void)hipEventRecord(e, sp);
+        (void)hipStreamWaitEvent(st, e, 0);
+        put_local_event(c, e);
+        pe.pcnt_kq = PE.e_cnt.as<int>(); pe.poff_kq = PE.e_poff.as<unsigned>(); pe.boff = PE.e_boff.as<int>(); pe.E = PE.e_E.as<unsigned>();
+        pe.boff_off_host = PE.e_boff_off.data(); pe.maxN = maxN;
+    }
+    return build_products(c, views, n_views, pv.data(), hres, map, summary, n_pot, 0, -1, nullptr, c->ch_keptcam.as<unsigned>(), early_done ? &pe : nullptr);
+}
+
+// the timing lines, the streams idle, the events back in their pools, the counters and -- after a pass that succeeded without the tests' caps -- what
+// the next pass over the same scene starts with
+int ChainRun::finish(const Delivery& dl, double t_prod0)
+{
+    if (c->opt.timing)
+        fprintf(stderr, "[l3d match_chain] setup %.2f ms | enqueue + watch loop %.2f ms (waiting: view results %.2f, stage-1 statistics %.2f) | delivery thread: d2h %.2f, callback %.2f\n",
+                (t_loop0 - t_setup0) * 1e3, (t_prod0 - t_loop0) * 1e3, t_wait * 1e3, t_ev1 * 1e3, dl.t_d2h * 1e3, dl.t_cb * 1e3);
+    if (c->opt.timing && map) fprintf(stderr, "[l3d match_chain] products on the device %.2f ms\n", (now_s() - t_prod0) * 1e3);
+    const double t_tail0 = now_s();
+    (void)hipStreamSynchronize(s1);
+    if (sp) (void)hipStreamSynchronize(sp);
+    (void)hipStreamSynchronize(st);
+    if (c->opt.timing) fprintf(stderr, "[l3d match_chain] hipSetDevice %.3f ms, final syncs %.3f ms\n", (t_setup0 - t_enter) * 1e3, (now_s() - t_tail0) * 1e3);
+    for (hipEvent_t e : ev) { if (cb) put_event(c, e); else put_local_event(c, e); }
+    for (hipEvent_t e : ev1) put_local_event(c, e);
+    c->stats[1] = raw_sum;
+    c->stats[3] = dl.kept_total;
+    if (rc_final == L3D_OK && !c->test_cand_cap && !c->test_arena_cap) {
+        c->chain_seen_views = n_views; c->chain_seen_pairs = pairs; c->chain_seen_cand_cap = cand_cap; c->chain_seen_arena_cap = arena_cap; c->chain_seen_kept = kept_seen;
+    }
+    return rc_final;
+}
+
+}  // namespace
+
 // cb: per-view delivery of the kept lists to the host (l3d_match_chain); map: products built on the device at the end of the chain
 // (l3d_match_chain_resident) -- either or both
 // [k_begin, k_end): the views this call computes (k_end < 0: all).  Views outside the range are treated as if they had never run: they
@@ -359,565 +958,44 @@ int l3d::run_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_cha
     c->products.valid = false;
     c->chain_routes[0] = c->chain_routes[1] = 0;
     if (n_views == 0) return L3D_OK;
-    const double t_enter = now_s();
+    ChainRun R(c, views, n_views, cb, map, k_begin, k_end, pre, ranged);
+    R.t_enter = now_s();
     HIPCHK(c, hipSetDevice(c->device));
-    const double t_setup0 = now_s();
-    c->pin_arena.reset();
-    hipStream_t st = c->stream;         // phase 2 (the chain proper)
-    hipStream_t s1 = c->stage1_stream;  // stage 1 runs ahead here, concurrently with the latency-bound kernels of phase 2
-    const bool serial = c->opt.chain_serial != 0;   // diagnostic: one stream, kernels one at a time (isolated durations)
-    if (serial) s1 = st;
-    (void)hipGetLastError();            // errors of earlier, already reported calls are not ours
+    R.t_setup0 = now_s();
+    if (int rc = R.setup()) return rc;
+    if (int rc = R.plan_capacities()) return rc;
+    if (int rc = R.plan_early()) return rc;
+    if (int rc = R.reserve_caps()) return rc;
+    if (int rc = R.take_over_preload()) return rc;
 
-    // ---- validation, table layout and upload, per-view slices of the whole-run arenas (l3d_chain_common.hip: shared with the sharded chain)
-    std::vector<ViewDev> vd;
-    ChainLayout L;
-    if (int rc = chain_plan_views(c, views, n_views, 0, 1, vd, L, "l3d_match_chain")) return rc;
-    if (int rc = chain_upload_tables(c, views, n_views, vd, L, st)) return rc;
-    // run-ahead depths, A/B measured on one box (ms per config-2 pass): (12, 24) 19.1, (6, 12) 18.7, (4, 8) 18.4, (2, 4) 18.3,
-    // (24, 40) 20.0 -- a shallow queue keeps the stage-1 candidates of a view cache-warm until its chain consumes them
-    // the ring covers every view that can be in flight between the one being collected and the newest stage 1: after an
-    // overflow ALL of them are refilled before any of their chains runs again (bit rows and stage-1 candidates alike)
-    const int kAhead = L3D_AHEAD, kStage1Ahead = L3D_S1AHEAD, kRing = kAhead + kStage1Ahead + 3;
-    // run tables (round 6): the kept writer fills one per view and leaves a (local camera << 16 | target) word per record in the side array
-    // (ch_keptcam); later views and the products read runs instead of scanning lists
-    if (int rc = chain_assign_arenas(c, views, n_views, vd, L, true, true, kRing, st, true)) return rc;
-    {
-        std::vector<const int*> rts((size_t)n_views);
-        for (int k = 0; k < n_views; ++k) rts[(size_t)k] = vd[(size_t)k].rt;
-        if (int rc = upload_rtinfo(c, views, n_views, rts, L.maxS, L.maxN, st)) return rc;
-    }
-    const unsigned char* dtab = L.dtab;
-    const int maxN = L.maxN;
-    if (ranged) {
-        // (after the arenas are laid out for all views: a view keeps its slices whatever the range is)
-        double p_range = 0, p_max = 0;
-        for (int k = 0; k < n_views; ++k) {
-            if (k < k_begin || k >= k_end) { vd[(size_t)k].verified = false; continue; }
-            if (!vd[(size_t)k].verified) continue;
-            double p = 0;
-            for (int j = 0; j < views[k].n_tbm; ++j) p += (double)views[k].S_src * views[k].offsets[2 * views[k].to_be_matched[j] + 1];
-            p_range += p; p_max = std::max(p_max, p);
-        }
-        L.pairs = p_range; L.max_pairs = p_max;
-    }
-    HIPCHK(c, c->ch_res.reserve((size_t)n_views * sizeof(ChainResult) + 16));
-    HIPCHK(c, c->ch_flags.reserve(64));
-    HIPCHK(c, c->ch_pin_res.reserve((size_t)n_views * (sizeof(ChainResult) + 8) + 64));
-    HIPCHK(c, hipMemsetAsync(c->ch_res.p, 0, (size_t)n_views * sizeof(ChainResult), st));
-    HIPCHK(c, hipMemsetAsync(c->ch_flags.p, 0, 64, st));
-    {   // stage 1 starts after the tables and the zeroed row counts are in place
-        hipEvent_t ready = get_local_event(c);
-        HIPCHK(c, hipEventRecord(ready, st));
-        HIPCHK(c, hipStreamWaitEvent(s1, ready, 0));
-        put_local_event(c, ready);
-    }
-    // per-view results are written by the kernels straight into host-mapped pinned memory (no copy operations on the streams)
-    ChainResult* hres = c->ch_pin_res.as<ChainResult>();
-    int* hstats = reinterpret_cast<int*>(c->ch_pin_res.as<unsigned char>() + (size_t)n_views * sizeof(ChainResult));
-    if (ranged) memset(hres, 0, (size_t)n_views * sizeof(ChainResult));          // (views outside the range: no records, whatever an earlier chain left here)
-    ChainResult* hres_dev = nullptr;
-    HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&hres_dev), hres, 0));
-    int* hstats_dev = reinterpret_cast<int*>(reinterpret_cast<unsigned char*>(hres_dev) + (size_t)n_views * sizeof(ChainResult));
-    // (the four depths of a stage-1 pair are triangulated once, by k_pair_fill: it runs ahead on the stage-1 stream, its true row counts are in place
-    // before the chain counts the view's reverse matches on top)
-    auto pair_args = [&](int k) { return chain_pair_args(c, views[k], vd[(size_t)k], dtab); };
-
-    { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return fail(c, L3D_ERR_HIP, std::string("chain setup: ") + hipGetErrorString(e_)); }
-    // ---- phase 1 (stage 1 of a view: pair test -> bit rows -> row counts -> statistics) is independent of the
-    // chain; it is enqueued a window ahead of phase 2 so that the GPU always has work while the host trails behind
-    const double pairs = L.pairs, max_pairs = L.max_pairs;
-    std::vector<hipEvent_t> ev1((size_t)n_views, nullptr);
-    int k_p1 = 0;                       // next view whose stage 1 is enqueued
-    c->stats[0] = pairs;
-    double raw_sum = 0;
-
-    // ---- capacities (guarded on the device; an overflow restarts the chain at that view with more room)
-    // first guess from the pair counts (raw density ~6 %, kept ~0.2 % of the pairs on the synthetic scenes)
-    size_t cand_cap = chain_first_cand_cap(max_pairs);
-    // The kept arena's first guess is GENEROUS (5 % of the pairs: the densest synthetic scene keeps 4.5 %, config 2 0.16 %) within 35 % of the free HBM: memory that is
-    // never written costs an allocation of a millisecond when it is the process's first big one, while growing later means a hipMalloc of tens of GB in a process that
-    // has freed big buffers before -- measured at 256 x 4000 x 24: 0.5 ms for the first 59 GB, 1.8-2.2 s for 75 GB at the second regrow, 25 ms per GB at 40 views in one
-    // run of three (profiles/r6_first_pass_allocations.txt).  A job sized by memory gives its capacities (l3d_set_chain_capacities) or the old guess (L3D_ARENA_GUESS=4)
-    size_t arena_cap = (size_t)(pairs * 0.004) + 1048576;
-    std::vector<hipEvent_t> ev((size_t)n_views, nullptr);
-    int k_enq = 0;                      // next view whose phase 2 is enqueued
-    int rc_final = L3D_OK;
-    // a pass over the same scene (same number of views, same pair count) starts with what the previous one ended up needing: no
-    // overflow, no restart, no allocation after the first pass
-    const bool same_scene = c->chain_seen_views == n_views && c->chain_seen_pairs == pairs;
-    if (same_scene) { cand_cap = std::max(cand_cap, c->chain_seen_cand_cap); arena_cap = std::max(arena_cap, c->chain_seen_arena_cap); }
-    else if (c->opt.arena_guess > 4 && !ranged && !pre) {      // (a block of views of a partitioned job is sized by memory: it keeps the small guess and grows)
-        size_t fr = 0, tot = 0;
-        if (hipMemGetInfo(&fr, &tot) == hipSuccess) {
-            const size_t want = (size_t)(pairs * 0.001 * c->opt.arena_guess) + 1048576, fits = (size_t)((double)fr * 0.35 / 40.0);
-            arena_cap = std::max(arena_cap, std::min(want, fits));
-        }
-        (void)hipGetLastError();
-    }
-    if (c->test_cand_cap) cand_cap = c->test_cand_cap;      // tests: force the overflow / restart path
-    if (c->test_arena_cap) arena_cap = c->test_arena_cap;
-    // views that own a slice of the arena: the range's verified views and the preloaded ones (a view's slice starts where the previous such view's ended)
-    std::vector<char> has_rec((size_t)n_views, 0);
-    for (int k = 0; k < n_views; ++k) has_rec[(size_t)k] = vd[(size_t)k].verified ? 1 : 0;
-    long long pre_records = 0;
-    if (pre) {
-        if (pre->k1 != k_begin || pre->k0 < 0 || pre->k0 > pre->k1 || (int)pre->n_kept.size() != pre->k1 - pre->k0 || (int)pre->R.size() != pre->k1 - pre->k0) return fail(c, L3D_ERR_INVALID, "match_chain: bad preload");
-        for (int k = pre->k0; k < pre->k1; ++k) { pre_records += pre->n_kept[(size_t)(k - pre->k0)]; has_rec[(size_t)k] = views[k].n_tbm > 0 ? 1 : 0; }
-        arena_cap += (size_t)pre_records;
-    }
-    // a turn of a node object that hands the chain over (match_chain_turn) under option regrow_free_mb: the room binds on everything the turn's arena
-    // takes -- this first guess, the regrow below, the slices its share puts behind the records -- as it does on the compact arena of a plain turn
-    const size_t turn_room = c->turn_arena_room;
-    if (turn_room) {
-        if ((size_t)pre_records + 65536 > turn_room)
-            return fail(c, L3D_ERR_NOMEM, "match_chain: the " + std::to_string(pre_records) + " records taken over from the turn before need more than the room for " + std::to_string(turn_room) + " records (" +
-                                          std::to_string(c->opt.regrow_free_mb) + " MB at " + std::to_string(sizeof(Match) + 4) + " B per record)");
-        arena_cap = std::min(arena_cap, turn_room);
-    }
-
-    // early pair transposes (round 6, l3d_products.hip): a (view, camera) pair of the potential-correspondence build depends on that view's kept list alone, so
-    // it is transposed on a side stream right behind the view's kept writer -- next to the following views' chains -- and the end of matchViews finds only the rows
-    // left.  Entries live in an array aligned with the kept arena (a view's pairs hold exactly its records).  L3D_PROD_EARLY=0: all transposes at the end (A/B)
-    Products& PE = c->products;
-    // Long lists only (> 2^18 records per view: what the last pass over this scene kept, or the arena's first guess), view by view.  At config 2 (36 k records per view)
-    // two launches and an event per view cost more than the 0.2 ms of transposes they take off the end (12.60 vs 12.41 ms per pass); eight views per launch still lose
-    // (12.52 vs 12.41; the first pass pays 5 ms for the side stream and its buffers).  Option values 2 / 3 force a view / eight views per launch (tests)
-    bool early = map && !ranged && !pre && !cb && c->opt.prod_early != 0 && c->opt.prod_transpose != 0 && maxN > 0;
-    int early_batch = c->opt.prod_early == 3 ? 8 : 1;
-    if (early && c->opt.prod_early == 1) {
-        const double per_view = (same_scene && c->chain_seen_kept > 0 ? c->chain_seen_kept : pairs * 0.004) / std::max(1, n_views);
-        early = per_view > (double)chain_long_list(c->opt);
-    }
-    int early_next = 0;                 // views [0, early_next) have their transposes launched
-    hipStream_t sp = nullptr;
-    int early_maxSt = 1;
-    if (early) {
-        std::vector<int> tab((size_t)n_views * maxN * 2 + (size_t)n_views * (sizeof(EarlyView) / 4), 0);       // [St | boff_off], n_views x maxN each; the views' descriptors behind them
-        PE.e_boff_off.assign((size_t)n_views * maxN, 0);
-        long long nb = 0;
-        for (int k = 0; k < n_views && early; ++k) {
-            if (!vd[(size_t)k].verified) continue;
-            for (int q = 0; q < views[k].N; ++q) {
-                const uint32_t* it = std::lower_bound(map->view_ids, map->view_ids + map->n_views, views[k].local2global[q]);
-                if (it == map->view_ids + map->n_views || *it != views[k].local2global[q]) continue;
-                const int t = (int)(it - map->view_ids), St = map->seg_base[t + 1] - map->seg_base[t];
-                if (St <= 0) continue;
-                tab[(size_t)k * maxN + q] = St;
-                tab[(size_t)n_views * maxN + (size_t)k * maxN + q] = (int)nb;
-                PE.e_boff_off[(size_t)k * maxN + q] = (int)nb;
-                nb += St + 1;
-                early_maxSt = std::max(early_maxSt, St);
-                if (nb > 0x7ffffff0ll) early = false;
-            }
-        }
-        if (early) {
-            if (!c->prod_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->prod_stream, hipStreamNonBlocking));
-            sp = c->prod_stream;
-            HIPCHK(c, PE.e_tab.reserve(tab.size() * 4 + 64));
-            static_assert(sizeof(EarlyView) % 8 == 0, "descriptor size");
-            {
-                const int* dt = PE.e_tab.as<int>();
-                EarlyView* hv = reinterpret_cast<EarlyView*>(tab.data() + (size_t)n_views * maxN * 2);       // (n_views * maxN * 2 ints: 8-byte aligned)
-                for (int k = 0; k < n_views; ++k) {
-                    EarlyView e;
-                    e.rt = vd[(size_t)k].verified ? vd[(size_t)k].rt : nullptr;
-                    e.St = dt + (size_t)k * maxN; e.boff_off = dt + (size_t)n_views * maxN + (size_t)k * maxN;
-                    e.k = k; e.S = views[k].S_src; e.N = views[k].N; e.pad = 0;
-                    hv[k] = e;
-                }
-            }
-            HIPCHK(c, PE.e_cnt.reserve((size_t)n_views * maxN * 4 + 64));
-            HIPCHK(c, PE.e_poff.reserve((size_t)n_views * maxN * 4 + 64));
-            HIPCHK(c, PE.e_boff.reserve((size_t)nb * 4 + 64));
-            HIPCHK(c, hipMemcpyAsync(PE.e_tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, st));
-            HIPCHK(c, hipStreamSynchronize(st));                    // (`tab` is pageable and leaves scope)
-        }
-    }
-    auto reserve_caps = [&]() -> int {
-        if (int rc = chain_reserve_candidates(c, L, cand_cap, kRing)) return rc;
-        HIPCHK(c, c->ch_kept.reserve(arena_cap * sizeof(Match)));
-        HIPCHK(c, c->ch_keptcam.reserve(arena_cap * 4 + 64));
-        if (early && arena_cap < 0x7ffffff0ull) { HIPCHK(c, PE.e_E.reserve(arena_cap * 4 + 64)); HIPCHK(c, PE.e_T.reserve(arena_cap * 4 + 64)); }
-        return L3D_OK;
-    };
-    { int rc = reserve_caps(); if (rc) return rc; }
-    if (pre && pre->k1 > pre->k0) {
-        long long base = 0;
-        size_t so = 0;
-        for (int k = pre->k0; k < pre->k1; ++k) {
-            ChainResult r;
-            r.kept_base = (uint64_t)base; r.n_want = 0; r.n_kept = has_rec[(size_t)k] ? pre->n_kept[(size_t)(k - pre->k0)] : 0; r.R = pre->R[(size_t)(k - pre->k0)]; r.overflow = 0;
-            hres[k] = r;
-            base += r.n_kept;
-            if (views[k].n_tbm > 0) {
-                // (chain_assign_arenas gave every verified view of the schedule its slices, whatever the range)
-                ChainViewDev& d = vd[(size_t)k];
-                if (views[k].S_src > 0 && d.best && pre->best) HIPCHK(c, hipMemcpyAsync(d.best, pre->best + so, (size_t)views[k].S_src * 8, hipMemcpyDeviceToDevice, st));
-                if (views[k].S_src > 0 && d.bestpos && pre->bestpos) HIPCHK(c, hipMemcpyAsync(d.bestpos, pre->bestpos + so, (size_t)views[k].S_src * 4, hipMemcpyDeviceToDevice, st));
-                so += (size_t)views[k].S_src;
-            }
-        }
-        if (base > 0) HIPCHK(c, hipMemcpyAsync(c->ch_kept.p, pre->records, (size_t)base * sizeof(Match), hipMemcpyDeviceToDevice, st));
-        if (base > 0) {
-            // the taken-over lists did not come out of this chain's kept writer: their side array and run tables are rebuilt from the records
-            std::vector<RtJob> jobs;
-            std::vector<const unsigned*> l2g;
-            for (int k = pre->k0; k < pre->k1; ++k) {
-                if (!has_rec[(size_t)k] || hres[k].n_kept == 0) continue;
-                if (!vd[(size_t)k].rt) return fail(c, L3D_ERR_INVALID, "match_chain: view " + std::to_string(k) + " was taken over with records but has no run table");
-                RtJob j;
-                j.recs = c->ch_kept.as<Match>() + hres[k].kept_base; j.qt = c->ch_keptcam.as<unsigned>() + hres[k].kept_base; j.rt = vd[(size_t)k].rt;
-                j.ids = nullptr; j.qs = nullptr; j.n = hres[k].n_kept; j.S = views[k].S_src; j.N = views[k].N; j.pad = 0;
-                jobs.push_back(j);
-                l2g.push_back(views[k].local2global);
-            }
-            if (!jobs.empty()) {
-                int bad = 0;
-                if (int rc = rebuild_run_tables(c, jobs, l2g, st, &bad)) return rc;
-                if (bad) return fail(c, L3D_ERR_INVALID, "match_chain: the lists taken over from another rank are not ordered (segment, camera) -- no run tables");
-            }
-        }
-        HIPCHK(c, hipMemcpyAsync(c->ch_res.as<ChainResult>() + pre->k0, hres + pre->k0, (size_t)(pre->k1 - pre->k0) * sizeof(ChainResult), hipMemcpyHostToDevice, st));
-    }
-    auto ringA_meta = [&](int k) { return c->ch_ringA_meta.as<uint2>() + (size_t)(k % kRing) * cand_cap; };
-    auto ringA_depths = [&](int k) { return c->ch_ringA_depths.as<float4>() + (size_t)(k % kRing) * cand_cap; };
-    // row starts + depth records of a view's stage-1 candidates alone (its reverse matches are not known yet), into the view's ring slot; k_place
-    // later moves them into the combined order on the chain stream, which stays short.  (Measured: triangulating on the chain stream instead was 5 %
-    // slower on config 2; letting the verification read the stage-1 candidates in place instead of copying them 20 % SLOWER -- the copy is a streaming
-    // pass that leaves the candidates cache-hot for the latency-bound kernels that follow.)
-    // the row starts of the stage-1 candidates are formed inside k_pair_fill from k_pair_mask's counters and their block sums: no
-    // scan launch on the stage-1 stream (the longer of the two), no statistics for the host to wait for -- up to 96 neighbours
-    const bool fused_rows = chain_fused_rows(maxN);
-    auto enqueue_fillA = [&](int k, hipStream_t s) {
-        const ViewDev& d = vd[(size_t)k];
-        const PairArgs pa = chain_fill_args(pair_args(k), d, fused_rows, cand_cap);
-        { ProfScope p(c, "pair_fill", s); launch_pair_fill(pa, d.rowA, ringA_meta(k), ringA_depths(k), s); }
-    };
-    auto enqueue_stage1 = [&](int k) -> int {
-        if (!vd[(size_t)k].verified) return L3D_OK;
-        hstats[2 * k] = hstats[2 * k + 1] = 0;
-        if (views[k].S_src > 0) {
-            const PairArgs pa = pair_args(k);
-            {   // bit rows + row counts (added into the rows zeroed at chain start) in one launch
-                const PairArgs pm = chain_mask_args(pa, vd[(size_t)k], fused_rows);
-                ProfScope p(c, "pair_mask", s1);
-                launch_pair_mask(pm, vd[(size_t)k].maxW, s1, c->opt.pair_spb);
-            }
-            // (unfused) row starts of the stage-1 candidates + their statistics straight into host-mapped memory (one launch)
-            if (!fused_rows) { ProfScope p(c, "scan", s1); launch_scan(vd[(size_t)k].rowcnt, vd[(size_t)k].rowA, views[k].S_src * views[k].N, nullptr, s1, nullptr, views[k].N, 0, views[k].S_src, hstats_dev + 2 * k); }
-            // the ring slot was last used by view k - kRing: wait until its chain has consumed it
-            for (int j = k - kRing; j >= 0; j -= kRing) if (ev[(size_t)j]) { HIPCHK(c, hipStreamWaitEvent(s1, ev[(size_t)j], 0)); break; }
-            enqueue_fillA(k, s1);
-        }
-        ev1[(size_t)k] = get_local_event(c);
-        HIPCHK(c, hipEventRecord(ev1[(size_t)k], s1));
-        return L3D_OK;
-    };
-
-    double t_ev1 = 0;                   // host time spent waiting for stage-1 statistics
-    double kept_seen = pre ? (double)pre_records : 0.0;     // kept records / views whose result record the host has read (sizes the source scans)
-    int views_seen = pre ? pre->k1 - pre->k0 : 0;
-    auto enqueue_view = [&](int k) -> int {
-        const l3d_chain_view& v = views[k];
-        const ViewDev& d = vd[(size_t)k];
-        while (k_p1 < n_views && k_p1 <= k + kStage1Ahead) { int rc = enqueue_stage1(k_p1); if (rc) return rc; ++k_p1; }
-        if (!d.verified) return L3D_OK;
-        const double te0 = now_s();
-        if (!fused_rows) HIPCHK(c, hipEventSynchronize(ev1[(size_t)k]));          // its stage-1 statistics (enqueued a window earlier)
-        t_ev1 += now_s() - te0;
-        HIPCHK(c, hipStreamWaitEvent(st, ev1[(size_t)k], 0));
-        PairArgs pa = pair_args(k);
-        pa.cand_cap = (int)cand_cap;
-        const int S = v.S_src, N = v.N;
-        const size_t nrow = (size_t)S * N;
-        Match* arena = c->ch_kept.as<Match>();
-        ChainResult* dres = c->ch_res.as<ChainResult>();
-        const int* d_sc = reinterpret_cast<const int*>(dtab + d.o_sc);
-        (void)hipGetLastError();
-        const int* d_si = reinterpret_cast<const int*>(dtab + d.o_si);
-        unsigned* cams = c->ch_keptcam.as<unsigned>();
-        // sized from the lists the chain has seen so far (the host trails a few views behind); short lists (config 2 keeps 36 k matches per view) are
-        // scanned record by record
-        const CollectRule rule = chain_collect_rule(c->opt, views_seen > 0, views_seen > 0 ? kept_seen / views_seen : 0.0, S, N, L.maxS);
-        const double avg_run = rule.avg_run;
-        ++c->chain_routes[rule.rt ? 1 : 0];
-        CollectIn ci;
-        ci.arena = arena; ci.dres = dres; ci.cams = cams; ci.info = c->ch_rtinfo.as<RtInfo>(); ci.d_sc = d_sc; ci.d_si = d_si;
-        ci.d_ss = reinterpret_cast<const int*>(dtab + d.o_ss); ci.d_tbm = pa.tbm; ci.n_sources = v.n_sources; ci.n_tbm = v.n_tbm; ci.view_id = v.view_id; ci.S = S; ci.N = N;
-        ci.rowcnt = d.rowcnt; ci.rowA = d.rowA; ci.metaA = ringA_meta(k); ci.depthsA = ringA_depths(k); ci.cand_cap = cand_cap;
-        ci.sort_apart = !(c->verify_mode == 0 && verify_window_supported(N));     // (the window kernel orders the runs itself)
-        enqueue_collect(c, ci, rule, st);
-        VerifyArgs va = chain_verify_args(c, v, d, dtab, cand_cap);
-        va.res = dres + k;
-        // (fused row starts: no statistics -- the largest LDS image the budget allows)
-        chain_launch_verify(c, va, d, d_sc, v.n_sources, fused_rows ? -1 : hstats[2 * k + 1], cand_cap, st);
-        {
-            ProfScope p(c, "kept_write");
-            int pv = k - 1;
-            while (pv >= 0 && !has_rec[(size_t)pv]) --pv;                    // the arena slice starts where the previous verified (or preloaded) view's ended
-            launch_kept_write_chain(va, c->kept_cnt.as<int>(), (int)nrow, pv >= 0 ? dres + pv : nullptr, (unsigned long long)arena_cap, dres + k, hres_dev + k,
-                                    reinterpret_cast<const unsigned*>(dtab + d.o_l2g), arena, st, (map || ranged) ? d.bestpos : nullptr, cams, d.rt, S);
-        }
-        { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return fail(c, L3D_ERR_HIP, std::string("chain launch, view ") + std::to_string(k) + ": " + hipGetErrorString(e_)); }
-        // (with a delivery callback the host starts D2H copies of device memory once it has seen this event: a default, fenced event then)
-        if (!ev[(size_t)k]) ev[(size_t)k] = cb ? get_event(c) : get_local_event(c);
-        HIPCHK(c, hipEventRecord(ev[(size_t)k], st));
-        if (early && arena_cap < 0x7ffffff0ull && k + 1 - early_next >= early_batch) {
-            HIPCHK(c, hipStreamWaitEvent(sp, ev[(size_t)k], 0));
-            launch_early_transposes(c, reinterpret_cast<const EarlyView*>(PE.e_tab.as<int>() + (size_t)n_views * maxN * 2), early_next, k + 1 - early_next, maxN, early_maxSt, dres, cams, PE.e_cnt.as<int>(),
-                                    PE.e_poff.as<unsigned>(), PE.e_boff.as<int>(), PE.e_E.as<unsigned>(), PE.e_T.as<unsigned>(), avg_run, sp);
-            early_next = k + 1;
-        }
-        return L3D_OK;
-    };
-
-    // ---- phase 2 + trailing result loop.  This thread enqueues and watches the per-view result records (overflow ->
-    // grow and restart at that view); finished views are handed, in order, to a delivery thread that copies the kept slice
-    // and the depth pairs (copy stream, SDMA) and runs the caller's bookkeeping -- so the ~13 launches per view of this
-    // thread are never held up by host work.
-    const double t_loop0 = now_s();
-    double kept_total = 0, t_cb = 0, t_wait = 0, t_d2h = 0;
-    struct Item { int k; int verified; ChainResult r; };
-    std::mutex mu;
-    std::condition_variable cv_work, cv_idle;
-    std::deque<Item> work;
-    bool done = false, busy = false;
-    int deliver_rc = L3D_OK;
-    std::string deliver_err;
-    std::thread deliverer([&]() {
-        if (!cb) return;                                // resident run: nothing is handed to the host
-        (void)hipSetDevice(c->device);
-        for (;;) {
-            Item it;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv_work.wait(lk, [&]() { return done || !work.empty(); });
-                if (work.empty()) return;
-                it = work.front();
-                work.pop_front();
-                busy = true;
-            }
-            int rc = L3D_OK;
-            std::string err;
-            if (deliver_rc == L3D_OK) {
-                const l3d_chain_view& v = views[it.k];
-                const ViewDev& d = vd[(size_t)it.k];
-                if (!it.verified) {                     // cudawrapper.cu:877-878: nothing to match, the caller keeps its list
-                    if (cb(user, it.k, 0, nullptr, 0, nullptr, 0, 0)) { rc = L3D_ERR_INVALID; err = "callback failed"; }
-                } else {
-                    const double td0 = now_s();
-                    // the kept list lands in the pinned arena, where it stays valid for the caller until the next chain starts
-                    hipError_t e = hipSuccess;
-                    l3d_match* kept_host = static_cast<l3d_match*>(c->pin_arena.alloc((size_t)it.r.n_kept * sizeof(Match) + 16, &e));
-                    if (e == hipSuccess) e = c->ch_pin_best.reserve((size_t)v.S_src * 8 + 16);
-                    if (e == hipSuccess && it.r.n_kept)
-                        e = hipMemcpyAsync(kept_host, c->ch_kept.as<Match>() + it.r.kept_base, (size_t)it.r.n_kept * sizeof(Match), hipMemcpyDeviceToHost, c->copy_stream);
-                    if (e == hipSuccess && v.S_src) e = hipMemcpyAsync(c->ch_pin_best.p, d.best, (size_t)v.S_src * 8, hipMemcpyDeviceToHost, c->copy_stream);
-                    if (e == hipSuccess) e = hipStreamSynchronize(c->copy_stream);
-                    if (e != hipSuccess) { rc = L3D_ERR_HIP; err = std::string("chain delivery, view ") + std::to_string(it.k) + ": " + hipGetErrorString(e); }
-                    else {
-                        float* best = c->ch_pin_best.as<float>();
-                        int nb = 0;
-                        if (it.r.R > 0)
-                            for (int s = 0; s < v.S_src; ++s)
-                                if (best[2 * s] != -1.0f) { best[2 * nb] = best[2 * s]; best[2 * nb + 1] = best[2 * s + 1]; ++nb; }   // in place: nb <= s
-                        kept_total += it.r.n_kept;
-                        const double tc0 = now_s();
-                        t_d2h += tc0 - td0;
-                        if (cb(user, it.k, 1, kept_host, it.r.n_kept, best, nb, it.r.R)) { rc = L3D_ERR_INVALID; err = "callback failed"; }
-                        t_cb += now_s() - tc0;
-                    }
-                }
-            }
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                if (rc && deliver_rc == L3D_OK) { deliver_rc = rc; deliver_err = err; }
-                busy = false;
-            }
-            cv_idle.notify_all();
-        }
-    });
-    auto hand_over = [&](int k, int verified, const ChainResult& r) {
-        if (!cb) { if (verified) kept_total += r.n_kept; return; }
-        { std::lock_guard<std::mutex> lk(mu); work.push_back(Item{ k, verified, r }); }
-        cv_work.notify_one();
-    };
-    auto wait_delivered = [&]() {                       // every handed-over view has left the device arena
-        if (!cb) return;
-        std::unique_lock<std::mutex> lk(mu);
-        cv_idle.wait(lk, [&]() { return work.empty() && !busy; });
-    };
-    auto hip_ok = [&](hipError_t e, const char* what) {
-        if (e == hipSuccess) return true;
-        rc_final = fail(c, L3D_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-        return false;
-    };
-    for (int k = 0; k < n_views && rc_final == L3D_OK; ++k) {
-        while (k_enq < n_views && k_enq <= k + kAhead) { int rc = enqueue_view(k_enq); if (rc) { rc_final = rc; break; } ++k_enq; }
-        if (rc_final) break;
-        { std::lock_guard<std::mutex> lk(mu); if (deliver_rc) break; }
-        const ViewDev& d = vd[(size_t)k];
-        if (!d.verified) { hand_over(k, 0, ChainResult()); continue; }
+    // ---- phase 2 + trailing result loop.  This thread enqueues (phase 2 of a view kAhead in front of the one it waits for, stage 1 kStage1Ahead in
+    // front of that) and watches the per-view result records: an overflow grows the buffers and restarts at that view, a finished view goes, in
+    // order, to the delivery thread.
+    R.t_loop0 = now_s();
+    Delivery dl(c, views, R.vd, cb, user);
+    for (int k = 0; k < n_views && R.rc_final == L3D_OK; ++k) {
+        while (R.k_enq < n_views && R.k_enq <= k + kAhead) { int rc = R.enqueue_view(R.k_enq); if (rc) { R.rc_final = rc; break; } ++R.k_enq; }
+        if (R.rc_final || dl.failed()) break;
+        if (!R.vd[(size_t)k].verified) { dl.push(k, 0, ChainResult()); continue; }
         const double tw0 = now_s();
-        if (!hip_ok(hipEventSynchronize(ev[(size_t)k]), "hipEventSynchronize")) break;
-        t_wait += now_s() - tw0;
-        const ChainResult r = hres[k];
+        if (!R.hip_ok(hipEventSynchronize(R.ev[(size_t)k]), "hipEventSynchronize")) break;
+        R.t_wait += now_s() - tw0;
+        const ChainResult r = R.hres[k];
         if (r.overflow) {
-            // not enough room for this view's candidates / kept matches: everything before it is valid and stays
-            // in the arena; wait for the queue (and the delivery of earlier views) to drain, grow, and re-enqueue from this view
-            if (!hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize") || !hip_ok(hipStreamSynchronize(s1), "hipStreamSynchronize")) break;
-            if (sp && !hip_ok(hipStreamSynchronize(sp), "hipStreamSynchronize")) break;
-            const double t_restart0 = now_s();
-            wait_delivered();
-            if (r.overflow & 1) cand_cap = (size_t)r.R + (size_t)r.R / 4 + 65536;
-            if (r.overflow & 2) {
-                // the arena cannot be reallocated without losing earlier lists that later views still read:
-                // copy it over
-                // (projected from the views done so far when there are enough of them: dense scenes keep 10x the first guess)
-                size_t new_cap = arena_cap * 2;
-                // (views of THIS call: a ranged chain -- a block of views -- must not size its arena for the whole scene)
-                const int n_pre = pre ? pre->k1 - pre->k0 : 0, done = k - k_begin + n_pre, span = k_end - k_begin + n_pre;
-                // the first views of a chain have few sources yet and keep less than the later ones (40 x 4000 x 24: the projection at view 8 x 1.3 fell 2 % short,
-                // the arena overflowed again at view 38 and DOUBLED to 9.8 GB -- an allocation that took 3 to 250 ms): 1.5 early on; past the
-                // middle the projection is good and replaces the doubling
-                if (done >= 4) {
-                    const size_t proj = (size_t)((double)r.kept_base / done * span * (2 * done < span ? 1.5 : 1.15)) + 1048576;
-                    new_cap = 2 * done < span ? std::max(new_cap, proj) : std::max(proj, arena_cap + arena_cap / 8);
-                }
-                // (records are indexed with 64 bits: memory is the only bound.)  The new arena must hold the records in use AND the view that overflowed
-                // (n_want: its true count), so that its re-run cannot overflow again.  The old arena and side array stay allocated until the used part is
-                // copied over, so near the top of HBM the new ones must fit BESIDE them, next to what the products will take (their table: 8 B per record,
-                // their smallest transient blocks: 6.4 GB): a size above what fits is cut down to it -- and when what fits cannot hold that view or is no
-                // larger than the arena that just overflowed, the chain fails with NOMEM and the sizes.  Every regrow grows the arena and lets the view
-                // through: the restarts are bounded.
-                const size_t need = (size_t)r.kept_base + (size_t)std::max(0, r.n_want) + 65536;
-                new_cap = std::max(new_cap, need);
-                {
-                    size_t fr = 0, tot = 0;
-                    if (hipMemGetInfo(&fr, &tot) == hipSuccess) {
-                        if (c->opt.regrow_free_mb > 0) fr = std::min(fr, (size_t)c->opt.regrow_free_mb << 20);     // (tests: a card with less room)
-                        const size_t per_rec = sizeof(Match) + 4 + (early && new_cap < 0x7ffffff0ull ? 4 : 0) + (map ? 8 : 0);
-                        // (a turn under the cap: the room is the arena's, nothing is kept back from it)
-                        const size_t reserve = turn_room ? 0 : map ? (size_t)((1ll << 28) * 24) + ((size_t)1 << 30) : (size_t)512 << 20;
-                        const size_t fits = turn_room ? turn_room : fr > reserve ? (fr - reserve) / per_rec : 0;
-                        if (new_cap > fits) {
-                            if (fits < need || fits <= arena_cap) {
-                                rc_final = fail(c, L3D_ERR_NOMEM, "match_chain: the kept arena of " + std::to_string(arena_cap) + " records is full at view " + std::to_string(k) + " of " + std::to_string(n_views) + " (" +
-                                                                      std::to_string((size_t)r.kept_base) + " records in use, the view keeps " + std::to_string(r.n_want) + ") and an arena of " +
-                                                                      std::to_string(need) + " records does not fit beside it (room for " + std::to_string(fits) + " at " + std::to_string(per_rec) + " B per record, " +
-                                                                      std::to_string(reserve >> 20) + " MB kept back; " + std::to_string(fr >> 20) + " of " + std::to_string(tot >> 20) +
-                                                                      " MB free): l3d_set_chain_capacities sizes the arena up front");
-                                break;
-                            }
-                            new_cap = fits;
-                        }
-                    }
-                    (void)hipGetLastError();
-                }
-                void* np = nullptr;
-                const double t_m0 = now_s();
-                {
-                    const hipError_t me = hipMalloc(&np, new_cap * sizeof(Match));
-                    if (me != hipSuccess) {
-                        size_t fr = 0, tot = 0;
-                        (void)hipMemGetInfo(&fr, &tot);
-                        rc_final = fail(c, L3D_ERR_NOMEM, "match_chain: growing the kept arena to " + std::to_string(new_cap * sizeof(Match) >> 20) + " MB at view " + std::to_string(k) + " of " + std::to_string(n_views) +
-                                                          " (" + std::to_string((size_t)r.kept_base * sizeof(Match) >> 20) + " MB in use, " + std::to_string(fr >> 20) + " of " + std::to_string(tot >> 20) + " MB free): " + hipGetErrorString(me));
-                        break;
-                    }
-                }
-                const double t_m1 = now_s();
-                if (!hip_ok(hipMemcpy(np, c->ch_kept.p, (size_t)r.kept_base * sizeof(Match), hipMemcpyDeviceToDevice), "hipMemcpy")) break;
-                const double t_m2 = now_s();
-                (void)hipFree(c->ch_kept.p);
-                if (c->opt.timing) fprintf(stderr, "[l3d match_chain]   arena of %zu MB: hipMalloc %.2f ms, copy of %zu MB %.2f ms, hipFree of the old one %.2f ms\n", new_cap * sizeof(Match) >> 20, (t_m1 - t_m0) * 1e3,
-                                           (size_t)r.kept_base * sizeof(Match) >> 20, (t_m2 - t_m1) * 1e3, (now_s() - t_m2) * 1e3);
-                c->ch_kept.p = np; c->ch_kept.cap = new_cap * sizeof(Match);
-                {                                           // (the side array grows with it, its used part kept)
-                    void* nc = nullptr;
-                    if (!hip_ok(hipMalloc(&nc, new_cap * 4 + 64), "hipMalloc (side words of the kept arena)")) break;
-                    if (!hip_ok(hipMemcpy(nc, c->ch_keptcam.p, (size_t)r.kept_base * 4, hipMemcpyDeviceToDevice), "hipMemcpy")) { (void)hipFree(nc); break; }
-                    (void)hipFree(c->ch_keptcam.p);
-                    c->ch_keptcam.p = nc; c->ch_keptcam.cap = new_cap * 4 + 64;
-                }
-                if (early && new_cap < 0x7ffffff0ull) {     // (the earlier views' transposed entries move with their records; beyond 2^31 records the end transposes block by block)
-                    void* ne = nullptr;
-                    if (!hip_ok(hipMalloc(&ne, new_cap * 4 + 64), "hipMalloc (transposed entries of the kept arena)")) break;
-                    if (!hip_ok(hipMemcpy(ne, PE.e_E.p, (size_t)r.kept_base * 4, hipMemcpyDeviceToDevice), "hipMemcpy")) { (void)hipFree(ne); break; }
-                    (void)hipFree(PE.e_E.p);
-                    PE.e_E.p = ne; PE.e_E.cap = new_cap * 4 + 64;
-                }
-                arena_cap = new_cap;
-            }
-            { int rc = reserve_caps(); if (rc) { rc_final = rc; break; } }
-            if (c->opt.timing) fprintf(stderr, "[l3d match_chain] view %d of %d overflowed (%d): candidates %zu, arena %zu records; regrown in %.2f ms, %.2f ms into the loop\n", k, n_views, r.overflow, cand_cap, arena_cap,
-                                       (now_s() - t_restart0) * 1e3, (now_s() - t_loop0) * 1e3);
-            // the row counts of the views enqueued after k were already incremented by their reverse matches: rebuild
-            // and the stage-1 candidate buffers of every view in flight live in the (re-sized) ring: refill them
-            for (int j = k; j < k_p1; ++j) {
-                if (!vd[(size_t)j].verified || views[j].S_src == 0) continue;
-                if (j < k_enq) {
-                    if (!hip_ok(hipMemsetAsync(vd[(size_t)j].rowcnt, 0, (size_t)views[j].S_src * views[j].N * 4, st), "hipMemsetAsync")) break;
-                    if (!fused_rows) launch_row_count(pair_args(j), vd[(size_t)j].rowcnt, st);      // (fused: the upper bounds live in rowub, untouched)
-                }
-                enqueue_fillA(j, st);
-            }
-            if (rc_final) break;
-            k_enq = k;
-            early_next = std::min(early_next, k);           // (the views run again are transposed again)
+            if (!R.restart_at(k, r, dl)) break;
             --k;
             continue;
         }
-        raw_sum += r.R;                     // candidates verified (stage-1 + existing), counted when the view is final (a restart enqueues views twice)
-        kept_seen += r.n_kept; views_seen += 1;
-        hand_over(k, 1, r);
+        R.raw_sum += r.R;                   // candidates verified (stage-1 + existing), counted when the view is final (a restart enqueues views twice)
+        R.kept_seen += r.n_kept; R.views_seen += 1;
+        dl.push(k, 1, r);
     }
-    { std::lock_guard<std::mutex> lk(mu); done = true; }
-    cv_work.notify_one();
-    deliverer.join();
-    if (rc_final == L3D_OK && deliver_rc) rc_final = fail(c, deliver_rc, deliver_err);
+    std::string deliver_err;
+    const int deliver_rc = dl.finish(&deliver_err);
+    if (R.rc_final == L3D_OK && deliver_rc) R.rc_final = fail(c, deliver_rc, deliver_err);
     const double t_prod0 = now_s();
-    if (rc_final == L3D_OK && map) {
-        // ---- the products of matchViews, on the device, from the arena (l3d_products.hip); enqueued behind the last view
-        std::vector<ProdChainView> pv((size_t)n_views);
-        for (int k = 0; k < n_views; ++k) pv[(size_t)k] = ProdChainView{ vd[(size_t)k].verified ? vd[(size_t)k].best : nullptr, vd[(size_t)k].verified ? vd[(size_t)k].bestpos : nullptr, vd[(size_t)k].verified ? 1 : 0,
-                                                                         vd[(size_t)k].verified ? vd[(size_t)k].rt : nullptr };
-        ProdEarly pe;
-        const bool early_done = early && arena_cap < 0x7ffffff0ull;
-        if (early_done) {
-            if (early_next < n_views) {                     // the last batch's remainder: on the chain's stream, behind the last view
-                const double avg_run = views_seen > 0 ? kept_seen / views_seen / std::max(1.0, (double)L.maxS * std::max(1, maxN)) : 1.0;
-                launch_early_transposes(c, reinterpret_cast<const EarlyView*>(PE.e_tab.as<int>() + (size_t)n_views * maxN * 2), early_next, n_views - early_next, maxN, early_maxSt, c->ch_res.as<ChainResult>(),
-                                        c->ch_keptcam.as<unsigned>(), PE.e_cnt.as<int>(), PE.e_poff.as<unsigned>(), PE.e_boff.as<int>(), PE.e_E.as<unsigned>(), PE.e_T.as<unsigned>(), avg_run, st);
-                early_next = n_views;
-            }
-            hipEvent_t e = get_local_event(c);
-            (void)hipEventRecord(e, sp);
-            (void)hipStreamWaitEvent(st, e, 0);
-            put_local_event(c, e);
-            pe.pcnt_kq = PE.e_cnt.as<int>(); pe.poff_kq = PE.e_poff.as<unsigned>(); pe.boff = PE.e_boff.as<int>(); pe.E = PE.e_E.as<unsigned>();
-            pe.boff_off_host = PE.e_boff_off.data(); pe.maxN = maxN;
-        }
-        rc_final = build_products(c, views, n_views, pv.data(), hres, map, summary, n_pot, 0, -1, nullptr, c->ch_keptcam.as<unsigned>(), early_done ? &pe : nullptr);
-    }
-    if (c->opt.timing)
-        fprintf(stderr, "[l3d match_chain] setup %.2f ms | enqueue + watch loop %.2f ms (waiting: view results %.2f, stage-1 statistics %.2f) | delivery thread: d2h %.2f, callback %.2f\n",
-                (t_loop0 - t_setup0) * 1e3, (t_prod0 - t_loop0) * 1e3, t_wait * 1e3, t_ev1 * 1e3, t_d2h * 1e3, t_cb * 1e3);
-    if (c->opt.timing && map) fprintf(stderr, "[l3d match_chain] products on the device %.2f ms\n", (now_s() - t_prod0) * 1e3);
-    const double t_tail0 = now_s();
-    (void)hipStreamSynchronize(s1);
-    if (sp) (void)hipStreamSynchronize(sp);
-    (void)hipStreamSynchronize(st);
-    if (c->opt.timing) fprintf(stderr, "[l3d match_chain] hipSetDevice %.3f ms, final syncs %.3f ms\n", (t_setup0 - t_enter) * 1e3, (now_s() - t_tail0) * 1e3);
-    for (hipEvent_t e : ev) { if (cb) put_event(c, e); else put_local_event(c, e); }
-    for (hipEvent_t e : ev1) put_local_event(c, e);
-    c->stats[1] = raw_sum;
-    c->stats[3] = kept_total;
-    if (rc_final == L3D_OK && !c->test_cand_cap && !c->test_arena_cap) {
-        c->chain_seen_views = n_views; c->chain_seen_pairs = pairs; c->chain_seen_cand_cap = cand_cap; c->chain_seen_arena_cap = arena_cap; c->chain_seen_kept = kept_seen;
-    }
-    return rc_final;
+    if (R.rc_final == L3D_OK && map) R.rc_final = R.products_tail(summary, n_pot);
+    return R.finish(dl, t_prod0);
 }
 
 extern "C" int l3d_match_chain(l3d_ctx* c, const l3d_chain_view* views, int n_views, l3d_chain_callback cb, void* user)
@@ -943,6 +1021,13 @@ extern "C" int l3d_last_chain_routes(l3d_ctx* c, int* n_scanned, int* n_run_tabl
 
 // host only: no context, no device
 extern "C" int l3d_test_rt_lanes(int opt, double avg_run) { return rt_lanes_per_run(opt, avg_run); }
+extern "C" int l3d_test_arena_regrow(uint64_t arena_cap, uint64_t kept_base, int n_want, int done, int span, uint64_t free_bytes, uint64_t turn_room, int early, int products, uint64_t out[5])
+{
+    if (!out) return L3D_ERR_INVALID;
+    const ArenaRegrow g = chain_arena_regrow((size_t)arena_cap, kept_base, n_want, done, span, free_bytes == UINT64_MAX ? kRegrowFreeUnknown : (size_t)free_bytes, (size_t)turn_room, early != 0, products != 0);
+    out[0] = g.new_cap; out[1] = g.need; out[2] = g.fits; out[3] = g.per_rec; out[4] = g.reserve;
+    return g.ok ? L3D_OK : L3D_ERR_NOMEM;
+}
 
 // One view's collect step on kept lists of the caller's (tests/test_gpu_collect_paths.py): everything is validated on the host, the lists go into the
 // arena with result records, side words and run tables (rebuild_run_tables), the outputs are filled with 0xff bytes, then enqueue_collect runs under

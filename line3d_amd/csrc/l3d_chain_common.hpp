@@ -74,6 +74,44 @@ void chain_launch_verify(l3d_ctx* c, VerifyArgs& va, const ChainViewDev& d, cons
 
 // first guess of the candidate capacity from the largest view's pair count (raw density ~6 % + reverse matches; guarded on the device)
 inline size_t chain_first_cand_cap(double max_pairs) { return (size_t)(max_pairs * 0.12) + 65536; }
+// The size (records) the single-GPU chain grows its kept arena to when a view overflowed it -- run_chain, and l3d_test_arena_regrow for
+// tests/test_regrow_cases_cpu.py.  arena_cap: the arena that overflowed; kept_base: the records in use; n_want: what the view keeps; done of span:
+// views of THIS call finished, preloaded ones included (a ranged chain -- a block of views -- must not size its arena for the whole scene);
+// free_bytes: the free HBM (kRegrowFreeUnknown: not known -- no cut, no NOMEM); turn_room: the room of a turn under option regrow_free_mb (records;
+// the room is the arena's, nothing is kept back from it); early: the chain transposes early; products: it builds the products (a dense map was given).
+//   The doubling, or the projection from the views done when there are enough of them (dense scenes keep 10x the first guess).  The first views of a
+// chain have few sources yet and keep less than the later ones (40 x 4000 x 24: the projection at view 8 x 1.3 fell 2 % short, the arena overflowed
+// again at view 38 and DOUBLED to 9.8 GB -- an allocation that took 3 to 250 ms): 1.5 early on; past the middle the projection is good and replaces
+// the doubling.
+//   Records are indexed with 64 bits: memory is the only bound.  The new arena must hold the records in use AND the view that overflowed (n_want: its
+// true count), so that its re-run cannot overflow again: `need`.  The old arena and side array stay allocated until the used part is copied over, so
+// near the top of HBM the new ones must fit BESIDE them (per_rec bytes a record: the record, its side word, an early-transpose entry below 2^31
+// records, 8 B of the products' table), next to what the products will take (`reserve`: their smallest transient blocks, 6.4 GB, + 1 GB): a size above
+// what fits is cut down to it -- and when what fits cannot hold that view or is no larger than the arena that just overflowed, the answer is !ok
+// (NOMEM and the sizes).  Every regrow grows the arena and lets the view through: the restarts are bounded.
+constexpr size_t kRegrowFreeUnknown = ~(size_t)0;
+struct ArenaRegrow { size_t new_cap, need, fits, per_rec, reserve; bool ok; };
+inline ArenaRegrow chain_arena_regrow(size_t arena_cap, uint64_t kept_base, int n_want, int done, int span, size_t free_bytes, size_t turn_room, bool early, bool products)
+{
+    ArenaRegrow g;
+    g.new_cap = arena_cap * 2;
+    if (done >= 4) {
+        const size_t proj = (size_t)((double)kept_base / done * span * (2 * done < span ? 1.5 : 1.15)) + 1048576;
+        g.new_cap = 2 * done < span ? std::max(g.new_cap, proj) : std::max(proj, arena_cap + arena_cap / 8);
+    }
+    g.need = (size_t)kept_base + (size_t)std::max(0, n_want) + 65536;
+    g.new_cap = std::max(g.new_cap, g.need);
+    const bool known = free_bytes != kRegrowFreeUnknown;
+    g.per_rec = sizeof(Match) + 4 + (early && g.new_cap < 0x7ffffff0ull ? 4 : 0) + (products ? 8 : 0);
+    g.reserve = turn_room ? 0 : products ? (size_t)((1ll << 28) * 24) + ((size_t)1 << 30) : (size_t)512 << 20;
+    g.fits = turn_room ? turn_room : known && free_bytes > g.reserve ? (free_bytes - g.reserve) / g.per_rec : 0;
+    g.ok = true;
+    if (known && g.new_cap > g.fits) {
+        if (g.fits < g.need || g.fits <= arena_cap) g.ok = false;
+        else g.new_cap = g.fits;
+    }
+    return g;
+}
 // Lanes that share a run when a view collects its reverse matches through the run tables (k_exist_count_rt, k_place_rt): always a power of two in
 // [1, 64] -- both kernels cut their workgroup into groups of g lanes (256 / g and 1024 / g of them) and step their segment loops by the number of
 // groups, so a g above the workgroup would make that step 0 (the loop never ends) and a g that does not divide it would let the last, partial group

@@ -377,16 +377,14 @@ void share_file(l3d_ctx* c, int n_views, const TurnRange& t, const ShareState& s
     c->stats[3] = kept; c->stats[1] = raw;
 }
 
-// `used` bytes of the kept arena kept across a growth (DevBuf::reserve drops the content)
+// the kept arena grown with an eighth on top, its first used_records kept (DevBuf::grow_keep: behind the copies the ingests queued on the stream)
 int arena_grow_keep(l3d_ctx* c, size_t records, size_t used_records)
 {
     if (records * sizeof(Match) <= c->ch_kept.cap) return L3D_OK;
     const size_t want = records * sizeof(Match) + records * sizeof(Match) / 8 + 4096;
-    void* np = nullptr;
-    if (hipMalloc(&np, want) != hipSuccess) { (void)hipGetLastError(); return fail(c, L3D_ERR_NOMEM, "growing the kept arena to " + std::to_string(want >> 20) + " MB"); }
-    if (used_records && c->ch_kept.p) HIPCHK(c, hipMemcpy(np, c->ch_kept.p, used_records * sizeof(Match), hipMemcpyDeviceToDevice));
-    if (c->ch_kept.p) (void)hipFree(c->ch_kept.p);
-    c->ch_kept.p = np; c->ch_kept.cap = want;
+    const hipError_t e = c->ch_kept.grow_keep(want, used_records * sizeof(Match), c->stream);
+    if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(c, L3D_ERR_NOMEM, "growing the kept arena to " + std::to_string(want >> 20) + " MB"); }
+    if (e != hipSuccess) return fail(c, L3D_ERR_HIP, std::string("copying the kept arena over: ") + hipGetErrorString(e));
     return L3D_OK;
 }
 

@@ -40,6 +40,30 @@ struct DevBuf {
         if (e == hipSuccess) cap = bytes + 256;
         return e;
     }
+    // Grown to exactly `bytes` (the caller adds its own slack) WITHOUT losing the first used_bytes (reserve drops the content).  They are copied on `st`
+    // and `st` is synchronised before the old buffer is freed: the context's streams are non-blocking, so a copy on the null stream would not wait
+    // for what is queued on them.  A failed allocation (hipErrorOutOfMemory) or copy leaves the old buffer as it was; the caller words the message.
+    // ms (optional): hipMalloc, the copy, hipFree of the old buffer, in milliseconds.
+    hipError_t grow_keep(size_t bytes, size_t used_bytes, hipStream_t st, double* ms = nullptr)
+    {
+        if (bytes <= cap) return hipSuccess;
+        const auto now_ms = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+        const double t0 = now_ms();
+        void* np = nullptr;
+        hipError_t e = hipMalloc(&np, bytes);
+        if (e != hipSuccess) return e;
+        const double t1 = now_ms();
+        if (used_bytes && p) {
+            e = hipMemcpyAsync(np, p, used_bytes, hipMemcpyDeviceToDevice, st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            if (e != hipSuccess) { (void)hipFree(np); return e; }
+        }
+        const double t2 = now_ms();
+        if (p) (void)hipFree(p);
+        p = np; cap = bytes;
+        if (ms) { ms[0] = t1 - t0; ms[1] = t2 - t1; ms[2] = now_ms() - t2; }
+        return hipSuccess;
+    }
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
