@@ -538,6 +538,18 @@ int l3d_test_rt_lanes(int opt, double avg_run);
  * needed, records that fit, bytes counted per record, bytes kept back }; L3D_OK, or L3D_ERR_NOMEM when what fits does not do */
 int l3d_test_arena_regrow(uint64_t arena_cap, uint64_t kept_base, int n_want, int done, int span, uint64_t free_bytes, uint64_t turn_room,
                           int early, int products, uint64_t out[5]);
+/* the rules of matchViews sharded by blocks of views (l3d_match_chain_blocks, l3d_match_chain_partition) on a table of digests given as plain arrays
+ * (tests; host only, no context, no device).  hash, n_kept: world x n_views, rank by rank -- every rank's digest of every view; comp_from[world]: the
+ * first view every rank computed; verified, S_src: per view.  check, tail: how many views in front of its block a rank is checked on and how far past
+ * it the chain runs (partition != 0 only).  Out: begin[world + 1] and owner[n_views], the blocks; reach_out = { reach, tail, check } as the modes derive
+ * them from window and neighbour_reach; miss[world], first_diff[world] (the first view at which a rank differs from its predecessor, or -1); summary =
+ * { ranks that missed, 1 when the pass is hopeless, the first rank whose table carries the failure mark or -1 }; what the predecessor of every rank
+ * that missed hands over, filed under the SENDER: t_rec[world] records, t_seg[world] segments, t_first[world] (its first verified view or -1), and
+ * maxima = { largest t_rec, largest t_seg } */
+int l3d_test_blocks_verdict(int n_views, int world, int window, int neighbour_reach, int check, int tail, int partition, const uint64_t* hash,
+                            const int32_t* n_kept, const int32_t* comp_from, const int32_t* verified, const int32_t* S_src, int32_t* begin, int32_t* owner,
+                            int32_t reach_out[3], int32_t* miss, int32_t* first_diff, int32_t summary[3], int64_t* t_rec, int64_t* t_seg, int32_t* t_first,
+                            int64_t maxima[2]);
 
 /* contract math exported for tests (device evaluation of c_expf / c_acosf / c_acos) */
 int l3d_test_contract_math(l3d_ctx* ctx, const float* x, int n, float* out_expf, float* out_acosf, double* out_acos);

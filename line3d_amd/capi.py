@@ -509,6 +509,25 @@ def arena_regrow(arena_cap, kept_base, n_want, done, span, free_bytes, turn_room
     return dict(ok=rc == 0, new_cap=int(out[0]), need=int(out[1]), fits=int(out[2]), per_rec=int(out[3]), reserve=int(out[4]))
 
 
+def blocks_verdict(n_views, world, check, tail, partition, hash, n_kept, comp_from, verified, S_src, window=0, neighbour_reach=0) -> dict:
+    """l3d_test_blocks_verdict: the rules of matchViews sharded by blocks of views on a table of digests (hash, n_kept: world x n_views) -- host only,
+    no context, no device.  -> dict(begin, owner, reach, miss, first_diff, n_miss, hopeless, failed_rank, t_rec, t_seg, t_first, max_rec, max_seg)"""
+    h = np.ascontiguousarray(hash, dtype=np.uint64).reshape(world, n_views)
+    nk = np.ascontiguousarray(n_kept, dtype=np.int32).reshape(world, n_views)
+    cf, ver, ss = (np.ascontiguousarray(a, dtype=np.int32) for a in (comp_from, verified, S_src))
+    assert len(cf) == world and len(ver) == n_views and len(ss) == n_views
+    begin, owner, reach = np.zeros(world + 1, np.int32), np.zeros(n_views, np.int32), np.zeros(3, np.int32)
+    miss, first_diff, summary, t_first = np.zeros(world, np.int32), np.zeros(world, np.int32), np.zeros(3, np.int32), np.zeros(world, np.int32)
+    t_rec, t_seg, maxima = np.zeros(world, np.int64), np.zeros(world, np.int64), np.zeros(2, np.int64)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
+    rc = load_library().l3d_test_blocks_verdict(C.c_int(n_views), C.c_int(world), C.c_int(window), C.c_int(neighbour_reach), C.c_int(check), C.c_int(tail), C.c_int(bool(partition)),
+                                                p(h), p(nk), p(cf), p(ver), p(ss), p(begin), p(owner), p(reach), p(miss), p(first_diff), p(summary), p(t_rec), p(t_seg), p(t_first), p(maxima))
+    if rc:
+        raise L3DError("l3d_test_blocks_verdict: error %d" % rc)
+    return dict(begin=begin.tolist(), owner=owner.tolist(), reach=tuple(reach.tolist()), miss=miss.tolist(), first_diff=first_diff.tolist(), n_miss=int(summary[0]),
+                hopeless=bool(summary[1]), failed_rank=int(summary[2]), t_rec=t_rec.tolist(), t_seg=t_seg.tolist(), t_first=t_first.tolist(), max_rec=int(maxima[0]), max_seg=int(maxima[1]))
+
+
 # dtype codes of l3d_device_image (L3D_U8 ...)
 U8, U16, F16, F32 = 0, 1, 2, 3
 _TYPESTR = {"|u1": U8, "<u2": U16, "<f2": F16, "<f4": F32}

@@ -255,6 +255,56 @@ def test_segment_sharded_partitioned_run_with_a_broken_exchange_fails_on_every_r
             l.close()
 
 
+def test_blocks_of_views_with_one_ranks_chain_out_of_memory_fail_on_every_rank():
+    """the failure protocol of l3d_match_chain_blocks and l3d_match_chain_partition: rank 1's kept arena is too small for its range and its regrow finds no
+    room (option regrow_free_mb = 1: a chain without products keeps 512 MB back, so the host rule answers NOMEM -- a return code, no device fault).  The
+    rank still enters the digest exchange, with the failure mark in its table, and the status words behind it; every rank comes back with an error, the
+    others naming rank 1, and nobody enters another collective."""
+    from line3d_amd.capi import L3DError
+    from line3d_amd.pipeline import Line3D, load_scene
+    from line3d_amd.synth import make_scene
+    V, S, N, W = 48, 150, 6, 3
+    ARENA = 1000
+    scene = make_scene(V, S, N, seed=5)
+    ref = _reference(scene, N, False)
+    # rank 1 keeps at least its own block, V / W views: whichever they are, more records than the arena given
+    kept = sorted(len(m) for m, _ in ref["lists"].values())
+    assert ARENA < sum(kept[:V // W]), kept
+    for mode in ("block_run", "partition_run"):
+        make, calls = thread_exchange(W, timeout=60.0)
+        ls, outcome = [], [None] * W
+        for r in range(W):
+            l = Line3D("", matchingNeighbors=N)
+            load_scene(l, scene)
+            l.prepare()
+            if r == 1:
+                l.context().set_chain_capacities(0, ARENA)
+                l.context().set_option("regrow_free_mb", 1)
+            ls.append(l)
+
+        def run(r):
+            try:
+                getattr(ls[r], mode)(r, W, make(r), None, -1)
+                outcome[r] = "ok"
+            except L3DError as e:
+                outcome[r] = "error: %s" % e
+        th = [threading.Thread(target=run, args=(r,)) for r in range(W)]
+        for x in th:
+            x.start()
+        for x in th:
+            x.join(timeout=120)
+        try:
+            assert not any(x.is_alive() for x in th), "%s: a rank is still waiting" % mode
+            assert all(o and o.startswith("error") for o in outcome), (mode, outcome)
+            assert "match_chain: the kept arena of %d records is full" % ARENA in outcome[1] and "does not fit beside it" in outcome[1], (mode, outcome[1])
+            for r in (0, 2):
+                assert "rank 1" in outcome[r], (mode, r, outcome[r])
+            assert [c[0] for c in calls] == [-1, -3], (mode, calls)
+        finally:
+            for l in ls:
+                l.close()
+
+
 def test_segment_sharded_partitioned_run_grows_one_ranks_arena_on_every_rank():
     """one rank's arena far too small: its verdict is no shared one by itself (every rank keeps other views) -- the ranks exchange it, all run again,
     the rank with more room"""
