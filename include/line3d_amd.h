@@ -1646,6 +1646,32 @@ int l3d_test_kept_write(l3d_ctx* ctx, int S, int N, const int32_t* row_start, co
                         const int32_t* kept_cnt, const uint32_t* local2global, l3d_test_kept_path* sel, l3d_match* records, uint32_t* side, int32_t* rt,
                         int32_t* best_pos);
 
+/* The affinity fill's core (affinity_fill_core of l3d_affinity.hip, the code l3d_affinity_fill, l3d_affinity_fill_resident and every rank of
+ * l3d_affinity_fill_sharded run) on host tables handed in as for l3d_affinity_fill, as ONE PART of a fill sharded by source key, exported for tests
+ * (tests/test_gpu_affinity_paths.py).  No collective runs, nothing is numbered: what comes back is what a rank holds before the exchanges.
+ * part in:  h0, h1: the sources (hypotheses) [h0, h1) whose candidates are enumerated; pos_base: where the part's candidates stand in the whole
+ *           enumeration (the sharded fill passes rank << 44); loc2glob (n_hyp, or NULL: the numbers stay local): the global number of every local
+ *           hypothesis, applied to the passed pairs; assume_symmetric != 0: every potential correspondence is taken to be recorded both ways
+ *           (k_aff_sym looks nothing up).
+ * out:      flags (entries of pot_tgt; may be NULL): one byte per potential correspondence as the last k_aff_groups launch left it -- bit 0 marked
+ *           as a target, bit 1 expanded, bit 2 m-used; needs_prev (n_views; may be NULL); part->n_launches: launches of k_aff_groups;
+ *           part->coll_sym: 1 = the collinearity table was found symmetric and the short-list path taken; part->n_candidates / n_passed: the part's
+ *           candidates and those that passed their threshold; pairs (2 x n_passed hypothesis numbers) / weights (n_passed): callee-allocated,
+ *           l3d_free; first (n_hyp; may be NULL): 2 * (pos_base + position among the part's candidates) + side as a minimum per LOCAL hypothesis,
+ *           ~0 = never touched.
+ * The table checks and their messages are those of l3d_affinity_fill; h0 > h1 or a range outside [0, n_hyp]: L3D_ERR_INVALID.  n_hyp == 0: L3D_OK,
+ * everything empty. */
+typedef struct l3d_test_affinity_part {
+    int32_t h0, h1;
+    uint64_t pos_base;
+    const int32_t* loc2glob;
+    int32_t assume_symmetric;
+    int32_t n_launches, coll_sym, pad;                  /* out */
+    int64_t n_candidates, n_passed;                     /* out */
+} l3d_test_affinity_part;
+int l3d_test_affinity_fill(l3d_ctx* ctx, const l3d_affinity_input* in, l3d_test_affinity_part* part, unsigned char* flags, int32_t* needs_prev,
+                           int32_t** pairs, float** weights, uint64_t* first);
+
 #ifdef __cplusplus
 }
 #endif

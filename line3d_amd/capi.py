@@ -817,6 +817,12 @@ class AffinityInput(C.Structure):
                 ("coll_w", C.c_void_p), ("sigma_a", C.c_float)]
 
 
+class AffinityPart(C.Structure):
+    """l3d_test_affinity_part (include/line3d_amd.h)"""
+    _fields_ = [("h0", C.c_int32), ("h1", C.c_int32), ("pos_base", C.c_uint64), ("loc2glob", C.c_void_p), ("assume_symmetric", C.c_int32),
+                ("n_launches", C.c_int32), ("coll_sym", C.c_int32), ("pad", C.c_int32), ("n_candidates", C.c_int64), ("n_passed", C.c_int64)]
+
+
 class Context:
     """One GPU, one stream, grow-only device arenas (l3d_ctx)."""
 
@@ -1488,15 +1494,43 @@ class Context:
                                                        C.c_float(sigma_a), _p(sim)))
         return sim
 
-    def affinity_fill(self, seg_base, view_hyp_begin, hyp, score, hyp_dense, best, pot_start, pot_tgt, coll_start, coll_other, coll_w, sigma_a):
-        """l3d_affinity_fill: flat tables -> (edges EDGE_DTYPE, node_hyp int32, number of enumerated candidate pairs)."""
-        In = AffinityInput
+    @staticmethod
+    def _affinity_input(seg_base, view_hyp_begin, hyp, score, hyp_dense, best, pot_start, pot_tgt, coll_start, coll_other, coll_w, sigma_a):
+        """-> (l3d_affinity_input, the arrays it points into)"""
         arrs = [np.ascontiguousarray(seg_base, np.int32), np.ascontiguousarray(view_hyp_begin, np.int32), np.ascontiguousarray(hyp, HYP_DTYPE),
                 np.ascontiguousarray(score, np.float32), np.ascontiguousarray(hyp_dense, np.int32), np.ascontiguousarray(best, np.int32),
                 np.ascontiguousarray(pot_start, np.int64), np.ascontiguousarray(pot_tgt, np.int32), np.ascontiguousarray(coll_start, np.int64),
                 np.ascontiguousarray(coll_other, np.int32), np.ascontiguousarray(coll_w, np.float32)]
         ptr = [a.ctypes.data_as(C.c_void_p) for a in arrs]
-        inp = In(len(arrs[0]) - 1, ptr[0], ptr[1], len(arrs[2]), ptr[2], ptr[3], ptr[4], ptr[5], ptr[6], ptr[7], ptr[8], ptr[9], ptr[10], float(sigma_a))
+        return AffinityInput(len(arrs[0]) - 1, ptr[0], ptr[1], len(arrs[2]), ptr[2], ptr[3], ptr[4], ptr[5], ptr[6], ptr[7], ptr[8], ptr[9], ptr[10], float(sigma_a)), arrs
+
+    def test_affinity_fill(self, tables, h0=0, h1=None, pos_base=0, loc2glob=None, assume_symmetric=False):
+        """l3d_test_affinity_fill: the fill's core as one part of a sharded fill.  tables: the arguments of affinity_fill, in order.  -> dict(flags uint8 per
+        potential correspondence, needs_prev int32 per view, n_launches, coll_sym, n_candidates, n_passed, pairs int32 (n_passed, 2), w float32, first uint64
+        per hypothesis)"""
+        inp, arrs = self._affinity_input(*tables)
+        nh, V, n_pot = len(arrs[2]), len(arrs[0]) - 1, len(arrs[7])
+        l2g = None if loc2glob is None else np.ascontiguousarray(loc2glob, np.int32)
+        if l2g is not None and len(l2g) != nh:
+            raise ValueError("loc2glob: one number per hypothesis")
+        part = AffinityPart(int(h0), nh if h1 is None else int(h1), int(pos_base), None if l2g is None else l2g.ctypes.data_as(C.c_void_p), int(bool(assume_symmetric)))
+        flags, needs_prev = np.zeros(n_pot + 1, np.uint8), np.zeros(V + 1, np.int32)
+        first = np.zeros(nh + 1, np.uint64)
+        pairs, w = C.c_void_p(), C.c_void_p()
+        self._chk(self.lib.l3d_test_affinity_fill(self.h, C.byref(inp), C.byref(part), _p(flags), _p(needs_prev), C.byref(pairs), C.byref(w), _p(first)))
+        n = int(part.n_passed)
+        out_pairs, out_w = np.zeros((n, 2), np.int32), np.zeros(n, np.float32)
+        if n:
+            C.memmove(out_pairs.ctypes.data, pairs, n * 8)
+            C.memmove(out_w.ctypes.data, w, n * 4)
+        self.lib.l3d_free(pairs)
+        self.lib.l3d_free(w)
+        return dict(flags=flags[:n_pot], needs_prev=needs_prev[:V], n_launches=int(part.n_launches), coll_sym=int(part.coll_sym),
+                    n_candidates=int(part.n_candidates), n_passed=n, pairs=out_pairs, w=out_w, first=first[:nh])
+
+    def affinity_fill(self, seg_base, view_hyp_begin, hyp, score, hyp_dense, best, pot_start, pot_tgt, coll_start, coll_other, coll_w, sigma_a):
+        """l3d_affinity_fill: flat tables -> (edges EDGE_DTYPE, node_hyp int32, number of enumerated candidate pairs)."""
+        inp, arrs = self._affinity_input(seg_base, view_hyp_begin, hyp, score, hyp_dense, best, pot_start, pot_tgt, coll_start, coll_other, coll_w, sigma_a)
         edges, nodes = C.c_void_p(), C.c_void_p()
         ne, nn, nc = C.c_int(0), C.c_int(0), C.c_int(0)
         self._chk(self.lib.l3d_affinity_fill(self.h, C.byref(inp), C.byref(edges), C.byref(ne), C.byref(nodes), C.byref(nn), C.byref(nc)))

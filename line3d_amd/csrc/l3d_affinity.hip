@@ -608,8 +608,12 @@ int affinity_number_edges(l3d_ctx* c, const unsigned long long* first, int nh, c
 // The fill proper, on tables that are already on the device (`a`: everything but dview / flags, which live in the context's scratch).
 // seg_base_h / vhb_h: host copies of the view tables (launch geometry).  part != nullptr: a rank's part of a fill sharded by source key
 // (SURVEY 8e): candidates of the sources [h0, h1) only, left as the passed list + first-touch minima in the context (no numbering).
+// cap != nullptr (l3d_test_affinity_fill only; null in every product call): what the k_aff_groups launches left, copied to the host behind them
+struct FillCapture { unsigned char* flags; int32_t* needs_prev; int n_launches; int coll_sym; };       // flags: n_pot bytes, needs_prev: n_views; either may be null
+
 int affinity_fill_core(l3d_ctx* c, AffIn a, const int32_t* seg_base_h, const int32_t* vhb_h, long long n_pot, long long n_coll, float sigma_a,
-                       l3d_edge** edges_out, int* n_edges_out, int32_t** node_hyp_out, int* n_nodes_out, int* n_candidates_out, const l3d::FillPart* part)
+                       l3d_edge** edges_out, int* n_edges_out, int32_t** node_hyp_out, int* n_nodes_out, int* n_candidates_out, const l3d::FillPart* part,
+                       FillCapture* cap = nullptr)
 {
     const int V = a.n_views, nh = a.n_hyp, nd = a.n_dense;
     hipStream_t st = c->stream;
@@ -669,6 +673,12 @@ int affinity_fill_core(l3d_ctx* c, AffIn a, const int32_t* seg_base_h, const int
     }
     if (timing) fprintf(stderr, "[l3d affinity] %d launch(es) of k_aff_groups for %d views\n", n_launches, V);
     lap("reverse records + groups");
+    if (cap) {
+        cap->n_launches = n_launches; cap->coll_sym = a.coll_sym;
+        if (cap->needs_prev) memcpy(cap->needs_prev, cut.data(), (size_t)V * 4);
+        if (cap->flags && n_pot > 0) HIPCHK(c, hipMemcpyAsync(cap->flags, a.flags, (size_t)n_pot, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+    }
 
     // ---- words, decisions, candidates: a BLOCK OF SOURCES at a time.  The reference enumerates its candidates source by source (line3D.cc:996-1221);
     // nothing in that order needs all of them at once, so the transient arrays -- decision words, candidate pairs and weights, their flags and
@@ -788,19 +798,16 @@ int affinity_fill_core(l3d_ctx* c, AffIn a, const int32_t* seg_base_h, const int
 
 }  // namespace
 
-extern "C" {
+namespace {
 
-int l3d_affinity_fill(l3d_ctx* c, const l3d_affinity_input* in, l3d_edge** edges_out, int* n_edges_out, int32_t** node_hyp_out, int* n_nodes_out,
-                      int* n_candidates_out)
+// The caller's tables: what the host can check before anything is launched, then the upload (one arena).  empty: no hypotheses -- nothing to do,
+// nothing was uploaded.
+int tables_to_device(l3d_ctx* c, const l3d_affinity_input* in, AffIn& a, long long& n_pot, long long& n_coll, bool& empty)
 {
-    if (!c) return L3D_ERR_INVALID;
-    if (!in || !edges_out || !n_edges_out || !node_hyp_out || !n_nodes_out) return fail(c, L3D_ERR_INVALID, "bad argument");
-    *edges_out = nullptr; *n_edges_out = 0; *node_hyp_out = nullptr; *n_nodes_out = 0;
-    c->resident_edges = 0; c->kept_edges = 0; c->resident_nodes = 0; c->resident_labels = 0;
-    if (n_candidates_out) *n_candidates_out = 0;
+    empty = false;
     const int V = in->n_views, nh = in->n_hyp;
     if (V < 0 || nh < 0 || (V > 0 && (!in->seg_base || !in->view_hyp_begin))) return fail(c, L3D_ERR_INVALID, "bad argument");
-    if (nh == 0) return L3D_OK;
+    if (nh == 0) { empty = true; return L3D_OK; }
     const int nd = in->seg_base[V];
     if (nd <= 0 || !in->hyp || !in->score || !in->hyp_dense || !in->best || !in->pot_start || !in->coll_start) return fail(c, L3D_ERR_INVALID, "bad argument");
     // the view tables decide where k_aff_dview writes and how the arena is laid out: checked on the host before anything is launched
@@ -809,7 +816,7 @@ int l3d_affinity_fill(l3d_ctx* c, const l3d_affinity_input* in, l3d_edge** edges
     for (int v = 0; v < V; ++v)
         if (in->seg_base[v + 1] < in->seg_base[v] || in->view_hyp_begin[v + 1] < in->view_hyp_begin[v]) return fail(c, L3D_ERR_INVALID, "affinity fill: view tables must ascend");
     if (in->seg_base[0] != 0 || in->view_hyp_begin[0] != 0 || in->view_hyp_begin[V] != nh) return fail(c, L3D_ERR_INVALID, "affinity fill: view tables do not cover the hypotheses");
-    const long long n_pot = in->pot_start[nd], n_coll = in->coll_start[nd];
+    n_pot = in->pot_start[nd]; n_coll = in->coll_start[nd];
     if (n_pot < 0 || n_coll < 0 || n_coll > 0x7fffffffll || (n_pot > 0 && !in->pot_tgt) || (n_coll > 0 && (!in->coll_other || !in->coll_w)))
         return fail(c, L3D_ERR_INVALID, "bad argument");
     HIPCHK(c, hipSetDevice(c->device));
@@ -843,7 +850,6 @@ int l3d_affinity_fill(l3d_ctx* c, const l3d_affinity_input* in, l3d_edge** edges
     HIPCHK(c, up(o_cs, in->coll_start, (size_t)(nd + 1) * 8));
     HIPCHK(c, up(o_co, in->coll_other, (size_t)n_coll * 4));
     HIPCHK(c, up(o_cw, in->coll_w, (size_t)n_coll * 4));
-    AffIn a;
     a.n_views = V; a.n_hyp = nh; a.n_dense = nd;
     a.seg_base = reinterpret_cast<const int*>(base + o_base);
     a.hyp = c->aff_hyp.as<Hypothesis>();
@@ -856,6 +862,26 @@ int l3d_affinity_fill(l3d_ctx* c, const l3d_affinity_input* in, l3d_edge** edges
     a.coll_other = reinterpret_cast<const int*>(base + o_co);
     a.coll_w = reinterpret_cast<const float*>(base + o_cw);
     a.pot_trusted = 0; a.coll_sym = 0;
+    return L3D_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int l3d_affinity_fill(l3d_ctx* c, const l3d_affinity_input* in, l3d_edge** edges_out, int* n_edges_out, int32_t** node_hyp_out, int* n_nodes_out,
+                      int* n_candidates_out)
+{
+    if (!c) return L3D_ERR_INVALID;
+    if (!in || !edges_out || !n_edges_out || !node_hyp_out || !n_nodes_out) return fail(c, L3D_ERR_INVALID, "bad argument");
+    *edges_out = nullptr; *n_edges_out = 0; *node_hyp_out = nullptr; *n_nodes_out = 0;
+    c->resident_edges = 0; c->kept_edges = 0; c->resident_nodes = 0; c->resident_labels = 0;
+    if (n_candidates_out) *n_candidates_out = 0;
+    AffIn a;
+    long long n_pot = 0, n_coll = 0;
+    bool empty = false;
+    if (int rc = tables_to_device(c, in, a, n_pot, n_coll, empty)) return rc;
+    if (empty) return L3D_OK;
     return affinity_fill_core(c, a, in->seg_base, in->view_hyp_begin, n_pot, n_coll, in->sigma_a, edges_out, n_edges_out, node_hyp_out, n_nodes_out, n_candidates_out, nullptr);
 }
 
@@ -864,6 +890,52 @@ int l3d_last_fill_counts(l3d_ctx* c, int64_t* n_candidates, int64_t* n_passed)
     if (!c) return L3D_ERR_INVALID;
     if (n_candidates) *n_candidates = c->fill_items;
     if (n_passed) *n_passed = c->fill_passed;
+    return L3D_OK;
+}
+
+// affinity_fill_core as one part of a sharded fill, on host tables (include/line3d_amd.h; tests/test_gpu_affinity_paths.py)
+int l3d_test_affinity_fill(l3d_ctx* c, const l3d_affinity_input* in, l3d_test_affinity_part* part, unsigned char* flags, int32_t* needs_prev,
+                           int32_t** pairs_out, float** weights_out, uint64_t* first_out)
+{
+    if (!c) return L3D_ERR_INVALID;
+    if (!in || !part || !pairs_out || !weights_out) return fail(c, L3D_ERR_INVALID, "bad argument");
+    *pairs_out = nullptr; *weights_out = nullptr;
+    part->n_launches = 0; part->coll_sym = 0; part->n_candidates = 0; part->n_passed = 0;
+    c->resident_edges = 0; c->kept_edges = 0; c->resident_nodes = 0; c->resident_labels = 0;
+    if (part->h0 < 0 || part->h1 < part->h0 || part->h1 > in->n_hyp) return fail(c, L3D_ERR_INVALID, "l3d_test_affinity_fill: the part's sources are no range of the hypotheses");
+    AffIn a;
+    long long n_pot = 0, n_coll = 0;
+    bool empty = false;
+    if (int rc = tables_to_device(c, in, a, n_pot, n_coll, empty)) return rc;
+    if (empty) return L3D_OK;
+    const int nh = in->n_hyp;
+    hipStream_t st = c->stream;
+    FillPart fp;
+    fp.h0 = part->h0; fp.h1 = part->h1; fp.pos_base = part->pos_base; fp.assume_symmetric = part->assume_symmetric ? 1 : 0;
+    if (part->loc2glob) {
+        HIPCHK(c, c->aff_l2g.reserve((size_t)nh * 4 + 64));
+        HIPCHK(c, hipMemcpyAsync(c->aff_l2g.p, part->loc2glob, (size_t)nh * 4, hipMemcpyHostToDevice, st));
+        fp.loc2glob = c->aff_l2g.as<int>();
+    }
+    FillCapture cap = { flags, needs_prev, 0, 0 };
+    int n_e = 0, n_n = 0, n_c = 0;
+    int32_t* nhp = nullptr;
+    if (int rc = affinity_fill_core(c, a, in->seg_base, in->view_hyp_begin, n_pot, n_coll, in->sigma_a, nullptr, &n_e, &nhp, &n_n, &n_c, &fp, &cap)) return rc;
+    part->n_launches = cap.n_launches; part->coll_sym = cap.coll_sym;
+    part->n_candidates = c->fill_items; part->n_passed = c->fill_passed;
+    const size_t np = (size_t)c->fill_passed;
+    int32_t* hp = static_cast<int32_t*>(malloc(np * 8 + 8));
+    float* hw = static_cast<float*>(malloc(np * 4 + 4));
+    if (!hp || !hw) { free(hp); free(hw); return fail(c, L3D_ERR_NOMEM, "l3d_test_affinity_fill: host allocation failed"); }
+    hipError_t e = hipSuccess;
+    if (np) {
+        e = hipMemcpyAsync(hp, c->aff_pass_pairs.p, np * 8, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(hw, c->aff_pass_w.p, np * 4, hipMemcpyDeviceToHost, st);
+    }
+    if (e == hipSuccess && first_out) e = hipMemcpyAsync(first_out, c->aff_first.p, (size_t)nh * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { free(hp); free(hw); return fail(c, L3D_ERR_HIP, std::string("l3d_test_affinity_fill: ") + hipGetErrorString(e)); }
+    *pairs_out = hp; *weights_out = hw;
     return L3D_OK;
 }
 

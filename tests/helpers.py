@@ -225,3 +225,37 @@ def sector_rejected(mv, cam, accepted):
     q1, q2 = one(s2[:, :2]), one(s2[:, 2:])
     a = np.stack([e1 @ q1.T, e1 @ q2.T, e2 @ q1.T, e2 @ q2.T])
     return int((accepted & ((a > 0).all(0) | (a < 0).all(0))).sum())
+
+
+# ---- the reference's `used` rule applied literally (tests/cpp/literal_used_rule.c) -----------------------------------------------------------------
+LITERAL_ITEM = np.dtype([("a", "<i4"), ("b", "<i4"), ("kind", "<i4"), ("cw", "<f4")])
+
+
+def literal_rule_lib():
+    """tests/cpp/literal_used_rule.c (the reference's `used` bookkeeping applied literally on one thread), built on demand"""
+    import ctypes as C
+    import os
+    import subprocess
+    here = os.path.dirname(os.path.abspath(__file__))
+    out = os.path.join(here, "cpp", "_build")
+    os.makedirs(out, exist_ok=True)
+    so = os.path.join(out, "libliteral_used_rule.so")
+    src = os.path.join(here, "cpp", "literal_used_rule.c")
+    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
+        subprocess.check_call(["gcc", "-O2", "-shared", "-fPIC", "-Wall", "-o", so, src])
+    lib = C.CDLL(so)
+    lib.literal_used_rule.restype = C.c_int64
+    return lib
+
+
+def literal_rule_items(lib, t):
+    """the literal rule's candidates (LITERAL_ITEM array, in the reference's order) on a table dict of tests/affinity_cases.py"""
+    import ctypes as C
+    keep = [np.ascontiguousarray(t["hyp_dense"], np.int32), np.ascontiguousarray(t["best"], np.int32), np.ascontiguousarray(t["pot_start"], np.int64),
+            np.ascontiguousarray(t["pot_tgt"], np.int32), np.ascontiguousarray(t["coll_start"], np.int64), np.ascontiguousarray(t["coll_other"], np.int32),
+            np.ascontiguousarray(t["coll_w"], np.float32)]
+    args = [C.c_int32(len(keep[1])), C.c_int32(len(keep[0]))] + [a.ctypes.data_as(C.c_void_p) for a in keep]
+    n = lib.literal_used_rule(*args, None, C.c_int64(0))
+    items = np.zeros(n, LITERAL_ITEM)
+    assert lib.literal_used_rule(*args, items.ctypes.data_as(C.c_void_p), C.c_int64(n)) == n
+    return items

@@ -50,7 +50,9 @@ def test_struct_layouts(tmp_path):
                    '  sizeof(l3d_test_kept_path), offsetof(l3d_test_kept_path, arena_cap), offsetof(l3d_test_kept_path, n_jobs), offsetof(l3d_test_kept_path, rebuild_blocks),\n'
                    '  offsetof(l3d_test_kept_path, kept_base));\n'
                    '  printf("%zu %zu %zu %zu %zu\\n", sizeof(l3d_test_collect_path), offsetof(l3d_test_collect_path, avg_kept), offsetof(l3d_test_collect_path, overflowed),\n'
-                   '  offsetof(l3d_test_collect_path, kernels), offsetof(l3d_test_collect_path, R)); return 0; }\n')
+                   '  offsetof(l3d_test_collect_path, kernels), offsetof(l3d_test_collect_path, R));\n'
+                   '  printf("%zu %zu %zu %zu %zu %zu\\n", sizeof(l3d_test_affinity_part), offsetof(l3d_test_affinity_part, pos_base), offsetof(l3d_test_affinity_part, loc2glob),\n'
+                   '  offsetof(l3d_test_affinity_part, assume_symmetric), offsetof(l3d_test_affinity_part, coll_sym), offsetof(l3d_test_affinity_part, n_passed)); return 0; }\n')
     exe = str(tmp_path / "layout")
     subprocess.check_call(["gcc", "-std=c99", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe])
     got = [int(x) for x in subprocess.run([exe], capture_output=True, text=True).stdout.split()]
@@ -67,7 +69,9 @@ def test_struct_layouts(tmp_path):
                    ctypes.sizeof(capi.KeptPath), capi.KeptPath.arena_cap.offset, capi.KeptPath.n_jobs.offset, capi.KeptPath.rebuild_blocks.offset,
                    capi.KeptPath.kept_base.offset,
                    ctypes.sizeof(capi.CollectPath), capi.CollectPath.avg_kept.offset, capi.CollectPath.overflowed.offset, capi.CollectPath.kernels.offset,
-                   capi.CollectPath.R.offset], got
+                   capi.CollectPath.R.offset,
+                   ctypes.sizeof(capi.AffinityPart), capi.AffinityPart.pos_base.offset, capi.AffinityPart.loc2glob.offset, capi.AffinityPart.assume_symmetric.offset,
+                   capi.AffinityPart.coll_sym.offset, capi.AffinityPart.n_passed.offset], got
 
 
 def test_no_gpu_fails_loudly():

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import l3d_oracle_pipeline as op
+from helpers import literal_rule_lib
 
 pytestmark = pytest.mark.gpu
 
@@ -160,23 +161,6 @@ def test_full_size_diffusion_equals_oracle(chain_run, oracle_lib):
     ctx.close()
 
 
-def _literal_rule_lib():
-    """tests/cpp/literal_used_rule.c (the reference's `used` bookkeeping applied literally on one thread), built on demand"""
-    import ctypes as C
-    import os
-    import subprocess
-    here = os.path.dirname(os.path.abspath(__file__))
-    out = os.path.join(here, "cpp", "_build")
-    os.makedirs(out, exist_ok=True)
-    so = os.path.join(out, "libliteral_used_rule.so")
-    src = os.path.join(here, "cpp", "literal_used_rule.c")
-    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
-        subprocess.check_call(["gcc", "-O2", "-shared", "-fPIC", "-Wall", "-o", so, src])
-    lib = C.CDLL(so)
-    lib.literal_used_rule.restype = C.c_int64
-    return lib
-
-
 def test_full_size_affinity_fill_device_equals_literal_host_rule(chain_run, full_scene, gpu_ctx, monkeypatch):
     """The affinity fill runs on the device (l3d_affinity_fill: per-target "expanded" bits instead of the reference's `used` maps),
     on tables that never left it.  Cross-check at full size: (i) the device path with 5-target passes (groups and flattened entries
@@ -244,7 +228,7 @@ def test_full_size_affinity_fill_device_equals_literal_host_rule(chain_run, full
     coll_start = np.zeros(nd + 1, np.int64)
     np.add.at(coll_start, ci + 1, 1)
     coll_start = np.cumsum(coll_start)
-    lib = _literal_rule_lib()
+    lib = literal_rule_lib()
     item_t = np.dtype([("a", "<i4"), ("b", "<i4"), ("kind", "<i4"), ("cw", "<f4")])
     pot_start, pot_tgt = np.ascontiguousarray(pr["pot_start"]), np.ascontiguousarray(pr["pot_tgt"])
     args = [C.c_int32(nd), C.c_int32(nh), hyp_dense.ctypes.data_as(C.c_void_p), best.ctypes.data_as(C.c_void_p), pot_start.ctypes.data_as(C.c_void_p),
