@@ -550,6 +550,28 @@ int l3d_test_blocks_verdict(int n_views, int world, int window, int neighbour_re
                             const int32_t* n_kept, const int32_t* comp_from, const int32_t* verified, const int32_t* S_src, int32_t* begin, int32_t* owner,
                             int32_t reach_out[3], int32_t* miss, int32_t* first_diff, int32_t summary[3], int64_t* t_rec, int64_t* t_seg, int32_t* t_first,
                             int64_t maxima[2]);
+/* the sizing rules of the segment-sharded run (l3d_shard_chain_open, l3d_shard_chain_run, l3d_line3d_shard_run) on plain numbers (tests; host only, no
+ * context, no device).  Five sections, each skipped when its input is NULL:
+ *   geom_in = { largest S_src, largest N, world, slot_records, option slot_cams_min, n_views } -> geom_out = { seg_cap, offsets of the best depth
+ *     pairs, the best positions, the records, the side words (0: none), the run table (0: none), slot bytes, bytes of a staging buffer, ring, max_n }
+ *   ring_in = { n_views, window, bytes of a view's gathered block, option slot_ring, partitioned, commits on the host } -> ring_out = { ring mode,
+ *     view blocks in the gathered buffer, slots sent from }
+ *   pairs, guess_in = { world, test cap (0: none), cap seen, option arena_guess, free bytes (-1: not known), option regrow_free_mb, partitioned, views
+ *     kept, n_views, cap seen by a partitioned pass } -> guess_out = { first guess of the compact kept arena, room under regrow_free_mb (0: no limit) }
+ *   verdict_in = { overflow bits (1 candidates, 2 slot, 4 gave up, 8 arena), largest candidate count, largest kept count, arena total } -> the
+ *     run's return code and error text (text_cap bytes, cut if longer)
+ *   retry_in = { bits, candidate capacity, largest candidate count, slot_records, largest kept count, arena needed, room, replayed exchange } ->
+ *     retry_out = { retry, next candidate capacity, next slot_records, next arena capacity (0 each: as it was), refused for room } */
+int l3d_test_shard_plan(const int64_t geom_in[6], int64_t geom_out[10], const int64_t ring_in[6], int32_t ring_out[3], double pairs, const int64_t guess_in[10],
+                        int64_t* guess_out, const int64_t verdict_in[4], int32_t* verdict_rc, char* text, int text_cap, const int64_t retry_in[8],
+                        int64_t retry_out[5]);
+/* the retirement schedule of a ring-mode run as l3d_shard_chain_run drives it (tests; host only): for every view k the views retired and the views whose
+ * retirement the chain has waited for when view k's exchange is enqueued (retired_at, waited_at: n_views each); every batch as four ints { first view,
+ * count, the view it was enqueued at (n_views: the final flush), 1 when the chain waited for the batch before it first } (batches: 4 x max_batches);
+ * summary = { ring mode, view blocks in the ring, batches, retired and waited for after the flush, 1 when a batch is still outstanding }.
+ * apart: the retirement runs on a side stream (option retire_apart).  Not in ring mode nothing is scheduled: the per-view arrays stay as given */
+int l3d_test_shard_retire(int n_views, int window, int slot_ring, int partition, int apart, int32_t* retired_at, int32_t* waited_at, int32_t* batches,
+                          int max_batches, int32_t summary[6]);
 
 /* contract math exported for tests (device evaluation of c_expf / c_acosf / c_acos) */
 int l3d_test_contract_math(l3d_ctx* ctx, const float* x, int n, float* out_expf, float* out_acosf, double* out_acos);

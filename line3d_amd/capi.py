@@ -528,6 +528,68 @@ def blocks_verdict(n_views, world, check, tail, partition, hash, n_kept, comp_fr
                 hopeless=bool(summary[1]), failed_rank=int(summary[2]), t_rec=t_rec.tolist(), t_seg=t_seg.tolist(), t_first=t_first.tolist(), max_rec=int(maxima[0]), max_seg=int(maxima[1]))
 
 
+def _i64(values):
+    return (C.c_int64 * len(values))(*[int(v) for v in values])
+
+
+def _shard_plan(geom=None, ring=None, pairs=0.0, guess=None, verdict=None, retry=None):
+    """l3d_test_shard_plan on the sections given -> (geom_out, ring_out, guess_out, verdict rc, text, retry_out)"""
+    geom_out, ring_out, guess_out, retry_out = (C.c_int64 * 10)(), (C.c_int32 * 3)(), (C.c_int64 * 2)(), (C.c_int64 * 5)()
+    vrc, text = C.c_int32(0), C.create_string_buffer(1024)
+    rc = load_library().l3d_test_shard_plan(_i64(geom) if geom else None, geom_out, _i64(ring) if ring else None, ring_out, C.c_double(float(pairs)),
+                                            _i64(guess) if guess else None, guess_out, _i64(verdict) if verdict else None, C.byref(vrc), text, C.c_int(len(text)),
+                                            _i64(retry) if retry else None, retry_out)
+    if rc:
+        raise L3DError("l3d_test_shard_plan: error %d" % rc)
+    return list(geom_out), list(ring_out), list(guess_out), int(vrc.value), text.value.decode(), list(retry_out)
+
+
+def shard_slot_geometry(maxS, maxN, world, slot_records, slot_cams_min, n_views) -> dict:
+    """l3d_test_shard_plan, geometry: the layout of a slot of the segment-sharded run -- host only, no context, no device"""
+    keys = ("seg_cap", "best_off", "bpos_off", "rec_off", "cam_off", "rt_off", "slot_bytes", "stage_bytes", "ring", "max_n")
+    return dict(zip(keys, _shard_plan(geom=(maxS, maxN, world, slot_records, slot_cams_min, n_views))[0]))
+
+
+def shard_ring_plan(n_views, window, block_bytes, slot_ring, partition, host_commit) -> dict:
+    """l3d_test_shard_plan, ring plan: whether the gathered blocks of a run live in a ring, and how long it is"""
+    out = _shard_plan(ring=(n_views, window, block_bytes, slot_ring, bool(partition), bool(host_commit)))[1]
+    return dict(ring_mode=bool(out[0]), ring_views=out[1], send_ring=out[2])
+
+
+def shard_arena_first_guess(pairs, world, test_cap, seen_cap, arena_guess, free_bytes, regrow_free_mb, partition, kept_views, n_views, part_seen):
+    """l3d_test_shard_plan, first guess: (records of the compact kept arena's first guess, room in records under regrow_free_mb); free_bytes -1: not known"""
+    out = _shard_plan(pairs=pairs, guess=(world, test_cap, seen_cap, arena_guess, free_bytes, regrow_free_mb, bool(partition), kept_views, n_views, part_seen))[2]
+    return out[0], out[1]
+
+
+def shard_verdict(bits, max_cand, max_kept, arena_total):
+    """l3d_test_shard_plan, verdict: (return code, error text) of a run whose gathered overflow bits are `bits`"""
+    out = _shard_plan(verdict=(bits, max_cand, max_kept, arena_total))
+    return out[3], out[4]
+
+
+def shard_retry(bits, cand_cap, max_cand, slot_records, max_kept, arena_needed, room, replay) -> dict:
+    """l3d_test_shard_plan, retry: what l3d_line3d_shard_run does with a capacity verdict"""
+    out = _shard_plan(retry=(bits, cand_cap, max_cand, slot_records, max_kept, arena_needed, room, bool(replay)))[5]
+    return dict(retry=bool(out[0]), cand_cap_next=out[1], slot_records_next=out[2], arena_cap_next=out[3], refuse_for_room=bool(out[4]))
+
+
+def shard_retire(n_views, window, slot_ring, partition, apart) -> dict:
+    """l3d_test_shard_retire: the retirement schedule of a ring-mode run over all its views -- host only, no context, no device.
+    -> dict(ring_mode, ring, retired_at, waited_at, batches [(first, count, enqueued at view, waited before)], retired, waited, outstanding)"""
+    n = max(0, n_views)
+    max_batches = n // 16 + n + 2
+    retired_at, waited_at = np.zeros(max(1, n), np.int32), np.zeros(max(1, n), np.int32)
+    batches, summary = np.zeros((max_batches, 4), np.int32), np.zeros(6, np.int32)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
+    rc = load_library().l3d_test_shard_retire(C.c_int(n_views), C.c_int(window), C.c_int(slot_ring), C.c_int(bool(partition)), C.c_int(bool(apart)), p(retired_at), p(waited_at),
+                                              p(batches), C.c_int(max_batches), p(summary))
+    if rc:
+        raise L3DError("l3d_test_shard_retire: error %d" % rc)
+    return dict(ring_mode=bool(summary[0]), ring=int(summary[1]), retired_at=retired_at[:n].tolist(), waited_at=waited_at[:n].tolist(),
+                batches=[tuple(int(x) for x in b) for b in batches[:int(summary[2])]], retired=int(summary[3]), waited=int(summary[4]), outstanding=bool(summary[5]))
+
+
 # dtype codes of l3d_device_image (L3D_U8 ...)
 U8, U16, F16, F32 = 0, 1, 2, 3
 _TYPESTR = {"|u1": U8, "<u2": U16, "<f2": F16, "<f4": F32}

@@ -380,6 +380,21 @@ int release_chain_scratch(l3d_ctx* c, std::initializer_list<DevBuf*> extra)
     return L3D_OK;
 }
 
+StatusWords exchange_status_words(l3d_exchange_fn exchange, void* user, int world, long long mine, void* own, void* all, hipStream_t st, std::vector<long long>& words)
+{
+    StatusWords s;
+    s.publish = hipMemcpyAsync(own, &mine, 8, hipMemcpyHostToDevice, st);
+    if (s.publish == hipSuccess) s.publish = hipStreamSynchronize(st);          // (`mine` is a stack word)
+    if (s.publish != hipSuccess) (void)hipMemsetAsync(own, 0xff, 8, st);        // (all ones = -1: failed)
+    s.exchanged = exchange && exchange(user, -3, own, all, 256, world, (void*)st) == 0;
+    if (!s.exchanged) return s;
+    words.assign((size_t)world, 0);
+    for (int r = 0; r < world && s.read == hipSuccess; ++r)
+        s.read = hipMemcpyAsync(&words[(size_t)r], static_cast<const unsigned char*>(all) + (size_t)r * 256, 8, hipMemcpyDeviceToHost, st);
+    if (s.read == hipSuccess) s.read = hipStreamSynchronize(st);
+    return s;
+}
+
 int chain_dense_view(const l3d_chain_view* views, int n_views, const l3d_dense_map* map, int k)
 {
     if (k >= n_views) return map->n_views;

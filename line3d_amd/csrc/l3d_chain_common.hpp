@@ -174,6 +174,13 @@ private:
 // neighbours), given back once both streams are idle -- a job sized by memory does this before it builds its products.  extra: the caller's own.
 L3D_HIDDEN int release_chain_scratch(l3d_ctx* c, std::initializer_list<DevBuf*> extra = {});
 
+// The status words of the partitioned jobs: every rank publishes ONE word (`own`: device, 256 B; negative by convention = this rank failed), the words
+// are exchanged with tag -3 (`all`: device, world x 256 B) and read back with one synchronisation.  A rank that cannot publish sends -1 and still
+// enters the exchange: nobody is left waiting.  Each caller words its own messages: publish / read are the HIP errors of the two halves, !exchanged the
+// failure of the exchange itself (every rank's does; `words` is then not filled).
+struct StatusWords { hipError_t publish = hipSuccess, read = hipSuccess; bool exchanged = false; };
+L3D_HIDDEN StatusWords exchange_status_words(l3d_exchange_fn exchange, void* user, int world, long long mine, void* own, void* all, hipStream_t st, std::vector<long long>& words);
+
 // the dense view a chain view is (ids ascend in both; k >= n_views: one past the last)
 L3D_HIDDEN int chain_dense_view(const l3d_chain_view* views, int n_views, const l3d_dense_map* map, int k);
 // a rank's share of partitioned products from its ranges in chain positions: its block, the views whose rows it builds, the views it holds

@@ -455,14 +455,10 @@ struct BlocksRun {
     int all_gather_word(long long mine, const char* what)
     {
         if (local_rc && mine >= 0) mine = -(long long)local_rc;
-        hipError_t e = hipMemcpyAsync(st_own, &mine, 8, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);                   // (`mine` is a stack word)
-        if (e != hipSuccess) { note(fail(c, L3D_ERR_HIP, std::string("l3d_match_chain_blocks: status word: ") + hipGetErrorString(e))); (void)hipMemsetAsync(st_own, 0xff, 8, st); }   // (all ones = -1: failed)
-        if (exchange(exchange_user, -3, st_own, st_all, 256, world, (void*)st)) return fail(c, L3D_ERR_HIP, std::string("l3d_match_chain_blocks: the exchange of the status words failed (") + what + ")");
-        e = hipSuccess;
-        for (int r = 0; r < world && e == hipSuccess; ++r) e = hipMemcpyAsync(&words[(size_t)r], reinterpret_cast<const unsigned char*>(st_all) + (size_t)r * 256, 8, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return fail(c, L3D_ERR_HIP, std::string("l3d_match_chain_blocks: status word: ") + hipGetErrorString(e));     // (after the collective: nobody waits for this rank any more)
+        const StatusWords s = exchange_status_words(exchange, exchange_user, world, mine, st_own, st_all, st, words);
+        if (s.publish != hipSuccess) note(fail(c, L3D_ERR_HIP, std::string("l3d_match_chain_blocks: status word: ") + hipGetErrorString(s.publish)));      // (it sent -1: failed)
+        if (!s.exchanged) return fail(c, L3D_ERR_HIP, std::string("l3d_match_chain_blocks: the exchange of the status words failed (") + what + ")");
+        if (s.read != hipSuccess) return fail(c, L3D_ERR_HIP, std::string("l3d_match_chain_blocks: status word: ") + hipGetErrorString(s.read));     // (after the collective: nobody waits for this rank any more)
         if (local_rc) return fail(c, local_rc, local_err);
         for (int r = 0; r < world; ++r)
             if (words[(size_t)r] < 0) return fail(c, L3D_ERR_HIP, "l3d_match_chain_blocks: rank " + std::to_string(r) + " failed (code " + std::to_string(-words[(size_t)r]) + ") while " + what);

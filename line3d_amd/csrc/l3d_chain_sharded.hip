@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <atomic>
 #include <condition_variable>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -25,6 +26,7 @@
 #include "l3d_kept.hpp"
 #include "l3d_chain_common.hpp"
 #include "l3d_products.hpp"
+#include "l3d_shard_rule.hpp"
 
 using namespace l3d;
 
@@ -43,10 +45,7 @@ static inline void wait_until(Pred pred, int spins_before_sleep)
 namespace l3d {
 
 struct SlotHeader { int n_kept, R, overflow, s0, s1, pad[3]; };
-static_assert(sizeof(SlotHeader) == 32, "slot header");
-
-// ring: view blocks the gathered buffer holds (view k lives in block k % ring); n_views when every block is kept
-struct SlotGeom { size_t slot_bytes, best_off, bpos_off, rec_off, cam_off, rt_off; int seg_cap, slot_records, world, ring, max_n; };   // rt_off: 0 = no run table in the slot   // cam_off: 0 = the slot carries no side array of target cameras
+static_assert(sizeof(SlotHeader) == kShardSlotHeaderBytes && sizeof(Match) == kShardRecordBytes, "slot header, kept record (SlotGeom: l3d_shard_rule.hpp)");
 
 // reverse matches for view `view_id`, source-segment range [s0,s1), out of the gathered slots of earlier views
 // (blockIdx.y = source * world + rank)
@@ -365,8 +364,6 @@ namespace {
 
 typedef l3d::ChainViewDev SViewDev;           // (s0, s1: this rank's source-segment range)
 
-size_t salign(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 }  // namespace
 
 struct l3d_shard_chain {
@@ -402,24 +399,29 @@ struct l3d_shard_chain {
     l3d_match* copy_dst = nullptr;           // ... and where its records go (pinned arena)
     double t_wait = 0, t_copy = 0, t_cb = 0, t_enq = 0, t_ex = 0;   // host-side phase timers (L3D_TIMING=1)
     int outcome[3] = { 0, 0, 0 };            // after l3d_shard_chain_run: OR of the ranks' overflow bits (8: the compact arena of the ring mode), largest candidate / kept count of a slot
-    // ring mode of l3d_shard_chain_run (commit on the device only): the gathered buffer holds `ring` view blocks, older ones are retired
-    bool ring_mode = false;
-    int window = 0;                          // max over views of (index - smallest source index): how far back a view reads
-    long long arena_cap = 0, arena_needed = 0;
-    long long* base_dev = nullptr;           // arena offset of every view (+ the total behind the last), kept on the device
-    SlotHeader* hdr_all = nullptr;           // the headers of all slots of all views (32 B each)
-    const long long* best_off_dev = nullptr;
-    const unsigned char* ver_dev = nullptr;
-    bool retire_tables = false;              // the retire kernel also files the slots' side words and run tables (ch_keptcam, ch_rt): the products need not rebuild them
-    std::vector<long long> rt_off;           // where view k's run table starts in ch_rt (ints)
+    // ring mode of l3d_shard_chain_run (commit on the device only): the gathered buffer holds `geom.ring` view blocks, older ones are retired.  Set by the
+    // run (ShardRun::plan_ring, setup_ring_tables, shared_verdict), read by the products; `window` alone is the schedule's, set when the chain is opened
+    struct Ring {
+        bool on = false;
+        int window = 0;                      // max over views of (index - smallest source index): how far back a view reads
+        long long arena_cap = 0, arena_needed = 0;
+        long long* base_dev = nullptr;       // arena offset of every view (+ the total behind the last), kept on the device
+        SlotHeader* hdr_all = nullptr;       // the headers of all slots of all views (32 B each)
+        const long long* best_off_dev = nullptr;
+        const unsigned char* ver_dev = nullptr;
+        bool retire_tables = false;          // the retire kernel also files the slots' side words and run tables (ch_keptcam, ch_rt): the products need not rebuild them
+        std::vector<long long> rt_off;       // where view k's run table starts in ch_rt (ints)
+    } ring;
     // partitioned retirement (l3d_shard_chain_partition): only the views flagged in `keep` go to this rank's compact arena
-    bool partition = false;
-    int part_own0 = 0, part_own1 = 0, part_reach = 0;
-    std::vector<unsigned char> keep;
-    const unsigned char* keep_dev = nullptr;
-    l3d_exchange_fn part_exchange = nullptr;   // the run's exchange: l3d_shard_chain_products' one status exchange
-    void* part_user = nullptr;
-    unsigned char* part_status = nullptr;
+    struct Part {
+        bool on = false;
+        int own0 = 0, own1 = 0, reach = 0;
+        std::vector<unsigned char> keep;
+        const unsigned char* keep_dev = nullptr;
+        l3d_exchange_fn exchange = nullptr;  // the run's exchange: l3d_shard_chain_products' one status exchange
+        void* user = nullptr;
+        unsigned char* status = nullptr;     // [own word | the ranks' words], 256 B each (RingTables::status)
+    } part;
 };
 
 extern "C" {
@@ -436,65 +438,48 @@ int l3d_shard_chain_open(l3d_ctx* c, const l3d_chain_view* views, int n_views, i
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     (void)hipGetLastError();
-    l3d_shard_chain* h = new l3d_shard_chain();
+    std::unique_ptr<l3d_shard_chain> h(new l3d_shard_chain());       // (the caller's once *out is set: every return before that frees it)
     h->c = c; h->views = views; h->n_views = n_views; h->rank = rank; h->world = world;
     ChainLayout L;
-    { int rc = chain_plan_views(c, views, n_views, rank, world, h->vd, L, "l3d_shard_chain_open"); if (rc) { delete h; return rc; } }
+    if (int rc = chain_plan_views(c, views, n_views, rank, world, h->vd, L, "l3d_shard_chain_open")) return rc;
     h->maxS = L.maxS; h->maxN = L.maxN; h->pairs = L.pairs;
-    const double max_pairs = L.max_pairs;
-    h->geom.world = world;
-    h->geom.ring = std::max(1, n_views);
     for (int k = 0; k < n_views; ++k)
-        for (int q = 0; q < views[k].n_sources; ++q) h->window = std::max(h->window, k - views[k].source_index[q]);
-    h->geom.seg_cap = (h->maxS + world - 1) / world + 1;
-    h->geom.slot_records = slot_records;
-    h->geom.best_off = sizeof(SlotHeader);
-    h->geom.bpos_off = h->geom.best_off + (size_t)h->geom.seg_cap * 8;
-    h->geom.rec_off = salign(h->geom.bpos_off + (size_t)h->geom.seg_cap * 4, 32);
-    // dense scenes (slots of 65 536 records and more): a side array of the records' target cameras travels with the slot -- the two scans every later
-    // neighbour makes of it (k_exist_count_slots, k_place_slots) read 4 bytes per record instead of 32; + 12.5 % on the all-gather.  Measured on one
-    // emulated rank of eight at 64 x 4000 x 24 (profiles/r5_emulated_rank_64x4000x24_w8_partition.txt)
-    h->geom.cam_off = slot_records >= c->opt.slot_cams_min ? salign(h->geom.rec_off + (size_t)slot_records * sizeof(Match), 32) : 0;
-    // ... and (round 6) the slot's RUN TABLE, (N + 1) x seg_cap ints (l3d_runtable.hpp; positions in the slot's records): a later neighbour reads the runs of its
-    // camera -- 1/N of the slot -- instead of scanning the side array (188 MB per view and rank at 64 x 4000 x 24 on eight ranks)
-    h->geom.max_n = h->maxN;
-    h->geom.rt_off = h->geom.cam_off ? salign(h->geom.cam_off + (size_t)slot_records * 4, 32) : 0;
-    h->geom.slot_bytes = salign(h->geom.rt_off ? h->geom.rt_off + ((size_t)h->maxN + 1) * h->geom.seg_cap * 4
-                                : (h->geom.cam_off ? h->geom.cam_off + (size_t)slot_records * 4 : h->geom.rec_off + (size_t)slot_records * sizeof(Match)), 256);
+        for (int q = 0; q < views[k].n_sources; ++q) h->ring.window = std::max(h->ring.window, k - views[k].source_index[q]);
+    // the slot (l3d_shard_rule.hpp).  The side array of dense scenes was measured on one emulated rank of eight at 64 x 4000 x 24
+    // (profiles/r5_emulated_rank_64x4000x24_w8_partition.txt); the run table saves 188 MB of scans per view and rank there
+    const SlotPlan plan = slot_geometry(h->maxS, h->maxN, world, slot_records, c->opt.slot_cams_min, n_views);
+    h->geom = plan.geom;
+    h->stage_bytes = plan.stage_bytes;
     *slot_bytes = h->geom.slot_bytes;
 
-    auto bail = [&](int rc) { delete h; return rc; };
-#define OCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { fail(c, L3D_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); return bail(L3D_ERR_HIP); } } while (0)
     // tables, target rays, per-view slices of the whole-run arenas (l3d_chain_common.hip: shared with the single-GPU chain)
-    { int rc = chain_upload_tables(c, views, n_views, h->vd, L, st); if (rc) return bail(rc); }
-    { int rc = chain_assign_arenas(c, views, n_views, h->vd, L, false, true, l3d_shard_chain::kRingA, st); if (rc) return bail(rc); }   // (+ best positions: l3d_shard_chain_products)
+    if (int rc = chain_upload_tables(c, views, n_views, h->vd, L, st)) return rc;
+    if (int rc = chain_assign_arenas(c, views, n_views, h->vd, L, false, true, l3d_shard_chain::kRingA, st)) return rc;   // (+ best positions: l3d_shard_chain_products)
     h->dtab = L.dtab;
     // (the run's statistics words; a partitioned run's products leave the per-view result records in the same buffer afterwards: sized for both)
-    OCHK(c->ch_pin_res.reserve((size_t)n_views * std::max<size_t>(8, sizeof(ChainResult)) + 64));
+    HIPCHK(c, c->ch_pin_res.reserve((size_t)n_views * std::max<size_t>(8, sizeof(ChainResult)) + 64));
     h->hstats = c->ch_pin_res.as<int>();
-    OCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->hstats_dev), h->hstats, 0));
+    HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&h->hstats_dev), h->hstats, 0));
     {   // stage 1 (own stream) starts after the tables and the zeroed row counts are in place
         hipEvent_t ready = get_event(c);
-        OCHK(hipEventRecord(ready, st));
-        OCHK(hipStreamWaitEvent(c->stage1_stream, ready, 0));
+        HIPCHK(c, hipEventRecord(ready, st));
+        HIPCHK(c, hipStreamWaitEvent(c->stage1_stream, ready, 0));
         put_event(c, ready);
     }
-    h->cand_cap = c->test_cand_cap ? c->test_cand_cap : chain_first_cand_cap(max_pairs);     // (l3d_set_chain_capacities: tests, retries with more room)
-    { int rc = chain_reserve_candidates(c, L, h->cand_cap, l3d_shard_chain::kRingA); if (rc) return bail(rc); }
-    h->stage_bytes = salign((size_t)world * ((size_t)h->geom.seg_cap * 8 + (size_t)slot_records * sizeof(Match)), 256);
-    OCHK(c->ch_pin_kept.reserve(2 * ((size_t)world * (size_t)h->geom.seg_cap * 8 + 64) + 64));
+    h->cand_cap = c->test_cand_cap ? c->test_cand_cap : chain_first_cand_cap(L.max_pairs);     // (l3d_set_chain_capacities: tests, retries with more room)
+    if (int rc = chain_reserve_candidates(c, L, h->cand_cap, l3d_shard_chain::kRingA)) return rc;
+    HIPCHK(c, c->ch_pin_kept.reserve(2 * ((size_t)world * (size_t)h->geom.seg_cap * 8 + 64) + 64));
     c->pin_arena.reset();
-    OCHK(c->ch_pin_best.reserve((size_t)n_views * sizeof(PackHeader) + 64));
+    HIPCHK(c, c->ch_pin_best.reserve((size_t)n_views * sizeof(PackHeader) + 64));
     h->hdr_host = c->ch_pin_best.as<PackHeader>();
-    OCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->hdr_dev), h->hdr_host, 0));
+    HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&h->hdr_dev), h->hdr_host, 0));
     h->packed.assign((size_t)n_views, 0);
-#undef OCHK
     h->ev1.assign((size_t)n_views, nullptr);
     h->ev2.assign((size_t)n_views, nullptr);
     for (int k = 0; k < n_views; ++k) { h->ev2[(size_t)k] = get_event(c); h->ev1[(size_t)k] = get_event(c); }
     h->ev3 = get_event(c);
     c->stats[0] = h->pairs;
-    *out = h;
+    *out = h.release();
     return L3D_OK;
 }
 
@@ -527,6 +512,22 @@ static int shard_stage1(l3d_shard_chain* h, int k)
     return L3D_OK;
 }
 
+// workgroups per (source view, rank) list of the two scans of the sources' slots: 16 for the lists of a sparse scene (a few thousand records: 5 steps
+// per thread), one per 4096 records of the slot's capacity on a dense one -- 650 k records per slot at 4000 segments x 24 neighbours were 160
+// dependent loads per thread (measured on one emulated rank of eight, 64 x 4000 x 24: exist + cand_move 47 -> see profiles/r5_emulated_rank_*).
+// A scan wants them by the slot's records; with run tables a list is seg_cap runs of sixteen lanes
+static int slot_scan_workgroups(const SlotGeom& g, int slot_scan_grain)
+{
+    return g.rt_off ? std::max(1, std::min(256, (g.seg_cap * 16 + 255) / 256)) : std::max(16, std::min(256, g.slot_records / (slot_scan_grain > 0 ? slot_scan_grain : 4096)));
+}
+// whether a view with sources orders its runs of reverse matches in a launch of its own (option exist_sort_apart: 0 never, > 0 always).  The window
+// kernel orders the runs itself -- except on a rank's small launch of a dense scene: a segment's workgroup ranks its 12 runs three per wave, one after
+// the other, and the launch waits for the heaviest segment; a launch of one wave per run is balanced.  Same rule as the split verification
+static bool sorts_runs_apart(const Options& o, int range_segments, size_t cand_cap)
+{
+    return o.exist_sort_apart != 0 && (o.exist_sort_apart > 0 || (range_segments <= o.vw_wide_max && cand_cap / (size_t)std::max(1, range_segments) >= (size_t)o.vw_split_avg));
+}
+
 // Enqueue view k up to (and including) the write of this rank's slot.  send_slot: device buffer of slot_bytes that the
 // caller all-gathers into gathered_base + (k*world + r)*slot_bytes for r = 0..world-1 (stream ordered, same stream).
 int l3d_shard_chain_enqueue(l3d_shard_chain* h, int k, void* send_slot, const void* gathered_base)
@@ -557,12 +558,7 @@ int l3d_shard_chain_enqueue(l3d_shard_chain* h, int k, void* send_slot, const vo
     const int* d_sc = reinterpret_cast<const int*>(dtab + d.o_sc);
     const int* d_si = reinterpret_cast<const int*>(dtab + d.o_si);
     unsigned char* slot = reinterpret_cast<unsigned char*>(send_slot);
-    // workgroups per (source view, rank) list of the two scans of the sources' slots: 16 for the lists of a sparse scene (a few thousand records: 5 steps
-    // per thread), one per 4096 records of the slot's capacity on a dense one -- 650 k records per slot at 4000 segments x 24 neighbours were 160
-    // dependent loads per thread (measured on one emulated rank of eight, 64 x 4000 x 24: exist + cand_move 47 -> see profiles/r5_emulated_rank_*)
-    // workgroups per (source, rank) list: a scan wants them by the slot's records; with run tables a list is seg_cap runs of sixteen lanes
-    const int wps = h->geom.rt_off ? std::max(1, std::min(256, (h->geom.seg_cap * 16 + 255) / 256))
-                                   : std::max(16, std::min(256, h->geom.slot_records / (h->c->opt.slot_scan_grain > 0 ? h->c->opt.slot_scan_grain : 4096)));
+    const int wps = slot_scan_workgroups(h->geom, c->opt.slot_scan_grain);
     if (v.n_sources) {
         ProfScope p(c, "exist");
         hipLaunchKernelGGL(k_exist_count_slots, dim3(wps, v.n_sources * h->world), dim3(256), 0, st, h->gathered, h->geom, d_si, d_sc, reinterpret_cast<const int*>(h->dtab + d.o_ss), v.view_id, N, d.s0, d.s1, d.rowcnt);
@@ -580,10 +576,7 @@ int l3d_shard_chain_enqueue(l3d_shard_chain* h, int k, void* send_slot, const vo
                                h->gathered, h->geom, d_si, d_sc, reinterpret_cast<const int*>(h->dtab + d.o_ss), v.view_id, N, S, d.s0, d.s1, c->row_start.as<int>(), c->ch_cursor.as<int>(),
                                c->cand_meta.as<uint2>(), c->cand_depths.as<float4>(), (int)h->cand_cap);
     }
-    // (the window kernel orders the runs itself -- except on a rank's small launch of a dense scene: a segment's workgroup ranks its 12 runs three per
-    // wave, one after the other, and the launch waits for the heaviest segment; a launch of one wave per run is balanced.  Same rule as the split verification)
-    const bool sort_apart = v.n_sources && c->opt.exist_sort_apart != 0 && (c->opt.exist_sort_apart > 0 ||
-                            ((d.s1 - d.s0) <= c->opt.vw_wide_max && h->cand_cap / (size_t)std::max(1, d.s1 - d.s0) >= (size_t)c->opt.vw_split_avg));
+    const bool sort_apart = v.n_sources && sorts_runs_apart(c->opt, d.s1 - d.s0, h->cand_cap);
     if (v.n_sources && (!(c->verify_mode == 0 && verify_window_supported(N)) || sort_apart)) {
         ProfScope p(c, "exist");
         launch_exist_sort_runs(d_sc, v.n_sources, N, S, c->row_start.as<int>(), c->cand_meta.as<uint2>(), c->cand_depths.as<float4>(), (int)h->cand_cap, st, d.s0, d.s1,
@@ -693,31 +686,159 @@ int l3d_shard_chain_fetch(l3d_shard_chain* h, int k, l3d_chain_callback cb, void
     return L3D_OK;
 }
 
+}  // extern "C"
+
 // ---- the whole sharded chain as ONE native call -------------------------------------------------------------------
 // The calling thread only enqueues: this rank's kernels of view k, then the exchange of the ranks' slots on the same
 // stream (RCCL all-gather over xGMI through l3d_exchange_rccl), then the "view complete" event.  A second host thread
 // trails behind on those events and does the host bookkeeping (fetch -> callback) of the ranks that commit.  No
 // interpreter, no host synchronisation on the enqueue path: per view the stream sees ~9 kernels + one collective.
-int l3d_shard_chain_run(l3d_shard_chain* h, l3d_exchange_fn exchange, void* exchange_user, l3d_chain_callback cb, void* cb_user)
-{
-    if (!h || !exchange) return L3D_ERR_INVALID;
-    l3d_ctx* c = h->c;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t slot = h->geom.slot_bytes, block = slot * (size_t)h->world;
-    // Ring mode: when the gathered blocks of all views exceed the budget (or L3D_SLOT_RING=1) and nobody commits on the host, the buffer
-    // holds window + batch + 2 view blocks; a batch of older views is retired into the compact kept arena (k_shard_retire) before its
-    // blocks are reused.  L3D_SLOT_RING=0 keeps every block (what the recording tests read back through l3d_shard_chain_gathered).
-    constexpr int kRetireBatch = 16;
-    const int ring_views = std::min(h->window + kRetireBatch + 2, std::max(1, h->n_views));
-    const size_t gathered_budget = (size_t)8 << 30;
-    h->ring_mode = !cb && c->opt.slot_ring != 0 && ring_views < h->n_views && (c->opt.slot_ring > 0 || (size_t)h->n_views * block > gathered_budget);
-    if (h->partition) {      // a partitioned job retires by definition: what a rank does not keep is gone when its ring block is reused
-        if (cb) return fail(c, L3D_ERR_UNSUPPORTED, "l3d_shard_chain_run: a partitioned run hands nothing to the host (cb must be NULL)");
-        h->ring_mode = true;  // (a schedule that reads further back than it has views -- scattered neighbourhoods -- gets a ring that never wraps: all retired at the end)
+namespace {
+
+// THE HELPER THREADS.  Each of the two classes owns its thread and its flags, and its destructor stops and joins.  A std::thread destroyed while
+// joinable terminates the process -- and would leave the peers waiting in their collectives: with the threads owned here, no return between their
+// start and the end of the run can skip the join, wherever a line is moved.
+
+// A second enqueue thread feeds the stage-1 stream (7 of the ~17 calls per view): with small per-rank slices the host launch rate, not the GPU, limits
+// the chain otherwise.  It stays kStage1Ahead views ahead of the chain thread (h->marked); the ring slot it writes was released by view k - kRingA,
+// whose completion event the chain thread has recorded by then.
+class Stage1Feeder {
+public:
+    explicit Stage1Feeder(l3d_shard_chain* h_) : h(h_)
+    {
+        h->s1_thread = true;
+        h->s1_done.store(0);
+        th = std::thread([this]() { run(); });
     }
-    h->geom.ring = h->ring_mode ? ring_views : std::max(1, h->n_views);
-    const int send_ring = h->ring_mode ? ring_views : h->n_views;            // (a slot is read by its exchange only)
-    if (h->ring_mode) {      // (rings of whole slots: GBs whose size is exact)
+    ~Stage1Feeder() { finish(); }
+    int failed() const { return rc.load(); }
+    void finish() { if (!th.joinable()) return; stop.store(true); th.join(); h->s1_thread = false; }
+
+private:
+    void run()
+    {
+        (void)hipSetDevice(h->c->device);
+        for (int k = 0; k < h->n_views && !stop.load(); ++k) {
+            wait_until([&]() { return stop.load() || h->marked.load(std::memory_order_acquire) >= k - l3d_shard_chain::kStage1Ahead; }, 64);
+            if (stop.load()) break;
+            const int r = shard_stage1(h, k);
+            if (r) { rc.store(r); break; }
+            h->s1_done.store(k + 1, std::memory_order_release);
+        }
+        h->s1_done.store(h->n_views + 1, std::memory_order_release);      // (never leave the chain thread waiting)
+    }
+    l3d_shard_chain* const h;
+    std::atomic<int> rc{L3D_OK};
+    std::atomic<bool> stop{false};
+    std::thread th;
+};
+
+// The bookkeeping thread of a committing rank: it trails the "view complete" events (h->marked, the one count of marked views -- the condition
+// variable only carries the wake-up) and hands every view to the callback (l3d_shard_chain_fetch).  A run without a callback starts no thread.
+class Fetcher {
+public:
+    Fetcher(l3d_shard_chain* h_, l3d_chain_callback cb_, void* user_) : h(h_), cb(cb_), user(user_) { if (cb) th = std::thread([this]() { run(); }); }
+    ~Fetcher() { finish(); }
+    void wake() { if (!cb) return; { std::lock_guard<std::mutex> lk(mu); } cv.notify_one(); }       // h->marked has advanced (under the lock: no wake-up is lost)
+    bool failed() { std::lock_guard<std::mutex> lk(mu); return rc != L3D_OK; }
+    // stopped (views that are not marked are left out) and joined: the first fetch's error (text: its message), or L3D_OK
+    int finish(std::string* text = nullptr)
+    {
+        if (th.joinable()) {
+            { std::lock_guard<std::mutex> lk(mu); stop = true; }
+            cv.notify_one();
+            th.join();
+        }
+        if (text) *text = err;
+        return rc;
+    }
+
+private:
+    void run()
+    {
+        (void)hipSetDevice(h->c->device);
+        for (int k = 0; k < h->n_views; ++k) {
+            {
+                std::unique_lock<std::mutex> lk(mu);
+                cv.wait(lk, [&]() { return h->marked.load(std::memory_order_acquire) > k || stop; });
+                if (h->marked.load(std::memory_order_acquire) <= k) return;
+            }
+            const int r = l3d_shard_chain_fetch(h, k, cb, user);
+            if (r) {
+                std::string m;
+                { std::lock_guard<std::mutex> lk(h->c->err_mu); m = h->c->err; }
+                std::lock_guard<std::mutex> lk(mu);
+                rc = r; err = m;
+                return;
+            }
+        }
+    }
+    l3d_shard_chain* const h;
+    const l3d_chain_callback cb;
+    void* const user;
+    std::mutex mu;
+    std::condition_variable cv;
+    bool stop = false;
+    int rc = L3D_OK;
+    std::string err;
+    std::thread th;
+};
+
+// One call of l3d_shard_chain_run as its phases.
+//   THE FAILURE PROTOCOL.  A rank that fails -- its own enqueue, its stage-1 thread, or (committing rank) the bookkeeping thread reading a slot that
+// overflowed -- must NOT stop calling the exchange: the other ranks keep enqueueing one collective per verified view and would wait for it forever.
+// From the failure on (drain) it sends a header that says "gave up" for every remaining view (no kernels) and keeps exchanging; k_check_slots then
+// gives every rank the same verdict.  Only a failing exchange call itself ends the loop (exchange_broken).
+struct ShardRun {
+    l3d_shard_chain* const h; l3d_ctx* const c;
+    const l3d_exchange_fn exchange; void* const exchange_user; const l3d_chain_callback cb;
+    const size_t slot, block;                   // bytes of a slot, of a view's gathered block
+    std::vector<unsigned char> verified;        // per view (uploaded for the retire kernel and for k_check_slots)
+    std::vector<long long> best_off_h;          // per view: where its best depth pairs start in ch_best
+    int send_ring = 0;                          // slots this rank sends from
+    unsigned char *send = nullptr, *gathered = nullptr;
+    RingTables T = RingTables();                // ring mode: the header block's layout, the block itself
+    unsigned char* hb = nullptr;
+    RetireSchedule sched;                       // ring mode: what is retired and waited for
+    hipStream_t rs = nullptr;                   // ... the stream the retirement runs on
+    hipEvent_t retire_done = nullptr;           // ... the outstanding batch's retirement on the side stream (sched.outstanding())
+    SlotHeader* abort_hdr = nullptr;            // the "gave up" header (pinned)
+    int rc = L3D_OK; std::string rc_msg;        // the run's first failure
+    bool draining = false, exchange_broken = false;
+    double t_run0 = 0;
+
+    ShardRun(l3d_shard_chain* h_, l3d_exchange_fn exchange_, void* exchange_user_, l3d_chain_callback cb_)
+        : h(h_), c(h_->c), exchange(exchange_), exchange_user(exchange_user_), cb(cb_), slot(h_->geom.slot_bytes), block(h_->geom.slot_bytes * (size_t)h_->world),
+          verified((size_t)h_->n_views), best_off_h((size_t)h_->n_views, 0)
+    {
+        for (int k = 0; k < h->n_views; ++k) verified[(size_t)k] = h->vd[(size_t)k].verified ? 1 : 0;
+    }
+
+    void drain(int code, const std::string& msg) { rc = code; rc_msg = msg; draining = true; }
+
+    int plan_ring();
+    void guess_arena();
+    int setup_ring_tables();
+    int setup_retire_tables();
+    int alloc_abort_header();
+    void retire_wait();
+    void retire_to(int upto);
+    void throttle(int k, Stage1Feeder& feeder, Fetcher& fetcher);
+    bool step(int k, Stage1Feeder& feeder, Fetcher& fetcher);
+    void finish_threads(Stage1Feeder& feeder, Fetcher& fetcher);
+    void shared_verdict();
+    hipError_t arena_verdict_exchange(hipError_t e, int& arena_overflow);
+    void settle_retirement();
+};
+
+// ---- the ring plan (shard_ring_plan) and the rings of slots and gathered blocks; where the retirement runs
+int ShardRun::plan_ring()
+{
+    const ShardRingPlan p = shard_ring_plan(h->n_views, h->ring.window, block, c->opt.slot_ring, h->part.on, cb != nullptr);
+    h->ring.on = p.ring_mode;
+    h->geom.ring = p.ring_views;
+    send_ring = p.send_ring;
+    if (h->ring.on) {      // (rings of whole slots: GBs whose size is exact)
         HIPCHK(c, c->ch_send.reserve_exact((size_t)send_ring * slot + 256));
         HIPCHK(c, c->ch_gathered.reserve_exact((size_t)h->geom.ring * block + 256));
     } else {
@@ -725,305 +846,298 @@ int l3d_shard_chain_run(l3d_shard_chain* h, l3d_exchange_fn exchange, void* exch
         HIPCHK(c, c->ch_gathered.reserve((size_t)h->geom.ring * block + 256));
     }
     h->eager_pack = cb != nullptr;
-    unsigned char* send = c->ch_send.as<unsigned char>();
-    unsigned char* gathered = c->ch_gathered.as<unsigned char>();
+    send = c->ch_send.as<unsigned char>();
+    gathered = c->ch_gathered.as<unsigned char>();
     // every verified view's block is fully written by its exchange before anything reads it; only the blocks of views
     // that are never verified (nothing to match) must read as "no kept records"
-    if (!h->ring_mode)
+    if (!h->ring.on)
         for (int k = 0; k < h->n_views; ++k)
-            if (!h->vd[(size_t)k].verified) HIPCHK(c, hipMemsetAsync(gathered + (size_t)k * block, 0, block, c->stream));
-    std::vector<unsigned char> ver_h((size_t)h->n_views);
-    std::vector<long long> best_off_h((size_t)h->n_views, 0);
-    int* ring_overflow = nullptr;
-    unsigned char* part_status = nullptr;      // partitioned: [own word | the ranks' words], 256 B each
-    size_t o_rto_ = 0, o_sn_ = 0;              // (ring mode: the run tables' offsets / the views' (S, N) in the header block)
-    h->retire_tables = false;
-    if (h->ring_mode) {
-        // compact arena (first guess like the single-GPU chain's, or what an earlier pass / a capacity verdict taught), the per-view offsets,
-        // the header table, the flags the retire kernel reads
-        h->arena_cap = c->test_arena_cap ? (long long)c->test_arena_cap : std::max((long long)(h->pairs * h->world * 0.004) + 1048576, (long long)c->chain_seen_arena_cap);
-        if (!h->partition && !c->test_arena_cap && c->opt.arena_guess > 4) {
-            // (as the single-GPU chain: a generous first guess within 35 % of the free HBM -- here a guess that is too small costs a capacity verdict and the whole chain again)
-            size_t fr = 0, tot = 0;
-            if (hipMemGetInfo(&fr, &tot) == hipSuccess) {
-                const long long want = (long long)(h->pairs * h->world * 0.001 * c->opt.arena_guess) + 1048576, fits = (long long)((double)fr * 0.35 / 40.0);
-                h->arena_cap = std::max(h->arena_cap, std::min(want, fits));
-            }
-            (void)hipGetLastError();
-        }
-        // (tests, option regrow_free_mb: a card with less room -- the compact arena and its side words may take that much and no more: a first guess above it
-        // is cut to it, a run that needs more ends with the capacity verdict and l3d_line3d_shard_run's NOMEM)
-        const long long room_records = c->opt.regrow_free_mb > 0 ? (long long)(((size_t)c->opt.regrow_free_mb << 20) / (sizeof(Match) + 4)) : 0;
-        if (room_records > 0 && !h->partition) h->arena_cap = std::min(h->arena_cap, room_records);
-        if (!h->partition) HIPCHK(c, c->ch_kept.reserve(((size_t)h->arena_cap + 64) * sizeof(Match)));
-        auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-        const size_t nvs = (size_t)h->n_views;
-        const size_t o_base = 0, o_hdr = al((nvs + 2) * 8), o_bo = o_hdr + al(nvs * h->world * sizeof(SlotHeader)), o_ver = o_bo + al(nvs * 8), o_ovf = o_ver + al(nvs), o_keep = o_ovf + 256, o_stat = o_keep + al(nvs),
-                     o_rto = o_stat + 256 * ((size_t)h->world + 1), o_sn = o_rto + al(nvs * 8), tot = o_sn + al(nvs * 8);
-        HIPCHK(c, c->ch_hdr.reserve(tot));
-        unsigned char* hb = c->ch_hdr.as<unsigned char>();
-        h->base_dev = reinterpret_cast<long long*>(hb + o_base);
-        h->hdr_all = reinterpret_cast<SlotHeader*>(hb + o_hdr);
-        for (int k = 0; k < h->n_views; ++k) {
-            ver_h[(size_t)k] = h->vd[(size_t)k].verified ? 1 : 0;
-            best_off_h[(size_t)k] = h->vd[(size_t)k].verified ? (long long)(h->vd[(size_t)k].best - c->ch_best.as<float2>()) : 0;
-        }
-        HIPCHK(c, hipMemsetAsync(hb, 0, o_bo, c->stream));
-        HIPCHK(c, hipMemsetAsync(hb + o_ovf, 0, 256, c->stream));
-        HIPCHK(c, hipMemcpyAsync(hb + o_bo, best_off_h.data(), nvs * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(hb + o_ver, ver_h.data(), nvs, hipMemcpyHostToDevice, c->stream));
-        h->best_off_dev = reinterpret_cast<const long long*>(hb + o_bo);
-        h->ver_dev = hb + o_ver;
-        h->keep_dev = nullptr;
-        if (h->partition) {
-            HIPCHK(c, hipMemcpyAsync(hb + o_keep, h->keep.data(), nvs, hipMemcpyHostToDevice, c->stream));
-            h->keep_dev = hb + o_keep;
-            // (the first guess of the arena: this rank's share of the scene's)
-            if (!c->test_arena_cap) { long long kv = 0; for (unsigned char x : h->keep) kv += x; h->arena_cap = std::max<long long>((long long)c->part_arena_seen, h->arena_cap * kv / std::max(1, h->n_views) + 1048576); }
-            if (room_records > 0) h->arena_cap = std::min(h->arena_cap, room_records);
-            HIPCHK(c, c->ch_kept.reserve_exact(((size_t)h->arena_cap + 64) * sizeof(Match)));
-        }
-        // the retired views' side words and run tables (slots that carry a side array carry both)
-        h->retire_tables = h->geom.rt_off != 0 && h->geom.cam_off != 0 && c->opt.prod_transpose != 0 && c->opt.retire_tables != 0;
-        if (h->retire_tables) {
-            h->rt_off.assign(nvs, 0);
-            std::vector<int2> sn(nvs);
-            long long rt_ints = 0;
-            for (int k = 0; k < h->n_views; ++k) {
-                sn[(size_t)k] = make_int2(h->views[k].S_src, h->views[k].N);
-                h->rt_off[(size_t)k] = rt_ints;
-                if (h->vd[(size_t)k].verified && (!h->partition || h->keep[(size_t)k])) rt_ints += ((long long)h->views[k].N + 1) * h->views[k].S_src;
-            }
-            HIPCHK(c, c->ch_rt.reserve((size_t)rt_ints * 4 + 256));
-            HIPCHK(c, c->ch_keptcam.reserve(((size_t)h->arena_cap + 64) * 4));
-            HIPCHK(c, hipMemcpyAsync(hb + o_rto, h->rt_off.data(), nvs * 8, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(hb + o_sn, sn.data(), nvs * 8, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));         // (`sn` leaves scope)
-        }
-        o_rto_ = o_rto; o_sn_ = o_sn;
-        ring_overflow = reinterpret_cast<int*>(hb + o_ovf);
-        part_status = hb + o_stat;
-        h->part_status = part_status; h->part_exchange = exchange; h->part_user = exchange_user;
-    }
-    int retired = 0;                        // views [0, retired) are in the compact arena (ring mode)
+            if (!verified[(size_t)k]) HIPCHK(c, hipMemsetAsync(gathered + (size_t)k * block, 0, block, c->stream));
+    h->ring.retire_tables = false;
     // The retirement copies a batch's records out of the ring (9.6 GB of traffic per pass of an emulated rank of eight at 64 x 4000 x 24: 4.7 of its 63 ms) and
-    // nothing of the chain reads what it writes: it runs on a side stream behind the batch's exchanges (round 6; L3D_RETIRE_APART=0: on the chain's stream).
-    // The chain waits for it only before the first exchange that overwrites a block of the batch (view a + ring for a batch that starts at view a)
-    hipStream_t rs = c->stream;
-    if (h->ring_mode && c->opt.retire_apart != 0) {
+    // nothing of the chain reads what it writes: it runs on a side stream behind the batch's exchanges (round 6; L3D_RETIRE_APART=0: on the chain's stream)
+    sched = RetireSchedule();
+    sched.window = h->ring.window; sched.ring = h->geom.ring; sched.apart = h->ring.on && c->opt.retire_apart != 0;
+    rs = c->stream;
+    if (sched.apart) {
         if (!c->prod_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->prod_stream, hipStreamNonBlocking));
         rs = c->prod_stream;
     }
-    hipEvent_t retire_done = nullptr;       // the last batch's retirement on the side stream, not yet waited for
-    int retire_need = 0;                    // ... the first view whose exchange needs it done
-    auto retire_wait = [&]() {
-        if (!retire_done) return;
-        (void)hipStreamWaitEvent(c->stream, retire_done, 0);
-        put_local_event(c, retire_done);
-        retire_done = nullptr;
-    };
-    auto retire_to = [&](int upto) {        // enqueue the retirement of views [retired, upto) behind their exchanges
-        while (retired < upto) {
-            const int nb = std::min(kRetireBatch, upto - retired);
-            if (rs != c->stream) {
-                retire_wait();
-                hipEvent_t e = get_local_event(c);
-                (void)hipEventRecord(e, c->stream);
-                (void)hipStreamWaitEvent(rs, e, 0);
-                put_local_event(c, e);
-            }
-            ProfScope p(c, "retire", rs);
-            hipLaunchKernelGGL(k_shard_retire, dim3(8, h->world, nb), dim3(256), 0, rs, gathered, h->geom, h->ver_dev, h->keep_dev, retired, nb, h->base_dev, h->arena_cap,
-                               h->best_off_dev, c->ch_kept.as<Match>(), c->ch_best.as<float2>(), c->ch_bestpos.as<int>(), h->hdr_all, ring_overflow,
-                               h->retire_tables ? c->ch_keptcam.as<unsigned>() : nullptr, h->retire_tables ? c->ch_rt.as<int>() : nullptr,
-                               reinterpret_cast<const long long*>(c->ch_hdr.as<unsigned char>() + o_rto_), reinterpret_cast<const int2*>(c->ch_hdr.as<unsigned char>() + o_sn_));
-            if (rs != c->stream) {
-                retire_done = get_local_event(c);
-                (void)hipEventRecord(retire_done, rs);
-                retire_need = retired + h->geom.ring;
-            }
-            retired += nb;
-        }
-    };
+    return L3D_OK;
+}
 
-    // the "gave up" header of the failure protocol below -- allocated BEFORE any helper thread exists: an early return with
-    // joinable threads would terminate the process and leave the peers waiting in their collectives
-    SlotHeader* abort_hdr = nullptr;
-    {
-        hipError_t ae = hipSuccess;
-        abort_hdr = static_cast<SlotHeader*>(c->pin_arena.alloc(sizeof(SlotHeader), &ae));
-        HIPCHK(c, ae);
-        memset(abort_hdr, 0, sizeof(SlotHeader));
-        abort_hdr->overflow = 4;
+// the compact arena's first guess (shard_arena_first_guess; the free HBM is asked for only where the rule reads it)
+void ShardRun::guess_arena()
+{
+    size_t fr = kShardFreeUnknown, tot = 0;
+    if (shard_guess_reads_free(h->part.on, c->test_arena_cap, c->opt.arena_guess)) {
+        if (hipMemGetInfo(&fr, &tot) != hipSuccess) fr = kShardFreeUnknown;
+        (void)hipGetLastError();
     }
-    std::mutex mu;
-    std::condition_variable cv;
-    int marked = 0;                         // views [0, marked) carry their "complete" event
-    bool stop = false;
-    int fetch_rc = L3D_OK;
-    std::string fetch_err;
-    std::thread fetcher;
-    if (cb) {
-        fetcher = std::thread([&]() {
-            (void)hipSetDevice(c->device);
-            for (int k = 0; k < h->n_views; ++k) {
-                {
-                    std::unique_lock<std::mutex> lk(mu);
-                    cv.wait(lk, [&]() { return marked > k || stop; });
-                    if (marked <= k) return;
-                }
-                const int rc = l3d_shard_chain_fetch(h, k, cb, cb_user);
-                if (rc) { std::lock_guard<std::mutex> lk(mu); fetch_rc = rc; fetch_err = c->err; return; }
-            }
-        });
+    long long kept_views = 0;
+    for (unsigned char x : h->part.keep) kept_views += x;
+    h->ring.arena_cap = shard_arena_first_guess(h->pairs, h->world, c->test_arena_cap, c->chain_seen_arena_cap, c->opt.arena_guess, fr, shard_room_records(c->opt.regrow_free_mb),
+                                                h->part.on, kept_views, h->n_views, c->part_arena_seen);
+}
+
+// ---- ring mode: the compact arena, the header block (RingTables) with the per-view offsets, the header table and the flags the retire kernel reads
+int ShardRun::setup_ring_tables()
+{
+    if (!h->ring.on) return L3D_OK;
+    l3d_shard_chain::Ring& R = h->ring;
+    const size_t nvs = (size_t)h->n_views;
+    guess_arena();
+    if (!h->part.on) HIPCHK(c, c->ch_kept.reserve(((size_t)R.arena_cap + 64) * sizeof(Match)));
+    T = ring_tables(nvs, h->world);
+    HIPCHK(c, c->ch_hdr.reserve(T.total));
+    hb = c->ch_hdr.as<unsigned char>();
+    R.base_dev = reinterpret_cast<long long*>(hb + T.base);
+    R.hdr_all = reinterpret_cast<SlotHeader*>(hb + T.hdr);
+    for (int k = 0; k < h->n_views; ++k) best_off_h[(size_t)k] = verified[(size_t)k] ? (long long)(h->vd[(size_t)k].best - c->ch_best.as<float2>()) : 0;
+    HIPCHK(c, hipMemsetAsync(hb, 0, T.best_off, c->stream));
+    HIPCHK(c, hipMemsetAsync(hb + T.overflow, 0, 256, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hb + T.best_off, best_off_h.data(), nvs * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hb + T.verified, verified.data(), nvs, hipMemcpyHostToDevice, c->stream));
+    R.best_off_dev = reinterpret_cast<const long long*>(hb + T.best_off);
+    R.ver_dev = hb + T.verified;
+    h->part.keep_dev = nullptr;
+    if (h->part.on) {
+        HIPCHK(c, hipMemcpyAsync(hb + T.keep, h->part.keep.data(), nvs, hipMemcpyHostToDevice, c->stream));
+        h->part.keep_dev = hb + T.keep;
+        HIPCHK(c, c->ch_kept.reserve_exact(((size_t)R.arena_cap + 64) * sizeof(Match)));
     }
-    // a second enqueue thread feeds the stage-1 stream (7 of the ~17 calls per view): with small per-rank slices the host
-    // launch rate, not the GPU, limits the chain otherwise.  It stays kStage1Ahead views ahead of the chain thread; the ring
-    // slot it writes was released by view k - kRingA, whose completion event the chain thread has recorded by then.
-    std::atomic<int> s1_rc{L3D_OK};
-    std::atomic<bool> s1_stop{false};
-    std::thread stage1;
-    h->s1_thread = true;
-    h->s1_done.store(0);
-    stage1 = std::thread([&]() {
-        (void)hipSetDevice(c->device);
-        for (int k = 0; k < h->n_views && !s1_stop.load(); ++k) {
-            wait_until([&]() { return s1_stop.load() || h->marked.load(std::memory_order_acquire) >= k - l3d_shard_chain::kStage1Ahead; }, 64);
-            if (s1_stop.load()) break;
-            const int r = shard_stage1(h, k);
-            if (r) { s1_rc.store(r); break; }
-            h->s1_done.store(k + 1, std::memory_order_release);
-        }
-        h->s1_done.store(h->n_views + 1, std::memory_order_release);      // (never leave the chain thread waiting)
-    });
-    int rc = L3D_OK;
-    std::string rc_msg;
-    const double t_run0 = now_s();
-    // A rank that fails -- its own enqueue, its stage-1 thread, or (committing rank) the bookkeeping thread reading a slot that
-    // overflowed -- must NOT stop calling the exchange: the other ranks keep enqueueing one collective per verified view and would
-    // wait for it forever.  From the failure on it sends a header that says "gave up" for every remaining view (no kernels) and
-    // keeps exchanging; k_check_slots then gives every rank the same verdict.  Only a failing exchange call itself ends the loop.
-    bool draining = false, exchange_broken = false;
+    if (int r = setup_retire_tables()) return r;
+    h->part.status = hb + T.status; h->part.exchange = exchange; h->part.user = exchange_user;
+    return L3D_OK;
+}
+
+// the retired views' side words and run tables (slots that carry a side array carry both)
+int ShardRun::setup_retire_tables()
+{
+    l3d_shard_chain::Ring& R = h->ring;
+    const size_t nvs = (size_t)h->n_views;
+    R.retire_tables = h->geom.rt_off != 0 && h->geom.cam_off != 0 && c->opt.prod_transpose != 0 && c->opt.retire_tables != 0;
+    if (!R.retire_tables) return L3D_OK;
+    R.rt_off.assign(nvs, 0);
+    std::vector<int2> sn(nvs);
+    long long rt_ints = 0;
     for (int k = 0; k < h->n_views; ++k) {
-        if (!draining) {
-            // a committing rank stays less than a staging ring ahead of its bookkeeping thread (which trails the GPU closely)
-            if (s1_rc.load()) { rc = s1_rc.load(); rc_msg = "l3d_shard_chain_run: stage 1 failed: " + c->err; draining = true; }
-            while (!draining && cb && h->fetched.load(std::memory_order_acquire) < k - (l3d_shard_chain::kRing - 2)) {
-                { std::lock_guard<std::mutex> lk(mu); if (fetch_rc) { draining = true; break; } }
-                std::this_thread::yield();
-            }
-            { std::lock_guard<std::mutex> lk(mu); if (fetch_rc) draining = true; }
+        sn[(size_t)k] = make_int2(h->views[k].S_src, h->views[k].N);
+        R.rt_off[(size_t)k] = rt_ints;
+        if (verified[(size_t)k] && (!h->part.on || h->part.keep[(size_t)k])) rt_ints += ((long long)h->views[k].N + 1) * h->views[k].S_src;
+    }
+    HIPCHK(c, c->ch_rt.reserve((size_t)rt_ints * 4 + 256));
+    HIPCHK(c, c->ch_keptcam.reserve(((size_t)R.arena_cap + 64) * 4));
+    HIPCHK(c, hipMemcpyAsync(hb + T.rt_off, R.rt_off.data(), nvs * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hb + T.view_sn, sn.data(), nvs * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));         // (`sn` leaves scope)
+    return L3D_OK;
+}
+
+// the "gave up" header of the failure protocol
+int ShardRun::alloc_abort_header()
+{
+    hipError_t ae = hipSuccess;
+    abort_hdr = static_cast<SlotHeader*>(c->pin_arena.alloc(sizeof(SlotHeader), &ae));
+    HIPCHK(c, ae);
+    memset(abort_hdr, 0, sizeof(SlotHeader));
+    abort_hdr->overflow = kShardBitGaveUp;
+    return L3D_OK;
+}
+
+// ---- the retirement: RetireSchedule decides, these two perform.  The chain's stream waits for the outstanding batch ...
+void ShardRun::retire_wait()
+{
+    if (!retire_done) return;
+    (void)hipStreamWaitEvent(c->stream, retire_done, 0);
+    put_local_event(c, retire_done);
+    retire_done = nullptr;
+}
+// ... and the retirement of views [retired, upto) is enqueued behind their exchanges, a batch at a time
+void ShardRun::retire_to(int upto)
+{
+    const l3d_shard_chain::Ring& R = h->ring;
+    for (RetireBatch b = sched.next(upto); b.count; b = sched.next(upto)) {
+        if (sched.apart) {
+            if (b.wait_before) retire_wait();
+            hipEvent_t e = get_local_event(c);
+            (void)hipEventRecord(e, c->stream);
+            (void)hipStreamWaitEvent(rs, e, 0);
+            put_local_event(c, e);
         }
-        const bool verified = h->vd[(size_t)k].verified;
-        if (!draining) {
-            const double te0 = now_s();
-            // ring mode: block k % ring is about to be overwritten by this view's exchange -- whatever lived there (view k - ring) and every
-            // older view must be in the arena first (a batch at a time; no later view reads them: they are further back than the window)
-            // (views in front of k - window are read by nobody from view k on; with ring = window + batch + 2 the block this view's exchange
-            // overwrites, k - ring, is always among the retired)
-            if (h->ring_mode && (k - h->window) - retired >= kRetireBatch) retire_to(k - h->window);
-            if (retire_done && k >= retire_need) retire_wait();
-            const int r2 = l3d_shard_chain_enqueue(h, k, send + (size_t)(k % send_ring) * slot, gathered);
-            h->t_enq += now_s() - te0;
-            if (r2) { rc = r2; rc_msg = c->err; draining = true; }
-        }
-        if (h->ring_mode && !verified && !draining)          // (a view that is never verified must read as "no kept records", whatever lived in its ring block)
-            if (hipMemsetAsync(gathered + (size_t)(k % h->geom.ring) * block, 0, block, c->stream) != hipSuccess) { (void)hipGetLastError(); }
-        if (draining && verified) {
-            if (hipMemcpyAsync(send + (size_t)(k % send_ring) * slot, abort_hdr, sizeof(SlotHeader), hipMemcpyHostToDevice, c->stream) != hipSuccess) { (void)hipGetLastError(); }
-        }
-        if (verified) {
-            const double te1 = now_s();
-            if (const int exr = exchange(exchange_user, k, send + (size_t)(k % send_ring) * slot, gathered + (size_t)(k % h->geom.ring) * block, slot, h->world, (void*)c->stream)) {
-                if (rc == L3D_OK) { rc = L3D_ERR_HIP; rc_msg = "l3d_shard_chain_run: the exchange of view " + std::to_string(k) + " failed (code " + std::to_string(exr) + ", last HIP error: " + hipGetErrorString(hipGetLastError()) + ")"; }
-                exchange_broken = true;
-                break;
-            }
-            h->t_ex += now_s() - te1;
-        }
-        if (!draining) {
-            const int r3 = l3d_shard_chain_mark(h, k);
-            if (r3) { rc = r3; rc_msg = c->err; draining = true; }
-            else { { std::lock_guard<std::mutex> lk(mu); marked = k + 1; } cv.notify_one(); }
+        ProfScope p(c, "retire", rs);
+        hipLaunchKernelGGL(k_shard_retire, dim3(8, h->world, b.count), dim3(256), 0, rs, gathered, h->geom, R.ver_dev, h->part.keep_dev, b.first, b.count, R.base_dev, R.arena_cap,
+                           R.best_off_dev, c->ch_kept.as<Match>(), c->ch_best.as<float2>(), c->ch_bestpos.as<int>(), R.hdr_all, reinterpret_cast<int*>(hb + T.overflow),
+                           R.retire_tables ? c->ch_keptcam.as<unsigned>() : nullptr, R.retire_tables ? c->ch_rt.as<int>() : nullptr,
+                           reinterpret_cast<const long long*>(hb + T.rt_off), reinterpret_cast<const int2*>(hb + T.view_sn));
+        if (sched.apart) {
+            retire_done = get_local_event(c);
+            (void)hipEventRecord(retire_done, rs);
         }
     }
-    s1_stop.store(true);
-    stage1.join();
-    h->s1_thread = false;
-    if (rc == L3D_OK && s1_rc.load()) rc = fail(c, s1_rc.load(), "l3d_shard_chain_run: stage 1 failed");
-    { std::lock_guard<std::mutex> lk(mu); stop = true; }
-    cv.notify_one();
+}
+
+// ---- one view: throttle -> retire what is due -> enqueue (draining: the "gave up" header) -> exchange -> mark
+// a committing rank stays less than a staging ring ahead of its bookkeeping thread (which trails the GPU closely)
+void ShardRun::throttle(int k, Stage1Feeder& feeder, Fetcher& fetcher)
+{
+    if (feeder.failed()) drain(feeder.failed(), "l3d_shard_chain_run: stage 1 failed: " + c->err);
+    while (!draining && cb && h->fetched.load(std::memory_order_acquire) < k - (l3d_shard_chain::kRing - 2)) {
+        if (fetcher.failed()) { draining = true; break; }
+        std::this_thread::yield();
+    }
+    if (fetcher.failed()) draining = true;
+}
+
+// false: the exchange call itself failed -- the loop ends
+bool ShardRun::step(int k, Stage1Feeder& feeder, Fetcher& fetcher)
+{
+    if (!draining) throttle(k, feeder, fetcher);
+    const bool ver = verified[(size_t)k] != 0;
+    unsigned char* const send_slot = send + (size_t)(k % send_ring) * slot;
+    unsigned char* const recv_block = gathered + (size_t)(k % h->geom.ring) * block;
+    if (!draining) {
+        const double te0 = now_s();
+        // ring mode: block k % ring is about to be overwritten by this view's exchange -- whatever lived there (view k - ring) and every older view must
+        // be in the arena first (RetireSchedule, l3d_shard_rule.hpp: a batch at a time; no later view reads them: they are further back than the window)
+        if (h->ring.on) {
+            retire_to(sched.due(k));
+            if (sched.wait_due(k)) retire_wait();
+        }
+        const int r = l3d_shard_chain_enqueue(h, k, send_slot, gathered);
+        h->t_enq += now_s() - te0;
+        if (r) drain(r, c->err);
+    }
+    if (h->ring.on && !ver && !draining)          // (a view that is never verified must read as "no kept records", whatever lived in its ring block)
+        if (hipMemsetAsync(recv_block, 0, block, c->stream) != hipSuccess) { (void)hipGetLastError(); }
+    if (draining && ver)
+        if (hipMemcpyAsync(send_slot, abort_hdr, sizeof(SlotHeader), hipMemcpyHostToDevice, c->stream) != hipSuccess) { (void)hipGetLastError(); }
+    if (ver) {
+        const double te1 = now_s();
+        if (const int exr = exchange(exchange_user, k, send_slot, recv_block, slot, h->world, (void*)c->stream)) {
+            if (rc == L3D_OK) { rc = L3D_ERR_HIP; rc_msg = "l3d_shard_chain_run: the exchange of view " + std::to_string(k) + " failed (code " + std::to_string(exr) + ", last HIP error: " + hipGetErrorString(hipGetLastError()) + ")"; }
+            exchange_broken = true;
+            return false;
+        }
+        h->t_ex += now_s() - te1;
+    }
+    if (!draining) {
+        const int r = l3d_shard_chain_mark(h, k);
+        if (r) drain(r, c->err);
+        else fetcher.wake();
+    }
+    return true;
+}
+
+// ---- both threads joined, the stream drained
+void ShardRun::finish_threads(Stage1Feeder& feeder, Fetcher& fetcher)
+{
+    feeder.finish();
+    if (rc == L3D_OK && feeder.failed()) { rc = feeder.failed(); rc_msg = "l3d_shard_chain_run: stage 1 failed"; }
     const double t_run1 = now_s();
     (void)hipStreamSynchronize(c->stream);
     const double t_run2 = now_s();
     // (l3d_shard_chain_enqueue has added these totals already: the native run's "raw" statistic counts every candidate twice -- left as it is here, a fix of its own)
-    for (int k = 0; k < h->n_views; ++k) if (h->vd[(size_t)k].verified) h->raw_sum += h->hstats[2 * k];
-    if (fetcher.joinable()) fetcher.join();
+    for (int k = 0; k < h->n_views; ++k) if (verified[(size_t)k]) h->raw_sum += h->hstats[2 * k];
+    std::string fetch_err;
+    const int fetch_rc = fetcher.finish(&fetch_err);
     if (c->opt.timing)
         fprintf(stderr, "[l3d shard chain run] enqueue loop %.2f ms, stream drained after %.2f ms, bookkeeping thread done after %.2f ms\n",
                 (t_run1 - t_run0) * 1e3, (t_run2 - t_run0) * 1e3, (now_s() - t_run0) * 1e3);
     if (rc == L3D_OK && fetch_rc) { rc = fetch_rc; rc_msg = fetch_err; }
-    // the verdict every rank shares: the overflow bits of all gathered headers
-    if (!exchange_broken) {
-        std::vector<unsigned char> ver((size_t)h->n_views);
-        for (int k = 0; k < h->n_views; ++k) ver[(size_t)k] = h->vd[(size_t)k].verified ? 1 : 0;
-        hipError_t e = c->ch_flags.reserve((size_t)h->n_views + 64);
-        int host3[3] = { 0, 0, 0 };
-        int ring_ovf_h = 0;
-        long long arena_total_h = 0;
-        if (e == hipSuccess) e = hipMemsetAsync(c->ch_flags.p, 0, 16, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(c->ch_flags.as<unsigned char>() + 16, ver.data(), (size_t)h->n_views, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) {
-            if (h->ring_mode) {
-                if (!draining) retire_to(h->n_views);                  // the views still in the ring
-                retire_wait();
-                if (retired == h->n_views) {
-                    hipLaunchKernelGGL(k_check_slots, dim3(8), dim3(256), 0, c->stream, reinterpret_cast<const unsigned char*>(h->hdr_all), sizeof(SlotHeader), h->geom,
-                                       c->ch_flags.as<unsigned char>() + 16, h->n_views, c->ch_flags.as<int>());
-                    e = hipMemcpyAsync(&ring_ovf_h, ring_overflow, 4, hipMemcpyDeviceToHost, c->stream);
-                    if (e == hipSuccess) e = hipMemcpyAsync(&arena_total_h, h->base_dev + h->n_views, 8, hipMemcpyDeviceToHost, c->stream);
-                } else {
-                    host3[0] = 4;                                      // this rank gave up before every view was exchanged: so did the verdict
-                }
-            } else {
-                hipLaunchKernelGGL(k_check_slots, dim3(8), dim3(256), 0, c->stream, gathered, slot, h->geom, c->ch_flags.as<unsigned char>() + 16, h->n_views, c->ch_flags.as<int>());
-            }
-            if (e == hipSuccess && !(h->ring_mode && retired != h->n_views)) e = hipMemcpyAsync(host3, c->ch_flags.p, 12, hipMemcpyDeviceToHost, c->stream);
+}
+
+// ---- the verdict every rank shares: the overflow bits of all gathered headers (k_check_slots: same blocks, same answer on every rank)
+void ShardRun::shared_verdict()
+{
+    const int nv = h->n_views;
+    int host3[3] = { 0, 0, 0 }, arena_overflow = 0;
+    long long arena_total = 0;
+    bool checked = false;                           // k_check_slots ran over every view's headers
+    hipError_t e = c->ch_flags.reserve((size_t)nv + 64);
+    if (e == hipSuccess) e = hipMemsetAsync(c->ch_flags.p, 0, 16, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->ch_flags.as<unsigned char>() + 16, verified.data(), (size_t)nv, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && h->ring.on) {
+        if (!draining) retire_to(nv);               // the views still in the ring
+        sched.wait_all();
+        retire_wait();
+        checked = sched.retired == nv;
+        if (checked) {
+            hipLaunchKernelGGL(k_check_slots, dim3(8), dim3(256), 0, c->stream, reinterpret_cast<const unsigned char*>(h->ring.hdr_all), sizeof(SlotHeader), h->geom,
+                               c->ch_flags.as<unsigned char>() + 16, nv, c->ch_flags.as<int>());
+            e = hipMemcpyAsync(&arena_overflow, hb + T.overflow, 4, hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(&arena_total, h->ring.base_dev + nv, 8, hipMemcpyDeviceToHost, c->stream);
+        } else {
+            host3[0] = kShardBitGaveUp;             // this rank gave up before every view was exchanged: so did the verdict
         }
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (h->partition && part_status) {
-            // every rank's arena is its own: "too small" is no shared verdict by itself -- one more exchange makes it one (entered by every rank,
-            // whatever happened to it: tag -3, the status words of the block modes)
-            long long w[2] = { e == hipSuccess ? (long long)ring_ovf_h : 1, 0 };
-            hipError_t e2 = hipMemcpyAsync(part_status, w, 16, hipMemcpyHostToDevice, c->stream);
-            if (e2 == hipSuccess) e2 = hipStreamSynchronize(c->stream);
-            if (exchange(exchange_user, -3, part_status, part_status + 256, 256, h->world, (void*)c->stream)) { if (rc == L3D_OK) { rc = L3D_ERR_HIP; rc_msg = "l3d_shard_chain_run: the exchange of the arena verdicts failed"; } }
-            else {
-                for (int r = 0; r < h->world && e2 == hipSuccess; ++r) {
-                    long long x = 0;
-                    e2 = hipMemcpyAsync(&x, part_status + 256 * ((size_t)r + 1), 8, hipMemcpyDeviceToHost, c->stream);
-                    if (e2 == hipSuccess) e2 = hipStreamSynchronize(c->stream);
-                    if (e2 == hipSuccess && x) ring_ovf_h = 1;
-                }
-            }
-            if (e == hipSuccess) e = e2;
-        }
-        if (e != hipSuccess) { if (rc == L3D_OK) { rc = L3D_ERR_HIP; rc_msg = std::string("l3d_shard_chain_run: reading the slot headers: ") + hipGetErrorString(e); } }
-        else {
-            if (ring_ovf_h) host3[0] |= 8;                          // the compact arena's first guess was too small (same data, same verdict on every rank)
-            h->arena_needed = arena_total_h;
-            h->outcome[0] = host3[0]; h->outcome[1] = host3[1]; h->outcome[2] = host3[2];
-            if (host3[0] && (rc == L3D_OK || rc == L3D_ERR_NOMEM)) {
-                rc = L3D_ERR_NOMEM;
-                rc_msg = std::string("l3d_shard_chain_run:") + ((host3[0] & 1) ? " candidate capacity exceeded on a rank (" + std::to_string(host3[1]) + " candidates in one view's range; l3d_set_chain_capacities);" : "") +
-                         ((host3[0] & 2) ? " slot_records too small (" + std::to_string(host3[2]) + " kept matches in one view's range);" : "") +
-                         ((host3[0] & 8) ? " the compact kept arena of the slot ring is too small (" + std::to_string(arena_total_h) + " kept matches);" : "") +
-                         ((host3[0] & 4) ? " a rank gave up;" : "");
-            }
-        }
+    } else if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_check_slots, dim3(8), dim3(256), 0, c->stream, gathered, slot, h->geom, c->ch_flags.as<unsigned char>() + 16, nv, c->ch_flags.as<int>());
+        checked = true;
     }
-    if (retire_done) { (void)hipStreamSynchronize(rs); put_local_event(c, retire_done); retire_done = nullptr; }      // (a run that ended early: nothing of it stays in flight)
-    return rc ? fail(c, rc, rc_msg) : L3D_OK;
+    if (e == hipSuccess && checked) e = hipMemcpyAsync(host3, c->ch_flags.p, 12, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (h->part.on && h->part.status) e = arena_verdict_exchange(e, arena_overflow);
+    if (e != hipSuccess) {
+        if (rc == L3D_OK) { rc = L3D_ERR_HIP; rc_msg = std::string("l3d_shard_chain_run: reading the slot headers: ") + hipGetErrorString(e); }
+        return;
+    }
+    if (arena_overflow) host3[0] |= kShardBitArena;     // the compact arena's first guess was too small (same data, same verdict on every rank)
+    h->ring.arena_needed = arena_total;
+    h->outcome[0] = host3[0]; h->outcome[1] = host3[1]; h->outcome[2] = host3[2];
+    const ShardVerdict v = shard_verdict(host3[0], host3[1], host3[2], arena_total);
+    if (v.rc && (rc == L3D_OK || rc == L3D_ERR_NOMEM)) { rc = v.rc; rc_msg = v.text; }
+}
+
+// partitioned: every rank's arena is its own, "too small" is no shared verdict by itself -- one more exchange makes it one (entered by every rank,
+// whatever happened to it: the status words of the block modes).  e: what reading this rank's own headers gave; returns the first error of the two
+hipError_t ShardRun::arena_verdict_exchange(hipError_t e, int& arena_overflow)
+{
+    std::vector<long long> words;
+    const StatusWords s = exchange_status_words(exchange, exchange_user, h->world, e == hipSuccess ? (long long)arena_overflow : 1, h->part.status, h->part.status + 256, c->stream, words);
+    if (!s.exchanged) {
+        if (rc == L3D_OK) { rc = L3D_ERR_HIP; rc_msg = "l3d_shard_chain_run: the exchange of the arena verdicts failed"; }
+        return e == hipSuccess ? s.publish : e;
+    }
+    const hipError_t e2 = s.publish != hipSuccess ? s.publish : s.read;
+    if (e2 == hipSuccess)
+        for (long long x : words) if (x) arena_overflow = 1;
+    return e == hipSuccess ? e2 : e;
+}
+
+// (a run that ended early: nothing of the retirement stays in flight)
+void ShardRun::settle_retirement()
+{
+    if (!retire_done) return;
+    (void)hipStreamSynchronize(rs);
+    put_local_event(c, retire_done);
+    retire_done = nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+int l3d_shard_chain_run(l3d_shard_chain* h, l3d_exchange_fn exchange, void* exchange_user, l3d_chain_callback cb, void* cb_user)
+{
+    if (!h || !exchange) return L3D_ERR_INVALID;
+    l3d_ctx* c = h->c;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (h->part.on && cb) return fail(c, L3D_ERR_UNSUPPORTED, "l3d_shard_chain_run: a partitioned run hands nothing to the host (cb must be NULL)");
+    ShardRun R(h, exchange, exchange_user, cb);
+    if (int rc = R.plan_ring()) return rc;
+    if (int rc = R.setup_ring_tables()) return rc;
+    if (int rc = R.alloc_abort_header()) return rc;
+    {   // (the threads live in this scope: whatever leaves it joins them)
+        Fetcher fetcher(h, cb, cb_user);
+        Stage1Feeder feeder(h);
+        R.t_run0 = now_s();
+        for (int k = 0; k < h->n_views; ++k)
+            if (!R.step(k, feeder, fetcher)) break;
+        R.finish_threads(feeder, fetcher);
+    }
+    if (!R.exchange_broken) R.shared_verdict();
+    R.settle_retirement();
+    return R.rc ? fail(c, R.rc, R.rc_msg) : L3D_OK;
 }
 
 // exchange adapters.  RCCL: user = l3d_rccl_link {communicator, address of ncclAllGather}; the library does not link
@@ -1058,8 +1172,8 @@ int l3d_exchange_replay(void* user, int view, const void* send_slot, void* recv_
     if (e != hipSuccess) fprintf(stderr, "[l3d exchange_replay] view %d: hipMemcpyAsync(dst %p, src %p + %zu, %zu bytes): %s\n", view, recv_block, user, (size_t)view * block, block, hipGetErrorString(e));
     return (int)e;
 }
-const void* l3d_shard_chain_gathered(l3d_shard_chain* h) { return h && !h->ring_mode ? h->c->ch_gathered.p : nullptr; }     // (ring mode: most blocks are gone)
-long long l3d_shard_chain_arena_needed(l3d_shard_chain* h) { return h ? h->arena_needed : 0; }
+const void* l3d_shard_chain_gathered(l3d_shard_chain* h) { return h && !h->ring.on ? h->c->ch_gathered.p : nullptr; }     // (ring mode: most blocks are gone)
+long long l3d_shard_chain_arena_needed(l3d_shard_chain* h) { return h ? h->ring.arena_needed : 0; }
 int l3d_shard_chain_info(l3d_shard_chain* h, size_t* cand_cap, int* slot_records, int* overflow_bits, int* max_candidates, int* max_kept)
 {
     if (!h) return L3D_ERR_INVALID;
@@ -1083,7 +1197,7 @@ int l3d_shard_chain_products(l3d_shard_chain* h, const l3d_dense_map* map, l3d_c
     l3d_ctx* c = h->c;
     if (!map || !summary) return fail(c, L3D_ERR_INVALID, "l3d_shard_chain_products: bad argument");
     if (!h->gathered || h->outcome[0]) return fail(c, L3D_ERR_INVALID, "l3d_shard_chain_products: no finished run without overflow on this chain");     // (a verdict every rank shares)
-    if (!h->partition) return shard_products_local(h, map, summary, n_pot, nullptr);
+    if (!h->part.on) return shard_products_local(h, map, summary, n_pot, nullptr);
     // partitioned: whatever this rank fails in on its own travels with ONE status exchange (tag -3) that every rank enters -- the ranks go on to the
     // collective finish together or not at all
     ProductsPart part;
@@ -1092,17 +1206,14 @@ int l3d_shard_chain_products(l3d_shard_chain* h, const l3d_dense_map* map, l3d_c
     std::string err_local;
     if (rc) { std::lock_guard<std::mutex> lk(c->err_mu); err_local = c->err; }
     hipStream_t st = c->stream;
-    long long w[2] = { rc ? -(long long)std::abs(rc) : (long long)n_local, 0 };
-    hipError_t e = hipMemcpyAsync(h->part_status, w, 16, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) (void)hipMemsetAsync(h->part_status, 0xff, 16, st);
-    if (!h->part_exchange || h->part_exchange(h->part_user, -3, h->part_status, h->part_status + 256, 256, h->world, (void*)st)) return fail(c, L3D_ERR_HIP, "l3d_shard_chain_products: the exchange of the status words failed");
+    std::vector<long long> words;
+    const StatusWords s = exchange_status_words(h->part.exchange, h->part.user, h->world, rc ? -(long long)std::abs(rc) : (long long)n_local, h->part.status, h->part.status + 256, st, words);
+    if (!s.exchanged) return fail(c, L3D_ERR_HIP, "l3d_shard_chain_products: the exchange of the status words failed");
     if (rc) return fail(c, rc, err_local);
+    if (s.read != hipSuccess) return fail(c, L3D_ERR_HIP, std::string("l3d_shard_chain_products: reading the status words: ") + hipGetErrorString(s.read));
     part.n_pot_all = 0;
     for (int r = 0; r < h->world; ++r) {
-        long long x = 0;
-        HIPCHK(c, hipMemcpyAsync(&x, h->part_status + 256 * ((size_t)r + 1), 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
+        const long long x = words[(size_t)r];
         if (x < 0) return fail(c, L3D_ERR_HIP, "l3d_shard_chain_products: rank " + std::to_string(r) + " failed (code " + std::to_string(-x) + ") while building its rows of the products");
         part.n_pot_all += x;
     }
@@ -1110,6 +1221,30 @@ int l3d_shard_chain_products(l3d_shard_chain* h, const l3d_dense_map* map, l3d_c
     c->products.n_pot = n_local;
     c->products.valid = true;
     if (n_pot) *n_pot = n_local;
+    return L3D_OK;
+}
+
+// a partitioned rank's share from its compact arena: rows of the views within reach of its block, best matches / medians of every view it kept
+static int shard_products_share(l3d_shard_chain* h, const l3d_dense_map* map, l3d_chain_summary* summary, int64_t* n_pot, ProductsPart* part_out,
+                                const std::vector<ProdChainView>& pvh, const std::vector<ChainResult>& hres, long long total, const unsigned* qt_arena)
+{
+    l3d_ctx* c = h->c;
+    const int nv = h->n_views, own0 = h->part.own0, own1 = h->part.own1, reach = h->part.reach;
+    ProductsPart part = products_part(h->views, nv, map, h->rank, h->world, own0, own1, std::max(0, own0 - reach), std::min(nv, own1 + reach), std::max(0, own0 - 2 * reach), std::min(nv, own1 + 2 * reach));
+    // (a turn of a node object whose ranks share a device: the share was computed alone -- world 1 -- and joins the collective finish as the rank it stands for)
+    if (c->turn_share && h->world == 1 && c->opt.part_vworld > 0) { part.world = c->opt.part_vworld; part.rank = std::max(0, std::min(c->opt.part_vrank, part.world - 1)); }
+    int64_t n_local = 0;
+    if (c->opt.part_release != 0) {
+        // the job is sized by memory: the chain's scratch and the rings of slots are given back before the products are built (as l3d_match_chain_partition does)
+        if (int rc = release_chain_scratch(c, { &c->ch_gathered, &c->ch_send })) return rc;
+        h->gathered = nullptr;
+    }
+    const int rc = build_products(c, h->views, nv, pvh.data(), hres.data(), map, summary, &n_local, part.row_dv0, part.row_dv1, reinterpret_cast<const char*>(h->part.keep.data()), qt_arena);
+    if (rc) return rc;
+    c->part_arena_seen = std::max(c->part_arena_seen, (size_t)total + (size_t)total / 8 + 65536);
+    if (n_pot) *n_pot = n_local;
+    if (part_out) *part_out = part;
+    memcpy(c->ch_pin_res.as<ChainResult>(), hres.data(), (size_t)nv * sizeof(ChainResult));      // (what l3d_chain_kept_list reads)
     return L3D_OK;
 }
 
@@ -1121,15 +1256,14 @@ static int shard_products_local(l3d_shard_chain* h, const l3d_dense_map* map, l3
     hipStream_t st = c->stream;
     const int nv = h->n_views;
     const size_t nvs = (size_t)nv;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     // scratch: verified flags | totals int2 | kept_base u64 | best_off i64
-    const size_t o_ver = 0, o_tot = al(nvs), o_kb = o_tot + al(nvs * 8), o_bo = o_kb + al(nvs * 8), bytes = o_bo + al(nvs * 8);
+    const size_t o_ver = 0, o_tot = align256(nvs), o_kb = o_tot + align256(nvs * 8), o_bo = o_kb + align256(nvs * 8), bytes = o_bo + align256(nvs * 8);
     HIPCHK(c, c->g7.reserve(bytes + 64));
     unsigned char* sc = c->g7.as<unsigned char>();
     std::vector<unsigned char> ver(nvs);
     for (int k = 0; k < nv; ++k) ver[(size_t)k] = h->vd[(size_t)k].verified ? 1 : 0;
     HIPCHK(c, hipMemcpyAsync(sc + o_ver, ver.data(), nvs, hipMemcpyHostToDevice, st));
-    if (h->ring_mode) hipLaunchKernelGGL(k_shard_totals, dim3((nv + 255) / 256), dim3(256), 0, st, reinterpret_cast<const unsigned char*>(h->hdr_all), sizeof(SlotHeader), h->geom, sc + o_ver, nv, reinterpret_cast<int2*>(sc + o_tot));
+    if (h->ring.on) hipLaunchKernelGGL(k_shard_totals, dim3((nv + 255) / 256), dim3(256), 0, st, reinterpret_cast<const unsigned char*>(h->ring.hdr_all), sizeof(SlotHeader), h->geom, sc + o_ver, nv, reinterpret_cast<int2*>(sc + o_tot));
     else hipLaunchKernelGGL(k_shard_totals, dim3((nv + 255) / 256), dim3(256), 0, st, h->gathered, h->geom.slot_bytes, h->geom, sc + o_ver, nv, reinterpret_cast<int2*>(sc + o_tot));
     std::vector<int2> tot(nvs);
     HIPCHK(c, hipMemcpyAsync(tot.data(), sc + o_tot, nvs * 8, hipMemcpyDeviceToHost, st));
@@ -1144,7 +1278,7 @@ static int shard_products_local(l3d_shard_chain* h, const l3d_dense_map* map, l3
     for (int k = 0; k < nv; ++k) {
         const SViewDev& d = h->vd[(size_t)k];
         ChainResult& r = hres[(size_t)k];
-        const bool here = !h->partition || h->keep[(size_t)k];            // (partitioned: the views this rank retired)
+        const bool here = !h->part.on || h->part.keep[(size_t)k];            // (partitioned: the views this rank retired)
         r.kept_base = (uint64_t)total; r.n_want = 0; r.n_kept = d.verified && here ? tot[(size_t)k].x : 0; r.R = d.verified && here ? tot[(size_t)k].y : 0; r.overflow = 0;
         kept_base[(size_t)k] = (unsigned long long)total;
         total += r.n_kept;
@@ -1152,33 +1286,14 @@ static int shard_products_local(l3d_shard_chain* h, const l3d_dense_map* map, l3
         pvh[(size_t)k].verified = d.verified ? 1 : 0;
         pvh[(size_t)k].best = d.verified && here ? d.best : nullptr;
         pvh[(size_t)k].bestpos = d.verified && here ? d.bestpos : nullptr;
-        pvh[(size_t)k].rt = h->ring_mode && h->retire_tables && d.verified && here ? c->ch_rt.as<int>() + h->rt_off[(size_t)k] : nullptr;
+        pvh[(size_t)k].rt = h->ring.on && h->ring.retire_tables && d.verified && here ? c->ch_rt.as<int>() + h->ring.rt_off[(size_t)k] : nullptr;
     }
-    const unsigned* qt_arena = h->ring_mode && h->retire_tables ? c->ch_keptcam.as<unsigned>() : nullptr;
-    if (h->ring_mode) {
+    const unsigned* qt_arena = h->ring.on && h->ring.retire_tables ? c->ch_keptcam.as<unsigned>() : nullptr;
+    if (h->ring.on) {
         // the records are in the arena already (k_shard_retire, view by view in this very order)
-        if (total != h->arena_needed) return fail(c, L3D_ERR_INVALID, "l3d_shard_chain_products: the retired records do not add up to the slot headers");
+        if (total != h->ring.arena_needed) return fail(c, L3D_ERR_INVALID, "l3d_shard_chain_products: the retired records do not add up to the slot headers");
         h->kept_total = (double)total;
-        if (h->partition) {
-            // this rank's share: rows of the views within reach of its block, best matches / medians of every view it kept
-            const int own0 = h->part_own0, own1 = h->part_own1, reach = h->part_reach;
-            ProductsPart part = products_part(h->views, nv, map, h->rank, h->world, own0, own1, std::max(0, own0 - reach), std::min(nv, own1 + reach), std::max(0, own0 - 2 * reach), std::min(nv, own1 + 2 * reach));
-            // (a turn of a node object whose ranks share a device: the share was computed alone -- world 1 -- and joins the collective finish as the rank it stands for)
-            if (c->turn_share && h->world == 1 && c->opt.part_vworld > 0) { part.world = c->opt.part_vworld; part.rank = std::max(0, std::min(c->opt.part_vrank, part.world - 1)); }
-            int64_t n_local = 0;
-            if (c->opt.part_release != 0) {
-                // the job is sized by memory: the chain's scratch and the rings of slots are given back before the products are built (as l3d_match_chain_partition does)
-                if (int rc = release_chain_scratch(c, { &c->ch_gathered, &c->ch_send })) return rc;
-                h->gathered = nullptr;
-            }
-            const int rc = build_products(c, h->views, nv, pvh.data(), hres.data(), map, summary, &n_local, part.row_dv0, part.row_dv1, reinterpret_cast<const char*>(h->keep.data()), qt_arena);
-            if (rc) return rc;
-            c->part_arena_seen = std::max(c->part_arena_seen, (size_t)total + (size_t)total / 8 + 65536);
-            if (n_pot) *n_pot = n_local;
-            if (part_out) *part_out = part;
-            memcpy(c->ch_pin_res.as<ChainResult>(), hres.data(), (size_t)nv * sizeof(ChainResult));      // (what l3d_chain_kept_list reads)
-            return L3D_OK;
-        }
+        if (h->part.on) return shard_products_share(h, map, summary, n_pot, part_out, pvh, hres, total, qt_arena);
         c->chain_seen_arena_cap = std::max(c->chain_seen_arena_cap, (size_t)total + (size_t)total / 8 + 65536);
         return build_products(c, h->views, nv, pvh.data(), hres.data(), map, summary, n_pot, 0, -1, nullptr, qt_arena);
     }
@@ -1229,10 +1344,10 @@ int l3d_shard_chain_partition(l3d_shard_chain* h, int own_begin, int own_end)
     l3d_ctx* c = h->c;
     const int nv = h->n_views;
     if (own_begin < 0 || own_end > nv || own_begin > own_end) return fail(c, L3D_ERR_INVALID, "l3d_shard_chain_partition: bad view range");
-    h->keep.assign((size_t)nv, 0);
+    h->part.keep.assign((size_t)nv, 0);
     int reach = 1;
-    if (int rc = l3d_partition_keep_views(h->views, nv, own_begin, own_end, h->keep.data(), &reach)) return fail(c, rc, "l3d_shard_chain_partition: bad schedule");
-    h->partition = true; h->part_own0 = own_begin; h->part_own1 = own_end; h->part_reach = reach;
+    if (int rc = l3d_partition_keep_views(h->views, nv, own_begin, own_end, h->part.keep.data(), &reach)) return fail(c, rc, "l3d_shard_chain_partition: bad schedule");
+    h->part.on = true; h->part.own0 = own_begin; h->part.own1 = own_end; h->part.reach = reach;
     return L3D_OK;
 }
 
@@ -1252,6 +1367,68 @@ int l3d_shard_chain_close(l3d_shard_chain* h)
                 h->rank, h->world, h->t_enq * 1e3, h->t_ex * 1e3, h->t_wait * 1e3, h->t_copy * 1e3, h->t_cb * 1e3);
     delete h;
     return L3D_OK;
+}
+
+// the rules of l3d_shard_rule.hpp on plain numbers (tests/test_shard_plan_cases_cpu.py): no context, no device.  A section whose input is null is skipped
+int l3d_test_shard_plan(const int64_t geom_in[6], int64_t geom_out[10], const int64_t ring_in[6], int32_t ring_out[3], double pairs, const int64_t guess_in[10],
+                        int64_t* guess_out, const int64_t verdict_in[4], int32_t* verdict_rc, char* text, int text_cap, const int64_t retry_in[8], int64_t retry_out[5])
+{
+    if (geom_in) {
+        if (!geom_out || geom_in[2] < 1 || geom_in[3] < 1) return L3D_ERR_INVALID;
+        const SlotPlan p = slot_geometry((int)geom_in[0], (int)geom_in[1], (int)geom_in[2], (int)geom_in[3], (int)geom_in[4], (int)geom_in[5]);
+        const SlotGeom& g = p.geom;
+        const int64_t v[10] = { g.seg_cap, (int64_t)g.best_off, (int64_t)g.bpos_off, (int64_t)g.rec_off, (int64_t)g.cam_off, (int64_t)g.rt_off, (int64_t)g.slot_bytes, (int64_t)p.stage_bytes, g.ring, g.max_n };
+        memcpy(geom_out, v, sizeof(v));
+    }
+    if (ring_in) {
+        if (!ring_out) return L3D_ERR_INVALID;
+        const ShardRingPlan p = shard_ring_plan((int)ring_in[0], (int)ring_in[1], (size_t)ring_in[2], (int)ring_in[3], ring_in[4] != 0, ring_in[5] != 0);
+        ring_out[0] = p.ring_mode ? 1 : 0; ring_out[1] = p.ring_views; ring_out[2] = p.send_ring;
+    }
+    if (guess_in) {      // world, test cap, seen cap, arena_guess, free bytes (-1: unknown), regrow_free_mb, partition, kept views, n_views, part seen
+        if (!guess_out) return L3D_ERR_INVALID;
+        guess_out[1] = shard_room_records((int)guess_in[5]);
+        guess_out[0] = shard_arena_first_guess(pairs, (int)guess_in[0], (size_t)guess_in[1], (size_t)guess_in[2], (int)guess_in[3], guess_in[4] < 0 ? kShardFreeUnknown : (size_t)guess_in[4],
+                                               guess_out[1], guess_in[6] != 0, guess_in[7], (int)guess_in[8], (size_t)guess_in[9]);
+    }
+    if (verdict_in) {    // bits, largest candidate count, largest kept count, arena total
+        if (!verdict_rc || !text || text_cap < 1) return L3D_ERR_INVALID;
+        const ShardVerdict v = shard_verdict((int)verdict_in[0], (int)verdict_in[1], (int)verdict_in[2], verdict_in[3]);
+        *verdict_rc = v.rc;
+        snprintf(text, (size_t)text_cap, "%s", v.text.c_str());
+    }
+    if (retry_in) {      // bits, cand_cap, largest candidate count, slot_records, largest kept count, arena needed, room, replay
+        if (!retry_out) return L3D_ERR_INVALID;
+        const ShardRetry r = shard_retry((int)retry_in[0], (size_t)retry_in[1], (int)retry_in[2], (int)retry_in[3], (int)retry_in[4], retry_in[5], retry_in[6], retry_in[7] != 0);
+        const int64_t v[5] = { r.retry ? 1 : 0, (int64_t)r.cand_cap_next, r.slot_records_next, (int64_t)r.arena_cap_next, r.refuse_for_room ? 1 : 0 };
+        memcpy(retry_out, v, sizeof(v));
+    }
+    return L3D_OK;
+}
+
+// RetireSchedule as l3d_shard_chain_run drives it, over all views of a run whose ring is planned by shard_ring_plan (tests/test_shard_retire_cases_cpu.py): for
+// every view the views retired / waited for when its exchange is enqueued, every batch as (first, count, the view it was enqueued at -- n_views: the final
+// flush --, waited before), and summary = { ring mode, ring, batches, retired and waited for after the flush, 1 when a batch is still outstanding }
+int l3d_test_shard_retire(int n_views, int window, int slot_ring, int partition, int apart, int32_t* retired_at, int32_t* waited_at, int32_t* batches, int max_batches, int32_t summary[6])
+{
+    if (n_views < 0 || window < 0 || (n_views > 0 && (!retired_at || !waited_at)) || !batches || max_batches < 0 || !summary) return L3D_ERR_INVALID;
+    const ShardRingPlan p = shard_ring_plan(n_views, window, 1, slot_ring, partition != 0, false);
+    RetireSchedule s;
+    s.window = window; s.ring = p.ring_views; s.apart = p.ring_mode && apart != 0;
+    int nb = 0;
+    auto retire_to = [&](int upto, int at) {
+        for (RetireBatch b = s.next(upto); b.count; b = s.next(upto), ++nb)
+            if (nb < max_batches) { int32_t* o = batches + 4 * (size_t)nb; o[0] = b.first; o[1] = b.count; o[2] = at; o[3] = b.wait_before ? 1 : 0; }
+    };
+    for (int k = 0; k < n_views && p.ring_mode; ++k) {
+        retire_to(s.due(k), k);
+        s.wait_due(k);
+        retired_at[k] = s.retired; waited_at[k] = s.waited();
+    }
+    if (p.ring_mode) { retire_to(n_views, n_views); s.wait_all(); }
+    const int32_t v[6] = { p.ring_mode ? 1 : 0, p.ring_views, nb, s.retired, s.waited(), s.outstanding() ? 1 : 0 };
+    memcpy(summary, v, sizeof(v));
+    return nb <= max_batches ? L3D_OK : L3D_ERR_INVALID;
 }
 
 }  // extern "C"

@@ -5,6 +5,7 @@
 #include "l3d_detect.hpp"
 #include "l3d_node.hpp"
 #include "l3d_turns.hpp"
+#include "l3d_shard_rule.hpp"
 
 #include <hip/hip_runtime_api.h>
 
@@ -1627,19 +1628,17 @@ int l3d_line3d_shard_run(l3d_line3d* h, int rank, int world, int slot_records, l
         if (rc == L3D_OK) return rc2;
         h->fail(rc, msg);
         if (hopt(h).timing) fprintf(stderr, "[l3d shard_run] attempt %d failed (%d): %s\n", attempt, rc, msg.c_str());
-        if (rc != L3D_ERR_NOMEM || (bits & 4 && !(bits & 11)) || !(bits & 11)) return rc;    // not a capacity verdict: nothing a retry would change
-        if (bits & 8) {
-            const long long need = P_shard_arena;
-            // (tests, option regrow_free_mb: the room the compact arena may take -- a run that needs more has its answer, no re-run)
-            const long long room = hopt(h).regrow_free_mb > 0 ? (long long)(((size_t)hopt(h).regrow_free_mb << 20) / (sizeof(l3d_match) + 4)) : 0;
-            if (room > 0 && need > room)
-                return h->fail(L3D_ERR_NOMEM, "shard_run: the compact arena of this rank needs " + std::to_string(need) + " records, there is room for " + std::to_string(room) + " (" +
-                                              std::to_string(hopt(h).regrow_free_mb) + " MB at " + std::to_string(sizeof(l3d_match) + 4) + " B per record)");
-            arena_cap_next = (size_t)need + (size_t)need / 4 + 65536;
-        }
-        if ((bits & 2) && exchange == l3d_exchange_replay) return rc;                        // recorded blocks have the recorded slot size: the caller records again with more room
-        if (bits & 1) cand_cap_next = h->shard_cand_cap_seen = std::max(cand_cap * 2, (size_t)max_cand + (size_t)max_cand / 4 + 65536);
-        if (bits & 2) slot_records = h->shard_slot_records_seen = std::max(slot_records * 2, max_kept + max_kept / 4 + 1024);
+        if (rc != L3D_ERR_NOMEM) return rc;
+        // what the shared verdict asks for (shard_retry, l3d_shard_rule.hpp): nothing a retry would change, or the same, larger capacities on every rank
+        const long long room = l3d::shard_room_records(hopt(h).regrow_free_mb);
+        const l3d::ShardRetry next = l3d::shard_retry(bits, cand_cap, max_cand, slot_records, max_kept, P_shard_arena, room, exchange == l3d_exchange_replay);
+        if (next.refuse_for_room)
+            return h->fail(L3D_ERR_NOMEM, "shard_run: the compact arena of this rank needs " + std::to_string(P_shard_arena) + " records, there is room for " + std::to_string(room) + " (" +
+                                          std::to_string(hopt(h).regrow_free_mb) + " MB at " + std::to_string(sizeof(l3d_match) + 4) + " B per record)");
+        if (!next.retry) return rc;
+        if (next.arena_cap_next) arena_cap_next = next.arena_cap_next;
+        if (next.cand_cap_next) cand_cap_next = h->shard_cand_cap_seen = next.cand_cap_next;
+        if (next.slot_records_next) slot_records = h->shard_slot_records_seen = next.slot_records_next;
     }
     return rc;
 }

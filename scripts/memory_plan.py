@@ -90,6 +90,7 @@ def plan_segments(V, S, N, W, kept_ratio):
     add("candidate store + window scratch (per launch)", cand_cap * 44, "chain_reserve_candidates")
     add("stage-1 candidate ring (10 views ahead)", 10 * cand_cap * 24, "chain_reserve_candidates (ring)")
     slot_records = max(10 * S * N // W, int(1.25 * kept_view / W) + 1024)
+    # (an estimate; the exact rule, with its alignments, the side words and the run table, is slot_geometry in line3d_amd/csrc/l3d_shard_rule.hpp)
     slot_bytes = 32 + (S // W + 1) * 12 + slot_records * 32
     ring = window + 18
     add("send + gathered slots: ring of %d views x %d ranks" % (ring, W), ring * (W + 1) * slot_bytes, "l3d_chain_sharded.hip:l3d_shard_chain_run (ring mode)")
