@@ -2,12 +2,15 @@
 // segment caches of an earlier Line3D run standing in for the images, or with the images as binary PPM / PGM files or baseline JPEG files (no
 // OpenCV, no tclap, no boost):
 //
-//   main_vsfm_amd [--refine] [--device-covisibility] <scene.nvm | bundle.rd.out> <data directory> [neighbors=10] [diffusion=0] [output folder=<data directory>] [image folder]
+//   main_vsfm_amd [--refine] [--device-covisibility] [--overlays <folder>] <scene.nvm | bundle.rd.out> <data directory> [neighbors=10] [diffusion=0] [output folder=<data directory>] [image folder]
 //
 // --refine (anywhere on the line): the 3-D lines are refined against the 2-D segments of their clusters before they are written (setRefinement: the
 // reference has no such step; its successor Line3D++ added one) -- the segments of a line in the STL / TXT files are then collinear.
 // --device-covisibility (anywhere on the line): the cameras' world point lists are counted on the GPU when compute3Dmodel starts, instead of one
 // observation at a time as the images are added (setDeviceCovisibility: the same neighbours, the same lines; it pays on models of many images).
+// --overlays <folder> (anywhere on the line): after compute3Dmodel every view's image -- loaded once more and undistorted as it was added; a grey canvas
+// of the view's size when the segment caches stood in for the images -- is written with the view's overlay (overlayView: its 2-D segments that belong to
+// a line, and the projected 3-D lines it observes, coloured by line) as "<folder>/overlay_<camera>.ppm" (binary P6; the folder has to exist).
 // With an image folder, camera i's image is "<image folder>/<camera name, extension replaced>.ppm" or ".pgm" (binary P6 / P5, maxval 255), or the
 // camera's own file "<image folder>/<camera name>" when it ends in .jpg / .jpeg (baseline JPEG, decoded on the device: addImageJPEGDistorted;
 // convert PNG and progressive JPEG beforehand).  The camera name is the NVM file's image name; for a bundler file it is the camera index as %08d
@@ -115,6 +118,28 @@ bool load_camera_jpeg(const std::string& folder, const std::string& name, std::v
     fclose(f);
     return !bytes.empty();
 }
+// an image as three channels (a grey one repeated), written as a binary P6 file
+void to_three_channels(PnmImage& img)
+{
+    if (img.ch == 3) return;
+    std::vector<unsigned char> rgb((size_t)img.cols * img.rows * 3);
+    for (int i = 0; i < img.rows; ++i)
+        for (int j = 0; j < img.cols; ++j)
+            for (int c = 0; c < 3; ++c) rgb[((size_t)i * img.cols + j) * 3 + c] = img.data[(size_t)i * img.step + (size_t)j * img.ch];
+    img.store.swap(rgb); img.data = img.store.data(); img.ch = 3; img.step = (size_t)img.cols * 3;
+}
+bool write_ppm(const std::string& path, const PnmImage& img)
+{
+    FILE* f = fopen(path.c_str(), "wb");
+    if (!f) return false;
+    fprintf(f, "P6\n%d %d\n255\n", img.cols, img.rows);
+    bool ok = true;
+    for (int i = 0; i < img.rows && ok; ++i) ok = fwrite(img.data + (size_t)i * img.step, 1, (size_t)img.cols * 3, f) == (size_t)img.cols * 3;
+    return fclose(f) == 0 && ok;
+}
+// what --overlays needs of a camera once the model is there
+struct OverlayJob { unsigned id; int w, h; double K[9], k[2]; std::string name; };
+
 // K, R, t of the facade's matrix-typed calls over plain arrays
 struct Mat3 { const double* p; double operator()(int i, int j) const { return p[i * 3 + j]; } };
 struct Vec3 { const double* p; double operator()(int i) const { return p[i]; } };
@@ -124,12 +149,18 @@ struct Vec3 { const double* p; double operator()(int i) const { return p[i]; } }
 int main(int argc, char** argv)
 {
     bool refine = false, device_covis = false;
+    std::string overlay_dir;
     {
         int k = 1;
-        for (int i = 1; i < argc; ++i) { if (std::string(argv[i]) == "--refine") refine = true; else if (std::string(argv[i]) == "--device-covisibility") device_covis = true; else argv[k++] = argv[i]; }
+        for (int i = 1; i < argc; ++i) {
+            if (std::string(argv[i]) == "--refine") refine = true;
+            else if (std::string(argv[i]) == "--device-covisibility") device_covis = true;
+            else if (std::string(argv[i]) == "--overlays" && i + 1 < argc) overlay_dir = argv[++i];
+            else argv[k++] = argv[i];
+        }
         argc = k;
     }
-    if (argc < 3) { fprintf(stderr, "usage: %s [--refine] [--device-covisibility] <scene.nvm | bundle.rd.out> <data directory> [neighbors=10] [diffusion=0] [output folder] [image folder]\n", argv[0]); return 2; }
+    if (argc < 3) { fprintf(stderr, "usage: %s [--refine] [--device-covisibility] [--overlays <folder>] <scene.nvm | bundle.rd.out> <data directory> [neighbors=10] [diffusion=0] [output folder] [image folder]\n", argv[0]); return 2; }
     const std::string nvm = argv[1], data_dir = argv[2];
     const int neighbors = argc > 3 ? atoi(argv[3]) : 10;
     const bool diffusion = argc > 4 && atoi(argv[4]) != 0;
@@ -151,6 +182,11 @@ int main(int argc, char** argv)
     if (refine) line3D.setRefinement(true);
     if (device_covis) line3D.setDeviceCovisibility(true);
     int added = 0;
+    std::vector<OverlayJob> jobs;
+    auto note = [&](unsigned id, int w, int h, const double* K, const double* k, const char* name) {
+        OverlayJob j; j.id = id; j.w = w; j.h = h; memcpy(j.K, K, sizeof(j.K)); j.k[0] = k[0]; j.k[1] = k[1]; j.name = name ? name : "";
+        jobs.push_back(j);
+    };
     for (int i = 0; i < n; ++i) {
         double focal = 0, dist[2] = { 0, 0 }, R[9], t[3];
         int nwp = 0;
@@ -170,6 +206,7 @@ int main(int argc, char** argv)
                 l3d_sfm_camera_cv_distortion(scene, i, k);
                 const unsigned before = line3D.numCameras();
                 line3D.addImageJPEGDistorted((unsigned)i, file.data(), file.size(), Mat3{ K }, Mat3{ R }, Vec3{ t }, k[0], k[1], wps);
+                if (line3D.numCameras() > before) note((unsigned)i, (int)jw, (int)jh, K, k, l3d_sfm_camera_name(scene, i));
                 added += (int)(line3D.numCameras() - before);
                 continue;
             }
@@ -177,6 +214,7 @@ int main(int argc, char** argv)
             l3d_sfm_camera_cv_distortion(scene, i, k);
             const unsigned before = line3D.numCameras();
             line3D.addImageDistorted((unsigned)i, img, Mat3{ K }, Mat3{ R }, Vec3{ t }, k[0], k[1], wps);
+            if (line3D.numCameras() > before) note((unsigned)i, img.cols, img.rows, K, k, l3d_sfm_camera_name(scene, i));
             added += (int)(line3D.numCameras() - before);
             continue;
         }
@@ -185,7 +223,7 @@ int main(int argc, char** argv)
         if (!find_cache(data_dir, (unsigned)i, w, h)) { fprintf(stderr, "camera %d: no segment cache in %s\n", i, data_dir.c_str()); continue; }
         double K[9];
         l3d_sfm_intrinsics(focal, w, h, K);
-        if (line3D.addImageFromCache((unsigned)i, w, h, K, R, t, wps)) ++added;
+        if (line3D.addImageFromCache((unsigned)i, w, h, K, R, t, wps)) { ++added; const double k0[2] = { 0, 0 }; note((unsigned)i, (int)w, (int)h, K, k0, nullptr); }
     }
     l3d_sfm_free(scene);
     fprintf(stderr, "[L3D] %d of %d cameras added\n", added, n);
@@ -201,5 +239,33 @@ int main(int argc, char** argv)
     name << "tL_" << 1.0f << "__tU_" << 5.0f << "__sigmaP_" << 3.5f << "__sigmaA_" << 10.0f << "__COLLIN__" << (diffusion ? "DIFFUSION" : "NO_DIFFUSION");
     line3D.save3DLinesAsSTL(result, name.str() + ".stl");                       // line3D.h:88-91
     line3D.save3DLinesAsTXT(result, name.str() + ".txt");
+
+    // --overlays: one viewable PPM per view
+    if (!overlay_dir.empty()) {
+        int written = 0;
+        for (const OverlayJob& j : jobs) {
+            PnmImage img;
+            bool have = false;
+            if (!image_dir.empty() && !j.name.empty()) {
+                have = load_camera_image(image_dir, j.name, img);
+                if (!have) {
+                    std::vector<unsigned char> file;
+                    unsigned jw = 0, jh = 0, jch = 0;
+                    if (load_camera_jpeg(image_dir, j.name, file) && line3D.decodeJPEG(file.data(), file.size(), img.store, jw, jh, jch)) {
+                        img.cols = (int)jw; img.rows = (int)jh; img.ch = (int)jch; img.step = (size_t)jw * jch; img.data = img.store.data();
+                        have = true;
+                    }
+                }
+                if (have && (j.k[0] != 0.0 || j.k[1] != 0.0)) have = line3D.undistortImage(img, Mat3{ j.K }, j.k[0], j.k[1]);
+            }
+            if (!have || img.cols != j.w || img.rows != j.h) {          // no image: a grey canvas of the view's size
+                img.cols = j.w; img.rows = j.h; img.ch = 3; img.step = (size_t)j.w * 3;
+                img.store.assign(img.step * (size_t)j.h, 128); img.data = img.store.data();
+            }
+            to_three_channels(img);
+            if (line3D.overlayView(j.id, img, L3D::OverlayStyle()) && write_ppm(overlay_dir + "/overlay_" + std::to_string(j.id) + ".ppm", img)) ++written;
+        }
+        fprintf(stderr, "[L3D] %d overlays written to %s\n", written, overlay_dir.c_str());
+    }
     return result.empty() ? 3 : 0;
 }

@@ -64,6 +64,18 @@ private:
     bool has_lens_ = false;
 };
 
+// The style of Line3D::overlayView (include/line3d_amd.h, "PROJECTION AND OVERLAYS": l3d_overlay_style) with its defaults: both layers, only the
+// lines observed in the view, coloured by line from the default palette, widths 1 and 2 pixels, opaque.  Change the members as needed
+struct OverlayStyle : l3d_overlay_style {
+    OverlayStyle() : l3d_overlay_style()
+    {
+        layers = L3D_LAYER_MEMBERS | L3D_LAYER_MODEL; select = L3D_SELECT_OBSERVED; by_line = 1; opacity = 255;
+        width_members = 1.0; width_model = 2.0; near_z = 1e-6;
+        const unsigned char green[4] = { 0, 255, 0, 255 }, red[4] = { 255, 0, 0, 255 };
+        memcpy(color_members, green, 4); memcpy(color_model, red, 4);
+    }
+};
+
 // commons.h:81-99
 class L3DSegment2D {
 public:
@@ -680,6 +692,63 @@ public:
         if (l3d_line3d_get_segment2D(h_, seg2D.camID(), seg2D.segID(), o) != L3D_OK)
             std::cerr << prefix_ << "no view with ID " << seg2D.camID() << "!" << std::endl;
         return float4{ o[0], o[1], o[2], o[3] };
+    }
+    // ---- the result over the views (no counterpart in the reference; include/line3d_amd.h, "PROJECTION AND OVERLAYS")
+    // The result's 3-D segments projected into views: camera-major, camStart[c] .. camStart[c + 1] are view viewIDs[c]'s.  segIndex counts the 3-D
+    // segments in getResult()'s order, lineIndex its lines; flags bit 0 / 1: the first / second end was moved by the near plane or the image's border.
+    // select: L3D_SELECT_ALL, or L3D_SELECT_OBSERVED (only lines with a 2-D segment in the view).  The cameras are the views' own, as they were added
+    struct Projection {
+        std::vector<float4> segments;
+        std::vector<int> segIndex, lineIndex;
+        std::vector<unsigned char> flags;
+        std::vector<long long> camStart;
+    };
+    Projection projectResult(const std::vector<unsigned int>& viewIDs, const int select = L3D_SELECT_ALL, const double nearZ = 1e-6, const double margin = 0.0)
+    {
+        Projection p;
+        std::vector<uint32_t> ids(viewIDs.begin(), viewIDs.end());
+        std::vector<int64_t> start(ids.size() + 1, 0);
+        float* s = nullptr; int32_t* si = nullptr; int32_t* li = nullptr; unsigned char* fl = nullptr;
+        const int rc = l3d_line3d_project_result(h_, ids.data(), (int)ids.size(), nullptr, select, nearZ, margin, &s, &si, &li, &fl, start.data());
+        report(rc);
+        if (rc != L3D_OK) return p;
+        const size_t n = (size_t)start.back();
+        for (size_t k = 0; k < n; ++k) p.segments.push_back(float4{ s[4 * k], s[4 * k + 1], s[4 * k + 2], s[4 * k + 3] });
+        p.segIndex.assign(si, si + n); p.lineIndex.assign(li, li + n); p.flags.assign(fl, fl + n);
+        p.camStart.assign(start.begin(), start.end());
+        l3d_free(s); l3d_free(si); l3d_free(li); l3d_free(fl);
+        return p;
+    }
+    // Overlay of a view: its 2-D segments that belong to a line, then the projected result, drawn over `image` (8 bits, the view's size) in place.
+    // `image`: anything with .data, .step, .cols, .rows and .channels() (cv::Mat).  style: L3D::OverlayStyle(), changed through its members
+    template <class Img, class = decltype(static_cast<unsigned char*>(std::declval<Img&>().data)), class = decltype(static_cast<int>(std::declval<const Img&>().channels()))>
+    bool overlayView(const unsigned int viewID, Img& image, const l3d_overlay_style& style)
+    {
+        const int rc = l3d_line3d_overlay(h_, viewID, static_cast<unsigned char*>(image.data), (int)image.cols, (int)image.rows, (int)image.channels(), (size_t)image.step, &style);
+        report(rc);
+        return rc == L3D_OK;
+    }
+    // ... over an image in device memory (L3D_U8; deviceImage() fills the descriptor of a GpuMat)
+    bool overlayViewDevice(const unsigned int viewID, const l3d_device_image& image, const l3d_overlay_style& style)
+    {
+        const int rc = l3d_line3d_overlay_device(h_, viewID, &image, &style);
+        report(rc);
+        return rc == L3D_OK;
+    }
+    // segments of the caller's (the image's grid) drawn over `image` on the object's device: segment k takes colours[k % colours.size()],
+    // (c0, c1, c2, alpha) in the image's channel order
+    template <class Img, class = decltype(static_cast<unsigned char*>(std::declval<Img&>().data)), class = decltype(static_cast<int>(std::declval<const Img&>().channels()))>
+    bool drawSegments(Img& image, const std::vector<float4>& segments, const std::vector<std::array<unsigned char, 4> >& colours, const double widthPx = 1.0, const int opacity = 255)
+    {
+        std::vector<float> s;
+        for (const float4& f : segments) { s.push_back(f.x); s.push_back(f.y); s.push_back(f.z); s.push_back(f.w); }
+        std::vector<unsigned char> c;
+        for (auto& col : colours) c.insert(c.end(), col.begin(), col.end());
+        l3d_ctx* ctx = l3d_line3d_context(h_);
+        const int rc = l3d_draw_segments(ctx, static_cast<unsigned char*>(image.data), (int)image.cols, (int)image.rows, (int)image.channels(), (size_t)image.step,
+                                         s.data(), (int)segments.size(), c.data(), (int)colours.size(), nullptr, widthPx, opacity);
+        if (rc != L3D_OK) std::cerr << prefix_ << (ctx ? l3d_last_error(ctx) : "no device context") << std::endl;
+        return rc == L3D_OK;
     }
     // line3D.h:91,94 -- `result` is written as given (the caller may have filtered it); formats as in line3D.cc:384-473
     void save3DLinesAsSTL(std::list<L3DFinalLine3D>& result, std::string filename)

@@ -1453,6 +1453,136 @@ int l3d_line3d_covisibility_path(const l3d_line3d* h);
 int l3d_line3d_get_neighbors(l3d_line3d* h, uint32_t view_id, uint32_t* ids, int cap, int* n);
 int l3d_line3d_get_view_similarities(l3d_line3d* h, uint32_t view_id, uint32_t* ids, float* sims, int cap, int* n);
 
+/* =================================================================================================
+ * PROJECTION AND OVERLAYS: 3-D segments projected into cameras and clipped to their images, and 2-D segments drawn over an image, on the device
+ * (line3d_amd/csrc/l3d_project.hpp, l3d_project.hip, l3d_draw.hpp, l3d_draw.hip).  The conventions the library works with, stated once:
+ * x = K (R X + t); pixel (j, i) has its centre at (j, i); the image covers [-0.5, w - 0.5] x [-0.5, h - 0.5]; segments live in the grid of the image
+ * as it was added (after an undistortion, before any max_img_width down-scaling).
+ *
+ * Numeric rules: all arithmetic is f64; every product, sum, quotient and square root is rounded on its own (nothing fused); integers are int64.
+ * tests/project_model.py and tests/draw_model.py hold the same rules in numpy; the host entry points run the kernels' functions lane after lane; the
+ * three agree bit for bit.
+ *
+ * 1. PROJECTION.  l3d_project_lines: n 3-D segments (seg3d: n x 6 f64, P then Q) into m cameras (l3d_camera: K, R, t row-major, width, height).
+ *   ONE (camera, segment) PAIR:
+ *   Camera frame.  For each row r of R:  c_r = ((R[r,0] X + R[r,1] Y) + R[r,2] Z) + t[r], giving (x, y, z) for P and for Q.  A pair with a camera-
+ *     frame coordinate that is not finite is dropped (so is, with it, every input that is not finite).
+ *   Near plane (near > 0, finite).  Both z < near: dropped.  zP < near <= zQ: s = (near - zP) / (zQ - zP) and P becomes
+ *     (xP + s (xQ - xP), yP + s (yQ - yP), near).  zQ < near <= zP: the same from Q, s = (near - zQ) / (zP - zQ), Q becomes
+ *     (xQ + s (xP - xQ), yQ + s (yP - yQ), near).
+ *   Pixels.  xn = x / z, yn = y / z;  u = (K[0] xn + K[1] yn) + K[2];  v = (K[3] xn + K[4] yn) + K[5].  du = uQ - uP, dv = vQ - vP.  Dropped: any of
+ *     uP, vP, uQ, vQ, du, dv not finite; du == dv == 0.
+ *   THE RECTANGLE RULE.  [xmin, xmax] x [ymin, ymax] = [-0.5 - margin, (width - 0.5) + margin] x [-0.5 - margin, (height - 0.5) + margin], margin >= 0.
+ *     Liang-Barsky on (du, dv) with t0 = 0, t1 = 1; the edges in the order left, right, top, bottom with (p, q) = (-du, uP - xmin), (du, xmax - uP),
+ *     (-dv, vP - ymin), (dv, ymax - vP).  p == 0: dropped iff q < 0.  Otherwise r = q / p; p < 0: dropped iff r > t1, then t0 = max(t0, r);
+ *     p > 0: dropped iff r < t0, then t1 = min(t1, r).  Kept iff t0 < t1 after the four edges.
+ *   Output.  First end (uP + t0 du, vP + t0 dv), exactly (uP, vP) where t0 == 0; second end (uP + t1 du, vP + t1 dv), exactly (uQ, vQ) where
+ *     t1 == 1; each rounded to f32.  flags bit 0: the P end moved (near plane, or t0 > 0); bit 1: the Q end moved (near plane, or t1 < 1).
+ *   OUTPUT.  Camera-major, within a camera in input order: seg2d (4 f32 per output), src_index (int32: the input segment), flags (u8), all
+ *     callee-allocated (l3d_free; one spare element each), and cam_start (m + 1 int64, the caller's): camera c's outputs are [cam_start[c], cam_start[c + 1]).
+ *   REFUSED before anything is launched, L3D_ERR_INVALID: a NULL pointer (seg3d may be NULL with n == 0, cameras with m == 0); n or m < 0; a camera
+ *     whose K third row is not exactly (0, 0, 1) or whose size is below 1 x 1; near not in (0, 1.7976931348623157e308]; margin not in [0, 2^30]; a
+ *     device segment array whose memory kind or extent fails the check an l3d_device_image gets, or that is not aligned to 8 bytes.  n is an int: a
+ *     camera cannot have more than 2^31 - 1 outputs.
+ *   THE KERNELS.  Cameras are processed in chunks.  k_proj_count: one (camera, segment) pair per lane, a wave never spans two cameras; a ballot gives
+ *     the wave's kept pairs as one 64-bit word.  k_proj_scan (one workgroup, l3d_scan.hpp) turns the words' bit counts into positions.  k_proj_write
+ *     runs the pair function again and writes at position-of-the-word + kept lanes below: the order comes from the scan, never from atomics.  Three
+ *     launches per chunk (profile names proj_count, proj_scan, proj_write) whatever n.  A chunk is L3D_PROJ_CHUNK cameras (0: 64), cut down so
+ *     that its ballot words stay below 2^20 and its pairs below 2^31 (never below one camera).
+ *   l3d_project_lines               seg3d in host memory
+ *   l3d_project_lines_device        seg3d in device memory, read in place (the caller has synchronised whatever wrote it); outputs host memory
+ *   l3d_test_project_lines_host     the same arguments without the context: the same functions, no device.  l3d_project_last_error (per thread)
+ *
+ * 2. DRAWING.  l3d_draw_segments draws n segments (n x 4 f32: x1, y1, x2, y2 in the image's grid) over 8-bit pixels, in place.
+ *   Stroke.  W16 = rint(width_px 16); width_px in [0.5, 64], so W16 is in 8..1024.  R16 = W16 / 2.0 + 8.0.
+ *   Clip.  A segment with a coordinate that is not finite is dropped.  The others go through THE RECTANGLE RULE with margin ceil(W16 / 32) + 1 (as
+ *     an integer: (W16 + 31) / 32 + 1); the ends are taken as in "Output" above, in f64.  A zero-length segment inside that rectangle passes the
+ *     rule (every p is 0) and gives a disc.
+ *   Fixed point.  Each clipped end is quantised to sixteenths of a pixel, X = rint(x 16) (ties to even) as int64; a pixel centre is (16 j, 16 i).
+ *   Distance d, in sixteenths, of a pixel centre C from the quantised segment P, Q:  a = C - P, b = Q - P, L2 = b.b, dot = a.b (int64, exact).
+ *     dot <= 0: d = sqrt((double)(a.a)).  dot >= L2: d = sqrt((double)|C - Q|^2).  Otherwise d = (double)|a x b| rinv with
+ *     rinv = 1.0 / sqrt((double)L2), computed once per segment.  Images are at most 32768 on a side, so every integer stays below 2^53.
+ *   Coverage.  cov = clamp((R16 - d) / 16.0, 0, 1), q = (int)floor(cov 255.0 + 0.5).  Caps are round.  A 1-pixel line on an integer y gives 255 on
+ *     its row and 0 beside it; on a half-integer y 128 and 128.
+ *   Winner.  Among the segments with q > 0 at a pixel the one with the largest key (q << 24) | k wins, k the segment's index: on equal coverage the
+ *     later segment.  The result is a function of the pixel alone: any schedule gives the same bytes.
+ *   Blend (integers).  The winner's colour is colors[color_index ? color_index[k] : k % n_colors] = (c0, c1, c2, alpha) in the image's channel order.
+ *     A = (alpha opacity + 127) / 255, a = (q A + 127) / 255, out = (src (255 - a) + col a + 127) / 255 for the colour components
+ *     0 .. min(channels, 3) - 1; a one-channel image uses component 0; a fourth channel is left as it is.
+ *   REFUSED before anything is launched, L3D_ERR_INVALID: a NULL pointer (segments may be NULL with n == 0); n < 0; a size below 1 x 1; channels not
+ *     1, 3 or 4; a row stride below width x channels; n_colors < 1; a color_index entry outside [0, n_colors); width_px outside [0.5, 64]; opacity
+ *     outside 0..255; for a device image what the device-image checks refuse.  L3D_ERR_UNSUPPORTED: n > 2^24; a side above 32768; a device image
+ *     whose dtype is not L3D_U8; more than 2^31 - 1 pieces (below).
+ *   THE KERNELS.  k_draw_pieces clips and quantises every segment and counts its pieces of 64 steps along the major axis (columns for |bx| >= |by|,
+ *     else rows); k_draw_scan (one workgroup) turns the counts into positions.  k_draw_cover: one wave per piece -- a long line and ten thousand
+ *     short ones keep the same number of waves busy; a lane takes one column (row) and walks the pixels across the stroke, the lanes of a wave
+ *     addressing neighbouring pixels, and a no-return 32-bit atomicMax files the key in a key plane the context owns.  k_draw_resolve: one thread per
+ *     pixel of the rows the pieces touch blends where the key is not 0 and writes the 0 back: the plane is zeroed when it is allocated or grown, never
+ *     per call.  Four launches whatever n (profile names draw_pieces, draw_scan, draw_cover, draw_resolve).  Host pixels are uploaded and copied
+ *     back; a device image is drawn where it lies: colour component k goes to source channel chan[k], any strides, and STREAM ORDER of the
+ *     device-image section applies.
+ *   l3d_draw_segments              pixels in host memory: height rows of width x channels bytes, row_stride bytes apart
+ *   l3d_draw_segments_device       an l3d_device_image
+ *   l3d_test_draw_segments_host    l3d_draw_segments without the context: the same functions, no device.  l3d_draw_last_error (per thread)
+ *
+ * 3. ON THE OBJECT.  The current result (l3d_line3d_get_result: world coordinates) projected into views and drawn over a view's image.
+ *   l3d_line3d_project_result   the 3-D segments of the result, in l3d_line3d_get_result's order, through l3d_project_lines.  cameras NULL: each
+ *                               view's own camera, K, R, t and size as the view was added (view_ids: n_views ids).  Otherwise n_views cameras of
+ *                               the caller's, and view_ids may be NULL.  select L3D_SELECT_ALL: every 3-D segment.  L3D_SELECT_OBSERVED: only the
+ *                               segments of lines that have a 2-D member in that view (needs view_ids): the subset of ALL, in the same order.
+ *                               Out, camera-major as above: seg2d, seg_index (into l3d_line3d_get_result's seg3d array), line_index, flags
+ *                               (callee-allocated, l3d_free) and cam_start (n_views + 1).  near_z, margin: as l3d_project_lines
+ *   l3d_line3d_overlay          draws over 8-bit pixels of the view's size (else L3D_ERR_INVALID), layer after layer, each ONE call of
+ *                               l3d_draw_segments: L3D_LAYER_MEMBERS, the view's 2-D segments that are members of a line, in line order, width
+ *                               width_members; then L3D_LAYER_MODEL, l3d_line3d_project_result of the view under style->select with style->near_z
+ *                               and margin 34 (above every stroke's own clip margin), width width_model.  Colours: by_line != 0:
+ *                               palette[line % n_palette] for both layers (palette NULL: l3d_default_palette, 12 entries); by_line == 0: color_members
+ *                               and color_model.  style NULL: both layers, OBSERVED, by line, the default palette, widths 1 and 2, opacity 255, near 1e-6
+ *   l3d_line3d_overlay_device   the same over an l3d_device_image (L3D_U8)
+ *   l3d_default_palette         12 x (c0, c1, c2, alpha): (230, 25, 75) (60, 180, 75) (255, 225, 25) (0, 130, 200) (245, 130, 48) (145, 30, 180)
+ *                               (70, 240, 240) (240, 50, 230) (210, 245, 60) (250, 190, 212) (0, 128, 128) (170, 110, 40), alpha 255 each
+ *   REFUSED, L3D_ERR_INVALID: before a finish (l3d_line3d_compute3Dmodel) has produced a result; an unknown view; a select or a layer mask out of
+ *   range; OBSERVED without view ids; what the two layers refuse, with their codes.  A node object projects and draws on rank 0's context, which holds
+ *   the result.
+ *
+ * OUT OF SCOPE: hidden-line removal and occlusion; drawing onto the distorted source image; dtypes other than U8; PNG output; a batch overlay call.
+ * ================================================================================================= */
+typedef struct l3d_camera {
+    double K[9], R[9], t[3];        /* row-major; x = K (R X + t) */
+    int32_t width, height;
+} l3d_camera;
+int l3d_project_lines(l3d_ctx* ctx, const double* seg3d, int n, const l3d_camera* cameras, int m, double near_z, double margin, float** seg2d,
+                      int32_t** src_index, unsigned char** flags, int64_t* cam_start /* m + 1 */);
+int l3d_project_lines_device(l3d_ctx* ctx, const double* seg3d, int n, const l3d_camera* cameras, int m, double near_z, double margin, float** seg2d,
+                             int32_t** src_index, unsigned char** flags, int64_t* cam_start);
+int l3d_test_project_lines_host(const double* seg3d, int n, const l3d_camera* cameras, int m, double near_z, double margin, float** seg2d,
+                                int32_t** src_index, unsigned char** flags, int64_t* cam_start);
+const char* l3d_project_last_error(void);
+int l3d_draw_segments(l3d_ctx* ctx, unsigned char* pixels, int width, int height, int channels, size_t row_stride, const float* segments, int n,
+                      const unsigned char* colors /* n_colors x 4 */, int n_colors, const int32_t* color_index /* NULL or n */, double width_px, int opacity);
+int l3d_draw_segments_device(l3d_ctx* ctx, const l3d_device_image* image, const float* segments, int n, const unsigned char* colors, int n_colors,
+                             const int32_t* color_index, double width_px, int opacity);
+int l3d_test_draw_segments_host(unsigned char* pixels, int width, int height, int channels, size_t row_stride, const float* segments, int n,
+                                const unsigned char* colors, int n_colors, const int32_t* color_index, double width_px, int opacity);
+const char* l3d_draw_last_error(void);
+enum { L3D_SELECT_ALL = 0, L3D_SELECT_OBSERVED = 1 };
+enum { L3D_LAYER_MEMBERS = 1, L3D_LAYER_MODEL = 2 };
+typedef struct l3d_overlay_style {
+    int32_t layers;                 /* L3D_LAYER_MEMBERS | L3D_LAYER_MODEL */
+    int32_t select;                 /* L3D_SELECT_ALL, L3D_SELECT_OBSERVED: the model layer */
+    int32_t by_line;                /* != 0: palette[line % n_palette] for both layers; 0: color_members / color_model */
+    int32_t opacity;                /* 0..255 */
+    double width_members, width_model, near_z;
+    unsigned char color_members[4], color_model[4];     /* c0, c1, c2, alpha in the image's channel order */
+    const unsigned char* palette;   /* n_palette x 4; NULL: l3d_default_palette */
+    int32_t n_palette, pad;
+} l3d_overlay_style;
+const unsigned char* l3d_default_palette(void);
+int l3d_line3d_project_result(l3d_line3d* h, const uint32_t* view_ids, int n_views, const l3d_camera* cameras, int select, double near_z, double margin,
+                              float** seg2d, int32_t** seg_index, int32_t** line_index, unsigned char** flags, int64_t* cam_start /* n_views + 1 */);
+int l3d_line3d_overlay(l3d_line3d* h, uint32_t view_id, unsigned char* pixels, int width, int height, int channels, size_t row_stride, const l3d_overlay_style* style);
+int l3d_line3d_overlay_device(l3d_line3d* h, uint32_t view_id, const l3d_device_image* image, const l3d_overlay_style* style);
+
 /* The detector's stages on their own, exported for tests (tests/test_gpu_detect_stages.py): the same kernels with the same launch shapes
  * as l3d_detect_segments, results copied to caller-allocated arrays.  (N, M) = (ceil(0.8 new_width), ceil(0.8 new_height)) is the scaled image.
  *   pixel stage   grey[new_width x new_height] after rescale + grey; img / mod / ang [N x M]: the Gaussian sampler's output, the 2x2 gradient's

@@ -450,6 +450,144 @@ def mask_segments_host(segments, mask, **kw):
     return segs, idx
 
 
+class Camera(C.Structure):
+    """l3d_camera: K, R, t (row-major, x = K (R X + t)) and the image size"""
+    _fields_ = [("K", C.c_double * 9), ("R", C.c_double * 9), ("t", C.c_double * 3), ("width", C.c_int32), ("height", C.c_int32)]
+
+
+def cameras(cams):
+    """An l3d_camera array from a list of (K, R, t, width, height) tuples or of dicts with those keys (an array made here passes through)"""
+    if isinstance(cams, C.Array) and cams._type_ is Camera:
+        return cams
+    arr = (Camera * max(1, len(cams)))()
+    for i, cam in enumerate(cams):
+        K, R, t, w, h = (cam[k] for k in ("K", "R", "t", "width", "height")) if isinstance(cam, dict) else cam
+        arr[i].K[:] = [float(v) for v in np.asarray(K, np.float64).reshape(9)]
+        arr[i].R[:] = [float(v) for v in np.asarray(R, np.float64).reshape(9)]
+        arr[i].t[:] = [float(v) for v in np.asarray(t, np.float64).reshape(3)]
+        arr[i].width, arr[i].height = int(w), int(h)
+    arr._n = len(cams)
+    return arr
+
+
+def _project_call(fn, head, seg_ptr, n, cams, m, near, margin):
+    """the argument list the projection calls share (head: the context, or nothing) -> (rc, seg2d (k, 4) float32, src_index (k,) int32,
+    flags (k,) uint8, cam_start (m + 1,) int64)"""
+    seg2d, src, flags = C.POINTER(C.c_float)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_ubyte)()
+    start = np.zeros(max(0, m) + 1, np.int64)
+    rc = fn(*head, seg_ptr, C.c_int(n), cams, C.c_int(m), C.c_double(near), C.c_double(margin), C.byref(seg2d), C.byref(src), C.byref(flags), _p(start))
+    if rc != 0:
+        return rc, None, None, None, None
+    k = int(start[-1])
+    segs = np.ctypeslib.as_array(seg2d, (k * 4,)).copy().reshape(-1, 4) if k else np.zeros((0, 4), np.float32)
+    idx = np.ctypeslib.as_array(src, (k,)).copy() if k else np.zeros(0, np.int32)
+    fl = np.ctypeslib.as_array(flags, (k,)).copy() if k else np.zeros(0, np.uint8)
+    lib = load_library()
+    for p in (seg2d, src, flags):
+        lib.l3d_free(p)
+    return 0, segs, idx, fl, start
+
+
+def _project_arguments(seg3d, cams):
+    s = np.ascontiguousarray(seg3d, np.float64).reshape(-1, 6)
+    arr = cameras(cams)
+    m = getattr(arr, "_n", len(arr))
+    return s, arr, m
+
+
+def project_lines_host(seg3d, cams, near=1e-6, margin=0.0):
+    """l3d_test_project_lines_host: the projection's arithmetic on the host -- no context, no device.  Arguments and result as
+    Context.project_lines (host arrays only).  A refusal raises L3DError carrying the status in .code."""
+    lib = load_library()
+    lib.l3d_project_last_error.restype = C.c_char_p
+    s, arr, m = _project_arguments(seg3d, cams)
+    rc, segs, idx, fl, start = _project_call(lib.l3d_test_project_lines_host, (), _p(s) if len(s) else None, len(s), arr if m else None, m, near, margin)
+    if rc != 0:
+        e = L3DError("line3d_amd error %d: %s" % (rc, lib.l3d_project_last_error().decode()))
+        e.code = rc
+        raise e
+    return segs, idx, fl, start
+
+
+SELECT_ALL, SELECT_OBSERVED = 0, 1
+LAYER_MEMBERS, LAYER_MODEL = 1, 2
+
+
+class OverlayStyle(C.Structure):
+    """l3d_overlay_style (include/line3d_amd.h)"""
+    _fields_ = [("layers", C.c_int32), ("select", C.c_int32), ("by_line", C.c_int32), ("opacity", C.c_int32), ("width_members", C.c_double),
+                ("width_model", C.c_double), ("near_z", C.c_double), ("color_members", C.c_ubyte * 4), ("color_model", C.c_ubyte * 4), ("palette", C.c_void_p),
+                ("n_palette", C.c_int32), ("pad", C.c_int32)]
+
+
+def default_palette():
+    """l3d_default_palette: (12, 4) uint8"""
+    lib = load_library()
+    lib.l3d_default_palette.restype = C.POINTER(C.c_ubyte)
+    return np.ctypeslib.as_array(lib.l3d_default_palette(), (12, 4)).copy()
+
+
+def overlay_style(layers=("members", "model"), select="observed", by_line=True, opacity=255, width_members=1.0, width_model=2.0, near=1e-6,
+                  color_members=(0, 255, 0, 255), color_model=(255, 0, 0, 255), palette=None):
+    """An l3d_overlay_style.  layers: names out of "members", "model" (or a bit mask); select: "all", "observed" (or a number); palette: None (the
+    default of 12 colours) or (n, 4) uint8, kept alive on the returned object"""
+    st = OverlayStyle()
+    names = {"members": LAYER_MEMBERS, "model": LAYER_MODEL}
+    st.layers = int(layers) if isinstance(layers, (int, np.integer)) else sum(names[str(v).lower()] for v in layers)
+    st.select = {"all": SELECT_ALL, "observed": SELECT_OBSERVED}[select.lower()] if isinstance(select, str) else int(select)
+    st.by_line, st.opacity = int(bool(by_line)), int(opacity)
+    st.width_members, st.width_model, st.near_z = float(width_members), float(width_model), float(near)
+    st.color_members[:] = [int(v) for v in color_members]
+    st.color_model[:] = [int(v) for v in color_model]
+    if palette is not None:
+        pal = np.ascontiguousarray(palette, np.uint8).reshape(-1, 4)
+        st.palette, st.n_palette = pal.ctypes.data if len(pal) else None, len(pal)
+        st._keep = pal
+    return st
+
+
+def _draw_image_copy(image):
+    """A copy of a uint8 image to draw on.  Rows that lie further apart than their pixels (a view into a wider array) keep their stride: the copy
+    is a view into a buffer of its own whose padding bytes are 0xa5 (out.base), so that a test can see them untouched"""
+    a = np.asarray(image)
+    if a.dtype != np.uint8 or a.ndim not in (2, 3):
+        raise TypeError("image must be a uint8 array H x W or H x W x C")
+    ch = 1 if a.ndim == 2 else a.shape[2]
+    row = a.shape[1] * ch
+    if a.shape[0] > 1 and a.strides[1] == ch and (a.ndim == 2 or a.strides[2] == 1) and a.strides[0] > row:
+        buf = np.full((a.shape[0], a.strides[0]), 0xA5, np.uint8)
+        out = buf[:, :row].reshape(a.shape)
+        out[...] = a
+        return out
+    return np.array(a, dtype=np.uint8, order="C", copy=True)
+
+
+def _draw_arguments(segments, colors, color_index):
+    s = np.ascontiguousarray(segments, np.float32).reshape(-1, 4)
+    col = np.ascontiguousarray(colors, np.uint8).reshape(-1, 4)
+    idx = None if color_index is None else np.ascontiguousarray(color_index, np.int32).reshape(-1)
+    if idx is not None and len(idx) != len(s):
+        raise ValueError("color_index has one entry per segment")
+    return s, col, idx
+
+
+def draw_segments_host(image, segments, colors, color_index=None, width_px=1.0, opacity=255):
+    """l3d_test_draw_segments_host: the drawing's arithmetic on the host -- no context, no device.  Arguments and result as
+    Context.draw_segments with a numpy image.  A refusal raises L3DError carrying the status in .code."""
+    lib = load_library()
+    lib.l3d_draw_last_error.restype = C.c_char_p
+    out = _draw_image_copy(image)
+    ptr, w, h, ch, stride = image_arguments(out)
+    s, col, idx = _draw_arguments(segments, colors, color_index)
+    rc = lib.l3d_test_draw_segments_host(ptr, C.c_int(w), C.c_int(h), C.c_int(ch), C.c_size_t(stride), _p(s) if len(s) else None, C.c_int(len(s)),
+                                         _p(col) if len(col) else None, C.c_int(len(col)), None if idx is None else _p(idx), C.c_double(width_px), C.c_int(opacity))
+    if rc != 0:
+        e = L3DError("line3d_amd error %d: %s" % (rc, lib.l3d_draw_last_error().decode()))
+        e.code = rc
+        raise e
+    return out
+
+
 def covisibility_arguments(lists):
     """The views' world point lists -> (point_ids uint32, list_start int64 of len(lists) + 1): the lists one after the other, in add order"""
     arrs = [np.ascontiguousarray(a, dtype=np.uint32).reshape(-1) for a in lists]
@@ -1712,6 +1850,44 @@ class Context:
             rc, segs, idx = _mask_segments_call(self.lib.l3d_mask_segments, (self.h,), _p(s) if len(s) else None, len(s), m)
         self._chk(rc)
         return segs, idx
+
+    def project_lines(self, seg3d, cams, near=1e-6, margin=0.0):
+        """l3d_project_lines: 3-D segments (n, 6) float64 (P then Q) into the cameras (capi.cameras(...), or a list of (K, R, t, width, height))
+        ("PROJECTION AND OVERLAYS") -> (seg2d (k, 4) float32, src_index (k,) int32, flags (k,) uint8, cam_start (m + 1,) int64): camera-major,
+        input order within a camera; flags bit 0 / 1: the P / Q end was moved by the near plane or the image's border.  seg3d may be a device
+        object (a contiguous float64 (n, 6) device tensor): it is read in place (l3d_project_lines_device); the caller has synchronised whatever
+        wrote it.  The result is host memory either way."""
+        if hasattr(seg3d, "__cuda_array_interface__"):
+            iface = seg3d.__cuda_array_interface__
+            shape, strides = tuple(int(v) for v in iface["shape"]), iface.get("strides")
+            if len(shape) != 2 or shape[1] != 6 or str(iface["typestr"]) != "<f8" or (strides is not None and tuple(int(v) for v in strides) != (48, 8)):
+                raise TypeError("device segments must be a contiguous float64 array n x 6")
+            arr = cameras(cams)
+            m = getattr(arr, "_n", len(arr))
+            rc, segs, idx, fl, start = _project_call(self.lib.l3d_project_lines_device, (self.h,), C.c_void_p(int(iface["data"][0]) or None), shape[0],
+                                                     arr if m else None, m, near, margin)
+        else:
+            s, arr, m = _project_arguments(seg3d, cams)
+            rc, segs, idx, fl, start = _project_call(self.lib.l3d_project_lines, (self.h,), _p(s) if len(s) else None, len(s), arr if m else None, m, near, margin)
+        self._chk(rc)
+        return segs, idx, fl, start
+
+    def draw_segments(self, image, segments, colors, color_index=None, width_px=1.0, opacity=255, layout=None, chan=None):
+        """l3d_draw_segments: segments (n, 4) float32 in the image's grid drawn over 8-bit pixels ("PROJECTION AND OVERLAYS").  colors: (n_colors, 4)
+        uint8, (c0, c1, c2, alpha) in the image's channel order; segment k takes colors[color_index[k]], or colors[k % n_colors] without
+        color_index.  A numpy image H x W or H x W x C gives a NEW array; a device object (a uint8 device tensor, a capi.device_image(...)
+        descriptor; layout and chan as device_image takes them) is drawn in place and returned (l3d_draw_segments_device)."""
+        s, col, idx = _draw_arguments(segments, colors, color_index)
+        tail = (_p(s) if len(s) else None, C.c_int(len(s)), _p(col) if len(col) else None, C.c_int(len(col)), None if idx is None else _p(idx),
+                C.c_double(width_px), C.c_int(opacity))
+        if is_device_object(image):
+            d = device_image(image, layout=layout, chan=chan)
+            self._chk(self.lib.l3d_draw_segments_device(self.h, C.byref(d), *tail))
+            return image
+        out = _draw_image_copy(image)
+        ptr, w, h, ch, stride = image_arguments(out)
+        self._chk(self.lib.l3d_draw_segments(self.h, ptr, C.c_int(w), C.c_int(h), C.c_int(ch), C.c_size_t(stride), *tail))
+        return out
 
     def covisibility(self, lists):
         """l3d_covisibility: what Line3D::processWorldpointList files for the views' world point lists (one array of uint32 ids per view, in add

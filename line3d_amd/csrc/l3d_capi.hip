@@ -31,7 +31,7 @@ static_assert(kVKAllPairs == L3D_VK_ALL_PAIRS && kVKSegPost == L3D_VK_SEG_POST &
               kVKWindowGB == L3D_VK_WINDOW_GB && kVKBuild == L3D_VK_BUILD && kVKWalk == L3D_VK_WALK && kVKWalkGB == L3D_VK_WALK_GB, "L3D_VK_* of the header");
 
 namespace {
-const char* kProfNames = "pair_mask;row_count;scan;pair_fill;cand_move;exist;verify;verify_window;seg_post;kept_write;collinearity;collinearity_fill;rownorm;diffusion_step;similarity;tgt_rays;prod_keys;prod_sort;prod_rows;hypotheses;uf_components;refine_lines;segmask_count;segmask_scan;segmask_write;covis_keys;covis_sort;covis_runs;covis_count;covis_scan;covis_write";
+const char* kProfNames = "pair_mask;row_count;scan;pair_fill;cand_move;exist;verify;verify_window;seg_post;kept_write;collinearity;collinearity_fill;rownorm;diffusion_step;similarity;tgt_rays;prod_keys;prod_sort;prod_rows;hypotheses;uf_components;refine_lines;segmask_count;segmask_scan;segmask_write;covis_keys;covis_sort;covis_runs;covis_count;covis_scan;covis_write;proj_count;proj_scan;proj_write;draw_pieces;draw_scan;draw_cover;draw_resolve";
 }  // namespace
 
 namespace l3d {
@@ -57,7 +57,7 @@ void ctx_release_share(l3d_ctx* c)
     (void)hipStreamSynchronize(c->stream);
     c->products.release();
     DevBuf* bufs[] = { &c->aff_hyp, &c->aff_first, &c->aff_pass_pairs, &c->aff_pass_w, &c->aff_l2g, &c->edges_keep, &c->ch_send, &c->ch_gathered, &c->ch_hdr,
-                       &c->g0, &c->g1, &c->g2, &c->g3, &c->g4, &c->g5, &c->g6, &c->g7 };
+                       &c->g0, &c->g1, &c->g2, &c->g3, &c->g4, &c->g5, &c->g6, &c->g7, &c->draw_plane };
     for (DevBuf* b : bufs) b->release();
     c->resident_hyp = 0; c->resident_edges = 0; c->kept_edges = 0; c->resident_nodes = 0; c->resident_labels = 0;
 }

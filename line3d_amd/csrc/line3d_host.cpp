@@ -678,6 +678,7 @@ int l3d_line3d_reset(l3d_line3d* h)
     h->worldpoints2views.clear(); h->visual_neighbors.clear(); h->fundamentals.clear(); h->matched.clear();
     h->pot.clear(); h->pot_foreign.clear(); h->hyps.clear(); h->best_idx.clear(); h->A.clear(); h->n_edges = 0; h->A_on_host = true; h->local2global.clear(); h->result.clear();
     h->refine_valid = false;                               // (the setting itself stays)
+    h->result_valid = false;
     h->covis_ids.clear(); h->covis_views.clear(); h->covis_start.assign(1, 0); h->covis_dirty = false; h->covis_path = 0;      // (covis_mode stays)
     h->computation = false; h->prepared = false;
     drop_plan(h);
@@ -1334,9 +1335,11 @@ int l3d_line3d_finish(l3d_line3d* h, int perform_diffusion)
     else if (h->resident_products) { const int rg = greedy_selection_resident(h); if (rg) return rg; }
     else greedy_selection(h);                              // optimizeLocalMatches, :888-896
     if (hopt(h).timing) fprintf(stderr, "[l3d finish] %-28s %8.2f ms\n", "greedy selection", (now_s() - t0) * 1e3);
+    h->result_valid = false;
     int rc = cluster_segments_2D(h, perform_diffusion != 0);
     h->refine_valid = false;
     if (!rc && h->refine_on) rc = refine_result(h);
+    h->result_valid = rc == L3D_OK;
     if (hopt(h).timing) fprintf(stderr, "[l3d finish] %-28s %8.2f ms\n", "total", (now_s() - t0) * 1e3);
     if (!rc && h->verbose)      // line3D.cc:959-961, 1226-1229, 1251
         printf("[L3D] #clusterable_segments:  %zu\n[L3D] A: #num_entries = %zu\n[L3D] A: #num_rows    = %zu\n[L3D] %zu 3D lines found!\n",
@@ -1807,6 +1810,167 @@ int l3d_line3d_get_segment2D(const l3d_line3d* h, uint32_t cam, uint32_t seg, fl
     if (it == h->views.end() || seg >= (uint32_t)it->second.S()) return L3D_ERR_INVALID;
     memcpy(out, &it->second.segs[(size_t)seg * 4], 16);
     return L3D_OK;
+}
+
+// ---- the result over the views ("PROJECTION AND OVERLAYS", 3): projected through l3d_project_lines, drawn through l3d_draw_segments, on the object's
+// context (a node object: rank 0's, which holds the result)
+static const unsigned char kDefaultPalette[12 * 4] = { 230, 25, 75, 255, 60, 180, 75, 255, 255, 225, 25, 255, 0, 130, 200, 255, 245, 130, 48, 255, 145, 30, 180, 255,
+                                                       70, 240, 240, 255, 240, 50, 230, 255, 210, 245, 60, 255, 250, 190, 212, 255, 0, 128, 128, 255, 170, 110, 40, 255 };
+const unsigned char* l3d_default_palette(void) { return kDefaultPalette; }
+
+static l3d_camera camera_as_added(const View& v)
+{
+    l3d_camera c;
+    memcpy(c.K, v.K.m, 72);
+    memcpy(c.R, v.R_added.m, 72);
+    c.t[0] = v.t_added.x; c.t[1] = v.t_added.y; c.t[2] = v.t_added.z;
+    c.width = (int32_t)v.width; c.height = (int32_t)v.height;
+    return c;
+}
+
+// owner: the object that holds the result.  The outputs are std::vectors here; the exported call packs them
+static int project_result_core(L* owner, const uint32_t* view_ids, int n_views, const l3d_camera* cameras, int select, double near_z, double margin,
+                               std::vector<float>& seg2d, std::vector<int32_t>& seg_index, std::vector<int32_t>& line_index, std::vector<unsigned char>& flags,
+                               int64_t* cam_start)
+{
+    if (!owner->result_valid) return owner->fail(L3D_ERR_INVALID, "project_result: no result yet (compute3Dmodel first)");
+    if (!owner->ctx) return owner->fail(L3D_ERR_INVALID, "project_result: no device context");
+    if (n_views < 0 || !cam_start) return owner->fail(L3D_ERR_INVALID, "project_result: bad argument");
+    if (select != L3D_SELECT_ALL && select != L3D_SELECT_OBSERVED) return owner->fail(L3D_ERR_INVALID, "project_result: select must be L3D_SELECT_ALL or L3D_SELECT_OBSERVED");
+    if (n_views > 0 && !view_ids && (!cameras || select == L3D_SELECT_OBSERVED)) return owner->fail(L3D_ERR_INVALID, "project_result: view ids are needed (no cameras given, or L3D_SELECT_OBSERVED)");
+    std::vector<l3d_camera> own;
+    if (!cameras) {
+        own.reserve((size_t)n_views);
+        for (int k = 0; k < n_views; ++k) {
+            const View* v = owner->find_view(view_ids[k]);
+            if (!v) return owner->fail(L3D_ERR_INVALID, "project_result: unknown view " + std::to_string(view_ids[k]));
+            own.push_back(camera_as_added(*v));
+        }
+        cameras = own.data();
+    } else if (view_ids)
+        for (int k = 0; k < n_views; ++k)
+            if (!owner->find_view(view_ids[k])) return owner->fail(L3D_ERR_INVALID, "project_result: unknown view " + std::to_string(view_ids[k]));
+    // the result's 3-D segments in l3d_line3d_get_result's order, and the line of each
+    std::vector<double> seg3d;
+    std::vector<int32_t> line_of;
+    for (size_t li = 0; li < owner->result.size(); ++li)
+        for (auto& s : owner->result[li].segs3D) {
+            const double v[6] = { s.first.x, s.first.y, s.first.z, s.second.x, s.second.y, s.second.z };
+            seg3d.insert(seg3d.end(), v, v + 6);
+            line_of.push_back((int32_t)li);
+        }
+    float* o = nullptr; int32_t* src = nullptr; unsigned char* fl = nullptr;
+    std::vector<int64_t> start((size_t)n_views + 1, 0);
+    const int rc = l3d_project_lines(owner->ctx, seg3d.data(), (int)line_of.size(), cameras, n_views, near_z, margin, &o, &src, &fl, start.data());
+    if (rc != L3D_OK) return owner->fail(rc, l3d_last_error(owner->ctx));
+    seg2d.clear(); seg_index.clear(); line_index.clear(); flags.clear();
+    std::vector<char> observed;
+    for (int k = 0; k < n_views; ++k) {
+        cam_start[k] = (int64_t)seg_index.size();
+        if (select == L3D_SELECT_OBSERVED) {                // the lines with a 2-D member in this view
+            observed.assign(owner->result.size(), 0);
+            for (size_t li = 0; li < owner->result.size(); ++li)
+                for (Key key : owner->result[li].segs2D) if (kcam(key) == view_ids[k]) { observed[li] = 1; break; }
+        }
+        for (int64_t i = start[(size_t)k]; i < start[(size_t)k + 1]; ++i) {
+            const int32_t li = line_of[(size_t)src[i]];
+            if (select == L3D_SELECT_OBSERVED && !observed[(size_t)li]) continue;
+            seg2d.insert(seg2d.end(), o + 4 * i, o + 4 * i + 4);
+            seg_index.push_back(src[i]); line_index.push_back(li); flags.push_back(fl[i]);
+        }
+    }
+    cam_start[n_views] = (int64_t)seg_index.size();
+    l3d_free(o); l3d_free(src); l3d_free(fl);
+    return L3D_OK;
+}
+
+int l3d_line3d_project_result(l3d_line3d* h, const uint32_t* view_ids, int n_views, const l3d_camera* cameras, int select, double near_z, double margin,
+                              float** seg2d, int32_t** seg_index, int32_t** line_index, unsigned char** flags, int64_t* cam_start)
+{
+    if (!h) return L3D_ERR_INVALID;
+    if (!seg2d || !seg_index || !line_index || !flags) return h->fail(L3D_ERR_INVALID, "project_result: a null output pointer");
+    *seg2d = nullptr; *seg_index = nullptr; *line_index = nullptr; *flags = nullptr;
+    L* owner = h->node ? rank0(h) : h;
+    std::vector<float> s2; std::vector<int32_t> si, li; std::vector<unsigned char> fl;
+    const int rc = project_result_core(owner, view_ids, n_views, cameras, select, near_z, margin, s2, si, li, fl, cam_start);
+    if (rc != L3D_OK) return owner == h ? rc : h->fail(rc, owner->err);
+    const size_t n = si.size();                         // (one spare element each: an empty result still hands out pointers that l3d_free takes)
+    float* a = static_cast<float*>(malloc((n * 4 + 1) * sizeof(float)));
+    int32_t* b = static_cast<int32_t*>(malloc((n + 1) * sizeof(int32_t)));
+    int32_t* c = static_cast<int32_t*>(malloc((n + 1) * sizeof(int32_t)));
+    unsigned char* d = static_cast<unsigned char*>(malloc(n + 1));
+    if (!a || !b || !c || !d) { free(a); free(b); free(c); free(d); return h->fail(L3D_ERR_NOMEM, "malloc"); }
+    if (n) { memcpy(a, s2.data(), n * 16); memcpy(b, si.data(), n * 4); memcpy(c, li.data(), n * 4); memcpy(d, fl.data(), n); }
+    *seg2d = a; *seg_index = b; *line_index = c; *flags = d;
+    return L3D_OK;
+}
+
+// pixels: the host's (image == nullptr) or a device image's
+static int overlay_run(l3d_line3d* h, uint32_t view_id, unsigned char* pixels, int width, int height, int channels, size_t row_stride, const l3d_device_image* image,
+                       const l3d_overlay_style* style)
+{
+    if (!h) return L3D_ERR_INVALID;
+    L* owner = h->node ? rank0(h) : h;
+    auto refuse = [&](int code, const std::string& m) { if (owner != h) owner->err = m; return h->fail(code, m); };
+    if (!owner->result_valid) return refuse(L3D_ERR_INVALID, "overlay: no result yet (compute3Dmodel first)");
+    if (!owner->ctx) return refuse(L3D_ERR_INVALID, "overlay: no device context");
+    if (!image && !pixels) return refuse(L3D_ERR_INVALID, "overlay: a null pointer");
+    const View* v = owner->find_view(view_id);
+    if (!v) return refuse(L3D_ERR_INVALID, "overlay: unknown view " + std::to_string(view_id));
+    if (image) { width = image->width; height = image->height; }
+    if ((unsigned)width != v->width || (unsigned)height != v->height || width < 1 || height < 1)
+        return refuse(L3D_ERR_INVALID, "overlay: the image is " + std::to_string(width) + " x " + std::to_string(height) + ", the view " + std::to_string(v->width) + " x " + std::to_string(v->height));
+    l3d_overlay_style st;
+    if (style) st = *style;
+    else {
+        memset(&st, 0, sizeof(st));
+        st.layers = L3D_LAYER_MEMBERS | L3D_LAYER_MODEL; st.select = L3D_SELECT_OBSERVED; st.by_line = 1; st.opacity = 255;
+        st.width_members = 1.0; st.width_model = 2.0; st.near_z = 1e-6;
+    }
+    if (st.layers < 0 || st.layers > (L3D_LAYER_MEMBERS | L3D_LAYER_MODEL)) return refuse(L3D_ERR_INVALID, "overlay: unknown layers");
+    const unsigned char* palette = st.palette ? st.palette : kDefaultPalette;
+    const int n_palette = st.palette ? st.n_palette : 12;
+    if (st.by_line && n_palette < 1) return refuse(L3D_ERR_INVALID, "overlay: an empty palette");
+    auto draw = [&](const std::vector<float>& segs, const std::vector<int32_t>& lines, const unsigned char* fixed, double width_px) {
+        std::vector<int32_t> idx;
+        if (st.by_line) { idx.resize(lines.size()); for (size_t k = 0; k < lines.size(); ++k) idx[k] = lines[k] % n_palette; }
+        const unsigned char* colors = st.by_line ? palette : fixed;
+        const int n_colors = st.by_line ? n_palette : 1, n = (int)lines.size();
+        const int rc = image ? l3d_draw_segments_device(owner->ctx, image, segs.data(), n, colors, n_colors, st.by_line ? idx.data() : nullptr, width_px, st.opacity)
+                             : l3d_draw_segments(owner->ctx, pixels, width, height, channels, row_stride, segs.data(), n, colors, n_colors, st.by_line ? idx.data() : nullptr, width_px, st.opacity);
+        return rc == L3D_OK ? rc : refuse(rc, l3d_last_error(owner->ctx));
+    };
+    if (st.layers & L3D_LAYER_MEMBERS) {
+        std::vector<float> segs;
+        std::vector<int32_t> lines;
+        for (size_t li = 0; li < owner->result.size(); ++li)
+            for (Key key : owner->result[li].segs2D)
+                if (kcam(key) == view_id && kseg(key) < (uint32_t)v->S()) {
+                    segs.insert(segs.end(), &v->segs[(size_t)kseg(key) * 4], &v->segs[(size_t)kseg(key) * 4] + 4);
+                    lines.push_back((int32_t)li);
+                }
+        if (int rc = draw(segs, lines, st.color_members, st.width_members)) return rc;
+    }
+    if (st.layers & L3D_LAYER_MODEL) {
+        std::vector<float> segs; std::vector<int32_t> si, lines; std::vector<unsigned char> fl;
+        int64_t start[2];
+        const int rc = project_result_core(owner, &view_id, 1, nullptr, st.select, st.near_z, 34.0, segs, si, lines, fl, start);
+        if (rc != L3D_OK) return owner == h ? rc : h->fail(rc, owner->err);
+        if (int rd = draw(segs, lines, st.color_model, st.width_model)) return rd;
+    }
+    return L3D_OK;
+}
+
+int l3d_line3d_overlay(l3d_line3d* h, uint32_t view_id, unsigned char* pixels, int width, int height, int channels, size_t row_stride, const l3d_overlay_style* style)
+{
+    return overlay_run(h, view_id, pixels, width, height, channels, row_stride, nullptr, style);
+}
+
+int l3d_line3d_overlay_device(l3d_line3d* h, uint32_t view_id, const l3d_device_image* image, const l3d_overlay_style* style)
+{
+    if (!h) return L3D_ERR_INVALID;
+    if (!image) return h->fail(L3D_ERR_INVALID, "overlay: a null pointer");
+    return overlay_run(h, view_id, nullptr, 0, 0, 0, 0, image, style);
 }
 
 // ---- inspection for tests / bench ----------------------------------------------------------------

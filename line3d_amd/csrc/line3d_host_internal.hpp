@@ -48,6 +48,8 @@ struct View {                                   // L3DView, view.h:40-153
     int index = 0;                              // dense index in ascending id order (set in prepare)
     M3 K, R, Kinv, Rt, RtKinv;
     V3 t, C;
+    M3 R_added;                                 // R and t as the view was added: transform_geometry rewrites R and t (l3d_line3d_project_result)
+    V3 t_added;
     double P[12];
     unsigned width = 0, height = 0;
     double pp[2];
@@ -228,6 +230,7 @@ struct l3d_line3d {
     bool A_on_host = true;
     std::vector<Key> local2global;
     std::vector<FinalLine> result;
+    bool result_valid = false;                                 // a finish has produced `result` (which may hold no line) since the last reset
     std::vector<size_t> hyp_begin;                             // per view index: first hypothesis (greedy_selection)
 
     // refinement of the result (l3d_line3d_set_refinement; off by default, reset keeps it) and what the last finish with it on recorded per line

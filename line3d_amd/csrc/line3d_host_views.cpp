@@ -62,6 +62,7 @@ int make_view(L* h, uint32_t id, unsigned width, unsigned height, const float* s
     memcpy(v.K.m, K, 72);
     memcpy(v.R.m, R, 72);
     v.t = { t[0], t[1], t[2] };
+    v.R_added = v.R; v.t_added = v.t;
     v.width = width; v.height = height;
     v.pp[0] = (double)((float)width / 2.0f);        // view.cc:20-21
     v.pp[1] = (double)((float)height / 2.0f);

@@ -383,6 +383,44 @@ class Line3D:
             out.append((seg2, seg3))
         return out
 
+    def project_result(self, view_ids=None, cameras=None, select="all", near=1e-6, margin=0.0):
+        """l3d_line3d_project_result: the result's 3-D segments (getResult's order) projected into views ("PROJECTION AND OVERLAYS", 3) ->
+        (seg2d (k, 4) float32, seg_index (k,) int32 into the flat list of getResult's 3-D segments, line_index (k,) int32, flags (k,) uint8,
+        cam_start (m + 1,) int64), camera-major.  cameras None: each view's own camera as it was added (view_ids needed); else a list of
+        (K, R, t, width, height), and view_ids may be None.  select "observed": only lines with a 2-D member in the view (needs view_ids)."""
+        ids = None if view_ids is None else np.ascontiguousarray(view_ids, np.uint32).reshape(-1)
+        cams = None if cameras is None else capi.cameras(cameras)
+        m = len(ids) if ids is not None else (getattr(cams, "_n", len(cams)) if cams is not None else 0)
+        if ids is not None and cams is not None and getattr(cams, "_n", len(cams)) != m:
+            raise ValueError("project_result: one camera per view id")
+        sel = {"all": capi.SELECT_ALL, "observed": capi.SELECT_OBSERVED}[select.lower()] if isinstance(select, str) else int(select)
+        seg2d, si, li, fl = C.POINTER(C.c_float)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_ubyte)()
+        start = np.zeros(m + 1, np.int64)
+        self._chk(self.lib.l3d_line3d_project_result(self.h, None if ids is None or not len(ids) else _p(ids), C.c_int(m), cams if cams is not None and m else None, C.c_int(sel),
+                                                     C.c_double(near), C.c_double(margin), C.byref(seg2d), C.byref(si), C.byref(li), C.byref(fl), _p(start)))
+        k = int(start[-1])
+        out = (np.ctypeslib.as_array(seg2d, (k * 4,)).copy().reshape(-1, 4) if k else np.zeros((0, 4), np.float32),
+               np.ctypeslib.as_array(si, (k,)).copy() if k else np.zeros(0, np.int32), np.ctypeslib.as_array(li, (k,)).copy() if k else np.zeros(0, np.int32),
+               np.ctypeslib.as_array(fl, (k,)).copy() if k else np.zeros(0, np.uint8), start)
+        for p in (seg2d, si, li, fl):
+            self.lib.l3d_free(p)
+        return out
+
+    def overlay(self, view_id, image, layers=("members", "model"), select="observed", by_line=True, style=None, layout=None, chan=None, **kw):
+        """l3d_line3d_overlay: the view's member segments and the projected result drawn over an image of the view's size ("PROJECTION AND
+        OVERLAYS", 3).  A numpy image gives a NEW array; a device object (a uint8 device tensor or a capi.device_image descriptor; layout, chan
+        as capi.device_image takes them) is drawn in place and returned.  style: a capi.overlay_style(...), or its keywords (opacity=,
+        width_members=, width_model=, near=, color_members=, color_model=, palette=) beside layers, select and by_line."""
+        st = style if style is not None else capi.overlay_style(layers=layers, select=select, by_line=by_line, **kw)
+        if capi.is_device_object(image):
+            d = capi.device_image(image, layout=layout, chan=chan)
+            self._chk(self.lib.l3d_line3d_overlay_device(self.h, C.c_uint32(view_id), C.byref(d), C.byref(st)))
+            return image
+        out = capi._draw_image_copy(image)
+        ptr, w, h, ch, stride = capi.image_arguments(out)
+        self._chk(self.lib.l3d_line3d_overlay(self.h, C.c_uint32(view_id), ptr, C.c_int(w), C.c_int(h), C.c_int(ch), C.c_size_t(stride), C.byref(st)))
+        return out
+
     def getSegment2D(self, camID, segID):
         o = (C.c_float * 4)()
         self.lib.l3d_line3d_get_segment2D(self.h, C.c_uint32(camID), C.c_uint32(segID), o)

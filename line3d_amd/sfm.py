@@ -153,8 +153,36 @@ def reconstruct(scene: SfmScene, segments, image_sizes, out_dir=None, neighbors=
     return l3d
 
 
+def undistorted_for_view(ctx, img, en):
+    """The image of an entry of reconstruct_from_images in its view's grid, as a host array H x W x 3: undistorted as the add undistorts it (k1, k2;
+    a lens; a lens onto a planned size), a grey image repeated over three channels"""
+    if en.get("out_size") is not None:
+        out = ctx.undistort(img, en["K"], lens=en["lens"], out_size=en["out_size"])
+    elif en.get("lens") is not None:
+        out = ctx.undistort(img, en["K"], lens=en["lens"])
+    elif en.get("dist") is not None and any(abs(float(c)) > 1e-12 for c in en["dist"]):
+        out = ctx.undistort(img, en["K"], k1=float(en["dist"][0]), k2=float(en["dist"][1]))
+    else:
+        out = img
+    if capi.is_device_object(out):
+        out = out.cpu().numpy() if hasattr(out, "cpu") else out
+    out = np.asarray(out, np.uint8)
+    return np.ascontiguousarray(np.repeat(out[:, :, None], 3, axis=2) if out.ndim == 2 else out[:, :, :3])
+
+
+def write_ppm(path, image):
+    """A uint8 image H x W x 3 as a binary P6 file"""
+    image = np.ascontiguousarray(image, np.uint8)
+    if image.ndim != 3 or image.shape[2] != 3:
+        raise ValueError("write_ppm takes an H x W x 3 uint8 image")
+    with open(path, "wb") as f:
+        f.write(b"P6\n%d %d\n255\n" % (image.shape[1], image.shape[0]))
+        f.write(image.tobytes())
+
+
 def reconstruct_from_images(scene: SfmScene, load_image, data_directory, out_dir=None, neighbors=10, diffusion=False, max_width=1920,
-                            load_and_store_segments=True, device=0, batch=16, refine=False, alpha=None, out_size=None, covisibility="host", **line3d_kwargs):
+                            load_and_store_segments=True, device=0, batch=16, refine=False, alpha=None, out_size=None, covisibility="host", overlay_dir=None,
+                            **line3d_kwargs):
     """The drivers' flow (main_vsfm.cpp:226-325) from pixels: per camera the image load_image(i, name) returns -- `bytes`: the contents of a
     baseline JPEG file, decoded on the device (Line3D.add_image_jpeg); or a uint8 array H x W or H x W x 3, decoded by the caller; or an image
     in device memory (a torch device tensor, a capi.device_image descriptor), read where it lies --, K from the focal length and the image size, the image undistorted with the camera's coefficients and its
@@ -167,7 +195,10 @@ def reconstruct_from_images(scene: SfmScene, load_image, data_directory, out_dir
     alpha, out_size (either given; "A REMAP" in include/line3d_amd.h): a camera with an active lens -- a COLMAP camera's, or an NVM / bundler camera's
     k1, k2 as a BROWN lens -- is PLANNED (capi.undistort_plan(lens, size, alpha or 0, out_size), once per distinct camera) and the view is added
     with the planned K and size, the blank pixels of the resampling invalid for the detector.  Neither given: what it did before.
-    covisibility: as in reconstruct."""
+    covisibility: as in reconstruct.
+    overlay_dir: after compute3Dmodel every view's image is loaded once more, undistorted into the view's grid (Context.undistort with the entry's
+    coefficients, lens or planned size) and written with the view's overlay (Line3D.overlay: its member segments and the projected lines it
+    observes) as overlay_<imageID>.ppm, binary P6, into this directory."""
     import os
     from .pipeline import Line3D
     l3d = Line3D(data_directory, matchingNeighbors=neighbors, device=device, **line3d_kwargs)
@@ -176,6 +207,7 @@ def reconstruct_from_images(scene: SfmScene, load_image, data_directory, out_dir
     if covisibility != "host":
         l3d.set_covisibility(covisibility)
     entries = []
+    added = []              # overlay_dir: what undistorts an entry's image into its view's grid
     planned = {}            # (lens, source size) -> (K, size): one plan per distinct camera
 
     def flush():
@@ -227,11 +259,28 @@ def reconstruct_from_images(scene: SfmScene, load_image, data_directory, out_dir
                 en.pop("dist", None)
                 en["lens"], en["K"], en["out_size"] = lens, planned[key][0], planned[key][1]
         entries.append(en)
+        if overlay_dir is not None:
+            added.append({k: en.get(k) for k in ("imageID", "K", "dist", "lens", "out_size")})
         if len(entries) >= batch:
             flush()
     if entries:
         flush()
     l3d.compute3Dmodel(diffusion)
+    if overlay_dir is not None:
+        os.makedirs(overlay_dir, exist_ok=True)
+        from .capi import L3DError
+        ctx = l3d.context()
+        for i, (cam, en) in enumerate(zip(scene.cameras, added)):
+            try:
+                l3d.project_result([en["imageID"]], select="observed")
+            except L3DError as e:                       # (an image in which nothing was detected is no view)
+                if "unknown view" in str(e):
+                    continue
+                raise
+            img = load_image(i, cam["name"])
+            if isinstance(img, (bytes, bytearray, memoryview)):
+                img = l3d.decode_jpeg(bytes(img))
+            write_ppm(os.path.join(overlay_dir, "overlay_%d.ppm" % en["imageID"]), l3d.overlay(en["imageID"], undistorted_for_view(ctx, img, en)))
     if out_dir is not None:
         os.makedirs(out_dir, exist_ok=True)
         base = os.path.join(out_dir, result_basename(max_width=max_width, neighbors=neighbors, diffusion=diffusion))
