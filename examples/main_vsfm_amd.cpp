@@ -2,8 +2,10 @@
 // segment caches of an earlier Line3D run standing in for the images, or with the images as binary PPM / PGM files or baseline JPEG files (no
 // OpenCV, no tclap, no boost):
 //
-//   main_vsfm_amd [--refine] [--device-covisibility] [--overlays <folder>] <scene.nvm | bundle.rd.out> <data directory> [neighbors=10] [diffusion=0] [output folder=<data directory>] [image folder]
+//   main_vsfm_amd [--merge] [--refine] [--device-covisibility] [--overlays <folder>] <scene.nvm | bundle.rd.out> <data directory> [neighbors=10] [diffusion=0] [output folder=<data directory>] [image folder]
 //
+// --merge (anywhere on the line): the near-copies of a 3-D line -- an edge seen along a camera path longer than the matching neighbourhood comes out
+// several times -- are merged on the GPU before the result is refined and written (setMerging, defaults; the counts are printed).
 // --refine (anywhere on the line): the 3-D lines are refined against the 2-D segments of their clusters before they are written (setRefinement: the
 // reference has no such step; its successor Line3D++ added one) -- the segments of a line in the STL / TXT files are then collinear.
 // --device-covisibility (anywhere on the line): the cameras' world point lists are counted on the GPU when compute3Dmodel starts, instead of one
@@ -148,19 +150,20 @@ struct Vec3 { const double* p; double operator()(int i) const { return p[i]; } }
 
 int main(int argc, char** argv)
 {
-    bool refine = false, device_covis = false;
+    bool refine = false, device_covis = false, merge = false;
     std::string overlay_dir;
     {
         int k = 1;
         for (int i = 1; i < argc; ++i) {
             if (std::string(argv[i]) == "--refine") refine = true;
+            else if (std::string(argv[i]) == "--merge") merge = true;
             else if (std::string(argv[i]) == "--device-covisibility") device_covis = true;
             else if (std::string(argv[i]) == "--overlays" && i + 1 < argc) overlay_dir = argv[++i];
             else argv[k++] = argv[i];
         }
         argc = k;
     }
-    if (argc < 3) { fprintf(stderr, "usage: %s [--refine] [--device-covisibility] [--overlays <folder>] <scene.nvm | bundle.rd.out> <data directory> [neighbors=10] [diffusion=0] [output folder] [image folder]\n", argv[0]); return 2; }
+    if (argc < 3) { fprintf(stderr, "usage: %s [--merge] [--refine] [--device-covisibility] [--overlays <folder>] <scene.nvm | bundle.rd.out> <data directory> [neighbors=10] [diffusion=0] [output folder] [image folder]\n", argv[0]); return 2; }
     const std::string nvm = argv[1], data_dir = argv[2];
     const int neighbors = argc > 3 ? atoi(argv[3]) : 10;
     const bool diffusion = argc > 4 && atoi(argv[4]) != 0;
@@ -179,6 +182,7 @@ int main(int argc, char** argv)
     // Line3D(data_directory, matchingNeighbors, ...) with the driver's defaults (main_vsfm.cpp:60-99)
     L3D::Line3D line3D(data_dir, neighbors, 5.0f, 1.0f, 3.5f, 10.0f, 0.25f, true, true);
     if (!line3D.valid()) { l3d_sfm_free(scene); return 1; }
+    if (merge) line3D.setMerging(true);
     if (refine) line3D.setRefinement(true);
     if (device_covis) line3D.setDeviceCovisibility(true);
     int added = 0;
@@ -231,6 +235,10 @@ int main(int argc, char** argv)
     std::list<L3D::L3DFinalLine3D> result;
     line3D.getResult(result);
     fprintf(stderr, "[L3D] %zu 3-D lines\n", result.size());
+    L3D::MergeStats ms;
+    if (merge && line3D.getMerging(ms))
+        fprintf(stderr, "[L3D] merging: %d -> %d lines in %d rounds (%d pairs in the first, %d groups merged, %d lines released)\n", ms.linesBefore, ms.linesAfter,
+                ms.rounds, ms.pairsFirstRound, ms.groupsMerged, ms.linesReleased);
 
     // the driver's output name (main_vsfm.cpp:289-313), numbers in stream-default formatting
     std::stringstream name;

@@ -102,6 +102,14 @@ private:
     std::list<L3DSegment2D> segments2D_;
 };
 
+// What the merging of duplicate lines did in the last compute3Dmodel (Line3D::getMerging; l3d_line3d_get_merging)
+struct MergeStats {
+    int linesBefore = 0, linesAfter = 0;
+    int rounds = 0;                 // rounds in which the search ran (the one that found no pair included)
+    int pairsFirstRound = 0;
+    int groupsMerged = 0, linesReleased = 0, emptyRefits = 0;       // summed over the rounds
+};
+
 class Line3D {
 public:
     // line3D.h:61-66 (data_directory: where addImage keeps its segment caches, line3D.cc:143-150)
@@ -638,6 +646,28 @@ public:
         std::vector<int32_t> st((size_t)nl);
         if (l3d_line3d_get_refinement(h_, rb.data(), ra.data(), nullptr, st.data()) != L3D_OK) return false;
         rmsBefore = rb; rmsAfter = ra; status.assign(st.begin(), st.end());
+        return true;
+    }
+    // Merging of duplicate lines (no counterpart in the reference; l3d_line3d_set_merging, "MERGING DUPLICATE LINES" in line3d_amd.h): with it on,
+    // compute3Dmodel groups the near-copies of a 3-D line (ends within distPx pixel footprints of the longer line's axis, directions within angleDeg,
+    // a gap along the axis of at most maxGap times the shorter length), refits every group from all of its 2-D segments and repeats, maxRounds times at
+    // the most, before the refinement.  Off by default; reset() keeps the setting.
+    void setMerging(bool on = true, double distPx = 4.0, double angleDeg = 5.0, double maxGap = 0.0, int maxRounds = 3)
+    {
+        report(l3d_line3d_set_merging(h_, on ? 1 : 0, distPx, angleDeg, maxGap, maxRounds));
+    }
+    // finalIndex (optional): one entry per line BEFORE merging, its index in getResult(); nSources (optional): one per line of getResult(), the lines it
+    // was made of.  false when the last compute3Dmodel ran without the merging.
+    bool getMerging(MergeStats& stats, std::vector<int>* finalIndex = nullptr, std::vector<int>* nSources = nullptr)
+    {
+        int32_t c[8];
+        if (l3d_line3d_get_merging(h_, c, nullptr, nullptr) != L3D_OK) return false;
+        stats.linesBefore = c[0]; stats.linesAfter = c[1]; stats.rounds = c[2]; stats.pairsFirstRound = c[3];
+        stats.groupsMerged = c[4]; stats.linesReleased = c[5]; stats.emptyRefits = c[6];
+        std::vector<int32_t> fi((size_t)c[0] + 1), ns((size_t)c[1] + 1);
+        if (l3d_line3d_get_merging(h_, c, fi.data(), ns.data()) != L3D_OK) return false;
+        if (finalIndex) finalIndex->assign(fi.begin(), fi.begin() + c[0]);
+        if (nSources) nSources->assign(ns.begin(), ns.begin() + c[1]);
         return true;
     }
     // Where addImage's world point links are filed (no counterpart in the reference; l3d_line3d_set_covisibility): false, the default, on the host as every

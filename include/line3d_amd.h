@@ -667,6 +667,25 @@ int l3d_line3d_finish(l3d_line3d* h, int perform_diffusion);   /* optimizeLocalM
  * the option. */
 int l3d_line3d_set_refinement(l3d_line3d* h, int on, int max_iterations, double huber_px);
 int l3d_line3d_get_refinement(const l3d_line3d* h, double* rms_before, double* rms_after, int32_t* iterations, int32_t* status);
+/* Merging of the result's duplicate lines ("MERGING DUPLICATE LINES", l3d_merge_lines), off by default: with it on, finish / compute3Dmodel run rounds of
+ * it between the line fit and the refinement.  Per round:
+ *   1. a line's P is the start of its first 3-D segment, Q the end of its last; tol = dist_px x sigma, sigma the mean over the line's 2-D members in their
+ *      stored order (a sequential sum, then one division) of z / f: z = R[2] . M + t[2] at M = (P + Q) / 2, f = (|K00| + |K11|) / 2, R, t, K of the
+ *      member's view as it was added.  Members with z <= 0 or a term that is not finite are skipped; none left: tol = 0
+ *   2. l3d_merge_lines with cos_min = cos(angle_deg pi / 180) (computed once, on the host, in double) and max_gap
+ *   3. every group of two or more lines is refitted from the union of its members in key order (camera, segment) by the fit path that built the result
+ *      (l3d_fit_clusters on the resident hypothesis table, or the host fit).  A refit that emits no 3-D segment leaves the group's lines as they were
+ *      (counted); otherwise the merged line takes the position of its lowest-index line and the others are removed; nothing else changes its order
+ *   4. rounds until one finds no pair, or max_rounds of them
+ * The refinement, if on, then runs on the merged list, and l3d_line3d_get_refinement has one entry per merged line.  reset keeps the setting.  A node
+ * object merges on rank 0's context; on a sharded finish every rank that has the option set runs it on the same list and ends with the same bytes.
+ *   get_merging   counts[8] = lines before, lines after, rounds in which the search ran (the one that found no pair included), pairs of round 1,
+ *                 groups merged, lines released by the star rule, refits that emitted nothing (the last three summed over the rounds), 0;
+ *                 final_index (may be NULL): one per line BEFORE merging, its index in the result; n_sources (may be NULL): one per line of the result,
+ *                 the lines before merging it was made of.  L3D_ERR_INVALID after a finish without the option.
+ * REFUSED by set_merging, L3D_ERR_INVALID: dist_px or max_gap negative or not finite, angle_deg outside [0, 90], max_rounds below 1. */
+int l3d_line3d_set_merging(l3d_line3d* h, int on, double dist_px, double angle_deg, double max_gap, int max_rounds);
+int l3d_line3d_get_merging(const l3d_line3d* h, int32_t* counts /* 8 */, int32_t* final_index, int32_t* n_sources);
 /* inspection (tests): what a refinement of the current result is fed with, in the normalised frame -- counts[3] = lines, members, cameras; then (any may be
  * NULL; sizes from a first call) group_start (lines + 1), member_cam, member_seg (4 each), member_pts (6 each), cameras (12 each, views in ascending id), and
  * Line3D::inverseTransform (line3D.cc:1782-1786) as transform[13] = Rinv (9, row-major), scale_inv, tneg (3): X = Rinv (P scale_inv + tneg). */
@@ -1582,6 +1601,37 @@ int l3d_line3d_project_result(l3d_line3d* h, const uint32_t* view_ids, int n_vie
                               float** seg2d, int32_t** seg_index, int32_t** line_index, unsigned char** flags, int64_t* cam_start /* n_views + 1 */);
 int l3d_line3d_overlay(l3d_line3d* h, uint32_t view_id, unsigned char* pixels, int width, int height, int channels, size_t row_stride, const l3d_overlay_style* style);
 int l3d_line3d_overlay_device(l3d_line3d* h, uint32_t view_id, const l3d_device_image* image, const l3d_overlay_style* style);
+
+/* =================================================================================================
+ * MERGING DUPLICATE LINES (no counterpart in the reference; formulas: line3d_amd/csrc/l3d_merge.hpp, numpy model: tests/merge_model.py).  A 3-D line is a
+ * cluster of 2-D segments linked through matches between NEIGHBOURING views, so an edge seen along a camera path longer than the matching neighbourhood
+ * comes out as several near-copies.  l3d_merge_lines finds them: an all-pairs test on the device, the components of the pair graph, and a star rule.
+ * Everything is f64; every product, sum and quotient is rounded once, in the written order; x . y = ((x0 y0) + (x1 y1)) + (x2 y2).
+ *
+ * A LINE OF THE TABLE   P, Q (lines[6 k ..]: 3 + 3 doubles), L = sqrt((Q - P) . (Q - P)), d = (Q - P) / L, and a tolerance tol[k] >= 0 in scene units.
+ *                       ELIGIBLE iff the seven numbers and L are finite and L > 0.
+ * THE PAIR TEST         for eligible i < j, a = the longer line (larger L; at equal L the lower index), b = the other.  All three must hold:
+ *                       1. |d_a . d_b| >= cos_min
+ *                       2. for X in {P_b, Q_b}: v = X - P_a, s = v . d_a, r = v - s d_a, e = sqrt(r . r); e_P <= max(tol_a, tol_b) and e_Q <= the same
+ *                       3. min(max(s_P, s_Q), L_a) - max(min(s_P, s_Q), 0) >= -(max_gap L_b)
+ * GROUPING              the connected components of the pair graph; a component's REPRESENTATIVE is its longest line (at equal L the lowest index); a
+ *                       line STAYS iff it is the representative or passes the pair test against it (the star rule: no chain A ~ B ~ C with A unlike C,
+ *                       so an arc of short segments never collapses into one line); every other line is RELEASED as a group of one.
+ *                       group[k] = the lowest index among the staying lines of k's component, or k (released, not eligible, no pair).
+ * OUTPUTS               group[n]; pairs: callee-allocated (l3d_free) int32 (i, j), ascending by (i, j) under any schedule, *n_pairs of them;
+ *                       counts[4] = eligible lines, components with a pair, lines released, groups of two or more lines.
+ *   l3d_merge_lines             the device: three launches find the pairs whatever n is (count, scan, write)
+ *   l3d_test_merge_lines_host   the same functions in loops on the host, no device needed, bit-equal.  l3d_merge_last_error (per thread)
+ * REFUSED, L3D_ERR_INVALID, before any launch: n < 0; a NULL array with n > 0 or a NULL output; cos_min outside [0, 1] or not a number; max_gap
+ *   negative or not finite; a negative or NaN tol.  L3D_ERR_UNSUPPORTED: more than 2^31 - 1 pairs (no allocation is attempted), or a pair list the
+ *   device cannot hold.  n == 0: empty outputs, L3D_OK.
+ * ================================================================================================= */
+typedef struct l3d_merge_params { double cos_min, max_gap; } l3d_merge_params;
+int l3d_merge_lines(l3d_ctx* ctx, const double* lines /* 6 n: P, Q */, const double* tol /* n */, int n, const l3d_merge_params* params, int32_t* group /* n */,
+                    int32_t** pairs, int* n_pairs, int32_t* counts /* 4 */);
+int l3d_test_merge_lines_host(const double* lines, const double* tol, int n, const l3d_merge_params* params, int32_t* group, int32_t** pairs, int* n_pairs,
+                              int32_t* counts);
+const char* l3d_merge_last_error(void);
 
 /* The detector's stages on their own, exported for tests (tests/test_gpu_detect_stages.py): the same kernels with the same launch shapes
  * as l3d_detect_segments, results copied to caller-allocated arrays.  (N, M) = (ceil(0.8 new_width), ceil(0.8 new_height)) is the scaled image.

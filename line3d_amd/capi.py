@@ -509,6 +509,56 @@ def project_lines_host(seg3d, cams, near=1e-6, margin=0.0):
     return segs, idx, fl, start
 
 
+class MergeParams(C.Structure):
+    """l3d_merge_params (include/line3d_amd.h)"""
+    _fields_ = [("cos_min", C.c_double), ("max_gap", C.c_double)]
+
+
+def merge_params(cos_min=None, max_gap=0.0, angle_deg=5.0):
+    """An l3d_merge_params.  cos_min None: cos(angle_deg pi / 180), in double"""
+    import math
+    p = MergeParams()
+    p.cos_min = math.cos(angle_deg * math.pi / 180.0) if cos_min is None else float(cos_min)
+    p.max_gap = float(max_gap)
+    return p
+
+
+def _merge_call(fn, head, lines, tol, prm):
+    """the argument list the merge calls share (head: the context, or nothing) -> (rc, dict(group (n,) int32, pairs (k, 2) int32, counts (4,) int32)).
+    lines / tol None: passed as NULL with the count in `lines` (an int), for the refusals"""
+    if lines is None or isinstance(lines, int):
+        n, lp, tp = int(lines or 0), None, (None if tol is None else _p(np.ascontiguousarray(tol, np.float64)))
+    else:
+        lines = np.ascontiguousarray(lines, np.float64).reshape(-1, 6)
+        n, lp = len(lines), (_p(lines) if len(lines) else None)
+        tol = None if tol is None else np.ascontiguousarray(tol, np.float64).reshape(-1)
+        if tol is not None and len(tol) != n:
+            raise ValueError("merge lines: one tolerance per line")
+        tp = None if tol is None or n == 0 else _p(tol)
+    group = np.zeros(max(1, n), np.int32)
+    counts = np.zeros(4, np.int32)
+    pairs, k = C.POINTER(C.c_int32)(), C.c_int(0)
+    rc = fn(*head, lp, tp, C.c_int(n), None if prm is None else C.byref(prm), _p(group), C.byref(pairs), C.byref(k), _p(counts))
+    if rc != 0:
+        return rc, None
+    pr = np.ctypeslib.as_array(pairs, (k.value * 2,)).copy().reshape(-1, 2) if k.value else np.zeros((0, 2), np.int32)
+    load_library().l3d_free(pairs)
+    return 0, dict(group=group[:max(0, n)].copy(), pairs=pr, counts=counts)
+
+
+def merge_lines_host(lines, tol, cos_min=None, max_gap=0.0, params=None):
+    """l3d_test_merge_lines_host: the grouping of duplicate 3-D lines on the host -- no context, no device.  Arguments and result as
+    Context.merge_lines.  A refusal raises L3DError carrying the status in .code."""
+    lib = load_library()
+    lib.l3d_merge_last_error.restype = C.c_char_p
+    rc, out = _merge_call(lib.l3d_test_merge_lines_host, (), lines, tol, merge_params(cos_min, max_gap) if params is None else params)
+    if rc != 0:
+        e = L3DError("line3d_amd error %d: %s" % (rc, lib.l3d_merge_last_error().decode()))
+        e.code = rc
+        raise e
+    return out
+
+
 SELECT_ALL, SELECT_OBSERVED = 0, 1
 LAYER_MEMBERS, LAYER_MODEL = 1, 2
 
@@ -1871,6 +1921,14 @@ class Context:
             rc, segs, idx, fl, start = _project_call(self.lib.l3d_project_lines, (self.h,), _p(s) if len(s) else None, len(s), arr if m else None, m, near, margin)
         self._chk(rc)
         return segs, idx, fl, start
+
+    def merge_lines(self, lines, tol, cos_min=None, max_gap=0.0, params=None):
+        """l3d_merge_lines: duplicate 3-D lines grouped on the device ("MERGING DUPLICATE LINES").  lines (n, 6) float64 (P then Q), tol (n,) float64
+        in scene units; cos_min None: cos(5 degrees) -> dict(group (n,) int32: the lowest index of the line's group, pairs (k, 2) int32 ascending
+        by (i, j), counts (4,) int32: eligible lines, components with a pair, lines released, groups of two or more)."""
+        rc, out = _merge_call(self.lib.l3d_merge_lines, (self.h,), lines, tol, merge_params(cos_min, max_gap) if params is None else params)
+        self._chk(rc)
+        return out
 
     def draw_segments(self, image, segments, colors, color_index=None, width_px=1.0, opacity=255, layout=None, chan=None):
         """l3d_draw_segments: segments (n, 4) float32 in the image's grid drawn over 8-bit pixels ("PROJECTION AND OVERLAYS").  colors: (n_colors, 4)

@@ -9,6 +9,7 @@
 // list (978 k entries) took; the device sorts take well under a millisecond.
 #include "l3d_sort.hpp"
 
+#include "l3d_cc.hpp"
 #include "l3d_ctx.hpp"
 #include "l3d_geometry.hpp"
 
@@ -154,7 +155,7 @@ __global__ void k_edge_weight_keys(const l3d_edge* __restrict__ E, int nnz, unsi
     key[k] = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
     val[k] = (unsigned)k;
 }
-// ---- connected components of the edge list (labels = smallest node id of the component): Felzenszwalb-Huttenlocher never looks
+// ---- connected components of the edge list (labels = smallest node id of the component; declared in l3d_cc.hpp): Felzenszwalb-Huttenlocher never looks
 // across components, so each one can be segmented on its own (l3d_clustering_edges_grouped).  Hooking by atomicMin on the roots +
 // full path compression, repeated until a hooking round changes nothing.
 __global__ void k_cc_init(int* __restrict__ comp, int n)

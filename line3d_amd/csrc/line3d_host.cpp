@@ -678,6 +678,7 @@ int l3d_line3d_reset(l3d_line3d* h)
     h->worldpoints2views.clear(); h->visual_neighbors.clear(); h->fundamentals.clear(); h->matched.clear();
     h->pot.clear(); h->pot_foreign.clear(); h->hyps.clear(); h->best_idx.clear(); h->A.clear(); h->n_edges = 0; h->A_on_host = true; h->local2global.clear(); h->result.clear();
     h->refine_valid = false;                               // (the setting itself stays)
+    h->merge_valid = false;                                // (the setting itself stays)
     h->result_valid = false;
     h->covis_ids.clear(); h->covis_views.clear(); h->covis_start.assign(1, 0); h->covis_dirty = false; h->covis_path = 0;      // (covis_mode stays)
     h->computation = false; h->prepared = false;
@@ -1338,6 +1339,8 @@ int l3d_line3d_finish(l3d_line3d* h, int perform_diffusion)
     h->result_valid = false;
     int rc = cluster_segments_2D(h, perform_diffusion != 0);
     h->refine_valid = false;
+    h->merge_valid = false;
+    if (!rc && h->merge_on) rc = merge_result(h);
     if (!rc && h->refine_on) rc = refine_result(h);
     h->result_valid = rc == L3D_OK;
     if (hopt(h).timing) fprintf(stderr, "[l3d finish] %-28s %8.2f ms\n", "total", (now_s() - t0) * 1e3);
@@ -1353,6 +1356,28 @@ int l3d_line3d_set_refinement(l3d_line3d* h, int on, int max_iterations, double 
     if (max_iterations < 0 || !(huber_px >= 0.0) || huber_px - huber_px != 0.0) return h->fail(L3D_ERR_INVALID, "set_refinement: max_iterations and huber_px must not be negative");
     if (h->node) return l3d_line3d_set_refinement(rank0(h), on, max_iterations, huber_px);
     h->refine_on = on != 0; h->refine_max_iterations = max_iterations; h->refine_huber_px = huber_px;
+    return L3D_OK;
+}
+// the merging of the result's duplicate lines (merge_result, line3d_host_finish.cpp).  A node object merges on rank 0, which holds the result
+int l3d_line3d_set_merging(l3d_line3d* h, int on, double dist_px, double angle_deg, double max_gap, int max_rounds)
+{
+    if (!h) return L3D_ERR_INVALID;
+    const auto finite_nonneg = [](double x) { return x >= 0.0 && x - x == 0.0; };
+    if (!finite_nonneg(dist_px) || !finite_nonneg(max_gap) || !(angle_deg >= 0.0 && angle_deg <= 90.0) || max_rounds < 1)
+        return h->fail(L3D_ERR_INVALID, "set_merging: dist_px and max_gap must be finite and not negative, angle_deg in [0, 90], max_rounds at least 1");
+    if (h->node) return l3d_line3d_set_merging(rank0(h), on, dist_px, angle_deg, max_gap, max_rounds);
+    h->merge_on = on != 0; h->merge_dist_px = dist_px; h->merge_angle_deg = angle_deg; h->merge_max_gap = max_gap; h->merge_max_rounds = max_rounds;
+    return L3D_OK;
+}
+int l3d_line3d_get_merging(const l3d_line3d* h, int32_t* counts, int32_t* final_index, int32_t* n_sources)
+{
+    if (!h) return L3D_ERR_INVALID;
+    if (h->node) return l3d_line3d_get_merging(rank0(h), counts, final_index, n_sources);
+    if (!h->merge_valid || !h->result_valid || h->merge_n_sources.size() != h->result.size())
+        return const_cast<L*>(h)->fail(L3D_ERR_INVALID, "get_merging: the last finish ran without the merging");
+    if (counts) memcpy(counts, h->merge_counts, sizeof(h->merge_counts));
+    if (final_index && !h->merge_final_index.empty()) memcpy(final_index, h->merge_final_index.data(), h->merge_final_index.size() * 4);
+    if (n_sources && !h->merge_n_sources.empty()) memcpy(n_sources, h->merge_n_sources.data(), h->merge_n_sources.size() * 4);
     return L3D_OK;
 }
 // where the world point links are filed ("CO-VISIBILITY"): 0 on the host as each view is added, 1 by prepare() on the device.  A node object: every rank

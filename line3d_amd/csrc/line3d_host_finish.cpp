@@ -593,6 +593,7 @@ int cluster_segments_2D(L* h, bool perform_diff)
                                                  tneg, &gstart, &memb, &n_groups, &cnt, &segs, &n_segs);
         if (rc) return h->fail(rc, std::string("line fit: ") + l3d_last_error(h->ctx));
         lap("  fit: grouping + fits (device)");
+        h->fit_on_device = true;
         std::vector<size_t> soff((size_t)n_groups + 1, 0);
         for (int v = 0; v < n_groups; ++v) soff[(size_t)v + 1] = soff[(size_t)v] + (size_t)cnt[v];
         std::vector<FinalLine> fitted((size_t)n_groups);
@@ -630,6 +631,7 @@ int cluster_segments_2D(L* h, bool perform_diff)
     for (int l = 0; l < n_nodes; ++l) if (lstart[(size_t)l + 1] - lstart[(size_t)l] >= 4) groups.push_back(l);
     std::vector<FinalLine> fitted(groups.size());
     lap("  fit: clusters by label");
+    h->fit_on_device = false;
     if (resident_list && (int)h->node_hyp.size() == n_nodes) {
         // ---- the fits on the device (l3d_fit_clusters): members as hypothesis indices in key order (= ascending index)
         std::vector<int32_t> memb_tmp((size_t)n_nodes);
@@ -664,6 +666,7 @@ int cluster_segments_2D(L* h, bool perform_diff)
                                         h->transf_Rinv.m, h->transf_scale_inv, tneg, &cnt, &segs, &n_segs);
         if (rc) return h->fail(rc, std::string("line fit: ") + l3d_last_error(h->ctx));
         lap("  fit: device");
+        h->fit_on_device = true;
         std::vector<size_t> soff(gof.size() + 1, 0);
         for (size_t v = 0; v < gof.size(); ++v) soff[v + 1] = soff[v] + (size_t)cnt[v];
         parallel_slices(gof.size(), finish_threads(), [&](size_t v0, size_t v1, unsigned) {
@@ -793,6 +796,150 @@ int refine_result(L* h)
     l3d_free(cnt); l3d_free(segs);
     h->refine_valid = true;
     if (hopt(h).timing) fprintf(stderr, "[l3d finish] %-28s %8.2f ms (%zu lines, %zu members)\n", "refinement", (now_s() - t0) * 1e3, nl, nm);
+    return L3D_OK;
+}
+
+// The duplicate lines of the result merged ("MERGING DUPLICATE LINES" in include/line3d_amd.h, on the object), after whichever fit path built the list and
+// before the refinement.  Per round: a line's P is the start of its first 3-D segment, Q the end of its last, its tolerance dist_px times the mean of
+// z / f over its members' views as they were added; l3d_merge_lines groups the lines; every group of two or more is refitted from the union of its
+// members, in key order, by the fit path that built the result, takes the position of its lowest-index line and removes the others -- unless the
+// refit emits nothing: then the group's lines stay as they were.  Rounds until one finds no pair, or max_rounds.
+int merge_result(L* h)
+{
+    h->merge_valid = false;
+    h->merge_final_index.clear(); h->merge_n_sources.clear();
+    int32_t* mc = h->merge_counts;
+    for (int k = 0; k < 8; ++k) mc[k] = 0;
+    const double t0 = now_s();
+    double t_lap = t0, t_table = 0.0, t_search = 0.0, t_members = 0.0, t_refit = 0.0, t_list = 0.0;
+    const auto lap = [&t_lap](double& acc) { const double t = now_s(); acc += t - t_lap; t_lap = t; };
+    const size_t n0 = h->result.size();
+    mc[0] = (int32_t)n0;
+    std::vector<std::vector<int32_t>> sources(n0);                              // per current line: the lines before merging it was made of
+    for (size_t k = 0; k < n0; ++k) sources[k].push_back((int32_t)k);
+    l3d_merge_params prm;
+    prm.cos_min = std::cos(h->merge_angle_deg * 3.14159265358979323846 / 180.0);
+    prm.max_gap = h->merge_max_gap;
+    for (int round = 0; round < h->merge_max_rounds && !h->result.empty(); ++round) {
+        const size_t n = h->result.size();
+        std::vector<double> lines(6 * n), tol(n);
+        std::atomic<int> bad{ 0 };
+        parallel_slices(n, finish_threads(), [&](size_t l0, size_t l1, unsigned) {
+            for (size_t l = l0; l < l1; ++l) {
+                const FinalLine& fl = h->result[l];
+                const V3 P = fl.segs3D.front().first, Q = fl.segs3D.back().second;
+                double* q = &lines[6 * l];
+                q[0] = P.x; q[1] = P.y; q[2] = P.z; q[3] = Q.x; q[4] = Q.y; q[5] = Q.z;
+                const double M[3] = { (P.x + Q.x) / 2.0, (P.y + Q.y) / 2.0, (P.z + Q.z) / 2.0 };
+                double sum = 0.0;
+                int cnt = 0;
+                for (Key k : fl.segs2D) {
+                    auto vt = h->views.find(kcam(k));
+                    if (vt == h->views.end()) { bad.store(1, std::memory_order_relaxed); break; }
+                    const View& v = vt->second;
+                    const double z = ((v.R_added(2, 0) * M[0] + v.R_added(2, 1) * M[1]) + v.R_added(2, 2) * M[2]) + v.t_added.z;
+                    const double f = (std::fabs(v.K(0, 0)) + std::fabs(v.K(1, 1))) / 2.0;
+                    const double r = z / f;
+                    if (!(z > 0.0) || !(std::fabs(r) <= 1.7976931348623157e308)) continue;
+                    sum = sum + r; ++cnt;
+                }
+                tol[l] = cnt ? h->merge_dist_px * (sum / (double)cnt) : 0.0;
+                if (!(tol[l] >= 0.0)) tol[l] = 0.0;                               // (dist_px 0 times an overflowed mean)
+            }
+        });
+        if (bad.load()) return h->fail(L3D_ERR_INVALID, "merging: a 2-D segment of the result has no view");
+        lap(t_table);
+        std::vector<int32_t> group(n);
+        int32_t* pairs = nullptr; int n_pairs = 0; int32_t c4[4];
+        const int rc = l3d_merge_lines(h->ctx, lines.data(), tol.data(), (int)n, &prm, group.data(), &pairs, &n_pairs, c4);
+        if (rc) return h->fail(rc, std::string("merging: ") + l3d_last_error(h->ctx));
+        l3d_free(pairs);
+        lap(t_search);
+        mc[2] = round + 1;
+        if (round == 0) mc[3] = n_pairs;
+        mc[5] += c4[2];
+        if (n_pairs == 0) break;
+        // ---- the groups of two or more, in the order of their lowest index: members in key order
+        std::vector<int32_t> size(n, 0), gslot(n, -1);
+        for (size_t k = 0; k < n; ++k) ++size[(size_t)group[k]];
+        std::vector<size_t> gof;                                                // position of every group handed to the refit
+        for (size_t k = 0; k < n; ++k) if (size[k] >= 2) { gslot[k] = (int32_t)gof.size(); gof.push_back(k); }
+        std::vector<std::vector<Key>> keys(gof.size());
+        for (size_t k = 0; k < n; ++k) if (gslot[(size_t)group[k]] >= 0) { auto& d = keys[(size_t)gslot[(size_t)group[k]]]; d.insert(d.end(), h->result[k].segs2D.begin(), h->result[k].segs2D.end()); }
+        for (auto& d : keys) std::sort(d.begin(), d.end());
+        std::vector<std::vector<std::pair<V3, V3>>> fitted(gof.size());
+        lap(t_members);
+        if (h->fit_on_device) {
+            std::vector<int32_t> gstart(1, 0), memb;
+            for (auto& d : keys) {
+                for (Key k : d) {
+                    auto hy = std::lower_bound(h->hyps.begin(), h->hyps.end(), k, [](const Hyp& a, Key b) { return a.src < b; });
+                    if (hy == h->hyps.end() || hy->src != k) return h->fail(L3D_ERR_INVALID, "merging: a 2-D segment of the result has no hypothesis");
+                    memb.push_back((int32_t)(hy - h->hyps.begin()));
+                }
+                gstart.push_back((int32_t)memb.size());
+            }
+            int32_t* cnt = nullptr; double* segs = nullptr; int n_segs = 0;
+            const double tneg[3] = { h->transf_tneg.x, h->transf_tneg.y, h->transf_tneg.z };
+            const int rf = l3d_fit_clusters(h->ctx, gstart.data(), (int)gof.size(), memb.data(), nullptr, h->aff.hyp_cam.data(), (int)h->hyps.size(), h->transf_Rinv.m,
+                                            h->transf_scale_inv, tneg, &cnt, &segs, &n_segs);
+            if (rf) return h->fail(rf, std::string("merging: line fit: ") + l3d_last_error(h->ctx));
+            size_t at = 0;
+            for (size_t g = 0; g < gof.size(); ++g)
+                for (int k = 0; k < cnt[g]; ++k, ++at) { const double* q = segs + 6 * at; fitted[g].emplace_back(V3{ q[0], q[1], q[2] }, V3{ q[3], q[4], q[5] }); }
+            l3d_free(cnt); l3d_free(segs);
+        } else {
+            parallel_slices(gof.size(), finish_threads(), [&](size_t g0, size_t g1, unsigned) {
+                std::vector<std::pair<Key, std::pair<V3, V3>>> t3;
+                for (size_t g = g0; g < g1; ++g) {
+                    t3.clear();
+                    for (Key k : keys[g]) {
+                        const int bb = best_of(h, k);
+                        if (bb < 0) continue;
+                        t3.push_back({ k, { inverse_transform(h, h->hyps[(size_t)bb].P1), inverse_transform(h, h->hyps[(size_t)bb].P2) } });
+                    }
+                    align_cluster(t3, fitted[g]);
+                }
+            });
+        }
+        lap(t_refit);
+        // ---- the new list: a merged line at the position of its lowest-index line, everything else in its order
+        std::vector<FinalLine> out;
+        std::vector<std::vector<int32_t>> out_src;
+        out.reserve(n); out_src.reserve(n);
+        std::vector<char> emitted(gof.size());
+        for (size_t g = 0; g < gof.size(); ++g) emitted[g] = !fitted[g].empty();
+        std::vector<std::vector<int32_t>> gsrc(gof.size());                     // per group: the lines before merging of all its lines
+        for (size_t k = 0; k < n; ++k) { const int32_t s = gslot[(size_t)group[k]]; if (s >= 0 && emitted[(size_t)s]) gsrc[(size_t)s].insert(gsrc[(size_t)s].end(), sources[k].begin(), sources[k].end()); }
+        for (size_t k = 0; k < n; ++k) {
+            const int32_t s = gslot[(size_t)group[k]];
+            if (s >= 0 && emitted[(size_t)s]) {
+                if ((size_t)group[k] != k) continue;                            // merged into the line at position group[k]
+                FinalLine fl;
+                fl.segs2D = std::move(keys[(size_t)s]);
+                fl.segs3D = std::move(fitted[(size_t)s]);
+                std::sort(gsrc[(size_t)s].begin(), gsrc[(size_t)s].end());
+                out.push_back(std::move(fl)); out_src.push_back(std::move(gsrc[(size_t)s]));
+                ++mc[4];
+                continue;
+            }
+            if (s >= 0 && (size_t)group[k] == k) ++mc[6];                       // the refit emitted nothing: the group's lines stay as they were
+            out.push_back(std::move(h->result[k])); out_src.push_back(std::move(sources[k]));
+        }
+        h->result.swap(out); sources.swap(out_src);
+        lap(t_list);
+    }
+    mc[1] = (int32_t)h->result.size();
+    h->merge_final_index.assign(n0, 0);
+    h->merge_n_sources.resize(h->result.size());
+    for (size_t k = 0; k < sources.size(); ++k) {
+        h->merge_n_sources[k] = (int32_t)sources[k].size();
+        for (int32_t s : sources[k]) h->merge_final_index[(size_t)s] = (int32_t)k;
+    }
+    h->merge_valid = true;
+    if (hopt(h).timing)
+        fprintf(stderr, "[l3d finish] %-28s %8.2f ms (%d -> %d lines, %d rounds; table %.2f, search %.2f, member lists %.2f, refit %.2f, new list %.2f ms)\n", "merging",
+                (now_s() - t0) * 1e3, mc[0], mc[1], mc[2], t_table * 1e3, t_search * 1e3, t_members * 1e3, t_refit * 1e3, t_list * 1e3);
     return L3D_OK;
 }
 

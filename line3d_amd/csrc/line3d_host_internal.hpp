@@ -240,6 +240,14 @@ struct l3d_line3d {
     std::vector<double> ref_rms_before, ref_rms_after;
     std::vector<int32_t> ref_iterations, ref_status;
 
+    // merging of duplicate lines (l3d_line3d_set_merging; off by default, reset keeps it) and what the last finish with it on recorded
+    bool merge_on = false, merge_valid = false;
+    double merge_dist_px = 4.0, merge_angle_deg = 5.0, merge_max_gap = 0.0;
+    int merge_max_rounds = 3;
+    int32_t merge_counts[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+    std::vector<int32_t> merge_final_index, merge_n_sources;
+    bool fit_on_device = false;                                // the last line fit ran on the resident hypothesis table (l3d_fit_clusters / l3d_fit_labelled_clusters)
+
     // co-visibility counted on the device (l3d_line3d_set_covisibility; 0 by default, reset keeps the setting): the views' world point lists in add
     // order, 4 bytes per observation, counted by prepare() when a list arrived since the last count
     int covis_mode = 0;
@@ -383,5 +391,7 @@ void destroy_finalizer(L* h);                       // joins the finaliser's wor
 struct RefineInput { std::vector<int32_t> gstart, mcam; std::vector<float> mseg; std::vector<double> mpts, cameras; };
 int refine_input(L* h, RefineInput& in);
 int refine_result(L* h);
+// the result's duplicate lines merged (l3d_merge_lines, then a refit of every group by the fit path that built the result): before refine_result
+int merge_result(L* h);
 
 }  // namespace l3dh

@@ -449,6 +449,26 @@ class Line3D:
         self._chk(self.lib.l3d_line3d_get_refinement(self.h, _p(rb), _p(ra), _p(it), _p(st)))
         return {"rms_before": rb, "rms_after": ra, "iterations": it, "status": st}
 
+    # -- merging of the result's duplicate lines (no counterpart in the reference) -------------------------------------------
+    def set_merging(self, on=True, dist_px=4.0, angle_deg=5.0, max_gap=0.0, max_rounds=3):
+        """l3d_line3d_set_merging: with it on, finish / compute3Dmodel group the near-copies of a 3-D line on the device (capi.Context.merge_lines: ends
+        within dist_px pixel footprints of the longer line's axis, directions within angle_deg, a gap of at most max_gap times the shorter length),
+        refit every group from all of its 2-D segments and repeat, max_rounds times at the most, before the refinement; off by default; reset keeps it."""
+        self._chk(self.lib.l3d_line3d_set_merging(self.h, C.c_int(int(bool(on))), C.c_double(float(dist_px)), C.c_double(float(angle_deg)), C.c_double(float(max_gap)),
+                                                  C.c_int(int(max_rounds))))
+
+    def merging(self):
+        """l3d_line3d_get_merging: dict of lines_before, lines_after, rounds, pairs_first_round, groups_merged, lines_released, empty_refits, final_index
+        (one per line before merging: its index in getResult()) and n_sources (one per line of getResult())."""
+        cnt = np.zeros(8, np.int32)
+        self._chk(self.lib.l3d_line3d_get_merging(self.h, _p(cnt), None, None))
+        fi, ns = np.zeros(max(1, int(cnt[0])), np.int32), np.zeros(max(1, int(cnt[1])), np.int32)
+        self._chk(self.lib.l3d_line3d_get_merging(self.h, _p(cnt), _p(fi), _p(ns)))
+        keys = ("lines_before", "lines_after", "rounds", "pairs_first_round", "groups_merged", "lines_released", "empty_refits")
+        out = {k: int(cnt[i]) for i, k in enumerate(keys)}
+        out["final_index"], out["n_sources"] = fi[:int(cnt[0])].copy(), ns[:int(cnt[1])].copy()
+        return out
+
     def refinement_input(self):
         """l3d_line3d_refinement_input (inspection): what a refinement of the current result is fed with -- dict of group_start, member_cam, member_seg,
         member_pts, cameras (normalised frame) and Rinv (3, 3), scale_inv, tneg (3,) of Line3D::inverseTransform."""
