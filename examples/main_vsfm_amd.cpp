@@ -2,12 +2,15 @@
 // segment caches of an earlier Line3D run standing in for the images, or with the images as binary PPM / PGM files or baseline JPEG files (no
 // OpenCV, no tclap, no boost):
 //
-//   main_vsfm_amd [--merge] [--refine] [--device-covisibility] [--overlays <folder>] <scene.nvm | bundle.rd.out> <data directory> [neighbors=10] [diffusion=0] [output folder=<data directory>] [image folder]
+//   main_vsfm_amd [--merge] [--refine] [--support] [--device-covisibility] [--overlays <folder>] <scene.nvm | bundle.rd.out> <data directory> [neighbors=10] [diffusion=0] [output folder=<data directory>] [image folder]
 //
 // --merge (anywhere on the line): the near-copies of a 3-D line -- an edge seen along a camera path longer than the matching neighbourhood comes out
 // several times -- are merged on the GPU before the result is refined and written (setMerging, defaults; the counts are printed).
 // --refine (anywhere on the line): the 3-D lines are refined against the 2-D segments of their clusters before they are written (setRefinement: the
 // reference has no such step; its successor Line3D++ added one) -- the segments of a line in the STL / TXT files are then collinear.
+// --support (anywhere on the line): as the last step of compute3Dmodel every line's 2-D segments are extended by the segments of ALL views that lie on
+// its projection (setSupport, defaults: 3 px, 5 degrees, half the shorter segment) -- a line otherwise lists only the views its cluster reached through
+// matches between neighbouring views; the TXT file and the overlays then show the added observations (the counts are printed).
 // --device-covisibility (anywhere on the line): the cameras' world point lists are counted on the GPU when compute3Dmodel starts, instead of one
 // observation at a time as the images are added (setDeviceCovisibility: the same neighbours, the same lines; it pays on models of many images).
 // --overlays <folder> (anywhere on the line): after compute3Dmodel every view's image -- loaded once more and undistorted as it was added; a grey canvas
@@ -150,20 +153,21 @@ struct Vec3 { const double* p; double operator()(int i) const { return p[i]; } }
 
 int main(int argc, char** argv)
 {
-    bool refine = false, device_covis = false, merge = false;
+    bool refine = false, device_covis = false, merge = false, support = false;
     std::string overlay_dir;
     {
         int k = 1;
         for (int i = 1; i < argc; ++i) {
             if (std::string(argv[i]) == "--refine") refine = true;
             else if (std::string(argv[i]) == "--merge") merge = true;
+            else if (std::string(argv[i]) == "--support") support = true;
             else if (std::string(argv[i]) == "--device-covisibility") device_covis = true;
             else if (std::string(argv[i]) == "--overlays" && i + 1 < argc) overlay_dir = argv[++i];
             else argv[k++] = argv[i];
         }
         argc = k;
     }
-    if (argc < 3) { fprintf(stderr, "usage: %s [--merge] [--refine] [--device-covisibility] [--overlays <folder>] <scene.nvm | bundle.rd.out> <data directory> [neighbors=10] [diffusion=0] [output folder] [image folder]\n", argv[0]); return 2; }
+    if (argc < 3) { fprintf(stderr, "usage: %s [--merge] [--refine] [--support] [--device-covisibility] [--overlays <folder>] <scene.nvm | bundle.rd.out> <data directory> [neighbors=10] [diffusion=0] [output folder] [image folder]\n", argv[0]); return 2; }
     const std::string nvm = argv[1], data_dir = argv[2];
     const int neighbors = argc > 3 ? atoi(argv[3]) : 10;
     const bool diffusion = argc > 4 && atoi(argv[4]) != 0;
@@ -184,6 +188,7 @@ int main(int argc, char** argv)
     if (!line3D.valid()) { l3d_sfm_free(scene); return 1; }
     if (merge) line3D.setMerging(true);
     if (refine) line3D.setRefinement(true);
+    if (support) line3D.setSupport(true);
     if (device_covis) line3D.setDeviceCovisibility(true);
     int added = 0;
     std::vector<OverlayJob> jobs;
@@ -239,6 +244,13 @@ int main(int argc, char** argv)
     if (merge && line3D.getMerging(ms))
         fprintf(stderr, "[L3D] merging: %d -> %d lines in %d rounds (%d pairs in the first, %d groups merged, %d lines released)\n", ms.linesBefore, ms.linesAfter,
                 ms.rounds, ms.pairsFirstRound, ms.groupsMerged, ms.linesReleased);
+    L3D::SupportStats ss;
+    if (support && line3D.getSupport(ss)) {
+        long long before = 0, added_members = 0;
+        for (size_t k = 0; k < ss.membersBefore.size(); ++k) { before += ss.membersBefore[k]; added_members += ss.membersAdded[k]; }
+        fprintf(stderr, "[L3D] support: %lld observations of the lines in all views, %lld of %lld members found again, %lld 2-D segments added to the lines\n", ss.records,
+                ss.membersFound, before, added_members);
+    }
 
     // the driver's output name (main_vsfm.cpp:289-313), numbers in stream-default formatting
     std::stringstream name;

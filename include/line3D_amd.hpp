@@ -10,6 +10,7 @@
 #pragma once
 
 #include <array>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <iostream>
@@ -108,6 +109,26 @@ struct MergeStats {
     int rounds = 0;                 // rounds in which the search ran (the one that found no pair included)
     int pairsFirstRound = 0;
     int groupsMerged = 0, linesReleased = 0, emptyRefits = 0;       // summed over the rounds
+};
+
+// The parameters of the support search (Line3D::gatherSupport; l3d_support_params): a 2-D segment supports a 3-D segment's projection when both of
+// its ends lie within distPx of it, the directions within angleDeg, and they overlap by at least minOverlap of the shorter one
+struct SupportParams {
+    double distPx = 3.0, angleDeg = 5.0, minOverlap = 0.5, nearZ = 1e-6;
+    double margin = -1.0;           // pixels around the image within which a projection is kept; negative: distPx
+};
+// One observation of a line (l3d_line_support): segment `seg` of view `viewID` lies on 3-D segment `seg3D` (index into the flat list of getResult's 3-D
+// segments) of the line
+struct LineSupport {
+    unsigned int viewID = 0, seg = 0;
+    int seg3D = 0;
+    float dist = 0.0f, overlap = 0.0f;
+    bool member = false, memberElsewhere = false, best = false;
+};
+// What the support did in the last compute3Dmodel (Line3D::getSupport; l3d_line3d_get_support)
+struct SupportStats {
+    long long records = 0, membersFound = 0, membersNotFound = 0, segmentsUnclaimed = 0;
+    std::vector<int> membersBefore, membersAdded, viewsBefore, viewsAfter;       // one per line of getResult()
 };
 
 class Line3D {
@@ -668,6 +689,54 @@ public:
         if (l3d_line3d_get_merging(h_, c, fi.data(), ns.data()) != L3D_OK) return false;
         if (finalIndex) finalIndex->assign(fi.begin(), fi.begin() + c[0]);
         if (nSources) nSources->assign(ns.begin(), ns.begin() + c[1]);
+        return true;
+    }
+    // Support of the result's lines over ALL views (no counterpart in the reference; "SUPPORT OF 3-D LINES" in line3d_amd.h).  gatherSupport, valid behind
+    // compute3Dmodel: per line of getResult() the 2-D segments of every view that lie on it, ordered by (view id, segment).  false: refused
+    bool gatherSupport(std::vector<std::vector<LineSupport> >& perLine, const SupportParams& params = SupportParams())
+    {
+        perLine.clear();
+        int nl = 0;
+        if (l3d_line3d_result_sizes(h_, &nl, nullptr, nullptr) != L3D_OK) return false;
+        l3d_support_params p;
+        p.dist_px = params.distPx; p.cos_min = std::cos(params.angleDeg * 3.14159265358979323846 / 180.0); p.min_overlap = params.minOverlap;
+        p.near_z = params.nearZ; p.margin = params.margin < 0.0 ? params.distPx : params.margin;
+        l3d_line_support* rec = nullptr;
+        std::vector<int64_t> start((size_t)nl + 1);
+        int64_t counts[4];
+        if (l3d_line3d_gather_support(h_, &p, &rec, start.data(), nullptr, counts) != L3D_OK) return false;
+        perLine.resize((size_t)nl);
+        for (int k = 0; k < nl; ++k)
+            for (int64_t r = start[(size_t)k]; r < start[(size_t)k + 1]; ++r) {
+                LineSupport o;
+                o.viewID = rec[r].view_id; o.seg = rec[r].seg; o.seg3D = rec[r].seg3d; o.dist = rec[r].dist; o.overlap = rec[r].overlap;
+                o.member = (rec[r].flags & L3D_SUPPORT_MEMBER) != 0; o.memberElsewhere = (rec[r].flags & L3D_SUPPORT_MEMBER_ELSEWHERE) != 0;
+                o.best = (rec[r].flags & L3D_SUPPORT_BEST) != 0;
+                perLine[(size_t)k].push_back(o);
+            }
+        l3d_free(rec);
+        return true;
+    }
+    // With it on, compute3Dmodel ends with the gather -- after the line fit, the merging and the refinement -- and appends to every line's 2-D segments
+    // the segments of all views for which it holds the best row and that are members of no line.  Off by default; reset() keeps the setting.
+    void setSupport(bool on = true, double distPx = 3.0, double angleDeg = 5.0, double minOverlap = 0.5)
+    {
+        report(l3d_line3d_set_support(h_, on ? 1 : 0, distPx, angleDeg, minOverlap));
+    }
+    // false when the last compute3Dmodel ran without the support
+    bool getSupport(SupportStats& stats)
+    {
+        int nl = 0;
+        int64_t c[4];
+        if (l3d_line3d_result_sizes(h_, &nl, nullptr, nullptr) != L3D_OK) return false;
+        std::vector<int32_t> per((size_t)nl * 4 + 4);
+        if (l3d_line3d_get_support(h_, c, per.data()) != L3D_OK) return false;
+        stats.records = c[0]; stats.membersFound = c[1]; stats.membersNotFound = c[2]; stats.segmentsUnclaimed = c[3];
+        stats.membersBefore.resize((size_t)nl); stats.membersAdded.resize((size_t)nl); stats.viewsBefore.resize((size_t)nl); stats.viewsAfter.resize((size_t)nl);
+        for (int k = 0; k < nl; ++k) {
+            stats.membersBefore[(size_t)k] = per[(size_t)k * 4]; stats.membersAdded[(size_t)k] = per[(size_t)k * 4 + 1];
+            stats.viewsBefore[(size_t)k] = per[(size_t)k * 4 + 2]; stats.viewsAfter[(size_t)k] = per[(size_t)k * 4 + 3];
+        }
         return true;
     }
     // Where addImage's world point links are filed (no counterpart in the reference; l3d_line3d_set_covisibility): false, the default, on the host as every

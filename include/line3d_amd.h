@@ -1633,6 +1633,105 @@ int l3d_test_merge_lines_host(const double* lines, const double* tol, int n, con
                               int32_t* counts);
 const char* l3d_merge_last_error(void);
 
+/* =================================================================================================
+ * SUPPORT OF 3-D LINES (no counterpart in the reference; formulas: line3d_amd/csrc/l3d_support.hpp, numpy model: tests/support_model.py).  A 3-D line
+ * knows only the 2-D segments of its cluster, and clusters are linked through matches between NEIGHBOURING views, so a line lists a small part of the
+ * views that see it.  l3d_support_lines answers "which 2-D segments of which cameras lie on this 3-D segment": every 3-D segment is projected into every
+ * camera and tested against every 2-D segment of that camera.  All arithmetic is f64; every product, sum, quotient and square root is rounded on its own,
+ * in the written order (nothing fused); integers are int64.  max(x, y) is (x < y ? y : x) and min(x, y) is (y < x ? y : x); a comparison with a NaN
+ * is false, so a condition written "must hold" fails on a NaN.
+ *
+ * INPUTS    seg3d: n x 6 f64, P then Q.  cameras: m l3d_camera.  seg2d: 4 f32 (x1, y1, x2, y2) per 2-D segment, the segments of camera c at
+ *           [seg_start[c], seg_start[c + 1]) (seg_start: m + 1 int64, ascending from 0); j below is a segment's index WITHIN its camera.
+ *           params: dist_px >= 0, cos_min in [0, 1], min_overlap in [0, 1], and near_z, margin as l3d_project_lines takes them.
+ * A ROW (camera c, 3-D segment k).  ONE (camera, segment) PAIR of "PROJECTION AND OVERLAYS", 1, unchanged through THE RECTANGLE RULE, with near_z and
+ *           margin; a pair dropped there has no row.  The ends stay in f64 and are not rounded to f32: A = (uP + t0 du, vP + t0 dv), exactly (uP, vP)
+ *           where t0 == 0; B = (uP + t1 du, vP + t1 dv), exactly (uQ, vQ) where t1 == 1.  a = B - A, La = sqrt((ax ax) + (ay ay)); no row unless La is
+ *           finite and > 0.  da = a / La (two quotients).
+ * A COLUMN (2-D segment j of camera c).  U = (x1, y1), V = (x2, y2) widened to f64; b = V - U, Lb = sqrt((bx bx) + (by by)); ELIGIBLE iff the four
+ *           numbers and Lb are finite and Lb > 0.  db = b / Lb.
+ * THE PAIR TEST of a row and an eligible column of the same camera.  All three must hold:
+ *           1. |(dax dbx) + (day dby)| >= cos_min
+ *           2. for X in {U, V}: w = X - A, e = |(wx day) - (wy dax)|, s = (wx dax) + (wy day); eU <= dist_px and eV <= dist_px
+ *           3. ov = min(max(sU, sV), La) - max(min(sU, sV), 0) and Lm = min(La, Lb); ov >= min_overlap Lm
+ * A RECORD  l3d_support_record, 16 bytes, for every pair that passes: seg3d = k, seg2d = j, dist = (float)max(eU, eV), overlap = (float)(ov / Lm).
+ * ORDER     camera-major; within a camera ascending k; within k ascending j -- under any schedule.
+ * BEST ROW  best[seg_start[c] + j] = the k of the record with the smallest (dist as f32, k) among camera c's records for j; -1 where there is none.
+ * OUTPUTS   records: callee-allocated (l3d_free; one spare record); cam_start (m + 1 int64, the caller's): camera c's records are
+ *           [cam_start[c], cam_start[c + 1]); best (int32, seg_start[m] of them, the caller's); counts[4] (int64) = rows, eligible columns, records,
+ *           columns with a best row.
+ * REFUSED before anything is launched, L3D_ERR_INVALID, in this order: a NULL records, cam_start or counts; n or m < 0; a NULL seg3d with n > 0 or
+ *           cameras with m > 0; with m > 0 a NULL seg_start, seg_start[0] != 0, a seg_start that descends, a camera with more than 2^31 - 1 segments,
+ *           a NULL seg2d or best with seg_start[m] > 0; NULL params; dist_px negative, not finite or NaN; cos_min or min_overlap outside [0, 1] or NaN;
+ *           what l3d_project_lines refuses: a camera whose K third row is not exactly (0, 0, 1) or whose size is below 1 x 1, near_z not in
+ *           (0, 1.7976931348623157e308], margin not in [0, 2^30]; for l3d_support_lines_device an array whose memory kind or extent fails the check an
+ *           l3d_device_image gets, a seg3d not aligned to 8 bytes or a seg2d not aligned to 4.  L3D_ERR_UNSUPPORTED: n > 2^30 (before any launch); a
+ *           single camera that alone yields more than 2^31 - 1 records (decided from the count pass's 64-bit totals, before the record list is
+ *           allocated), or a record list the device cannot hold.  n == 0 or m == 0: nothing is launched; no records, cam_start and counts all 0, best all -1,
+ *           L3D_OK.
+ * THE KERNELS.  k_sup_prepare builds the column table of all cameras once (64 bytes a column: U, V, db, Lb and the eligibility).  The search is count /
+ *           scan / write over chunks of cameras: 256 threads per workgroup, a lane owns one (camera, 3-D segment) row, the camera is the grid's y
+ *           dimension, so a wave never spans two cameras.  A lane projects its row, then walks the camera's columns, staged in LDS tiles of 256 (every
+ *           lane reads the same entry: a broadcast).  The tiles of a camera are cut into contiguous chunks along the grid's z dimension when the rows
+ *           alone cannot fill the device.  k_sup_count counts per (camera, row, column chunk) and sums every camera's records in 64 bits; k_sup_scan
+ *           (one workgroup, l3d_scan.hpp) turns the counts into positions; k_sup_write runs the same functions again and files each lane's records in
+ *           ascending j.  There is no floating-point atomic anywhere and the order comes from the scan.  Three launches per chunk whatever n and the
+ *           segment counts are (profile names sup_count, sup_scan, sup_write); sup_prepare and sup_best run once per call.  A chunk is L3D_SUP_CHUNK
+ *           cameras (0: 64), cut down so that rows x cameras x column chunks stays within 2^30 (the scan's length) and, after its count pass, to the
+ *           leading cameras whose records together stay within 2^31 - 1 (the others are counted again with the next chunk); never below one camera.
+ *           Sixteen guard slots behind the record list are filled before every write pass and checked after it.  The record list of the whole call
+ *           stays on the device until k_sup_best has run over it: a 64-bit integer atomicMin on (bits of dist << 32) | k per column -- a non-negative
+ *           float's bits order as its value -- so best does not depend on the schedule either.
+ *   l3d_support_lines              seg3d and seg2d in host memory
+ *   l3d_support_lines_device       both in device memory, read in place (the caller has synchronised whatever wrote them); everything else host memory
+ *   l3d_test_support_lines_host    the same arguments without the context: the same functions in loops, no device.  l3d_support_last_error (per thread)
+ *
+ * ON THE OBJECT.  The 3-D segments of the current result (l3d_line3d_get_result's order; world coordinates) against the 2-D segments of EVERY view, each
+ *           view's camera as it was added (K, R, t and size), views in ascending id; one l3d_support_lines call on the object's context (a node object:
+ *           rank 0's, which holds the result).
+ *   l3d_line3d_gather_support   valid after a finish, like l3d_line3d_project_result.  params NULL: 3 px, cos(5 degrees), overlap 0.5, near 1e-6, margin 3
+ *                               (= dist_px).  One l3d_line_support (24 bytes) per (LINE, view, segment): view_id, seg (the segment's index in its
+ *                               view), seg3d (index into l3d_line3d_get_result's seg3d array), dist, overlap, flags.  A (view, segment) that several 3-D
+ *                               segments of one line reach is reported once, with the smallest (dist as f32, seg3d).  flags bit 0: the segment is a
+ *                               member of this line; bit 1: it is a member of another line; bit 2: this line holds the segment's best row (BEST ROW
+ *                               above, over all 3-D segments of the result).  Records are ordered by (line, view id, segment); records:
+ *                               callee-allocated (l3d_free; one spare record); line_start (lines + 1 int64, the caller's) delimits each line's records;
+ *                               line_views (2 per line, int32, may be NULL): the views with a member, the views with a record; counts[4] (int64):
+ *                               records; members found again (records with bit 0); members not found; segments that lie on a line (have a record) and
+ *                               are members of none.
+ *   l3d_line3d_set_support      off by default; reset keeps the setting, like l3d_line3d_set_merging and l3d_line3d_set_refinement.  With it on, finish /
+ *                               compute3Dmodel end with the gather -- after the line fit, the merging and the refinement, as the last step -- with
+ *                               dist_px, cos(angle_deg pi / 180) (computed once, on the host, in double), min_overlap, near 1e-6 and margin dist_px, and
+ *                               EXTEND the member lists: a record joins its line's 2-D segments iff it has bit 2 set and neither bit 0 nor bit 1, so a
+ *                               2-D segment stays in at most one line.  New members are appended behind the old ones in (view id, segment) order; the 3-D
+ *                               segments are untouched.  l3d_line3d_get_result, the TXT writer, L3D_SELECT_OBSERVED and the overlay's members layer then
+ *                               see the added observations.  With it off nothing is launched and the result is what it was.
+ *   l3d_line3d_get_support      what the last finish recorded: counts[4] as above (before the lists were extended) and per line (4 int32 each): original
+ *                               members, members added, views with a member before, views with a member after.  Either may be NULL.
+ *   REFUSED, L3D_ERR_INVALID: gather_support before a finish has produced a result, with a NULL records, line_start or counts, and what
+ *   l3d_support_lines refuses, with its codes; set_support with dist_px negative or not finite, angle_deg outside [0, 90], min_overlap outside [0, 1];
+ *   get_support when the last finish ran without the support.
+ *
+ * OUT OF SCOPE: refinement over the extended members (the refinement runs before the gather, over the members of the line fit); hidden-line reasoning (a segment behind a wall still supports); a spatial index over the
+ * columns; a variant whose outputs stay on the device; more than one device.
+ * ================================================================================================= */
+typedef struct l3d_support_params { double dist_px, cos_min, min_overlap, near_z, margin; } l3d_support_params;
+typedef struct l3d_support_record { int32_t seg3d, seg2d; float dist, overlap; } l3d_support_record;
+int l3d_support_lines(l3d_ctx* ctx, const double* seg3d, int n, const l3d_camera* cameras, int m, const float* seg2d, const int64_t* seg_start /* m + 1 */,
+                      const l3d_support_params* params, l3d_support_record** records, int64_t* cam_start /* m + 1 */, int32_t* best /* seg_start[m] */,
+                      int64_t* counts /* 4 */);
+int l3d_support_lines_device(l3d_ctx* ctx, const double* seg3d, int n, const l3d_camera* cameras, int m, const float* seg2d, const int64_t* seg_start,
+                             const l3d_support_params* params, l3d_support_record** records, int64_t* cam_start, int32_t* best, int64_t* counts);
+int l3d_test_support_lines_host(const double* seg3d, int n, const l3d_camera* cameras, int m, const float* seg2d, const int64_t* seg_start,
+                                const l3d_support_params* params, l3d_support_record** records, int64_t* cam_start, int32_t* best, int64_t* counts);
+const char* l3d_support_last_error(void);
+typedef struct l3d_line_support { uint32_t view_id, seg; int32_t seg3d; float dist, overlap; uint32_t flags; } l3d_line_support;
+enum { L3D_SUPPORT_MEMBER = 1, L3D_SUPPORT_MEMBER_ELSEWHERE = 2, L3D_SUPPORT_BEST = 4 };
+int l3d_line3d_gather_support(l3d_line3d* h, const l3d_support_params* params, l3d_line_support** records, int64_t* line_start /* lines + 1 */,
+                              int32_t* line_views /* 2 lines, or NULL */, int64_t* counts /* 4 */);
+int l3d_line3d_set_support(l3d_line3d* h, int on, double dist_px, double angle_deg, double min_overlap);
+int l3d_line3d_get_support(const l3d_line3d* h, int64_t* counts /* 4 */, int32_t* per_line /* 4 lines */);
+
 /* The detector's stages on their own, exported for tests (tests/test_gpu_detect_stages.py): the same kernels with the same launch shapes
  * as l3d_detect_segments, results copied to caller-allocated arrays.  (N, M) = (ceil(0.8 new_width), ceil(0.8 new_height)) is the scaled image.
  *   pixel stage   grey[new_width x new_height] after rescale + grey; img / mod / ang [N x M]: the Gaussian sampler's output, the 2x2 gradient's

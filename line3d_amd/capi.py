@@ -559,6 +559,83 @@ def merge_lines_host(lines, tol, cos_min=None, max_gap=0.0, params=None):
     return out
 
 
+class SupportParams(C.Structure):
+    """l3d_support_params (include/line3d_amd.h)"""
+    _fields_ = [("dist_px", C.c_double), ("cos_min", C.c_double), ("min_overlap", C.c_double), ("near_z", C.c_double), ("margin", C.c_double)]
+
+
+class SupportRecord(C.Structure):
+    """l3d_support_record: 16 bytes"""
+    _fields_ = [("seg3d", C.c_int32), ("seg2d", C.c_int32), ("dist", C.c_float), ("overlap", C.c_float)]
+
+
+class LineSupport(C.Structure):
+    """l3d_line_support: 24 bytes"""
+    _fields_ = [("view_id", C.c_uint32), ("seg", C.c_uint32), ("seg3d", C.c_int32), ("dist", C.c_float), ("overlap", C.c_float), ("flags", C.c_uint32)]
+
+
+LINE_SUPPORT = np.dtype([("view_id", np.uint32), ("seg", np.uint32), ("seg3d", np.int32), ("dist", np.float32), ("overlap", np.float32), ("flags", np.uint32)])
+SUPPORT_MEMBER, SUPPORT_MEMBER_ELSEWHERE, SUPPORT_BEST = 1, 2, 4
+SUPPORT_RECORD = np.dtype([("seg3d", np.int32), ("seg2d", np.int32), ("dist", np.float32), ("overlap", np.float32)])
+
+
+def support_params(dist_px=3.0, cos_min=None, min_overlap=0.5, near_z=1e-6, margin=None, angle_deg=5.0):
+    """An l3d_support_params.  cos_min None: cos(angle_deg pi / 180), in double; margin None: dist_px"""
+    import math
+    p = SupportParams()
+    p.dist_px = float(dist_px)
+    p.cos_min = math.cos(angle_deg * math.pi / 180.0) if cos_min is None else float(cos_min)
+    p.min_overlap = float(min_overlap)
+    p.near_z = float(near_z)
+    p.margin = float(dist_px) if margin is None else float(margin)
+    return p
+
+
+def support_columns(segments_per_camera):
+    """a list of (k, 4) float32 arrays, one per camera -> (all of them one after the other (T, 4), seg_start (m + 1,) int64)"""
+    per = [np.ascontiguousarray(s, np.float32).reshape(-1, 4) for s in segments_per_camera]
+    start = np.zeros(len(per) + 1, np.int64)
+    if per:
+        start[1:] = np.cumsum([len(s) for s in per])
+    return (np.concatenate(per) if per else np.zeros((0, 4), np.float32)), start
+
+
+def _support_call(fn, head, seg_ptr, n, cams, m, seg2d_ptr, start, prm):
+    """the argument list the support calls share (head: the context, or nothing) -> (rc, dict(records: SUPPORT_RECORD array, cam_start (m + 1,) int64,
+    best (seg_start[m],) int32, counts (4,) int64: rows, eligible columns, records, columns with a best row))"""
+    rec = C.POINTER(SupportRecord)()
+    cam_start = np.zeros(max(0, m) + 1, np.int64)
+    T = int(start[-1]) if start is not None and len(start) and m > 0 else 0
+    best = np.zeros(max(1, T), np.int32)
+    counts = np.zeros(4, np.int64)
+    rc = fn(*head, seg_ptr, C.c_int(n), cams, C.c_int(m), seg2d_ptr, None if start is None else _p(start), None if prm is None else C.byref(prm),
+            C.byref(rec), _p(cam_start), _p(best), _p(counts))
+    if rc != 0:
+        return rc, None
+    k = int(counts[2])
+    records = np.frombuffer(C.string_at(rec, k * 16), SUPPORT_RECORD).copy() if k else np.zeros(0, SUPPORT_RECORD)
+    load_library().l3d_free(rec)
+    return 0, dict(records=records, cam_start=cam_start, best=best[:max(0, T)].copy(), counts=counts)
+
+
+def support_lines_host(seg3d, cams, segments_per_camera, params=None):
+    """l3d_test_support_lines_host: the support search on the host -- no context, no device.  Arguments and result as Context.support_lines (host arrays
+    only).  A refusal raises L3DError carrying the status in .code."""
+    lib = load_library()
+    lib.l3d_support_last_error.restype = C.c_char_p
+    s, arr, m = _project_arguments(seg3d, cams)
+    cols, start = support_columns(segments_per_camera)
+    if len(start) != m + 1:
+        raise ValueError("support lines: one array of 2-D segments per camera")
+    rc, out = _support_call(lib.l3d_test_support_lines_host, (), _p(s) if len(s) else None, len(s), arr if m else None, m, _p(cols) if len(cols) else None, start,
+                            support_params() if params is None else params)
+    if rc != 0:
+        e = L3DError("line3d_amd error %d: %s" % (rc, lib.l3d_support_last_error().decode()))
+        e.code = rc
+        raise e
+    return out
+
+
 SELECT_ALL, SELECT_OBSERVED = 0, 1
 LAYER_MEMBERS, LAYER_MODEL = 1, 2
 
@@ -1921,6 +1998,43 @@ class Context:
             rc, segs, idx, fl, start = _project_call(self.lib.l3d_project_lines, (self.h,), _p(s) if len(s) else None, len(s), arr if m else None, m, near, margin)
         self._chk(rc)
         return segs, idx, fl, start
+
+    def support_lines(self, seg3d, cams, segments_per_camera, params=None):
+        """l3d_support_lines: the 2-D segments of every camera that support each 3-D segment ("SUPPORT OF 3-D LINES").  seg3d (n, 6) float64 (P then
+        Q); cams as project_lines takes them; segments_per_camera: one (k, 4) float32 array per camera; params: capi.support_params(...) (None: 3 px,
+        5 degrees, overlap 0.5, near 1e-6, margin 3) -> dict(records: SUPPORT_RECORD array (seg3d, seg2d within the camera, dist, overlap), ordered by
+        (camera, seg3d, seg2d); cam_start (m + 1,) int64; best (all 2-D segments,) int32: the 3-D segment nearest to each, -1 for none; counts (4,)
+        int64: rows, eligible columns, records, columns with a best row).  With seg3d a device object (a contiguous float64 (n, 6) device tensor),
+        segments_per_camera is (a contiguous float32 (T, 4) device tensor, seg_start (m + 1,)): both are read in place (l3d_support_lines_device);
+        the caller has synchronised whatever wrote them.  The result is host memory either way."""
+        prm = support_params() if params is None else params
+        if hasattr(seg3d, "__cuda_array_interface__"):
+            cols, start = segments_per_camera
+            start = np.ascontiguousarray(start, np.int64).reshape(-1)
+            ptrs = []
+            for obj, width, typestr, what in ((seg3d, 6, "<f8", "float64 array n x 6"), (cols, 4, "<f4", "float32 array T x 4")):
+                if not hasattr(obj, "__cuda_array_interface__"):
+                    raise TypeError("support lines: with device 3-D segments the 2-D segments are a device object too")
+                iface = obj.__cuda_array_interface__
+                shape, strides = tuple(int(v) for v in iface["shape"]), iface.get("strides")
+                item = 8 if width == 6 else 4
+                if len(shape) != 2 or shape[1] != width or str(iface["typestr"]) != typestr or (strides is not None and tuple(int(v) for v in strides) != (width * item, item)):
+                    raise TypeError("device segments must be a contiguous " + what)
+                ptrs.append((C.c_void_p(int(iface["data"][0]) or None), shape[0]))
+            arr = cameras(cams)
+            m = getattr(arr, "_n", len(arr))
+            if len(start) != m + 1 or (m > 0 and int(start[-1]) != ptrs[1][1]):
+                raise ValueError("support lines: seg_start has one entry per camera and one more, the last the number of 2-D segments")
+            rc, out = _support_call(self.lib.l3d_support_lines_device, (self.h,), ptrs[0][0], ptrs[0][1], arr if m else None, m, ptrs[1][0], start, prm)
+        else:
+            s, arr, m = _project_arguments(seg3d, cams)
+            cols, start = support_columns(segments_per_camera)
+            if len(start) != m + 1:
+                raise ValueError("support lines: one array of 2-D segments per camera")
+            rc, out = _support_call(self.lib.l3d_support_lines, (self.h,), _p(s) if len(s) else None, len(s), arr if m else None, m, _p(cols) if len(cols) else None,
+                                    start, prm)
+        self._chk(rc)
+        return out
 
     def merge_lines(self, lines, tol, cos_min=None, max_gap=0.0, params=None):
         """l3d_merge_lines: duplicate 3-D lines grouped on the device ("MERGING DUPLICATE LINES").  lines (n, 6) float64 (P then Q), tol (n,) float64

@@ -31,7 +31,7 @@ static_assert(kVKAllPairs == L3D_VK_ALL_PAIRS && kVKSegPost == L3D_VK_SEG_POST &
               kVKWindowGB == L3D_VK_WINDOW_GB && kVKBuild == L3D_VK_BUILD && kVKWalk == L3D_VK_WALK && kVKWalkGB == L3D_VK_WALK_GB, "L3D_VK_* of the header");
 
 namespace {
-const char* kProfNames = "pair_mask;row_count;scan;pair_fill;cand_move;exist;verify;verify_window;seg_post;kept_write;collinearity;collinearity_fill;rownorm;diffusion_step;similarity;tgt_rays;prod_keys;prod_sort;prod_rows;hypotheses;uf_components;refine_lines;segmask_count;segmask_scan;segmask_write;covis_keys;covis_sort;covis_runs;covis_count;covis_scan;covis_write;proj_count;proj_scan;proj_write;draw_pieces;draw_scan;draw_cover;draw_resolve;merge_prepare;merge_count;merge_scan;merge_write;merge_cc_init;merge_cc_hook;merge_cc_compress;merge_rep;merge_star;merge_group";
+const char* kProfNames = "pair_mask;row_count;scan;pair_fill;cand_move;exist;verify;verify_window;seg_post;kept_write;collinearity;collinearity_fill;rownorm;diffusion_step;similarity;tgt_rays;prod_keys;prod_sort;prod_rows;hypotheses;uf_components;refine_lines;segmask_count;segmask_scan;segmask_write;covis_keys;covis_sort;covis_runs;covis_count;covis_scan;covis_write;proj_count;proj_scan;proj_write;draw_pieces;draw_scan;draw_cover;draw_resolve;merge_prepare;merge_count;merge_scan;merge_write;merge_cc_init;merge_cc_hook;merge_cc_compress;merge_rep;merge_star;merge_group;sup_prepare;sup_count;sup_scan;sup_write;sup_best";
 }  // namespace
 
 namespace l3d {

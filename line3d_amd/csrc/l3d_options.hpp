@@ -58,7 +58,8 @@ namespace l3d {
     X(det_batch_images, "L3D_DET_BATCH_IMAGES", 0, "tests: images per chunk of a batched detector call (0: by the index widths and half of the free HBM)") \
     X(covis_tile, "L3D_COVIS_TILE", 0, "co-visibility counting: view columns per tile of the LDS histogram (0: 8192, the most; tests: small values force many tiles)") \
     X(proj_chunk, "L3D_PROJ_CHUNK", 0, "l3d_project_lines: cameras per chunk of the three projection launches (0: 64; tests: 1 and 2 force many chunks)") \
-    X(host_bookkeeping, "L3D_HOST_BOOKKEEPING", 0, "CROSS-CHECK BUILD ONLY (-DL3D_CROSSCHECKS, libline3d_amd_check.so): matchViews with the rounds-1-2 host bookkeeping") \
+    X(sup_chunk, "L3D_SUP_CHUNK", 0, "l3d_support_lines: cameras per chunk of the three search launches (0: 64; tests: 1 and 2 force many chunks)") \
+    X(host_bookkeeping,"L3D_HOST_BOOKKEEPING", 0, "CROSS-CHECK BUILD ONLY (-DL3D_CROSSCHECKS, libline3d_amd_check.so): matchViews with the rounds-1-2 host bookkeeping") \
     X(host_clustering, "L3D_HOST_CLUSTERING", 0, "CROSS-CHECK BUILD ONLY: merge loop and grouping on the host threads")             \
     X(match_sync, "L3D_MATCH_SYNC", 0, "CROSS-CHECK BUILD ONLY: matchViews through the per-view seam call by default")
 

@@ -70,8 +70,11 @@ L3D_PJ_HD void pixel(const l3d_camera& c, const double* p, double& u, double& v)
     v = (c.K[3] * xn + c.K[4] * yn) + c.K[5];
 }
 
-// One (camera, segment) pair.  s: P then Q, 6 doubles.  true: kept, with the 2-D segment in o and the flags in fl
-L3D_PJ_HD bool project_pair(const l3d_camera& c, const double* s, double near_z, double margin, float* o, unsigned char& fl)
+// One (camera, segment) pair through THE RECTANGLE RULE.  s: P then Q, 6 doubles.  true: kept, with the pixels of both ends, (du, dv), the rule's t0 < t1
+// and whether the near plane moved an end (l3d_support.hpp takes its rows from here, in f64)
+struct Ends { double uP, vP, uQ, vQ, du, dv, t0, t1; bool movedP, movedQ; };
+
+L3D_PJ_HD bool project_ends(const l3d_camera& c, const double* s, double near_z, double margin, Ends& e)
 {
     double P[3], Q[3];
     camera_frame(c, s, P);
@@ -96,6 +99,17 @@ L3D_PJ_HD bool project_pair(const l3d_camera& c, const double* s, double near_z,
     if (du == 0.0 && dv == 0.0) return false;
     double t0, t1;
     if (!clip_rect(image_rect(c.width, c.height, margin), uP, vP, du, dv, t0, t1)) return false;
+    e.uP = uP; e.vP = vP; e.uQ = uQ; e.vQ = vQ; e.du = du; e.dv = dv; e.t0 = t0; e.t1 = t1; e.movedP = movedP; e.movedQ = movedQ;
+    return true;
+}
+
+// One (camera, segment) pair.  s: P then Q, 6 doubles.  true: kept, with the 2-D segment in o and the flags in fl
+L3D_PJ_HD bool project_pair(const l3d_camera& c, const double* s, double near_z, double margin, float* o, unsigned char& fl)
+{
+    Ends e;
+    if (!project_ends(c, s, near_z, margin, e)) return false;
+    const double uP = e.uP, vP = e.vP, uQ = e.uQ, vQ = e.vQ, du = e.du, dv = e.dv, t0 = e.t0, t1 = e.t1;
+    const bool movedP = e.movedP, movedQ = e.movedQ;
     if (t0 == 0.0) { o[0] = (float)uP; o[1] = (float)vP; }
     else { o[0] = (float)(uP + t0 * du); o[1] = (float)(vP + t0 * dv); }
     if (t1 == 1.0) { o[2] = (float)uQ; o[3] = (float)vQ; }

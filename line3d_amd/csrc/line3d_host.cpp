@@ -679,6 +679,7 @@ int l3d_line3d_reset(l3d_line3d* h)
     h->pot.clear(); h->pot_foreign.clear(); h->hyps.clear(); h->best_idx.clear(); h->A.clear(); h->n_edges = 0; h->A_on_host = true; h->local2global.clear(); h->result.clear();
     h->refine_valid = false;                               // (the setting itself stays)
     h->merge_valid = false;                                // (the setting itself stays)
+    h->support_valid = false;                              // (the setting itself stays)
     h->result_valid = false;
     h->covis_ids.clear(); h->covis_views.clear(); h->covis_start.assign(1, 0); h->covis_dirty = false; h->covis_path = 0;      // (covis_mode stays)
     h->computation = false; h->prepared = false;
@@ -1342,7 +1343,9 @@ int l3d_line3d_finish(l3d_line3d* h, int perform_diffusion)
     h->merge_valid = false;
     if (!rc && h->merge_on) rc = merge_result(h);
     if (!rc && h->refine_on) rc = refine_result(h);
+    h->support_valid = false;
     h->result_valid = rc == L3D_OK;
+    if (!rc && h->support_on) { rc = support_result(h); h->result_valid = rc == L3D_OK; }
     if (hopt(h).timing) fprintf(stderr, "[l3d finish] %-28s %8.2f ms\n", "total", (now_s() - t0) * 1e3);
     if (!rc && h->verbose)      // line3D.cc:959-961, 1226-1229, 1251
         printf("[L3D] #clusterable_segments:  %zu\n[L3D] A: #num_entries = %zu\n[L3D] A: #num_rows    = %zu\n[L3D] %zu 3D lines found!\n",
@@ -1378,6 +1381,49 @@ int l3d_line3d_get_merging(const l3d_line3d* h, int32_t* counts, int32_t* final_
     if (counts) memcpy(counts, h->merge_counts, sizeof(h->merge_counts));
     if (final_index && !h->merge_final_index.empty()) memcpy(final_index, h->merge_final_index.data(), h->merge_final_index.size() * 4);
     if (n_sources && !h->merge_n_sources.empty()) memcpy(n_sources, h->merge_n_sources.data(), h->merge_n_sources.size() * 4);
+    return L3D_OK;
+}
+// the support of the result's lines over all views (support_gather / support_result, line3d_host_finish.cpp).  A node object gathers on rank 0, which holds
+// the result
+int l3d_line3d_set_support(l3d_line3d* h, int on, double dist_px, double angle_deg, double min_overlap)
+{
+    if (!h) return L3D_ERR_INVALID;
+    if (!(dist_px >= 0.0 && dist_px - dist_px == 0.0) || !(angle_deg >= 0.0 && angle_deg <= 90.0) || !(min_overlap >= 0.0 && min_overlap <= 1.0))
+        return h->fail(L3D_ERR_INVALID, "set_support: dist_px must be finite and not negative, angle_deg in [0, 90], min_overlap in [0, 1]");
+    if (h->node) return l3d_line3d_set_support(rank0(h), on, dist_px, angle_deg, min_overlap);
+    h->support_on = on != 0; h->support_dist_px = dist_px; h->support_angle_deg = angle_deg; h->support_min_overlap = min_overlap;
+    return L3D_OK;
+}
+int l3d_line3d_get_support(const l3d_line3d* h, int64_t* counts, int32_t* per_line)
+{
+    if (!h) return L3D_ERR_INVALID;
+    if (h->node) return l3d_line3d_get_support(rank0(h), counts, per_line);
+    if (!h->support_valid || !h->result_valid || h->support_per_line.size() != 4 * h->result.size())
+        return const_cast<L*>(h)->fail(L3D_ERR_INVALID, "get_support: the last finish ran without the support");
+    if (counts) memcpy(counts, h->support_counts, sizeof(h->support_counts));
+    if (per_line && !h->support_per_line.empty()) memcpy(per_line, h->support_per_line.data(), h->support_per_line.size() * 4);
+    return L3D_OK;
+}
+int l3d_line3d_gather_support(l3d_line3d* h, const l3d_support_params* params, l3d_line_support** records, int64_t* line_start, int32_t* line_views, int64_t* counts)
+{
+    if (!h) return L3D_ERR_INVALID;
+    if (!records || !line_start || !counts) return h->fail(L3D_ERR_INVALID, "gather_support: a null output pointer");
+    *records = nullptr;
+    L* owner = h->node ? rank0(h) : h;
+    l3d_support_params prm;
+    if (params) prm = *params;
+    else { prm.dist_px = 3.0; prm.cos_min = std::cos(5.0 * 3.14159265358979323846 / 180.0); prm.min_overlap = 0.5; prm.near_z = 1e-6; prm.margin = 3.0; }
+    std::vector<l3d_line_support> rec;
+    std::vector<int64_t> start;
+    std::vector<int32_t> views;
+    const int rc = support_gather(owner, prm, rec, start, views, counts);
+    if (rc != L3D_OK) return owner == h ? rc : h->fail(rc, owner->err);
+    l3d_line_support* o = static_cast<l3d_line_support*>(malloc((rec.size() + 1) * sizeof(l3d_line_support)));      // (one spare record)
+    if (!o) return h->fail(L3D_ERR_NOMEM, "malloc");
+    if (!rec.empty()) memcpy(o, rec.data(), rec.size() * sizeof(l3d_line_support));
+    memcpy(line_start, start.data(), start.size() * 8);
+    if (line_views && !views.empty()) memcpy(line_views, views.data(), views.size() * 4);
+    *records = o;
     return L3D_OK;
 }
 // where the world point links are filed ("CO-VISIBILITY"): 0 on the host as each view is added, 1 by prepare() on the device.  A node object: every rank
@@ -1842,16 +1888,6 @@ int l3d_line3d_get_segment2D(const l3d_line3d* h, uint32_t cam, uint32_t seg, fl
 static const unsigned char kDefaultPalette[12 * 4] = { 230, 25, 75, 255, 60, 180, 75, 255, 255, 225, 25, 255, 0, 130, 200, 255, 245, 130, 48, 255, 145, 30, 180, 255,
                                                        70, 240, 240, 255, 240, 50, 230, 255, 210, 245, 60, 255, 250, 190, 212, 255, 0, 128, 128, 255, 170, 110, 40, 255 };
 const unsigned char* l3d_default_palette(void) { return kDefaultPalette; }
-
-static l3d_camera camera_as_added(const View& v)
-{
-    l3d_camera c;
-    memcpy(c.K, v.K.m, 72);
-    memcpy(c.R, v.R_added.m, 72);
-    c.t[0] = v.t_added.x; c.t[1] = v.t_added.y; c.t[2] = v.t_added.z;
-    c.width = (int32_t)v.width; c.height = (int32_t)v.height;
-    return c;
-}
 
 // owner: the object that holds the result.  The outputs are std::vectors here; the exported call packs them
 static int project_result_core(L* owner, const uint32_t* view_ids, int n_views, const l3d_camera* cameras, int select, double near_z, double margin,

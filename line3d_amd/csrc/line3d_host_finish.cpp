@@ -736,7 +736,10 @@ int refine_input(L* h, RefineInput& in)
     in.cameras.assign(12 * nv + 1, 0.0);
     for (size_t i = 0; i < nv; ++i) memcpy(&in.cameras[12 * i], h->vlist[i]->P, 96);
     in.gstart.assign(nl + 1, 0);
-    for (size_t l = 0; l < nl; ++l) in.gstart[l + 1] = in.gstart[l] + (int32_t)h->result[l].segs2D.size();
+    // (after a finish with the support on, a line's first members are those of the line fit: the ones the support added have no hypothesis)
+    const bool extended = h->support_valid && h->support_per_line.size() == 4 * nl;
+    auto members = [&](size_t l) { return extended ? (size_t)h->support_per_line[4 * l] : h->result[l].segs2D.size(); };
+    for (size_t l = 0; l < nl; ++l) in.gstart[l + 1] = in.gstart[l] + (int32_t)members(l);
     const size_t nm = (size_t)in.gstart[nl];
     in.mcam.assign(nm + 1, 0); in.mseg.assign(4 * nm + 4, 0.0f); in.mpts.assign(6 * nm + 6, 0.0);
     std::vector<int32_t>& gstart = in.gstart; std::vector<int32_t>& mcam = in.mcam; std::vector<float>& mseg = in.mseg; std::vector<double>& mpts = in.mpts;
@@ -744,7 +747,8 @@ int refine_input(L* h, RefineInput& in)
     parallel_slices(nl, finish_threads(), [&](size_t l0, size_t l1, unsigned) {
         for (size_t l = l0; l < l1; ++l) {
             size_t m = (size_t)gstart[l];
-            for (Key k : h->result[l].segs2D) {
+            for (size_t e = 0; e < members(l); ++e) {
+                const Key k = h->result[l].segs2D[e];
                 auto vt = h->views.find(kcam(k));
                 // (the hypotheses are in key order: greedy selection numbers them view by view, segment by segment)
                 auto hy = std::lower_bound(h->hyps.begin(), h->hyps.end(), k, [](const Hyp& a, Key b) { return a.src < b; });
@@ -796,6 +800,151 @@ int refine_result(L* h)
     l3d_free(cnt); l3d_free(segs);
     h->refine_valid = true;
     if (hopt(h).timing) fprintf(stderr, "[l3d finish] %-28s %8.2f ms (%zu lines, %zu members)\n", "refinement", (now_s() - t0) * 1e3, nl, nm);
+    return L3D_OK;
+}
+
+// The support of the result's lines ("SUPPORT OF 3-D LINES" in include/line3d_amd.h, on the object): the 3-D segments of the result in
+// l3d_line3d_get_result's order against every view's segments, the view's camera as it was added; one l3d_support_lines call on the owner's context.  A
+// (view, segment) that several 3-D segments of one line reach is reported once, with the smallest (dist, seg3d).
+int support_gather(L* owner, const l3d_support_params& prm, std::vector<l3d_line_support>& rec, std::vector<int64_t>& line_start, std::vector<int32_t>& line_views, int64_t* counts)
+{
+    for (int k = 0; k < 4; ++k) counts[k] = 0;
+    if (!owner->result_valid) return owner->fail(L3D_ERR_INVALID, "gather_support: no result yet (compute3Dmodel first)");
+    if (!owner->ctx) return owner->fail(L3D_ERR_INVALID, "gather_support: no device context");
+    const size_t nl = owner->result.size(), nv = owner->views.size();
+    std::vector<double> seg3d;
+    std::vector<int32_t> line_of;
+    for (size_t li = 0; li < nl; ++li)
+        for (auto& s : owner->result[li].segs3D) {
+            const double v[6] = { s.first.x, s.first.y, s.first.z, s.second.x, s.second.y, s.second.z };
+            seg3d.insert(seg3d.end(), v, v + 6);
+            line_of.push_back((int32_t)li);
+        }
+    // the views in ascending id: cameras, segments one after the other, and per segment the line it is a member of (-1: none; several: the first, and a mark)
+    std::vector<l3d_camera> cams;
+    std::vector<uint32_t> ids;
+    std::vector<int64_t> seg_start(1, 0);
+    std::vector<float> segs;
+    std::map<uint32_t, size_t> cam_of;
+    for (auto& kv : owner->views) {
+        cam_of[kv.first] = cams.size();
+        cams.push_back(camera_as_added(kv.second));
+        ids.push_back(kv.first);
+        segs.insert(segs.end(), kv.second.segs.begin(), kv.second.segs.end());
+        seg_start.push_back((int64_t)(segs.size() / 4));
+    }
+    const size_t T = (size_t)seg_start[nv];
+    std::vector<int32_t> member_line(T, -1);
+    std::vector<unsigned char> several(T, 0);
+    size_t n_members = 0;
+    for (size_t li = 0; li < nl; ++li)
+        for (Key key : owner->result[li].segs2D) {
+            auto ct = cam_of.find(kcam(key));
+            if (ct == cam_of.end() || (int64_t)kseg(key) >= seg_start[ct->second + 1] - seg_start[ct->second]) return owner->fail(L3D_ERR_INVALID, "gather_support: a 2-D segment of the result has no view");
+            const size_t at = (size_t)seg_start[ct->second] + kseg(key);
+            if (member_line[at] < 0) member_line[at] = (int32_t)li; else if (member_line[at] != (int32_t)li) several[at] = 1;
+            ++n_members;
+        }
+    std::vector<int32_t> best(T + 1, -1);
+    std::vector<int64_t> cam_start(nv + 1, 0);
+    l3d_support_record* raw = nullptr;
+    int64_t c4[4];
+    const int rc = l3d_support_lines(owner->ctx, seg3d.data(), (int)line_of.size(), cams.data(), (int)nv, segs.data(), seg_start.data(), &prm, &raw, cam_start.data(), best.data(), c4);
+    if (rc != L3D_OK) return owner->fail(rc, std::string("gather_support: ") + l3d_last_error(owner->ctx));
+    // one entry per (line, view, segment): the smallest (dist, seg3d).  The records come camera-major and, within a camera, by ascending seg3d -- which is
+    // by ascending line, the 3-D segments being numbered line after line: filing them into their lines' buckets camera after camera orders them by
+    // (line, view); only a line's few records of one view are left to sort, by (segment, dist, seg3d)
+    struct E { int32_t line; uint32_t cam; l3d_support_record r; };
+    std::vector<size_t> bucket(nl + 1, 0);
+    for (int64_t r = 0; r < cam_start[nv]; ++r) ++bucket[(size_t)line_of[(size_t)raw[r].seg3d] + 1];
+    for (size_t li = 0; li < nl; ++li) bucket[li + 1] += bucket[li];
+    std::vector<E> all((size_t)cam_start[nv]);
+    {
+        std::vector<size_t> at(bucket.begin(), bucket.end() - 1);
+        for (size_t c = 0; c < nv; ++c)
+            for (int64_t r = cam_start[c]; r < cam_start[c + 1]; ++r) { const int32_t li = line_of[(size_t)raw[r].seg3d]; all[at[(size_t)li]++] = E{ li, (uint32_t)c, raw[r] }; }
+    }
+    l3d_free(raw);
+    for (size_t i = 0; i < all.size();) {
+        size_t j = i + 1;
+        while (j < all.size() && all[j].line == all[i].line && all[j].cam == all[i].cam) ++j;
+        if (j - i > 1)
+            std::sort(all.begin() + (ptrdiff_t)i, all.begin() + (ptrdiff_t)j, [](const E& a, const E& b) {
+                if (a.r.seg2d != b.r.seg2d) return a.r.seg2d < b.r.seg2d;
+                if (a.r.dist != b.r.dist) return a.r.dist < b.r.dist;
+                return a.r.seg3d < b.r.seg3d;
+            });
+        i = j;
+    }
+    rec.clear();
+    line_start.assign(nl + 1, 0);
+    line_views.assign(2 * nl, 0);
+    std::vector<unsigned char> on_a_line(T, 0);
+    int64_t found = 0;
+    int32_t prev_line = -1;
+    uint32_t prev_cam = 0;
+    for (size_t i = 0; i < all.size(); ++i) {
+        const E& e = all[i];
+        if (i && all[i - 1].line == e.line && all[i - 1].cam == e.cam && all[i - 1].r.seg2d == e.r.seg2d) continue;
+        const size_t at = (size_t)seg_start[e.cam] + (size_t)e.r.seg2d;
+        bool mine = member_line[at] == e.line;
+        if (!mine && several[at]) { const std::vector<Key>& m = owner->result[(size_t)e.line].segs2D; mine = std::find(m.begin(), m.end(), mk(ids[e.cam], (uint32_t)e.r.seg2d)) != m.end(); }
+        const bool other = member_line[at] >= 0 && (member_line[at] != e.line || several[at]);
+        const bool holds_best = best[at] >= 0 && line_of[(size_t)best[at]] == e.line;
+        l3d_line_support o;
+        o.view_id = ids[e.cam]; o.seg = (uint32_t)e.r.seg2d; o.seg3d = e.r.seg3d; o.dist = e.r.dist; o.overlap = e.r.overlap;
+        o.flags = (mine ? 1u : 0u) | (other ? 2u : 0u) | (holds_best ? 4u : 0u);
+        if (e.line != prev_line || e.cam != prev_cam) ++line_views[2 * (size_t)e.line + 1];
+        prev_line = e.line; prev_cam = e.cam;
+        rec.push_back(o);
+        ++line_start[(size_t)e.line + 1];
+        found += mine ? 1 : 0;
+        on_a_line[at] = 1;
+    }
+    for (size_t li = 0; li < nl; ++li) {
+        line_start[li + 1] += line_start[li];
+        std::vector<uint32_t> mv;
+        for (Key key : owner->result[li].segs2D) mv.push_back(kcam(key));
+        std::sort(mv.begin(), mv.end());
+        line_views[2 * li] = (int32_t)(std::unique(mv.begin(), mv.end()) - mv.begin());
+    }
+    counts[0] = (int64_t)rec.size(); counts[1] = found; counts[2] = (int64_t)n_members - found;
+    for (size_t at = 0; at < T; ++at) counts[3] += on_a_line[at] && member_line[at] < 0 ? 1 : 0;
+    return L3D_OK;
+}
+
+// The gather as the last step of a finish (l3d_line3d_set_support), after the line fit, the merging and the refinement.  It EXTENDS the member lists: a
+// record joins its line's segs2D iff the line holds the segment's best row (bit 2) and the segment is a member of no line (bits 0 and 1 clear), so a 2-D
+// segment stays in at most one line; new members go behind the old ones in (view id, segment) order; the 3-D segments are untouched.
+int support_result(L* h)
+{
+    h->support_valid = false;
+    const double t0 = now_s();
+    l3d_support_params prm;
+    prm.dist_px = h->support_dist_px; prm.cos_min = std::cos(h->support_angle_deg * 3.14159265358979323846 / 180.0); prm.min_overlap = h->support_min_overlap;
+    prm.near_z = 1e-6; prm.margin = h->support_dist_px;
+    std::vector<l3d_line_support> rec;
+    std::vector<int64_t> start;
+    std::vector<int32_t> views;
+    h->result_valid = true;                                            // (the gather reads the result this finish has just built)
+    if (const int rc = support_gather(h, prm, rec, start, views, h->support_counts)) { h->result_valid = false; return rc; }
+    const size_t nl = h->result.size();
+    h->support_per_line.assign(4 * nl, 0);
+    size_t added = 0;
+    for (size_t li = 0; li < nl; ++li) {
+        FinalLine& fl = h->result[li];
+        std::vector<uint32_t> seen;
+        for (Key key : fl.segs2D) seen.push_back(kcam(key));
+        h->support_per_line[4 * li] = (int32_t)fl.segs2D.size();
+        h->support_per_line[4 * li + 2] = views[2 * li];
+        for (int64_t r = start[li]; r < start[li + 1]; ++r)
+            if (rec[(size_t)r].flags == 4u) { fl.segs2D.push_back(mk(rec[(size_t)r].view_id, rec[(size_t)r].seg)); seen.push_back(rec[(size_t)r].view_id); ++added; }
+        h->support_per_line[4 * li + 1] = (int32_t)fl.segs2D.size() - h->support_per_line[4 * li];
+        std::sort(seen.begin(), seen.end());
+        h->support_per_line[4 * li + 3] = (int32_t)(std::unique(seen.begin(), seen.end()) - seen.begin());
+    }
+    h->support_valid = true;
+    if (hopt(h).timing) fprintf(stderr, "[l3d finish] %-28s %8.2f ms (%zu lines, %lld records, %zu members added)\n", "support", (now_s() - t0) * 1e3, nl, (long long)h->support_counts[0], added);
     return L3D_OK;
 }
 

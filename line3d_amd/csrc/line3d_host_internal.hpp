@@ -161,6 +161,17 @@ struct FinalLine {
     std::vector<std::pair<V3, V3>> segs3D;
 };
 
+// a view's camera as it was added (transform_geometry rewrites R and t)
+inline l3d_camera camera_as_added(const View& v)
+{
+    l3d_camera c;
+    memcpy(c.K, v.K.m, 72);
+    memcpy(c.R, v.R_added.m, 72);
+    c.t[0] = v.t_added.x; c.t[1] = v.t_added.y; c.t[2] = v.t_added.z;
+    c.width = (int32_t)v.width; c.height = (int32_t)v.height;
+    return c;
+}
+
 struct NodeRanks;                                  // the ranks of a node object (line3d_host.cpp)
 
 }  // namespace l3dh
@@ -246,6 +257,12 @@ struct l3d_line3d {
     int merge_max_rounds = 3;
     int32_t merge_counts[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
     std::vector<int32_t> merge_final_index, merge_n_sources;
+    // support of the result's lines over all views (l3d_line3d_set_support; off by default, reset keeps it) and what the last finish with it on recorded:
+    // counts as l3d_line3d_gather_support, per line (original members, members added, views before, views after)
+    bool support_on = false, support_valid = false;
+    double support_dist_px = 3.0, support_angle_deg = 5.0, support_min_overlap = 0.5;
+    int64_t support_counts[4] = { 0, 0, 0, 0 };
+    std::vector<int32_t> support_per_line;
     bool fit_on_device = false;                                // the last line fit ran on the resident hypothesis table (l3d_fit_clusters / l3d_fit_labelled_clusters)
 
     // co-visibility counted on the device (l3d_line3d_set_covisibility; 0 by default, reset keeps the setting): the views' world point lists in add
@@ -393,5 +410,10 @@ int refine_input(L* h, RefineInput& in);
 int refine_result(L* h);
 // the result's duplicate lines merged (l3d_merge_lines, then a refit of every group by the fit path that built the result): before refine_result
 int merge_result(L* h);
+// the support of the result's lines ("SUPPORT OF 3-D LINES", on the object): every view's camera as it was added and its segments, through
+// l3d_support_lines on the owner's context; records ordered by (line, view id, segment), line_start (lines + 1), line_views (2 per line), counts[4]
+int support_gather(L* owner, const l3d_support_params& prm, std::vector<l3d_line_support>& rec, std::vector<int64_t>& line_start, std::vector<int32_t>& line_views, int64_t* counts);
+// the gather as the last step of a finish, and the member lists extended by it: after merge_result and refine_result
+int support_result(L* h);
 
 }  // namespace l3dh

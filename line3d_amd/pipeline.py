@@ -469,6 +469,46 @@ class Line3D:
         out["final_index"], out["n_sources"] = fi[:int(cnt[0])].copy(), ns[:int(cnt[1])].copy()
         return out
 
+    # -- support of the result's lines over all views (no counterpart in the reference) ----------------------------------------------
+    def gather_support(self, params=None, **kw):
+        """l3d_line3d_gather_support: which 2-D segments of which views lie on each line of the current result ("SUPPORT OF 3-D LINES", on the
+        object).  params: a capi.support_params(...), or its keywords (dist_px=, cos_min= or angle_deg=, min_overlap=, near_z=, margin=); neither: 3 px,
+        5 degrees, overlap 0.5, near 1e-6, margin 3 -> dict(records: capi.LINE_SUPPORT array (view_id, seg, seg3d into the flat list of getResult's 3-D
+        segments, dist, overlap, flags: 1 member of this line, 2 member of another line, 4 this line holds the segment's best row), ordered by (line,
+        view id, segment); line_start (lines + 1,) int64; line_views (lines, 2) int32: views with a member, views with a record; counts (4,) int64:
+        records, members found again, members not found, segments on a line that are members of none)."""
+        prm = params if params is not None else (capi.support_params(**kw) if kw else None)
+        nl = C.c_int(0)
+        self._chk(self.lib.l3d_line3d_result_sizes(self.h, C.byref(nl), None, None))
+        n = nl.value
+        rec = C.POINTER(capi.LineSupport)()
+        start, views, counts = np.zeros(n + 1, np.int64), np.zeros((max(1, n), 2), np.int32), np.zeros(4, np.int64)
+        self._chk(self.lib.l3d_line3d_gather_support(self.h, None if prm is None else C.byref(prm), C.byref(rec), _p(start), _p(views), _p(counts)))
+        k = int(counts[0])
+        records = np.frombuffer(C.string_at(rec, k * 24), capi.LINE_SUPPORT).copy() if k else np.zeros(0, capi.LINE_SUPPORT)
+        self.lib.l3d_free(rec)
+        return {"records": records, "line_start": start, "line_views": views[:n].copy(), "counts": counts}
+
+    def set_support(self, on=True, dist_px=3.0, angle_deg=5.0, min_overlap=0.5):
+        """l3d_line3d_set_support: with it on, finish / compute3Dmodel end with gather_support (after the line fit, the merging and the refinement) and
+        extend every line's 2-D segments by the segments of all views for which it holds the best row and that are members of no line, behind the old
+        members in (view id, segment) order; the 3-D segments are untouched; off by default; reset keeps it."""
+        self._chk(self.lib.l3d_line3d_set_support(self.h, C.c_int(int(bool(on))), C.c_double(float(dist_px)), C.c_double(float(angle_deg)), C.c_double(float(min_overlap))))
+
+    def support(self):
+        """l3d_line3d_get_support: what the last finish with the support on recorded -- dict of records, members_found, members_not_found,
+        segments_unclaimed (gather_support's counts, before the lists were extended) and, one per line of getResult(), members_before, members_added,
+        views_before, views_after."""
+        nl = C.c_int(0)
+        self._chk(self.lib.l3d_line3d_result_sizes(self.h, C.byref(nl), None, None))
+        n = nl.value
+        cnt, per = np.zeros(4, np.int64), np.zeros((max(1, n), 4), np.int32)
+        self._chk(self.lib.l3d_line3d_get_support(self.h, _p(cnt), _p(per)))
+        out = {k: int(cnt[i]) for i, k in enumerate(("records", "members_found", "members_not_found", "segments_unclaimed"))}
+        for i, k in enumerate(("members_before", "members_added", "views_before", "views_after")):
+            out[k] = per[:n, i].copy()
+        return out
+
     def refinement_input(self):
         """l3d_line3d_refinement_input (inspection): what a refinement of the current result is fed with -- dict of group_start, member_cam, member_seg,
         member_pts, cameras (normalised frame) and Rinv (3, 3), scale_inv, tneg (3,) of Line3D::inverseTransform."""
