@@ -2,7 +2,7 @@
 // segment caches of an earlier Line3D run standing in for the images, or with the images as binary PPM / PGM files or baseline JPEG files (no
 // OpenCV, no tclap, no boost):
 //
-//   main_vsfm_amd [--merge] [--refine] [--support] [--device-covisibility] [--overlays <folder>] <scene.nvm | bundle.rd.out> <data directory> [neighbors=10] [diffusion=0] [output folder=<data directory>] [image folder]
+//   main_vsfm_amd [--merge] [--refine] [--support] [--junctions [--snap]] [--obj <file>] [--device-covisibility] [--overlays <folder>] <scene.nvm | bundle.rd.out> <data directory> [neighbors=10] [diffusion=0] [output folder=<data directory>] [image folder]
 //
 // --merge (anywhere on the line): the near-copies of a 3-D line -- an edge seen along a camera path longer than the matching neighbourhood comes out
 // several times -- are merged on the GPU before the result is refined and written (setMerging, defaults; the counts are printed).
@@ -11,6 +11,10 @@
 // --support (anywhere on the line): as the last step of compute3Dmodel every line's 2-D segments are extended by the segments of ALL views that lie on
 // its projection (setSupport, defaults: 3 px, 5 degrees, half the shorter segment) -- a line otherwise lists only the views its cluster reached through
 // matches between neighbouring views; the TXT file and the overlays then show the added observations (the counts are printed).
+// --junctions (anywhere on the line): after the merging and the refinement the places where lines meet are found on the GPU -- line ends grouped into
+// vertices, free ends that rest on the inside of another line (setJunctions, defaults: 4 px, 12 px, 10 degrees, a quarter of the length; the counts are
+// printed); with --snap those ends are moved there along their own axes.  --obj <file>: the result is also written as a Wavefront OBJ wireframe whose
+// lines share the vertices' indices (save3DLinesAsOBJ; without --junctions no index is shared).
 // --device-covisibility (anywhere on the line): the cameras' world point lists are counted on the GPU when compute3Dmodel starts, instead of one
 // observation at a time as the images are added (setDeviceCovisibility: the same neighbours, the same lines; it pays on models of many images).
 // --overlays <folder> (anywhere on the line): after compute3Dmodel every view's image -- loaded once more and undistorted as it was added; a grey canvas
@@ -153,21 +157,24 @@ struct Vec3 { const double* p; double operator()(int i) const { return p[i]; } }
 
 int main(int argc, char** argv)
 {
-    bool refine = false, device_covis = false, merge = false, support = false;
-    std::string overlay_dir;
+    bool refine = false, device_covis = false, merge = false, support = false, junctions = false, snap = false;
+    std::string overlay_dir, obj_file;
     {
         int k = 1;
         for (int i = 1; i < argc; ++i) {
             if (std::string(argv[i]) == "--refine") refine = true;
             else if (std::string(argv[i]) == "--merge") merge = true;
             else if (std::string(argv[i]) == "--support") support = true;
+            else if (std::string(argv[i]) == "--junctions") junctions = true;
+            else if (std::string(argv[i]) == "--snap") snap = true;
+            else if (std::string(argv[i]) == "--obj" && i + 1 < argc) obj_file = argv[++i];
             else if (std::string(argv[i]) == "--device-covisibility") device_covis = true;
             else if (std::string(argv[i]) == "--overlays" && i + 1 < argc) overlay_dir = argv[++i];
             else argv[k++] = argv[i];
         }
         argc = k;
     }
-    if (argc < 3) { fprintf(stderr, "usage: %s [--merge] [--refine] [--support] [--device-covisibility] [--overlays <folder>] <scene.nvm | bundle.rd.out> <data directory> [neighbors=10] [diffusion=0] [output folder] [image folder]\n", argv[0]); return 2; }
+    if (argc < 3) { fprintf(stderr, "usage: %s [--merge] [--refine] [--support] [--junctions [--snap]] [--obj <file>] [--device-covisibility] [--overlays <folder>] <scene.nvm | bundle.rd.out> <data directory> [neighbors=10] [diffusion=0] [output folder] [image folder]\n", argv[0]); return 2; }
     const std::string nvm = argv[1], data_dir = argv[2];
     const int neighbors = argc > 3 ? atoi(argv[3]) : 10;
     const bool diffusion = argc > 4 && atoi(argv[4]) != 0;
@@ -189,6 +196,7 @@ int main(int argc, char** argv)
     if (merge) line3D.setMerging(true);
     if (refine) line3D.setRefinement(true);
     if (support) line3D.setSupport(true);
+    if (junctions) { L3D::JunctionParams jp; jp.snap = snap; line3D.setJunctions(true, jp); }
     if (device_covis) line3D.setDeviceCovisibility(true);
     int added = 0;
     std::vector<OverlayJob> jobs;
@@ -251,6 +259,11 @@ int main(int argc, char** argv)
         fprintf(stderr, "[L3D] support: %lld observations of the lines in all views, %lld of %lld members found again, %lld 2-D segments added to the lines\n", ss.records,
                 ss.membersFound, before, added_members);
     }
+    L3D::JunctionStats js;
+    if (junctions && line3D.getJunctions(js))
+        fprintf(stderr, "[L3D] junctions: %zu vertices from %d corner pairs, %d line ends rest on another line, %d ends moved\n", js.vertices.size(), js.lRecords,
+                js.nodesAttached, js.endsMoved);
+    if (!obj_file.empty() && !line3D.save3DLinesAsOBJ(obj_file)) fprintf(stderr, "[L3D] %s could not be written\n", obj_file.c_str());
 
     // the driver's output name (main_vsfm.cpp:289-313), numbers in stream-default formatting
     std::stringstream name;

@@ -111,6 +111,27 @@ struct MergeStats {
     int groupsMerged = 0, linesReleased = 0, emptyRefits = 0;       // summed over the rounds
 };
 
+// The parameters of the junctions (Line3D::setJunctions; l3d_line3d_set_junctions): two lines meet when their axes pass within distPx pixel footprints
+// of each other at an angle of at least angleMinDeg, each prolonged by at most extPx footprints and maxExtRel of its length; snap moves the ends that
+// stay in a vertex or rest on another line there, along their own axes
+struct JunctionParams {
+    double distPx = 4.0, extPx = 12.0, angleMinDeg = 10.0, maxExtRel = 0.25;
+    bool snap = false;
+};
+
+// A vertex of the wireframe: its position, its lowest staying line end (2 x line + end; end 0 = start of the first 3-D segment) and the ends it joins
+struct JunctionVertex {
+    double X[3] = { 0.0, 0.0, 0.0 };
+    int firstNode = 0, degree = 0;
+};
+
+// What the junctions found in the last compute3Dmodel (Line3D::getJunctions; l3d_line3d_get_junctions)
+struct JunctionStats {
+    std::vector<JunctionVertex> vertices;
+    std::vector<int> vertexP, vertexQ, attachLineP, attachLineQ;       // one per line of getResult(); -1: none
+    int eligibleLines = 0, lRecords = 0, tRecords = 0, xRecords = 0, components = 0, nodesReleased = 0, nodesAttached = 0, endsMoved = 0, movesSkipped = 0;
+};
+
 // The parameters of the support search (Line3D::gatherSupport; l3d_support_params): a 2-D segment supports a 3-D segment's projection when both of
 // its ends lie within distPx of it, the directions within angleDeg, and they overlap by at least minOverlap of the shorter one
 struct SupportParams {
@@ -739,6 +760,40 @@ public:
         }
         return true;
     }
+    // Junctions of the result's lines: a wireframe (no counterpart in the reference; "JUNCTIONS OF 3-D LINES" in line3d_amd.h).  With it on, compute3Dmodel
+    // finds where lines meet after the merging and the refinement and before the support: the line ends grouped into vertices, and the free ends that
+    // rest on the inside of another line.  Off by default; reset() keeps the setting.
+    void setJunctions(bool on = true, const JunctionParams& p = JunctionParams())
+    {
+        report(l3d_line3d_set_junctions(h_, on ? 1 : 0, p.distPx, p.extPx, p.angleMinDeg, p.maxExtRel, p.snap ? 1 : 0));
+    }
+    // false when the last compute3Dmodel ran without the junctions
+    bool getJunctions(JunctionStats& stats)
+    {
+        int nl = 0, nv = 0;
+        int32_t c[10];
+        if (l3d_line3d_result_sizes(h_, &nl, nullptr, nullptr) != L3D_OK) return false;
+        std::vector<int32_t> per((size_t)nl * 4 + 4);
+        l3d_junction_vertex* v = nullptr;
+        if (l3d_line3d_get_junctions(h_, &v, &nv, per.data(), c) != L3D_OK) return false;
+        stats.vertices.resize((size_t)nv);
+        for (int k = 0; k < nv; ++k) {
+            JunctionVertex& o = stats.vertices[(size_t)k];
+            o.X[0] = v[k].X[0]; o.X[1] = v[k].X[1]; o.X[2] = v[k].X[2]; o.firstNode = v[k].first_node; o.degree = v[k].degree;
+        }
+        l3d_free(v);
+        stats.vertexP.resize((size_t)nl); stats.vertexQ.resize((size_t)nl); stats.attachLineP.resize((size_t)nl); stats.attachLineQ.resize((size_t)nl);
+        for (int k = 0; k < nl; ++k) {
+            stats.vertexP[(size_t)k] = per[(size_t)k * 4]; stats.vertexQ[(size_t)k] = per[(size_t)k * 4 + 1];
+            stats.attachLineP[(size_t)k] = per[(size_t)k * 4 + 2]; stats.attachLineQ[(size_t)k] = per[(size_t)k * 4 + 3];
+        }
+        stats.eligibleLines = c[0]; stats.lRecords = c[1]; stats.tRecords = c[2]; stats.xRecords = c[3]; stats.components = c[4];
+        stats.nodesReleased = c[6]; stats.nodesAttached = c[7]; stats.endsMoved = c[8]; stats.movesSkipped = c[9];
+        return true;
+    }
+    // the current result as a Wavefront OBJ wireframe (l3d_line3d_save_wireframe): the vertices of the junctions, then every line as a group of its
+    // own; an end that stays in a vertex uses the shared index.  Works without the junctions too: then no index is shared.  false: not written
+    bool save3DLinesAsOBJ(const std::string& filename) { return l3d_line3d_save_wireframe(h_, filename.c_str()) == L3D_OK; }
     // Where addImage's world point links are filed (no counterpart in the reference; l3d_line3d_set_covisibility): false, the default, on the host as every
     // view is added; true: the lists are stored and compute3Dmodel counts them on the device -- the same neighbours and the same result.  Refused while the
     // object holds views; reset() keeps the setting.

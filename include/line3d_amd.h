@@ -1732,6 +1732,101 @@ int l3d_line3d_gather_support(l3d_line3d* h, const l3d_support_params* params, l
 int l3d_line3d_set_support(l3d_line3d* h, int on, double dist_px, double angle_deg, double min_overlap);
 int l3d_line3d_get_support(const l3d_line3d* h, int64_t* counts /* 4 */, int32_t* per_line /* 4 lines */);
 
+/* =================================================================================================
+ * JUNCTIONS OF 3-D LINES (no counterpart in the reference; formulas: line3d_amd/csrc/l3d_junction.hpp, numpy model: tests/junction_model.py).  The model is
+ * a set of loose segments: nothing says which lines meet, and two edges of one corner end a little short of each other or overshoot.
+ * l3d_junction_lines finds where lines meet: an all-pairs closest-approach test on the device, the line ends grouped into vertices, and the free ends
+ * that rest on the inside of another line.  The arithmetic is that of MERGING DUPLICATE LINES: everything is f64; every product, sum, quotient and
+ * square root is rounded on its own, in the written order (nothing fused); x . y = ((x0 y0) + (x1 y1)) + (x2 y2); max(x, y) is (x < y ? y : x) and
+ * min(x, y) is (y < x ? y : x); a comparison with a NaN is false.
+ *
+ * A LINE OF THE TABLE   P, Q (lines[6 k ..]), L = sqrt((Q - P) . (Q - P)), d = (Q - P) / L, and two numbers in scene units: tol[k] >= 0, how far apart
+ *                       two lines may pass, and ext[k] >= 0, how far line k may be prolonged beyond either end.  ELIGIBLE iff the eight numbers and L
+ *                       are finite and L > 0.
+ * THE PAIR TEST         for eligible i < j.  All of the following must hold:
+ *                       1. b = d_i . d_j and |b| <= cos_max (near-parallel pairs belong to the merging)
+ *                       2. w = P_i - P_j, p = d_i . w, q = d_j . w, den = 1 - (b b), den > 0; s = ((b q) - p) / den, t = (q - (b p)) / den: the
+ *                          parameters of the closest points of the two axes
+ *                       3. -ext_i <= s <= L_i + ext_i and -ext_j <= t <= L_j + ext_j
+ *                       4. Ci = P_i + (s d_i), Cj = P_j + (t d_j), g = sqrt((Ci - Cj) . (Ci - Cj)), g <= max(tol_i, tol_j)
+ * WHERE ON A LINE       where_i from (s, L_i, ext_i), where_j from (t, L_j, ext_j): if s + s <= L: L3D_JUNCTION_END_P (0) iff s <= ext, else
+ *                       L3D_JUNCTION_INTERIOR (2); otherwise L3D_JUNCTION_END_Q (1) iff L - s <= ext, else INTERIOR.
+ * KIND OF A PAIR        L (0): both at an end; T (1): exactly one at an end; X (2): both interior.  X pairs are listed only when
+ *                       params.crossings != 0 (they are skipped when the records are counted and when they are written alike).
+ * A RECORD              l3d_junction_record, 64 bytes, for every listed pair: i, j, where_i, where_j, s, t, gap = g, X = (Ci + Cj) 0.5 per coordinate.
+ *                       Records are ordered ascending by (i, j) under any schedule.
+ * VERTICES              The nodes are the line ends, 2 k + e (e = 0 for P, 1 for Q).  Every L record is an edge between its two nodes
+ *                       (2 i + where_i, 2 j + where_j); a vertex candidate is a connected component of that graph.  Its REPRESENTATIVE is the node of the
+ *                       longest line, at equal L the lowest node index.  A node STAYS iff it is the representative, or the pair test between its line
+ *                       and the representative's line passes as an L pair at exactly these two ends (the star rule of the merging, for the same reason:
+ *                       a row of short lines must not collapse into one vertex; hence at most one end of a line stays in a vertex, and the other end
+ *                       of the representative's line never stays).  Every other node of a component with an edge is RELEASED.  A VERTEX is a
+ *                       component's staying set when it has two or more nodes.  Its position: S = 0, then S = S + X, per coordinate, over the records
+ *                       between the representative and every other staying node, in ascending order of that node's index; then S / m, m = the number of
+ *                       those records as a double.  Vertices are numbered in the order of their lowest staying nodes.
+ * ATTACHMENTS           for a node that is in no vertex: node_attach[node] = the index of the T record in which this node is the end, among several
+ *                       the one with the smallest (gap, record index); -1 if there is none, and -1 for every node of a vertex.
+ * OUTPUTS               records: callee-allocated (l3d_free; one spare record), *n_records; node_vertex[2 n]: the vertex index or -1; vertices:
+ *                       callee-allocated l3d_junction_vertex (X, first_node = the lowest staying node, degree = the staying nodes), *n_vertices;
+ *                       node_attach[2 n]; counts[8] = eligible lines, L records, T records, X records, components with an edge, vertices, nodes
+ *                       released, nodes attached.
+ * REFUSED before anything is launched, L3D_ERR_INVALID: a NULL output; n < 0; a NULL array with n > 0; NULL params; cos_max outside [0, 1) or NaN; a
+ *   negative or NaN tol or ext.  L3D_ERR_UNSUPPORTED: n > 2^30 (before any launch; n = 2^30 itself has 2^31 nodes, one more than the components' int
+ *   labels number, and is answered the same way by the device call); more than 2^31 - 1 records, decided from the count pass's 64-bit total with
+ *   no allocation attempted; a record list the device cannot hold.  n == 0: empty outputs, L3D_OK.
+ * THE KERNELS (l3d_junction.hip).  k_junc_prepare builds the table, 80 bytes a line.  The search is k_junc_count / k_junc_scan / k_junc_write: 256
+ *   threads per workgroup, one row line per lane, column tiles of 256 lines staged in LDS and read as broadcasts, rows j > i only, column chunks along
+ *   the grid's y dimension when rows alone cannot fill the device, positions from one scan: three launches whatever n is.  Sixteen guard records behind
+ *   the list are filled before the write pass and checked after it.  The write pass also files one edge per record for the components (k_cc_init /
+ *   k_cc_hook / k_cc_compress over the 2 n nodes; a record that is no L pair files an edge from node 0 to itself).  k_junc_rep (two phases: integer
+ *   atomicMax on the bits of L, atomicMin on the node) names the representatives, k_junc_star decides who stays, k_junc_flag and k_junc_vscan number
+ *   the vertices, k_junc_keys writes one 64-bit key (lowest staying node, node) per staying node that is not the representative, a radix sort
+ *   (junc_sort) orders them, and k_junc_vertex -- one lane per vertex, walking its keys -- sums the positions in the stated order.  k_junc_attach (two
+ *   phases over the records: atomicMin on the bits of gap, then on the record index) and k_junc_finish give the attachments.  No floating-point atomic
+ *   anywhere.  Profile names: junc_*.
+ *   l3d_junction_lines             the device
+ *   l3d_test_junction_lines_host   the same arguments without the context: the same functions in loops, no device, bit-equal.
+ *   l3d_junction_last_error        per thread
+ *
+ * ON THE OBJECT.  Per line of the result: P = the start of its first 3-D segment, Q = the end of its last; tol = dist_px x sigma, sigma exactly as
+ *           step 1 of the merging defines it (the mean of z / f over the members' views); ext = min(ext_px x sigma, max_ext_rel x L);
+ *           cos_max = cos(angle_min_deg pi / 180), computed once on the host in double; no crossings.  One l3d_junction_lines call on the object's
+ *           context (a node object: rank 0's, which holds the result; a sharded finish: every rank that has the option set, each with the same bytes).
+ *   l3d_line3d_set_junctions    off by default; reset keeps the setting.  With it on, finish / compute3Dmodel run the junctions after the merging and
+ *                               the refinement and before the support gather.  snap != 0: an end that stays in a vertex moves to the foot of the
+ *                               vertex position on its own axis, P + ((X - P) . d) d, and an attached end to its own closest point Ci (P + s d with the
+ *                               record's parameter); P and d are the line's before any move.  The start of the first 3-D segment or the end of the
+ *                               last one is replaced, the P end first; the 2-D members are untouched.  A move after which
+ *                               (far end - new end) . (far end - old end) > 0 fails for that 3-D segment would reverse or annihilate it: it is
+ *                               skipped and counted.  With the option off nothing is launched and the result is what it was.
+ *   l3d_line3d_get_junctions    what the last finish recorded: vertices (callee-allocated, l3d_free; one spare), per line 4 int32 (vertex of the P end,
+ *                               vertex of the Q end, the line the P end is attached to, the line the Q end is attached to; -1: none) and counts[10]:
+ *                               the eight of l3d_junction_lines, the ends moved, the moves skipped.  Any output may be NULL.
+ *   l3d_line3d_save_wireframe   the current result as a Wavefront OBJ: one "v" line per vertex of the last finish's junctions, in vertex order (none when
+ *                               that finish ran without the option), then per line k "g line_<k>" and, per 3-D segment, a "v" line for each end that is
+ *                               not shared and "l a b"; the start of the first and the end of the last 3-D segment of a line whose end stays in a vertex
+ *                               use that vertex's index.  Coordinates are written as %.17g: the file parses back to the same doubles.
+ *   REFUSED, L3D_ERR_INVALID: set_junctions with dist_px or ext_px negative or not finite, angle_min_deg outside (0, 90], max_ext_rel outside [0, 0.5];
+ *   get_junctions when the last finish ran without the junctions; save_wireframe without a result or a file that cannot be written.
+ *
+ * OUT OF SCOPE: faces or planes from the wireframe; junctions across objects or devices; a spatial index over the columns; outputs that stay on the
+ * device; refitting lines so that they pass exactly through their vertices (snapping only moves ends along their own axes); hidden-line reasoning.
+ * ================================================================================================= */
+enum { L3D_JUNCTION_END_P = 0, L3D_JUNCTION_END_Q = 1, L3D_JUNCTION_INTERIOR = 2 };
+typedef struct l3d_junction_params { double cos_max; int32_t crossings, pad; } l3d_junction_params;
+typedef struct l3d_junction_record { int32_t i, j, where_i, where_j; double s, t, gap; double X[3]; } l3d_junction_record;
+typedef struct l3d_junction_vertex { double X[3]; int32_t first_node, degree; } l3d_junction_vertex;
+int l3d_junction_lines(l3d_ctx* ctx, const double* lines /* 6 n: P, Q */, const double* tol /* n */, const double* ext /* n */, int n,
+                       const l3d_junction_params* params, l3d_junction_record** records, int* n_records, int32_t* node_vertex /* 2 n */,
+                       l3d_junction_vertex** vertices, int* n_vertices, int32_t* node_attach /* 2 n */, int32_t* counts /* 8 */);
+int l3d_test_junction_lines_host(const double* lines, const double* tol, const double* ext, int n, const l3d_junction_params* params,
+                                 l3d_junction_record** records, int* n_records, int32_t* node_vertex, l3d_junction_vertex** vertices, int* n_vertices,
+                                 int32_t* node_attach, int32_t* counts);
+const char* l3d_junction_last_error(void);
+int l3d_line3d_set_junctions(l3d_line3d* h, int on, double dist_px, double ext_px, double angle_min_deg, double max_ext_rel, int snap);
+int l3d_line3d_get_junctions(const l3d_line3d* h, l3d_junction_vertex** vertices, int* n_vertices, int32_t* per_line /* 4 lines */, int32_t* counts /* 10 */);
+int l3d_line3d_save_wireframe(const l3d_line3d* h, const char* filename);
+
 /* The detector's stages on their own, exported for tests (tests/test_gpu_detect_stages.py): the same kernels with the same launch shapes
  * as l3d_detect_segments, results copied to caller-allocated arrays.  (N, M) = (ceil(0.8 new_width), ceil(0.8 new_height)) is the scaled image.
  *   pixel stage   grey[new_width x new_height] after rescale + grey; img / mod / ang [N x M]: the Gaussian sampler's output, the 2x2 gradient's

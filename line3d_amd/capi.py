@@ -559,6 +559,82 @@ def merge_lines_host(lines, tol, cos_min=None, max_gap=0.0, params=None):
     return out
 
 
+class JunctionParams(C.Structure):
+    """l3d_junction_params (include/line3d_amd.h)"""
+    _fields_ = [("cos_max", C.c_double), ("crossings", C.c_int32), ("pad", C.c_int32)]
+
+
+class JunctionRecord(C.Structure):
+    """l3d_junction_record: 64 bytes"""
+    _fields_ = [("i", C.c_int32), ("j", C.c_int32), ("where_i", C.c_int32), ("where_j", C.c_int32), ("s", C.c_double), ("t", C.c_double), ("gap", C.c_double),
+                ("X", C.c_double * 3)]
+
+
+class JunctionVertex(C.Structure):
+    """l3d_junction_vertex: 32 bytes"""
+    _fields_ = [("X", C.c_double * 3), ("first_node", C.c_int32), ("degree", C.c_int32)]
+
+
+JUNCTION_RECORD = np.dtype([("i", np.int32), ("j", np.int32), ("where_i", np.int32), ("where_j", np.int32), ("s", np.float64), ("t", np.float64),
+                            ("gap", np.float64), ("X", np.float64, (3,))])
+JUNCTION_VERTEX = np.dtype([("X", np.float64, (3,)), ("first_node", np.int32), ("degree", np.int32)])
+JUNCTION_END_P, JUNCTION_END_Q, JUNCTION_INTERIOR = 0, 1, 2
+
+
+def junction_params(cos_max=None, crossings=0, angle_min_deg=10.0):
+    """An l3d_junction_params.  cos_max None: cos(angle_min_deg pi / 180), in double"""
+    import math
+    p = JunctionParams()
+    p.cos_max = math.cos(angle_min_deg * math.pi / 180.0) if cos_max is None else float(cos_max)
+    p.crossings = int(crossings)
+    p.pad = 0
+    return p
+
+
+def _junction_call(fn, head, lines, tol, ext, prm):
+    """the argument list the junction calls share (head: the context, or nothing) -> (rc, dict(records: JUNCTION_RECORD array, node_vertex (2 n,) int32,
+    vertices: JUNCTION_VERTEX array, node_attach (2 n,) int32, counts (8,) int32)).  lines None or an int: passed as NULL with that count, for the
+    refusals"""
+    dbl = lambda a: None if a is None else np.ascontiguousarray(a, np.float64).reshape(-1)
+    if lines is None or isinstance(lines, int):
+        n, lp, tol, ext = int(lines or 0), None, dbl(tol), dbl(ext)
+    else:
+        lines = np.ascontiguousarray(lines, np.float64).reshape(-1, 6)
+        n, lp, tol, ext = len(lines), (_p(lines) if len(lines) else None), dbl(tol), dbl(ext)
+        if (tol is not None and len(tol) != n) or (ext is not None and len(ext) != n):
+            raise ValueError("junction lines: one tolerance and one extension per line")
+    tp = None if tol is None or len(tol) == 0 else _p(tol)
+    ep = None if ext is None or len(ext) == 0 else _p(ext)
+    node_vertex = np.zeros(max(2, 2 * n), np.int32)
+    node_attach = np.zeros(max(2, 2 * n), np.int32)
+    counts = np.zeros(8, np.int32)
+    rec, vert, nr, nv = C.POINTER(JunctionRecord)(), C.POINTER(JunctionVertex)(), C.c_int(0), C.c_int(0)
+    rc = fn(*head, lp, tp, ep, C.c_int(n), None if prm is None else C.byref(prm), C.byref(rec), C.byref(nr), _p(node_vertex), C.byref(vert), C.byref(nv),
+            _p(node_attach), _p(counts))
+    if rc != 0:
+        return rc, None
+    records = np.frombuffer(C.string_at(rec, nr.value * 64), JUNCTION_RECORD).copy() if nr.value else np.zeros(0, JUNCTION_RECORD)
+    vertices = np.frombuffer(C.string_at(vert, nv.value * 32), JUNCTION_VERTEX).copy() if nv.value else np.zeros(0, JUNCTION_VERTEX)
+    lib = load_library()
+    lib.l3d_free(rec)
+    lib.l3d_free(vert)
+    m = 2 * max(0, n)
+    return 0, dict(records=records, node_vertex=node_vertex[:m].copy(), vertices=vertices, node_attach=node_attach[:m].copy(), counts=counts)
+
+
+def junction_lines_host(lines, tol, ext, cos_max=None, crossings=0, params=None):
+    """l3d_test_junction_lines_host: the junctions of 3-D lines on the host -- no context, no device.  Arguments and result as Context.junction_lines.
+    A refusal raises L3DError carrying the status in .code."""
+    lib = load_library()
+    lib.l3d_junction_last_error.restype = C.c_char_p
+    rc, out = _junction_call(lib.l3d_test_junction_lines_host, (), lines, tol, ext, junction_params(cos_max, crossings) if params is None else params)
+    if rc != 0:
+        e = L3DError("line3d_amd error %d: %s" % (rc, lib.l3d_junction_last_error().decode()))
+        e.code = rc
+        raise e
+    return out
+
+
 class SupportParams(C.Structure):
     """l3d_support_params (include/line3d_amd.h)"""
     _fields_ = [("dist_px", C.c_double), ("cos_min", C.c_double), ("min_overlap", C.c_double), ("near_z", C.c_double), ("margin", C.c_double)]
@@ -2041,6 +2117,15 @@ class Context:
         in scene units; cos_min None: cos(5 degrees) -> dict(group (n,) int32: the lowest index of the line's group, pairs (k, 2) int32 ascending
         by (i, j), counts (4,) int32: eligible lines, components with a pair, lines released, groups of two or more)."""
         rc, out = _merge_call(self.lib.l3d_merge_lines, (self.h,), lines, tol, merge_params(cos_min, max_gap) if params is None else params)
+        self._chk(rc)
+        return out
+
+    def junction_lines(self, lines, tol, ext, cos_max=None, crossings=0, params=None):
+        """l3d_junction_lines: where 3-D lines meet, on the device ("JUNCTIONS OF 3-D LINES").  lines (n, 6) float64 (P then Q), tol and ext (n,) float64
+        in scene units; cos_max None: cos(10 degrees) -> dict(records: JUNCTION_RECORD array ascending by (i, j), node_vertex (2 n,) int32: per line
+        end 2 k + e its vertex or -1, vertices: JUNCTION_VERTEX array, node_attach (2 n,) int32: per free end its T record or -1, counts (8,) int32:
+        eligible lines, L, T and X records, components with an edge, vertices, nodes released, nodes attached)."""
+        rc, out = _junction_call(self.lib.l3d_junction_lines, (self.h,), lines, tol, ext, junction_params(cos_max, crossings) if params is None else params)
         self._chk(rc)
         return out
 

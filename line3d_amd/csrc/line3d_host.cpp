@@ -680,6 +680,7 @@ int l3d_line3d_reset(l3d_line3d* h)
     h->refine_valid = false;                               // (the setting itself stays)
     h->merge_valid = false;                                // (the setting itself stays)
     h->support_valid = false;                              // (the setting itself stays)
+    h->junc_valid = false;                                 // (the setting itself stays)
     h->result_valid = false;
     h->covis_ids.clear(); h->covis_views.clear(); h->covis_start.assign(1, 0); h->covis_dirty = false; h->covis_path = 0;      // (covis_mode stays)
     h->computation = false; h->prepared = false;
@@ -1343,6 +1344,8 @@ int l3d_line3d_finish(l3d_line3d* h, int perform_diffusion)
     h->merge_valid = false;
     if (!rc && h->merge_on) rc = merge_result(h);
     if (!rc && h->refine_on) rc = refine_result(h);
+    h->junc_valid = false;
+    if (!rc && h->junc_on) rc = junction_result(h);
     h->support_valid = false;
     h->result_valid = rc == L3D_OK;
     if (!rc && h->support_on) { rc = support_result(h); h->result_valid = rc == L3D_OK; }
@@ -1425,6 +1428,66 @@ int l3d_line3d_gather_support(l3d_line3d* h, const l3d_support_params* params, l
     if (line_views && !views.empty()) memcpy(line_views, views.data(), views.size() * 4);
     *records = o;
     return L3D_OK;
+}
+// the junctions of the result's lines (junction_result, line3d_host_finish.cpp).  A node object runs them on rank 0, which holds the result
+int l3d_line3d_set_junctions(l3d_line3d* h, int on, double dist_px, double ext_px, double angle_min_deg, double max_ext_rel, int snap)
+{
+    if (!h) return L3D_ERR_INVALID;
+    const auto finite_nonneg = [](double x) { return x >= 0.0 && x - x == 0.0; };
+    if (!finite_nonneg(dist_px) || !finite_nonneg(ext_px) || !(angle_min_deg > 0.0 && angle_min_deg <= 90.0) || !(max_ext_rel >= 0.0 && max_ext_rel <= 0.5))
+        return h->fail(L3D_ERR_INVALID, "set_junctions: dist_px and ext_px must be finite and not negative, angle_min_deg in (0, 90], max_ext_rel in [0, 0.5]");
+    if (h->node) return l3d_line3d_set_junctions(rank0(h), on, dist_px, ext_px, angle_min_deg, max_ext_rel, snap);
+    h->junc_on = on != 0; h->junc_dist_px = dist_px; h->junc_ext_px = ext_px; h->junc_angle_min_deg = angle_min_deg; h->junc_max_ext_rel = max_ext_rel; h->junc_snap = snap != 0;
+    return L3D_OK;
+}
+int l3d_line3d_get_junctions(const l3d_line3d* h, l3d_junction_vertex** vertices, int* n_vertices, int32_t* per_line, int32_t* counts)
+{
+    if (!h) return L3D_ERR_INVALID;
+    if (h->node) return l3d_line3d_get_junctions(rank0(h), vertices, n_vertices, per_line, counts);
+    if (vertices) *vertices = nullptr;
+    if (n_vertices) *n_vertices = 0;
+    if (!h->junc_valid || !h->result_valid || h->junc_per_line.size() != 4 * h->result.size())
+        return const_cast<L*>(h)->fail(L3D_ERR_INVALID, "get_junctions: the last finish ran without the junctions");
+    if (vertices) {
+        l3d_junction_vertex* o = static_cast<l3d_junction_vertex*>(malloc((h->junc_vertices.size() + 1) * sizeof(l3d_junction_vertex)));     // (one spare vertex)
+        if (!o) return const_cast<L*>(h)->fail(L3D_ERR_NOMEM, "malloc");
+        if (!h->junc_vertices.empty()) memcpy(o, h->junc_vertices.data(), h->junc_vertices.size() * sizeof(l3d_junction_vertex));
+        *vertices = o;
+    }
+    if (n_vertices) *n_vertices = (int)h->junc_vertices.size();
+    if (per_line && !h->junc_per_line.empty()) memcpy(per_line, h->junc_per_line.data(), h->junc_per_line.size() * 4);
+    if (counts) memcpy(counts, h->junc_counts, sizeof(h->junc_counts));
+    return L3D_OK;
+}
+// the result as a Wavefront OBJ wireframe: the vertices of the last finish's junctions first (none without them), then every line as a group of its own
+int l3d_line3d_save_wireframe(const l3d_line3d* h, const char* filename)
+{
+    if (h && h->node) return l3d_line3d_save_wireframe(rank0(h), filename);
+    if (!h || !filename) return L3D_ERR_INVALID;
+    if (!h->result_valid) return const_cast<L*>(h)->fail(L3D_ERR_INVALID, "save_wireframe: no result");
+    const bool shared = h->junc_valid && h->junc_per_line.size() == 4 * h->result.size();
+    FILE* f = fopen(filename, "w");
+    if (!f) return const_cast<L*>(h)->fail(L3D_ERR_INVALID, "save_wireframe: the file cannot be opened");
+    long long next = 1;
+    if (shared)
+        for (const l3d_junction_vertex& v : h->junc_vertices) { fprintf(f, "v %.17g %.17g %.17g\n", v.X[0], v.X[1], v.X[2]); ++next; }
+    for (size_t l = 0; l < h->result.size(); ++l) {
+        const auto& segs = h->result[l].segs3D;
+        fprintf(f, "g line_%zu\n", l);
+        for (size_t k = 0; k < segs.size(); ++k) {
+            long long ab[2];
+            for (int e = 0; e < 2; ++e) {
+                const int32_t vx = shared && ((e == 0 && k == 0) || (e == 1 && k + 1 == segs.size())) ? h->junc_per_line[4 * l + (size_t)e] : -1;
+                if (vx >= 0) { ab[e] = vx + 1; continue; }
+                const V3& p = e == 0 ? segs[k].first : segs[k].second;
+                fprintf(f, "v %.17g %.17g %.17g\n", p.x, p.y, p.z);
+                ab[e] = next++;
+            }
+            fprintf(f, "l %lld %lld\n", ab[0], ab[1]);
+        }
+    }
+    const bool ok = ferror(f) == 0;
+    return (fclose(f) == 0 && ok) ? L3D_OK : const_cast<L*>(h)->fail(L3D_ERR_INVALID, "save_wireframe: the file could not be written");
 }
 // where the world point links are filed ("CO-VISIBILITY"): 0 on the host as each view is added, 1 by prepare() on the device.  A node object: every rank
 // takes the setting, rank 0 counts

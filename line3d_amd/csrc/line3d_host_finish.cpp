@@ -948,6 +948,28 @@ int support_result(L* h)
     return L3D_OK;
 }
 
+// SIGMA of a line (step 1 of the merging; the junctions share it): the mean over the members, in their stored order, of z / f -- z = R[2] . M + t[2] at
+// M = (P + Q) / 2, f = (|K00| + |K11|) / 2 of the member's view as it was added.  Members with z <= 0 or a term that is not finite are skipped; none
+// left: 0.  missing: a member has no view
+static double line_sigma(const L* h, const FinalLine& fl, bool& missing)
+{
+    const V3 P = fl.segs3D.front().first, Q = fl.segs3D.back().second;
+    const double M[3] = { (P.x + Q.x) / 2.0, (P.y + Q.y) / 2.0, (P.z + Q.z) / 2.0 };
+    double sum = 0.0;
+    int cnt = 0;
+    for (Key k : fl.segs2D) {
+        auto vt = h->views.find(kcam(k));
+        if (vt == h->views.end()) { missing = true; return 0.0; }
+        const View& v = vt->second;
+        const double z = ((v.R_added(2, 0) * M[0] + v.R_added(2, 1) * M[1]) + v.R_added(2, 2) * M[2]) + v.t_added.z;
+        const double f = (std::fabs(v.K(0, 0)) + std::fabs(v.K(1, 1))) / 2.0;
+        const double r = z / f;
+        if (!(z > 0.0) || !(std::fabs(r) <= 1.7976931348623157e308)) continue;
+        sum = sum + r; ++cnt;
+    }
+    return cnt ? sum / (double)cnt : 0.0;
+}
+
 // The duplicate lines of the result merged ("MERGING DUPLICATE LINES" in include/line3d_amd.h, on the object), after whichever fit path built the list and
 // before the refinement.  Per round: a line's P is the start of its first 3-D segment, Q the end of its last, its tolerance dist_px times the mean of
 // z / f over its members' views as they were added; l3d_merge_lines groups the lines; every group of two or more is refitted from the union of its
@@ -979,20 +1001,10 @@ int merge_result(L* h)
                 const V3 P = fl.segs3D.front().first, Q = fl.segs3D.back().second;
                 double* q = &lines[6 * l];
                 q[0] = P.x; q[1] = P.y; q[2] = P.z; q[3] = Q.x; q[4] = Q.y; q[5] = Q.z;
-                const double M[3] = { (P.x + Q.x) / 2.0, (P.y + Q.y) / 2.0, (P.z + Q.z) / 2.0 };
-                double sum = 0.0;
-                int cnt = 0;
-                for (Key k : fl.segs2D) {
-                    auto vt = h->views.find(kcam(k));
-                    if (vt == h->views.end()) { bad.store(1, std::memory_order_relaxed); break; }
-                    const View& v = vt->second;
-                    const double z = ((v.R_added(2, 0) * M[0] + v.R_added(2, 1) * M[1]) + v.R_added(2, 2) * M[2]) + v.t_added.z;
-                    const double f = (std::fabs(v.K(0, 0)) + std::fabs(v.K(1, 1))) / 2.0;
-                    const double r = z / f;
-                    if (!(z > 0.0) || !(std::fabs(r) <= 1.7976931348623157e308)) continue;
-                    sum = sum + r; ++cnt;
-                }
-                tol[l] = cnt ? h->merge_dist_px * (sum / (double)cnt) : 0.0;
+                bool missing = false;
+                const double sigma = line_sigma(h, fl, missing);
+                if (missing) { bad.store(1, std::memory_order_relaxed); continue; }
+                tol[l] = h->merge_dist_px * sigma;
                 if (!(tol[l] >= 0.0)) tol[l] = 0.0;                               // (dist_px 0 times an overflowed mean)
             }
         });
@@ -1092,5 +1104,93 @@ int merge_result(L* h)
     return L3D_OK;
 }
 
+// The junctions of the result ("JUNCTIONS OF 3-D LINES" in include/line3d_amd.h, on the object), after the merging and the refinement and before the
+// support gather.  A line's P is the start of its first 3-D segment, Q the end of its last; tol = dist_px x sigma (line_sigma, the merging's),
+// ext = min(ext_px x sigma, max_ext_rel x L) with L = sqrt((Q - P) . (Q - P)); one l3d_junction_lines call without crossings.  With snap, an end that
+// stays in a vertex moves to the foot of the vertex on the line's own axis, P + ((X - P) . d) d, an attached end to its own closest point P + s d; P
+// and d = (Q - P) / L are those of the table, taken before any move.  The P end is moved first, then the Q end; a move after which
+// (far end - new end) . (far end - old end) > 0 no longer holds for the 3-D segment it ends -- the segment would turn round or vanish -- is skipped
+void junction_geometry(const FinalLine& fl, double* q)
+{
+    const V3 P = fl.segs3D.front().first, Q = fl.segs3D.back().second;
+    q[0] = P.x; q[1] = P.y; q[2] = P.z; q[3] = Q.x; q[4] = Q.y; q[5] = Q.z;
+}
+
+int junction_result(L* h)
+{
+    h->junc_valid = false;
+    h->junc_vertices.clear(); h->junc_per_line.clear();
+    for (int k = 0; k < 10; ++k) h->junc_counts[k] = 0;
+    const double t0 = now_s();
+    const size_t n = h->result.size();
+    std::vector<double> lines(6 * n + 6), tol(n + 1), ext(n + 1);
+    std::atomic<int> bad{ 0 };
+    parallel_slices(n, finish_threads(), [&](size_t l0, size_t l1, unsigned) {
+        for (size_t l = l0; l < l1; ++l) {
+            const FinalLine& fl = h->result[l];
+            double* q = &lines[6 * l];
+            junction_geometry(fl, q);
+            bool missing = false;
+            const double sigma = line_sigma(h, fl, missing);
+            if (missing) { bad.store(1, std::memory_order_relaxed); continue; }
+            const double v[3] = { q[3] - q[0], q[4] - q[1], q[5] - q[2] };
+            const double len = std::sqrt(((v[0] * v[0]) + (v[1] * v[1])) + (v[2] * v[2]));
+            const double a = h->junc_ext_px * sigma, b = h->junc_max_ext_rel * len;
+            tol[l] = h->junc_dist_px * sigma;
+            ext[l] = b < a ? b : a;
+            if (!(tol[l] >= 0.0)) tol[l] = 0.0;                                   // (0 times an overflowed mean)
+            if (!(ext[l] >= 0.0)) ext[l] = 0.0;
+        }
+    });
+    if (bad.load()) return h->fail(L3D_ERR_INVALID, "junctions: a 2-D segment of the result has no view");
+    l3d_junction_params prm;
+    prm.cos_max = std::cos(h->junc_angle_min_deg * 3.14159265358979323846 / 180.0);
+    prm.crossings = 0; prm.pad = 0;
+    std::vector<int32_t> node_vertex(2 * n + 2), node_attach(2 * n + 2);
+    l3d_junction_record* rec = nullptr; l3d_junction_vertex* vert = nullptr; int n_rec = 0, n_vert = 0;
+    const int rc = l3d_junction_lines(h->ctx, lines.data(), tol.data(), ext.data(), (int)n, &prm, &rec, &n_rec, node_vertex.data(), &vert, &n_vert, node_attach.data(), h->junc_counts);
+    if (rc) return h->fail(rc, std::string("junctions: ") + l3d_last_error(h->ctx));
+    h->junc_vertices.assign(vert, vert + n_vert);
+    h->junc_per_line.assign(4 * n, -1);
+    for (size_t l = 0; l < n; ++l)
+        for (int e = 0; e < 2; ++e) {
+            const size_t node = 2 * l + (size_t)e;
+            h->junc_per_line[4 * l + (size_t)e] = node_vertex[node];
+            if (node_attach[node] >= 0) { const l3d_junction_record& r = rec[node_attach[node]]; h->junc_per_line[4 * l + 2 + (size_t)e] = (size_t)r.i == l ? r.j : r.i; }
+        }
+    if (h->junc_snap) {
+        for (size_t l = 0; l < n; ++l) {
+            const double* q = &lines[6 * l];
+            const double v[3] = { q[3] - q[0], q[4] - q[1], q[5] - q[2] };
+            const double len = std::sqrt(((v[0] * v[0]) + (v[1] * v[1])) + (v[2] * v[2]));
+            const double d[3] = { v[0] / len, v[1] / len, v[2] / len };
+            for (int e = 0; e < 2; ++e) {
+                const size_t node = 2 * l + (size_t)e;
+                double s;
+                if (node_vertex[node] >= 0) {
+                    const double* X = vert[node_vertex[node]].X;
+                    const double w[3] = { X[0] - q[0], X[1] - q[1], X[2] - q[2] };
+                    s = ((w[0] * d[0]) + (w[1] * d[1])) + (w[2] * d[2]);
+                } else if (node_attach[node] >= 0) {
+                    const l3d_junction_record& r = rec[node_attach[node]];
+                    s = (size_t)r.i == l ? r.s : r.t;
+                } else continue;
+                const V3 to = { q[0] + (s * d[0]), q[1] + (s * d[1]), q[2] + (s * d[2]) };
+                std::pair<V3, V3>& seg = e == 0 ? h->result[l].segs3D.front() : h->result[l].segs3D.back();
+                const V3 far = e == 0 ? seg.second : seg.first, old = e == 0 ? seg.first : seg.second;
+                const V3 a = far - to, b = far - old;
+                if (!((((a.x * b.x) + (a.y * b.y)) + (a.z * b.z)) > 0.0)) { ++h->junc_counts[9]; continue; }
+                (e == 0 ? seg.first : seg.second) = to;
+                ++h->junc_counts[8];
+            }
+        }
+    }
+    l3d_free(rec); l3d_free(vert);
+    h->junc_valid = true;
+    if (hopt(h).timing)
+        fprintf(stderr, "[l3d finish] %-28s %8.2f ms (%zu lines, %d records, %d vertices, %d ends attached, %d ends moved)\n", "junctions", (now_s() - t0) * 1e3, n, n_rec, n_vert,
+                h->junc_counts[7], h->junc_counts[8]);
+    return L3D_OK;
+}
 
 }  // namespace l3dh

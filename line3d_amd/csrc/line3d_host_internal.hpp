@@ -263,6 +263,15 @@ struct l3d_line3d {
     double support_dist_px = 3.0, support_angle_deg = 5.0, support_min_overlap = 0.5;
     int64_t support_counts[4] = { 0, 0, 0, 0 };
     std::vector<int32_t> support_per_line;
+    // junctions of the result's lines (l3d_line3d_set_junctions; off by default, reset keeps it) and what the last finish with it on recorded: the
+    // vertices, per line (vertex of P, vertex of Q, line the P end is attached to, line the Q end is attached to; -1: none), l3d_junction_lines' counts[8]
+    // and, with snap, the ends moved and the moves skipped
+    bool junc_on = false, junc_valid = false;
+    double junc_dist_px = 4.0, junc_ext_px = 12.0, junc_angle_min_deg = 10.0, junc_max_ext_rel = 0.25;
+    int junc_snap = 0;
+    int32_t junc_counts[10] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+    std::vector<l3d_junction_vertex> junc_vertices;
+    std::vector<int32_t> junc_per_line;
     bool fit_on_device = false;                                // the last line fit ran on the resident hypothesis table (l3d_fit_clusters / l3d_fit_labelled_clusters)
 
     // co-visibility counted on the device (l3d_line3d_set_covisibility; 0 by default, reset keeps the setting): the views' world point lists in add
@@ -415,5 +424,7 @@ int merge_result(L* h);
 int support_gather(L* owner, const l3d_support_params& prm, std::vector<l3d_line_support>& rec, std::vector<int64_t>& line_start, std::vector<int32_t>& line_views, int64_t* counts);
 // the gather as the last step of a finish, and the member lists extended by it: after merge_result and refine_result
 int support_result(L* h);
+// the junctions of the result's lines (l3d_junction_lines), the ends snapped when asked for: after merge_result and refine_result, before support_result
+int junction_result(L* h);
 
 }  // namespace l3dh

@@ -509,6 +509,41 @@ class Line3D:
             out[k] = per[:n, i].copy()
         return out
 
+    # -- junctions of the result's lines: a wireframe (no counterpart in the reference) --------------------------------------------
+    def set_junctions(self, on=True, dist_px=4.0, ext_px=12.0, angle_min_deg=10.0, max_ext_rel=0.25, snap=False):
+        """l3d_line3d_set_junctions: with it on, finish / compute3Dmodel find where the lines of the result meet (capi.Context.junction_lines: axes that
+        pass within dist_px pixel footprints of each other, at least angle_min_deg apart, each line prolonged by at most ext_px footprints and
+        max_ext_rel of its length), after the merging and the refinement and before the support gather.  snap: the ends that stay in a vertex or rest
+        on another line move there along their own axes; off by default; reset keeps it."""
+        self._chk(self.lib.l3d_line3d_set_junctions(self.h, C.c_int(int(bool(on))), C.c_double(float(dist_px)), C.c_double(float(ext_px)), C.c_double(float(angle_min_deg)),
+                                                    C.c_double(float(max_ext_rel)), C.c_int(int(bool(snap)))))
+
+    def junctions(self):
+        """l3d_line3d_get_junctions: what the last finish with the junctions on recorded -- dict of vertices (capi.JUNCTION_VERTEX array: X, first_node,
+        degree), per line of getResult() vertex_P, vertex_Q (the vertex an end stays in, or -1) and attach_line_P, attach_line_Q (the line an end rests
+        on, or -1), and the counts: eligible_lines, l_records, t_records, x_records, components, vertices_found, nodes_released, nodes_attached, ends_moved,
+        moves_skipped."""
+        nl = C.c_int(0)
+        self._chk(self.lib.l3d_line3d_result_sizes(self.h, C.byref(nl), None, None))
+        n = nl.value
+        vert, nv = C.POINTER(capi.JunctionVertex)(), C.c_int(0)
+        per, cnt = np.zeros((max(1, n), 4), np.int32), np.zeros(10, np.int32)
+        self._chk(self.lib.l3d_line3d_get_junctions(self.h, C.byref(vert), C.byref(nv), _p(per), _p(cnt)))
+        vertices = np.frombuffer(C.string_at(vert, nv.value * 32), capi.JUNCTION_VERTEX).copy() if nv.value else np.zeros(0, capi.JUNCTION_VERTEX)
+        self.lib.l3d_free(vert)
+        out = {"vertices": vertices}
+        for i, k in enumerate(("vertex_P", "vertex_Q", "attach_line_P", "attach_line_Q")):
+            out[k] = per[:n, i].copy()
+        for i, k in enumerate(("eligible_lines", "l_records", "t_records", "x_records", "components", "vertices_found", "nodes_released", "nodes_attached", "ends_moved",
+                               "moves_skipped")):
+            out[k] = int(cnt[i])
+        return out
+
+    def save3DLinesAsOBJ(self, filename):
+        """l3d_line3d_save_wireframe: the result as a Wavefront OBJ wireframe -- the vertices of the last finish's junctions, then every line as a group of
+        its own; an end that stays in a vertex uses the shared index; coordinates as %.17g.  Works without the junctions too (no shared vertices)."""
+        self._chk(self.lib.l3d_line3d_save_wireframe(self.h, str(filename).encode()))
+
     def refinement_input(self):
         """l3d_line3d_refinement_input (inspection): what a refinement of the current result is fed with -- dict of group_start, member_cam, member_seg,
         member_pts, cameras (normalised frame) and Rinv (3, 3), scale_inv, tneg (3,) of Line3D::inverseTransform."""

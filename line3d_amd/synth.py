@@ -233,6 +233,78 @@ def make_scene_scattered(n_views: int, n_segments: int, seed: int = 4242, n_worl
     return Scene(views, np.concatenate([start, end], axis=1), params)
 
 
+def make_scene_boxes(n_views: int, n_boxes: int, n_neighbors: int, seed: int = 1234, noise_px: float = 0.5, width: int = 1920, height: int = 1080,
+                     f: float = 1500.0, step: float = 0.12, tilt: float = 0.35) -> Scene:
+    """A scene with corners: n_boxes boxes, each tilted by up to `tilt` radians about a random axis, inside the 2 x 1.2 x 2 volume make_scene fills, one
+    per cell of a grid so that two boxes never touch; every box gives 12 edges and 8 corners of degree 3.  The helix cameras, the pixel noise and the
+    `gt` field (per view: the edge every observed segment shows) are make_scene's; every view sees every edge whole (hidden lines are not removed).  The
+    Scene carries in addition `corners` (8 n_boxes, 3): the true corner points, and `corner_edges` (8 n_boxes, 3): the three edges (rows of segs3d) that
+    meet in each; edge k belongs to box k // 12, corner c to box c // 8."""
+    rng = SplitMix64(seed)
+    K = np.array([[f, 0.0, width / 2.0], [0.0, f, height / 2.0], [0.0, 0.0, 1.0]])
+    cams = []
+    jit = rng.normal(6 * n_views).reshape(n_views, 6)
+    for i in range(n_views):
+        th = step * i
+        turn = int(th // (2.0 * np.pi))
+        C = np.array([(4.0 + 0.35 * turn) * np.cos(th), 0.3 * np.sin(0.7 * i) + 0.25 * turn, (4.0 + 0.35 * turn) * np.sin(th)]) + 0.02 * jit[i, :3]
+        R = _look_at(C, 0.05 * jit[i, 3:])
+        cams.append((R, -R @ C))
+
+    g = max(1, int(np.ceil(np.sqrt(n_boxes / 2.0))))                    # cells: g x 2 x g
+    cell = np.array([2.0 / g, 0.6, 2.0 / g])
+    u = rng.uniform(n_boxes * 10).reshape(n_boxes, 10)
+    corners, edges, corner_edges = [], [], []
+    for b in range(n_boxes):
+        ix, iy, iz = (b // 2) % g, b % 2, (b // 2) // g
+        centre = (np.array([ix, iy, iz]) + 0.5) * cell - np.array([1.0, 0.6, 1.0]) + 0.1 * cell * (u[b, 0:3] - 0.5)
+        half = cell * np.array([0.18, 0.22, 0.18]) * (0.8 + 0.4 * u[b, 3:6])
+        axis = u[b, 6:9] - 0.5
+        axis /= np.linalg.norm(axis)
+        ang = tilt * (2.0 * u[b, 9] - 1.0)
+        A = np.array([[0.0, -axis[2], axis[1]], [axis[2], 0.0, -axis[0]], [-axis[1], axis[0], 0.0]])
+        rot = np.eye(3) + np.sin(ang) * A + (1.0 - np.cos(ang)) * (A @ A)
+        signs = np.array([[(c >> k) & 1 for k in range(3)] for c in range(8)]) * 2.0 - 1.0
+        pts = centre + (signs * half) @ rot.T
+        meet = [[] for _ in range(8)]
+        for c in range(8):
+            for k in range(3):
+                if not (c >> k) & 1:
+                    e = len(edges)
+                    edges.append(np.concatenate([pts[c], pts[c | (1 << k)]]))
+                    meet[c].append(e)
+                    meet[c | (1 << k)].append(e)
+        corners.extend(pts)
+        corner_edges.extend(meet)
+    segs3d = np.array(edges)
+    n_segments = len(segs3d)
+
+    def project(R, t, X):
+        x = (K @ (R @ X.T + t[:, None])).T
+        return x[:, :2] / x[:, 2:3], x[:, 2]
+
+    views = []
+    half_n = n_neighbors // 2
+    for i, (R, t) in enumerate(cams):
+        p1, z1 = project(R, t, segs3d[:, :3])
+        p2, z2 = project(R, t, segs3d[:, 3:])
+        for p, z in ((p1, z1), (p2, z2)):
+            if not np.all((z > 0.1) & (p[:, 0] >= 1.0) & (p[:, 0] < width - 1.0) & (p[:, 1] >= 1.0) & (p[:, 1] < height - 1.0)):
+                raise RuntimeError("view %d does not see every box edge whole" % i)
+        noise = noise_px * rng.normal(4 * n_segments).reshape(n_segments, 4)
+        perm = rng.permutation(n_segments)
+        segs = np.concatenate([p1, p2], axis=1)[perm] + noise
+        sims = {j: 1.0 / (1.0 + abs(i - j)) for j in range(max(0, i - half_n), min(n_views, i + half_n + 1)) if j != i}
+        views.append(dict(id=i, K=K.copy(), R=R.copy(), t=t.copy(), width=width, height=height,
+                          segments=np.ascontiguousarray(segs, dtype=np.float32), sims=sims, gt=perm.copy()))
+    params = dict(n_views=n_views, n_boxes=n_boxes, n_segments=n_segments, n_neighbors=n_neighbors, seed=seed, noise_px=noise_px, width=width, height=height, f=f,
+                  step=step, tilt=tilt, kind="boxes")
+    scene = Scene(views, segs3d, params)
+    scene.corners = np.array(corners)
+    scene.corner_edges = np.array(corner_edges, np.int32)
+    return scene
+
+
 def pair_work(scene: Scene) -> int:
     """Stage-1 segment pairs as the reference schedules them: each mutual
     view pair is evaluated once, from the view processed first (ascending id)."""
