@@ -2,7 +2,7 @@
 // segment caches of an earlier Line3D run standing in for the images, or with the images as binary PPM / PGM files or baseline JPEG files (no
 // OpenCV, no tclap, no boost):
 //
-//   main_vsfm_amd [--merge] [--refine] [--support] [--junctions [--snap]] [--obj <file>] [--device-covisibility] [--overlays <folder>] <scene.nvm | bundle.rd.out> <data directory> [neighbors=10] [diffusion=0] [output folder=<data directory>] [image folder]
+//   main_vsfm_amd [--merge] [--refine] [--support] [--junctions [--snap]] [--obj <file>] [--planes [--planes-obj <file>]] [--device-covisibility] [--overlays <folder>] <scene.nvm | bundle.rd.out> <data directory> [neighbors=10] [diffusion=0] [output folder=<data directory>] [image folder]
 //
 // --merge (anywhere on the line): the near-copies of a 3-D line -- an edge seen along a camera path longer than the matching neighbourhood comes out
 // several times -- are merged on the GPU before the result is refined and written (setMerging, defaults; the counts are printed).
@@ -15,6 +15,9 @@
 // vertices, free ends that rest on the inside of another line (setJunctions, defaults: 4 px, 12 px, 10 degrees, a quarter of the length; the counts are
 // printed); with --snap those ends are moved there along their own axes.  --obj <file>: the result is also written as a Wavefront OBJ wireframe whose
 // lines share the vertices' indices (save3DLinesAsOBJ; without --junctions no index is shared).
+// --planes (anywhere on the line): after the junctions the lines that lie in one plane are found on the GPU -- every pair of lines that meet spans a
+// hypothesis, agreeing hypotheses are averaged into a plane (setPlanes, defaults: 4 px, 10 degrees, 3 lines; a summary is printed).  --planes-obj <file>:
+// the planes are also written as a Wavefront OBJ, one rectangle per plane (save3DPlanesAsOBJ).
 // --device-covisibility (anywhere on the line): the cameras' world point lists are counted on the GPU when compute3Dmodel starts, instead of one
 // observation at a time as the images are added (setDeviceCovisibility: the same neighbours, the same lines; it pays on models of many images).
 // --overlays <folder> (anywhere on the line): after compute3Dmodel every view's image -- loaded once more and undistorted as it was added; a grey canvas
@@ -157,8 +160,8 @@ struct Vec3 { const double* p; double operator()(int i) const { return p[i]; } }
 
 int main(int argc, char** argv)
 {
-    bool refine = false, device_covis = false, merge = false, support = false, junctions = false, snap = false;
-    std::string overlay_dir, obj_file;
+    bool refine = false, device_covis = false, merge = false, support = false, junctions = false, snap = false, planes = false;
+    std::string overlay_dir, obj_file, planes_obj_file;
     {
         int k = 1;
         for (int i = 1; i < argc; ++i) {
@@ -168,13 +171,15 @@ int main(int argc, char** argv)
             else if (std::string(argv[i]) == "--junctions") junctions = true;
             else if (std::string(argv[i]) == "--snap") snap = true;
             else if (std::string(argv[i]) == "--obj" && i + 1 < argc) obj_file = argv[++i];
+            else if (std::string(argv[i]) == "--planes") planes = true;
+            else if (std::string(argv[i]) == "--planes-obj" && i + 1 < argc) planes_obj_file = argv[++i];
             else if (std::string(argv[i]) == "--device-covisibility") device_covis = true;
             else if (std::string(argv[i]) == "--overlays" && i + 1 < argc) overlay_dir = argv[++i];
             else argv[k++] = argv[i];
         }
         argc = k;
     }
-    if (argc < 3) { fprintf(stderr, "usage: %s [--merge] [--refine] [--support] [--junctions [--snap]] [--obj <file>] [--device-covisibility] [--overlays <folder>] <scene.nvm | bundle.rd.out> <data directory> [neighbors=10] [diffusion=0] [output folder] [image folder]\n", argv[0]); return 2; }
+    if (argc < 3) { fprintf(stderr, "usage: %s [--merge] [--refine] [--support] [--junctions [--snap]] [--obj <file>] [--planes [--planes-obj <file>]] [--device-covisibility] [--overlays <folder>] <scene.nvm | bundle.rd.out> <data directory> [neighbors=10] [diffusion=0] [output folder] [image folder]\n", argv[0]); return 2; }
     const std::string nvm = argv[1], data_dir = argv[2];
     const int neighbors = argc > 3 ? atoi(argv[3]) : 10;
     const bool diffusion = argc > 4 && atoi(argv[4]) != 0;
@@ -197,6 +202,7 @@ int main(int argc, char** argv)
     if (refine) line3D.setRefinement(true);
     if (support) line3D.setSupport(true);
     if (junctions) { L3D::JunctionParams jp; jp.snap = snap; line3D.setJunctions(true, jp); }
+    if (planes) line3D.setPlanes(true);
     if (device_covis) line3D.setDeviceCovisibility(true);
     int added = 0;
     std::vector<OverlayJob> jobs;
@@ -264,6 +270,11 @@ int main(int argc, char** argv)
         fprintf(stderr, "[L3D] junctions: %zu vertices from %d corner pairs, %d line ends rest on another line, %d ends moved\n", js.vertices.size(), js.lRecords,
                 js.nodesAttached, js.endsMoved);
     if (!obj_file.empty() && !line3D.save3DLinesAsOBJ(obj_file)) fprintf(stderr, "[L3D] %s could not be written\n", obj_file.c_str());
+    L3D::PlaneStats ps;
+    if (planes && line3D.getPlanes(ps))
+        fprintf(stderr, "[L3D] planes: %zu planes from %d seed pairs in %d groups, %d member lines in all, %d pairs released\n", ps.planes.size(), ps.eligibleHypotheses,
+                ps.components, ps.memberRecords, ps.hypothesesReleased);
+    if (planes && !planes_obj_file.empty() && !line3D.save3DPlanesAsOBJ(planes_obj_file)) fprintf(stderr, "[L3D] %s could not be written\n", planes_obj_file.c_str());
 
     // the driver's output name (main_vsfm.cpp:289-313), numbers in stream-default formatting
     std::stringstream name;

@@ -132,6 +132,29 @@ struct JunctionStats {
     int eligibleLines = 0, lRecords = 0, tRecords = 0, xRecords = 0, components = 0, nodesReleased = 0, nodesAttached = 0, endsMoved = 0, movesSkipped = 0;
 };
 
+// The parameters of the planes (Line3D::setPlanes; l3d_line3d_set_planes): two hypotheses -- planes spanned by pairs of lines that meet -- are grouped when
+// their normals lie within angleDeg and the lines of each lie within distPx pixel footprints of the other's plane; a plane needs minLines member lines
+struct PlaneParams {
+    double distPx = 4.0, angleDeg = 10.0;
+    int minLines = 3;
+};
+
+// A plane of the result: N . X = c, the frame (u, v) at O = c N, the rectangle (min a, max a, min b, max b) of its members' ends in that frame, the
+// seed pairs it was averaged from and the lines that lie in it
+struct Plane {
+    double N[3] = { 0.0, 0.0, 0.0 }, c = 0.0, u[3] = { 0.0, 0.0, 0.0 }, v[3] = { 0.0, 0.0, 0.0 }, rect[4] = { 0.0, 0.0, 0.0, 0.0 };
+    int hypotheses = 0;
+    std::vector<int> lines;            // indices into getResult(), ascending
+    std::vector<bool> seed;            // per member line: it is a line of one of the plane's seed pairs
+};
+
+// What the planes found in the last compute3Dmodel (Line3D::getPlanes; l3d_line3d_get_planes)
+struct PlaneStats {
+    std::vector<Plane> planes;
+    std::vector<int> planesPerLine;    // one per line of getResult()
+    int eligibleLines = 0, eligibleHypotheses = 0, hypothesisEdges = 0, components = 0, hypothesesReleased = 0, candidatesDropped = 0, memberRecords = 0;
+};
+
 // The parameters of the support search (Line3D::gatherSupport; l3d_support_params): a 2-D segment supports a 3-D segment's projection when both of
 // its ends lie within distPx of it, the directions within angleDeg, and they overlap by at least minOverlap of the shorter one
 struct SupportParams {
@@ -794,6 +817,41 @@ public:
     // the current result as a Wavefront OBJ wireframe (l3d_line3d_save_wireframe): the vertices of the junctions, then every line as a group of its
     // own; an end that stays in a vertex uses the shared index.  Works without the junctions too: then no index is shared.  false: not written
     bool save3DLinesAsOBJ(const std::string& filename) { return l3d_line3d_save_wireframe(h_, filename.c_str()) == L3D_OK; }
+    // Planes of the result's lines: faces for the wireframe (no counterpart in the reference; "PLANES OF 3-D LINES" in line3d_amd.h).  With it on,
+    // compute3Dmodel finds which lines lie in one plane, after the junctions -- whose search runs for the seed pairs even when setJunctions is off -- and
+    // before the support.  Off by default; reset() keeps the setting.
+    void setPlanes(bool on = true, const PlaneParams& p = PlaneParams()) { report(l3d_line3d_set_planes(h_, on ? 1 : 0, p.distPx, p.angleDeg, p.minLines)); }
+    // false when the last compute3Dmodel ran without the planes
+    bool getPlanes(PlaneStats& stats)
+    {
+        int nl = 0, np = 0, nm = 0;
+        int32_t c[8];
+        if (l3d_line3d_result_sizes(h_, &nl, nullptr, nullptr) != L3D_OK) return false;
+        std::vector<int32_t> per((size_t)nl + 1);
+        l3d_plane* pl = nullptr;
+        l3d_plane_member* mem = nullptr;
+        if (l3d_line3d_get_planes(h_, &pl, &np, &mem, &nm, per.data(), c) != L3D_OK) return false;
+        stats.planes.assign((size_t)np, Plane());
+        for (int k = 0; k < np; ++k) {
+            Plane& o = stats.planes[(size_t)k];
+            for (int d = 0; d < 3; ++d) { o.N[d] = pl[k].N[d]; o.u[d] = pl[k].u[d]; o.v[d] = pl[k].v[d]; }
+            for (int d = 0; d < 4; ++d) o.rect[d] = pl[k].rect[d];
+            o.c = pl[k].c; o.hypotheses = pl[k].n_hyp;
+        }
+        for (int k = 0; k < nm; ++k) {
+            Plane& o = stats.planes[(size_t)mem[k].plane];
+            o.lines.push_back(mem[k].line);
+            o.seed.push_back((mem[k].flags & L3D_PLANE_SEED) != 0);
+        }
+        l3d_free(pl); l3d_free(mem);
+        stats.planesPerLine.assign(per.begin(), per.begin() + nl);
+        stats.eligibleLines = c[0]; stats.eligibleHypotheses = c[1]; stats.hypothesisEdges = c[2]; stats.components = c[3]; stats.hypothesesReleased = c[4];
+        stats.candidatesDropped = c[5]; stats.memberRecords = c[7];
+        return true;
+    }
+    // the planes of the last compute3Dmodel as a Wavefront OBJ (l3d_line3d_save_planes): per plane a group of the four corners of its rectangle and one
+    // face.  false: not written (also when the last compute3Dmodel ran without the planes)
+    bool save3DPlanesAsOBJ(const std::string& filename) { return l3d_line3d_save_planes(h_, filename.c_str()) == L3D_OK; }
     // Where addImage's world point links are filed (no counterpart in the reference; l3d_line3d_set_covisibility): false, the default, on the host as every
     // view is added; true: the lists are stored and compute3Dmodel counts them on the device -- the same neighbours and the same result.  Refused while the
     // object holds views; reset() keeps the setting.

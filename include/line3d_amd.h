@@ -1809,7 +1809,7 @@ int l3d_line3d_get_support(const l3d_line3d* h, int64_t* counts /* 4 */, int32_t
  *   REFUSED, L3D_ERR_INVALID: set_junctions with dist_px or ext_px negative or not finite, angle_min_deg outside (0, 90], max_ext_rel outside [0, 0.5];
  *   get_junctions when the last finish ran without the junctions; save_wireframe without a result or a file that cannot be written.
  *
- * OUT OF SCOPE: faces or planes from the wireframe; junctions across objects or devices; a spatial index over the columns; outputs that stay on the
+ * OUT OF SCOPE: faces or planes from the wireframe (they have a section of their own: PLANES OF 3-D LINES, below); junctions across objects or devices; a spatial index over the columns; outputs that stay on the
  * device; refitting lines so that they pass exactly through their vertices (snapping only moves ends along their own axes); hidden-line reasoning.
  * ================================================================================================= */
 enum { L3D_JUNCTION_END_P = 0, L3D_JUNCTION_END_Q = 1, L3D_JUNCTION_INTERIOR = 2 };
@@ -1826,6 +1826,100 @@ const char* l3d_junction_last_error(void);
 int l3d_line3d_set_junctions(l3d_line3d* h, int on, double dist_px, double ext_px, double angle_min_deg, double max_ext_rel, int snap);
 int l3d_line3d_get_junctions(const l3d_line3d* h, l3d_junction_vertex** vertices, int* n_vertices, int32_t* per_line /* 4 lines */, int32_t* counts /* 10 */);
 int l3d_line3d_save_wireframe(const l3d_line3d* h, const char* filename);
+
+/* =================================================================================================
+ * PLANES OF 3-D LINES (no counterpart in the reference; formulas: line3d_amd/csrc/l3d_plane.hpp, numpy model: tests/plane_model.py).  A wireframe says
+ * which lines meet; l3d_plane_lines says which lines lie in one plane and where that plane is: every pair of lines that meet (a SEED) spans a plane
+ * hypothesis, hypotheses that agree are grouped, the group's plane is an area-weighted average, and every line of the table that lies in it is a
+ * member.  The arithmetic is that of MERGING DUPLICATE LINES and of the JUNCTIONS: everything is f64; every product, sum, quotient and square root is
+ * rounded on its own, in the written order (nothing fused); x . y = ((x0 y0) + (x1 y1)) + (x2 y2);
+ * a x b = ((a1 b2) - (a2 b1), (a2 b0) - (a0 b2), (a0 b1) - (a1 b0)); max(x, y) is (x < y ? y : x) and min(x, y) is (y < x ? y : x); a comparison
+ * with a NaN is false.
+ *
+ * INPUTS                lines[6 n] (P, Q per line), tol[n] >= 0 in scene units, seeds[2 m]: int32 pairs (i, j) of lines that meet, and the parameters
+ *                       cos_max, cos_min, min_lines.
+ * A LINE OF THE TABLE   L = sqrt((Q - P) . (Q - P)), d = (Q - P) / L.  ELIGIBLE iff the seven numbers and L are finite and L > 0.
+ * LIES IN (k; N, c)     line k lies in the plane (N, c) iff |(N . P_k) - c| <= tol_k and |(N . Q_k) - c| <= tol_k.
+ * A HYPOTHESIS h        from seed h = (i, j).  ELIGIBLE iff i != j, both lines are eligible, b = d_i . d_j with |b| <= cos_max, den = 1 - (b b) > 0,
+ *                       cr = d_i x d_j, mm = sqrt(cr . cr) > 0.  Then N_h = cr / mm; with w = P_i - P_j, p = d_i . w, q = d_j . w,
+ *                       s = ((b q) - p) / den, t = (q - (b p)) / den, Ci = P_i + (s d_i), Cj = P_j + (t d_j): X_h = (Ci + Cj) 0.5 per coordinate,
+ *                       c_h = N_h . X_h, and the weight A_h = (L_i L_j) mm (twice the area of the triangle the two lines span).  Two seeds of the
+ *                       same pair are two hypotheses.
+ * THE PAIR TEST         for eligible hypotheses h < g: |N_h . N_g| >= cos_min, both lines of g LIE IN (N_h, c_h) and both lines of h LIE IN
+ *                       (N_g, c_g).  Every passing pair is an edge; a plane CANDIDATE is a connected component of that graph over the eligible
+ *                       hypotheses, singletons included.
+ * THE STAR RULE         the REPRESENTATIVE of a component is the hypothesis with the largest A, at equal A the lowest index.  A hypothesis STAYS iff
+ *                       it is the representative or passes the pair test against it; the others are RELEASED (the merging's reason: a fan of slowly
+ *                       turning hypotheses must not collapse into one plane).
+ * PARAMETERS            over the staying hypotheses of a candidate in ascending index: sg_h = -1 if N_h . N_rep < 0, else 1;
+ *                       S = S + ((A_h sg_h) N_h) per coordinate from S = 0; W = W + A_h from 0; N = S / sqrt(S . S); then T = T + (A_h (N . X_h)) from
+ *                       0 and c = T / W.
+ * FRAME                 with d of line i of the representative's seed: u' = d - ((d . N) N), lu = sqrt(u' . u'), u = u' / lu, v = N x u, O = c N.
+ * MEMBERS               an eligible line k is a MEMBER of the candidate iff it LIES IN (N, c); flag bit 0 (L3D_PLANE_SEED) iff it is a line of one of
+ *                       the candidate's staying hypotheses.  A line may be a member of several planes (a box edge lies in two).
+ * KEPT                  a candidate is KEPT iff sqrt(S . S), W and lu are finite and > 0 (otherwise no line is tested against it) and its members number
+ *                       at least min_lines.  Planes are the kept candidates, numbered in the order of their lowest staying hypotheses.
+ * EXTENT                rect = (min a, max a, min b, max b) of a = u . (X - O), b = v . (X - O) over both ends X of all members.
+ * OUTPUTS               planes: callee-allocated l3d_plane, 128 bytes (N, c, u, v, rect; rep, first_hyp = the lowest staying hypothesis, n_hyp = the
+ *                       staying hypotheses, n_lines = the members), *n_planes; members: callee-allocated l3d_plane_member (plane, line, flags, pad),
+ *                       ascending by (plane, line) under any schedule, *n_members; one spare record follows each list (l3d_free); hyp_plane[m]: the
+ *                       plane a seed stays in, or -1; counts[8] = eligible lines, eligible hypotheses, hypothesis edges, components (candidates),
+ *                       hypotheses released, candidates dropped, planes, member records.
+ * REFUSED before anything is launched, L3D_ERR_INVALID: a NULL output; n or m < 0; a NULL array with n or m > 0; NULL params; cos_max outside [0, 1),
+ *   cos_min outside (0, 1], min_lines < 2; a negative or NaN tol; a seed index outside [0, n).  L3D_ERR_UNSUPPORTED: n or m above 2^30 (before any
+ *   launch); more than 2^31 - 1 edges or member records, decided from the count pass's 64-bit total with nothing allocated; more than 2^30 wave words
+ *   in the membership pass (candidates x ceil(n / 64)); a list the device cannot hold.  n == 0 or m == 0: nothing is launched, empty outputs, counts
+ *   all zero, L3D_OK.
+ * THE KERNELS (l3d_plane.hip).  k_plane_prepare builds the line table (96 bytes a line), k_plane_hyp the hypothesis table, one lane per seed (160
+ *   bytes a hypothesis: its plane and its two lines' ends and tolerances, plus 32 bytes for X and A).  The hypothesis search is k_plane_count /
+ *   k_plane_scan / k_plane_write: 256 threads per workgroup, one row hypothesis per lane, column tiles of 256 hypotheses staged in LDS (40 KB) and
+ *   read as broadcasts, rows g > h only, column chunks along the grid's y dimension when rows alone cannot fill the device, positions from one scan:
+ *   three launches whatever m is; sixteen guard records behind the edge list are filled before the write pass and checked after it.  Components:
+ *   k_cc_init / k_cc_hook / k_cc_compress.  k_plane_rep (two phases: integer atomicMax on the bits of A, atomicMin on the index), k_plane_star,
+ *   k_plane_flag and a scan number the candidates; k_plane_keys writes a key (lowest staying hypothesis, hypothesis) per staying hypothesis, a radix
+ *   sort orders them, and k_plane_param -- one lane per candidate, walking its keys -- sums in the stated order.  Membership tests every (candidate,
+ *   line) pair, one pair per lane with a ballot word per wave: k_plane_mcount, then k_plane_keep (the keep flags, the 64-bit total), a scan that
+ *   numbers the planes, k_plane_mmask (the words of dropped candidates count nothing), k_plane_mscan and k_plane_mwrite; k_plane_seed sets the
+ *   SEED flags (integer atomicOr), k_plane_extent -- one lane per plane over its records -- the extents, k_plane_finish hyp_plane.  The number of
+ *   launches does not depend on n or m beyond the components' rounds.  No floating-point atomic anywhere.  Profile names: plane_*.
+ *   l3d_plane_lines             the device
+ *   l3d_test_plane_lines_host   the same arguments without the context: the same functions in loops, no device, bit-equal.
+ *   l3d_plane_last_error        per thread
+ *
+ * ON THE OBJECT.  Per line of the result: P = the start of its first 3-D segment, Q = the end of its last, as the junctions left them (after their snap);
+ *           tol = dist_px x sigma, the sigma the junction search computed for the line (before any snap); cos_max = the junctions' own,
+ *           cos(angle_min_deg pi / 180); cos_min = cos(angle_deg pi / 180), computed once on the host in double; the seeds are the L and T records of the
+ *           junction search, in record order.  One l3d_plane_lines call on the object's context (a node object: rank 0's, which holds the result; a
+ *           sharded finish follows the junctions).
+ *   l3d_line3d_set_planes       off by default (4 px, 10 degrees, 3 lines); reset keeps the setting.  With it on, finish / compute3Dmodel run the planes
+ *                               after the junctions and before the support gather.  With the junctions option off the junction search runs all the
+ *                               same, with the junctions' stored parameters and without snap; its vertices are discarded and l3d_line3d_get_junctions
+ *                               still refuses.  With the planes option off nothing is launched and every output is what it was.
+ *   l3d_line3d_get_planes       what the last finish recorded: the planes and the member records (callee-allocated, l3d_free; one spare each), per line
+ *                               the number of planes it lies in, and the counts[8] of l3d_plane_lines.  Any output may be NULL.
+ *   l3d_line3d_save_planes      the planes of the last finish as a Wavefront OBJ: per plane k "g plane_<k>", four "v" lines -- the corners
+ *                               ((c N) + (a u)) + (b v) of its rectangle for (a, b) = (rect0, rect2), (rect1, rect2), (rect1, rect3), (rect0, rect3),
+ *                               written as %.17g: the file parses back to the same doubles -- and one "f" line.  l3d_line3d_save_wireframe is unchanged.
+ *   REFUSED, L3D_ERR_INVALID: set_planes with dist_px negative or not finite, angle_deg outside [0, 90), min_lines < 2; get_planes and save_planes when
+ *   the last finish ran without the planes; a file that cannot be written.
+ *
+ * OUT OF SCOPE: polygonal face boundaries or a closed mesh; a least-squares refit beyond the stated average; moving lines into their planes; seeds
+ * from parallel coplanar lines; a reach limit on members; hidden-line removal; planes across objects or devices; outputs that stay on the device.
+ * ================================================================================================= */
+enum { L3D_PLANE_SEED = 1 };
+typedef struct l3d_plane_params { double cos_max, cos_min; int32_t min_lines, pad; } l3d_plane_params;
+typedef struct l3d_plane { double N[3], c, u[3], v[3], rect[4]; int32_t rep, first_hyp, n_hyp, n_lines; } l3d_plane;
+typedef struct l3d_plane_member { int32_t plane, line, flags, pad; } l3d_plane_member;
+int l3d_plane_lines(l3d_ctx* ctx, const double* lines /* 6 n: P, Q */, const double* tol /* n */, int n, const int32_t* seeds /* 2 m */, int m,
+                    const l3d_plane_params* params, l3d_plane** planes, int* n_planes, l3d_plane_member** members, int* n_members,
+                    int32_t* hyp_plane /* m */, int32_t* counts /* 8 */);
+int l3d_test_plane_lines_host(const double* lines, const double* tol, int n, const int32_t* seeds, int m, const l3d_plane_params* params,
+                              l3d_plane** planes, int* n_planes, l3d_plane_member** members, int* n_members, int32_t* hyp_plane, int32_t* counts);
+const char* l3d_plane_last_error(void);
+int l3d_line3d_set_planes(l3d_line3d* h, int on, double dist_px, double angle_deg, int min_lines);
+int l3d_line3d_get_planes(const l3d_line3d* h, l3d_plane** planes, int* n_planes, l3d_plane_member** members, int* n_members, int32_t* per_line /* lines */,
+                          int32_t* counts /* 8 */);
+int l3d_line3d_save_planes(const l3d_line3d* h, const char* filename);
 
 /* The detector's stages on their own, exported for tests (tests/test_gpu_detect_stages.py): the same kernels with the same launch shapes
  * as l3d_detect_segments, results copied to caller-allocated arrays.  (N, M) = (ceil(0.8 new_width), ceil(0.8 new_height)) is the scaled image.

@@ -635,6 +635,85 @@ def junction_lines_host(lines, tol, ext, cos_max=None, crossings=0, params=None)
     return out
 
 
+class PlaneParams(C.Structure):
+    """l3d_plane_params (include/line3d_amd.h)"""
+    _fields_ = [("cos_max", C.c_double), ("cos_min", C.c_double), ("min_lines", C.c_int32), ("pad", C.c_int32)]
+
+
+class Plane(C.Structure):
+    """l3d_plane: 128 bytes"""
+    _fields_ = [("N", C.c_double * 3), ("c", C.c_double), ("u", C.c_double * 3), ("v", C.c_double * 3), ("rect", C.c_double * 4), ("rep", C.c_int32),
+                ("first_hyp", C.c_int32), ("n_hyp", C.c_int32), ("n_lines", C.c_int32)]
+
+
+class PlaneMember(C.Structure):
+    """l3d_plane_member: 16 bytes"""
+    _fields_ = [("plane", C.c_int32), ("line", C.c_int32), ("flags", C.c_int32), ("pad", C.c_int32)]
+
+
+PLANE = np.dtype([("N", np.float64, (3,)), ("c", np.float64), ("u", np.float64, (3,)), ("v", np.float64, (3,)), ("rect", np.float64, (4,)), ("rep", np.int32),
+                  ("first_hyp", np.int32), ("n_hyp", np.int32), ("n_lines", np.int32)])
+PLANE_MEMBER = np.dtype([("plane", np.int32), ("line", np.int32), ("flags", np.int32), ("pad", np.int32)])
+PLANE_SEED = 1
+
+
+def plane_params(cos_max=None, cos_min=None, min_lines=3, angle_min_deg=10.0, angle_deg=10.0):
+    """An l3d_plane_params.  cos_max None: cos(angle_min_deg pi / 180), the junctions' own; cos_min None: cos(angle_deg pi / 180); both in double"""
+    import math
+    p = PlaneParams()
+    p.cos_max = math.cos(angle_min_deg * math.pi / 180.0) if cos_max is None else float(cos_max)
+    p.cos_min = math.cos(angle_deg * math.pi / 180.0) if cos_min is None else float(cos_min)
+    p.min_lines = int(min_lines)
+    p.pad = 0
+    return p
+
+
+def _plane_call(fn, head, lines, tol, seeds, prm):
+    """the argument list the plane calls share (head: the context, or nothing) -> (rc, dict(planes: PLANE array, members: PLANE_MEMBER array,
+    hyp_plane (m,) int32, counts (8,) int32)).  lines or seeds None or an int: passed as NULL with that count, for the refusals"""
+    if lines is None or isinstance(lines, int):
+        n, lp = int(lines or 0), None
+        tol = None if tol is None else np.ascontiguousarray(tol, np.float64).reshape(-1)
+    else:
+        lines = np.ascontiguousarray(lines, np.float64).reshape(-1, 6)
+        n, lp = len(lines), (_p(lines) if len(lines) else None)
+        tol = None if tol is None else np.ascontiguousarray(tol, np.float64).reshape(-1)
+        if tol is not None and len(tol) != n:
+            raise ValueError("plane lines: one tolerance per line")
+    if seeds is None or isinstance(seeds, int):
+        m, sp = int(seeds or 0), None
+    else:
+        seeds = np.ascontiguousarray(seeds, np.int32).reshape(-1, 2)
+        m, sp = len(seeds), (_p(seeds) if len(seeds) else None)
+    tp = None if tol is None or len(tol) == 0 else _p(tol)
+    hyp_plane = np.zeros(max(1, m) if sp is not None else 1, np.int32)
+    counts = np.zeros(8, np.int32)
+    pl, mem, npl, nm = C.POINTER(Plane)(), C.POINTER(PlaneMember)(), C.c_int(0), C.c_int(0)
+    rc = fn(*head, lp, tp, C.c_int(n), sp, C.c_int(m), None if prm is None else C.byref(prm), C.byref(pl), C.byref(npl), C.byref(mem), C.byref(nm), _p(hyp_plane),
+            _p(counts))
+    if rc != 0:
+        return rc, None
+    planes = np.frombuffer(C.string_at(pl, npl.value * 128), PLANE).copy() if npl.value else np.zeros(0, PLANE)
+    members = np.frombuffer(C.string_at(mem, nm.value * 16), PLANE_MEMBER).copy() if nm.value else np.zeros(0, PLANE_MEMBER)
+    lib = load_library()
+    lib.l3d_free(pl)
+    lib.l3d_free(mem)
+    return 0, dict(planes=planes, members=members, hyp_plane=hyp_plane[:max(0, m)].copy(), counts=counts)
+
+
+def plane_lines_host(lines, tol, seeds, cos_max=None, cos_min=None, min_lines=3, params=None):
+    """l3d_test_plane_lines_host: the planes of 3-D lines on the host -- no context, no device.  Arguments and result as Context.plane_lines.
+    A refusal raises L3DError carrying the status in .code."""
+    lib = load_library()
+    lib.l3d_plane_last_error.restype = C.c_char_p
+    rc, out = _plane_call(lib.l3d_test_plane_lines_host, (), lines, tol, seeds, plane_params(cos_max, cos_min, min_lines) if params is None else params)
+    if rc != 0:
+        e = L3DError("line3d_amd error %d: %s" % (rc, lib.l3d_plane_last_error().decode()))
+        e.code = rc
+        raise e
+    return out
+
+
 class SupportParams(C.Structure):
     """l3d_support_params (include/line3d_amd.h)"""
     _fields_ = [("dist_px", C.c_double), ("cos_min", C.c_double), ("min_overlap", C.c_double), ("near_z", C.c_double), ("margin", C.c_double)]
@@ -2126,6 +2205,16 @@ class Context:
         end 2 k + e its vertex or -1, vertices: JUNCTION_VERTEX array, node_attach (2 n,) int32: per free end its T record or -1, counts (8,) int32:
         eligible lines, L, T and X records, components with an edge, vertices, nodes released, nodes attached)."""
         rc, out = _junction_call(self.lib.l3d_junction_lines, (self.h,), lines, tol, ext, junction_params(cos_max, crossings) if params is None else params)
+        self._chk(rc)
+        return out
+
+    def plane_lines(self, lines, tol, seeds, cos_max=None, cos_min=None, min_lines=3, params=None):
+        """l3d_plane_lines: which 3-D lines lie in one plane, on the device ("PLANES OF 3-D LINES").  lines (n, 6) float64 (P then Q), tol (n,) float64
+        in scene units, seeds (m, 2) int32: pairs of lines that meet; cos_max None: cos(10 degrees), cos_min None: cos(10 degrees) ->
+        dict(planes: PLANE array in the order of their lowest staying seeds, members: PLANE_MEMBER array ascending by (plane, line), hyp_plane (m,)
+        int32: per seed the plane it stays in or -1, counts (8,) int32: eligible lines, eligible hypotheses, hypothesis edges, components, hypotheses
+        released, candidates dropped, planes, member records)."""
+        rc, out = _plane_call(self.lib.l3d_plane_lines, (self.h,), lines, tol, seeds, plane_params(cos_max, cos_min, min_lines) if params is None else params)
         self._chk(rc)
         return out
 

@@ -31,7 +31,7 @@ static_assert(kVKAllPairs == L3D_VK_ALL_PAIRS && kVKSegPost == L3D_VK_SEG_POST &
               kVKWindowGB == L3D_VK_WINDOW_GB && kVKBuild == L3D_VK_BUILD && kVKWalk == L3D_VK_WALK && kVKWalkGB == L3D_VK_WALK_GB, "L3D_VK_* of the header");
 
 namespace {
-const char* kProfNames = "pair_mask;row_count;scan;pair_fill;cand_move;exist;verify;verify_window;seg_post;kept_write;collinearity;collinearity_fill;rownorm;diffusion_step;similarity;tgt_rays;prod_keys;prod_sort;prod_rows;hypotheses;uf_components;refine_lines;segmask_count;segmask_scan;segmask_write;covis_keys;covis_sort;covis_runs;covis_count;covis_scan;covis_write;proj_count;proj_scan;proj_write;draw_pieces;draw_scan;draw_cover;draw_resolve;merge_prepare;merge_count;merge_scan;merge_write;merge_cc_init;merge_cc_hook;merge_cc_compress;merge_rep;merge_star;merge_group;sup_prepare;sup_count;sup_scan;sup_write;sup_best;junc_prepare;junc_count;junc_scan;junc_write;junc_cc_init;junc_cc_hook;junc_cc_compress;junc_rep;junc_star;junc_flag;junc_vscan;junc_keys;junc_sort;junc_vertex;junc_attach;junc_finish";
+const char* kProfNames = "pair_mask;row_count;scan;pair_fill;cand_move;exist;verify;verify_window;seg_post;kept_write;collinearity;collinearity_fill;rownorm;diffusion_step;similarity;tgt_rays;prod_keys;prod_sort;prod_rows;hypotheses;uf_components;refine_lines;segmask_count;segmask_scan;segmask_write;covis_keys;covis_sort;covis_runs;covis_count;covis_scan;covis_write;proj_count;proj_scan;proj_write;draw_pieces;draw_scan;draw_cover;draw_resolve;merge_prepare;merge_count;merge_scan;merge_write;merge_cc_init;merge_cc_hook;merge_cc_compress;merge_rep;merge_star;merge_group;sup_prepare;sup_count;sup_scan;sup_write;sup_best;junc_prepare;junc_count;junc_scan;junc_write;junc_cc_init;junc_cc_hook;junc_cc_compress;junc_rep;junc_star;junc_flag;junc_vscan;junc_keys;junc_sort;junc_vertex;junc_attach;junc_finish;plane_prepare;plane_hyp;plane_count;plane_scan;plane_write;plane_cc_init;plane_cc_hook;plane_cc_compress;plane_rep;plane_star;plane_flag;plane_cscan;plane_keys;plane_sort;plane_param;plane_mcount;plane_keep;plane_pscan;plane_mmask;plane_mscan;plane_mwrite;plane_seed;plane_extent;plane_finish";
 }  // namespace
 
 namespace l3d {
@@ -57,7 +57,7 @@ void ctx_release_share(l3d_ctx* c)
     (void)hipStreamSynchronize(c->stream);
     c->products.release();
     DevBuf* bufs[] = { &c->aff_hyp, &c->aff_first, &c->aff_pass_pairs, &c->aff_pass_w, &c->aff_l2g, &c->edges_keep, &c->ch_send, &c->ch_gathered, &c->ch_hdr,
-                       &c->g0, &c->g1, &c->g2, &c->g3, &c->g4, &c->g5, &c->g6, &c->g7, &c->draw_plane, &c->merge_tab, &c->merge_pairs, &c->junc_tab, &c->junc_rec };
+                       &c->g0, &c->g1, &c->g2, &c->g3, &c->g4, &c->g5, &c->g6, &c->g7, &c->draw_plane, &c->merge_tab, &c->merge_pairs, &c->junc_tab, &c->junc_rec, &c->plane_tab, &c->plane_rec, &c->plane_waves };
     for (DevBuf* b : bufs) b->release();
     c->resident_hyp = 0; c->resident_edges = 0; c->kept_edges = 0; c->resident_nodes = 0; c->resident_labels = 0;
 }
@@ -346,7 +346,7 @@ void l3d_ctx_destroy(l3d_ctx* c)
     for (auto e : c->local_event_pool) (void)hipEventDestroy(e);
     DevBuf* bufs[] = { &c->src_segs, &c->tgt_segs, &c->tables, &c->tbm, &c->l2g, &c->exist, &c->mask, &c->rowcnt, &c->row_start,
                        &c->cand_meta, &c->cand_depths, &c->cand_conf, &c->kept_cnt, &c->kept_start, &c->best, &c->kept, &c->scal, &c->stamps, &c->vw_scratch, &c->vw_bstart, &c->vw_segstate, &c->ch_tables, &c->ch_mask, &c->ch_rowcnt, &c->ch_cursor, &c->ch_best, &c->ch_kept, &c->ch_keptcam, &c->ch_rt, &c->ch_rtinfo, &c->ch_rtjobs, &c->ch_existpart, &c->ch_res, &c->ch_flags, &c->ch_send, &c->ch_gathered, &c->ch_stage, &c->ch_rowA, &c->ch_ringA_meta, &c->ch_ringA_depths, &c->ch_segorder,
-                       &c->ch_rays, &c->aff_hyp, &c->aff_first, &c->aff_pass_pairs, &c->aff_pass_w, &c->aff_l2g, &c->edges_keep, &c->g0, &c->g1, &c->g2, &c->g3, &c->g4, &c->g5, &c->g6, &c->g7, &c->merge_tab, &c->merge_pairs, &c->junc_tab, &c->junc_rec };
+                       &c->ch_rays, &c->aff_hyp, &c->aff_first, &c->aff_pass_pairs, &c->aff_pass_w, &c->aff_l2g, &c->edges_keep, &c->g0, &c->g1, &c->g2, &c->g3, &c->g4, &c->g5, &c->g6, &c->g7, &c->merge_tab, &c->merge_pairs, &c->junc_tab, &c->junc_rec, &c->plane_tab, &c->plane_rec, &c->plane_waves };
     for (auto* b : bufs) b->release();
     c->ch_bestpos.release(); c->ch_hdr.release();
     c->products.release();

@@ -267,6 +267,7 @@ struct l3d_ctx {
     bool draw_plane_dirty = false;  // a draw call failed between its cover and its resolve: the plane is zeroed again before the next one
     l3d::DevBuf merge_tab, merge_pairs;   // l3d_merge.hip: the line table with its per-line arrays | the pair list (edges and (i, j) pairs)
     l3d::DevBuf junc_tab, junc_rec;       // l3d_junction.hip: the line table with its per-line and per-node arrays | the record list and its edges
+    l3d::DevBuf plane_tab, plane_rec, plane_waves;   // l3d_plane.hip: the tables with their per-hypothesis arrays | the edges, then the member records and planes | the membership's wave words
     l3d::DevBuf aff_hyp;            // hypothesis table of the last l3d_affinity_fill (kept for l3d_fit_clusters)
     l3d::DevBuf aff_l2g;            // sharded fill: global number of every local hypothesis
     l3d::DevBuf aff_first, aff_pass_pairs, aff_pass_w;   // affinity fill in blocks of sources: first-touch minima per hypothesis, the candidates that passed (pairs, weights)

@@ -681,6 +681,7 @@ int l3d_line3d_reset(l3d_line3d* h)
     h->merge_valid = false;                                // (the setting itself stays)
     h->support_valid = false;                              // (the setting itself stays)
     h->junc_valid = false;                                 // (the setting itself stays)
+    h->plane_valid = false;                                // (the setting itself stays)
     h->result_valid = false;
     h->covis_ids.clear(); h->covis_views.clear(); h->covis_start.assign(1, 0); h->covis_dirty = false; h->covis_path = 0;      // (covis_mode stays)
     h->computation = false; h->prepared = false;
@@ -1345,7 +1346,10 @@ int l3d_line3d_finish(l3d_line3d* h, int perform_diffusion)
     if (!rc && h->merge_on) rc = merge_result(h);
     if (!rc && h->refine_on) rc = refine_result(h);
     h->junc_valid = false;
-    if (!rc && h->junc_on) rc = junction_result(h);
+    h->plane_valid = false;
+    JunctionHandOn hand;
+    if (!rc && (h->junc_on || h->plane_on)) rc = junction_result(h, h->plane_on ? &hand : nullptr);
+    if (!rc && h->plane_on) rc = plane_result(h, hand);
     h->support_valid = false;
     h->result_valid = rc == L3D_OK;
     if (!rc && h->support_on) { rc = support_result(h); h->result_valid = rc == L3D_OK; }
@@ -1488,6 +1492,69 @@ int l3d_line3d_save_wireframe(const l3d_line3d* h, const char* filename)
     }
     const bool ok = ferror(f) == 0;
     return (fclose(f) == 0 && ok) ? L3D_OK : const_cast<L*>(h)->fail(L3D_ERR_INVALID, "save_wireframe: the file could not be written");
+}
+// the planes of the result's lines (plane_result, line3d_host_finish.cpp).  A node object runs them on rank 0, which holds the result
+int l3d_line3d_set_planes(l3d_line3d* h, int on, double dist_px, double angle_deg, int min_lines)
+{
+    if (!h) return L3D_ERR_INVALID;
+    if (!(dist_px >= 0.0 && dist_px - dist_px == 0.0) || !(angle_deg >= 0.0 && angle_deg < 90.0) || min_lines < 2)
+        return h->fail(L3D_ERR_INVALID, "set_planes: dist_px must be finite and not negative, angle_deg in [0, 90), min_lines at least 2");
+    if (h->node) return l3d_line3d_set_planes(rank0(h), on, dist_px, angle_deg, min_lines);
+    h->plane_on = on != 0; h->plane_dist_px = dist_px; h->plane_angle_deg = angle_deg; h->plane_min_lines = min_lines;
+    return L3D_OK;
+}
+int l3d_line3d_get_planes(const l3d_line3d* h, l3d_plane** planes, int* n_planes, l3d_plane_member** members, int* n_members, int32_t* per_line, int32_t* counts)
+{
+    if (!h) return L3D_ERR_INVALID;
+    if (h->node) return l3d_line3d_get_planes(rank0(h), planes, n_planes, members, n_members, per_line, counts);
+    if (planes) *planes = nullptr;
+    if (n_planes) *n_planes = 0;
+    if (members) *members = nullptr;
+    if (n_members) *n_members = 0;
+    if (!h->plane_valid || !h->result_valid || h->plane_per_line.size() != h->result.size())
+        return const_cast<L*>(h)->fail(L3D_ERR_INVALID, "get_planes: the last finish ran without the planes");
+    l3d_plane* op = nullptr; l3d_plane_member* om = nullptr;
+    if (planes) {
+        op = static_cast<l3d_plane*>(malloc((h->plane_list.size() + 1) * sizeof(l3d_plane)));                       // (one spare record)
+        if (!op) return const_cast<L*>(h)->fail(L3D_ERR_NOMEM, "malloc");
+        if (!h->plane_list.empty()) memcpy(op, h->plane_list.data(), h->plane_list.size() * sizeof(l3d_plane));
+    }
+    if (members) {
+        om = static_cast<l3d_plane_member*>(malloc((h->plane_members.size() + 1) * sizeof(l3d_plane_member)));
+        if (!om) { free(op); return const_cast<L*>(h)->fail(L3D_ERR_NOMEM, "malloc"); }
+        if (!h->plane_members.empty()) memcpy(om, h->plane_members.data(), h->plane_members.size() * sizeof(l3d_plane_member));
+    }
+    if (planes) *planes = op;
+    if (members) *members = om;
+    if (n_planes) *n_planes = (int)h->plane_list.size();
+    if (n_members) *n_members = (int)h->plane_members.size();
+    if (per_line && !h->plane_per_line.empty()) memcpy(per_line, h->plane_per_line.data(), h->plane_per_line.size() * 4);
+    if (counts) memcpy(counts, h->plane_counts, sizeof(h->plane_counts));
+    return L3D_OK;
+}
+// the planes of the last finish as a Wavefront OBJ: per plane a group of the four corners of its rectangle, O + a u + b v, and one face
+int l3d_line3d_save_planes(const l3d_line3d* h, const char* filename)
+{
+    if (h && h->node) return l3d_line3d_save_planes(rank0(h), filename);
+    if (!h || !filename) return L3D_ERR_INVALID;
+    if (!h->plane_valid || !h->result_valid) return const_cast<L*>(h)->fail(L3D_ERR_INVALID, "save_planes: the last finish ran without the planes");
+    FILE* f = fopen(filename, "w");
+    if (!f) return const_cast<L*>(h)->fail(L3D_ERR_INVALID, "save_planes: the file cannot be opened");
+    long long next = 1;
+    for (size_t k = 0; k < h->plane_list.size(); ++k) {
+        const l3d_plane& p = h->plane_list[k];
+        fprintf(f, "g plane_%zu\n", k);
+        const int ia[4] = { 0, 1, 1, 0 }, ib[4] = { 2, 2, 3, 3 };
+        for (int e = 0; e < 4; ++e) {
+            double X[3];
+            for (int d = 0; d < 3; ++d) X[d] = ((p.c * p.N[d]) + (p.rect[ia[e]] * p.u[d])) + (p.rect[ib[e]] * p.v[d]);
+            fprintf(f, "v %.17g %.17g %.17g\n", X[0], X[1], X[2]);
+        }
+        fprintf(f, "f %lld %lld %lld %lld\n", next, next + 1, next + 2, next + 3);
+        next += 4;
+    }
+    const bool ok = ferror(f) == 0;
+    return (fclose(f) == 0 && ok) ? L3D_OK : const_cast<L*>(h)->fail(L3D_ERR_INVALID, "save_planes: the file could not be written");
 }
 // where the world point links are filed ("CO-VISIBILITY"): 0 on the host as each view is added, 1 by prepare() on the device.  A node object: every rank
 // takes the setting, rank 0 counts

@@ -1116,11 +1116,13 @@ void junction_geometry(const FinalLine& fl, double* q)
     q[0] = P.x; q[1] = P.y; q[2] = P.z; q[3] = Q.x; q[4] = Q.y; q[5] = Q.z;
 }
 
-int junction_result(L* h)
+int junction_result(L* h, JunctionHandOn* hand)
 {
+    const bool record = h->junc_on;                        // (off: the search runs for the planes alone)
     h->junc_valid = false;
     h->junc_vertices.clear(); h->junc_per_line.clear();
     for (int k = 0; k < 10; ++k) h->junc_counts[k] = 0;
+    if (hand) { hand->sigma.assign(h->result.size(), 0.0); hand->seeds.clear(); }
     const double t0 = now_s();
     const size_t n = h->result.size();
     std::vector<double> lines(6 * n + 6), tol(n + 1), ext(n + 1);
@@ -1133,6 +1135,7 @@ int junction_result(L* h)
             bool missing = false;
             const double sigma = line_sigma(h, fl, missing);
             if (missing) { bad.store(1, std::memory_order_relaxed); continue; }
+            if (hand) hand->sigma[l] = sigma;
             const double v[3] = { q[3] - q[0], q[4] - q[1], q[5] - q[2] };
             const double len = std::sqrt(((v[0] * v[0]) + (v[1] * v[1])) + (v[2] * v[2]));
             const double a = h->junc_ext_px * sigma, b = h->junc_max_ext_rel * len;
@@ -1148,8 +1151,18 @@ int junction_result(L* h)
     prm.crossings = 0; prm.pad = 0;
     std::vector<int32_t> node_vertex(2 * n + 2), node_attach(2 * n + 2);
     l3d_junction_record* rec = nullptr; l3d_junction_vertex* vert = nullptr; int n_rec = 0, n_vert = 0;
-    const int rc = l3d_junction_lines(h->ctx, lines.data(), tol.data(), ext.data(), (int)n, &prm, &rec, &n_rec, node_vertex.data(), &vert, &n_vert, node_attach.data(), h->junc_counts);
+    int32_t counts[8];
+    const int rc = l3d_junction_lines(h->ctx, lines.data(), tol.data(), ext.data(), (int)n, &prm, &rec, &n_rec, node_vertex.data(), &vert, &n_vert, node_attach.data(), counts);
     if (rc) return h->fail(rc, std::string("junctions: ") + l3d_last_error(h->ctx));
+    if (hand)
+        for (int k = 0; k < n_rec; ++k)
+            if (rec[k].where_i != L3D_JUNCTION_INTERIOR || rec[k].where_j != L3D_JUNCTION_INTERIOR) { hand->seeds.push_back(rec[k].i); hand->seeds.push_back(rec[k].j); }
+    if (!record) {                                         // the vertices are discarded: get_junctions still refuses
+        l3d_free(rec); l3d_free(vert);
+        if (hopt(h).timing) fprintf(stderr, "[l3d finish] %-28s %8.2f ms (%zu lines, %d records)\n", "junction search (planes)", (now_s() - t0) * 1e3, n, n_rec);
+        return L3D_OK;
+    }
+    for (int k = 0; k < 8; ++k) h->junc_counts[k] = counts[k];
     h->junc_vertices.assign(vert, vert + n_vert);
     h->junc_per_line.assign(4 * n, -1);
     for (size_t l = 0; l < n; ++l)
@@ -1190,6 +1203,43 @@ int junction_result(L* h)
     if (hopt(h).timing)
         fprintf(stderr, "[l3d finish] %-28s %8.2f ms (%zu lines, %d records, %d vertices, %d ends attached, %d ends moved)\n", "junctions", (now_s() - t0) * 1e3, n, n_rec, n_vert,
                 h->junc_counts[7], h->junc_counts[8]);
+    return L3D_OK;
+}
+
+// The planes of the result ("PLANES OF 3-D LINES" in include/line3d_amd.h, on the object), after the junctions (and their snap) and before the support
+// gather.  A line's P is the start of its first 3-D segment, Q the end of its last, as the junctions left them; tol = dist_px x the sigma the junction
+// search computed; cos_max is the junctions' own, cos_min = cos(angle_deg pi / 180); the seeds are the L and T records of that search, in record order
+int plane_result(L* h, const JunctionHandOn& hand)
+{
+    h->plane_valid = false;
+    h->plane_list.clear(); h->plane_members.clear(); h->plane_per_line.clear();
+    for (int k = 0; k < 8; ++k) h->plane_counts[k] = 0;
+    const double t0 = now_s();
+    const size_t n = h->result.size();
+    if (hand.sigma.size() != n) return h->fail(L3D_ERR_INVALID, "planes: the junction search did not run on this result");
+    std::vector<double> lines(6 * n + 6), tol(n + 1);
+    for (size_t l = 0; l < n; ++l) {
+        junction_geometry(h->result[l], &lines[6 * l]);
+        tol[l] = h->plane_dist_px * hand.sigma[l];
+        if (!(tol[l] >= 0.0)) tol[l] = 0.0;                                       // (0 times an overflowed mean)
+    }
+    l3d_plane_params prm;
+    prm.cos_max = std::cos(h->junc_angle_min_deg * 3.14159265358979323846 / 180.0);
+    prm.cos_min = std::cos(h->plane_angle_deg * 3.14159265358979323846 / 180.0);
+    prm.min_lines = h->plane_min_lines; prm.pad = 0;
+    const int m = (int)(hand.seeds.size() / 2);
+    std::vector<int32_t> hyp_plane((size_t)m + 1);
+    l3d_plane* pl = nullptr; l3d_plane_member* mem = nullptr; int n_pl = 0, n_mem = 0;
+    const int rc = l3d_plane_lines(h->ctx, lines.data(), tol.data(), (int)n, hand.seeds.data(), m, &prm, &pl, &n_pl, &mem, &n_mem, hyp_plane.data(), h->plane_counts);
+    if (rc) return h->fail(rc, std::string("planes: ") + l3d_last_error(h->ctx));
+    h->plane_list.assign(pl, pl + n_pl);
+    h->plane_members.assign(mem, mem + n_mem);
+    h->plane_per_line.assign(n, 0);
+    for (int k = 0; k < n_mem; ++k) ++h->plane_per_line[(size_t)mem[k].line];
+    l3d_free(pl); l3d_free(mem);
+    h->plane_valid = true;
+    if (hopt(h).timing)
+        fprintf(stderr, "[l3d finish] %-28s %8.2f ms (%zu lines, %d seeds, %d planes, %d member records)\n", "planes", (now_s() - t0) * 1e3, n, m, n_pl, n_mem);
     return L3D_OK;
 }
 

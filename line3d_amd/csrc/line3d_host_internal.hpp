@@ -272,6 +272,15 @@ struct l3d_line3d {
     int32_t junc_counts[10] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
     std::vector<l3d_junction_vertex> junc_vertices;
     std::vector<int32_t> junc_per_line;
+    // planes of the result's lines (l3d_line3d_set_planes; off by default, reset keeps it) and what the last finish with it on recorded: the planes, the
+    // member records, per line the number of planes it lies in, and l3d_plane_lines' counts[8]
+    bool plane_on = false, plane_valid = false;
+    double plane_dist_px = 4.0, plane_angle_deg = 10.0;
+    int plane_min_lines = 3;
+    int32_t plane_counts[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+    std::vector<l3d_plane> plane_list;
+    std::vector<l3d_plane_member> plane_members;
+    std::vector<int32_t> plane_per_line;
     bool fit_on_device = false;                                // the last line fit ran on the resident hypothesis table (l3d_fit_clusters / l3d_fit_labelled_clusters)
 
     // co-visibility counted on the device (l3d_line3d_set_covisibility; 0 by default, reset keeps the setting): the views' world point lists in add
@@ -424,7 +433,12 @@ int merge_result(L* h);
 int support_gather(L* owner, const l3d_support_params& prm, std::vector<l3d_line_support>& rec, std::vector<int64_t>& line_start, std::vector<int32_t>& line_views, int64_t* counts);
 // the gather as the last step of a finish, and the member lists extended by it: after merge_result and refine_result
 int support_result(L* h);
-// the junctions of the result's lines (l3d_junction_lines), the ends snapped when asked for: after merge_result and refine_result, before support_result
-int junction_result(L* h);
+// what the junction search hands on to the planes: per line the sigma its tolerance was made from, and the L and T records as pairs (i, j), in record order
+struct JunctionHandOn { std::vector<double> sigma; std::vector<int32_t> seeds; };
+// the junctions of the result's lines (l3d_junction_lines), the ends snapped when asked for: after merge_result and refine_result, before support_result.
+// With the junctions option off (the planes need the search): the stored parameters, no snap, nothing recorded.  hand (optional): filled for plane_result
+int junction_result(L* h, JunctionHandOn* hand = nullptr);
+// the planes of the result's lines (l3d_plane_lines) over the junction search's seeds: after junction_result, before support_result
+int plane_result(L* h, const JunctionHandOn& hand);
 
 }  // namespace l3dh

@@ -544,6 +544,40 @@ class Line3D:
         its own; an end that stays in a vertex uses the shared index; coordinates as %.17g.  Works without the junctions too (no shared vertices)."""
         self._chk(self.lib.l3d_line3d_save_wireframe(self.h, str(filename).encode()))
 
+    # -- planes of the result's lines: faces for the wireframe (no counterpart in the reference; DESIGN.md 4m) ------------------------------------
+    def set_planes(self, on=True, dist_px=4.0, angle_deg=10.0, min_lines=3):
+        """l3d_line3d_set_planes: with it on, finish / compute3Dmodel find which lines of the result lie in one plane (capi.Context.plane_lines: every
+        pair of lines that meet spans a hypothesis, hypotheses within angle_deg whose lines lie within dist_px pixel footprints of each other's planes
+        are grouped, a plane needs min_lines member lines), after the junctions -- whose search runs for the seeds even when that option is off -- and
+        before the support gather.  Off by default; reset keeps it."""
+        self._chk(self.lib.l3d_line3d_set_planes(self.h, C.c_int(int(bool(on))), C.c_double(float(dist_px)), C.c_double(float(angle_deg)), C.c_int(int(min_lines))))
+
+    def planes(self):
+        """l3d_line3d_get_planes: what the last finish with the planes on recorded -- dict of planes (capi.PLANE array: N, c, u, v, rect, rep, first_hyp,
+        n_hyp, n_lines), members (capi.PLANE_MEMBER array ascending by (plane, line)), planes_per_line (per line of getResult() the number of planes it
+        lies in), and the counts: eligible_lines, eligible_hypotheses, hypothesis_edges, components, hypotheses_released, candidates_dropped,
+        planes_found, member_records."""
+        nl = C.c_int(0)
+        self._chk(self.lib.l3d_line3d_result_sizes(self.h, C.byref(nl), None, None))
+        n = nl.value
+        pl, mem, npl, nm = C.POINTER(capi.Plane)(), C.POINTER(capi.PlaneMember)(), C.c_int(0), C.c_int(0)
+        per, cnt = np.zeros(max(1, n), np.int32), np.zeros(8, np.int32)
+        self._chk(self.lib.l3d_line3d_get_planes(self.h, C.byref(pl), C.byref(npl), C.byref(mem), C.byref(nm), _p(per), _p(cnt)))
+        out = {"planes": np.frombuffer(C.string_at(pl, npl.value * 128), capi.PLANE).copy() if npl.value else np.zeros(0, capi.PLANE),
+               "members": np.frombuffer(C.string_at(mem, nm.value * 16), capi.PLANE_MEMBER).copy() if nm.value else np.zeros(0, capi.PLANE_MEMBER),
+               "planes_per_line": per[:n].copy()}
+        self.lib.l3d_free(pl)
+        self.lib.l3d_free(mem)
+        for i, k in enumerate(("eligible_lines", "eligible_hypotheses", "hypothesis_edges", "components", "hypotheses_released", "candidates_dropped", "planes_found",
+                               "member_records")):
+            out[k] = int(cnt[i])
+        return out
+
+    def save3DPlanesAsOBJ(self, filename):
+        """l3d_line3d_save_planes: the planes of the last finish as a Wavefront OBJ -- per plane a group of the four corners of its rectangle and one face;
+        coordinates as %.17g."""
+        self._chk(self.lib.l3d_line3d_save_planes(self.h, str(filename).encode()))
+
     def refinement_input(self):
         """l3d_line3d_refinement_input (inspection): what a refinement of the current result is fed with -- dict of group_start, member_cam, member_seg,
         member_pts, cameras (normalised frame) and Rinv (3, 3), scale_inv, tneg (3,) of Line3D::inverseTransform."""

@@ -104,7 +104,7 @@ def result_basename(max_width=-1, neighbors=10, min_uncertainty=1.0, max_uncerta
 
 
 def reconstruct(scene: SfmScene, segments, image_sizes, out_dir=None, neighbors=10, diffusion=False, device=0, masks=None, mask_mode="split", mask_threshold=1,
-                mask_keep_permille=500, mask_max_gap=0, mask_min_length=0.0, covisibility="host", merge=False, support=False, junctions=False, **line3d_kwargs):
+                mask_keep_permille=500, mask_max_gap=0, mask_min_length=0.0, covisibility="host", merge=False, support=False, junctions=False, planes=False, **line3d_kwargs):
     """The drivers' flow (main_vsfm.cpp:226-325) with detected segments in place of images: K from focal and image size,
     addImage with the world point lists, compute3Dmodel, optional STL + TXT output under the drivers' file name.
     segments[i]: (S,4) float32 of camera i (undistorted image coordinates); image_sizes[i]: (width, height).
@@ -119,7 +119,8 @@ def reconstruct(scene: SfmScene, segments, image_sizes, out_dir=None, neighbors=
     merge: the duplicate 3-D lines of the result are merged on the device (Line3D.set_merging, defaults) before it is written.
     support: every line's 2-D segments are extended by the segments of ALL views that lie on it (Line3D.set_support, defaults), as the last step.
     junctions: where the lines meet is found on the device (Line3D.set_junctions, defaults; Line3D.junctions() and save3DLinesAsOBJ then hold the
-    wireframe)."""
+    wireframe).
+    planes: which lines lie in one plane is found on the device (Line3D.set_planes, defaults; Line3D.planes() and save3DPlanesAsOBJ then hold the faces)."""
     import os
     from . import capi
     from .pipeline import Line3D
@@ -131,6 +132,8 @@ def reconstruct(scene: SfmScene, segments, image_sizes, out_dir=None, neighbors=
         l3d.set_support(True)
     if junctions:
         l3d.set_junctions(True)
+    if planes:
+        l3d.set_planes(True)
     if covisibility != "host":
         l3d.set_covisibility(covisibility)
 
@@ -192,7 +195,7 @@ def write_ppm(path, image):
 
 def reconstruct_from_images(scene: SfmScene, load_image, data_directory, out_dir=None, neighbors=10, diffusion=False, max_width=1920,
                             load_and_store_segments=True, device=0, batch=16, refine=False, alpha=None, out_size=None, covisibility="host", overlay_dir=None,
-                            merge=False, support=False, junctions=False, **line3d_kwargs):
+                            merge=False, support=False, junctions=False, planes=False, **line3d_kwargs):
     """The drivers' flow (main_vsfm.cpp:226-325) from pixels: per camera the image load_image(i, name) returns -- `bytes`: the contents of a
     baseline JPEG file, decoded on the device (Line3D.add_image_jpeg); or a uint8 array H x W or H x W x 3, decoded by the caller; or an image
     in device memory (a torch device tensor, a capi.device_image descriptor), read where it lies --, K from the focal length and the image size, the image undistorted with the camera's coefficients and its
@@ -206,6 +209,7 @@ def reconstruct_from_images(scene: SfmScene, load_image, data_directory, out_dir
     support: every line's 2-D segments are extended by the segments of ALL views that lie on it (Line3D.set_support, defaults), after the refinement;
     the TXT file and the overlays then show them.
     junctions: where the lines meet is found on the device (Line3D.set_junctions, defaults), after the refinement and before the support.
+    planes: which lines lie in one plane is found on the device (Line3D.set_planes, defaults), after the junctions and before the support.
     alpha, out_size (either given; "A REMAP" in include/line3d_amd.h): a camera with an active lens -- a COLMAP camera's, or an NVM / bundler camera's
     k1, k2 as a BROWN lens -- is PLANNED (capi.undistort_plan(lens, size, alpha or 0, out_size), once per distinct camera) and the view is added
     with the planned K and size, the blank pixels of the resampling invalid for the detector.  Neither given: what it did before.
@@ -224,6 +228,8 @@ def reconstruct_from_images(scene: SfmScene, load_image, data_directory, out_dir
         l3d.set_support(True)
     if junctions:
         l3d.set_junctions(True)
+    if planes:
+        l3d.set_planes(True)
     if covisibility != "host":
         l3d.set_covisibility(covisibility)
     entries = []
