@@ -2162,6 +2162,93 @@ typedef struct l3d_test_affinity_part {
 int l3d_test_affinity_fill(l3d_ctx* ctx, const l3d_affinity_input* in, l3d_test_affinity_part* part, unsigned char* flags, int32_t* needs_prev,
                            int32_t** pairs, float** weights, uint64_t* first);
 
+/* The slot kernels of the segment-sharded chain (l3d_chain_sharded.hip) on slots the caller hands in, exported for tests
+ * (tests/test_gpu_shard_slots.py).  No chain is opened and no collective runs: each hook launches the product's own kernels under the product's own
+ * grid rules, after everything a kernel uses as an index or a count has been checked on the host (L3D_ERR_INVALID before anything is launched).
+ *   geom   the six inputs of the slot's geometry (l3d_test_shard_plan: largest S_src <= 16384, largest N in [1, 255], world in [1, 64], slot_records
+ *          in [1, 2^20], option slot_cams_min, n_views <= 4096) and `ring`, the view blocks of the gathered buffer (0: n_views, as the geometry sets it;
+ *          a ring-mode run sets fewer).  View j's slots lie in block j % ring, rank r's at (block * world + r) * slot_bytes. */
+typedef struct l3d_test_shard_geom {
+    int32_t maxS, maxN, world, slot_records, slot_cams_min, n_views, ring, pad;
+} l3d_test_shard_geom;
+
+/* k_slot_write for ONE view's verified candidates and ONE rank's range [s0, s1) of its segments.
+ *   S, N, row_start, cand_meta, cand_depths, cand_conf, kept_cnt, local2global: as l3d_test_kept_write takes them (the whole view); best S x 2: the
+ *   depth pair of every segment's best hypothesis; cand_cap: what the kernel guards against row_start[S*N].
+ * out: slot, the slot_bytes of the geometry: 0xff bytes where the kernel did not write, 0x7f bytes in the best positions (-1 is an answer).  The hook
+ *   keeps 256 guard bytes behind the slot on the device and reports a write into them as L3D_ERR_INVALID.
+ * Refused before launch: N outside [1, 255], row_start not ascending from 0, a candidate whose camera is not its row's or whose target does not fit
+ * 16 bits, kept_cnt that is not the count of confidences above 1, a range outside [0, S] or longer than seg_cap - 1, N > maxN, S > maxS. */
+int l3d_test_shard_slot_write(l3d_ctx* ctx, int S, int N, const int32_t* row_start, const uint32_t* cand_meta, const float* cand_depths, const float* cand_conf,
+                              const int32_t* kept_cnt, const uint32_t* local2global, const float* best, int s0, int s1, const l3d_test_shard_geom* geom,
+                              int cand_cap, unsigned char* slot);
+
+/* The collect step of the sharded chain for view k and one rank's range [s0, s1): k_exist_count_slots, the range scan, k_place_slots and (sort_apart)
+ * the launch that orders the runs, over a gathered buffer of the caller's (ring x world x slot_bytes).
+ *   views, n_views, k; rowA, metaA, depthsA, n_A, rowcnt: as l3d_test_collect_candidates reads them (every view's S_src <= maxS and N <= maxN)
+ * sel in:  s0, s1; cand_cap: the candidate capacity the kernels guard, also the entries of cand_meta / cand_depths (it must hold the range's
+ *          candidates: this hook does not run the overflow path); sort_apart; slot_scan_grain: option slot_scan_grain for the call.
+ * out:     row_start S*N + 1, cursor S*N, seg_order S, cand_meta cand_cap x 2, cand_depths cand_cap x 4 (0xff bytes where no kernel wrote: the rows
+ *          outside the range are not the rank's); sel->wps (workgroups per (source, rank) list), blocks_move, R (row_start[S*N]: the range's total).
+ * Refused before launch, beside what l3d_test_collect_candidates refuses: a source whose ring block a later view in front of k has overwritten
+ * (source_index + ring < k); and, in every slot of a source that lists view k as a neighbour: n_kept outside [0, slot_records] (unless the header
+ * carries an overflow bit), a header range that is not 0 <= s0 <= s1 <= 65536 with s1 - s0 <= seg_cap - 1; in a slot that holds records: a record
+ * whose segment is outside the header's range, whose camera is no neighbour of its view or whose target does not fit 16 bits, records out of (segment,
+ * local camera) order, a side word that is not (local camera << 16 | target) of its record, a run-table entry (rows 0..N, columns 0..s1 - s0) that is
+ * not the position of the first record at or behind (segment, camera).  The body of an overflowed or empty slot is not looked at: no kernel may read it. */
+typedef struct l3d_test_shard_collect_path {
+    int32_t s0, s1, cand_cap, sort_apart, slot_scan_grain;
+    int32_t wps, blocks_move, R;                        /* out */
+} l3d_test_shard_collect_path;
+int l3d_test_shard_collect(l3d_ctx* ctx, const l3d_chain_view* views, int n_views, int k, const unsigned char* gathered, const l3d_test_shard_geom* geom,
+                           const int32_t* rowA, const uint32_t* metaA, const float* depthsA, int n_A, const int32_t* rowcnt,
+                           l3d_test_shard_collect_path* sel, int32_t* row_start, uint32_t* cand_meta, float* cand_depths, int32_t* cursor, int32_t* seg_order);
+
+/* The consumers of the gathered blocks over ALL views' slots of the caller's (n_views x world x slot_bytes, view j's block at j):
+ *   k_shard_totals and k_check_slots over the headers in front of the slots (stride slot_bytes) and over the compact 32-byte table the retire run
+ *   leaves; k_pack_view per verified view; k_shard_pack_all once; k_shard_retire in the batches listed, over a ring of geom->ring blocks that the hook
+ *   fills as the run's exchanges would: view j's block goes to ring block j % ring (zeros for a view that is not verified) just before the first batch
+ *   enqueued at a view behind j.
+ * in:  verified (n_views bytes), keep (n_views bytes or NULL), best_off (n_views: where a view's best pairs and positions go, in entries), view_sn
+ *      (n_views x (S_src, N)), rt_off (n_views: where its run table starts in rt_all, in ints; read with retire_tables), batches (n_batches x (first,
+ *      count, the view the batch is enqueued at -- n_views: the final flush), as l3d_test_shard_retire lists them), retire_tables (the retire kernel
+ *      files side words and run tables: the geometry must have them), arena_cap (records the retire kernel guards), pack_cap (records of the pack-all
+ *      arena: must hold the verified views), best_cap (entries of the best arrays), rt_cap (ints of rt_all).
+ * out: stage (n_views x stage_bytes) and pack_hdr (n_views x 32 B) of k_pack_view; totals (2 x n_views x 2: stride slot_bytes, then 32) and check
+ *      (2 x 3 likewise); pa_* from k_shard_pack_all and rt_* from k_shard_retire: arena (pack_cap / arena_cap records), best (best_cap x 2), bestpos
+ *      (best_cap); base_dev (n_views + 2; zeros where not written, as the run starts them), hdr_all (n_views x world x 32 B), overflow (1 int), qt_arena
+ *      (arena_cap), rt_all (rt_cap).  0xff bytes where no kernel wrote, 0x7f in the best positions.
+ * Refused before launch: flags that are not 0 or 1; a view whose (S, N) exceeds the geometry or whose best pairs or run table end past their
+ * capacity; in a verified view's slot a header with R < 0, overflow outside [0, 7], a range that is not 0 <= s0 <= s1 <= S with s1 - s0 <= seg_cap -
+ * 1, or (no overflow bit) n_kept outside [0, slot_records]; verified views that keep more than pack_cap; batches that are not contiguous and ascending
+ * from view 0, that retire a view not yet exchanged (first + count > at), or that read a ring block already overwritten (first + ring < at). */
+typedef struct l3d_test_shard_pack_io {
+    const unsigned char* verified;
+    const unsigned char* keep;
+    const int64_t* best_off;
+    const int32_t* view_sn;
+    const int64_t* rt_off;
+    const int32_t* batches;
+    int32_t n_batches, retire_tables;
+    int64_t arena_cap, pack_cap, best_cap, rt_cap;
+    unsigned char* stage;                               /* out, from here on */
+    unsigned char* pack_hdr;
+    int32_t* totals;
+    int32_t* check;
+    l3d_match* pa_arena;
+    float* pa_best;
+    int32_t* pa_bestpos;
+    l3d_match* rt_arena;
+    float* rt_best;
+    int32_t* rt_bestpos;
+    int64_t* base_dev;
+    unsigned char* hdr_all;
+    int32_t* overflow;
+    uint32_t* qt_arena;
+    int32_t* rt_all;
+} l3d_test_shard_pack_io;
+int l3d_test_shard_pack(l3d_ctx* ctx, const unsigned char* gathered, const l3d_test_shard_geom* geom, l3d_test_shard_pack_io* io);
+
 #ifdef __cplusplus
 }
 #endif

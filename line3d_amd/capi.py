@@ -1230,6 +1230,34 @@ class KeptPath(C.Structure):
                 ("rebuild_blocks", C.c_int32), ("pad", C.c_int32), ("kept_base", C.c_uint64)]
 
 
+class ShardGeom(C.Structure):
+    """l3d_test_shard_geom (include/line3d_amd.h)"""
+    _fields_ = [("maxS", C.c_int32), ("maxN", C.c_int32), ("world", C.c_int32), ("slot_records", C.c_int32), ("slot_cams_min", C.c_int32),
+                ("n_views", C.c_int32), ("ring", C.c_int32), ("pad", C.c_int32)]
+
+
+class ShardCollectPath(C.Structure):
+    """l3d_test_shard_collect_path (include/line3d_amd.h)"""
+    _fields_ = [("s0", C.c_int32), ("s1", C.c_int32), ("cand_cap", C.c_int32), ("sort_apart", C.c_int32), ("slot_scan_grain", C.c_int32),
+                ("wps", C.c_int32), ("blocks_move", C.c_int32), ("R", C.c_int32)]
+
+
+class ShardPackIO(C.Structure):
+    """l3d_test_shard_pack_io (include/line3d_amd.h)"""
+    _fields_ = [("verified", C.c_void_p), ("keep", C.c_void_p), ("best_off", C.c_void_p), ("view_sn", C.c_void_p), ("rt_off", C.c_void_p),
+                ("batches", C.c_void_p), ("n_batches", C.c_int32), ("retire_tables", C.c_int32), ("arena_cap", C.c_int64), ("pack_cap", C.c_int64),
+                ("best_cap", C.c_int64), ("rt_cap", C.c_int64), ("stage", C.c_void_p), ("pack_hdr", C.c_void_p), ("totals", C.c_void_p),
+                ("check", C.c_void_p), ("pa_arena", C.c_void_p), ("pa_best", C.c_void_p), ("pa_bestpos", C.c_void_p), ("rt_arena", C.c_void_p),
+                ("rt_best", C.c_void_p), ("rt_bestpos", C.c_void_p), ("base_dev", C.c_void_p), ("hdr_all", C.c_void_p), ("overflow", C.c_void_p),
+                ("qt_arena", C.c_void_p), ("rt_all", C.c_void_p)]
+
+
+def shard_geom(geom) -> "ShardGeom":
+    """the geometry inputs of the sharded chain's test hooks from a dict: maxS, maxN, world, slot_records, slot_cams_min, n_views and (optional) ring"""
+    return ShardGeom(int(geom["maxS"]), int(geom["maxN"]), int(geom["world"]), int(geom["slot_records"]), int(geom["slot_cams_min"]), int(geom["n_views"]),
+                     int(geom.get("ring", 0)), 0)
+
+
 # l3d_test_products_path: build / refused
 PROD_TRANSPOSED, PROD_SORTED = 1, 2
 PROD_REFUSED_WIDE_VIEW, PROD_REFUSED_UNORDERED = 1, 2
@@ -1837,6 +1865,98 @@ class Context:
         return dict(records=records, side=side, rt=rt, best_pos=best_pos, kept_base=int(sel.kept_base), n_kept=int(sel.n_kept), R=int(sel.R),
                     overflow=int(sel.overflow), n_want=int(sel.n_want), rebuild_err=int(sel.rebuild_err), rebuild_blocks=int(sel.rebuild_blocks),
                     jobs=[dict(n=int(cj[i].n), qt=outs[i][0][:int(cj[i].n)], rt=outs[i][1]) for i in range(len(jobs))])
+
+    def test_shard_slot_write(self, N, row_start, cand_meta, cand_depths, cand_conf, kept_cnt, l2g, best, s0, s1, geom, cand_cap=None):
+        """l3d_test_shard_slot_write: k_slot_write for one view's verified candidates and the range [s0, s1) -> the slot's bytes (uint8, slot_bytes of
+        the geometry; 0xff where the kernel did not write, 0x7f in the best positions).  geom: the dict shard_geom takes; cand_cap None: exactly R.
+        Nothing is checked here: a broken table is the library's to refuse."""
+        row_start = np.ascontiguousarray(row_start, dtype=np.int32)
+        cand_meta = np.ascontiguousarray(cand_meta, dtype=np.uint32).reshape(-1, 2)
+        cand_depths = np.ascontiguousarray(cand_depths, dtype=np.float32).reshape(-1, 4)
+        cand_conf = np.ascontiguousarray(cand_conf, dtype=np.float32)
+        kept_cnt, l2g = np.ascontiguousarray(kept_cnt, dtype=np.int32), np.ascontiguousarray(l2g, dtype=np.uint32)
+        best = np.ascontiguousarray(best, dtype=np.float32).reshape(-1, 2)
+        S, R = len(kept_cnt), len(cand_conf)
+        assert row_start.shape == (S * N + 1,) and len(cand_meta) == R and len(cand_depths) == R and l2g.shape == (N,) and len(best) == S
+        g = shard_geom(geom)
+        try:
+            n_bytes = shard_slot_geometry(g.maxS, g.maxN, g.world, g.slot_records, g.slot_cams_min, g.n_views)["slot_bytes"]
+        except L3DError:
+            n_bytes = 0                 # (a geometry the library refuses: the call below says so)
+        slot = np.zeros(max(1, n_bytes), np.uint8)
+        nz = lambda a: _p(a) if a.size else None
+        self._chk(self.lib.l3d_test_shard_slot_write(self.h, C.c_int(S), C.c_int(N), _p(row_start), nz(cand_meta), nz(cand_depths), nz(cand_conf), nz(kept_cnt), _p(l2g),
+                                                     nz(best), C.c_int(int(s0)), C.c_int(int(s1)), C.byref(g), C.c_int(R if cand_cap is None else int(cand_cap)), _p(slot)))
+        return slot[:n_bytes]
+
+    def test_shard_collect(self, views, k, gathered, geom, s0, s1, rowA, metaA, depthsA, rowcnt, cand_cap, sort_apart=0, slot_scan_grain=0):
+        """l3d_test_shard_collect: the collect step of the sharded chain for view k and the range [s0, s1) over the gathered bytes (uint8, ring x world
+        x slot_bytes).  views: as test_collect_candidates takes them (kept is not read).  -> dict(row_start, cand_meta (cand_cap, 2), cand_depths
+        (cand_cap, 4), cursor, seg_order, wps, blocks_move, R); 0xff bytes where no kernel wrote.  Nothing is checked here."""
+        n = len(views)
+        arr, keep = (ChainView * max(1, n))(), []
+        for j, v in enumerate(views):
+            l2g, tbm = np.ascontiguousarray(v["l2g"], dtype=np.uint32), np.ascontiguousarray(v["tbm"], dtype=np.int32)
+            sc, si = np.ascontiguousarray(v["source_cam"], dtype=np.int32), np.ascontiguousarray(v["source_index"], dtype=np.int32)
+            keep += [l2g, tbm, sc, si]
+            e = arr[j]
+            e.view_id, e.S_src, e.N, e.n_tbm, e.n_sources = int(v["id"]), int(v["S"]), len(l2g), int(v["n_tbm"]), len(sc)
+            e.local2global, e.to_be_matched, e.source_cam, e.source_index = l2g.ctypes.data, tbm.ctypes.data, sc.ctypes.data, si.ctypes.data
+        S, N = int(views[k]["S"]), len(views[k]["l2g"])
+        gathered = np.ascontiguousarray(gathered, dtype=np.uint8)
+        rowA, rowcnt = np.ascontiguousarray(rowA, dtype=np.int32), np.ascontiguousarray(rowcnt, dtype=np.int32)
+        metaA, depthsA = np.ascontiguousarray(metaA, dtype=np.uint32).reshape(-1, 2), np.ascontiguousarray(depthsA, dtype=np.float32).reshape(-1, 4)
+        assert rowA.shape == rowcnt.shape == (S * N,) and len(metaA) == len(depthsA)
+        g = shard_geom(geom)
+        sel = ShardCollectPath(int(s0), int(s1), int(cand_cap), int(sort_apart), int(slot_scan_grain), 0, 0, 0)
+        out = dict(row_start=np.zeros(S * N + 1, np.int32), cand_meta=np.zeros((int(cand_cap), 2), np.uint32), cand_depths=np.zeros((int(cand_cap), 4), np.float32),
+                   cursor=np.zeros(S * N, np.int32), seg_order=np.zeros(S, np.int32))
+        nz = lambda a: _p(a) if a.size else None
+        self._chk(self.lib.l3d_test_shard_collect(self.h, arr, C.c_int(n), C.c_int(int(k)), nz(gathered), C.byref(g), nz(rowA), nz(metaA), nz(depthsA), C.c_int(len(metaA)),
+                                                  nz(rowcnt), C.byref(sel), _p(out["row_start"]), nz(out["cand_meta"]), nz(out["cand_depths"]), nz(out["cursor"]),
+                                                  nz(out["seg_order"])))
+        out.update(wps=int(sel.wps), blocks_move=int(sel.blocks_move), R=int(sel.R))
+        return out
+
+    def test_shard_pack(self, gathered, geom, verified, best_off, view_sn, batches, arena_cap, pack_cap, best_cap, keep=None, rt_off=None, rt_cap=0,
+                        retire_tables=0):
+        """l3d_test_shard_pack: the consumers of the gathered blocks over all views' slots (uint8, n_views x world x slot_bytes).  batches: (first, count,
+        enqueued at view) triples.  -> dict(stage (n_views, stage_bytes) uint8, pack_hdr (n_views, 32) uint8, totals (2, n_views, 2), check (2, 3),
+        pa_arena / rt_arena (MATCH_DTYPE), pa_best / rt_best (best_cap, 2), pa_bestpos / rt_bestpos, base_dev (n_views + 2) int64, hdr_all (n_views,
+        world, 8) int32, overflow, qt_arena (arena_cap) uint32, rt_all (rt_cap) int32).  Nothing is checked here."""
+        g = shard_geom(geom)
+        nv, W = g.n_views, g.world
+        try:
+            stage_bytes = shard_slot_geometry(g.maxS, g.maxN, g.world, g.slot_records, g.slot_cams_min, g.n_views)["stage_bytes"]
+        except L3DError:
+            stage_bytes = 0
+        gathered = np.ascontiguousarray(gathered, dtype=np.uint8)
+        ver, bo = np.ascontiguousarray(verified, dtype=np.uint8), np.ascontiguousarray(best_off, dtype=np.int64)
+        sn = np.ascontiguousarray(view_sn, dtype=np.int32).reshape(-1, 2)
+        bt = np.ascontiguousarray(batches, dtype=np.int32).reshape(-1, 3)
+        kp = None if keep is None else np.ascontiguousarray(keep, dtype=np.uint8)
+        ro = None if rt_off is None else np.ascontiguousarray(rt_off, dtype=np.int64)
+        assert len(ver) == len(bo) == len(sn) == nv and (kp is None or len(kp) == nv) and (ro is None or len(ro) == nv)
+        one = lambda n: max(1, int(n))
+        out = dict(stage=np.zeros((nv, one(stage_bytes)), np.uint8), pack_hdr=np.zeros((nv, 32), np.uint8), totals=np.zeros((2, nv, 2), np.int32),
+                   check=np.zeros((2, 3), np.int32), pa_arena=np.zeros(one(pack_cap), MATCH_DTYPE), pa_best=np.zeros((one(best_cap), 2), np.float32),
+                   pa_bestpos=np.zeros(one(best_cap), np.int32), rt_arena=np.zeros(one(arena_cap), MATCH_DTYPE), rt_best=np.zeros((one(best_cap), 2), np.float32),
+                   rt_bestpos=np.zeros(one(best_cap), np.int32), base_dev=np.zeros(nv + 2, np.int64), hdr_all=np.zeros((nv, W, 8), np.int32),
+                   overflow=np.zeros(1, np.int32), qt_arena=np.zeros(one(arena_cap), np.uint32), rt_all=np.zeros(one(rt_cap), np.int32))
+        io = ShardPackIO()
+        io.verified, io.keep, io.best_off, io.view_sn = ver.ctypes.data, None if kp is None else kp.ctypes.data, bo.ctypes.data, sn.ctypes.data
+        io.rt_off, io.batches, io.n_batches, io.retire_tables = None if ro is None else ro.ctypes.data, bt.ctypes.data if len(bt) else None, len(bt), int(retire_tables)
+        io.arena_cap, io.pack_cap, io.best_cap, io.rt_cap = int(arena_cap), int(pack_cap), int(best_cap), int(rt_cap)
+        for name in ("stage", "pack_hdr", "totals", "check", "pa_arena", "pa_best", "pa_bestpos", "rt_arena", "rt_best", "rt_bestpos", "base_dev", "hdr_all", "overflow",
+                     "qt_arena", "rt_all"):
+            setattr(io, name, out[name].ctypes.data)
+        self._chk(self.lib.l3d_test_shard_pack(self.h, _p(gathered) if gathered.size else None, C.byref(g), C.byref(io)))
+        for name, n in (("pa_arena", pack_cap), ("rt_arena", arena_cap), ("qt_arena", arena_cap), ("pa_best", best_cap), ("rt_best", best_cap), ("pa_bestpos", best_cap),
+                        ("rt_bestpos", best_cap), ("rt_all", rt_cap)):
+            out[name] = out[name][:int(n)]
+        out["stage"] = out["stage"][:, :stage_bytes]
+        out["overflow"] = int(out["overflow"][0])
+        return out
 
     def chain_products_get(self, n_dense: int, n_pot: int, slack: int = 0):
         """l3d_chain_products_get: (pot_start int64 (n_dense + 1,), pot_tgt int32 (n_pot + slack,), best MATCH_DTYPE (n_dense,)).  The slots of

@@ -65,7 +65,7 @@ __global__ void k_exist_count_slots(const unsigned char* __restrict__ G, SlotGeo
     const unsigned want = (unsigned)src_slot[src];
     const int stride = gridDim.x * blockDim.x;
     int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (side && g.rt_off && (int)want <= g.max_n) {
+    if (side) {                                                 // (a slot with side words has a run table, and a neighbour's local number is a row of it: slot_geometry)
         if (n <= 0) return;                                     // (an overflowed slot holds no records and no run table)
         // run tables: the runs of this view's camera in the rank's slot, sixteen lanes per run
         const int* rt = reinterpret_cast<const int*>(slot + g.rt_off);
@@ -77,15 +77,6 @@ __global__ void k_exist_count_slots(const unsigned char* __restrict__ G, SlotGeo
             const int a = r0[sl], b = r1[sl];
             for (int k = a + gl; k < b; k += 16) { const unsigned w = side[k]; const int u = (int)(w & 0xffffu); if (u >= s0 && u < s1) atomicAdd(&rowcnt[u * N + cam], 1); }
         }
-        return;
-    }
-    if (side) {
-        auto count = [&](unsigned w) { const int u = (int)(w & 0xffffu); if ((w >> 16) == want && u >= s0 && u < s1) atomicAdd(&rowcnt[u * N + cam], 1); };
-        for (; i + 3 * stride < n; i += 4 * stride) {      // four words in flight per thread
-            const unsigned c0 = side[i], c1 = side[i + stride], c2 = side[i + 2 * stride], c3 = side[i + 3 * stride];
-            count(c0); count(c1); count(c2); count(c3);
-        }
-        for (; i < n; i += stride) count(side[i]);
         return;
     }
     for (; i < n; i += stride) {
@@ -121,10 +112,9 @@ __global__ __launch_bounds__(256) void k_place_slots(int blocks_move, int wps, c
         const Match m = kept[i];
         if (m.camID2 == view_id && (int)m.segID2 >= s0 && (int)m.segID2 < s1) place_reverse_match(m, N, cam, row_start, cursor, meta, depths);
     };
-    auto mine = [&](unsigned w) { const int u = (int)(w & 0xffffu); return (w >> 16) == want && u >= s0 && u < s1; };
     const int stride = wps * 256;
     int i = bx * 256 + (int)threadIdx.x;
-    if (side && g.rt_off && (int)want <= g.max_n) {     // run tables: k_exist_count_slots
+    if (side) {     // run tables: k_exist_count_slots
         if (n <= 0) return;
         const int* rt = reinterpret_cast<const int*>(slot + g.rt_off);
         const int* r0 = rt + (size_t)want * g.seg_cap;
@@ -135,17 +125,6 @@ __global__ __launch_bounds__(256) void k_place_slots(int blocks_move, int wps, c
             const int a = r0[sl], b = r1[sl];
             for (int k = a + gl; k < b; k += 16) { const unsigned w = side[k]; const int u = (int)(w & 0xffffu); if (u >= s0 && u < s1) place(k); }
         }
-        return;
-    }
-    if (side) {     // (four words in flight per thread; a record is read only where the word says it is this rank's)
-        for (; i + 3 * stride < n; i += 4 * stride) {
-            const unsigned c0 = side[i], c1 = side[i + stride], c2 = side[i + 2 * stride], c3 = side[i + 3 * stride];
-            if (mine(c0)) place(i);
-            if (mine(c1)) place(i + stride);
-            if (mine(c2)) place(i + 2 * stride);
-            if (mine(c3)) place(i + 3 * stride);
-        }
-        for (; i < n; i += stride) if (mine(side[i])) place(i);
         return;
     }
     for (; i < n; i += stride) place(i);
@@ -1429,6 +1408,435 @@ int l3d_test_shard_retire(int n_views, int window, int slot_ring, int partition,
     const int32_t v[6] = { p.ring_mode ? 1 : 0, p.ring_views, nb, s.retired, s.waited(), s.outstanding() ? 1 : 0 };
     memcpy(summary, v, sizeof(v));
     return nb <= max_batches ? L3D_OK : L3D_ERR_INVALID;
+}
+
+}  // extern "C"
+
+// ---- the slot kernels on slots handed in (tests/test_gpu_shard_slots.py): l3d_test_shard_slot_write, l3d_test_shard_collect, l3d_test_shard_pack.
+// Everything a kernel uses as an index or a count is checked here, on the host, before anything is launched.
+namespace {
+
+int test_shard_geom(l3d_ctx* c, const l3d_test_shard_geom* gi, SlotPlan& p, const char* what)
+{
+    if (!gi || gi->maxS < 0 || gi->maxS > 16384 || gi->maxN < 1 || gi->maxN > 255 || gi->world < 1 || gi->world > 64 || gi->slot_records < 1 || gi->slot_records > (1 << 20) ||
+        gi->n_views < 0 || gi->n_views > 4096 || gi->ring < 0 || gi->ring > 4096)
+        return fail(c, L3D_ERR_INVALID, std::string(what) + ": geometry out of range");
+    p = slot_geometry(gi->maxS, gi->maxN, gi->world, gi->slot_records, gi->slot_cams_min, gi->n_views);
+    if (gi->ring > 0) p.geom.ring = gi->ring;
+    return L3D_OK;
+}
+
+// the header of a slot whose view has S segments: empty text = fine
+std::string test_slot_header(const SlotHeader& h, const SlotGeom& g, int S)
+{
+    if (h.R < 0 || h.overflow < 0 || h.overflow > 7) return "a header with R < 0 or overflow outside [0, 7]";
+    if (h.s0 < 0 || h.s1 < h.s0 || h.s1 > S || h.s1 - h.s0 > g.seg_cap - 1) return "a header whose range is not 0 <= s0 <= s1 <= S with s1 - s0 <= seg_cap - 1";
+    if (!h.overflow && (h.n_kept < 0 || h.n_kept > g.slot_records)) return "a header whose n_kept is outside [0, slot_records]";
+    return std::string();
+}
+
+// the body of a slot of view w that holds records (header checked): records, side words, run table
+std::string test_slot_body(const unsigned char* slot, const SlotGeom& g, const l3d_chain_view& w)
+{
+    const SlotHeader* hd = reinterpret_cast<const SlotHeader*>(slot);
+    const int n = hd->n_kept, ns = hd->s1 - hd->s0;
+    const Match* rec = reinterpret_cast<const Match*>(slot + g.rec_off);
+    const unsigned* side = g.cam_off ? reinterpret_cast<const unsigned*>(slot + g.cam_off) : nullptr;
+    std::vector<std::pair<unsigned, int>> cams;
+    for (int q = w.N - 1; q >= 0; --q) cams.push_back(std::make_pair(w.local2global[q], q));
+    std::stable_sort(cams.begin(), cams.end(), [](const std::pair<unsigned, int>& a, const std::pair<unsigned, int>& b) { return a.first < b.first; });
+    std::vector<int> key((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        const Match& m = rec[i];
+        auto it = std::lower_bound(cams.begin(), cams.end(), std::make_pair(m.camID2, -1));
+        if (it == cams.end() || it->first != m.camID2) return "a record whose camera is no neighbour of its view";
+        if ((long long)m.segID1 < hd->s0 || (long long)m.segID1 >= hd->s1) return "a record whose segment is outside its header's range";
+        if (m.segID2 >= 65536u) return "a record whose target does not fit 16 bits";
+        // (several neighbours with one id: the lowest local number, as chain_source_slot finds it)
+        int q = it->second;
+        for (auto jt = it; jt != cams.end() && jt->first == m.camID2; ++jt) q = std::min(q, jt->second);
+        key[(size_t)i] = ((int)m.segID1 - hd->s0) * 256 + q;
+        if (i > 0 && key[(size_t)i] < key[(size_t)i - 1]) return "records out of (segment, local camera) order";
+        if (side && side[i] != (((unsigned)q << 16) | m.segID2)) return "a side word that is not (local camera << 16 | target) of its record";
+    }
+    if (g.rt_off) {
+        const int* rt = reinterpret_cast<const int*>(slot + g.rt_off);
+        for (int q = 0; q <= w.N; ++q)
+            for (int j = 0; j < ns; ++j) {
+                const int want = q < w.N ? j * 256 + q : (j + 1) * 256;
+                if (rt[(size_t)q * g.seg_cap + j] != (int)(std::lower_bound(key.begin(), key.end(), want) - key.begin())) return "a run-table entry that is not the position of the first record at or behind (segment, camera)";
+            }
+    }
+    return std::string();
+}
+
+}  // namespace
+
+extern "C" {
+
+// k_slot_write on one view's verified candidates of the caller's, for one rank's range: validated on the host, the slot filled with 0xff bytes (0x7f in the
+// best positions), 256 guard bytes behind it, then the launch l3d_shard_chain_enqueue makes.
+int l3d_test_shard_slot_write(l3d_ctx* c, int S, int N, const int32_t* row_start, const uint32_t* cand_meta, const float* cand_depths, const float* cand_conf,
+                              const int32_t* kept_cnt, const uint32_t* local2global, const float* best, int s0, int s1, const l3d_test_shard_geom* geom,
+                              int cand_cap, unsigned char* slot)
+{
+    if (!c) return L3D_ERR_INVALID;
+    SlotPlan plan;
+    if (int rc = test_shard_geom(c, geom, plan, "shard_slot_write")) return rc;
+    const SlotGeom g = plan.geom;
+    if (S < 0 || N < 1 || N > 255 || !row_start || !local2global || !slot || cand_cap < 0 || (S > 0 && (!kept_cnt || !best))) return fail(c, L3D_ERR_INVALID, "shard_slot_write: bad argument");
+    if (N > geom->maxN || S > geom->maxS) return fail(c, L3D_ERR_INVALID, "shard_slot_write: the view is larger than the geometry's largest");
+    if (s0 < 0 || s1 < s0 || s1 > S || s1 - s0 > g.seg_cap - 1) return fail(c, L3D_ERR_INVALID, "shard_slot_write: the range is outside [0, S] or longer than seg_cap - 1");
+    const size_t nrow = (size_t)S * N;
+    if (row_start[0] != 0) return fail(c, L3D_ERR_INVALID, "shard_slot_write: row_start must start at 0");
+    for (size_t i = 0; i < nrow; ++i) if (row_start[i + 1] < row_start[i]) return fail(c, L3D_ERR_INVALID, "shard_slot_write: row_start does not ascend");
+    const int R = row_start[nrow];
+    if (R > 0 && (!cand_meta || !cand_depths || !cand_conf)) return fail(c, L3D_ERR_INVALID, "shard_slot_write: candidates missing");
+    for (int y = 0; y < S; ++y) {
+        int kept = 0;
+        for (int q = 0; q < N; ++q)
+            for (int r = row_start[(size_t)y * N + q]; r < row_start[(size_t)y * N + q + 1]; ++r) {
+                if (cand_meta[2 * (size_t)r + 1] != (unsigned)q) return fail(c, L3D_ERR_INVALID, "shard_slot_write: a candidate's camera is not its row's");
+                if (cand_meta[2 * (size_t)r] >= 65536u) return fail(c, L3D_ERR_INVALID, "shard_slot_write: a target id does not fit 16 bits");
+                kept += cand_conf[r] > 1.0f ? 1 : 0;
+            }
+        if (kept_cnt[y] != kept) return fail(c, L3D_ERR_INVALID, "shard_slot_write: kept_cnt of segment " + std::to_string(y) + " is not its count of confidences above 1");
+    }
+
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    (void)hipGetLastError();
+    const size_t rcap = (size_t)std::max(R, 1), guard = 256;
+    HIPCHK(c, c->row_start.reserve((nrow + 1) * 4));
+    HIPCHK(c, c->cand_meta.reserve(rcap * 8)); HIPCHK(c, c->cand_depths.reserve(rcap * 16)); HIPCHK(c, c->cand_conf.reserve(rcap * 4));
+    HIPCHK(c, c->kept_cnt.reserve((size_t)S * 4 + 4)); HIPCHK(c, c->l2g.reserve((size_t)N * 4)); HIPCHK(c, c->best.reserve((size_t)S * 8 + 8));
+    HIPCHK(c, c->ch_send.reserve(g.slot_bytes + guard));
+    HIPCHK(c, hipMemcpyAsync(c->row_start.p, row_start, (nrow + 1) * 4, hipMemcpyHostToDevice, st));
+    if (R) {
+        HIPCHK(c, hipMemcpyAsync(c->cand_meta.p, cand_meta, (size_t)R * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(c->cand_depths.p, cand_depths, (size_t)R * 16, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(c->cand_conf.p, cand_conf, (size_t)R * 4, hipMemcpyHostToDevice, st));
+    }
+    if (S) {
+        HIPCHK(c, hipMemcpyAsync(c->kept_cnt.p, kept_cnt, (size_t)S * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(c->best.p, best, (size_t)S * 8, hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(c, hipMemcpyAsync(c->l2g.p, local2global, (size_t)N * 4, hipMemcpyHostToDevice, st));
+    unsigned char* dslot = c->ch_send.as<unsigned char>();
+    HIPCHK(c, hipMemsetAsync(dslot, 0xff, g.slot_bytes + guard, st));
+    HIPCHK(c, hipMemsetAsync(dslot + g.bpos_off, 0x7f, (size_t)g.seg_cap * 4, st));          // (-1 is an answer of the writer's: no kept match)
+    VerifyArgs va;
+    memset(&va, 0, sizeof(va));
+    va.row_start = c->row_start.as<int>(); va.cand_meta = c->cand_meta.as<uint2>(); va.cand_depths = c->cand_depths.as<float4>(); va.cand_conf = c->cand_conf.as<float>();
+    va.N = N; va.seg_begin = s0; va.seg_end = s1; va.nrow_total = (int)nrow; va.cand_cap = cand_cap; va.only_above = -1;
+    {
+        ProfScope p(c, "kept_write");
+        hipLaunchKernelGGL(k_slot_write, dim3(std::max(1, s1 - s0)), dim3(256), 0, st, va, c->kept_cnt.as<int>() + s0, (int)nrow, g.slot_records, c->l2g.as<unsigned>(),
+                           c->best.as<float2>(), g, dslot);
+    }
+    std::vector<unsigned char> back(g.slot_bytes + guard);
+    HIPCHK(c, hipMemcpyAsync(back.data(), dslot, back.size(), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, hipGetLastError());
+    for (size_t i = g.slot_bytes; i < back.size(); ++i) if (back[i] != 0xff) return fail(c, L3D_ERR_INVALID, "shard_slot_write: the kernel wrote behind the slot");
+    memcpy(slot, back.data(), g.slot_bytes);
+    return L3D_OK;
+}
+
+// The collect step of l3d_shard_chain_enqueue for view k and one range over a gathered buffer of the caller's: every slot a kernel will read is validated
+// on the host, the outputs are filled with 0xff bytes, then the chain's launches run with its grid rules.
+int l3d_test_shard_collect(l3d_ctx* c, const l3d_chain_view* views, int n_views, int k, const unsigned char* gathered, const l3d_test_shard_geom* geom,
+                           const int32_t* rowA, const uint32_t* metaA, const float* depthsA, int n_A, const int32_t* rowcnt,
+                           l3d_test_shard_collect_path* sel, int32_t* row_start, uint32_t* cand_meta, float* cand_depths, int32_t* cursor, int32_t* seg_order)
+{
+    if (!c) return L3D_ERR_INVALID;
+    SlotPlan plan;
+    if (int rc = test_shard_geom(c, geom, plan, "shard_collect")) return rc;
+    const SlotGeom g = plan.geom;
+    if (!sel || !views || !gathered || n_views < 1 || n_views != geom->n_views || k < 0 || k >= n_views || !row_start || n_A < 0 || sel->cand_cap < 0 ||
+        (sel->cand_cap > 0 && (!cand_meta || !cand_depths)) || (n_A > 0 && (!metaA || !depthsA)))
+        return fail(c, L3D_ERR_INVALID, "shard_collect: bad argument");
+    const l3d_chain_view& v = views[k];
+    const int S = v.S_src, N = v.N, s0 = sel->s0, s1 = sel->s1;
+    if (S < 0 || S > geom->maxS || N < 1 || N > geom->maxN || v.n_tbm < 1 || v.n_tbm > N || !v.to_be_matched || !v.local2global || v.n_sources < 0 ||
+        (v.n_sources && (!v.source_cam || !v.source_index)) || (S > 0 && (!rowA || !rowcnt || !cursor || !seg_order)))
+        return fail(c, L3D_ERR_INVALID, "shard_collect: the view under test is not a verified view within the geometry");
+    if (s0 < 0 || s1 < s0 || s1 > S || s1 - s0 > g.seg_cap - 1) return fail(c, L3D_ERR_INVALID, "shard_collect: the range is outside [0, S] or longer than seg_cap - 1");
+    std::vector<char> is_tbm((size_t)N, 0), is_src((size_t)N, 0);
+    for (int j = 0; j < v.n_tbm; ++j) {
+        const int cam = v.to_be_matched[j];
+        if (cam < 0 || cam >= N || is_tbm[(size_t)cam]) return fail(c, L3D_ERR_INVALID, "shard_collect: to_be_matched out of range or repeated");
+        is_tbm[(size_t)cam] = 1;
+    }
+    for (int j = 0; j < k; ++j)
+        if (views[j].S_src < 0 || views[j].S_src > geom->maxS || views[j].N < 0 || views[j].N > geom->maxN || (views[j].N > 0 && !views[j].local2global))
+            return fail(c, L3D_ERR_INVALID, "shard_collect: an earlier view's sizes are outside the geometry");
+    long long reverse = 0;
+    std::vector<int> src_slot((size_t)v.n_sources, -1);
+    for (int q = 0; q < v.n_sources; ++q) {
+        const int cam = v.source_cam[q], si = v.source_index[q];
+        if (si < 0 || si >= k || cam < 0 || cam >= N || is_tbm[(size_t)cam] || is_src[(size_t)cam])
+            return fail(c, L3D_ERR_INVALID, "shard_collect: a source must be an earlier view, its camera a neighbour that is not to be matched, named once");
+        is_src[(size_t)cam] = 1;
+        if ((long long)si + g.ring < k) return fail(c, L3D_ERR_INVALID, "shard_collect: the ring block of source view " + std::to_string(si) + " was overwritten before view " + std::to_string(k));
+        const l3d_chain_view& w = views[si];
+        src_slot[(size_t)q] = chain_source_slot(views, v, q);
+        if (src_slot[(size_t)q] < 0) continue;                  // (no kernel reads behind the header of such a source's slots)
+        for (int r = 0; r < g.world; ++r) {
+            const unsigned char* slot = gathered + ((size_t)(si % g.ring) * g.world + r) * g.slot_bytes;
+            const SlotHeader* hd = reinterpret_cast<const SlotHeader*>(slot);
+            std::string bad = test_slot_header(*hd, g, 65536);
+            if (bad.empty() && !hd->overflow && hd->n_kept > 0) {
+                bad = hd->s1 > w.S_src ? std::string("a header whose range ends past its view's segments") : test_slot_body(slot, g, w);
+                const Match* rec = reinterpret_cast<const Match*>(slot + g.rec_off);
+                for (int i = 0; i < hd->n_kept && bad.empty(); ++i) reverse += rec[i].camID2 == v.view_id && (int)rec[i].segID2 >= s0 && (int)rec[i].segID2 < s1 ? 1 : 0;
+            }
+            if (!bad.empty()) return fail(c, L3D_ERR_INVALID, "shard_collect: source view " + std::to_string(si) + ", rank " + std::to_string(r) + ": " + bad);
+        }
+    }
+    const size_t nrow = (size_t)S * N;
+    long long stage1 = 0;
+    for (size_t row = 0; row < nrow; ++row) {
+        const bool tbm = is_tbm[row % (size_t)N] != 0;
+        if (rowcnt[row] < 0 || (!tbm && rowcnt[row] != 0)) return fail(c, L3D_ERR_INVALID, "shard_collect: a stage-1 count below 0, or above 0 for a camera that is not to be matched");
+        if (tbm && (rowA[row] < 0 || (long long)rowA[row] + rowcnt[row] > n_A)) return fail(c, L3D_ERR_INVALID, "shard_collect: a stage-1 row outside the stage-1 candidates");
+        if ((int)(row / (size_t)N) >= s0 && (int)(row / (size_t)N) < s1) stage1 += rowcnt[row];
+    }
+    if (stage1 + reverse > sel->cand_cap) return fail(c, L3D_ERR_INVALID, "shard_collect: cand_cap does not hold the range's " + std::to_string(stage1 + reverse) + " candidates");
+    sel->wps = sel->blocks_move = sel->R = 0;
+
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    (void)hipGetLastError();
+    const size_t cap = (size_t)sel->cand_cap, ccap = std::max<size_t>(cap, 1), gbytes = (size_t)g.ring * g.world * g.slot_bytes;
+    std::vector<int> tab;
+    tab.insert(tab.end(), v.to_be_matched, v.to_be_matched + v.n_tbm);
+    const size_t o_sc = tab.size();
+    if (v.n_sources) tab.insert(tab.end(), v.source_cam, v.source_cam + v.n_sources);
+    const size_t o_si = tab.size();
+    if (v.n_sources) tab.insert(tab.end(), v.source_index, v.source_index + v.n_sources);
+    const size_t o_ss = tab.size();
+    tab.insert(tab.end(), src_slot.begin(), src_slot.end());
+    HIPCHK(c, c->tables.reserve(tab.size() * 4 + 16));
+    HIPCHK(c, hipMemcpyAsync(c->tables.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, st));
+    const int* dt = c->tables.as<int>();
+    ChainLayout L;
+    L.maxS = S; L.maxN = N;
+    if (int rc = chain_reserve_candidates(c, L, ccap, 0)) return rc;
+    HIPCHK(c, c->ch_gathered.reserve(gbytes + 256));
+    HIPCHK(c, c->rowcnt.reserve(nrow * 4 + 16)); HIPCHK(c, c->ch_rowA.reserve(nrow * 4 + 16));
+    HIPCHK(c, c->ch_ringA_meta.reserve((size_t)std::max(n_A, 1) * 8)); HIPCHK(c, c->ch_ringA_depths.reserve((size_t)std::max(n_A, 1) * 16));
+    HIPCHK(c, c->row_start.reserve((nrow + 1) * 4)); HIPCHK(c, c->ch_cursor.reserve(nrow * 4 + 16)); HIPCHK(c, c->ch_segorder.reserve((size_t)S * 4 + 16));
+    HIPCHK(c, hipMemsetAsync(c->ch_gathered.p, 0xee, c->ch_gathered.cap, st));          // (behind the ring: headers that carry every overflow bit -- no records)
+    HIPCHK(c, hipMemcpyAsync(c->ch_gathered.p, gathered, gbytes, hipMemcpyHostToDevice, st));
+    if (nrow) {
+        HIPCHK(c, hipMemcpyAsync(c->rowcnt.p, rowcnt, nrow * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(c->ch_rowA.p, rowA, nrow * 4, hipMemcpyHostToDevice, st));
+    }
+    if (n_A) {
+        HIPCHK(c, hipMemcpyAsync(c->ch_ringA_meta.p, metaA, (size_t)n_A * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(c->ch_ringA_depths.p, depthsA, (size_t)n_A * 16, hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(c, hipMemsetAsync(c->row_start.p, 0xff, (nrow + 1) * 4, st));
+    HIPCHK(c, hipMemsetAsync(c->ch_cursor.p, 0xff, nrow * 4 + 16, st));
+    HIPCHK(c, hipMemsetAsync(c->ch_segorder.p, 0xff, (size_t)S * 4 + 16, st));
+    HIPCHK(c, hipMemsetAsync(c->cand_meta.p, 0xff, ccap * 8, st));
+    HIPCHK(c, hipMemsetAsync(c->cand_depths.p, 0xff, ccap * 16, st));
+
+    const unsigned char* G = c->ch_gathered.as<unsigned char>();
+    const int wps = slot_scan_workgroups(g, sel->slot_scan_grain);
+    if (v.n_sources) {
+        ProfScope p(c, "exist");
+        hipLaunchKernelGGL(k_exist_count_slots, dim3(wps, v.n_sources * g.world), dim3(256), 0, st, G, g, dt + o_si, dt + o_sc, dt + o_ss, v.view_id, N, s0, s1, c->rowcnt.as<int>());
+    }
+    { ProfScope p(c, "scan"); launch_scan_range(c->rowcnt.as<int>(), c->row_start.as<int>(), N, s0, s1, (int)nrow, c->ch_cursor.as<int>(), c->ch_segorder.as<int>(), st); }
+    const int blocks_move = ((s1 - s0) * v.n_tbm + 3) / 4;
+    {
+        ProfScope p(c, "cand_move");
+        const int blocks = blocks_move + wps * v.n_sources * g.world;
+        if (blocks > 0)
+            hipLaunchKernelGGL(k_place_slots, dim3(blocks), dim3(256), 0, st, blocks_move, wps, dt, v.n_tbm, c->ch_rowA.as<int>(), c->ch_ringA_meta.as<uint2>(), c->ch_ringA_depths.as<float4>(),
+                               G, g, dt + o_si, dt + o_sc, dt + o_ss, v.view_id, N, S, s0, s1, c->row_start.as<int>(), c->ch_cursor.as<int>(), c->cand_meta.as<uint2>(),
+                               c->cand_depths.as<float4>(), (int)cap);
+    }
+    if (v.n_sources && sel->sort_apart) {
+        ProfScope p(c, "exist");
+        launch_exist_sort_runs(dt + o_sc, v.n_sources, N, S, c->row_start.as<int>(), c->cand_meta.as<uint2>(), c->cand_depths.as<float4>(), (int)cap, st, s0, s1,
+                               c->vw_scratch.as<float>(), (long long)ccap + kVWSlack, c->cand_conf.as<unsigned>());
+    }
+    sel->wps = wps; sel->blocks_move = blocks_move;
+    HIPCHK(c, hipMemcpyAsync(row_start, c->row_start.p, (nrow + 1) * 4, hipMemcpyDeviceToHost, st));
+    if (nrow) HIPCHK(c, hipMemcpyAsync(cursor, c->ch_cursor.p, nrow * 4, hipMemcpyDeviceToHost, st));
+    if (S) HIPCHK(c, hipMemcpyAsync(seg_order, c->ch_segorder.p, (size_t)S * 4, hipMemcpyDeviceToHost, st));
+    if (cap) {
+        HIPCHK(c, hipMemcpyAsync(cand_meta, c->cand_meta.p, cap * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(cand_depths, c->cand_depths.p, cap * 16, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, hipGetLastError());
+    sel->R = row_start[nrow];
+    return L3D_OK;
+}
+
+// The consumers of the gathered blocks over all views' slots of the caller's: headers and ranges validated on the host (nothing else of a slot is an
+// index to these kernels), every output filled with 0xff bytes, then the launches of shared_verdict, shard_pack, shard_products_local and retire_to.
+int l3d_test_shard_pack(l3d_ctx* c, const unsigned char* gathered, const l3d_test_shard_geom* geom, l3d_test_shard_pack_io* io)
+{
+    if (!c) return L3D_ERR_INVALID;
+    SlotPlan plan;
+    if (int rc = test_shard_geom(c, geom, plan, "shard_pack")) return rc;
+    const SlotGeom g = plan.geom;
+    const int nv = geom ? geom->n_views : 0, W = g.world;
+    if (!gathered || !io || nv < 1 || !io->verified || !io->best_off || !io->view_sn || io->n_batches < 0 || (io->n_batches > 0 && !io->batches) || io->arena_cap < 0 ||
+        io->arena_cap > (1 << 26) || io->pack_cap < 0 || io->pack_cap > (1 << 26) || io->best_cap < 0 || io->best_cap > (1 << 26) || io->rt_cap < 0 || io->rt_cap > (1 << 28) ||
+        !io->stage || !io->pack_hdr || !io->totals || !io->check || !io->base_dev || !io->hdr_all || !io->overflow ||
+        (io->pack_cap > 0 && !io->pa_arena) || (io->arena_cap > 0 && !io->rt_arena) || (io->best_cap > 0 && (!io->pa_best || !io->pa_bestpos || !io->rt_best || !io->rt_bestpos)))
+        return fail(c, L3D_ERR_INVALID, "shard_pack: bad argument");
+    const bool tables = io->retire_tables != 0;
+    if (tables && (!g.rt_off || !g.cam_off || !io->rt_off || (io->arena_cap > 0 && !io->qt_arena) || (io->rt_cap > 0 && !io->rt_all)))
+        return fail(c, L3D_ERR_INVALID, "shard_pack: retire tables need a geometry with side words and run tables, rt_off, qt_arena and rt_all");
+    const size_t nvs = (size_t)nv, block = (size_t)W * g.slot_bytes;
+    long long pack_total = 0, all_records = 0;
+    std::vector<unsigned long long> kept_base(nvs, 0);
+    std::vector<int2> want_tot(nvs);
+    for (int k = 0; k < nv; ++k) {
+        const int S = io->view_sn[2 * k], N = io->view_sn[2 * k + 1];
+        if (io->verified[k] > 1 || (io->keep && io->keep[k] > 1)) return fail(c, L3D_ERR_INVALID, "shard_pack: a flag that is not 0 or 1");
+        if (S < 0 || S > geom->maxS || N < 1 || N > geom->maxN) return fail(c, L3D_ERR_INVALID, "shard_pack: a view larger than the geometry's largest");
+        if (io->best_off[k] < 0 || io->best_off[k] + S > io->best_cap) return fail(c, L3D_ERR_INVALID, "shard_pack: a view's best pairs end past best_cap");
+        if (tables && io->verified[k] && (!io->keep || io->keep[k]) && (io->rt_off[k] < 0 || io->rt_off[k] + ((long long)N + 1) * S > io->rt_cap))
+            return fail(c, L3D_ERR_INVALID, "shard_pack: a view's run table ends past rt_cap");
+        kept_base[(size_t)k] = (unsigned long long)pack_total;
+        long long n = 0, R = 0;
+        if (io->verified[k])
+            for (int r = 0; r < W; ++r) {
+                const SlotHeader* hd = reinterpret_cast<const SlotHeader*>(gathered + (size_t)k * block + (size_t)r * g.slot_bytes);
+                const std::string bad = test_slot_header(*hd, g, S);
+                if (!bad.empty()) return fail(c, L3D_ERR_INVALID, "shard_pack: view " + std::to_string(k) + ", rank " + std::to_string(r) + ": " + bad);
+                n += hd->overflow ? 0 : hd->n_kept; R += hd->R;
+            }
+        want_tot[(size_t)k] = make_int2((int)n, (int)std::min(R, 0x7fffffffll));
+        pack_total += n; all_records += n;
+    }
+    if (pack_total > io->pack_cap) return fail(c, L3D_ERR_INVALID, "shard_pack: the verified views keep " + std::to_string(pack_total) + " records: more than pack_cap");
+    {
+        int next = 0, at_before = 0;
+        for (int b = 0; b < io->n_batches; ++b) {
+            const int first = io->batches[3 * b], count = io->batches[3 * b + 1], at = io->batches[3 * b + 2];
+            if (first != next || count < 1 || first + count > nv || at < at_before || at > nv) return fail(c, L3D_ERR_INVALID, "shard_pack: the batches are not contiguous and ascending from view 0");
+            if (first + count > at) return fail(c, L3D_ERR_INVALID, "shard_pack: batch " + std::to_string(b) + " retires a view that is not exchanged yet");
+            if ((long long)first + g.ring < at) return fail(c, L3D_ERR_INVALID, "shard_pack: batch " + std::to_string(b) + " reads a ring block that is already overwritten");
+            next = first + count; at_before = at;
+        }
+    }
+
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    (void)hipGetLastError();
+    // (room behind every arena for all the records there are: a record filed at a wrong offset still lands in the buffer, and shows)
+    const size_t slack = (size_t)all_records + 64, pcap = (size_t)io->pack_cap, acap = (size_t)io->arena_cap, bcap = (size_t)io->best_cap, rcap = (size_t)io->rt_cap;
+    // small tables: verified | keep | best_off | kept_base | rt_off | view_sn | totals x 2 | check x 2 | pack headers | base_dev | hdr_all | overflow
+    const size_t o_ver = 0, o_keep = align256(nvs), o_bo = o_keep + align256(nvs), o_kb = o_bo + align256(nvs * 8), o_ro = o_kb + align256(nvs * 8), o_sn = o_ro + align256(nvs * 8),
+                 o_tot = o_sn + align256(nvs * 8), o_chk = o_tot + align256(2 * nvs * 8), o_ph = o_chk + 256, o_base = o_ph + align256(nvs * 32), o_hdr = o_base + align256((nvs + 2) * 8),
+                 o_ovf = o_hdr + align256(nvs * W * 32), small = o_ovf + 256;
+    HIPCHK(c, c->g0.reserve((size_t)nv * block + 256)); HIPCHK(c, c->g1.reserve((size_t)g.ring * block + 256)); HIPCHK(c, c->g2.reserve((nvs + 1) * plan.stage_bytes + 256));
+    HIPCHK(c, c->g3.reserve(small)); HIPCHK(c, c->g4.reserve((pcap + acap + 2 * slack) * sizeof(Match))); HIPCHK(c, c->g5.reserve(2 * (bcap + 64) * 12));
+    HIPCHK(c, c->g6.reserve((acap + slack) * 4)); HIPCHK(c, c->g7.reserve((rcap + 64) * 4));
+    unsigned char* sm = c->g3.as<unsigned char>();
+    unsigned char* full = c->g0.as<unsigned char>();
+    unsigned char* ring = c->g1.as<unsigned char>();
+    unsigned char* stage = c->g2.as<unsigned char>();
+    Match* pa_arena = c->g4.as<Match>();
+    Match* rt_arena = pa_arena + pcap + slack;
+    float2* pa_best = c->g5.as<float2>();
+    float2* rt_best = pa_best + bcap + 64;
+    int* pa_bpos = reinterpret_cast<int*>(rt_best + bcap + 64);
+    int* rt_bpos = pa_bpos + bcap + 64;
+    HIPCHK(c, hipMemcpyAsync(full, gathered, (size_t)nv * block, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemsetAsync(ring, 0xff, (size_t)g.ring * block, st));
+    HIPCHK(c, hipMemsetAsync(stage, 0xff, nvs * plan.stage_bytes, st));
+    HIPCHK(c, hipMemsetAsync(sm, 0xff, small, st));
+    HIPCHK(c, hipMemsetAsync(c->g4.p, 0xff, (pcap + acap + 2 * slack) * sizeof(Match), st));
+    HIPCHK(c, hipMemsetAsync(c->g5.p, 0xff, 2 * (bcap + 64) * 8, st));
+    HIPCHK(c, hipMemsetAsync(pa_bpos, 0x7f, 2 * (bcap + 64) * 4, st));
+    HIPCHK(c, hipMemsetAsync(c->g6.p, 0xff, (acap + slack) * 4, st));
+    HIPCHK(c, hipMemsetAsync(c->g7.p, 0xff, (rcap + 64) * 4, st));
+    HIPCHK(c, hipMemcpyAsync(sm + o_ver, io->verified, nvs, hipMemcpyHostToDevice, st));
+    if (io->keep) HIPCHK(c, hipMemcpyAsync(sm + o_keep, io->keep, nvs, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(sm + o_bo, io->best_off, nvs * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(sm + o_kb, kept_base.data(), nvs * 8, hipMemcpyHostToDevice, st));
+    if (tables) HIPCHK(c, hipMemcpyAsync(sm + o_ro, io->rt_off, nvs * 8, hipMemcpyHostToDevice, st));
+    else HIPCHK(c, hipMemsetAsync(sm + o_ro, 0, nvs * 8, st));
+    HIPCHK(c, hipMemcpyAsync(sm + o_sn, io->view_sn, nvs * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemsetAsync(sm + o_chk, 0, 256, st));                                   // (both kernels' answers are ORs and maxima into zeroed words)
+    HIPCHK(c, hipMemsetAsync(sm + o_base, 0, (nvs + 2) * 8, st));                        // (the run starts the offsets at zero: setup_ring_tables)
+    HIPCHK(c, hipMemsetAsync(sm + o_ovf, 0, 4, st));
+    const unsigned char* ver = sm + o_ver;
+    int2* tot = reinterpret_cast<int2*>(sm + o_tot);
+    int* chk = reinterpret_cast<int*>(sm + o_chk);
+    SlotHeader* hdr_all = reinterpret_cast<SlotHeader*>(sm + o_hdr);
+
+    // ---- the headers in front of the slots: totals, verdict; the hand-over of every verified view; all views into one arena
+    hipLaunchKernelGGL(k_shard_totals, dim3((nv + 255) / 256), dim3(256), 0, st, full, g.slot_bytes, g, ver, nv, tot);
+    hipLaunchKernelGGL(k_check_slots, dim3(8), dim3(256), 0, st, full, g.slot_bytes, g, ver, nv, chk);
+    std::vector<int2> got_tot(nvs);
+    HIPCHK(c, hipMemcpyAsync(got_tot.data(), tot, nvs * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, hipGetLastError());
+    // (the products lay the arena out from these totals: a kernel that counts differently than the host did must not place a record)
+    for (int k = 0; k < nv; ++k)
+        if (got_tot[(size_t)k].x != want_tot[(size_t)k].x) return fail(c, L3D_ERR_INVALID, "shard_pack: k_shard_totals counts " + std::to_string(got_tot[(size_t)k].x) + " kept records in view " + std::to_string(k) + ", the headers add up to " + std::to_string(want_tot[(size_t)k].x));
+    for (int k = 0; k < nv; ++k)
+        if (io->verified[k])
+            hipLaunchKernelGGL(k_pack_view, dim3(8, W), dim3(256), 0, st, full + (size_t)k * block, g, stage + (size_t)k * plan.stage_bytes, reinterpret_cast<PackHeader*>(sm + o_ph) + k);
+    hipLaunchKernelGGL(k_shard_pack_all, dim3(8, W, nv), dim3(256), 0, st, full, g, ver, reinterpret_cast<const unsigned long long*>(sm + o_kb), reinterpret_cast<const long long*>(sm + o_bo),
+                       pa_arena, pa_best, pa_bpos);
+    // ---- the ring: blocks arrive as the exchanges bring them, batches leave as listed
+    int exchanged = 0;
+    for (int b = 0; b < io->n_batches; ++b) {
+        const int first = io->batches[3 * b], count = io->batches[3 * b + 1], at = io->batches[3 * b + 2];
+        for (; exchanged < at; ++exchanged) {
+            unsigned char* dst = ring + (size_t)(exchanged % g.ring) * block;
+            if (io->verified[exchanged]) HIPCHK(c, hipMemcpyAsync(dst, full + (size_t)exchanged * block, block, hipMemcpyDeviceToDevice, st));
+            else HIPCHK(c, hipMemsetAsync(dst, 0, block, st));
+        }
+        ProfScope p(c, "retire", st);
+        hipLaunchKernelGGL(k_shard_retire, dim3(8, W, count), dim3(256), 0, st, ring, g, ver, io->keep ? sm + o_keep : nullptr, first, count, reinterpret_cast<long long*>(sm + o_base),
+                           (long long)io->arena_cap, reinterpret_cast<const long long*>(sm + o_bo), rt_arena, rt_best, rt_bpos, hdr_all, reinterpret_cast<int*>(sm + o_ovf),
+                           tables ? c->g6.as<unsigned>() : nullptr, tables ? c->g7.as<int>() : nullptr, reinterpret_cast<const long long*>(sm + o_ro), reinterpret_cast<const int2*>(sm + o_sn));
+    }
+    // ---- the compact header table the retire run left: totals and verdict again
+    hipLaunchKernelGGL(k_shard_totals, dim3((nv + 255) / 256), dim3(256), 0, st, reinterpret_cast<const unsigned char*>(hdr_all), sizeof(SlotHeader), g, ver, nv, tot + nvs);
+    hipLaunchKernelGGL(k_check_slots, dim3(8), dim3(256), 0, st, reinterpret_cast<const unsigned char*>(hdr_all), sizeof(SlotHeader), g, ver, nv, chk + 3);
+
+    HIPCHK(c, hipMemcpyAsync(io->stage, stage, nvs * plan.stage_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(io->pack_hdr, sm + o_ph, nvs * 32, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(io->totals, tot, 2 * nvs * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(io->check, chk, 24, hipMemcpyDeviceToHost, st));
+    if (pcap) HIPCHK(c, hipMemcpyAsync(io->pa_arena, pa_arena, pcap * sizeof(Match), hipMemcpyDeviceToHost, st));
+    if (acap) HIPCHK(c, hipMemcpyAsync(io->rt_arena, rt_arena, acap * sizeof(Match), hipMemcpyDeviceToHost, st));
+    if (bcap) {
+        HIPCHK(c, hipMemcpyAsync(io->pa_best, pa_best, bcap * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(io->rt_best, rt_best, bcap * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(io->pa_bestpos, pa_bpos, bcap * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(io->rt_bestpos, rt_bpos, bcap * 4, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(c, hipMemcpyAsync(io->base_dev, sm + o_base, (nvs + 2) * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(io->hdr_all, hdr_all, nvs * W * 32, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(io->overflow, sm + o_ovf, 4, hipMemcpyDeviceToHost, st));
+    if (acap && io->qt_arena) HIPCHK(c, hipMemcpyAsync(io->qt_arena, c->g6.p, acap * 4, hipMemcpyDeviceToHost, st));
+    if (rcap && io->rt_all) HIPCHK(c, hipMemcpyAsync(io->rt_all, c->g7.p, rcap * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, hipGetLastError());
+    // the room behind the arenas must be as it was
+    {
+        std::vector<unsigned char> tail(slack * sizeof(Match));
+        for (const Match* a : { pa_arena + pcap, rt_arena + acap }) {
+            HIPCHK(c, hipMemcpy(tail.data(), a, tail.size(), hipMemcpyDeviceToHost));
+            for (unsigned char x : tail) if (x != 0xff) return fail(c, L3D_ERR_INVALID, "shard_pack: a kernel wrote behind its arena");
+        }
+    }
+    return L3D_OK;
 }
 
 }  // extern "C"

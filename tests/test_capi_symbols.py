@@ -52,7 +52,11 @@ def test_struct_layouts(tmp_path):
                    '  printf("%zu %zu %zu %zu %zu\\n", sizeof(l3d_test_collect_path), offsetof(l3d_test_collect_path, avg_kept), offsetof(l3d_test_collect_path, overflowed),\n'
                    '  offsetof(l3d_test_collect_path, kernels), offsetof(l3d_test_collect_path, R));\n'
                    '  printf("%zu %zu %zu %zu %zu %zu\\n", sizeof(l3d_test_affinity_part), offsetof(l3d_test_affinity_part, pos_base), offsetof(l3d_test_affinity_part, loc2glob),\n'
-                   '  offsetof(l3d_test_affinity_part, assume_symmetric), offsetof(l3d_test_affinity_part, coll_sym), offsetof(l3d_test_affinity_part, n_passed)); return 0; }\n')
+                   '  offsetof(l3d_test_affinity_part, assume_symmetric), offsetof(l3d_test_affinity_part, coll_sym), offsetof(l3d_test_affinity_part, n_passed));\n'
+                   '  printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(l3d_test_shard_geom), offsetof(l3d_test_shard_geom, ring), sizeof(l3d_test_shard_collect_path),\n'
+                   '  offsetof(l3d_test_shard_collect_path, slot_scan_grain), offsetof(l3d_test_shard_collect_path, R), sizeof(l3d_test_shard_pack_io),\n'
+                   '  offsetof(l3d_test_shard_pack_io, n_batches), offsetof(l3d_test_shard_pack_io, arena_cap), offsetof(l3d_test_shard_pack_io, stage),\n'
+                   '  offsetof(l3d_test_shard_pack_io, rt_all)); return 0; }\n')
     exe = str(tmp_path / "layout")
     subprocess.check_call(["gcc", "-std=c99", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe])
     got = [int(x) for x in subprocess.run([exe], capture_output=True, text=True).stdout.split()]
@@ -71,7 +75,18 @@ def test_struct_layouts(tmp_path):
                    ctypes.sizeof(capi.CollectPath), capi.CollectPath.avg_kept.offset, capi.CollectPath.overflowed.offset, capi.CollectPath.kernels.offset,
                    capi.CollectPath.R.offset,
                    ctypes.sizeof(capi.AffinityPart), capi.AffinityPart.pos_base.offset, capi.AffinityPart.loc2glob.offset, capi.AffinityPart.assume_symmetric.offset,
-                   capi.AffinityPart.coll_sym.offset, capi.AffinityPart.n_passed.offset], got
+                   capi.AffinityPart.coll_sym.offset, capi.AffinityPart.n_passed.offset,
+                   ctypes.sizeof(capi.ShardGeom), capi.ShardGeom.ring.offset, ctypes.sizeof(capi.ShardCollectPath), capi.ShardCollectPath.slot_scan_grain.offset,
+                   capi.ShardCollectPath.R.offset, ctypes.sizeof(capi.ShardPackIO), capi.ShardPackIO.n_batches.offset, capi.ShardPackIO.arena_cap.offset,
+                   capi.ShardPackIO.stage.offset, capi.ShardPackIO.rt_all.offset], got
+
+
+def test_the_shard_slot_hooks_are_exported():
+    """the hooks tests/test_gpu_shard_slots.py drives, by name: a header that lost one would pass the test above"""
+    from line3d_amd import capi
+    lib = capi.load_library()
+    for name in ("l3d_test_shard_slot_write", "l3d_test_shard_collect", "l3d_test_shard_pack"):
+        assert name in _declared() and hasattr(lib, name), name
 
 
 def test_no_gpu_fails_loudly():
